@@ -73,7 +73,11 @@ def main():
                     help="weak: the workload's reads PER GPU (default, the driver's contract); strong: that many reads in TOTAL, split over the GPUs")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + PGRC_BENCH_FORCE_DEVICE=0 rehearses the N>1 path on a one-GPU box (collectives staged through the host)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's results) as DIR/<name>.npy; see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -190,6 +194,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs)
     _, _, _, hist, matched = ctx.get_results(arrays=False)
     ctr = ctx.counters()
     cp = copmem_params(seed_len, G)
@@ -352,6 +358,29 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_READS = 1 << 20     # at most this many reads' results are dumped: 24 MB of .npy files
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(ctx, out_dir):
+    """What the timed path hands its caller after the last step (pgrc_match_get_results: per read its position, RC flag and
+    mismatch count, the histogram of the mismatch counts, the number of matched reads), written as .npy for an output-for-output
+    comparison of two builds.  Above DUMP_SAMPLE_READS reads, a fixed seeded sample of the reads (the same for every run of a
+    workload; `read_index` names them).  Positions go to float64 (exact below 2^53; the unmatched value 2^64 - 1 rounds to 2^64)."""
+    import numpy as np
+    pos, rc, mism, hist, matched = ctx.get_results()
+    n = pos.size
+    if n > DUMP_SAMPLE_READS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_READS, replace=False))
+    else:
+        idx = np.arange(n)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"read_index": idx.astype(np.float64), "pos": pos[idx].astype(np.float64), "rc": rc[idx].astype(np.float32),
+              "mism": mism[idx].astype(np.float32), "hist": hist.astype(np.float64), "matched": np.array([matched], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def boundary_leg(n, L, G, kmax):

@@ -193,7 +193,7 @@ int pgrc_or_index_build(const char *pg, uint64_t pg_len, uint32_t seed_len, pgrc
     }
     /* now cumm[h+1] = start(h); shift down so cumm[h] = start(h), keeping a fill cursor */
     uint32_t *cursor = (uint32_t *)malloc(((size_t)hs + 1) * sizeof(uint32_t));
-    uint32_t *positions = (uint32_t *)malloc((size_t)(run + 2) * sizeof(uint32_t));
+    uint64_t *positions = (uint64_t *)malloc((size_t)(run + 2) * sizeof(uint64_t));
     if (!cursor || !positions) { free(cumm); free(cursor); free(positions); return 3; }
     for (uint64_t h = 0; h <= (uint64_t)hs; h++) cursor[h] = cumm[h + 1];
     for (uint64_t h = 0; h <= (uint64_t)hs; h++) cumm[h] = cursor[h];
@@ -202,7 +202,7 @@ int pgrc_or_index_build(const char *pg, uint64_t pg_len, uint32_t seed_len, pgrc
     for (uint64_t i = 0; i < npos; i++) {
         uint64_t p = i * (uint64_t)k1;
         uint32_t h = pgrc_or_copmem_hash(K, pg + p) & mask;
-        if (cursor[h] < cumm[h + 1]) positions[cursor[h]++] = (uint32_t)p;
+        if (cursor[h] < cumm[h + 1]) positions[cursor[h]++] = p;
     }
     free(cursor);
     out->cumm = cumm;

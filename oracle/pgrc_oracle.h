@@ -58,7 +58,7 @@ typedef struct {
     pgrc_or_copmem_params p;
     uint64_t pg_len;
     uint32_t *cumm;
-    uint32_t *positions;
+    uint64_t *positions;     /* 64-bit: texts of 4 Gi symbols and more (the reference's u64 branch, CopMEMMatcher.cpp:579-586) */
     uint64_t count;
 } pgrc_or_index;
 

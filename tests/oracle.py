@@ -22,7 +22,7 @@ class CopmemParams(C.Structure):
 
 class Index(C.Structure):
     _fields_ = [("p", CopmemParams), ("pg_len", C.c_uint64), ("cumm", C.POINTER(C.c_uint32)),
-                ("positions", C.POINTER(C.c_uint32)), ("count", C.c_uint64)]
+                ("positions", C.POINTER(C.c_uint64)), ("count", C.c_uint64)]
 
 
 class Result(C.Structure):
