@@ -1,0 +1,185 @@
+"""Host-side mirror of the reference decoder's read rebuild (pgrc/pgrc-decoder.cpp) over include/pgrc_decode.h: the reads
+are rebuilt from the pseudogenomes and their reads lists on the MI355X.  No compute here.
+
+The class's methods are named after the reference's three writers; each returns the rows of every output file as
+uint8 arrays of shape (n, L+1), a row being L symbols and '\\n'."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import PgrcMatchError, lib
+
+_P = C.c_void_p
+
+PGRC_DECODE_SE, PGRC_DECODE_PE, PGRC_DECODE_ORD = 0, 1, 2
+
+
+class DecodeList(C.Structure):      # pgrc_decode_list
+    _fields_ = [("struct_size", C.c_uint32), ("text_base", C.c_uint64), ("n_entries", C.c_uint64), ("off", _P),
+                ("off_width", C.c_uint32), ("pos", _P), ("rev_comp", _P), ("mis_cnt", _P), ("mis_sym", _P),
+                ("mis_off", _P), ("mis_off_width", C.c_uint32), ("mis_off_rev_coded", C.c_int32),
+                ("mis_sym_form", C.c_int32), ("bases_order", C.c_char_p)]
+
+
+class DecodeOrder(C.Structure):     # pgrc_decode_order
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("n_total", C.c_uint64), ("rl_idx_order", _P),
+                ("org_idx_to_pos", _P), ("paired", C.c_int32), ("rev_compl_pair_file", C.c_int32)]
+
+
+class DecodeTiming(C.Structure):    # pgrc_decode_timing
+    _fields_ = [("ms_text", C.c_float), ("ms_lists_device", C.c_float), ("ms_order_device", C.c_float),
+                ("ms_rows_device", C.c_float), ("ms_rows", C.c_float), ("rows_bytes", C.c_uint64)]
+
+
+# include/pgrc_decode.h (kept apart from _lib._PROTOS, which mirrors pgrc_match.h / pgrc_mem.h / pgrc_reads.h)
+DECODE_PROTOS = [
+    ("pgrc_decode_create", C.c_int, [C.c_uint32, C.c_int32, C.POINTER(_P)]),
+    ("pgrc_decode_destroy", None, [_P]),
+    ("pgrc_decode_last_error", C.c_char_p, [_P]),
+    ("pgrc_decode_set_text", C.c_int, [_P, _P, C.c_uint64]),
+    ("pgrc_decode_add_list", C.c_int, [_P, C.POINTER(DecodeList)]),
+    ("pgrc_decode_set_order", C.c_int, [_P, C.POINTER(DecodeOrder)]),
+    ("pgrc_decode_row_count", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("pgrc_decode_rows", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P]),
+    ("pgrc_decode_rows_device", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P]),
+    ("pgrc_decode_get_timing", C.c_int, [_P, C.POINTER(DecodeTiming)]),
+]
+for _name, _res, _args in DECODE_PROTOS:
+    _fn = getattr(lib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+
+
+def _arr(a, dtype):
+    return None if a is None else np.ascontiguousarray(a, dtype=dtype)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(_P)
+
+
+class PgRCDecoder:
+    """The reads of a decoded archive, rebuilt on the device: the joined text HQ | LQ | N, the three reads lists, then
+    one of the three writers."""
+
+    def __init__(self, read_length: int, device: int = -1):
+        self._h = _P()
+        rc = lib.pgrc_decode_create(int(read_length), int(device), C.byref(self._h))
+        if rc:
+            raise PgrcMatchError(rc, (lib.pgrc_decode_last_error(None) or b"").decode())
+        self.readLength = int(read_length)
+
+    def _ck(self, rc: int) -> None:
+        if rc:
+            raise PgrcMatchError(rc, (lib.pgrc_decode_last_error(self._h) or b"").decode())
+
+    def set_text(self, joined) -> None:
+        """the joined pseudogenome text (bytes or uint8 array); copied to the device"""
+        t = np.frombuffer(joined, dtype=np.uint8) if isinstance(joined, (bytes, bytearray)) else _arr(joined, np.uint8)
+        self._ck(lib.pgrc_decode_set_text(self._h, _ptr(t), t.size))
+
+    def add_list(self, n_entries: int, text_base: int = 0, off=None, pos=None, rev_comp=None, mis_cnt=None, mis_sym=None,
+                 mis_off=None, mis_off_rev_coded: bool = True, mis_sym_form: int = 0, bases_order=None) -> None:
+        """one reads list (HQ, LQ, N in that order).  off: offset deltas as uint8 or uint16 (the width follows the dtype);
+        pos: absolute positions in the list's text instead; mis_off: uint8 or uint16 offsets (rev-coded by default)."""
+        a = DecodeList()
+        a.struct_size = C.sizeof(DecodeList)
+        a.text_base = int(text_base)
+        a.n_entries = int(n_entries)
+        keep = []
+        if off is not None:
+            off = np.ascontiguousarray(off)
+            assert off.dtype in (np.uint8, np.uint16) and off.size == n_entries
+            a.off, a.off_width = _ptr(off), off.dtype.itemsize
+            keep.append(off)
+        if pos is not None:
+            pos = _arr(pos, np.uint64)
+            a.pos = _ptr(pos)
+            keep.append(pos)
+        if rev_comp is not None:
+            rev_comp = _arr(rev_comp, np.uint8)
+            a.rev_comp = _ptr(rev_comp)
+            keep.append(rev_comp)
+        if mis_cnt is not None:
+            mis_cnt = _arr(mis_cnt, np.uint8)
+            mis_sym = _arr(mis_sym, np.uint8)
+            mis_off = np.ascontiguousarray(mis_off)
+            assert mis_off.dtype in (np.uint8, np.uint16)
+            a.mis_cnt, a.mis_sym, a.mis_off = _ptr(mis_cnt), _ptr(mis_sym), _ptr(mis_off)
+            a.mis_off_width = mis_off.dtype.itemsize
+            keep += [mis_cnt, mis_sym, mis_off]
+        a.mis_off_rev_coded = int(bool(mis_off_rev_coded))
+        a.mis_sym_form = int(mis_sym_form)
+        a.bases_order = None if bases_order is None else (bases_order.encode() if isinstance(bases_order, str) else bytes(bases_order))
+        self._ck(lib.pgrc_decode_add_list(self._h, C.byref(a)))
+
+    def set_order(self, mode: int, n_total: int = 0, rl_idx_order=None, org_idx_to_pos=None, paired: bool = False,
+                  rev_compl_pair_file: bool = False) -> None:
+        o = DecodeOrder()
+        o.struct_size = C.sizeof(DecodeOrder)
+        o.mode = int(mode)
+        o.n_total = int(n_total)
+        ro = _arr(rl_idx_order, np.uint32)
+        op = _arr(org_idx_to_pos, np.uint64)
+        o.rl_idx_order, o.org_idx_to_pos = _ptr(ro), _ptr(op)
+        o.paired = int(bool(paired))
+        o.rev_compl_pair_file = int(bool(rev_compl_pair_file))
+        self._ck(lib.pgrc_decode_set_order(self._h, C.byref(o)))
+
+    def row_count(self, file: int = 0) -> int:
+        n = C.c_uint64(0)
+        self._ck(lib.pgrc_decode_row_count(self._h, int(file), C.byref(n)))
+        return n.value
+
+    def rows(self, file: int = 0, first: int = 0, n: int | None = None, out=None) -> np.ndarray:
+        """rows [first, first+n) of one output file of the current order, (n, L+1) uint8 (into `out` if given: any
+        C-contiguous uint8 buffer of n*(L+1) bytes, e.g. a pinned torch tensor's numpy view)"""
+        if n is None:
+            n = self.row_count(file) - first
+        L1 = self.readLength + 1
+        if out is None:
+            out = np.empty((n, L1), dtype=np.uint8)
+        assert out.flags.c_contiguous and out.nbytes == n * L1
+        self._ck(lib.pgrc_decode_rows(self._h, int(file), int(first), int(n), out.ctypes.data_as(_P)))
+        return out.reshape(n, L1)
+
+    def rows_device(self, file: int, first: int, n: int, dev_ptr: int) -> None:
+        """rows into device memory (16-byte aligned), on the context's stream"""
+        self._ck(lib.pgrc_decode_rows_device(self._h, int(file), int(first), int(n), _P(dev_ptr)))
+
+    def timing(self) -> dict:
+        t = DecodeTiming()
+        self._ck(lib.pgrc_decode_get_timing(self._h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_}
+
+    # ---- the reference's writers (pgrc/pgrc-decoder.cpp)
+    def writeAllReadsInSEMode(self) -> np.ndarray:
+        """:137-239 -- every list in list order"""
+        self.set_order(PGRC_DECODE_SE)
+        return self.rows(0)
+
+    def writeAllReadsInPEMode(self, rlIdxOrder, revComplPairFile: bool = False):
+        """:241-383 -- file p holds rows i = p (mod 2) of rlIdxOrder; -> (file 1 rows, file 2 rows)"""
+        ro = np.ascontiguousarray(rlIdxOrder, dtype=np.uint32)
+        self.set_order(PGRC_DECODE_PE, ro.size, rl_idx_order=ro, rev_compl_pair_file=revComplPairFile)
+        return self.rows(0), self.rows(1)
+
+    def writeAllReadsInORDMode(self, orgIdx2PgPos, singleReadsMode: bool = True, revComplPairFile: bool = False):
+        """:385-527 -- one row per original index; -> (rows,) or (file 1 rows, file 2 rows)"""
+        op = np.ascontiguousarray(orgIdx2PgPos, dtype=np.uint64)
+        self.set_order(PGRC_DECODE_ORD, op.size, org_idx_to_pos=op, paired=not singleReadsMode,
+                       rev_compl_pair_file=revComplPairFile)
+        return tuple(self.rows(p) for p in range(1 if singleReadsMode else 2))
+
+    def close(self) -> None:
+        if self._h:
+            lib.pgrc_decode_destroy(self._h)
+            self._h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
