@@ -106,6 +106,51 @@ typedef struct {
 } pgrc_decode_timing;
 int pgrc_decode_get_timing(pgrc_decode_ctx *ctx, pgrc_decode_timing *out);
 
+/* ---- The matched pseudogenomes (the inverse of row f2, SimplePgMatcher::restoreMatchedPgs, SimplePgMatcher.cpp:259-351).
+ * The encoder's markAndRemoveExactMatches replaced every matched stretch of each pseudogenome by one '%' and wrote, per
+ * mark, a source offset into the ORIGINAL HQ text (4 bytes little-endian when org_hq_len <= UINT32_MAX, else 8) and a
+ * length (byte-frugal: 7 bits per byte, low group first, high bit = more bytes; the stream starts with minMatchLength
+ * and every mark's value is its length minus it).  A mark's text is the reverse complement (complementsLut) of
+ * src[off, off+len) -- the plain substring when rev_compl is 0.  HQ restores from itself (a mark may copy what an
+ * earlier mark produced), LQ and N from the restored HQ. */
+typedef struct {
+    uint32_t struct_size;           /* sizeof(pgrc_decode_mapped) */
+    const char *mapped;             /* comboPgMapped: the mapped HQ, LQ and N one after the other */
+    uint64_t mapped_len[3];         /* hqPgMappedLen, lqPgMappedLen, nPgMappedLen (0 with empty streams: no such part) */
+    uint64_t org_hq_len;            /* orgHqPgLen: the restored HQ length; also decides the offset width of all parts */
+    const uint8_t *map_off[3];      /* per part: the offsets stream */
+    uint64_t map_off_bytes[3];
+    const uint8_t *map_len[3];      /* per part: the byte-frugal lengths stream (empty: no marks, minMatchLength 0) */
+    uint64_t map_len_bytes[3];
+    int32_t rev_compl;              /* revComplMatching: 1 in every call of the reference's decoder */
+} pgrc_decode_mapped;
+/* Restores the three parts on the device and installs the joined restored text HQ | LQ | N, as pgrc_decode_set_text
+ * would with that text (the lists and the order are dropped).  PGRC_E_PARAM, with no text installed afterwards, when the
+ * marks and the stream values disagree in number, a byte-frugal value is longer than 10 bytes or runs past its stream's
+ * end, an offsets stream is not marks x width bytes, a source range reaches past the HQ end, an HQ mark's source reaches
+ * its own output position, or the restored HQ length differs from org_hq_len. */
+int pgrc_decode_set_mapped_text(pgrc_decode_ctx *ctx, const pgrc_decode_mapped *m);
+/* the restored HQ, LQ and N lengths (the lists' text_base: 0, lens[0], lens[0] + lens[1]); PGRC_E_STATE unless the text
+ * came from pgrc_decode_set_mapped_text */
+int pgrc_decode_text_lengths(pgrc_decode_ctx *ctx, uint64_t lens[3]);
+/* bytes [first, first+n) of the installed joined text into out (pinned memory directly, other memory in chunks through
+ * the context's staging buffers) */
+int pgrc_decode_get_text(pgrc_decode_ctx *ctx, uint64_t first, uint64_t n, char *out);
+
+typedef struct {
+    uint32_t struct_size;           /* sizeof(pgrc_decode_restore_timing) */
+    float ms_upload;                /* host wall time of the upload of the mapped text and the streams */
+    float ms_parse_device;          /* device time: marks, stream values, offsets, output positions, checks */
+    float ms_literals_device;       /* device time: the literal runs shifted to their output positions */
+    float ms_matches_device;        /* device time: HQ chain resolution and the fill of every part's matches */
+    float ms_call;                  /* host wall time of the whole call */
+    uint32_t passes;                /* pointer-jumping passes of the HQ chain resolution */
+    uint64_t marks[3];              /* marks per part */
+    uint64_t matched[3];            /* matched (restored from a source) symbols per part */
+} pgrc_decode_restore_timing;
+/* of the last successful pgrc_decode_set_mapped_text */
+int pgrc_decode_get_restore_timing(pgrc_decode_ctx *ctx, pgrc_decode_restore_timing *out);
+
 #ifdef __cplusplus
 }
 #endif

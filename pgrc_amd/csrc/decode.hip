@@ -17,22 +17,14 @@
 //                 ascend), else from per-row 16-byte gathers; RC and mismatches are applied in LDS; the tile leaves as
 //                 16-byte stores per lane
 //   download      rows are made into a device chunk and copied down while the next chunk is made (two chunks)
-#include <string.h>
-
-#include <algorithm>
 #include <chrono>
-#include <string>
 
-#include "ctx.h"
-#include "pgrc_decode.h"
+#include "decctx.h"
 
-#define DEC_TPB 256
 #define DEC_RMAX 256            // rows per tile at most (per-row LDS arrays)
 #define DEC_TILE_TARGET 8192    // bytes of a tile, about
 #define DEC_SRC_CAP 16384       // LDS bytes for the windows: a tile's text span, or its rows' gathered 16-byte lines
 #define DEC_TILE_CAP 12288      // R*(L+1) < DEC_TILE_TARGET + 16*(L+1) <= 12288
-#define DEC_TEXT_PAD 64         // zero bytes after the text: aligned 16-byte loads past a window's end stay inside
-#define DEC_STAGE_BYTES (64ull << 20)
 #define DEC_CHUNK_BYTES (64ull << 20)
 
 // error flags of the device checks
@@ -41,11 +33,6 @@
 #define DEC_F_MISOFF 4u         // a mismatch offset outside the read
 #define DEC_F_MISSYM 8u         // a mismatch code outside its form's range
 #define DEC_F_NOPOS 16u         // a row needs the positions of a list that has none
-
-struct DecBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
 
 struct DecList {                // device view of one list (kernel argument)
     const uint64_t *pos;        // joined-text positions, NULL = none
@@ -75,166 +62,7 @@ struct DecArgs {
     uint32_t *err;
 };
 
-struct pgrc_decode_ctx {
-    uint32_t L = 0;
-    int device = 0;
-    hipStream_t stream = nullptr, copy_stream = nullptr;
-    hipEvent_t ev_made[2]{}, ev_copied[2]{}, ev_k0[2]{}, ev_a{}, ev_b{};
-    uint8_t *stage[2]{};        // pinned staging (uploads and downloads of pageable memory)
-    DecBuf chunk[2];            // device chunks of rows
-    DecBuf text, flag, scratch;
-    uint64_t text_len = 0;
-    bool have_text = false;
-    struct List {
-        DecBuf pos, rc, mcum, moff, msym, raw;
-        uint64_t n = 0, nmis = 0;
-        bool has_pos = false, has_rc = false, has_mis = false;
-        uint32_t form = 0;
-        char order[5];
-        uint64_t text_base = 0;
-    } lst[3];
-    uint32_t nl = 0;
-    bool have_order = false;
-    pgrc_decode_order ord{};
-    DecBuf rl_order, org2pos, rank;
-    pgrc_decode_timing tm{};
-    std::string err;
-};
-
 static thread_local std::string g_dec_create_err;
-
-#define DEC_TRY(d, expr)                                                                     \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            (d)->err = std::string(#expr) + ": " + hipGetErrorString(e__);               \
-            return pgrc_hip_code(e__);                                                       \
-        }                                                                                    \
-    } while (0)
-
-static int dec_fail(pgrc_decode_ctx *d, int code, const std::string &msg) {
-    d->err = msg;
-    return code;
-}
-
-static int dec_buf(pgrc_decode_ctx *d, DecBuf &b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.p && b.bytes >= bytes) return PGRC_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return dec_fail(d, pgrc_hip_code(e), "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
-    }
-    b.bytes = bytes;
-    return PGRC_OK;
-}
-
-static void dec_free(DecBuf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-}
-
-// ------------------------------------------------------------------------------------------------ scans (u64 results)
-// The three-kernel scan of export.hip's k_scan_* restated over a transform of the input: per-block sums, one block that
-// scans them, per-block rescan with the carried-in prefix.
-#define DS_EPT 16
-#define DS_EPB (DEC_TPB * DS_EPT)
-
-__device__ __forceinline__ uint64_t ds_block_exclusive(uint64_t v, uint64_t *smem, uint64_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint64_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += u;
-    }
-    if (lane == 63) smem[wv] = inc;
-    __syncthreads();
-    uint64_t woff = 0, tot = 0;
-    for (uint32_t k = 0; k < DEC_TPB / 64; k++) {
-        const uint64_t s = smem[k];
-        if (k < wv) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
-}
-
-struct XfU8 { const uint8_t *p; __device__ uint64_t operator()(uint64_t i) const { return p[i]; } };
-struct XfU16 { const uint16_t *p; __device__ uint64_t operator()(uint64_t i) const { return p[i]; } };
-struct XfBelow { const uint64_t *p; uint64_t lim; __device__ uint64_t operator()(uint64_t i) const { return p[i] < lim ? 1u : 0u; } };
-
-template <typename Xf>
-__global__ void __launch_bounds__(DEC_TPB) k_ds_sums(Xf xf, uint64_t n, uint64_t *bsum) {
-    __shared__ uint64_t smem[DEC_TPB / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * DS_EPB + (uint64_t)threadIdx.x * DS_EPT;
-    uint64_t s = 0;
-    for (int k = 0; k < DS_EPT; k++)
-        if (base + k < n) s += xf(base + k);
-    uint64_t tot;
-    ds_block_exclusive(s, smem, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(DEC_TPB) k_ds_bsums(uint64_t *bsum, uint64_t nb) {
-    __shared__ uint64_t smem[DEC_TPB / 64];
-    uint64_t run = 0;
-    for (uint64_t b0 = 0; b0 < nb; b0 += DEC_TPB) {
-        const uint64_t i = b0 + threadIdx.x;
-        const uint64_t v = i < nb ? bsum[i] : 0;
-        uint64_t tot;
-        const uint64_t ex = ds_block_exclusive(v, smem, &tot);
-        if (i < nb) bsum[i] = run + ex;
-        run += tot;
-    }
-    if (threadIdx.x == 0) bsum[nb] = run;
-}
-
-// out[i] = base + (INCLUSIVE ? sum of xf(0..i) : sum of xf(0..i-1)); the exclusive form also writes out[n] = base + total
-template <typename Xf, bool INCLUSIVE>
-__global__ void __launch_bounds__(DEC_TPB) k_ds_write(Xf xf, uint64_t n, const uint64_t *__restrict__ bsum, uint64_t nb, uint64_t base_val,
-                                                      uint64_t *__restrict__ out) {
-    __shared__ uint64_t smem[DEC_TPB / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * DS_EPB + (uint64_t)threadIdx.x * DS_EPT;
-    uint64_t v[DS_EPT], s = 0;
-#pragma unroll
-    for (int k = 0; k < DS_EPT; k++) {
-        v[k] = (base + k < n) ? xf(base + k) : 0;
-        s += v[k];
-    }
-    uint64_t tot;
-    uint64_t acc = base_val + bsum[blockIdx.x] + ds_block_exclusive(s, smem, &tot);
-#pragma unroll
-    for (int k = 0; k < DS_EPT; k++) {
-        if (base + k < n) out[base + k] = INCLUSIVE ? acc + v[k] : acc;
-        acc += v[k];
-    }
-    if (!INCLUSIVE && blockIdx.x == 0 && threadIdx.x == 0) out[n] = base_val + bsum[nb];
-}
-
-__global__ void k_ds_set(uint64_t *out, uint64_t v) { *out = v; }
-
-template <bool INCLUSIVE, typename Xf>
-static int dec_scan(pgrc_decode_ctx *d, Xf xf, uint64_t n, uint64_t base_val, uint64_t *d_out) {
-    const uint64_t nb = (n + DS_EPB - 1) / DS_EPB;
-    int e;
-    if ((e = dec_buf(d, d->scratch, (nb + 2) * sizeof(uint64_t)))) return e;
-    uint64_t *bs = (uint64_t *)d->scratch.p;
-    if (!n) {
-        if (!INCLUSIVE) hipLaunchKernelGGL(k_ds_set, dim3(1), dim3(1), 0, d->stream, d_out, base_val);
-        DEC_TRY(d, hipGetLastError());
-        return PGRC_OK;
-    }
-    hipLaunchKernelGGL((k_ds_sums<Xf>), dim3((uint32_t)nb), dim3(DEC_TPB), 0, d->stream, xf, n, bs);
-    hipLaunchKernelGGL(k_ds_bsums, dim3(1), dim3(DEC_TPB), 0, d->stream, bs, nb);
-    hipLaunchKernelGGL((k_ds_write<Xf, INCLUSIVE>), dim3((uint32_t)nb), dim3(DEC_TPB), 0, d->stream, xf, n, (const uint64_t *)bs, nb, base_val, d_out);
-    DEC_TRY(d, hipGetLastError());
-    return PGRC_OK;
-}
 
 // ------------------------------------------------------------------------------------------------ entry tables
 __global__ void k_dec_widen_pos(const uint64_t *__restrict__ in, uint64_t n, uint64_t base, uint64_t *__restrict__ out) {
@@ -295,29 +123,6 @@ __global__ void k_dec_mis(const uint64_t *__restrict__ mcum, uint64_t n, const O
 }
 
 // ------------------------------------------------------------------------------------------------ the row kernel
-// complementsLut (helper.cpp:243-262): IUPAC complements of both cases to upper case, every other byte to 0
-__device__ __forceinline__ uint8_t dec_complement(uint32_t c) {
-    const uint32_t u = c & 0xDFu;   // upper case (only letters are mapped)
-    if (c < 'A' || (c > 'Z' && c < 'a') || c > 'z') return 0;
-    switch (u) {
-    case 'A': return 'T';
-    case 'C': return 'G';
-    case 'G': return 'C';
-    case 'T': return 'A';
-    case 'N': return 'N';
-    case 'U': return 'A';
-    case 'Y': return 'R';
-    case 'R': return 'Y';
-    case 'K': return 'M';
-    case 'M': return 'K';
-    case 'B': return 'V';
-    case 'V': return 'B';
-    case 'D': return 'H';
-    case 'H': return 'D';
-    default: return 0;
-    }
-}
-
 __global__ void __launch_bounds__(DEC_TPB) k_dec_rows(DecArgs a) {
     __shared__ __align__(16) uint8_t s_src[DEC_SRC_CAP];
     __shared__ __align__(16) uint8_t s_tile[DEC_TILE_CAP];
@@ -480,12 +285,6 @@ static uint32_t dec_rows_per_tile(uint32_t L) {
     return R;
 }
 
-static float dec_elapsed(hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return ms;
-}
-
 static int dec_check_err(pgrc_decode_ctx *d, const char *what) {
     uint32_t f = 0;
     DEC_TRY(d, hipMemcpyAsync(&f, d->flag.p, 4, hipMemcpyDeviceToHost, d->stream));
@@ -498,26 +297,6 @@ static int dec_check_err(pgrc_decode_ctx *d, const char *what) {
     if (f & DEC_F_MISSYM) m += " a mismatch code outside its form's range;";
     if (f & DEC_F_NOPOS) m += " a row of a list without positions;";
     return dec_fail(d, PGRC_E_PARAM, m);
-}
-
-static int dec_clear_err(pgrc_decode_ctx *d) {
-    DEC_TRY(d, hipMemsetAsync(d->flag.p, 0, 4, d->stream));
-    return PGRC_OK;
-}
-
-// host -> device through the two pinned staging buffers: the copy of one overlaps the host's fill of the other
-static int dec_upload(pgrc_decode_ctx *d, void *d_dst, const void *h_src, uint64_t bytes) {
-    const uint8_t *src = (const uint8_t *)h_src;
-    uint8_t *dst = (uint8_t *)d_dst;
-    int k = 0;
-    for (uint64_t o = 0; o < bytes; o += DEC_STAGE_BYTES, k ^= 1) {
-        const uint64_t c = std::min<uint64_t>(DEC_STAGE_BYTES, bytes - o);
-        DEC_TRY(d, hipEventSynchronize(d->ev_copied[k]));
-        memcpy(d->stage[k], src + o, c);
-        DEC_TRY(d, hipMemcpyAsync(dst + o, d->stage[k], c, hipMemcpyHostToDevice, d->stream));
-        DEC_TRY(d, hipEventRecord(d->ev_copied[k], d->stream));
-    }
-    return PGRC_OK;
 }
 
 extern "C" {
@@ -566,7 +345,9 @@ void pgrc_decode_destroy(pgrc_decode_ctx *d) {
     if (d->copy_stream) (void)hipStreamSynchronize(d->copy_stream);
     for (auto &l : d->lst)
         for (DecBuf *b : {&l.pos, &l.rc, &l.mcum, &l.moff, &l.msym, &l.raw}) dec_free(*b);
-    for (DecBuf *b : {&d->chunk[0], &d->chunk[1], &d->text, &d->flag, &d->scratch, &d->rl_order, &d->org2pos, &d->rank}) dec_free(*b);
+    for (DecBuf *b : {&d->chunk[0], &d->chunk[1], &d->text, &d->flag, &d->scratch, &d->rl_order, &d->org2pos, &d->rank, &d->rs_mapped, &d->rs_marks,
+                       &d->rs_vals, &d->rs_ptr, &d->rs_bsum})
+        dec_free(*b);
     for (int k = 0; k < 2; k++) {
         if (d->stage[k]) (void)hipHostFree(d->stage[k]);
         for (hipEvent_t ev : {d->ev_made[k], d->ev_copied[k], d->ev_k0[k]})
@@ -587,6 +368,7 @@ int pgrc_decode_set_text(pgrc_decode_ctx *d, const char *joined, uint64_t len) {
     PGRC_ON_DEVICE(d);
     const auto t0 = std::chrono::steady_clock::now();
     d->have_text = false;
+    d->have_parts = false;
     d->nl = 0;
     d->have_order = false;
     d->tm = pgrc_decode_timing{};

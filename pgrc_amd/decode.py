@@ -33,6 +33,18 @@ class DecodeTiming(C.Structure):    # pgrc_decode_timing
                 ("ms_rows_device", C.c_float), ("ms_rows", C.c_float), ("rows_bytes", C.c_uint64)]
 
 
+class DecodeMapped(C.Structure):    # pgrc_decode_mapped
+    _fields_ = [("struct_size", C.c_uint32), ("mapped", _P), ("mapped_len", C.c_uint64 * 3), ("org_hq_len", C.c_uint64),
+                ("map_off", _P * 3), ("map_off_bytes", C.c_uint64 * 3), ("map_len", _P * 3),
+                ("map_len_bytes", C.c_uint64 * 3), ("rev_compl", C.c_int32)]
+
+
+class RestoreTiming(C.Structure):   # pgrc_decode_restore_timing
+    _fields_ = [("struct_size", C.c_uint32), ("ms_upload", C.c_float), ("ms_parse_device", C.c_float),
+                ("ms_literals_device", C.c_float), ("ms_matches_device", C.c_float), ("ms_call", C.c_float),
+                ("passes", C.c_uint32), ("marks", C.c_uint64 * 3), ("matched", C.c_uint64 * 3)]
+
+
 # include/pgrc_decode.h (kept apart from _lib._PROTOS, which mirrors pgrc_match.h / pgrc_mem.h / pgrc_reads.h)
 DECODE_PROTOS = [
     ("pgrc_decode_create", C.c_int, [C.c_uint32, C.c_int32, C.POINTER(_P)]),
@@ -45,6 +57,10 @@ DECODE_PROTOS = [
     ("pgrc_decode_rows", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P]),
     ("pgrc_decode_rows_device", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P]),
     ("pgrc_decode_get_timing", C.c_int, [_P, C.POINTER(DecodeTiming)]),
+    ("pgrc_decode_set_mapped_text", C.c_int, [_P, C.POINTER(DecodeMapped)]),
+    ("pgrc_decode_text_lengths", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("pgrc_decode_get_text", C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
+    ("pgrc_decode_get_restore_timing", C.c_int, [_P, C.POINTER(RestoreTiming)]),
 ]
 for _name, _res, _args in DECODE_PROTOS:
     _fn = getattr(lib, _name)
@@ -60,6 +76,17 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(_P)
 
 
+def _bytes(a) -> np.ndarray:
+    """bytes, bytearray, str or an array as a contiguous uint8 array (None: empty)"""
+    if a is None:
+        return np.zeros(0, np.uint8)
+    if isinstance(a, str):
+        a = a.encode("latin-1")
+    if isinstance(a, (bytes, bytearray, memoryview)):
+        return np.frombuffer(a, dtype=np.uint8)
+    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+
 class PgRCDecoder:
     """The reads of a decoded archive, rebuilt on the device: the joined text HQ | LQ | N, the three reads lists, then
     one of the three writers."""
@@ -70,6 +97,7 @@ class PgRCDecoder:
         if rc:
             raise PgrcMatchError(rc, (lib.pgrc_decode_last_error(None) or b"").decode())
         self.readLength = int(read_length)
+        self._text_len = 0
 
     def _ck(self, rc: int) -> None:
         if rc:
@@ -78,7 +106,56 @@ class PgRCDecoder:
     def set_text(self, joined) -> None:
         """the joined pseudogenome text (bytes or uint8 array); copied to the device"""
         t = np.frombuffer(joined, dtype=np.uint8) if isinstance(joined, (bytes, bytearray)) else _arr(joined, np.uint8)
+        self._text_len = 0
         self._ck(lib.pgrc_decode_set_text(self._h, _ptr(t), t.size))
+        self._text_len = t.size
+
+    def restoreMatchedPgs(self, mapped, mapped_lens, org_hq_len: int, map_off, map_len, rev_compl: bool = True) -> None:
+        """SimplePgMatcher::restoreMatchedPgs (SimplePgMatcher.cpp:259-351) on the device: `mapped` is the joined mapped
+        text HQ | LQ | N (comboPgMapped) with the part lengths `mapped_lens`; map_off and map_len hold the three parts'
+        offsets and byte-frugal lengths streams (None or empty for an absent part).  Installs the restored joined text
+        as set_text would; the lists and the order are dropped."""
+        t = _bytes(mapped)
+        lens = [int(x) for x in mapped_lens]
+        assert len(lens) == 3 and sum(lens) == t.size and len(map_off) == 3 and len(map_len) == 3
+        offs = [_bytes(x) for x in map_off]
+        lns = [_bytes(x) for x in map_len]
+        a = DecodeMapped()
+        a.struct_size = C.sizeof(DecodeMapped)
+        a.mapped = _ptr(t)
+        a.org_hq_len = int(org_hq_len)
+        a.rev_compl = int(bool(rev_compl))
+        for p in range(3):
+            a.mapped_len[p] = lens[p]
+            a.map_off[p], a.map_off_bytes[p] = _ptr(offs[p]), offs[p].size
+            a.map_len[p], a.map_len_bytes[p] = _ptr(lns[p]), lns[p].size
+        self._text_len = 0
+        self._ck(lib.pgrc_decode_set_mapped_text(self._h, C.byref(a)))
+        self._text_len = sum(self.text_lengths())
+
+    def text_lengths(self) -> tuple:
+        """(HQ, LQ, N) lengths of the restored text: the lists' text_base are 0, HQ and HQ + LQ"""
+        v = (C.c_uint64 * 3)()
+        self._ck(lib.pgrc_decode_text_lengths(self._h, v))
+        return tuple(int(x) for x in v)
+
+    def text(self, first: int = 0, n: int | None = None, out=None) -> np.ndarray:
+        """bytes [first, first+n) of the installed joined text as uint8 (into `out` if given)"""
+        if n is None:
+            n = self._text_len - first
+        if out is None:
+            out = np.empty(n, dtype=np.uint8)
+        assert out.flags.c_contiguous and out.nbytes == n
+        self._ck(lib.pgrc_decode_get_text(self._h, int(first), int(n), out.ctypes.data_as(_P)))
+        return out
+
+    def restore_timing(self) -> dict:
+        t = RestoreTiming()
+        t.struct_size = C.sizeof(RestoreTiming)
+        self._ck(lib.pgrc_decode_get_restore_timing(self._h, C.byref(t)))
+        d = {k: getattr(t, k) for k, _ in t._fields_ if k != "struct_size"}
+        d["marks"], d["matched"] = list(t.marks), list(t.matched)
+        return d
 
     def add_list(self, n_entries: int, text_base: int = 0, off=None, pos=None, rev_comp=None, mis_cnt=None, mis_sym=None,
                  mis_off=None, mis_off_rev_coded: bool = True, mis_sym_form: int = 0, bases_order=None) -> None:
