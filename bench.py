@@ -12,7 +12,10 @@ with no data-path collective) and the packed Pg is shared by ONE all-gather (RCC
 `--scaling strong` keeps the TOTAL at the workload's read count and splits it N ways (BASELINE.json configs[3], "C4":
 `--workload C3-PE --scaling strong --gpus 8` = 100M PE reads over 8 GPUs); every rank still builds the whole index.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 with `roofline` and `phases_ms` (figures of the timed steps themselves).  A plain run does only
+what that line's headline needs: set up, warm up, time the steps, write `--dump-outputs`, print.  `--full` adds the legs that take
+runs of their own: `cpu_baseline` (the reference on the host cores), `parity_sample` (a sample checked against the reference)
+and, for C3 / C3-N, `boundary` (the same job from host buffers through the C ABI).
 """
 import argparse
 import json
@@ -62,13 +65,17 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=os.environ.get("PGRC_BENCH_WORKLOAD", "C3"), choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the CPU baseline, the parity sample and the boundary leg (the --no-* / --cpu-* / "
+                         "--parity-* options below shape them); off by default: a plain run only sets up, warms up, times the steps, "
+                         "dumps and prints")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline's main leg (0 = all of the box's hardware threads: BASELINE.md section 3, `-t $(nproc)`)")
-    ap.add_argument("--no-boundary", action="store_true", help="skip the boundary leg (host buffers -> host results through the C ABI, PCIe included; never `value`)")
+    ap.add_argument("--no-boundary", action="store_true", help="with --full: skip the boundary leg (host buffers -> host results through the C ABI, PCIe included; never `value`)")
     ap.add_argument("--no-cpu-t1", action="store_true", help="skip the -t 1 leg of the CPU baseline (two more serial index builds)")
     ap.add_argument("--cpu-sample-reads", type=int, default=3_000_000)
     ap.add_argument("--parity-sample-reads", type=int, default=100_000,
-                    help="reads checked bit for bit against the SERIAL-index reference (0 = skip)")
+                    help="with --full: reads checked bit for bit against the SERIAL-index reference (0 = skip)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: the workload's reads PER GPU (default, the driver's contract); strong: that many reads in TOTAL, split over the GPUs")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -336,20 +343,21 @@ def main():
             "ranks": per_rank,
             "counters": {k: ctr[k] for k in ("searched", "candidates", "probes", "entry_fetches", "verifies", "index_entries", "dual", "redo_reads", "dual_seed_probes")},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        # ---- the legs of --full: runs of their own after the timed steps, never `value`
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, ctx, g, rs, n_per, L, G, seed_len, kmax)
             except Exception as e:  # the GPU measurement must not be lost to a host-side problem
                 out["cpu_baseline"] = {"value": None, "unit": "reads/s", "cores": 0, "kind": "port", "sample": "failed: " + repr(e)}
 
-        if args.parity_sample_reads > 0:          # (at N > 1: rank 0's shard -- its own reads, the gathered text it matched them against)
+        if args.full and args.parity_sample_reads > 0:          # (at N > 1: rank 0's shard -- its own reads, the gathered text it matched them against)
             try:
                 out["parity_sample"] = parity_sample(args, ctx, g, rs, n_per, L, G, seed_len, kmax)
                 if world > 1:
                     out["parity_sample"]["shard"] = f"rank 0 of {world}: reads [{first_read}, {first_read + n_per}) of the set"
             except Exception as e:
                 out["parity_sample"] = {"diff": None, "error": repr(e)}
-        if world == 1 and not args.no_boundary and args.workload in ("C3", "C3-N"):
+        if args.full and world == 1 and not args.no_boundary and args.workload in ("C3", "C3-N"):
             try:
                 out["boundary"] = boundary_leg(n_per, L, G, kmax)
             except Exception as e:
@@ -487,12 +495,12 @@ def seed_mode_line(args, ctx, ctr, value, dt, step_sorted, world, n_per, n_total
                         "gather_ceiling_G_per_s": GATHER_CEILING_GPS},
            "counters": {"searched": ctr["searched"], "candidates": ctr["candidates"]},
            "results_digest": digest}
-    if world == 1 and args.parity_sample_reads > 0:
+    if args.full and world == 1 and args.parity_sample_reads > 0:
         try:
             out["parity_sample"] = seed_parity_sample(args, ctx, n_per, L, G, seed_len, kmax, mode)
         except Exception as e:
             out["parity_sample"] = {"diff": None, "error": repr(e)}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = seed_cpu_baseline(n_per, L, G, seed_len, kmax, mode)
         except Exception as e:
