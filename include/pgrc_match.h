@@ -282,6 +282,12 @@ typedef struct {
                              * context runs the two passes in turn until another text / read set is handed over */
     uint64_t dual_seed_probes; /* screened == 2: seeds the dual kernel probed -- a seed's forward and RC head (dual[2] counts
                              * both) lie in ONE 128-byte line of the pair table: this is the number of line requests for heads */
+    /* ---- fields from here on: only pgrc_match_get_counters_sized fills them (pgrc_match_get_counters writes the first
+     *      PGRC_MATCH_COUNTERS_BASE_SIZE bytes, the struct that callers built before it grew hold) */
+    uint64_t dual_skip_reads; /* screened == 2: reads whose dual query passed over the seeds between two rounds (the round
+                             * skip, PGRC_ROUND_SKIP) */
+    uint64_t dual_rewinds;  /* screened == 2: times such a read went back to the seeds it had passed over (an acceptable
+                             * candidate in skip mode, or the seeds ran out) */
 } pgrc_match_counters;
 /* flags[i] != 0: read i was one of `redo_reads` -- the dual kernel met a bucket it could not judge without the
  * reference's own falses count and did the read again in the reference's order (tests and bench.py draw their parity
@@ -293,6 +299,8 @@ int pgrc_match_get_redo_flags(pgrc_match_ctx *ctx, uint8_t *flags);
  *     PGRC_DUAL=0|1          never / whenever it applies: one query per read over both strands (the dual kernel)
  *     PGRC_SCREEN=0|1        never / whenever it applies: the screened schedule (exact-match screen, forward pass, RC pass)
  *     PGRC_EARLY_STOP=0      every read probes all its seeds, as the reference does (and the two passes in turn)
+ *     PGRC_ROUND_SKIP=0      the dual kernel probes every seed up to the early stop (default 1: between two rounds it
+ *                            probes only round seeds until an acceptable candidate makes it go back; dualkern.h)
  *     PGRC_BUILD_STREAMS=1   the two index builds of such a run on one stream instead of two
  *     PGRC_HEAD_PAIR=0|1..4  no pair table (a head table per strand) / groups of 1, 2, 4, 8 buckets (default 3 = groups of 4)
  *     PGRC_NREAD_INLINE=0    every read with an N takes the byte-path kernel (default: the dual kernel takes those with <= 4 N)
@@ -312,11 +320,13 @@ int pgrc_match_get_redo_flags(pgrc_match_ctx *ctx, uint8_t *flags);
 int pgrc_match_reload_options(pgrc_match_ctx *ctx);
 /* enable per-kernel HIP-event timing + work counters for subsequent runs */
 int pgrc_match_set_profiling(pgrc_match_ctx *ctx, int enabled);
+/* the first PGRC_MATCH_COUNTERS_BASE_SIZE bytes of pgrc_match_counters (up to dual_seed_probes): what a caller built before the
+ * struct grew holds, so such a caller keeps working; the later fields stay as the caller left them */
+#define PGRC_MATCH_COUNTERS_BASE_SIZE (offsetof(pgrc_match_counters, dual_seed_probes) + sizeof(uint64_t))
 int pgrc_match_get_counters(pgrc_match_ctx *ctx, pgrc_match_counters *out);
-/* the same for a caller that may have been built against another version of this header: pgrc_match_counters only ever grows at
+/* all of it, for a caller that may have been built against another version of this header: pgrc_match_counters only ever grows at
  * its END, and this writes exactly out_size bytes -- the first out_size bytes of the current struct, zeros beyond what the
- * library knows -- so `pgrc_match_get_counters_sized(ctx, &c, sizeof c)` never writes past the caller's struct (pgrc_match_get_counters
- * writes the library's sizeof) */
+ * library knows -- so `pgrc_match_get_counters_sized(ctx, &c, sizeof c)` never writes past the caller's struct */
 int pgrc_match_get_counters_sized(pgrc_match_ctx *ctx, void *out, size_t out_size);
 
 /* ---- synthetic inputs (include/pgrc_synth.h) ---- */

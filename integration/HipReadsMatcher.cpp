@@ -208,7 +208,7 @@ namespace PgTools {
             failOn(pgrc_match_get_results(ctx, readMatchPos.data(), rc.data(), readMismatchesCount.data(), hist,
                                           &matched), "get_results");
             pgrc_match_counters ctr;
-            if (pgrc_match_get_counters(ctx, &ctr) == PGRC_OK && ctr.screened == 2) dualRuns++;
+            if (pgrc_match_get_counters_sized(ctx, &ctr, sizeof ctr) == PGRC_OK && ctr.screened == 2) dualRuns++;
             // vector<bool> is bit-packed: threads may only share it along 64-bit word boundaries (the reference's own
             // parallel loop does not respect that, ReadsMatchers.cpp:426-446)
             const uint64_t chunk = 64u * 4096u, total = deviceReads;
@@ -640,7 +640,7 @@ namespace PgTools {
         failOn(pgrc_match_stream_end(ctx, hist, &matched), "stream_end");
         streamedRuns++;
         pgrc_match_counters ctr;
-        if (pgrc_match_get_counters(ctx, &ctr) == PGRC_OK && ctr.screened == 2) dualRuns++;
+        if (pgrc_match_get_counters_sized(ctx, &ctr, sizeof ctr) == PGRC_OK && ctr.screened == 2) dualRuns++;
         const uint64_t chunk = 64u * 4096u, total = readsCount;     // (vector<bool>: threads share it along word boundaries only)
         #pragma omp parallel for schedule(static)
         for (uint64_t c0 = 0; c0 < total; c0 += chunk) {

@@ -132,6 +132,7 @@ PgrcOptions pgrc_options_from_env() {
     o.dual = flag("PGRC_DUAL");
     o.screen = flag("PGRC_SCREEN");
     o.early_stop = flag("PGRC_EARLY_STOP") != 0;
+    o.round_skip = flag("PGRC_ROUND_SKIP") != 0;
     o.builds_in_turn = flag("PGRC_BUILD_STREAMS") == 1;
     if (const char *hp = getenv("PGRC_HEAD_PAIR")) o.head_pair = hp[0] == '0' ? 0u : (hp[0] >= '1' && hp[0] <= '4') ? 1u << (hp[0] - '1') : 4u;
     if (const char *is = getenv("PGRC_INDEX_SORT")) o.index_front = !strcmp(is, "own") ? 1 : 0;
@@ -318,7 +319,7 @@ int pgrc_match_create(const pgrc_match_params *p, pgrc_match_ctx **out) {
         if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
     }
     int be;
-    if ((be = pgrc_buf_ensure(c, c->d_hist, 256 * sizeof(uint64_t))) || (be = pgrc_buf_ensure(c, c->d_counters, 32 * sizeof(uint64_t)))) {
+    if ((be = pgrc_buf_ensure(c, c->d_hist, 256 * sizeof(uint64_t))) || (be = pgrc_buf_ensure(c, c->d_counters, 40 * sizeof(uint64_t)))) {
         g_create_err = c->err;
         pgrc_buf_free(c->d_hist);
         delete c;
@@ -975,7 +976,7 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
     PGRC_ON_DEVICE(c);
     int e;
     if (!c->have_results && (e = pgrc_match_init_results(c))) return e;
-    HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, 32 * sizeof(uint64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, 40 * sizeof(uint64_t), c->stream));
     memset(&c->ctr, 0, sizeof c->ctr);
     const bool prof = c->profiling && c->have_events;
     int evi = 0;
@@ -1078,7 +1079,7 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
     mark();
     uint64_t ctr[16];
     HIP_TRY(c, hipMemcpy(ctr, c->d_counters.p, sizeof ctr, hipMemcpyDeviceToHost));
-    uint64_t scr[8];
+    uint64_t scr[9];
     HIP_TRY(c, hipMemcpy(scr, (const uint64_t *)c->d_counters.p + 24, sizeof scr, hipMemcpyDeviceToHost));
     for (int s = 0; s < 2 && c->prm.mode == 'c'; s++) {      // (modes d/i/e: pgrc_seedidx_run filled searched / candidates)
         c->ctr.searched[s] = ctr[8 * s + 0];
@@ -1091,6 +1092,8 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
         for (int k = 0; k < 5; k++) c->ctr.dual[k] = scr[k];
         c->ctr.redo_reads = scr[5];
         c->ctr.dual_seed_probes = scr[6];
+        c->ctr.dual_skip_reads = scr[7];
+        c->ctr.dual_rewinds = scr[8];
         c->ctr.screened = 2;
     } else if (screened) {           // the screen ran on the RC text: its work counts with that strand's (not "searched")
         c->ctr.candidates[1] += scr[1];
@@ -1168,11 +1171,21 @@ int pgrc_match_get_results_device(pgrc_match_ctx *c, void **d_pos, void **d_rc, 
     return PGRC_OK;
 }
 
-int pgrc_match_get_counters(pgrc_match_ctx *c, pgrc_match_counters *out) {
+static int get_counters_full(pgrc_match_ctx *c, pgrc_match_counters *out) {
     if (!c || !out) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_get_counters(c, out);
     *out = c->ctr;
     out->index_entries[0] = out->index_entries[1] = c->npos;
+    return PGRC_OK;
+}
+
+// Callers compiled against the header before pgrc_match_counters grew hold a struct that ends at dual_seed_probes: this
+// writes that much and no more (the fields after it come through pgrc_match_get_counters_sized)
+int pgrc_match_get_counters(pgrc_match_ctx *c, pgrc_match_counters *out) {
+    pgrc_match_counters full;
+    const int e = get_counters_full(c, &full);
+    if (e) return e;
+    memcpy(out, &full, PGRC_MATCH_COUNTERS_BASE_SIZE);
     return PGRC_OK;
 }
 
@@ -1181,7 +1194,7 @@ int pgrc_match_get_counters(pgrc_match_ctx *c, pgrc_match_counters *out) {
 int pgrc_match_get_counters_sized(pgrc_match_ctx *c, void *out, size_t out_size) {
     if (!c || !out) return PGRC_E_PARAM;
     pgrc_match_counters full;
-    const int e = pgrc_match_get_counters(c, &full);
+    const int e = get_counters_full(c, &full);
     if (e) return e;
     memset(out, 0, out_size);
     memcpy(out, &full, std::min(out_size, sizeof full));

@@ -882,6 +882,7 @@ int pgrc_copmem_match_dual(pgrc_match_ctx *c) {
     a.k2 = (uint32_t)c->cp.k2;
     a.mask = c->cp.hash_size - 1;
     a.kmax = c->prm.max_mismatches;
+    a.skip = c->opt.round_skip ? 1u : 0u;                // PGRC_ROUND_SKIP=0: every seed up to the early stop (A/B runs, tests)
     switch (c->nw) {
 #define CASE_NW(N) case N: launch_dual<N>(c, a); break;
         CASE_NW(2) CASE_NW(3) CASE_NW(4) CASE_NW(5) CASE_NW(6) CASE_NW(7) CASE_NW(8) CASE_NW(9)

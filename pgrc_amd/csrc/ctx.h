@@ -44,6 +44,7 @@ struct PgrcOptions {
     int dual = -1;                  // PGRC_DUAL        -1 the library's choice, 0 never, 1 whenever the dual kernel applies
     int screen = -1;                // PGRC_SCREEN      -1 not asked for, 0 never, 1 whenever the screened schedule applies
     bool early_stop = true;         // PGRC_EARLY_STOP=0: every read probes all its seeds, as the reference does
+    bool round_skip = true;         // PGRC_ROUND_SKIP=0: the dual kernel probes every seed up to the early stop (no round skip)
     bool builds_in_turn = false;    // PGRC_BUILD_STREAMS=1: the two index builds of a two-strand run on one stream
     uint32_t head_pair = 4;         // PGRC_HEAD_PAIR   0: a head table per strand; 1..4: pair table with groups of 1, 2, 4, 8 buckets
     int index_front = 0;            // PGRC_INDEX_SORT  0 "sweep" (idxsweep.hip), 1 "own" (idxsort.hip's stable scatter passes)

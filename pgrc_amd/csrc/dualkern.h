@@ -27,6 +27,20 @@
 // the speculative first attempt, the redo rule and the hand-out direction as run-time parameters (measured in round 4, kept
 // in DESIGN.md's appendix of dead ends).  16 staged reads per wave instead of 32 keep a block at 26.1 KB of LDS: six blocks
 // per CU.
+//
+// Round skip (a.skip; PGRC_ROUND_SKIP=0 turns it off).  Only the seeds of a round can make a round clean; the other seeds of
+// a round period matter only if they yield an acceptance.  So when a round ends and a strand is still active, the lane jumps
+// to the next round's first seed (F_SKIP; the first passed-over seed and both strands' clean rounds are kept in `fl`) and
+// probes round seeds only: every bucket whole (no truncation by the budget, no F_REDO), U left alone, nothing accepted.  A
+// candidate of an active strand s with a count <= eff(s), or the end of the seeds, REWINDS the lane: back to the first
+// passed-over seed with the clean rounds of that moment and no dirty round, from where it goes on in seed order as without
+// the rule (and may skip again at the next round end).  A strand whose clean rounds exceed eff(s) in skip mode stops, as
+// always.  Why the result is the same: that strand stops only after eff(s) + 1 clean rounds without a candidate <= eff(s);
+// by the early-stop argument (copmem.hip, "Early stop") no alignment with <= eff(s) mismatches exists anywhere in the text,
+// so no passed-over seed could have been accepted, whatever the falses budget would have cut.  eff(s) only falls, so such a
+// stop still holds after a later rewind of the other strand.  Everything else is replayed in seed order, so ties, limits
+// and U (an upper bound of the falses of the reference's run: skip mode adds nothing to it) come out as before.  F_SEQ never
+// skips.  tests/roundskip_model.py restates the rule; tests/test_round_skip_rule.py holds it to the reference's order.
 #pragma once
 
 #include "ctx.h"
@@ -46,10 +60,12 @@ struct DualArgs {
     uint8_t *rc;
     uint8_t *mism;
     unsigned long long *counters; // [0] searched [1] candidates [2] heads probed [3] entry fetches [4] verifies [5] redo [6] seeds probed
+                                  // [7] reads that entered skip mode [8] rewinds
     unsigned long long *work;
     uint8_t *redo_flag;           // per read: 2 = done again in the reference's order (F_SEQ); introspection only
     uint32_t L, K, k1, k2, mask, kmax;
     uint32_t chunk;               // reads a wave reserves per visit to the work counter (pgrc_match_chunk)
+    uint32_t skip;                // 1: the round skip (see above); 0: every seed up to the early stop (PGRC_ROUND_SKIP=0)
 };
 
 // reads a wave stages in LDS per burst of full-line loads: 16 at six waves per SIMD (LDS for six blocks per CU), else 32
@@ -93,14 +109,18 @@ k_copmem_match_dual(const DualArgs a) {
 
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t n_search = 0, n_cand = 0, n_probe = 0, n_ent = 0, n_ver = 0, n_redo = 0, n_seed = 0;   // wave-uniform: SGPRs
+    uint32_t n_skip = 0, n_rew = 0;
     const uint32_t budget = (a.L + 1u - a.K) / a.k2;
     const uint32_t rper = (a.K + a.k1 * a.k2 - 1u) / (a.k1 * a.k2) * a.k1;
 
     enum { M_PROBE = 0, M_ENTRY = 1, M_VERIFY = 2, M_NEED = 3, M_ADV = 4, M_DEAD = 5 };
     // F_SEQ: the falses bound ran out: the lane does this read again in the reference's order, right here (forward query
     // with its real falses count and bucket truncation, then -- F_SEQ1 -- the RC query from the forward result)
+    // F_SKIP: round seeds only (the round skip); bits 11..30 of fl then hold the first passed-over seed (8 bits) and both
+    // strands' clean rounds when the lane started skipping (6 bits each: a read has at most (L - K) / K + 2 < 16 rounds).
+    // F_SKIPPED: the read has skipped (counted once).
     enum { F_ACT0 = 1, F_ACT1 = 2, F_FOUND0 = 4, F_FOUND1 = 8, F_DIRTY0 = 16, F_DIRTY1 = 32, F_REDO = 64, F_FWDEXACT = 128,
-           F_SEQ = 256, F_SEQ1 = 512 };
+           F_SEQ = 256, F_SEQ1 = 512, F_SKIP = 1024, F_SKIPPED = 1u << 31 };
     // ---- the lane's read.  Five registers hold what round 4 kept in twenty:
     //   sr = si | rq << 8 | rcl0 << 16 | rcl1 << 24      seed index (< 240), seed inside the round period, clean rounds per strand
     //   cc = cur0 | cur1 << 8 | cin << 16 | L0 << 24     best count per strand, the read's count before the run, its starting limit
@@ -140,6 +160,12 @@ k_copmem_match_dual(const DualArgs a) {
     };
     auto set_lim = [&](uint32_t s, int v) { ll = (ll & ~(0x1FFu << (9u * s))) | ((uint32_t)(v + 1) << (9u * s)); };
     auto set_cur = [&](uint32_t s, uint32_t v) { cc = (cc & ~(0xFFu << (8u * s))) | (v << (8u * s)); };
+    // the end of skip mode: back to the first passed-over seed (inside its round period: k1), its clean rounds, no dirty round
+    auto rewind = [&]() {
+        sr = ((fl >> 11) & 0xFFu) | (a.k1 << 8) | (((fl >> 19) & 63u) << 16) | (((fl >> 25) & 63u) << 24);
+        fl &= (uint32_t)(F_SKIPPED | (F_SKIP - 1)) & ~(uint32_t)(F_DIRTY0 | F_DIRTY1);
+        jn &= ~(1u << 9);
+    };
 
     for (;;) {
         // ---- refill (as in k_copmem_match_sm, staged)
@@ -215,7 +241,7 @@ k_copmem_match_dual(const DualArgs a) {
         uint64_t v = 0;
         bool counted_ent = false;
         uint32_t ncand_it = 0, nprobe_it = 0;
-        bool n_redo_it = false;
+        bool n_redo_it = false, rew = false, skip_new = false;
         if (m0 == M_PROBE) {
             // the seed's window, cut out of the read's LDS copy: symbols s .. s + K - 1
             const uint32_t s = DK_SI() * a.k2, q = s >> 4, shb = (s & 15u) * 2u;
@@ -329,10 +355,11 @@ k_copmem_match_dual(const DualArgs a) {
                 const uint32_t cnt = head_count(oh);
                 if (!cnt) {
                     bdone = true;
-                } else if (!(fl & F_SEQ) && DK_U(x) > budget && cnt > PGRC_TRUNC_BUCKET) {
+                } else if (!(fl & (F_SEQ | F_SKIP)) && DK_U(x) > budget && cnt > PGRC_TRUNC_BUCKET) {
                     // some run could have cut THIS bucket to its first 4 entries by now (:510-514 -- all the budget ever does; a
                     // bucket of at most 4 is the same bucket whatever the falses count): not decidable this way -> the read again,
-                    // in the reference's order
+                    // in the reference's order.  (Skip mode opens every bucket whole: it accepts nothing, and what it proves
+                    // absent is absent from the whole text.)
                     fl |= F_REDO;
                     next = M_NEED;
                 } else {
@@ -369,7 +396,7 @@ k_copmem_match_dual(const DualArgs a) {
                     const int fpc = __popc((xr | (xr >> 1)) & fpm_tab[si]);   // a lower bound of the head count
                     if (fpc > eff(x)) {
                         const uint32_t u = ((fl & F_SEQ) || fpc > DK_L0()) ? 1u : 2u;   // (sequential: a certain head reject)
-                        uu += u << (16u * x);
+                        if (!(fl & F_SKIP)) uu += u << (16u * x);
                     } else {
                         const uint32_t epoch = DK_EPOCH();
                         const uint2 cv = vcache[((uint32_t)p * 0x9E3779B1u + x) >> (32 - VC_BITS)][threadIdx.x];
@@ -403,8 +430,13 @@ k_copmem_match_dual(const DualArgs a) {
                     // the tail is clean (then it is a head reject or an acceptance), else 2 (a tail reject is counted twice)
                     u = ((int)jmh > DK_L0() || jmt == 0u) ? 1u : 2u;
                 }
-                uu += u << (16u * x);
-                if (m <= eff(x)) {
+                if (!(fl & F_SKIP)) uu += u << (16u * x);
+                if (m <= eff(x) && (fl & F_SKIP)) {                  // acceptable, met in skip mode: the passed-over seeds in order
+                    rewind();
+                    rew = true;
+                    next = M_PROBE;
+                    ap = false;
+                } else if (m <= eff(x)) {
                     set_cur(x, (uint32_t)m);
                     set_lim(x, m - 1);
                     if (x == 0u) { best0 = jpos; fl |= F_FOUND0; }
@@ -440,11 +472,28 @@ k_copmem_match_dual(const DualArgs a) {
                 rcl1 += (fl & F_DIRTY1) ? 0u : 1u;
                 fl &= ~(uint32_t)(F_DIRTY0 | F_DIRTY1);
             }
-            const uint32_t si = DK_SI() + 1u;
-            sr = si | ((rq + 1u == rper ? 0u : rq + 1u) << 8) | (rcl0 << 16) | (rcl1 << 24);
+            uint32_t si = DK_SI() + 1u, rqn = rq + 1u == rper ? 0u : rq + 1u;
             jn &= ~(1u << 9);
             if ((fl & F_ACT0) && (int)rcl0 > eff(0u)) fl &= ~(uint32_t)F_ACT0;   // nothing acceptable is left on that strand
             if ((fl & F_ACT1) && (int)rcl1 > eff(1u)) fl &= ~(uint32_t)F_ACT1;
+            if (rqn == a.k1 && a.skip && (fl & (F_ACT0 | F_ACT1)) && !(fl & F_SEQ)) {
+                // a round is over and its period has seeds between it and the next round (rper > k1): pass over them
+                const uint32_t nx = si + rper - a.k1;
+                if (!(fl & F_SKIP) && nx < nseeds) {
+                    skip_new = !(fl & F_SKIPPED);
+                    fl |= F_SKIP | F_SKIPPED | (si << 11) | (rcl0 << 19) | (rcl1 << 25);
+                }
+                if (fl & F_SKIP) {
+                    si = nx;
+                    rqn = 0;
+                }
+            }
+            sr = si | (rqn << 8) | (rcl0 << 16) | (rcl1 << 24);
+            if ((fl & F_SKIP) && si >= nseeds && (fl & (F_ACT0 | F_ACT1))) {   // the seeds ran out in skip mode
+                rewind();
+                rew = true;
+                si = DK_SI();
+            }
             next = (si < nseeds && (fl & (F_ACT0 | F_ACT1))) ? M_PROBE : M_NEED;
         }
         // ---- the reference's order for a read whose falses bound ran out: restart it as a forward query, then an RC query
@@ -494,6 +543,8 @@ k_copmem_match_dual(const DualArgs a) {
             }
         }
         n_redo += (uint32_t)__popcll(__ballot(n_redo_it));
+        n_skip += (uint32_t)__popcll(__ballot(skip_new));
+        n_rew += (uint32_t)__popcll(__ballot(rew));
         mode = next;
     }
     if (a.counters && lane == 0) {
@@ -504,6 +555,8 @@ k_copmem_match_dual(const DualArgs a) {
         atomicAdd(&a.counters[4], (unsigned long long)n_ver);
         atomicAdd(&a.counters[5], (unsigned long long)n_redo);
         atomicAdd(&a.counters[6], (unsigned long long)n_seed);
+        atomicAdd(&a.counters[7], (unsigned long long)n_skip);
+        atomicAdd(&a.counters[8], (unsigned long long)n_rew);
     }
 #undef DK_SI
 #undef DK_RQ

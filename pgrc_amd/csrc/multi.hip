@@ -476,7 +476,7 @@ int pgrc_multi_get_counters(pgrc_match_ctx *f, pgrc_match_counters *out) {
     memset(out, 0, sizeof *out);
     for (pgrc_match_ctx *c : m->child) {
         pgrc_match_counters x;
-        int e = pgrc_match_get_counters(c, &x);
+        int e = pgrc_match_get_counters_sized(c, &x, sizeof x);
         if (e) return e;
         for (int s = 0; s < 2; s++) {
             out->searched[s] += x.searched[s];
@@ -496,6 +496,8 @@ int pgrc_multi_get_counters(pgrc_match_ctx *f, pgrc_match_counters *out) {
         out->schedule_downgraded |= x.schedule_downgraded;
         for (int k = 0; k < 5; k++) out->dual[k] += x.dual[k];
         out->dual_seed_probes += x.dual_seed_probes;
+        out->dual_skip_reads += x.dual_skip_reads;
+        out->dual_rewinds += x.dual_rewinds;
     }
     out->ms_allgather = m->ms_allgather;
     return PGRC_OK;

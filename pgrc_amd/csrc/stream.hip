@@ -114,7 +114,7 @@ extern "C" int pgrc_match_stream_begin(pgrc_match_ctx *c, uint64_t *pos, uint8_t
     if ((e = pgrc_launch_init_results(c))) return e;
     if ((e = pgrc_buf_ensure(c, c->d_scr_pos, c->n * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, c->d_scr_flag, c->n ? c->n : 1))) return e;
     HIP_TRY(c, hipMemsetAsync(c->d_scr_flag.p, 0, c->n ? c->n : 1, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, 32 * sizeof(uint64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, 40 * sizeof(uint64_t), c->stream));
     memset(&c->ctr, 0, sizeof c->ctr);
     if (!c->st_ready) HIP_TRY(c, hipEventCreateWithFlags(&c->st_ready, hipEventDisableTiming));
     HIP_TRY(c, hipEventRecord(c->st_ready, c->stream));              // both indexes built, per-read state initialised
@@ -238,12 +238,14 @@ extern "C" int pgrc_match_stream_end(pgrc_match_ctx *c, uint64_t hist[256], uint
     release_kept(c);
     if (!e && c->st_err) { e = c->st_err; c->err = "stream_end: a result download failed"; }
     if (e) return e;
-    uint64_t scr[8];
+    uint64_t scr[9];
     HIP_TRY(c, hipMemcpy(scr, (const uint64_t *)c->d_counters.p + 24, sizeof scr, hipMemcpyDeviceToHost));
     if (c->st_dual) {
         for (int k = 0; k < 5; k++) c->ctr.dual[k] = scr[k];
         c->ctr.redo_reads = scr[5];
         c->ctr.dual_seed_probes = scr[6];
+        c->ctr.dual_skip_reads = scr[7];
+        c->ctr.dual_rewinds = scr[8];
         c->ctr.screened = 2;
     }
     c->ctr.ms_total = (float)((now_s() - c->st_t0) * 1e3);           // (host clock: stream_begin .. here)

@@ -335,6 +335,7 @@ class MatchContext:
                 "ms_other": c.ms_other, "ms_total": c.ms_total, "ms_allgather": c.ms_allgather,
                 "screened": c.screened, "ms_screen": c.ms_screen, "redo_reads": c.redo_reads,
                 "schedule_downgraded": c.schedule_downgraded, "dual_seed_probes": c.dual_seed_probes,
+                "dual_skip_reads": c.dual_skip_reads, "dual_rewinds": c.dual_rewinds,
                 "dual": dict(zip(("searched", "candidates", "probes", "entry_fetches", "verifies"), list(c.dual)))}
 
 

@@ -36,6 +36,7 @@ def main():
     keys = sorted({k for v in variants for k in v})
     res = {i: [] for i in range(len(variants))}
     ref = None
+    ctrs = {}
     for r in range(a.rounds + 1):
         for i, v in enumerate(variants):
             for k in keys: os.environ.pop(k, None)
@@ -47,8 +48,9 @@ def main():
             if ref is None: ref = (hist.tolist(), matched)
             assert (hist.tolist(), matched) == ref, "variants disagree on results"
             if r: res[i].append((c["ms_match"][0], c["ms_match"][1], c["ms_index"][0] + c["ms_index"][1], c["ms_total"], c["ms_screen"]))
+            ctrs[i] = {k: c.get(k) for k in ("dual_seed_probes", "dual_skip_reads", "dual_rewinds", "redo_reads")}
     for i, v in enumerate(variants):
         med = [statistics.median(x[k] for x in res[i]) for k in range(5)]
-        print(f"{a.variants[i]:40s} dual/screen {med[4]:7.2f}  match_fwd {med[0]:7.2f}  match_rc {med[1]:7.2f}  index {med[2]:7.2f}  total {med[3]:7.2f} ms")
+        print(f"{a.variants[i]:40s} dual/screen {med[4]:7.2f}  match_fwd {med[0]:7.2f}  match_rc {med[1]:7.2f}  index {med[2]:7.2f}  total {med[3]:7.2f} ms  {json.dumps(ctrs[i])}")
 if __name__ == "__main__":
     main()
