@@ -155,7 +155,6 @@ PgrcOptions pgrc_options_from_env() {
     if (num("PGRC_SEED_SEGMENT") > 0) o.seed_segment = (uint64_t)num("PGRC_SEED_SEGMENT");
     if (num("PGRC_MEM_EVENT_CAP") > 0) o.mem_event_cap = (uint64_t)num("PGRC_MEM_EVENT_CAP");
     if (const char *ag = getenv("PGRC_ALLGATHER")) o.allgather = !strcmp(ag, "rccl") ? 1 : !strcmp(ag, "copy") ? 2 : 0;
-    o.dual_variant = (int)num("PGRC_DUAL_VARIANT");
     return o;
 }
 

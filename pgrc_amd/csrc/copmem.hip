@@ -186,14 +186,6 @@ struct MatchArgs {
 //     accepted with m > 0 mismatches -- or lying in a repeat -- meets the same alignments again at every
 //     later seed sampled there; their head/tail counts cannot change, only the limit they are judged
 //     against does, so the text window is fetched once.
-#ifndef PROBE_AHEAD
-#define PROBE_AHEAD 1       // probing lanes fetch the next seed's bucket head together with their own
-#endif
-#ifdef MATCH_WAVES_PER_EU     // experiments only (tools/variants.sh): the compiler's own choice is 6 for L <= 160
-#define MATCH_OCCUPANCY_ATTR __attribute__((amdgpu_waves_per_eu(MATCH_WAVES_PER_EU)))
-#else
-#define MATCH_OCCUPANCY_ATTR
-#endif
 // reads a wave reserves per visit to the global work counter: 1024 for a whole read set (256 / 512 / 1024: step +0 / -0.2 /
 // -0.4 % at C3), less for a short launch -- a block of a streamed run: 7 M reads over ~5000 resident waves are 1.35 chunks of
 // 1024 per wave, i.e. half the waves do two chunks while the others wait (10 ms per block instead of 6)
@@ -245,7 +237,7 @@ static uint32_t pgrc_match_chunk(const pgrc_match_ctx *c, uint64_t n) {
 // POS64: text positions need more than 32 bits (Pg >= 4 Gi symbols: the reference's u64 index branch,
 // CopMEMMatcher.cpp:579-586); otherwise positions are kept in one register.
 template <int NW, int KQ, bool POS64, int STAGE = 0>
-__global__ void __launch_bounds__(MATCH_TPB) MATCH_OCCUPANCY_ATTR k_copmem_match_sm(const MatchArgs a) {
+__global__ void __launch_bounds__(MATCH_TPB) k_copmem_match_sm(const MatchArgs a) {
     typedef typename std::conditional<POS64, uint64_t, uint32_t>::type pos_t;
     constexpr pos_t POS_NONE = (pos_t)~(pos_t)0;
     constexpr uint32_t EPOCH_BITS = POS64 ? 13u : 16u; // POS64 keeps position bits 32..39 next to the counts
@@ -296,11 +288,9 @@ __global__ void __launch_bounds__(MATCH_TPB) MATCH_OCCUPANCY_ATTR k_copmem_match
     pos_t cand_p = 0;
     uint64_t pend_e = 0;          // an entry already in registers (entry 1 of the head / second half of a pair)
     bool has_pend = false;
-#if PROBE_AHEAD
     ulonglong2 hdn = make_ulonglong2(HEAD_EMPTY, HEAD_EMPTY);   // the head of this lane's NEXT seed, fetched ahead
     uint32_t fpn = 0;
     bool have_n = false;
-#endif
     constexpr int PWN = ((NW + 1 + 3) / 4) * 4;
 
     // judge a verified alignment (head count mh, tail count mt) exactly as CopMEMMatcher.cpp:536-560
@@ -368,9 +358,7 @@ __global__ void __launch_bounds__(MATCH_TPB) MATCH_OCCUPANCY_ATTR k_copmem_match
                         rclean = 0;
                         rdirty = false;
                         has_pend = false;
-#if PROBE_AHEAD
                         have_n = false;
-#endif
                         epoch = (epoch + 1u) & ((1u << EPOCH_BITS) - 1u); // invalidates this lane's verify-cache entries
                         if (epoch == 0) {                            // wrapped: really clear them
 #pragma unroll
@@ -394,27 +382,21 @@ __global__ void __launch_bounds__(MATCH_TPB) MATCH_OCCUPANCY_ATTR k_copmem_match
         uint64_t v = 0;
         bool counted_ent = false;
         uint32_t ncand_it = 0;        // candidates tested in this iteration (a probing lane may consume two heads)
-#if PROBE_AHEAD
         // A probing lane also fetches the head of the NEXT seed: if its own bucket turns out empty (every second one) it
         // consumes that head in the same iteration, otherwise it keeps it for later.  Two gathers in flight per probing
         // lane instead of one; nothing is fetched twice and nothing beyond the read's last seed.
         ulonglong2 hd2 = make_ulonglong2(HEAD_EMPTY, HEAD_EMPTY);
         uint32_t fp2 = 0;
         bool got2 = false;
-#endif
         if (m0 == M_PROBE) {
-#if PROBE_AHEAD
             if (have_n) {
                 hd = hdn;
                 fp_read = fpn;
-            } else
-#endif
-            {
+            } else {
                 const uint32_t h = hash_fp_window<KQ>(sh[0], NW > 1 ? sh[1 % NW] : 0u, NW > 2 ? sh[2 % NW] : 0u,
                                                       NW > 3 ? sh[3 % NW] : 0u, a.K, lut, &fp_read) & a.mask;
                 hd = a.head[head_slot(h, a.hsh)];
             }
-#if PROBE_AHEAD
             if (si + 1 < nseeds) {
                 // the window of the next seed: the read shifted by one more seed step (sbits <= 30)
                 const uint32_t n0 = funnel_r(sh[0], NW > 1 ? sh[1 % NW] : 0u, sbits);
@@ -426,7 +408,6 @@ __global__ void __launch_bounds__(MATCH_TPB) MATCH_OCCUPANCY_ATTR k_copmem_match
                 got2 = true;
             }
             have_n = false;
-#endif
         } else if (m0 == M_ENTRY) {
             if (has_pend) {
                 v = pend_e;
@@ -526,7 +507,6 @@ __global__ void __launch_bounds__(MATCH_TPB) MATCH_OCCUPANCY_ATTR k_copmem_match
             take_entry(v);
         } else if (m0 == M_PROBE) {
             take_head(hd);
-#if PROBE_AHEAD
             if (got2) {
                 if (next == M_ADV) {                                 // empty bucket: the next seed's head is here already
                     advance();
@@ -544,7 +524,6 @@ __global__ void __launch_bounds__(MATCH_TPB) MATCH_OCCUPANCY_ATTR k_copmem_match
                     have_n = true;
                 }
             }
-#endif
         }
         if (next == M_ADV) {
             advance();
@@ -584,9 +563,7 @@ __global__ void __launch_bounds__(MATCH_TPB) MATCH_OCCUPANCY_ATTR k_copmem_match
                     rclean = 0;
                     rdirty = false;
                     has_pend = false;
-#if PROBE_AHEAD
                     have_n = false;
-#endif
 #pragma unroll
                     for (int k = 0; k < NW; k++) sh[k] = rd_lds[k][threadIdx.x];
                     next = M_PROBE;
@@ -803,16 +780,9 @@ __global__ void __launch_bounds__(NREAD_TPB) k_copmem_match_n(const NReadArgs a)
 // ----------------------------------------------------------------------------- one query over both strands
 // (the kernel: dualkern.h)
 
-#ifdef PGRC_AB_DUAL
-int pgrc_copmem_match_dual_r04(pgrc_match_ctx *c);    // tools/variants/dual_r04.hip: round 4's kernel, for in-context A/B runs
-#include "../../tools/variants/dualkern_r05a.h"       // round 5's kernel before the VALU diet (PGRC_DUAL_VARIANT=5)
-#endif
-#ifndef DUAL_WAVES
-#define DUAL_WAVES 6             // waves per SIMD the dual kernel is built for at read lengths up to 160 (NW <= 10)
-#endif
-
-template <int NW, int WAVES>
-static void launch_dual_w(pgrc_match_ctx *c, const DualArgs &a) {
+template <int NW>
+static void launch_dual(pgrc_match_ctx *c, const DualArgs &a) {
+    constexpr int WAVES = NW <= 10 ? 6 : 4;    // waves per SIMD the kernel is built for: six at read lengths up to 160
     const uint64_t want = (a.n + MATCH_TPB - 1) / MATCH_TPB;
     // A persistent grid: more blocks than fit (six per CU at 150 bp) simply queue.
     const uint32_t per_cu = 8u;
@@ -828,26 +798,9 @@ static void launch_dual_w(pgrc_match_ctx *c, const DualArgs &a) {
     }
 }
 
-template <int NW>
-static void launch_dual(pgrc_match_ctx *c, const DualArgs &a) {
-#ifdef PGRC_AB_DUAL
-    // A/B builds carry round 5's first kernel too (PGRC_DUAL_VARIANT=5) -- 100 / 150 bp reads, K = 28, 32-bit positions only
-    if (c->opt.dual_variant == 5 && (NW == 7 || NW == 10) && a.K == 28 && !(c->G + 256 >= (1ull << 32) || c->opt.force_pos64)) {
-        const uint64_t want = (a.n + MATCH_TPB - 1) / MATCH_TPB;
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)c->num_cus * 8u);
-        hipLaunchKernelGGL((k_copmem_match_dual_r05a<(NW == 7 || NW == 10) ? NW : 10, 7, false, 6>), dim3(grid), dim3(MATCH_TPB), 0, c->stream, a);
-        return;
-    }
-#endif
-    launch_dual_w<NW, (NW <= 10 ? DUAL_WAVES : 4)>(c, a);
-}
-
 // The dual kernel over all reads without N: the ACTIVE index set must describe the RC strand, the alternate set the
 // forward strand (api.hip builds them in that order).  The reads with N follow in two ordinary passes (phase 4).
 int pgrc_copmem_match_dual(pgrc_match_ctx *c) {
-#ifdef PGRC_AB_DUAL
-    if (c->opt.dual_variant == 4) return pgrc_copmem_match_dual_r04(c);
-#endif
     const uint64_t lo = std::min<uint64_t>(c->range_lo, c->n), rn = std::min<uint64_t>(c->n - lo, c->range_n);   // (a block of a streamed run, or everything)
     if (rn == 0) return PGRC_OK;
     if (c->index_strand != 1 || c->alt_index_strand != 0 || !c->ent_ptr || !c->alt_ent_ptr || !c->d_scr_pos.p || c->head_sh != c->alt_head_sh) {

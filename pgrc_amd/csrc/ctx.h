@@ -67,7 +67,6 @@ struct PgrcOptions {
     uint64_t seed_segment = 0;
     uint64_t mem_event_cap = 0;     // PGRC_MEM_EVENT_CAP: first guess of the Pg-vs-Pg matcher's event buffer (tests; 0 = default)
     int allgather = 0;              // PGRC_ALLGATHER    multi-device contexts: 0 by device list, 1 "rccl", 2 "copy" (tests)
-    int dual_variant = -1;          // PGRC_DUAL_VARIANT which build of the dual kernel runs (A/B builds only; -1 = default)
 };
 PgrcOptions pgrc_options_from_env();
 bool pgrc_pack_ascii_host(const uint8_t *src, uint64_t count, uint32_t *dst, uint32_t threads);   // api.hip: ASCII ACGT -> 2-bit words, false = a symbol outside ACGT

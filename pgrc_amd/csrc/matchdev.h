@@ -1,4 +1,4 @@
-// matchdev.h -- device-side pieces shared by the match kernels of mode c (copmem.hip; the A/B builds under tools/variants/).
+// matchdev.h -- device-side pieces shared by the match kernels of mode c (copmem.hip, dualkern.h).
 #pragma once
 
 #include <type_traits>

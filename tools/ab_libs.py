@@ -4,8 +4,8 @@ loaded into the SAME process (one copy of the package per library), all contexts
 HBM, and the variants run interleaved.
 CAUTION: every context has its own index and result buffers, and the match kernel's time depends on where they were
 allocated (up to 13 % between contexts of ONE library: DESIGN.md section 9).  Give every variant several contexts
-(x=base y=base u=w7 v=w7) and compare the fastest of each -- or use a run-time knob in one context (tools/ab_match.py).
-usage: tools/ab_libs.py [--workload C3] [--rounds 6] base w7 a=base b=base ...   ("name=variant": a second context)"""
+(x=base y=base u=vc2 v=vc2) and compare the fastest of each -- or use a run-time knob in one context (tools/ab_match.py).
+usage: tools/ab_libs.py [--workload C3] [--rounds 6] base vc2 a=base b=base ...   ("name=variant": a second context)"""
 import argparse, importlib.util, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
