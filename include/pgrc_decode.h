@@ -16,7 +16,8 @@
  * Here the host hands over the joined text and the reassembled per-entry streams of every list (entropy decoding and
  * archive parsing stay with the caller); positions and mismatch list starts are prefix scans on the device, every row
  * is an independent job of a row kernel that assembles tiles of rows in LDS, and rows come back to the host in chunks
- * copied down while the next chunk is made.
+ * copied down while the next chunk is made.  Two more of the decoder's stages follow further down: the restore of the matched
+ * pseudogenomes and the pair-position coding of the order-preserving paired mode (with its encoder).
  *
  * Same conventions as pgrc_match.h: 0 = success, PGRC_E_* otherwise; host buffers stay the caller's (nothing is
  * borrowed beyond a call); no CPU fallback -- without a HIP device every call fails.
@@ -150,6 +151,77 @@ typedef struct {
 } pgrc_decode_restore_timing;
 /* of the last successful pgrc_decode_set_mapped_text */
 int pgrc_decode_get_restore_timing(pgrc_decode_ctx *ctx, pgrc_decode_restore_timing *out);
+
+/* ---- The pair-position coding of the order-preserving paired mode (SeparatedPseudoGenomePersistence::
+ * compressReadsPgPositions, SeparatedPseudoGenomePersistence.cpp:445-574, and decompressReadsPgPositions, :582-673; not
+ * singleFileMode, delta coding on, i.e. archives of version >= 1.3).  T = readsTotalCount (even) reads are P = T/2 pairs;
+ * positions are W = pos_width bytes wide (4 iff the joined Pg length <= UINT32_MAX, pgrc-decoder.cpp:805).
+ *
+ * The base read's position of every pair goes out as it is, in PAIR order.  The pairs are then ranked by base position
+ * (stable: ties by pair number) and every mate is coded in RANK order, with rel = |mate - base| in W bytes:
+ *   near   rel <= 65535: off16_flag 1, a base-first flag (base < mate, strictly) and rel as uint16
+ *   far    otherwise: off16_flag 0 and a delta16_flag --
+ *     delta  rel - refPrev fits int16: delta16_flag 1, a base-first flag, the difference; refPrev = rel
+ *     full   otherwise: delta16_flag 0 and the mate's position itself; refPrev = rel, unless the far pair before this one
+ *            was a delta pair: then refPrev stays (:521)
+ * refPrev starts as 0.  The three scalars of the reference's serial loop are a three-state machine over the far pairs (the
+ * pair before was a delta pair / a full pair that kept refPrev / a full pair that set it): the encoder finds
+ * every pair's state with one scan of state maps, the decoder refPrev with one segmented sum, and everything else is
+ * prefix scans of the flags, all on the device; the rank order is radix.hip's stable sort.
+ *
+ * All three calls work on a decode context (its stream, staging buffers and error string) and need no text.  P is limited
+ * to the radix sort's record count (below 0xFFFFF000 pairs). */
+typedef struct {
+    uint32_t struct_size;           /* sizeof(pgrc_pairpos_streams) */
+    uint32_t pos_width;             /* W: 4 or 8 */
+    uint64_t n_total;               /* T: readsTotalCount, even */
+    const void *base_pos;           /* basePairPos: T/2 positions of W bytes, pair order */
+    const uint8_t *off16_flag;      /* offsetInUint16Flag: T/2 flags, rank order (1 = near) */
+    const uint8_t *off_base_first;  /* offsetIsBaseFirstFlag: n_off16 */
+    const uint16_t *off_value;      /* offsetInUint16Value: n_off16 */
+    const uint8_t *delta16_flag;    /* deltaInInt16Flag: n_delta_flag, one per far pair (non-zero = delta) */
+    const uint8_t *delta_base_first;/* deltaIsBaseFirstFlag: n_delta16 */
+    const int16_t *delta_value;     /* deltaInInt16Value: n_delta16 */
+    const void *not_base_pos;       /* notBasePairPos: n_not_base positions of W bytes */
+    uint64_t n_off16, n_delta_flag, n_delta16, n_not_base;     /* elements of the variable-length streams (off_base_first
+                                                                * and off_value share n_off16, delta_base_first and
+                                                                * delta_value n_delta16) */
+} pgrc_pairpos_streams;
+
+/* compressReadsPgPositions: org_idx_to_pos holds T positions with the mates INTERLEAVED ([2p] = the base read of pair p,
+ * [2p+1] its mate), as the reference's encoder has them.  On success *out describes the eight streams in ONE block of
+ * page-locked host memory that the library allocated (it starts at out->base_pos) and pgrc_pairpos_free gives back.
+ * PGRC_E_PARAM: odd n_total, pos_width not 4 or 8, a position >= 2^32 with pos_width 4, too many pairs. */
+int pgrc_pairpos_encode(pgrc_decode_ctx *ctx, const uint64_t *org_idx_to_pos, uint64_t n_total, uint32_t pos_width,
+                        pgrc_pairpos_streams *out);
+void pgrc_pairpos_free(pgrc_pairpos_streams *streams);   /* of pgrc_pairpos_encode only; clears the struct */
+
+/* decompressReadsPgPositions: the positions as T uint64, FILE-MAJOR ([p] = the base read of pair p, [T/2 + p] its mate --
+ * the layout of pgrc_decode_order.org_idx_to_pos with paired = 1), each truncated to W bytes as the reference's store
+ * does.  PGRC_E_PARAM (the reference reads past its vectors in these cases): odd n_total, pos_width not 4 or 8, a NULL
+ * stream with a non-zero count, ones in off16_flag != n_off16, its other flags != n_delta_flag, non-zero flags in
+ * delta16_flag != n_delta16, its zeros != n_not_base, too many pairs. */
+int pgrc_pairpos_decode(pgrc_decode_ctx *ctx, const pgrc_pairpos_streams *streams, uint64_t *pg_pos);
+
+/* What pgrc_decode_set_order does for mode = PGRC_DECODE_ORD, paired = 1, with the positions decoded on the device
+ * straight into the context's order: the array never exists on the host.  Every check of pgrc_decode_set_order runs on
+ * the decoded positions; after any failure the context has no order. */
+int pgrc_decode_set_order_pair_streams(pgrc_decode_ctx *ctx, const pgrc_pairpos_streams *streams, int32_t rev_compl_pair_file);
+
+typedef struct {
+    uint32_t struct_size;           /* sizeof(pgrc_pairpos_timing) */
+    int32_t encode;                 /* 1 = the last call was pgrc_pairpos_encode, 0 = a decode */
+    float ms_upload;                /* host wall time until the input was queued for the device */
+    float ms_sort_device;           /* device time: records and the rank order (radix sort) */
+    float ms_scan_device;           /* device time: classification, the flag scans and the chain */
+    float ms_scatter_device;        /* device time: compaction of the streams (encode) / the mates' scatter (decode) */
+    float ms_download;              /* host wall time of the copy down (encode, pgrc_pairpos_decode) */
+    float ms_call;                  /* host wall time of the whole call (of set_order_pair_streams: its checks included) */
+    uint64_t bytes_up, bytes_down;
+    uint64_t n_near, n_delta, n_full;   /* pairs by kind */
+} pgrc_pairpos_timing;
+/* of the context's last successful pair-position call */
+int pgrc_pairpos_get_timing(pgrc_decode_ctx *ctx, pgrc_pairpos_timing *out);
 
 #ifdef __cplusplus
 }

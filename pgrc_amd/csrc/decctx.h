@@ -1,5 +1,5 @@
-// decctx.h -- the decode context of include/pgrc_decode.h and the helpers its two sources share: decode.hip (the reads
-// rebuild) and restore.hip (the restore of the matched pseudogenomes).
+// decctx.h -- the decode context of include/pgrc_decode.h and the helpers its sources share: decode.hip (the reads
+// rebuild), restore.hip (the restore of the matched pseudogenomes) and pairpos.hip (the pair positions of the paired ORD mode).
 #pragma once
 
 #include <string.h>
@@ -48,8 +48,23 @@ struct pgrc_decode_ctx {
     uint64_t part_len[3] = {};
     DecBuf rs_mapped, rs_marks, rs_vals, rs_ptr, rs_bsum;   // the mapped parts and streams; per-mark arrays; values; pointers; block counts
     pgrc_decode_restore_timing rtm{};
+    // the pair-position coding (pairpos.hip): the uploaded input, the sort's records (and values, W = 8) in turn, per-rank
+    // and per-far-pair arrays, the device-side output, scan scratch; radix.hip's sort runs on a private match-context
+    // shell that borrows this context's stream (pp_mc, made on first use), with pp_sort as its scratch
+    DecBuf pp_in, pp_rec[2], pp_val[2], pp_rank, pp_far, pp_out, pp_bsum;
+    pgrc_match_ctx *pp_mc = nullptr;
+    DevBuf pp_sort;
+    hipEvent_t pp_ev[6]{};
+    bool have_pp_timing = false;
+    pgrc_pairpos_timing ptm{};
     std::string err;
 };
+
+// pairpos.hip: the file-major positions of `s` as n_total u64 at d_out (device, on d->stream; synchronised on return);
+// fills d->ptm but for ms_download / ms_call
+int pgrc_pairpos_decode_device(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint64_t *d_out);
+int pgrc_pairpos_check_streams(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s);   // the checks that need no device (PGRC_E_PARAM)
+void pgrc_pairpos_release(pgrc_decode_ctx *d);     // the buffers, events and shell above (pgrc_decode_destroy)
 
 #define DEC_TRY(d, expr)                                                                     \
     do {                                                                                     \

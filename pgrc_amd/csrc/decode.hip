@@ -355,6 +355,7 @@ void pgrc_decode_destroy(pgrc_decode_ctx *d) {
     }
     if (d->ev_a) (void)hipEventDestroy(d->ev_a);
     if (d->ev_b) (void)hipEventDestroy(d->ev_b);
+    pgrc_pairpos_release(d);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     delete d;
@@ -483,6 +484,23 @@ static uint64_t dec_entries(const pgrc_decode_ctx *d) {
     return t;
 }
 
+// ORD: the checks of the T positions in d->org2pos (windows inside the text) and the ranks of the HQ rows
+static int dec_ord_checks(pgrc_decode_ctx *d, uint64_t T) {
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((T + 255) / 256, 4096));
+    const uint64_t hq_len = d->nl > 1 ? d->lst[1].text_base : d->text_len;
+    int e;
+    if (T) {
+        if (d->text_len < d->L) DEC_TRY(d, hipMemsetAsync(d->flag.p, DEC_F_WINDOW, 1, d->stream));
+        else hipLaunchKernelGGL(k_dec_check_windows, dim3(grid), dim3(256), 0, d->stream, (const uint64_t *)d->org2pos.p, T, d->text_len - d->L, (uint32_t *)d->flag.p);
+    }
+    if ((e = dec_scan<false>(d, XfBelow{(const uint64_t *)d->org2pos.p, hq_len}, T, 0, (uint64_t *)d->rank.p))) return e;
+    uint64_t hq_rows = 0;
+    DEC_TRY(d, hipMemcpyAsync(&hq_rows, (uint64_t *)d->rank.p + T, 8, hipMemcpyDeviceToHost, d->stream));
+    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    if (hq_rows > d->lst[0].n) return dec_fail(d, PGRC_E_PARAM, "ORD order: more rows below hqPgLen than HQ entries");
+    return PGRC_OK;
+}
+
 int pgrc_decode_set_order(pgrc_decode_ctx *d, const pgrc_decode_order *o) {
     if (!d) return PGRC_E_PARAM;
     if (!o || o->struct_size != sizeof(pgrc_decode_order)) return dec_fail(d, PGRC_E_PARAM, "order is NULL or struct_size is not sizeof(pgrc_decode_order)");
@@ -504,18 +522,9 @@ int pgrc_decode_set_order(pgrc_decode_ctx *d, const pgrc_decode_order *o) {
         if (T) hipLaunchKernelGGL(k_dec_check_index, dim3(grid), dim3(256), 0, d->stream, (const uint32_t *)d->rl_order.p, T, dec_entries(d), (uint32_t *)d->flag.p);
     } else if (o->mode == PGRC_DECODE_ORD) {
         if (!o->org_idx_to_pos && T) return dec_fail(d, PGRC_E_PARAM, "ORD order without org_idx_to_pos");
-        const uint64_t hq_len = d->nl > 1 ? d->lst[1].text_base : d->text_len;
         if ((e = dec_buf(d, d->org2pos, T * 8)) || (e = dec_buf(d, d->rank, (T + 1) * 8))) return e;
         if ((e = dec_upload(d, d->org2pos.p, o->org_idx_to_pos, T * 8))) return e;
-        if (T) {
-            if (d->text_len < d->L) DEC_TRY(d, hipMemsetAsync(d->flag.p, DEC_F_WINDOW, 1, d->stream));
-            else hipLaunchKernelGGL(k_dec_check_windows, dim3(grid), dim3(256), 0, d->stream, (const uint64_t *)d->org2pos.p, T, d->text_len - d->L, (uint32_t *)d->flag.p);
-        }
-        if ((e = dec_scan<false>(d, XfBelow{(const uint64_t *)d->org2pos.p, hq_len}, T, 0, (uint64_t *)d->rank.p))) return e;
-        uint64_t hq_rows = 0;
-        DEC_TRY(d, hipMemcpyAsync(&hq_rows, (uint64_t *)d->rank.p + T, 8, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
-        if (hq_rows > d->lst[0].n) return dec_fail(d, PGRC_E_PARAM, "ORD order: more rows below hqPgLen than HQ entries");
+        if ((e = dec_ord_checks(d, T))) return e;
     } else {
         return dec_fail(d, PGRC_E_PARAM, "unknown order mode");
     }
@@ -527,6 +536,39 @@ int pgrc_decode_set_order(pgrc_decode_ctx *d, const pgrc_decode_order *o) {
     d->ord.rl_idx_order = nullptr;
     d->ord.org_idx_to_pos = nullptr;
     d->have_order = true;
+    return PGRC_OK;
+}
+
+// The paired ORD order from the archive's own streams: the positions are decoded on the device (pairpos.hip) into org2pos
+int pgrc_decode_set_order_pair_streams(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, int32_t rev_compl_pair_file) {
+    if (!d) return PGRC_E_PARAM;
+    d->have_order = false;
+    int e;
+    if ((e = pgrc_pairpos_check_streams(d, s))) return e;
+    if (!d->nl) return dec_fail(d, PGRC_E_STATE, "set_order_pair_streams before add_list");
+    PGRC_ON_DEVICE(d);
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t T = s->n_total;
+    if ((e = dec_buf(d, d->org2pos, T * 8)) || (e = dec_buf(d, d->rank, (T + 1) * 8))) return e;
+    if ((e = pgrc_pairpos_decode_device(d, s, (uint64_t *)d->org2pos.p))) return e;
+    if ((e = dec_clear_err(d))) return e;
+    DEC_TRY(d, hipEventRecord(d->ev_a, d->stream));
+    if ((e = dec_ord_checks(d, T))) return e;
+    DEC_TRY(d, hipGetLastError());
+    DEC_TRY(d, hipEventRecord(d->ev_b, d->stream));
+    if ((e = dec_check_err(d, "set_order_pair_streams"))) return e;
+    d->tm.ms_order_device = dec_elapsed(d->ev_a, d->ev_b);
+    d->ord = pgrc_decode_order{};
+    d->ord.struct_size = sizeof(pgrc_decode_order);
+    d->ord.mode = PGRC_DECODE_ORD;
+    d->ord.n_total = T;
+    d->ord.paired = 1;
+    d->ord.rev_compl_pair_file = rev_compl_pair_file;
+    d->have_order = true;
+    d->ptm.ms_download = 0;
+    d->ptm.bytes_down = 0;
+    d->ptm.ms_call = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    d->have_pp_timing = true;
     return PGRC_OK;
 }
 

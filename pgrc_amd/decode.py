@@ -45,6 +45,20 @@ class RestoreTiming(C.Structure):   # pgrc_decode_restore_timing
                 ("passes", C.c_uint32), ("marks", C.c_uint64 * 3), ("matched", C.c_uint64 * 3)]
 
 
+class PairPosStreams(C.Structure):  # pgrc_pairpos_streams
+    _fields_ = [("struct_size", C.c_uint32), ("pos_width", C.c_uint32), ("n_total", C.c_uint64), ("base_pos", _P),
+                ("off16_flag", _P), ("off_base_first", _P), ("off_value", _P), ("delta16_flag", _P),
+                ("delta_base_first", _P), ("delta_value", _P), ("not_base_pos", _P), ("n_off16", C.c_uint64),
+                ("n_delta_flag", C.c_uint64), ("n_delta16", C.c_uint64), ("n_not_base", C.c_uint64)]
+
+
+class PairPosTiming(C.Structure):   # pgrc_pairpos_timing
+    _fields_ = [("struct_size", C.c_uint32), ("encode", C.c_int32), ("ms_upload", C.c_float),
+                ("ms_sort_device", C.c_float), ("ms_scan_device", C.c_float), ("ms_scatter_device", C.c_float),
+                ("ms_download", C.c_float), ("ms_call", C.c_float), ("bytes_up", C.c_uint64),
+                ("bytes_down", C.c_uint64), ("n_near", C.c_uint64), ("n_delta", C.c_uint64), ("n_full", C.c_uint64)]
+
+
 # include/pgrc_decode.h (kept apart from _lib._PROTOS, which mirrors pgrc_match.h / pgrc_mem.h / pgrc_reads.h)
 DECODE_PROTOS = [
     ("pgrc_decode_create", C.c_int, [C.c_uint32, C.c_int32, C.POINTER(_P)]),
@@ -61,6 +75,11 @@ DECODE_PROTOS = [
     ("pgrc_decode_text_lengths", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("pgrc_decode_get_text", C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
     ("pgrc_decode_get_restore_timing", C.c_int, [_P, C.POINTER(RestoreTiming)]),
+    ("pgrc_pairpos_encode", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.POINTER(PairPosStreams)]),
+    ("pgrc_pairpos_free", None, [C.POINTER(PairPosStreams)]),
+    ("pgrc_pairpos_decode", C.c_int, [_P, C.POINTER(PairPosStreams), _P]),
+    ("pgrc_decode_set_order_pair_streams", C.c_int, [_P, C.POINTER(PairPosStreams), C.c_int32]),
+    ("pgrc_pairpos_get_timing", C.c_int, [_P, C.POINTER(PairPosTiming)]),
 ]
 for _name, _res, _args in DECODE_PROTOS:
     _fn = getattr(lib, _name)
@@ -85,6 +104,33 @@ def _bytes(a) -> np.ndarray:
     if isinstance(a, (bytes, bytearray, memoryview)):
         return np.frombuffer(a, dtype=np.uint8)
     return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+
+# the eight streams of the pair-position coding, in the archive's order, with their element types (the two position
+# streams are uint32 or uint64 by pos_width)
+PAIRPOS_STREAMS = (("base_pos", None), ("off16_flag", np.uint8), ("off_base_first", np.uint8), ("off_value", np.uint16),
+                   ("delta16_flag", np.uint8), ("delta_base_first", np.uint8), ("delta_value", np.int16),
+                   ("not_base_pos", None))
+
+
+def _pairpos_struct(streams: dict):
+    """the dict compressReadsPgPositions returns (stream name -> array, plus n_total and pos_width) as a
+    pgrc_pairpos_streams; the counts are the arrays' sizes.  -> (struct, the arrays it points into)"""
+    w = int(streams["pos_width"])
+    s = PairPosStreams()
+    s.struct_size = C.sizeof(PairPosStreams)
+    s.pos_width = w
+    s.n_total = int(streams["n_total"])
+    keep = []
+    for name, dt in PAIRPOS_STREAMS:
+        a = np.ascontiguousarray(streams[name], dtype=dt if dt is not None else (np.uint64 if w == 8 else np.uint32))
+        keep.append(a)
+        setattr(s, name, _ptr(a) if a.size else None)
+    s.n_off16 = int(streams.get("n_off16", keep[2].size))
+    s.n_delta_flag = int(streams.get("n_delta_flag", keep[4].size))
+    s.n_delta16 = int(streams.get("n_delta16", keep[5].size))
+    s.n_not_base = int(streams.get("n_not_base", keep[7].size))
+    return s, keep
 
 
 class PgRCDecoder:
@@ -205,6 +251,47 @@ class PgRCDecoder:
         o.rev_compl_pair_file = int(bool(rev_compl_pair_file))
         self._ck(lib.pgrc_decode_set_order(self._h, C.byref(o)))
 
+    def set_order_pair_streams(self, streams: dict, rev_compl_pair_file: bool = False) -> None:
+        """the paired ORD order from the archive's pair-position streams (a dict as compressReadsPgPositions returns):
+        the positions are decoded on the device into the context's order and never exist on the host"""
+        s, keep = _pairpos_struct(streams)
+        self._ck(lib.pgrc_decode_set_order_pair_streams(self._h, C.byref(s), int(bool(rev_compl_pair_file))))
+
+    def decompressReadsPgPositions(self, streams: dict) -> np.ndarray:
+        """SeparatedPseudoGenomePersistence::decompressReadsPgPositions (:582-673) on the device: the positions as
+        n_total uint64, file-major ([p] the base read of pair p, [n_total/2 + p] its mate)"""
+        s, keep = _pairpos_struct(streams)
+        out = np.empty(int(s.n_total), dtype=np.uint64)
+        self._ck(lib.pgrc_pairpos_decode(self._h, C.byref(s), _ptr(out)))
+        return out
+
+    def compressReadsPgPositions(self, org_idx_to_pos, pos_width: int) -> dict:
+        """SeparatedPseudoGenomePersistence::compressReadsPgPositions (:445-574) on the device: org_idx_to_pos holds
+        the mates interleaved ([2p] the base read of pair p, [2p+1] its mate); -> the eight streams by name (copies),
+        n_total and pos_width"""
+        op = np.ascontiguousarray(org_idx_to_pos, dtype=np.uint64)
+        s = PairPosStreams()
+        self._ck(lib.pgrc_pairpos_encode(self._h, _ptr(op), op.size, int(pos_width), C.byref(s)))
+        try:
+            cnt = {"base_pos": op.size // 2, "off16_flag": op.size // 2, "off_base_first": s.n_off16,
+                   "off_value": s.n_off16, "delta16_flag": s.n_delta_flag, "delta_base_first": s.n_delta16,
+                   "delta_value": s.n_delta16, "not_base_pos": s.n_not_base}
+            out = {"n_total": op.size, "pos_width": int(pos_width)}
+            for name, dt in PAIRPOS_STREAMS:
+                dt = np.dtype(dt if dt is not None else (np.uint64 if pos_width == 8 else np.uint32))
+                n = int(cnt[name])
+                out[name] = (np.frombuffer((C.c_uint8 * (n * dt.itemsize)).from_address(getattr(s, name)), dtype=dt).copy()
+                             if n else np.zeros(0, dt))
+        finally:
+            lib.pgrc_pairpos_free(C.byref(s))
+        return out
+
+    def pairpos_timing(self) -> dict:
+        t = PairPosTiming()
+        t.struct_size = C.sizeof(PairPosTiming)
+        self._ck(lib.pgrc_pairpos_get_timing(self._h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_ if k != "struct_size"}
+
     def row_count(self, file: int = 0) -> int:
         n = C.c_uint64(0)
         self._ck(lib.pgrc_decode_row_count(self._h, int(file), C.byref(n)))
@@ -260,3 +347,21 @@ class PgRCDecoder:
             self.close()
         except Exception:
             pass
+
+
+def compressReadsPgPositions(org_idx_to_pos, pos_width: int, device: int = -1) -> dict:
+    """PgRCDecoder.compressReadsPgPositions on a context of its own"""
+    dec = PgRCDecoder(1, device)
+    try:
+        return dec.compressReadsPgPositions(org_idx_to_pos, pos_width)
+    finally:
+        dec.close()
+
+
+def decompressReadsPgPositions(streams: dict, device: int = -1) -> np.ndarray:
+    """PgRCDecoder.decompressReadsPgPositions on a context of its own"""
+    dec = PgRCDecoder(1, device)
+    try:
+        return dec.decompressReadsPgPositions(streams)
+    finally:
+        dec.close()
