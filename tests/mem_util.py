@@ -95,3 +95,21 @@ def mem_sweep_texts(seed, target):
         other[:target + 10] = orc.revcomp_ascii(src[-(target + 10):])
         other[-(target + 10):] = src[:target + 10]
     return src, other
+
+
+# ---- a destination made of the far end of a long source (tests/test_gpu_fullsize.py, tests/mem_scale.py --cases above4g)
+
+def stretches_of_source(src, lo, seed=7, count=40):
+    """a short text assembled from `count` stretches of src[lo:] (40-100 kbp each, a substitution every ~700 symbols, every
+    other stretch reverse-complemented), random spacers of up to 300 symbols between them"""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for k in range(count):
+        ln = int(rng.integers(40_000, 100_000))
+        s = int(rng.integers(lo, src.size - ln))
+        seg = src[s:s + ln].copy()
+        at = rng.integers(0, ln, size=ln // 700)
+        seg[at] = ACGT[(np.searchsorted(ACGT, seg[at]) + 1) % 4]
+        parts.append(orc.revcomp_ascii(seg) if k % 2 else seg)
+        parts.append(ACGT[rng.integers(0, 4, size=int(rng.integers(0, 300)))])
+    return np.concatenate(parts)

@@ -6,13 +6,17 @@ against the reference (serial canonical index, whole pseudogenome) -- or the ora
   C4  100 M x 150 bp PE, reads in 8 shards, the packed Pg assembled from 8 slices    test_c4_full_size_eight_shards
   C5  one GPU's 1/8 of 500 M x 250 bp, k <= 5, Pg 3.1 Gbp (hash 2^30)               test_c5_shard_full_size
   P64 Pg of 4.4 Gbp: the 64-bit-position kernels at a real >= 4 Gi text             test_p64_full_size
+      ... the export of that run's matches and Pg-vs-Pg matching over the same text  test_p64_export_after_the_run,
+                                                                                     test_p64_pg_vs_pg_matching
 and row f2 (Pg-vs-Pg) at the C3 Pg size."""
 import numpy as np
 import pytest
 import torch
 
+import export_util as xu
+import mem_util
 import oracle as orc
-from pgrc_amd import MatchContext, synth
+from pgrc_amd import CopMEMMatcher, MatchContext, synth
 from util import revcomp
 
 pytestmark = pytest.mark.gpu
@@ -255,14 +259,17 @@ def test_c4_full_size_eight_shards(c3world):
     assert end == n and np.array_equal(total_hist, hist)
 
 
-def _full_size_run(n, L, G, seed_len, kmax, sample, also_mode=None):
-    """inputs generated in HBM, one run over all n reads, properties, and the first `sample` reads against the checker
-    on the whole text"""
-    g = synth.pg_params(G, seed=12345)
+def _full_size_run(n, L, G, seed_len, kmax, sample, also_mode=None, world=None):
+    """inputs generated in HBM (the text: that of `world`, if one is given), one run over all n reads, properties, and the
+    first `sample` reads against the checker on the whole text"""
     rs = synth.reads_params(n, L, seed=12345)
     nw, stride, pgw = (L + 15) // 16, (n + 63) & ~63, (G + 15) // 16
-    d_pg = torch.zeros(pgw + 64, dtype=torch.int32, device="cuda")
-    synth.pg_device(g, d_pg.data_ptr())
+    if world is None:
+        g = synth.pg_params(G, seed=12345)
+        d_pg = torch.zeros(pgw + 64, dtype=torch.int32, device="cuda")
+        synth.pg_device(g, d_pg.data_ptr())
+    else:
+        g, d_pg = world.g, world.d_pg
     d_rd = torch.empty(nw * stride, dtype=torch.int32, device="cuda")
     synth.reads_device(g, d_pg.data_ptr(), rs, 0, n, d_rd.data_ptr(), stride)
     torch.cuda.synchronize()
@@ -274,7 +281,7 @@ def _full_size_run(n, L, G, seed_len, kmax, sample, also_mode=None):
     pos, rc, mism, hist, matched = ctx.get_results()
     _bookkeeping(n, G, L, kmax, pos, rc, mism, hist, matched)
     assert hist[0] >= 0.55 * n and matched >= 0.85 * n
-    pg = _unpack(d_pg.cpu().numpy().view(np.uint32)[:pgw], G)
+    pg = _unpack(d_pg.cpu().numpy().view(np.uint32)[:pgw], G) if world is None else world.pg
     reads = synth.reads_host(g, pg, rs, 0, sample)
     _alignments_are_real(pg, reads, pos[:sample], rc[:sample], mism[:sample])
     # the parity sample: the first reads, a stride over all of them, and a stride over the reads the dual kernel redid in
@@ -299,6 +306,8 @@ def _full_size_run(n, L, G, seed_len, kmax, sample, also_mode=None):
         assert (m2 == 0)[mism == 0].all() and mt2 >= 0.85 * n
         _alignments_are_real(pg, reads, p2[:sample], r2[:sample], m2[:sample])
         assert int((p2[m2 != 255] >= np.uint64(2**32)).sum()) > 100_000
+    if world is not None:
+        world.rc, world.reads = rc, reads              # (the host rows of the first `sample` reads, for the legs after the run)
     return ctx, pos, mism
 
 
@@ -314,12 +323,149 @@ def test_c5_shard_full_size():
     assert ctx.counters()["index_entries"][0] > 600_000_000
 
 
-def test_p64_full_size():
+class _P64World:
+    """The P64 pseudogenome (4.4 Gbp, seed 12345) in HBM and on the host, made once for the P64 tests, and the 50 M-read
+    run over it: made by the first test that asks for it, kept for the legs that consume its results."""
+    n, L, G, seed_len, kmax, sample = 50_000_000, 150, 4_400_000_000, 38, 3, 50_000
+
+    def __init__(self):
+        self.g = synth.pg_params(self.G, seed=12345)
+        pgw = (self.G + 15) // 16
+        self.d_pg = torch.zeros(pgw + 64, dtype=torch.int32, device="cuda")
+        synth.pg_device(self.g, self.d_pg.data_ptr())
+        torch.cuda.synchronize()
+        self.pg = _unpack(self.d_pg.cpu().numpy().view(np.uint32)[:pgw], self.G)
+        self._run = self._failed = None
+
+    def run(self):
+        """-> (ctx, pos, mism) of _full_size_run; self.rc and self.reads (host rows of the first `sample` reads) beside.  A run
+        that failed is not made again for the next test that asks: that test fails with the same error."""
+        if self._failed is not None:
+            raise self._failed
+        if self._run is None:
+            try:
+                self._run = _full_size_run(self.n, self.L, self.G, self.seed_len, self.kmax, self.sample, also_mode="d", world=self)
+            except Exception as e:
+                self._failed = e
+                raise
+        return self._run
+
+
+@pytest.fixture(scope="module")
+def p64world():
+    w = _P64World()
+    yield w
+    w._run = None
+    del w.d_pg
+    torch.cuda.empty_cache()
+
+
+def test_p64_full_size(p64world):
     """A text of 4.4 Gbp (>= 4 Gi symbols): the reference's u64 index branch (CopMEMMatcher.cpp:579-586), here the
     64-bit-position kernels, at a size where positions really leave 32 bits; mode d on the same inputs scans the text in
     two segments."""
-    ctx, pos, mism = _full_size_run(50_000_000, 150, 4_400_000_000, 38, 3, 50_000, also_mode="d")
+    ctx, pos, mism = p64world.run()
     assert int((pos[mism != 255] >= np.uint64(2**32)).sum()) > 100_000
+
+
+def test_p64_export_after_the_run(p64world):
+    """The export of a real run's matches above 2^32 (export.hip over positions the matcher made): the matched reads among
+    the first `sample` reads of the 50 M-read context -- their host rows exist -- in a stable host order against an old
+    list over the whole text (deltas of 150-250, closed at G - L: 22 M entries, half a million of them above 2^32), in
+    both offset widths, and the same reads as a caller-made entry list with fillers; every stream equals the oracle's."""
+    w = p64world
+    ctx, pos, mism = w.run()
+    rc, reads = w.rc, w.reads
+    n, L, G, sample = w.n, w.L, w.G, w.sample
+    rng = np.random.default_rng(64)
+    off = rng.integers(150, 251, size=(G - L) // 195).astype(np.uint8)
+    off[0] = 0
+    lpos = np.cumsum(off, dtype=np.int64)
+    h = int(np.searchsorted(lpos, G - L, side="right"))
+    assert h < off.size
+    off = off[:h]
+    if lpos[h - 1] != G - L:                            # closed: the last entry's read ends where the text ends
+        off = np.append(off, np.uint8(G - L - lpos[h - 1]))
+    h = off.size
+    assert int(off.astype(np.int64).sum()) == G - L
+    # the checker reads rows `order[j]` of the read set only: the first `sample` rows stand for it
+    case = {"pg": w.pg, "reads": reads, "L": L, "list_off": off, "list_org": (n + np.arange(h)).astype(np.uint32),
+            "list_rc": (rng.random(h) < 0.4).astype(np.uint8)}
+    res = {"pos": pos, "rc": rc, "mism": mism}
+    order = xu.stable_order(pos[:sample])
+    assert order.size >= 0.85 * sample
+    above = int((pos[order] >= np.uint64(2**32)).sum())
+    print(f"p64 export: {order.size} matched reads of the first {sample}, {above} of them above 2^32, {h} old entries")
+    for byte_mode in (True, False):
+        want = xu.oracle_export_pg_order(case, res, order, byte_mode=byte_mode, with_read_org=False)
+        got = ctx.export_pg_order(order, off, case["list_org"], case["list_rc"], None, False, byte_mode)
+        for k in xu.STREAMS:
+            assert np.array_equal(got[k], want[k]), ("pg order", byte_mode, k)
+        assert got["last_pos"] == want["last_pos"] == G - L
+        assert got["org_idx"].size == h + order.size
+    # ... as entries: the same reads in a random order, fillers among them
+    er = np.concatenate([order, np.full(500, 0xFFFFFFFF, dtype=np.uint32)])[rng.permutation(order.size + 500)]
+    eo = np.where(er == 0xFFFFFFFF, n + np.arange(er.size), er).astype(np.uint32)
+    for byte_mode in (True, False):
+        want = xu.oracle_export_entries(case, res, er, eo, byte_mode=byte_mode)
+        got = ctx.export_entries(er, eo, False, byte_mode)
+        for k in xu.STREAMS:
+            assert np.array_equal(got[k], want[k]), ("entries", byte_mode, k)
+    assert above > 1000
+
+
+def test_p64_pg_vs_pg_matching(p64world):
+    """Row f2 beyond 4 Gi symbols (the 64-bit branches of mem.hip), over the 4.4 Gbp text as the source.
+    Identity: a destination of 5.6 Mbp that holds 40 stretches of the source above 2^32 on both strands (a substitution every
+    ~700 symbols), dest_is_src = False, in the encoder's combination (reverse-complement matching): the match list equals
+    the checker's -- the compiled reference's matchTexts, else the oracle port -- row for row, and more than
+    1000 of its source positions lie above 2^32.  The checker runs in a thread beside the GPU legs: its C code releases the interpreter lock.
+    Properties: the text against itself (forward); every sampled match -- 2000 of all, 2000 with a source position above
+    2^32 -- is a real, right-maximal exact match of at least 45 symbols.  (Recorded once: 365 541 matches, 16 327 of them
+    above 2^32.)
+    Cost of the checker's call, nearly all of it the serial index build over the 4.4 Gbp source, measured on the test
+    machine's host: the compiled reference 49.5 s -- the whole test then takes 49.5 s, the GPU legs run beside it (the
+    identity match itself 9 ms), against test_p64_full_size's 46.7 s plus 6.3 s for making the text in the same run; the
+    oracle port, used only where the reference is not compiled, 287 s.  Both gave the 4572 matches of the GPU, 3470 of them
+    with a source position above 2^32.  (The forward combination on the same destination: tests/mem_scale.py --cases
+    above4g-fwd.)"""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    G, src = p64world.G, p64world.pg
+    other = mem_util.stretches_of_source(src, 1 << 32)
+    dest = orc.mem_dest(src, np.concatenate([other, orc.revcomp_ascii(other)]), False, True)
+    checker = orc.ref_mem_match if orc.have_ref() else orc.oracle_mem_match
+    if orc.have_ref():
+        orc.ref()                                  # (loaded here, not in the thread)
+
+    def timed():
+        t = time.perf_counter()
+        r = checker(src, dest, False, True)
+        return r, time.perf_counter() - t
+
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        fut = pool.submit(timed)
+        m = CopMEMMatcher(src, 45)
+        got = m.matchTexts(dest, False, True)
+        mt = m.matchTexts(src, True, False)
+        m.close()
+        ps, ln, pd = mt[:, 0].astype(np.int64), mt[:, 1].astype(np.int64), mt[:, 2].astype(np.int64)
+        assert len(mt) > 100000 and ln.min() >= 45 and (pd < ps).all() and (ps + ln).max() <= G
+        assert int(ps.max()) > (1 << 32), "no match beyond 4 Gi: the 64-bit paths were not exercised"
+        rng = np.random.default_rng(2)
+        hi = np.flatnonzero(ps > (1 << 32))
+        print(f"p64 Pg-vs-Pg: {len(mt)} matches, {len(hi)} above 2^32")
+        for k in np.concatenate([rng.choice(len(mt), 2000), rng.choice(hi, min(2000, len(hi)))]):
+            a, b, n = ps[k], pd[k], ln[k]
+            assert np.array_equal(src[a:a + n], src[b:b + n]), k
+            assert a + n == G or src[a + n] != src[b + n], k
+        want, secs = fut.result()
+    above = int((got[:, 0] >= np.uint64(1 << 32)).sum())
+    print(f"p64 Pg-vs-Pg identity: {len(got)} matches ({len(want)} from {checker.__name__}), {above} with a source position "
+          f"above 2^32, destination {dest.size} symbols, checker {secs:.1f} s")
+    assert np.array_equal(got, want)
+    # 40 stretches of at least 40 kbp on two strands, cut about every 700 symbols: several thousand matches from above 2^32
+    assert above > 1000
 
 
 def test_c1_full_size_exact_matcher():
@@ -349,7 +495,6 @@ def test_pg_vs_pg_matching_full_size_properties(c3world):
     reported match is a real exact match, long enough, not extensible to the right, extensible to the left by at most
     the reference's one symbol at a text start; the self-match filter holds.
     (Identity with the reference at this size: tests/mem_scale.py, profiles/r01_mem_scale_C3.json.)"""
-    from pgrc_amd import CopMEMMatcher
     G = c3world.G
     src = c3world.pg
     m = CopMEMMatcher(src, 45)
