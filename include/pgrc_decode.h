@@ -223,6 +223,78 @@ typedef struct {
 /* of the context's last successful pair-position call */
 int pgrc_pairpos_get_timing(pgrc_decode_ctx *ctx, pgrc_pairpos_timing *out);
 
+/* ---- The pair-order coding of the paired mode that does NOT preserve the order (SeparatedPseudoGenomePersistence::
+ * compressReadsOrder, SeparatedPseudoGenomePersistence.cpp:220-339, called from pgrc-encoder.cpp:223): the encoder's side
+ * only.  The decoder (decompressReadsOrder, :341-443) is a true recurrence -- the k-th pair lands on the k-th entry that no
+ * earlier pair has marked -- and stays with the caller; pgrc_decode_set_order takes its rlIdxOrder.
+ *
+ * T = readsCount (even, below 2^32) entries of the joined reads lists HQ | LQ | N; org[i] is entry i's original index, a
+ * permutation of [0, T); reads 2q and 2q+1 are mates.  With rev[org[i]] = i the mate of entry i is rev[org[i] ^ 1].
+ * Entry i is a BASE iff its mate lies after it; the P = T/2 bases, in entry order, number the pairs.  Pair k with base i
+ * and rel = mate - i >= 1 is
+ *   near   rel <= 255: off8_flag[k] 1 and rel as uint8
+ *   far    otherwise: off8_flag[k] 0 and a delta8_flag --
+ *     delta  rel - refPrev fits int8: delta8_flag 1 and the difference; refPrev = rel
+ *     full   otherwise: delta8_flag 0 and rel as uint32; refPrev = rel, unless the far pair before this one was a delta
+ *            pair: then refPrev stays (:290)
+ * refPrev starts as 0: the chain of the pair-position coding above with int8 for int16, run by the same kernels.
+ *
+ * The forms are the combinations of the reference's (completeOrderInfo, ignorePairOrderInformation, singleFileMode) that
+ * write different streams ("*" = either value): */
+enum {
+    PGRC_PAIRORDER_IGNORE = 0,              /* (false, true, *): the five common streams -- off8_flag, off_value, delta8_flag,
+                                             * delta_value, full_offset -- and nothing else */
+    PGRC_PAIRORDER_FILE_FLAGS = 1,          /* (false, false, *): the five, and the base's file (org[i] & 1) per pair in
+                                             * off_base_file_flag (near pairs) and nonoff_base_file_flag (far pairs) */
+    PGRC_PAIRORDER_COMPLETE = 2,            /* (true, *, false): the five, and pair_base_org_idx[org[i] / 2] = 2k + (org[i] & 1)
+                                             * for the base i of every pair k (revPairBaseOrgIdx) */
+    PGRC_PAIRORDER_COMPLETE_SINGLE_FILE = 3 /* (true, *, true): rev alone, T uint32 */
+};
+
+typedef struct {
+    uint32_t struct_size;           /* sizeof(pgrc_pairorder_streams) */
+    int32_t form;                   /* PGRC_PAIRORDER_* */
+    uint64_t n_total;               /* T: readsCount, even */
+    const uint8_t *off8_flag;       /* offsetInUint8Flag: T/2 flags, pair order (1 = near); the START OF THE BLOCK in every
+                                     * form, also where it holds no element */
+    const uint8_t *off_value;       /* offsetInUint8Value: n_off8 */
+    const uint8_t *delta8_flag;     /* deltaInInt8Flag: n_delta_flag, one per far pair */
+    const int8_t *delta_value;      /* deltaInInt8Value: n_delta8 */
+    const uint32_t *full_offset;    /* fullOffset: n_full */
+    const uint32_t *pair_base_org_idx;      /* revPairBaseOrgIdx: T/2 (COMPLETE; NULL otherwise) */
+    const uint8_t *off_base_file_flag;      /* offsetPairBaseFileFlag: n_off8 (FILE_FLAGS; NULL otherwise) */
+    const uint8_t *nonoff_base_file_flag;   /* nonOffsetPairBaseFileFlag: n_delta_flag (FILE_FLAGS; NULL otherwise) */
+    const uint32_t *rev;            /* T (COMPLETE_SINGLE_FILE; NULL otherwise) */
+    uint64_t n_off8, n_delta_flag, n_delta8, n_full;    /* elements of the variable-length streams (all 0 with
+                                                         * COMPLETE_SINGLE_FILE, where off8_flag holds no element either) */
+} pgrc_pairorder_streams;
+
+/* compressReadsOrder: org_idx[l] holds the n[l] original indexes of list l (HQ, LQ, N) as the lists have them; the joined
+ * array is never made on the host (NULL with n[l] = 0: no such list).  On success *out describes the streams in ONE block
+ * of page-locked host memory that the library allocated (it starts at out->off8_flag) and pgrc_pairorder_free gives back.
+ * PGRC_E_PARAM, where the reference's behaviour is undefined: a total that is odd or 2^32 or more, a value >= T, a
+ * value that occurs twice, an unknown form, a NULL list with a non-zero count.  After any failure *out is cleared and the
+ * context stays usable.  Works on a decode context (its stream, staging buffers and error string) and needs no text. */
+int pgrc_pairorder_encode(pgrc_decode_ctx *ctx, const uint32_t *const org_idx[3], const uint64_t n[3], int32_t form,
+                          pgrc_pairorder_streams *out);
+void pgrc_pairorder_free(pgrc_pairorder_streams *streams);   /* of pgrc_pairorder_encode; clears the struct */
+
+typedef struct {
+    uint32_t struct_size;           /* sizeof(pgrc_pairorder_timing) */
+    int32_t form;
+    float ms_upload;                /* host wall time until the input was queued for the device */
+    float ms_inverse_device;        /* device time: the scatter of rev and the classification (mate, base flag, rel) */
+    float ms_scatter_device;        /* ... of which the scatter alone (with the sentinel fill queued before it) */
+    float ms_scan_device;           /* device time: the three flag scans and the chain (maps, map scan, kinds) */
+    float ms_compact_device;        /* device time: pair order, pair_base_org_idx, the near, far, delta and full streams */
+    float ms_download;              /* host wall time: the page-locked block and the copy down */
+    float ms_call;                  /* host wall time of the whole call */
+    uint64_t bytes_up, bytes_down;
+    uint64_t n_near, n_delta, n_full;   /* pairs by kind (0 with COMPLETE_SINGLE_FILE: no pair is coded) */
+} pgrc_pairorder_timing;
+/* of the context's last successful pgrc_pairorder_encode */
+int pgrc_pairorder_get_timing(pgrc_decode_ctx *ctx, pgrc_pairorder_timing *out);
+
 #ifdef __cplusplus
 }
 #endif

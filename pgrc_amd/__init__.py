@@ -19,4 +19,4 @@ from .matchers import (  # noqa: F401
 from .textmatch import CopMEMMatcher  # noqa: F401
 from .readsets import DividedPCLReadsSets  # noqa: F401
 from . import synth  # noqa: F401
-from .decode import PgRCDecoder, compressReadsPgPositions, decompressReadsPgPositions  # noqa: F401
+from .decode import PgRCDecoder, compressReadsOrder, compressReadsPgPositions, decompressReadsPgPositions  # noqa: F401

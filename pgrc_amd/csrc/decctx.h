@@ -1,5 +1,6 @@
 // decctx.h -- the decode context of include/pgrc_decode.h and the helpers its sources share: decode.hip (the reads
-// rebuild), restore.hip (the restore of the matched pseudogenomes) and pairpos.hip (the pair positions of the paired ORD mode).
+// rebuild), restore.hip (the restore of the matched pseudogenomes), pairpos.hip (the pair positions of the paired ORD mode)
+// and pairorder.hip (the pair order of the paired non-ORD mode).
 #pragma once
 
 #include <string.h>
@@ -57,6 +58,12 @@ struct pgrc_decode_ctx {
     hipEvent_t pp_ev[6]{};
     bool have_pp_timing = false;
     pgrc_pairpos_timing ptm{};
+    // the pair-order coding (pairorder.hip): the joined orgIdx, rev, per-entry and per-pair arrays, the device-side streams,
+    // scan scratch and the two error words
+    DecBuf po_in, po_rev, po_ent, po_pair, po_out, po_bsum;
+    hipEvent_t po_ev[11]{};
+    bool have_po_timing = false;
+    pgrc_pairorder_timing potm{};
     std::string err;
 };
 
@@ -65,6 +72,7 @@ struct pgrc_decode_ctx {
 int pgrc_pairpos_decode_device(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint64_t *d_out);
 int pgrc_pairpos_check_streams(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s);   // the checks that need no device (PGRC_E_PARAM)
 void pgrc_pairpos_release(pgrc_decode_ctx *d);     // the buffers, events and shell above (pgrc_decode_destroy)
+void pgrc_pairorder_release(pgrc_decode_ctx *d);   // pairorder.hip: its buffers and events (pgrc_decode_destroy)
 
 #define DEC_TRY(d, expr)                                                                     \
     do {                                                                                     \

@@ -356,6 +356,7 @@ void pgrc_decode_destroy(pgrc_decode_ctx *d) {
     if (d->ev_a) (void)hipEventDestroy(d->ev_a);
     if (d->ev_b) (void)hipEventDestroy(d->ev_b);
     pgrc_pairpos_release(d);
+    pgrc_pairorder_release(d);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     delete d;

@@ -15,16 +15,9 @@
 //                                  neighbouring values.  Maps compose associatively: scanops.h's scan with PpCompose gives
 //                                  every far pair the map of all pairs before it, hence its state, its kind and its int16.
 // Integer work bound by HBM streams and gathers; no atomics, no library kernel.
-#include <chrono>
+#include "ppchain.h"
 
-#include "decctx.h"
-#include "scanops.h"
-
-#define PP_TPB 256
 #define PP_MAX_PAIRS 0xFFFFF000ull     // rx_sort's record limit
-
-static size_t pp_a16(size_t x) { return (x + 15) & ~(size_t)15; }
-static uint32_t pp_grid(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + PP_TPB - 1) / PP_TPB); }
 
 // ------------------------------------------------------------------------------------------------ records, rank entries
 struct PpBaseOrg {          // encoder: the interleaved array; the mate's position goes into the range check
@@ -309,43 +302,7 @@ static __global__ void __launch_bounds__(PP_TPB) k_pp_enc_compact(uint64_t P, co
     }
 }
 
-// states of the chain: what the far pair before was
-#define PP_S_A 0u           // a delta pair: refPrev = its rel
-#define PP_S_B 1u           // a full pair that kept refPrev = the rel of the pair before it
-#define PP_S_C 2u           // a full pair that set refPrev = its rel (and the start, with rel 0)
-#define PP_MAP_IDENT (PP_S_A | PP_S_B << 2 | PP_S_C << 4)
-
-__device__ __forceinline__ bool pp_fits16(uint64_t x) { return (int64_t)x >= -32768 && (int64_t)x <= 32767; }
-
-struct PpCompose {          // first a, then b
-    __device__ uint32_t operator()(uint32_t a, uint32_t b) const {
-        uint32_t r = 0;
-#pragma unroll
-        for (uint32_t s = 0; s < 3; s++) r |= ((b >> (2u * ((a >> (2u * s)) & 3u))) & 3u) << (2u * s);
-        return r;
-    }
-};
-
-static __global__ void __launch_bounds__(PP_TPB) k_pp_enc_maps(uint64_t nf, const uint64_t *__restrict__ far_rel, uint8_t *__restrict__ map) {
-    const uint64_t k = (uint64_t)blockIdx.x * PP_TPB + threadIdx.x;
-    if (k >= nf) return;
-    const uint64_t r0 = far_rel[k], r1 = k >= 1 ? far_rel[k - 1] : 0, r2 = k >= 2 ? far_rel[k - 2] : 0;
-    const bool d1 = pp_fits16(r0 - r1), d2 = pp_fits16(r0 - r2);
-    map[k] = (uint8_t)((d1 ? PP_S_A : PP_S_B) | (d2 ? PP_S_A : PP_S_C) << 2 | (d1 ? PP_S_A : PP_S_C) << 4);
-}
-
-// pre[k]: the composed map of the far pairs before k; the chain starts in C
-static __global__ void __launch_bounds__(PP_TPB) k_pp_enc_kinds(uint64_t nf, const uint64_t *__restrict__ far_rel, const uint32_t *__restrict__ pre,
-                                                                uint8_t *__restrict__ del_flag, int16_t *__restrict__ dval) {
-    const uint64_t k = (uint64_t)blockIdx.x * PP_TPB + threadIdx.x;
-    if (k >= nf) return;
-    const uint32_t st = (pre[k] >> 4) & 3u;
-    const uint64_t ref = st == PP_S_B ? (k >= 2 ? far_rel[k - 2] : 0) : (k >= 1 ? far_rel[k - 1] : 0);
-    const uint64_t dl = far_rel[k] - ref;
-    del_flag[k] = pp_fits16(dl) ? 1 : 0;
-    dval[k] = (int16_t)dl;
-}
-
+// (the chain itself -- states, maps, PpCompose, k_pp_enc_maps / k_pp_enc_kinds -- is ppchain.h, shared with pairorder.hip)
 template <bool W8>
 __global__ void __launch_bounds__(PP_TPB) k_pp_enc_far(uint64_t nf, const uint32_t *__restrict__ far_rank, const uint64_t *__restrict__ far_rel,
                                                        const uint8_t *__restrict__ del_flag, const uint32_t *__restrict__ del_inc, const int16_t *__restrict__ dval,
@@ -416,8 +373,6 @@ static int pp_sort_buffers(pgrc_decode_ctx *d, bool w8, uint64_t P) {
     }
     return PGRC_OK;
 }
-
-static float pp_ms(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 // device -> host on the context's stream: page-locked memory directly, other memory through the staging buffers
 static int pp_download(pgrc_decode_ctx *d, void *h_dst, const void *d_src, uint64_t bytes) {
@@ -643,9 +598,9 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, uint64_t T, 
     DEC_TRY(d, hipStreamSynchronize(d->stream));
     const uint64_t nf = P - n_near;
     if (nf) {
-        hipLaunchKernelGGL(k_pp_enc_maps, dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint64_t *)far_rel, map);
+        hipLaunchKernelGGL((k_pp_enc_maps<int16_t, uint64_t>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint64_t *)far_rel, map);
         DEC_TRY(d, sco_scan<false>(d->stream, (const uint8_t *)map, pre, nf, ScoIdentity{}, PpCompose{}, PP_MAP_IDENT, sco_tmp));
-        hipLaunchKernelGGL(k_pp_enc_kinds, dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint64_t *)far_rel, (const uint32_t *)pre, del_flag, dval);
+        hipLaunchKernelGGL((k_pp_enc_kinds<int16_t, uint64_t>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint64_t *)far_rel, (const uint32_t *)pre, del_flag, dval);
         DEC_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)del_flag, del_inc, nf, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
         DEC_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }

@@ -59,6 +59,24 @@ class PairPosTiming(C.Structure):   # pgrc_pairpos_timing
                 ("bytes_down", C.c_uint64), ("n_near", C.c_uint64), ("n_delta", C.c_uint64), ("n_full", C.c_uint64)]
 
 
+PGRC_PAIRORDER_IGNORE, PGRC_PAIRORDER_FILE_FLAGS, PGRC_PAIRORDER_COMPLETE, PGRC_PAIRORDER_COMPLETE_SINGLE_FILE = 0, 1, 2, 3
+
+
+class PairOrderStreams(C.Structure):    # pgrc_pairorder_streams
+    _fields_ = [("struct_size", C.c_uint32), ("form", C.c_int32), ("n_total", C.c_uint64), ("off8_flag", _P),
+                ("off_value", _P), ("delta8_flag", _P), ("delta_value", _P), ("full_offset", _P),
+                ("pair_base_org_idx", _P), ("off_base_file_flag", _P), ("nonoff_base_file_flag", _P), ("rev", _P),
+                ("n_off8", C.c_uint64), ("n_delta_flag", C.c_uint64), ("n_delta8", C.c_uint64), ("n_full", C.c_uint64)]
+
+
+class PairOrderTiming(C.Structure):     # pgrc_pairorder_timing
+    _fields_ = [("struct_size", C.c_uint32), ("form", C.c_int32), ("ms_upload", C.c_float),
+                ("ms_inverse_device", C.c_float), ("ms_scatter_device", C.c_float), ("ms_scan_device", C.c_float),
+                ("ms_compact_device", C.c_float),
+                ("ms_download", C.c_float), ("ms_call", C.c_float), ("bytes_up", C.c_uint64),
+                ("bytes_down", C.c_uint64), ("n_near", C.c_uint64), ("n_delta", C.c_uint64), ("n_full", C.c_uint64)]
+
+
 # include/pgrc_decode.h (kept apart from _lib._PROTOS, which mirrors pgrc_match.h / pgrc_mem.h / pgrc_reads.h)
 DECODE_PROTOS = [
     ("pgrc_decode_create", C.c_int, [C.c_uint32, C.c_int32, C.POINTER(_P)]),
@@ -80,6 +98,9 @@ DECODE_PROTOS = [
     ("pgrc_pairpos_decode", C.c_int, [_P, C.POINTER(PairPosStreams), _P]),
     ("pgrc_decode_set_order_pair_streams", C.c_int, [_P, C.POINTER(PairPosStreams), C.c_int32]),
     ("pgrc_pairpos_get_timing", C.c_int, [_P, C.POINTER(PairPosTiming)]),
+    ("pgrc_pairorder_encode", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.c_int32, C.POINTER(PairOrderStreams)]),
+    ("pgrc_pairorder_free", None, [C.POINTER(PairOrderStreams)]),
+    ("pgrc_pairorder_get_timing", C.c_int, [_P, C.POINTER(PairOrderTiming)]),
 ]
 for _name, _res, _args in DECODE_PROTOS:
     _fn = getattr(lib, _name)
@@ -131,6 +152,12 @@ def _pairpos_struct(streams: dict):
     s.n_delta16 = int(streams.get("n_delta16", keep[5].size))
     s.n_not_base = int(streams.get("n_not_base", keep[7].size))
     return s, keep
+
+
+# the streams of the pair-order coding in the struct's order, with their element types
+PAIRORDER_STREAMS = (("off8_flag", np.uint8), ("off_value", np.uint8), ("delta8_flag", np.uint8), ("delta_value", np.int8),
+                     ("full_offset", np.uint32), ("pair_base_org_idx", np.uint32), ("off_base_file_flag", np.uint8),
+                     ("nonoff_base_file_flag", np.uint8), ("rev", np.uint32))
 
 
 class PgRCDecoder:
@@ -292,6 +319,44 @@ class PgRCDecoder:
         self._ck(lib.pgrc_pairpos_get_timing(self._h, C.byref(t)))
         return {k: getattr(t, k) for k, _ in t._fields_ if k != "struct_size"}
 
+    def compressReadsOrder(self, org_idx_parts, form: int) -> dict:
+        """SeparatedPseudoGenomePersistence::compressReadsOrder (:220-339) on the device: org_idx_parts holds the orgIdx
+        arrays of up to three reads lists (HQ, LQ, N; one array: a single list), which are never joined on the host;
+        form is one of PGRC_PAIRORDER_*; -> the form's streams by name (copies; the streams the form does not write
+        are absent), n_total and form"""
+        if isinstance(org_idx_parts, np.ndarray):
+            org_idx_parts = [org_idx_parts]
+        parts = [np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in org_idx_parts]
+        assert len(parts) <= 3
+        ptrs, cnts = (_P * 3)(), (C.c_uint64 * 3)()
+        for l, a in enumerate(parts):
+            ptrs[l], cnts[l] = (a.ctypes.data if a.size else None), a.size
+        s = PairOrderStreams()
+        self._ck(lib.pgrc_pairorder_encode(self._h, ptrs, cnts, int(form), C.byref(s)))
+        try:
+            T = int(s.n_total)
+            coded = form != PGRC_PAIRORDER_COMPLETE_SINGLE_FILE
+            cnt = {"off8_flag": T // 2 if coded else 0, "off_value": s.n_off8, "delta8_flag": s.n_delta_flag,
+                   "delta_value": s.n_delta8, "full_offset": s.n_full, "pair_base_org_idx": T // 2,
+                   "off_base_file_flag": s.n_off8, "nonoff_base_file_flag": s.n_delta_flag, "rev": T}
+            present = (PAIRORDER_STREAMS[:5] if coded else ()) + {PGRC_PAIRORDER_IGNORE: (), PGRC_PAIRORDER_FILE_FLAGS: PAIRORDER_STREAMS[6:8],
+                                                                   PGRC_PAIRORDER_COMPLETE: PAIRORDER_STREAMS[5:6]}.get(form, PAIRORDER_STREAMS[8:])
+            out = {"n_total": T, "form": int(s.form)}
+            for name, dt in present:
+                dt = np.dtype(dt)
+                n = int(cnt[name])
+                out[name] = (np.frombuffer((C.c_uint8 * (n * dt.itemsize)).from_address(getattr(s, name)), dtype=dt).copy()
+                             if n else np.zeros(0, dt))
+        finally:
+            lib.pgrc_pairorder_free(C.byref(s))
+        return out
+
+    def pairorder_timing(self) -> dict:
+        t = PairOrderTiming()
+        t.struct_size = C.sizeof(PairOrderTiming)
+        self._ck(lib.pgrc_pairorder_get_timing(self._h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_ if k != "struct_size"}
+
     def row_count(self, file: int = 0) -> int:
         n = C.c_uint64(0)
         self._ck(lib.pgrc_decode_row_count(self._h, int(file), C.byref(n)))
@@ -363,5 +428,14 @@ def decompressReadsPgPositions(streams: dict, device: int = -1) -> np.ndarray:
     dec = PgRCDecoder(1, device)
     try:
         return dec.decompressReadsPgPositions(streams)
+    finally:
+        dec.close()
+
+
+def compressReadsOrder(org_idx_parts, form: int, device: int = -1) -> dict:
+    """PgRCDecoder.compressReadsOrder on a context of its own"""
+    dec = PgRCDecoder(1, device)
+    try:
+        return dec.compressReadsOrder(org_idx_parts, form)
     finally:
         dec.close()
