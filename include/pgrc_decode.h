@@ -213,8 +213,8 @@ typedef struct {
     int32_t encode;                 /* 1 = the last call was pgrc_pairpos_encode, 0 = a decode */
     float ms_upload;                /* host wall time until the input was queued for the device */
     float ms_sort_device;           /* device time: records and the rank order (radix sort) */
-    float ms_scan_device;           /* device time: classification, the flag scans and the chain */
-    float ms_scatter_device;        /* device time: compaction of the streams (encode) / the mates' scatter (decode) */
+    float ms_scan_device;           /* device time: classification, the flag scans and (encode) the chain */
+    float ms_scatter_device;        /* device time: compaction of the streams (encode) / the chain's scan, whose last pass scatters the mates (decode) */
     float ms_download;              /* host wall time of the copy down (encode, pgrc_pairpos_decode) */
     float ms_call;                  /* host wall time of the whole call (of set_order_pair_streams: its checks included) */
     uint64_t bytes_up, bytes_down;

@@ -124,7 +124,7 @@ int pgrc_copmem_export_index(pgrc_match_ctx *c, uint32_t *h_cumm, uint32_t *h_po
     const uint32_t sgrid = (uint32_t)((hs + 255) / 256 < 65536u * 8u ? (hs + 255) / 256 : 65536u * 8u);
     hipLaunchKernelGGL(k_export_counts, dim3(sgrid), dim3(256), 0, c->stream, (const ulonglong2 *)c->head_ptr, c->head_sh, hs, (uint32_t *)cnt.p);
     // cumm = exclusive scan of the counts (the build's own scan kernels; in place in `cnt`, then copied)
-    if ((e = pgrc_buf_ensure(c, temp, (pgrc_ps_scan_blocks(hs + 2) + 2) * sizeof(uint32_t)))) { cleanup(); return e; }
+    if ((e = pgrc_buf_ensure(c, temp, pgrc_ps_scan_blocks(hs + 2) * sizeof(uint32_t)))) { cleanup(); return e; }
     if ((e = pgrc_ps_scan_u32(c, (uint32_t *)cnt.p, hs + 2, (uint32_t *)temp.p))) { cleanup(); return e; }
     hipError_t he = hipMemcpyAsync(cumm.p, cnt.p, (hs + 2) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
     uint32_t total = 0;

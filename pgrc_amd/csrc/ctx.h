@@ -287,8 +287,9 @@ int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_
 int pgrc_ps_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uint64_t *d_vals, uint32_t hbits, uint32_t cb, uint64_t *d_ent);
 int pgrc_ps_finish_packed(pgrc_match_ctx *c, const uint64_t *d_recs, const uint32_t *d_pstart, uint32_t *d_slow, uint32_t np, uint32_t cb,
                           uint32_t rec_sh, uint64_t *d_ent);
+// the shared scan (scanops.h) in place over u32 counts, exclusive; d_fold: pgrc_ps_scan_blocks(n) words of scratch
 uint64_t pgrc_ps_scan_blocks(uint64_t n);
-int pgrc_ps_scan_u32(pgrc_match_ctx *c, uint32_t *d_io, uint64_t n, uint32_t *d_bsum);
+int pgrc_ps_scan_u32(pgrc_match_ctx *c, uint32_t *d_io, uint64_t n, uint32_t *d_fold);
 // idxsweep.hip: the default front end (one-sweep scatter passes that hash the text themselves, 8-byte records)
 bool pgrc_os_applicable(const pgrc_match_ctx *c, uint32_t hbits);
 int pgrc_os_build_index(pgrc_match_ctx *c, int strand, uint32_t hbits);

@@ -10,6 +10,7 @@
 
 #include "ctx.h"
 #include "pgrc_decode.h"
+#include "scanops.h"
 
 #define DEC_TPB 256
 #define DEC_TEXT_PAD 64         // zero bytes after the text: aligned 16-byte loads past a window's end stay inside
@@ -136,100 +137,16 @@ static int dec_upload(pgrc_decode_ctx *d, void *d_dst, const void *h_src, uint64
 }
 
 // ------------------------------------------------------------------------------------------------ scans (u64 results)
-// The three-kernel scan of export.hip's k_scan_* restated over a transform of the input: per-block sums, one block that
-// scans them, per-block rescan with the carried-in prefix.
-#define DS_EPT 16
-#define DS_EPB (DEC_TPB * DS_EPT)
-
-__device__ __forceinline__ uint64_t ds_block_exclusive(uint64_t v, uint64_t *smem, uint64_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint64_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += u;
-    }
-    if (lane == 63) smem[wv] = inc;
-    __syncthreads();
-    uint64_t woff = 0, tot = 0;
-    for (uint32_t k = 0; k < DEC_TPB / 64; k++) {
-        const uint64_t s = smem[k];
-        if (k < wv) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
-}
-
 struct XfU8 { const uint8_t *p; __device__ uint64_t operator()(uint64_t i) const { return p[i]; } };
 struct XfU16 { const uint16_t *p; __device__ uint64_t operator()(uint64_t i) const { return p[i]; } };
 struct XfBelow { const uint64_t *p; uint64_t lim; __device__ uint64_t operator()(uint64_t i) const { return p[i] < lim ? 1u : 0u; } };
 
-template <typename Xf>
-__global__ void __launch_bounds__(DEC_TPB) k_ds_sums(Xf xf, uint64_t n, uint64_t *bsum) {
-    __shared__ uint64_t smem[DEC_TPB / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * DS_EPB + (uint64_t)threadIdx.x * DS_EPT;
-    uint64_t s = 0;
-    for (int k = 0; k < DS_EPT; k++)
-        if (base + k < n) s += xf(base + k);
-    uint64_t tot;
-    ds_block_exclusive(s, smem, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-static __global__ void __launch_bounds__(DEC_TPB) k_ds_bsums(uint64_t *bsum, uint64_t nb) {
-    __shared__ uint64_t smem[DEC_TPB / 64];
-    uint64_t run = 0;
-    for (uint64_t b0 = 0; b0 < nb; b0 += DEC_TPB) {
-        const uint64_t i = b0 + threadIdx.x;
-        const uint64_t v = i < nb ? bsum[i] : 0;
-        uint64_t tot;
-        const uint64_t ex = ds_block_exclusive(v, smem, &tot);
-        if (i < nb) bsum[i] = run + ex;
-        run += tot;
-    }
-    if (threadIdx.x == 0) bsum[nb] = run;
-}
-
-// out[i] = base + (INCLUSIVE ? sum of xf(0..i) : sum of xf(0..i-1)); the exclusive form also writes out[n] = base + total
-template <typename Xf, bool INCLUSIVE>
-__global__ void __launch_bounds__(DEC_TPB) k_ds_write(Xf xf, uint64_t n, const uint64_t *__restrict__ bsum, uint64_t nb, uint64_t base_val,
-                                                      uint64_t *__restrict__ out) {
-    __shared__ uint64_t smem[DEC_TPB / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * DS_EPB + (uint64_t)threadIdx.x * DS_EPT;
-    uint64_t v[DS_EPT], s = 0;
-#pragma unroll
-    for (int k = 0; k < DS_EPT; k++) {
-        v[k] = (base + k < n) ? xf(base + k) : 0;
-        s += v[k];
-    }
-    uint64_t tot;
-    uint64_t acc = base_val + bsum[blockIdx.x] + ds_block_exclusive(s, smem, &tot);
-#pragma unroll
-    for (int k = 0; k < DS_EPT; k++) {
-        if (base + k < n) out[base + k] = INCLUSIVE ? acc + v[k] : acc;
-        acc += v[k];
-    }
-    if (!INCLUSIVE && blockIdx.x == 0 && threadIdx.x == 0) out[n] = base_val + bsum[nb];
-}
-
-static __global__ void k_ds_set(uint64_t *out, uint64_t v) { *out = v; }
-
+// out[i] = base_val + (INCLUSIVE ? sum of xf(0..i) : sum of xf(0..i-1)); the exclusive form also writes out[n] = base_val + total
 template <bool INCLUSIVE, typename Xf>
 static int dec_scan(pgrc_decode_ctx *d, Xf xf, uint64_t n, uint64_t base_val, uint64_t *d_out) {
-    const uint64_t nb = (n + DS_EPB - 1) / DS_EPB;
     int e;
-    if ((e = dec_buf(d, d->scratch, (nb + 2) * sizeof(uint64_t)))) return e;
-    uint64_t *bs = (uint64_t *)d->scratch.p;
-    if (!n) {
-        if (!INCLUSIVE) hipLaunchKernelGGL(k_ds_set, dim3(1), dim3(1), 0, d->stream, d_out, base_val);
-        DEC_TRY(d, hipGetLastError());
-        return PGRC_OK;
-    }
-    hipLaunchKernelGGL((k_ds_sums<Xf>), dim3((uint32_t)nb), dim3(DEC_TPB), 0, d->stream, xf, n, bs);
-    hipLaunchKernelGGL(k_ds_bsums, dim3(1), dim3(DEC_TPB), 0, d->stream, bs, nb);
-    hipLaunchKernelGGL((k_ds_write<Xf, INCLUSIVE>), dim3((uint32_t)nb), dim3(DEC_TPB), 0, d->stream, xf, n, (const uint64_t *)bs, nb, base_val, d_out);
-    DEC_TRY(d, hipGetLastError());
+    if ((e = dec_buf(d, d->scratch, sco_scratch_elems(n) * sizeof(uint64_t)))) return e;
+    DEC_TRY(d, (sco_device_scan<INCLUSIVE, true>(d->stream, xf, n, ScoPlus{}, (uint64_t)0, base_val, ScoStore<uint64_t>{d_out}, (uint64_t *)d->scratch.p)));
     return PGRC_OK;
 }
 

@@ -423,7 +423,7 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
     int e;
     const size_t bytes = (size_t)n * L;
     if ((e = pgrc_buf_ensure(c, d->d_flags, n * sizeof(uint32_t))) || (e = pgrc_buf_ensure(c, d->d_high, n)) || (e = pgrc_buf_ensure(c, d->d_cls, n)) ||
-        (e = pgrc_buf_ensure(c, d->d_bsum, (pgrc_ps_scan_blocks(n + 1) + 1) * sizeof(uint32_t))))
+        (e = pgrc_buf_ensure(c, d->d_bsum, pgrc_ps_scan_blocks(n + 1) * sizeof(uint32_t))))
         return e;
     for (int k = 0; k < 3; k++)
         if ((e = pgrc_buf_ensure(c, d->d_cnt[k], (n + 1) * sizeof(uint32_t)))) return e;
@@ -558,7 +558,7 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
     for (int f = 0; f < (paired ? 2 : 1); f++) {
         const uint64_t n16 = (len[f] + 15) / 16;
         if ((e = pgrc_buf_ensure(c, d->d_text[f], len[f] + 32)) || (e = pgrc_buf_ensure(c, d->d_nl[f], (n16 + 1) * sizeof(uint32_t))) ||
-            (e = pgrc_buf_ensure(c, d->d_bsum, (pgrc_ps_scan_blocks(n16 + 1) + 1) * sizeof(uint32_t))))
+            (e = pgrc_buf_ensure(c, d->d_bsum, pgrc_ps_scan_blocks(n16 + 1) * sizeof(uint32_t))))
             return e;
         if (len[f]) DIV_TRY(d, hipMemcpyAsync(d->d_text[f].p, src[f], len[f], hipMemcpyHostToDevice, s));
         DIV_TRY(d, hipMemsetAsync((uint8_t *)d->d_text[f].p + len[f], 0, 32, s));

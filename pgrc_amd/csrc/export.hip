@@ -12,7 +12,7 @@
 // same position follows the new one), and appends one record per entry to seven byte streams: offset delta to the
 // previously written entry, original index, RC flag, mismatch count, mismatch codes, and the mismatch offsets coded
 // backwards from the read end.  All of it is a merge of two sorted lists plus per-entry independent work:
-//   positions of the old list  = prefix sum of its offset deltas                     (k_scan_*)
+//   positions of the old list  = prefix sum of its offset deltas                     (scanops.h)
 //   rank of every entry        = its index + a binary search in the OTHER list       (k_export_place_*)
 //   offset deltas              = difference of neighbours in the merged order        (k_export_offsets)
 //   mismatch lists             = prefix sum of the counts, then one thread per entry (k_export_mismatches)
@@ -31,97 +31,17 @@
 
 #include "ctx.h"
 #include "devutil.h"
+#include "scanops.h"
 
 #define EX_NONE 0xFFFFFFFFu
 
-// ---------------------------------------------------------------- exclusive scan: u8 or u32 values -> u64
-#define SC_TPB 256
-#define SC_EPT 16
-#define SC_EPB (SC_TPB * SC_EPT)
-
-template <typename T>
-__device__ __forceinline__ uint64_t sc_block_scan(uint64_t v, uint64_t *smem, uint64_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint64_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += u;
-    }
-    if (lane == 63) smem[wv] = inc;
-    __syncthreads();
-    uint64_t woff = 0, tot = 0;
-    for (uint32_t k = 0; k < SC_TPB / 64; k++) {
-        const uint64_t s = smem[k];
-        if (k < wv) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
-}
-
-template <typename T>
-__global__ void __launch_bounds__(SC_TPB) k_scan_sums(const T *__restrict__ in, uint64_t n, uint64_t *bsum) {
-    __shared__ uint64_t smem[SC_TPB / 64 + 1];
-    const uint64_t base = (uint64_t)blockIdx.x * SC_EPB + (uint64_t)threadIdx.x * SC_EPT;
-    uint64_t s = 0;
-    for (int k = 0; k < SC_EPT; k++)
-        if (base + k < n) s += in[base + k];
-    uint64_t tot;
-    sc_block_scan<T>(s, smem, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// block sums -> exclusive block offsets (one block: nb = n / 4096 values, a few passes of 256)
-__global__ void __launch_bounds__(SC_TPB) k_scan_bsums(uint64_t *bsum, uint64_t nb) {
-    __shared__ uint64_t smem[SC_TPB / 64 + 1];
-    uint64_t run = 0;
-    for (uint64_t b0 = 0; b0 < nb; b0 += SC_TPB) {
-        const uint64_t i = b0 + threadIdx.x;
-        const uint64_t v = i < nb ? bsum[i] : 0;
-        uint64_t tot;
-        const uint64_t ex = sc_block_scan<uint64_t>(v, smem, &tot);
-        if (i < nb) bsum[i] = run + ex;
-        run += tot;
-    }
-    if (threadIdx.x == 0) bsum[nb] = run;
-}
-
+// ---------------------------------------------------------------- scan: u8 or u32 values -> u64
 // out[i] = (INCLUSIVE ? in[0..i] : in[0..i-1]) summed; out has n (+1 for the exclusive form: out[n] = total) entries
 template <typename T, bool INCLUSIVE>
-__global__ void __launch_bounds__(SC_TPB)
-k_scan_write(const T *__restrict__ in, uint64_t n, const uint64_t *__restrict__ bsum, uint64_t nb, uint64_t *out) {
-    __shared__ uint64_t smem[SC_TPB / 64 + 1];
-    const uint64_t base = (uint64_t)blockIdx.x * SC_EPB + (uint64_t)threadIdx.x * SC_EPT;
-    uint64_t v[SC_EPT], s = 0;
-#pragma unroll
-    for (int k = 0; k < SC_EPT; k++) {
-        v[k] = (base + k < n) ? (uint64_t)in[base + k] : 0;
-        s += v[k];
-    }
-    uint64_t tot;
-    uint64_t off = sc_block_scan<T>(s, smem, &tot) + bsum[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < SC_EPT; k++) {
-        if (base + k < n) out[base + k] = INCLUSIVE ? off + v[k] : off;
-        off += v[k];
-    }
-    if (!INCLUSIVE && blockIdx.x == 0 && threadIdx.x == 0) out[n] = bsum[nb];
-}
-
-template <typename T, bool INCLUSIVE>
 static int device_scan(pgrc_match_ctx *c, const T *d_in, uint64_t n, uint64_t *d_out, DevBuf &bs) {
-    const uint64_t nb = (n + SC_EPB - 1) / SC_EPB;
     int e;
-    if ((e = pgrc_buf_ensure(c, bs, (nb + 2) * sizeof(uint64_t)))) return e;
-    if (!n) {
-        if (!INCLUSIVE) HIP_TRY(c, hipMemsetAsync(d_out, 0, sizeof(uint64_t), c->stream));
-        return PGRC_OK;
-    }
-    hipLaunchKernelGGL((k_scan_sums<T>), dim3((uint32_t)nb), dim3(SC_TPB), 0, c->stream, d_in, n, (uint64_t *)bs.p);
-    hipLaunchKernelGGL(k_scan_bsums, dim3(1), dim3(SC_TPB), 0, c->stream, (uint64_t *)bs.p, nb);
-    hipLaunchKernelGGL((k_scan_write<T, INCLUSIVE>), dim3((uint32_t)nb), dim3(SC_TPB), 0, c->stream, d_in, n, (const uint64_t *)bs.p, nb, d_out);
-    HIP_TRY(c, hipGetLastError());
+    if ((e = pgrc_buf_ensure(c, bs, sco_scratch_elems(n) * sizeof(uint64_t)))) return e;
+    HIP_TRY(c, sco_sum_u64<INCLUSIVE>(c->stream, d_in, n, d_out, (uint64_t *)bs.p));
     return PGRC_OK;
 }
 

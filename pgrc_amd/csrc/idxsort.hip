@@ -25,6 +25,7 @@
 #include "ctx.h"
 #include "devutil.h"
 #include "headfmt.h"
+#include "scanops.h"
 
 #define PS_TPB 1024
 #define PS_NW (PS_TPB / 64)
@@ -41,91 +42,13 @@ struct PsPlan {
 };
 
 // ---------------------------------------------------------------- exclusive scan u32 -> u32 (counts of one pass)
-#define PSC_TPB 256
-#define PSC_EPT 16
-#define PSC_EPB (PSC_TPB * PSC_EPT)
+uint64_t pgrc_ps_scan_blocks(uint64_t n) { return sco_scratch_elems(n); }
 
-__device__ __forceinline__ uint32_t psc_block_scan(uint32_t v, uint32_t *smem, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += u;
-    }
-    if (lane == 63) smem[wv] = inc;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (uint32_t k = 0; k < nwv; k++) {
-        const uint32_t s = smem[k];
-        if (k < wv) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
-}
-
-__global__ void __launch_bounds__(PSC_TPB) k_psc_sums(const uint32_t *__restrict__ in, uint64_t n, uint32_t *bsum) {
-    __shared__ uint32_t smem[PSC_TPB / 64 + 1];
-    const uint64_t base = (uint64_t)blockIdx.x * PSC_EPB + (uint64_t)threadIdx.x * PSC_EPT;
-    uint32_t s = 0;
-    if (base + PSC_EPT <= n) {
-        const uint4 *p = reinterpret_cast<const uint4 *>(in + base);
-#pragma unroll
-        for (int k = 0; k < PSC_EPT / 4; k++) { const uint4 q = p[k]; s += q.x + q.y + q.z + q.w; }
-    } else {
-        for (int k = 0; k < PSC_EPT; k++)
-            if (base + k < n) s += in[base + k];
-    }
-    uint32_t tot;
-    psc_block_scan(s, smem, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(PSC_TPB) k_psc_bsums(uint32_t *bsum, uint64_t nb) {
-    __shared__ uint32_t smem[PSC_TPB / 64 + 1];
-    uint32_t run = 0;
-    for (uint64_t b0 = 0; b0 < nb; b0 += PSC_TPB) {
-        const uint64_t i = b0 + threadIdx.x;
-        const uint32_t v = i < nb ? bsum[i] : 0;
-        uint32_t tot;
-        const uint32_t ex = psc_block_scan(v, smem, &tot);
-        if (i < nb) bsum[i] = run + ex;
-        run += tot;
-    }
-}
-
-__global__ void __launch_bounds__(PSC_TPB) k_psc_write(uint32_t *__restrict__ io, uint64_t n, const uint32_t *__restrict__ bsum) {
-    __shared__ uint32_t smem[PSC_TPB / 64 + 1];
-    const uint64_t base = (uint64_t)blockIdx.x * PSC_EPB + (uint64_t)threadIdx.x * PSC_EPT;
-    uint32_t v[PSC_EPT], s = 0;
-#pragma unroll
-    for (int k = 0; k < PSC_EPT; k++) {
-        v[k] = (base + k < n) ? io[base + k] : 0;
-        s += v[k];
-    }
-    uint32_t tot;
-    uint32_t off = psc_block_scan(s, smem, &tot) + bsum[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < PSC_EPT; k++) {
-        if (base + k < n) io[base + k] = off;
-        off += v[k];
-    }
-}
-
-uint64_t pgrc_ps_scan_blocks(uint64_t n) { return (n + PSC_EPB - 1) / PSC_EPB; }
-
-// in place: counts -> exclusive prefix sums (d_bsum: pgrc_ps_scan_blocks(n) + 1 words of scratch)
-static int ps_scan(pgrc_match_ctx *c, uint32_t *d_io, uint64_t n, uint32_t *d_bsum) {
-    const uint64_t nb = (n + PSC_EPB - 1) / PSC_EPB;
-    hipLaunchKernelGGL(k_psc_sums, dim3((uint32_t)nb), dim3(PSC_TPB), 0, c->stream, (const uint32_t *)d_io, n, d_bsum);
-    hipLaunchKernelGGL(k_psc_bsums, dim3(1), dim3(PSC_TPB), 0, c->stream, d_bsum, nb);
-    hipLaunchKernelGGL(k_psc_write, dim3((uint32_t)nb), dim3(PSC_TPB), 0, c->stream, d_io, n, (const uint32_t *)d_bsum);
-    HIP_TRY(c, hipGetLastError());
+// in place: counts -> exclusive prefix sums (d_fold: pgrc_ps_scan_blocks(n) words of scratch)
+int pgrc_ps_scan_u32(pgrc_match_ctx *c, uint32_t *d_io, uint64_t n, uint32_t *d_fold) {
+    HIP_TRY(c, sco_scan<false>(c->stream, (const uint32_t *)d_io, d_io, n, ScoIdentity{}, ScoPlus{}, 0u, d_fold));
     return PGRC_OK;
 }
-
-int pgrc_ps_scan_u32(pgrc_match_ctx *c, uint32_t *d_io, uint64_t n, uint32_t *d_bsum) { return ps_scan(c, d_io, n, d_bsum); }
 
 // ---------------------------------------------------------------- record generation (one wave = 64 consecutive sampled positions)
 
@@ -249,7 +172,7 @@ __device__ __forceinline__ void ps_scatter_tile(ScatterLds &s, const uint32_t (&
         }
     }
     uint32_t all;
-    const uint32_t ex = psc_block_scan(tot, s.scan_tmp, &all);
+    const uint32_t ex = sco_block_sum(tot, s.scan_tmp, &all);
     if (threadIdx.x < D) s.dstart[threadIdx.x] = ex;
     __syncthreads();
 #pragma unroll
@@ -442,7 +365,7 @@ k_ps_finish_fast(const uint32_t *__restrict__ keys, const uint64_t *__restrict__
                 sum += kc | ((kc > 2u ? kc - 1u : 0u) << 16);
             }
             uint32_t both;
-            uint32_t off = psc_block_scan(sum, scan_tmp, &both);
+            uint32_t off = sco_block_sum(sum, scan_tmp, &both);
             total = both & 0xFFFFu;
             xtotal = both >> 16;
 #pragma unroll
@@ -587,7 +510,7 @@ k_ps_finish(const uint32_t *__restrict__ keys, const uint64_t *__restrict__ vals
                     kept[b0 + q] = (uint8_t)min(c, 14u);
                     sum += min(c, PGRC_BUCKET_CAP);
                 }
-                uint32_t off = psc_block_scan(sum, scan_tmp, &total);
+                uint32_t off = sco_block_sum(sum, scan_tmp, &total);
                 for (uint32_t q = 0; q < PF_NB / PF_TPB; q++) {
                     cnt[b0 + q] = off;
                     if (kept[b0 + q] > PGRC_BUCKET_CAP) {      // an over-full bucket: its 13 slots start as "no entry yet"
@@ -701,7 +624,7 @@ int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_
     for (int k = 0; k < 2; k++)
         if ((e = pgrc_buf_ensure(c, c->d_skey[k], (n + 16) * sizeof(uint32_t))) || (e = pgrc_buf_ensure(c, c->d_sval[k], (n + 16) * sizeof(uint64_t)))) return e;
     const uint64_t ncnt = (uint64_t)D * pl.ntiles;
-    const uint64_t nbs = (ncnt + PSC_EPB - 1) / PSC_EPB + 1;
+    const uint64_t nbs = sco_scratch_elems(ncnt);
     if ((e = pgrc_buf_ensure(c, c->d_sorttmp, (ncnt + nbs) * sizeof(uint32_t) + 256))) return e;
     uint32_t *cnt = (uint32_t *)c->d_sorttmp.p, *bsum = cnt + ncnt;
     uint32_t *kA = (uint32_t *)c->d_skey[0].p, *kB = (uint32_t *)c->d_skey[1].p;
@@ -717,11 +640,11 @@ int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_
     const uint32_t sh1 = cb, sh2 = cb + pl.b1;
     // pass 1: text -> A; pass 2: A -> B
     hipLaunchKernelGGL(k_ps_hist_gen, dim3(grid), dim3(PS_TPB), 0, c->stream, g, sh1, (1u << pl.b1) - 1u, pl.ntiles, cnt);
-    if ((e = ps_scan(c, cnt, ((uint64_t)1 << pl.b1) * pl.ntiles, bsum))) return e;
+    if ((e = pgrc_ps_scan_u32(c, cnt, ((uint64_t)1 << pl.b1) * pl.ntiles, bsum))) return e;
     hipLaunchKernelGGL(k_ps_scatter_gen, dim3(grid), dim3(PS_TPB), 0, c->stream, g, sh1, pl.b1, pl.ntiles, (const uint32_t *)cnt, kA, vA);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(k_ps_hist_keys, dim3(grid), dim3(PS_TPB), 0, c->stream, (const uint32_t *)kA, n, sh2, (1u << pl.b2) - 1u, pl.ntiles, cnt);
-    if ((e = ps_scan(c, cnt, ncnt, bsum))) return e;
+    if ((e = pgrc_ps_scan_u32(c, cnt, ncnt, bsum))) return e;
     hipLaunchKernelGGL(k_ps_scatter_keys, dim3(grid), dim3(PS_TPB), 0, c->stream, (const uint32_t *)kA, (const uint64_t *)vA, n, sh2, pl.b2,
                        pl.ntiles, (const uint32_t *)cnt, kB, vB);
     HIP_TRY(c, hipGetLastError());

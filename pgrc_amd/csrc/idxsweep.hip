@@ -36,6 +36,7 @@
 
 #include "ctx.h"
 #include "devutil.h"
+#include "scanops.h"
 
 #define OS_NW 16                          // waves of the largest block
 #define OS_MAXD 512u                      // digits per pass: at most 9 bits
@@ -57,26 +58,6 @@ __device__ __forceinline__ uint32_t os_tile_of_block(uint32_t b, uint32_t nb, ui
     if (!xcd) return b;
     const uint32_t x = b & 7u, q = nb >> 3, r = nb & 7u;
     return x * q + min(x, r) + (b >> 3);
-}
-
-__device__ __forceinline__ uint32_t os_block_scan(uint32_t v, uint32_t *smem, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += u;
-    }
-    if (lane == 63) smem[wv] = inc;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (uint32_t k = 0; k < nwv; k++) {
-        const uint32_t s = smem[k];
-        if (k < wv) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
 }
 
 // ---------------------------------------------------------------- hashing a tile of the text
@@ -245,7 +226,7 @@ __global__ void __launch_bounds__(1024) k_os_prepare(const OsPlan pl, const uint
     // every pass-1 bin gets at least one pass-2 tile (an empty one still hands on the partition starts of its d_lo)
     const uint32_t nt = d < D1 ? max(1u, (c1 + tile - 1u) / tile) : 0u;
     uint32_t tot;
-    const uint32_t et = os_block_scan(nt, smem, &tot);
+    const uint32_t et = sco_block_sum(nt, smem, &tot);
     if (d < D1) tile_start[d] = et;
     if (d == 0) {
         tile_start[D1] = tot;
@@ -280,7 +261,7 @@ __device__ __forceinline__ void os_scatter_tile(OsTileLds &s, uint64_t *recS, AU
         uint32_t c[2] = {0, 0};
         for (uint32_t q = 0; q < per; q++) c[q] = d0 + q < D ? s.cnt[d0 + q] : 0u;
         uint32_t tot;
-        run = os_block_scan(c[0] + c[1], s.scan_tmp, &tot);
+        run = sco_block_sum(c[0] + c[1], s.scan_tmp, &tot);
         for (uint32_t q = 0; q < per; q++) {
             if (d0 + q < D) {
                 s.dstart[d0 + q] = run;
@@ -488,7 +469,7 @@ int pgrc_os_build_index(pgrc_match_ctx *c, int strand, uint32_t hbits) {
         (e = pgrc_buf_ensure(c, c->d_skey[0], (n + 16) * sizeof(uint32_t))))
         return e;
     const uint64_t n1 = (uint64_t)D1 * pl.ntiles1, n2 = (uint64_t)D2 * pl.ntiles2_max;
-    const uint64_t nbs = pgrc_ps_scan_blocks(std::max(n1, n2)) + 2;
+    const uint64_t nbs = pgrc_ps_scan_blocks(std::max(n1, n2));
     const uint64_t flag_words = 2ull * np + 2;                 // np flags, the list of flagged partitions, its length (idxsort.hip)
     const uint64_t words = flag_words + (OS_MAXD + 2) + (np + 2) + nbs + n1 + n2 + 4 * (pl.ntiles2_max + 1) + 64;
     if ((e = pgrc_buf_ensure(c, c->d_sorttmp, words * sizeof(uint32_t)))) return e;

@@ -869,7 +869,7 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     MEM_TRY(m, hipMemsetAsync(m->d_small.p, 0, 64, c->stream));
     const uint32_t g = (uint32_t)((nev + 255) / 256);
     // scratch of the scans below (scanops.h): block folds of nev values
-    if ((e = pgrc_buf_ensure(c, m->d_scan, sco_scratch_words(nev) * sizeof(uint32_t)))) { m->err = c->err; return e; }
+    if ((e = pgrc_buf_ensure(c, m->d_scan, sco_scratch_elems(nev) * sizeof(uint32_t)))) { m->err = c->err; return e; }
     uint32_t *d_bsum = (uint32_t *)m->d_scan.p;
     {
         uint64_t *sk0 = (uint64_t *)m->d_skey[0].p, *si0 = (uint64_t *)m->d_sidx[0].p;

@@ -127,7 +127,7 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     const uint64_t binc_at = pp_a16(T * 4) + 16, ent_bytes = binc_at + T * 4 + 16;
     const uint64_t file_at = pp_a16(P * 4) + 16, ninc_at = file_at + pp_a16(P) + 16, frel_at = ninc_at + pp_a16(P * 4) + 16, pre_at = frel_at + pp_a16(P * 4) + 16,
                    dinc_at = pre_at + pp_a16(P * 4) + 16, dval_at = dinc_at + pp_a16(P * 4) + 16, map_at = dval_at + pp_a16(P) + 16, pair_bytes = map_at + P + 16;
-    const uint64_t sco_bytes = pp_a16(sco_scratch_words(T) * 4), bsum_bytes = sco_bytes + 32;
+    const uint64_t sco_bytes = pp_a16(sco_scratch_elems(T) * 4), bsum_bytes = sco_bytes + 32;
     if ((e = dec_buf(d, d->po_in, T * 4 + 16)) || (e = dec_buf(d, d->po_rev, T * 4 + 16)) || (e = dec_buf(d, d->po_ent, ent_bytes)) ||
         (e = dec_buf(d, d->po_pair, coded ? pair_bytes : 16)) || (e = dec_buf(d, d->po_out, dev.total)) || (e = dec_buf(d, d->po_bsum, bsum_bytes)))
         return e;

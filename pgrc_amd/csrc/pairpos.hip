@@ -6,7 +6,7 @@
 // ones, over the position bits in use), and the loop falls apart into per-pair work between prefix scans:
 //   flags -> stream indexes        scanops.h over the flag bytes (how many near / delta pairs precede a pair)
 //   decoder, refPrev               every far pair is ADD d (delta), SET |mate - base| (full after a full, or the first far
-//                                  pair) or KEEP (full after a delta): a segmented inclusive sum in int64 (k_pp_seg_*), run
+//                                  pair) or KEEP (full after a delta): a segmented inclusive sum in int64 (scanops.h), run   
 //                                  over ALL ranked pairs with the near ones as ADD 0, so no far-to-rank map is needed
 //   encoder, refPrev               before far pair k it is rel[k-1] (state A: k-1 was a delta pair; C: a full pair that set
 //                                  it; the start is C with rel[-1] = 0) or rel[k-2] (state B: k-1 was a full pair that kept
@@ -143,41 +143,13 @@ __global__ void __launch_bounds__(PP_TPB) k_pp_dec_ops(const uint64_t *__restric
     kind[i] = (uint8_t)PP_K_SET;
 }
 
-// The segmented sum: a sibling of decctx.h's three-kernel scan over (value, set) with (a, b) -> b.set ? b : (a.v + b.v, a.set)
-struct PpSeg {
+// The segmented sum: scanops.h's scan over (value, set) with (a, b) -> b.set ? b : (a.v + b.v, a.set)
+struct __attribute__((packed, aligned(4))) PpSeg {      // 12 bytes: three words to shuffle
     int64_t v;
     uint32_t set;
 };
 __device__ __forceinline__ PpSeg pp_seg_op(PpSeg a, PpSeg b) { return b.set ? b : PpSeg{a.v + b.v, a.set}; }
-
-__device__ __forceinline__ PpSeg pp_seg_block_exclusive(PpSeg x, int64_t *sv, uint32_t *ss, PpSeg *total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    PpSeg inc = x;
-    for (int o = 1; o < 64; o <<= 1) {
-        PpSeg u;
-        u.v = __shfl_up(inc.v, o, 64);
-        u.set = __shfl_up(inc.set, o, 64);
-        if (lane >= (uint32_t)o) inc = pp_seg_op(u, inc);
-    }
-    PpSeg before;
-    before.v = __shfl_up(inc.v, 1, 64);
-    before.set = __shfl_up(inc.set, 1, 64);
-    if (lane == 0) before = PpSeg{0, 0u};
-    if (lane == 63) {
-        sv[wv] = inc.v;
-        ss[wv] = inc.set;
-    }
-    __syncthreads();
-    PpSeg woff{0, 0u}, tot{0, 0u};
-    for (uint32_t k = 0; k < PP_TPB / 64; k++) {
-        const PpSeg s{sv[k], ss[k]};
-        if (k < wv) woff = pp_seg_op(woff, s);
-        tot = pp_seg_op(tot, s);
-    }
-    __syncthreads();
-    *total = tot;
-    return pp_seg_op(woff, before);
-}
+struct PpSegOp { __device__ PpSeg operator()(PpSeg a, PpSeg b) const { return pp_seg_op(a, b); } };
 
 struct PpChainIn {          // the chain's entry of ranked pair i: near and keeping pairs add nothing
     const uint8_t *kind;
@@ -189,62 +161,6 @@ struct PpChainIn {          // the chain's entry of ranked pair i: near and keep
     }
 };
 
-template <typename Xf>
-__global__ void __launch_bounds__(PP_TPB) k_pp_seg_sums(Xf xf, uint64_t n, int64_t *__restrict__ bv, uint32_t *__restrict__ bs) {
-    __shared__ int64_t sv[PP_TPB / 64];
-    __shared__ uint32_t ss[PP_TPB / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * DS_EPB + (uint64_t)threadIdx.x * DS_EPT;
-    PpSeg s{0, 0u};
-    for (int k = 0; k < DS_EPT; k++)
-        if (base + k < n) s = pp_seg_op(s, xf(base + k));
-    PpSeg tot;
-    pp_seg_block_exclusive(s, sv, ss, &tot);
-    if (threadIdx.x == 0) {
-        bv[blockIdx.x] = tot.v;
-        bs[blockIdx.x] = tot.set;
-    }
-}
-
-// one block: the blocks' folds -> the fold of everything before each block
-static __global__ void __launch_bounds__(PP_TPB) k_pp_seg_bsums(int64_t *bv, uint32_t *bs, uint64_t nb) {
-    __shared__ int64_t sv[PP_TPB / 64];
-    __shared__ uint32_t ss[PP_TPB / 64];
-    PpSeg run{0, 0u};
-    for (uint64_t b0 = 0; b0 < nb; b0 += PP_TPB) {
-        const uint64_t i = b0 + threadIdx.x;
-        const PpSeg v = i < nb ? PpSeg{bv[i], bs[i]} : PpSeg{0, 0u};
-        PpSeg tot;
-        const PpSeg ex = pp_seg_op(run, pp_seg_block_exclusive(v, sv, ss, &tot));
-        if (i < nb) {
-            bv[i] = ex.v;
-            bs[i] = ex.set;
-        }
-        run = pp_seg_op(run, tot);
-    }
-}
-
-// sink(i, the inclusive sum at i) for every i
-template <typename Xf, typename Sink>
-__global__ void __launch_bounds__(PP_TPB) k_pp_seg_write(Xf xf, uint64_t n, const int64_t *__restrict__ bv, const uint32_t *__restrict__ bs, Sink sink) {
-    __shared__ int64_t sv[PP_TPB / 64];
-    __shared__ uint32_t ss[PP_TPB / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * DS_EPB + (uint64_t)threadIdx.x * DS_EPT;
-    PpSeg v[DS_EPT], s{0, 0u};
-#pragma unroll
-    for (int k = 0; k < DS_EPT; k++) {
-        v[k] = (base + k < n) ? xf(base + k) : PpSeg{0, 0u};
-        s = pp_seg_op(s, v[k]);
-    }
-    PpSeg tot;
-    const PpSeg ex = pp_seg_block_exclusive(s, sv, ss, &tot);
-    PpSeg acc = pp_seg_op(PpSeg{bv[blockIdx.x], bs[blockIdx.x]}, ex);
-#pragma unroll
-    for (int k = 0; k < DS_EPT; k++) {
-        acc = pp_seg_op(acc, v[k]);
-        if (base + k < n) sink(base + k, acc.v);
-    }
-}
-
 // the mate of a delta pair: base +- refPrev at its place, back in pair order
 template <bool W8>
 struct PpDeltaSink {
@@ -252,9 +168,10 @@ struct PpDeltaSink {
     const uint8_t *kind;
     uint64_t P;
     uint64_t *out;
-    __device__ void operator()(uint64_t i, int64_t ref) const {
+    __device__ void operator()(uint64_t i, PpSeg acc) const {          // acc: the inclusive sum at i
         const uint32_t k = kind[i];
         if (!(k & PP_K_DELTA)) return;
+        const int64_t ref = acc.v;
         uint64_t base, pair;
         pp_entry<W8>(a, b, i, base, pair);
         const uint64_t m = (k & PP_K_BF) ? base + (uint64_t)ref : base - (uint64_t)ref;
@@ -413,9 +330,7 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
         up += nbytes[k];
     }
     const uint64_t near_at = 0, kind_at = near_at + pp_a16(P * 4) + 16, val_at = kind_at + pp_a16(P) + 16, rank_bytes = val_at + P * 8 + 16;
-    const uint64_t nseg = (P + DS_EPB - 1) / DS_EPB;
-    const uint64_t sco_words = sco_scratch_words(std::max(P, nf));
-    const uint64_t bsum_bytes = std::max<uint64_t>(pp_a16(sco_words * 4), pp_a16(nseg * 8) + pp_a16(nseg * 4) + 32) + 2 * PP_OR_BLOCKS * 8 + 64;
+    const uint64_t bsum_bytes = pp_a16(sco_scratch_elems(std::max(P, nf)) * sizeof(PpSeg)) + 2 * PP_OR_BLOCKS * 8 + 64;     // (the flag scans' u32 folds too)
     if ((e = dec_buf(d, d->pp_in, in_bytes)) || (e = dec_buf(d, d->pp_rank, rank_bytes)) || (e = dec_buf(d, d->pp_far, nf * 4 + 16)) || (e = dec_buf(d, d->pp_bsum, bsum_bytes)))
         return e;
     uint8_t *in = (uint8_t *)d->pp_in.p;
@@ -465,19 +380,11 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
     const uint64_t *a = nullptr, *b = nullptr;
     if ((e = pp_sort(d, W8, P, ors[0], &a, &b))) return e;
     DEC_TRY(d, hipEventRecord(d->pp_ev[3], d->stream));
-    int64_t *bv = (int64_t *)d->pp_bsum.p;
-    uint32_t *bs = (uint32_t *)((uint8_t *)d->pp_bsum.p + pp_a16(nseg * 8) + 16);
-    const PpChainIn xf{kind, val};
-    if (P) {
-        hipLaunchKernelGGL((k_pp_dec_ops<W8>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, a, b, P, ds, d_out, kind, val);
-        hipLaunchKernelGGL((k_pp_seg_sums<PpChainIn>), dim3((uint32_t)nseg), dim3(PP_TPB), 0, d->stream, xf, P, bv, bs);
-        hipLaunchKernelGGL(k_pp_seg_bsums, dim3(1), dim3(PP_TPB), 0, d->stream, bv, bs, nseg);
-    }
+    if (P) hipLaunchKernelGGL((k_pp_dec_ops<W8>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, a, b, P, ds, d_out, kind, val);
     DEC_TRY(d, hipGetLastError());
     DEC_TRY(d, hipEventRecord(d->pp_ev[4], d->stream));
-    if (P) hipLaunchKernelGGL((k_pp_seg_write<PpChainIn, PpDeltaSink<W8>>), dim3((uint32_t)nseg), dim3(PP_TPB), 0, d->stream, xf, P, (const int64_t *)bv, (const uint32_t *)bs,
-                              PpDeltaSink<W8>{a, b, kind, P, d_out});
-    DEC_TRY(d, hipGetLastError());
+    // refPrev at every ranked pair; the scan's last pass puts the delta pairs' mates in their places
+    DEC_TRY(d, (sco_device_scan<true, false>(d->stream, PpChainIn{kind, val}, P, PpSegOp{}, PpSeg{0, 0u}, PpSeg{0, 0u}, PpDeltaSink<W8>{a, b, kind, P, d_out}, (PpSeg *)d->pp_bsum.p)));
     DEC_TRY(d, hipEventRecord(d->pp_ev[5], d->stream));
     DEC_TRY(d, hipStreamSynchronize(d->stream));
     pgrc_pairpos_timing &t = d->ptm;
@@ -545,7 +452,7 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, uint64_t T, 
     const uint64_t near_at = pp_a16(P * 8) + 16, bf_at = near_at + pp_a16(P * 4) + 16, rank_bytes = bf_at + P + 16;
     const uint64_t frank_at = pp_a16(P * 8) + 16, pre_at = frank_at + pp_a16(P * 4) + 16, dinc_at = pre_at + pp_a16(P * 4) + 16,
                    dval_at = dinc_at + pp_a16(P * 4) + 16, map_at = dval_at + pp_a16(P * 2) + 16, far_bytes = map_at + P + 16;
-    const uint64_t bsum_bytes = pp_a16(sco_scratch_words(P) * 4) + 2 * PP_OR_BLOCKS * 8 + 64;
+    const uint64_t bsum_bytes = pp_a16(sco_scratch_elems(P) * 4) + 2 * PP_OR_BLOCKS * 8 + 64;
     if ((e = dec_buf(d, d->pp_in, T * 8 + 16)) || (e = dec_buf(d, d->pp_rank, rank_bytes)) || (e = dec_buf(d, d->pp_far, far_bytes)) ||
         (e = dec_buf(d, d->pp_out, dev.total)) || (e = dec_buf(d, d->pp_bsum, bsum_bytes)))
         return e;

@@ -7,7 +7,7 @@
 //
 // One pass over `dbits` <= 8 key bits, tiles of RX_TILE consecutive records:
 //   k_rx_hist     every tile counts its records per digit (LDS atomics)        -> cnt[digit][tile]
-//   exclusive scan of that matrix in (digit, tile) order (idxsort.hip's k_psc_*) -> where a tile's run of a digit starts
+//   exclusive scan of that matrix in (digit, tile) order (scanops.h, in place) -> where a tile's run of a digit starts
 //   k_rx_scatter  ranks inside the tile by ballots (lanes of a group with one digit find each other with `dbits`
 //                 ballots; per-wave counters in LDS; waves in order), the tile is laid out by digit in LDS and every
 //                 digit's run goes out as one contiguous piece: whole lines, and equal digits keep their input order.
@@ -21,6 +21,7 @@
 
 #include "ctx.h"
 #include "devutil.h"
+#include "scanops.h"
 
 #define RX_TPB 1024
 #define RX_NW (RX_TPB / 64)
@@ -52,26 +53,6 @@ struct RxLds {
     uint32_t gbase[RX_MAXD];             // where the tile's run of a digit starts in the output
     uint32_t scan_tmp[RX_NW + 1];
 };
-
-__device__ __forceinline__ uint32_t rx_block_scan(uint32_t v, uint32_t *smem, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += u;
-    }
-    if (lane == 63) smem[wv] = inc;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (uint32_t k = 0; k < nwv; k++) {
-        const uint32_t s = smem[k];
-        if (k < wv) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
-}
 
 // Records arrive as RX_E groups per wave; group i of wave w holds the tile's records w * 512 + i * 64 + lane, so "earlier
 // wave, then earlier group, then lower lane" is the input order -- and the order equal digits leave in.
@@ -136,7 +117,7 @@ k_rx_scatter(const uint64_t *__restrict__ in, const uint64_t *__restrict__ vin, 
         }
     }
     uint32_t all;
-    const uint32_t ex = rx_block_scan(tot, s.scan_tmp, &all);
+    const uint32_t ex = sco_block_sum(tot, s.scan_tmp, &all);
     if (threadIdx.x < D) s.dstart[threadIdx.x] = ex;
     __syncthreads();
 #pragma unroll
@@ -231,7 +212,7 @@ k_rx_segments(uint64_t *__restrict__ keys, uint64_t *__restrict__ vals, const ui
             }
         }
         uint32_t all;
-        const uint32_t ex = rx_block_scan(tot, s.scan_tmp, &all);
+        const uint32_t ex = sco_block_sum(tot, s.scan_tmp, &all);
         if (threadIdx.x < D) s.dstart[threadIdx.x] = ex;
         __syncthreads();
 #pragma unroll
@@ -307,7 +288,7 @@ static int rx_sort(pgrc_match_ctx *c, uint64_t *d_a, uint64_t *d_b, uint64_t *v_
     const uint64_t ntiles = (n + RX_TILE - 1) / RX_TILE;
     const uint64_t ncnt = (uint64_t)RX_MAXD * ntiles;
     int e;
-    if ((e = pgrc_buf_ensure(c, scratch, (ncnt + pgrc_ps_scan_blocks(ncnt) + 2) * sizeof(uint32_t) + 256))) return e;
+    if ((e = pgrc_buf_ensure(c, scratch, (ncnt + pgrc_ps_scan_blocks(ncnt)) * sizeof(uint32_t) + 256))) return e;
     if (pairs) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_rx_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(RX_TILE * sizeof(uint64_t))));
     uint32_t *cnt = (uint32_t *)scratch.p, *bsum = cnt + ncnt;
     const uint32_t bits = bit_hi - bit_lo, passes = (bits + 7) / 8;

@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(DEC_TPB) k_rs_count(const uint8_t *__restrict_
     for (uint32_t v = 0; v < RS_WPB / DEC_TPB; v++)
         s += __popc(rs_word_mask<MODE>(buf, n, (uint64_t)blockIdx.x * RS_WPB + v * DEC_TPB + threadIdx.x));
     uint64_t tot;
-    ds_block_exclusive(s, smem, &tot);
+    sco_block_sum<DEC_TPB / 64>(s, smem, &tot);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(DEC_TPB) k_rs_write(const uint8_t *__restrict_
         const uint64_t q = (uint64_t)blockIdx.x * RS_WPB + v * DEC_TPB + threadIdx.x;
         uint32_t m = rs_word_mask<MODE>(buf, n, q);
         uint64_t tot;
-        uint64_t r = base + ds_block_exclusive(__popc(m), smem, &tot);
+        uint64_t r = base + sco_block_sum<DEC_TPB / 64>((uint64_t)__popc(m), smem, &tot);
         base += tot;
         while (m) {
             const uint32_t b = __ffs(m) - 1;

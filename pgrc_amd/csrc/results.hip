@@ -8,6 +8,7 @@
 //            fillEntryWithReversedMismatches :53-66; code = (val(pg)<<4)+val(read), helper.cpp:358-362.
 #include "ctx.h"
 #include "devutil.h"
+#include "scanops.h"
 
 __global__ void __launch_bounds__(256) k_init_results(uint64_t *pos, uint8_t *rc, uint8_t *mism, uint64_t n) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -53,75 +54,8 @@ int pgrc_launch_hist(pgrc_match_ctx *c) {
 
 // ---------------------------------------------------------------- mismatch extraction
 
-// exclusive u64 scan of per-read mismatch counts (255 -> 0): 3-kernel block scan
-#define XS_TPB 256
-#define XS_EPT 16
-#define XS_EPB (XS_TPB * XS_EPT)
-
 __device__ __forceinline__ uint32_t mcount(uint8_t m) { return m == PGRC_NOT_MATCHED_CNT ? 0u : (uint32_t)m; }
-
-__device__ __forceinline__ uint32_t xs_block_scan(uint32_t v, uint32_t *smem, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += u;
-    }
-    if (lane == 63) smem[wv] = inc;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (uint32_t k = 0; k < XS_TPB / 64; k++) {
-        uint32_t s = smem[k];
-        if (k < wv) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
-}
-
-__global__ void __launch_bounds__(XS_TPB) k_xs_sums(const uint8_t *__restrict__ mism, uint64_t n, uint64_t *bsum) {
-    __shared__ uint32_t smem[XS_TPB / 64 + 1];
-    const uint64_t base = (uint64_t)blockIdx.x * XS_EPB + (uint64_t)threadIdx.x * XS_EPT;
-    uint32_t s = 0;
-    for (int k = 0; k < XS_EPT; k++)
-        if (base + k < n) s += mcount(mism[base + k]);
-    uint32_t tot;
-    xs_block_scan(s, smem, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-__global__ void k_xs_bsums(uint64_t *bsum, uint64_t nb) { // nb is small (n/4096): one thread suffices
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        uint64_t run = 0;
-        for (uint64_t i = 0; i < nb; i++) {
-            uint64_t v = bsum[i];
-            bsum[i] = run;
-            run += v;
-        }
-        bsum[nb] = run;
-    }
-}
-
-__global__ void __launch_bounds__(XS_TPB) k_xs_write(const uint8_t *__restrict__ mism, uint64_t n,
-                                                     const uint64_t *__restrict__ bsum, uint64_t nb, uint64_t *cum) {
-    __shared__ uint32_t smem[XS_TPB / 64 + 1];
-    const uint64_t base = (uint64_t)blockIdx.x * XS_EPB + (uint64_t)threadIdx.x * XS_EPT;
-    uint32_t v[XS_EPT], s = 0;
-#pragma unroll
-    for (int k = 0; k < XS_EPT; k++) {
-        v[k] = (base + k < n) ? mcount(mism[base + k]) : 0;
-        s += v[k];
-    }
-    uint32_t tot;
-    uint64_t off = (uint64_t)xs_block_scan(s, smem, &tot) + bsum[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < XS_EPT; k++) {
-        if (base + k < n) cum[base + k] = off;
-        off += v[k];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) cum[n] = bsum[nb];
-}
+struct XsCount { __device__ uint32_t operator()(uint8_t m) const { return mcount(m); } };    // a read's mismatch count (255 -> 0)
 
 struct ExtractArgs {
     const uint32_t *pg;
@@ -192,19 +126,13 @@ int pgrc_extract_lists_device(pgrc_match_ctx *c, const uint8_t *d_revflags, bool
     const uint64_t n = c->n;
     DevBuf d_bsum;
     int e;
-    const uint64_t nb = (n + XS_EPB - 1) / XS_EPB;
     if ((e = pgrc_buf_ensure(c, d_cum, (n + 1) * sizeof(uint64_t)))) return e;
-    if ((e = pgrc_buf_ensure(c, d_bsum, (nb + 2) * sizeof(uint64_t)))) return e;
-    if (n) {
-        hipLaunchKernelGGL(k_xs_sums, dim3((uint32_t)nb), dim3(XS_TPB), 0, c->stream, (const uint8_t *)c->d_mism.p, n, (uint64_t *)d_bsum.p);
-        hipLaunchKernelGGL(k_xs_bsums, dim3(1), dim3(64), 0, c->stream, (uint64_t *)d_bsum.p, nb);
-        hipLaunchKernelGGL(k_xs_write, dim3((uint32_t)nb), dim3(XS_TPB), 0, c->stream, (const uint8_t *)c->d_mism.p, n,
-                           (const uint64_t *)d_bsum.p, nb, (uint64_t *)d_cum.p);
-    } else {
-        (void)hipMemsetAsync(d_cum.p, 0, sizeof(uint64_t), c->stream);
-    }
+    if ((e = pgrc_buf_ensure(c, d_bsum, sco_scratch_elems(n) * sizeof(uint64_t)))) return e;
+    // d_cum = exclusive scan of the counts in u64, d_cum[n] = their total
+    const hipError_t he = sco_device_scan<false, true>(c->stream, ScoLoad<uint64_t, uint8_t, XsCount>{(const uint8_t *)c->d_mism.p, XsCount{}}, n, ScoPlus{}, (uint64_t)0, (uint64_t)0,
+                                                 ScoStore<uint64_t>{(uint64_t *)d_cum.p}, (uint64_t *)d_bsum.p);
     uint64_t total = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&total, (const uint64_t *)d_cum.p + n, sizeof total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+    if (he != hipSuccess || hipMemcpyAsync(&total, (const uint64_t *)d_cum.p + n, sizeof total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) {
         pgrc_buf_free(d_bsum);
         c->err = "extract: scan failed";

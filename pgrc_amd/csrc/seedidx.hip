@@ -211,44 +211,10 @@ __global__ void __launch_bounds__(256) k_seed_keys_ascii(const SeedArgs a, uint6
 #define SG_EVEN 4096u
 __device__ __forceinline__ bool seed_key_starts(const uint64_t *__restrict__ ks, uint32_t i) { return i == 0u || ks[i] != ks[i - 1u]; }
 
-// a block's exclusive sum / inclusive maximum over its threads in thread order (SG_TPB threads), and the block's total / maximum
-__device__ __forceinline__ uint32_t sg_block_excl_sum(uint32_t v, uint32_t *smem, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += u;
-    }
-    if (lane == 63u) smem[wv] = inc;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (uint32_t k = 0; k < SG_TPB / 64; k++) {
-        const uint32_t x = smem[k];
-        if (k < wv) woff += x;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
-}
-__device__ __forceinline__ uint32_t sg_block_incl_max(uint32_t v, uint32_t *smem, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o && u > inc) inc = u;
-    }
-    if (lane == 63u) smem[wv] = inc;
-    __syncthreads();
-    uint32_t wmax = 0, tot = 0;
-    for (uint32_t k = 0; k < SG_TPB / 64; k++) {
-        const uint32_t x = smem[k];
-        if (k < wv && x > wmax) wmax = x;
-        if (x > tot) tot = x;
-    }
-    __syncthreads();
-    *total = tot;
-    return inc > wmax ? inc : wmax;
+struct SgMax { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; } };
+// the maximum over the threads before this one in the block (SG_TPB threads), and the block's maximum
+__device__ __forceinline__ uint32_t sg_block_excl_max(uint32_t v, uint32_t *smem, uint32_t *total) {
+    return sco_block_exclusive<SG_TPB / 64>(v, SgMax{}, 0u, smem, total);
 }
 
 __global__ void __launch_bounds__(256) k_seed_even_bounds(uint32_t nent, uint32_t nseg, uint32_t *__restrict__ seg) {
@@ -267,7 +233,7 @@ k_seed_seg_summary(const uint64_t *__restrict__ ks, const uint32_t *__restrict__
         const uint32_t i = base + threadIdx.x;
         const bool f = i < s1 && seed_key_starts(ks, i);
         uint32_t tot;
-        const uint32_t r = c + sg_block_excl_sum(f ? 1u : 0u, smem, &tot);
+        const uint32_t r = c + sco_block_sum<SG_TPB / 64>(f ? 1u : 0u, smem, &tot);
         if (f) {
             const uint32_t v = (uint32_t)(ks[i] >> (64u - tbits)) - r + SX_BIAS;
             if (v > m) m = v;
@@ -275,7 +241,7 @@ k_seed_seg_summary(const uint64_t *__restrict__ ks, const uint32_t *__restrict__
         c += tot;
     }
     uint32_t mm;
-    (void)sg_block_incl_max(m, smem, &mm);
+    (void)sg_block_excl_max(m, smem, &mm);
     if (threadIdx.x == 0) {
         seg_nd[blockIdx.x] = c;
         seg_m[blockIdx.x] = mm;
@@ -293,17 +259,10 @@ k_seed_seg_scan(const uint32_t *__restrict__ seg_nd, const uint32_t *__restrict_
         const uint32_t p = base + threadIdx.x;
         const uint32_t n = p < nseg ? seg_nd[p] : 0u;
         uint32_t tot;
-        const uint32_t b = c + sg_block_excl_sum(n, smem, &tot);
+        const uint32_t b = c + sco_block_sum<SG_TPB / 64>(n, smem, &tot);
         const uint32_t v = (p < nseg && n) ? seg_m[p] - b : 0u;           // the segment's maximum in global numbering
         uint32_t vmax;
-        const uint32_t inc = sg_block_incl_max(v, smem, &vmax);
-        // exclusive: what reaches segment p is the maximum over the segments before it
-        uint32_t prev = __shfl_up(inc, 1, 64);
-        __shared__ uint32_t wlast[SG_TPB / 64];
-        if ((threadIdx.x & 63u) == 63u) wlast[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        if ((threadIdx.x & 63u) == 0u) prev = threadIdx.x ? wlast[(threadIdx.x >> 6) - 1u] : 0u;
-        __syncthreads();
+        const uint32_t prev = sg_block_excl_max(v, smem, &vmax);       // what reaches segment p: the maximum over the segments before it
         if (p < nseg) {
             base_d[p] = b;
             pin[p] = prev > carry ? prev : carry;
@@ -326,10 +285,10 @@ k_seed_seg_write(const uint64_t *__restrict__ ks, const uint64_t *__restrict__ v
         const uint32_t i = base + threadIdx.x;
         const bool f = i < s1 && seed_key_starts(ks, i);
         uint32_t tot;
-        const uint32_t r = c + sg_block_excl_sum(f ? 1u : 0u, smem, &tot);
+        const uint32_t r = c + sco_block_sum<SG_TPB / 64>(f ? 1u : 0u, smem, &tot);
         const uint32_t v = f ? (uint32_t)(ks[i] >> (64u - tbits)) - (d0 + r) + SX_BIAS : 0u;      // home - d + bias (home < 2^31, d < 2^30: no wrap)
         uint32_t vmax;
-        const uint32_t inc = sg_block_incl_max(v, smem, &vmax);
+        const uint32_t inc = max(sg_block_excl_max(v, smem, &vmax), v);
         if (f) {
             dstart[d0 + r] = i;
             pm[d0 + r] = inc > carry ? inc : carry;
@@ -724,7 +683,6 @@ k_seed_expand(const SeedArgs a, uint64_t wbase, uint64_t nwin, const uint64_t *_
     if (threadIdx.x == 0) { nfound = 0; nheavy = 0; hitcnt[0] = 0; hitcnt[1] = 0; }
     __syncthreads();
     const uint64_t b0 = wbase + (uint64_t)blockIdx.x * EXP_WIN;
-    const uint32_t lane = threadIdx.x & 63u;
     // forward windows [b0, b0 + EXP_WIN) are the RC strand's windows [rc_top - (b0 + EXP_WIN - 1), rc_top - b0]
     uint64_t w0_fw, w0_rc;
     {
@@ -775,28 +733,14 @@ k_seed_expand(const SeedArgs a, uint64_t wbase, uint64_t nwin, const uint64_t *_
             v[q] = f < nf ? f_pre[f] : 0u;
             s += v[q];
         }
-        uint32_t inc = s;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t u = __shfl_up(inc, o, 64);
-            if (lane >= (uint32_t)o) inc += u;
-        }
-        if (lane == 63) scan_tmp[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        uint32_t woff = 0, tot = 0;
-        for (uint32_t k = 0; k < EXP_TPB / 64; k++) {
-            const uint32_t x = scan_tmp[k];
-            if (k < (threadIdx.x >> 6)) woff += x;
-            tot += x;
-        }
-        total = tot;
-        uint32_t run = woff + inc - s;
+        uint32_t run = sco_block_sum<EXP_TPB / 64, false>(s, scan_tmp, &total);      // (the barrier below comes before scan_tmp is next written)
 #pragma unroll
         for (int q = 0; q < EXP_R; q++) {
             const uint32_t f = threadIdx.x * EXP_R + q;
             if (f < nf) f_pre[f] = run;
             run += v[q];
         }
-        if (threadIdx.x == 0) f_pre[nf] = tot;            // the end of the last range
+        if (threadIdx.x == 0) f_pre[nf] = total;          // the end of the last range
     }
     __syncthreads();
     // the hits: pair o of the block = entry (o - prefix[f]) of the window f that holds it

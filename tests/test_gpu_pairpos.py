@@ -55,15 +55,21 @@ def test_reference_fixtures_both_directions(path):
 
 
 @pytest.mark.parametrize("W", [4, 8])
-@pytest.mark.parametrize("pairs", [0, 1, 2, 63, 64, 65, 8191, 8192, 8193, 1_000_000])
+@pytest.mark.parametrize("pairs", [0, 1, 2, 63, 64, 65, 4095, 4096, 4097, 8191, 8192, 8193, 1_000_000, 1_048_577, 2_100_000])
 def test_random_settings_equal_the_restatement(pairs, W):
+    """(the device scans work in blocks of 4096 elements and carry a running fold from one round of 256 blocks to the next: 4095
+    to 4097 pairs lie around one block; 1 048 577 pairs put the scans over the pairs one element past a round; at 2 100 000
+    pairs, generated without near pairs, the scans over the far pairs alone lie past a round too, which is asserted)"""
     dec = PgRCDecoder(100, device=0)
     for rep in range(3 if pairs < 100_000 else 1):
         seed = 7000 + 10 * pairs % 9973 + 3 * rep + W
         knobs = [pp.DEFAULT_MIX, dict(near=0.2, jump=0.3, ret=0.15, tie=0.3, special=0.2),
                  dict(near=0.0, jump=0.05, ret=0.02, tie=0.0, special=0.01, drift=30000)][rep]
+        if pairs > 1_000_000:
+            knobs = dict(pp.DEFAULT_MIX, near=0.0)
         org = pp.make_positions(seed, pairs, W, **knobs)
         want = pp.compress_literal(org, W)
+        assert pairs < 2_000_000 or np.asarray(want["delta16_flag"]).size > 1_048_576
         got = dec.compressReadsPgPositions(org, W)
         assert_streams(got, want)
         assert np.array_equal(dec.decompressReadsPgPositions(want), pp.decompress_literal(want))

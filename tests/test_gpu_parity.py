@@ -373,15 +373,27 @@ def test_bad_symbols_and_errors():
 
 
 def test_mismatch_extraction():
-    pg, reads = make_inputs(200000, 5000, 100, seed=44, n_with_n=300)
+    _check_mismatch_extraction(200000, 5000, 300)
+
+
+@pytest.mark.parametrize("pg_len,n_reads", [(200000, 4096), (200000, 4097), (3_000_000, 1_100_000)])
+def test_mismatch_extraction_around_the_scan_blocks(pg_len, n_reads):
+    """the scan of the counts works in blocks of 4096 reads and carries a running sum from one round of 256 blocks to the next:
+    exactly one block, one read more, and more than one round (1 048 576 reads)"""
+    _check_mismatch_extraction(pg_len, n_reads, 300)
+
+
+def _check_mismatch_extraction(pg_len, n_reads, n_with_n):
+    pg, reads = make_inputs(pg_len, n_reads, 100, seed=44, n_with_n=n_with_n)
     g = gpu_match("c", pg, reads, 38, 33, 0)
     ctx = g["ctx"]
     n = reads.shape[0]
     for flags in (None, (g["rc"] != (np.arange(n) & 1)).astype(np.uint8)):
         cum, codes, offs = ctx.extract_mismatches(flags)
         cnt = np.where(g["mism"] == 255, 0, g["mism"]).astype(np.uint64)
-        assert np.array_equal(np.diff(cum), cnt)
-        for i in np.flatnonzero(cnt)[:1500]:
+        assert cum.size == n + 1 and cum[0] == 0 and np.array_equal(np.diff(cum), cnt)
+        idx = np.flatnonzero(cnt)
+        for i in np.unique(np.concatenate([idx[:1500], idx[-500:]])):      # (the last reads: behind every block of the scan)
             rev = bool(g["rc"][i]) if flags is None else bool(flags[i])
             co, oo = orc.oracle_extract(pg, g["pos"][i], reads[i], g["rc"][i], rev, int(cnt[i]))
             s, e = int(cum[i]), int(cum[i + 1])

@@ -5,7 +5,7 @@ WRITE_SIZE passes of tools/pmc_groups.sh: bytes summed over every dispatch of th
 profiles/r05_ubench_gather_pmc.txt); WRITE_SIZE is exact.  usage: tools/pmc_seed_traffic.py <pmc dir> <out.json> <workload>"""
 import csv, glob, json, os, sys
 root, out, wl = sys.argv[1:4]
-KERNS = ("k_seed_", "k_rx_", "k_sco_", "k_psc_")
+KERNS = ("k_seed_", "k_rx_", "k_sco_")
 tot = {"FETCH_SIZE": 0.0, "WRITE_SIZE": 0.0}
 per = {}
 steps = {}

@@ -35,7 +35,7 @@ for f in sorted(glob.glob(os.path.join(root, "**", "*counter_collection.csv"), r
     for cn in ("FETCH_SIZE", "WRITE_SIZE"):
         if cn in names:
             idx[cn] += sum(float(r["Counter_Value"]) * 1024.0 for r in rows if r["Counter_Name"] == cn and
-                           any(k in r["Kernel_Name"] for k in ("k_os_", "k_ps_", "k_psc_")))
+                           any(k in r["Kernel_Name"] for k in ("k_os_", "k_ps_", "k_sco_")))
             if cn == "FETCH_SIZE":
                 nm = sum(1 for r in rows if r["Counter_Name"] == cn and kern in r["Kernel_Name"])
                 steps = nm // per_step if per_step else 0
