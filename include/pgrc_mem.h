@@ -56,6 +56,42 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *ctx, const char *dest, uint64_t n2, int d
                          uint32_t min_match_len, pgrc_text_match **matches, uint64_t *count);
 void pgrc_mem_free_matches(pgrc_text_match *matches);
 
+/* markAndRemoveExactMatches (matching/SimplePgMatcher.cpp:69-148), the second half of SimplePgMatcher::matchPgsInPg, on
+ * the device: the matches are normalised (correctDestPositionDueToRevComplMatching, :58-61;
+ * resolveMappingCollisionsInTheSameText, :157-171), sorted, made unique and walked greedily; every kept match becomes one
+ * '%' in the text, one entry of the offsets stream (4 bytes when the source length <= UINT32_MAX, else 8, little endian)
+ * and one byte-frugal value of the lengths stream, which leads with min_match_len.
+ *
+ * It maps the destination of the LAST SUCCESSFUL pgrc_mem_match_texts of this context, which is still packed in HBM (no
+ * text is uploaded): the context remembers that call's n2, dest_is_src and rev_compl_matching.  pgrc_mem_set_src_ascii
+ * and a failed pgrc_mem_match_texts forget them (PGRC_E_STATE here).  The mapped text is the destination in its forward
+ * orientation, i.e. destPg itself, not the reverse complement that was matched.  A destination shorter than the index's
+ * K-mer has no window to match, but pgrc_mem_match_texts still packs it to HBM so that it can be mapped.  One exception:
+ * such a short destination that holds a symbol outside ACGNT is accepted by pgrc_mem_match_texts as it always was (no
+ * window reads it), but it is not remembered: PGRC_E_STATE here.
+ *
+ * matches: a host array in matchTexts' coordinates, normally what that call returned (it need not be: symbols are not
+ * compared).  min_match_len: UINT32_MAX = the target match length.  mapped_out: the caller's buffer (pageable or
+ * page-locked) of mapped_cap >= n2 bytes; it may be the destination string's own storage -- the library does not read the
+ * host text.  The two streams come in one block the library allocates; pgrc_mem_free_mapping frees it and clears *out.
+ * count == 0: the text unchanged, an empty map_off and a map_len that holds min_match_len alone (what the reference
+ * writes when a matcher exists and finds nothing).
+ *
+ * PGRC_E_PARAM (with *out cleared, the context still usable): mapped_cap < n2; a match with length 0, with
+ * pos_src + length > the source length or with pos_dest + length > n2; min_match_len == 0.
+ *
+ * Out of scope: the case without a matcher (a source shorter than the target length: SimplePgMatcher writes the text
+ * and no streams) and the entropy coding of the three results; both stay with the caller. */
+typedef struct {
+    uint64_t mapped_len;                      /* bytes written to mapped_out */
+    uint64_t marks, unique_matches, matched_symbols; /* unique_matches: different normalised (dest, src, length) triples */
+    uint8_t *map_off; uint64_t map_off_bytes; /* marks x 4 or 8 */
+    uint8_t *map_len; uint64_t map_len_bytes; /* leads with min_match_len */
+} pgrc_mem_mapping;
+int pgrc_mem_mark_and_remove(pgrc_mem_ctx *ctx, const pgrc_text_match *matches, uint64_t count, uint32_t min_match_len,
+                             char *mapped_out, uint64_t mapped_cap, pgrc_mem_mapping *out);
+void pgrc_mem_free_mapping(pgrc_mem_mapping *m);
+
 /* introspection (tests, bench) */
 typedef struct {
     uint64_t probes;       /* destination windows hashed */
@@ -68,6 +104,9 @@ typedef struct {
     uint32_t event_blocks; /* blocks of 256 windows that hold events */
 } pgrc_mem_counters;
 int pgrc_mem_get_counters(pgrc_mem_ctx *ctx, pgrc_mem_counters *out);
+/* phases of the last pgrc_mem_mark_and_remove in milliseconds: [0] normalise + sort + unique, [1] the greedy path,
+ * [2] marks and both streams, [3] the text kernel (device events), [4] the downloads (host clock) */
+int pgrc_mem_mapping_timing(pgrc_mem_ctx *ctx, float ms[5]);
 
 #ifdef __cplusplus
 }

@@ -41,4 +41,28 @@ namespace PgTools {
         pgrc_mem_free_matches(m);
         callsServed++;
     }
+
+    uint64_t HipTextMatcher::markAndRemoveExactMatches(const vector<TextMatch> &matches, string &destPg, string &resPgMapOff,
+                                                       string &resPgMapLen, uint32_t minMatchLength) {
+        static_assert(sizeof(pgrc_text_match) == 3 * sizeof(uint64_t), "pgrc_text_match is three 64-bit words");
+        vector<pgrc_text_match> in(matches.size());
+        for (size_t i = 0; i < matches.size(); i++) {
+            in[i].pos_src = matches[i].posSrcText;
+            in[i].length = matches[i].length;
+            in[i].pos_dest = matches[i].posDestText;
+        }
+        pgrc_mem_mapping mp;
+        const int e = pgrc_mem_mark_and_remove(ctx, in.data(), in.size(), minMatchLength, (char *) destPg.data(),
+                                               destPg.length(), &mp);
+        if (e) {
+            fprintf(stderr, "HipTextMatcher: %s (error %d)\n", pgrc_mem_last_error(ctx), e);
+            exit(EXIT_FAILURE);
+        }
+        destPg.resize(mp.mapped_len);
+        resPgMapOff.assign((const char *) mp.map_off, mp.map_off_bytes);
+        resPgMapLen.assign((const char *) mp.map_len, mp.map_len_bytes);
+        const uint64_t marks = mp.marks;
+        pgrc_mem_free_mapping(&mp);
+        return marks;
+    }
 }

@@ -28,6 +28,15 @@ namespace PgTools {
         void matchTexts(vector<TextMatch> &resMatches, const string &destText, bool destIsSrc, bool revComplMatching,
                         uint32_t minMatchLength) override;
 
+        // The second half of SimplePgMatcher::markAndRemoveExactMatches (matching/SimplePgMatcher.cpp:85-143) on the device, for the
+        // destination of the last matchTexts call: `matches` as that call returned them (BEFORE
+        // correctDestPositionDueToRevComplMatching and resolveMappingCollisionsInTheSameText: the library applies both), destPg
+        // the text in its forward orientation -- only its storage is used: the mapped text is written over it and it is
+        // resized, as the reference's memmove loop leaves it.  minMatchLength: UINT32_MAX = the target length.
+        // -> the number of marks
+        uint64_t markAndRemoveExactMatches(const vector<TextMatch> &matches, string &destPg, string &resPgMapOff,
+                                           string &resPgMapLen, uint32_t minMatchLength = UINT32_MAX);
+
         static uint64_t callsServed;     // diagnostics / tests
     };
 }

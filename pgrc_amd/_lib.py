@@ -94,6 +94,12 @@ class MemCounters(C.Structure):
                 ("ms_replay", C.c_float), ("replay_rounds", C.c_uint32), ("event_blocks", C.c_uint32)]
 
 
+class MemMapping(C.Structure):   # pgrc_mem_mapping (include/pgrc_mem.h)
+    _fields_ = [("mapped_len", C.c_uint64), ("marks", C.c_uint64), ("unique_matches", C.c_uint64), ("matched_symbols", C.c_uint64),
+                ("map_off", C.POINTER(C.c_uint8)), ("map_off_bytes", C.c_uint64), ("map_len", C.POINTER(C.c_uint8)),
+                ("map_len_bytes", C.c_uint64)]
+
+
 # every symbol include/pgrc_match.h and include/pgrc_mem.h declare: (name, restype, argtypes)
 _P = C.c_void_p
 _PROTOS = [
@@ -155,6 +161,9 @@ _PROTOS = [
                                        C.POINTER(C.c_uint64)]),
     ("pgrc_mem_free_matches", None, [C.POINTER(TextMatch)]),
     ("pgrc_mem_get_counters", C.c_int, [_P, C.POINTER(MemCounters)]),
+    ("pgrc_mem_mark_and_remove", C.c_int, [_P, C.POINTER(TextMatch), C.c_uint64, C.c_uint32, _P, C.c_uint64, C.POINTER(MemMapping)]),
+    ("pgrc_mem_free_mapping", None, [C.POINTER(MemMapping)]),
+    ("pgrc_mem_mapping_timing", C.c_int, [_P, C.POINTER(C.c_float * 5)]),
     # include/pgrc_reads.h
     ("pgrc_divider_create", C.c_int, [C.POINTER(DivideParams), C.POINTER(_P)]),
     ("pgrc_divider_destroy", None, [_P]),

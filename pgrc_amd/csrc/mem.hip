@@ -39,32 +39,8 @@
 #include "ctx.h"
 #include "devutil.h"
 #include "headfmt.h"
+#include "memctx.h"
 #include "pgrc_mem.h"
-
-struct pgrc_mem_ctx {
-    pgrc_match_ctx *base = nullptr;   // owns the packed source, its reverse complement and the seed index
-    uint32_t L = 0;
-    int K = 0, k1 = 0, k2 = 0, LK2 = 0, KLK24 = 0;
-    const char *src = nullptr;        // borrowed host text
-    uint64_t N = 0;
-    bool have_src = false;
-    DevBuf d_dest, d_nmap, d_stage, d_flag, d_cursor, d_evk[2], d_evv[2], d_tmp, d_scan, d_orun, d_oflag;
-    DevBuf d_skey[2], d_sidx[2], d_first, d_runid, d_rstart, d_rend;   // events by (diagonal, window): sort ping-pong, runs
-    DevBuf d_rdend, d_outc, d_ebstart, d_ebin, d_ebout, d_ebinc, d_small, d_match;   // the replay: per run, per event, per event block
-    hipEvent_t ev[5]{};               // phase timing (created on first use)
-    bool have_ev = false;
-    pgrc_mem_counters ctr{};
-    std::string err;
-};
-
-#define MEM_TRY(m, expr)                                                                     \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            (m)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                   \
-            return pgrc_hip_code(e__);                                                       \
-        }                                                                                    \
-    } while (0)
 
 static thread_local std::string g_mem_create_err; // reported by pgrc_mem_last_error(NULL)
 
@@ -696,6 +672,7 @@ void pgrc_mem_destroy(pgrc_mem_ctx *m) {
                       &m->d_sidx[1], &m->d_first, &m->d_runid, &m->d_rstart, &m->d_rend, &m->d_rdend, &m->d_outc, &m->d_ebstart,
                       &m->d_ebin, &m->d_ebout, &m->d_ebinc, &m->d_small, &m->d_match};
     for (DevBuf *b : bufs) pgrc_buf_free(*b);
+    pgrc_pgmap_release(m);
     if (m->have_ev)
         for (auto &x : m->ev) (void)hipEventDestroy(x);
     pgrc_match_destroy(m->base);
@@ -712,6 +689,7 @@ int pgrc_mem_set_src_ascii(pgrc_mem_ctx *m, const char *src, uint64_t n) {
     if (!m || !src) return PGRC_E_PARAM;
     pgrc_match_ctx *c = m->base;
     m->have_src = false;
+    m->map_ready = false;
     PgrcDeviceScope dev_scope__(c->device);
     if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     const auto t0 = std::chrono::steady_clock::now();
@@ -736,6 +714,7 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     if (!m || !dest || !matches || !count) return PGRC_E_PARAM;
     *matches = nullptr;
     *count = 0;
+    m->map_ready = false;                 // (a failed call leaves no destination for pgrc_mem_mark_and_remove)
     if (!m->have_src) { m->err = "match_texts: set the source text first"; return PGRC_E_STATE; }
     pgrc_match_ctx *c = m->base;
     if ((int)min_len < m->K) { m->err = "Minimal matching length cannot be smaller than K"; return PGRC_E_PARAM; }   // :606-609
@@ -747,7 +726,6 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     const uint64_t K = (uint64_t)m->K, k2 = (uint64_t)m->k2;
     const uint64_t nprobes = N2 >= K ? (N2 - K) / k2 + 1 : 0;          // windows q = t * k2 with q + K <= N2
     m->ctr.probes = nprobes;
-    if (nprobes == 0) return PGRC_OK;
     int e;
     if (!m->have_ev) {
         for (auto &x : m->ev) MEM_TRY(m, hipEventCreate(&x));
@@ -770,7 +748,7 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     } else {
         const uint64_t CH = 64ull << 20;
         if ((e = pgrc_buf_ensure(c, m->d_dest, (dwords + PGRC_PG_PAD_WORDS) * 4)) || (e = pgrc_buf_ensure(c, m->d_nmap, (dwords + PGRC_PG_PAD_WORDS) * 2)) ||
-            (e = pgrc_buf_ensure(c, m->d_stage, (size_t)std::min(CH, N2))) || (e = pgrc_buf_ensure(c, m->d_flag, 4))) { m->err = c->err; return e; }
+            (e = pgrc_buf_ensure(c, m->d_stage, (size_t)std::max<uint64_t>(16, std::min(CH, N2)))) || (e = pgrc_buf_ensure(c, m->d_flag, 4))) { m->err = c->err; return e; }
         (void)hipMemsetAsync(m->d_dest.p, 0, (dwords + PGRC_PG_PAD_WORDS) * 4, c->stream);
         (void)hipMemsetAsync(m->d_nmap.p, 0, (dwords + PGRC_PG_PAD_WORDS) * 2, c->stream);
         (void)hipMemsetAsync(m->d_flag.p, 0, 4, c->stream);
@@ -788,11 +766,23 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
         }
         uint32_t fl = 0;
         MEM_TRY(m, hipMemcpy(&fl, m->d_flag.p, 4, hipMemcpyDeviceToHost));
+        // no window reads it: no error, as before texts shorter than K were uploaded; but it cannot be mapped (pgrc_mem.h)
+        if ((fl & 1u) && nprobes == 0) return PGRC_OK;
         if (fl & 1u) { m->err = "destination text contains a symbol outside ACGNT"; return PGRC_E_SYMBOL; }
         a.dest = (const uint32_t *)m->d_dest.p;
         a.nmap = (fl & 2u) ? (const uint16_t *)m->d_nmap.p : nullptr;
         a.dest_words_alloc = dwords + PGRC_PG_PAD_WORDS;
     }
+    // the destination is resident from here on: what pgrc_mem_mark_and_remove maps once this call has succeeded
+    auto done = [&]() {
+        m->map_ready = true;
+        m->map_n2 = N2;
+        m->map_dest_is_src = dest_is_src != 0;
+        m->map_rev_compl = rev_compl != 0;
+        m->map_has_n = a.nmap != nullptr;
+        return PGRC_OK;
+    };
+    if (nprobes == 0) return done();      // (a text shorter than K: no window, no match)
     a.src = (const uint32_t *)c->pg2[0].p;
     a.N = m->N;
     a.N2 = N2;
@@ -843,7 +833,7 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     m->ctr.ms_sort = m->ctr.ms_extend = m->ctr.ms_replay = m->ctr.ms_host = 0.f;
     (void)hipEventSynchronize(ev[1]);
     (void)hipEventElapsedTime(&m->ctr.ms_probe, ev[0], ev[1]);
-    if (!nev) return PGRC_OK;
+    if (!nev) return done();
     if (nev >= 0xFFFFFFF0ull) { m->err = "more than 2^32 events"; return PGRC_E_PARAM; }
 
     // ---- 2. the order in which the reference meets them: by window, then by bucket order
@@ -1002,7 +992,7 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     (void)hipEventElapsedTime(&m->ctr.ms_extend, ev[2], ev[3]);
     (void)hipEventElapsedTime(&m->ctr.ms_replay, ev[3], ev[4]);                       // (with the host's part between the rounds)
     m->ctr.ms_host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - th0).count();
-    return PGRC_OK;
+    return done();
 }
 
 } // extern "C"

@@ -29,6 +29,7 @@ class CopMEMMatcher:
             raise PgrcMatchError(rc, (lib.pgrc_mem_last_error(None) or b"").decode())
         self.targetMatchLength = int(targetMatchLength)
         self._src = _ascii(srcText)          # the library borrows the text: keep it alive
+        self._last_n2 = 0
         self._ck(lib.pgrc_mem_set_src_ascii(self._h, self._src.ctypes.data_as(C.c_void_p), self._src.size))
 
     def _ck(self, rc: int) -> None:
@@ -39,6 +40,7 @@ class CopMEMMatcher:
         """-> uint64 array [count, 3] of (posSrcText, length, posDestText), discovery order.  destText is the text as
         SimplePgMatcher hands it over (already reverse-complemented when revComplMatching)."""
         d = _ascii(destText)
+        self._last_n2 = 0
         out = C.POINTER(_lib.TextMatch)()
         cnt = C.c_uint64(0)
         self._ck(lib.pgrc_mem_match_texts(self._h, d.ctypes.data_as(C.c_void_p), d.size, int(bool(destIsSrc)),
@@ -46,11 +48,39 @@ class CopMEMMatcher:
                                           self.targetMatchLength if minMatchLength is None else int(minMatchLength),
                                           C.byref(out), C.byref(cnt)))
         n = cnt.value
+        self._last_n2 = d.size               # (the destination stays on the device: markAndRemoveExactMatches maps it)
         res = np.zeros((n, 3), dtype=np.uint64)
         if n:
             res[:] = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint64)), shape=(n * 3,)).reshape(n, 3)
             lib.pgrc_mem_free_matches(out)
         return res
+
+    def markAndRemoveExactMatches(self, matches, minMatchLength: int | None = None, mapped_out: np.ndarray | None = None):
+        """markAndRemoveExactMatches (matching/SimplePgMatcher.cpp:69-148) of the destination of the last matchTexts call,
+        which is still on the device: matches as matchTexts returns them (uint64 [count, 3]).
+        -> (mapped, map_off, map_len, info) as uint8 arrays; info: marks, unique_matches, matched_symbols.  mapped_out: a uint8 buffer of at least the destination's length to write the mapped text into (it may
+        be the destination text itself); the returned `mapped` is then a view of it."""
+        mt = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+        n2 = self._last_n2
+        buf = np.empty(max(n2, 1), dtype=np.uint8) if mapped_out is None else mapped_out
+        if buf.dtype != np.uint8 or not buf.flags.c_contiguous or not buf.flags.writeable:
+            raise ValueError("mapped_out: a writeable contiguous uint8 array")
+        mp = _lib.MemMapping()
+        self._ck(lib.pgrc_mem_mark_and_remove(self._h, C.cast(mt.ctypes.data_as(C.c_void_p), C.POINTER(_lib.TextMatch)), mt.shape[0],
+                                              UINT32_MAX if minMatchLength is None else int(minMatchLength),
+                                              buf.ctypes.data_as(C.c_void_p), buf.size if n2 else 0, C.byref(mp)))
+        off = np.ctypeslib.as_array(mp.map_off, shape=(mp.map_off_bytes,)).copy() if mp.map_off_bytes else np.zeros(0, np.uint8)
+        lens = np.ctypeslib.as_array(mp.map_len, shape=(mp.map_len_bytes,)).copy()
+        info = {"marks": mp.marks, "unique_matches": mp.unique_matches, "matched_symbols": mp.matched_symbols}
+        mapped = buf[:mp.mapped_len]
+        lib.pgrc_mem_free_mapping(C.byref(mp))
+        return mapped, off, lens, info
+
+    def mapping_timing(self) -> dict:
+        """phases of the last markAndRemoveExactMatches in milliseconds (introspection: tests, tools)"""
+        ms = (C.c_float * 5)()
+        self._ck(lib.pgrc_mem_mapping_timing(self._h, C.byref(ms)))
+        return dict(zip(("ms_sort", "ms_path", "ms_streams", "ms_text", "ms_download"), (float(x) for x in ms)))
 
     def counters(self) -> dict:
         c = _lib.MemCounters()
