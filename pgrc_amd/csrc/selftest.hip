@@ -1,0 +1,331 @@
+// selftest.hip -- test entries into the shared primitives: scanops.h's block scan and device scan, radix.hip's stable sort and
+// segment sort.  Thin kernels and host wrappers, nothing else; linked with the product's objects into libpgrc_selftest.so
+// (never into libpgrc_match.so).  tests/test_gpu_primitives.py drives it against numpy.
+//
+// Every entry takes host arrays, runs on the handle's device and returns host arrays.  Every device buffer that a primitive
+// writes has a guard zone of ST_GUARD elements after its logical end, filled with ST_FILL bytes like the buffer itself; the
+// entry reports in *guards which zones are still intact (one bit per zone).  The scan's fold scratch has exactly
+// sco_scratch_elems(n) elements in front of its guard.
+//
+// Two preconditions of the primitives are met by construction and are not tested:
+//   * the uint4 fast path of the u32 scan needs in.p aligned to 16 bytes (the buffers come straight from hipMalloc);
+//   * sco_block_exclusive<NWV = 0> needs blockDim.x to be a multiple of 64 (the entry refuses anything else).
+#include <vector>
+
+#include "ctx.h"
+#include "scanops.h"
+
+#define ST_GUARD 64
+#define ST_FILL 0xA5
+
+struct pgrc_selftest {
+    pgrc_match_ctx *mc = nullptr;       // never run as a matcher: the device, the stream, the error string and radix.hip's scratch growth
+    DevBuf sort_scratch;
+};
+
+namespace {
+
+struct StBuf {                          // `bytes` logical bytes and `guard` bytes after them, all ST_FILL at first
+                                        // (and 16 spare bytes behind the guard, unchecked: an empty buffer without a guard, the
+                                        // input of n = 0, is still a real allocation)
+    uint8_t *p = nullptr;
+    size_t bytes = 0, guard = 0;
+    ~StBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t logical, size_t guard_bytes) {
+        bytes = logical;
+        guard = guard_bytes;
+        hipError_t e = hipMalloc((void **)&p, bytes + guard + 16);
+        if (e != hipSuccess) return e;
+        return hipMemset(p, ST_FILL, bytes + guard + 16);
+    }
+    hipError_t intact(bool *ok) const {
+        std::vector<uint8_t> h(guard);
+        hipError_t e = hipMemcpy(h.data(), p + bytes, guard, hipMemcpyDeviceToHost);
+        *ok = true;
+        for (uint8_t b : h) *ok &= b == ST_FILL;
+        return e;
+    }
+};
+
+// the operators of the library's scans, restated (their originals live in mem.hip, pgmap.hip and pairpos.hip)
+struct StIsOne { __device__ uint32_t operator()(uint8_t x) const { return x == 1u ? 1u : 0u; } };
+struct StMax { __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a > b ? a : b; } };
+#define ST_NONE 0xFFFFFFFFu
+struct StLastValid { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return b != ST_NONE ? b : a; } };
+struct __attribute__((packed, aligned(4))) StSeg {      // 12 bytes: three words to shuffle
+    int64_t v;
+    uint32_t set;
+};
+struct StSegOp { __device__ StSeg operator()(StSeg a, StSeg b) const { return b.set ? b : StSeg{a.v + b.v, a.set}; } };
+
+enum {
+    ST_U32_SUM_U32 = 0,     // sco_scan, identity transform (uint4 loads on whole blocks)
+    ST_U32_FLAG_U8 = 1,     // sco_scan through a predicate
+    ST_U64_SUM_U8 = 2,      // sco_sum_u64 (start = 0, total) / sco_device_scan with start
+    ST_U64_SUM_U16 = 3,
+    ST_U64_SUM_U32 = 4,
+    ST_U64_SUM_U64 = 5,
+    ST_U64_MAX = 6,
+    ST_U32_LAST_VALID = 7,  // non-commuting, identity ST_NONE
+    ST_SEG_SUM = 8,         // the 12-byte (int64, set) element
+    ST_KINDS = 9
+};
+const size_t k_in_size[ST_KINDS] = {4, 1, 1, 2, 4, 8, 8, 4, 12}, k_t_size[ST_KINDS] = {4, 4, 8, 8, 8, 8, 8, 4, 12};
+
+template <typename In>
+hipError_t st_sum_u64(hipStream_t s, const void *in, uint64_t n, uint64_t start, bool inclusive, bool total, uint64_t *out, uint64_t *fold) {
+    const In *p = (const In *)in;
+    if (total && !start) return inclusive ? sco_sum_u64<true>(s, p, n, out, fold) : sco_sum_u64<false>(s, p, n, out, fold);
+    const ScoLoad<uint64_t, In, ScoIdentity> ld{p, ScoIdentity{}};
+    const ScoStore<uint64_t> st{out};
+    if (total)
+        return inclusive ? sco_device_scan<true, true>(s, ld, n, ScoPlus{}, (uint64_t)0, start, st, fold)
+                         : sco_device_scan<false, true>(s, ld, n, ScoPlus{}, (uint64_t)0, start, st, fold);
+    return inclusive ? sco_device_scan<true, false>(s, ld, n, ScoPlus{}, (uint64_t)0, start, st, fold)
+                     : sco_device_scan<false, false>(s, ld, n, ScoPlus{}, (uint64_t)0, start, st, fold);
+}
+
+template <typename In, typename Xf, typename Op>
+hipError_t st_scan_u32(hipStream_t s, const void *in, void *out, uint64_t n, bool inclusive, Xf xf, Op op, uint32_t ident, void *fold) {
+    return inclusive ? sco_scan<true>(s, (const In *)in, (uint32_t *)out, n, xf, op, ident, (uint32_t *)fold)
+                     : sco_scan<false>(s, (const In *)in, (uint32_t *)out, n, xf, op, ident, (uint32_t *)fold);
+}
+
+template <typename T, typename Op>
+hipError_t st_scan_plain(hipStream_t s, const void *in, void *out, uint64_t n, bool inclusive, Op op, T ident, void *fold) {
+    const ScoLoad<T, T, ScoIdentity> ld{(const T *)in, ScoIdentity{}};
+    const ScoStore<T> st{(T *)out};
+    return inclusive ? sco_device_scan<true, false>(s, ld, n, op, ident, ident, st, (T *)fold)
+                     : sco_device_scan<false, false>(s, ld, n, op, ident, ident, st, (T *)fold);
+}
+
+// one block: every thread's exclusive value and the total it was handed; then a second scan over the same smem, of
+// op(first exclusive value, the input in reverse thread order)
+template <int NWV, bool SYNC, typename T, typename Op>
+__global__ void __launch_bounds__(1024) k_st_block(const T *__restrict__ in, Op op, T ident, T *__restrict__ ex, T *__restrict__ tot, T *__restrict__ second) {
+    __shared__ T smem[16];
+    const uint32_t t = threadIdx.x;
+    T total, total2;
+    const T e = sco_block_exclusive<NWV, SYNC>(in[t], op, ident, smem, &total);
+    ex[t] = e;
+    tot[t] = total;
+    if (!SYNC) __syncthreads();
+    const T v2 = op(e, in[blockDim.x - 1u - t]);
+    second[t] = sco_block_exclusive<NWV, SYNC>(v2, op, ident, smem, &total2);
+}
+
+template <typename T, typename Op>
+int st_block_run(pgrc_selftest *h, uint32_t threads, bool nwv_static, bool sync_after, const void *in, Op op, T ident, void *ex, void *tot, void *second,
+                 uint32_t *guards) {
+    pgrc_match_ctx *c = h->mc;
+    const size_t bytes = (size_t)threads * sizeof(T);
+    StBuf din, dout[3];
+    HIP_TRY(c, din.alloc(bytes, 0));
+    for (StBuf &b : dout) HIP_TRY(c, b.alloc(bytes, ST_GUARD * sizeof(T)));
+    HIP_TRY(c, hipMemcpy(din.p, in, bytes, hipMemcpyHostToDevice));
+#define ST_LAUNCH(NWV, SYNC)                                                                                                              \
+    hipLaunchKernelGGL((k_st_block<NWV, SYNC, T, Op>), dim3(1), dim3(threads), 0, c->stream, (const T *)din.p, op, ident, (T *)dout[0].p, \
+                       (T *)dout[1].p, (T *)dout[2].p)
+#define ST_CASE(NWV)                 \
+    case NWV:                        \
+        if (sync_after) {            \
+            ST_LAUNCH(NWV, true);    \
+        } else {                     \
+            ST_LAUNCH(NWV, false);   \
+        }                            \
+        break;
+    switch (nwv_static ? threads / 64u : 0u) {
+        ST_CASE(0)
+        ST_CASE(1)
+        ST_CASE(2)
+        ST_CASE(4)
+        ST_CASE(8)
+        ST_CASE(16)
+    default:
+        c->err = "selftest: no block scan for this block size";
+        return PGRC_E_PARAM;
+    }
+#undef ST_CASE
+#undef ST_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    void *host[3] = {ex, tot, second};
+    *guards = 0;
+    for (int k = 0; k < 3; k++) {
+        bool ok;
+        HIP_TRY(c, hipMemcpy(host[k], dout[k].p, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(c, dout[k].intact(&ok));
+        *guards |= (ok ? 1u : 0u) << k;
+    }
+    return PGRC_OK;
+}
+
+}  // namespace
+
+extern "C" int pgrc_selftest_create(int device, pgrc_selftest **out) {
+    *out = nullptr;
+    pgrc_selftest *h = new pgrc_selftest();
+    h->mc = new pgrc_match_ctx();
+    h->mc->device = device;
+    PgrcDeviceScope scope(device);
+    if (!scope.ok || hipStreamCreate(&h->mc->stream) != hipSuccess) {
+        delete h->mc;
+        delete h;
+        return PGRC_E_NO_DEVICE;
+    }
+    *out = h;
+    return PGRC_OK;
+}
+
+extern "C" void pgrc_selftest_destroy(pgrc_selftest *h) {
+    if (!h) return;
+    PgrcDeviceScope scope(h->mc->device);
+    (void)hipStreamSynchronize(h->mc->stream);
+    pgrc_buf_free(h->sort_scratch);
+    (void)hipStreamDestroy(h->mc->stream);
+    delete h->mc;
+    delete h;
+}
+
+extern "C" const char *pgrc_selftest_last_error(const pgrc_selftest *h) { return h->mc->err.c_str(); }
+
+extern "C" uint64_t pgrc_selftest_scratch_elems(uint64_t n) { return sco_scratch_elems(n); }
+
+// out: n + 1 elements of the kind's output type (element n is ST_FILL bytes unless the scan wrote a total there).
+// *guards: bit 0 the zone after out[n], bit 1 the zone after the fold scratch.  in_place: the scan reads what it writes (kinds
+// whose input and output elements have one size).  start and total_at_n: the u64 sums only.
+extern "C" int pgrc_selftest_device_scan(pgrc_selftest *h, int kind, const void *in, uint64_t n, uint64_t start, int inclusive, int total_at_n, int in_place,
+                                         void *out, uint32_t *guards) {
+    pgrc_match_ctx *c = h->mc;
+    PGRC_ON_DEVICE(c);
+    const bool u64sum = kind >= ST_U64_SUM_U8 && kind <= ST_U64_SUM_U64;
+    if (kind < 0 || kind >= ST_KINDS || (!u64sum && (start || total_at_n)) || (in_place && k_in_size[kind] != k_t_size[kind])) {
+        c->err = "selftest: no such scan";
+        return PGRC_E_PARAM;
+    }
+    const size_t isz = k_in_size[kind], tsz = k_t_size[kind];
+    StBuf din, dout, dfold;
+    HIP_TRY(c, dout.alloc((n + 1) * tsz, ST_GUARD * tsz));
+    HIP_TRY(c, dfold.alloc(sco_scratch_elems(n) * tsz, ST_GUARD * tsz));
+    if (!in_place) HIP_TRY(c, din.alloc(n * isz, 0));
+    const void *src = in_place ? dout.p : din.p;
+    if (n) HIP_TRY(c, hipMemcpy((void *)src, in, n * isz, hipMemcpyHostToDevice));
+    hipStream_t s = c->stream;
+    const bool inc = inclusive != 0;
+    hipError_t e = hipSuccess;
+    switch (kind) {
+    case ST_U32_SUM_U32: e = st_scan_u32<uint32_t>(s, src, dout.p, n, inc, ScoIdentity{}, ScoPlus{}, 0u, dfold.p); break;
+    case ST_U32_FLAG_U8: e = st_scan_u32<uint8_t>(s, src, dout.p, n, inc, StIsOne{}, ScoPlus{}, 0u, dfold.p); break;
+    case ST_U64_SUM_U8: e = st_sum_u64<uint8_t>(s, src, n, start, inc, total_at_n != 0, (uint64_t *)dout.p, (uint64_t *)dfold.p); break;
+    case ST_U64_SUM_U16: e = st_sum_u64<uint16_t>(s, src, n, start, inc, total_at_n != 0, (uint64_t *)dout.p, (uint64_t *)dfold.p); break;
+    case ST_U64_SUM_U32: e = st_sum_u64<uint32_t>(s, src, n, start, inc, total_at_n != 0, (uint64_t *)dout.p, (uint64_t *)dfold.p); break;
+    case ST_U64_SUM_U64: e = st_sum_u64<uint64_t>(s, src, n, start, inc, total_at_n != 0, (uint64_t *)dout.p, (uint64_t *)dfold.p); break;
+    case ST_U64_MAX: e = st_scan_plain<uint64_t>(s, src, dout.p, n, inc, StMax{}, (uint64_t)0, dfold.p); break;
+    case ST_U32_LAST_VALID: e = st_scan_u32<uint32_t>(s, src, dout.p, n, inc, ScoIdentity{}, StLastValid{}, ST_NONE, dfold.p); break;
+    case ST_SEG_SUM: e = st_scan_plain<StSeg>(s, src, dout.p, n, inc, StSegOp{}, StSeg{0, 0u}, dfold.p); break;
+    }
+    HIP_TRY(c, e);
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipMemcpy(out, dout.p, (n + 1) * tsz, hipMemcpyDeviceToHost));
+    bool ok_out, ok_fold;
+    HIP_TRY(c, dout.intact(&ok_out));
+    HIP_TRY(c, dfold.intact(&ok_fold));
+    *guards = (ok_out ? 1u : 0u) | (ok_fold ? 2u : 0u);
+    return PGRC_OK;
+}
+
+// One block of block_threads threads (a multiple of 64, at most 1024).  kind: 0 sum over u32, 1 sum over u64, 2 maximum over
+// u64, 3 the 12-byte segmented sum.  nwv_static: the wave count as a template argument, else NWV = 0.  With sync_after = 0 the
+// kernel puts its own barrier between the two scans.  *guards: bits 0..2, the zones after the three outputs.
+extern "C" int pgrc_selftest_block_scan(pgrc_selftest *h, int kind, uint32_t block_threads, int nwv_static, int sync_after, const void *in, void *out_exclusive,
+                                        void *out_total_per_thread, void *out_second, uint32_t *guards) {
+    pgrc_match_ctx *c = h->mc;
+    PGRC_ON_DEVICE(c);
+    if (!block_threads || block_threads % 64u || block_threads > 1024u) {
+        c->err = "selftest: the block scan needs whole waves, at most 16";
+        return PGRC_E_PARAM;
+    }
+    const bool st = nwv_static != 0, sy = sync_after != 0;
+    switch (kind) {
+    case 0: return st_block_run<uint32_t>(h, block_threads, st, sy, in, ScoPlus{}, 0u, out_exclusive, out_total_per_thread, out_second, guards);
+    case 1: return st_block_run<uint64_t>(h, block_threads, st, sy, in, ScoPlus{}, (uint64_t)0, out_exclusive, out_total_per_thread, out_second, guards);
+    case 2: return st_block_run<uint64_t>(h, block_threads, st, sy, in, StMax{}, (uint64_t)0, out_exclusive, out_total_per_thread, out_second, guards);
+    case 3: return st_block_run<StSeg>(h, block_threads, st, sy, in, StSegOp{}, StSeg{0, 0u}, out_exclusive, out_total_per_thread, out_second, guards);
+    }
+    c->err = "selftest: no such block scan";
+    return PGRC_E_PARAM;
+}
+
+// pgrc_radix_sort_u64 (vals = null) or pgrc_radix_sort_pairs_u64, copied from wherever *sorted points.  *guards: bits 0, 1 the
+// zones after the two key buffers, bits 2, 3 after the two value buffers (set when there are none).
+extern "C" int pgrc_selftest_sort(pgrc_selftest *h, const uint64_t *keys, const uint64_t *vals, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, uint64_t *out_keys,
+                                  uint64_t *out_vals, uint32_t *guards) {
+    pgrc_match_ctx *c = h->mc;
+    PGRC_ON_DEVICE(c);
+    StBuf k[2], v[2];
+    for (StBuf &b : k) HIP_TRY(c, b.alloc(n * 8, ST_GUARD * 8));
+    if (n) HIP_TRY(c, hipMemcpy(k[0].p, keys, n * 8, hipMemcpyHostToDevice));
+    uint64_t *ks = nullptr, *vs = nullptr;
+    int e;
+    if (vals) {
+        for (StBuf &b : v) HIP_TRY(c, b.alloc(n * 8, ST_GUARD * 8));
+        if (n) HIP_TRY(c, hipMemcpy(v[0].p, vals, n * 8, hipMemcpyHostToDevice));
+        e = pgrc_radix_sort_pairs_u64(c, (uint64_t *)k[0].p, (uint64_t *)k[1].p, (uint64_t *)v[0].p, (uint64_t *)v[1].p, n, bit_lo, bit_hi, h->sort_scratch, &ks, &vs);
+    } else {
+        e = pgrc_radix_sort_u64(c, (uint64_t *)k[0].p, (uint64_t *)k[1].p, n, bit_lo, bit_hi, h->sort_scratch, &ks);
+    }
+    if (e) return e;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (n) HIP_TRY(c, hipMemcpy(out_keys, ks, n * 8, hipMemcpyDeviceToHost));
+    if (n && vals) HIP_TRY(c, hipMemcpy(out_vals, vs, n * 8, hipMemcpyDeviceToHost));
+    *guards = vals ? 0u : 12u;
+    for (int i = 0; i < 2; i++) {
+        bool ok;
+        HIP_TRY(c, k[i].intact(&ok));
+        *guards |= (ok ? 1u : 0u) << i;
+        if (vals) {
+            HIP_TRY(c, v[i].intact(&ok));
+            *guards |= (ok ? 4u : 0u) << i;
+        }
+    }
+    return PGRC_OK;
+}
+
+// pgrc_radix_sort_segments_pairs_u64 over seg[0 .. nseg] (seg[nseg] pairs in all), in place.  out_ovl: cap + 1 words, the words
+// the kernel did not write are ST_FILL bytes.  *guards: bits 0, 1 the zones after keys and values, bit 2 after ovl[cap].
+extern "C" int pgrc_selftest_sort_segments(pgrc_selftest *h, const uint64_t *keys, const uint64_t *vals, const uint32_t *seg, uint32_t nseg, uint32_t bit_lo,
+                                           uint32_t bit_hi, uint32_t top_bits, uint32_t cap, uint64_t *out_keys, uint64_t *out_vals, uint32_t *out_ovl,
+                                           uint32_t *guards) {
+    pgrc_match_ctx *c = h->mc;
+    PGRC_ON_DEVICE(c);
+    const uint64_t n = seg[nseg];
+    StBuf k, v, ds, ovl;
+    HIP_TRY(c, k.alloc(n * 8, ST_GUARD * 8));
+    HIP_TRY(c, v.alloc(n * 8, ST_GUARD * 8));
+    HIP_TRY(c, ds.alloc(((size_t)nseg + 1) * 4, 0));
+    HIP_TRY(c, ovl.alloc(((size_t)cap + 1) * 4, ST_GUARD * 4));
+    if (n) {
+        HIP_TRY(c, hipMemcpy(k.p, keys, n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(v.p, vals, n * 8, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(c, hipMemcpy(ds.p, seg, ((size_t)nseg + 1) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(ovl.p, 0, 4));
+    c->opt.test_segment_top_bits = top_bits;
+    const int e = pgrc_radix_sort_segments_pairs_u64(c, (uint64_t *)k.p, (uint64_t *)v.p, (const uint32_t *)ds.p, nseg, bit_lo, bit_hi, (uint32_t *)ovl.p, cap);
+    c->opt.test_segment_top_bits = 0;
+    if (e) return e;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (n) {
+        HIP_TRY(c, hipMemcpy(out_keys, k.p, n * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(out_vals, v.p, n * 8, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(c, hipMemcpy(out_ovl, ovl.p, ((size_t)cap + 1) * 4, hipMemcpyDeviceToHost));
+    bool ok[3];
+    HIP_TRY(c, k.intact(&ok[0]));
+    HIP_TRY(c, v.intact(&ok[1]));
+    HIP_TRY(c, ovl.intact(&ok[2]));
+    *guards = (ok[0] ? 1u : 0u) | (ok[1] ? 2u : 0u) | (ok[2] ? 4u : 0u);
+    return PGRC_OK;
+}

@@ -1,7 +1,8 @@
 """The read rebuild on the device (include/pgrc_decode.h, pgrc_amd/decode.py): rows equal to decode_util's restatement of
 the reference decoder's writers and to the ground truth -- the input reads -- over export streams made on the device and
 over the reference-made streams of the committed fixtures; list shapes at the edges (no RC flags or mismatches, empty
-lists, text spans too large for LDS, a joined text above 2^32 symbols), rows fetched in pieces, bad windows refused;
+lists, lists sized to the device scan's block of 4096 and past its carry round of 1 048 576 entries, text spans too large
+for LDS, a joined text above 2^32 symbols), rows fetched in pieces, bad windows refused;
 and a round trip match -> export -> rebuild at millions of reads."""
 import time
 
@@ -176,6 +177,76 @@ def _hq_with_mismatches(rng, n, L, pos, form):
     return {"text_base": 0, "n": n, "pos": pos, "rc": (rng.random(n) < 0.5).astype(np.uint8), "mis_cnt": cnt,
             "mis_sym": sym, "mis_off": du.offsets_to_rev_offsets(cnt, offs, L).astype(np.uint8), "rev_coded": True,
             "form": form, "order": b"TGNAC" if form == 0 else None}
+
+
+def _mismatch_streams(rng, n, L):
+    """0..3 mismatches per entry at distinct ascending offsets, without a loop over the entries -> (mis_cnt, the offsets in
+    list order, the rev-coded offsets as the stream holds them: per entry L-1 - off[m-1], then off[i+1] - 1 - off[i] downwards)"""
+    cnt = rng.integers(0, 4, n).astype(np.uint8)
+    have = np.arange(3)[None, :] < cnt[:, None]
+    pick = np.argsort(rng.random((n, L)), axis=1)[:, :3]                # three distinct offsets per entry
+    asc = np.sort(np.where(have, pick, L), axis=1)                      # the entry's own come first, ascending
+    desc = np.take_along_axis(asc, np.maximum(cnt[:, None].astype(np.int64) - 1 - np.arange(3)[None, :], 0), axis=1)
+    above = np.concatenate([np.full((n, 1), L), desc[:, :-1]], axis=1)  # what the walk stands behind: L, then the last offset
+    return cnt, asc[have].astype(np.int64), (above - 1 - desc)[have].astype(np.int64)
+
+
+def _scan_edge_job(seed, n_hq, n_lq, T, lq_type, form, L=16):
+    """Hand-made lists that drive the decoder's three scans at given sizes: an HQ list at delta offsets with RC flags and
+    mismatches (the `mcum` scan and its total), an LQ list at delta offsets of `lq_type` behind a non-zero text_base (the
+    positions scan with a start), and T ORD positions on both sides of hqPgLen (the rank scan).  Offsets of 0..3 keep the
+    text at about 1.5 symbols per entry; the u16 list has some above 255."""
+    rng = np.random.default_rng(seed)
+    hq_off = rng.integers(0, 4, n_hq).astype(np.uint8)
+    hq_len = int(hq_off.sum(dtype=np.int64)) + L            # an HQ text ends where its last read ends
+    lq_off = rng.integers(0, 4, n_lq).astype(lq_type)
+    if lq_type is np.uint16:
+        lq_off[rng.integers(0, n_lq, 1 + n_lq // 1000)] = rng.integers(256, 1000, 1 + n_lq // 1000)
+    text = _random_text(rng, hq_len + int(lq_off.sum(dtype=np.int64)) + L)
+    cnt, offs, rev = _mismatch_streams(rng, n_hq, L)
+    assert np.array_equal(du.rev_offsets_to_offsets(cnt, rev, L), offs)
+    if n_hq <= 5000:
+        assert np.array_equal(du.offsets_to_rev_offsets(cnt, offs, L), rev)
+    m = offs.size
+    sym = ((rng.integers(0, 4, m) << 4) | rng.integers(0, 5, m)).astype(np.uint8) if form == 1 else rng.integers(0, 4, m).astype(np.uint8)
+    hq = {"text_base": 0, "n": n_hq, "off": hq_off, "rc": (rng.random(n_hq) < 0.5).astype(np.uint8), "mis_cnt": cnt,
+          "mis_sym": sym, "mis_off": rev.astype(np.uint8), "rev_coded": True, "form": form,
+          "order": b"TGNAC" if form == 0 else None}
+    lq = {"text_base": hq_len, "n": n_lq, "off": lq_off}
+    below = rng.random(T) < 0.5                              # about T / 2 rows below hqPgLen: never more than HQ entries
+    o2p = np.where(below, rng.integers(0, hq_len - L + 1, T), rng.integers(hq_len, text.size - L + 1, T)).astype(np.uint64)
+    assert 0 < hq_len and int(below.sum()) <= n_hq
+    return {"L": L, "text": text, "lists": [hq, lq]}, o2p
+
+
+def _check_scan_edge_job(dc, o2p):
+    dec = decoder(dc)
+    se = dec.writeAllReadsInSEMode()
+    assert se.shape == (dc["lists"][0]["n"] + dc["lists"][1]["n"], dc["L"] + 1)
+    assert np.array_equal(se, du.write_se(dc))
+    (rows,) = dec.writeAllReadsInORDMode(o2p)
+    assert rows.shape == (o2p.size, dc["L"] + 1)
+    assert np.array_equal(rows, du.write_ord(dc, o2p, False, False)[0])
+    dec.close()
+
+
+@pytest.mark.parametrize("lq_type,form", [(np.uint8, 1), (np.uint16, 0)])
+@pytest.mark.parametrize("n", [1, 4095, 4096, 4097])
+def test_lists_at_the_scan_block_edges(n, lq_type, form):
+    """n entries per list and T = n ORD rows around the device scan's block of 4096: the positions scan starts from a
+    text_base other than 0, the mismatch list starts end in their total, the ranks of the HQ rows in theirs"""
+    dc, o2p = _scan_edge_job(100 + n, n, n, n, lq_type, form)
+    assert dc["lists"][1]["text_base"] > 0
+    _check_scan_edge_job(dc, o2p)
+
+
+def test_lists_past_one_carry_round_of_the_scan():
+    """1 048 577 LQ entries at u16 offsets behind a non-zero text_base, an HQ list with mismatches that also crosses
+    1 048 576 entries, and as many ORD rows: the scans' carry kernel goes into its second round of 256 blocks"""
+    n = (1 << 20) + 1
+    dc, o2p = _scan_edge_job(7, n + 22, n, n, np.uint16, 1)
+    assert dc["lists"][1]["text_base"] > 0 and dc["lists"][0]["mis_cnt"].sum(dtype=np.int64) > n
+    _check_scan_edge_job(dc, o2p)
 
 
 def test_tile_span_too_large_for_lds_takes_the_gathers():

@@ -180,6 +180,48 @@ def test_device_made_position_order(n, G, dups):
         assert np.array_equal(got[k], want[k]), (n, G, k, "three shards")
 
 
+@pytest.mark.parametrize("entries,n,G", [(4095, 3000, 120_000), (4096, 3000, 120_000), (4097, 3000, 120_000),
+                                         (1_048_600, 600_000, 4_000_000)])
+def test_entry_counts_at_the_scan_edges(entries, n, G):
+    """Streams of exactly 4095, 4096 and 4097 entries (the device scan's block of 4096) and of more than 1 048 576 (one round
+    of its carry kernel): the u8 -> u64 sums over the entries' mismatch counts and offsets.  Every read is a Pg window, half
+    of them reverse-complemented, with up to two substitutions in its last 20 symbols, so every read matches and the entry
+    count is the reads plus the old list."""
+    L = 100
+    rng = np.random.default_rng(entries)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    pg = acgt[rng.integers(0, 4, G)]
+    reads = pg[rng.integers(0, G - L + 1, n)[:, None] + np.arange(L)]
+    for k in range(2):                               # substitution k of the reads that have more than k
+        r = np.flatnonzero(rng.integers(0, 3, n) > k)
+        c = L - 20 + 10 * k + rng.integers(0, 10, r.size)
+        reads[r, c] = acgt[(np.searchsorted(acgt, reads[r, c]) + rng.integers(1, 4, r.size)) % 4]
+    flip = rng.random(n) < 0.5
+    reads[flip] = orc.revcomp_ascii(reads[flip].reshape(-1)).reshape(-1, L)[::-1]
+    h = entries - n                                  # the old list: h entries up to G - L
+    off = rng.integers(0, 2 * int(0.9 * (G - L) / h) - 1, h).astype(np.uint8)      # (a mean gap of 0.9 (G - L) / h, below 256)
+    assert int(off.sum(dtype=np.int64)) <= G - L
+    perm = rng.permutation(entries).astype(np.uint32)
+    case = {"pg": pg, "reads": reads, "n_n": 0, "L": L, "list_off": off, "list_org": perm[:h].copy(),
+            "list_rc": (rng.random(h) < 0.4).astype(np.uint8), "read_org": np.sort(perm[h:]), "total": entries}
+    g = gpu_match("c", pg, reads, 38, L // 3, 0)
+    assert g["matched"] == n and (g["mism"] != 255).all()
+    res = {k: g[k] for k in ("pos", "rc", "mism")}
+    got = g["ctx"].export_pg_order(None, off, case["list_org"], case["list_rc"], case["read_org"], False, True)
+    assert got["org_idx"].size == entries
+    want = xu.oracle_export_pg_order(case, res, xu.stable_order(res["pos"]))
+    assert want["org_idx"].size == entries and int(want["mis_cnt"].sum(dtype=np.int64)) > n // 2
+    for k in xu.STREAMS:
+        assert np.array_equal(got[k], want[k]), (entries, k)
+    assert got["last_pos"] == want["last_pos"]
+    er, eo = xu.original_order_entries(case["read_org"], res["mism"] != 255, entries, False, n)
+    got = g["ctx"].export_original_order(case["read_org"], entries, False, False, True)
+    want = xu.oracle_export_entries(case, res, er, eo)
+    assert got["org_idx"].size == want["org_idx"].size
+    for k in xu.STREAMS:
+        assert np.array_equal(got[k], want[k]), (entries, "original order", k)
+
+
 def test_order_null_is_only_accepted_without_matched_reads_or_with_the_flag():
     """pgrc_export_pg_order_args.order == NULL: with n_matched > 0 and without order_on_device it is a caller's
     mistake (PGRC_E_PARAM, not silently another tie order); with n_matched == 0 it means "no matched read" -- what

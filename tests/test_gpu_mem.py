@@ -141,6 +141,43 @@ def test_mem_replay_rounds_on_the_device():
         assert check(src, other, what=f"seed {seed}") > 100
 
 
+def low_complexity_pair():
+    """(src, other) of test_mem_low_complexity_past_one_scan_round"""
+    rng = np.random.default_rng(5)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    G, G2 = 600_000, 3_400_000
+    src = acgt[rng.integers(0, 4, G)]
+    other = acgt[rng.integers(0, 4, G2)]
+    src[5000:11000] = ord("A")
+    nb = G2 // 768
+    s = rng.integers(20_000, G - 200, nb)
+    d = np.arange(nb) * 768 + rng.integers(0, 600, nb)
+    back = np.arange(119, -1, -1)
+    other[(d[:, None] + np.arange(120)).reshape(-1)] = acgt[3 - np.searchsorted(acgt, src[(s[:, None] + back).reshape(-1)])]
+    for k in range(12):
+        other[100_000 + k * 270_000: 130_000 + k * 270_000] = ord("T")
+    return src, other
+
+
+def test_mem_low_complexity_past_one_scan_round():
+    """An LQ-like text against an HQ-like source with more than 1 048 576 events in more than 4096 event blocks: the scans of
+    mem.hip (the two run numberings, the event blocks' "last valid" match, the accepted events) go past one round of the
+    carry kernel and past one block of 4096 event blocks.  Twelve poly-T tracts of 30 000 symbols, read reverse-complemented,
+    meet a poly-A tract of 6000 in the source, whose bucket keeps 13 positions: (30 000 - K) / k2 + 1 = 9990 windows a tract
+    with 13 events each (K = 32, k2 = 3), about 1.56 M events; a reverse-complemented copy of 120 source symbols in every
+    block of 768 destination symbols puts events into the 4427 blocks of 256 windows."""
+    from pgrc_amd import CopMEMMatcher
+    src, other = low_complexity_pair()
+    dest = orc.mem_dest(src, other, 0, 1)
+    m = CopMEMMatcher(src, 45)
+    g = m.matchTexts(dest, False, True)
+    c = m.counters()
+    m.close()
+    assert c["events"] > 1_048_576 and c["event_blocks"] > 4096, c
+    o = orc.oracle_mem_match(src, dest, 0, 1)
+    assert len(o) > other.size // 768 and np.array_equal(g, o), (len(g), len(o))
+
+
 def test_mem_event_buffer_regrows(monkeypatch):
     """more events than the first guess of the event buffer: the probe pass is rerun with the exact size"""
     monkeypatch.setenv("PGRC_MEM_EVENT_CAP", "7")
