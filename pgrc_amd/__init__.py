@@ -20,3 +20,4 @@ from .textmatch import CopMEMMatcher  # noqa: F401
 from .readsets import DividedPCLReadsSets  # noqa: F401
 from . import synth  # noqa: F401
 from .decode import PgRCDecoder, compressReadsOrder, compressReadsPgPositions, decompressReadsPgPositions  # noqa: F401
+from .assemble import PgAssembler  # noqa: F401

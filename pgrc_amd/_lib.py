@@ -100,6 +100,25 @@ class MemMapping(C.Structure):   # pgrc_mem_mapping (include/pgrc_mem.h)
                 ("map_len_bytes", C.c_uint64)]
 
 
+class AsmInput(C.Structure):    # pgrc_asm_input (include/pgrc_assemble.h)
+    _fields_ = [("struct_size", C.c_uint32), ("read_len", C.c_uint32), ("symbols", C.c_uint32), ("overlap_width", C.c_uint32),
+                ("n_reads", C.c_uint64), ("packed_rows", C.c_void_p), ("next_read", C.c_void_p), ("overlap", C.c_void_p),
+                ("index_mapping", C.c_void_p)]
+
+
+class AsmResult(C.Structure):   # pgrc_asm_result
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pg_len", C.c_uint64), ("n_reads", C.c_uint64),
+                ("cycles", C.c_uint64), ("overlap_lost", C.c_uint64), ("components", C.c_uint64), ("singles", C.c_uint64),
+                ("org_idx", C.POINTER(C.c_uint32)), ("off", C.POINTER(C.c_uint16))]
+
+
+class AsmTiming(C.Structure):   # pgrc_asm_timing
+    _fields_ = [("struct_size", C.c_uint32), ("passes_cycles", C.c_uint32), ("passes_rank", C.c_uint32), ("ms_upload", C.c_float),
+                ("ms_checks_device", C.c_float), ("ms_cycles_device", C.c_float), ("ms_rank_device", C.c_float),
+                ("ms_lists_device", C.c_float), ("ms_text_device", C.c_float), ("ms_download", C.c_float), ("ms_call", C.c_float),
+                ("bytes_up", C.c_uint64), ("bytes_down", C.c_uint64)]
+
+
 # every symbol include/pgrc_match.h and include/pgrc_mem.h declare: (name, restype, argtypes)
 _P = C.c_void_p
 _PROTOS = [
@@ -175,7 +194,22 @@ _PROTOS = [
     ("pgrc_divider_last_was_terminal", C.c_int, [_P]),
 ]
 
+# include/pgrc_assemble.h (kept apart from _PROTOS, which mirrors pgrc_match.h / pgrc_mem.h / pgrc_reads.h, as
+# decode.py keeps include/pgrc_decode.h apart)
+ASM_PROTOS = [
+    ("pgrc_asm_create", C.c_int, [C.c_int32, C.POINTER(_P)]),
+    ("pgrc_asm_destroy", None, [_P]),
+    ("pgrc_asm_last_error", C.c_char_p, [_P]),
+    ("pgrc_asm_run", C.c_int, [_P, C.POINTER(AsmInput), C.POINTER(AsmResult)]),
+    ("pgrc_asm_free_result", None, [C.POINTER(AsmResult)]),
+    ("pgrc_asm_get_text", C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
+    ("pgrc_asm_text_device", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    ("pgrc_asm_packed_device", C.c_int, [_P, C.POINTER(_P)]),
+    ("pgrc_asm_get_timing", C.c_int, [_P, C.POINTER(AsmTiming)]),
+]
+
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
+ASM_EXPORTED_SYMBOLS = [p[0] for p in ASM_PROTOS]
 
 
 def _preload_torch_hip_runtime() -> None:
@@ -204,7 +238,7 @@ def _load() -> C.CDLL:
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or `make -C pgrc_amd/csrc`.")
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in _PROTOS:
+    for name, res, args in _PROTOS + ASM_PROTOS:
         fn = getattr(lib, name)  # AttributeError here = header / library out of sync: fail loudly
         fn.restype = res
         fn.argtypes = args
