@@ -21,3 +21,4 @@ from .readsets import DividedPCLReadsSets  # noqa: F401
 from . import synth  # noqa: F401
 from .decode import PgRCDecoder, compressReadsOrder, compressReadsPgPositions, decompressReadsPgPositions  # noqa: F401
 from .assemble import PgAssembler  # noqa: F401
+from .overlap import OverlapFinder  # noqa: F401

@@ -119,6 +119,24 @@ class AsmTiming(C.Structure):   # pgrc_asm_timing
                 ("bytes_up", C.c_uint64), ("bytes_down", C.c_uint64)]
 
 
+class OvlInput(C.Structure):    # pgrc_ovl_input (include/pgrc_overlap.h)
+    _fields_ = [("struct_size", C.c_uint32), ("read_len", C.c_uint32), ("symbols", C.c_uint32), ("overlap_width", C.c_uint32),
+                ("n_reads", C.c_uint64), ("stop_coef", C.c_double), ("packed_rows", C.c_void_p), ("sorted_order", C.c_void_p)]
+
+
+class OvlResult(C.Structure):   # pgrc_ovl_result
+    _fields_ = [("struct_size", C.c_uint32), ("sweeps", C.c_uint32), ("n_reads", C.c_uint64), ("n_left", C.c_uint64),
+                ("duplicates", C.c_uint64), ("links", C.c_uint64), ("next_read", C.POINTER(C.c_uint32)), ("overlap", C.c_void_p),
+                ("reads_left_after", C.POINTER(C.c_uint64))]
+
+
+class OvlTiming(C.Structure):   # pgrc_ovl_timing
+    _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("ms_upload", C.c_float), ("ms_order_device", C.c_float),
+                ("ms_start_device", C.c_float), ("ms_merge_device", C.c_float), ("ms_pair_device", C.c_float),
+                ("ms_compact_device", C.c_float), ("ms_download", C.c_float), ("ms_call", C.c_float), ("bytes_up", C.c_uint64),
+                ("bytes_down", C.c_uint64)]
+
+
 # every symbol include/pgrc_match.h and include/pgrc_mem.h declare: (name, restype, argtypes)
 _P = C.c_void_p
 _PROTOS = [
@@ -208,8 +226,22 @@ ASM_PROTOS = [
     ("pgrc_asm_get_timing", C.c_int, [_P, C.POINTER(AsmTiming)]),
 ]
 
+# include/pgrc_overlap.h
+OVL_PROTOS = [
+    ("pgrc_ovl_create", C.c_int, [C.c_int32, C.POINTER(_P)]),
+    ("pgrc_ovl_destroy", None, [_P]),
+    ("pgrc_ovl_last_error", C.c_char_p, [_P]),
+    ("pgrc_ovl_run", C.c_int, [_P, C.POINTER(OvlInput), C.POINTER(OvlResult)]),
+    ("pgrc_ovl_free_result", None, [C.POINTER(OvlResult)]),
+    ("pgrc_ovl_both_sides", C.c_int, [_P, _P]),
+    ("pgrc_ovl_assemble", C.c_int, [_P, _P, _P, C.POINTER(AsmResult)]),
+    ("pgrc_ovl_get_timing", C.c_int, [_P, C.POINTER(OvlTiming)]),
+    ("pgrc_ovl_get_sweep_ms", C.c_int, [_P, C.POINTER(C.c_float), C.c_uint32]),
+]
+
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 ASM_EXPORTED_SYMBOLS = [p[0] for p in ASM_PROTOS]
+OVL_EXPORTED_SYMBOLS = [p[0] for p in OVL_PROTOS]
 
 
 def _preload_torch_hip_runtime() -> None:
@@ -238,7 +270,7 @@ def _load() -> C.CDLL:
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or `make -C pgrc_amd/csrc`.")
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in _PROTOS + ASM_PROTOS:
+    for name, res, args in _PROTOS + ASM_PROTOS + OVL_PROTOS:
         fn = getattr(lib, name)  # AttributeError here = header / library out of sync: fail loudly
         fn.restype = res
         fn.argtypes = args

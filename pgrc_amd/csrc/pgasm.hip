@@ -19,6 +19,7 @@
 // a returned value.
 #include <chrono>
 
+#include "asmctx.h"
 #include "decctx.h"
 #include "devutil.h"
 #include "pgrc_assemble.h"
@@ -301,7 +302,26 @@ static int as_jump(pgrc_asm_ctx *a, bool rank, uint64_t R, uint32_t cap, uint32_
     return PGRC_OK;
 }
 
-static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out) {
+// the input to the context's buffers: from the host, or (on_device: pgrc_ovl_assemble) rows, next_read and overlap from
+// device memory of the same device; the index mapping is the caller's host array either way
+static int as_stage(pgrc_asm_ctx *a, const pgrc_asm_input *in, bool on_device) {
+    pgrc_decode_ctx *d = a->d;
+    const uint64_t R = in->n_reads, N1 = R + 1;
+    const uint32_t L = in->read_len, width = in->overlap_width;
+    const uint32_t rb = in->symbols == 4 ? (L + 3) / 4 : (L + 2) / 3;
+    int e;
+    if (on_device) {
+        DEC_TRY(d, hipMemcpyAsync(a->rows.p, in->packed_rows, R * rb, hipMemcpyDeviceToDevice, d->stream));
+        DEC_TRY(d, hipMemcpyAsync(a->nx.p, in->next_read, N1 * 4, hipMemcpyDeviceToDevice, d->stream));
+        DEC_TRY(d, hipMemcpyAsync(a->ovraw.p, in->overlap, N1 * width, hipMemcpyDeviceToDevice, d->stream));
+    } else if ((e = as_upload(d, a->rows.p, in->packed_rows, R * rb)) || (e = as_upload(d, a->nx.p, in->next_read, N1 * 4)) ||
+               (e = as_upload(d, a->ovraw.p, in->overlap, N1 * width)))
+        return e;
+    if (in->index_mapping && (e = as_upload(d, a->map.p, in->index_mapping, R * 4))) return e;
+    return PGRC_OK;
+}
+
+static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out, bool on_device) {
     pgrc_decode_ctx *d = a->d;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = in->n_reads, N1 = R + 1;
@@ -325,9 +345,7 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     unsigned long long *cnt = (unsigned long long *)a->words.p;
     uint32_t *bad = (uint32_t *)((uint8_t *)a->words.p + AS_CNT_WORDS * 8);
 
-    if ((e = as_upload(d, a->rows.p, in->packed_rows, R * rb)) || (e = as_upload(d, nx, in->next_read, N1 * 4)) ||
-        (e = as_upload(d, a->ovraw.p, in->overlap, N1 * width)) || (map && (e = as_upload(d, a->map.p, in->index_mapping, R * 4))))
-        return e;
+    if ((e = as_stage(a, in, on_device))) return e;
     DEC_TRY(d, hipMemsetAsync(nx, 0, 4, d->stream));            // element 0 is ignored: no successor
     DEC_TRY(d, hipMemsetAsync(pred, 0, N1 * 4, d->stream));
     DEC_TRY(d, hipMemsetAsync(len, 0, N1 * 4, d->stream));
@@ -441,11 +459,41 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     t.ms_text_device = dec_elapsed(a->ev[5], a->ev[6]);
     t.ms_download = ms_download;
     t.ms_call = as_ms(t0);
-    t.bytes_up = R * rb + N1 * 4 + N1 * width + (map ? R * 4 : 0);
+    t.bytes_up = (on_device ? 0 : R * rb + N1 * 4 + N1 * width) + (map ? R * 4 : 0);
     t.bytes_down = R * 6;
     a->have_timing = true;
     return PGRC_OK;
 }
+
+static int as_entry(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out, bool on_device) {
+    if (!a) return PGRC_E_PARAM;
+    if (!out) return as_fail(a, "out is NULL");
+    *out = pgrc_asm_result{};
+    // the last run's text goes whatever becomes of this one
+    a->d->have_text = false;
+    a->d->have_parts = false;
+    a->d->nl = 0;
+    a->d->have_order = false;
+    a->have_packed = false;
+    a->have_timing = false;
+    if (!in) return as_fail(a, "in is NULL");
+    if (in->struct_size != sizeof(pgrc_asm_input)) return as_fail(a, "struct_size is not sizeof(pgrc_asm_input)");
+    if (in->read_len < 1 || in->read_len > 255) return as_fail(a, "the read length must be in [1, 255]");
+    if (in->symbols != 4 && in->symbols != 5) return as_fail(a, "the alphabet has 4 (ACGT) or 5 (ACGNT) symbols");
+    if (in->overlap_width != 1 && in->overlap_width != 2) return as_fail(a, "an overlap has 1 or 2 bytes");
+    if (in->n_reads < 1 || in->n_reads > 0xFFFFFFFEull) return as_fail(a, "the reads' count must be in [1, 2^32 - 2]");
+    if (!in->packed_rows || !in->next_read || !in->overlap) return as_fail(a, "packed_rows, next_read or overlap is NULL");
+    PGRC_ON_DEVICE(a->d);
+    const int e = as_run(a, in, out, on_device);
+    if (e) {
+        (void)hipStreamSynchronize(a->d->stream);
+        *out = pgrc_asm_result{};
+    }
+    return e;
+}
+
+int pgasm_run_device(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out) { return as_entry(a, in, out, true); }
+int pgasm_device(const pgrc_asm_ctx *a) { return a->d->device; }
 
 extern "C" {
 
@@ -479,32 +527,7 @@ void pgrc_asm_destroy(pgrc_asm_ctx *a) {
 
 const char *pgrc_asm_last_error(const pgrc_asm_ctx *a) { return pgrc_decode_last_error(a ? a->d : nullptr); }
 
-int pgrc_asm_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out) {
-    if (!a) return PGRC_E_PARAM;
-    if (!out) return as_fail(a, "out is NULL");
-    *out = pgrc_asm_result{};
-    // the last run's text goes whatever becomes of this one
-    a->d->have_text = false;
-    a->d->have_parts = false;
-    a->d->nl = 0;
-    a->d->have_order = false;
-    a->have_packed = false;
-    a->have_timing = false;
-    if (!in) return as_fail(a, "in is NULL");
-    if (in->struct_size != sizeof(pgrc_asm_input)) return as_fail(a, "struct_size is not sizeof(pgrc_asm_input)");
-    if (in->read_len < 1 || in->read_len > 255) return as_fail(a, "the read length must be in [1, 255]");
-    if (in->symbols != 4 && in->symbols != 5) return as_fail(a, "the alphabet has 4 (ACGT) or 5 (ACGNT) symbols");
-    if (in->overlap_width != 1 && in->overlap_width != 2) return as_fail(a, "an overlap has 1 or 2 bytes");
-    if (in->n_reads < 1 || in->n_reads > 0xFFFFFFFEull) return as_fail(a, "the reads' count must be in [1, 2^32 - 2]");
-    if (!in->packed_rows || !in->next_read || !in->overlap) return as_fail(a, "packed_rows, next_read or overlap is NULL");
-    PGRC_ON_DEVICE(a->d);
-    const int e = as_run(a, in, out);
-    if (e) {
-        (void)hipStreamSynchronize(a->d->stream);
-        *out = pgrc_asm_result{};
-    }
-    return e;
-}
+int pgrc_asm_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out) { return as_entry(a, in, out, false); }
 
 void pgrc_asm_free_result(pgrc_asm_result *r) {
     if (!r) return;

@@ -23,6 +23,36 @@ struct ScoPlus {
     __device__ T operator()(T a, T b) const { return a + b; }
 };
 
+// A weak order of five items in a u32: the dense rank of item g (0 .. 4) in bits [3g, 3g + 3).  sco_dense5 ranks five keys
+// (the number of distinct smaller keys).  ScoWeakOrder5 is "a, then b": the items sorted by b's ranks, ties kept in a's order
+// -- the dense ranks of the pairs (b[g], a[g]).  Associative, not commutative; the all-equal order 0 is its identity (pgovl.hip:
+// the order of the groups in front of every run of equal suffixes).
+__host__ __device__ __forceinline__ uint32_t sco_dense5(const uint32_t (&key)[5]) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int g = 0; g < 5; g++) {
+        uint32_t rank = 0;
+#pragma unroll
+        for (int h = 0; h < 5; h++) {
+            bool first = key[h] < key[g];
+#pragma unroll
+            for (int h2 = 0; h2 < h; h2++) first = first && key[h2] != key[h];
+            rank += first ? 1u : 0u;
+        }
+        w |= rank << (3 * g);
+    }
+    return w;
+}
+struct ScoWeakOrder5 {
+    __host__ __device__ uint32_t operator()(uint32_t a, uint32_t b) const {
+        uint32_t key[5];
+#pragma unroll
+        for (int g = 0; g < 5; g++) key[g] = (((b >> (3 * g)) & 7u) << 3) | ((a >> (3 * g)) & 7u);
+        return sco_dense5(key);
+    }
+};
+#define SCO_WEAK5_SYMBOL_ORDER (0u | 1u << 3 | 2u << 6 | 3u << 9 | 4u << 12)
+
 // a value of any size that is a multiple of 4 bytes, from the lane `o` below, word by word
 template <typename T>
 __device__ __forceinline__ T sco_shfl_up(T v, int o) {
