@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "pgrc_match.h"
+#include "pgrc_varlen.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -131,6 +132,14 @@ typedef struct {
  * end, an offsets stream is not marks x width bytes, a source range reaches past the HQ end, an HQ mark's source reaches
  * its own output position, or the restored HQ length differs from org_hq_len. */
 int pgrc_decode_set_mapped_text(pgrc_decode_ctx *ctx, const pgrc_decode_mapped *m);
+/* The same with the joined mapped text still in the form the archive holds it in: the payload of
+ * VarLenDNACoder::Compress (pgrc_varlen.h), which restoreMatchedPgs gets from VarLenDNACoder::Uncompress.  m->mapped must be
+ * NULL; the sum of m->mapped_len[] is the expected decoded length.  The coded bytes go up (about 0.3 byte a symbol), `v`
+ * decodes them in HBM and the restore runs unchanged.  PGRC_E_PARAM: a decoded length that differs from the expected one
+ * (the reference exits there), a coder on another device, v or (with coded_len > 0) coded NULL.  Every failure leaves no
+ * text installed.  pgrc_varlen_timing(v) reports the decode; pgrc_decode_get_restore_timing counts it in ms_upload. */
+int pgrc_decode_set_mapped_text_coded(pgrc_decode_ctx *ctx, const pgrc_decode_mapped *m, pgrc_varlen *v, const void *coded,
+                                      uint64_t coded_len);
 /* the restored HQ, LQ and N lengths (the lists' text_base: 0, lens[0], lens[0] + lens[1]); PGRC_E_STATE unless the text
  * came from pgrc_decode_set_mapped_text */
 int pgrc_decode_text_lengths(pgrc_decode_ctx *ctx, uint64_t lens[3]);

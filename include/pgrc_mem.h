@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "pgrc_match.h"
+#include "pgrc_varlen.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -91,6 +92,24 @@ typedef struct {
 int pgrc_mem_mark_and_remove(pgrc_mem_ctx *ctx, const pgrc_text_match *matches, uint64_t count, uint32_t min_match_len,
                              char *mapped_out, uint64_t mapped_cap, pgrc_mem_mapping *out);
 void pgrc_mem_free_mapping(pgrc_mem_mapping *m);
+
+/* The same mapping with the mapped text KEPT IN HBM, for the variable-length DNA coder (pgrc_varlen.h) that the reference
+ * runs over the joined mapped texts HQ | LQ | N before LZMA / PPMd (SimplePgMatcher::matchPgsInPg,
+ * matching/SimplePgMatcher.cpp:208-231): the text then crosses the link at about 0.3 byte a symbol instead of one.
+ *
+ * pgrc_mem_mark_and_remove_resident is pgrc_mem_mark_and_remove without mapped_out: the mapped text stays in the
+ * context's slot `part` (0 HQ, 1 LQ, 2 N; anything else is PGRC_E_PARAM), the two streams and the counters come back as
+ * before, out->mapped_len is the slot's length.  A failed call leaves the slot unset.
+ *
+ * pgrc_mem_encode_mapped codes the slots 0 | 1 | 2 as ONE text with `v` into coded_out (host, cap bytes;
+ * pgrc_varlen_bound(sum of the lengths) always suffices) and returns the three mapped lengths, which the caller writes as
+ * pgsLen.  An unset N slot is an empty part; an unset HQ or LQ slot is PGRC_E_STATE; a coder on another device is
+ * PGRC_E_PARAM; the coder's own failures (PGRC_E_SYMBOL, a cap below the coded length: PGRC_E_PARAM with *coded_len = the
+ * length needed) come back as they are.  pgrc_mem_set_src_ascii forgets the slots.  The case without a matcher (a source
+ * shorter than the target length) stays with the caller, who codes the texts with pgrc_varlen_encode directly. */
+int pgrc_mem_mark_and_remove_resident(pgrc_mem_ctx *ctx, const pgrc_text_match *matches, uint64_t count, uint32_t min_match_len,
+                                      int32_t part, pgrc_mem_mapping *out);
+int pgrc_mem_encode_mapped(pgrc_mem_ctx *ctx, pgrc_varlen *v, void *coded_out, uint64_t cap, uint64_t *coded_len, uint64_t lens[3]);
 
 /* introspection (tests, bench) */
 typedef struct {

@@ -22,3 +22,4 @@ from . import synth  # noqa: F401
 from .decode import PgRCDecoder, compressReadsOrder, compressReadsPgPositions, decompressReadsPgPositions  # noqa: F401
 from .assemble import PgAssembler  # noqa: F401
 from .overlap import OverlapFinder  # noqa: F401
+from .varlen import VarLenDNACoder  # noqa: F401

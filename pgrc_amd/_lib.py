@@ -100,6 +100,16 @@ class MemMapping(C.Structure):   # pgrc_mem_mapping (include/pgrc_mem.h)
                 ("map_len_bytes", C.c_uint64)]
 
 
+class VarLenPart(C.Structure):   # pgrc_varlen_part (include/pgrc_varlen.h)
+    _fields_ = [("ptr", C.c_void_p), ("len", C.c_uint64), ("on_device", C.c_int32)]
+
+
+class VarLenTimes(C.Structure):  # pgrc_varlen_times
+    _fields_ = [("ms_upload", C.c_float), ("ms_maps", C.c_float), ("ms_scan", C.c_float), ("ms_emit", C.c_float),
+                ("ms_download", C.c_float), ("ms_call", C.c_float), ("symbols", C.c_uint64), ("coded_bytes", C.c_uint64),
+                ("was_decode", C.c_int32)]
+
+
 class AsmInput(C.Structure):    # pgrc_asm_input (include/pgrc_assemble.h)
     _fields_ = [("struct_size", C.c_uint32), ("read_len", C.c_uint32), ("symbols", C.c_uint32), ("overlap_width", C.c_uint32),
                 ("n_reads", C.c_uint64), ("packed_rows", C.c_void_p), ("next_read", C.c_void_p), ("overlap", C.c_void_p),
@@ -201,6 +211,8 @@ _PROTOS = [
     ("pgrc_mem_mark_and_remove", C.c_int, [_P, C.POINTER(TextMatch), C.c_uint64, C.c_uint32, _P, C.c_uint64, C.POINTER(MemMapping)]),
     ("pgrc_mem_free_mapping", None, [C.POINTER(MemMapping)]),
     ("pgrc_mem_mapping_timing", C.c_int, [_P, C.POINTER(C.c_float * 5)]),
+    ("pgrc_mem_mark_and_remove_resident", C.c_int, [_P, C.POINTER(TextMatch), C.c_uint64, C.c_uint32, C.c_int32, C.POINTER(MemMapping)]),
+    ("pgrc_mem_encode_mapped", C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64 * 3)]),
     # include/pgrc_reads.h
     ("pgrc_divider_create", C.c_int, [C.POINTER(DivideParams), C.POINTER(_P)]),
     ("pgrc_divider_destroy", None, [_P]),
@@ -239,7 +251,19 @@ OVL_PROTOS = [
     ("pgrc_ovl_get_sweep_ms", C.c_int, [_P, C.POINTER(C.c_float), C.c_uint32]),
 ]
 
+# include/pgrc_varlen.h
+VARLEN_PROTOS = [
+    ("pgrc_varlen_create", C.c_int, [_P, C.c_uint64, C.c_int32, C.POINTER(_P)]),
+    ("pgrc_varlen_destroy", None, [_P]),
+    ("pgrc_varlen_last_error", C.c_char_p, [_P]),
+    ("pgrc_varlen_bound", C.c_uint64, [C.c_uint64]),
+    ("pgrc_varlen_encode", C.c_int, [_P, C.POINTER(VarLenPart), C.c_uint32, _P, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]),
+    ("pgrc_varlen_decode", C.c_int, [_P, _P, C.c_uint64, C.c_int32, C.c_uint64, _P, C.c_int32]),
+    ("pgrc_varlen_timing", C.c_int, [_P, C.POINTER(VarLenTimes)]),
+]
+
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
+VARLEN_EXPORTED_SYMBOLS = [p[0] for p in VARLEN_PROTOS]
 ASM_EXPORTED_SYMBOLS = [p[0] for p in ASM_PROTOS]
 OVL_EXPORTED_SYMBOLS = [p[0] for p in OVL_PROTOS]
 
@@ -270,7 +294,7 @@ def _load() -> C.CDLL:
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or `make -C pgrc_amd/csrc`.")
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in _PROTOS + ASM_PROTOS + OVL_PROTOS:
+    for name, res, args in _PROTOS + ASM_PROTOS + OVL_PROTOS + VARLEN_PROTOS:
         fn = getattr(lib, name)  # AttributeError here = header / library out of sync: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -49,6 +49,7 @@ struct pgrc_decode_ctx {
     bool have_parts = false;
     uint64_t part_len[3] = {};
     DecBuf rs_mapped, rs_marks, rs_vals, rs_ptr, rs_bsum;   // the mapped parts and streams; per-mark arrays; values; pointers; block counts
+    DecBuf rs_coded, rs_join;   // pgrc_decode_set_mapped_text_coded: the coded bytes and the joined text they decode to
     pgrc_decode_restore_timing rtm{};
     // the pair-position coding (pairpos.hip): the uploaded input, the sort's records (and values, W = 8) in turn, per-rank
     // and per-far-pair arrays, the device-side output, scan scratch; radix.hip's sort runs on a private match-context

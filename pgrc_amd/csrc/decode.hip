@@ -346,7 +346,7 @@ void pgrc_decode_destroy(pgrc_decode_ctx *d) {
     for (auto &l : d->lst)
         for (DecBuf *b : {&l.pos, &l.rc, &l.mcum, &l.moff, &l.msym, &l.raw}) dec_free(*b);
     for (DecBuf *b : {&d->chunk[0], &d->chunk[1], &d->text, &d->flag, &d->scratch, &d->rl_order, &d->org2pos, &d->rank, &d->rs_mapped, &d->rs_marks,
-                       &d->rs_vals, &d->rs_ptr, &d->rs_bsum})
+                       &d->rs_vals, &d->rs_ptr, &d->rs_bsum, &d->rs_coded, &d->rs_join})
         dec_free(*b);
     for (int k = 0; k < 2; k++) {
         if (d->stage[k]) (void)hipHostFree(d->stage[k]);

@@ -690,6 +690,7 @@ int pgrc_mem_set_src_ascii(pgrc_mem_ctx *m, const char *src, uint64_t n) {
     pgrc_match_ctx *c = m->base;
     m->have_src = false;
     m->map_ready = false;
+    for (bool &set : m->res_set) set = false;   // (the mapped texts kept in HBM belong to the old source)
     PgrcDeviceScope dev_scope__(c->device);
     if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     const auto t0 = std::chrono::steady_clock::now();

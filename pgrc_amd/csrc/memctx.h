@@ -31,6 +31,11 @@ struct pgrc_mem_ctx {
     hipEvent_t pm_ev[6]{};            // phases of the mapping (created on first use)
     bool have_pm_ev = false;
     float pm_ms[5] = {0, 0, 0, 0, 0}; // normalise + sort, path, streams, text, download
+    // the mapped texts that pgrc_mem_mark_and_remove_resident left in HBM, slot 0 HQ, 1 LQ, 2 N: what pgrc_mem_encode_mapped
+    // codes as one text (pgrc_mem_set_src_ascii forgets them)
+    DevBuf pm_res[3];
+    uint64_t res_len[3] = {0, 0, 0};
+    bool res_set[3] = {false, false, false};
 };
 
 #define MEM_TRY(m, expr)                                                                     \

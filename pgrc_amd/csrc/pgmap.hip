@@ -33,6 +33,7 @@
 #include "devutil.h"
 #include "memctx.h"
 #include "pgrc_mem.h"
+#include "varlenctx.h"
 
 #define PM_TPB 256
 #define PM_LPT 4               // 8-byte words of the mapped text per lane
@@ -292,12 +293,18 @@ void pgrc_pgmap_release(pgrc_mem_ctx *m) {
     DevBuf *bufs[] = {&m->pm_in, &m->pm_f[0], &m->pm_f[1], &m->pm_f[2], &m->pm_key[0], &m->pm_key[1], &m->pm_idx[0], &m->pm_idx[1], &m->pm_flag,
                       &m->pm_slot, &m->pm_u[0], &m->pm_u[1], &m->pm_u[2], &m->pm_u[3], &m->pm_pmax, &m->pm_jump[0], &m->pm_jump[1], &m->pm_kept,
                       &m->pm_m[0], &m->pm_m[1], &m->pm_m[2], &m->pm_dp, &m->pm_len, &m->pm_nb, &m->pm_cum, &m->pm_nbpos, &m->pm_mp, &m->pm_off,
-                      &m->pm_lens, &m->pm_out, &m->pm_fold, &m->pm_small};
+                      &m->pm_lens, &m->pm_out, &m->pm_fold, &m->pm_small, &m->pm_res[0], &m->pm_res[1], &m->pm_res[2]};
+    for (bool &set : m->res_set) set = false;
     for (DevBuf *b : bufs) pgrc_buf_free(*b);
     if (m->have_pm_ev)
         for (auto &x : m->pm_ev) (void)hipEventDestroy(x);
     m->have_pm_ev = false;
 }
+
+// pgrc_mem_mark_and_remove (part < 0: the mapped text goes down to mapped_out) and pgrc_mem_mark_and_remove_resident (part
+// 0 .. 2: it stays in HBM, in the context's slot `part`)
+static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, uint64_t count, uint32_t min_match_len, char *mapped_out,
+                              uint64_t mapped_cap, int part, pgrc_mem_mapping *out);
 
 extern "C" {
 
@@ -315,13 +322,54 @@ int pgrc_mem_mapping_timing(pgrc_mem_ctx *m, float ms[5]) {
 
 int pgrc_mem_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, uint64_t count, uint32_t min_match_len, char *mapped_out,
                              uint64_t mapped_cap, pgrc_mem_mapping *out) {
+    return pm_mark_and_remove(m, matches, count, min_match_len, mapped_out, mapped_cap, -1, out);
+}
+
+int pgrc_mem_mark_and_remove_resident(pgrc_mem_ctx *m, const pgrc_text_match *matches, uint64_t count, uint32_t min_match_len, int32_t part,
+                                      pgrc_mem_mapping *out) {
+    if (m && out && (part < 0 || part > 2)) {
+        memset(out, 0, sizeof *out);
+        m->err = "mark_and_remove_resident: part must be 0 (HQ), 1 (LQ) or 2 (N)";
+        return PGRC_E_PARAM;
+    }
+    return pm_mark_and_remove(m, matches, count, min_match_len, nullptr, 0, part, out);
+}
+
+int pgrc_mem_encode_mapped(pgrc_mem_ctx *m, pgrc_varlen *v, void *coded_out, uint64_t cap, uint64_t *coded_len, uint64_t lens[3]) {
+    if (!m) return PGRC_E_PARAM;
+    if (!v || !coded_len || !lens) { m->err = "encode_mapped: the coder, coded_len or lens is NULL"; return PGRC_E_PARAM; }
+    *coded_len = 0;
+    lens[0] = lens[1] = lens[2] = 0;
+    if (!m->res_set[0] || !m->res_set[1]) {
+        m->err = "encode_mapped: no resident HQ or LQ text (call pgrc_mem_mark_and_remove_resident for parts 1, 2 and 0 first)";
+        return PGRC_E_STATE;
+    }
+    if (v->device != m->base->device) { m->err = "encode_mapped: the coder is on another device"; return PGRC_E_PARAM; }
+    pgrc_varlen_part parts[3];
+    for (int p = 0; p < 3; p++) {
+        parts[p].len = m->res_set[p] ? m->res_len[p] : 0;       // (an unset N slot: an empty part)
+        parts[p].ptr = m->pm_res[p].p;
+        parts[p].on_device = 1;
+    }
+    const int e = pgrc_varlen_encode(v, parts, 3, coded_out, cap, 0, coded_len);
+    if (e) { m->err = std::string("encode_mapped: ") + pgrc_varlen_last_error(v); return e; }
+    for (int p = 0; p < 3; p++) lens[p] = parts[p].len;
+    return PGRC_OK;
+}
+
+} // extern "C"
+
+static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, uint64_t count, uint32_t min_match_len, char *mapped_out,
+                              uint64_t mapped_cap, int part, pgrc_mem_mapping *out) {
     if (!m || !out) return PGRC_E_PARAM;
     memset(out, 0, sizeof *out);
+    const bool resident = part >= 0;
+    if (resident) m->res_set[part] = false;                    // (a failed call leaves no text in the slot)
     if (!m->map_ready || !m->have_src) { m->err = "mark_and_remove: no destination (call pgrc_mem_match_texts first)"; return PGRC_E_STATE; }
     const uint64_t N = m->N, N2 = m->map_n2, n = count;
     const uint64_t min_len = min_match_len == UINT32_MAX ? m->L : min_match_len;
     if (min_len == 0) { m->err = "mark_and_remove: min_match_len is 0"; return PGRC_E_PARAM; }
-    if (mapped_cap < N2 || (N2 && !mapped_out)) { m->err = "mark_and_remove: mapped_out is smaller than the destination"; return PGRC_E_PARAM; }
+    if (!resident && (mapped_cap < N2 || (N2 && !mapped_out))) { m->err = "mark_and_remove: mapped_out is smaller than the destination"; return PGRC_E_PARAM; }
     if (n && !matches) return PGRC_E_PARAM;
     if (n >= 0xFFFFF000ull) { m->err = "mark_and_remove: too many matches"; return PGRC_E_PARAM; }
     pgrc_match_ctx *c = m->base;
@@ -469,7 +517,8 @@ int pgrc_mem_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, ui
     // ---- 4. the mapped text
     const uint64_t mapped_len = N2 - tot[0] + marks;           // (every mark replaces at least one symbol: <= N2)
     const uint64_t nwords = (mapped_len + 7) / 8;
-    ens(m->pm_out, nwords * 8);
+    DevBuf &text_buf = resident ? m->pm_res[part] : m->pm_out;
+    ens(text_buf, nwords * 8);
     if (e) return e;
     if (nwords) {
         PmText t;
@@ -482,7 +531,7 @@ int pgrc_mem_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, ui
         t.marks = marks;
         t.mapped_len = mapped_len;
         t.nwords = nwords;
-        t.out = (uint64_t *)m->pm_out.p;
+        t.out = (uint64_t *)text_buf.p;
         hipLaunchKernelGGL(k_pm_text, dim3(pm_grid((nwords + PM_LPT - 1) / PM_LPT)), dim3(PM_TPB), 0, st, t);
         MEM_TRY(m, hipGetLastError());
     }
@@ -504,7 +553,7 @@ int pgrc_mem_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, ui
     hipError_t he = hipSuccess;
     if (off_bytes) he = hipMemcpyAsync(block, m->pm_off.p, off_bytes, hipMemcpyDeviceToHost, st);
     if (he == hipSuccess && tot[1]) he = hipMemcpyAsync(block + off_bytes + nh, m->pm_lens.p, tot[1], hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && mapped_len) he = hipMemcpyAsync(mapped_out, m->pm_out.p, mapped_len, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && mapped_len && !resident) he = hipMemcpyAsync(mapped_out, m->pm_out.p, mapped_len, hipMemcpyDeviceToHost, st);
     if (he == hipSuccess) he = hipStreamSynchronize(st);
     if (he != hipSuccess) { free(block); m->err = std::string("mapping download: ") + hipGetErrorString(he); return pgrc_hip_code(he); }
     m->pm_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -517,7 +566,9 @@ int pgrc_mem_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, ui
     out->map_off_bytes = off_bytes;
     out->map_len = block + off_bytes;
     out->map_len_bytes = len_bytes;
+    if (resident) {
+        m->res_len[part] = mapped_len;
+        m->res_set[part] = true;
+    }
     return PGRC_OK;
 }
-
-} // extern "C"

@@ -25,6 +25,7 @@
 #include <chrono>
 
 #include "decctx.h"
+#include "varlenctx.h"
 
 #define RS_WPB 1024                      // 16-byte words per block of the parse passes (4 per lane)
 #define RS_SPT 16                        // matched symbols per lane of the symbol kernels
@@ -289,10 +290,9 @@ static uint32_t rs_grid(uint64_t items, uint64_t per_block) {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + per_block - 1) / per_block, 1u << 30));
 }
 
-extern "C" {
-
-int pgrc_decode_set_mapped_text(pgrc_decode_ctx *d, const pgrc_decode_mapped *m) {
-    if (!d) return PGRC_E_PARAM;
+// pgrc_decode_set_mapped_text (v == NULL: the mapped text comes as bytes in m->mapped) and pgrc_decode_set_mapped_text_coded
+// (the coded bytes go up and varlen.hip decodes them in HBM; the parts then reach their places by device copies)
+static int rs_set_mapped(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_varlen *v, const void *coded, uint64_t coded_len) {
     if (!m || m->struct_size != sizeof(pgrc_decode_mapped))
         return dec_fail(d, PGRC_E_PARAM, "mapped is NULL or struct_size is not sizeof(pgrc_decode_mapped)");
     d->have_text = false;
@@ -301,7 +301,11 @@ int pgrc_decode_set_mapped_text(pgrc_decode_ctx *d, const pgrc_decode_mapped *m)
     d->have_order = false;
     d->tm = pgrc_decode_timing{};
     const uint64_t mtot = m->mapped_len[0] + m->mapped_len[1] + m->mapped_len[2];
-    if (mtot && !m->mapped) return rs_fail(d, "mapped is NULL");
+    if (v) {
+        if (m->mapped) return rs_fail(d, "mapped must be NULL when the text comes coded");
+        if (coded_len && !coded) return rs_fail(d, "coded is NULL");
+        if (v->device != d->device) return rs_fail(d, "the coder is on another device");
+    } else if (mtot && !m->mapped) return rs_fail(d, "mapped is NULL");
     for (int p = 0; p < 3; p++)
         if ((m->map_off_bytes[p] && !m->map_off[p]) || (m->map_len_bytes[p] && !m->map_len[p])) return rs_fail(d, "a stream is NULL");
     PGRC_ON_DEVICE(d);
@@ -314,9 +318,10 @@ int pgrc_decode_set_mapped_text(pgrc_decode_ctx *d, const pgrc_decode_mapped *m)
     // byte arrays: 0..2 the parts, 3..5 the offsets streams, 6..8 the lengths streams
     const uint8_t *hsrc[9];
     uint64_t nbytes[9], at[9], dev_bytes = 0;
-    uint64_t mo = 0;
+    uint64_t mo = 0, part_at[3];
     for (int p = 0; p < 3; p++) {
-        hsrc[p] = (const uint8_t *)m->mapped + mo;
+        part_at[p] = mo;
+        hsrc[p] = v ? nullptr : (const uint8_t *)m->mapped + mo;
         nbytes[p] = m->mapped_len[p];
         mo += m->mapped_len[p];
         hsrc[3 + p] = m->map_off[p];
@@ -330,12 +335,21 @@ int pgrc_decode_set_mapped_text(pgrc_decode_ctx *d, const pgrc_decode_mapped *m)
     }
     if ((e = dec_buf(d, d->rs_mapped, dev_bytes))) return e;
     uint8_t *dm = (uint8_t *)d->rs_mapped.p;
-    const bool pinned = mtot && rs_pinned(m->mapped);
+    if (v) {
+        if ((e = dec_buf(d, d->rs_coded, coded_len)) || (e = dec_buf(d, d->rs_join, mtot))) return e;
+        if (coded_len && rs_pinned(coded)) DEC_TRY(d, hipMemcpyAsync(d->rs_coded.p, coded, coded_len, hipMemcpyHostToDevice, d->stream));
+        else if (coded_len && (e = dec_upload(d, d->rs_coded.p, coded, coded_len))) return e;
+        DEC_TRY(d, hipStreamSynchronize(d->stream));
+        if ((e = pgrc_varlen_decode(v, d->rs_coded.p, coded_len, 1, mtot, d->rs_join.p, 1)))
+            return dec_fail(d, e, std::string("set_mapped_text_coded: ") + pgrc_varlen_last_error(v));
+    }
+    const bool pinned = !v && mtot && rs_pinned(m->mapped);
     for (int s = 0; s < 9; s++) {
         const uint64_t z = nbytes[s] & ~15ull;
         DEC_TRY(d, hipMemsetAsync(dm + at[s] + z, 0, rs_a16(nbytes[s] + RS_PAD) - z, d->stream));
         if (!nbytes[s]) continue;
-        if (s < 3 && pinned) DEC_TRY(d, hipMemcpyAsync(dm + at[s], hsrc[s], nbytes[s], hipMemcpyHostToDevice, d->stream));
+        if (s < 3 && v) DEC_TRY(d, hipMemcpyAsync(dm + at[s], (const uint8_t *)d->rs_join.p + part_at[s], nbytes[s], hipMemcpyDeviceToDevice, d->stream));
+        else if (s < 3 && pinned) DEC_TRY(d, hipMemcpyAsync(dm + at[s], hsrc[s], nbytes[s], hipMemcpyHostToDevice, d->stream));
         else if ((e = dec_upload(d, dm + at[s], hsrc[s], nbytes[s]))) return e;
     }
     DEC_TRY(d, hipStreamSynchronize(d->stream));
@@ -501,6 +515,19 @@ int pgrc_decode_set_mapped_text(pgrc_decode_ctx *d, const pgrc_decode_mapped *m)
     tm.ms_call = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     d->rtm = tm;
     return PGRC_OK;
+}
+
+extern "C" {
+
+int pgrc_decode_set_mapped_text(pgrc_decode_ctx *d, const pgrc_decode_mapped *m) {
+    if (!d) return PGRC_E_PARAM;
+    return rs_set_mapped(d, m, nullptr, nullptr, 0);
+}
+
+int pgrc_decode_set_mapped_text_coded(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_varlen *v, const void *coded, uint64_t coded_len) {
+    if (!d) return PGRC_E_PARAM;
+    if (!v) return dec_fail(d, PGRC_E_PARAM, "set_mapped_text_coded: the coder is NULL");
+    return rs_set_mapped(d, m, v, coded, coded_len);
 }
 
 int pgrc_decode_text_lengths(pgrc_decode_ctx *d, uint64_t lens[3]) {

@@ -53,6 +53,19 @@ struct ScoWeakOrder5 {
 };
 #define SCO_WEAK5_SYMBOL_ORDER (0u | 1u << 3 | 2u << 6 | 3u << 9 | 4u << 12)
 
+// A map {0..3} -> {0..3} in 8 bits of a u32: the image of e in bits [2e, 2e + 2).  ScoMap4 is "a, then b": e -> b[a[e]].
+// Associative, not commutative; SCO_MAP4_IDENTITY is its identity (varlen.hip: a tile of the text takes the offset at which
+// the parse enters it to the offset at which the parse leaves it).
+struct ScoMap4 {
+    __host__ __device__ uint32_t operator()(uint32_t a, uint32_t b) const {
+        uint32_t r = 0;
+#pragma unroll
+        for (int e = 0; e < 4; e++) r |= ((b >> (2 * ((a >> (2 * e)) & 3u))) & 3u) << (2 * e);
+        return r;
+    }
+};
+#define SCO_MAP4_IDENTITY 0xE4u
+
 // a value of any size that is a multiple of 4 bytes, from the lane `o` below, word by word
 template <typename T>
 __device__ __forceinline__ T sco_shfl_up(T v, int o) {

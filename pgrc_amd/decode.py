@@ -90,6 +90,7 @@ DECODE_PROTOS = [
     ("pgrc_decode_rows_device", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P]),
     ("pgrc_decode_get_timing", C.c_int, [_P, C.POINTER(DecodeTiming)]),
     ("pgrc_decode_set_mapped_text", C.c_int, [_P, C.POINTER(DecodeMapped)]),
+    ("pgrc_decode_set_mapped_text_coded", C.c_int, [_P, C.POINTER(DecodeMapped), _P, _P, C.c_uint64]),
     ("pgrc_decode_text_lengths", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("pgrc_decode_get_text", C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
     ("pgrc_decode_get_restore_timing", C.c_int, [_P, C.POINTER(RestoreTiming)]),
@@ -204,6 +205,27 @@ class PgRCDecoder:
             a.map_len[p], a.map_len_bytes[p] = _ptr(lns[p]), lns[p].size
         self._text_len = 0
         self._ck(lib.pgrc_decode_set_mapped_text(self._h, C.byref(a)))
+        self._text_len = sum(self.text_lengths())
+
+    def set_mapped_text_coded(self, coder, coded, mapped_lens, org_hq_len: int, map_off, map_len, rev_compl: bool = True) -> None:
+        """restoreMatchedPgs with the joined mapped text still coded: `coded` is the payload of VarLenDNACoder::Compress,
+        `coder` the pgrc_amd.VarLenDNACoder made from its book.  The coded bytes go up and are decoded on the device."""
+        t = _bytes(coded)
+        lens = [int(x) for x in mapped_lens]
+        assert len(lens) == 3 and len(map_off) == 3 and len(map_len) == 3
+        offs = [_bytes(x) for x in map_off]
+        lns = [_bytes(x) for x in map_len]
+        a = DecodeMapped()
+        a.struct_size = C.sizeof(DecodeMapped)
+        a.mapped = None
+        a.org_hq_len = int(org_hq_len)
+        a.rev_compl = int(bool(rev_compl))
+        for p in range(3):
+            a.mapped_len[p] = lens[p]
+            a.map_off[p], a.map_off_bytes[p] = _ptr(offs[p]), offs[p].size
+            a.map_len[p], a.map_len_bytes[p] = _ptr(lns[p]), lns[p].size
+        self._text_len = 0
+        self._ck(lib.pgrc_decode_set_mapped_text_coded(self._h, C.byref(a), coder._h, _ptr(t) if t.size else None, t.size))
         self._text_len = sum(self.text_lengths())
 
     def text_lengths(self) -> tuple:

@@ -30,6 +30,7 @@ class CopMEMMatcher:
         self.targetMatchLength = int(targetMatchLength)
         self._src = _ascii(srcText)          # the library borrows the text: keep it alive
         self._last_n2 = 0
+        self._res_len = [0, 0, 0]            # the mapped texts kept on the device (markAndRemoveExactMatchesResident)
         self._ck(lib.pgrc_mem_set_src_ascii(self._h, self._src.ctypes.data_as(C.c_void_p), self._src.size))
 
     def _ck(self, rc: int) -> None:
@@ -75,6 +76,34 @@ class CopMEMMatcher:
         mapped = buf[:mp.mapped_len]
         lib.pgrc_mem_free_mapping(C.byref(mp))
         return mapped, off, lens, info
+
+    def markAndRemoveExactMatchesResident(self, matches, part: int, minMatchLength: int | None = None):
+        """markAndRemoveExactMatches with the mapped text kept on the device, in slot `part` (0 HQ, 1 LQ, 2 N), for
+        encodeMapped.  -> (mapped_len, map_off, map_len, info)"""
+        mt = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+        mp = _lib.MemMapping()
+        self._ck(lib.pgrc_mem_mark_and_remove_resident(self._h, C.cast(mt.ctypes.data_as(C.c_void_p), C.POINTER(_lib.TextMatch)), mt.shape[0],
+                                                       UINT32_MAX if minMatchLength is None else int(minMatchLength), int(part), C.byref(mp)))
+        off = np.ctypeslib.as_array(mp.map_off, shape=(mp.map_off_bytes,)).copy() if mp.map_off_bytes else np.zeros(0, np.uint8)
+        lens = np.ctypeslib.as_array(mp.map_len, shape=(mp.map_len_bytes,)).copy()
+        info = {"marks": mp.marks, "unique_matches": mp.unique_matches, "matched_symbols": mp.matched_symbols}
+        mapped_len = int(mp.mapped_len)
+        self._res_len[int(part)] = mapped_len
+        lib.pgrc_mem_free_mapping(C.byref(mp))
+        return mapped_len, off, lens, info
+
+    def encodeMapped(self, coder, out: np.ndarray | None = None):
+        """the resident mapped texts HQ | LQ | N coded as one text by `coder` (pgrc_amd.VarLenDNACoder): what
+        SimplePgMatcher::matchPgsInPg hands to LZMA / PPMd.  -> (coded, (hq_len, lq_len, n_len)); out: a uint8 buffer to
+        write into (page-locked memory copies faster), else one of the worst-case size is made."""
+        n = C.c_uint64(0)
+        lens = (C.c_uint64 * 3)()
+        if out is None:                                         # (pgrc_varlen_bound: one code a symbol at worst)
+            out = np.empty(max(int(lib.pgrc_varlen_bound(sum(self._res_len))), 1), dtype=np.uint8)
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("out: a writeable contiguous uint8 array")
+        self._ck(lib.pgrc_mem_encode_mapped(self._h, coder._h, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n), C.byref(lens)))
+        return out[:n.value], tuple(int(x) for x in lens)
 
     def mapping_timing(self) -> dict:
         """phases of the last markAndRemoveExactMatches in milliseconds (introspection: tests, tools)"""
