@@ -34,7 +34,7 @@ size_t pool_cap() {
 const size_t POOL_MIN = 64ull << 20;
 }
 
-int pgrc_buf_ensure(pgrc_match_ctx *c, DevBuf &b, size_t bytes) {
+int pgrc_buf_ensure(PgrcDev *c, DevBuf &b, size_t bytes) {
     if (bytes == 0) bytes = 16;
     if (b.p && b.bytes >= bytes) return PGRC_OK;
     pgrc_buf_free(b);
@@ -67,6 +67,29 @@ int pgrc_buf_ensure(pgrc_match_ctx *c, DevBuf &b, size_t bytes) {
     static const bool debug_alloc = getenv("PGRC_DEBUG_ALLOC") != nullptr;     // (process-wide, read once)
     if (debug_alloc) fprintf(stderr, "pgrc alloc ctx %p buf %p: %zu bytes at %p\n", (void *)c, (void *)&b, bytes, b.p);
     return PGRC_OK;
+}
+
+int pgrc_buf_unpooled(PgrcDev *c, DevBuf &b, size_t bytes) {
+    bytes = std::max<size_t>(bytes, 64);
+    if (b.p && b.bytes >= bytes) return PGRC_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        c->err = "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e);
+        return pgrc_hip_code(e);
+    }
+    b.bytes = bytes;
+    return PGRC_OK;
+}
+
+bool pgrc_host_pinned(const void *p) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) == hipSuccess) return attr.type == hipMemoryTypeHost;
+    (void)hipGetLastError();
+    return false;
 }
 
 // quiesced: the caller has waited for the device since the buffer was last used (pgrc_buf_free_all: one wait for a batch)

@@ -34,6 +34,14 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// What every context is on the device side: its device, the stream its work is ordered on and the text of its last
+// error.  The shared services (the allocators below, pack.hip, radix.hip, pgrc_ps_scan_u32) need nothing else.
+struct PgrcDev {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+};
+
 struct pgrc_multi;   // multi.hip
 
 // Run-time options of a context.  The environment is read ONCE, when the context is created (pgrc_options_from_env,
@@ -71,7 +79,7 @@ struct PgrcOptions {
 PgrcOptions pgrc_options_from_env();
 bool pgrc_pack_ascii_host(const uint8_t *src, uint64_t count, uint32_t *dst, uint32_t threads);   // api.hip: ASCII ACGT -> 2-bit words, false = a symbol outside ACGT
 
-struct pgrc_match_ctx {
+struct pgrc_match_ctx : PgrcDev {
     PgrcOptions opt;                    // read from the environment by pgrc_match_create (see above)
 
     // several devices behind this object (pgrc_match_create_multi): it is then only the front, the work happens in
@@ -81,12 +89,9 @@ struct pgrc_match_ctx {
     pgrc_match_ctx *export_front = nullptr;   // set in that gathered view: the front whose shards hold the reads (mismatch lists per shard)
 
     pgrc_match_params prm{};
-    int device = 0;
     int num_cus = 256;
-    hipStream_t stream = nullptr;
     hipStream_t side_stream = nullptr;  // the kernel for reads with N runs beside the main match kernel (created on first use)
     hipEvent_t side_ev[2]{};
-    std::string err;
 
     // pseudogenome
     uint64_t G = 0;
@@ -232,9 +237,13 @@ struct PgrcDeviceScope {
         return PGRC_E_NO_DEVICE;                                                             \
     }
 
-int pgrc_buf_ensure(pgrc_match_ctx *c, DevBuf &b, size_t bytes);
+// the pooled allocator (api.hip): grow-only, rounded up, and what it gives back goes to the process-wide pool
+int pgrc_buf_ensure(PgrcDev *c, DevBuf &b, size_t bytes);
 void pgrc_buf_free(DevBuf &b);
 void pgrc_buf_free_all(DevBuf *const *bufs, size_t count);   // one wait for the device for the whole batch
+// the unpooled one: grow-only, exactly `bytes` (64 at least) from hipMalloc, given back with dec_free
+int pgrc_buf_unpooled(PgrcDev *c, DevBuf &b, size_t bytes);
+bool pgrc_host_pinned(const void *p);   // a host pointer that HIP knows as page-locked: copies to and from it need no staging
 
 // api.hip: (re)allocates and clears both strands' text buffers for a text of G symbols
 extern "C" int pgrc_pg_alloc(pgrc_match_ctx *c, uint64_t G);
@@ -263,19 +272,19 @@ std::vector<PgrcShardView> pgrc_multi_shards(pgrc_match_ctx *f);
 void pgrc_export_drop_view(pgrc_match_ctx *front);   // export.hip: forget the gathered view (text, reads or results change)
 
 // pack.hip
-int pgrc_launch_pack_ascii(pgrc_match_ctx *c, const uint8_t *d_ascii, uint64_t count, uint32_t *d_words,
+int pgrc_launch_pack_ascii(PgrcDev *c, const uint8_t *d_ascii, uint64_t count, uint32_t *d_words,
                            uint32_t *d_errflag);
-int pgrc_launch_revcomp(pgrc_match_ctx *c, const uint32_t *d_fw, uint32_t *d_rc, uint64_t G);
-int pgrc_launch_pack_reads_ascii(pgrc_match_ctx *c, const uint8_t *d_ascii, uint64_t first, uint64_t count,
+int pgrc_launch_revcomp(PgrcDev *c, const uint32_t *d_fw, uint32_t *d_rc, uint64_t G);
+int pgrc_launch_pack_reads_ascii(PgrcDev *c, const uint8_t *d_ascii, uint64_t first, uint64_t count,
                                  uint32_t L, uint32_t *d_words, uint64_t stride, uint8_t *d_nflag,
                                  uint32_t *d_errflag);
-int pgrc_launch_repack_reads_ref(pgrc_match_ctx *c, const uint8_t *d_packed, uint64_t first, uint64_t count,
+int pgrc_launch_repack_reads_ref(PgrcDev *c, const uint8_t *d_packed, uint64_t first, uint64_t count,
                                  uint32_t L, uint32_t *d_words, uint64_t stride);
-int pgrc_launch_unpack_reads_acgnt(pgrc_match_ctx *c, const uint8_t *d_packed, uint64_t first, uint64_t count,
+int pgrc_launch_unpack_reads_acgnt(PgrcDev *c, const uint8_t *d_packed, uint64_t first, uint64_t count,
                                    uint32_t L, uint32_t *d_words, uint64_t stride, uint8_t *d_nflag, uint32_t *d_errflag);
-int pgrc_launch_npos_rows(pgrc_match_ctx *c, const uint8_t *d_rows, int symbols, uint64_t first, uint64_t count, uint32_t L,
+int pgrc_launch_npos_rows(PgrcDev *c, const uint8_t *d_rows, int symbols, uint64_t first, uint64_t count, uint32_t L,
                           uint8_t *d_nflag, uint32_t *d_npos);
-int pgrc_launch_nrows_ascii_acgnt(pgrc_match_ctx *c, const uint8_t *d_packed, const uint32_t *d_local_idx, uint64_t count,
+int pgrc_launch_nrows_ascii_acgnt(PgrcDev *c, const uint8_t *d_packed, const uint32_t *d_local_idx, uint64_t count,
                                   uint32_t L, uint8_t *d_ascii);
 
 // copmem.hip
@@ -289,7 +298,7 @@ int pgrc_ps_finish_packed(pgrc_match_ctx *c, const uint64_t *d_recs, const uint3
                           uint32_t rec_sh, uint64_t *d_ent);
 // the shared scan (scanops.h) in place over u32 counts, exclusive; d_fold: pgrc_ps_scan_blocks(n) words of scratch
 uint64_t pgrc_ps_scan_blocks(uint64_t n);
-int pgrc_ps_scan_u32(pgrc_match_ctx *c, uint32_t *d_io, uint64_t n, uint32_t *d_fold);
+int pgrc_ps_scan_u32(PgrcDev *c, uint32_t *d_io, uint64_t n, uint32_t *d_fold);
 // idxsweep.hip: the default front end (one-sweep scatter passes that hash the text themselves, 8-byte records)
 bool pgrc_os_applicable(const pgrc_match_ctx *c, uint32_t hbits);
 int pgrc_os_build_index(pgrc_match_ctx *c, int strand, uint32_t hbits);
@@ -309,13 +318,13 @@ int pgrc_copmem_export_index(pgrc_match_ctx *c, uint32_t *h_cumm, uint32_t *h_po
 
 // radix.hip: stable LSD radix sort of 64-bit records by the bit field [bit_lo, bit_hi) (hand-written; d_b / k_b / v_b: scratch of n
 // records; `scratch` grows as needed; *sorted: wherever the last pass put them); the pairs form carries a 64-bit value per key
-int pgrc_radix_sort_u64(pgrc_match_ctx *c, uint64_t *d_a, uint64_t *d_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, DevBuf &scratch,
+int pgrc_radix_sort_u64(PgrcDev *c, uint64_t *d_a, uint64_t *d_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, DevBuf &scratch,
                         uint64_t **sorted);
-int pgrc_radix_sort_pairs_u64(pgrc_match_ctx *c, uint64_t *k_a, uint64_t *k_b, uint64_t *v_a, uint64_t *v_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi,
+int pgrc_radix_sort_pairs_u64(PgrcDev *c, uint64_t *k_a, uint64_t *k_b, uint64_t *v_a, uint64_t *v_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi,
                               DevBuf &scratch, uint64_t **ksorted, uint64_t **vsorted);
 #define PGRC_RX_SEGMENT_MAX 8192u      // pairs a segment of pgrc_radix_sort_segments_pairs_u64 may hold (radix.hip RX_TILE)
-int pgrc_radix_sort_segments_pairs_u64(pgrc_match_ctx *c, uint64_t *keys, uint64_t *vals, const uint32_t *seg, uint32_t nseg, uint32_t bit_lo, uint32_t bit_hi,
-                                       uint32_t *ovl, uint32_t cap);
+int pgrc_radix_sort_segments_pairs_u64(PgrcDev *c, uint64_t *keys, uint64_t *vals, const uint32_t *seg, uint32_t nseg, uint32_t bit_lo, uint32_t bit_hi,
+                                       uint32_t *ovl, uint32_t cap, uint32_t top_bits);
 
 // seedidx.hip (modes d / i / e)
 int pgrc_seedidx_run(pgrc_match_ctx *c, int first_strand, int last_strand);

@@ -16,23 +16,17 @@
 #define DEC_TEXT_PAD 64         // zero bytes after the text: aligned 16-byte loads past a window's end stay inside
 #define DEC_STAGE_BYTES (64ull << 20)
 
-struct DecBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
-struct pgrc_decode_ctx {
+struct pgrc_decode_ctx : PgrcDev {
     uint32_t L = 0;
-    int device = 0;
-    hipStream_t stream = nullptr, copy_stream = nullptr;
+    hipStream_t copy_stream = nullptr;
     hipEvent_t ev_made[2]{}, ev_copied[2]{}, ev_k0[2]{}, ev_a{}, ev_b{};
     uint8_t *stage[2]{};        // pinned staging (uploads and downloads of pageable memory)
-    DecBuf chunk[2];            // device chunks of rows
-    DecBuf text, flag, scratch;
+    DevBuf chunk[2];            // device chunks of rows
+    DevBuf text, flag, scratch;
     uint64_t text_len = 0;
     bool have_text = false;
     struct List {
-        DecBuf pos, rc, mcum, moff, msym, raw;
+        DevBuf pos, rc, mcum, moff, msym, raw;
         uint64_t n = 0, nmis = 0;
         bool has_pos = false, has_rc = false, has_mis = false;
         uint32_t form = 0;
@@ -42,70 +36,43 @@ struct pgrc_decode_ctx {
     uint32_t nl = 0;
     bool have_order = false;
     pgrc_decode_order ord{};
-    DecBuf rl_order, org2pos, rank;
+    DevBuf rl_order, org2pos, rank;
     pgrc_decode_timing tm{};
     // pgrc_decode_set_mapped_text (restore.hip): the parts of the restored text, its scratch (kept for the next call,
     // freed with the context) and its timing
     bool have_parts = false;
     uint64_t part_len[3] = {};
-    DecBuf rs_mapped, rs_marks, rs_vals, rs_ptr, rs_bsum;   // the mapped parts and streams; per-mark arrays; values; pointers; block counts
-    DecBuf rs_coded, rs_join;   // pgrc_decode_set_mapped_text_coded: the coded bytes and the joined text they decode to
+    DevBuf rs_mapped, rs_marks, rs_vals, rs_ptr, rs_bsum;   // the mapped parts and streams; per-mark arrays; values; pointers; block counts
+    DevBuf rs_coded, rs_join;   // pgrc_decode_set_mapped_text_coded: the coded bytes and the joined text they decode to
     pgrc_decode_restore_timing rtm{};
     // the pair-position coding (pairpos.hip): the uploaded input, the sort's records (and values, W = 8) in turn, per-rank
-    // and per-far-pair arrays, the device-side output, scan scratch; radix.hip's sort runs on a private match-context
-    // shell that borrows this context's stream (pp_mc, made on first use), with pp_sort as its scratch
-    DecBuf pp_in, pp_rec[2], pp_val[2], pp_rank, pp_far, pp_out, pp_bsum;
-    pgrc_match_ctx *pp_mc = nullptr;
+    // and per-far-pair arrays, the device-side output, scan scratch; pp_sort: the scratch of radix.hip's sort
+    DevBuf pp_in, pp_rec[2], pp_val[2], pp_rank, pp_far, pp_out, pp_bsum;
     DevBuf pp_sort;
     hipEvent_t pp_ev[6]{};
     bool have_pp_timing = false;
     pgrc_pairpos_timing ptm{};
     // the pair-order coding (pairorder.hip): the joined orgIdx, rev, per-entry and per-pair arrays, the device-side streams,
     // scan scratch and the two error words
-    DecBuf po_in, po_rev, po_ent, po_pair, po_out, po_bsum;
+    DevBuf po_in, po_rev, po_ent, po_pair, po_out, po_bsum;
     hipEvent_t po_ev[11]{};
     bool have_po_timing = false;
     pgrc_pairorder_timing potm{};
-    std::string err;
 };
 
 // pairpos.hip: the file-major positions of `s` as n_total u64 at d_out (device, on d->stream; synchronised on return);
 // fills d->ptm but for ms_download / ms_call
 int pgrc_pairpos_decode_device(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint64_t *d_out);
 int pgrc_pairpos_check_streams(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s);   // the checks that need no device (PGRC_E_PARAM)
-void pgrc_pairpos_release(pgrc_decode_ctx *d);     // the buffers, events and shell above (pgrc_decode_destroy)
+void pgrc_pairpos_release(pgrc_decode_ctx *d);     // the buffers and events above (pgrc_decode_destroy)
 void pgrc_pairorder_release(pgrc_decode_ctx *d);   // pairorder.hip: its buffers and events (pgrc_decode_destroy)
-
-#define DEC_TRY(d, expr)                                                                     \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            (d)->err = std::string(#expr) + ": " + hipGetErrorString(e__);               \
-            return pgrc_hip_code(e__);                                                       \
-        }                                                                                    \
-    } while (0)
 
 static int dec_fail(pgrc_decode_ctx *d, int code, const std::string &msg) {
     d->err = msg;
     return code;
 }
 
-static int dec_buf(pgrc_decode_ctx *d, DecBuf &b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.p && b.bytes >= bytes) return PGRC_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return dec_fail(d, pgrc_hip_code(e), "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
-    }
-    b.bytes = bytes;
-    return PGRC_OK;
-}
-
-static void dec_free(DecBuf &b) {
+static void dec_free(DevBuf &b) {
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr;
     b.bytes = 0;
@@ -118,7 +85,7 @@ static float dec_elapsed(hipEvent_t a, hipEvent_t b) {
 }
 
 static int dec_clear_err(pgrc_decode_ctx *d) {
-    DEC_TRY(d, hipMemsetAsync(d->flag.p, 0, 4, d->stream));
+    HIP_TRY(d, hipMemsetAsync(d->flag.p, 0, 4, d->stream));
     return PGRC_OK;
 }
 
@@ -129,11 +96,18 @@ static int dec_upload(pgrc_decode_ctx *d, void *d_dst, const void *h_src, uint64
     int k = 0;
     for (uint64_t o = 0; o < bytes; o += DEC_STAGE_BYTES, k ^= 1) {
         const uint64_t c = std::min<uint64_t>(DEC_STAGE_BYTES, bytes - o);
-        DEC_TRY(d, hipEventSynchronize(d->ev_copied[k]));
+        HIP_TRY(d, hipEventSynchronize(d->ev_copied[k]));
         memcpy(d->stage[k], src + o, c);
-        DEC_TRY(d, hipMemcpyAsync(dst + o, d->stage[k], c, hipMemcpyHostToDevice, d->stream));
-        DEC_TRY(d, hipEventRecord(d->ev_copied[k], d->stream));
+        HIP_TRY(d, hipMemcpyAsync(dst + o, d->stage[k], c, hipMemcpyHostToDevice, d->stream));
+        HIP_TRY(d, hipEventRecord(d->ev_copied[k], d->stream));
     }
+    return PGRC_OK;
+}
+
+// the same from memory that may be page-locked: then the copy engine reads it where it is
+static int dec_upload_host(pgrc_decode_ctx *d, void *dst, const void *src, uint64_t bytes) {
+    if (!bytes || !pgrc_host_pinned(src)) return dec_upload(d, dst, src, bytes);
+    HIP_TRY(d, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d->stream));
     return PGRC_OK;
 }
 
@@ -146,8 +120,8 @@ struct XfBelow { const uint64_t *p; uint64_t lim; __device__ uint64_t operator()
 template <bool INCLUSIVE, typename Xf>
 static int dec_scan(pgrc_decode_ctx *d, Xf xf, uint64_t n, uint64_t base_val, uint64_t *d_out) {
     int e;
-    if ((e = dec_buf(d, d->scratch, sco_scratch_elems(n) * sizeof(uint64_t)))) return e;
-    DEC_TRY(d, (sco_device_scan<INCLUSIVE, true>(d->stream, xf, n, ScoPlus{}, (uint64_t)0, base_val, ScoStore<uint64_t>{d_out}, (uint64_t *)d->scratch.p)));
+    if ((e = pgrc_buf_unpooled(d, d->scratch, sco_scratch_elems(n) * sizeof(uint64_t)))) return e;
+    HIP_TRY(d, (sco_device_scan<INCLUSIVE, true>(d->stream, xf, n, ScoPlus{}, (uint64_t)0, base_val, ScoStore<uint64_t>{d_out}, (uint64_t *)d->scratch.p)));
     return PGRC_OK;
 }
 

@@ -287,8 +287,8 @@ static uint32_t dec_rows_per_tile(uint32_t L) {
 
 static int dec_check_err(pgrc_decode_ctx *d, const char *what) {
     uint32_t f = 0;
-    DEC_TRY(d, hipMemcpyAsync(&f, d->flag.p, 4, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipMemcpyAsync(&f, d->flag.p, 4, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     if (!f) return PGRC_OK;
     std::string m = std::string(what) + ":";
     if (f & DEC_F_WINDOW) m += " a window reaches past the text end;";
@@ -327,7 +327,7 @@ int pgrc_decode_create(uint32_t read_length, int32_t device, pgrc_decode_ctx **o
             hipEventCreate(&d->ev_k0[k]) != hipSuccess || hipHostMalloc((void **)&d->stage[k], DEC_STAGE_BYTES) != hipSuccess)
             e = PGRC_E_ALLOC;
     if (!e && (hipEventCreate(&d->ev_a) != hipSuccess || hipEventCreate(&d->ev_b) != hipSuccess)) e = PGRC_E_DEVICE;
-    if (!e) e = dec_buf(d, d->flag, 16);
+    if (!e) e = pgrc_buf_unpooled(d, d->flag, 16);
     if (e) {
         g_dec_create_err = d->err.empty() ? "HIP stream / event / pinned buffer creation failed" : d->err;
         (void)hipGetLastError();
@@ -344,8 +344,8 @@ void pgrc_decode_destroy(pgrc_decode_ctx *d) {
     if (d->stream) (void)hipStreamSynchronize(d->stream);
     if (d->copy_stream) (void)hipStreamSynchronize(d->copy_stream);
     for (auto &l : d->lst)
-        for (DecBuf *b : {&l.pos, &l.rc, &l.mcum, &l.moff, &l.msym, &l.raw}) dec_free(*b);
-    for (DecBuf *b : {&d->chunk[0], &d->chunk[1], &d->text, &d->flag, &d->scratch, &d->rl_order, &d->org2pos, &d->rank, &d->rs_mapped, &d->rs_marks,
+        for (DevBuf *b : {&l.pos, &l.rc, &l.mcum, &l.moff, &l.msym, &l.raw}) dec_free(*b);
+    for (DevBuf *b : {&d->chunk[0], &d->chunk[1], &d->text, &d->flag, &d->scratch, &d->rl_order, &d->org2pos, &d->rank, &d->rs_mapped, &d->rs_marks,
                        &d->rs_vals, &d->rs_ptr, &d->rs_bsum, &d->rs_coded, &d->rs_join})
         dec_free(*b);
     for (int k = 0; k < 2; k++) {
@@ -376,10 +376,10 @@ int pgrc_decode_set_text(pgrc_decode_ctx *d, const char *joined, uint64_t len) {
     d->tm = pgrc_decode_timing{};
     const uint64_t bytes = ((len + 15) & ~15ull) + DEC_TEXT_PAD;
     int e;
-    if ((e = dec_buf(d, d->text, bytes))) return e;
-    DEC_TRY(d, hipMemsetAsync((uint8_t *)d->text.p + (len & ~15ull), 0, bytes - (len & ~15ull), d->stream));
+    if ((e = pgrc_buf_unpooled(d, d->text, bytes))) return e;
+    HIP_TRY(d, hipMemsetAsync((uint8_t *)d->text.p + (len & ~15ull), 0, bytes - (len & ~15ull), d->stream));
     if ((e = dec_upload(d, d->text.p, joined, len))) return e;
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     d->text_len = len;
     d->have_text = true;
     d->tm.ms_text = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -416,46 +416,46 @@ int pgrc_decode_add_list(pgrc_decode_ctx *d, const pgrc_decode_list *a) {
     memcpy(l.order, order, 5);
     int e;
     if ((e = dec_clear_err(d))) return e;
-    DEC_TRY(d, hipEventRecord(d->ev_a, d->stream));
+    HIP_TRY(d, hipEventRecord(d->ev_a, d->stream));
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 4096));
     if (a->off || a->pos) {
         l.has_pos = true;
-        if ((e = dec_buf(d, l.pos, (n + 1) * 8))) return e;
+        if ((e = pgrc_buf_unpooled(d, l.pos, (n + 1) * 8))) return e;
         if (a->off) {
-            if ((e = dec_buf(d, l.raw, n * a->off_width + 16))) return e;
+            if ((e = pgrc_buf_unpooled(d, l.raw, n * a->off_width + 16))) return e;
             if ((e = dec_upload(d, l.raw.p, a->off, n * a->off_width))) return e;
             if (a->off_width == 1) e = dec_scan<true>(d, XfU8{(const uint8_t *)l.raw.p}, n, a->text_base, (uint64_t *)l.pos.p);
             else e = dec_scan<true>(d, XfU16{(const uint16_t *)l.raw.p}, n, a->text_base, (uint64_t *)l.pos.p);
             if (e) return e;
         } else {
-            if ((e = dec_buf(d, l.raw, n * 8 + 16))) return e;
+            if ((e = pgrc_buf_unpooled(d, l.raw, n * 8 + 16))) return e;
             if ((e = dec_upload(d, l.raw.p, a->pos, n * 8))) return e;
             if (n) hipLaunchKernelGGL(k_dec_widen_pos, dim3(grid), dim3(256), 0, d->stream, (const uint64_t *)l.raw.p, n, a->text_base, (uint64_t *)l.pos.p);
         }
         if (n) {
-            if (d->text_len < d->L) DEC_TRY(d, hipMemsetAsync(d->flag.p, DEC_F_WINDOW, 1, d->stream));
+            if (d->text_len < d->L) HIP_TRY(d, hipMemsetAsync(d->flag.p, DEC_F_WINDOW, 1, d->stream));
             else hipLaunchKernelGGL(k_dec_check_windows, dim3(grid), dim3(256), 0, d->stream, (const uint64_t *)l.pos.p, n, d->text_len - d->L, (uint32_t *)d->flag.p);
         }
     }
     if (a->rev_comp) {
         l.has_rc = true;
-        if ((e = dec_buf(d, l.rc, n))) return e;
+        if ((e = pgrc_buf_unpooled(d, l.rc, n))) return e;
         if ((e = dec_upload(d, l.rc.p, a->rev_comp, n))) return e;
     }
     if (a->mis_cnt) {
         l.has_mis = true;
-        if ((e = dec_buf(d, l.raw, std::max<uint64_t>(n, 16)))) return e;
+        if ((e = pgrc_buf_unpooled(d, l.raw, std::max<uint64_t>(n, 16)))) return e;
         if ((e = dec_upload(d, l.raw.p, a->mis_cnt, n))) return e;
-        if ((e = dec_buf(d, l.mcum, (n + 1) * 8))) return e;
+        if ((e = pgrc_buf_unpooled(d, l.mcum, (n + 1) * 8))) return e;
         if ((e = dec_scan<false>(d, XfU8{(const uint8_t *)l.raw.p}, n, 0, (uint64_t *)l.mcum.p))) return e;
         uint64_t nm = 0;
-        DEC_TRY(d, hipMemcpyAsync(&nm, (uint64_t *)l.mcum.p + n, 8, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(d, hipMemcpyAsync(&nm, (uint64_t *)l.mcum.p + n, 8, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
         l.nmis = nm;
         if (nm && (!a->mis_sym || !a->mis_off)) return dec_fail(d, PGRC_E_PARAM, "mismatches counted but mis_sym / mis_off is NULL");
         // raw (reused): the codes, then the offsets at a 16-byte aligned place
         const uint64_t off_at = (nm + 15) & ~15ull;
-        if ((e = dec_buf(d, l.raw, off_at + nm * mw + 16)) || (e = dec_buf(d, l.moff, nm)) || (e = dec_buf(d, l.msym, nm))) return e;
+        if ((e = pgrc_buf_unpooled(d, l.raw, off_at + nm * mw + 16)) || (e = pgrc_buf_unpooled(d, l.moff, nm)) || (e = pgrc_buf_unpooled(d, l.msym, nm))) return e;
         if ((e = dec_upload(d, l.raw.p, a->mis_sym, nm)) || (e = dec_upload(d, (uint8_t *)l.raw.p + off_at, a->mis_off, nm * mw))) return e;
         if (n) {
             const uint8_t *syms = (const uint8_t *)l.raw.p;
@@ -469,8 +469,8 @@ int pgrc_decode_add_list(pgrc_decode_ctx *d, const pgrc_decode_list *a) {
                                    (uint8_t *)l.moff.p, (uint8_t *)l.msym.p, (uint32_t *)d->flag.p);
         }
     }
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->ev_b, d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->ev_b, d->stream));
     if ((e = dec_check_err(d, "add_list"))) return e;
     dec_free(l.raw);
     d->tm.ms_lists_device += dec_elapsed(d->ev_a, d->ev_b);
@@ -491,13 +491,13 @@ static int dec_ord_checks(pgrc_decode_ctx *d, uint64_t T) {
     const uint64_t hq_len = d->nl > 1 ? d->lst[1].text_base : d->text_len;
     int e;
     if (T) {
-        if (d->text_len < d->L) DEC_TRY(d, hipMemsetAsync(d->flag.p, DEC_F_WINDOW, 1, d->stream));
+        if (d->text_len < d->L) HIP_TRY(d, hipMemsetAsync(d->flag.p, DEC_F_WINDOW, 1, d->stream));
         else hipLaunchKernelGGL(k_dec_check_windows, dim3(grid), dim3(256), 0, d->stream, (const uint64_t *)d->org2pos.p, T, d->text_len - d->L, (uint32_t *)d->flag.p);
     }
     if ((e = dec_scan<false>(d, XfBelow{(const uint64_t *)d->org2pos.p, hq_len}, T, 0, (uint64_t *)d->rank.p))) return e;
     uint64_t hq_rows = 0;
-    DEC_TRY(d, hipMemcpyAsync(&hq_rows, (uint64_t *)d->rank.p + T, 8, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipMemcpyAsync(&hq_rows, (uint64_t *)d->rank.p + T, 8, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     if (hq_rows > d->lst[0].n) return dec_fail(d, PGRC_E_PARAM, "ORD order: more rows below hqPgLen than HQ entries");
     return PGRC_OK;
 }
@@ -511,26 +511,26 @@ int pgrc_decode_set_order(pgrc_decode_ctx *d, const pgrc_decode_order *o) {
     const uint64_t T = o->n_total;
     int e;
     if ((e = dec_clear_err(d))) return e;
-    DEC_TRY(d, hipEventRecord(d->ev_a, d->stream));
+    HIP_TRY(d, hipEventRecord(d->ev_a, d->stream));
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((T + 255) / 256, 4096));
     if (o->mode == PGRC_DECODE_SE) {
         if (o->rev_compl_pair_file) return dec_fail(d, PGRC_E_PARAM, "the pair-file rule needs PE or ORD order");
     } else if (o->mode == PGRC_DECODE_PE) {
         if (!o->rl_idx_order && T) return dec_fail(d, PGRC_E_PARAM, "PE order without rl_idx_order");
         if (T != dec_entries(d)) return dec_fail(d, PGRC_E_PARAM, "PE order: n_total differs from the lists' entries");
-        if ((e = dec_buf(d, d->rl_order, T * 4))) return e;
+        if ((e = pgrc_buf_unpooled(d, d->rl_order, T * 4))) return e;
         if ((e = dec_upload(d, d->rl_order.p, o->rl_idx_order, T * 4))) return e;
         if (T) hipLaunchKernelGGL(k_dec_check_index, dim3(grid), dim3(256), 0, d->stream, (const uint32_t *)d->rl_order.p, T, dec_entries(d), (uint32_t *)d->flag.p);
     } else if (o->mode == PGRC_DECODE_ORD) {
         if (!o->org_idx_to_pos && T) return dec_fail(d, PGRC_E_PARAM, "ORD order without org_idx_to_pos");
-        if ((e = dec_buf(d, d->org2pos, T * 8)) || (e = dec_buf(d, d->rank, (T + 1) * 8))) return e;
+        if ((e = pgrc_buf_unpooled(d, d->org2pos, T * 8)) || (e = pgrc_buf_unpooled(d, d->rank, (T + 1) * 8))) return e;
         if ((e = dec_upload(d, d->org2pos.p, o->org_idx_to_pos, T * 8))) return e;
         if ((e = dec_ord_checks(d, T))) return e;
     } else {
         return dec_fail(d, PGRC_E_PARAM, "unknown order mode");
     }
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->ev_b, d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->ev_b, d->stream));
     if ((e = dec_check_err(d, "set_order"))) return e;
     d->tm.ms_order_device = dec_elapsed(d->ev_a, d->ev_b);
     d->ord = *o;
@@ -550,13 +550,13 @@ int pgrc_decode_set_order_pair_streams(pgrc_decode_ctx *d, const pgrc_pairpos_st
     PGRC_ON_DEVICE(d);
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t T = s->n_total;
-    if ((e = dec_buf(d, d->org2pos, T * 8)) || (e = dec_buf(d, d->rank, (T + 1) * 8))) return e;
+    if ((e = pgrc_buf_unpooled(d, d->org2pos, T * 8)) || (e = pgrc_buf_unpooled(d, d->rank, (T + 1) * 8))) return e;
     if ((e = pgrc_pairpos_decode_device(d, s, (uint64_t *)d->org2pos.p))) return e;
     if ((e = dec_clear_err(d))) return e;
-    DEC_TRY(d, hipEventRecord(d->ev_a, d->stream));
+    HIP_TRY(d, hipEventRecord(d->ev_a, d->stream));
     if ((e = dec_ord_checks(d, T))) return e;
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->ev_b, d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->ev_b, d->stream));
     if ((e = dec_check_err(d, "set_order_pair_streams"))) return e;
     d->tm.ms_order_device = dec_elapsed(d->ev_a, d->ev_b);
     d->ord = pgrc_decode_order{};
@@ -637,7 +637,7 @@ static int dec_launch(pgrc_decode_ctx *d, DecArgs a, uint64_t first, uint64_t n,
     a.out = (uint8_t *)d_out;
     const uint64_t blocks = (n + a.R - 1) / a.R;
     hipLaunchKernelGGL(k_dec_rows, dim3((uint32_t)blocks), dim3(DEC_TPB), 0, d->stream, a);
-    DEC_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
     return PGRC_OK;
 }
 
@@ -662,13 +662,13 @@ int pgrc_decode_rows_device(pgrc_decode_ctx *d, uint32_t file, uint64_t first, u
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t R = dec_rows_per_tile(d->L);
     if ((e = dec_clear_err(d))) return e;
-    DEC_TRY(d, hipEventRecord(d->ev_a, d->stream));
+    HIP_TRY(d, hipEventRecord(d->ev_a, d->stream));
     // launches of at most 2^31 / R tiles (the grid's x limit)
     const uint64_t step = (uint64_t)R * (1ull << 30);
     const DecArgs a = dec_args(d, file, R);
     for (uint64_t o = 0; o < n; o += step)
         if ((e = dec_launch(d, a, first + o, std::min(step, n - o), (uint8_t *)d_out + o * (d->L + 1)))) return e;
-    DEC_TRY(d, hipEventRecord(d->ev_b, d->stream));
+    HIP_TRY(d, hipEventRecord(d->ev_b, d->stream));
     if ((e = dec_check_err(d, "rows"))) return e;
     d->tm.ms_rows_device = dec_elapsed(d->ev_a, d->ev_b);
     d->tm.rows_bytes = n * (d->L + 1);
@@ -686,12 +686,9 @@ int pgrc_decode_rows(pgrc_decode_ctx *d, uint32_t file, uint64_t first, uint64_t
     const uint32_t R = dec_rows_per_tile(d->L), L1 = d->L + 1;
     const uint64_t crows = std::max<uint64_t>(R, DEC_CHUNK_BYTES / L1 / R * R);     // rows of one chunk: whole tiles
     const uint64_t cbytes = crows * L1;
-    if ((e = dec_buf(d, d->chunk[0], cbytes)) || (e = dec_buf(d, d->chunk[1], cbytes))) return e;
+    if ((e = pgrc_buf_unpooled(d, d->chunk[0], cbytes)) || (e = pgrc_buf_unpooled(d, d->chunk[1], cbytes))) return e;
     // pinned memory of the caller is written by the copy engine itself; other memory through the staging buffers
-    bool direct = false;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, out) == hipSuccess) direct = attr.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();
+    const bool direct = pgrc_host_pinned(out);
     if (!direct && cbytes > DEC_STAGE_BYTES) return dec_fail(d, PGRC_E_PARAM, "internal: chunk above the staging size");
     if ((e = dec_clear_err(d))) return e;
     const DecArgs a = dec_args(d, file, R);
@@ -703,19 +700,19 @@ int pgrc_decode_rows(pgrc_decode_ctx *d, uint32_t file, uint64_t first, uint64_t
         const int k = (int)(c & 1);
         const uint64_t r0 = c * crows, rn = std::min(crows, n - r0);
         if (c >= 2) {   // chunk c-2 used these buffers: its copy is done before the kernel overwrites them
-            DEC_TRY(d, hipEventSynchronize(d->ev_copied[k]));
+            HIP_TRY(d, hipEventSynchronize(d->ev_copied[k]));
             ms_k += dec_elapsed(d->ev_k0[k], d->ev_made[k]);
         }
-        DEC_TRY(d, hipEventRecord(d->ev_k0[k], d->stream));
+        HIP_TRY(d, hipEventRecord(d->ev_k0[k], d->stream));
         if ((e = dec_launch(d, a, first + r0, rn, d->chunk[k].p))) return e;
-        DEC_TRY(d, hipEventRecord(d->ev_made[k], d->stream));
-        DEC_TRY(d, hipStreamWaitEvent(d->copy_stream, d->ev_made[k], 0));
+        HIP_TRY(d, hipEventRecord(d->ev_made[k], d->stream));
+        HIP_TRY(d, hipStreamWaitEvent(d->copy_stream, d->ev_made[k], 0));
         void *dst = direct ? (void *)(out + r0 * L1) : (void *)d->stage[k];
-        DEC_TRY(d, hipMemcpyAsync(dst, d->chunk[k].p, rn * L1, hipMemcpyDeviceToHost, d->copy_stream));
-        DEC_TRY(d, hipEventRecord(d->ev_copied[k], d->copy_stream));
+        HIP_TRY(d, hipMemcpyAsync(dst, d->chunk[k].p, rn * L1, hipMemcpyDeviceToHost, d->copy_stream));
+        HIP_TRY(d, hipEventRecord(d->ev_copied[k], d->copy_stream));
         if (!direct) {
             if (pend_k >= 0) {   // the previous chunk is down (or nearly): hand it over while this one is made and copied
-                DEC_TRY(d, hipEventSynchronize(d->ev_copied[pend_k]));
+                HIP_TRY(d, hipEventSynchronize(d->ev_copied[pend_k]));
                 memcpy(out + pend_off, d->stage[pend_k], pend_bytes);
             }
             pend_k = k;
@@ -723,7 +720,7 @@ int pgrc_decode_rows(pgrc_decode_ctx *d, uint32_t file, uint64_t first, uint64_t
             pend_bytes = rn * L1;
         }
     }
-    DEC_TRY(d, hipStreamSynchronize(d->copy_stream));
+    HIP_TRY(d, hipStreamSynchronize(d->copy_stream));
     if (pend_k >= 0) memcpy(out + pend_off, d->stage[pend_k], pend_bytes);
     for (uint64_t c = nchunks >= 2 ? nchunks - 2 : 0; c < nchunks; c++) ms_k += dec_elapsed(d->ev_k0[c & 1], d->ev_made[c & 1]);
     if ((e = dec_check_err(d, "rows"))) return e;

@@ -35,8 +35,7 @@
 #define DVF_BAD 2u          // a byte outside ACGNT in the symbol row
 #define DVF_BAD_Q 4u        // a quality character beyond the reference's table (133 entries)
 
-struct pgrc_divider {
-    pgrc_match_ctx base;     // device, stream, error text, scan scratch (only the plumbing of the matcher's context)
+struct pgrc_divider : PgrcDev {
     pgrc_divide_params prm{};
     int suffix_pos = 0;
     DevBuf d_reads, d_quals, d_flags, d_high, d_cls, d_cnt[3], d_bsum, d_rows[3], d_idx[2], d_lut, d_err;
@@ -59,7 +58,7 @@ static int dv_host_ensure(pgrc_divider *d, pgrc_divider::HostBuf &b, size_t byte
     if (hipHostMalloc(&b.p, want, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
         b.p = nullptr;
-        d->base.err = "divider: pinned host allocation of " + std::to_string(want) + " bytes failed";
+        d->err = "divider: pinned host allocation of " + std::to_string(want) + " bytes failed";
         return PGRC_E_ALLOC;
     }
     b.bytes = want;
@@ -317,18 +316,9 @@ k_fq_rows(const FqRowsArgs a) {
 
 // ------------------------------------------------------------------------------------------------ host side
 
-#define DIV_TRY(d, expr)                                                                     \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            (d)->base.err = std::string(#expr) + ": " + hipGetErrorString(e__);              \
-            return pgrc_hip_code(e__);                                                       \
-        }                                                                                    \
-    } while (0)
-
 extern "C" {
 
-const char *pgrc_divider_last_error(const pgrc_divider *d) { return d ? d->base.err.c_str() : g_div_create_err.c_str(); }
+const char *pgrc_divider_last_error(const pgrc_divider *d) { return d ? d->err.c_str() : g_div_create_err.c_str(); }
 
 int pgrc_divider_create(const pgrc_divide_params *p, pgrc_divider **out) {
     if (!p || !out) return PGRC_E_PARAM;
@@ -348,7 +338,7 @@ int pgrc_divider_create(const pgrc_divide_params *p, pgrc_divider **out) {
     (void)hipGetLastError();
     pgrc_divider *d = new pgrc_divider();
     d->prm = *p;
-    d->base.device = dev;
+    d->device = dev;
     // suffix_pos = read_length * (1 - error_level), a double truncated to int (DivisionReadsSetDecorators.cpp:14)
     d->suffix_pos = (int)((double)p->read_len * (1 - p->error_limit));
     // (suffix_pos == read_len -- error_limit 0 -- is what the reference accepts too: it tests the quality string's terminator)
@@ -357,19 +347,19 @@ int pgrc_divider_create(const pgrc_divide_params *p, pgrc_divider **out) {
         delete d;
         return PGRC_E_PARAM;
     }
-    he = hipStreamCreateWithFlags(&d->base.stream, hipStreamNonBlocking);
+    he = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
     // qualityLut (helper.cpp:284-327): the probability that a base call of Phred quality q is right, 1 - 10^(-q / 10), as a
     // float, for the characters '!' + 0 .. '!' + 40; 1 for the next 59; 0 below '!'.  (The reference spells the 41 values
     // out as decimal literals; their float roundings equal those of the formula -- tests/test_divide_oracle.py.)
     float lut[133];
     for (int c = 0; c < 133; c++) lut[c] = c < 33 ? 0.f : (c - 33 <= 40 ? (float)(1.0 - pow(10.0, -(double)(c - 33) / 10.0)) : 1.f);
     int e = PGRC_OK;
-    if (he == hipSuccess) e = pgrc_buf_ensure(&d->base, d->d_lut, sizeof lut);
-    if (he == hipSuccess && !e) e = pgrc_buf_ensure(&d->base, d->d_err, sizeof(uint32_t));
-    if (he == hipSuccess && !e) he = hipMemcpyAsync(d->d_lut.p, lut, sizeof lut, hipMemcpyHostToDevice, d->base.stream);
-    if (he == hipSuccess && !e) he = hipStreamSynchronize(d->base.stream);
+    if (he == hipSuccess) e = pgrc_buf_ensure(d, d->d_lut, sizeof lut);
+    if (he == hipSuccess && !e) e = pgrc_buf_ensure(d, d->d_err, sizeof(uint32_t));
+    if (he == hipSuccess && !e) he = hipMemcpyAsync(d->d_lut.p, lut, sizeof lut, hipMemcpyHostToDevice, d->stream);
+    if (he == hipSuccess && !e) he = hipStreamSynchronize(d->stream);
     if (he != hipSuccess || e) {
-        g_div_create_err = he != hipSuccess ? std::string("divider: ") + hipGetErrorString(he) : d->base.err;
+        g_div_create_err = he != hipSuccess ? std::string("divider: ") + hipGetErrorString(he) : d->err;
         const int code = he != hipSuccess ? pgrc_hip_code(he) : e;
         pgrc_divider_destroy(d);
         return code;
@@ -380,7 +370,7 @@ int pgrc_divider_create(const pgrc_divide_params *p, pgrc_divider **out) {
 
 void pgrc_divider_destroy(pgrc_divider *d) {
     if (!d) return;
-    PgrcDeviceScope scope(d->base.device);
+    PgrcDeviceScope scope(d->device);
     (void)hipDeviceSynchronize();
     DevBuf *bufs[] = {&d->d_reads, &d->d_quals, &d->d_flags, &d->d_high, &d->d_cls, &d->d_cnt[0], &d->d_cnt[1], &d->d_cnt[2], &d->d_bsum,
                       &d->d_rows[0], &d->d_rows[1], &d->d_rows[2], &d->d_idx[0], &d->d_idx[1], &d->d_lut, &d->d_err,
@@ -390,7 +380,7 @@ void pgrc_divider_destroy(pgrc_divider *d) {
         if (h->p) (void)hipHostFree(h->p);
     if (d->have_ev)
         for (auto &x : d->ev) (void)hipEventDestroy(x);
-    if (d->base.stream) (void)hipStreamDestroy(d->base.stream);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
 
@@ -407,7 +397,7 @@ int pgrc_divider_last_ms(const pgrc_divider *d, float ms[3]) {
 static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out) {
     const pgrc_divide_params &p = d->prm;
     const bool by_quality = p.error_limit < 1;
-    pgrc_match_ctx *c = &d->base;
+    PgrcDev *c = d;
     const uint32_t L = p.read_len;
     const bool n_apart = p.separate_n_reads_set || p.n_reads_lq;
     // alphabets (DividedPCLReadsSets.cpp:10-21)
@@ -428,8 +418,8 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
     for (int k = 0; k < 3; k++)
         if ((e = pgrc_buf_ensure(c, d->d_cnt[k], (n + 1) * sizeof(uint32_t)))) return e;
     hipStream_t s = c->stream;
-    DIV_TRY(d, hipMemsetAsync(d->d_flags.p, 0, n * sizeof(uint32_t), s));
-    DIV_TRY(d, hipMemsetAsync(d->d_err.p, 0, sizeof(uint32_t), s));
+    HIP_TRY(d, hipMemsetAsync(d->d_flags.p, 0, n * sizeof(uint32_t), s));
+    HIP_TRY(d, hipMemsetAsync(d->d_err.p, 0, sizeof(uint32_t), s));
     const uint32_t g = (uint32_t)((n + 1 + 255) / 256);
     hipLaunchKernelGGL(k_dv_symbols, dim3((uint32_t)std::min<uint64_t>((bytes / 4 + 255) / 256 + 1, 65536)), dim3(256), 0, s,
                        (const uint8_t *)d->d_reads.p, (uint64_t)bytes, L, (uint32_t *)d->d_flags.p);
@@ -439,13 +429,13 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
     hipLaunchKernelGGL(k_dv_class, dim3(g), dim3(256), 0, s, (const uint32_t *)d->d_flags.p, (const uint8_t *)d->d_high.p, n, n_apart ? 1 : 0,
                        p.separate_n_reads_set ? 1 : 0, by_quality ? 1 : 0, (uint8_t *)d->d_cls.p, (uint32_t *)d->d_cnt[0].p,
                        (uint32_t *)d->d_cnt[1].p, (uint32_t *)d->d_cnt[2].p, (uint32_t *)d->d_err.p);
-    DIV_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
     for (int k = 0; k < 3; k++)
         if ((e = pgrc_ps_scan_u32(c, (uint32_t *)d->d_cnt[k].p, n + 1, (uint32_t *)d->d_bsum.p))) return e;
     uint32_t cnt[3] = {0, 0, 0}, bad = 0;
-    for (int k = 0; k < 3; k++) DIV_TRY(d, hipMemcpyAsync(&cnt[k], (const uint32_t *)d->d_cnt[k].p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    DIV_TRY(d, hipMemcpyAsync(&bad, d->d_err.p, sizeof bad, hipMemcpyDeviceToHost, s));
-    DIV_TRY(d, hipStreamSynchronize(s));
+    for (int k = 0; k < 3; k++) HIP_TRY(d, hipMemcpyAsync(&cnt[k], (const uint32_t *)d->d_cnt[k].p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(d, hipMemcpyAsync(&bad, d->d_err.p, sizeof bad, hipMemcpyDeviceToHost, s));
+    HIP_TRY(d, hipStreamSynchronize(s));
     if (bad & DVF_BAD) { c->err = "reads contain a symbol outside ACGNT"; return PGRC_E_SYMBOL; }
     if (bad & DVF_BAD_Q) { c->err = "a quality character lies beyond the reference's table (133 entries)"; return PGRC_E_SYMBOL; }
     for (int k = 0; k < 3; k++)
@@ -469,7 +459,7 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
     a.n = n;
     const uint64_t work = n * a.row_bytes_max;
     hipLaunchKernelGGL(k_dv_pack, dim3((uint32_t)((work + 255) / 256)), dim3(256), 0, s, a);
-    DIV_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
     (void)hipEventRecord(d->ev[2], s);
     out->n_hq = cnt[0]; out->n_lq = cnt[1]; out->n_n = cnt[2];
     for (int k = 0; k < 3; k++)
@@ -495,7 +485,7 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
 
 static int dv_events(pgrc_divider *d) {
     if (d->have_ev) return PGRC_OK;
-    for (auto &x : d->ev) DIV_TRY(d, hipEventCreate(&x));
+    for (auto &x : d->ev) HIP_TRY(d, hipEventCreate(&x));
     d->have_ev = true;
     return PGRC_OK;
 }
@@ -504,9 +494,9 @@ int pgrc_divider_run(pgrc_divider *d, const char *reads, const char *quals, uint
     if (!d || !out || (n && !reads)) return PGRC_E_PARAM;
     memset(out, 0, sizeof *out);
     const bool by_quality = d->prm.error_limit < 1;
-    if (by_quality && n && !quals) { d->base.err = "divider: quality rows are needed when error_limit < 1"; return PGRC_E_PARAM; }
-    if (n >= (1ull << 32) - 1) { d->base.err = "divider: batches of less than 2^32 - 1 reads"; return PGRC_E_PARAM; }
-    pgrc_match_ctx *c = &d->base;
+    if (by_quality && n && !quals) { d->err = "divider: quality rows are needed when error_limit < 1"; return PGRC_E_PARAM; }
+    if (n >= (1ull << 32) - 1) { d->err = "divider: batches of less than 2^32 - 1 reads"; return PGRC_E_PARAM; }
+    PgrcDev *c = d;
     PgrcDeviceScope scope(c->device);
     if (!scope.ok) { c->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     int e;
@@ -515,8 +505,8 @@ int pgrc_divider_run(pgrc_divider *d, const char *reads, const char *quals, uint
     if (n) {
         if ((e = pgrc_buf_ensure(c, d->d_reads, bytes + 16)) || (by_quality && (e = pgrc_buf_ensure(c, d->d_quals, bytes + 16)))) return e;
         (void)hipEventRecord(d->ev[0], c->stream);
-        DIV_TRY(d, hipMemcpyAsync(d->d_reads.p, reads, bytes, hipMemcpyHostToDevice, c->stream));
-        if (by_quality) DIV_TRY(d, hipMemcpyAsync(d->d_quals.p, quals, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(d, hipMemcpyAsync(d->d_reads.p, reads, bytes, hipMemcpyHostToDevice, c->stream));
+        if (by_quality) HIP_TRY(d, hipMemcpyAsync(d->d_quals.p, quals, bytes, hipMemcpyHostToDevice, c->stream));
         (void)hipEventRecord(d->ev[1], c->stream);
     }
     return divide_resident(d, n, out);
@@ -538,7 +528,7 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
     *consumed = 0;
     *n_records = 0;
     if (pair_consumed) *pair_consumed = 0;
-    pgrc_match_ctx *c = &d->base;
+    PgrcDev *c = d;
     if (bytes >= (1ull << 31) || pair_bytes >= (1ull << 31)) { c->err = "divider: pieces of FASTQ text below 2 GiB"; return PGRC_E_PARAM; }
     PgrcDeviceScope scope(c->device);
     if (!scope.ok) { c->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
@@ -560,15 +550,15 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
         if ((e = pgrc_buf_ensure(c, d->d_text[f], len[f] + 32)) || (e = pgrc_buf_ensure(c, d->d_nl[f], (n16 + 1) * sizeof(uint32_t))) ||
             (e = pgrc_buf_ensure(c, d->d_bsum, pgrc_ps_scan_blocks(n16 + 1) * sizeof(uint32_t))))
             return e;
-        if (len[f]) DIV_TRY(d, hipMemcpyAsync(d->d_text[f].p, src[f], len[f], hipMemcpyHostToDevice, s));
-        DIV_TRY(d, hipMemsetAsync((uint8_t *)d->d_text[f].p + len[f], 0, 32, s));
+        if (len[f]) HIP_TRY(d, hipMemcpyAsync(d->d_text[f].p, src[f], len[f], hipMemcpyHostToDevice, s));
+        HIP_TRY(d, hipMemsetAsync((uint8_t *)d->d_text[f].p + len[f], 0, 32, s));
         hipLaunchKernelGGL(k_fq_count, dim3((uint32_t)((n16 + 1 + 255) / 256)), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, len[f], n16,
                            (uint32_t *)d->d_nl[f].p);
         if ((e = pgrc_ps_scan_u32(c, (uint32_t *)d->d_nl[f].p, n16 + 1, (uint32_t *)d->d_bsum.p))) return e;
         uint32_t nl = 0;
         uint8_t last = '\n';
-        DIV_TRY(d, hipMemcpyAsync(&nl, (const uint32_t *)d->d_nl[f].p + n16, sizeof nl, hipMemcpyDeviceToHost, s));
-        DIV_TRY(d, hipStreamSynchronize(s));
+        HIP_TRY(d, hipMemcpyAsync(&nl, (const uint32_t *)d->d_nl[f].p + n16, sizeof nl, hipMemcpyDeviceToHost, s));
+        HIP_TRY(d, hipStreamSynchronize(s));
         if (len[f]) last = (uint8_t)src[f][len[f] - 1];
         // std::getline: a last piece without its newline is a line too, once nothing more will come
         lines[f] = nl + ((fin[f] && len[f] && last != '\n') ? 1u : 0u);
@@ -576,7 +566,7 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
         if ((e = pgrc_buf_ensure(c, d->d_ls[f], ((size_t)nl + 8) * sizeof(uint32_t)))) return e;
         hipLaunchKernelGGL(k_fq_starts, dim3((uint32_t)((n16 + 255) / 256 + 1)), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, len[f], n16,
                            (const uint32_t *)d->d_nl[f].p, nl, (uint32_t *)d->d_ls[f].p);
-        DIV_TRY(d, hipGetLastError());
+        HIP_TRY(d, hipGetLastError());
     }
     // whole records in what we have: four lines each
     const uint64_t rec[2] = {lines[0] / 4, lines[1] / 4};
@@ -604,7 +594,7 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
     if (n >= (1ull << 32) - 1) { c->err = "divider: batches of less than 2^32 - 1 reads"; return PGRC_E_PARAM; }
     const size_t rows = (size_t)n * L;
     if ((e = pgrc_buf_ensure(c, d->d_reads, rows + 16)) || (by_quality && (e = pgrc_buf_ensure(c, d->d_quals, rows + 16)))) return e;
-    DIV_TRY(d, hipMemsetAsync(d->d_err.p, 0, sizeof(uint32_t), s));
+    HIP_TRY(d, hipMemsetAsync(d->d_err.p, 0, sizeof(uint32_t), s));
     uint32_t ends[2] = {0, 0};        // first byte after the last record taken from each piece
     if (n) {
         FqRowsArgs a;
@@ -623,12 +613,12 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
         a.err = (uint32_t *)d->d_err.p;
         const uint64_t work = n * (L + 1);
         hipLaunchKernelGGL(k_fq_rows, dim3((uint32_t)((work + 255) / 256)), dim3(256), 0, s, a);
-        DIV_TRY(d, hipGetLastError());
+        HIP_TRY(d, hipGetLastError());
         uint32_t bad = 0;
-        DIV_TRY(d, hipMemcpyAsync(&bad, d->d_err.p, sizeof bad, hipMemcpyDeviceToHost, s));
+        HIP_TRY(d, hipMemcpyAsync(&bad, d->d_err.p, sizeof bad, hipMemcpyDeviceToHost, s));
         for (int f = 0; f < (paired ? 2 : 1); f++)         // line 4 * take starts where the records taken end (ls[nl + 1] = the end of the text)
-            if (take[f]) DIV_TRY(d, hipMemcpyAsync(&ends[f], (const uint32_t *)d->d_ls[f].p + 4 * take[f], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        DIV_TRY(d, hipStreamSynchronize(s));
+            if (take[f]) HIP_TRY(d, hipMemcpyAsync(&ends[f], (const uint32_t *)d->d_ls[f].p + 4 * take[f], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(d, hipStreamSynchronize(s));
         if (bad) { c->err = "Unsupported variable length reads (a FASTQ record whose read is not read_len letters long)"; return PGRC_E_PARAM; }
     }
     *consumed = ends[0];

@@ -510,9 +510,6 @@ __global__ void __launch_bounds__(256) k_ord_reads(const uint64_t *__restrict__ 
         order[k] = (uint32_t)rec[k];
 }
 
-int pgrc_radix_sort_u64(pgrc_match_ctx *c, uint64_t *d_a, uint64_t *d_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, DevBuf &scratch,
-                        uint64_t **sorted);
-
 // -> b.order (device), *m_out = matched reads
 static int device_position_order(pgrc_match_ctx *c, Bufs &b, uint64_t *m_out) {
     const uint64_t n = c->n;

@@ -45,7 +45,7 @@ struct PsPlan {
 uint64_t pgrc_ps_scan_blocks(uint64_t n) { return sco_scratch_elems(n); }
 
 // in place: counts -> exclusive prefix sums (d_fold: pgrc_ps_scan_blocks(n) words of scratch)
-int pgrc_ps_scan_u32(pgrc_match_ctx *c, uint32_t *d_io, uint64_t n, uint32_t *d_fold) {
+int pgrc_ps_scan_u32(PgrcDev *c, uint32_t *d_io, uint64_t n, uint32_t *d_fold) {
     HIP_TRY(c, sco_scan<false>(c->stream, (const uint32_t *)d_io, d_io, n, ScoIdentity{}, ScoPlus{}, 0u, d_fold));
     return PGRC_OK;
 }

@@ -729,7 +729,7 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     m->ctr.probes = nprobes;
     int e;
     if (!m->have_ev) {
-        for (auto &x : m->ev) MEM_TRY(m, hipEventCreate(&x));
+        for (auto &x : m->ev) HIP_TRY(m, hipEventCreate(&x));
         m->have_ev = true;
     }
     hipEvent_t *ev = m->ev;
@@ -766,7 +766,7 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
             if (he != hipSuccess) { m->err = std::string("destination upload: ") + hipGetErrorString(he); return PGRC_E_DEVICE; }
         }
         uint32_t fl = 0;
-        MEM_TRY(m, hipMemcpy(&fl, m->d_flag.p, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(m, hipMemcpy(&fl, m->d_flag.p, 4, hipMemcpyDeviceToHost));
         // no window reads it: no error, as before texts shorter than K were uploaded; but it cannot be mapped (pgrc_mem.h)
         if ((fl & 1u) && nprobes == 0) return PGRC_OK;
         if (fl & 1u) { m->err = "destination text contains a symbol outside ACGNT"; return PGRC_E_SYMBOL; }
@@ -857,7 +857,7 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     // d_small: [0] "a block was replayed" flag, [1] first stale event, [2] events with a context outside a text, [4..7] two u64 of a range
     uint32_t *d_changed = (uint32_t *)m->d_small.p, *d_first_stale = d_changed + 1, *d_nstale = d_changed + 2;
     uint64_t *d_range = (uint64_t *)m->d_small.p + 2;
-    MEM_TRY(m, hipMemsetAsync(m->d_small.p, 0, 64, c->stream));
+    HIP_TRY(m, hipMemsetAsync(m->d_small.p, 0, 64, c->stream));
     const uint32_t g = (uint32_t)((nev + 255) / 256);
     // scratch of the scans below (scanops.h): block folds of nev values
     if ((e = pgrc_buf_ensure(c, m->d_scan, sco_scratch_elems(nev) * sizeof(uint32_t)))) { m->err = c->err; return e; }
@@ -874,12 +874,12 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
         if ((e = pgrc_radix_sort_pairs_u64(c, sk0, (uint64_t *)m->d_skey[1].p, si0, (uint64_t *)m->d_sidx[1].p, nev, 0, (uint32_t)db, m->d_tmp, &sks, &sis))) { m->err = c->err; return e; }
         const uint64_t *sidx = sis, *skey = sks;
         hipLaunchKernelGGL(k_mem_connect, dim3(g), dim3(256), 0, c->stream, a, ek, ep, sidx, skey, (uint64_t)nev, (uint32_t *)m->d_first.p);
-        MEM_TRY(m, (sco_scan<true>(c->stream, (const uint32_t *)m->d_first.p, (uint32_t *)m->d_runid.p, (uint64_t)nev, ScoIdentity(), ScoPlus(), 0u, d_bsum)));
+        HIP_TRY(m, (sco_scan<true>(c->stream, (const uint32_t *)m->d_first.p, (uint32_t *)m->d_runid.p, (uint64_t)nev, ScoIdentity(), ScoPlus(), 0u, d_bsum)));
         hipLaunchKernelGGL(k_mem_run_ends, dim3(g), dim3(256), 0, c->stream, a, ek, ep, sidx, (const uint32_t *)m->d_first.p,
                            (const uint32_t *)m->d_runid.p, (uint64_t)nev, (uint64_t *)m->d_rstart.p, (uint64_t *)m->d_rend.p, (uint64_t *)m->d_rdend.p);
         hipLaunchKernelGGL(k_mem_apply, dim3(g), dim3(256), 0, c->stream, sidx, (const uint32_t *)m->d_runid.p, (uint64_t)nev,
                            (const uint64_t *)m->d_rstart.p, (const uint64_t *)m->d_rend.p, min_len, (uint32_t *)m->d_orun.p, (uint8_t *)m->d_oflag.p);
-        MEM_TRY(m, hipGetLastError());
+        HIP_TRY(m, hipGetLastError());
     }
     (void)hipEventRecord(ev[3], c->stream);
 
@@ -894,11 +894,11 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     }
     uint32_t *d_lead = (uint32_t *)m->d_first.p, *d_lid = (uint32_t *)m->d_runid.p;      // (free again: the runs are numbered)
     hipLaunchKernelGGL(k_mem_lead, dim3(g), dim3(256), 0, c->stream, ek, (uint64_t)nev, nmain, d_lead);
-    MEM_TRY(m, (sco_scan<true>(c->stream, (const uint32_t *)d_lead, d_lid, (uint64_t)nev, ScoIdentity(), ScoPlus(), 0u, d_bsum)));
+    HIP_TRY(m, (sco_scan<true>(c->stream, (const uint32_t *)d_lead, d_lid, (uint64_t)nev, ScoIdentity(), ScoPlus(), 0u, d_bsum)));
     uint32_t neb = 0, nstale = 0;
-    MEM_TRY(m, hipMemcpyAsync(&neb, d_lid + (nev - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    MEM_TRY(m, hipMemcpyAsync(&nstale, d_nstale, 4, hipMemcpyDeviceToHost, c->stream));
-    MEM_TRY(m, hipStreamSynchronize(c->stream));
+    HIP_TRY(m, hipMemcpyAsync(&neb, d_lid + (nev - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(m, hipMemcpyAsync(&nstale, d_nstale, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(m, hipStreamSynchronize(c->stream));
     m->ctr.event_blocks = neb;
     if ((e = pgrc_buf_ensure(c, m->d_ebstart, ((size_t)neb + 1) * 4)) || (e = pgrc_buf_ensure(c, m->d_ebin, (size_t)neb * 4)) ||
         (e = pgrc_buf_ensure(c, m->d_ebout, (size_t)neb * 4)) || (e = pgrc_buf_ensure(c, m->d_ebinc, (size_t)neb * 4))) { m->err = c->err; return e; }
@@ -927,11 +927,11 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     auto settle = [&]() -> int {
         for (;;) {
             uint32_t changed = 0;
-            MEM_TRY(m, (sco_scan<false>(c->stream, (const uint32_t *)m->d_ebout.p, (uint32_t *)m->d_ebinc.p, (uint64_t)neb, ScoIdentity(), MemLastValid(), MR_NONE, d_bsum)));
-            MEM_TRY(m, hipMemsetAsync(d_changed, 0, 4, c->stream));
+            HIP_TRY(m, (sco_scan<false>(c->stream, (const uint32_t *)m->d_ebout.p, (uint32_t *)m->d_ebinc.p, (uint64_t)neb, ScoIdentity(), MemLastValid(), MR_NONE, d_bsum)));
+            HIP_TRY(m, hipMemsetAsync(d_changed, 0, 4, c->stream));
             hipLaunchKernelGGL(k_mem_replay, dim3(gb), dim3(64 * MEM_RP_WAVES), 0, c->stream, ra);
-            MEM_TRY(m, hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, c->stream));
-            MEM_TRY(m, hipStreamSynchronize(c->stream));
+            HIP_TRY(m, hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(m, hipStreamSynchronize(c->stream));
             if (!changed) return PGRC_OK;
             m->ctr.replay_rounds++;
         }
@@ -940,17 +940,17 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     // events whose registers are stale, in order: the first one reached is decided on the host, then the replay goes on
     while (nstale) {
         uint32_t x = MR_NONE;
-        MEM_TRY(m, hipMemsetAsync(d_first_stale, 0xFF, 4, c->stream));
+        HIP_TRY(m, hipMemsetAsync(d_first_stale, 0xFF, 4, c->stream));
         hipLaunchKernelGGL(k_mem_first_stale, dim3((uint32_t)std::min<uint64_t>((nev + 255) / 256, 4096)), dim3(256), 0, c->stream,
                            (const uint8_t *)m->d_outc.p, (uint64_t)nev, d_first_stale);
-        MEM_TRY(m, hipMemcpyAsync(&x, d_first_stale, 4, hipMemcpyDeviceToHost, c->stream));
-        MEM_TRY(m, hipStreamSynchronize(c->stream));
+        HIP_TRY(m, hipMemcpyAsync(&x, d_first_stale, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(m, hipStreamSynchronize(c->stream));
         if (x == MR_NONE) break;
         uint64_t key = 0, p = 0;
         uint8_t fl8 = 0;
-        MEM_TRY(m, hipMemcpy(&key, ek + x, 8, hipMemcpyDeviceToHost));
-        MEM_TRY(m, hipMemcpy(&p, ep + x, 8, hipMemcpyDeviceToHost));
-        MEM_TRY(m, hipMemcpy(&fl8, (const uint8_t *)m->d_oflag.p + x, 1, hipMemcpyDeviceToHost));
+        HIP_TRY(m, hipMemcpy(&key, ek + x, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(m, hipMemcpy(&p, ep + x, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(m, hipMemcpy(&fl8, (const uint8_t *)m->d_oflag.p + x, 1, hipMemcpyDeviceToHost));
         StaleWalk sw;
         sw.m = m; sw.dest = dest; sw.N2 = N2; sw.dest_is_src = dest_is_src != 0; sw.rev_compl = rev_compl != 0;
         sw.skip = ra.skip; sw.nmain = nmain; sw.d_ek = ek; sw.d_outc = (const uint8_t *)m->d_outc.p; sw.nev = nev; sw.d_range = d_range;
@@ -972,10 +972,10 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     // ---- 5. the matches, in discovery order
     const auto th0 = std::chrono::steady_clock::now();
     uint32_t *d_slot = (uint32_t *)m->d_first.p;                                       // (the block leaders are not needed any more)
-    MEM_TRY(m, (sco_scan<true>(c->stream, (const uint8_t *)m->d_outc.p, d_slot, (uint64_t)nev, MemIsAccept(), ScoPlus(), 0u, d_bsum)));
+    HIP_TRY(m, (sco_scan<true>(c->stream, (const uint8_t *)m->d_outc.p, d_slot, (uint64_t)nev, MemIsAccept(), ScoPlus(), 0u, d_bsum)));
     uint32_t nmatch = 0;
-    MEM_TRY(m, hipMemcpyAsync(&nmatch, d_slot + (nev - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    MEM_TRY(m, hipStreamSynchronize(c->stream));
+    HIP_TRY(m, hipMemcpyAsync(&nmatch, d_slot + (nev - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(m, hipStreamSynchronize(c->stream));
     if (nmatch) {
         if ((e = pgrc_buf_ensure(c, m->d_match, (size_t)nmatch * sizeof(pgrc_text_match)))) { m->err = c->err; return e; }
         hipLaunchKernelGGL(k_mem_emit, dim3(g), dim3(256), 0, c->stream, ek, ep, (const uint32_t *)m->d_orun.p, (const uint8_t *)m->d_outc.p,

@@ -38,14 +38,5 @@ struct pgrc_mem_ctx {
     bool res_set[3] = {false, false, false};
 };
 
-#define MEM_TRY(m, expr)                                                                     \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            (m)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                   \
-            return pgrc_hip_code(e__);                                                       \
-        }                                                                                    \
-    } while (0)
-
 // pgmap.hip: the mapping's device buffers and events (pgrc_mem_destroy gives them back)
 void pgrc_pgmap_release(pgrc_mem_ctx *m);

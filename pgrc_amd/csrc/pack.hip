@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(256) k_pack_ascii(const uint8_t *__restrict__ 
     }
 }
 
-int pgrc_launch_pack_ascii(pgrc_match_ctx *c, const uint8_t *d_ascii, uint64_t count, uint32_t *d_words,
+int pgrc_launch_pack_ascii(PgrcDev *c, const uint8_t *d_ascii, uint64_t count, uint32_t *d_words,
                            uint32_t *d_errflag) {
     if (count == 0) return PGRC_OK;
     uint64_t nwords = (count + 15) / 16;
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(256) k_revcomp(const uint32_t *__restrict__ fw
     }
 }
 
-int pgrc_launch_revcomp(pgrc_match_ctx *c, const uint32_t *d_fw, uint32_t *d_rc, uint64_t G) {
+int pgrc_launch_revcomp(PgrcDev *c, const uint32_t *d_fw, uint32_t *d_rc, uint64_t G) {
     uint64_t nwords = (G + 15) / 16;
     if (!nwords) return PGRC_OK;
     uint32_t grid = (uint32_t)((nwords + 255) / 256 < 65536 * 4 ? (nwords + 255) / 256 : 65536 * 4);
@@ -111,7 +111,7 @@ k_pack_reads_ascii(const uint8_t *__restrict__ ascii, uint64_t first, uint64_t c
     }
 }
 
-int pgrc_launch_pack_reads_ascii(pgrc_match_ctx *c, const uint8_t *d_ascii, uint64_t first, uint64_t count,
+int pgrc_launch_pack_reads_ascii(PgrcDev *c, const uint8_t *d_ascii, uint64_t first, uint64_t count,
                                  uint32_t L, uint32_t *d_words, uint64_t stride, uint8_t *d_nflag,
                                  uint32_t *d_errflag) {
     if (!count) return PGRC_OK;
@@ -150,7 +150,7 @@ k_repack_reads_ref(const uint8_t *__restrict__ packed, uint64_t first, uint64_t 
     }
 }
 
-int pgrc_launch_repack_reads_ref(pgrc_match_ctx *c, const uint8_t *d_packed, uint64_t first, uint64_t count,
+int pgrc_launch_repack_reads_ref(PgrcDev *c, const uint8_t *d_packed, uint64_t first, uint64_t count,
                                  uint32_t L, uint32_t *d_words, uint64_t stride) {
     if (!count) return PGRC_OK;
     uint32_t nw = (L + 15) / 16, pb = (L + 3) / 4;
@@ -215,7 +215,7 @@ k_unpack_reads_acgnt(const uint8_t *__restrict__ packed, uint64_t first, uint64_
     }
 }
 
-int pgrc_launch_unpack_reads_acgnt(pgrc_match_ctx *c, const uint8_t *d_packed, uint64_t first, uint64_t count, uint32_t L,
+int pgrc_launch_unpack_reads_acgnt(PgrcDev *c, const uint8_t *d_packed, uint64_t first, uint64_t count, uint32_t L,
                                    uint32_t *d_words, uint64_t stride, uint8_t *d_nflag, uint32_t *d_errflag) {
     if (!count) return PGRC_OK;
     const uint32_t nw = (L + 15) / 16, pb = (L + 2) / 3;
@@ -241,7 +241,7 @@ k_nrows_ascii_acgnt(const uint8_t *__restrict__ packed, const uint32_t *__restri
     }
 }
 
-int pgrc_launch_nrows_ascii_acgnt(pgrc_match_ctx *c, const uint8_t *d_packed, const uint32_t *d_local_idx, uint64_t count,
+int pgrc_launch_nrows_ascii_acgnt(PgrcDev *c, const uint8_t *d_packed, const uint32_t *d_local_idx, uint64_t count,
                                   uint32_t L, uint8_t *d_ascii) {
     if (!count) return PGRC_OK;
     const uint64_t total = count * L;
@@ -283,7 +283,7 @@ k_npos_rows(const uint8_t *__restrict__ rows, int symbols, uint64_t first, uint6
     }
 }
 
-int pgrc_launch_npos_rows(pgrc_match_ctx *c, const uint8_t *d_rows, int symbols, uint64_t first, uint64_t count, uint32_t L,
+int pgrc_launch_npos_rows(PgrcDev *c, const uint8_t *d_rows, int symbols, uint64_t first, uint64_t count, uint32_t L,
                           uint8_t *d_nflag, uint32_t *d_npos) {
     if (!count) return PGRC_OK;
     if (L > 255 || !d_npos) { c->err = "npos_rows: a read position must fit one byte (read_len <= 255)"; return PGRC_E_PARAM; }

@@ -90,7 +90,7 @@ static __global__ void __launch_bounds__(PP_TPB) k_po_far(uint64_t nf, const uin
 static int po_fail(pgrc_decode_ctx *d, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, "pair order (encode): " + msg); }
 
 void pgrc_pairorder_release(pgrc_decode_ctx *d) {
-    for (DecBuf *b : {&d->po_in, &d->po_rev, &d->po_ent, &d->po_pair, &d->po_out, &d->po_bsum}) dec_free(*b);
+    for (DevBuf *b : {&d->po_in, &d->po_rev, &d->po_ent, &d->po_pair, &d->po_out, &d->po_bsum}) dec_free(*b);
     for (hipEvent_t &ev : d->po_ev) {
         if (ev) (void)hipEventDestroy(ev);
         ev = nullptr;
@@ -122,14 +122,14 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     const auto t0 = std::chrono::steady_clock::now();
     int e;
     for (hipEvent_t &ev : d->po_ev)
-        if (!ev) DEC_TRY(d, hipEventCreate(&ev));
+        if (!ev) HIP_TRY(d, hipEventCreate(&ev));
     const PoLayout dev = po_layout(form, T, P, P, P, P);         // on the device every stream has room for all pairs
     const uint64_t binc_at = pp_a16(T * 4) + 16, ent_bytes = binc_at + T * 4 + 16;
     const uint64_t file_at = pp_a16(P * 4) + 16, ninc_at = file_at + pp_a16(P) + 16, frel_at = ninc_at + pp_a16(P * 4) + 16, pre_at = frel_at + pp_a16(P * 4) + 16,
                    dinc_at = pre_at + pp_a16(P * 4) + 16, dval_at = dinc_at + pp_a16(P * 4) + 16, map_at = dval_at + pp_a16(P) + 16, pair_bytes = map_at + P + 16;
     const uint64_t sco_bytes = pp_a16(sco_scratch_elems(T) * 4), bsum_bytes = sco_bytes + 32;
-    if ((e = dec_buf(d, d->po_in, T * 4 + 16)) || (e = dec_buf(d, d->po_rev, T * 4 + 16)) || (e = dec_buf(d, d->po_ent, ent_bytes)) ||
-        (e = dec_buf(d, d->po_pair, coded ? pair_bytes : 16)) || (e = dec_buf(d, d->po_out, dev.total)) || (e = dec_buf(d, d->po_bsum, bsum_bytes)))
+    if ((e = pgrc_buf_unpooled(d, d->po_in, T * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->po_rev, T * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->po_ent, ent_bytes)) ||
+        (e = pgrc_buf_unpooled(d, d->po_pair, coded ? pair_bytes : 16)) || (e = pgrc_buf_unpooled(d, d->po_out, dev.total)) || (e = pgrc_buf_unpooled(d, d->po_bsum, bsum_bytes)))
         return e;
     uint32_t *org = (uint32_t *)d->po_in.p, *rev = (uint32_t *)d->po_rev.p;
     uint8_t *en = (uint8_t *)d->po_ent.p, *pr = (uint8_t *)d->po_pair.p, *ob = (uint8_t *)d->po_out.p;
@@ -141,26 +141,26 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
         if (n[l] && (e = dec_upload(d, org + first, org_h[l], n[l] * 4))) return e;
         first += n[l];
     }
-    DEC_TRY(d, hipEventRecord(d->po_ev[0], d->stream));
-    if (T) DEC_TRY(d, hipMemsetAsync(rev, 0xFF, T * 4, d->stream));      // the sentinel: no entry index (T <= 2^32 - 2)
-    DEC_TRY(d, hipMemsetAsync(bad, 0, 16, d->stream));
+    HIP_TRY(d, hipEventRecord(d->po_ev[0], d->stream));
+    if (T) HIP_TRY(d, hipMemsetAsync(rev, 0xFF, T * 4, d->stream));      // the sentinel: no entry index (T <= 2^32 - 2)
+    HIP_TRY(d, hipMemsetAsync(bad, 0, 16, d->stream));
     const float ms_upload = pp_ms(t0);
 
     uint32_t h_bad[2] = {0, 0}, n_base = 0, n_near = 0, n_del = 0;
     if (T) {
         hipLaunchKernelGGL(k_po_scatter, dim3(pp_grid(T)), dim3(PP_TPB), 0, d->stream, (const uint32_t *)org, T, rev, bad);
-        DEC_TRY(d, hipEventRecord(d->po_ev[10], d->stream));
+        HIP_TRY(d, hipEventRecord(d->po_ev[10], d->stream));
         hipLaunchKernelGGL(k_po_class, dim3(pp_grid(T)), dim3(PP_TPB), 0, d->stream, (const uint32_t *)org, T, (const uint32_t *)rev, rel, bad);
-        DEC_TRY(d, hipGetLastError());
+        HIP_TRY(d, hipGetLastError());
     }
-    DEC_TRY(d, hipEventRecord(d->po_ev[1], d->stream));
+    HIP_TRY(d, hipEventRecord(d->po_ev[1], d->stream));
     if (T && coded) {
-        DEC_TRY(d, sco_scan<true>(d->stream, (const uint32_t *)rel, base_inc, T, PoNonZero{}, ScoPlus{}, 0u, sco_tmp));
-        DEC_TRY(d, hipMemcpyAsync(&n_base, base_inc + T - 1, 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, sco_scan<true>(d->stream, (const uint32_t *)rel, base_inc, T, PoNonZero{}, ScoPlus{}, 0u, sco_tmp));
+        HIP_TRY(d, hipMemcpyAsync(&n_base, base_inc + T - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    DEC_TRY(d, hipEventRecord(d->po_ev[2], d->stream));
-    DEC_TRY(d, hipMemcpyAsync(h_bad, bad, 8, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipEventRecord(d->po_ev[2], d->stream));
+    HIP_TRY(d, hipMemcpyAsync(h_bad, bad, 8, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     // nothing below is indexed by a pair number before the input is known to be a permutation
     if (h_bad[0]) return po_fail(d, "an original index of " + std::to_string(T) + " (the entries' count) or more");
     if (h_bad[1]) return po_fail(d, "an original index occurs twice");
@@ -175,36 +175,36 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     uint32_t *full = (uint32_t *)(ob + dev.at[PO_FULL]), *pbo = complete ? (uint32_t *)(ob + dev.at[PO_PBO]) : nullptr;
     uint8_t *off_file = ff ? ob + dev.at[PO_OFFF] : nullptr, *nonoff_file = ff ? ob + dev.at[PO_NONF] : nullptr;
     const bool pairs = coded && P;
-    DEC_TRY(d, hipEventRecord(d->po_ev[8], d->stream));         // (the host's wait above is no device time)
+    HIP_TRY(d, hipEventRecord(d->po_ev[8], d->stream));         // (the host's wait above is no device time)
     if (pairs) hipLaunchKernelGGL(k_po_pairs, dim3(pp_grid(T)), dim3(PP_TPB), 0, d->stream, (const uint32_t *)org, T, (const uint32_t *)rel, (const uint32_t *)base_inc, prel,
                                   off8_flag, pfile, pbo);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->po_ev[3], d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->po_ev[3], d->stream));
     if (pairs) {
-        DEC_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)off8_flag, near_inc, P, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
-        DEC_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)off8_flag, near_inc, P, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
+        HIP_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    DEC_TRY(d, hipEventRecord(d->po_ev[4], d->stream));
+    HIP_TRY(d, hipEventRecord(d->po_ev[4], d->stream));
     if (pairs) hipLaunchKernelGGL(k_po_compact, dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, P, (const uint8_t *)off8_flag, (const uint32_t *)near_inc, (const uint32_t *)prel,
                                   (const uint8_t *)pfile, off_val, off_file, far_rel, nonoff_file);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->po_ev[5], d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->po_ev[5], d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     const uint64_t nf = pairs ? P - n_near : 0;
-    DEC_TRY(d, hipEventRecord(d->po_ev[9], d->stream));
+    HIP_TRY(d, hipEventRecord(d->po_ev[9], d->stream));
     if (nf) {
         hipLaunchKernelGGL((k_pp_enc_maps<int8_t, uint32_t>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rel, map);
-        DEC_TRY(d, sco_scan<false>(d->stream, (const uint8_t *)map, pre, nf, ScoIdentity{}, PpCompose{}, PP_MAP_IDENT, sco_tmp));
+        HIP_TRY(d, sco_scan<false>(d->stream, (const uint8_t *)map, pre, nf, ScoIdentity{}, PpCompose{}, PP_MAP_IDENT, sco_tmp));
         hipLaunchKernelGGL((k_pp_enc_kinds<int8_t, uint32_t>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rel, (const uint32_t *)pre, del_flag, dval);
-        DEC_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)del_flag, del_inc, nf, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
-        DEC_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)del_flag, del_inc, nf, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
+        HIP_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    DEC_TRY(d, hipEventRecord(d->po_ev[6], d->stream));
+    HIP_TRY(d, hipEventRecord(d->po_ev[6], d->stream));
     if (nf) hipLaunchKernelGGL(k_po_far, dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rel, (const uint8_t *)del_flag, (const uint32_t *)del_inc,
                                (const int8_t *)dval, del_val, full);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->po_ev[7], d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->po_ev[7], d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
 
     // the streams, now that their sizes are known: one page-locked block
     const auto t1 = std::chrono::steady_clock::now();

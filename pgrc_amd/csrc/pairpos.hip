@@ -246,25 +246,18 @@ __global__ void __launch_bounds__(PP_TPB) k_pp_enc_far(uint64_t nf, const uint32
 static int pp_fail(pgrc_decode_ctx *d, const char *who, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, std::string(who) + ": " + msg); }
 
 static int pp_prepare(pgrc_decode_ctx *d) {
-    if (!d->pp_mc) {
-        for (hipEvent_t &ev : d->pp_ev)
-            if (!ev) DEC_TRY(d, hipEventCreate(&ev));
-        d->pp_mc = new pgrc_match_ctx();      // never run as a matcher: radix.hip's stream, error string and scratch growth
-        d->pp_mc->device = d->device;
-        d->pp_mc->stream = d->stream;
-    }
+    for (hipEvent_t &ev : d->pp_ev)
+        if (!ev) HIP_TRY(d, hipEventCreate(&ev));
     return PGRC_OK;
 }
 
 void pgrc_pairpos_release(pgrc_decode_ctx *d) {
-    for (DecBuf *b : {&d->pp_in, &d->pp_rec[0], &d->pp_rec[1], &d->pp_val[0], &d->pp_val[1], &d->pp_rank, &d->pp_far, &d->pp_out, &d->pp_bsum}) dec_free(*b);
+    for (DevBuf *b : {&d->pp_in, &d->pp_rec[0], &d->pp_rec[1], &d->pp_val[0], &d->pp_val[1], &d->pp_rank, &d->pp_far, &d->pp_out, &d->pp_bsum}) dec_free(*b);
     pgrc_buf_free(d->pp_sort);
     for (hipEvent_t &ev : d->pp_ev) {
         if (ev) (void)hipEventDestroy(ev);
         ev = nullptr;
     }
-    delete d->pp_mc;
-    d->pp_mc = nullptr;
 }
 
 // the rank order of the P records in pp_rec[0] (pp_val[0]): stable by the position bits in use
@@ -273,10 +266,10 @@ static int pp_sort(pgrc_decode_ctx *d, bool w8, uint64_t P, uint64_t base_or, co
     while (hb < 64 && (base_or >> hb)) hb++;
     uint64_t *sorted = nullptr, *vsorted = nullptr;
     int e;
-    if (w8) e = pgrc_radix_sort_pairs_u64(d->pp_mc, (uint64_t *)d->pp_rec[0].p, (uint64_t *)d->pp_rec[1].p, (uint64_t *)d->pp_val[0].p, (uint64_t *)d->pp_val[1].p, P, 0, hb,
+    if (w8) e = pgrc_radix_sort_pairs_u64(d, (uint64_t *)d->pp_rec[0].p, (uint64_t *)d->pp_rec[1].p, (uint64_t *)d->pp_val[0].p, (uint64_t *)d->pp_val[1].p, P, 0, hb,
                                           d->pp_sort, &sorted, &vsorted);
-    else e = pgrc_radix_sort_u64(d->pp_mc, (uint64_t *)d->pp_rec[0].p, (uint64_t *)d->pp_rec[1].p, P, 32, 32 + std::min(hb, 32u), d->pp_sort, &sorted);
-    if (e) return dec_fail(d, e, "pair positions: " + d->pp_mc->err);
+    else e = pgrc_radix_sort_u64(d, (uint64_t *)d->pp_rec[0].p, (uint64_t *)d->pp_rec[1].p, P, 32, 32 + std::min(hb, 32u), d->pp_sort, &sorted);
+    if (e) return dec_fail(d, e, "pair positions: " + d->err);
     *a = sorted;
     *b = vsorted;
     return PGRC_OK;
@@ -285,28 +278,24 @@ static int pp_sort(pgrc_decode_ctx *d, bool w8, uint64_t P, uint64_t base_or, co
 static int pp_sort_buffers(pgrc_decode_ctx *d, bool w8, uint64_t P) {
     int e;
     for (int k = 0; k < 2; k++) {
-        if ((e = dec_buf(d, d->pp_rec[k], P * 8))) return e;
-        if (w8 && (e = dec_buf(d, d->pp_val[k], P * 8))) return e;
+        if ((e = pgrc_buf_unpooled(d, d->pp_rec[k], P * 8))) return e;
+        if (w8 && (e = pgrc_buf_unpooled(d, d->pp_val[k], P * 8))) return e;
     }
     return PGRC_OK;
 }
 
 // device -> host on the context's stream: page-locked memory directly, other memory through the staging buffers
 static int pp_download(pgrc_decode_ctx *d, void *h_dst, const void *d_src, uint64_t bytes) {
-    hipPointerAttribute_t attr;
-    bool direct = false;
-    if (hipPointerGetAttributes(&attr, h_dst) == hipSuccess) direct = attr.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();
-    if (direct) {
-        if (bytes) DEC_TRY(d, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
+    if (pgrc_host_pinned(h_dst)) {
+        if (bytes) HIP_TRY(d, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
         return PGRC_OK;
     }
-    DEC_TRY(d, hipStreamSynchronize(d->stream));       // (uploads through the staging buffers have landed)
+    HIP_TRY(d, hipStreamSynchronize(d->stream));       // (uploads through the staging buffers have landed)
     for (uint64_t o = 0; o < bytes; o += DEC_STAGE_BYTES) {
         const uint64_t c = std::min<uint64_t>(DEC_STAGE_BYTES, bytes - o);
-        DEC_TRY(d, hipMemcpyAsync(d->stage[0], (const uint8_t *)d_src + o, c, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(d, hipMemcpyAsync(d->stage[0], (const uint8_t *)d_src + o, c, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
         memcpy((uint8_t *)h_dst + o, d->stage[0], c);
     }
     return PGRC_OK;
@@ -331,7 +320,7 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
     }
     const uint64_t near_at = 0, kind_at = near_at + pp_a16(P * 4) + 16, val_at = kind_at + pp_a16(P) + 16, rank_bytes = val_at + P * 8 + 16;
     const uint64_t bsum_bytes = pp_a16(sco_scratch_elems(std::max(P, nf)) * sizeof(PpSeg)) + 2 * PP_OR_BLOCKS * 8 + 64;     // (the flag scans' u32 folds too)
-    if ((e = dec_buf(d, d->pp_in, in_bytes)) || (e = dec_buf(d, d->pp_rank, rank_bytes)) || (e = dec_buf(d, d->pp_far, nf * 4 + 16)) || (e = dec_buf(d, d->pp_bsum, bsum_bytes)))
+    if ((e = pgrc_buf_unpooled(d, d->pp_in, in_bytes)) || (e = pgrc_buf_unpooled(d, d->pp_rank, rank_bytes)) || (e = pgrc_buf_unpooled(d, d->pp_far, nf * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->pp_bsum, bsum_bytes)))
         return e;
     uint8_t *in = (uint8_t *)d->pp_in.p;
     for (int k = 0; k < 8; k++)
@@ -353,25 +342,25 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
     uint64_t *bor = (uint64_t *)((uint8_t *)d->pp_bsum.p + bsum_bytes - 2 * PP_OR_BLOCKS * 8 - 32);     // block ORs, then the two results
     uint32_t *sco_tmp = (uint32_t *)d->pp_bsum.p;
 
-    DEC_TRY(d, hipEventRecord(d->pp_ev[0], d->stream));
+    HIP_TRY(d, hipEventRecord(d->pp_ev[0], d->stream));
     const uint32_t nor = (uint32_t)std::min<uint64_t>(pp_grid(P), PP_OR_BLOCKS);
     if (W8) hipLaunchKernelGGL((k_pp_records<true, PpBaseStream<uint64_t>>), dim3(nor), dim3(PP_TPB), 0, d->stream, PpBaseStream<uint64_t>{(const uint64_t *)(in + at[0])}, P,
                                (uint64_t *)d->pp_rec[0].p, (uint64_t *)d->pp_val[0].p, bor);
     else hipLaunchKernelGGL((k_pp_records<false, PpBaseStream<uint32_t>>), dim3(nor), dim3(PP_TPB), 0, d->stream, PpBaseStream<uint32_t>{(const uint32_t *)(in + at[0])}, P,
                             (uint64_t *)d->pp_rec[0].p, (uint64_t *)nullptr, bor);
     hipLaunchKernelGGL(k_pp_or_final, dim3(1), dim3(64), 0, d->stream, (const uint64_t *)bor, nor, bor + 2 * PP_OR_BLOCKS);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->pp_ev[1], d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->pp_ev[1], d->stream));
     // the flags' counts, held against the stream sizes before anything is indexed by them
-    DEC_TRY(d, sco_scan<true>(d->stream, ds.off16_flag, near_inc, P, PpIsOne{}, ScoPlus{}, 0u, sco_tmp));
-    DEC_TRY(d, sco_scan<true>(d->stream, ds.del_flag, del_inc, nf, PpNonZero{}, ScoPlus{}, 0u, sco_tmp));
-    DEC_TRY(d, hipEventRecord(d->pp_ev[2], d->stream));
+    HIP_TRY(d, sco_scan<true>(d->stream, ds.off16_flag, near_inc, P, PpIsOne{}, ScoPlus{}, 0u, sco_tmp));
+    HIP_TRY(d, sco_scan<true>(d->stream, ds.del_flag, del_inc, nf, PpNonZero{}, ScoPlus{}, 0u, sco_tmp));
+    HIP_TRY(d, hipEventRecord(d->pp_ev[2], d->stream));
     uint64_t ors[2] = {0, 0};
     uint32_t n_near = 0, n_del = 0;
-    DEC_TRY(d, hipMemcpyAsync(ors, bor + 2 * PP_OR_BLOCKS, 16, hipMemcpyDeviceToHost, d->stream));
-    if (P) DEC_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
-    if (nf) DEC_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipMemcpyAsync(ors, bor + 2 * PP_OR_BLOCKS, 16, hipMemcpyDeviceToHost, d->stream));
+    if (P) HIP_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
+    if (nf) HIP_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     if (n_near != s->n_off16) return pp_fail(d, who, "off16_flag holds " + std::to_string(n_near) + " ones, n_off16 is " + std::to_string(s->n_off16));
     if (P - n_near != nf) return pp_fail(d, who, "off16_flag holds " + std::to_string(P - n_near) + " far pairs, n_delta_flag is " + std::to_string(nf));
     if (n_del != s->n_delta16) return pp_fail(d, who, "delta16_flag holds " + std::to_string(n_del) + " delta pairs, n_delta16 is " + std::to_string(s->n_delta16));
@@ -379,14 +368,14 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
 
     const uint64_t *a = nullptr, *b = nullptr;
     if ((e = pp_sort(d, W8, P, ors[0], &a, &b))) return e;
-    DEC_TRY(d, hipEventRecord(d->pp_ev[3], d->stream));
+    HIP_TRY(d, hipEventRecord(d->pp_ev[3], d->stream));
     if (P) hipLaunchKernelGGL((k_pp_dec_ops<W8>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, a, b, P, ds, d_out, kind, val);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->pp_ev[4], d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->pp_ev[4], d->stream));
     // refPrev at every ranked pair; the scan's last pass puts the delta pairs' mates in their places
-    DEC_TRY(d, (sco_device_scan<true, false>(d->stream, PpChainIn{kind, val}, P, PpSegOp{}, PpSeg{0, 0u}, PpSeg{0, 0u}, PpDeltaSink<W8>{a, b, kind, P, d_out}, (PpSeg *)d->pp_bsum.p)));
-    DEC_TRY(d, hipEventRecord(d->pp_ev[5], d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, (sco_device_scan<true, false>(d->stream, PpChainIn{kind, val}, P, PpSegOp{}, PpSeg{0, 0u}, PpSeg{0, 0u}, PpDeltaSink<W8>{a, b, kind, P, d_out}, (PpSeg *)d->pp_bsum.p)));
+    HIP_TRY(d, hipEventRecord(d->pp_ev[5], d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     pgrc_pairpos_timing &t = d->ptm;
     t = pgrc_pairpos_timing{};
     t.struct_size = sizeof(pgrc_pairpos_timing);
@@ -453,8 +442,8 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, uint64_t T, 
     const uint64_t frank_at = pp_a16(P * 8) + 16, pre_at = frank_at + pp_a16(P * 4) + 16, dinc_at = pre_at + pp_a16(P * 4) + 16,
                    dval_at = dinc_at + pp_a16(P * 4) + 16, map_at = dval_at + pp_a16(P * 2) + 16, far_bytes = map_at + P + 16;
     const uint64_t bsum_bytes = pp_a16(sco_scratch_elems(P) * 4) + 2 * PP_OR_BLOCKS * 8 + 64;
-    if ((e = dec_buf(d, d->pp_in, T * 8 + 16)) || (e = dec_buf(d, d->pp_rank, rank_bytes)) || (e = dec_buf(d, d->pp_far, far_bytes)) ||
-        (e = dec_buf(d, d->pp_out, dev.total)) || (e = dec_buf(d, d->pp_bsum, bsum_bytes)))
+    if ((e = pgrc_buf_unpooled(d, d->pp_in, T * 8 + 16)) || (e = pgrc_buf_unpooled(d, d->pp_rank, rank_bytes)) || (e = pgrc_buf_unpooled(d, d->pp_far, far_bytes)) ||
+        (e = pgrc_buf_unpooled(d, d->pp_out, dev.total)) || (e = pgrc_buf_unpooled(d, d->pp_bsum, bsum_bytes)))
         return e;
     if (T && (e = dec_upload(d, d->pp_in.p, org_h, T * 8))) return e;
     const float ms_upload = pp_ms(t0);
@@ -474,49 +463,49 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, uint64_t T, 
     uint64_t *bor = (uint64_t *)((uint8_t *)d->pp_bsum.p + bsum_bytes - 2 * PP_OR_BLOCKS * 8 - 32);
     uint32_t *sco_tmp = (uint32_t *)d->pp_bsum.p;
 
-    DEC_TRY(d, hipEventRecord(d->pp_ev[0], d->stream));
+    HIP_TRY(d, hipEventRecord(d->pp_ev[0], d->stream));
     const uint32_t nor = (uint32_t)std::min<uint64_t>(pp_grid(P), PP_OR_BLOCKS);
     hipLaunchKernelGGL((k_pp_records<W8, PpBaseOrg>), dim3(nor), dim3(PP_TPB), 0, d->stream, PpBaseOrg{org}, P, (uint64_t *)d->pp_rec[0].p,
                        (uint64_t *)(W8 ? d->pp_val[0].p : nullptr), bor);
     hipLaunchKernelGGL(k_pp_or_final, dim3(1), dim3(64), 0, d->stream, (const uint64_t *)bor, nor, bor + 2 * PP_OR_BLOCKS);
-    DEC_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
     uint64_t ors[2] = {0, 0};
-    DEC_TRY(d, hipMemcpyAsync(ors, bor + 2 * PP_OR_BLOCKS, 16, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipMemcpyAsync(ors, bor + 2 * PP_OR_BLOCKS, 16, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     if (!W8 && (ors[1] >> 32)) return pp_fail(d, who, "a position of 2^32 or more with pos_width 4");
     const uint64_t *a = nullptr, *b = nullptr;
     if ((e = pp_sort(d, W8, P, ors[0], &a, &b))) return e;
-    DEC_TRY(d, hipEventRecord(d->pp_ev[1], d->stream));
+    HIP_TRY(d, hipEventRecord(d->pp_ev[1], d->stream));
     uint32_t n_near = 0, n_del = 0;
     if (P) {
         hipLaunchKernelGGL((k_pp_enc_class<W8>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, a, b, org, P, off16_flag, rel, bf);
-        DEC_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)off16_flag, near_inc, P, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
-        DEC_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)off16_flag, near_inc, P, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
+        HIP_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    DEC_TRY(d, hipEventRecord(d->pp_ev[2], d->stream));
+    HIP_TRY(d, hipEventRecord(d->pp_ev[2], d->stream));
     if (P) {
         if (W8) hipLaunchKernelGGL((k_pp_enc_base<uint64_t>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, org, P, (uint64_t *)(ob + dev.at[0]));
         else hipLaunchKernelGGL((k_pp_enc_base<uint32_t>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, org, P, (uint32_t *)(ob + dev.at[0]));
         hipLaunchKernelGGL(k_pp_enc_compact, dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, P, (const uint8_t *)off16_flag, (const uint32_t *)near_inc, (const uint64_t *)rel,
                            (const uint8_t *)bf, off_bf, off_val, far_rel, far_rank);
     }
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->pp_ev[3], d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->pp_ev[3], d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     const uint64_t nf = P - n_near;
     if (nf) {
         hipLaunchKernelGGL((k_pp_enc_maps<int16_t, uint64_t>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint64_t *)far_rel, map);
-        DEC_TRY(d, sco_scan<false>(d->stream, (const uint8_t *)map, pre, nf, ScoIdentity{}, PpCompose{}, PP_MAP_IDENT, sco_tmp));
+        HIP_TRY(d, sco_scan<false>(d->stream, (const uint8_t *)map, pre, nf, ScoIdentity{}, PpCompose{}, PP_MAP_IDENT, sco_tmp));
         hipLaunchKernelGGL((k_pp_enc_kinds<int16_t, uint64_t>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint64_t *)far_rel, (const uint32_t *)pre, del_flag, dval);
-        DEC_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)del_flag, del_inc, nf, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
-        DEC_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)del_flag, del_inc, nf, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
+        HIP_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    DEC_TRY(d, hipEventRecord(d->pp_ev[4], d->stream));
+    HIP_TRY(d, hipEventRecord(d->pp_ev[4], d->stream));
     if (nf) hipLaunchKernelGGL((k_pp_enc_far<W8>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rank, (const uint64_t *)far_rel,
                                (const uint8_t *)del_flag, (const uint32_t *)del_inc, (const int16_t *)dval, (const uint8_t *)bf, a, b, del_bf, del_val, not_base);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->pp_ev[5], d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->pp_ev[5], d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
 
     // the streams, now that their sizes are known: one page-locked block
     const auto t1 = std::chrono::steady_clock::now();
@@ -603,7 +592,7 @@ int pgrc_pairpos_decode(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint6
     const auto t0 = std::chrono::steady_clock::now();
     int e;
     if ((e = pgrc_pairpos_check_streams(d, s))) return e;
-    if ((e = dec_buf(d, d->pp_out, s->n_total * 8 + 16))) return e;
+    if ((e = pgrc_buf_unpooled(d, d->pp_out, s->n_total * 8 + 16))) return e;
     if ((e = pgrc_pairpos_decode_device(d, s, (uint64_t *)d->pp_out.p))) return e;
     const auto t1 = std::chrono::steady_clock::now();
     if ((e = pp_download(d, pg_pos, d->pp_out.p, s->n_total * 8))) return e;

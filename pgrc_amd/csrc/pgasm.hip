@@ -35,8 +35,7 @@ enum { AS_CNT_CYCLES, AS_CNT_LOST, AS_CNT_COMPONENTS, AS_CNT_SINGLES, AS_CNT_WOR
 
 struct pgrc_asm_ctx {
     pgrc_decode_ctx *d = nullptr;       // the stream, the staging buffers, the error string and the text (text, text_len, have_text)
-    pgrc_match_ctx *mc = nullptr;       // never run as a matcher: pack.hip's stream and error string (made on first use)
-    DecBuf rows, nx, ovraw, ov, pred, st, len, walk, sh, off, org, start, map, fold, words, packed;
+    DevBuf rows, nx, ovraw, ov, pred, st, len, walk, sh, off, org, start, map, fold, words, packed;
     hipEvent_t ev[7]{};
     uint32_t symbols = 0;
     bool have_packed = false, have_timing = false;
@@ -266,22 +265,6 @@ static __global__ void __launch_bounds__(AS_TPB) k_as_text(const uint8_t *__rest
 // ------------------------------------------------------------------------------------------------ host side
 static int as_fail(pgrc_asm_ctx *a, const std::string &msg) { return dec_fail(a->d, PGRC_E_PARAM, "assemble: " + msg); }
 
-static bool as_pinned(const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) == hipSuccess) return attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return false;
-}
-
-static int as_upload(pgrc_decode_ctx *d, void *dst, const void *src, uint64_t bytes) {
-    if (!bytes) return PGRC_OK;
-    if (as_pinned(src)) {
-        DEC_TRY(d, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d->stream));
-        return PGRC_OK;
-    }
-    return dec_upload(d, dst, src, bytes);
-}
-
 // jumping passes until one reports no live pointer, `cap` at the most; *live_out: the last pass's report
 static int as_jump(pgrc_asm_ctx *a, bool rank, uint64_t R, uint32_t cap, uint32_t *passes, uint32_t *live_out) {
     pgrc_decode_ctx *d = a->d;
@@ -293,9 +276,9 @@ static int as_jump(pgrc_asm_ctx *a, bool rank, uint64_t R, uint32_t cap, uint32_
         if ((e = dec_clear_err(d))) return e;
         if (rank) hipLaunchKernelGGL(k_as_rank_jump, dim3(as_grid(R + 1)), dim3(AS_TPB), 0, d->stream, st, R, flag);
         else hipLaunchKernelGGL(k_as_cyc_jump, dim3(as_grid(R + 1)), dim3(AS_TPB), 0, d->stream, st, R, flag);
-        DEC_TRY(d, hipGetLastError());
-        DEC_TRY(d, hipMemcpyAsync(&more, flag, 4, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(d, hipGetLastError());
+        HIP_TRY(d, hipMemcpyAsync(&more, flag, 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
         ++*passes;
     }
     *live_out = more;
@@ -311,13 +294,13 @@ static int as_stage(pgrc_asm_ctx *a, const pgrc_asm_input *in, bool on_device) {
     const uint32_t rb = in->symbols == 4 ? (L + 3) / 4 : (L + 2) / 3;
     int e;
     if (on_device) {
-        DEC_TRY(d, hipMemcpyAsync(a->rows.p, in->packed_rows, R * rb, hipMemcpyDeviceToDevice, d->stream));
-        DEC_TRY(d, hipMemcpyAsync(a->nx.p, in->next_read, N1 * 4, hipMemcpyDeviceToDevice, d->stream));
-        DEC_TRY(d, hipMemcpyAsync(a->ovraw.p, in->overlap, N1 * width, hipMemcpyDeviceToDevice, d->stream));
-    } else if ((e = as_upload(d, a->rows.p, in->packed_rows, R * rb)) || (e = as_upload(d, a->nx.p, in->next_read, N1 * 4)) ||
-               (e = as_upload(d, a->ovraw.p, in->overlap, N1 * width)))
+        HIP_TRY(d, hipMemcpyAsync(a->rows.p, in->packed_rows, R * rb, hipMemcpyDeviceToDevice, d->stream));
+        HIP_TRY(d, hipMemcpyAsync(a->nx.p, in->next_read, N1 * 4, hipMemcpyDeviceToDevice, d->stream));
+        HIP_TRY(d, hipMemcpyAsync(a->ovraw.p, in->overlap, N1 * width, hipMemcpyDeviceToDevice, d->stream));
+    } else if ((e = dec_upload_host(d, a->rows.p, in->packed_rows, R * rb)) || (e = dec_upload_host(d, a->nx.p, in->next_read, N1 * 4)) ||
+               (e = dec_upload_host(d, a->ovraw.p, in->overlap, N1 * width)))
         return e;
-    if (in->index_mapping && (e = as_upload(d, a->map.p, in->index_mapping, R * 4))) return e;
+    if (in->index_mapping && (e = dec_upload_host(d, a->map.p, in->index_mapping, R * 4))) return e;
     return PGRC_OK;
 }
 
@@ -329,13 +312,13 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     const uint32_t rb = symbols == 4 ? (L + 3) / 4 : (L + 2) / 3;
     int e;
     for (hipEvent_t &ev : a->ev)
-        if (!ev) DEC_TRY(d, hipEventCreate(&ev));
+        if (!ev) HIP_TRY(d, hipEventCreate(&ev));
     const uint64_t fold_bytes = as_a16(sco_scratch_elems(N1) * 8);
-    if ((e = dec_buf(d, a->rows, R * rb + 16)) || (e = dec_buf(d, a->nx, N1 * 4)) || (e = dec_buf(d, a->ovraw, N1 * width)) || (e = dec_buf(d, a->ov, N1 * 2)) ||
-        (e = dec_buf(d, a->pred, N1 * 4)) || (e = dec_buf(d, a->st, N1 * 8)) || (e = dec_buf(d, a->len, N1 * 4)) || (e = dec_buf(d, a->walk, R * 4)) ||
-        (e = dec_buf(d, a->sh, R * 2)) || (e = dec_buf(d, a->off, R * 2)) || (e = dec_buf(d, a->org, R * 4)) || (e = dec_buf(d, a->start, N1 * 8)) ||
-        (e = dec_buf(d, a->map, in->index_mapping ? R * 4 : 16)) || (e = dec_buf(d, a->fold, fold_bytes)) ||
-        (e = dec_buf(d, a->words, AS_BAD_WORDS * 4 + AS_CNT_WORDS * 8 + 16)))
+    if ((e = pgrc_buf_unpooled(d, a->rows, R * rb + 16)) || (e = pgrc_buf_unpooled(d, a->nx, N1 * 4)) || (e = pgrc_buf_unpooled(d, a->ovraw, N1 * width)) || (e = pgrc_buf_unpooled(d, a->ov, N1 * 2)) ||
+        (e = pgrc_buf_unpooled(d, a->pred, N1 * 4)) || (e = pgrc_buf_unpooled(d, a->st, N1 * 8)) || (e = pgrc_buf_unpooled(d, a->len, N1 * 4)) || (e = pgrc_buf_unpooled(d, a->walk, R * 4)) ||
+        (e = pgrc_buf_unpooled(d, a->sh, R * 2)) || (e = pgrc_buf_unpooled(d, a->off, R * 2)) || (e = pgrc_buf_unpooled(d, a->org, R * 4)) || (e = pgrc_buf_unpooled(d, a->start, N1 * 8)) ||
+        (e = pgrc_buf_unpooled(d, a->map, in->index_mapping ? R * 4 : 16)) || (e = pgrc_buf_unpooled(d, a->fold, fold_bytes)) ||
+        (e = pgrc_buf_unpooled(d, a->words, AS_BAD_WORDS * 4 + AS_CNT_WORDS * 8 + 16)))
         return e;
     const uint8_t *rows = (const uint8_t *)a->rows.p;
     uint32_t *nx = (uint32_t *)a->nx.p, *pred = (uint32_t *)a->pred.p, *len = (uint32_t *)a->len.p, *walk = (uint32_t *)a->walk.p, *org = (uint32_t *)a->org.p;
@@ -346,26 +329,26 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     uint32_t *bad = (uint32_t *)((uint8_t *)a->words.p + AS_CNT_WORDS * 8);
 
     if ((e = as_stage(a, in, on_device))) return e;
-    DEC_TRY(d, hipMemsetAsync(nx, 0, 4, d->stream));            // element 0 is ignored: no successor
-    DEC_TRY(d, hipMemsetAsync(pred, 0, N1 * 4, d->stream));
-    DEC_TRY(d, hipMemsetAsync(len, 0, N1 * 4, d->stream));
-    DEC_TRY(d, hipMemsetAsync(a->words.p, 0, AS_BAD_WORDS * 4 + AS_CNT_WORDS * 8, d->stream));
+    HIP_TRY(d, hipMemsetAsync(nx, 0, 4, d->stream));            // element 0 is ignored: no successor
+    HIP_TRY(d, hipMemsetAsync(pred, 0, N1 * 4, d->stream));
+    HIP_TRY(d, hipMemsetAsync(len, 0, N1 * 4, d->stream));
+    HIP_TRY(d, hipMemsetAsync(a->words.p, 0, AS_BAD_WORDS * 4 + AS_CNT_WORDS * 8, d->stream));
     const float ms_upload = as_ms(t0);
     const uint32_t grid = as_grid(N1);
 
     // pred and the checks
-    DEC_TRY(d, hipEventRecord(a->ev[0], d->stream));
+    HIP_TRY(d, hipEventRecord(a->ev[0], d->stream));
     hipLaunchKernelGGL(k_as_pred, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint32_t *)nx, (const void *)a->ovraw.p, width, R, L, pred, ov, bad);
     hipLaunchKernelGGL(k_as_link, dim3(grid), dim3(AS_TPB), 0, d->stream, rows, rb, symbols, L, (const uint32_t *)nx, (const uint16_t *)ov, (const uint32_t *)pred, R, bad);
     if (symbols == 5) {
         const uint64_t total = R * rb;
         hipLaunchKernelGGL(k_as_rows5, dim3((uint32_t)std::min<uint64_t>(as_grid(total), 1u << 20)), dim3(AS_TPB), 0, d->stream, rows, total, rb, L, bad);
     }
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(a->ev[1], d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(a->ev[1], d->stream));
     uint32_t h_bad[AS_BAD_WORDS] = {};
-    DEC_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     // nothing below follows a pointer before the graph is known to be paths and cycles over 1 .. R
     if (h_bad[AS_BAD_NEXT]) return as_fail(a, "a successor above the reads' count " + std::to_string(R));
     if (h_bad[AS_BAD_PRED]) return as_fail(a, "a read has two predecessors");
@@ -378,41 +361,41 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     uint32_t bits = 0;
     while (bits < 33 && (1ull << bits) < N1) bits++;            // ceil(log2(R + 1))
     uint32_t passes_cyc = 0, passes_rank = 0, live = 0;
-    DEC_TRY(d, hipEventRecord(a->ev[2], d->stream));
+    HIP_TRY(d, hipEventRecord(a->ev[2], d->stream));
     hipLaunchKernelGGL(k_as_cyc_init, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint32_t *)nx, R, st);
     if ((e = as_jump(a, false, R, bits + 1, &passes_cyc, &live))) return e;
     if (live) hipLaunchKernelGGL(k_as_cut, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint64_t *)st, R, nx, ov, pred, cnt);
-    DEC_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
 
     // ranking
-    DEC_TRY(d, hipEventRecord(a->ev[3], d->stream));
+    HIP_TRY(d, hipEventRecord(a->ev[3], d->stream));
     hipLaunchKernelGGL(k_as_rank_init, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint32_t *)pred, R, st);
     if ((e = as_jump(a, true, R, bits + 3, &passes_rank, &live))) return e;
     if (live) return dec_fail(d, PGRC_E_DEVICE, "assemble: the chains did not resolve in " + std::to_string(passes_rank) + " passes");
 
     // lists
-    DEC_TRY(d, hipEventRecord(a->ev[4], d->stream));
+    HIP_TRY(d, hipEventRecord(a->ev[4], d->stream));
     hipLaunchKernelGGL(k_as_tails, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint64_t *)st, (const uint32_t *)nx, R, len, cnt);
-    DEC_TRY(d, sco_scan<false>(d->stream, (const uint32_t *)len, len, N1, ScoIdentity{}, ScoPlus{}, 0u, (uint32_t *)a->fold.p));
+    HIP_TRY(d, sco_scan<false>(d->stream, (const uint32_t *)len, len, N1, ScoIdentity{}, ScoPlus{}, 0u, (uint32_t *)a->fold.p));
     hipLaunchKernelGGL(k_as_place, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint64_t *)st, (const uint32_t *)len, (const uint16_t *)ov, map, R, L, walk, sh, off, org);
-    DEC_TRY(d, sco_sum_u64<false>(d->stream, (const uint16_t *)sh, R, start, (uint64_t *)a->fold.p));
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(a->ev[5], d->stream));
+    HIP_TRY(d, sco_sum_u64<false>(d->stream, (const uint16_t *)sh, R, start, (uint64_t *)a->fold.p));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(a->ev[5], d->stream));
     uint64_t pg_len = 0;
     unsigned long long h_cnt[AS_CNT_WORDS] = {};
-    DEC_TRY(d, hipMemcpyAsync(&pg_len, start + R, 8, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipMemcpyAsync(&pg_len, start + R, 8, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     if (pg_len < L || pg_len > R * L) return dec_fail(d, PGRC_E_DEVICE, "assemble: a text of " + std::to_string(pg_len) + " symbols");
 
     // text: whole tiles, then the zero bytes the row kernels of a decode context expect after a text
     const uint64_t tiles = (pg_len + AS_TILE - 1) / AS_TILE;
-    if ((e = dec_buf(d, d->text, tiles * AS_TILE + DEC_TEXT_PAD))) return e;
-    DEC_TRY(d, hipMemsetAsync((uint8_t *)d->text.p + tiles * AS_TILE, 0, DEC_TEXT_PAD, d->stream));
+    if ((e = pgrc_buf_unpooled(d, d->text, tiles * AS_TILE + DEC_TEXT_PAD))) return e;
+    HIP_TRY(d, hipMemsetAsync((uint8_t *)d->text.p + tiles * AS_TILE, 0, DEC_TEXT_PAD, d->stream));
     hipLaunchKernelGGL(k_as_text, dim3((uint32_t)tiles), dim3(AS_TPB), 0, d->stream, rows, rb, symbols, (const uint32_t *)walk, (const uint16_t *)sh,
                        (const uint64_t *)start, R, pg_len, (uint8_t *)d->text.p);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(a->ev[6], d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(a->ev[6], d->stream));
 
     // the reads list: one page-locked block, copied down while the text is made
     const auto t1 = std::chrono::steady_clock::now();
@@ -514,13 +497,12 @@ void pgrc_asm_destroy(pgrc_asm_ctx *a) {
     {
         PgrcDeviceScope scope(a->d->device);
         (void)hipStreamSynchronize(a->d->stream);
-        for (DecBuf *b : {&a->rows, &a->nx, &a->ovraw, &a->ov, &a->pred, &a->st, &a->len, &a->walk, &a->sh, &a->off, &a->org, &a->start, &a->map, &a->fold, &a->words,
+        for (DevBuf *b : {&a->rows, &a->nx, &a->ovraw, &a->ov, &a->pred, &a->st, &a->len, &a->walk, &a->sh, &a->off, &a->org, &a->start, &a->map, &a->fold, &a->words,
                            &a->packed})
             dec_free(*b);
         for (hipEvent_t ev : a->ev)
             if (ev) (void)hipEventDestroy(ev);
     }
-    delete a->mc;
     pgrc_decode_destroy(a->d);
     delete a;
 }
@@ -558,21 +540,16 @@ int pgrc_asm_packed_device(pgrc_asm_ctx *a, const void **d_words) {
     if (a->symbols != 4) return as_fail(a, "the 2-bit text exists over ACGT only");
     PGRC_ON_DEVICE(d);
     if (!a->have_packed) {
-        if (!a->mc) {
-            a->mc = new pgrc_match_ctx();
-            a->mc->device = d->device;
-            a->mc->stream = d->stream;
-        }
         const uint64_t nwords = (d->text_len + 15) / 16;
         int e;
-        if ((e = dec_buf(d, a->packed, nwords * 4 + 64))) return e;
+        if ((e = pgrc_buf_unpooled(d, a->packed, nwords * 4 + 64))) return e;
         if ((e = dec_clear_err(d))) return e;
-        DEC_TRY(d, hipMemsetAsync((uint32_t *)a->packed.p + nwords, 0, 64, d->stream));
-        if ((e = pgrc_launch_pack_ascii(a->mc, (const uint8_t *)d->text.p, d->text_len, (uint32_t *)a->packed.p, (uint32_t *)d->flag.p)))
-            return dec_fail(d, e, "assemble: " + a->mc->err);
+        HIP_TRY(d, hipMemsetAsync((uint32_t *)a->packed.p + nwords, 0, 64, d->stream));
+        if ((e = pgrc_launch_pack_ascii(d, (const uint8_t *)d->text.p, d->text_len, (uint32_t *)a->packed.p, (uint32_t *)d->flag.p)))
+            return dec_fail(d, e, "assemble: " + d->err);
         uint32_t symerr = 0;
-        DEC_TRY(d, hipMemcpyAsync(&symerr, d->flag.p, 4, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(d, hipMemcpyAsync(&symerr, d->flag.p, 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
         if (symerr) return dec_fail(d, PGRC_E_DEVICE, "assemble: the text holds a byte outside ACGT");
         a->have_packed = true;
     }

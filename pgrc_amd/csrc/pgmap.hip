@@ -376,7 +376,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
     PgrcDeviceScope dev_scope__(c->device);
     if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     if (!m->have_pm_ev) {
-        for (auto &x : m->pm_ev) MEM_TRY(m, hipEventCreate(&x));
+        for (auto &x : m->pm_ev) HIP_TRY(m, hipEventCreate(&x));
         m->have_pm_ev = true;
     }
     hipEvent_t *ev = m->pm_ev;
@@ -392,7 +392,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
     if (e) return e;
     uint64_t *fold64 = (uint64_t *)m->pm_fold.p;
     uint32_t *fold32 = (uint32_t *)m->pm_fold.p;
-    MEM_TRY(m, hipEventRecord(ev[0], st));
+    HIP_TRY(m, hipEventRecord(ev[0], st));
 
     // ---- 1. normalise, sort by (dst, src, len), unique
     uint64_t nu = 0, nuniq = 0;
@@ -405,8 +405,8 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
         if (e) return e;
         uint64_t *f_dst = (uint64_t *)m->pm_f[0].p, *f_src = (uint64_t *)m->pm_f[1].p, *f_len = (uint64_t *)m->pm_f[2].p;
         uint32_t *d_bad = (uint32_t *)m->pm_small.p;
-        MEM_TRY(m, hipMemsetAsync(d_bad, 0, 4, st));
-        MEM_TRY(m, hipMemcpyAsync(m->pm_in.p, matches, n * sizeof(pgrc_text_match), hipMemcpyHostToDevice, st));
+        HIP_TRY(m, hipMemsetAsync(d_bad, 0, 4, st));
+        HIP_TRY(m, hipMemcpyAsync(m->pm_in.p, matches, n * sizeof(pgrc_text_match), hipMemcpyHostToDevice, st));
         uint64_t *kcur = (uint64_t *)m->pm_key[0].p, *kalt = (uint64_t *)m->pm_key[1].p, *icur = (uint64_t *)m->pm_idx[0].p, *ialt = (uint64_t *)m->pm_idx[1].p;
         PmNorm a;
         a.in = (const pgrc_text_match *)m->pm_in.p;
@@ -417,8 +417,8 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
         a.bad = d_bad;
         hipLaunchKernelGGL(k_pm_norm, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, a);
         uint32_t bad = 0;
-        MEM_TRY(m, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
-        MEM_TRY(m, hipStreamSynchronize(st));
+        HIP_TRY(m, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(m, hipStreamSynchronize(st));
         if (bad) {
             m->err = std::string("mark_and_remove: a match ") + ((bad & PM_BAD_LEN) ? "of length 0" : (bad & PM_BAD_SRC) ? "reaches past the source's end" : "reaches past the destination's end");
             return PGRC_E_PARAM;
@@ -435,12 +435,12 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
         uint32_t *d_slot = (uint32_t *)m->pm_slot.p, *d_uslot = d_slot + n;
         hipLaunchKernelGGL(k_pm_uniq, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, (const uint64_t *)icur, (const uint64_t *)f_dst, (const uint64_t *)f_src,
                            (const uint64_t *)f_len, n, min_len, (uint8_t *)m->pm_flag.p);
-        MEM_TRY(m, (sco_scan<true>(st, (const uint8_t *)m->pm_flag.p, d_slot, n, PmBit0(), ScoPlus(), 0u, fold32)));
-        MEM_TRY(m, (sco_scan<true>(st, (const uint8_t *)m->pm_flag.p, d_uslot, n, PmBit1(), ScoPlus(), 0u, fold32)));
+        HIP_TRY(m, (sco_scan<true>(st, (const uint8_t *)m->pm_flag.p, d_slot, n, PmBit0(), ScoPlus(), 0u, fold32)));
+        HIP_TRY(m, (sco_scan<true>(st, (const uint8_t *)m->pm_flag.p, d_uslot, n, PmBit1(), ScoPlus(), 0u, fold32)));
         uint32_t cnt[2] = {0, 0};
-        MEM_TRY(m, hipMemcpyAsync(&cnt[0], d_slot + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        MEM_TRY(m, hipMemcpyAsync(&cnt[1], d_uslot + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        MEM_TRY(m, hipStreamSynchronize(st));
+        HIP_TRY(m, hipMemcpyAsync(&cnt[0], d_slot + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(m, hipMemcpyAsync(&cnt[1], d_uslot + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(m, hipStreamSynchronize(st));
         nu = cnt[0];
         nuniq = cnt[1];
         if (nu) {
@@ -451,8 +451,8 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
                                (uint64_t *)m->pm_u[1].p, (uint64_t *)m->pm_u[2].p, (uint64_t *)m->pm_u[3].p);
         }
     }
-    MEM_TRY(m, hipGetLastError());
-    MEM_TRY(m, hipEventRecord(ev[1], st));
+    HIP_TRY(m, hipGetLastError());
+    HIP_TRY(m, hipEventRecord(ev[1], st));
 
     // ---- 2. the greedy pass as a path
     uint64_t marks = 0;
@@ -466,7 +466,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
         if (e) return e;
         uint64_t *pmax = (uint64_t *)m->pm_pmax.p;
         uint32_t *kept = (uint32_t *)m->pm_kept.p, *kslot = (uint32_t *)m->pm_slot.p;
-        MEM_TRY(m, (sco_device_scan<true, false>(st, ScoLoad<uint64_t, uint64_t, ScoIdentity>{ut, ScoIdentity{}}, nu, PmMax(), (uint64_t)0, (uint64_t)0,
+        HIP_TRY(m, (sco_device_scan<true, false>(st, ScoLoad<uint64_t, uint64_t, ScoIdentity>{ut, ScoIdentity{}}, nu, PmMax(), (uint64_t)0, (uint64_t)0,
                                                  ScoStore<uint64_t>{pmax}, fold64)));
         uint32_t *jin = (uint32_t *)m->pm_jump[0].p, *jout = (uint32_t *)m->pm_jump[1].p;
         hipLaunchKernelGGL(k_pm_next, dim3(pm_grid(nu + 1)), dim3(PM_TPB), 0, st, ue, (const uint64_t *)pmax, nu, jin, kept);
@@ -474,16 +474,16 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
             hipLaunchKernelGGL(k_pm_jump, dim3(pm_grid(nu + 1)), dim3(PM_TPB), 0, st, (const uint32_t *)jin, jout, kept, nu);
             std::swap(jin, jout);
         }
-        MEM_TRY(m, (sco_scan<true>(st, (const uint32_t *)kept, kslot, nu, ScoIdentity(), ScoPlus(), 0u, fold32)));
+        HIP_TRY(m, (sco_scan<true>(st, (const uint32_t *)kept, kslot, nu, ScoIdentity(), ScoPlus(), 0u, fold32)));
         uint32_t nk = 0;
-        MEM_TRY(m, hipMemcpyAsync(&nk, kslot + (nu - 1), 4, hipMemcpyDeviceToHost, st));
-        MEM_TRY(m, hipStreamSynchronize(st));
+        HIP_TRY(m, hipMemcpyAsync(&nk, kslot + (nu - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(m, hipStreamSynchronize(st));
         marks = nk;
         hipLaunchKernelGGL(k_pm_marks, dim3(pm_grid(nu)), dim3(PM_TPB), 0, st, (const uint32_t *)kept, (const uint32_t *)kslot, ud, us, ue, nu,
                            (uint64_t *)m->pm_m[0].p, (uint64_t *)m->pm_m[1].p, (uint64_t *)m->pm_m[2].p);
     }
-    MEM_TRY(m, hipGetLastError());
-    MEM_TRY(m, hipEventRecord(ev[2], st));
+    HIP_TRY(m, hipGetLastError());
+    HIP_TRY(m, hipEventRecord(ev[2], st));
 
     // ---- 3. the marks and the two streams
     ens(m->pm_dp, marks * 8);
@@ -499,20 +499,20 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
         hipLaunchKernelGGL(k_pm_shape, dim3(pm_grid(marks)), dim3(PM_TPB), 0, st, (const uint64_t *)m->pm_m[0].p, (const uint64_t *)m->pm_m[1].p,
                            (const uint64_t *)m->pm_m[2].p, marks, rc ? 1u : 0u, min_len, width, (uint64_t *)m->pm_dp.p, (uint64_t *)m->pm_len.p,
                            (uint8_t *)m->pm_nb.p, m->pm_off.p);
-    MEM_TRY(m, (sco_sum_u64<false>(st, (const uint64_t *)m->pm_len.p, marks, cum, fold64)));
-    MEM_TRY(m, (sco_sum_u64<false>(st, (const uint8_t *)m->pm_nb.p, marks, nbpos, fold64)));
+    HIP_TRY(m, (sco_sum_u64<false>(st, (const uint64_t *)m->pm_len.p, marks, cum, fold64)));
+    HIP_TRY(m, (sco_sum_u64<false>(st, (const uint8_t *)m->pm_nb.p, marks, nbpos, fold64)));
     uint64_t tot[2] = {0, 0};                                  // matched symbols; bytes of the length values
-    MEM_TRY(m, hipMemcpyAsync(&tot[0], cum + marks, 8, hipMemcpyDeviceToHost, st));
-    MEM_TRY(m, hipMemcpyAsync(&tot[1], nbpos + marks, 8, hipMemcpyDeviceToHost, st));
-    MEM_TRY(m, hipStreamSynchronize(st));
+    HIP_TRY(m, hipMemcpyAsync(&tot[0], cum + marks, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(m, hipMemcpyAsync(&tot[1], nbpos + marks, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(m, hipStreamSynchronize(st));
     if (tot[0] > N2 || tot[1] > 10 * marks) { m->err = "mark_and_remove: inconsistent marks"; return PGRC_E_DEVICE; }
     ens(m->pm_lens, tot[1]);
     if (e) return e;
     if (marks)
         hipLaunchKernelGGL(k_pm_streams, dim3(pm_grid(marks)), dim3(PM_TPB), 0, st, (const uint64_t *)m->pm_dp.p, (const uint64_t *)m->pm_len.p,
                            (const uint64_t *)cum, (const uint64_t *)nbpos, marks, min_len, (uint64_t *)m->pm_mp.p, (uint8_t *)m->pm_lens.p);
-    MEM_TRY(m, hipGetLastError());
-    MEM_TRY(m, hipEventRecord(ev[3], st));
+    HIP_TRY(m, hipGetLastError());
+    HIP_TRY(m, hipEventRecord(ev[3], st));
 
     // ---- 4. the mapped text
     const uint64_t mapped_len = N2 - tot[0] + marks;           // (every mark replaces at least one symbol: <= N2)
@@ -533,10 +533,10 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
         t.nwords = nwords;
         t.out = (uint64_t *)text_buf.p;
         hipLaunchKernelGGL(k_pm_text, dim3(pm_grid((nwords + PM_LPT - 1) / PM_LPT)), dim3(PM_TPB), 0, st, t);
-        MEM_TRY(m, hipGetLastError());
+        HIP_TRY(m, hipGetLastError());
     }
-    MEM_TRY(m, hipEventRecord(ev[4], st));
-    MEM_TRY(m, hipStreamSynchronize(st));
+    HIP_TRY(m, hipEventRecord(ev[4], st));
+    HIP_TRY(m, hipStreamSynchronize(st));
 
     // ---- 5. the downloads
     const auto t0 = std::chrono::steady_clock::now();

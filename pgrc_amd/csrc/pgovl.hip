@@ -35,9 +35,8 @@ enum { OV_BAD_ROW, OV_BAD_RANGE, OV_BAD_TWICE, OV_BAD_SORT, OV_BAD_PLACE, OV_BAD
 
 struct pgrc_ovl_ctx {
     pgrc_decode_ctx *d = nullptr;       // the stream, the staging buffers, the error string
-    pgrc_match_ctx *mc = nullptr;       // never run as a matcher: radix.hip's stream and error string (made on first use)
     DevBuf sort_scratch;
-    DecBuf rows, sym, nx, ov, ovout, order, seen, eq, s[2], p[2], base, lens, rk, trans, merged, mk, keep, taken, offs, offp, gs, fold, words, rec[2], prev, flags;
+    DevBuf rows, sym, nx, ov, ovout, order, seen, eq, s[2], p[2], base, lens, rk, trans, merged, mk, keep, taken, offs, offp, gs, fold, words, rec[2], prev, flags;
     hipEvent_t ev[6]{};
     uint64_t R = 0;
     uint32_t L = 0, symbols = 0, rb = 0;
@@ -327,25 +326,9 @@ static __global__ void __launch_bounds__(OV_TPB) k_ov_both(const uint32_t *__res
 // ------------------------------------------------------------------------------------------------ host side
 static int ov_fail(pgrc_ovl_ctx *o, const std::string &msg) { return dec_fail(o->d, PGRC_E_PARAM, "overlap: " + msg); }
 
-static bool ov_pinned(const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) == hipSuccess) return attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return false;
-}
-
-static int ov_upload(pgrc_decode_ctx *d, void *dst, const void *src, uint64_t bytes) {
-    if (!bytes) return PGRC_OK;
-    if (ov_pinned(src)) {
-        DEC_TRY(d, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d->stream));
-        return PGRC_OK;
-    }
-    return dec_upload(d, dst, src, bytes);
-}
-
 // off[0 .. n] = the exclusive scan of the flags (negated: inv), off[n] = their count
 static int ov_scan_flags(pgrc_ovl_ctx *o, const uint8_t *flag, uint32_t inv, uint64_t n, uint32_t *off) {
-    DEC_TRY(o->d, (sco_device_scan<false, true>(o->d->stream, OvFlag{flag, inv}, n, ScoPlus{}, 0u, 0u, ScoStore<uint32_t>{off}, (uint32_t *)o->fold.p)));
+    HIP_TRY(o->d, (sco_device_scan<false, true>(o->d->stream, OvFlag{flag, inv}, n, ScoPlus{}, 0u, 0u, ScoStore<uint32_t>{off}, (uint32_t *)o->fold.p)));
     return PGRC_OK;
 }
 
@@ -353,25 +336,20 @@ static int ov_scan_flags(pgrc_ovl_ctx *o, const uint8_t *flag, uint32_t inv, uin
 static int ov_make_order(pgrc_ovl_ctx *o, uint64_t R, uint32_t L, uint32_t stride) {
     pgrc_decode_ctx *d = o->d;
     int e;
-    if ((e = dec_buf(d, o->rec[0], R * 8)) || (e = dec_buf(d, o->rec[1], R * 8))) return e;
-    if (!o->mc) {
-        o->mc = new pgrc_match_ctx();
-        o->mc->device = d->device;
-        o->mc->stream = d->stream;
-    }
+    if ((e = pgrc_buf_unpooled(d, o->rec[0], R * 8)) || (e = pgrc_buf_unpooled(d, o->rec[1], R * 8))) return e;
     uint64_t *cur = (uint64_t *)o->rec[0].p, *oth = (uint64_t *)o->rec[1].p;
     const uint8_t *sym = (const uint8_t *)o->sym.p;
     const uint32_t chunks = (L + OV_CHUNK - 1) / OV_CHUNK;
     for (uint32_t c = chunks; c-- > 0;) {
         if (c + 1 == chunks) hipLaunchKernelGGL(k_ov_keys<true>, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, sym, stride, c, R, (const uint64_t *)nullptr, cur);
         else hipLaunchKernelGGL(k_ov_keys<false>, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, sym, stride, c, R, (const uint64_t *)cur, cur);
-        DEC_TRY(d, hipGetLastError());
+        HIP_TRY(d, hipGetLastError());
         uint64_t *sorted = nullptr;
-        if ((e = pgrc_radix_sort_u64(o->mc, cur, oth, R, 32, 32 + 3 * OV_CHUNK, o->sort_scratch, &sorted))) return dec_fail(d, e, "overlap: " + o->mc->err);
+        if ((e = pgrc_radix_sort_u64(d, cur, oth, R, 32, 32 + 3 * OV_CHUNK, o->sort_scratch, &sorted))) return dec_fail(d, e, "overlap: " + d->err);
         if (sorted != cur) std::swap(cur, oth);
     }
     hipLaunchKernelGGL(k_ov_order_of, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint64_t *)cur, R, (uint32_t *)o->order.p);
-    DEC_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
     return PGRC_OK;
 }
 
@@ -387,14 +365,14 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     const uint64_t n_left = iters > 1 ? iters : 1;
     int e;
     for (hipEvent_t &ev : o->ev)
-        if (!ev) DEC_TRY(d, hipEventCreate(&ev));
-    if ((e = dec_buf(d, o->rows, R * rb + 16)) || (e = dec_buf(d, o->sym, R * stride + 16)) || (e = dec_buf(d, o->nx, N1 * 4)) || (e = dec_buf(d, o->ov, N1 * 2)) ||
-        (e = dec_buf(d, o->ovout, N1)) || (e = dec_buf(d, o->order, R * 4)) || (e = dec_buf(d, o->seen, N1 * 4)) || (e = dec_buf(d, o->eq, R)) ||
-        (e = dec_buf(d, o->s[0], R * 4)) || (e = dec_buf(d, o->s[1], R * 4)) || (e = dec_buf(d, o->p[0], R * 4)) || (e = dec_buf(d, o->p[1], R * 4)) ||
-        (e = dec_buf(d, o->base, R * 4)) || (e = dec_buf(d, o->lens, R * 20)) || (e = dec_buf(d, o->rk, R * 4)) || (e = dec_buf(d, o->trans, R * 4 + 64)) ||
-        (e = dec_buf(d, o->merged, R * 4)) || (e = dec_buf(d, o->mk, R * 4)) || (e = dec_buf(d, o->keep, R)) || (e = dec_buf(d, o->taken, R)) ||
-        (e = dec_buf(d, o->offs, N1 * 4)) || (e = dec_buf(d, o->offp, N1 * 4)) || (e = dec_buf(d, o->gs, 64)) ||
-        (e = dec_buf(d, o->fold, ov_a16(sco_scratch_elems(N1) * 8))) || (e = dec_buf(d, o->words, OV_BAD_WORDS * 4 + 16)))
+        if (!ev) HIP_TRY(d, hipEventCreate(&ev));
+    if ((e = pgrc_buf_unpooled(d, o->rows, R * rb + 16)) || (e = pgrc_buf_unpooled(d, o->sym, R * stride + 16)) || (e = pgrc_buf_unpooled(d, o->nx, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->ov, N1 * 2)) ||
+        (e = pgrc_buf_unpooled(d, o->ovout, N1)) || (e = pgrc_buf_unpooled(d, o->order, R * 4)) || (e = pgrc_buf_unpooled(d, o->seen, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->eq, R)) ||
+        (e = pgrc_buf_unpooled(d, o->s[0], R * 4)) || (e = pgrc_buf_unpooled(d, o->s[1], R * 4)) || (e = pgrc_buf_unpooled(d, o->p[0], R * 4)) || (e = pgrc_buf_unpooled(d, o->p[1], R * 4)) ||
+        (e = pgrc_buf_unpooled(d, o->base, R * 4)) || (e = pgrc_buf_unpooled(d, o->lens, R * 20)) || (e = pgrc_buf_unpooled(d, o->rk, R * 4)) || (e = pgrc_buf_unpooled(d, o->trans, R * 4 + 64)) ||
+        (e = pgrc_buf_unpooled(d, o->merged, R * 4)) || (e = pgrc_buf_unpooled(d, o->mk, R * 4)) || (e = pgrc_buf_unpooled(d, o->keep, R)) || (e = pgrc_buf_unpooled(d, o->taken, R)) ||
+        (e = pgrc_buf_unpooled(d, o->offs, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->offp, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->gs, 64)) ||
+        (e = pgrc_buf_unpooled(d, o->fold, ov_a16(sco_scratch_elems(N1) * 8))) || (e = pgrc_buf_unpooled(d, o->words, OV_BAD_WORDS * 4 + 16)))
         return e;
     const uint8_t *rows = (const uint8_t *)o->rows.p;
     uint8_t *sym = (uint8_t *)o->sym.p, *eq = (uint8_t *)o->eq.p, *keep = (uint8_t *)o->keep.p, *taken = (uint8_t *)o->taken.p;
@@ -403,30 +381,30 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     uint32_t *gs = (uint32_t *)o->gs.p, *bad = (uint32_t *)o->words.p;
     uint16_t *ov = (uint16_t *)o->ov.p;
 
-    if ((e = ov_upload(d, o->rows.p, in->packed_rows, R * rb))) return e;
-    if (in->sorted_order && (e = ov_upload(d, order, in->sorted_order, R * 4))) return e;
-    DEC_TRY(d, hipMemsetAsync(sym, 0, R * stride + 16, d->stream));
-    DEC_TRY(d, hipMemsetAsync(nx, 0, N1 * 4, d->stream));
-    DEC_TRY(d, hipMemsetAsync(ov, 0, N1 * 2, d->stream));
-    DEC_TRY(d, hipMemsetAsync(o->seen.p, 0, N1 * 4, d->stream));
-    DEC_TRY(d, hipMemsetAsync(bad, 0, OV_BAD_WORDS * 4, d->stream));
+    if ((e = dec_upload_host(d, o->rows.p, in->packed_rows, R * rb))) return e;
+    if (in->sorted_order && (e = dec_upload_host(d, order, in->sorted_order, R * 4))) return e;
+    HIP_TRY(d, hipMemsetAsync(sym, 0, R * stride + 16, d->stream));
+    HIP_TRY(d, hipMemsetAsync(nx, 0, N1 * 4, d->stream));
+    HIP_TRY(d, hipMemsetAsync(ov, 0, N1 * 2, d->stream));
+    HIP_TRY(d, hipMemsetAsync(o->seen.p, 0, N1 * 4, d->stream));
+    HIP_TRY(d, hipMemsetAsync(bad, 0, OV_BAD_WORDS * 4, d->stream));
     const float ms_upload = ov_ms(t0);
 
     // the rows unpacked and checked, the order made or checked
-    DEC_TRY(d, hipEventRecord(o->ev[0], d->stream));
+    HIP_TRY(d, hipEventRecord(o->ev[0], d->stream));
     {
         const uint64_t total = R * rb;
         hipLaunchKernelGGL(k_ov_unpack, dim3((uint32_t)std::min<uint64_t>(ov_grid(total), 1u << 20)), dim3(OV_TPB), 0, d->stream, rows, total, rb, symbols, L, stride, sym, bad);
-        DEC_TRY(d, hipGetLastError());
+        HIP_TRY(d, hipGetLastError());
     }
     if (in->sorted_order) hipLaunchKernelGGL(k_ov_perm, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, R, (uint32_t *)o->seen.p, bad);
     else if ((e = ov_make_order(o, R, L, stride))) return e;
     hipLaunchKernelGGL(k_ov_adjacent, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, L, (const uint32_t *)order, R, eq, bad);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(o->ev[1], d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(o->ev[1], d->stream));
     uint32_t h_bad[OV_BAD_WORDS] = {};
-    DEC_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     // nothing below follows a read number before the order is known to be a permutation of 1 .. R
     if (h_bad[OV_BAD_ROW]) return ov_fail(o, "a row byte that is no packing of the alphabet");
     if (h_bad[OV_BAD_RANGE]) return ov_fail(o, "sorted_order holds a number outside 1 .. " + std::to_string(R));
@@ -439,23 +417,23 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
 
     // the start: chains of equal reads, P and S, the groups by the first symbol
     uint32_t *S = (uint32_t *)o->s[0].p, *S2 = (uint32_t *)o->s[1].p, *P = (uint32_t *)o->p[0].p, *P2 = (uint32_t *)o->p[1].p;
-    DEC_TRY(d, hipEventRecord(o->ev[0], d->stream));
+    HIP_TRY(d, hipEventRecord(o->ev[0], d->stream));
     hipLaunchKernelGGL(k_ov_chains, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, (const uint8_t *)eq, R, L, nx, ov, keep, taken);
-    DEC_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
     if ((e = ov_scan_flags(o, keep, 0, R, offs)) || (e = ov_scan_flags(o, taken, 0, R, offp))) return e;
     hipLaunchKernelGGL(k_ov_compact, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, (const uint8_t *)keep, 0u, (const uint32_t *)offs, R, R, S);
     hipLaunchKernelGGL(k_ov_compact, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, (const uint8_t *)taken, 0u, (const uint32_t *)offp, R, R, P);
-    DEC_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
     uint32_t h_n[2] = {};
-    DEC_TRY(d, hipMemcpyAsync(&h_n[0], offs + R, 4, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipMemcpyAsync(&h_n[1], offp + R, 4, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipMemcpyAsync(&h_n[0], offs + R, 4, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipMemcpyAsync(&h_n[1], offp + R, 4, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     uint64_t ns = h_n[0], np = h_n[1];
     if (ns != np || ns < 1 || ns > R) return dec_fail(d, PGRC_E_DEVICE, "overlap: " + std::to_string(ns) + " chain ends and " + std::to_string(np) + " chain heads");
     hipLaunchKernelGGL(k_ov_groups, dim3(ov_grid(ns + 1)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, 0u, (const uint32_t *)S, ns, gs);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(o->ev[1], d->stream));
-    DEC_TRY(d, hipEventSynchronize(o->ev[1]));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(o->ev[1], d->stream));
+    HIP_TRY(d, hipEventSynchronize(o->ev[1]));
     const float ms_start = dec_elapsed(o->ev[0], o->ev[1]);
 
     // the block of the result; the reads-left numbers are written as they come
@@ -617,14 +595,13 @@ void pgrc_ovl_destroy(pgrc_ovl_ctx *o) {
     {
         PgrcDeviceScope scope(o->d->device);
         (void)hipStreamSynchronize(o->d->stream);
-        for (DecBuf *b : {&o->rows, &o->sym, &o->nx, &o->ov, &o->ovout, &o->order, &o->seen, &o->eq, &o->s[0], &o->s[1], &o->p[0], &o->p[1], &o->base, &o->lens, &o->rk,
+        for (DevBuf *b : {&o->rows, &o->sym, &o->nx, &o->ov, &o->ovout, &o->order, &o->seen, &o->eq, &o->s[0], &o->s[1], &o->p[0], &o->p[1], &o->base, &o->lens, &o->rk,
                            &o->trans, &o->merged, &o->mk, &o->keep, &o->taken, &o->offs, &o->offp, &o->gs, &o->fold, &o->words, &o->rec[0], &o->rec[1], &o->prev, &o->flags})
             dec_free(*b);
         pgrc_buf_free(o->sort_scratch);
         for (hipEvent_t ev : o->ev)
             if (ev) (void)hipEventDestroy(ev);
     }
-    delete o->mc;
     pgrc_decode_destroy(o->d);
     delete o;
 }
@@ -667,21 +644,21 @@ int pgrc_ovl_both_sides(pgrc_ovl_ctx *o, uint8_t *flags) {
     PGRC_ON_DEVICE(d);
     const uint64_t R = o->R, N1 = R + 1;
     int e;
-    if ((e = dec_buf(d, o->prev, N1 * 2)) || (e = dec_buf(d, o->flags, R))) return e;
-    DEC_TRY(d, hipMemsetAsync(o->prev.p, 0, N1 * 2, d->stream));
+    if ((e = pgrc_buf_unpooled(d, o->prev, N1 * 2)) || (e = pgrc_buf_unpooled(d, o->flags, R))) return e;
+    HIP_TRY(d, hipMemsetAsync(o->prev.p, 0, N1 * 2, d->stream));
     hipLaunchKernelGGL(k_ov_prev, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, R, (uint16_t *)o->prev.p);
     hipLaunchKernelGGL(k_ov_both, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, (const uint16_t *)o->prev.p, R, o->L,
                        (uint8_t *)o->flags.p);
-    DEC_TRY(d, hipGetLastError());
-    if (ov_pinned(flags)) {
-        DEC_TRY(d, hipMemcpyAsync(flags, o->flags.p, R, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipGetLastError());
+    if (pgrc_host_pinned(flags)) {
+        HIP_TRY(d, hipMemcpyAsync(flags, o->flags.p, R, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
         return PGRC_OK;
     }
     for (uint64_t at = 0; at < R; at += DEC_STAGE_BYTES) {     // pageable memory: through a staging buffer
         const uint64_t c = std::min<uint64_t>(DEC_STAGE_BYTES, R - at);
-        DEC_TRY(d, hipMemcpyAsync(d->stage[0], (const uint8_t *)o->flags.p + at, c, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(d, hipMemcpyAsync(d->stage[0], (const uint8_t *)o->flags.p + at, c, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
         memcpy(flags + at, d->stage[0], c);
     }
     return PGRC_OK;
@@ -696,7 +673,7 @@ int pgrc_ovl_assemble(pgrc_ovl_ctx *o, pgrc_asm_ctx *a, const uint32_t *index_ma
     if (pgasm_device(a) != d->device) return ov_fail(o, "the two contexts are on different devices");
     {
         PGRC_ON_DEVICE(d);
-        DEC_TRY(d, hipStreamSynchronize(d->stream));        // (a run leaves its stream idle; both_sides may have used it since)
+        HIP_TRY(d, hipStreamSynchronize(d->stream));        // (a run leaves its stream idle; both_sides may have used it since)
     }
     pgrc_asm_input in{};
     in.struct_size = sizeof(in);

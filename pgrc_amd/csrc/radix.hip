@@ -264,10 +264,11 @@ k_rx_segments(uint64_t *__restrict__ keys, uint64_t *__restrict__ vals, const ui
 }
 
 // seg[0 .. nseg]: the bounds of the segments of keys[] / vals[] (device; ascending, seg[nseg] = the number of pairs); ovl: cap + 1
-// words on the device, ovl[0] zeroed by the caller.  On c->stream, no synchronisation.
-int pgrc_radix_sort_segments_pairs_u64(pgrc_match_ctx *c, uint64_t *keys, uint64_t *vals, const uint32_t *seg, uint32_t nseg, uint32_t bit_lo, uint32_t bit_hi,
-                                       uint32_t *ovl, uint32_t cap) {
-    const uint32_t top_bits = c->opt.test_segment_top_bits ? c->opt.test_segment_top_bits : 32u;
+// words on the device, ovl[0] zeroed by the caller; top_bits: the short way's span of top bits (0 = the default of 32; the tests' knob).
+// On c->stream, no synchronisation.
+int pgrc_radix_sort_segments_pairs_u64(PgrcDev *c, uint64_t *keys, uint64_t *vals, const uint32_t *seg, uint32_t nseg, uint32_t bit_lo, uint32_t bit_hi,
+                                       uint32_t *ovl, uint32_t cap, uint32_t top_bits) {
+    if (!top_bits) top_bits = 32u;
     if (!nseg || bit_hi <= bit_lo) return PGRC_OK;
     HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_rx_segments), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(RX_TILE * sizeof(uint64_t))));
     hipLaunchKernelGGL(k_rx_segments, dim3(nseg), dim3(RX_TPB), RX_TILE * sizeof(uint64_t), c->stream, keys, vals, seg, bit_lo, bit_hi, top_bits, ovl, cap);
@@ -278,7 +279,7 @@ int pgrc_radix_sort_segments_pairs_u64(pgrc_match_ctx *c, uint64_t *keys, uint64
 // Sorts d_a[0 .. n) by the bits [bit_lo, bit_hi) of every record, stable; d_b: n records of scratch; `scratch` grows as
 // needed (count matrix).  *sorted = d_a or d_b, wherever the last pass put the records.  With v_a / v_b (both or neither): every
 // record carries a 64-bit value that moves with it; *vsorted = where the values ended up.  All on c->stream, no synchronisation.
-static int rx_sort(pgrc_match_ctx *c, uint64_t *d_a, uint64_t *d_b, uint64_t *v_a, uint64_t *v_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi,
+static int rx_sort(PgrcDev *c, uint64_t *d_a, uint64_t *d_b, uint64_t *v_a, uint64_t *v_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi,
                    DevBuf &scratch, uint64_t **sorted, uint64_t **vsorted) {
     *sorted = d_a;
     if (vsorted) *vsorted = v_a;
@@ -317,12 +318,12 @@ static int rx_sort(pgrc_match_ctx *c, uint64_t *d_a, uint64_t *d_b, uint64_t *v_
     return PGRC_OK;
 }
 
-int pgrc_radix_sort_u64(pgrc_match_ctx *c, uint64_t *d_a, uint64_t *d_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, DevBuf &scratch,
+int pgrc_radix_sort_u64(PgrcDev *c, uint64_t *d_a, uint64_t *d_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, DevBuf &scratch,
                         uint64_t **sorted) {
     return rx_sort(c, d_a, d_b, nullptr, nullptr, n, bit_lo, bit_hi, scratch, sorted, nullptr);
 }
 
-int pgrc_radix_sort_pairs_u64(pgrc_match_ctx *c, uint64_t *k_a, uint64_t *k_b, uint64_t *v_a, uint64_t *v_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi,
+int pgrc_radix_sort_pairs_u64(PgrcDev *c, uint64_t *k_a, uint64_t *k_b, uint64_t *v_a, uint64_t *v_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi,
                               DevBuf &scratch, uint64_t **ksorted, uint64_t **vsorted) {
     return rx_sort(c, k_a, k_b, v_a, v_b, n, bit_lo, bit_hi, scratch, ksorted, vsorted);
 }

@@ -277,13 +277,6 @@ __global__ void __launch_bounds__(DEC_TPB) k_rs_fill(RsPart p, int rc, const uin
 // ------------------------------------------------------------------------------------------------ host side
 static uint64_t rs_a16(uint64_t x) { return (x + 15) & ~15ull; }
 
-static bool rs_pinned(const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) == hipSuccess) return attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return false;
-}
-
 static int rs_fail(pgrc_decode_ctx *d, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, "set_mapped_text: " + msg); }
 
 static uint32_t rs_grid(uint64_t items, uint64_t per_block) {
@@ -333,33 +326,30 @@ static int rs_set_mapped(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_v
         at[s] = dev_bytes;
         dev_bytes += rs_a16(nbytes[s] + RS_PAD);
     }
-    if ((e = dec_buf(d, d->rs_mapped, dev_bytes))) return e;
+    if ((e = pgrc_buf_unpooled(d, d->rs_mapped, dev_bytes))) return e;
     uint8_t *dm = (uint8_t *)d->rs_mapped.p;
     if (v) {
-        if ((e = dec_buf(d, d->rs_coded, coded_len)) || (e = dec_buf(d, d->rs_join, mtot))) return e;
-        if (coded_len && rs_pinned(coded)) DEC_TRY(d, hipMemcpyAsync(d->rs_coded.p, coded, coded_len, hipMemcpyHostToDevice, d->stream));
-        else if (coded_len && (e = dec_upload(d, d->rs_coded.p, coded, coded_len))) return e;
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
+        if ((e = pgrc_buf_unpooled(d, d->rs_coded, coded_len)) || (e = pgrc_buf_unpooled(d, d->rs_join, mtot))) return e;
+        if ((e = dec_upload_host(d, d->rs_coded.p, coded, coded_len))) return e;
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
         if ((e = pgrc_varlen_decode(v, d->rs_coded.p, coded_len, 1, mtot, d->rs_join.p, 1)))
             return dec_fail(d, e, std::string("set_mapped_text_coded: ") + pgrc_varlen_last_error(v));
     }
-    const bool pinned = !v && mtot && rs_pinned(m->mapped);
     for (int s = 0; s < 9; s++) {
         const uint64_t z = nbytes[s] & ~15ull;
-        DEC_TRY(d, hipMemsetAsync(dm + at[s] + z, 0, rs_a16(nbytes[s] + RS_PAD) - z, d->stream));
+        HIP_TRY(d, hipMemsetAsync(dm + at[s] + z, 0, rs_a16(nbytes[s] + RS_PAD) - z, d->stream));
         if (!nbytes[s]) continue;
-        if (s < 3 && v) DEC_TRY(d, hipMemcpyAsync(dm + at[s], (const uint8_t *)d->rs_join.p + part_at[s], nbytes[s], hipMemcpyDeviceToDevice, d->stream));
-        else if (s < 3 && pinned) DEC_TRY(d, hipMemcpyAsync(dm + at[s], hsrc[s], nbytes[s], hipMemcpyHostToDevice, d->stream));
-        else if ((e = dec_upload(d, dm + at[s], hsrc[s], nbytes[s]))) return e;
+        if (s < 3 && v) HIP_TRY(d, hipMemcpyAsync(dm + at[s], (const uint8_t *)d->rs_join.p + part_at[s], nbytes[s], hipMemcpyDeviceToDevice, d->stream));
+        else if ((e = s < 3 ? dec_upload_host(d, dm + at[s], hsrc[s], nbytes[s]) : dec_upload(d, dm + at[s], hsrc[s], nbytes[s]))) return e;   // (the streams: always staged)
     }
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     pgrc_decode_restore_timing tm{};
     tm.struct_size = sizeof(tm);
     tm.ms_upload = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
 
     // 2. parse: count the marks (parts) and the value ends (lengths streams) per block, scan the block counts
     if ((e = dec_clear_err(d))) return e;
-    DEC_TRY(d, hipEventRecord(d->ev_a, d->stream));
+    HIP_TRY(d, hipEventRecord(d->ev_a, d->stream));
     const int job_buf[6] = {0, 1, 2, 6, 7, 8};
     uint64_t nb[6], bs_at[6], bs_words = 0;
     for (int j = 0; j < 6; j++) {
@@ -367,7 +357,7 @@ static int rs_set_mapped(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_v
         bs_at[j] = bs_words;
         bs_words += 2 * nb[j] + 1;                       // block counts, then their exclusive scan (nb + 1)
     }
-    if ((e = dec_buf(d, d->rs_bsum, bs_words * 8))) return e;
+    if ((e = pgrc_buf_unpooled(d, d->rs_bsum, bs_words * 8))) return e;
     uint64_t *bs = (uint64_t *)d->rs_bsum.p;
     for (int j = 0; j < 6; j++) {
         const int s = job_buf[j];
@@ -377,10 +367,10 @@ static int rs_set_mapped(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_v
         }
         if ((e = dec_scan<false>(d, XfU64{bs + bs_at[j]}, nb[j], 0, bs + bs_at[j] + nb[j]))) return e;
     }
-    DEC_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
     uint64_t cnt[6];
-    for (int j = 0; j < 6; j++) DEC_TRY(d, hipMemcpyAsync(&cnt[j], bs + bs_at[j] + 2 * nb[j], 8, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    for (int j = 0; j < 6; j++) HIP_TRY(d, hipMemcpyAsync(&cnt[j], bs + bs_at[j] + 2 * nb[j], 8, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     static const char *pname[3] = {"HQ", "LQ", "N"};
     for (int p = 0; p < 3; p++) {
         const uint64_t n = cnt[p], nv = cnt[3 + p];
@@ -399,7 +389,7 @@ static int rs_set_mapped(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_v
         val_at[p] = val_words;
         val_words += cnt[p] + 1;
     }
-    if ((e = dec_buf(d, d->rs_marks, mk_words * 8)) || (e = dec_buf(d, d->rs_vals, val_words * 8))) return e;
+    if ((e = pgrc_buf_unpooled(d, d->rs_marks, mk_words * 8)) || (e = pgrc_buf_unpooled(d, d->rs_vals, val_words * 8))) return e;
     RsPart part[3];
     uint32_t *flag = (uint32_t *)d->flag.p;
     for (int p = 0; p < 3; p++) {
@@ -420,7 +410,7 @@ static int rs_set_mapped(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_v
         x.lim = m->org_hq_len;
         x.width = width;
         x.hq = p == 0;
-        if (!cnt[3 + p]) DEC_TRY(d, hipMemsetAsync(v, 0, 8, d->stream));      // an empty lengths stream: minMatchLength 0
+        if (!cnt[3 + p]) HIP_TRY(d, hipMemsetAsync(v, 0, 8, d->stream));      // an empty lengths stream: minMatchLength 0
         if (nb[p])
             hipLaunchKernelGGL(k_rs_write<0>, dim3((uint32_t)nb[p]), dim3(DEC_TPB), 0, d->stream, dm + at[p], nbytes[p],
                                (const uint64_t *)(bs + bs_at[p] + nb[p]), x.mpos, flag);
@@ -431,13 +421,13 @@ static int rs_set_mapped(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_v
         if ((e = dec_scan<false>(d, XfU64{x.len}, n, 0, x.cum))) return e;
         if (n) hipLaunchKernelGGL(k_rs_check, dim3(rs_grid(n, 256)), dim3(256), 0, d->stream, x, flag);
     }
-    DEC_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipGetLastError());
     uint64_t matched[3];
     uint32_t f = 0;
-    for (int p = 0; p < 3; p++) DEC_TRY(d, hipMemcpyAsync(&matched[p], part[p].cum + cnt[p], 8, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipMemcpyAsync(&f, flag, 4, hipMemcpyDeviceToHost, d->stream));
-    DEC_TRY(d, hipEventRecord(d->ev_b, d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    for (int p = 0; p < 3; p++) HIP_TRY(d, hipMemcpyAsync(&matched[p], part[p].cum + cnt[p], 8, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipMemcpyAsync(&f, flag, 4, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipEventRecord(d->ev_b, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     tm.ms_parse_device = dec_elapsed(d->ev_a, d->ev_b);
     if (f) {
         std::string msg;
@@ -459,36 +449,36 @@ static int rs_set_mapped(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_v
 
     // 3. literals into the text buffer (padded as pgrc_decode_set_text pads it)
     const uint64_t tbytes = rs_a16(total) + DEC_TEXT_PAD;
-    if ((e = dec_buf(d, d->text, tbytes))) return e;
+    if ((e = pgrc_buf_unpooled(d, d->text, tbytes))) return e;
     uint8_t *text = (uint8_t *)d->text.p;
-    DEC_TRY(d, hipMemsetAsync(text + (total & ~15ull), 0, tbytes - (total & ~15ull), d->stream));
-    DEC_TRY(d, hipEventRecord(d->ev_a, d->stream));
+    HIP_TRY(d, hipMemsetAsync(text + (total & ~15ull), 0, tbytes - (total & ~15ull), d->stream));
+    HIP_TRY(d, hipEventRecord(d->ev_a, d->stream));
     for (int p = 0; p < 3; p++)
         if (plen[p]) {
             const uint64_t words = ((part[p].tbase + plen[p] + 7) >> 3) - (part[p].tbase >> 3);
             hipLaunchKernelGGL(k_rs_literals, dim3(rs_grid(words, (uint64_t)DEC_TPB * RS_LPT)), dim3(DEC_TPB), 0, d->stream, part[p], text);
         }
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->ev_b, d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->ev_b, d->stream));
 
     // 4. matches: HQ chains by pointer jumping, then the HQ fill, then LQ and N in one hop from the finished HQ
     uint32_t passes = 0;
     if (matched[0]) {
-        if ((e = dec_buf(d, d->rs_ptr, matched[0] * 8))) return e;
+        if ((e = pgrc_buf_unpooled(d, d->rs_ptr, matched[0] * 8))) return e;
         uint64_t *ptr = (uint64_t *)d->rs_ptr.p;
         if ((e = dec_clear_err(d))) return e;
         hipLaunchKernelGGL(k_rs_ptr_init, dim3(rs_grid(matched[0], (uint64_t)DEC_TPB * RS_SPT)), dim3(DEC_TPB), 0, d->stream, part[0], rc, ptr, flag);
-        DEC_TRY(d, hipGetLastError());
+        HIP_TRY(d, hipGetLastError());
         const uint32_t jgrid = rs_grid(matched[0], (uint64_t)DEC_TPB * 16);
         for (;;) {
             uint32_t more = 0;
-            DEC_TRY(d, hipMemcpyAsync(&more, flag, 4, hipMemcpyDeviceToHost, d->stream));
-            DEC_TRY(d, hipStreamSynchronize(d->stream));
+            HIP_TRY(d, hipMemcpyAsync(&more, flag, 4, hipMemcpyDeviceToHost, d->stream));
+            HIP_TRY(d, hipStreamSynchronize(d->stream));
             if (!more) break;
             if (passes > 64) return dec_fail(d, PGRC_E_DEVICE, "set_mapped_text: HQ chains did not resolve in 64 passes");
             if ((e = dec_clear_err(d))) return e;
             hipLaunchKernelGGL(k_rs_jump, dim3(jgrid), dim3(DEC_TPB), 0, d->stream, ptr, matched[0], flag);
-            DEC_TRY(d, hipGetLastError());
+            HIP_TRY(d, hipGetLastError());
             passes++;
         }
         hipLaunchKernelGGL(k_rs_fill, dim3(rs_grid(matched[0], (uint64_t)DEC_TPB * RS_SPT)), dim3(DEC_TPB), 0, d->stream, part[0], rc,
@@ -498,9 +488,9 @@ static int rs_set_mapped(pgrc_decode_ctx *d, const pgrc_decode_mapped *m, pgrc_v
         if (matched[p])
             hipLaunchKernelGGL(k_rs_fill, dim3(rs_grid(matched[p], (uint64_t)DEC_TPB * RS_SPT)), dim3(DEC_TPB), 0, d->stream, part[p], rc,
                                (const uint64_t *)nullptr, text);
-    DEC_TRY(d, hipGetLastError());
-    DEC_TRY(d, hipEventRecord(d->ev_k0[0], d->stream));
-    DEC_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->ev_k0[0], d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
     tm.ms_literals_device = dec_elapsed(d->ev_a, d->ev_b);
     tm.ms_matches_device = dec_elapsed(d->ev_b, d->ev_k0[0]);
     tm.passes = passes;
@@ -545,9 +535,9 @@ int pgrc_decode_get_text(pgrc_decode_ctx *d, uint64_t first, uint64_t n, char *o
     if (!out) return dec_fail(d, PGRC_E_PARAM, "out is NULL");
     PGRC_ON_DEVICE(d);
     const uint8_t *src = (const uint8_t *)d->text.p + first;
-    if (rs_pinned(out)) {
-        DEC_TRY(d, hipMemcpyAsync(out, src, n, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipStreamSynchronize(d->stream));
+    if (pgrc_host_pinned(out)) {
+        HIP_TRY(d, hipMemcpyAsync(out, src, n, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
         return PGRC_OK;
     }
     // pieces through the two staging buffers: piece c is copied down while piece c-1 is handed over
@@ -556,17 +546,17 @@ int pgrc_decode_get_text(pgrc_decode_ctx *d, uint64_t first, uint64_t n, char *o
     for (uint64_t o = 0, c = 0; o < n; o += DEC_STAGE_BYTES, c++) {
         const int k = (int)(c & 1);
         const uint64_t b = std::min<uint64_t>(DEC_STAGE_BYTES, n - o);
-        DEC_TRY(d, hipMemcpyAsync(d->stage[k], src + o, b, hipMemcpyDeviceToHost, d->stream));
-        DEC_TRY(d, hipEventRecord(d->ev_copied[k], d->stream));
+        HIP_TRY(d, hipMemcpyAsync(d->stage[k], src + o, b, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(d, hipEventRecord(d->ev_copied[k], d->stream));
         if (pend >= 0) {
-            DEC_TRY(d, hipEventSynchronize(d->ev_copied[pend]));
+            HIP_TRY(d, hipEventSynchronize(d->ev_copied[pend]));
             memcpy(out + pend_off, d->stage[pend], pend_bytes);
         }
         pend = k;
         pend_off = o;
         pend_bytes = b;
     }
-    DEC_TRY(d, hipEventSynchronize(d->ev_copied[pend]));
+    HIP_TRY(d, hipEventSynchronize(d->ev_copied[pend]));
     memcpy(out + pend_off, d->stage[pend], pend_bytes);
     return PGRC_OK;
 }

@@ -1068,7 +1068,7 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
         HIP_TRY(c, hipMemsetAsync(ovl, 0, sizeof(uint32_t), c->stream));
         hipLaunchKernelGGL(k_seed_bounds, dim3((nseg + 1 + 255) / 256), dim3(256), 0, c->stream, (const uint64_t *)ks, (uint32_t)nent, seg);
         HIP_TRY(c, hipGetLastError());
-        if ((e = pgrc_radix_sort_segments_pairs_u64(c, ks, vs, seg, nseg, 0, 64u - SX_SEG_BITS, ovl, OVL_CAP))) return e;
+        if ((e = pgrc_radix_sort_segments_pairs_u64(c, ks, vs, seg, nseg, 0, 64u - SX_SEG_BITS, ovl, OVL_CAP, c->opt.test_segment_top_bits))) return e;
         uint32_t h_ovl[OVL_CAP + 1];
         HIP_TRY(c, hipMemcpyAsync(h_ovl, ovl, sizeof h_ovl, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -19,7 +19,7 @@
 #define ST_FILL 0xA5
 
 struct pgrc_selftest {
-    pgrc_match_ctx *mc = nullptr;       // never run as a matcher: the device, the stream, the error string and radix.hip's scratch growth
+    PgrcDev dev;                        // with a stream of its own
     DevBuf sort_scratch;
 };
 
@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(1024) k_st_block(const T *__restrict__ in, Op 
 template <typename T, typename Op>
 int st_block_run(pgrc_selftest *h, uint32_t threads, bool nwv_static, bool sync_after, const void *in, Op op, T ident, void *ex, void *tot, void *second,
                  uint32_t *guards) {
-    pgrc_match_ctx *c = h->mc;
+    PgrcDev *c = &h->dev;
     const size_t bytes = (size_t)threads * sizeof(T);
     StBuf din, dout[3];
     HIP_TRY(c, din.alloc(bytes, 0));
@@ -167,11 +167,9 @@ int st_block_run(pgrc_selftest *h, uint32_t threads, bool nwv_static, bool sync_
 extern "C" int pgrc_selftest_create(int device, pgrc_selftest **out) {
     *out = nullptr;
     pgrc_selftest *h = new pgrc_selftest();
-    h->mc = new pgrc_match_ctx();
-    h->mc->device = device;
+    h->dev.device = device;
     PgrcDeviceScope scope(device);
-    if (!scope.ok || hipStreamCreate(&h->mc->stream) != hipSuccess) {
-        delete h->mc;
+    if (!scope.ok || hipStreamCreate(&h->dev.stream) != hipSuccess) {
         delete h;
         return PGRC_E_NO_DEVICE;
     }
@@ -181,15 +179,14 @@ extern "C" int pgrc_selftest_create(int device, pgrc_selftest **out) {
 
 extern "C" void pgrc_selftest_destroy(pgrc_selftest *h) {
     if (!h) return;
-    PgrcDeviceScope scope(h->mc->device);
-    (void)hipStreamSynchronize(h->mc->stream);
+    PgrcDeviceScope scope(h->dev.device);
+    (void)hipStreamSynchronize(h->dev.stream);
     pgrc_buf_free(h->sort_scratch);
-    (void)hipStreamDestroy(h->mc->stream);
-    delete h->mc;
+    (void)hipStreamDestroy(h->dev.stream);
     delete h;
 }
 
-extern "C" const char *pgrc_selftest_last_error(const pgrc_selftest *h) { return h->mc->err.c_str(); }
+extern "C" const char *pgrc_selftest_last_error(const pgrc_selftest *h) { return h->dev.err.c_str(); }
 
 extern "C" uint64_t pgrc_selftest_scratch_elems(uint64_t n) { return sco_scratch_elems(n); }
 
@@ -198,7 +195,7 @@ extern "C" uint64_t pgrc_selftest_scratch_elems(uint64_t n) { return sco_scratch
 // whose input and output elements have one size).  start and total_at_n: the u64 sums only.
 extern "C" int pgrc_selftest_device_scan(pgrc_selftest *h, int kind, const void *in, uint64_t n, uint64_t start, int inclusive, int total_at_n, int in_place,
                                          void *out, uint32_t *guards) {
-    pgrc_match_ctx *c = h->mc;
+    PgrcDev *c = &h->dev;
     PGRC_ON_DEVICE(c);
     const bool u64sum = kind >= ST_U64_SUM_U8 && kind <= ST_U64_SUM_U64;
     if (kind < 0 || kind >= ST_KINDS || (!u64sum && (start || total_at_n)) || (in_place && k_in_size[kind] != k_t_size[kind])) {
@@ -241,7 +238,7 @@ extern "C" int pgrc_selftest_device_scan(pgrc_selftest *h, int kind, const void 
 // kernel puts its own barrier between the two scans.  *guards: bits 0..2, the zones after the three outputs.
 extern "C" int pgrc_selftest_block_scan(pgrc_selftest *h, int kind, uint32_t block_threads, int nwv_static, int sync_after, const void *in, void *out_exclusive,
                                         void *out_total_per_thread, void *out_second, uint32_t *guards) {
-    pgrc_match_ctx *c = h->mc;
+    PgrcDev *c = &h->dev;
     PGRC_ON_DEVICE(c);
     if (!block_threads || block_threads % 64u || block_threads > 1024u) {
         c->err = "selftest: the block scan needs whole waves, at most 16";
@@ -262,7 +259,7 @@ extern "C" int pgrc_selftest_block_scan(pgrc_selftest *h, int kind, uint32_t blo
 // zones after the two key buffers, bits 2, 3 after the two value buffers (set when there are none).
 extern "C" int pgrc_selftest_sort(pgrc_selftest *h, const uint64_t *keys, const uint64_t *vals, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, uint64_t *out_keys,
                                   uint64_t *out_vals, uint32_t *guards) {
-    pgrc_match_ctx *c = h->mc;
+    PgrcDev *c = &h->dev;
     PGRC_ON_DEVICE(c);
     StBuf k[2], v[2];
     for (StBuf &b : k) HIP_TRY(c, b.alloc(n * 8, ST_GUARD * 8));
@@ -298,7 +295,7 @@ extern "C" int pgrc_selftest_sort(pgrc_selftest *h, const uint64_t *keys, const 
 extern "C" int pgrc_selftest_sort_segments(pgrc_selftest *h, const uint64_t *keys, const uint64_t *vals, const uint32_t *seg, uint32_t nseg, uint32_t bit_lo,
                                            uint32_t bit_hi, uint32_t top_bits, uint32_t cap, uint64_t *out_keys, uint64_t *out_vals, uint32_t *out_ovl,
                                            uint32_t *guards) {
-    pgrc_match_ctx *c = h->mc;
+    PgrcDev *c = &h->dev;
     PGRC_ON_DEVICE(c);
     const uint64_t n = seg[nseg];
     StBuf k, v, ds, ovl;
@@ -312,9 +309,7 @@ extern "C" int pgrc_selftest_sort_segments(pgrc_selftest *h, const uint64_t *key
     }
     HIP_TRY(c, hipMemcpy(ds.p, seg, ((size_t)nseg + 1) * 4, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(ovl.p, 0, 4));
-    c->opt.test_segment_top_bits = top_bits;
-    const int e = pgrc_radix_sort_segments_pairs_u64(c, (uint64_t *)k.p, (uint64_t *)v.p, (const uint32_t *)ds.p, nseg, bit_lo, bit_hi, (uint32_t *)ovl.p, cap);
-    c->opt.test_segment_top_bits = 0;
+    const int e = pgrc_radix_sort_segments_pairs_u64(c, (uint64_t *)k.p, (uint64_t *)v.p, (const uint32_t *)ds.p, nseg, bit_lo, bit_hi, (uint32_t *)ovl.p, cap, top_bits);
     if (e) return e;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (n) {

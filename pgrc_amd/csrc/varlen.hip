@@ -322,30 +322,6 @@ static int vl_fail(pgrc_varlen *v, int code, const std::string &msg) {
     return code;
 }
 
-#define VL_TRY(v, expr)                                                                      \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            (v)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                   \
-            return pgrc_hip_code(e__);                                                       \
-        }                                                                                    \
-    } while (0)
-
-static int vl_buf(pgrc_varlen *v, DevBuf &b, uint64_t bytes) {
-    bytes = std::max<uint64_t>(bytes, 64);
-    if (b.p && b.bytes >= bytes) return PGRC_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    const hipError_t e = hipMalloc(&b.p, (size_t)bytes);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return vl_fail(v, pgrc_hip_code(e), "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
-    }
-    b.bytes = (size_t)bytes;
-    return PGRC_OK;
-}
-
 static bool vl_is_device_ptr(const void *p) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) == hipSuccess) return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
@@ -465,9 +441,9 @@ int pgrc_varlen_create(const void *book, uint64_t book_bytes, int32_t device, pg
     if (!e && hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess) e = PGRC_E_DEVICE;
     for (int k = 0; k < 4 && !e; k++)
         if (hipEventCreate(&v->ev[k]) != hipSuccess) e = PGRC_E_DEVICE;
-    if (!e) e = vl_buf(v, v->d_tab, sizeof(VlTables));
-    if (!e) e = vl_buf(v, v->d_book, sizeof(VlBook));
-    if (!e) e = vl_buf(v, v->d_flag, 64);
+    if (!e) e = pgrc_buf_unpooled(v, v->d_tab, sizeof(VlTables));
+    if (!e) e = pgrc_buf_unpooled(v, v->d_book, sizeof(VlBook));
+    if (!e) e = pgrc_buf_unpooled(v, v->d_flag, 64);
     if (!e && (hipMemcpyAsync(v->d_tab.p, &v->tab, sizeof(VlTables), hipMemcpyHostToDevice, v->stream) != hipSuccess ||
                hipMemcpyAsync(v->d_book.p, &v->book, sizeof(VlBook), hipMemcpyHostToDevice, v->stream) != hipSuccess ||
                hipStreamSynchronize(v->stream) != hipSuccess))
@@ -516,7 +492,7 @@ int pgrc_varlen_encode(pgrc_varlen *v, const pgrc_varlen_part *parts, uint32_t n
     uint64_t host_bytes = 0;
     for (uint32_t k = 0; k < n_parts; k++)
         if (!parts[k].on_device) host_bytes += parts[k].len;
-    if (host_bytes && (e = vl_buf(v, v->d_src, n))) return e;
+    if (host_bytes && (e = pgrc_buf_unpooled(v, v->d_src, n))) return e;
     VlSrc s{};
     s.n = n;
     uint64_t at = 0;
@@ -527,39 +503,39 @@ int pgrc_varlen_encode(pgrc_varlen *v, const pgrc_varlen_part *parts, uint32_t n
             if (parts[k].on_device) s.p[k] = (const uint8_t *)parts[k].ptr;
             else {
                 s.p[k] = (const uint8_t *)v->d_src.p + at;
-                VL_TRY(v, hipMemcpyAsync((uint8_t *)v->d_src.p + at, parts[k].ptr, len, hipMemcpyHostToDevice, st));
+                HIP_TRY(v, hipMemcpyAsync((uint8_t *)v->d_src.p + at, parts[k].ptr, len, hipMemcpyHostToDevice, st));
             }
         }
         at += len;
         s.end[k] = at;
     }
     if (host_bytes) {
-        VL_TRY(v, hipStreamSynchronize(st));
+        HIP_TRY(v, hipStreamSynchronize(st));
         v->tm.ms_upload = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     const uint64_t nb = (n + VL_TILE - 1) / VL_TILE;
     if (nb > 0x7FFFFFFFull) return vl_fail(v, PGRC_E_PARAM, "encode: the text is too long");
-    if ((e = vl_buf(v, v->d_bmap, nb * 4)) || (e = vl_buf(v, v->d_bent, nb * 4)) || (e = vl_buf(v, v->d_bcnt, nb * 8)) ||
-        (e = vl_buf(v, v->d_bbase, (nb + 1) * 8)) || (e = vl_buf(v, v->d_fold, sco_scratch_elems(nb) * 8)))
+    if ((e = pgrc_buf_unpooled(v, v->d_bmap, nb * 4)) || (e = pgrc_buf_unpooled(v, v->d_bent, nb * 4)) || (e = pgrc_buf_unpooled(v, v->d_bcnt, nb * 8)) ||
+        (e = pgrc_buf_unpooled(v, v->d_bbase, (nb + 1) * 8)) || (e = pgrc_buf_unpooled(v, v->d_fold, sco_scratch_elems(nb) * 8)))
         return e;
     uint32_t *bmap = (uint32_t *)v->d_bmap.p, *bent = (uint32_t *)v->d_bent.p, *d_bad = (uint32_t *)v->d_flag.p;
     uint64_t *bcnt = (uint64_t *)v->d_bcnt.p, *bbase = (uint64_t *)v->d_bbase.p;
     const VlTables *tab = (const VlTables *)v->d_tab.p;
-    VL_TRY(v, hipMemsetAsync(d_bad, 0, 4, st));
-    VL_TRY(v, hipEventRecord(v->ev[0], st));
+    HIP_TRY(v, hipMemsetAsync(d_bad, 0, 4, st));
+    HIP_TRY(v, hipEventRecord(v->ev[0], st));
     hipLaunchKernelGGL(k_vl_maps, dim3((uint32_t)nb), dim3(VL_TPB), 0, st, s, tab, bmap, bcnt, d_bad);
-    VL_TRY(v, hipGetLastError());
-    VL_TRY(v, hipEventRecord(v->ev[1], st));
-    VL_TRY(v, (sco_device_scan<false, false>(st, ScoLoad<uint32_t, uint32_t, ScoIdentity>{bmap, ScoIdentity{}}, nb, ScoMap4{}, (uint32_t)SCO_MAP4_IDENTITY,
+    HIP_TRY(v, hipGetLastError());
+    HIP_TRY(v, hipEventRecord(v->ev[1], st));
+    HIP_TRY(v, (sco_device_scan<false, false>(st, ScoLoad<uint32_t, uint32_t, ScoIdentity>{bmap, ScoIdentity{}}, nb, ScoMap4{}, (uint32_t)SCO_MAP4_IDENTITY,
                                              (uint32_t)SCO_MAP4_IDENTITY, ScoStore<uint32_t>{bent}, (uint32_t *)v->d_fold.p)));
-    VL_TRY(v, (sco_device_scan<false, true>(st, VlBlockCount{bcnt, bent}, nb, ScoPlus{}, (uint64_t)0, (uint64_t)0, ScoStore<uint64_t>{bbase},
+    HIP_TRY(v, (sco_device_scan<false, true>(st, VlBlockCount{bcnt, bent}, nb, ScoPlus{}, (uint64_t)0, (uint64_t)0, ScoStore<uint64_t>{bbase},
                                             (uint64_t *)v->d_fold.p)));
     uint64_t total = 0;
     uint32_t bad = 0;
-    VL_TRY(v, hipMemcpyAsync(&total, bbase + nb, 8, hipMemcpyDeviceToHost, st));
-    VL_TRY(v, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
-    VL_TRY(v, hipEventRecord(v->ev[2], st));
-    VL_TRY(v, hipStreamSynchronize(st));
+    HIP_TRY(v, hipMemcpyAsync(&total, bbase + nb, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(v, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(v, hipEventRecord(v->ev[2], st));
+    HIP_TRY(v, hipStreamSynchronize(st));
     if (bad) return vl_fail(v, PGRC_E_SYMBOL, "encode: the text holds a byte that is no symbol of the book");
     if (total > n) return vl_fail(v, PGRC_E_DEVICE, "encode: inconsistent counts");
     *coded_len = total;
@@ -567,17 +543,17 @@ int pgrc_varlen_encode(pgrc_varlen *v, const pgrc_varlen_part *parts, uint32_t n
     if (total > out_cap) return vl_fail(v, PGRC_E_PARAM, "encode: out_cap " + std::to_string(out_cap) + " is below the coded length " + std::to_string(total));
     uint8_t *d_out = (uint8_t *)out;
     if (!out_on_device) {
-        if ((e = vl_buf(v, v->d_coded, total))) return e;
+        if ((e = pgrc_buf_unpooled(v, v->d_coded, total))) return e;
         d_out = (uint8_t *)v->d_coded.p;
     }
     hipLaunchKernelGGL(k_vl_emit, dim3((uint32_t)nb), dim3(VL_TPB), 0, st, s, tab, (const uint32_t *)bent, (const uint64_t *)bbase, d_out, total);
-    VL_TRY(v, hipGetLastError());
-    VL_TRY(v, hipEventRecord(v->ev[3], st));
-    VL_TRY(v, hipStreamSynchronize(st));
+    HIP_TRY(v, hipGetLastError());
+    HIP_TRY(v, hipEventRecord(v->ev[3], st));
+    HIP_TRY(v, hipStreamSynchronize(st));
     if (!out_on_device) {
         const auto t1 = std::chrono::steady_clock::now();
-        VL_TRY(v, hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, st));
-        VL_TRY(v, hipStreamSynchronize(st));
+        HIP_TRY(v, hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, st));
+        HIP_TRY(v, hipStreamSynchronize(st));
         v->tm.ms_download = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
     }
     (void)hipEventElapsedTime(&v->tm.ms_maps, v->ev[0], v->ev[1]);
@@ -608,44 +584,44 @@ int pgrc_varlen_decode(pgrc_varlen *v, const void *coded, uint64_t coded_len, in
     int e;
     const uint8_t *d_coded = (const uint8_t *)coded;
     if (!coded_on_device) {
-        if ((e = vl_buf(v, v->d_coded, m))) return e;
-        VL_TRY(v, hipMemcpyAsync(v->d_coded.p, coded, m, hipMemcpyHostToDevice, st));
-        VL_TRY(v, hipStreamSynchronize(st));
+        if ((e = pgrc_buf_unpooled(v, v->d_coded, m))) return e;
+        HIP_TRY(v, hipMemcpyAsync(v->d_coded.p, coded, m, hipMemcpyHostToDevice, st));
+        HIP_TRY(v, hipStreamSynchronize(st));
         d_coded = (const uint8_t *)v->d_coded.p;
         v->tm.ms_upload = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     const uint64_t nb = (m + VL_DTILE - 1) / VL_DTILE;
     if (nb > 0x7FFFFFFFull) return vl_fail(v, PGRC_E_PARAM, "decode: the coded stream is too long");
-    if ((e = vl_buf(v, v->d_bsum, nb * 4)) || (e = vl_buf(v, v->d_bbase, (nb + 1) * 8)) || (e = vl_buf(v, v->d_fold, sco_scratch_elems(nb) * 8))) return e;
+    if ((e = pgrc_buf_unpooled(v, v->d_bsum, nb * 4)) || (e = pgrc_buf_unpooled(v, v->d_bbase, (nb + 1) * 8)) || (e = pgrc_buf_unpooled(v, v->d_fold, sco_scratch_elems(nb) * 8))) return e;
     uint32_t *bsum = (uint32_t *)v->d_bsum.p;
     uint64_t *bbase = (uint64_t *)v->d_bbase.p;
     const VlBook *book = (const VlBook *)v->d_book.p;
-    VL_TRY(v, hipEventRecord(v->ev[0], st));
+    HIP_TRY(v, hipEventRecord(v->ev[0], st));
     hipLaunchKernelGGL(k_vl_declen, dim3((uint32_t)nb), dim3(VL_TPB), 0, st, d_coded, m, book, bsum);
-    VL_TRY(v, hipGetLastError());
-    VL_TRY(v, hipEventRecord(v->ev[1], st));
-    VL_TRY(v, (sco_sum_u64<false>(st, (const uint32_t *)bsum, nb, bbase, (uint64_t *)v->d_fold.p)));
+    HIP_TRY(v, hipGetLastError());
+    HIP_TRY(v, hipEventRecord(v->ev[1], st));
+    HIP_TRY(v, (sco_sum_u64<false>(st, (const uint32_t *)bsum, nb, bbase, (uint64_t *)v->d_fold.p)));
     uint64_t total = 0;
-    VL_TRY(v, hipMemcpyAsync(&total, bbase + nb, 8, hipMemcpyDeviceToHost, st));
-    VL_TRY(v, hipEventRecord(v->ev[2], st));
-    VL_TRY(v, hipStreamSynchronize(st));
+    HIP_TRY(v, hipMemcpyAsync(&total, bbase + nb, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(v, hipEventRecord(v->ev[2], st));
+    HIP_TRY(v, hipStreamSynchronize(st));
     v->tm.symbols = total;
     if (total != expected_len)
         return vl_fail(v, PGRC_E_PARAM, "decode: unexpected decoded length " + std::to_string(total) + " (expected " + std::to_string(expected_len) + ")");
     if (total) {
         uint8_t *d_out = (uint8_t *)out;
         if (!out_on_device) {
-            if ((e = vl_buf(v, v->d_text, total))) return e;
+            if ((e = pgrc_buf_unpooled(v, v->d_text, total))) return e;
             d_out = (uint8_t *)v->d_text.p;
         }
         hipLaunchKernelGGL(k_vl_expand, dim3((uint32_t)nb), dim3(VL_TPB), 0, st, d_coded, m, book, (const uint64_t *)bbase, d_out, total);
-        VL_TRY(v, hipGetLastError());
-        VL_TRY(v, hipEventRecord(v->ev[3], st));
-        VL_TRY(v, hipStreamSynchronize(st));
+        HIP_TRY(v, hipGetLastError());
+        HIP_TRY(v, hipEventRecord(v->ev[3], st));
+        HIP_TRY(v, hipStreamSynchronize(st));
         if (!out_on_device) {
             const auto t1 = std::chrono::steady_clock::now();
-            VL_TRY(v, hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, st));
-            VL_TRY(v, hipStreamSynchronize(st));
+            HIP_TRY(v, hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, st));
+            HIP_TRY(v, hipStreamSynchronize(st));
             v->tm.ms_download = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
         }
         (void)hipEventElapsedTime(&v->tm.ms_emit, v->ev[2], v->ev[3]);

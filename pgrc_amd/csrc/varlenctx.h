@@ -26,9 +26,7 @@ struct VlBook {
 };
 static_assert(sizeof(VlBook) % 16 == 0, "copied to LDS as uint4");
 
-struct pgrc_varlen {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct pgrc_varlen : PgrcDev {
     hipEvent_t ev[4]{};
     uint32_t ncodes = 0;
     VlTables tab{};
@@ -36,5 +34,4 @@ struct pgrc_varlen {
     VlBook book{};
     DevBuf d_tab, d_book, d_src, d_coded, d_text, d_bmap, d_bent, d_bcnt, d_bsum, d_bbase, d_fold, d_flag;
     pgrc_varlen_times tm{};
-    std::string err;
 };

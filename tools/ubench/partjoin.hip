@@ -17,9 +17,6 @@
 #include "ctx.h"
 #include "devutil.h"
 
-int pgrc_radix_sort_u64(pgrc_match_ctx *c, uint64_t *d_a, uint64_t *d_b, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, DevBuf &scratch,
-                        uint64_t **sorted);
-
 #define UB_IDBITS 34u
 
 __device__ __forceinline__ uint64_t ub_mix(uint64_t z) {
@@ -87,7 +84,7 @@ __global__ void __launch_bounds__(1024) k_ub_join(const uint64_t *__restrict__ r
 
 extern "C" int pgrc_match_ubench_partjoin(uint64_t n, uint32_t hbits, float ms[4], uint64_t sums[2]) {
     if (!ms || !sums || hbits < UB_CB + 2 || hbits > 30 || n < 1 || n >= (1ull << 32) - 8192) return PGRC_E_PARAM;
-    pgrc_match_ctx c;
+    PgrcDev c;
     DevBuf head, ra, rb, scratch, sum, pst;
     auto done = [&](int e) { for (DevBuf *b : {&head, &ra, &rb, &scratch, &sum, &pst}) pgrc_buf_free(*b); return e; };
     const uint64_t hs = 1ull << hbits;
