@@ -13,11 +13,13 @@
  * ptr[misOff[i]] = code2mismatch(ptr[misOff[i]], misSymCode[i]) (helper.cpp:353-356) under the symbol order of the
  * archive header (pgrc-decoder.cpp:731-735).  Entries are numbered HQ, then LQ, then N (rlIdx).
  *
- * Here the host hands over the joined text and the reassembled per-entry streams of every list (entropy decoding and
- * archive parsing stay with the caller); positions and mismatch list starts are prefix scans on the device, every row
+ * Here the host hands over the joined text and the streams of every list (entropy decoding and archive parsing stay with
+ * the caller) -- either reassembled per entry (pgrc_decode_add_list) or, since pgrc_decode_add_list_archive, as the archive
+ * holds them: the reassembly of the mismatch streams no longer has to stay with the caller; positions and mismatch list starts are prefix scans on the device, every row
  * is an independent job of a row kernel that assembles tiles of rows in LDS, and rows come back to the host in chunks
- * copied down while the next chunk is made.  Two more of the decoder's stages follow further down: the restore of the matched
- * pseudogenomes and the pair-position coding of the order-preserving paired mode (with its encoder).
+ * copied down while the next chunk is made.  More of the decoder's stages follow further down: the restore of the matched
+ * pseudogenomes, the pair-position coding of the order-preserving paired mode (with its encoder), the encoder's pair-order
+ * coding and the archive form of a list's mismatch streams (both directions).
  *
  * Same conventions as pgrc_match.h: 0 = success, PGRC_E_* otherwise; host buffers stay the caller's (nothing is
  * borrowed beyond a call); no CPU fallback -- without a HIP device every call fails.
@@ -303,6 +305,78 @@ typedef struct {
 } pgrc_pairorder_timing;
 /* of the context's last successful pgrc_pairorder_encode */
 int pgrc_pairorder_get_timing(pgrc_decode_ctx *ctx, pgrc_pairorder_timing *out);
+
+/* ---- The archive form of a reads list's mismatch streams (SeparatedPseudoGenomeOutputBuilder::compressedBuild,
+ * SeparatedPseudoGenomePersistence.cpp:905-952, and the loader's inverse, ExtendedReadsListWithConstantAccessOption::
+ * loadConstantAccessExtendedReadsList, SeparatedExtendedReadsList.cpp:210-294).  The builder's
+ * writeReadEntry appends one count per entry, one context code (actual << 4) + mismatch per mismatch and one rev-coded
+ * offset per mismatch (pgrc_export_streams); the archive holds them reshaped:
+ *   zero flags   toStringAndSeparateZeros (:801-813): zero_flags[i] = (mis_cnt[i] == 0), and the non-zero counts in entry
+ *                order
+ *   symbols      reorderingSymbolsExclusiveMismatchEncoding (:1115-1138): the mismatch VALUES (low nibbles) are counted,
+ *                the five values ordered by descending count (ties keep A C G T N), bases_order = the symbols in that order,
+ *                and every code becomes rev[mismatch] - (rev[mismatch] > rev[actual]), rev = the place of a value in it
+ *   offsets      compressRlMisRevOffDest (:823-903): an entry with count c sends its c bytes, in stream order, to
+ *                destination c (1 <= c <= 254).  limit = the largest non-empty destination (0 without mismatches); the
+ *                props bytes are [limit, 1, 2, ..., limit - 1].  With CODER_LEVEL_FAST the props are [1] and destination 1
+ *                is the unsplit stream.  (separateFirstOffsetMode and transposeMode are off in every call of the reference.)
+ * All of it is flags, prefix sums, a five-bin histogram and ONE stable split of the entries by their count: a count matrix
+ * (count, tile) over tiles of PGRC_LIST_ARCHIVE_TILE entries, its scan, and ballot ranks inside a tile.  No merged stream is
+ * made on the host in either direction.
+ *
+ * Limits: offsets of ONE byte (the loader reads them into vector<uint8_t>), n_entries < 2^32 and n_mismatches < 2^32
+ * (PGRC_E_PARAM otherwise).  The calls work on a decode context (its stream, staging buffers and error string). */
+#define PGRC_LIST_ARCHIVE_TILE 8192u    /* entries of one tile of the split */
+typedef struct {
+    uint32_t struct_size;           /* sizeof(pgrc_list_archive_streams) */
+    uint32_t props_len;             /* bytes of props: max(1, limit) */
+    uint64_t n_entries, n_mismatches, n_nonzero;
+    const uint8_t *zero_flags;      /* n_entries; the START OF THE BLOCK of pgrc_list_archive_encode */
+    const uint8_t *nonzero_cnt;     /* n_nonzero */
+    const uint8_t *mis_sym;         /* n_mismatches exclusive codes (0 .. 3; 4 only where actual == mismatch == the last value) */
+    char bases_order[5];            /* the five symbols by descending count of their value */
+    uint32_t n_dests;               /* limit: props[0] */
+    const uint8_t *props;           /* [limit, 1, ..., limit - 1], or [0] */
+    const uint8_t *dest[255];       /* index 1 .. n_dests: the offsets of the entries with that count; [0] unused */
+    uint64_t dest_len[255];         /* bytes of dest[c]: c * (entries with count c); n_mismatches for the one stream of [1] */
+    void *block;                    /* encode: the one page-locked block all streams lie in (= zero_flags) */
+} pgrc_list_archive_streams;
+
+/* compressedBuild's reshaping of in->mis_cnt, in->mis_sym and in->mis_rev_off (in->off_width must be 1).  fast_level != 0:
+ * CODER_LEVEL_FAST.  On success *out describes the streams in ONE block of page-locked host memory that the library
+ * allocated, filled by one copy from the device; the destinations lie one behind the other in it; pgrc_list_archive_free
+ * gives it back.  PGRC_E_PARAM: off_width != 1, 2^32 entries or mismatches or more, a NULL stream with a non-zero count,
+ * n_mismatches != the sum of the counts, a nibble of a code above 4, a count of 255 at the normal level (it indexes past
+ * the reference's 255-element map).  After any failure *out is cleared and the context stays usable. */
+int pgrc_list_archive_encode(pgrc_decode_ctx *ctx, const pgrc_export_streams *in, int32_t fast_level, pgrc_list_archive_streams *out);
+void pgrc_list_archive_free(pgrc_list_archive_streams *streams);   /* of pgrc_list_archive_encode; clears the struct */
+
+/* pgrc_decode_add_list with the list's mismatches still in the archive's form: `list` carries text_base, n_entries, off /
+ * pos and rev_comp as for pgrc_decode_add_list and its mis_* pointers must be NULL; `s` goes up as it is, the per-entry
+ * tables are rebuilt on the device (counts from the flags, every entry's offsets gathered from the source of its count at
+ * c * (entries before it with count c) and turned into forward offsets on the way) and the context is left as
+ * pgrc_decode_add_list leaves it with the reassembled streams (mis_sym_form 0, rev-coded offsets, s->bases_order).
+ * With limit = 1 every entry takes its bytes from the one stream at its mismatch-list start, whatever its count (the
+ * loader maps every count to the last source).  Refused with PGRC_E_PARAM before any table is kept: entries without a zero
+ * flag != n_nonzero, a count above limit (limit != 1), props other than the ones the reference writes (limit <= 254,
+ * props[m] == m), dest_len[c] != c * (entries with count c), n_mismatches != the sum of the counts, n_entries !=
+ * list->n_entries, and everything pgrc_decode_add_list refuses. */
+int pgrc_decode_add_list_archive(pgrc_decode_ctx *ctx, const pgrc_decode_list *list, const pgrc_list_archive_streams *s);
+
+typedef struct {
+    uint32_t struct_size;           /* sizeof(pgrc_list_archive_timing) */
+    int32_t encode;                 /* 1 = the last call was pgrc_list_archive_encode, 0 = pgrc_decode_add_list_archive */
+    float ms_upload;                /* host wall time until the streams were queued for the device */
+    float ms_flags_device;          /* device time: the flag scan, zero flags / counts, the mismatch-list starts */
+    float ms_symbols_device;        /* device time: histogram and recode (encode) / the check of the codes (decode) */
+    float ms_split_device;          /* device time: count matrix, its scan, scatter (encode) / gather with the conversion (decode) */
+    float ms_download;              /* host wall time: the page-locked block and the copy down (encode) */
+    float ms_call;                  /* host wall time of the whole call (decode: positions and RC flags of the list included) */
+    uint64_t bytes_up, bytes_down;
+    uint64_t n_nonzero, limit;
+} pgrc_list_archive_timing;
+/* of the context's last successful pgrc_list_archive_encode or pgrc_decode_add_list_archive */
+int pgrc_list_archive_get_timing(pgrc_decode_ctx *ctx, pgrc_list_archive_timing *out);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,19 @@ class ExportStreams(C.Structure):   # pgrc_export_streams
                 ("mis_sym", C.POINTER(C.c_uint8)), ("mis_rev_off", C.POINTER(C.c_uint8)), ("last_pos", C.c_uint64)]
 
 
+class ListArchiveStreams(C.Structure):   # pgrc_list_archive_streams (include/pgrc_decode.h)
+    _fields_ = [("struct_size", C.c_uint32), ("props_len", C.c_uint32), ("n_entries", C.c_uint64), ("n_mismatches", C.c_uint64),
+                ("n_nonzero", C.c_uint64), ("zero_flags", C.c_void_p), ("nonzero_cnt", C.c_void_p), ("mis_sym", C.c_void_p),
+                ("bases_order", C.c_char * 5), ("n_dests", C.c_uint32), ("props", C.c_void_p), ("dest", C.c_void_p * 255),
+                ("dest_len", C.c_uint64 * 255), ("block", C.c_void_p)]
+
+
+class ListArchiveTiming(C.Structure):    # pgrc_list_archive_timing
+    _fields_ = [("struct_size", C.c_uint32), ("encode", C.c_int32), ("ms_upload", C.c_float), ("ms_flags_device", C.c_float),
+                ("ms_symbols_device", C.c_float), ("ms_split_device", C.c_float), ("ms_download", C.c_float), ("ms_call", C.c_float),
+                ("bytes_up", C.c_uint64), ("bytes_down", C.c_uint64), ("n_nonzero", C.c_uint64), ("limit", C.c_uint64)]
+
+
 class ExportPgOrderArgs(C.Structure):   # pgrc_export_pg_order_args
     _fields_ = [("order", C.c_void_p), ("n_matched", C.c_uint64), ("read_org_idx", C.c_void_p), ("list_off", C.c_void_p),
                 ("list_org_idx", C.c_void_p), ("list_rev_comp", C.c_void_p), ("list_count", C.c_uint64),

@@ -1,6 +1,6 @@
 // decctx.h -- the decode context of include/pgrc_decode.h and the helpers its sources share: decode.hip (the reads
-// rebuild), restore.hip (the restore of the matched pseudogenomes), pairpos.hip (the pair positions of the paired ORD mode)
-// and pairorder.hip (the pair order of the paired non-ORD mode).
+// rebuild), restore.hip (the restore of the matched pseudogenomes), pairpos.hip (the pair positions of the paired ORD mode),
+// pairorder.hip (the pair order of the paired non-ORD mode) and listarchive.hip (the archive form of a list's mismatch streams).
 #pragma once
 
 #include <string.h>
@@ -15,6 +15,13 @@
 #define DEC_TPB 256
 #define DEC_TEXT_PAD 64         // zero bytes after the text: aligned 16-byte loads past a window's end stay inside
 #define DEC_STAGE_BYTES (64ull << 20)
+
+// error flags of the device checks (the word at pgrc_decode_ctx::flag)
+#define DEC_F_WINDOW 1u         // a window reaches past the text end
+#define DEC_F_INDEX 2u          // an rlIdx / rank out of range
+#define DEC_F_MISOFF 4u         // a mismatch offset outside the read
+#define DEC_F_MISSYM 8u         // a mismatch code outside its form's range
+#define DEC_F_NOPOS 16u         // a row needs the positions of a list that has none
 
 struct pgrc_decode_ctx : PgrcDev {
     uint32_t L = 0;
@@ -58,6 +65,12 @@ struct pgrc_decode_ctx : PgrcDev {
     hipEvent_t po_ev[11]{};
     bool have_po_timing = false;
     pgrc_pairorder_timing potm{};
+    // the archive form of the mismatch streams (listarchive.hip): the uploaded streams, the flag scan, the counts (decode),
+    // the mismatch-list starts (encode), the count matrix and its scan scratch, the per-count words, the device-side block
+    DevBuf la_in, la_inc, la_cnt, la_mcum, la_mat, la_fold, la_small, la_out;
+    hipEvent_t la_ev[8]{};
+    bool have_la_timing = false;
+    pgrc_list_archive_timing latm{};
 };
 
 // pairpos.hip: the file-major positions of `s` as n_total u64 at d_out (device, on d->stream; synchronised on return);
@@ -66,6 +79,12 @@ int pgrc_pairpos_decode_device(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s
 int pgrc_pairpos_check_streams(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s);   // the checks that need no device (PGRC_E_PARAM)
 void pgrc_pairpos_release(pgrc_decode_ctx *d);     // the buffers and events above (pgrc_decode_destroy)
 void pgrc_pairorder_release(pgrc_decode_ctx *d);   // pairorder.hip: its buffers and events (pgrc_decode_destroy)
+void pgrc_la_release(pgrc_decode_ctx *d);          // listarchive.hip: its buffers and events (pgrc_decode_destroy)
+// listarchive.hip: the mismatch tables of list `l` (mcum, moff, msym, nmis) from the archive-form streams `s`, on d->stream;
+// device-side findings (DEC_F_MISOFF, DEC_F_MISSYM) go to d->flag, which the caller reads (pgrc_decode_add_list_archive)
+int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list_archive_streams *s);
+// decode.hip: pgrc_decode_add_list, with the mismatches from `arch` when it is given
+int pgrc_dec_add_list(pgrc_decode_ctx *d, const pgrc_decode_list *a, const pgrc_list_archive_streams *arch);
 
 static int dec_fail(pgrc_decode_ctx *d, int code, const std::string &msg) {
     d->err = msg;

@@ -27,13 +27,6 @@
 #define DEC_TILE_CAP 12288      // R*(L+1) < DEC_TILE_TARGET + 16*(L+1) <= 12288
 #define DEC_CHUNK_BYTES (64ull << 20)
 
-// error flags of the device checks
-#define DEC_F_WINDOW 1u         // a window reaches past the text end
-#define DEC_F_INDEX 2u          // an rlIdx / rank out of range
-#define DEC_F_MISOFF 4u         // a mismatch offset outside the read
-#define DEC_F_MISSYM 8u         // a mismatch code outside its form's range
-#define DEC_F_NOPOS 16u         // a row needs the positions of a list that has none
-
 struct DecList {                // device view of one list (kernel argument)
     const uint64_t *pos;        // joined-text positions, NULL = none
     const uint8_t *rc;          // NULL = revComp disabled
@@ -357,6 +350,7 @@ void pgrc_decode_destroy(pgrc_decode_ctx *d) {
     if (d->ev_b) (void)hipEventDestroy(d->ev_b);
     pgrc_pairpos_release(d);
     pgrc_pairorder_release(d);
+    pgrc_la_release(d);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     delete d;
@@ -386,19 +380,24 @@ int pgrc_decode_set_text(pgrc_decode_ctx *d, const char *joined, uint64_t len) {
     return PGRC_OK;
 }
 
-int pgrc_decode_add_list(pgrc_decode_ctx *d, const pgrc_decode_list *a) {
+int pgrc_decode_add_list(pgrc_decode_ctx *d, const pgrc_decode_list *a) { return pgrc_dec_add_list(d, a, nullptr); }
+
+}   // extern "C"
+
+int pgrc_dec_add_list(pgrc_decode_ctx *d, const pgrc_decode_list *a, const pgrc_list_archive_streams *arch) {
     if (!d) return PGRC_E_PARAM;
     if (!a || a->struct_size != sizeof(pgrc_decode_list)) return dec_fail(d, PGRC_E_PARAM, "list is NULL or struct_size is not sizeof(pgrc_decode_list)");
     if (!d->have_text) return dec_fail(d, PGRC_E_STATE, "add_list before set_text");
     if (d->nl == 3) return dec_fail(d, PGRC_E_STATE, "three lists (HQ, LQ, N) are already added");
-    if (d->nl > 0 && (a->rev_comp || a->mis_cnt)) return dec_fail(d, PGRC_E_PARAM, "the LQ and N lists carry no RC flags and no mismatches");
+    if (arch && (a->mis_cnt || a->mis_sym || a->mis_off)) return dec_fail(d, PGRC_E_PARAM, "add_list_archive: the list's mis_* pointers must be NULL");
+    if (d->nl > 0 && (a->rev_comp || a->mis_cnt || arch)) return dec_fail(d, PGRC_E_PARAM, "the LQ and N lists carry no RC flags and no mismatches");
     if (a->off && a->off_width != 1 && a->off_width != 2) return dec_fail(d, PGRC_E_PARAM, "off_width must be 1 or 2");
     const uint32_t mw = a->mis_off_width ? a->mis_off_width : (a->off ? a->off_width : 1);
     if (a->mis_cnt && (mw != 1 && mw != 2)) return dec_fail(d, PGRC_E_PARAM, "mis_off_width must be 1 or 2");
     if (a->mis_sym_form != 0 && a->mis_sym_form != 1) return dec_fail(d, PGRC_E_PARAM, "mis_sym_form must be 0 or 1");
     if (a->text_base > d->text_len) return dec_fail(d, PGRC_E_PARAM, "text_base beyond the text");
-    const char *order = a->bases_order ? a->bases_order : "ACGTN";
-    if (a->mis_cnt && !a->mis_sym_form) {
+    const char *order = arch ? arch->bases_order : a->bases_order ? a->bases_order : "ACGTN";
+    if (arch || (a->mis_cnt && !a->mis_sym_form)) {
         bool seen[256] = {};
         for (int v = 0; v < 5; v++) {
             if (seen[(uint8_t)order[v]]) return dec_fail(d, PGRC_E_PARAM, "bases_order repeats a symbol");
@@ -412,7 +411,7 @@ int pgrc_decode_add_list(pgrc_decode_ctx *d, const pgrc_decode_list *a) {
     l.nmis = 0;
     l.n = n;
     l.text_base = a->text_base;
-    l.form = (uint32_t)a->mis_sym_form;
+    l.form = arch ? 0u : (uint32_t)a->mis_sym_form;
     memcpy(l.order, order, 5);
     int e;
     if ((e = dec_clear_err(d))) return e;
@@ -469,15 +468,21 @@ int pgrc_decode_add_list(pgrc_decode_ctx *d, const pgrc_decode_list *a) {
                                    (uint8_t *)l.moff.p, (uint8_t *)l.msym.p, (uint32_t *)d->flag.p);
         }
     }
+    if (arch) {
+        l.has_mis = true;
+        if ((e = pgrc_la_tables(d, l, arch))) return e;
+    }
     HIP_TRY(d, hipGetLastError());
     HIP_TRY(d, hipEventRecord(d->ev_b, d->stream));
-    if ((e = dec_check_err(d, "add_list"))) return e;
+    if ((e = dec_check_err(d, arch ? "add_list_archive" : "add_list"))) return e;
     dec_free(l.raw);
     d->tm.ms_lists_device += dec_elapsed(d->ev_a, d->ev_b);
     d->nl++;
     d->have_order = false;
     return PGRC_OK;
 }
+
+extern "C" {
 
 static uint64_t dec_entries(const pgrc_decode_ctx *d) {
     uint64_t t = 0;

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import PgrcMatchError, lib
+from ._lib import ExportStreams, ListArchiveStreams, ListArchiveTiming, PgrcMatchError, lib
 
 _P = C.c_void_p
 
@@ -102,6 +102,10 @@ DECODE_PROTOS = [
     ("pgrc_pairorder_encode", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.c_int32, C.POINTER(PairOrderStreams)]),
     ("pgrc_pairorder_free", None, [C.POINTER(PairOrderStreams)]),
     ("pgrc_pairorder_get_timing", C.c_int, [_P, C.POINTER(PairOrderTiming)]),
+    ("pgrc_list_archive_encode", C.c_int, [_P, C.POINTER(ExportStreams), C.c_int32, C.POINTER(ListArchiveStreams)]),
+    ("pgrc_list_archive_free", None, [C.POINTER(ListArchiveStreams)]),
+    ("pgrc_decode_add_list_archive", C.c_int, [_P, C.POINTER(DecodeList), C.POINTER(ListArchiveStreams)]),
+    ("pgrc_list_archive_get_timing", C.c_int, [_P, C.POINTER(ListArchiveTiming)]),
 ]
 for _name, _res, _args in DECODE_PROTOS:
     _fn = getattr(lib, _name)
@@ -159,6 +163,45 @@ def _pairpos_struct(streams: dict):
 PAIRORDER_STREAMS = (("off8_flag", np.uint8), ("off_value", np.uint8), ("delta8_flag", np.uint8), ("delta_value", np.int8),
                      ("full_offset", np.uint32), ("pair_base_org_idx", np.uint32), ("off_base_file_flag", np.uint8),
                      ("nonoff_base_file_flag", np.uint8), ("rev", np.uint32))
+
+
+PGRC_LIST_ARCHIVE_TILE = 8192       # entries of one tile of the split (include/pgrc_decode.h)
+
+
+def _u8ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8)) if a.size else None
+
+
+def _export_struct(mis_cnt, mis_sym, mis_rev_off):
+    """the three mismatch streams of a pgrc_export_streams (the other streams stay NULL) -> (struct, the arrays it points into)"""
+    keep = [_bytes(mis_cnt), _bytes(mis_sym), np.ascontiguousarray(mis_rev_off)]
+    x = ExportStreams()
+    x.n_entries, x.n_mismatches, x.off_width = keep[0].size, keep[1].size, keep[2].dtype.itemsize
+    keep[2] = keep[2].view(np.uint8).reshape(-1)
+    x.mis_cnt, x.mis_sym, x.mis_rev_off = _u8ptr(keep[0]), _u8ptr(keep[1]), _u8ptr(keep[2])
+    return x, keep
+
+
+def _list_archive_struct(st: dict):
+    """the dict list_archive_encode returns as a pgrc_list_archive_streams; the counts are the arrays' sizes unless the dict
+    names them (n_entries, n_mismatches, n_nonzero, n_dests, props_len, dest_len).  -> (struct, the arrays it points into)"""
+    s = ListArchiveStreams()
+    s.struct_size = C.sizeof(ListArchiveStreams)
+    keep = {k: _bytes(st[k]) for k in ("zero_flags", "nonzero_cnt", "mis_sym", "props")}
+    for k, a in keep.items():
+        setattr(s, k, _ptr(a) if a.size else None)
+    s.n_entries = int(st.get("n_entries", keep["zero_flags"].size))
+    s.n_mismatches = int(st.get("n_mismatches", keep["mis_sym"].size))
+    s.n_nonzero = int(st.get("n_nonzero", keep["nonzero_cnt"].size))
+    s.props_len = int(st.get("props_len", keep["props"].size))
+    s.bases_order = bytes(st["bases_order"])
+    dests = [_bytes(a) for a in st["dests"]]
+    s.n_dests = int(st.get("n_dests", len(dests) - 1))
+    lens = st.get("dest_len", [a.size for a in dests])
+    for c in range(1, min(len(dests), 255)):
+        s.dest[c] = dests[c].ctypes.data if dests[c].size else None
+        s.dest_len[c] = int(lens[c])
+    return s, (keep, dests)
 
 
 class PgRCDecoder:
@@ -377,6 +420,57 @@ class PgRCDecoder:
         t = PairOrderTiming()
         t.struct_size = C.sizeof(PairOrderTiming)
         self._ck(lib.pgrc_pairorder_get_timing(self._h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_ if k != "struct_size"}
+
+    def list_archive_encode(self, mis_cnt, mis_sym, mis_rev_off, fast_level: bool = False) -> dict:
+        """SeparatedPseudoGenomeOutputBuilder::compressedBuild's reshaping of a list's mismatch streams (:905-952) on the
+        device: counts, context codes and rev-coded offsets as pgrc_export_streams holds them -> zero_flags, nonzero_cnt,
+        mis_sym (exclusive codes), bases_order, props and dests (a list: dests[c] the offsets of the entries with c
+        mismatches, [0] empty), all copies"""
+        x, keep = _export_struct(mis_cnt, mis_sym, mis_rev_off)
+        s = ListArchiveStreams()
+        self._ck(lib.pgrc_list_archive_encode(self._h, C.byref(x), int(bool(fast_level)), C.byref(s)))
+        try:
+            def take(p, n):
+                return np.frombuffer((C.c_uint8 * n).from_address(p), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+            out = {"n_entries": int(s.n_entries), "n_mismatches": int(s.n_mismatches), "n_nonzero": int(s.n_nonzero),
+                   "zero_flags": take(s.zero_flags, int(s.n_entries)), "nonzero_cnt": take(s.nonzero_cnt, int(s.n_nonzero)),
+                   "mis_sym": take(s.mis_sym, int(s.n_mismatches)), "bases_order": bytes(s.bases_order[:5]),
+                   "props": take(s.props, int(s.props_len)),
+                   "dests": [np.zeros(0, np.uint8)] + [take(s.dest[c], int(s.dest_len[c])) for c in range(1, int(s.n_dests) + 1)],
+                   "one_block": all(s.dest[c] is None or s.block <= s.dest[c] < s.props for c in range(1, int(s.n_dests) + 1))}
+        finally:
+            lib.pgrc_list_archive_free(C.byref(s))
+        return out
+
+    def add_list_archive(self, n_entries: int, streams: dict, text_base: int = 0, off=None, pos=None, rev_comp=None) -> None:
+        """add_list with the list's mismatch streams in the archive's form (a dict as list_archive_encode returns): they go
+        up as they are and the per-entry tables are rebuilt on the device"""
+        a = DecodeList()
+        a.struct_size = C.sizeof(DecodeList)
+        a.text_base = int(text_base)
+        a.n_entries = int(n_entries)
+        keep = []
+        if off is not None:
+            off = np.ascontiguousarray(off)
+            assert off.dtype in (np.uint8, np.uint16) and off.size == n_entries
+            a.off, a.off_width = _ptr(off), off.dtype.itemsize
+            keep.append(off)
+        if pos is not None:
+            pos = _arr(pos, np.uint64)
+            a.pos = _ptr(pos)
+            keep.append(pos)
+        if rev_comp is not None:
+            rev_comp = _arr(rev_comp, np.uint8)
+            a.rev_comp = _ptr(rev_comp)
+            keep.append(rev_comp)
+        s, keep2 = _list_archive_struct(streams)
+        self._ck(lib.pgrc_decode_add_list_archive(self._h, C.byref(a), C.byref(s)))
+
+    def list_archive_timing(self) -> dict:
+        t = ListArchiveTiming()
+        t.struct_size = C.sizeof(ListArchiveTiming)
+        self._ck(lib.pgrc_list_archive_get_timing(self._h, C.byref(t)))
         return {k: getattr(t, k) for k, _ in t._fields_ if k != "struct_size"}
 
     def row_count(self, file: int = 0) -> int:
