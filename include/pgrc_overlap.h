@@ -22,7 +22,9 @@
  * the order is made on the device by a stable sort of the rows, equal reads in ascending number -- a valid outcome of the
  * reference's sort, which differs from any other only in the order inside runs of equal reads.
  *
- * The parallel generator of -t > 1 and avoidCyclesMode are not covered.
+ * The encoder takes ParallelGreedySwipingPackedOverlapGeneratorTemplate instead when it runs with more than one thread on a set of
+ * more than 50 000 reads; its findOverlappingReads is reproduced under PGRC_OVL_RULE_PARALLEL (pgrc_ovl_set_rule below,
+ * DESIGN.md 4.18).  avoidCyclesMode is not covered.
  *
  * Same conventions as pgrc_assemble.h: 0 = success, PGRC_E_* otherwise; struct sizes are checked; host buffers stay the
  * caller's; no CPU fallback -- without a HIP device pgrc_ovl_create fails with PGRC_E_NO_DEVICE.
@@ -87,6 +89,44 @@ int pgrc_ovl_both_sides(pgrc_ovl_ctx *ctx, uint8_t *flags);
  * contexts on one device; no host round trip).  index_mapping: R original indexes or NULL.  Afterwards asm_ctx is as after a
  * pgrc_asm_run of its own (pgrc_asm_get_text, pgrc_asm_packed_device, pgrc_asm_free_result(asm_result), ...). */
 int pgrc_ovl_assemble(pgrc_ovl_ctx *ctx, pgrc_asm_ctx *asm_ctx, const uint32_t *index_mapping, pgrc_asm_result *asm_result);
+
+/* The rule of the sweeps.  PGRC_OVL_RULE_SERIAL (the default) is the generator of one thread.  PGRC_OVL_RULE_PARALLEL is
+ * ParallelGreedySwipingPackedOverlapGeneratorTemplate::findOverlappingReads (ParallelGreedySwipingPackedOverlapPseudoGenomeGenerator.cpp;
+ * avoidCyclesMode = false, where its threads only share out blocks and the result does not depend on their number):
+ *   - a block is the set of strings with one prefix of three symbols; the order of the five groups in the merge starts anew, in
+ *     symbol order, with every block, and a suffix that finds no prefix stays in the list (no drop rule);
+ *   - the sweeps i >= L - 3 pair whole blocks of three, two and one symbols.  The suffixes of sweep L - 3 stand in the order
+ *     of a merge whose compare runs past the reads' end into the packed rows behind them: by the reads x + 1, x + 2, ... that
+ *     follow read x in the set, the groups popped smallest head first though they are not sorted by that key.  Behind the last
+ *     row the reference reads memory that is not its own; here a missing row is below any row, and such compares are counted:
+ *     the result is the reference's only if past_end_compares is 0.  The compares counted are the device's own: every suffix
+ *     against the largest key before it in its group's share of the block, and the searches among the other groups' shares.
+ *     Where no other read equals the last read of the set, only a compare with the last read can run past the end, and the
+ *     device makes one whenever the reference does.  Where one does, two other reads whose followers agree up to the last
+ *     row compare past the end as well, and the device's compares need not include that pair;
+ *   - after the sweeps L - 3 and L - 2 what is left is regrouped by dropping the first symbol, in stable order.
+ * read_len must be at least 4 under this rule (the reference reads symbol 3 of every read).
+ * The two entry points are exported as pgrc_ovlrule_set and pgrc_ovlrule_get_info; pgrc_ovl_set_rule and
+ * pgrc_ovl_get_rule_info are their names in this header. */
+#define PGRC_OVL_RULE_SERIAL 0u
+#define PGRC_OVL_RULE_PARALLEL 1u
+
+typedef struct {
+    uint32_t struct_size;           /* sizeof(pgrc_ovl_rule_info) */
+    uint32_t rule;                  /* the rule of the run */
+    uint32_t blocks;                /* symbols ^ 3 under the parallel rule, 0 under the serial one */
+    uint32_t tail_sweeps;           /* 0 .. 3: the run's sweeps i >= L - 3, which pair whole blocks (0 under the serial rule) */
+    uint64_t follower_compares;     /* compares decided by the rows that follow the two reads (the merge in front of sweep L - 3) */
+    uint64_t past_end_compares;     /* ... of which ran past the last row */
+} pgrc_ovl_rule_info;
+
+/* Sets the rule of the context's later runs.  PGRC_E_PARAM: a NULL context or any other value.  Under the parallel rule
+ * pgrc_ovl_run refuses read_len < 4 with PGRC_E_PARAM and leaves the context usable. */
+int pgrc_ovlrule_set(pgrc_ovl_ctx *ctx, uint32_t rule);
+/* of the context's last successful pgrc_ovl_run; PGRC_E_STATE before one */
+int pgrc_ovlrule_get_info(pgrc_ovl_ctx *ctx, pgrc_ovl_rule_info *out);
+#define pgrc_ovl_set_rule pgrc_ovlrule_set
+#define pgrc_ovl_get_rule_info pgrc_ovlrule_get_info
 
 typedef struct {
     uint32_t struct_size;           /* sizeof(pgrc_ovl_timing) */

@@ -160,6 +160,13 @@ class OvlTiming(C.Structure):   # pgrc_ovl_timing
                 ("bytes_down", C.c_uint64)]
 
 
+class OvlRuleInfo(C.Structure):  # pgrc_ovl_rule_info
+    _fields_ = [("struct_size", C.c_uint32), ("rule", C.c_uint32), ("blocks", C.c_uint32), ("tail_sweeps", C.c_uint32),
+                ("follower_compares", C.c_uint64), ("past_end_compares", C.c_uint64)]
+
+
+OVL_RULES = {"serial": 0, "parallel": 1}     # PGRC_OVL_RULE_*
+
 # every symbol include/pgrc_match.h and include/pgrc_mem.h declare: (name, restype, argtypes)
 _P = C.c_void_p
 _PROTOS = [
@@ -264,6 +271,12 @@ OVL_PROTOS = [
     ("pgrc_ovl_get_sweep_ms", C.c_int, [_P, C.POINTER(C.c_float), C.c_uint32]),
 ]
 
+# include/pgrc_overlap.h, the rule of the sweeps (pgrc_ovl_set_rule and pgrc_ovl_get_rule_info there)
+OVL_RULE_PROTOS = [
+    ("pgrc_ovlrule_set", C.c_int, [_P, C.c_uint32]),
+    ("pgrc_ovlrule_get_info", C.c_int, [_P, C.POINTER(OvlRuleInfo)]),
+]
+
 # include/pgrc_varlen.h
 VARLEN_PROTOS = [
     ("pgrc_varlen_create", C.c_int, [_P, C.c_uint64, C.c_int32, C.POINTER(_P)]),
@@ -279,6 +292,7 @@ EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 VARLEN_EXPORTED_SYMBOLS = [p[0] for p in VARLEN_PROTOS]
 ASM_EXPORTED_SYMBOLS = [p[0] for p in ASM_PROTOS]
 OVL_EXPORTED_SYMBOLS = [p[0] for p in OVL_PROTOS]
+OVL_RULE_EXPORTED_SYMBOLS = [p[0] for p in OVL_RULE_PROTOS]
 
 
 def _preload_torch_hip_runtime() -> None:
@@ -307,7 +321,7 @@ def _load() -> C.CDLL:
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or `make -C pgrc_amd/csrc`.")
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in _PROTOS + ASM_PROTOS + OVL_PROTOS + VARLEN_PROTOS:
+    for name, res, args in _PROTOS + ASM_PROTOS + OVL_PROTOS + OVL_RULE_PROTOS + VARLEN_PROTOS:
         fn = getattr(lib, name)  # AttributeError here = header / library out of sync: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -16,6 +16,10 @@
 //              its own prefix is held back one place), links, and applies the drop rule of :193
 //   compaction the flags of S and P are scanned and both lists are written anew; the next groups are read off the new S
 // The host reads two counters per sweep (what is left of S and of P) and ends when either is empty.
+// PGRC_OVL_RULE_PARALLEL is findOverlappingReads of ParallelGreedySwipingPackedOverlapGeneratorTemplate instead: the
+// groups' order starts anew with every block of three symbols (a reset bit in the same scan), nothing is dropped, the sweeps from
+// L - 3 on pair whole blocks -- the first in the order of a merge by the rows that follow the reads, the other two regrouped
+// by dropping a symbol.  The serial rule's kernels are the same templates with the switches off.
 // Rows are unpacked once to a byte per symbol in rows of 8-byte words, so that eight symbols at any offset are two aligned
 // loads, a shift and one compare.  Integer work bound by random row reads of the searches; no library kernel.
 #include <chrono>
@@ -28,6 +32,7 @@
 #include "pgrc_overlap.h"
 
 #define OV_TPB 256
+#define OV_BLOCK_PREFIX 3u       // blockPrefixLength of the parallel generator
 #define OV_CHUNK 8u             // symbols of one key of the order's sort: 3 bits each, 24 bits a key
 
 // the words of `bad`, in the order the refusals are reported
@@ -37,10 +42,13 @@ struct pgrc_ovl_ctx {
     pgrc_decode_ctx *d = nullptr;       // the stream, the staging buffers, the error string
     DevBuf sort_scratch;
     DevBuf rows, sym, nx, ov, ovout, order, seen, eq, s[2], p[2], base, lens, rk, trans, merged, mk, keep, taken, offs, offp, gs, fold, words, rec[2], prev, flags;
+    DevBuf rnk, lead, cnt;              // the parallel rule: the reads' dense ranks, the prefix maxima of a share, two counters
     hipEvent_t ev[6]{};
     uint64_t R = 0;
     uint32_t L = 0, symbols = 0, rb = 0;
     bool have_run = false;
+    uint32_t rule = PGRC_OVL_RULE_SERIAL;
+    pgrc_ovl_rule_info info{};
     pgrc_ovl_timing tm{};
     std::vector<float> sweep_ms;
 };
@@ -199,6 +207,9 @@ __device__ __forceinline__ uint32_t ov_bound_s(const uint8_t *__restrict__ sym, 
 
 // ranks: per suffix the start of its run in the merged order, the five shares of the run, its rank inside its group's share;
 // the first suffix of a run (rank 0 in the first group that takes part) writes the run's transition at the run's start
+// RESET (the parallel rule): a run that is the first of its block -- no suffix below it in any group shares its first three
+// symbols -- writes "the symbol order, then the run" with the reset bit (scanops.h ScoWeakOrder5Reset)
+template <bool RESET>
 static __global__ void __launch_bounds__(OV_TPB) k_ov_ranks(const uint8_t *__restrict__ sym, uint32_t stride, uint32_t i, uint32_t L, const uint32_t *__restrict__ S,
                                                             uint32_t n, const uint32_t *__restrict__ gs, uint32_t *__restrict__ base, uint32_t *__restrict__ lens,
                                                             uint32_t *__restrict__ rk, uint32_t *__restrict__ trans) {
@@ -206,11 +217,12 @@ static __global__ void __launch_bounds__(OV_TPB) k_ov_ranks(const uint8_t *__res
     if (j >= n) return;
     const uint8_t *x = sym + (uint64_t)(S[j] - 1) * stride;
     const uint32_t g = x[i - 1];
-    uint32_t len[5], start = 0, mine = 0, first = 5;
+    uint32_t len[5], below[5], start = 0, mine = 0, first = 5;
 #pragma unroll
     for (uint32_t h = 0; h < 5u; h++) {
         const uint32_t lo = gs[h], hi = gs[h + 1];
         const uint32_t lb = ov_bound_s<false>(sym, stride, i, L, S, lo, hi, x);
+        below[h] = lb > lo ? lb : 0u;       // (place + 1 of the group's last suffix below the run; 0: none)
         uint32_t ub = lb;
         // most runs have no share in another group: one compare tells
         if (lb < hi && ov_cmp(sym + (uint64_t)(S[lb] - 1) * stride, i, x, i, L - i) == 0) ub = ov_bound_s<true>(sym, stride, i, L, S, lb + 1, hi, x);
@@ -223,15 +235,29 @@ static __global__ void __launch_bounds__(OV_TPB) k_ov_ranks(const uint8_t *__res
     rk[j] = mine;
 #pragma unroll
     for (uint32_t h = 0; h < 5u; h++) lens[(uint64_t)h * n + j] = len[h];
-    if (mine == 0 && first == g && start < n) trans[start] = sco_dense5(len);
+    if (mine == 0 && first == g && start < n) {
+        uint32_t w = sco_dense5(len);
+        if (RESET) {
+            bool head = true;
+#pragma unroll
+            for (uint32_t h = 0; h < 5u; h++)
+                if (below[h] && ov_cmp(sym + (uint64_t)(S[below[h] - 1] - 1) * stride, i, x, i, OV_BLOCK_PREFIX) == 0) head = false;
+            if (head) w = ScoWeakOrder5{}((uint32_t)SCO_WEAK5_SYMBOL_ORDER, w) | SCO_WEAK5_RESET;
+        }
+        trans[start] = w;
+    }
 }
 
 // place: round r of a run emits the r-th suffix of every group with more than r of them, in the order of the groups in front of
 // the run -- before this suffix come min(len_h, r) of every group and one more of every group with len_h > r that stands earlier
+// The parallel rule.  OV_PLACE_RESET: `state` is the scan of the transitions `trans` with resets; a run that starts a block stands
+// behind the symbol order.  OV_PLACE_CONCAT (the last two sweeps): a block is its groups' shares one after the other
+enum { OV_PLACE_SERIAL, OV_PLACE_RESET, OV_PLACE_CONCAT };
+template <int MODE>
 static __global__ void __launch_bounds__(OV_TPB) k_ov_place(const uint32_t *__restrict__ S, uint32_t n, const uint8_t *__restrict__ sym, uint32_t stride, uint32_t i,
                                                             const uint32_t *__restrict__ base, const uint32_t *__restrict__ lens, const uint32_t *__restrict__ rk,
-                                                            const uint32_t *__restrict__ state, uint32_t *__restrict__ merged, uint32_t *__restrict__ mk,
-                                                            uint32_t *__restrict__ bad) {
+                                                            const uint32_t *__restrict__ state, const uint32_t *__restrict__ trans, uint32_t *__restrict__ merged,
+                                                            uint32_t *__restrict__ mk, uint32_t *__restrict__ bad) {
     const uint32_t j = blockIdx.x * OV_TPB + threadIdx.x;
     if (j >= n) return;
     const uint32_t x = S[j], g = sym[(uint64_t)(x - 1) * stride + i - 1], b = base[j], r = rk[j];
@@ -239,12 +265,16 @@ static __global__ void __launch_bounds__(OV_TPB) k_ov_place(const uint32_t *__re
         bad[OV_BAD_PLACE] = 1;
         return;
     }
-    const uint32_t w = state[b], wg = (w >> (3u * g)) & 7u;
-    uint32_t k = 0;
+    uint32_t w = SCO_WEAK5_SYMBOL_ORDER;
+    if (MODE == OV_PLACE_SERIAL) w = state[b];
+    if (MODE == OV_PLACE_RESET && !(trans[b] & SCO_WEAK5_RESET)) w = state[b] & ~SCO_WEAK5_RESET;
+    const uint32_t wg = (w >> (3u * g)) & 7u;
+    uint32_t k = MODE == OV_PLACE_CONCAT ? r : 0u;
 #pragma unroll
     for (uint32_t h = 0; h < 5u; h++) {
         const uint32_t len = lens[(uint64_t)h * n + j];
-        k += min(len, r) + ((len > r && ((w >> (3u * h)) & 7u) < wg) ? 1u : 0u);
+        if (MODE == OV_PLACE_CONCAT) k += h < g ? len : 0u;
+        else k += min(len, r) + ((len > r && ((w >> (3u * h)) & 7u) < wg) ? 1u : 0u);
     }
     if ((uint64_t)b + k >= n) {
         bad[OV_BAD_PLACE] = 1;
@@ -259,6 +289,8 @@ static __global__ void __launch_bounds__(OV_TPB) k_ov_place(const uint32_t *__re
 // e(t) and t - 1 is none, so inside a streak of e the events alternate.  A[k] takes B[k - 1] after an event, B[k + 1] at an
 // event, B[k] otherwise -- if that prefix exists.  An unpaired suffix leaves S for good if the cursor of :193 is at the end
 // when it is met: no prefix of its class is left for it and no prefix above its class exists.
+// DROP = false (the parallel rule): an unpaired suffix always stays.
+template <bool DROP>
 static __global__ void __launch_bounds__(OV_TPB) k_ov_pair(const uint8_t *__restrict__ sym, uint32_t stride, uint32_t i, uint32_t L, const uint32_t *__restrict__ merged,
                                                            const uint32_t *__restrict__ mk, uint32_t n, const uint32_t *__restrict__ P, uint32_t np,
                                                            uint32_t *__restrict__ nx, uint16_t *__restrict__ ov, uint8_t *__restrict__ keep, uint8_t *__restrict__ taken) {
@@ -294,10 +326,129 @@ static __global__ void __launch_bounds__(OV_TPB) k_ov_pair(const uint8_t *__rest
         ov[x] = (uint16_t)m;
         taken[take] = 1;
     } else {
-        const bool dropped = !here && ov_cmp(sx, i, sym + (uint64_t)(P[np - 1] - 1) * stride, 0, m) >= 0;
+        const bool dropped = DROP && !here && ov_cmp(sx, i, sym + (uint64_t)(P[np - 1] - 1) * stride, 0, m) >= 0;
         stays = !dropped;
     }
     keep[p] = stays;
+}
+
+// ------------------------------------------------------------------------------------------------ kernels: the merge in front of sweep L - 3
+// The parallel generator merges the suffixes of three symbols with a compare of length 0 that never stops
+// (SymbolsPackingFacility::compareSequences :278-293): it runs on into the packed rows behind the two reads.  The key of read x
+// is so the sequence of the reads x + 1, x + 2, ..., here of their dense ranks in the sorted order; a read past R is below any.
+// Two different reads never compare equal: the larger one's rows end first.
+struct OvFollow {
+    const uint32_t *rnk;        // rnk[x], x = 1 .. R: the number of distinct reads below read x
+    uint32_t R;
+    __device__ int cmp(uint32_t x, uint32_t y, uint32_t *past) const {
+        if (x == y) return 0;
+        for (uint64_t k = 1;; k++) {
+            const uint64_t a = x + k, b = y + k;
+            if (a > R || b > R) {
+                *past += 1;
+                return a > b ? -1 : 1;
+            }
+            const uint32_t ra = rnk[a], rb = rnk[b];
+            if (ra != rb) return ra < rb ? -1 : 1;
+        }
+    }
+};
+
+static __global__ void __launch_bounds__(OV_TPB) k_ov_rank_of(const uint32_t *__restrict__ order, const uint32_t *__restrict__ runs_before, uint64_t R,
+                                                              uint32_t *__restrict__ rnk) {
+    const uint64_t j = (uint64_t)blockIdx.x * OV_TPB + threadIdx.x;
+    if (j < R) rnk[order[j]] = runs_before[j];
+}
+
+static __global__ void __launch_bounds__(OV_TPB) k_ov_place_of(const uint32_t *__restrict__ S, uint32_t n, uint32_t *__restrict__ at) {
+    const uint32_t j = blockIdx.x * OV_TPB + threadIdx.x;
+    if (j < n) at[S[j]] = j;
+}
+
+// the scan of the prefix maxima over the shares (one group's suffixes of one block; contiguous in S): an element is a read
+// number, with OV_SHARE_FIRST on a share's first; 0 is the identity
+#define OV_SHARE_FIRST (1ull << 32)
+struct OvShareIn {
+    const uint8_t *sym;
+    const uint32_t *S;
+    uint32_t stride, from;      // from = i - 1: the group's symbol and the block's three
+    __device__ uint64_t operator()(uint64_t j) const {
+        const uint32_t x = S[j];
+        const bool first = j == 0 || ov_cmp(sym + (uint64_t)(x - 1) * stride, from, sym + (uint64_t)(S[j - 1] - 1) * stride, from, OV_BLOCK_PREFIX + 1u) != 0;
+        return (first ? OV_SHARE_FIRST : 0ull) | x;
+    }
+};
+struct OvShareMax {
+    OvFollow f;
+    __device__ uint64_t operator()(uint64_t a, uint64_t b) const {
+        if (b & OV_SHARE_FIRST) return b;
+        const uint32_t x = (uint32_t)a, y = (uint32_t)b;
+        uint32_t past = 0;
+        const uint32_t m = !x ? y : !y ? x : f.cmp(y, x, &past) > 0 ? y : x;
+        return (a & OV_SHARE_FIRST) | m;
+    }
+};
+struct OvLeadStore {
+    uint32_t *p;
+    __device__ void operator()(uint64_t i, uint64_t v) const { p[i] = (uint32_t)v; }
+};
+
+// A share is cut into segments at its prefix maxima (lead[j]: the maximum up to j, a read; at[read]: its place in S).  The block's
+// segments come out by the key of their first suffix, so in front of suffix j stand: its segment up to j, the share up to the
+// segment, and of every other group's share the suffixes whose maximum is below this one's (the maxima of a share ascend: a
+// search).  Counted (cnt[0]: compares, cnt[1]: those that ran past row R): every suffix but a share's first against the
+// maximum before it, and the searches of a segment's first suffix.
+static __global__ void __launch_bounds__(OV_TPB) k_ov_place_follow(const uint32_t *__restrict__ S, uint32_t n, const uint8_t *__restrict__ sym, uint32_t stride, uint32_t i,
+                                                                   uint32_t L, const uint32_t *__restrict__ gs, const uint32_t *__restrict__ base,
+                                                                   const uint32_t *__restrict__ lens, const uint32_t *__restrict__ rk, const uint32_t *__restrict__ lead,
+                                                                   const uint32_t *__restrict__ at, OvFollow f, uint32_t *__restrict__ merged, uint32_t *__restrict__ mk,
+                                                                   unsigned long long *__restrict__ cnt, uint32_t *__restrict__ bad) {
+    const uint32_t j = blockIdx.x * OV_TPB + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t x = S[j], b = base[j], r = rk[j], m = lead[j];
+    const uint8_t *sx = sym + (uint64_t)(x - 1) * stride;
+    const uint32_t g = sx[i - 1], pm = m >= 1 && m <= f.R ? at[m] : n;
+    if (b >= n || r > j || pm > j || pm < j - r) {        // (never: the maximum of a share's part up to j lies inside it)
+        bad[OV_BAD_PLACE] = 1;
+        return;
+    }
+    const bool heads = pm == j;
+    uint32_t compares = 0, past = 0, k = r;         // own share: its segments keep their order, so all that stood in front of j
+    if (r > 0) {
+        (void)f.cmp(x, lead[j - 1], &past);
+        compares++;
+    }
+#pragma unroll
+    for (uint32_t h = 0; h < 5u; h++) {
+        const uint32_t len = lens[(uint64_t)h * n + j];
+        if (h == g || !len) continue;
+        const uint32_t first = ov_bound_s<false>(sym, stride, i, L, S, gs[h], gs[h + 1], sx);
+        uint32_t lo = first, hi = first + len;
+        if (hi > n) {
+            bad[OV_BAD_PLACE] = 1;
+            return;
+        }
+        while (lo < hi) {           // the first place of the share whose maximum is not below this one's
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            uint32_t p = 0;
+            const int c = f.cmp(lead[mid], m, &p);
+            if (heads) {
+                compares++;
+                past += p;
+            }
+            if (c < 0) lo = mid + 1;
+            else hi = mid;
+        }
+        k += lo - first;
+    }
+    if (compares) atomicAdd(cnt, (unsigned long long)compares);
+    if (past) atomicAdd(cnt + 1, (unsigned long long)past);
+    if ((uint64_t)b + k >= n) {
+        bad[OV_BAD_PLACE] = 1;
+        return;
+    }
+    merged[b + k] = x;
+    mk[b + k] = k;
 }
 
 // ------------------------------------------------------------------------------------------------ kernels: afterwards
@@ -363,6 +514,9 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     const uint32_t iters = (uint8_t)((double)L * in->stop_coef);           // uint_read_len_min of :145
     const uint32_t sweeps = iters > 1 ? iters - 1 : 0;
     const uint64_t n_left = iters > 1 ? iters : 1;
+    const bool par = o->rule == PGRC_OVL_RULE_PARALLEL;
+    const uint32_t tail_from = L - OV_BLOCK_PREFIX;        // the parallel rule (L >= 4): the first sweep that pairs whole blocks
+    const bool follow = par && tail_from <= sweeps;         // ... is run, and the merge in front of it
     int e;
     for (hipEvent_t &ev : o->ev)
         if (!ev) HIP_TRY(d, hipEventCreate(&ev));
@@ -374,6 +528,7 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
         (e = pgrc_buf_unpooled(d, o->offs, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->offp, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->gs, 64)) ||
         (e = pgrc_buf_unpooled(d, o->fold, ov_a16(sco_scratch_elems(N1) * 8))) || (e = pgrc_buf_unpooled(d, o->words, OV_BAD_WORDS * 4 + 16)))
         return e;
+    if (par && ((e = pgrc_buf_unpooled(d, o->rnk, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->lead, R * 4)) || (e = pgrc_buf_unpooled(d, o->cnt, 16)))) return e;
     const uint8_t *rows = (const uint8_t *)o->rows.p;
     uint8_t *sym = (uint8_t *)o->sym.p, *eq = (uint8_t *)o->eq.p, *keep = (uint8_t *)o->keep.p, *taken = (uint8_t *)o->taken.p;
     uint32_t *nx = (uint32_t *)o->nx.p, *order = (uint32_t *)o->order.p, *base = (uint32_t *)o->base.p, *lens = (uint32_t *)o->lens.p, *rk = (uint32_t *)o->rk.p;
@@ -388,6 +543,7 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     HIP_TRY(d, hipMemsetAsync(ov, 0, N1 * 2, d->stream));
     HIP_TRY(d, hipMemsetAsync(o->seen.p, 0, N1 * 4, d->stream));
     HIP_TRY(d, hipMemsetAsync(bad, 0, OV_BAD_WORDS * 4, d->stream));
+    if (par) HIP_TRY(d, hipMemsetAsync(o->cnt.p, 0, 16, d->stream));
     const float ms_upload = ov_ms(t0);
 
     // the rows unpacked and checked, the order made or checked
@@ -418,6 +574,11 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     // the start: chains of equal reads, P and S, the groups by the first symbol
     uint32_t *S = (uint32_t *)o->s[0].p, *S2 = (uint32_t *)o->s[1].p, *P = (uint32_t *)o->p[0].p, *P2 = (uint32_t *)o->p[1].p;
     HIP_TRY(d, hipEventRecord(o->ev[0], d->stream));
+    if (follow) {       // the reads' dense ranks: the runs of equal reads that end in front of a place of the order
+        if ((e = ov_scan_flags(o, eq, 1, R, offs))) return e;
+        hipLaunchKernelGGL(k_ov_rank_of, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, (const uint32_t *)offs, R, (uint32_t *)o->rnk.p);
+        HIP_TRY(d, hipGetLastError());
+    }
     hipLaunchKernelGGL(k_ov_chains, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, (const uint8_t *)eq, R, L, nx, ov, keep, taken);
     HIP_TRY(d, hipGetLastError());
     if ((e = ov_scan_flags(o, keep, 0, R, offs)) || (e = ov_scan_flags(o, taken, 0, R, offp))) return e;
@@ -462,13 +623,43 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
         hipError_t he = hipMemsetAsync(trans, 0, (uint64_t)n * 4, d->stream);
         if (he == hipSuccess) he = hipMemsetAsync(taken, 0, npp, d->stream);
         if (he == hipSuccess) he = hipEventRecord(o->ev[0], d->stream);
-        hipLaunchKernelGGL(k_ov_ranks, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs, base, lens,
-                           rk, trans);
-        if (he == hipSuccess)
-            he = sco_device_scan<false, false>(d->stream, ScoLoad<uint32_t, uint32_t, ScoIdentity>{trans, ScoIdentity{}}, (uint64_t)n, ScoWeakOrder5{}, 0u,
-                                               (uint32_t)SCO_WEAK5_SYMBOL_ORDER, ScoStore<uint32_t>{trans}, (uint32_t *)o->fold.p);
-        hipLaunchKernelGGL(k_ov_place, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i, (const uint32_t *)base,
-                           (const uint32_t *)lens, (const uint32_t *)rk, (const uint32_t *)trans, merged, mk, bad);
+        if (!par) {
+            hipLaunchKernelGGL(k_ov_ranks<false>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
+                               base, lens, rk, trans);
+            if (he == hipSuccess)
+                he = sco_device_scan<false, false>(d->stream, ScoLoad<uint32_t, uint32_t, ScoIdentity>{trans, ScoIdentity{}}, (uint64_t)n, ScoWeakOrder5{}, 0u,
+                                                   (uint32_t)SCO_WEAK5_SYMBOL_ORDER, ScoStore<uint32_t>{trans}, (uint32_t *)o->fold.p);
+            hipLaunchKernelGGL(k_ov_place<OV_PLACE_SERIAL>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i,
+                               (const uint32_t *)base, (const uint32_t *)lens, (const uint32_t *)rk, (const uint32_t *)trans, (const uint32_t *)trans, merged, mk, bad);
+        } else if (i < tail_from) {
+            // the order of the groups starts anew with every block: the transitions keep their reset bits, the scan goes to offs
+            hipLaunchKernelGGL(k_ov_ranks<true>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
+                               base, lens, rk, trans);
+            if (he == hipSuccess)
+                he = sco_device_scan<false, false>(d->stream, ScoLoad<uint32_t, uint32_t, ScoIdentity>{trans, ScoIdentity{}}, (uint64_t)n, ScoWeakOrder5Reset{}, 0u,
+                                                   (uint32_t)SCO_WEAK5_SYMBOL_ORDER, ScoStore<uint32_t>{offs}, (uint32_t *)o->fold.p);
+            hipLaunchKernelGGL(k_ov_place<OV_PLACE_RESET>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i,
+                               (const uint32_t *)base, (const uint32_t *)lens, (const uint32_t *)rk, (const uint32_t *)offs, (const uint32_t *)trans, merged, mk, bad);
+        } else if (i == tail_from) {
+            // a run is a block; its order is the merge by the rows that follow the reads
+            const OvFollow f{(const uint32_t *)o->rnk.p, (uint32_t)R};
+            uint32_t *lead = (uint32_t *)o->lead.p, *at = (uint32_t *)o->seen.p;
+            hipLaunchKernelGGL(k_ov_ranks<false>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
+                               base, lens, rk, trans);
+            hipLaunchKernelGGL(k_ov_place_of, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, at);
+            if (he == hipSuccess)
+                he = sco_device_scan<true, false>(d->stream, OvShareIn{(const uint8_t *)sym, (const uint32_t *)S, stride, i - 1u}, (uint64_t)n, OvShareMax{f}, (uint64_t)0,
+                                                  (uint64_t)0, OvLeadStore{lead}, (uint64_t *)o->fold.p);
+            hipLaunchKernelGGL(k_ov_place_follow, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i, L, (const uint32_t *)gs,
+                               (const uint32_t *)base, (const uint32_t *)lens, (const uint32_t *)rk, (const uint32_t *)lead, (const uint32_t *)at, f, merged, mk,
+                               (unsigned long long *)o->cnt.p, bad);
+        } else {
+            // what is left was regrouped by dropping its first symbol: a block is its groups' shares one after the other
+            hipLaunchKernelGGL(k_ov_ranks<false>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
+                               base, lens, rk, trans);
+            hipLaunchKernelGGL(k_ov_place<OV_PLACE_CONCAT>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i,
+                               (const uint32_t *)base, (const uint32_t *)lens, (const uint32_t *)rk, (const uint32_t *)trans, (const uint32_t *)trans, merged, mk, bad);
+        }
         if (he == hipSuccess) he = hipGetLastError();
         if (he == hipSuccess) he = hipEventRecord(o->ev[1], d->stream);
         uint32_t placed_bad = 0;
@@ -478,8 +669,12 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
             e = dec_fail(d, PGRC_E_DEVICE, "overlap: sweep " + std::to_string(i) + ": a place outside the merged order");
             break;
         }
-        hipLaunchKernelGGL(k_ov_pair, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)merged, (const uint32_t *)mk, n,
-                           (const uint32_t *)P, npp, nx, ov, keep, taken);
+        if (par)
+            hipLaunchKernelGGL(k_ov_pair<false>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)merged, (const uint32_t *)mk,
+                               n, (const uint32_t *)P, npp, nx, ov, keep, taken);
+        else
+            hipLaunchKernelGGL(k_ov_pair<true>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)merged, (const uint32_t *)mk,
+                               n, (const uint32_t *)P, npp, nx, ov, keep, taken);
         if (he == hipSuccess) he = hipGetLastError();
         if (he == hipSuccess) he = hipEventRecord(o->ev[2], d->stream);
         if (he != hipSuccess) {
@@ -538,6 +733,8 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
         hipLaunchKernelGGL(k_ov_narrow, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint16_t *)ov, N1, (uint8_t *)o->ovout.p);
         he = hipGetLastError();
     }
+    unsigned long long h_cnt[2] = {};
+    if (he == hipSuccess && par) he = hipMemcpyAsync(h_cnt, o->cnt.p, sizeof(h_cnt), hipMemcpyDeviceToHost, d->stream);
     if (he == hipSuccess) he = hipMemcpyAsync(blk, nx, N1 * 4, hipMemcpyDeviceToHost, d->stream);
     if (he == hipSuccess) he = hipMemcpyAsync(blk + ov_at, width == 1 ? o->ovout.p : (void *)ov, N1 * width, hipMemcpyDeviceToHost, d->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
@@ -559,6 +756,15 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     o->symbols = symbols;
     o->rb = rb;
     o->have_run = true;
+    o->info = pgrc_ovl_rule_info{};
+    o->info.struct_size = sizeof(pgrc_ovl_rule_info);
+    o->info.rule = o->rule;
+    if (par) {
+        o->info.blocks = symbols * symbols * symbols;
+        o->info.tail_sweeps = sweeps >= tail_from ? sweeps - tail_from + 1 : 0;
+        o->info.follower_compares = h_cnt[0];
+        o->info.past_end_compares = h_cnt[1];
+    }
     pgrc_ovl_timing &t = o->tm;
     t = pgrc_ovl_timing{};
     t.struct_size = sizeof(pgrc_ovl_timing);
@@ -596,7 +802,7 @@ void pgrc_ovl_destroy(pgrc_ovl_ctx *o) {
         PgrcDeviceScope scope(o->d->device);
         (void)hipStreamSynchronize(o->d->stream);
         for (DevBuf *b : {&o->rows, &o->sym, &o->nx, &o->ov, &o->ovout, &o->order, &o->seen, &o->eq, &o->s[0], &o->s[1], &o->p[0], &o->p[1], &o->base, &o->lens, &o->rk,
-                           &o->trans, &o->merged, &o->mk, &o->keep, &o->taken, &o->offs, &o->offp, &o->gs, &o->fold, &o->words, &o->rec[0], &o->rec[1], &o->prev, &o->flags})
+                           &o->trans, &o->merged, &o->mk, &o->keep, &o->taken, &o->offs, &o->offp, &o->gs, &o->fold, &o->words, &o->rec[0], &o->rec[1], &o->prev, &o->flags, &o->rnk, &o->lead, &o->cnt})
             dec_free(*b);
         pgrc_buf_free(o->sort_scratch);
         for (hipEvent_t ev : o->ev)
@@ -621,6 +827,7 @@ int pgrc_ovl_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *out
     if (in->n_reads < 1 || in->n_reads > 0xFFFFFFFEull) return ov_fail(o, "the reads' count must be in [1, 2^32 - 2]");
     if (!(in->stop_coef >= 0.0 && in->stop_coef <= 1.0)) return ov_fail(o, "the stop coefficient must be in [0, 1]");
     if (!in->packed_rows) return ov_fail(o, "packed_rows is NULL");
+    if (o->rule == PGRC_OVL_RULE_PARALLEL && in->read_len <= OV_BLOCK_PREFIX) return ov_fail(o, "the rule of the parallel generator needs a read length of at least 4");
     PGRC_ON_DEVICE(o->d);
     const int e = ov_run(o, in, out);
     if (e) {
@@ -687,6 +894,21 @@ int pgrc_ovl_assemble(pgrc_ovl_ctx *o, pgrc_asm_ctx *a, const uint32_t *index_ma
     in.index_mapping = index_mapping;
     const int e = pgasm_run_device(a, &in, res);
     if (e) return dec_fail(d, e, std::string("overlap: ") + (pgrc_asm_last_error(a) ? pgrc_asm_last_error(a) : ""));
+    return PGRC_OK;
+}
+
+int pgrc_ovlrule_set(pgrc_ovl_ctx *o, uint32_t rule) {
+    if (!o) return PGRC_E_PARAM;
+    if (rule != PGRC_OVL_RULE_SERIAL && rule != PGRC_OVL_RULE_PARALLEL) return ov_fail(o, "the rule is PGRC_OVL_RULE_SERIAL or PGRC_OVL_RULE_PARALLEL");
+    o->rule = rule;
+    return PGRC_OK;
+}
+
+int pgrc_ovlrule_get_info(pgrc_ovl_ctx *o, pgrc_ovl_rule_info *out) {
+    if (!o) return PGRC_E_PARAM;
+    if (!out || out->struct_size != sizeof(pgrc_ovl_rule_info)) return dec_fail(o->d, PGRC_E_PARAM, "overlap: rule info is NULL or struct_size is not sizeof(pgrc_ovl_rule_info)");
+    if (!o->have_run) return dec_fail(o->d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
+    *out = o->info;
     return PGRC_OK;
 }
 

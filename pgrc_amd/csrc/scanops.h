@@ -53,6 +53,17 @@ struct ScoWeakOrder5 {
 };
 #define SCO_WEAK5_SYMBOL_ORDER (0u | 1u << 3 | 2u << 6 | 3u << 9 | 4u << 12)
 
+// The same fold over segments: an element with SCO_WEAK5_RESET set forgets everything in front of it (its order already holds
+// whatever a segment starts from), and the bit stays on the fold of anything that holds such an element.  Associative; 0 is
+// still the identity (pgovl.hip under the parallel rule: the order of the groups starts anew with every block).
+#define SCO_WEAK5_RESET 0x80000000u
+struct ScoWeakOrder5Reset {
+    __host__ __device__ uint32_t operator()(uint32_t a, uint32_t b) const {
+        if (b & SCO_WEAK5_RESET) return b;
+        return (a & SCO_WEAK5_RESET) | ScoWeakOrder5{}(a & ~SCO_WEAK5_RESET, b & ~SCO_WEAK5_RESET);
+    }
+};
+
 // A map {0..3} -> {0..3} in 8 bits of a u32: the image of e in bits [2e, 2e + 2).  ScoMap4 is "a, then b": e -> b[a[e]].
 // Associative, not commutative; SCO_MAP4_IDENTITY is its identity (varlen.hip: a tile of the text takes the offset at which
 // the parse enters it to the offset at which the parse leaves it).

@@ -1,7 +1,7 @@
 """Host-side mirror of the overlap search of the pseudogenome generator (include/pgrc_overlap.h): what the reference's
 GreedySwipingPackedOverlapGeneratorTemplate::findOverlappingReads does at one thread -- the duplicates' chains and the sweeps
-that link a read's suffix to another read's prefix -- and getBothSidesOverlappedReads, on the MI355X.  numpy in and out; no
-compute here."""
+that link a read's suffix to another read's prefix -- or, under rule="parallel", what the parallel generator's does, and
+getBothSidesOverlappedReads, on the MI355X.  numpy in and out; no compute here."""
 from __future__ import annotations
 
 import ctypes as C
@@ -26,11 +26,29 @@ class OverlapFinder:
         if rc:
             raise PgrcMatchError(rc, (lib.pgrc_ovl_last_error(self._h) or b"").decode())
 
-    def run(self, packed_rows, read_len: int, symbols: int = 4, stop_coef: float = 1.0, sorted_order=None, overlap_width: int = 1) -> dict:
+    def set_rule(self, rule: str) -> None:
+        """the rule of the later runs: "serial" (the generator of one thread) or "parallel" (the parallel generator)"""
+        if rule not in _lib.OVL_RULES:
+            raise ValueError('rule: "serial" or "parallel"')
+        self._ck(lib.pgrc_ovlrule_set(self._h, _lib.OVL_RULES[rule]))
+
+    def rule_info(self) -> dict:
+        """pgrc_ovl_rule_info of the last run: rule ("serial" | "parallel"), blocks, tail_sweeps, follower_compares,
+        past_end_compares"""
+        info = _lib.OvlRuleInfo(C.sizeof(_lib.OvlRuleInfo))
+        self._ck(lib.pgrc_ovlrule_get_info(self._h, C.byref(info)))
+        out = {k: int(getattr(info, k)) for k, _ in info._fields_ if k != "struct_size"}
+        out["rule"] = {v: k for k, v in _lib.OVL_RULES.items()}[out["rule"]]
+        return out
+
+    def run(self, packed_rows, read_len: int, symbols: int = 4, stop_coef: float = 1.0, sorted_order=None, overlap_width: int = 1,
+            rule: str | None = None) -> dict:
         """packed_rows: uint8 [R, row_bytes]; sorted_order: the read numbers 1 .. R in sorted order (uint32 [R]) or None: made
-        on the device, equal reads in ascending number.
+        on the device, equal reads in ascending number; rule: "serial" | "parallel", kept for the later runs (None: as it is).
         -> next_read (uint32 [R + 1]), overlap (uint8 or uint16 [R + 1]), reads_left (uint64: after the duplicates, then after
         every sweep), duplicates, links, sweeps; rows and graph stay on the device (both_sides(), assemble())."""
+        if rule is not None:
+            self.set_rule(rule)
         rows = np.ascontiguousarray(packed_rows, dtype=np.uint8)
         rb = row_bytes(read_len, symbols)
         R = rows.size // rb if rb else 0

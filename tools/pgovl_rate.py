@@ -7,6 +7,9 @@ condition; the result is checked for what any run must give (every link's overla
 reads-left numbers fall by the links made).  Prints one JSON object.
 
     python tools/pgovl_rate.py [--reads R] [--repeats N] [--out profiles/pgovl_rate.json]
+    python tools/pgovl_rate.py --rule parallel [--reads R] [--repeats N] [--out profiles/pgovl_rate_parallel.json]
+        the rule of the parallel generator and, beside it in the same process on the same set, the
+        serial rule: "parallel" and "serial" in one JSON object, each by phase and by sweep, with the rule info
     python tools/pgovl_rate.py --reference-cpu [--reads R] --out FILE     # no GPU: times the reference's serial
         findOverlappingReads on the same set with the fixture driver (needs oracle/_ref and the reference tree) and adds
         "reference_cpu" to FILE
@@ -103,6 +106,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--reference-cpu", action="store_true")
+    ap.add_argument("--rule", choices=("serial", "parallel"), default="serial")
     args = ap.parse_args()
     if args.reference_cpu:
         return reference_cpu(args)
@@ -117,10 +121,35 @@ def main():
     ovl, asm = OverlapFinder(device=0), PgAssembler(device=0)
     res = {"what": "pgrc_ovl_run, 150 bp over ACGT from a genome at coverage 30 with 1 % substitutions, stop coefficient 1, the order made on the device; "
                    "pgrc_ovl_assemble behind it", "reads": R, "read_len": L, "repeats": args.repeats}
+    if args.rule == "parallel":
+        res["what"] += "; under the rule of the parallel generator and, beside it, under the serial rule"
+        for rule in ("serial", "parallel"):
+            res[rule] = measure(ovl, asm, rows, codes, args.repeats, rule)
+            res[rule]["rule_info"] = ovl.rule_info()
+    else:
+        res.update(measure(ovl, asm, rows, codes, args.repeats, None))
+    ovl.close()
+    asm.close()
+    res["host_generate_s"] = round(t_gen, 1)
+    if args.rule == "serial" and args.out and os.path.exists(args.out):     # (a reference time taken earlier stays)
+        old = json.load(open(args.out))
+        if "reference_cpu" in old:
+            res["reference_cpu"] = old["reference_cpu"]
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+def measure(ovl, asm, rows, codes, repeats, rule):
+    """repeats timed runs behind a warm-up under `rule` (None: as the context is) -> the figures of one rule"""
+    res = {}
     runs = []
-    for _ in range(args.repeats + 1):                           # (the first call sizes the buffers)
+    for _ in range(repeats + 1):                                # (the first call sizes the buffers)
         c0 = time.perf_counter()
-        out = ovl.run(rows, L, 4, 1.0, None)
+        out = ovl.run(rows, L, 4, 1.0, None, rule=rule)
         c1 = time.perf_counter()
         pg = ovl.assemble(asm)
         c2 = time.perf_counter()
@@ -139,19 +168,7 @@ def main():
              bytes_up=int(runs[0]["bytes_up"]), bytes_down=int(runs[0]["bytes_down"]),
              ms_sweeps_device=[round(x, 3) for x in runs[-1]["ms_sweeps_device"]])
     res["device"] = r
-    ovl.close()
-    asm.close()
-    res["host_generate_s"] = round(t_gen, 1)
-    if args.out and os.path.exists(args.out):                   # (a reference time taken earlier stays)
-        old = json.load(open(args.out))
-        if "reference_cpu" in old:
-            res["reference_cpu"] = old["reference_cpu"]
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-    return 0
+    return res
 
 
 if __name__ == "__main__":
