@@ -167,6 +167,24 @@ class OvlRuleInfo(C.Structure):  # pgrc_ovl_rule_info
 
 OVL_RULES = {"serial": 0, "parallel": 1}     # PGRC_OVL_RULE_*
 
+
+class RsetsParams(C.Structure):  # pgrc_rsets_params (include/pgrc_readsets.h)
+    _fields_ = [("struct_size", C.c_uint32), ("read_len", C.c_uint32), ("separate_n_reads_set", C.c_int32), ("n_reads_lq", C.c_int32),
+                ("device", C.c_int32)]
+
+
+class RsetsInfo(C.Structure):    # pgrc_rsets_info
+    _fields_ = [("struct_size", C.c_uint32), ("finished", C.c_uint32), ("reads_total_count", C.c_uint64), ("count", C.c_uint64 * 3),
+                ("symbols", C.c_uint32 * 3), ("row_bytes", C.c_uint32 * 3), ("disposed", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+class RsetsTiming(C.Structure):  # pgrc_rsets_timing
+    _fields_ = [("struct_size", C.c_uint32), ("edit", C.c_uint32), ("ms_checks_device", C.c_float), ("ms_desc_device", C.c_float),
+                ("ms_rows_device", C.c_float), ("ms_call", C.c_float), ("rows_moved", C.c_uint64), ("bytes_moved", C.c_uint64)]
+
+
+RSETS_WHICH = {"hq": 0, "lq": 1, "n": 2}     # PGRC_RSETS_*
+
 # every symbol include/pgrc_match.h and include/pgrc_mem.h declare: (name, restype, argtypes)
 _P = C.c_void_p
 _PROTOS = [
@@ -288,7 +306,29 @@ VARLEN_PROTOS = [
     ("pgrc_varlen_timing", C.c_int, [_P, C.POINTER(VarLenTimes)]),
 ]
 
+# include/pgrc_readsets.h
+RSETS_PROTOS = [
+    ("pgrc_rsets_create", C.c_int, [C.POINTER(RsetsParams), C.POINTER(_P)]),
+    ("pgrc_rsets_destroy", None, [_P]),
+    ("pgrc_rsets_last_error", C.c_char_p, [_P]),
+    ("pgrc_rsets_append", C.c_int, [_P, C.POINTER(DividedReads), C.c_uint64]),
+    ("pgrc_rsets_append_divider", C.c_int, [_P, _P]),
+    ("pgrc_rsets_finish", C.c_int, [_P]),
+    ("pgrc_rsets_get_info", C.c_int, [_P, C.POINTER(RsetsInfo)]),
+    ("pgrc_rsets_get_rows", C.c_int, [_P, C.c_int32, C.c_uint64, C.c_uint64, _P]),
+    ("pgrc_rsets_get_mapping", C.c_int, [_P, C.c_int32, _P]),
+    ("pgrc_rsets_dispose", C.c_int, [_P, C.c_int32]),
+    ("pgrc_rsets_move_lq", C.c_int, [_P, _P, C.c_int32]),
+    ("pgrc_rsets_move_by_overlap", C.c_int, [_P, _P]),
+    ("pgrc_rsets_remove", C.c_int, [_P, _P, C.c_int32]),
+    ("pgrc_rsets_remove_matched", C.c_int, [_P, _P]),
+    ("pgrc_rsets_overlap", C.c_int, [_P, C.c_int32, _P, C.c_double, C.c_uint32, _P, C.POINTER(OvlResult)]),
+    ("pgrc_rsets_to_matcher", C.c_int, [_P, _P]),
+    ("pgrc_rsets_get_timing", C.c_int, [_P, C.POINTER(RsetsTiming)]),
+]
+
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
+RSETS_EXPORTED_SYMBOLS = [p[0] for p in RSETS_PROTOS]
 VARLEN_EXPORTED_SYMBOLS = [p[0] for p in VARLEN_PROTOS]
 ASM_EXPORTED_SYMBOLS = [p[0] for p in ASM_PROTOS]
 OVL_EXPORTED_SYMBOLS = [p[0] for p in OVL_PROTOS]
@@ -321,7 +361,7 @@ def _load() -> C.CDLL:
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or `make -C pgrc_amd/csrc`.")
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in _PROTOS + ASM_PROTOS + OVL_PROTOS + OVL_RULE_PROTOS + VARLEN_PROTOS:
+    for name, res, args in _PROTOS + ASM_PROTOS + OVL_PROTOS + OVL_RULE_PROTOS + VARLEN_PROTOS + RSETS_PROTOS:
         fn = getattr(lib, name)  # AttributeError here = header / library out of sync: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -644,7 +644,8 @@ int pgrc_match_begin_reads(pgrc_match_ctx *c, uint64_t n) {
 // buffer and converted to the word-major 2-bit layout there; reads holding an N are flagged, and their ASCII rows
 // (made on the device for the packed formats) are kept for the side list of end_reads.
 #define UP_MARK(c, what) do { if ((c)->opt.stream_timing && (c)->st_on) fprintf(stderr, "pgrc stream: %8.2f ms    append: %s\n", (std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - (c)->st_t0) * 1e3, what); } while (0)
-static int append_rows(pgrc_match_ctx *c, const uint8_t *rows, uint64_t count, int32_t symbols) {
+// src_device: `rows` is memory of the context's device (packed rows only): the staging copy is device to device
+static int append_rows(pgrc_match_ctx *c, const uint8_t *rows, uint64_t count, int32_t symbols, bool src_device = false) {
     if (!c->up_open || c->up_next + count > c->n) { c->err = "append_reads: outside begin/end or too many rows"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     const uint32_t L = c->prm.read_len;
@@ -677,7 +678,7 @@ static int append_rows(pgrc_match_ctx *c, const uint8_t *rows, uint64_t count, i
         const int turn = (int)(c->up_chunk++ & 1u);
         hipStream_t up = streamed ? c->up_stream[turn] : c->stream;
         void *stage = c->up_stage[turn].p;
-        if (hipMemcpyAsync(stage, rows + off * rb, cnt * rb, hipMemcpyHostToDevice, up) != hipSuccess) { rcode = PGRC_E_DEVICE; break; }
+        if (hipMemcpyAsync(stage, rows + off * rb, cnt * rb, src_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, up) != hipSuccess) { rcode = PGRC_E_DEVICE; break; }
         c->stream = up;                                      // (the launchers below queue on c->stream)
         if (symbols == 0)
             rcode = pgrc_launch_pack_reads_ascii(c, (const uint8_t *)stage, first, cnt, L, (uint32_t *)c->reads_own.p, c->stride,
@@ -755,6 +756,14 @@ int pgrc_match_append_reads_packed(pgrc_match_ctx *c, const uint8_t *packed, uin
     if (c->multi) return pgrc_multi_append_reads(c, packed, count, symbols);
     return append_rows(c, packed, count, symbols);
 }
+
+}   // extern "C"
+int pgrc_append_rows_device(pgrc_match_ctx *c, const uint8_t *d_packed, uint64_t count, int32_t symbols) {
+    if (!c || (!d_packed && count) || (symbols != 4 && symbols != 5)) return PGRC_E_PARAM;
+    if (c->multi) { c->err = "append_reads: rows on a device go to a single-device context"; return PGRC_E_PARAM; }
+    return append_rows(c, d_packed, count, symbols, true);
+}
+extern "C" {
 
 int pgrc_match_end_reads(pgrc_match_ctx *c) {
     if (!c) return PGRC_E_PARAM;

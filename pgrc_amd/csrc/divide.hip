@@ -27,6 +27,7 @@
 
 #include "ctx.h"
 #include "pgrc_reads.h"
+#include "rsetsctx.h"
 
 #define DV_HQ 0u
 #define DV_LQ 1u
@@ -47,6 +48,10 @@ struct pgrc_divider : PgrcDev {
     bool have_ev = false;
     float ms[3] = {0, 0, 0};
     bool last_terminal = false;   // the last pgrc_divider_run_fastq took what the reference's iteration would take before it ends
+    // what the last run left in d_rows / d_idx (pgrc_divider_last_device: readsets.hip takes the sets where they lie)
+    bool last_valid = false;
+    uint64_t last_n = 0, last_cnt[3] = {0, 0, 0};
+    uint32_t last_sym[3] = {0, 0, 0}, last_rb[3] = {0, 0, 0};
 };
 
 static int dv_host_ensure(pgrc_divider *d, pgrc_divider::HostBuf &b, size_t bytes) {
@@ -409,7 +414,10 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
     }
     out->hq_symbols = sym[0]; out->lq_symbols = sym[1]; out->n_symbols = sym[2];
     out->hq_row_bytes = rb[0]; out->lq_row_bytes = rb[1]; out->n_row_bytes = rb[2];
-    if (n == 0) return PGRC_OK;
+    d->last_valid = false;
+    d->last_n = n;
+    for (int k = 0; k < 3; k++) { d->last_cnt[k] = 0; d->last_sym[k] = sym[k]; d->last_rb[k] = rb[k]; }
+    if (n == 0) { d->last_valid = true; return PGRC_OK; }
     int e;
     const size_t bytes = (size_t)n * L;
     if ((e = pgrc_buf_ensure(c, d->d_flags, n * sizeof(uint32_t))) || (e = pgrc_buf_ensure(c, d->d_high, n)) || (e = pgrc_buf_ensure(c, d->d_cls, n)) ||
@@ -480,8 +488,28 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
     out->lq_index = (const uint32_t *)d->h_idx[0].p;
     out->n_index = (const uint32_t *)d->h_idx[1].p;
     for (int k = 0; k < 3; k++) (void)hipEventElapsedTime(&d->ms[k], d->ev[k], d->ev[k + 1]);
+    for (int k = 0; k < 3; k++) d->last_cnt[k] = cnt[k];
+    d->last_valid = true;
     return PGRC_OK;
 }
+
+}   // extern "C"
+void pgrc_divider_last_device(const pgrc_divider *d, PgrcDividerLast *out) {
+    *out = PgrcDividerLast{};
+    out->valid = d->last_valid;
+    out->device = d->device;
+    out->prm = d->prm;
+    out->n_records = d->last_n;
+    for (int k = 0; k < 3; k++) {
+        out->cnt[k] = d->last_cnt[k];
+        out->symbols[k] = d->last_sym[k];
+        out->rb[k] = d->last_rb[k];
+        out->d_rows[k] = (const uint8_t *)d->d_rows[k].p;
+    }
+    out->d_idx[0] = (const uint32_t *)d->d_idx[0].p;
+    out->d_idx[1] = (const uint32_t *)d->d_idx[1].p;
+}
+extern "C" {
 
 static int dv_events(pgrc_divider *d) {
     if (d->have_ev) return PGRC_OK;
@@ -492,6 +520,7 @@ static int dv_events(pgrc_divider *d) {
 
 int pgrc_divider_run(pgrc_divider *d, const char *reads, const char *quals, uint64_t n, pgrc_divided_reads *out) {
     if (!d || !out || (n && !reads)) return PGRC_E_PARAM;
+    d->last_valid = false;          // (whatever becomes of this run, the last one's sets are no longer the divider's last)
     memset(out, 0, sizeof *out);
     const bool by_quality = d->prm.error_limit < 1;
     if (by_quality && n && !quals) { d->err = "divider: quality rows are needed when error_limit < 1"; return PGRC_E_PARAM; }
@@ -524,6 +553,7 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
                            int32_t rev_compl_pair, int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed,
                            uint64_t *n_records, pgrc_divided_reads *out) {
     if (!d || !out || !consumed || !n_records || (bytes && !text) || (pair_bytes && !pair_text) || (pair_text && !pair_consumed)) return PGRC_E_PARAM;
+    d->last_valid = false;
     memset(out, 0, sizeof *out);
     *consumed = 0;
     *n_records = 0;

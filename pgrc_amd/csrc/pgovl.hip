@@ -30,6 +30,7 @@
 #include "decctx.h"
 #include "devutil.h"
 #include "pgrc_overlap.h"
+#include "rsetsctx.h"
 
 #define OV_TPB 256
 #define OV_BLOCK_PREFIX 3u       // blockPrefixLength of the parallel generator
@@ -47,6 +48,7 @@ struct pgrc_ovl_ctx {
     uint64_t R = 0;
     uint32_t L = 0, symbols = 0, rb = 0;
     bool have_run = false;
+    uint64_t run_serial = 0;            // counts the runs (pgovl_run_serial: readsets.hip knows its own run by it)
     uint32_t rule = PGRC_OVL_RULE_SERIAL;
     pgrc_ovl_rule_info info{};
     pgrc_ovl_timing tm{};
@@ -504,7 +506,8 @@ static int ov_make_order(pgrc_ovl_ctx *o, uint64_t R, uint32_t L, uint32_t strid
     return PGRC_OK;
 }
 
-static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *out) {
+// rows_on_device: in->packed_rows is memory of this device (pgovl_run_rows), copied where the host's rows are uploaded
+static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *out, bool rows_on_device) {
     pgrc_decode_ctx *d = o->d;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = in->n_reads, N1 = R + 1;
@@ -536,7 +539,8 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     uint32_t *gs = (uint32_t *)o->gs.p, *bad = (uint32_t *)o->words.p;
     uint16_t *ov = (uint16_t *)o->ov.p;
 
-    if ((e = dec_upload_host(d, o->rows.p, in->packed_rows, R * rb))) return e;
+    if (rows_on_device) HIP_TRY(d, hipMemcpyAsync(o->rows.p, in->packed_rows, R * rb, hipMemcpyDeviceToDevice, d->stream));
+    else if ((e = dec_upload_host(d, o->rows.p, in->packed_rows, R * rb))) return e;
     if (in->sorted_order && (e = dec_upload_host(d, order, in->sorted_order, R * 4))) return e;
     HIP_TRY(d, hipMemsetAsync(sym, 0, R * stride + 16, d->stream));
     HIP_TRY(d, hipMemsetAsync(nx, 0, N1 * 4, d->stream));
@@ -777,7 +781,7 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     t.ms_compact_device = ms_compact;
     t.ms_download = ov_ms(t1);
     t.ms_call = ov_ms(t0);
-    t.bytes_up = R * rb + (in->sorted_order ? R * 4 : 0);
+    t.bytes_up = (rows_on_device ? 0 : R * rb) + (in->sorted_order ? R * 4 : 0);
     t.bytes_down = N1 * 4 + N1 * width;
     return PGRC_OK;
 }
@@ -814,11 +818,17 @@ void pgrc_ovl_destroy(pgrc_ovl_ctx *o) {
 
 const char *pgrc_ovl_last_error(const pgrc_ovl_ctx *o) { return pgrc_decode_last_error(o ? o->d : nullptr); }
 
-int pgrc_ovl_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *out) {
+}   // extern "C"
+
+int pgovl_device(const pgrc_ovl_ctx *o) { return o->d->device; }
+uint64_t pgovl_run_serial(const pgrc_ovl_ctx *o) { return o->have_run ? o->run_serial : 0; }
+
+int pgovl_run_rows(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *out, bool rows_on_device) {
     if (!o) return PGRC_E_PARAM;
     if (!out) return ov_fail(o, "out is NULL");
     *out = pgrc_ovl_result{};
     o->have_run = false;        // the last run's graph goes whatever becomes of this one
+    o->run_serial++;
     if (!in) return ov_fail(o, "in is NULL");
     if (in->struct_size != sizeof(pgrc_ovl_input)) return ov_fail(o, "struct_size is not sizeof(pgrc_ovl_input)");
     if (in->read_len < 1 || in->read_len > 255) return ov_fail(o, "the read length must be in [1, 255]");
@@ -829,13 +839,44 @@ int pgrc_ovl_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *out
     if (!in->packed_rows) return ov_fail(o, "packed_rows is NULL");
     if (o->rule == PGRC_OVL_RULE_PARALLEL && in->read_len <= OV_BLOCK_PREFIX) return ov_fail(o, "the rule of the parallel generator needs a read length of at least 4");
     PGRC_ON_DEVICE(o->d);
-    const int e = ov_run(o, in, out);
+    const int e = ov_run(o, in, out, rows_on_device);
     if (e) {
         (void)hipStreamSynchronize(o->d->stream);
         *out = pgrc_ovl_result{};
     }
     return e;
 }
+
+// getBothSidesOverlappedReads of the last run into o->flags, queued on the stream
+static int ov_both_sides_queue(pgrc_ovl_ctx *o) {
+    pgrc_decode_ctx *d = o->d;
+    const uint64_t R = o->R, N1 = R + 1;
+    int e;
+    if ((e = pgrc_buf_unpooled(d, o->prev, N1 * 2)) || (e = pgrc_buf_unpooled(d, o->flags, R))) return e;
+    HIP_TRY(d, hipMemsetAsync(o->prev.p, 0, N1 * 2, d->stream));
+    hipLaunchKernelGGL(k_ov_prev, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, R, (uint16_t *)o->prev.p);
+    hipLaunchKernelGGL(k_ov_both, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, (const uint16_t *)o->prev.p, R, o->L,
+                       (uint8_t *)o->flags.p);
+    HIP_TRY(d, hipGetLastError());
+    return PGRC_OK;
+}
+
+int pgovl_both_sides_device(pgrc_ovl_ctx *o, const uint8_t **d_flags, uint64_t *R) {
+    if (!o || !d_flags || !R) return PGRC_E_PARAM;
+    pgrc_decode_ctx *d = o->d;
+    if (!o->have_run) return dec_fail(d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
+    PGRC_ON_DEVICE(d);
+    int e;
+    if ((e = ov_both_sides_queue(o))) return e;
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    *d_flags = (const uint8_t *)o->flags.p;
+    *R = o->R;
+    return PGRC_OK;
+}
+
+extern "C" {
+
+int pgrc_ovl_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *out) { return pgovl_run_rows(o, in, out, false); }
 
 void pgrc_ovl_free_result(pgrc_ovl_result *r) {
     if (!r) return;
@@ -849,14 +890,9 @@ int pgrc_ovl_both_sides(pgrc_ovl_ctx *o, uint8_t *flags) {
     pgrc_decode_ctx *d = o->d;
     if (!o->have_run) return dec_fail(d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
     PGRC_ON_DEVICE(d);
-    const uint64_t R = o->R, N1 = R + 1;
+    const uint64_t R = o->R;
     int e;
-    if ((e = pgrc_buf_unpooled(d, o->prev, N1 * 2)) || (e = pgrc_buf_unpooled(d, o->flags, R))) return e;
-    HIP_TRY(d, hipMemsetAsync(o->prev.p, 0, N1 * 2, d->stream));
-    hipLaunchKernelGGL(k_ov_prev, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, R, (uint16_t *)o->prev.p);
-    hipLaunchKernelGGL(k_ov_both, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, (const uint16_t *)o->prev.p, R, o->L,
-                       (uint8_t *)o->flags.p);
-    HIP_TRY(d, hipGetLastError());
+    if ((e = ov_both_sides_queue(o))) return e;
     if (pgrc_host_pinned(flags)) {
         HIP_TRY(d, hipMemcpyAsync(flags, o->flags.p, R, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(d, hipStreamSynchronize(d->stream));

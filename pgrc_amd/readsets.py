@@ -1,5 +1,6 @@
 """Host-side mirror of the reference's read-set division (readsset/DividedPCLReadsSets.h) on top of
-include/pgrc_reads.h: computes nothing itself."""
+include/pgrc_reads.h, and of the divided sets kept on the device between the encoder's stages (include/pgrc_readsets.h):
+computes nothing itself."""
 from __future__ import annotations
 
 import ctypes as C
@@ -100,6 +101,138 @@ class DividedPCLReadsSets:
     def close(self) -> None:
         if self._h:
             lib.pgrc_divider_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DividedReadsSets:
+    """The DividedPCLReadsSets object on the device (include/pgrc_readsets.h): the packed HQ / LQ / N sets and the two index
+    mappings, filled from the divider, edited where they lie (moveLqReadsFromHqReadsSetsToLqReadsSets,
+    generateHqReadsIndexesMapping, removeReadsFromLqReadsSet / removeReadsFromNReadsSet) and handed to the overlap search and
+    the matcher without a row or a per-read flag crossing the link.  `which` is "hq", "lq" or "n"."""
+
+    def __init__(self, readLength: int, separateNReadsSet: bool = False, nReadsLQ: bool = False, device: int = -1):
+        prm = _lib.RsetsParams(C.sizeof(_lib.RsetsParams), int(readLength), int(bool(separateNReadsSet)), int(bool(nReadsLQ)), int(device))
+        self._h = C.c_void_p()
+        code = lib.pgrc_rsets_create(C.byref(prm), C.byref(self._h))
+        if code:
+            raise PgrcMatchError(code, (lib.pgrc_rsets_last_error(None) or b"").decode())
+        self.readLength = int(readLength)
+
+    def _ck(self, code: int) -> None:
+        if code:
+            raise PgrcMatchError(code, (lib.pgrc_rsets_last_error(self._h) or b"").decode())
+
+    @staticmethod
+    def _which(which) -> int:
+        return _lib.RSETS_WHICH[which] if isinstance(which, str) else int(which)
+
+    def append(self, batch: dict, n_records: Optional[int] = None) -> None:
+        """a batch as DividedPCLReadsSets.divide returns it"""
+        keep = [np.ascontiguousarray(batch[k], dtype=np.uint8) for k in ("hq_rows", "lq_rows", "n_rows")]
+        keep += [np.ascontiguousarray(batch[k], dtype=np.uint32) for k in ("lq_index", "n_index")]
+        ptr = [a.ctypes.data_as(C.c_void_p) if a.size else None for a in keep]
+        b = _lib.DividedReads(int(batch["n_hq"]), int(batch["n_lq"]), int(batch["n_n"]), *[int(x) for x in batch["symbols"]],
+                              *[int(x) for x in batch["row_bytes"]], *ptr)
+        if n_records is None:
+            n_records = b.n_hq + b.n_lq + b.n_n
+        self._ck(lib.pgrc_rsets_append(self._h, C.byref(b), int(n_records)))
+
+    def append_divider(self, divider: DividedPCLReadsSets) -> None:
+        """the sets of the divider's last run, copied on the device"""
+        self._ck(lib.pgrc_rsets_append_divider(self._h, divider._h))
+
+    def finish(self) -> None:
+        self._ck(lib.pgrc_rsets_finish(self._h))
+
+    def info(self) -> dict:
+        i = _lib.RsetsInfo(C.sizeof(_lib.RsetsInfo))
+        self._ck(lib.pgrc_rsets_get_info(self._h, C.byref(i)))
+        return {"finished": bool(i.finished), "reads_total_count": int(i.reads_total_count), "count": tuple(int(x) for x in i.count),
+                "symbols": tuple(int(x) for x in i.symbols), "row_bytes": tuple(int(x) for x in i.row_bytes),
+                "disposed": tuple(bool(x) for x in i.disposed)}
+
+    def get_rows(self, which, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        w = self._which(which)
+        i = self.info()
+        if n is None:
+            n = i["count"][w] - first
+        out = np.empty((max(int(n), 0), i["row_bytes"][w]), dtype=np.uint8)
+        self._ck(lib.pgrc_rsets_get_rows(self._h, w, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def get_mapping(self, which) -> np.ndarray:
+        """count + 1 entries, the guard last; "hq": generateHqReadsIndexesMapping"""
+        w = self._which(which)
+        i = self.info()
+        n = i["count"][w] if w else i["reads_total_count"] - i["count"][1] - i["count"][2]     # HQ: the indexes in neither mapping
+        out = np.empty(n + 1, dtype=np.uint32)
+        self._ck(lib.pgrc_rsets_get_mapping(self._h, w, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def dispose(self, which) -> None:
+        self._ck(lib.pgrc_rsets_dispose(self._h, self._which(which)))
+
+    @staticmethod
+    def _flags(flags, on_device: bool):
+        if on_device:
+            return C.c_void_p(int(flags)), None
+        a = np.ascontiguousarray(flags, dtype=np.uint8)
+        return (a.ctypes.data_as(C.c_void_p) if a.size else None), a
+
+    def move_lq(self, is_hq, on_device: bool = False) -> None:
+        """is_hq: one byte per HQ row, or (on_device) a device pointer to them"""
+        p, keep = self._flags(is_hq, on_device)
+        self._ck(lib.pgrc_rsets_move_lq(self._h, p, int(bool(on_device))))
+
+    def move_by_overlap(self, finder) -> None:
+        self._ck(lib.pgrc_rsets_move_by_overlap(self._h, finder._h))
+
+    def remove(self, is_mapped, on_device: bool = False) -> None:
+        """is_mapped: LQ count + N count bytes, the LQ set's first, or (on_device) a device pointer to them"""
+        p, keep = self._flags(is_mapped, on_device)
+        self._ck(lib.pgrc_rsets_remove(self._h, p, int(bool(on_device))))
+
+    def remove_matched(self, matcher) -> None:
+        self._ck(lib.pgrc_rsets_remove_matched(self._h, matcher._h))
+
+    def overlap(self, which, finder, stop_coef: float = 1.0, overlap_width: int = 1, sorted_order=None) -> dict:
+        """OverlapFinder.run on the set's rows, taken on the device -> as OverlapFinder.run"""
+        so = None if sorted_order is None else np.ascontiguousarray(sorted_order, dtype=np.uint32)
+        res = _lib.OvlResult()
+        finder.n_reads = 0
+        self._ck(lib.pgrc_rsets_overlap(self._h, self._which(which), finder._h, float(stop_coef), int(overlap_width),
+                                        None if so is None else so.ctypes.data_as(C.c_void_p), C.byref(res)))
+        n = res.n_reads + 1
+        ov_t = C.c_uint8 if overlap_width == 1 else C.c_uint16
+        out = {"next_read": np.ctypeslib.as_array(res.next_read, shape=(n,)).copy(),
+               "overlap": np.ctypeslib.as_array(C.cast(res.overlap, C.POINTER(ov_t)), shape=(n,)).copy(),
+               "reads_left": np.ctypeslib.as_array(res.reads_left_after, shape=(res.n_left,)).copy(),
+               "duplicates": res.duplicates, "links": res.links, "sweeps": res.sweeps}
+        finder.n_reads = res.n_reads
+        finder.sweeps = res.sweeps
+        lib.pgrc_ovl_free_result(C.byref(res))
+        return out
+
+    def to_matcher(self, matcher) -> None:
+        """the LQ rows, then the N rows, become the matcher's reads (MatchContext.set_reads_packed_sets from the device)"""
+        i = self.info()
+        self._ck(lib.pgrc_rsets_to_matcher(self._h, matcher._h))
+        matcher.n = i["count"][1] + i["count"][2]
+
+    def timing(self) -> dict:
+        t = _lib.RsetsTiming(C.sizeof(_lib.RsetsTiming))
+        self._ck(lib.pgrc_rsets_get_timing(self._h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_ if k != "struct_size"}
+
+    def close(self) -> None:
+        if self._h:
+            lib.pgrc_rsets_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
