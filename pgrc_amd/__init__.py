@@ -23,3 +23,4 @@ from .decode import PgRCDecoder, compressReadsOrder, compressReadsPgPositions, d
 from .assemble import PgAssembler  # noqa: F401
 from .overlap import OverlapFinder  # noqa: F401
 from .varlen import VarLenDNACoder  # noqa: F401
+from .rlist import ReadsList  # noqa: F401

@@ -185,6 +185,38 @@ class RsetsTiming(C.Structure):  # pgrc_rsets_timing
 
 RSETS_WHICH = {"hq": 0, "lq": 1, "n": 2}     # PGRC_RSETS_*
 
+
+class RlistInfo(C.Structure):    # pgrc_rlist_info (include/pgrc_readslist.h)
+    _fields_ = [("struct_size", C.c_uint32), ("off_width", C.c_uint32), ("n_entries", C.c_uint64), ("n_mismatches", C.c_uint64),
+                ("last_pos", C.c_uint64), ("has_rev_comp", C.c_uint32), ("has_mismatches", C.c_uint32)]
+
+
+class RlistTiming(C.Structure):  # pgrc_rlist_timing
+    _fields_ = [("struct_size", C.c_uint32), ("call", C.c_uint32), ("ms_fetch_device", C.c_float), ("ms_build_device", C.c_float),
+                ("ms_pack_device", C.c_float), ("ms_call", C.c_float), ("bytes_up", C.c_uint64), ("bytes_down", C.c_uint64),
+                ("bytes_device_copy", C.c_uint64)]
+
+
+class RlistExportArgs(C.Structure):  # pgrc_rlist_export_args
+    _fields_ = [("struct_size", C.c_uint32), ("order_on_device", C.c_int32), ("order", C.c_void_p), ("n_matched", C.c_uint64),
+                ("read_org_idx", C.c_void_p), ("sets", C.c_void_p), ("rev_compl_pair_file", C.c_int32), ("byte_per_read_length", C.c_int32)]
+
+
+class RlistArchive(C.Structure):     # pgrc_rlist_archive
+    _fields_ = [("struct_size", C.c_uint32), ("off_width", C.c_uint32), ("n_entries", C.c_uint64), ("off", C.c_void_p),
+                ("rev_comp", C.c_void_p), ("org_idx", C.c_void_p), ("block_bytes", C.c_uint64), ("block", C.c_void_p),
+                ("archive", ListArchiveStreams)]
+
+
+class RlistPairPosArgs(C.Structure):     # pgrc_rlist_pairpos_args
+    _fields_ = [("struct_size", C.c_uint32), ("pos_width", C.c_uint32), ("n_total", C.c_uint64), ("hq", C.c_void_p), ("lq", C.c_void_p),
+                ("n", C.c_void_p), ("hq_len", C.c_uint64), ("lq_len", C.c_uint64), ("matcher", C.c_void_p), ("read_org_idx", C.c_void_p),
+                ("sets", C.c_void_p)]
+
+
+RLIST_CALLS = {1: "set_host", 2: "from_assembly", 3: "export_pg_order", 4: "download", 5: "archive_encode", 6: "pair_order",
+               7: "pair_positions"}     # PGRC_RLIST_*
+
 # every symbol include/pgrc_match.h and include/pgrc_mem.h declare: (name, restype, argtypes)
 _P = C.c_void_p
 _PROTOS = [
@@ -327,7 +359,26 @@ RSETS_PROTOS = [
     ("pgrc_rsets_get_timing", C.c_int, [_P, C.POINTER(RsetsTiming)]),
 ]
 
+# include/pgrc_readslist.h (the pair streams' structs live in decode.py, which mirrors include/pgrc_decode.h: plain pointers here)
+RLIST_PROTOS = [
+    ("pgrc_rlist_create", C.c_int, [C.c_int32, C.POINTER(_P)]),
+    ("pgrc_rlist_destroy", None, [_P]),
+    ("pgrc_rlist_last_error", C.c_char_p, [_P]),
+    ("pgrc_rlist_get_info", C.c_int, [_P, C.POINTER(RlistInfo)]),
+    ("pgrc_rlist_get_timing", C.c_int, [_P, C.POINTER(RlistTiming)]),
+    ("pgrc_rlist_set_host", C.c_int, [_P, C.POINTER(ExportStreams)]),
+    ("pgrc_rlist_from_assembly", C.c_int, [_P, _P, _P, C.c_int32]),
+    ("pgrc_rlist_from_overlap", C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(AsmResult)]),
+    ("pgrc_rlist_export_pg_order", C.c_int, [_P, _P, C.POINTER(RlistExportArgs)]),
+    ("pgrc_rlist_download", C.c_int, [_P, C.POINTER(ExportStreams)]),
+    ("pgrc_rlist_archive_encode", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(RlistArchive)]),
+    ("pgrc_rlist_archive_free", None, [C.POINTER(RlistArchive)]),
+    ("pgrc_rlist_pair_order", C.c_int, [C.POINTER(_P), C.c_int32, _P]),
+    ("pgrc_rlist_pair_positions", C.c_int, [C.POINTER(RlistPairPosArgs), _P]),
+]
+
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
+RLIST_EXPORTED_SYMBOLS = [p[0] for p in RLIST_PROTOS]
 RSETS_EXPORTED_SYMBOLS = [p[0] for p in RSETS_PROTOS]
 VARLEN_EXPORTED_SYMBOLS = [p[0] for p in VARLEN_PROTOS]
 ASM_EXPORTED_SYMBOLS = [p[0] for p in ASM_PROTOS]
@@ -361,7 +412,7 @@ def _load() -> C.CDLL:
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or `make -C pgrc_amd/csrc`.")
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in _PROTOS + ASM_PROTOS + OVL_PROTOS + OVL_RULE_PROTOS + VARLEN_PROTOS + RSETS_PROTOS:
+    for name, res, args in _PROTOS + ASM_PROTOS + OVL_PROTOS + OVL_RULE_PROTOS + VARLEN_PROTOS + RSETS_PROTOS + RLIST_PROTOS:
         fn = getattr(lib, name)  # AttributeError here = header / library out of sync: fail loudly
         fn.restype = res
         fn.argtypes = args

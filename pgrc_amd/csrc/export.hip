@@ -32,6 +32,7 @@
 #include "ctx.h"
 #include "devutil.h"
 #include "scanops.h"
+#include "rlistctx.h"
 
 #define EX_NONE 0xFFFFFFFFu
 
@@ -419,7 +420,8 @@ static void touch_pages(std::initializer_list<std::pair<void *, size_t>> bufs) {
     for (auto &x : th) x.join();
 }
 
-static int finish_export(pgrc_match_ctx *c, Bufs &b, uint64_t ne, int pair_file, uint32_t width, pgrc_export_streams *out) {
+// download = false (pgrc_export_pg_order_resident): the streams stay in `b`, complete on return; out gets the counts alone
+static int finish_export(pgrc_match_ctx *c, Bufs &b, uint64_t ne, int pair_file, uint32_t width, pgrc_export_streams *out, bool download = true) {
     int e;
     if ((e = pgrc_buf_ensure(c, b.mbase, (ne + 1) * sizeof(uint64_t)))) return e;
     if ((e = device_scan<uint8_t, false>(c, (const uint8_t *)b.emc.p, ne, (uint64_t *)b.mbase.p, b.bs))) return e;
@@ -458,6 +460,10 @@ static int finish_export(pgrc_match_ctx *c, Bufs &b, uint64_t ne, int pair_file,
     out->n_entries = ne;
     out->n_mismatches = total;
     out->off_width = width;
+    if (!download) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return PGRC_OK;
+    }
     out->off = (uint8_t *)malloc(std::max<uint64_t>(ne * width, 1));
     out->org_idx = (uint32_t *)malloc(std::max<uint64_t>(ne * sizeof(uint32_t), 1));
     out->rev_comp = (uint8_t *)malloc(std::max<uint64_t>(ne, 1));
@@ -537,23 +543,37 @@ static int device_position_order(pgrc_match_ctx *c, Bufs &b, uint64_t *m_out) {
     return done(PGRC_OK);
 }
 
-static int export_pg_order(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x, Bufs &b, pgrc_export_streams *out) {
+// dev != NULL (pgrc_export_pg_order_resident): the old list and the reads' original indexes are read where they lie on the
+// device (offsets of 16 bits), the new offsets are made in 16 bits whatever the mode, and nothing is downloaded
+static int export_pg_order(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x, Bufs &b, pgrc_export_streams *out, const PgrcExportListSrc *dev = nullptr) {
     uint64_t m = x->n_matched;
-    const uint64_t h = x->list_count;
-    const uint32_t width = x->byte_per_read_length ? 1u : 2u;
+    const uint64_t h = dev ? dev->count : x->list_count;
+    const uint32_t width = x->byte_per_read_length ? 1u : 2u, off_width = dev ? 2u : width;
     int e;
     if (x->order_on_device) {
         if ((e = device_position_order(c, b, &m))) return e;
     } else if ((e = upload(c, b.order, x->order, m * sizeof(uint32_t)))) return e;    // (order == NULL: m == 0, checked by the caller)
     const uint64_t ne = m + h;
-    if (x->read_org_idx && (e = upload(c, b.rorg, x->read_org_idx, c->n * sizeof(uint32_t)))) return e;
-    if ((e = upload(c, b.loff, x->list_off, h)) || (e = upload(c, b.lorg, x->list_org_idx, h * sizeof(uint32_t)))) return e;
-    if (x->list_rev_comp && (e = upload(c, b.lrc, x->list_rev_comp, h))) return e;
+    const uint32_t *d_rorg = dev ? dev->d_read_org : nullptr, *d_lorg = dev ? dev->d_org : nullptr;
+    const uint8_t *d_lrc = dev ? dev->d_rc : nullptr;
+    const bool have_lrc = dev ? dev->d_rc != nullptr : x->list_rev_comp != nullptr;
+    if (!d_rorg && x->read_org_idx) {
+        if ((e = upload(c, b.rorg, x->read_org_idx, c->n * sizeof(uint32_t)))) return e;
+        d_rorg = (const uint32_t *)b.rorg.p;
+    }
     if ((e = pgrc_buf_ensure(c, b.lpos, (h + 1) * sizeof(uint64_t)))) return e;
-    if ((e = device_scan<uint8_t, true>(c, (const uint8_t *)b.loff.p, h, (uint64_t *)b.lpos.p, b.bs))) return e;
+    if (dev) {
+        if ((e = device_scan<uint16_t, true>(c, dev->d_off, h, (uint64_t *)b.lpos.p, b.bs))) return e;
+    } else {
+        if ((e = upload(c, b.loff, x->list_off, h)) || (e = upload(c, b.lorg, x->list_org_idx, h * sizeof(uint32_t)))) return e;
+        if (x->list_rev_comp && (e = upload(c, b.lrc, x->list_rev_comp, h))) return e;
+        d_lorg = (const uint32_t *)b.lorg.p;
+        d_lrc = (const uint8_t *)b.lrc.p;
+        if ((e = device_scan<uint8_t, true>(c, (const uint8_t *)b.loff.p, h, (uint64_t *)b.lpos.p, b.bs))) return e;
+    }
     if ((e = pgrc_buf_ensure(c, b.epos, ne * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, b.eread, ne * sizeof(uint32_t))) ||
         (e = pgrc_buf_ensure(c, b.eorg, ne * sizeof(uint32_t))) || (e = pgrc_buf_ensure(c, b.erc, ne)) ||
-        (e = pgrc_buf_ensure(c, b.emc, ne)) || (e = pgrc_buf_ensure(c, b.off, ne * width)))
+        (e = pgrc_buf_ensure(c, b.emc, ne)) || (e = pgrc_buf_ensure(c, b.off, ne * off_width)))
         return e;
     ExportArgs a;
     a.pos = (const uint64_t *)c->d_pos.p;
@@ -561,10 +581,10 @@ static int export_pg_order(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x
     a.mism = (const uint8_t *)c->d_mism.p;
     a.order = (const uint32_t *)b.order.p;
     a.m = m;
-    a.read_org = x->read_org_idx ? (const uint32_t *)b.rorg.p : nullptr;
+    a.read_org = d_rorg;
     a.lpos = (const uint64_t *)b.lpos.p;
-    a.lorg = (const uint32_t *)b.lorg.p;
-    a.lrc = x->list_rev_comp ? (const uint8_t *)b.lrc.p : nullptr;
+    a.lorg = d_lorg;
+    a.lrc = have_lrc ? d_lrc : nullptr;
     a.h = h;
     a.epos = (uint64_t *)b.epos.p;
     a.eread = (uint32_t *)b.eread.p;
@@ -577,7 +597,7 @@ static int export_pg_order(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x
     if (m) hipLaunchKernelGGL(k_export_place_new, dim3(grid_for(m)), dim3(256), 0, c->stream, a);
     if (h) hipLaunchKernelGGL(k_export_place_old, dim3(grid_for(h)), dim3(256), 0, c->stream, a);
     if (ne) {
-        if (width == 1) hipLaunchKernelGGL(k_export_offsets<uint8_t>, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint64_t *)b.epos.p, ne, (uint8_t *)b.off.p);
+        if (off_width == 1) hipLaunchKernelGGL(k_export_offsets<uint8_t>, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint64_t *)b.epos.p, ne, (uint8_t *)b.off.p);
         else hipLaunchKernelGGL(k_export_offsets<uint16_t>, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint64_t *)b.epos.p, ne, (uint16_t *)b.off.p);
     }
     HIP_TRY(c, hipGetLastError());
@@ -585,7 +605,7 @@ static int export_pg_order(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x
     HIP_TRY(c, hipMemcpyAsync(&bad, b.flag.p, sizeof bad, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (bad) { c->err = "export_pg_order: order[] names a read without a match"; return PGRC_E_PARAM; }
-    if ((e = finish_export(c, b, ne, x->rev_compl_pair_file, width, out))) return e;
+    if ((e = finish_export(c, b, ne, x->rev_compl_pair_file, width, out, dev == nullptr))) return e;
     // the builder's lastWrittenPos: the position of the last entry written
     out->last_pos = 0;
     if (ne) {
@@ -703,6 +723,51 @@ extern "C" int pgrc_match_export_pg_order(pgrc_match_ctx *c, const pgrc_export_p
     if (e && w != c) c->err = w->err;
     if (e) pgrc_match_free_export(out);
     return e;
+}
+
+// pgrc_match_export_pg_order with the old list read on the device and the merged list left there (rlistctx.h).  The caller
+// has checked what pgrc_match_export_pg_order checks of the pointers; the rest is checked here.
+int pgrc_export_pg_order_resident(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x, const PgrcExportListSrc *src, PgrcExportResident *res) {
+    *res = PgrcExportResident{};
+    if (c->multi) { c->err = "export: the resident export needs a matcher on one device"; return PGRC_E_PARAM; }
+    if (!c->have_results || !c->have_pg || !c->have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
+    if (!x->order_on_device) {
+        if (x->n_matched > c->n) { c->err = "export: more matched reads than reads"; return PGRC_E_PARAM; }
+        if (!x->order && x->n_matched) { c->err = "export_pg_order: order == NULL with n_matched > 0 (set order_on_device to let the library make the order)"; return PGRC_E_PARAM; }
+    }
+    for (uint64_t j = 0; !x->order_on_device && x->order && j < x->n_matched; j++)
+        if (x->order[j] >= c->n) { c->err = "export_pg_order: read index out of range"; return PGRC_E_PARAM; }
+    PgrcDeviceScope scope(c->device);
+    Bufs *b = new Bufs();
+    pgrc_export_streams st;
+    memset(&st, 0, sizeof st);
+    const int e = export_pg_order(c, x, *b, &st, src);
+    if (e) {
+        b->release();
+        delete b;
+        return e;
+    }
+    res->n_entries = st.n_entries;
+    res->n_mismatches = st.n_mismatches;
+    res->mis_off_width = st.off_width;
+    res->last_pos = st.last_pos;
+    res->d_off = (const uint16_t *)b->off.p;
+    res->d_org = (const uint32_t *)b->eorg.p;
+    res->d_rc = (const uint8_t *)b->erc.p;
+    res->d_cnt = (const uint8_t *)b->emc.p;
+    res->d_sym = (const uint8_t *)b->sym.p;
+    res->d_rev_off = b->roff.p;
+    res->keep = b;
+    return PGRC_OK;
+}
+
+void pgrc_export_resident_release(PgrcExportResident *res) {
+    if (res->keep) {
+        Bufs *b = (Bufs *)res->keep;
+        b->release();
+        delete b;
+    }
+    *res = PgrcExportResident{};
 }
 
 // b.eread / b.eorg hold the entry list on the device: field arrays, offsets, mismatch streams

@@ -22,6 +22,7 @@
 // kernel.  The 16-bit LDS counters hold at most LA_WSPAN = 1024 (a wave's entries) and LA_TILE = 8192 (a wave's offset).
 // Positions in the destinations are 32-bit: n_mismatches < 2^32 and n_entries < 2^32 are required.
 #include "ppchain.h"
+#include "rlistctx.h"
 
 #define LA_TPB 512
 #define LA_NW (LA_TPB / 64)
@@ -358,26 +359,24 @@ static LaLayout la_layout(uint64_t n, uint64_t m) {
     return o;
 }
 
-static int la_encode_run(pgrc_decode_ctx *d, const pgrc_export_streams *in, bool fast, pgrc_list_archive_streams *out) {
+// what the device part of the encoder hands to the host part
+struct LaEncoded {
+    uint32_t n_nonzero = 0, limit = 0;
+    uint8_t order[5] = {};
+    uint64_t h_small[LA_S_BINS] = {};
+};
+
+// the device side of the encoder: cnt (n), sym and off (m each) lie in device memory, complete on d->stream; the block is
+// written at ob (la_layout; room for at_nz + n + 16 bytes).  The caller has recorded la_ev[0].
+static int la_encode_device(pgrc_decode_ctx *d, const uint8_t *cnt, const uint8_t *sym, const uint8_t *off, uint64_t n, uint64_t m, bool fast, uint8_t *ob, LaEncoded *res) {
     static const char *who = "encode";
-    const uint64_t n = in->n_entries, m = in->n_mismatches;
-    const auto t0 = std::chrono::steady_clock::now();
     int e;
-    if ((e = la_events(d))) return e;
     const LaLayout lay = la_layout(n, m);
-    const uint64_t sym_at = pp_a16(n) + 16, off_at = sym_at + pp_a16(m) + 16;
-    if ((e = pgrc_buf_unpooled(d, d->la_in, off_at + m + 16)) || (e = pgrc_buf_unpooled(d, d->la_inc, n * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->la_mcum, (n + 1) * 8)) ||
-        (e = pgrc_buf_unpooled(d, d->la_small, LA_S_WORDS * 8)) || (e = pgrc_buf_unpooled(d, d->la_out, lay.at_nz + n + 16)))
-        return e;
-    uint8_t *ib = (uint8_t *)d->la_in.p, *ob = (uint8_t *)d->la_out.p;
-    uint8_t *cnt = ib, *sym = ib + sym_at, *off = ib + off_at;
+    if ((e = pgrc_buf_unpooled(d, d->la_inc, n * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->la_mcum, (n + 1) * 8)) || (e = pgrc_buf_unpooled(d, d->la_small, LA_S_WORDS * 8))) return e;
     uint32_t *inc = (uint32_t *)d->la_inc.p;
     uint64_t *mcum = (uint64_t *)d->la_mcum.p;
     unsigned long long *small = (unsigned long long *)d->la_small.p;
-    if ((e = dec_upload_host(d, cnt, in->mis_cnt, n)) || (e = dec_upload_host(d, sym, in->mis_sym, m)) || (e = dec_upload_host(d, off, in->mis_rev_off, m))) return e;
     HIP_TRY(d, hipMemsetAsync(small, 0, LA_S_WORDS * 8, d->stream));
-    HIP_TRY(d, hipEventRecord(d->la_ev[0], d->stream));
-    const float ms_upload = pp_ms(t0);
 
     // flags, non-zero counts, mismatch-list starts
     uint32_t n_nonzero = 0;
@@ -443,6 +442,87 @@ static int la_encode_run(pgrc_decode_ctx *d, const pgrc_export_streams *in, bool
     HIP_TRY(d, hipEventRecord(d->la_ev[4], d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
 
+    res->n_nonzero = n_nonzero;
+    res->limit = limit;
+    memcpy(res->order, order, 5);
+    memcpy(res->h_small, h_small, sizeof(h_small));
+    return PGRC_OK;
+}
+
+// the streams of a block that lies at blk in host memory; the props, which the host makes, go behind the non-zero counts
+static void la_describe(pgrc_list_archive_streams *out, uint8_t *blk, uint64_t n, uint64_t m, bool fast, const LaEncoded &r) {
+    const LaLayout lay = la_layout(n, m);
+    const uint32_t limit = r.limit;
+    out->struct_size = sizeof(pgrc_list_archive_streams);
+    out->n_entries = n;
+    out->n_mismatches = m;
+    out->n_nonzero = r.n_nonzero;
+    out->zero_flags = blk;
+    out->nonzero_cnt = blk + lay.at_nz;
+    out->mis_sym = blk + lay.at_sym;
+    for (int i = 0; i < 5; i++) out->bases_order[i] = "ACGTN"[r.order[i]];
+    uint8_t *props = blk + lay.at_nz + pp_a16(r.n_nonzero) + 16;
+    props[0] = (uint8_t)limit;
+    for (uint32_t c = 1; c < limit; c++) props[c] = (uint8_t)c;
+    out->props = props;
+    out->props_len = std::max(1u, limit);
+    out->n_dests = limit;
+    if (fast) {
+        out->dest[1] = blk + lay.at_dest;
+        out->dest_len[1] = m;
+    } else {
+        for (uint32_t c = 1; c <= limit; c++) {
+            out->dest[c] = blk + lay.at_dest + r.h_small[LA_S_START + c];
+            out->dest_len[c] = (uint64_t)c * r.h_small[LA_S_TOTAL + c];
+        }
+    }
+}
+
+uint64_t pgrc_la_device_bytes(uint64_t n, uint64_t m) { return la_layout(n, m).at_nz + n + 16; }
+uint64_t pgrc_la_host_bytes(uint64_t n, uint64_t m) { return la_layout(n, m).at_nz + pp_a16(n) + 16 + 256; }
+
+int pgrc_la_encode_resident(pgrc_decode_ctx *d, const uint8_t *d_cnt, const uint8_t *d_sym, const uint8_t *d_off, uint64_t n, uint64_t m, bool fast, uint8_t *d_block,
+                            PgrcLaResident *res) {
+    int e;
+    if ((e = la_events(d))) return e;
+    HIP_TRY(d, hipEventRecord(d->la_ev[0], d->stream));
+    LaEncoded r;
+    if ((e = la_encode_device(d, d_cnt, d_sym, d_off, n, m, fast, d_block, &r))) return e;
+    res->down = la_layout(n, m).at_nz + r.n_nonzero;
+    res->n_nonzero = r.n_nonzero;
+    res->limit = r.limit;
+    memcpy(res->order, r.order, 5);
+    memcpy(res->h_small, r.h_small, sizeof(r.h_small));
+    static_assert(sizeof(res->h_small) == sizeof(r.h_small), "rlistctx.h states the words");
+    return PGRC_OK;
+}
+
+void pgrc_la_describe_resident(pgrc_list_archive_streams *out, uint8_t *blk, uint64_t n, uint64_t m, bool fast, const PgrcLaResident *res) {
+    LaEncoded r;
+    r.n_nonzero = res->n_nonzero;
+    r.limit = res->limit;
+    memcpy(r.order, res->order, 5);
+    memcpy(r.h_small, res->h_small, sizeof(r.h_small));
+    la_describe(out, blk, n, m, fast, r);
+}
+
+static int la_encode_run(pgrc_decode_ctx *d, const pgrc_export_streams *in, bool fast, pgrc_list_archive_streams *out) {
+    const uint64_t n = in->n_entries, m = in->n_mismatches;
+    const auto t0 = std::chrono::steady_clock::now();
+    int e;
+    if ((e = la_events(d))) return e;
+    const LaLayout lay = la_layout(n, m);
+    const uint64_t sym_at = pp_a16(n) + 16, off_at = sym_at + pp_a16(m) + 16;
+    if ((e = pgrc_buf_unpooled(d, d->la_in, off_at + m + 16)) || (e = pgrc_buf_unpooled(d, d->la_out, lay.at_nz + n + 16))) return e;
+    uint8_t *ib = (uint8_t *)d->la_in.p, *ob = (uint8_t *)d->la_out.p;
+    uint8_t *cnt = ib, *sym = ib + sym_at, *off = ib + off_at;
+    if ((e = dec_upload_host(d, cnt, in->mis_cnt, n)) || (e = dec_upload_host(d, sym, in->mis_sym, m)) || (e = dec_upload_host(d, off, in->mis_rev_off, m))) return e;
+    HIP_TRY(d, hipEventRecord(d->la_ev[0], d->stream));
+    const float ms_upload = pp_ms(t0);
+    LaEncoded r;
+    if ((e = la_encode_device(d, cnt, sym, off, n, m, fast, ob, &r))) return e;
+    const uint32_t n_nonzero = r.n_nonzero, limit = r.limit;
+
     // one page-locked block, one copy: everything the device made; the props are the host's
     const auto t1 = std::chrono::steady_clock::now();
     const uint64_t at_props = lay.at_nz + pp_a16(n_nonzero) + 16, total = at_props + 256, down = lay.at_nz + n_nonzero;
@@ -458,29 +538,7 @@ static int la_encode_run(pgrc_decode_ctx *d, const pgrc_export_streams *in, bool
         (void)hipHostFree(blk);
         return dec_fail(d, pgrc_hip_code(he), std::string("list archive (encode): copy down: ") + hipGetErrorString(he));
     }
-    out->struct_size = sizeof(pgrc_list_archive_streams);
-    out->n_entries = n;
-    out->n_mismatches = m;
-    out->n_nonzero = n_nonzero;
-    out->zero_flags = blk;
-    out->nonzero_cnt = blk + lay.at_nz;
-    out->mis_sym = blk + lay.at_sym;
-    for (int i = 0; i < 5; i++) out->bases_order[i] = "ACGTN"[order[i]];
-    uint8_t *props = blk + at_props;
-    props[0] = (uint8_t)limit;
-    for (uint32_t c = 1; c < limit; c++) props[c] = (uint8_t)c;
-    out->props = props;
-    out->props_len = std::max(1u, limit);
-    out->n_dests = limit;
-    if (fast) {
-        out->dest[1] = blk + lay.at_dest;
-        out->dest_len[1] = m;
-    } else {
-        for (uint32_t c = 1; c <= limit; c++) {
-            out->dest[c] = blk + lay.at_dest + h_small[LA_S_START + c];
-            out->dest_len[c] = (uint64_t)c * h_small[LA_S_TOTAL + c];
-        }
-    }
+    la_describe(out, blk, n, m, fast, r);
     out->block = blk;
     pgrc_list_archive_timing &t = d->latm;
     t = pgrc_list_archive_timing{};

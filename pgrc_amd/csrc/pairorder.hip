@@ -13,6 +13,7 @@
 //                                  maps -> scan with PpCompose -> kinds with int8 deltas, a scan of the delta flags
 // Integer work bound by two random 4- / 8-byte accesses per entry and HBM streams; no atomics, no library kernel.
 #include "ppchain.h"
+#include "rlistctx.h"
 
 // ------------------------------------------------------------------------------------------------ kernels
 // bad[0]: a value >= T was seen
@@ -116,7 +117,9 @@ static PoLayout po_layout(int32_t form, uint64_t T, uint64_t n_near, uint64_t nf
     return o;
 }
 
-static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], const uint64_t n[3], uint64_t T, int32_t form, pgrc_pairorder_streams *out) {
+// d_joined: the joined array in memory of the context's device, complete when the call is made (pgrc_pairorder_encode_joined);
+// NULL: the three host lists go up into po_in
+static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], const uint64_t n[3], const uint32_t *d_joined, uint64_t T, int32_t form, pgrc_pairorder_streams *out) {
     const uint64_t P = T / 2;
     const bool coded = form != PGRC_PAIRORDER_COMPLETE_SINGLE_FILE, ff = form == PGRC_PAIRORDER_FILE_FLAGS, complete = form == PGRC_PAIRORDER_COMPLETE;
     const auto t0 = std::chrono::steady_clock::now();
@@ -128,17 +131,18 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     const uint64_t file_at = pp_a16(P * 4) + 16, ninc_at = file_at + pp_a16(P) + 16, frel_at = ninc_at + pp_a16(P * 4) + 16, pre_at = frel_at + pp_a16(P * 4) + 16,
                    dinc_at = pre_at + pp_a16(P * 4) + 16, dval_at = dinc_at + pp_a16(P * 4) + 16, map_at = dval_at + pp_a16(P) + 16, pair_bytes = map_at + P + 16;
     const uint64_t sco_bytes = pp_a16(sco_scratch_elems(T) * 4), bsum_bytes = sco_bytes + 32;
-    if ((e = pgrc_buf_unpooled(d, d->po_in, T * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->po_rev, T * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->po_ent, ent_bytes)) ||
+    if ((e = pgrc_buf_unpooled(d, d->po_in, d_joined ? 16 : T * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->po_rev, T * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->po_ent, ent_bytes)) ||
         (e = pgrc_buf_unpooled(d, d->po_pair, coded ? pair_bytes : 16)) || (e = pgrc_buf_unpooled(d, d->po_out, dev.total)) || (e = pgrc_buf_unpooled(d, d->po_bsum, bsum_bytes)))
         return e;
-    uint32_t *org = (uint32_t *)d->po_in.p, *rev = (uint32_t *)d->po_rev.p;
+    const uint32_t *org = d_joined ? d_joined : (const uint32_t *)d->po_in.p;
+    uint32_t *rev = (uint32_t *)d->po_rev.p;
     uint8_t *en = (uint8_t *)d->po_ent.p, *pr = (uint8_t *)d->po_pair.p, *ob = (uint8_t *)d->po_out.p;
     uint32_t *rel = (uint32_t *)en, *base_inc = (uint32_t *)(en + binc_at);
     uint32_t *sco_tmp = (uint32_t *)d->po_bsum.p, *bad = (uint32_t *)((uint8_t *)d->po_bsum.p + sco_bytes);
     // the three lists one after the other, as the reads lists number their entries
     uint64_t first = 0;
-    for (int l = 0; l < 3; l++) {
-        if (n[l] && (e = dec_upload(d, org + first, org_h[l], n[l] * 4))) return e;
+    for (int l = 0; l < 3 && !d_joined; l++) {
+        if (n[l] && (e = dec_upload(d, (uint32_t *)d->po_in.p + first, org_h[l], n[l] * 4))) return e;
         first += n[l];
     }
     HIP_TRY(d, hipEventRecord(d->po_ev[0], d->stream));
@@ -261,13 +265,24 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     t.ms_compact_device = dec_elapsed(d->po_ev[8], d->po_ev[3]) + dec_elapsed(d->po_ev[4], d->po_ev[5]) + dec_elapsed(d->po_ev[6], d->po_ev[7]);
     t.ms_download = pp_ms(t1);
     t.ms_call = pp_ms(t0);
-    t.bytes_up = T * 4;
+    t.bytes_up = d_joined ? 0 : T * 4;
     t.bytes_down = down;
     t.n_near = n_near;
     t.n_delta = n_del;
     t.n_full = nf - n_del;
     d->have_po_timing = true;
     return PGRC_OK;
+}
+
+int pgrc_pairorder_encode_joined(pgrc_decode_ctx *d, const uint32_t *d_joined, uint64_t T, int32_t form, pgrc_pairorder_streams *out) {
+    *out = pgrc_pairorder_streams{};
+    if (form < PGRC_PAIRORDER_IGNORE || form > PGRC_PAIRORDER_COMPLETE_SINGLE_FILE) return po_fail(d, "unknown form " + std::to_string(form));
+    if (T >= (1ull << 32)) return po_fail(d, "2^32 entries or more");
+    if (T & 1) return po_fail(d, "the entries' count is odd");
+    d->have_po_timing = false;
+    const int e = po_encode_run(d, nullptr, nullptr, d_joined, T, form, out);
+    if (e) *out = pgrc_pairorder_streams{};
+    return e;
 }
 
 extern "C" {
@@ -286,7 +301,7 @@ int pgrc_pairorder_encode(pgrc_decode_ctx *d, const uint32_t *const org_idx[3], 
     if (T & 1) return po_fail(d, "the entries' count is odd");
     PGRC_ON_DEVICE(d);
     d->have_po_timing = false;
-    const int e = po_encode_run(d, org_idx, n, T, form, out);
+    const int e = po_encode_run(d, org_idx, n, nullptr, T, form, out);
     if (e) *out = pgrc_pairorder_streams{};
     return e;
 }

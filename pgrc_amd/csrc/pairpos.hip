@@ -16,6 +16,7 @@
 //                                  every far pair the map of all pairs before it, hence its state, its kind and its int16.
 // Integer work bound by HBM streams and gathers; no atomics, no library kernel.
 #include "ppchain.h"
+#include "rlistctx.h"
 
 #define PP_MAX_PAIRS 0xFFFFF000ull     // rx_sort's record limit
 
@@ -430,8 +431,9 @@ static PpEncOut pp_enc_layout(uint64_t P, uint64_t W, uint64_t n_near, uint64_t 
     return o;
 }
 
+// on_device: org_h is memory of the context's device, complete when the call is made, and is read where it lies
 template <bool W8>
-static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, uint64_t T, pgrc_pairpos_streams *out) {
+static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_device, uint64_t T, pgrc_pairpos_streams *out) {
     static const char *who = "pair positions (encode)";
     const uint64_t P = T / 2, W = W8 ? 8 : 4;
     const auto t0 = std::chrono::steady_clock::now();
@@ -442,12 +444,12 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, uint64_t T, 
     const uint64_t frank_at = pp_a16(P * 8) + 16, pre_at = frank_at + pp_a16(P * 4) + 16, dinc_at = pre_at + pp_a16(P * 4) + 16,
                    dval_at = dinc_at + pp_a16(P * 4) + 16, map_at = dval_at + pp_a16(P * 2) + 16, far_bytes = map_at + P + 16;
     const uint64_t bsum_bytes = pp_a16(sco_scratch_elems(P) * 4) + 2 * PP_OR_BLOCKS * 8 + 64;
-    if ((e = pgrc_buf_unpooled(d, d->pp_in, T * 8 + 16)) || (e = pgrc_buf_unpooled(d, d->pp_rank, rank_bytes)) || (e = pgrc_buf_unpooled(d, d->pp_far, far_bytes)) ||
+    if ((e = pgrc_buf_unpooled(d, d->pp_in, on_device ? 16 : T * 8 + 16)) || (e = pgrc_buf_unpooled(d, d->pp_rank, rank_bytes)) || (e = pgrc_buf_unpooled(d, d->pp_far, far_bytes)) ||
         (e = pgrc_buf_unpooled(d, d->pp_out, dev.total)) || (e = pgrc_buf_unpooled(d, d->pp_bsum, bsum_bytes)))
         return e;
-    if (T && (e = dec_upload(d, d->pp_in.p, org_h, T * 8))) return e;
+    if (T && !on_device && (e = dec_upload(d, d->pp_in.p, org_h, T * 8))) return e;
     const float ms_upload = pp_ms(t0);
-    const uint64_t *org = (const uint64_t *)d->pp_in.p;
+    const uint64_t *org = on_device ? org_h : (const uint64_t *)d->pp_in.p;
     uint8_t *rk = (uint8_t *)d->pp_rank.p, *fr = (uint8_t *)d->pp_far.p, *ob = (uint8_t *)d->pp_out.p;
     uint64_t *rel = (uint64_t *)rk;
     uint32_t *near_inc = (uint32_t *)(rk + near_at);
@@ -555,13 +557,22 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, uint64_t T, 
     t.ms_scatter_device = dec_elapsed(d->pp_ev[2], d->pp_ev[3]) + dec_elapsed(d->pp_ev[4], d->pp_ev[5]);
     t.ms_download = pp_ms(t1);
     t.ms_call = pp_ms(t0);
-    t.bytes_up = T * 8;
+    t.bytes_up = on_device ? 0 : T * 8;
     t.bytes_down = down;
     t.n_near = n_near;
     t.n_delta = n_del;
     t.n_full = nf - n_del;
     d->have_pp_timing = true;
     return PGRC_OK;
+}
+
+int pgrc_pairpos_encode_device(pgrc_decode_ctx *d, const uint64_t *d_org_idx_to_pos, uint64_t n_total, uint32_t pos_width, pgrc_pairpos_streams *out) {
+    static const char *who = "pair positions (encode)";
+    if (n_total & 1) return pp_fail(d, who, "n_total is odd");
+    if (pos_width != 4 && pos_width != 8) return pp_fail(d, who, "pos_width must be 4 or 8");
+    if (n_total / 2 >= PP_MAX_PAIRS) return pp_fail(d, who, "too many pairs for the rank sort");
+    d->have_pp_timing = false;
+    return pos_width == 8 ? pp_encode_run<true>(d, d_org_idx_to_pos, true, n_total, out) : pp_encode_run<false>(d, d_org_idx_to_pos, true, n_total, out);
 }
 
 extern "C" {
@@ -576,7 +587,7 @@ int pgrc_pairpos_encode(pgrc_decode_ctx *d, const uint64_t *org_idx_to_pos, uint
     if (n_total / 2 >= PP_MAX_PAIRS) return pp_fail(d, who, "too many pairs for the rank sort");
     PGRC_ON_DEVICE(d);
     d->have_pp_timing = false;
-    return pos_width == 8 ? pp_encode_run<true>(d, org_idx_to_pos, n_total, out) : pp_encode_run<false>(d, org_idx_to_pos, n_total, out);
+    return pos_width == 8 ? pp_encode_run<true>(d, org_idx_to_pos, false, n_total, out) : pp_encode_run<false>(d, org_idx_to_pos, false, n_total, out);
 }
 
 void pgrc_pairpos_free(pgrc_pairpos_streams *s) {

@@ -23,6 +23,7 @@
 #include "decctx.h"
 #include "devutil.h"
 #include "pgrc_assemble.h"
+#include "rlistctx.h"
 
 #define AS_TPB 256
 #define AS_TILE 8192u           // text bytes of a block: two 16-byte lanes per thread
@@ -39,6 +40,9 @@ struct pgrc_asm_ctx {
     hipEvent_t ev[7]{};
     uint32_t symbols = 0;
     bool have_packed = false, have_timing = false;
+    // the reads list of the last successful run where it lies (org, off): its entries, and whether the run applied a host mapping
+    uint64_t list_n = 0;
+    bool list_mapped = false;
     pgrc_asm_timing tm{};
 };
 
@@ -304,7 +308,9 @@ static int as_stage(pgrc_asm_ctx *a, const pgrc_asm_input *in, bool on_device) {
     return PGRC_OK;
 }
 
-static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out, bool on_device) {
+// list_stays: the reads list is not brought down (pgasm_run_device_resident): out->org_idx and out->off stay NULL, the list
+// lies in a->org and a->off for pgasm_last_list
+static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out, bool on_device, bool list_stays) {
     pgrc_decode_ctx *d = a->d;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = in->n_reads, N1 = R + 1;
@@ -401,20 +407,25 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     const auto t1 = std::chrono::steady_clock::now();
     const uint64_t off_at = as_a16(R * 4), total = off_at + as_a16(R * 2);
     uint8_t *blk = nullptr;
-    hipError_t he = hipHostMalloc((void **)&blk, total);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(d->stream);
-        return dec_fail(d, PGRC_E_ALLOC, "assemble: hipHostMalloc(" + std::to_string(total) + ") failed");
-    }
-    he = hipMemcpyAsync(blk, org, R * 4, hipMemcpyDeviceToHost, d->copy_stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(blk + off_at, off, R * 2, hipMemcpyDeviceToHost, d->copy_stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(d->copy_stream);
-    const float ms_download = as_ms(t1);
-    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
-    if (he != hipSuccess) {
-        (void)hipHostFree(blk);
-        return dec_fail(d, pgrc_hip_code(he), std::string("assemble: copy down: ") + hipGetErrorString(he));
+    float ms_download = 0;
+    if (list_stays) {
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
+    } else {
+        hipError_t he = hipHostMalloc((void **)&blk, total);
+        if (he != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(d->stream);
+            return dec_fail(d, PGRC_E_ALLOC, "assemble: hipHostMalloc(" + std::to_string(total) + ") failed");
+        }
+        he = hipMemcpyAsync(blk, org, R * 4, hipMemcpyDeviceToHost, d->copy_stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(blk + off_at, off, R * 2, hipMemcpyDeviceToHost, d->copy_stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(d->copy_stream);
+        ms_download = as_ms(t1);
+        if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
+        if (he != hipSuccess) {
+            (void)hipHostFree(blk);
+            return dec_fail(d, pgrc_hip_code(he), std::string("assemble: copy down: ") + hipGetErrorString(he));
+        }
     }
     out->struct_size = sizeof(pgrc_asm_result);
     out->pg_len = pg_len;
@@ -424,11 +435,13 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     out->components = h_cnt[AS_CNT_COMPONENTS];
     out->singles = h_cnt[AS_CNT_SINGLES];
     out->org_idx = (const uint32_t *)blk;
-    out->off = (const uint16_t *)(blk + off_at);
+    out->off = blk ? (const uint16_t *)(blk + off_at) : nullptr;
     d->L = L;
     d->text_len = pg_len;
     d->have_text = true;
     a->symbols = symbols;
+    a->list_n = R;
+    a->list_mapped = map != nullptr;
     pgrc_asm_timing &t = a->tm;
     t = pgrc_asm_timing{};
     t.struct_size = sizeof(pgrc_asm_timing);
@@ -443,12 +456,12 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     t.ms_download = ms_download;
     t.ms_call = as_ms(t0);
     t.bytes_up = (on_device ? 0 : R * rb + N1 * 4 + N1 * width) + (map ? R * 4 : 0);
-    t.bytes_down = R * 6;
+    t.bytes_down = list_stays ? 0 : R * 6;
     a->have_timing = true;
     return PGRC_OK;
 }
 
-static int as_entry(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out, bool on_device) {
+static int as_entry(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out, bool on_device, bool list_stays = false) {
     if (!a) return PGRC_E_PARAM;
     if (!out) return as_fail(a, "out is NULL");
     *out = pgrc_asm_result{};
@@ -467,7 +480,7 @@ static int as_entry(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *
     if (in->n_reads < 1 || in->n_reads > 0xFFFFFFFEull) return as_fail(a, "the reads' count must be in [1, 2^32 - 2]");
     if (!in->packed_rows || !in->next_read || !in->overlap) return as_fail(a, "packed_rows, next_read or overlap is NULL");
     PGRC_ON_DEVICE(a->d);
-    const int e = as_run(a, in, out, on_device);
+    const int e = as_run(a, in, out, on_device, list_stays);
     if (e) {
         (void)hipStreamSynchronize(a->d->stream);
         *out = pgrc_asm_result{};
@@ -476,7 +489,21 @@ static int as_entry(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *
 }
 
 int pgasm_run_device(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out) { return as_entry(a, in, out, true); }
+int pgasm_run_device_resident(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *out) { return as_entry(a, in, out, true, true); }
 int pgasm_device(const pgrc_asm_ctx *a) { return a->d->device; }
+
+void pgasm_last_list(const pgrc_asm_ctx *a, PgasmLastList *out) {
+    *out = PgasmLastList{};
+    out->device = a->d->device;
+    out->valid = a->d->have_text;
+    if (!out->valid) return;
+    out->mapped = a->list_mapped;
+    out->n = a->list_n;
+    out->read_len = a->d->L;
+    out->pg_len = a->d->text_len;
+    out->d_org = (const uint32_t *)a->org.p;
+    out->d_off = (const uint16_t *)a->off.p;
+}
 
 extern "C" {
 

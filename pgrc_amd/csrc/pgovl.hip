@@ -861,6 +861,33 @@ static int ov_both_sides_queue(pgrc_ovl_ctx *o) {
     return PGRC_OK;
 }
 
+// pgrc_ovl_assemble; list_stays: the reads list is left on the device (pgasm_run_device_resident; rlistctx.h)
+int pgovl_assemble(pgrc_ovl_ctx *o, pgrc_asm_ctx *a, const uint32_t *index_mapping, pgrc_asm_result *res, bool list_stays) {
+    if (!o) return PGRC_E_PARAM;
+    if (!a || !res) return ov_fail(o, "asm_ctx or asm_result is NULL");
+    *res = pgrc_asm_result{};
+    pgrc_decode_ctx *d = o->d;
+    if (!o->have_run) return dec_fail(d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
+    if (pgasm_device(a) != d->device) return ov_fail(o, "the two contexts are on different devices");
+    {
+        PGRC_ON_DEVICE(d);
+        HIP_TRY(d, hipStreamSynchronize(d->stream));        // (a run leaves its stream idle; both_sides may have used it since)
+    }
+    pgrc_asm_input in{};
+    in.struct_size = sizeof(in);
+    in.read_len = o->L;
+    in.symbols = o->symbols;
+    in.overlap_width = 2;
+    in.n_reads = o->R;
+    in.packed_rows = (const uint8_t *)o->rows.p;
+    in.next_read = (const uint32_t *)o->nx.p;
+    in.overlap = o->ov.p;
+    in.index_mapping = index_mapping;
+    const int e = list_stays ? pgasm_run_device_resident(a, &in, res) : pgasm_run_device(a, &in, res);
+    if (e) return dec_fail(d, e, std::string("overlap: ") + (pgrc_asm_last_error(a) ? pgrc_asm_last_error(a) : ""));
+    return PGRC_OK;
+}
+
 int pgovl_both_sides_device(pgrc_ovl_ctx *o, const uint8_t **d_flags, uint64_t *R) {
     if (!o || !d_flags || !R) return PGRC_E_PARAM;
     pgrc_decode_ctx *d = o->d;
@@ -908,29 +935,7 @@ int pgrc_ovl_both_sides(pgrc_ovl_ctx *o, uint8_t *flags) {
 }
 
 int pgrc_ovl_assemble(pgrc_ovl_ctx *o, pgrc_asm_ctx *a, const uint32_t *index_mapping, pgrc_asm_result *res) {
-    if (!o) return PGRC_E_PARAM;
-    if (!a || !res) return ov_fail(o, "asm_ctx or asm_result is NULL");
-    *res = pgrc_asm_result{};
-    pgrc_decode_ctx *d = o->d;
-    if (!o->have_run) return dec_fail(d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
-    if (pgasm_device(a) != d->device) return ov_fail(o, "the two contexts are on different devices");
-    {
-        PGRC_ON_DEVICE(d);
-        HIP_TRY(d, hipStreamSynchronize(d->stream));        // (a run leaves its stream idle; both_sides may have used it since)
-    }
-    pgrc_asm_input in{};
-    in.struct_size = sizeof(in);
-    in.read_len = o->L;
-    in.symbols = o->symbols;
-    in.overlap_width = 2;
-    in.n_reads = o->R;
-    in.packed_rows = (const uint8_t *)o->rows.p;
-    in.next_read = (const uint32_t *)o->nx.p;
-    in.overlap = o->ov.p;
-    in.index_mapping = index_mapping;
-    const int e = pgasm_run_device(a, &in, res);
-    if (e) return dec_fail(d, e, std::string("overlap: ") + (pgrc_asm_last_error(a) ? pgrc_asm_last_error(a) : ""));
-    return PGRC_OK;
+    return pgovl_assemble(o, a, index_mapping, res, false);
 }
 
 int pgrc_ovlrule_set(pgrc_ovl_ctx *o, uint32_t rule) {

@@ -453,6 +453,7 @@ static int rs_remove(pgrc_rsets *s, const uint8_t *d_flags) {
     return PGRC_OK;
 }
 
+// generateHqReadsIndexesMapping into desc[0] (nh + 1 entries, queued); out: the host copy, or NULL to leave it on the device
 static int rs_hq_mapping(pgrc_rsets *s, uint32_t *out) {
     pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
@@ -474,7 +475,11 @@ static int rs_hq_mapping(pgrc_rsets *s, uint32_t *out) {
     hipLaunchKernelGGL(k_rs_hq_map, dim3(rs_grid(A + 1)), dim3(RS_TPB), 0, d->stream, (const uint8_t *)s->cls.p, A, (const uint32_t *)s->cnt[0].p, (uint32_t *)s->desc[0].p);
     HIP_TRY(d, hipGetLastError());
     HIP_TRY(d, hipEventRecord(s->ev[2], d->stream));
-    if ((e = rs_download(d, out, s->desc[0].p, (nh + 1) * 4))) return e;
+    if (out) {
+        if ((e = rs_download(d, out, s->desc[0].p, (nh + 1) * 4))) return e;
+    } else {
+        HIP_TRY(d, hipStreamSynchronize(d->stream));
+    }
     s->tm.struct_size = sizeof(pgrc_rsets_timing);
     s->tm.edit = 3;
     s->tm.ms_checks_device = dec_elapsed(s->ev[0], s->ev[1]);
@@ -821,3 +826,25 @@ int pgrc_rsets_get_timing(pgrc_rsets *s, pgrc_rsets_timing *out) {
 }
 
 }   // extern "C"
+
+// rlistctx.h: the mapping of set `which` where it lies on the device, *entries indexes in front of the guard.  HQ: made by the
+// code of pgrc_rsets_get_mapping into scratch of the object, valid until its next edit or get_mapping
+int pgrc_rsets_mapping_device(pgrc_rsets *s, int32_t which, const uint32_t **d_map, uint64_t *entries) {
+    int e;
+    if ((e = rs_which(s, which, "mapping"))) return e;
+    if (which == PGRC_RSETS_HQ) {
+        if ((e = rs_need(s, "mapping", {1, 2}))) return e;
+        PGRC_ON_DEVICE(s->d);
+        if ((e = rs_hq_mapping(s, nullptr))) {
+            (void)hipStreamSynchronize(s->d->stream);
+            return e;
+        }
+        *d_map = (const uint32_t *)s->desc[0].p;
+        *entries = s->A - s->set[1].n - s->set[2].n;
+        return PGRC_OK;
+    }
+    if ((e = rs_need(s, "mapping", {which}))) return e;
+    *d_map = (const uint32_t *)s->set[which].map.p;
+    *entries = s->set[which].n;
+    return PGRC_OK;
+}

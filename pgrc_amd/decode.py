@@ -204,6 +204,52 @@ def _list_archive_struct(st: dict):
     return s, (keep, dests)
 
 
+def _pairpos_dict(s) -> dict:
+    """the eight streams of a filled pgrc_pairpos_streams by name (copies), n_total and pos_width"""
+    T, pos_width = int(s.n_total), int(s.pos_width)
+    cnt = {"base_pos": T // 2, "off16_flag": T // 2, "off_base_first": s.n_off16,
+           "off_value": s.n_off16, "delta16_flag": s.n_delta_flag, "delta_base_first": s.n_delta16,
+           "delta_value": s.n_delta16, "not_base_pos": s.n_not_base}
+    out = {"n_total": T, "pos_width": pos_width}
+    for name, dt in PAIRPOS_STREAMS:
+        dt = np.dtype(dt if dt is not None else (np.uint64 if pos_width == 8 else np.uint32))
+        n = int(cnt[name])
+        out[name] = (np.frombuffer((C.c_uint8 * (n * dt.itemsize)).from_address(getattr(s, name)), dtype=dt).copy()
+                     if n else np.zeros(0, dt))
+    return out
+
+
+def _pairorder_dict(s) -> dict:
+    """the streams a filled pgrc_pairorder_streams holds for its form by name (copies), n_total and form"""
+    T, form = int(s.n_total), int(s.form)
+    coded = form != PGRC_PAIRORDER_COMPLETE_SINGLE_FILE
+    cnt = {"off8_flag": T // 2 if coded else 0, "off_value": s.n_off8, "delta8_flag": s.n_delta_flag,
+           "delta_value": s.n_delta8, "full_offset": s.n_full, "pair_base_org_idx": T // 2,
+           "off_base_file_flag": s.n_off8, "nonoff_base_file_flag": s.n_delta_flag, "rev": T}
+    present = (PAIRORDER_STREAMS[:5] if coded else ()) + {PGRC_PAIRORDER_IGNORE: (), PGRC_PAIRORDER_FILE_FLAGS: PAIRORDER_STREAMS[6:8],
+                                                           PGRC_PAIRORDER_COMPLETE: PAIRORDER_STREAMS[5:6]}.get(form, PAIRORDER_STREAMS[8:])
+    out = {"n_total": T, "form": form}
+    for name, dt in present:
+        dt = np.dtype(dt)
+        n = int(cnt[name])
+        out[name] = (np.frombuffer((C.c_uint8 * (n * dt.itemsize)).from_address(getattr(s, name)), dtype=dt).copy()
+                     if n else np.zeros(0, dt))
+    return out
+
+
+def _list_archive_dict(s, block=None) -> dict:
+    """a filled pgrc_list_archive_streams as list_archive_encode returns it (copies); block: where its one block starts"""
+    def take(p, n):
+        return np.frombuffer((C.c_uint8 * n).from_address(p), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+    block = s.block if block is None else block
+    return {"n_entries": int(s.n_entries), "n_mismatches": int(s.n_mismatches), "n_nonzero": int(s.n_nonzero),
+            "zero_flags": take(s.zero_flags, int(s.n_entries)), "nonzero_cnt": take(s.nonzero_cnt, int(s.n_nonzero)),
+            "mis_sym": take(s.mis_sym, int(s.n_mismatches)), "bases_order": bytes(s.bases_order[:5]),
+            "props": take(s.props, int(s.props_len)),
+            "dests": [np.zeros(0, np.uint8)] + [take(s.dest[c], int(s.dest_len[c])) for c in range(1, int(s.n_dests) + 1)],
+            "one_block": all(s.dest[c] is None or block <= s.dest[c] < s.props for c in range(1, int(s.n_dests) + 1))}
+
+
 class PgRCDecoder:
     """The reads of a decoded archive, rebuilt on the device: the joined text HQ | LQ | N, the three reads lists, then
     one of the three writers."""
@@ -365,15 +411,7 @@ class PgRCDecoder:
         s = PairPosStreams()
         self._ck(lib.pgrc_pairpos_encode(self._h, _ptr(op), op.size, int(pos_width), C.byref(s)))
         try:
-            cnt = {"base_pos": op.size // 2, "off16_flag": op.size // 2, "off_base_first": s.n_off16,
-                   "off_value": s.n_off16, "delta16_flag": s.n_delta_flag, "delta_base_first": s.n_delta16,
-                   "delta_value": s.n_delta16, "not_base_pos": s.n_not_base}
-            out = {"n_total": op.size, "pos_width": int(pos_width)}
-            for name, dt in PAIRPOS_STREAMS:
-                dt = np.dtype(dt if dt is not None else (np.uint64 if pos_width == 8 else np.uint32))
-                n = int(cnt[name])
-                out[name] = (np.frombuffer((C.c_uint8 * (n * dt.itemsize)).from_address(getattr(s, name)), dtype=dt).copy()
-                             if n else np.zeros(0, dt))
+            out = _pairpos_dict(s)
         finally:
             lib.pgrc_pairpos_free(C.byref(s))
         return out
@@ -399,19 +437,7 @@ class PgRCDecoder:
         s = PairOrderStreams()
         self._ck(lib.pgrc_pairorder_encode(self._h, ptrs, cnts, int(form), C.byref(s)))
         try:
-            T = int(s.n_total)
-            coded = form != PGRC_PAIRORDER_COMPLETE_SINGLE_FILE
-            cnt = {"off8_flag": T // 2 if coded else 0, "off_value": s.n_off8, "delta8_flag": s.n_delta_flag,
-                   "delta_value": s.n_delta8, "full_offset": s.n_full, "pair_base_org_idx": T // 2,
-                   "off_base_file_flag": s.n_off8, "nonoff_base_file_flag": s.n_delta_flag, "rev": T}
-            present = (PAIRORDER_STREAMS[:5] if coded else ()) + {PGRC_PAIRORDER_IGNORE: (), PGRC_PAIRORDER_FILE_FLAGS: PAIRORDER_STREAMS[6:8],
-                                                                   PGRC_PAIRORDER_COMPLETE: PAIRORDER_STREAMS[5:6]}.get(form, PAIRORDER_STREAMS[8:])
-            out = {"n_total": T, "form": int(s.form)}
-            for name, dt in present:
-                dt = np.dtype(dt)
-                n = int(cnt[name])
-                out[name] = (np.frombuffer((C.c_uint8 * (n * dt.itemsize)).from_address(getattr(s, name)), dtype=dt).copy()
-                             if n else np.zeros(0, dt))
+            out = _pairorder_dict(s)
         finally:
             lib.pgrc_pairorder_free(C.byref(s))
         return out
@@ -431,14 +457,7 @@ class PgRCDecoder:
         s = ListArchiveStreams()
         self._ck(lib.pgrc_list_archive_encode(self._h, C.byref(x), int(bool(fast_level)), C.byref(s)))
         try:
-            def take(p, n):
-                return np.frombuffer((C.c_uint8 * n).from_address(p), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
-            out = {"n_entries": int(s.n_entries), "n_mismatches": int(s.n_mismatches), "n_nonzero": int(s.n_nonzero),
-                   "zero_flags": take(s.zero_flags, int(s.n_entries)), "nonzero_cnt": take(s.nonzero_cnt, int(s.n_nonzero)),
-                   "mis_sym": take(s.mis_sym, int(s.n_mismatches)), "bases_order": bytes(s.bases_order[:5]),
-                   "props": take(s.props, int(s.props_len)),
-                   "dests": [np.zeros(0, np.uint8)] + [take(s.dest[c], int(s.dest_len[c])) for c in range(1, int(s.n_dests) + 1)],
-                   "one_block": all(s.dest[c] is None or s.block <= s.dest[c] < s.props for c in range(1, int(s.n_dests) + 1))}
+            out = _list_archive_dict(s)
         finally:
             lib.pgrc_list_archive_free(C.byref(s))
         return out
