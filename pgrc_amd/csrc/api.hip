@@ -171,6 +171,7 @@ PgrcOptions pgrc_options_from_env() {
     if (num("PGRC_UPLOAD_CHUNK_MB") > 0) o.upload_chunk_mb = (uint64_t)std::min<long long>(4096, num("PGRC_UPLOAD_CHUNK_MB"));
     o.seed_filter = flag("PGRC_SEED_FILTER");
     if (num("PGRC_TEST_SEGMENT_TOP_BITS") > 0) o.test_segment_top_bits = (uint32_t)std::min<long long>(64, num("PGRC_TEST_SEGMENT_TOP_BITS")) & ~7u;
+    if (num("PGRC_TEST_PACK_CHUNK") > 0) o.test_pack_chunk = std::min<uint64_t>(32ull << 20, std::max<uint64_t>(16ull << 10, (uint64_t)num("PGRC_TEST_PACK_CHUNK") & ~15ull));
     if (const char *hf = getenv("PGRC_SEED_HEAVY_FORM")) o.seed_heavy_form = !strcmp(hf, "window") ? 0 : 1;
     if (const char *ss = getenv("PGRC_SEED_SORT")) o.seed_sort = !strcmp(ss, "full") ? 0 : !strcmp(ss, "segments") ? 1 : -1;
     if (num("PGRC_SEED_HEAVY") > 0) o.seed_heavy = (uint32_t)std::min<long long>(4096, num("PGRC_SEED_HEAVY"));
@@ -468,12 +469,13 @@ int pgrc_match_pack_pg_slice(pgrc_match_ctx *c, const char *pg, uint64_t count, 
         // T worker threads (started once per call) pack chunk k into pinned buffer k % 2, each its share of the chunk's words; this
         // thread copies a chunk when all have packed it and frees its buffer when the copy is through -- the workers pack chunk
         // k + 1 meanwhile.  The buffers are pinned (one pair per process: the copies are plain DMA, nothing is pinned on the fly).
-        const uint64_t CH = 32ull << 20;                     // symbols per chunk (a multiple of 16)
+        const uint64_t CH_MAX = 32ull << 20;                 // symbols per chunk (a multiple of 16)
+        const uint64_t CH = c->opt.test_pack_chunk ? c->opt.test_pack_chunk : CH_MAX;   // (PGRC_TEST_PACK_CHUNK: a multiple of 16 in [16 Ki, CH_MAX])
         static std::mutex pin_mu;
         static uint32_t *pin[2] = {nullptr, nullptr};
         std::unique_lock<std::mutex> pin_lock(pin_mu);       // (one text at a time through the pair of buffers)
         for (int k = 0; k < 2; k++)
-            if (!pin[k]) HIP_TRY(c, hipHostMalloc((void **)&pin[k], CH / 4, hipHostMallocDefault));
+            if (!pin[k]) HIP_TRY(c, hipHostMalloc((void **)&pin[k], CH_MAX / 4, hipHostMallocDefault));
         const uint32_t T = c->opt.host_threads ? c->opt.host_threads : std::min<uint32_t>(8u, std::max(1u, std::thread::hardware_concurrency()));
         const uint64_t nchunks = (count + CH - 1) / CH;
         std::vector<std::atomic<uint32_t>> packed(nchunks);

@@ -68,6 +68,7 @@ struct PgrcOptions {
     uint64_t upload_chunk_mb = 0;   // PGRC_UPLOAD_CHUNK_MB: staging chunk of append_reads_* (0 = 256, or 1024 for a streamed run)
     int seed_filter = -1;           // PGRC_SEED_FILTER  modes d/i/e: -1 where it pays, 0 never, 1 always
     uint32_t test_segment_top_bits = 0;   // PGRC_TEST_SEGMENT_TOP_BITS: the segment sort's short way over this many top bits (tests: 8 makes it fail and the long way run)
+    uint64_t test_pack_chunk = 0;   // PGRC_TEST_PACK_CHUNK: symbols per chunk of the host packer (tests: a small text runs many chunks; 0 = 32 Mi)
     int seed_heavy_form = 1;        // PGRC_SEED_HEAVY_FORM=window|grouped: heavy windows a wave each / grouped by their key (default)
     int seed_sort = -1;             // PGRC_SEED_SORT=full|segments: how modes d/i/e sort their (key, entry) pairs (-1: by the batch's size)
     uint32_t seed_heavy = 0;        // PGRC_SEED_HEAVY   modes d/i/e: entries of a window above which the persistent grid expands it (0 = default)

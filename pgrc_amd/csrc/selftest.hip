@@ -1,14 +1,18 @@
 // selftest.hip -- test entries into the shared primitives: scanops.h's block scan and device scan, radix.hip's stable sort and
-// segment sort.  Thin kernels and host wrappers, nothing else; linked with the product's objects into libpgrc_selftest.so
-// (never into libpgrc_match.so).  tests/test_gpu_primitives.py drives it against numpy.
+// segment sort; and into the hand-over: pack.hip's text and read kernels, and what a context holds of its reads and its text
+// after them.  Thin kernels and host wrappers, nothing else; linked with the product's objects into libpgrc_selftest.so
+// (never into libpgrc_match.so).  tests/test_gpu_primitives.py and tests/test_gpu_handover.py drive it against numpy
+// (DESIGN.md 4.12).
 //
 // Every entry takes host arrays, runs on the handle's device and returns host arrays.  Every device buffer that a primitive
 // writes has a guard zone of ST_GUARD elements after its logical end, filled with ST_FILL bytes like the buffer itself; the
 // entry reports in *guards which zones are still intact (one bit per zone).  The scan's fold scratch has exactly
 // sco_scratch_elems(n) elements in front of its guard.
 //
-// Two preconditions of the primitives are met by construction and are not tested:
+// Three preconditions of the primitives are met by construction and are not tested:
 //   * the uint4 fast path of the u32 scan needs in.p aligned to 16 bytes (the buffers come straight from hipMalloc);
+//   * k_pack_ascii's 16-byte loads need its ASCII input aligned to 16 bytes (pgrc_selftest_pack_text: straight from hipMalloc,
+//     as the product's staging buffer is);
 //   * sco_block_exclusive<NWV = 0> needs blockDim.x to be a multiple of 64 (the entry refuses anything else).
 #include <vector>
 
@@ -322,5 +326,178 @@ extern "C" int pgrc_selftest_sort_segments(pgrc_selftest *h, const uint64_t *key
     HIP_TRY(c, v.intact(&ok[1]));
     HIP_TRY(c, ovl.intact(&ok[2]));
     *guards = (ok[0] ? 1u : 0u) | (ok[1] ? 2u : 0u) | (ok[2] ? 4u : 0u);
+    return PGRC_OK;
+}
+
+// ------------------------------------------------------------------ the hand-over (pack.hip; tests/test_gpu_handover.py)
+
+// pgrc_launch_pack_ascii over `count` >= 1 host symbols.  out_words: ceil(count / 16) words.  *guards: bit 0 the zone after the
+// words, bit 1 the zone after the error flag.
+extern "C" int pgrc_selftest_pack_text(pgrc_selftest *h, const uint8_t *ascii, uint64_t count, uint32_t *out_words, uint32_t *out_err, uint32_t *guards) {
+    PgrcDev *c = &h->dev;
+    PGRC_ON_DEVICE(c);
+    if (!count) {
+        c->err = "selftest: an empty text launches nothing";
+        return PGRC_E_PARAM;
+    }
+    const uint64_t nwords = (count + 15) / 16;
+    StBuf din, dw, dflag;
+    HIP_TRY(c, din.alloc(count, 0));
+    HIP_TRY(c, dw.alloc(nwords * 4, ST_GUARD * 4));
+    HIP_TRY(c, dflag.alloc(4, ST_GUARD * 4));
+    HIP_TRY(c, hipMemcpy(din.p, ascii, count, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(dflag.p, 0, 4));
+    const int e = pgrc_launch_pack_ascii(c, din.p, count, (uint32_t *)dw.p, (uint32_t *)dflag.p);
+    if (e) return e;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_words, dw.p, nwords * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_err, dflag.p, 4, hipMemcpyDeviceToHost));
+    bool ok_w, ok_f;
+    HIP_TRY(c, dw.intact(&ok_w));
+    HIP_TRY(c, dflag.intact(&ok_f));
+    *guards = (ok_w ? 1u : 0u) | (ok_f ? 2u : 0u);
+    return PGRC_OK;
+}
+
+// pgrc_launch_revcomp over ceil(G / 16) host words, G >= 1.  The forward buffer carries PGRC_PG_PAD_WORDS zero words behind the
+// text, as pgrc_pg_alloc provides (the kernel reads fw[q + 1]).  *guards: bit 0 the zone after the output words.
+extern "C" int pgrc_selftest_revcomp(pgrc_selftest *h, const uint32_t *words, uint64_t G, uint32_t *out_words, uint32_t *guards) {
+    PgrcDev *c = &h->dev;
+    PGRC_ON_DEVICE(c);
+    if (!G) {
+        c->err = "selftest: an empty text launches nothing";
+        return PGRC_E_PARAM;
+    }
+    const uint64_t nwords = (G + 15) / 16;
+    StBuf dfw, drc;
+    HIP_TRY(c, dfw.alloc((nwords + PGRC_PG_PAD_WORDS) * 4, 0));
+    HIP_TRY(c, drc.alloc(nwords * 4, ST_GUARD * 4));
+    HIP_TRY(c, hipMemset(dfw.p, 0, (nwords + PGRC_PG_PAD_WORDS) * 4));
+    HIP_TRY(c, hipMemcpy(dfw.p, words, nwords * 4, hipMemcpyHostToDevice));
+    const int e = pgrc_launch_revcomp(c, (const uint32_t *)dfw.p, (uint32_t *)drc.p, G);
+    if (e) return e;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_words, drc.p, nwords * 4, hipMemcpyDeviceToHost));
+    bool ok;
+    HIP_TRY(c, drc.intact(&ok));
+    *guards = ok ? 1u : 0u;
+    return PGRC_OK;
+}
+
+// One block of `count` rows put at reads [first, first + count) of a set of n_total reads: kind 0 ASCII rows
+// (k_pack_reads_ascii), 4 the reference's ACGT packing (k_repack_reads_ref), 5 its ACGNT packing (k_unpack_reads_acgnt); then
+// k_npos_rows for kinds 0 and 5 -- the sequence of append_rows (api.hip).  The word array of ceil(L / 16) * stride words and
+// npos[n_total] start as ST_FILL bytes, nflag[n_total] as zeros (begin_reads clears it); all three come back whole.
+// *guards: bit 0 the zone after the words, 1 after nflag, 2 after npos, 3 after the error flag.
+extern "C" int pgrc_selftest_pack_reads(pgrc_selftest *h, int kind, const uint8_t *rows, uint64_t first, uint64_t count, uint32_t L, uint64_t n_total,
+                                        uint64_t stride, uint32_t *out_words, uint8_t *out_nflag, uint32_t *out_npos, uint32_t *out_err, uint32_t *guards) {
+    PgrcDev *c = &h->dev;
+    PGRC_ON_DEVICE(c);
+    if ((kind != 0 && kind != 4 && kind != 5) || !L || L > 255 || !count || first + count > n_total || n_total > stride) {
+        c->err = "selftest: no such block of reads";
+        return PGRC_E_PARAM;
+    }
+    const uint32_t nw = (L + 15) / 16, rb = kind == 0 ? L : kind == 4 ? (L + 3) / 4 : (L + 2) / 3;
+    StBuf drows, dw, dnf, dnp, dflag;
+    HIP_TRY(c, drows.alloc(count * rb, 0));
+    HIP_TRY(c, dw.alloc((size_t)nw * stride * 4, ST_GUARD * 4));
+    HIP_TRY(c, dnf.alloc(n_total, ST_GUARD));
+    HIP_TRY(c, dnp.alloc(n_total * 4, ST_GUARD * 4));
+    HIP_TRY(c, dflag.alloc(4, ST_GUARD * 4));
+    HIP_TRY(c, hipMemcpy(drows.p, rows, count * rb, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(dnf.p, 0, n_total));
+    HIP_TRY(c, hipMemset(dflag.p, 0, 4));
+    int e;
+    if (kind == 0) e = pgrc_launch_pack_reads_ascii(c, drows.p, first, count, L, (uint32_t *)dw.p, stride, dnf.p, (uint32_t *)dflag.p);
+    else if (kind == 4) e = pgrc_launch_repack_reads_ref(c, drows.p, first, count, L, (uint32_t *)dw.p, stride);
+    else e = pgrc_launch_unpack_reads_acgnt(c, drows.p, first, count, L, (uint32_t *)dw.p, stride, dnf.p, (uint32_t *)dflag.p);
+    if (!e && kind != 4) e = pgrc_launch_npos_rows(c, drows.p, kind, first, count, L, dnf.p, (uint32_t *)dnp.p);
+    if (e) return e;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_words, dw.p, (size_t)nw * stride * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_nflag, dnf.p, n_total, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_npos, dnp.p, n_total * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_err, dflag.p, 4, hipMemcpyDeviceToHost));
+    const StBuf *zone[4] = {&dw, &dnf, &dnp, &dflag};
+    *guards = 0;
+    for (int k = 0; k < 4; k++) {
+        bool ok;
+        HIP_TRY(c, zone[k]->intact(&ok));
+        *guards |= (ok ? 1u : 0u) << k;
+    }
+    return PGRC_OK;
+}
+
+// pgrc_launch_nrows_ascii_acgnt: the ASCII rows of the ACGNT-packed rows local_idx[0 .. count) (each below n_rows), in that
+// order.  *guards: bit 0 the zone after the count * L output bytes.
+extern "C" int pgrc_selftest_nrows_ascii(pgrc_selftest *h, const uint8_t *packed, uint64_t n_rows, const uint32_t *local_idx, uint64_t count, uint32_t L,
+                                         uint8_t *out_ascii, uint32_t *guards) {
+    PgrcDev *c = &h->dev;
+    PGRC_ON_DEVICE(c);
+    bool inside = L && L <= 255 && count;
+    for (uint64_t k = 0; inside && k < count; k++) inside = local_idx[k] < n_rows;
+    if (!inside) {
+        c->err = "selftest: no such rows";
+        return PGRC_E_PARAM;
+    }
+    const uint32_t pb = (L + 2) / 3;
+    StBuf drows, didx, dout;
+    HIP_TRY(c, drows.alloc(n_rows * pb, 0));
+    HIP_TRY(c, didx.alloc(count * 4, 0));
+    HIP_TRY(c, dout.alloc(count * L, ST_GUARD));
+    HIP_TRY(c, hipMemcpy(drows.p, packed, n_rows * pb, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(didx.p, local_idx, count * 4, hipMemcpyHostToDevice));
+    const int e = pgrc_launch_nrows_ascii_acgnt(c, drows.p, (const uint32_t *)didx.p, count, L, dout.p);
+    if (e) return e;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_ascii, dout.p, count * L, hipMemcpyDeviceToHost));
+    bool ok;
+    HIP_TRY(c, dout.intact(&ok));
+    *guards = ok ? 1u : 0u;
+    return PGRC_OK;
+}
+
+// What a context of the PRODUCT library holds after a hand-over, read only.  libpgrc_match.so and this library are linked from
+// the same objects in one `make`, so pgrc_match_ctx and pgrc_multi have one layout in both; this library's copy of
+// pgrc_multi_shards reads the front's shard list.  shard < 0: `ctx` is a single-device context; otherwise shard `shard` of the
+// multi-device front `ctx`.  info[0 .. 10): n, stride, nw, n_nreads, n_many, 1 where nread_npos was ever allocated, pg_words,
+// the shard's first read, its end, the number of shards.  Every output may be null (a first call asks for info alone):
+// reads2 nw * stride words, nflag n bytes, npos n words, nidx n_nreads words, nascii n_nreads * read_len bytes, text pg_words
+// words of the forward text.
+extern "C" int pgrc_selftest_reads_state(pgrc_selftest *h, const pgrc_match_ctx *ctx, int32_t shard, uint64_t *info, uint32_t *out_reads2, uint8_t *out_nflag,
+                                         uint32_t *out_npos, uint32_t *out_nidx, uint8_t *out_nascii, uint32_t *out_text) {
+    PgrcDev *c = &h->dev;
+    if (!ctx || !info || (shard < 0) != (ctx->multi == nullptr)) {
+        c->err = "selftest: no such context or shard";
+        return PGRC_E_PARAM;
+    }
+    const pgrc_match_ctx *s = ctx;
+    uint64_t lo = 0, hi = ctx->n, shards = 1;
+    if (ctx->multi) {
+        const std::vector<PgrcShardView> v = pgrc_multi_shards(const_cast<pgrc_match_ctx *>(ctx));
+        if ((size_t)shard >= v.size()) {
+            c->err = "selftest: no such context or shard";
+            return PGRC_E_PARAM;
+        }
+        s = v[shard].ctx;
+        lo = v[shard].lo;
+        hi = v[shard].hi;
+        shards = v.size();
+    }
+    const bool has_npos = s->nread_npos.p && s->nread_npos.bytes >= s->n * 4;
+    const uint64_t vals[10] = {s->n, s->stride, s->nw, s->n_nreads, s->n_many, has_npos ? 1u : 0u, s->have_pg ? s->pg_words : 0, lo, hi, shards};
+    for (int k = 0; k < 10; k++) info[k] = vals[k];
+    PgrcDeviceScope scope(s->device);
+    if (!scope.ok) {
+        c->err = "selftest: hipSetDevice failed";
+        return PGRC_E_NO_DEVICE;
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
+    if (out_reads2 && s->have_reads && s->n) HIP_TRY(c, hipMemcpy(out_reads2, s->reads2, (size_t)s->nw * s->stride * 4, hipMemcpyDeviceToHost));
+    if (out_nflag && s->n && s->nread_flag.p) HIP_TRY(c, hipMemcpy(out_nflag, s->nread_flag.p, s->n, hipMemcpyDeviceToHost));
+    if (out_npos && s->n && has_npos) HIP_TRY(c, hipMemcpy(out_npos, s->nread_npos.p, s->n * 4, hipMemcpyDeviceToHost));
+    if (out_nidx && s->n_nreads) HIP_TRY(c, hipMemcpy(out_nidx, s->nread_idx.p, s->n_nreads * 4, hipMemcpyDeviceToHost));
+    if (out_nascii && s->n_nreads) HIP_TRY(c, hipMemcpy(out_nascii, s->nread_ascii.p, s->n_nreads * s->prm.read_len, hipMemcpyDeviceToHost));
+    if (out_text && s->have_pg) HIP_TRY(c, hipMemcpy(out_text, s->pg2[0].p, s->pg_words * 4, hipMemcpyDeviceToHost));
     return PGRC_OK;
 }
