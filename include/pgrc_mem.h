@@ -57,6 +57,31 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *ctx, const char *dest, uint64_t n2, int d
                          uint32_t min_match_len, pgrc_text_match **matches, uint64_t *count);
 void pgrc_mem_free_matches(pgrc_text_match *matches);
 
+/* The same two calls for texts that are ALREADY IN HBM as ASCII, on the context's device: what pgrc_asm_text_device
+ * (pgrc_assemble.h) returns.  The assembled pseudogenomes then reach SimplePgMatcher::matchPgsInPg's stage
+ * (matching/SimplePgMatcher.cpp:175-206) without a trip to the host and back; only the matches, the two small streams per
+ * text and the coded block come down.  Host and device forms mix freely: a device source with host
+ * destinations and the reverse.  The texts may start at any byte address and must be complete when the call is made (no
+ * kernel still writing them on another stream); they are read only while the call runs.
+ *
+ * pgrc_mem_set_src_device: pgrc_mem_set_src_ascii over d_ascii[0 .. n) (ACGT).  The text is packed into the context's own
+ * words and indexed; nothing is borrowed -- the assembler may run again at once.  Same codes and messages as the host form
+ * (PGRC_E_SYMBOL for a symbol outside ACGT, ...), and it forgets the remembered destination and the mapped slots as that does.
+ *
+ * pgrc_mem_match_texts_device: the destination in its FORWARD orientation, as assembled (it may contain 'N').  With
+ * rev_compl_matching the library reverse-complements it on the device while packing it (the reference's complement table:
+ * N stays N), so the matches, their coordinates and their order are those that pgrc_mem_match_texts returns for the
+ * host-reversed text, and pgrc_mem_mark_and_remove, _resident and pgrc_mem_encode_mapped follow as after that call.  With
+ * dest_is_src the library uses its own copy of the source; d_dest_ascii is not read and may be NULL.  Errors as in the host
+ * form (PGRC_E_SYMBOL for a symbol outside ACGNT -- except in a text shorter than the K-mer, which is accepted but not
+ * remembered --, PGRC_E_PARAM for dest_is_src with another length, a too long text, min_match_len < K; PGRC_E_STATE without
+ * a source).
+ *
+ * Both: PGRC_E_PARAM for a pointer that is not device memory of the context's device (hipPointerGetAttributes). */
+int pgrc_mem_set_src_device(pgrc_mem_ctx *ctx, const void *d_ascii, uint64_t n);
+int pgrc_mem_match_texts_device(pgrc_mem_ctx *ctx, const void *d_dest_ascii, uint64_t n2, int dest_is_src, int rev_compl_matching,
+                                uint32_t min_match_len, pgrc_text_match **matches, uint64_t *count);
+
 /* markAndRemoveExactMatches (matching/SimplePgMatcher.cpp:69-148), the second half of SimplePgMatcher::matchPgsInPg, on
  * the device: the matches are normalised (correctDestPositionDueToRevComplMatching, :58-61;
  * resolveMappingCollisionsInTheSameText, :157-171), sorted, made unique and walked greedily; every kept match becomes one
@@ -64,8 +89,9 @@ void pgrc_mem_free_matches(pgrc_text_match *matches);
  * and one byte-frugal value of the lengths stream, which leads with min_match_len.
  *
  * It maps the destination of the LAST SUCCESSFUL pgrc_mem_match_texts of this context, which is still packed in HBM (no
- * text is uploaded): the context remembers that call's n2, dest_is_src and rev_compl_matching.  pgrc_mem_set_src_ascii
- * and a failed pgrc_mem_match_texts forget them (PGRC_E_STATE here).  The mapped text is the destination in its forward
+ * text is uploaded): the context remembers that call's n2, dest_is_src and rev_compl_matching (pgrc_mem_match_texts_device
+ * counts as that call).  pgrc_mem_set_src_ascii, pgrc_mem_set_src_device and a failed pgrc_mem_match_texts forget them
+ * (PGRC_E_STATE here).  The mapped text is the destination in its forward
  * orientation, i.e. destPg itself, not the reverse complement that was matched.  A destination shorter than the index's
  * K-mer has no window to match, but pgrc_mem_match_texts still packs it to HBM so that it can be mapped.  One exception:
  * such a short destination that holds a symbol outside ACGNT is accepted by pgrc_mem_match_texts as it always was (no
@@ -115,7 +141,8 @@ int pgrc_mem_encode_mapped(pgrc_mem_ctx *ctx, pgrc_varlen *v, void *coded_out, u
 typedef struct {
     uint64_t probes;       /* destination windows hashed */
     uint64_t events;       /* (window, index entry) pairs with equal K-mers */
-    uint64_t stale_lookups;/* events that needed the stale-register emulation on the host */
+    uint64_t stale_lookups;/* events that needed the stale-register emulation on the host (for a text without a host copy it
+                            * fetches the few bytes it looks at from the packed text on the device) */
     float ms_index, ms_probe, ms_sort, ms_extend;
     float ms_host;         /* compaction + download of the matches */
     float ms_replay;       /* the sequential rules on the device, all rounds (host clock) */

@@ -277,6 +277,9 @@ _PROTOS = [
     ("pgrc_mem_match_texts", C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.POINTER(TextMatch)),
                                        C.POINTER(C.c_uint64)]),
     ("pgrc_mem_free_matches", None, [C.POINTER(TextMatch)]),
+    ("pgrc_mem_set_src_device", C.c_int, [_P, _P, C.c_uint64]),
+    ("pgrc_mem_match_texts_device", C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.POINTER(TextMatch)),
+                                              C.POINTER(C.c_uint64)]),
     ("pgrc_mem_get_counters", C.c_int, [_P, C.POINTER(MemCounters)]),
     ("pgrc_mem_mark_and_remove", C.c_int, [_P, C.POINTER(TextMatch), C.c_uint64, C.c_uint32, _P, C.c_uint64, C.POINTER(MemMapping)]),
     ("pgrc_mem_free_mapping", None, [C.POINTER(MemMapping)]),

@@ -288,6 +288,12 @@ int pgrc_launch_npos_rows(PgrcDev *c, const uint8_t *d_rows, int symbols, uint64
 int pgrc_launch_nrows_ascii_acgnt(PgrcDev *c, const uint8_t *d_packed, const uint32_t *d_local_idx, uint64_t count,
                                   uint32_t L, uint8_t *d_ascii);
 
+// mempack.hip: an ASCII text in HBM (any byte alignment) -> words_out 2-bit words (zero behind the text), the N map (or null)
+// and the flag word (bit 0 a symbol outside ACGNT, bit 1 an N; the caller clears it), forward or reverse-complemented, in
+// one launch of at most block_cap blocks (0: the usual 65 536)
+int pgrc_launch_mem_pack_device(PgrcDev *c, const uint8_t *d_ascii, uint64_t n, bool reversed, uint32_t *d_words, uint16_t *d_nmap, uint64_t words_out,
+                                uint32_t *d_flags, uint32_t block_cap);
+
 // copmem.hip
 int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand);
 // idxsort.hip: the partition build of the same index (hand-written scatter passes, in-LDS finish of a partition)

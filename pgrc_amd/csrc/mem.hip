@@ -24,6 +24,10 @@
 // hold by walking back through the windows actually examined (one block's outcomes and bucket lookups from the device
 // on demand), tells the device the verdict and lets the replay continue.
 //
+// A source or destination that lies in HBM as ASCII already (an assembled pseudogenome) skips the staged upload: one launch of
+// mempack.hip's kernel packs it, reverse-complemented if need be (pgrc_mem_set_src_device, pgrc_mem_match_texts_device), and the
+// walk above rebuilds the few bytes it looks at from the packed words.
+//
 // All integer work, bound by the random head gathers (one per window): no MFMA.
 #include <algorithm>
 #include <atomic>
@@ -520,7 +524,9 @@ static uint32_t le32(const char *p) {
 // lookups, fetched from the device on demand -- to the entry that wrote the register last.
 struct StaleWalk {
     pgrc_mem_ctx *m;
-    const char *dest;
+    const char *dest;                            // host text, or null: the destination exists on the device alone (d_dw, d_dn)
+    const uint32_t *d_dw = nullptr;              // device: the destination's words and N map (null: no N) as the kernels read them
+    const uint16_t *d_dn = nullptr;
     uint64_t N2;
     bool dest_is_src, rev_compl;
     uint64_t skip, nmain;                        // probes jumped over after a hit; probes of the main loop (whole blocks of 256)
@@ -537,6 +543,29 @@ struct StaleWalk {
     int lookup_err = 0;
 
     static bool jump_lt(const Jump &j, uint64_t v) { return j.t < v; }
+    // `len` <= 64 symbols of a text at `pos` as the reference reads them: from the host text, or, for a text without a host
+    // copy (pgrc_mem_set_src_device, pgrc_mem_match_texts_device), rebuilt from its packed words and N map (rare path)
+    const char *text_at(const char *host, const uint32_t *d_words, const uint16_t *d_nmap, uint64_t pos, uint32_t len, char *buf) {
+        if (host) return host + pos;
+        const uint64_t w0 = pos >> 4, nw = ((pos + len + 15) >> 4) - w0;        // at most 5 words
+        uint32_t w[6] = {0, 0, 0, 0, 0, 0};
+        uint16_t nm[6] = {0, 0, 0, 0, 0, 0};
+        if (hipMemcpy(w, d_words + w0, nw * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            (d_nmap && hipMemcpy(nm, d_nmap + w0, nw * 2, hipMemcpyDeviceToHost) != hipSuccess)) { lookup_err = 1; memset(buf, 0, len); return buf; }
+        for (uint32_t k = 0; k < len; k++) {
+            const uint64_t x = pos + k - (w0 << 4);
+            buf[k] = ((nm[x >> 4] >> (x & 15)) & 1u) ? 'N' : "ACGT"[(w[x >> 4] >> (2 * (x & 15))) & 3u];
+        }
+        return buf;
+    }
+    uint32_t src32(uint64_t pos) {
+        char buf[4];
+        return le32(text_at(m->src, (const uint32_t *)m->base->pg2[0].p, nullptr, pos, 4, buf));
+    }
+    uint32_t dest32(uint64_t pos) {
+        char buf[4];
+        return le32(text_at(dest, d_dw, d_dn, pos, 4, buf));
+    }
     // the jumps of the block that probe t belongs to (a jump never leaves its block)
     void load_block(uint64_t t) {
         const uint64_t b = mem_block_of(t, nmain);
@@ -573,7 +602,8 @@ struct StaleWalk {
     // the bucket of a destination window, from the device (rare path)
     int bucket(uint64_t q, uint64_t *pos) {
         pgrc_match_ctx *c = m->base;
-        const uint32_t h = host_hash(m->K, dest + q) & (uint32_t)(c->cp.hash_size - 1);
+        char win[64];                            // (K <= 56)
+        const uint32_t h = host_hash(m->K, text_at(dest, d_dw, d_dn, q, (uint32_t)m->K, win)) & (uint32_t)(c->cp.hash_size - 1);
         unsigned long long hd[2];
         if (hipMemcpy(hd, (const char *)c->head_ptr + (size_t)head_slot(h, c->head_sh) * 16, 16, hipMemcpyDeviceToHost) != hipSuccess) { lookup_err = 1; return 0; }
         if (hd[0] == HEAD_EMPTY) return 0;
@@ -604,7 +634,7 @@ struct StaleWalk {
                 const uint64_t p = pos[j];
                 if (self_filtered(q, p)) continue;   // (a): never reached the register update
                 if (left ? p >= (uint64_t)m->LK2 : p + (uint64_t)m->KLK24 + 4 <= m->N)
-                    return le32(left ? m->src + p - m->LK2 : m->src + p + m->KLK24);
+                    return src32(left ? p - m->LK2 : p + m->KLK24);
             }
             // previous examined probe
             for (;;) {
@@ -629,7 +659,7 @@ struct StaleWalk {
             const uint64_t q = tt * (uint64_t)m->k2;
             if (q + (uint64_t)m->KLK24 + 4 > N2) continue;
             if (bucket(q, pos) == 0) continue;       // empty bucket: the registers are not touched (:376-379)
-            return le32(dest + q + m->KLK24);
+            return dest32(q + m->KLK24);
         }
         return 0u;
     }
@@ -685,8 +715,8 @@ int pgrc_mem_get_counters(pgrc_mem_ctx *m, pgrc_mem_counters *out) {
     return PGRC_OK;
 }
 
-int pgrc_mem_set_src_ascii(pgrc_mem_ctx *m, const char *src, uint64_t n) {
-    if (!m || !src) return PGRC_E_PARAM;
+// what both forms of "set the source" share: the old source's state forgotten, `pack` puts the text into the base context, the index
+static int mem_set_src(pgrc_mem_ctx *m, const char *host_src, uint64_t n, int (*pack)(pgrc_mem_ctx *, const void *, uint64_t), const void *text) {
     pgrc_match_ctx *c = m->base;
     m->have_src = false;
     m->map_ready = false;
@@ -694,7 +724,7 @@ int pgrc_mem_set_src_ascii(pgrc_mem_ctx *m, const char *src, uint64_t n) {
     PgrcDeviceScope dev_scope__(c->device);
     if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     const auto t0 = std::chrono::steady_clock::now();
-    int e = pgrc_match_set_pg_ascii(c, src, n);
+    int e = pack(m, text, n);
     if (!e) e = pgrc_copmem_build_index(c, 0);
     if (!e && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "index build failed"; e = PGRC_E_DEVICE; }
     if (e) { m->err = c->err; return e; }
@@ -702,17 +732,60 @@ int pgrc_mem_set_src_ascii(pgrc_mem_ctx *m, const char *src, uint64_t n) {
     m->K = c->cp.K; m->k1 = c->cp.k1; m->k2 = c->cp.k2;
     m->LK2 = ((int)m->L - m->K) / 2;                       // CopMEMMatcher.cpp:87-89
     m->KLK24 = m->K + m->LK2 - 4;
-    m->src = src;
+    m->src = host_src;
     m->N = n;
     m->have_src = true;
     return PGRC_OK;
 }
 
+// is p memory of the context's device?  (anything else -- host memory, pageable or page-locked, another device's -- is refused)
+static bool mem_on_device(const pgrc_mem_ctx *m, const void *p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();                 // (pageable host memory is unknown to the runtime: not an error to keep)
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice && at.device == m->base->device;
+}
+
+int pgrc_mem_set_src_ascii(pgrc_mem_ctx *m, const char *src, uint64_t n) {
+    if (!m || !src) return PGRC_E_PARAM;
+    return mem_set_src(m, src, n, [](pgrc_mem_ctx *mm, const void *text, uint64_t len) -> int { return pgrc_match_set_pg_ascii(mm->base, (const char *)text, len); }, src);
+}
+
+int pgrc_mem_set_src_device(pgrc_mem_ctx *m, const void *d_ascii, uint64_t n) {
+    if (!m || !d_ascii) return PGRC_E_PARAM;
+    if (!mem_on_device(m, d_ascii)) {
+        m->have_src = false;
+        m->map_ready = false;
+        for (bool &set : m->res_set) set = false;
+        m->err = "set_src_device: the text is not memory of the context's device";
+        return PGRC_E_PARAM;
+    }
+    // the text is packed into the context's own words by k_mem_pack_dev (no N map: an N is as wrong here as any other symbol),
+    // and the flag is read back before the call returns: nothing of the caller's buffer is read afterwards
+    return mem_set_src(m, nullptr, n, [](pgrc_mem_ctx *mm, const void *text, uint64_t len) -> int {
+        pgrc_match_ctx *c = mm->base;
+        int e = pgrc_pg_alloc(c, len);
+        if (!e) e = pgrc_buf_ensure(c, mm->d_flag, 4);
+        if (e) return e;
+        HIP_TRY(c, hipMemsetAsync(mm->d_flag.p, 0, 4, c->stream));
+        if ((e = pgrc_launch_mem_pack_device(c, (const uint8_t *)text, len, false, (uint32_t *)c->pg2[0].p, nullptr, c->pg_words, (uint32_t *)mm->d_flag.p, 0))) return e;
+        uint32_t fl = 0;
+        HIP_TRY(c, hipMemcpyAsync(&fl, mm->d_flag.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (fl) { c->err = "pseudogenome contains a symbol outside ACGT"; return PGRC_E_SYMBOL; }
+        c->have_pg = true;
+        return PGRC_OK;
+    }, d_ascii);
+}
+
 void pgrc_mem_free_matches(pgrc_text_match *p) { free(p); }
 
-int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int dest_is_src, int rev_compl, uint32_t min_len,
-                         pgrc_text_match **matches, uint64_t *count) {
-    if (!m || !dest || !matches || !count) return PGRC_E_PARAM;
+// matchTexts over a destination on the host (dest: the text as matched, reverse-complemented already when rev_compl) or in HBM
+// (dest == null, d_ascii: the FORWARD text, which the packing kernel reverse-complements; it may be null with dest_is_src)
+static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, uint64_t N2, int dest_is_src, int rev_compl, uint32_t min_len,
+                     pgrc_text_match **matches, uint64_t *count) {
     *matches = nullptr;
     *count = 0;
     m->map_ready = false;                 // (a failed call leaves no destination for pgrc_mem_mark_and_remove)
@@ -721,6 +794,7 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     if ((int)min_len < m->K) { m->err = "Minimal matching length cannot be smaller than K"; return PGRC_E_PARAM; }   // :606-609
     if (dest_is_src && N2 != m->N) { m->err = "match_texts: dest_is_src with a text of another length"; return PGRC_E_PARAM; }
     if (N2 / (uint64_t)m->k2 + 1 >= (1ull << 40)) { m->err = "destination text too long"; return PGRC_E_PARAM; }
+    if (d_ascii && !mem_on_device(m, d_ascii)) { m->err = "match_texts_device: the destination is not memory of the context's device"; return PGRC_E_PARAM; }
     PgrcDeviceScope dev_scope__(c->device);
     if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     m->ctr.probes = m->ctr.events = m->ctr.stale_lookups = 0;
@@ -749,11 +823,20 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     } else {
         const uint64_t CH = 64ull << 20;
         if ((e = pgrc_buf_ensure(c, m->d_dest, (dwords + PGRC_PG_PAD_WORDS) * 4)) || (e = pgrc_buf_ensure(c, m->d_nmap, (dwords + PGRC_PG_PAD_WORDS) * 2)) ||
-            (e = pgrc_buf_ensure(c, m->d_stage, (size_t)std::max<uint64_t>(16, std::min(CH, N2)))) || (e = pgrc_buf_ensure(c, m->d_flag, 4))) { m->err = c->err; return e; }
-        (void)hipMemsetAsync(m->d_dest.p, 0, (dwords + PGRC_PG_PAD_WORDS) * 4, c->stream);
-        (void)hipMemsetAsync(m->d_nmap.p, 0, (dwords + PGRC_PG_PAD_WORDS) * 2, c->stream);
+            (dest && (e = pgrc_buf_ensure(c, m->d_stage, (size_t)std::max<uint64_t>(16, std::min(CH, N2))))) || (e = pgrc_buf_ensure(c, m->d_flag, 4))) { m->err = c->err; return e; }
         (void)hipMemsetAsync(m->d_flag.p, 0, 4, c->stream);
-        for (uint64_t off = 0; off < N2; off += CH) {
+        if (!dest) {
+            // the text is in HBM: ONE launch packs it whole, reverse-complemented on the way if need be, and writes the zero pad
+            // behind it too (k_mem_pack_dev, mempack.hip); the flag's download below ends the reading of the caller's buffer
+            if ((e = pgrc_launch_mem_pack_device(c, d_ascii, N2, rev_compl != 0, (uint32_t *)m->d_dest.p, (uint16_t *)m->d_nmap.p, dwords + PGRC_PG_PAD_WORDS,
+                                                 (uint32_t *)m->d_flag.p, 0))) { m->err = c->err; return e; }
+            const hipError_t he = hipStreamSynchronize(c->stream);
+            if (he != hipSuccess) { m->err = std::string("destination packing: ") + hipGetErrorString(he); return PGRC_E_DEVICE; }
+        } else {
+            (void)hipMemsetAsync(m->d_dest.p, 0, (dwords + PGRC_PG_PAD_WORDS) * 4, c->stream);
+            (void)hipMemsetAsync(m->d_nmap.p, 0, (dwords + PGRC_PG_PAD_WORDS) * 2, c->stream);
+        }
+        for (uint64_t off = 0; dest && off < N2; off += CH) {
             const uint64_t len = std::min(CH, N2 - off);
             hipError_t he = hipMemcpyAsync(m->d_stage.p, dest + off, len, hipMemcpyHostToDevice, c->stream);
             if (he == hipSuccess) {
@@ -952,16 +1035,16 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
         HIP_TRY(m, hipMemcpy(&p, ep + x, 8, hipMemcpyDeviceToHost));
         HIP_TRY(m, hipMemcpy(&fl8, (const uint8_t *)m->d_oflag.p + x, 1, hipMemcpyDeviceToHost));
         StaleWalk sw;
-        sw.m = m; sw.dest = dest; sw.N2 = N2; sw.dest_is_src = dest_is_src != 0; sw.rev_compl = rev_compl != 0;
+        sw.m = m; sw.dest = dest; sw.d_dw = a.dest; sw.d_dn = a.nmap; sw.N2 = N2; sw.dest_is_src = dest_is_src != 0; sw.rev_compl = rev_compl != 0;
         sw.skip = ra.skip; sw.nmain = nmain; sw.d_ek = ek; sw.d_outc = (const uint8_t *)m->d_outc.p; sw.nev = nev; sw.d_range = d_range;
         const uint64_t t = key >> 4, q = t * k2;
         const uint32_t order = (uint32_t)(key & 15u), fl = fl8;
         m->ctr.stale_lookups++;
         // (c) with the registers as the reference holds them (:401-404)
-        const uint32_t l1 = (fl & MF_L1_OK) ? le32(m->src + p - m->LK2) : sw.stale_src_reg(true, t, order);
-        const uint32_t r1 = (fl & MF_R1_OK) ? le32(m->src + p + m->KLK24) : sw.stale_src_reg(false, t, order);
-        const uint32_t l2 = (fl & MF_L2_OK) ? le32(dest + q - m->LK2) : 0u;   // windows below LK2 come first: still the initial 0
-        const uint32_t r2 = (fl & MF_R2_OK) ? le32(dest + q + m->KLK24) : sw.stale_r2(t);
+        const uint32_t l1 = (fl & MF_L1_OK) ? sw.src32(p - m->LK2) : sw.stale_src_reg(true, t, order);
+        const uint32_t r1 = (fl & MF_R1_OK) ? sw.src32(p + m->KLK24) : sw.stale_src_reg(false, t, order);
+        const uint32_t l2 = (fl & MF_L2_OK) ? sw.dest32(q - m->LK2) : 0u;     // windows below LK2 come first: still the initial 0
+        const uint32_t r2 = (fl & MF_R2_OK) ? sw.dest32(q + m->KLK24) : sw.stale_r2(t);
         if (sw.lookup_err) { m->err = "bucket lookup failed"; return PGRC_E_DEVICE; }
         hipLaunchKernelGGL(k_mem_resolve, dim3(1), dim3(1), 0, c->stream, x, (r1 == r2 || l1 == l2) ? 1 : 0, (uint8_t *)m->d_oflag.p,
                            (const uint32_t *)d_lid, (uint32_t *)m->d_ebin.p);
@@ -994,6 +1077,19 @@ int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int des
     (void)hipEventElapsedTime(&m->ctr.ms_replay, ev[3], ev[4]);                       // (with the host's part between the rounds)
     m->ctr.ms_host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - th0).count();
     return done();
+}
+
+int pgrc_mem_match_texts(pgrc_mem_ctx *m, const char *dest, uint64_t N2, int dest_is_src, int rev_compl, uint32_t min_len,
+                         pgrc_text_match **matches, uint64_t *count) {
+    if (!m || !dest || !matches || !count) return PGRC_E_PARAM;
+    return mem_match(m, dest, nullptr, N2, dest_is_src, rev_compl, min_len, matches, count);
+}
+
+int pgrc_mem_match_texts_device(pgrc_mem_ctx *m, const void *d_dest_ascii, uint64_t N2, int dest_is_src, int rev_compl, uint32_t min_len,
+                                pgrc_text_match **matches, uint64_t *count) {
+    if (!m || (!d_dest_ascii && !dest_is_src) || !matches || !count) return PGRC_E_PARAM;
+    // (with dest_is_src the library matches its own copy of the source: the pointer is not read and may be null)
+    return mem_match(m, nullptr, (const uint8_t *)d_dest_ascii, N2, dest_is_src, rev_compl, min_len, matches, count);
 }
 
 } // extern "C"

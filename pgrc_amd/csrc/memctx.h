@@ -10,7 +10,7 @@ struct pgrc_mem_ctx {
     pgrc_match_ctx *base = nullptr;   // owns the packed source, its reverse complement and the seed index
     uint32_t L = 0;
     int K = 0, k1 = 0, k2 = 0, LK2 = 0, KLK24 = 0;
-    const char *src = nullptr;        // borrowed host text
+    const char *src = nullptr;        // borrowed host text; null after pgrc_mem_set_src_device (the packed words are all there is)
     uint64_t N = 0;
     bool have_src = false;
     DevBuf d_dest, d_nmap, d_stage, d_flag, d_cursor, d_evk[2], d_evv[2], d_tmp, d_scan, d_orun, d_oflag;

@@ -1,10 +1,10 @@
 // selftest.hip -- test entries into the shared primitives: scanops.h's block scan and device scan, radix.hip's stable sort and
-// segment sort; and into the hand-over: pack.hip's text and read kernels, and what a context holds of its reads and its text
-// after them.  Thin kernels and host wrappers, nothing else; linked with the product's objects into libpgrc_selftest.so
-// (never into libpgrc_match.so).  tests/test_gpu_primitives.py and tests/test_gpu_handover.py drive it against numpy
-// (DESIGN.md 4.12).
+// segment sort; and into the hand-over: pack.hip's text and read kernels, mempack.hip's packing of a text that is in HBM already,
+// and what a context holds of its reads and its text after them.  Thin kernels and host wrappers, nothing else; linked with the product's objects into libpgrc_selftest.so
+// (never into libpgrc_match.so).  tests/test_gpu_primitives.py, tests/test_gpu_handover.py and tests/test_gpu_memdev.py
+// drive it against numpy.
 //
-// Every entry takes host arrays, runs on the handle's device and returns host arrays.  Every device buffer that a primitive
+// Every entry takes host arrays (pgrc_selftest_mem_pack_device: its text at a device address), runs on the handle's device and returns host arrays.  Every device buffer that a primitive
 // writes has a guard zone of ST_GUARD elements after its logical end, filled with ST_FILL bytes like the buffer itself; the
 // entry reports in *guards which zones are still intact (one bit per zone).  The scan's fold scratch has exactly
 // sco_scratch_elems(n) elements in front of its guard.
@@ -357,6 +357,76 @@ extern "C" int pgrc_selftest_pack_text(pgrc_selftest *h, const uint8_t *ascii, u
     HIP_TRY(c, dflag.intact(&ok_f));
     *guards = (ok_w ? 1u : 0u) | (ok_f ? 2u : 0u);
     return PGRC_OK;
+}
+
+// pgrc_launch_mem_pack_device (mempack.hip; tests/test_gpu_memdev.py) over the n >= 1 ASCII bytes at the DEVICE address d_ascii,
+// which may have any alignment, forward or reverse-complemented, in at most block_cap blocks (0: no cap of the entry's own; a
+// small cap makes a short text loop in the grid stride).  As the matcher asks for it: ceil(n / 16) + PGRC_PG_PAD_WORDS words
+// and as many 16-bit N masks (with_nmap = 0: none, out_nmap comes back as ST_FILL bytes), all pre-filled with ST_FILL; the flag
+// word starts as zero.  *guards: bit 0 the zone after the words, bit 1 after the N map, bit 2 after the flag word.
+extern "C" int pgrc_selftest_mem_pack_device(pgrc_selftest *h, const void *d_ascii, uint64_t n, int reversed, uint32_t block_cap, int with_nmap,
+                                             uint32_t *out_words, uint16_t *out_nmap, uint32_t *out_flags, uint32_t *guards) {
+    PgrcDev *c = &h->dev;
+    PGRC_ON_DEVICE(c);
+    if (!n || !d_ascii) {
+        c->err = "selftest: an empty text launches nothing";
+        return PGRC_E_PARAM;
+    }
+    const uint64_t total = (n + 15) / 16 + PGRC_PG_PAD_WORDS;
+    StBuf dw, dn, dflag;
+    HIP_TRY(c, dw.alloc(total * 4, ST_GUARD * 4));
+    HIP_TRY(c, dn.alloc(total * 2, ST_GUARD * 2));
+    HIP_TRY(c, dflag.alloc(4, ST_GUARD * 4));
+    HIP_TRY(c, hipMemset(dflag.p, 0, 4));
+    HIP_TRY(c, hipDeviceSynchronize());          // (the caller's text may have been written on another stream)
+    const int e = pgrc_launch_mem_pack_device(c, (const uint8_t *)d_ascii, n, reversed != 0, (uint32_t *)dw.p, with_nmap ? (uint16_t *)dn.p : nullptr, total,
+                                              (uint32_t *)dflag.p, block_cap);
+    if (e) return e;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_words, dw.p, total * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_nmap, dn.p, total * 2, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_flags, dflag.p, 4, hipMemcpyDeviceToHost));
+    const StBuf *zone[3] = {&dw, &dn, &dflag};
+    *guards = 0;
+    for (int k = 0; k < 3; k++) {
+        bool ok;
+        HIP_TRY(c, zone[k]->intact(&ok));
+        *guards |= (ok ? 1u : 0u) << k;
+    }
+    return PGRC_OK;
+}
+
+// The same launch `repeats` times into buffers made once, HIP events around each: ms[0 .. repeats) is the kernel's device time
+// (tools/mem_resident_rate.py sets it beside a device-to-device copy of the text's bytes).  No guard zones, nothing comes back.
+extern "C" int pgrc_selftest_mem_pack_time(pgrc_selftest *h, const void *d_ascii, uint64_t n, int reversed, uint32_t repeats, float *ms) {
+    PgrcDev *c = &h->dev;
+    PGRC_ON_DEVICE(c);
+    if (!n || !d_ascii || !ms) {
+        c->err = "selftest: an empty text launches nothing";
+        return PGRC_E_PARAM;
+    }
+    const uint64_t total = (n + 15) / 16 + PGRC_PG_PAD_WORDS;
+    StBuf dw, dn, dflag;
+    HIP_TRY(c, dw.alloc(total * 4, 0));
+    HIP_TRY(c, dn.alloc(total * 2, 0));
+    HIP_TRY(c, dflag.alloc(4, 0));
+    hipEvent_t ev[2];
+    HIP_TRY(c, hipEventCreate(&ev[0]));
+    HIP_TRY(c, hipEventCreate(&ev[1]));
+    HIP_TRY(c, hipDeviceSynchronize());
+    int e = PGRC_OK;
+    for (uint32_t r = 0; r < repeats && !e; r++) {
+        (void)hipEventRecord(ev[0], c->stream);
+        e = pgrc_launch_mem_pack_device(c, (const uint8_t *)d_ascii, n, reversed != 0, (uint32_t *)dw.p, (uint16_t *)dn.p, total, (uint32_t *)dflag.p, 0);
+        (void)hipEventRecord(ev[1], c->stream);
+        if (!e && (hipEventSynchronize(ev[1]) != hipSuccess || hipEventElapsedTime(&ms[r], ev[0], ev[1]) != hipSuccess)) {
+            c->err = "selftest: timing the packing kernel failed";
+            e = PGRC_E_DEVICE;
+        }
+    }
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    return e;
 }
 
 // pgrc_launch_revcomp over ceil(G / 16) host words, G >= 1.  The forward buffer carries PGRC_PG_PAD_WORDS zero words behind the

@@ -23,19 +23,52 @@ class CopMEMMatcher:
     (matching/copmem/CopMEMMatcher.cpp:571-591, :604-622)."""
 
     def __init__(self, srcText, targetMatchLength: int, minMatchLength: int = UINT32_MAX, device: int = -1):
+        """srcText None: a matcher without a source yet; setSrcDevice gives it one that is already on the device."""
         self._h = C.c_void_p()
         rc = lib.pgrc_mem_create(int(targetMatchLength), int(minMatchLength), int(device), C.byref(self._h))
         if rc:
             raise PgrcMatchError(rc, (lib.pgrc_mem_last_error(None) or b"").decode())
         self.targetMatchLength = int(targetMatchLength)
-        self._src = _ascii(srcText)          # the library borrows the text: keep it alive
+        self._src = None
         self._last_n2 = 0
         self._res_len = [0, 0, 0]            # the mapped texts kept on the device (markAndRemoveExactMatchesResident)
-        self._ck(lib.pgrc_mem_set_src_ascii(self._h, self._src.ctypes.data_as(C.c_void_p), self._src.size))
+        if srcText is not None:
+            self._src = _ascii(srcText)      # the library borrows the text: keep it alive
+            self._ck(lib.pgrc_mem_set_src_ascii(self._h, self._src.ctypes.data_as(C.c_void_p), self._src.size))
 
     def _ck(self, rc: int) -> None:
         if rc:
             raise PgrcMatchError(rc, (lib.pgrc_mem_last_error(self._h) or b"").decode())
+
+    def setSrcDevice(self, ptr: int, n: int) -> None:
+        """the source text from `n` ASCII bytes at the raw device address `ptr` (PgAssembler.text_device()): packed into the
+        matcher's own words and indexed; the buffer is not read after the call."""
+        self._last_n2 = 0
+        self._res_len = [0, 0, 0]
+        self._ck(lib.pgrc_mem_set_src_device(self._h, C.c_void_p(int(ptr)), int(n)))
+        self._src = None                     # (the host text of an earlier source is borrowed no longer)
+
+    def _matches(self, out, cnt) -> np.ndarray:
+        n = cnt.value
+        res = np.zeros((n, 3), dtype=np.uint64)
+        if n:
+            res[:] = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint64)), shape=(n * 3,)).reshape(n, 3)
+            lib.pgrc_mem_free_matches(out)
+        return res
+
+    def matchTextsDevice(self, ptr: int, n2: int, destIsSrc: bool, revComplMatching: bool, minMatchLength: int | None = None) -> np.ndarray:
+        """matchTexts over `n2` ASCII bytes at the raw device address `ptr`, the destination in its FORWARD orientation: with
+        revComplMatching the library reverse-complements it on the device.  -> the matches that matchTexts returns for the
+        host-reversed text.  With destIsSrc `ptr` may be 0."""
+        self._last_n2 = 0
+        out = C.POINTER(_lib.TextMatch)()
+        cnt = C.c_uint64(0)
+        self._ck(lib.pgrc_mem_match_texts_device(self._h, C.c_void_p(int(ptr)) if ptr else None, int(n2), int(bool(destIsSrc)),
+                                                 int(bool(revComplMatching)),
+                                                 self.targetMatchLength if minMatchLength is None else int(minMatchLength),
+                                                 C.byref(out), C.byref(cnt)))
+        self._last_n2 = int(n2)
+        return self._matches(out, cnt)
 
     def matchTexts(self, destText, destIsSrc: bool, revComplMatching: bool, minMatchLength: int | None = None) -> np.ndarray:
         """-> uint64 array [count, 3] of (posSrcText, length, posDestText), discovery order.  destText is the text as
@@ -48,13 +81,8 @@ class CopMEMMatcher:
                                           int(bool(revComplMatching)),
                                           self.targetMatchLength if minMatchLength is None else int(minMatchLength),
                                           C.byref(out), C.byref(cnt)))
-        n = cnt.value
         self._last_n2 = d.size               # (the destination stays on the device: markAndRemoveExactMatches maps it)
-        res = np.zeros((n, 3), dtype=np.uint64)
-        if n:
-            res[:] = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint64)), shape=(n * 3,)).reshape(n, 3)
-            lib.pgrc_mem_free_matches(out)
-        return res
+        return self._matches(out, cnt)
 
     def markAndRemoveExactMatches(self, matches, minMatchLength: int | None = None, mapped_out: np.ndarray | None = None):
         """markAndRemoveExactMatches (matching/SimplePgMatcher.cpp:69-148) of the destination of the last matchTexts call,
