@@ -17,6 +17,7 @@
 #include <stdio.h>
 #include <condition_variable>
 #include <deque>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -245,6 +246,52 @@ void pgrc_buf_free_all(DevBuf *const *bufs, size_t count);   // one wait for the
 // the unpooled one: grow-only, exactly `bytes` (64 at least) from hipMalloc, given back with dec_free
 int pgrc_buf_unpooled(PgrcDev *c, DevBuf &b, size_t bytes);
 bool pgrc_host_pinned(const void *p);   // a host pointer that HIP knows as page-locked: copies to and from it need no staging
+
+static void dec_free(DevBuf &b) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+}
+
+// A context names its unpooled buffers once, in a function that returns this list: its destroy function frees the list, and
+// whatever else needs all of them walks it
+typedef std::vector<DevBuf *> DevBufList;
+static void dec_free_all(const DevBufList &bufs) {
+    for (DevBuf *b : bufs) dec_free(*b);
+}
+
+// pgrc_buf_unpooled for every {buffer, bytes} in turn; the first error ends it
+static int pgrc_bufs_unpooled(PgrcDev *c, std::initializer_list<std::pair<DevBuf *, size_t>> want) {
+    for (const auto &w : want)
+        if (int e = pgrc_buf_unpooled(c, *w.first, w.second)) return e;
+    return PGRC_OK;
+}
+
+static float dec_elapsed(hipEvent_t a, hipEvent_t b) {       // 0 if either event was never recorded
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return ms;
+}
+
+// The timing events of a call's phases: made on first use, recorded on a stream, read in pairs, given back with the context
+template <int N>
+struct PhaseEvents {
+    hipEvent_t ev[N]{};
+    template <typename Ctx>     // (a PgrcDev, or the Pg-vs-Pg matcher's context with an error text of its own)
+    int ensure(Ctx *c) {
+        for (hipEvent_t &ev : this->ev)
+            if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+        return PGRC_OK;
+    }
+    hipError_t record(int k, hipStream_t stream) { return hipEventRecord(ev[k], stream); }
+    float ms(int a, int b) const { return dec_elapsed(ev[a], ev[b]); }
+    void release() {
+        for (hipEvent_t &ev : this->ev) {
+            if (ev) (void)hipEventDestroy(ev);
+            ev = nullptr;
+        }
+    }
+};
 
 // api.hip: (re)allocates and clears both strands' text buffers for a text of G symbols
 extern "C" int pgrc_pg_alloc(pgrc_match_ctx *c, uint64_t G);

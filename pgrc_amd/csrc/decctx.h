@@ -1,20 +1,14 @@
 // decctx.h -- the decode context of include/pgrc_decode.h and the helpers its sources share: decode.hip (the reads
 // rebuild), restore.hip (the restore of the matched pseudogenomes), pairpos.hip (the pair positions of the paired ORD mode),
 // pairorder.hip (the pair order of the paired non-ORD mode) and listarchive.hip (the archive form of a list's mismatch streams).
+// What it shares with the other stages -- the stream, the staging buffers, the copies through them -- is stagectx.h's PgrcStage.
 #pragma once
 
-#include <string.h>
-
-#include <algorithm>
-#include <string>
-
-#include "ctx.h"
 #include "pgrc_decode.h"
-#include "scanops.h"
+#include "stagectx.h"
 
 #define DEC_TPB 256
 #define DEC_TEXT_PAD 64         // zero bytes after the text: aligned 16-byte loads past a window's end stay inside
-#define DEC_STAGE_BYTES (64ull << 20)
 
 // error flags of the device checks (the word at pgrc_decode_ctx::flag)
 #define DEC_F_WINDOW 1u         // a window reaches past the text end
@@ -23,13 +17,12 @@
 #define DEC_F_MISSYM 8u         // a mismatch code outside its form's range
 #define DEC_F_NOPOS 16u         // a row needs the positions of a list that has none
 
-struct pgrc_decode_ctx : PgrcDev {
+struct pgrc_decode_ctx : PgrcStage {
     uint32_t L = 0;
     hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_made[2]{}, ev_copied[2]{}, ev_k0[2]{}, ev_a{}, ev_b{};
-    uint8_t *stage[2]{};        // pinned staging (uploads and downloads of pageable memory)
+    hipEvent_t ev_made[2]{}, ev_k0[2]{}, ev_a{}, ev_b{};
     DevBuf chunk[2];            // device chunks of rows
-    DevBuf text, flag, scratch;
+    DevBuf text;
     uint64_t text_len = 0;
     bool have_text = false;
     struct List {
@@ -56,23 +49,26 @@ struct pgrc_decode_ctx : PgrcDev {
     // and per-far-pair arrays, the device-side output, scan scratch; pp_sort: the scratch of radix.hip's sort
     DevBuf pp_in, pp_rec[2], pp_val[2], pp_rank, pp_far, pp_out, pp_bsum;
     DevBuf pp_sort;
-    hipEvent_t pp_ev[6]{};
+    PhaseEvents<6> pp_ev;
     bool have_pp_timing = false;
     pgrc_pairpos_timing ptm{};
     // the pair-order coding (pairorder.hip): the joined orgIdx, rev, per-entry and per-pair arrays, the device-side streams,
     // scan scratch and the two error words
     DevBuf po_in, po_rev, po_ent, po_pair, po_out, po_bsum;
-    hipEvent_t po_ev[11]{};
+    PhaseEvents<11> po_ev;
     bool have_po_timing = false;
     pgrc_pairorder_timing potm{};
     // the archive form of the mismatch streams (listarchive.hip): the uploaded streams, the flag scan, the counts (decode),
     // the mismatch-list starts (encode), the count matrix and its scan scratch, the per-count words, the device-side block
     DevBuf la_in, la_inc, la_cnt, la_mcum, la_mat, la_fold, la_small, la_out;
-    hipEvent_t la_ev[8]{};
+    PhaseEvents<5> la_ev;
     bool have_la_timing = false;
     pgrc_list_archive_timing latm{};
 };
 
+// decode.hip: pgrc_decode_create without a read length, for the stages that keep a decode context for what it holds and runs
+// and give every call its own length (pgasm.hip: the text; rlist.hip: the list archive, the pair order, the pair positions)
+int pgrc_decode_create_on(int32_t device, pgrc_decode_ctx **out);
 // pairpos.hip: the file-major positions of `s` as n_total u64 at d_out (device, on d->stream; synchronised on return);
 // fills d->ptm but for ms_download / ms_call
 int pgrc_pairpos_decode_device(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint64_t *d_out);
@@ -86,63 +82,10 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
 // decode.hip: pgrc_decode_add_list, with the mismatches from `arch` when it is given
 int pgrc_dec_add_list(pgrc_decode_ctx *d, const pgrc_decode_list *a, const pgrc_list_archive_streams *arch);
 
-static int dec_fail(pgrc_decode_ctx *d, int code, const std::string &msg) {
-    d->err = msg;
-    return code;
-}
-
-static void dec_free(DevBuf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-}
-
-static float dec_elapsed(hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return ms;
-}
-
-static int dec_clear_err(pgrc_decode_ctx *d) {
-    HIP_TRY(d, hipMemsetAsync(d->flag.p, 0, 4, d->stream));
-    return PGRC_OK;
-}
-
-// host -> device through the two pinned staging buffers: the copy of one overlaps the host's fill of the other
-static int dec_upload(pgrc_decode_ctx *d, void *d_dst, const void *h_src, uint64_t bytes) {
-    const uint8_t *src = (const uint8_t *)h_src;
-    uint8_t *dst = (uint8_t *)d_dst;
-    int k = 0;
-    for (uint64_t o = 0; o < bytes; o += DEC_STAGE_BYTES, k ^= 1) {
-        const uint64_t c = std::min<uint64_t>(DEC_STAGE_BYTES, bytes - o);
-        HIP_TRY(d, hipEventSynchronize(d->ev_copied[k]));
-        memcpy(d->stage[k], src + o, c);
-        HIP_TRY(d, hipMemcpyAsync(dst + o, d->stage[k], c, hipMemcpyHostToDevice, d->stream));
-        HIP_TRY(d, hipEventRecord(d->ev_copied[k], d->stream));
-    }
-    return PGRC_OK;
-}
-
-// the same from memory that may be page-locked: then the copy engine reads it where it is
-static int dec_upload_host(pgrc_decode_ctx *d, void *dst, const void *src, uint64_t bytes) {
-    if (!bytes || !pgrc_host_pinned(src)) return dec_upload(d, dst, src, bytes);
-    HIP_TRY(d, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d->stream));
-    return PGRC_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ scans (u64 results)
 struct XfU8 { const uint8_t *p; __device__ uint64_t operator()(uint64_t i) const { return p[i]; } };
 struct XfU16 { const uint16_t *p; __device__ uint64_t operator()(uint64_t i) const { return p[i]; } };
 struct XfBelow { const uint64_t *p; uint64_t lim; __device__ uint64_t operator()(uint64_t i) const { return p[i] < lim ? 1u : 0u; } };
-
-// out[i] = base_val + (INCLUSIVE ? sum of xf(0..i) : sum of xf(0..i-1)); the exclusive form also writes out[n] = base_val + total
-template <bool INCLUSIVE, typename Xf>
-static int dec_scan(pgrc_decode_ctx *d, Xf xf, uint64_t n, uint64_t base_val, uint64_t *d_out) {
-    int e;
-    if ((e = pgrc_buf_unpooled(d, d->scratch, sco_scratch_elems(n) * sizeof(uint64_t)))) return e;
-    HIP_TRY(d, (sco_device_scan<INCLUSIVE, true>(d->stream, xf, n, ScoPlus{}, (uint64_t)0, base_val, ScoStore<uint64_t>{d_out}, (uint64_t *)d->scratch.p)));
-    return PGRC_OK;
-}
 
 // complementsLut (helper.cpp:243-262): IUPAC complements of both cases to upper case, every other byte to 0
 static __device__ __forceinline__ uint8_t dec_complement(uint32_t c) {

@@ -292,37 +292,62 @@ static int dec_check_err(pgrc_decode_ctx *d, const char *what) {
     return dec_fail(d, PGRC_E_PARAM, m);
 }
 
-extern "C" {
-
-int pgrc_decode_create(uint32_t read_length, int32_t device, pgrc_decode_ctx **out) {
-    if (!out) return PGRC_E_PARAM;
-    *out = nullptr;
-    if (read_length < 1 || read_length > 255) { g_dec_create_err = "read length must be in [1, 255]"; return PGRC_E_PARAM; }
+int pgrc_stage_open(PgrcStage *s, int32_t device, std::string *create_err) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         (void)hipGetLastError();
-        g_dec_create_err = "no HIP device";
+        *create_err = "no HIP device";
         return PGRC_E_NO_DEVICE;
     }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) { g_dec_create_err = "hipGetDevice failed"; return PGRC_E_NO_DEVICE; }
-    if (device >= ndev) { g_dec_create_err = "device " + std::to_string(device) + " does not exist"; return PGRC_E_NO_DEVICE; }
-    pgrc_decode_ctx *d = new pgrc_decode_ctx();
-    d->L = read_length;
-    d->device = device;
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) { *create_err = "hipGetDevice failed"; return PGRC_E_NO_DEVICE; }
+    if (device >= ndev) { *create_err = "device " + std::to_string(device) + " does not exist"; return PGRC_E_NO_DEVICE; }
+    s->device = device;
     PgrcDeviceScope scope(device);
     int e = PGRC_OK;
     if (!scope.ok) e = PGRC_E_NO_DEVICE;
-    if (!e && (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess ||
-               hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking) != hipSuccess))
-        e = PGRC_E_DEVICE;
+    if (!e && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) e = PGRC_E_DEVICE;
     for (int k = 0; k < 2 && !e; k++)
-        if (hipEventCreateWithFlags(&d->ev_copied[k], hipEventDisableTiming) != hipSuccess || hipEventCreate(&d->ev_made[k]) != hipSuccess ||
-            hipEventCreate(&d->ev_k0[k]) != hipSuccess || hipHostMalloc((void **)&d->stage[k], DEC_STAGE_BYTES) != hipSuccess)
+        if (hipEventCreateWithFlags(&s->ev_copied[k], hipEventDisableTiming) != hipSuccess || hipHostMalloc((void **)&s->stage[k], DEC_STAGE_BYTES) != hipSuccess)
             e = PGRC_E_ALLOC;
-    if (!e && (hipEventCreate(&d->ev_a) != hipSuccess || hipEventCreate(&d->ev_b) != hipSuccess)) e = PGRC_E_DEVICE;
-    if (!e) e = pgrc_buf_unpooled(d, d->flag, 16);
+    if (!e) e = pgrc_buf_unpooled(s, s->flag, 16);
     if (e) {
-        g_dec_create_err = d->err.empty() ? "HIP stream / event / pinned buffer creation failed" : d->err;
+        *create_err = s->err.empty() ? "HIP stream / event / pinned buffer creation failed" : s->err;
+        (void)hipGetLastError();
+        pgrc_stage_close(s);
+    }
+    return e;
+}
+
+void pgrc_stage_close(PgrcStage *s) {
+    PgrcDeviceScope scope(s->device);
+    if (s->stream) (void)hipStreamSynchronize(s->stream);
+    dec_free_all({&s->flag, &s->scratch});
+    for (int k = 0; k < 2; k++) {
+        if (s->stage[k]) (void)hipHostFree(s->stage[k]);
+        if (s->ev_copied[k]) (void)hipEventDestroy(s->ev_copied[k]);
+        s->stage[k] = nullptr;
+        s->ev_copied[k] = nullptr;
+    }
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    s->stream = nullptr;
+}
+
+// the decoder's own members on an open stage; the exported create adds the read length
+int pgrc_decode_create_on(int32_t device, pgrc_decode_ctx **out) {
+    *out = nullptr;
+    pgrc_decode_ctx *d = new pgrc_decode_ctx();
+    int e = pgrc_stage_open(d, device, &g_dec_create_err);
+    if (e) {
+        delete d;
+        return e;
+    }
+    PgrcDeviceScope scope(d->device);
+    if (hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking) != hipSuccess) e = PGRC_E_DEVICE;
+    for (int k = 0; k < 2 && !e; k++)
+        if (hipEventCreate(&d->ev_made[k]) != hipSuccess || hipEventCreate(&d->ev_k0[k]) != hipSuccess) e = PGRC_E_ALLOC;
+    if (!e && (hipEventCreate(&d->ev_a) != hipSuccess || hipEventCreate(&d->ev_b) != hipSuccess)) e = PGRC_E_DEVICE;
+    if (e) {
+        g_dec_create_err = "HIP stream / event / pinned buffer creation failed";
         (void)hipGetLastError();
         pgrc_decode_destroy(d);
         return e;
@@ -331,28 +356,37 @@ int pgrc_decode_create(uint32_t read_length, int32_t device, pgrc_decode_ctx **o
     return PGRC_OK;
 }
 
+static DevBufList dec_bufs(pgrc_decode_ctx *d) {
+    DevBufList all = {&d->chunk[0], &d->chunk[1], &d->text, &d->rl_order, &d->org2pos, &d->rank, &d->rs_mapped, &d->rs_marks, &d->rs_vals, &d->rs_ptr, &d->rs_bsum,
+                      &d->rs_coded, &d->rs_join};
+    for (auto &l : d->lst) all.insert(all.end(), {&l.pos, &l.rc, &l.mcum, &l.moff, &l.msym, &l.raw});
+    return all;
+}
+
+extern "C" {
+
+int pgrc_decode_create(uint32_t read_length, int32_t device, pgrc_decode_ctx **out) {
+    if (!out) return PGRC_E_PARAM;
+    *out = nullptr;
+    if (read_length < 1 || read_length > 255) { g_dec_create_err = "read length must be in [1, 255]"; return PGRC_E_PARAM; }
+    const int e = pgrc_decode_create_on(device, out);
+    if (!e) (*out)->L = read_length;
+    return e;
+}
+
 void pgrc_decode_destroy(pgrc_decode_ctx *d) {
     if (!d) return;
     PgrcDeviceScope scope(d->device);
     if (d->stream) (void)hipStreamSynchronize(d->stream);
     if (d->copy_stream) (void)hipStreamSynchronize(d->copy_stream);
-    for (auto &l : d->lst)
-        for (DevBuf *b : {&l.pos, &l.rc, &l.mcum, &l.moff, &l.msym, &l.raw}) dec_free(*b);
-    for (DevBuf *b : {&d->chunk[0], &d->chunk[1], &d->text, &d->flag, &d->scratch, &d->rl_order, &d->org2pos, &d->rank, &d->rs_mapped, &d->rs_marks,
-                       &d->rs_vals, &d->rs_ptr, &d->rs_bsum, &d->rs_coded, &d->rs_join})
-        dec_free(*b);
-    for (int k = 0; k < 2; k++) {
-        if (d->stage[k]) (void)hipHostFree(d->stage[k]);
-        for (hipEvent_t ev : {d->ev_made[k], d->ev_copied[k], d->ev_k0[k]})
-            if (ev) (void)hipEventDestroy(ev);
-    }
-    if (d->ev_a) (void)hipEventDestroy(d->ev_a);
-    if (d->ev_b) (void)hipEventDestroy(d->ev_b);
+    dec_free_all(dec_bufs(d));
+    for (hipEvent_t ev : {d->ev_made[0], d->ev_made[1], d->ev_k0[0], d->ev_k0[1], d->ev_a, d->ev_b})
+        if (ev) (void)hipEventDestroy(ev);
     pgrc_pairpos_release(d);
     pgrc_pairorder_release(d);
     pgrc_la_release(d);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
+    pgrc_stage_close(d);
     delete d;
 }
 

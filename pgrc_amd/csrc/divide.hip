@@ -44,8 +44,7 @@ struct pgrc_divider : PgrcDev {
     // the results of a run on the host: pinned, grow-only, the divider's (fresh pageable pages would be touched for the first
     // time by the copy, at one thread's page-fault rate: 11 GB/s against the link's 56)
     struct HostBuf { void *p = nullptr; size_t bytes = 0; } h_rows[3], h_idx[2];
-    hipEvent_t ev[4]{};
-    bool have_ev = false;
+    PhaseEvents<4> ev;
     float ms[3] = {0, 0, 0};
     bool last_terminal = false;   // the last pgrc_divider_run_fastq took what the reference's iteration would take before it ends
     // what the last run left in d_rows / d_idx (pgrc_divider_last_device: readsets.hip takes the sets where they lie)
@@ -383,8 +382,7 @@ void pgrc_divider_destroy(pgrc_divider *d) {
     for (DevBuf *b : bufs) pgrc_buf_free(*b);
     for (auto *h : {&d->h_rows[0], &d->h_rows[1], &d->h_rows[2], &d->h_idx[0], &d->h_idx[1]})
         if (h->p) (void)hipHostFree(h->p);
-    if (d->have_ev)
-        for (auto &x : d->ev) (void)hipEventDestroy(x);
+    d->ev.release();
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -468,7 +466,7 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
     const uint64_t work = n * a.row_bytes_max;
     hipLaunchKernelGGL(k_dv_pack, dim3((uint32_t)((work + 255) / 256)), dim3(256), 0, s, a);
     HIP_TRY(d, hipGetLastError());
-    (void)hipEventRecord(d->ev[2], s);
+    (void)d->ev.record(2, s);
     out->n_hq = cnt[0]; out->n_lq = cnt[1]; out->n_n = cnt[2];
     for (int k = 0; k < 3; k++)
         if ((e = dv_host_ensure(d, d->h_rows[k], (size_t)cnt[k] * rb[k]))) return e;
@@ -479,7 +477,7 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
         if (cnt[k] && rb[k]) he = hipMemcpyAsync(d->h_rows[k].p, d->d_rows[k].p, (size_t)cnt[k] * rb[k], hipMemcpyDeviceToHost, s);
     for (int k = 0; k < 2 && he == hipSuccess; k++)
         if (cnt[k + 1]) he = hipMemcpyAsync(d->h_idx[k].p, d->d_idx[k].p, (size_t)cnt[k + 1] * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (he == hipSuccess) he = hipEventRecord(d->ev[3], s);
+    if (he == hipSuccess) he = d->ev.record(3, s);
     if (he == hipSuccess) he = hipStreamSynchronize(s);
     if (he != hipSuccess) { c->err = std::string("divider: ") + hipGetErrorString(he); return pgrc_hip_code(he); }
     out->hq_rows = (const uint8_t *)d->h_rows[0].p;
@@ -487,7 +485,7 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
     out->n_rows = (const uint8_t *)d->h_rows[2].p;
     out->lq_index = (const uint32_t *)d->h_idx[0].p;
     out->n_index = (const uint32_t *)d->h_idx[1].p;
-    for (int k = 0; k < 3; k++) (void)hipEventElapsedTime(&d->ms[k], d->ev[k], d->ev[k + 1]);
+    for (int k = 0; k < 3; k++) d->ms[k] = d->ev.ms(k, k + 1);
     for (int k = 0; k < 3; k++) d->last_cnt[k] = cnt[k];
     d->last_valid = true;
     return PGRC_OK;
@@ -511,13 +509,6 @@ void pgrc_divider_last_device(const pgrc_divider *d, PgrcDividerLast *out) {
 }
 extern "C" {
 
-static int dv_events(pgrc_divider *d) {
-    if (d->have_ev) return PGRC_OK;
-    for (auto &x : d->ev) HIP_TRY(d, hipEventCreate(&x));
-    d->have_ev = true;
-    return PGRC_OK;
-}
-
 int pgrc_divider_run(pgrc_divider *d, const char *reads, const char *quals, uint64_t n, pgrc_divided_reads *out) {
     if (!d || !out || (n && !reads)) return PGRC_E_PARAM;
     d->last_valid = false;          // (whatever becomes of this run, the last one's sets are no longer the divider's last)
@@ -529,14 +520,14 @@ int pgrc_divider_run(pgrc_divider *d, const char *reads, const char *quals, uint
     PgrcDeviceScope scope(c->device);
     if (!scope.ok) { c->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     int e;
-    if ((e = dv_events(d))) return e;
+    if ((e = d->ev.ensure(d))) return e;
     const size_t bytes = (size_t)n * d->prm.read_len;
     if (n) {
         if ((e = pgrc_buf_ensure(c, d->d_reads, bytes + 16)) || (by_quality && (e = pgrc_buf_ensure(c, d->d_quals, bytes + 16)))) return e;
-        (void)hipEventRecord(d->ev[0], c->stream);
+        (void)d->ev.record(0, c->stream);
         HIP_TRY(d, hipMemcpyAsync(d->d_reads.p, reads, bytes, hipMemcpyHostToDevice, c->stream));
         if (by_quality) HIP_TRY(d, hipMemcpyAsync(d->d_quals.p, quals, bytes, hipMemcpyHostToDevice, c->stream));
-        (void)hipEventRecord(d->ev[1], c->stream);
+        (void)d->ev.record(1, c->stream);
     }
     return divide_resident(d, n, out);
 }
@@ -563,7 +554,7 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
     PgrcDeviceScope scope(c->device);
     if (!scope.ok) { c->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     int e;
-    if ((e = dv_events(d))) return e;
+    if ((e = d->ev.ensure(d))) return e;
     const uint32_t L = d->prm.read_len;
     const bool paired = pair_text != nullptr;
     const bool by_quality = d->prm.error_limit < 1;
@@ -574,7 +565,7 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
     const bool fin[2] = {(final_piece & 3) != 0, (final_piece & 5) != 0};
     uint64_t lines[2] = {0, 0};
     uint32_t nls[2] = {0, 0};
-    (void)hipEventRecord(d->ev[0], s);
+    (void)d->ev.record(0, s);
     for (int f = 0; f < (paired ? 2 : 1); f++) {
         const uint64_t n16 = (len[f] + 15) / 16;
         if ((e = pgrc_buf_ensure(c, d->d_text[f], len[f] + 32)) || (e = pgrc_buf_ensure(c, d->d_nl[f], (n16 + 1) * sizeof(uint32_t))) ||
@@ -653,7 +644,7 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
     }
     *consumed = ends[0];
     if (paired) *pair_consumed = ends[1];
-    (void)hipEventRecord(d->ev[1], s);
+    (void)d->ev.record(1, s);
     *n_records = n;
     return divide_resident(d, n, out);
 }

@@ -301,24 +301,15 @@ static __global__ void __launch_bounds__(LA_TPB) k_la_gather(const uint8_t *__re
 static int la_fail(pgrc_decode_ctx *d, const char *who, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, std::string("list archive (") + who + "): " + msg); }
 
 void pgrc_la_release(pgrc_decode_ctx *d) {
-    for (DevBuf *b : {&d->la_in, &d->la_inc, &d->la_cnt, &d->la_mcum, &d->la_mat, &d->la_fold, &d->la_small, &d->la_out}) dec_free(*b);
-    for (hipEvent_t &ev : d->la_ev) {
-        if (ev) (void)hipEventDestroy(ev);
-        ev = nullptr;
-    }
-}
-
-static int la_events(pgrc_decode_ctx *d) {
-    for (hipEvent_t &ev : d->la_ev)
-        if (!ev) HIP_TRY(d, hipEventCreate(&ev));
-    return PGRC_OK;
+    dec_free_all({&d->la_in, &d->la_inc, &d->la_cnt, &d->la_mcum, &d->la_mat, &d->la_fold, &d->la_small, &d->la_out});
+    d->la_ev.release();
 }
 
 // count matrix of the n counts at `cnt`, scanned; the per-count words in la_small and (synchronised) at h_small
 static int la_matrix(pgrc_decode_ctx *d, const uint8_t *cnt, uint64_t n, uint64_t *ntiles_out, uint64_t (&h_small)[LA_S_BINS]) {
     const uint64_t ntiles = std::max<uint64_t>(1, (n + LA_TILE - 1) / LA_TILE), cells = ntiles * 256;
     int e;
-    if ((e = pgrc_buf_unpooled(d, d->la_mat, cells * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->la_fold, pgrc_ps_scan_blocks(cells) * 4 + 16))) return e;
+    if ((e = pgrc_bufs_unpooled(d, {{&d->la_mat, cells * 4 + 16}, {&d->la_fold, pgrc_ps_scan_blocks(cells) * 4 + 16}}))) return e;
     uint32_t *mat = (uint32_t *)d->la_mat.p;
     hipLaunchKernelGGL(k_la_count, dim3((uint32_t)ntiles), dim3(LA_TPB), 0, d->stream, cnt, n, ntiles, mat);
     HIP_TRY(d, hipGetLastError());
@@ -353,9 +344,9 @@ struct LaLayout {
 static LaLayout la_layout(uint64_t n, uint64_t m) {
     LaLayout o;
     o.at_flags = 0;
-    o.at_sym = pp_a16(n) + 16;
-    o.at_dest = o.at_sym + pp_a16(m) + 16;
-    o.at_nz = o.at_dest + pp_a16(m) + 16;
+    o.at_sym = dec_a16(n) + 16;
+    o.at_dest = o.at_sym + dec_a16(m) + 16;
+    o.at_nz = o.at_dest + dec_a16(m) + 16;
     return o;
 }
 
@@ -372,7 +363,7 @@ static int la_encode_device(pgrc_decode_ctx *d, const uint8_t *cnt, const uint8_
     static const char *who = "encode";
     int e;
     const LaLayout lay = la_layout(n, m);
-    if ((e = pgrc_buf_unpooled(d, d->la_inc, n * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->la_mcum, (n + 1) * 8)) || (e = pgrc_buf_unpooled(d, d->la_small, LA_S_WORDS * 8))) return e;
+    if ((e = pgrc_bufs_unpooled(d, {{&d->la_inc, n * 4 + 16}, {&d->la_mcum, (n + 1) * 8}, {&d->la_small, LA_S_WORDS * 8}}))) return e;
     uint32_t *inc = (uint32_t *)d->la_inc.p;
     uint64_t *mcum = (uint64_t *)d->la_mcum.p;
     unsigned long long *small = (unsigned long long *)d->la_small.p;
@@ -390,13 +381,13 @@ static int la_encode_device(pgrc_decode_ctx *d, const uint8_t *cnt, const uint8_
     }
     if ((e = dec_scan<false>(d, XfU8{cnt}, n, 0, mcum))) return e;
     HIP_TRY(d, hipMemcpyAsync(&m_dev, mcum + n, 8, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipEventRecord(d->la_ev[1], d->stream));
+    HIP_TRY(d, d->la_ev.record(1, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     // nothing below reads a code or an offset before the counts are known to describe the streams
     if (m_dev != m) return la_fail(d, who, "n_mismatches is " + std::to_string(m) + ", the counts sum to " + std::to_string(m_dev));
 
     // symbols
-    HIP_TRY(d, hipEventRecord(d->la_ev[2], d->stream));
+    HIP_TRY(d, d->la_ev.record(2, d->stream));
     uint64_t h_bins[8] = {};
     if (m) {
         // 2048 blocks at most, and each bin of a block below 2^32: a block sees m / blocks + 4096 codes at most
@@ -421,7 +412,7 @@ static int la_encode_device(pgrc_decode_ctx *d, const uint8_t *cnt, const uint8_
         hipLaunchKernelGGL(k_la_recode, dim3(pp_grid((m >> 4) + 1)), dim3(PP_TPB), 0, d->stream, (const uint8_t *)sym, m, lo, hi, ob + lay.at_sym);
         HIP_TRY(d, hipGetLastError());
     }
-    HIP_TRY(d, hipEventRecord(d->la_ev[3], d->stream));
+    HIP_TRY(d, d->la_ev.record(3, d->stream));
 
     // the split
     uint64_t h_small[LA_S_BINS] = {};
@@ -439,7 +430,7 @@ static int la_encode_device(pgrc_decode_ctx *d, const uint8_t *cnt, const uint8_
                                   (const unsigned long long *)small, (const uint64_t *)mcum, (const uint8_t *)off, ob + lay.at_dest);
         HIP_TRY(d, hipGetLastError());
     }
-    HIP_TRY(d, hipEventRecord(d->la_ev[4], d->stream));
+    HIP_TRY(d, d->la_ev.record(4, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
 
     res->n_nonzero = n_nonzero;
@@ -461,7 +452,7 @@ static void la_describe(pgrc_list_archive_streams *out, uint8_t *blk, uint64_t n
     out->nonzero_cnt = blk + lay.at_nz;
     out->mis_sym = blk + lay.at_sym;
     for (int i = 0; i < 5; i++) out->bases_order[i] = "ACGTN"[r.order[i]];
-    uint8_t *props = blk + lay.at_nz + pp_a16(r.n_nonzero) + 16;
+    uint8_t *props = blk + lay.at_nz + dec_a16(r.n_nonzero) + 16;
     props[0] = (uint8_t)limit;
     for (uint32_t c = 1; c < limit; c++) props[c] = (uint8_t)c;
     out->props = props;
@@ -479,13 +470,13 @@ static void la_describe(pgrc_list_archive_streams *out, uint8_t *blk, uint64_t n
 }
 
 uint64_t pgrc_la_device_bytes(uint64_t n, uint64_t m) { return la_layout(n, m).at_nz + n + 16; }
-uint64_t pgrc_la_host_bytes(uint64_t n, uint64_t m) { return la_layout(n, m).at_nz + pp_a16(n) + 16 + 256; }
+uint64_t pgrc_la_host_bytes(uint64_t n, uint64_t m) { return la_layout(n, m).at_nz + dec_a16(n) + 16 + 256; }
 
 int pgrc_la_encode_resident(pgrc_decode_ctx *d, const uint8_t *d_cnt, const uint8_t *d_sym, const uint8_t *d_off, uint64_t n, uint64_t m, bool fast, uint8_t *d_block,
                             PgrcLaResident *res) {
     int e;
-    if ((e = la_events(d))) return e;
-    HIP_TRY(d, hipEventRecord(d->la_ev[0], d->stream));
+    if ((e = d->la_ev.ensure(d))) return e;
+    HIP_TRY(d, d->la_ev.record(0, d->stream));
     LaEncoded r;
     if ((e = la_encode_device(d, d_cnt, d_sym, d_off, n, m, fast, d_block, &r))) return e;
     res->down = la_layout(n, m).at_nz + r.n_nonzero;
@@ -510,22 +501,22 @@ static int la_encode_run(pgrc_decode_ctx *d, const pgrc_export_streams *in, bool
     const uint64_t n = in->n_entries, m = in->n_mismatches;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
-    if ((e = la_events(d))) return e;
+    if ((e = d->la_ev.ensure(d))) return e;
     const LaLayout lay = la_layout(n, m);
-    const uint64_t sym_at = pp_a16(n) + 16, off_at = sym_at + pp_a16(m) + 16;
-    if ((e = pgrc_buf_unpooled(d, d->la_in, off_at + m + 16)) || (e = pgrc_buf_unpooled(d, d->la_out, lay.at_nz + n + 16))) return e;
+    const uint64_t sym_at = dec_a16(n) + 16, off_at = sym_at + dec_a16(m) + 16;
+    if ((e = pgrc_bufs_unpooled(d, {{&d->la_in, off_at + m + 16}, {&d->la_out, lay.at_nz + n + 16}}))) return e;
     uint8_t *ib = (uint8_t *)d->la_in.p, *ob = (uint8_t *)d->la_out.p;
     uint8_t *cnt = ib, *sym = ib + sym_at, *off = ib + off_at;
     if ((e = dec_upload_host(d, cnt, in->mis_cnt, n)) || (e = dec_upload_host(d, sym, in->mis_sym, m)) || (e = dec_upload_host(d, off, in->mis_rev_off, m))) return e;
-    HIP_TRY(d, hipEventRecord(d->la_ev[0], d->stream));
-    const float ms_upload = pp_ms(t0);
+    HIP_TRY(d, d->la_ev.record(0, d->stream));
+    const float ms_upload = dec_ms_since(t0);
     LaEncoded r;
     if ((e = la_encode_device(d, cnt, sym, off, n, m, fast, ob, &r))) return e;
     const uint32_t n_nonzero = r.n_nonzero, limit = r.limit;
 
     // one page-locked block, one copy: everything the device made; the props are the host's
     const auto t1 = std::chrono::steady_clock::now();
-    const uint64_t at_props = lay.at_nz + pp_a16(n_nonzero) + 16, total = at_props + 256, down = lay.at_nz + n_nonzero;
+    const uint64_t at_props = lay.at_nz + dec_a16(n_nonzero) + 16, total = at_props + 256, down = lay.at_nz + n_nonzero;
     uint8_t *blk = nullptr;
     hipError_t he = hipHostMalloc((void **)&blk, total);
     if (he != hipSuccess) {
@@ -545,11 +536,11 @@ static int la_encode_run(pgrc_decode_ctx *d, const pgrc_export_streams *in, bool
     t.struct_size = sizeof(pgrc_list_archive_timing);
     t.encode = 1;
     t.ms_upload = ms_upload;
-    t.ms_flags_device = dec_elapsed(d->la_ev[0], d->la_ev[1]);
-    t.ms_symbols_device = dec_elapsed(d->la_ev[2], d->la_ev[3]);
-    t.ms_split_device = dec_elapsed(d->la_ev[3], d->la_ev[4]);
-    t.ms_download = pp_ms(t1);
-    t.ms_call = pp_ms(t0);
+    t.ms_flags_device = d->la_ev.ms(0, 1);
+    t.ms_symbols_device = d->la_ev.ms(2, 3);
+    t.ms_split_device = d->la_ev.ms(3, 4);
+    t.ms_download = dec_ms_since(t1);
+    t.ms_call = dec_ms_since(t0);
     t.bytes_up = n + 2 * m;
     t.bytes_down = down;
     t.n_nonzero = n_nonzero;
@@ -583,12 +574,11 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
     }
     if (sum != m) return la_fail(d, who, "the destinations hold " + std::to_string(sum) + " bytes, n_mismatches is " + std::to_string(m));
     int e;
-    if ((e = la_events(d))) return e;
+    if ((e = d->la_ev.ensure(d))) return e;
     // uploads: flags | non-zero counts in la_in, the codes straight into the list, the sources one behind the other in la_out
-    const uint64_t nz_at = pp_a16(n) + 16;
-    if ((e = pgrc_buf_unpooled(d, d->la_in, nz_at + nz + 16)) || (e = pgrc_buf_unpooled(d, d->la_inc, n * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->la_cnt, n + 16)) ||
-        (e = pgrc_buf_unpooled(d, d->la_small, LA_S_WORDS * 8)) || (e = pgrc_buf_unpooled(d, d->la_out, m + 16)) || (e = pgrc_buf_unpooled(d, l.mcum, (n + 1) * 8)) ||
-        (e = pgrc_buf_unpooled(d, l.moff, m)) || (e = pgrc_buf_unpooled(d, l.msym, m)))
+    const uint64_t nz_at = dec_a16(n) + 16;
+    if ((e = pgrc_bufs_unpooled(d, {{&d->la_in, nz_at + nz + 16}, {&d->la_inc, n * 4 + 16}, {&d->la_cnt, n + 16}, {&d->la_small, LA_S_WORDS * 8}, {&d->la_out, m + 16},
+                                    {&l.mcum, (n + 1) * 8}, {&l.moff, m}, {&l.msym, m}})))
         return e;
     uint8_t *flags = (uint8_t *)d->la_in.p, *nonzero = flags + nz_at, *cnt = (uint8_t *)d->la_cnt.p, *src = (uint8_t *)d->la_out.p;
     uint32_t *inc = (uint32_t *)d->la_inc.p;
@@ -602,8 +592,8 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
         if ((e = dec_upload_host(d, src + at, s->dest[c], s->dest_len[c]))) return e;
         at += s->dest_len[c];
     }
-    HIP_TRY(d, hipEventRecord(d->la_ev[0], d->stream));
-    const float ms_upload = pp_ms(t0);
+    HIP_TRY(d, d->la_ev.record(0, d->stream));
+    const float ms_upload = dec_ms_since(t0);
 
     // counts from the flags; mismatch-list starts
     uint32_t n_clear = 0;
@@ -620,16 +610,16 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
     HIP_TRY(d, hipGetLastError());
     if ((e = dec_scan<false>(d, XfU8{cnt}, n, 0, mcum))) return e;
     HIP_TRY(d, hipMemcpyAsync(&m_dev, mcum + n, 8, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipEventRecord(d->la_ev[1], d->stream));
+    HIP_TRY(d, d->la_ev.record(1, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     if (m_dev != m) return la_fail(d, who, "n_mismatches is " + std::to_string(m) + ", the counts sum to " + std::to_string(m_dev));
     l.nmis = m;
 
     // the codes
-    HIP_TRY(d, hipEventRecord(d->la_ev[2], d->stream));
+    HIP_TRY(d, d->la_ev.record(2, d->stream));
     if (m) hipLaunchKernelGGL(k_la_symcheck, dim3((uint32_t)std::min<uint64_t>(pp_grid(m), 4096)), dim3(PP_TPB), 0, d->stream, (const uint8_t *)l.msym.p, m, (uint32_t *)d->flag.p);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(d->la_ev[3], d->stream));
+    HIP_TRY(d, d->la_ev.record(3, d->stream));
 
     // the gather.  limit <= 1: every count reads the one source at its mismatch-list start (its length is m: checked above)
     if (m) {
@@ -654,16 +644,16 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
         }
         HIP_TRY(d, hipGetLastError());
     }
-    HIP_TRY(d, hipEventRecord(d->la_ev[4], d->stream));
+    HIP_TRY(d, d->la_ev.record(4, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     pgrc_list_archive_timing &t = d->latm;
     t = pgrc_list_archive_timing{};
     t.struct_size = sizeof(pgrc_list_archive_timing);
     t.encode = 0;
     t.ms_upload = ms_upload;
-    t.ms_flags_device = dec_elapsed(d->la_ev[0], d->la_ev[1]);
-    t.ms_symbols_device = dec_elapsed(d->la_ev[2], d->la_ev[3]);
-    t.ms_split_device = dec_elapsed(d->la_ev[3], d->la_ev[4]);
+    t.ms_flags_device = d->la_ev.ms(0, 1);
+    t.ms_symbols_device = d->la_ev.ms(2, 3);
+    t.ms_split_device = d->la_ev.ms(3, 4);
     t.bytes_up = n + nz + 2 * m;
     t.n_nonzero = nz;
     t.limit = limit;
@@ -701,7 +691,7 @@ int pgrc_decode_add_list_archive(pgrc_decode_ctx *d, const pgrc_decode_list *lis
     d->have_la_timing = false;
     const int e = pgrc_dec_add_list(d, list, s);
     if (e) return e;
-    d->latm.ms_call = pp_ms(t0);
+    d->latm.ms_call = dec_ms_since(t0);
     d->have_la_timing = true;
     return PGRC_OK;
 }

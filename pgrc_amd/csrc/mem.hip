@@ -703,8 +703,7 @@ void pgrc_mem_destroy(pgrc_mem_ctx *m) {
                       &m->d_ebin, &m->d_ebout, &m->d_ebinc, &m->d_small, &m->d_match};
     for (DevBuf *b : bufs) pgrc_buf_free(*b);
     pgrc_pgmap_release(m);
-    if (m->have_ev)
-        for (auto &x : m->ev) (void)hipEventDestroy(x);
+    m->ev.release();
     pgrc_match_destroy(m->base);
     delete m;
 }
@@ -802,11 +801,8 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
     const uint64_t nprobes = N2 >= K ? (N2 - K) / k2 + 1 : 0;          // windows q = t * k2 with q + K <= N2
     m->ctr.probes = nprobes;
     int e;
-    if (!m->have_ev) {
-        for (auto &x : m->ev) HIP_TRY(m, hipEventCreate(&x));
-        m->have_ev = true;
-    }
-    hipEvent_t *ev = m->ev;
+    if ((e = m->ev.ensure(m))) return e;
+    auto &ev = m->ev;
 
     // ---- the destination in HBM
     MemArgs a;
@@ -897,7 +893,7 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
     uint64_t cap = std::max<uint64_t>((nprobes <= (64ull << 20) ? nprobes : nprobes / 4) + 65536, m->d_evk[0].bytes / 8);
     if (c->opt.mem_event_cap) cap = c->opt.mem_event_cap;   // (PGRC_MEM_EVENT_CAP, test knob: start tiny to exercise the regrow-and-rerun path)
     unsigned long long nev = 0;
-    (void)hipEventRecord(ev[0], c->stream);
+    (void)ev.record(0, c->stream);
     for (int attempt = 0; attempt < 2; attempt++) {
         for (int k = 0; k < 2; k++)
             if ((e = pgrc_buf_ensure(c, m->d_evk[k], cap * 8)) || (e = pgrc_buf_ensure(c, m->d_evv[k], cap * 8))) { m->err = c->err; return e; }
@@ -911,12 +907,12 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
         if (nev <= cap) break;
         cap = nev + nev / 4;                                // the guess was too small: once more, with headroom for the next call
     }
-    (void)hipEventRecord(ev[1], c->stream);
+    (void)ev.record(1, c->stream);
     m->ctr.events = nev;
     m->ctr.replay_rounds = m->ctr.event_blocks = 0;
     m->ctr.ms_sort = m->ctr.ms_extend = m->ctr.ms_replay = m->ctr.ms_host = 0.f;
-    (void)hipEventSynchronize(ev[1]);
-    (void)hipEventElapsedTime(&m->ctr.ms_probe, ev[0], ev[1]);
+    (void)hipEventSynchronize(ev.ev[1]);
+    m->ctr.ms_probe = ev.ms(0, 1);
     if (!nev) return done();
     if (nev >= 0xFFFFFFF0ull) { m->err = "more than 2^32 events"; return PGRC_E_PARAM; }
 
@@ -927,7 +923,7 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
     uint64_t *ksorted = nullptr, *vsorted = nullptr;
     if ((e = pgrc_radix_sort_pairs_u64(c, (uint64_t *)m->d_evk[0].p, (uint64_t *)m->d_evk[1].p, (uint64_t *)m->d_evv[0].p, (uint64_t *)m->d_evv[1].p, nev, 0,
                                        4 + tb, m->d_tmp, &ksorted, &vsorted))) { m->err = c->err; return e; }
-    (void)hipEventRecord(ev[2], c->stream);
+    (void)ev.record(2, c->stream);
     const uint64_t *ek = ksorted, *ep = vsorted;
 
     // ---- 3. side contexts; extents per run of connected events on a diagonal
@@ -964,7 +960,7 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
                            (const uint64_t *)m->d_rstart.p, (const uint64_t *)m->d_rend.p, min_len, (uint32_t *)m->d_orun.p, (uint8_t *)m->d_oflag.p);
         HIP_TRY(m, hipGetLastError());
     }
-    (void)hipEventRecord(ev[3], c->stream);
+    (void)ev.record(3, c->stream);
 
     // ---- 4. the sequential rules on the device (k_mem_replay)
     uint64_t nmain;
@@ -1050,7 +1046,7 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
                            (const uint32_t *)d_lid, (uint32_t *)m->d_ebin.p);
         if ((e = settle())) return e;
     }
-    (void)hipEventRecord(ev[4], c->stream);
+    (void)ev.record(4, c->stream);
 
     // ---- 5. the matches, in discovery order
     const auto th0 = std::chrono::steady_clock::now();
@@ -1072,9 +1068,9 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
         *matches = outp;
     }
     *count = nmatch;
-    (void)hipEventElapsedTime(&m->ctr.ms_sort, ev[1], ev[2]);
-    (void)hipEventElapsedTime(&m->ctr.ms_extend, ev[2], ev[3]);
-    (void)hipEventElapsedTime(&m->ctr.ms_replay, ev[3], ev[4]);                       // (with the host's part between the rounds)
+    m->ctr.ms_sort = ev.ms(1, 2);
+    m->ctr.ms_extend = ev.ms(2, 3);
+    m->ctr.ms_replay = ev.ms(3, 4);                       // (with the host's part between the rounds)
     m->ctr.ms_host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - th0).count();
     return done();
 }

@@ -16,8 +16,7 @@ struct pgrc_mem_ctx {
     DevBuf d_dest, d_nmap, d_stage, d_flag, d_cursor, d_evk[2], d_evv[2], d_tmp, d_scan, d_orun, d_oflag;
     DevBuf d_skey[2], d_sidx[2], d_first, d_runid, d_rstart, d_rend;   // events by (diagonal, window): sort ping-pong, runs
     DevBuf d_rdend, d_outc, d_ebstart, d_ebin, d_ebout, d_ebinc, d_small, d_match;   // the replay: per run, per event, per event block
-    hipEvent_t ev[5]{};               // phase timing (created on first use)
-    bool have_ev = false;
+    PhaseEvents<5> ev;                // phase timing (created on first use)
     pgrc_mem_counters ctr{};
     std::string err;
 
@@ -28,8 +27,7 @@ struct pgrc_mem_ctx {
     uint64_t map_n2 = 0;
     DevBuf pm_in, pm_f[3], pm_key[2], pm_idx[2], pm_flag, pm_slot, pm_u[4], pm_pmax, pm_jump[2], pm_kept, pm_m[3], pm_dp, pm_len,
         pm_nb, pm_cum, pm_nbpos, pm_mp, pm_off, pm_lens, pm_out, pm_fold, pm_small;
-    hipEvent_t pm_ev[6]{};            // phases of the mapping (created on first use)
-    bool have_pm_ev = false;
+    PhaseEvents<5> pm_ev;             // phases of the mapping (created on first use)
     float pm_ms[5] = {0, 0, 0, 0, 0}; // normalise + sort, path, streams, text, download
     // the mapped texts that pgrc_mem_mark_and_remove_resident left in HBM, slot 0 HQ, 1 LQ, 2 N: what pgrc_mem_encode_mapped
     // codes as one text (pgrc_mem_set_src_ascii forgets them)

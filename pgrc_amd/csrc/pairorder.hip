@@ -91,11 +91,8 @@ static __global__ void __launch_bounds__(PP_TPB) k_po_far(uint64_t nf, const uin
 static int po_fail(pgrc_decode_ctx *d, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, "pair order (encode): " + msg); }
 
 void pgrc_pairorder_release(pgrc_decode_ctx *d) {
-    for (DevBuf *b : {&d->po_in, &d->po_rev, &d->po_ent, &d->po_pair, &d->po_out, &d->po_bsum}) dec_free(*b);
-    for (hipEvent_t &ev : d->po_ev) {
-        if (ev) (void)hipEventDestroy(ev);
-        ev = nullptr;
-    }
+    dec_free_all({&d->po_in, &d->po_rev, &d->po_ent, &d->po_pair, &d->po_out, &d->po_bsum});
+    d->po_ev.release();
 }
 
 // the nine streams in the order of pgrc_pairorder_streams: where they start in a block, and their bytes
@@ -112,7 +109,7 @@ static PoLayout po_layout(int32_t form, uint64_t T, uint64_t n_near, uint64_t nf
     for (int k = 0; k < PO_NS; k++) {
         o.at[k] = o.total;
         o.bytes[k] = b[k];
-        o.total += pp_a16(b[k]) + 16;
+        o.total += dec_a16(b[k]) + 16;
     }
     return o;
 }
@@ -124,15 +121,14 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     const bool coded = form != PGRC_PAIRORDER_COMPLETE_SINGLE_FILE, ff = form == PGRC_PAIRORDER_FILE_FLAGS, complete = form == PGRC_PAIRORDER_COMPLETE;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
-    for (hipEvent_t &ev : d->po_ev)
-        if (!ev) HIP_TRY(d, hipEventCreate(&ev));
+    if ((e = d->po_ev.ensure(d))) return e;
     const PoLayout dev = po_layout(form, T, P, P, P, P);         // on the device every stream has room for all pairs
-    const uint64_t binc_at = pp_a16(T * 4) + 16, ent_bytes = binc_at + T * 4 + 16;
-    const uint64_t file_at = pp_a16(P * 4) + 16, ninc_at = file_at + pp_a16(P) + 16, frel_at = ninc_at + pp_a16(P * 4) + 16, pre_at = frel_at + pp_a16(P * 4) + 16,
-                   dinc_at = pre_at + pp_a16(P * 4) + 16, dval_at = dinc_at + pp_a16(P * 4) + 16, map_at = dval_at + pp_a16(P) + 16, pair_bytes = map_at + P + 16;
-    const uint64_t sco_bytes = pp_a16(sco_scratch_elems(T) * 4), bsum_bytes = sco_bytes + 32;
-    if ((e = pgrc_buf_unpooled(d, d->po_in, d_joined ? 16 : T * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->po_rev, T * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->po_ent, ent_bytes)) ||
-        (e = pgrc_buf_unpooled(d, d->po_pair, coded ? pair_bytes : 16)) || (e = pgrc_buf_unpooled(d, d->po_out, dev.total)) || (e = pgrc_buf_unpooled(d, d->po_bsum, bsum_bytes)))
+    const uint64_t binc_at = dec_a16(T * 4) + 16, ent_bytes = binc_at + T * 4 + 16;
+    const uint64_t file_at = dec_a16(P * 4) + 16, ninc_at = file_at + dec_a16(P) + 16, frel_at = ninc_at + dec_a16(P * 4) + 16, pre_at = frel_at + dec_a16(P * 4) + 16,
+                   dinc_at = pre_at + dec_a16(P * 4) + 16, dval_at = dinc_at + dec_a16(P * 4) + 16, map_at = dval_at + dec_a16(P) + 16, pair_bytes = map_at + P + 16;
+    const uint64_t sco_bytes = dec_a16(sco_scratch_elems(T) * 4), bsum_bytes = sco_bytes + 32;
+    if ((e = pgrc_bufs_unpooled(d, {{&d->po_in, d_joined ? 16 : T * 4 + 16}, {&d->po_rev, T * 4 + 16}, {&d->po_ent, ent_bytes}, {&d->po_pair, coded ? pair_bytes : 16},
+                                    {&d->po_out, dev.total}, {&d->po_bsum, bsum_bytes}})))
         return e;
     const uint32_t *org = d_joined ? d_joined : (const uint32_t *)d->po_in.p;
     uint32_t *rev = (uint32_t *)d->po_rev.p;
@@ -145,24 +141,24 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
         if (n[l] && (e = dec_upload(d, (uint32_t *)d->po_in.p + first, org_h[l], n[l] * 4))) return e;
         first += n[l];
     }
-    HIP_TRY(d, hipEventRecord(d->po_ev[0], d->stream));
+    HIP_TRY(d, d->po_ev.record(0, d->stream));
     if (T) HIP_TRY(d, hipMemsetAsync(rev, 0xFF, T * 4, d->stream));      // the sentinel: no entry index (T <= 2^32 - 2)
     HIP_TRY(d, hipMemsetAsync(bad, 0, 16, d->stream));
-    const float ms_upload = pp_ms(t0);
+    const float ms_upload = dec_ms_since(t0);
 
     uint32_t h_bad[2] = {0, 0}, n_base = 0, n_near = 0, n_del = 0;
     if (T) {
         hipLaunchKernelGGL(k_po_scatter, dim3(pp_grid(T)), dim3(PP_TPB), 0, d->stream, (const uint32_t *)org, T, rev, bad);
-        HIP_TRY(d, hipEventRecord(d->po_ev[10], d->stream));
+        HIP_TRY(d, d->po_ev.record(10, d->stream));
         hipLaunchKernelGGL(k_po_class, dim3(pp_grid(T)), dim3(PP_TPB), 0, d->stream, (const uint32_t *)org, T, (const uint32_t *)rev, rel, bad);
         HIP_TRY(d, hipGetLastError());
     }
-    HIP_TRY(d, hipEventRecord(d->po_ev[1], d->stream));
+    HIP_TRY(d, d->po_ev.record(1, d->stream));
     if (T && coded) {
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint32_t *)rel, base_inc, T, PoNonZero{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_base, base_inc + T - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, hipEventRecord(d->po_ev[2], d->stream));
+    HIP_TRY(d, d->po_ev.record(2, d->stream));
     HIP_TRY(d, hipMemcpyAsync(h_bad, bad, 8, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     // nothing below is indexed by a pair number before the input is known to be a permutation
@@ -179,23 +175,23 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     uint32_t *full = (uint32_t *)(ob + dev.at[PO_FULL]), *pbo = complete ? (uint32_t *)(ob + dev.at[PO_PBO]) : nullptr;
     uint8_t *off_file = ff ? ob + dev.at[PO_OFFF] : nullptr, *nonoff_file = ff ? ob + dev.at[PO_NONF] : nullptr;
     const bool pairs = coded && P;
-    HIP_TRY(d, hipEventRecord(d->po_ev[8], d->stream));         // (the host's wait above is no device time)
+    HIP_TRY(d, d->po_ev.record(8, d->stream));         // (the host's wait above is no device time)
     if (pairs) hipLaunchKernelGGL(k_po_pairs, dim3(pp_grid(T)), dim3(PP_TPB), 0, d->stream, (const uint32_t *)org, T, (const uint32_t *)rel, (const uint32_t *)base_inc, prel,
                                   off8_flag, pfile, pbo);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(d->po_ev[3], d->stream));
+    HIP_TRY(d, d->po_ev.record(3, d->stream));
     if (pairs) {
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)off8_flag, near_inc, P, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, hipEventRecord(d->po_ev[4], d->stream));
+    HIP_TRY(d, d->po_ev.record(4, d->stream));
     if (pairs) hipLaunchKernelGGL(k_po_compact, dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, P, (const uint8_t *)off8_flag, (const uint32_t *)near_inc, (const uint32_t *)prel,
                                   (const uint8_t *)pfile, off_val, off_file, far_rel, nonoff_file);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(d->po_ev[5], d->stream));
+    HIP_TRY(d, d->po_ev.record(5, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     const uint64_t nf = pairs ? P - n_near : 0;
-    HIP_TRY(d, hipEventRecord(d->po_ev[9], d->stream));
+    HIP_TRY(d, d->po_ev.record(9, d->stream));
     if (nf) {
         hipLaunchKernelGGL((k_pp_enc_maps<int8_t, uint32_t>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rel, map);
         HIP_TRY(d, sco_scan<false>(d->stream, (const uint8_t *)map, pre, nf, ScoIdentity{}, PpCompose{}, PP_MAP_IDENT, sco_tmp));
@@ -203,11 +199,11 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)del_flag, del_inc, nf, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, hipEventRecord(d->po_ev[6], d->stream));
+    HIP_TRY(d, d->po_ev.record(6, d->stream));
     if (nf) hipLaunchKernelGGL(k_po_far, dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rel, (const uint8_t *)del_flag, (const uint32_t *)del_inc,
                                (const int8_t *)dval, del_val, full);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(d->po_ev[7], d->stream));
+    HIP_TRY(d, d->po_ev.record(7, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
 
     // the streams, now that their sizes are known: one page-locked block
@@ -259,12 +255,12 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     t.struct_size = sizeof(pgrc_pairorder_timing);
     t.form = form;
     t.ms_upload = ms_upload;
-    t.ms_inverse_device = dec_elapsed(d->po_ev[0], d->po_ev[1]);
-    t.ms_scatter_device = T ? dec_elapsed(d->po_ev[0], d->po_ev[10]) : 0;
-    t.ms_scan_device = dec_elapsed(d->po_ev[1], d->po_ev[2]) + dec_elapsed(d->po_ev[3], d->po_ev[4]) + dec_elapsed(d->po_ev[9], d->po_ev[6]);
-    t.ms_compact_device = dec_elapsed(d->po_ev[8], d->po_ev[3]) + dec_elapsed(d->po_ev[4], d->po_ev[5]) + dec_elapsed(d->po_ev[6], d->po_ev[7]);
-    t.ms_download = pp_ms(t1);
-    t.ms_call = pp_ms(t0);
+    t.ms_inverse_device = d->po_ev.ms(0, 1);
+    t.ms_scatter_device = T ? d->po_ev.ms(0, 10) : 0;
+    t.ms_scan_device = d->po_ev.ms(1, 2) + d->po_ev.ms(3, 4) + d->po_ev.ms(9, 6);
+    t.ms_compact_device = d->po_ev.ms(8, 3) + d->po_ev.ms(4, 5) + d->po_ev.ms(6, 7);
+    t.ms_download = dec_ms_since(t1);
+    t.ms_call = dec_ms_since(t0);
     t.bytes_up = d_joined ? 0 : T * 4;
     t.bytes_down = down;
     t.n_near = n_near;

@@ -246,19 +246,10 @@ __global__ void __launch_bounds__(PP_TPB) k_pp_enc_far(uint64_t nf, const uint32
 // ------------------------------------------------------------------------------------------------ host side
 static int pp_fail(pgrc_decode_ctx *d, const char *who, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, std::string(who) + ": " + msg); }
 
-static int pp_prepare(pgrc_decode_ctx *d) {
-    for (hipEvent_t &ev : d->pp_ev)
-        if (!ev) HIP_TRY(d, hipEventCreate(&ev));
-    return PGRC_OK;
-}
-
 void pgrc_pairpos_release(pgrc_decode_ctx *d) {
-    for (DevBuf *b : {&d->pp_in, &d->pp_rec[0], &d->pp_rec[1], &d->pp_val[0], &d->pp_val[1], &d->pp_rank, &d->pp_far, &d->pp_out, &d->pp_bsum}) dec_free(*b);
+    dec_free_all({&d->pp_in, &d->pp_rec[0], &d->pp_rec[1], &d->pp_val[0], &d->pp_val[1], &d->pp_rank, &d->pp_far, &d->pp_out, &d->pp_bsum});
     pgrc_buf_free(d->pp_sort);
-    for (hipEvent_t &ev : d->pp_ev) {
-        if (ev) (void)hipEventDestroy(ev);
-        ev = nullptr;
-    }
+    d->pp_ev.release();
 }
 
 // the rank order of the P records in pp_rec[0] (pp_val[0]): stable by the position bits in use
@@ -285,23 +276,6 @@ static int pp_sort_buffers(pgrc_decode_ctx *d, bool w8, uint64_t P) {
     return PGRC_OK;
 }
 
-// device -> host on the context's stream: page-locked memory directly, other memory through the staging buffers
-static int pp_download(pgrc_decode_ctx *d, void *h_dst, const void *d_src, uint64_t bytes) {
-    if (pgrc_host_pinned(h_dst)) {
-        if (bytes) HIP_TRY(d, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
-        return PGRC_OK;
-    }
-    HIP_TRY(d, hipStreamSynchronize(d->stream));       // (uploads through the staging buffers have landed)
-    for (uint64_t o = 0; o < bytes; o += DEC_STAGE_BYTES) {
-        const uint64_t c = std::min<uint64_t>(DEC_STAGE_BYTES, bytes - o);
-        HIP_TRY(d, hipMemcpyAsync(d->stage[0], (const uint8_t *)d_src + o, c, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
-        memcpy((uint8_t *)h_dst + o, d->stage[0], c);
-    }
-    return PGRC_OK;
-}
-
 template <bool W8>
 static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint64_t *d_out) {
     static const char *who = "pair positions (decode)";
@@ -309,24 +283,23 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
     const uint64_t nf = s->n_delta_flag;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
-    if ((e = pp_prepare(d)) || (e = pp_sort_buffers(d, W8, P))) return e;
+    if ((e = d->pp_ev.ensure(d)) || (e = pp_sort_buffers(d, W8, P))) return e;
     // the streams, each at a 16-byte aligned place
     const void *hsrc[8] = {s->base_pos, s->off16_flag, s->off_base_first, s->off_value, s->delta16_flag, s->delta_base_first, s->delta_value, s->not_base_pos};
     const uint64_t nbytes[8] = {P * W, P, s->n_off16, s->n_off16 * 2, nf, s->n_delta16, s->n_delta16 * 2, s->n_not_base * W};
     uint64_t at[8], in_bytes = 0, up = 0;
     for (int k = 0; k < 8; k++) {
         at[k] = in_bytes;
-        in_bytes += pp_a16(nbytes[k]) + 16;
+        in_bytes += dec_a16(nbytes[k]) + 16;
         up += nbytes[k];
     }
-    const uint64_t near_at = 0, kind_at = near_at + pp_a16(P * 4) + 16, val_at = kind_at + pp_a16(P) + 16, rank_bytes = val_at + P * 8 + 16;
-    const uint64_t bsum_bytes = pp_a16(sco_scratch_elems(std::max(P, nf)) * sizeof(PpSeg)) + 2 * PP_OR_BLOCKS * 8 + 64;     // (the flag scans' u32 folds too)
-    if ((e = pgrc_buf_unpooled(d, d->pp_in, in_bytes)) || (e = pgrc_buf_unpooled(d, d->pp_rank, rank_bytes)) || (e = pgrc_buf_unpooled(d, d->pp_far, nf * 4 + 16)) || (e = pgrc_buf_unpooled(d, d->pp_bsum, bsum_bytes)))
-        return e;
+    const uint64_t near_at = 0, kind_at = near_at + dec_a16(P * 4) + 16, val_at = kind_at + dec_a16(P) + 16, rank_bytes = val_at + P * 8 + 16;
+    const uint64_t bsum_bytes = dec_a16(sco_scratch_elems(std::max(P, nf)) * sizeof(PpSeg)) + 2 * PP_OR_BLOCKS * 8 + 64;     // (the flag scans' u32 folds too)
+    if ((e = pgrc_bufs_unpooled(d, {{&d->pp_in, in_bytes}, {&d->pp_rank, rank_bytes}, {&d->pp_far, nf * 4 + 16}, {&d->pp_bsum, bsum_bytes}}))) return e;
     uint8_t *in = (uint8_t *)d->pp_in.p;
     for (int k = 0; k < 8; k++)
         if (nbytes[k] && (e = dec_upload(d, in + at[k], hsrc[k], nbytes[k]))) return e;
-    const float ms_upload = pp_ms(t0);
+    const float ms_upload = dec_ms_since(t0);
     PpDecStreams ds;
     ds.off16_flag = in + at[1];
     ds.off_bf = in + at[2];
@@ -343,7 +316,7 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
     uint64_t *bor = (uint64_t *)((uint8_t *)d->pp_bsum.p + bsum_bytes - 2 * PP_OR_BLOCKS * 8 - 32);     // block ORs, then the two results
     uint32_t *sco_tmp = (uint32_t *)d->pp_bsum.p;
 
-    HIP_TRY(d, hipEventRecord(d->pp_ev[0], d->stream));
+    HIP_TRY(d, d->pp_ev.record(0, d->stream));
     const uint32_t nor = (uint32_t)std::min<uint64_t>(pp_grid(P), PP_OR_BLOCKS);
     if (W8) hipLaunchKernelGGL((k_pp_records<true, PpBaseStream<uint64_t>>), dim3(nor), dim3(PP_TPB), 0, d->stream, PpBaseStream<uint64_t>{(const uint64_t *)(in + at[0])}, P,
                                (uint64_t *)d->pp_rec[0].p, (uint64_t *)d->pp_val[0].p, bor);
@@ -351,11 +324,11 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
                             (uint64_t *)d->pp_rec[0].p, (uint64_t *)nullptr, bor);
     hipLaunchKernelGGL(k_pp_or_final, dim3(1), dim3(64), 0, d->stream, (const uint64_t *)bor, nor, bor + 2 * PP_OR_BLOCKS);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(d->pp_ev[1], d->stream));
+    HIP_TRY(d, d->pp_ev.record(1, d->stream));
     // the flags' counts, held against the stream sizes before anything is indexed by them
     HIP_TRY(d, sco_scan<true>(d->stream, ds.off16_flag, near_inc, P, PpIsOne{}, ScoPlus{}, 0u, sco_tmp));
     HIP_TRY(d, sco_scan<true>(d->stream, ds.del_flag, del_inc, nf, PpNonZero{}, ScoPlus{}, 0u, sco_tmp));
-    HIP_TRY(d, hipEventRecord(d->pp_ev[2], d->stream));
+    HIP_TRY(d, d->pp_ev.record(2, d->stream));
     uint64_t ors[2] = {0, 0};
     uint32_t n_near = 0, n_del = 0;
     HIP_TRY(d, hipMemcpyAsync(ors, bor + 2 * PP_OR_BLOCKS, 16, hipMemcpyDeviceToHost, d->stream));
@@ -369,22 +342,22 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
 
     const uint64_t *a = nullptr, *b = nullptr;
     if ((e = pp_sort(d, W8, P, ors[0], &a, &b))) return e;
-    HIP_TRY(d, hipEventRecord(d->pp_ev[3], d->stream));
+    HIP_TRY(d, d->pp_ev.record(3, d->stream));
     if (P) hipLaunchKernelGGL((k_pp_dec_ops<W8>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, a, b, P, ds, d_out, kind, val);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(d->pp_ev[4], d->stream));
+    HIP_TRY(d, d->pp_ev.record(4, d->stream));
     // refPrev at every ranked pair; the scan's last pass puts the delta pairs' mates in their places
     HIP_TRY(d, (sco_device_scan<true, false>(d->stream, PpChainIn{kind, val}, P, PpSegOp{}, PpSeg{0, 0u}, PpSeg{0, 0u}, PpDeltaSink<W8>{a, b, kind, P, d_out}, (PpSeg *)d->pp_bsum.p)));
-    HIP_TRY(d, hipEventRecord(d->pp_ev[5], d->stream));
+    HIP_TRY(d, d->pp_ev.record(5, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     pgrc_pairpos_timing &t = d->ptm;
     t = pgrc_pairpos_timing{};
     t.struct_size = sizeof(pgrc_pairpos_timing);
     t.encode = 0;
     t.ms_upload = ms_upload;
-    t.ms_sort_device = dec_elapsed(d->pp_ev[0], d->pp_ev[1]) + dec_elapsed(d->pp_ev[2], d->pp_ev[3]);
-    t.ms_scan_device = dec_elapsed(d->pp_ev[1], d->pp_ev[2]) + dec_elapsed(d->pp_ev[3], d->pp_ev[4]);
-    t.ms_scatter_device = dec_elapsed(d->pp_ev[4], d->pp_ev[5]);
+    t.ms_sort_device = d->pp_ev.ms(0, 1) + d->pp_ev.ms(2, 3);
+    t.ms_scan_device = d->pp_ev.ms(1, 2) + d->pp_ev.ms(3, 4);
+    t.ms_scatter_device = d->pp_ev.ms(4, 5);
     t.bytes_up = up;
     t.n_near = n_near;
     t.n_delta = n_del;
@@ -426,7 +399,7 @@ static PpEncOut pp_enc_layout(uint64_t P, uint64_t W, uint64_t n_near, uint64_t 
     for (int k = 0; k < 8; k++) {
         o.at[k] = o.total;
         o.bytes[k] = b[k];
-        o.total += pp_a16(b[k]) + 16;
+        o.total += dec_a16(b[k]) + 16;
     }
     return o;
 }
@@ -438,17 +411,16 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
     const uint64_t P = T / 2, W = W8 ? 8 : 4;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
-    if ((e = pp_prepare(d)) || (e = pp_sort_buffers(d, W8, P))) return e;
+    if ((e = d->pp_ev.ensure(d)) || (e = pp_sort_buffers(d, W8, P))) return e;
     const PpEncOut dev = pp_enc_layout(P, W, P, P, P, P);        // on the device every stream has room for all pairs
-    const uint64_t near_at = pp_a16(P * 8) + 16, bf_at = near_at + pp_a16(P * 4) + 16, rank_bytes = bf_at + P + 16;
-    const uint64_t frank_at = pp_a16(P * 8) + 16, pre_at = frank_at + pp_a16(P * 4) + 16, dinc_at = pre_at + pp_a16(P * 4) + 16,
-                   dval_at = dinc_at + pp_a16(P * 4) + 16, map_at = dval_at + pp_a16(P * 2) + 16, far_bytes = map_at + P + 16;
-    const uint64_t bsum_bytes = pp_a16(sco_scratch_elems(P) * 4) + 2 * PP_OR_BLOCKS * 8 + 64;
-    if ((e = pgrc_buf_unpooled(d, d->pp_in, on_device ? 16 : T * 8 + 16)) || (e = pgrc_buf_unpooled(d, d->pp_rank, rank_bytes)) || (e = pgrc_buf_unpooled(d, d->pp_far, far_bytes)) ||
-        (e = pgrc_buf_unpooled(d, d->pp_out, dev.total)) || (e = pgrc_buf_unpooled(d, d->pp_bsum, bsum_bytes)))
+    const uint64_t near_at = dec_a16(P * 8) + 16, bf_at = near_at + dec_a16(P * 4) + 16, rank_bytes = bf_at + P + 16;
+    const uint64_t frank_at = dec_a16(P * 8) + 16, pre_at = frank_at + dec_a16(P * 4) + 16, dinc_at = pre_at + dec_a16(P * 4) + 16,
+                   dval_at = dinc_at + dec_a16(P * 4) + 16, map_at = dval_at + dec_a16(P * 2) + 16, far_bytes = map_at + P + 16;
+    const uint64_t bsum_bytes = dec_a16(sco_scratch_elems(P) * 4) + 2 * PP_OR_BLOCKS * 8 + 64;
+    if ((e = pgrc_bufs_unpooled(d, {{&d->pp_in, on_device ? 16 : T * 8 + 16}, {&d->pp_rank, rank_bytes}, {&d->pp_far, far_bytes}, {&d->pp_out, dev.total}, {&d->pp_bsum, bsum_bytes}})))
         return e;
     if (T && !on_device && (e = dec_upload(d, d->pp_in.p, org_h, T * 8))) return e;
-    const float ms_upload = pp_ms(t0);
+    const float ms_upload = dec_ms_since(t0);
     const uint64_t *org = on_device ? org_h : (const uint64_t *)d->pp_in.p;
     uint8_t *rk = (uint8_t *)d->pp_rank.p, *fr = (uint8_t *)d->pp_far.p, *ob = (uint8_t *)d->pp_out.p;
     uint64_t *rel = (uint64_t *)rk;
@@ -465,7 +437,7 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
     uint64_t *bor = (uint64_t *)((uint8_t *)d->pp_bsum.p + bsum_bytes - 2 * PP_OR_BLOCKS * 8 - 32);
     uint32_t *sco_tmp = (uint32_t *)d->pp_bsum.p;
 
-    HIP_TRY(d, hipEventRecord(d->pp_ev[0], d->stream));
+    HIP_TRY(d, d->pp_ev.record(0, d->stream));
     const uint32_t nor = (uint32_t)std::min<uint64_t>(pp_grid(P), PP_OR_BLOCKS);
     hipLaunchKernelGGL((k_pp_records<W8, PpBaseOrg>), dim3(nor), dim3(PP_TPB), 0, d->stream, PpBaseOrg{org}, P, (uint64_t *)d->pp_rec[0].p,
                        (uint64_t *)(W8 ? d->pp_val[0].p : nullptr), bor);
@@ -477,14 +449,14 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
     if (!W8 && (ors[1] >> 32)) return pp_fail(d, who, "a position of 2^32 or more with pos_width 4");
     const uint64_t *a = nullptr, *b = nullptr;
     if ((e = pp_sort(d, W8, P, ors[0], &a, &b))) return e;
-    HIP_TRY(d, hipEventRecord(d->pp_ev[1], d->stream));
+    HIP_TRY(d, d->pp_ev.record(1, d->stream));
     uint32_t n_near = 0, n_del = 0;
     if (P) {
         hipLaunchKernelGGL((k_pp_enc_class<W8>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, a, b, org, P, off16_flag, rel, bf);
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)off16_flag, near_inc, P, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, hipEventRecord(d->pp_ev[2], d->stream));
+    HIP_TRY(d, d->pp_ev.record(2, d->stream));
     if (P) {
         if (W8) hipLaunchKernelGGL((k_pp_enc_base<uint64_t>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, org, P, (uint64_t *)(ob + dev.at[0]));
         else hipLaunchKernelGGL((k_pp_enc_base<uint32_t>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, org, P, (uint32_t *)(ob + dev.at[0]));
@@ -492,7 +464,7 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
                            (const uint8_t *)bf, off_bf, off_val, far_rel, far_rank);
     }
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(d->pp_ev[3], d->stream));
+    HIP_TRY(d, d->pp_ev.record(3, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     const uint64_t nf = P - n_near;
     if (nf) {
@@ -502,11 +474,11 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)del_flag, del_inc, nf, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, hipEventRecord(d->pp_ev[4], d->stream));
+    HIP_TRY(d, d->pp_ev.record(4, d->stream));
     if (nf) hipLaunchKernelGGL((k_pp_enc_far<W8>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rank, (const uint64_t *)far_rel,
                                (const uint8_t *)del_flag, (const uint32_t *)del_inc, (const int16_t *)dval, (const uint8_t *)bf, a, b, del_bf, del_val, not_base);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(d->pp_ev[5], d->stream));
+    HIP_TRY(d, d->pp_ev.record(5, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
 
     // the streams, now that their sizes are known: one page-locked block
@@ -552,11 +524,11 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
     t.struct_size = sizeof(pgrc_pairpos_timing);
     t.encode = 1;
     t.ms_upload = ms_upload;
-    t.ms_sort_device = dec_elapsed(d->pp_ev[0], d->pp_ev[1]);
-    t.ms_scan_device = dec_elapsed(d->pp_ev[1], d->pp_ev[2]) + dec_elapsed(d->pp_ev[3], d->pp_ev[4]);
-    t.ms_scatter_device = dec_elapsed(d->pp_ev[2], d->pp_ev[3]) + dec_elapsed(d->pp_ev[4], d->pp_ev[5]);
-    t.ms_download = pp_ms(t1);
-    t.ms_call = pp_ms(t0);
+    t.ms_sort_device = d->pp_ev.ms(0, 1);
+    t.ms_scan_device = d->pp_ev.ms(1, 2) + d->pp_ev.ms(3, 4);
+    t.ms_scatter_device = d->pp_ev.ms(2, 3) + d->pp_ev.ms(4, 5);
+    t.ms_download = dec_ms_since(t1);
+    t.ms_call = dec_ms_since(t0);
     t.bytes_up = on_device ? 0 : T * 8;
     t.bytes_down = down;
     t.n_near = n_near;
@@ -606,10 +578,10 @@ int pgrc_pairpos_decode(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint6
     if ((e = pgrc_buf_unpooled(d, d->pp_out, s->n_total * 8 + 16))) return e;
     if ((e = pgrc_pairpos_decode_device(d, s, (uint64_t *)d->pp_out.p))) return e;
     const auto t1 = std::chrono::steady_clock::now();
-    if ((e = pp_download(d, pg_pos, d->pp_out.p, s->n_total * 8))) return e;
-    d->ptm.ms_download = pp_ms(t1);
+    if ((e = dec_download_host(d, pg_pos, d->pp_out.p, s->n_total * 8))) return e;
+    d->ptm.ms_download = dec_ms_since(t1);
     d->ptm.bytes_down = s->n_total * 8;
-    d->ptm.ms_call = pp_ms(t0);
+    d->ptm.ms_call = dec_ms_since(t0);
     d->have_pp_timing = true;
     return PGRC_OK;
 }

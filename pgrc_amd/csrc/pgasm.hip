@@ -35,9 +35,11 @@ enum { AS_BAD_NEXT, AS_BAD_PRED, AS_BAD_OVL, AS_BAD_OVL_END, AS_BAD_LINK, AS_BAD
 enum { AS_CNT_CYCLES, AS_CNT_LOST, AS_CNT_COMPONENTS, AS_CNT_SINGLES, AS_CNT_WORDS };
 
 struct pgrc_asm_ctx {
-    pgrc_decode_ctx *d = nullptr;       // the stream, the staging buffers, the error string and the text (text, text_len, have_text)
+    // The stage handle, and a decode context because the assembled text is one's text: pgrc_decode_get_text reads it, and it
+    // ends in the padding the row kernels expect (text, text_len, have_text; the read length is that of the last run)
+    pgrc_decode_ctx *d = nullptr;
     DevBuf rows, nx, ovraw, ov, pred, st, len, walk, sh, off, org, start, map, fold, words, packed;
-    hipEvent_t ev[7]{};
+    PhaseEvents<7> ev;
     uint32_t symbols = 0;
     bool have_packed = false, have_timing = false;
     // the reads list of the last successful run where it lies (org, off): its entries, and whether the run applied a host mapping
@@ -46,10 +48,8 @@ struct pgrc_asm_ctx {
     pgrc_asm_timing tm{};
 };
 
-static inline uint64_t as_a16(uint64_t b) { return (b + 15) & ~15ull; }
-static inline uint32_t as_grid(uint64_t n) { return (uint32_t)((n + AS_TPB - 1) / AS_TPB); }
-static inline float as_ms(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+static DevBufList as_bufs(pgrc_asm_ctx *a) {
+    return {&a->rows, &a->nx, &a->ovraw, &a->ov, &a->pred, &a->st, &a->len, &a->walk, &a->sh, &a->off, &a->org, &a->start, &a->map, &a->fold, &a->words, &a->packed};
 }
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -278,8 +278,8 @@ static int as_jump(pgrc_asm_ctx *a, bool rank, uint64_t R, uint32_t cap, uint32_
     *passes = 0;
     while (more && *passes < cap) {
         if ((e = dec_clear_err(d))) return e;
-        if (rank) hipLaunchKernelGGL(k_as_rank_jump, dim3(as_grid(R + 1)), dim3(AS_TPB), 0, d->stream, st, R, flag);
-        else hipLaunchKernelGGL(k_as_cyc_jump, dim3(as_grid(R + 1)), dim3(AS_TPB), 0, d->stream, st, R, flag);
+        if (rank) hipLaunchKernelGGL(k_as_rank_jump, dim3(dec_grid(R + 1, AS_TPB)), dim3(AS_TPB), 0, d->stream, st, R, flag);
+        else hipLaunchKernelGGL(k_as_cyc_jump, dim3(dec_grid(R + 1, AS_TPB)), dim3(AS_TPB), 0, d->stream, st, R, flag);
         HIP_TRY(d, hipGetLastError());
         HIP_TRY(d, hipMemcpyAsync(&more, flag, 4, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(d, hipStreamSynchronize(d->stream));
@@ -317,14 +317,11 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     const uint32_t L = in->read_len, symbols = in->symbols, width = in->overlap_width;
     const uint32_t rb = symbols == 4 ? (L + 3) / 4 : (L + 2) / 3;
     int e;
-    for (hipEvent_t &ev : a->ev)
-        if (!ev) HIP_TRY(d, hipEventCreate(&ev));
-    const uint64_t fold_bytes = as_a16(sco_scratch_elems(N1) * 8);
-    if ((e = pgrc_buf_unpooled(d, a->rows, R * rb + 16)) || (e = pgrc_buf_unpooled(d, a->nx, N1 * 4)) || (e = pgrc_buf_unpooled(d, a->ovraw, N1 * width)) || (e = pgrc_buf_unpooled(d, a->ov, N1 * 2)) ||
-        (e = pgrc_buf_unpooled(d, a->pred, N1 * 4)) || (e = pgrc_buf_unpooled(d, a->st, N1 * 8)) || (e = pgrc_buf_unpooled(d, a->len, N1 * 4)) || (e = pgrc_buf_unpooled(d, a->walk, R * 4)) ||
-        (e = pgrc_buf_unpooled(d, a->sh, R * 2)) || (e = pgrc_buf_unpooled(d, a->off, R * 2)) || (e = pgrc_buf_unpooled(d, a->org, R * 4)) || (e = pgrc_buf_unpooled(d, a->start, N1 * 8)) ||
-        (e = pgrc_buf_unpooled(d, a->map, in->index_mapping ? R * 4 : 16)) || (e = pgrc_buf_unpooled(d, a->fold, fold_bytes)) ||
-        (e = pgrc_buf_unpooled(d, a->words, AS_BAD_WORDS * 4 + AS_CNT_WORDS * 8 + 16)))
+    if ((e = a->ev.ensure(d))) return e;
+    const uint64_t fold_bytes = dec_a16(sco_scratch_elems(N1) * 8);
+    if ((e = pgrc_bufs_unpooled(d, {{&a->rows, R * rb + 16}, {&a->nx, N1 * 4}, {&a->ovraw, N1 * width}, {&a->ov, N1 * 2}, {&a->pred, N1 * 4}, {&a->st, N1 * 8},
+                                    {&a->len, N1 * 4}, {&a->walk, R * 4}, {&a->sh, R * 2}, {&a->off, R * 2}, {&a->org, R * 4}, {&a->start, N1 * 8},
+                                    {&a->map, in->index_mapping ? R * 4 : 16}, {&a->fold, fold_bytes}, {&a->words, AS_BAD_WORDS * 4 + AS_CNT_WORDS * 8 + 16}})))
         return e;
     const uint8_t *rows = (const uint8_t *)a->rows.p;
     uint32_t *nx = (uint32_t *)a->nx.p, *pred = (uint32_t *)a->pred.p, *len = (uint32_t *)a->len.p, *walk = (uint32_t *)a->walk.p, *org = (uint32_t *)a->org.p;
@@ -339,19 +336,19 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     HIP_TRY(d, hipMemsetAsync(pred, 0, N1 * 4, d->stream));
     HIP_TRY(d, hipMemsetAsync(len, 0, N1 * 4, d->stream));
     HIP_TRY(d, hipMemsetAsync(a->words.p, 0, AS_BAD_WORDS * 4 + AS_CNT_WORDS * 8, d->stream));
-    const float ms_upload = as_ms(t0);
-    const uint32_t grid = as_grid(N1);
+    const float ms_upload = dec_ms_since(t0);
+    const uint32_t grid = dec_grid(N1, AS_TPB);
 
     // pred and the checks
-    HIP_TRY(d, hipEventRecord(a->ev[0], d->stream));
+    HIP_TRY(d, a->ev.record(0, d->stream));
     hipLaunchKernelGGL(k_as_pred, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint32_t *)nx, (const void *)a->ovraw.p, width, R, L, pred, ov, bad);
     hipLaunchKernelGGL(k_as_link, dim3(grid), dim3(AS_TPB), 0, d->stream, rows, rb, symbols, L, (const uint32_t *)nx, (const uint16_t *)ov, (const uint32_t *)pred, R, bad);
     if (symbols == 5) {
         const uint64_t total = R * rb;
-        hipLaunchKernelGGL(k_as_rows5, dim3((uint32_t)std::min<uint64_t>(as_grid(total), 1u << 20)), dim3(AS_TPB), 0, d->stream, rows, total, rb, L, bad);
+        hipLaunchKernelGGL(k_as_rows5, dim3((uint32_t)std::min<uint64_t>(dec_grid(total, AS_TPB), 1u << 20)), dim3(AS_TPB), 0, d->stream, rows, total, rb, L, bad);
     }
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(a->ev[1], d->stream));
+    HIP_TRY(d, a->ev.record(1, d->stream));
     uint32_t h_bad[AS_BAD_WORDS] = {};
     HIP_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
@@ -367,26 +364,26 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     uint32_t bits = 0;
     while (bits < 33 && (1ull << bits) < N1) bits++;            // ceil(log2(R + 1))
     uint32_t passes_cyc = 0, passes_rank = 0, live = 0;
-    HIP_TRY(d, hipEventRecord(a->ev[2], d->stream));
+    HIP_TRY(d, a->ev.record(2, d->stream));
     hipLaunchKernelGGL(k_as_cyc_init, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint32_t *)nx, R, st);
     if ((e = as_jump(a, false, R, bits + 1, &passes_cyc, &live))) return e;
     if (live) hipLaunchKernelGGL(k_as_cut, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint64_t *)st, R, nx, ov, pred, cnt);
     HIP_TRY(d, hipGetLastError());
 
     // ranking
-    HIP_TRY(d, hipEventRecord(a->ev[3], d->stream));
+    HIP_TRY(d, a->ev.record(3, d->stream));
     hipLaunchKernelGGL(k_as_rank_init, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint32_t *)pred, R, st);
     if ((e = as_jump(a, true, R, bits + 3, &passes_rank, &live))) return e;
     if (live) return dec_fail(d, PGRC_E_DEVICE, "assemble: the chains did not resolve in " + std::to_string(passes_rank) + " passes");
 
     // lists
-    HIP_TRY(d, hipEventRecord(a->ev[4], d->stream));
+    HIP_TRY(d, a->ev.record(4, d->stream));
     hipLaunchKernelGGL(k_as_tails, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint64_t *)st, (const uint32_t *)nx, R, len, cnt);
     HIP_TRY(d, sco_scan<false>(d->stream, (const uint32_t *)len, len, N1, ScoIdentity{}, ScoPlus{}, 0u, (uint32_t *)a->fold.p));
     hipLaunchKernelGGL(k_as_place, dim3(grid), dim3(AS_TPB), 0, d->stream, (const uint64_t *)st, (const uint32_t *)len, (const uint16_t *)ov, map, R, L, walk, sh, off, org);
     HIP_TRY(d, sco_sum_u64<false>(d->stream, (const uint16_t *)sh, R, start, (uint64_t *)a->fold.p));
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(a->ev[5], d->stream));
+    HIP_TRY(d, a->ev.record(5, d->stream));
     uint64_t pg_len = 0;
     unsigned long long h_cnt[AS_CNT_WORDS] = {};
     HIP_TRY(d, hipMemcpyAsync(&pg_len, start + R, 8, hipMemcpyDeviceToHost, d->stream));
@@ -401,11 +398,11 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     hipLaunchKernelGGL(k_as_text, dim3((uint32_t)tiles), dim3(AS_TPB), 0, d->stream, rows, rb, symbols, (const uint32_t *)walk, (const uint16_t *)sh,
                        (const uint64_t *)start, R, pg_len, (uint8_t *)d->text.p);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(a->ev[6], d->stream));
+    HIP_TRY(d, a->ev.record(6, d->stream));
 
     // the reads list: one page-locked block, copied down while the text is made
     const auto t1 = std::chrono::steady_clock::now();
-    const uint64_t off_at = as_a16(R * 4), total = off_at + as_a16(R * 2);
+    const uint64_t off_at = dec_a16(R * 4), total = off_at + dec_a16(R * 2);
     uint8_t *blk = nullptr;
     float ms_download = 0;
     if (list_stays) {
@@ -420,7 +417,7 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
         he = hipMemcpyAsync(blk, org, R * 4, hipMemcpyDeviceToHost, d->copy_stream);
         if (he == hipSuccess) he = hipMemcpyAsync(blk + off_at, off, R * 2, hipMemcpyDeviceToHost, d->copy_stream);
         if (he == hipSuccess) he = hipStreamSynchronize(d->copy_stream);
-        ms_download = as_ms(t1);
+        ms_download = dec_ms_since(t1);
         if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
         if (he != hipSuccess) {
             (void)hipHostFree(blk);
@@ -448,13 +445,13 @@ static int as_run(pgrc_asm_ctx *a, const pgrc_asm_input *in, pgrc_asm_result *ou
     t.passes_cycles = passes_cyc;
     t.passes_rank = passes_rank;
     t.ms_upload = ms_upload;
-    t.ms_checks_device = dec_elapsed(a->ev[0], a->ev[1]);
-    t.ms_cycles_device = dec_elapsed(a->ev[2], a->ev[3]);
-    t.ms_rank_device = dec_elapsed(a->ev[3], a->ev[4]);
-    t.ms_lists_device = dec_elapsed(a->ev[4], a->ev[5]);
-    t.ms_text_device = dec_elapsed(a->ev[5], a->ev[6]);
+    t.ms_checks_device = a->ev.ms(0, 1);
+    t.ms_cycles_device = a->ev.ms(2, 3);
+    t.ms_rank_device = a->ev.ms(3, 4);
+    t.ms_lists_device = a->ev.ms(4, 5);
+    t.ms_text_device = a->ev.ms(5, 6);
     t.ms_download = ms_download;
-    t.ms_call = as_ms(t0);
+    t.ms_call = dec_ms_since(t0);
     t.bytes_up = (on_device ? 0 : R * rb + N1 * 4 + N1 * width) + (map ? R * 4 : 0);
     t.bytes_down = list_stays ? 0 : R * 6;
     a->have_timing = true;
@@ -511,7 +508,7 @@ int pgrc_asm_create(int32_t device, pgrc_asm_ctx **out) {
     if (!out) return PGRC_E_PARAM;
     *out = nullptr;
     pgrc_decode_ctx *d = nullptr;
-    const int e = pgrc_decode_create(1, device, &d);        // (the read length is set by every run)
+    const int e = pgrc_decode_create_on(device, &d);
     if (e) return e;
     pgrc_asm_ctx *a = new pgrc_asm_ctx();
     a->d = d;
@@ -524,11 +521,8 @@ void pgrc_asm_destroy(pgrc_asm_ctx *a) {
     {
         PgrcDeviceScope scope(a->d->device);
         (void)hipStreamSynchronize(a->d->stream);
-        for (DevBuf *b : {&a->rows, &a->nx, &a->ovraw, &a->ov, &a->pred, &a->st, &a->len, &a->walk, &a->sh, &a->off, &a->org, &a->start, &a->map, &a->fold, &a->words,
-                           &a->packed})
-            dec_free(*b);
-        for (hipEvent_t ev : a->ev)
-            if (ev) (void)hipEventDestroy(ev);
+        dec_free_all(as_bufs(a));
+        a->ev.release();
     }
     pgrc_decode_destroy(a->d);
     delete a;

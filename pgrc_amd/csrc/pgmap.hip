@@ -296,9 +296,7 @@ void pgrc_pgmap_release(pgrc_mem_ctx *m) {
                       &m->pm_lens, &m->pm_out, &m->pm_fold, &m->pm_small, &m->pm_res[0], &m->pm_res[1], &m->pm_res[2]};
     for (bool &set : m->res_set) set = false;
     for (DevBuf *b : bufs) pgrc_buf_free(*b);
-    if (m->have_pm_ev)
-        for (auto &x : m->pm_ev) (void)hipEventDestroy(x);
-    m->have_pm_ev = false;
+    m->pm_ev.release();
 }
 
 // pgrc_mem_mark_and_remove (part < 0: the mapped text goes down to mapped_out) and pgrc_mem_mark_and_remove_resident (part
@@ -375,13 +373,10 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
     pgrc_match_ctx *c = m->base;
     PgrcDeviceScope dev_scope__(c->device);
     if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
-    if (!m->have_pm_ev) {
-        for (auto &x : m->pm_ev) HIP_TRY(m, hipEventCreate(&x));
-        m->have_pm_ev = true;
-    }
-    hipEvent_t *ev = m->pm_ev;
+    int e = m->pm_ev.ensure(m);
+    if (e) return e;
+    auto &ev = m->pm_ev;
     hipStream_t st = c->stream;
-    int e = 0;
     auto ens = [&](DevBuf &b, uint64_t bytes) {
         if (!e && (e = pgrc_buf_ensure(c, b, (size_t)std::max<uint64_t>(bytes, 64)))) m->err = c->err;
     };
@@ -392,7 +387,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
     if (e) return e;
     uint64_t *fold64 = (uint64_t *)m->pm_fold.p;
     uint32_t *fold32 = (uint32_t *)m->pm_fold.p;
-    HIP_TRY(m, hipEventRecord(ev[0], st));
+    HIP_TRY(m, ev.record(0, st));
 
     // ---- 1. normalise, sort by (dst, src, len), unique
     uint64_t nu = 0, nuniq = 0;
@@ -452,7 +447,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
         }
     }
     HIP_TRY(m, hipGetLastError());
-    HIP_TRY(m, hipEventRecord(ev[1], st));
+    HIP_TRY(m, ev.record(1, st));
 
     // ---- 2. the greedy pass as a path
     uint64_t marks = 0;
@@ -483,7 +478,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
                            (uint64_t *)m->pm_m[0].p, (uint64_t *)m->pm_m[1].p, (uint64_t *)m->pm_m[2].p);
     }
     HIP_TRY(m, hipGetLastError());
-    HIP_TRY(m, hipEventRecord(ev[2], st));
+    HIP_TRY(m, ev.record(2, st));
 
     // ---- 3. the marks and the two streams
     ens(m->pm_dp, marks * 8);
@@ -512,7 +507,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
         hipLaunchKernelGGL(k_pm_streams, dim3(pm_grid(marks)), dim3(PM_TPB), 0, st, (const uint64_t *)m->pm_dp.p, (const uint64_t *)m->pm_len.p,
                            (const uint64_t *)cum, (const uint64_t *)nbpos, marks, min_len, (uint64_t *)m->pm_mp.p, (uint8_t *)m->pm_lens.p);
     HIP_TRY(m, hipGetLastError());
-    HIP_TRY(m, hipEventRecord(ev[3], st));
+    HIP_TRY(m, ev.record(3, st));
 
     // ---- 4. the mapped text
     const uint64_t mapped_len = N2 - tot[0] + marks;           // (every mark replaces at least one symbol: <= N2)
@@ -535,7 +530,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
         hipLaunchKernelGGL(k_pm_text, dim3(pm_grid((nwords + PM_LPT - 1) / PM_LPT)), dim3(PM_TPB), 0, st, t);
         HIP_TRY(m, hipGetLastError());
     }
-    HIP_TRY(m, hipEventRecord(ev[4], st));
+    HIP_TRY(m, ev.record(4, st));
     HIP_TRY(m, hipStreamSynchronize(st));
 
     // ---- 5. the downloads
@@ -557,7 +552,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
     if (he == hipSuccess) he = hipStreamSynchronize(st);
     if (he != hipSuccess) { free(block); m->err = std::string("mapping download: ") + hipGetErrorString(he); return pgrc_hip_code(he); }
     m->pm_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (int k = 0; k < 4; k++) (void)hipEventElapsedTime(&m->pm_ms[k], ev[k], ev[k + 1]);
+    for (int k = 0; k < 4; k++) m->pm_ms[k] = ev.ms(k, k + 1);
     out->mapped_len = mapped_len;
     out->marks = marks;
     out->unique_matches = nuniq;

@@ -27,7 +27,6 @@
 #include <vector>
 
 #include "asmctx.h"
-#include "decctx.h"
 #include "devutil.h"
 #include "pgrc_overlap.h"
 #include "rsetsctx.h"
@@ -39,12 +38,11 @@
 // the words of `bad`, in the order the refusals are reported
 enum { OV_BAD_ROW, OV_BAD_RANGE, OV_BAD_TWICE, OV_BAD_SORT, OV_BAD_PLACE, OV_BAD_WORDS };
 
-struct pgrc_ovl_ctx {
-    pgrc_decode_ctx *d = nullptr;       // the stream, the staging buffers, the error string
+struct pgrc_ovl_ctx : PgrcStage {
     DevBuf sort_scratch;
     DevBuf rows, sym, nx, ov, ovout, order, seen, eq, s[2], p[2], base, lens, rk, trans, merged, mk, keep, taken, offs, offp, gs, fold, words, rec[2], prev, flags;
     DevBuf rnk, lead, cnt;              // the parallel rule: the reads' dense ranks, the prefix maxima of a share, two counters
-    hipEvent_t ev[6]{};
+    PhaseEvents<4> ev;
     uint64_t R = 0;
     uint32_t L = 0, symbols = 0, rb = 0;
     bool have_run = false;
@@ -55,10 +53,11 @@ struct pgrc_ovl_ctx {
     std::vector<float> sweep_ms;
 };
 
-static inline uint64_t ov_a16(uint64_t b) { return (b + 15) & ~15ull; }
-static inline uint32_t ov_grid(uint64_t n) { return (uint32_t)((n + OV_TPB - 1) / OV_TPB); }
-static inline float ov_ms(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+static thread_local std::string g_ov_create_err;
+
+static DevBufList ov_bufs(pgrc_ovl_ctx *o) {       // (sort_scratch is pooled)
+    return {&o->rows, &o->sym, &o->nx, &o->ov, &o->ovout, &o->order, &o->seen, &o->eq, &o->s[0], &o->s[1], &o->p[0], &o->p[1], &o->base, &o->lens, &o->rk, &o->trans,
+            &o->merged, &o->mk, &o->keep, &o->taken, &o->offs, &o->offp, &o->gs, &o->fold, &o->words, &o->rec[0], &o->rec[1], &o->prev, &o->flags, &o->rnk, &o->lead, &o->cnt};
 }
 
 // ------------------------------------------------------------------------------------------------ strings
@@ -477,38 +476,36 @@ static __global__ void __launch_bounds__(OV_TPB) k_ov_both(const uint32_t *__res
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int ov_fail(pgrc_ovl_ctx *o, const std::string &msg) { return dec_fail(o->d, PGRC_E_PARAM, "overlap: " + msg); }
+static int ov_fail(pgrc_ovl_ctx *o, const std::string &msg) { return dec_fail(o, PGRC_E_PARAM, "overlap: " + msg); }
 
 // off[0 .. n] = the exclusive scan of the flags (negated: inv), off[n] = their count
 static int ov_scan_flags(pgrc_ovl_ctx *o, const uint8_t *flag, uint32_t inv, uint64_t n, uint32_t *off) {
-    HIP_TRY(o->d, (sco_device_scan<false, true>(o->d->stream, OvFlag{flag, inv}, n, ScoPlus{}, 0u, 0u, ScoStore<uint32_t>{off}, (uint32_t *)o->fold.p)));
+    HIP_TRY(o, (sco_device_scan<false, true>(o->stream, OvFlag{flag, inv}, n, ScoPlus{}, 0u, 0u, ScoStore<uint32_t>{off}, (uint32_t *)o->fold.p)));
     return PGRC_OK;
 }
 
 // the sorted order made on the device: a stable LSD sort of the read numbers by 8 symbols a time, last chunk first
 static int ov_make_order(pgrc_ovl_ctx *o, uint64_t R, uint32_t L, uint32_t stride) {
-    pgrc_decode_ctx *d = o->d;
     int e;
-    if ((e = pgrc_buf_unpooled(d, o->rec[0], R * 8)) || (e = pgrc_buf_unpooled(d, o->rec[1], R * 8))) return e;
+    if ((e = pgrc_bufs_unpooled(o, {{&o->rec[0], R * 8}, {&o->rec[1], R * 8}}))) return e;
     uint64_t *cur = (uint64_t *)o->rec[0].p, *oth = (uint64_t *)o->rec[1].p;
     const uint8_t *sym = (const uint8_t *)o->sym.p;
     const uint32_t chunks = (L + OV_CHUNK - 1) / OV_CHUNK;
     for (uint32_t c = chunks; c-- > 0;) {
-        if (c + 1 == chunks) hipLaunchKernelGGL(k_ov_keys<true>, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, sym, stride, c, R, (const uint64_t *)nullptr, cur);
-        else hipLaunchKernelGGL(k_ov_keys<false>, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, sym, stride, c, R, (const uint64_t *)cur, cur);
-        HIP_TRY(d, hipGetLastError());
+        if (c + 1 == chunks) hipLaunchKernelGGL(k_ov_keys<true>, dim3(dec_grid(R, OV_TPB)), dim3(OV_TPB), 0, o->stream, sym, stride, c, R, (const uint64_t *)nullptr, cur);
+        else hipLaunchKernelGGL(k_ov_keys<false>, dim3(dec_grid(R, OV_TPB)), dim3(OV_TPB), 0, o->stream, sym, stride, c, R, (const uint64_t *)cur, cur);
+        HIP_TRY(o, hipGetLastError());
         uint64_t *sorted = nullptr;
-        if ((e = pgrc_radix_sort_u64(d, cur, oth, R, 32, 32 + 3 * OV_CHUNK, o->sort_scratch, &sorted))) return dec_fail(d, e, "overlap: " + d->err);
+        if ((e = pgrc_radix_sort_u64(o, cur, oth, R, 32, 32 + 3 * OV_CHUNK, o->sort_scratch, &sorted))) return dec_fail(o, e, "overlap: " + o->err);
         if (sorted != cur) std::swap(cur, oth);
     }
-    hipLaunchKernelGGL(k_ov_order_of, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint64_t *)cur, R, (uint32_t *)o->order.p);
-    HIP_TRY(d, hipGetLastError());
+    hipLaunchKernelGGL(k_ov_order_of, dim3(dec_grid(R, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint64_t *)cur, R, (uint32_t *)o->order.p);
+    HIP_TRY(o, hipGetLastError());
     return PGRC_OK;
 }
 
 // rows_on_device: in->packed_rows is memory of this device (pgovl_run_rows), copied where the host's rows are uploaded
 static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *out, bool rows_on_device) {
-    pgrc_decode_ctx *d = o->d;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = in->n_reads, N1 = R + 1;
     const uint32_t L = in->read_len, symbols = in->symbols, width = in->overlap_width;
@@ -521,17 +518,13 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     const uint32_t tail_from = L - OV_BLOCK_PREFIX;        // the parallel rule (L >= 4): the first sweep that pairs whole blocks
     const bool follow = par && tail_from <= sweeps;         // ... is run, and the merge in front of it
     int e;
-    for (hipEvent_t &ev : o->ev)
-        if (!ev) HIP_TRY(d, hipEventCreate(&ev));
-    if ((e = pgrc_buf_unpooled(d, o->rows, R * rb + 16)) || (e = pgrc_buf_unpooled(d, o->sym, R * stride + 16)) || (e = pgrc_buf_unpooled(d, o->nx, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->ov, N1 * 2)) ||
-        (e = pgrc_buf_unpooled(d, o->ovout, N1)) || (e = pgrc_buf_unpooled(d, o->order, R * 4)) || (e = pgrc_buf_unpooled(d, o->seen, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->eq, R)) ||
-        (e = pgrc_buf_unpooled(d, o->s[0], R * 4)) || (e = pgrc_buf_unpooled(d, o->s[1], R * 4)) || (e = pgrc_buf_unpooled(d, o->p[0], R * 4)) || (e = pgrc_buf_unpooled(d, o->p[1], R * 4)) ||
-        (e = pgrc_buf_unpooled(d, o->base, R * 4)) || (e = pgrc_buf_unpooled(d, o->lens, R * 20)) || (e = pgrc_buf_unpooled(d, o->rk, R * 4)) || (e = pgrc_buf_unpooled(d, o->trans, R * 4 + 64)) ||
-        (e = pgrc_buf_unpooled(d, o->merged, R * 4)) || (e = pgrc_buf_unpooled(d, o->mk, R * 4)) || (e = pgrc_buf_unpooled(d, o->keep, R)) || (e = pgrc_buf_unpooled(d, o->taken, R)) ||
-        (e = pgrc_buf_unpooled(d, o->offs, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->offp, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->gs, 64)) ||
-        (e = pgrc_buf_unpooled(d, o->fold, ov_a16(sco_scratch_elems(N1) * 8))) || (e = pgrc_buf_unpooled(d, o->words, OV_BAD_WORDS * 4 + 16)))
+    if ((e = o->ev.ensure(o))) return e;
+    if ((e = pgrc_bufs_unpooled(o, {{&o->rows, R * rb + 16}, {&o->sym, R * stride + 16}, {&o->nx, N1 * 4}, {&o->ov, N1 * 2}, {&o->ovout, N1}, {&o->order, R * 4},
+                                    {&o->seen, N1 * 4}, {&o->eq, R}, {&o->s[0], R * 4}, {&o->s[1], R * 4}, {&o->p[0], R * 4}, {&o->p[1], R * 4}, {&o->base, R * 4},
+                                    {&o->lens, R * 20}, {&o->rk, R * 4}, {&o->trans, R * 4 + 64}, {&o->merged, R * 4}, {&o->mk, R * 4}, {&o->keep, R}, {&o->taken, R},
+                                    {&o->offs, N1 * 4}, {&o->offp, N1 * 4}, {&o->gs, 64}, {&o->fold, dec_a16(sco_scratch_elems(N1) * 8)}, {&o->words, OV_BAD_WORDS * 4 + 16}})))
         return e;
-    if (par && ((e = pgrc_buf_unpooled(d, o->rnk, N1 * 4)) || (e = pgrc_buf_unpooled(d, o->lead, R * 4)) || (e = pgrc_buf_unpooled(d, o->cnt, 16)))) return e;
+    if (par && (e = pgrc_bufs_unpooled(o, {{&o->rnk, N1 * 4}, {&o->lead, R * 4}, {&o->cnt, 16}}))) return e;
     const uint8_t *rows = (const uint8_t *)o->rows.p;
     uint8_t *sym = (uint8_t *)o->sym.p, *eq = (uint8_t *)o->eq.p, *keep = (uint8_t *)o->keep.p, *taken = (uint8_t *)o->taken.p;
     uint32_t *nx = (uint32_t *)o->nx.p, *order = (uint32_t *)o->order.p, *base = (uint32_t *)o->base.p, *lens = (uint32_t *)o->lens.p, *rk = (uint32_t *)o->rk.p;
@@ -539,74 +532,74 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     uint32_t *gs = (uint32_t *)o->gs.p, *bad = (uint32_t *)o->words.p;
     uint16_t *ov = (uint16_t *)o->ov.p;
 
-    if (rows_on_device) HIP_TRY(d, hipMemcpyAsync(o->rows.p, in->packed_rows, R * rb, hipMemcpyDeviceToDevice, d->stream));
-    else if ((e = dec_upload_host(d, o->rows.p, in->packed_rows, R * rb))) return e;
-    if (in->sorted_order && (e = dec_upload_host(d, order, in->sorted_order, R * 4))) return e;
-    HIP_TRY(d, hipMemsetAsync(sym, 0, R * stride + 16, d->stream));
-    HIP_TRY(d, hipMemsetAsync(nx, 0, N1 * 4, d->stream));
-    HIP_TRY(d, hipMemsetAsync(ov, 0, N1 * 2, d->stream));
-    HIP_TRY(d, hipMemsetAsync(o->seen.p, 0, N1 * 4, d->stream));
-    HIP_TRY(d, hipMemsetAsync(bad, 0, OV_BAD_WORDS * 4, d->stream));
-    if (par) HIP_TRY(d, hipMemsetAsync(o->cnt.p, 0, 16, d->stream));
-    const float ms_upload = ov_ms(t0);
+    if (rows_on_device) HIP_TRY(o, hipMemcpyAsync(o->rows.p, in->packed_rows, R * rb, hipMemcpyDeviceToDevice, o->stream));
+    else if ((e = dec_upload_host(o, o->rows.p, in->packed_rows, R * rb))) return e;
+    if (in->sorted_order && (e = dec_upload_host(o, order, in->sorted_order, R * 4))) return e;
+    HIP_TRY(o, hipMemsetAsync(sym, 0, R * stride + 16, o->stream));
+    HIP_TRY(o, hipMemsetAsync(nx, 0, N1 * 4, o->stream));
+    HIP_TRY(o, hipMemsetAsync(ov, 0, N1 * 2, o->stream));
+    HIP_TRY(o, hipMemsetAsync(o->seen.p, 0, N1 * 4, o->stream));
+    HIP_TRY(o, hipMemsetAsync(bad, 0, OV_BAD_WORDS * 4, o->stream));
+    if (par) HIP_TRY(o, hipMemsetAsync(o->cnt.p, 0, 16, o->stream));
+    const float ms_upload = dec_ms_since(t0);
 
     // the rows unpacked and checked, the order made or checked
-    HIP_TRY(d, hipEventRecord(o->ev[0], d->stream));
+    HIP_TRY(o, o->ev.record(0, o->stream));
     {
         const uint64_t total = R * rb;
-        hipLaunchKernelGGL(k_ov_unpack, dim3((uint32_t)std::min<uint64_t>(ov_grid(total), 1u << 20)), dim3(OV_TPB), 0, d->stream, rows, total, rb, symbols, L, stride, sym, bad);
-        HIP_TRY(d, hipGetLastError());
+        hipLaunchKernelGGL(k_ov_unpack, dim3((uint32_t)std::min<uint64_t>(dec_grid(total, OV_TPB), 1u << 20)), dim3(OV_TPB), 0, o->stream, rows, total, rb, symbols, L, stride, sym, bad);
+        HIP_TRY(o, hipGetLastError());
     }
-    if (in->sorted_order) hipLaunchKernelGGL(k_ov_perm, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, R, (uint32_t *)o->seen.p, bad);
+    if (in->sorted_order) hipLaunchKernelGGL(k_ov_perm, dim3(dec_grid(R, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)order, R, (uint32_t *)o->seen.p, bad);
     else if ((e = ov_make_order(o, R, L, stride))) return e;
-    hipLaunchKernelGGL(k_ov_adjacent, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, L, (const uint32_t *)order, R, eq, bad);
-    HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(o->ev[1], d->stream));
+    hipLaunchKernelGGL(k_ov_adjacent, dim3(dec_grid(R, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint8_t *)sym, stride, L, (const uint32_t *)order, R, eq, bad);
+    HIP_TRY(o, hipGetLastError());
+    HIP_TRY(o, o->ev.record(1, o->stream));
     uint32_t h_bad[OV_BAD_WORDS] = {};
-    HIP_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(o, hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(o, hipStreamSynchronize(o->stream));
     // nothing below follows a read number before the order is known to be a permutation of 1 .. R
     if (h_bad[OV_BAD_ROW]) return ov_fail(o, "a row byte that is no packing of the alphabet");
     if (h_bad[OV_BAD_RANGE]) return ov_fail(o, "sorted_order holds a number outside 1 .. " + std::to_string(R));
     if (h_bad[OV_BAD_TWICE]) return ov_fail(o, "sorted_order holds a read twice");
     if (h_bad[OV_BAD_SORT]) {
-        if (!in->sorted_order) return dec_fail(d, PGRC_E_DEVICE, "overlap: the order made on the device is not sorted");
+        if (!in->sorted_order) return dec_fail(o, PGRC_E_DEVICE, "overlap: the order made on the device is not sorted");
         return ov_fail(o, "sorted_order is not sorted: a read is followed by a smaller one");
     }
-    const float ms_order = dec_elapsed(o->ev[0], o->ev[1]);
+    const float ms_order = o->ev.ms(0, 1);
 
     // the start: chains of equal reads, P and S, the groups by the first symbol
     uint32_t *S = (uint32_t *)o->s[0].p, *S2 = (uint32_t *)o->s[1].p, *P = (uint32_t *)o->p[0].p, *P2 = (uint32_t *)o->p[1].p;
-    HIP_TRY(d, hipEventRecord(o->ev[0], d->stream));
+    HIP_TRY(o, o->ev.record(0, o->stream));
     if (follow) {       // the reads' dense ranks: the runs of equal reads that end in front of a place of the order
         if ((e = ov_scan_flags(o, eq, 1, R, offs))) return e;
-        hipLaunchKernelGGL(k_ov_rank_of, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, (const uint32_t *)offs, R, (uint32_t *)o->rnk.p);
-        HIP_TRY(d, hipGetLastError());
+        hipLaunchKernelGGL(k_ov_rank_of, dim3(dec_grid(R, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)order, (const uint32_t *)offs, R, (uint32_t *)o->rnk.p);
+        HIP_TRY(o, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_ov_chains, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, (const uint8_t *)eq, R, L, nx, ov, keep, taken);
-    HIP_TRY(d, hipGetLastError());
+    hipLaunchKernelGGL(k_ov_chains, dim3(dec_grid(R, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)order, (const uint8_t *)eq, R, L, nx, ov, keep, taken);
+    HIP_TRY(o, hipGetLastError());
     if ((e = ov_scan_flags(o, keep, 0, R, offs)) || (e = ov_scan_flags(o, taken, 0, R, offp))) return e;
-    hipLaunchKernelGGL(k_ov_compact, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, (const uint8_t *)keep, 0u, (const uint32_t *)offs, R, R, S);
-    hipLaunchKernelGGL(k_ov_compact, dim3(ov_grid(R)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)order, (const uint8_t *)taken, 0u, (const uint32_t *)offp, R, R, P);
-    HIP_TRY(d, hipGetLastError());
+    hipLaunchKernelGGL(k_ov_compact, dim3(dec_grid(R, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)order, (const uint8_t *)keep, 0u, (const uint32_t *)offs, R, R, S);
+    hipLaunchKernelGGL(k_ov_compact, dim3(dec_grid(R, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)order, (const uint8_t *)taken, 0u, (const uint32_t *)offp, R, R, P);
+    HIP_TRY(o, hipGetLastError());
     uint32_t h_n[2] = {};
-    HIP_TRY(d, hipMemcpyAsync(&h_n[0], offs + R, 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipMemcpyAsync(&h_n[1], offp + R, 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(o, hipMemcpyAsync(&h_n[0], offs + R, 4, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(o, hipMemcpyAsync(&h_n[1], offp + R, 4, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(o, hipStreamSynchronize(o->stream));
     uint64_t ns = h_n[0], np = h_n[1];
-    if (ns != np || ns < 1 || ns > R) return dec_fail(d, PGRC_E_DEVICE, "overlap: " + std::to_string(ns) + " chain ends and " + std::to_string(np) + " chain heads");
-    hipLaunchKernelGGL(k_ov_groups, dim3(ov_grid(ns + 1)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, 0u, (const uint32_t *)S, ns, gs);
-    HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(o->ev[1], d->stream));
-    HIP_TRY(d, hipEventSynchronize(o->ev[1]));
-    const float ms_start = dec_elapsed(o->ev[0], o->ev[1]);
+    if (ns != np || ns < 1 || ns > R) return dec_fail(o, PGRC_E_DEVICE, "overlap: " + std::to_string(ns) + " chain ends and " + std::to_string(np) + " chain heads");
+    hipLaunchKernelGGL(k_ov_groups, dim3(dec_grid(ns + 1, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint8_t *)sym, stride, 0u, (const uint32_t *)S, ns, gs);
+    HIP_TRY(o, hipGetLastError());
+    HIP_TRY(o, o->ev.record(1, o->stream));
+    HIP_TRY(o, hipEventSynchronize(o->ev.ev[1]));
+    const float ms_start = o->ev.ms(0, 1);
 
     // the block of the result; the reads-left numbers are written as they come
-    const uint64_t ov_at = ov_a16(N1 * 4), left_at = ov_at + ov_a16(N1 * width), total = left_at + ov_a16(n_left * 8);
+    const uint64_t ov_at = dec_a16(N1 * 4), left_at = ov_at + dec_a16(N1 * width), total = left_at + dec_a16(n_left * 8);
     uint8_t *blk = nullptr;
     if (hipHostMalloc((void **)&blk, total) != hipSuccess) {
         (void)hipGetLastError();
-        return dec_fail(d, PGRC_E_ALLOC, "overlap: hipHostMalloc(" + std::to_string(total) + ") failed");
+        return dec_fail(o, PGRC_E_ALLOC, "overlap: hipHostMalloc(" + std::to_string(total) + ") failed");
     }
     uint64_t *left = (uint64_t *)(blk + left_at);
     const uint64_t duplicates = R - ns;
@@ -624,91 +617,91 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
             continue;
         }
         const uint32_t n = (uint32_t)ns, npp = (uint32_t)np;
-        hipError_t he = hipMemsetAsync(trans, 0, (uint64_t)n * 4, d->stream);
-        if (he == hipSuccess) he = hipMemsetAsync(taken, 0, npp, d->stream);
-        if (he == hipSuccess) he = hipEventRecord(o->ev[0], d->stream);
+        hipError_t he = hipMemsetAsync(trans, 0, (uint64_t)n * 4, o->stream);
+        if (he == hipSuccess) he = hipMemsetAsync(taken, 0, npp, o->stream);
+        if (he == hipSuccess) he = o->ev.record(0, o->stream);
         if (!par) {
-            hipLaunchKernelGGL(k_ov_ranks<false>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
+            hipLaunchKernelGGL(k_ov_ranks<false>, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
                                base, lens, rk, trans);
             if (he == hipSuccess)
-                he = sco_device_scan<false, false>(d->stream, ScoLoad<uint32_t, uint32_t, ScoIdentity>{trans, ScoIdentity{}}, (uint64_t)n, ScoWeakOrder5{}, 0u,
+                he = sco_device_scan<false, false>(o->stream, ScoLoad<uint32_t, uint32_t, ScoIdentity>{trans, ScoIdentity{}}, (uint64_t)n, ScoWeakOrder5{}, 0u,
                                                    (uint32_t)SCO_WEAK5_SYMBOL_ORDER, ScoStore<uint32_t>{trans}, (uint32_t *)o->fold.p);
-            hipLaunchKernelGGL(k_ov_place<OV_PLACE_SERIAL>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i,
+            hipLaunchKernelGGL(k_ov_place<OV_PLACE_SERIAL>, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i,
                                (const uint32_t *)base, (const uint32_t *)lens, (const uint32_t *)rk, (const uint32_t *)trans, (const uint32_t *)trans, merged, mk, bad);
         } else if (i < tail_from) {
             // the order of the groups starts anew with every block: the transitions keep their reset bits, the scan goes to offs
-            hipLaunchKernelGGL(k_ov_ranks<true>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
+            hipLaunchKernelGGL(k_ov_ranks<true>, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
                                base, lens, rk, trans);
             if (he == hipSuccess)
-                he = sco_device_scan<false, false>(d->stream, ScoLoad<uint32_t, uint32_t, ScoIdentity>{trans, ScoIdentity{}}, (uint64_t)n, ScoWeakOrder5Reset{}, 0u,
+                he = sco_device_scan<false, false>(o->stream, ScoLoad<uint32_t, uint32_t, ScoIdentity>{trans, ScoIdentity{}}, (uint64_t)n, ScoWeakOrder5Reset{}, 0u,
                                                    (uint32_t)SCO_WEAK5_SYMBOL_ORDER, ScoStore<uint32_t>{offs}, (uint32_t *)o->fold.p);
-            hipLaunchKernelGGL(k_ov_place<OV_PLACE_RESET>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i,
+            hipLaunchKernelGGL(k_ov_place<OV_PLACE_RESET>, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i,
                                (const uint32_t *)base, (const uint32_t *)lens, (const uint32_t *)rk, (const uint32_t *)offs, (const uint32_t *)trans, merged, mk, bad);
         } else if (i == tail_from) {
             // a run is a block; its order is the merge by the rows that follow the reads
             const OvFollow f{(const uint32_t *)o->rnk.p, (uint32_t)R};
             uint32_t *lead = (uint32_t *)o->lead.p, *at = (uint32_t *)o->seen.p;
-            hipLaunchKernelGGL(k_ov_ranks<false>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
+            hipLaunchKernelGGL(k_ov_ranks<false>, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
                                base, lens, rk, trans);
-            hipLaunchKernelGGL(k_ov_place_of, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, at);
+            hipLaunchKernelGGL(k_ov_place_of, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)S, n, at);
             if (he == hipSuccess)
-                he = sco_device_scan<true, false>(d->stream, OvShareIn{(const uint8_t *)sym, (const uint32_t *)S, stride, i - 1u}, (uint64_t)n, OvShareMax{f}, (uint64_t)0,
+                he = sco_device_scan<true, false>(o->stream, OvShareIn{(const uint8_t *)sym, (const uint32_t *)S, stride, i - 1u}, (uint64_t)n, OvShareMax{f}, (uint64_t)0,
                                                   (uint64_t)0, OvLeadStore{lead}, (uint64_t *)o->fold.p);
-            hipLaunchKernelGGL(k_ov_place_follow, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i, L, (const uint32_t *)gs,
+            hipLaunchKernelGGL(k_ov_place_follow, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i, L, (const uint32_t *)gs,
                                (const uint32_t *)base, (const uint32_t *)lens, (const uint32_t *)rk, (const uint32_t *)lead, (const uint32_t *)at, f, merged, mk,
                                (unsigned long long *)o->cnt.p, bad);
         } else {
             // what is left was regrouped by dropping its first symbol: a block is its groups' shares one after the other
-            hipLaunchKernelGGL(k_ov_ranks<false>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
+            hipLaunchKernelGGL(k_ov_ranks<false>, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)S, n, (const uint32_t *)gs,
                                base, lens, rk, trans);
-            hipLaunchKernelGGL(k_ov_place<OV_PLACE_CONCAT>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i,
+            hipLaunchKernelGGL(k_ov_place<OV_PLACE_CONCAT>, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)S, n, (const uint8_t *)sym, stride, i,
                                (const uint32_t *)base, (const uint32_t *)lens, (const uint32_t *)rk, (const uint32_t *)trans, (const uint32_t *)trans, merged, mk, bad);
         }
         if (he == hipSuccess) he = hipGetLastError();
-        if (he == hipSuccess) he = hipEventRecord(o->ev[1], d->stream);
+        if (he == hipSuccess) he = o->ev.record(1, o->stream);
         uint32_t placed_bad = 0;
-        if (he == hipSuccess) he = hipMemcpyAsync(&placed_bad, bad + OV_BAD_PLACE, 4, hipMemcpyDeviceToHost, d->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(&placed_bad, bad + OV_BAD_PLACE, 4, hipMemcpyDeviceToHost, o->stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(o->stream);
         if (he == hipSuccess && placed_bad) {       // (never: the merged order is a permutation of S; nothing is paired from a broken one)
-            e = dec_fail(d, PGRC_E_DEVICE, "overlap: sweep " + std::to_string(i) + ": a place outside the merged order");
+            e = dec_fail(o, PGRC_E_DEVICE, "overlap: sweep " + std::to_string(i) + ": a place outside the merged order");
             break;
         }
         if (par)
-            hipLaunchKernelGGL(k_ov_pair<false>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)merged, (const uint32_t *)mk,
+            hipLaunchKernelGGL(k_ov_pair<false>, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)merged, (const uint32_t *)mk,
                                n, (const uint32_t *)P, npp, nx, ov, keep, taken);
         else
-            hipLaunchKernelGGL(k_ov_pair<true>, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)merged, (const uint32_t *)mk,
+            hipLaunchKernelGGL(k_ov_pair<true>, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint8_t *)sym, stride, i, L, (const uint32_t *)merged, (const uint32_t *)mk,
                                n, (const uint32_t *)P, npp, nx, ov, keep, taken);
         if (he == hipSuccess) he = hipGetLastError();
-        if (he == hipSuccess) he = hipEventRecord(o->ev[2], d->stream);
+        if (he == hipSuccess) he = o->ev.record(2, o->stream);
         if (he != hipSuccess) {
-            e = dec_fail(d, pgrc_hip_code(he), std::string("overlap: sweep: ") + hipGetErrorString(he));
+            e = dec_fail(o, pgrc_hip_code(he), std::string("overlap: sweep: ") + hipGetErrorString(he));
             break;
         }
         if ((e = ov_scan_flags(o, keep, 0, n, offs)) || (e = ov_scan_flags(o, taken, 1, npp, offp))) break;
-        he = hipMemcpyAsync(&h_n[0], offs + n, 4, hipMemcpyDeviceToHost, d->stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(&h_n[1], offp + npp, 4, hipMemcpyDeviceToHost, d->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
+        he = hipMemcpyAsync(&h_n[0], offs + n, 4, hipMemcpyDeviceToHost, o->stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(&h_n[1], offp + npp, 4, hipMemcpyDeviceToHost, o->stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(o->stream);
         if (he != hipSuccess) {
-            e = dec_fail(d, pgrc_hip_code(he), std::string("overlap: sweep: ") + hipGetErrorString(he));
+            e = dec_fail(o, pgrc_hip_code(he), std::string("overlap: sweep: ") + hipGetErrorString(he));
             break;
         }
         if (h_n[0] > n || h_n[1] > npp) {
-            e = dec_fail(d, PGRC_E_DEVICE, "overlap: sweep " + std::to_string(i) + ": more left than there was");
+            e = dec_fail(o, PGRC_E_DEVICE, "overlap: sweep " + std::to_string(i) + ": more left than there was");
             break;
         }
-        hipLaunchKernelGGL(k_ov_compact, dim3(ov_grid(n)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)merged, (const uint8_t *)keep, 0u, (const uint32_t *)offs, (uint64_t)n,
+        hipLaunchKernelGGL(k_ov_compact, dim3(dec_grid(n, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)merged, (const uint8_t *)keep, 0u, (const uint32_t *)offs, (uint64_t)n,
                            (uint64_t)h_n[0], S2);
-        hipLaunchKernelGGL(k_ov_compact, dim3(ov_grid(npp)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)P, (const uint8_t *)taken, 1u, (const uint32_t *)offp, (uint64_t)npp,
+        hipLaunchKernelGGL(k_ov_compact, dim3(dec_grid(npp, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)P, (const uint8_t *)taken, 1u, (const uint32_t *)offp, (uint64_t)npp,
                            (uint64_t)h_n[1], P2);
         std::swap(S, S2);
         std::swap(P, P2);
-        hipLaunchKernelGGL(k_ov_groups, dim3(ov_grid((uint64_t)h_n[0] + 1)), dim3(OV_TPB), 0, d->stream, (const uint8_t *)sym, stride, i, (const uint32_t *)S, (uint64_t)h_n[0], gs);
+        hipLaunchKernelGGL(k_ov_groups, dim3(dec_grid((uint64_t)h_n[0] + 1, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint8_t *)sym, stride, i, (const uint32_t *)S, (uint64_t)h_n[0], gs);
         he = hipGetLastError();
-        if (he == hipSuccess) he = hipEventRecord(o->ev[3], d->stream);
-        if (he == hipSuccess) he = hipEventSynchronize(o->ev[3]);
+        if (he == hipSuccess) he = o->ev.record(3, o->stream);
+        if (he == hipSuccess) he = hipEventSynchronize(o->ev.ev[3]);
         if (he != hipSuccess) {
-            e = dec_fail(d, pgrc_hip_code(he), std::string("overlap: sweep: ") + hipGetErrorString(he));
+            e = dec_fail(o, pgrc_hip_code(he), std::string("overlap: sweep: ") + hipGetErrorString(he));
             break;
         }
         const uint64_t made = np - h_n[1];
@@ -717,7 +710,7 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
         left[i] = reads_left;
         ns = h_n[0];
         np = h_n[1];
-        const float a = dec_elapsed(o->ev[0], o->ev[1]), b = dec_elapsed(o->ev[1], o->ev[2]), c = dec_elapsed(o->ev[2], o->ev[3]);
+        const float a = o->ev.ms(0, 1), b = o->ev.ms(1, 2), c = o->ev.ms(2, 3);
         ms_merge += a;
         ms_pair += b;
         ms_compact += c;
@@ -725,7 +718,7 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
         passes++;
     }
     if (e) {
-        (void)hipStreamSynchronize(d->stream);
+        (void)hipStreamSynchronize(o->stream);
         (void)hipHostFree(blk);
         return e;
     }
@@ -734,17 +727,17 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     const auto t1 = std::chrono::steady_clock::now();
     hipError_t he = hipSuccess;
     if (width == 1) {
-        hipLaunchKernelGGL(k_ov_narrow, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint16_t *)ov, N1, (uint8_t *)o->ovout.p);
+        hipLaunchKernelGGL(k_ov_narrow, dim3(dec_grid(N1, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint16_t *)ov, N1, (uint8_t *)o->ovout.p);
         he = hipGetLastError();
     }
     unsigned long long h_cnt[2] = {};
-    if (he == hipSuccess && par) he = hipMemcpyAsync(h_cnt, o->cnt.p, sizeof(h_cnt), hipMemcpyDeviceToHost, d->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(blk, nx, N1 * 4, hipMemcpyDeviceToHost, d->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(blk + ov_at, width == 1 ? o->ovout.p : (void *)ov, N1 * width, hipMemcpyDeviceToHost, d->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
+    if (he == hipSuccess && par) he = hipMemcpyAsync(h_cnt, o->cnt.p, sizeof(h_cnt), hipMemcpyDeviceToHost, o->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(blk, nx, N1 * 4, hipMemcpyDeviceToHost, o->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(blk + ov_at, width == 1 ? o->ovout.p : (void *)ov, N1 * width, hipMemcpyDeviceToHost, o->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(o->stream);
     if (he != hipSuccess) {
         (void)hipHostFree(blk);
-        return dec_fail(d, pgrc_hip_code(he), std::string("overlap: copy down: ") + hipGetErrorString(he));
+        return dec_fail(o, pgrc_hip_code(he), std::string("overlap: copy down: ") + hipGetErrorString(he));
     }
     out->struct_size = sizeof(pgrc_ovl_result);
     out->sweeps = sweeps;
@@ -779,8 +772,8 @@ static int ov_run(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *ou
     t.ms_merge_device = ms_merge;
     t.ms_pair_device = ms_pair;
     t.ms_compact_device = ms_compact;
-    t.ms_download = ov_ms(t1);
-    t.ms_call = ov_ms(t0);
+    t.ms_download = dec_ms_since(t1);
+    t.ms_call = dec_ms_since(t0);
     t.bytes_up = (rows_on_device ? 0 : R * rb) + (in->sorted_order ? R * 4 : 0);
     t.bytes_down = N1 * 4 + N1 * width;
     return PGRC_OK;
@@ -791,36 +784,29 @@ extern "C" {
 int pgrc_ovl_create(int32_t device, pgrc_ovl_ctx **out) {
     if (!out) return PGRC_E_PARAM;
     *out = nullptr;
-    pgrc_decode_ctx *d = nullptr;
-    const int e = pgrc_decode_create(1, device, &d);        // (the read length is set by every run)
-    if (e) return e;
     pgrc_ovl_ctx *o = new pgrc_ovl_ctx();
-    o->d = d;
-    *out = o;
-    return PGRC_OK;
+    const int e = pgrc_stage_open(o, device, &g_ov_create_err);
+    if (e) delete o;
+    else *out = o;
+    return e;
 }
 
 void pgrc_ovl_destroy(pgrc_ovl_ctx *o) {
     if (!o) return;
-    {
-        PgrcDeviceScope scope(o->d->device);
-        (void)hipStreamSynchronize(o->d->stream);
-        for (DevBuf *b : {&o->rows, &o->sym, &o->nx, &o->ov, &o->ovout, &o->order, &o->seen, &o->eq, &o->s[0], &o->s[1], &o->p[0], &o->p[1], &o->base, &o->lens, &o->rk,
-                           &o->trans, &o->merged, &o->mk, &o->keep, &o->taken, &o->offs, &o->offp, &o->gs, &o->fold, &o->words, &o->rec[0], &o->rec[1], &o->prev, &o->flags, &o->rnk, &o->lead, &o->cnt})
-            dec_free(*b);
-        pgrc_buf_free(o->sort_scratch);
-        for (hipEvent_t ev : o->ev)
-            if (ev) (void)hipEventDestroy(ev);
-    }
-    pgrc_decode_destroy(o->d);
+    PgrcDeviceScope scope(o->device);
+    (void)hipStreamSynchronize(o->stream);
+    dec_free_all(ov_bufs(o));
+    pgrc_buf_free(o->sort_scratch);
+    o->ev.release();
+    pgrc_stage_close(o);
     delete o;
 }
 
-const char *pgrc_ovl_last_error(const pgrc_ovl_ctx *o) { return pgrc_decode_last_error(o ? o->d : nullptr); }
+const char *pgrc_ovl_last_error(const pgrc_ovl_ctx *o) { return o ? o->err.c_str() : g_ov_create_err.c_str(); }
 
 }   // extern "C"
 
-int pgovl_device(const pgrc_ovl_ctx *o) { return o->d->device; }
+int pgovl_device(const pgrc_ovl_ctx *o) { return o->device; }
 uint64_t pgovl_run_serial(const pgrc_ovl_ctx *o) { return o->have_run ? o->run_serial : 0; }
 
 int pgovl_run_rows(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *out, bool rows_on_device) {
@@ -838,10 +824,10 @@ int pgovl_run_rows(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *o
     if (!(in->stop_coef >= 0.0 && in->stop_coef <= 1.0)) return ov_fail(o, "the stop coefficient must be in [0, 1]");
     if (!in->packed_rows) return ov_fail(o, "packed_rows is NULL");
     if (o->rule == PGRC_OVL_RULE_PARALLEL && in->read_len <= OV_BLOCK_PREFIX) return ov_fail(o, "the rule of the parallel generator needs a read length of at least 4");
-    PGRC_ON_DEVICE(o->d);
+    PGRC_ON_DEVICE(o);
     const int e = ov_run(o, in, out, rows_on_device);
     if (e) {
-        (void)hipStreamSynchronize(o->d->stream);
+        (void)hipStreamSynchronize(o->stream);
         *out = pgrc_ovl_result{};
     }
     return e;
@@ -849,15 +835,14 @@ int pgovl_run_rows(pgrc_ovl_ctx *o, const pgrc_ovl_input *in, pgrc_ovl_result *o
 
 // getBothSidesOverlappedReads of the last run into o->flags, queued on the stream
 static int ov_both_sides_queue(pgrc_ovl_ctx *o) {
-    pgrc_decode_ctx *d = o->d;
     const uint64_t R = o->R, N1 = R + 1;
     int e;
-    if ((e = pgrc_buf_unpooled(d, o->prev, N1 * 2)) || (e = pgrc_buf_unpooled(d, o->flags, R))) return e;
-    HIP_TRY(d, hipMemsetAsync(o->prev.p, 0, N1 * 2, d->stream));
-    hipLaunchKernelGGL(k_ov_prev, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, R, (uint16_t *)o->prev.p);
-    hipLaunchKernelGGL(k_ov_both, dim3(ov_grid(N1)), dim3(OV_TPB), 0, d->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, (const uint16_t *)o->prev.p, R, o->L,
+    if ((e = pgrc_bufs_unpooled(o, {{&o->prev, N1 * 2}, {&o->flags, R}}))) return e;
+    HIP_TRY(o, hipMemsetAsync(o->prev.p, 0, N1 * 2, o->stream));
+    hipLaunchKernelGGL(k_ov_prev, dim3(dec_grid(N1, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, R, (uint16_t *)o->prev.p);
+    hipLaunchKernelGGL(k_ov_both, dim3(dec_grid(N1, OV_TPB)), dim3(OV_TPB), 0, o->stream, (const uint32_t *)o->nx.p, (const uint16_t *)o->ov.p, (const uint16_t *)o->prev.p, R, o->L,
                        (uint8_t *)o->flags.p);
-    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(o, hipGetLastError());
     return PGRC_OK;
 }
 
@@ -866,12 +851,11 @@ int pgovl_assemble(pgrc_ovl_ctx *o, pgrc_asm_ctx *a, const uint32_t *index_mappi
     if (!o) return PGRC_E_PARAM;
     if (!a || !res) return ov_fail(o, "asm_ctx or asm_result is NULL");
     *res = pgrc_asm_result{};
-    pgrc_decode_ctx *d = o->d;
-    if (!o->have_run) return dec_fail(d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
-    if (pgasm_device(a) != d->device) return ov_fail(o, "the two contexts are on different devices");
+    if (!o->have_run) return dec_fail(o, PGRC_E_STATE, "overlap: no run has succeeded on this context");
+    if (pgasm_device(a) != o->device) return ov_fail(o, "the two contexts are on different devices");
     {
-        PGRC_ON_DEVICE(d);
-        HIP_TRY(d, hipStreamSynchronize(d->stream));        // (a run leaves its stream idle; both_sides may have used it since)
+        PGRC_ON_DEVICE(o);
+        HIP_TRY(o, hipStreamSynchronize(o->stream));        // (a run leaves its stream idle; both_sides may have used it since)
     }
     pgrc_asm_input in{};
     in.struct_size = sizeof(in);
@@ -884,18 +868,17 @@ int pgovl_assemble(pgrc_ovl_ctx *o, pgrc_asm_ctx *a, const uint32_t *index_mappi
     in.overlap = o->ov.p;
     in.index_mapping = index_mapping;
     const int e = list_stays ? pgasm_run_device_resident(a, &in, res) : pgasm_run_device(a, &in, res);
-    if (e) return dec_fail(d, e, std::string("overlap: ") + (pgrc_asm_last_error(a) ? pgrc_asm_last_error(a) : ""));
+    if (e) return dec_fail(o, e, std::string("overlap: ") + (pgrc_asm_last_error(a) ? pgrc_asm_last_error(a) : ""));
     return PGRC_OK;
 }
 
 int pgovl_both_sides_device(pgrc_ovl_ctx *o, const uint8_t **d_flags, uint64_t *R) {
     if (!o || !d_flags || !R) return PGRC_E_PARAM;
-    pgrc_decode_ctx *d = o->d;
-    if (!o->have_run) return dec_fail(d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
-    PGRC_ON_DEVICE(d);
+    if (!o->have_run) return dec_fail(o, PGRC_E_STATE, "overlap: no run has succeeded on this context");
+    PGRC_ON_DEVICE(o);
     int e;
     if ((e = ov_both_sides_queue(o))) return e;
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(o, hipStreamSynchronize(o->stream));
     *d_flags = (const uint8_t *)o->flags.p;
     *R = o->R;
     return PGRC_OK;
@@ -914,24 +897,10 @@ void pgrc_ovl_free_result(pgrc_ovl_result *r) {
 int pgrc_ovl_both_sides(pgrc_ovl_ctx *o, uint8_t *flags) {
     if (!o) return PGRC_E_PARAM;
     if (!flags) return ov_fail(o, "flags is NULL");
-    pgrc_decode_ctx *d = o->d;
-    if (!o->have_run) return dec_fail(d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
-    PGRC_ON_DEVICE(d);
-    const uint64_t R = o->R;
-    int e;
-    if ((e = ov_both_sides_queue(o))) return e;
-    if (pgrc_host_pinned(flags)) {
-        HIP_TRY(d, hipMemcpyAsync(flags, o->flags.p, R, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
-        return PGRC_OK;
-    }
-    for (uint64_t at = 0; at < R; at += DEC_STAGE_BYTES) {     // pageable memory: through a staging buffer
-        const uint64_t c = std::min<uint64_t>(DEC_STAGE_BYTES, R - at);
-        HIP_TRY(d, hipMemcpyAsync(d->stage[0], (const uint8_t *)o->flags.p + at, c, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
-        memcpy(flags + at, d->stage[0], c);
-    }
-    return PGRC_OK;
+    if (!o->have_run) return dec_fail(o, PGRC_E_STATE, "overlap: no run has succeeded on this context");
+    PGRC_ON_DEVICE(o);
+    const int e = ov_both_sides_queue(o);
+    return e ? e : dec_download_host(o, flags, o->flags.p, o->R);
 }
 
 int pgrc_ovl_assemble(pgrc_ovl_ctx *o, pgrc_asm_ctx *a, const uint32_t *index_mapping, pgrc_asm_result *res) {
@@ -947,16 +916,16 @@ int pgrc_ovlrule_set(pgrc_ovl_ctx *o, uint32_t rule) {
 
 int pgrc_ovlrule_get_info(pgrc_ovl_ctx *o, pgrc_ovl_rule_info *out) {
     if (!o) return PGRC_E_PARAM;
-    if (!out || out->struct_size != sizeof(pgrc_ovl_rule_info)) return dec_fail(o->d, PGRC_E_PARAM, "overlap: rule info is NULL or struct_size is not sizeof(pgrc_ovl_rule_info)");
-    if (!o->have_run) return dec_fail(o->d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
+    if (!out || out->struct_size != sizeof(pgrc_ovl_rule_info)) return dec_fail(o, PGRC_E_PARAM, "overlap: rule info is NULL or struct_size is not sizeof(pgrc_ovl_rule_info)");
+    if (!o->have_run) return dec_fail(o, PGRC_E_STATE, "overlap: no run has succeeded on this context");
     *out = o->info;
     return PGRC_OK;
 }
 
 int pgrc_ovl_get_timing(pgrc_ovl_ctx *o, pgrc_ovl_timing *out) {
     if (!o) return PGRC_E_PARAM;
-    if (!out || out->struct_size != sizeof(pgrc_ovl_timing)) return dec_fail(o->d, PGRC_E_PARAM, "timing is NULL or struct_size is not sizeof(pgrc_ovl_timing)");
-    if (!o->have_run) return dec_fail(o->d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
+    if (!out || out->struct_size != sizeof(pgrc_ovl_timing)) return dec_fail(o, PGRC_E_PARAM, "timing is NULL or struct_size is not sizeof(pgrc_ovl_timing)");
+    if (!o->have_run) return dec_fail(o, PGRC_E_STATE, "overlap: no run has succeeded on this context");
     *out = o->tm;
     return PGRC_OK;
 }
@@ -964,7 +933,7 @@ int pgrc_ovl_get_timing(pgrc_ovl_ctx *o, pgrc_ovl_timing *out) {
 int pgrc_ovl_get_sweep_ms(pgrc_ovl_ctx *o, float *ms, uint32_t n) {
     if (!o) return PGRC_E_PARAM;
     if (!ms && n) return ov_fail(o, "ms is NULL");
-    if (!o->have_run) return dec_fail(o->d, PGRC_E_STATE, "overlap: no run has succeeded on this context");
+    if (!o->have_run) return dec_fail(o, PGRC_E_STATE, "overlap: no run has succeeded on this context");
     for (uint32_t k = 0; k < n && k < o->sweep_ms.size(); k++) ms[k] = o->sweep_ms[k];
     return PGRC_OK;
 }

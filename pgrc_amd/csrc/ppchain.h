@@ -15,9 +15,7 @@
 
 #define PP_TPB 256
 
-static size_t pp_a16(size_t x) { return (x + 15) & ~(size_t)15; }
-static uint32_t pp_grid(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + PP_TPB - 1) / PP_TPB); }
-static float pp_ms(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+static uint32_t pp_grid(uint64_t n) { return std::max(1u, dec_grid(n, PP_TPB)); }      // (one block for nothing, too)
 
 // states of the chain: what the far pair before was
 #define PP_S_A 0u           // a delta pair: refPrev = its rel

@@ -27,11 +27,13 @@ enum { RS_BAD_RANGE, RS_BAD_ASCEND, RS_BAD_BOTH, RS_BAD_WORDS };
 
 static thread_local std::string g_rs_create_err;
 
-static inline uint32_t rs_grid(uint64_t n) { return (uint32_t)((n + RS_TPB - 1) / RS_TPB); }
-static inline float rs_ms(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+static int rs_fail(pgrc_rsets *s, int code, const std::string &msg) { return dec_fail(s, code, "read sets: " + msg); }
+
+static DevBufList rs_bufs(pgrc_rsets *s) {
+    DevBufList all = {&s->cls, &s->cnt[0], &s->cnt[1], &s->cnt[2], &s->flags, &s->desc[0], &s->desc[1], &s->fold, &s->words, &s->stage_idx};
+    for (RsSet &t : s->set) all.insert(all.end(), {&t.rows, &t.map});
+    return all;
 }
-static int rs_fail(pgrc_rsets *s, int code, const std::string &msg) { return dec_fail(s->d, code, "read sets: " + msg); }
 
 // ------------------------------------------------------------------------------------------------ kernels: classes and counts
 static __global__ void __launch_bounds__(RS_TPB) k_rs_offset(const uint32_t *__restrict__ in, uint64_t n, uint32_t base, uint32_t *__restrict__ out) {
@@ -187,56 +189,36 @@ static __global__ void __launch_bounds__(RS_TPB) k_rs_rows(RsSrc src, const uint
 // ------------------------------------------------------------------------------------------------ host side: helpers
 static int rs_move_rows(pgrc_rsets *s, const uint8_t *src0, uint64_t n0, const uint8_t *src1, uint64_t n1, const uint32_t *desc, uint64_t nout, uint32_t rb, uint8_t *out) {
     if (!nout || !rb) return PGRC_OK;
-    pgrc_decode_ctx *d = s->d;
     RsSrc src;
     src.p[0] = src0; src.rows[0] = n0;
     src.p[1] = src1; src.rows[1] = n1;
     const uint32_t tile_rows = std::max(16u, (RS_TILE_BYTES / rb) & ~15u);
     const uint32_t magic = rb == 1 ? 0u : (uint32_t)((1ull << 32) / rb) + 1u;
     const uint64_t tiles = (nout + tile_rows - 1) / tile_rows;
-    hipLaunchKernelGGL(k_rs_rows, dim3((uint32_t)tiles), dim3(RS_TPB), 0, d->stream, src, desc, nout, rb, magic, tile_rows, out);
-    HIP_TRY(d, hipGetLastError());
+    hipLaunchKernelGGL(k_rs_rows, dim3((uint32_t)tiles), dim3(RS_TPB), 0, s->stream, src, desc, nout, rb, magic, tile_rows, out);
+    HIP_TRY(s, hipGetLastError());
     s->tm.rows_moved += nout;
     s->tm.bytes_moved += nout * rb;
     return PGRC_OK;
 }
 
-// device -> host memory that may be pageable
-static int rs_download(pgrc_decode_ctx *d, void *h_dst, const void *d_src, uint64_t bytes) {
-    if (!bytes) return PGRC_OK;
-    if (pgrc_host_pinned(h_dst)) {
-        HIP_TRY(d, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
-        return PGRC_OK;
-    }
-    for (uint64_t at = 0; at < bytes; at += DEC_STAGE_BYTES) {
-        const uint64_t c = std::min<uint64_t>(DEC_STAGE_BYTES, bytes - at);
-        HIP_TRY(d, hipEventSynchronize(d->ev_copied[0]));       // (an upload may still read the staging buffer)
-        HIP_TRY(d, hipMemcpyAsync(d->stage[0], (const uint8_t *)d_src + at, c, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
-        memcpy((uint8_t *)h_dst + at, d->stage[0], c);
-    }
-    return PGRC_OK;
-}
-
 // what a set holds into its new, larger buffer; the new buffer is given back if the copy fails
-static int rs_copy_kept(pgrc_decode_ctx *d, DevBuf &nb, const void *old, uint64_t bytes) {
-    hipError_t he = bytes ? hipMemcpyAsync(nb.p, old, bytes, hipMemcpyDeviceToDevice, d->stream) : hipSuccess;
-    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
+static int rs_copy_kept(PgrcStage *s, DevBuf &nb, const void *old, uint64_t bytes) {
+    hipError_t he = bytes ? hipMemcpyAsync(nb.p, old, bytes, hipMemcpyDeviceToDevice, s->stream) : hipSuccess;
+    if (he == hipSuccess) he = hipStreamSynchronize(s->stream);
     if (he == hipSuccess) return PGRC_OK;
     dec_free(nb);
-    return dec_fail(d, pgrc_hip_code(he), std::string("read sets: growing a set: ") + hipGetErrorString(he));
+    return dec_fail(s, pgrc_hip_code(he), std::string("read sets: growing a set: ") + hipGetErrorString(he));
 }
 
 // room for `rows` rows / `entries` mapping entries, what the set holds kept
 static int rs_reserve(pgrc_rsets *s, RsSet &t, uint64_t rows, uint64_t entries) {
-    pgrc_decode_ctx *d = s->d;
     int e;
     if (rows > t.cap_rows) {
         const uint64_t cap = std::max(rows, t.cap_rows * 2);
         DevBuf nb;
-        if ((e = pgrc_buf_unpooled(d, nb, cap * t.rb))) return e;
-        if ((e = rs_copy_kept(d, nb, t.rows.p, t.n * t.rb))) return e;
+        if ((e = pgrc_buf_unpooled(s, nb, cap * t.rb))) return e;
+        if ((e = rs_copy_kept(s, nb, t.rows.p, t.n * t.rb))) return e;
         dec_free(t.rows);
         t.rows = nb;
         t.cap_rows = cap;
@@ -244,8 +226,8 @@ static int rs_reserve(pgrc_rsets *s, RsSet &t, uint64_t rows, uint64_t entries) 
     if (entries > t.cap_map) {
         const uint64_t cap = std::max(entries, t.cap_map * 2);
         DevBuf nb;
-        if ((e = pgrc_buf_unpooled(d, nb, cap * 4))) return e;
-        if ((e = rs_copy_kept(d, nb, t.map.p, t.n * 4))) return e;
+        if ((e = pgrc_buf_unpooled(s, nb, cap * 4))) return e;
+        if ((e = rs_copy_kept(s, nb, t.map.p, t.n * 4))) return e;
         dec_free(t.map);
         t.map = nb;
         t.cap_map = cap;
@@ -262,18 +244,17 @@ static int rs_bad_words(pgrc_rsets *s, const uint32_t *bad, const char *what) {
 
 // the class bytes of `A` indexes from two lists (either may be empty) and their checks, queued; `bad` cleared first
 static int rs_classes_of(pgrc_rsets *s, uint64_t A, const uint32_t *lq, uint64_t nl, const uint32_t *nn_map, uint64_t nn) {
-    pgrc_decode_ctx *d = s->d;
     int e;
-    if ((e = pgrc_buf_unpooled(d, s->cls, A + 16)) || (e = pgrc_buf_unpooled(d, s->words, 64))) return e;
+    if ((e = pgrc_bufs_unpooled(s, {{&s->cls, A + 16}, {&s->words, 64}}))) return e;
     uint8_t *cls = (uint8_t *)s->cls.p;
     uint32_t *bad = (uint32_t *)s->words.p;
-    if (A) HIP_TRY(d, hipMemsetAsync(cls, 0, A, d->stream));
-    HIP_TRY(d, hipMemsetAsync(bad, 0, 64, d->stream));
-    if (nl) hipLaunchKernelGGL(k_rs_scatter, dim3(rs_grid(nl)), dim3(RS_TPB), 0, d->stream, lq, nl, A, (uint8_t)1, cls);
-    if (nn) hipLaunchKernelGGL(k_rs_scatter, dim3(rs_grid(nn)), dim3(RS_TPB), 0, d->stream, nn_map, nn, A, (uint8_t)2, cls);
-    if (nl) hipLaunchKernelGGL(k_rs_check, dim3(rs_grid(nl)), dim3(RS_TPB), 0, d->stream, lq, nl, A, (uint8_t)1, (const uint8_t *)cls, bad);
-    if (nn) hipLaunchKernelGGL(k_rs_check, dim3(rs_grid(nn)), dim3(RS_TPB), 0, d->stream, nn_map, nn, A, (uint8_t)2, (const uint8_t *)cls, bad);
-    HIP_TRY(d, hipGetLastError());
+    if (A) HIP_TRY(s, hipMemsetAsync(cls, 0, A, s->stream));
+    HIP_TRY(s, hipMemsetAsync(bad, 0, 64, s->stream));
+    if (nl) hipLaunchKernelGGL(k_rs_scatter, dim3(dec_grid(nl, RS_TPB)), dim3(RS_TPB), 0, s->stream, lq, nl, A, (uint8_t)1, cls);
+    if (nn) hipLaunchKernelGGL(k_rs_scatter, dim3(dec_grid(nn, RS_TPB)), dim3(RS_TPB), 0, s->stream, nn_map, nn, A, (uint8_t)2, cls);
+    if (nl) hipLaunchKernelGGL(k_rs_check, dim3(dec_grid(nl, RS_TPB)), dim3(RS_TPB), 0, s->stream, lq, nl, A, (uint8_t)1, (const uint8_t *)cls, bad);
+    if (nn) hipLaunchKernelGGL(k_rs_check, dim3(dec_grid(nn, RS_TPB)), dim3(RS_TPB), 0, s->stream, nn_map, nn, A, (uint8_t)2, (const uint8_t *)cls, bad);
+    HIP_TRY(s, hipGetLastError());
     return PGRC_OK;
 }
 static int rs_classes(pgrc_rsets *s) {
@@ -283,16 +264,9 @@ static int rs_classes(pgrc_rsets *s) {
 // cnt[k][0 .. n] = the exclusive counts of `in`, element n the total
 template <typename In>
 static int rs_count(pgrc_rsets *s, In in, uint64_t n, int k) {
-    pgrc_decode_ctx *d = s->d;
     int e;
-    if ((e = pgrc_buf_unpooled(d, s->cnt[k], (n + 1) * 4)) || (e = pgrc_buf_unpooled(d, s->fold, sco_scratch_elems(n + 1) * 4 + 16))) return e;
-    HIP_TRY(d, (sco_device_scan<false, true>(d->stream, in, n, ScoPlus{}, 0u, 0u, ScoStore<uint32_t>{(uint32_t *)s->cnt[k].p}, (uint32_t *)s->fold.p)));
-    return PGRC_OK;
-}
-
-static int rs_events(pgrc_rsets *s) {
-    for (hipEvent_t &ev : s->ev)
-        if (!ev) HIP_TRY(s->d, hipEventCreate(&ev));
+    if ((e = pgrc_bufs_unpooled(s, {{&s->cnt[k], (n + 1) * 4}, {&s->fold, sco_scratch_elems(n + 1) * 4 + 16}}))) return e;
+    HIP_TRY(s, (sco_device_scan<false, true>(s->stream, in, n, ScoPlus{}, 0u, 0u, ScoStore<uint32_t>{(uint32_t *)s->cnt[k].p}, (uint32_t *)s->fold.p)));
     return PGRC_OK;
 }
 
@@ -300,7 +274,7 @@ static int rs_events(pgrc_rsets *s) {
 static int rs_flags(pgrc_rsets *s, const uint8_t *flags, uint64_t n, int32_t on_device, const uint8_t **d_flags) {
     if (on_device || !n) { *d_flags = flags; return PGRC_OK; }
     int e;
-    if ((e = pgrc_buf_unpooled(s->d, s->flags, n + 16)) || (e = dec_upload_host(s->d, s->flags.p, flags, n))) return e;
+    if ((e = pgrc_buf_unpooled(s, s->flags, n + 16)) || (e = dec_upload_host(s, s->flags.p, flags, n))) return e;
     *d_flags = (const uint8_t *)s->flags.p;
     return PGRC_OK;
 }
@@ -324,53 +298,51 @@ static int rs_need(pgrc_rsets *s, const char *what, std::initializer_list<int> s
 
 // ------------------------------------------------------------------------------------------------ host side: the edits
 static int rs_move(pgrc_rsets *s, const uint8_t *d_is_hq) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     RsSet &hq = s->set[0], &lq = s->set[1];
     const uint64_t A = s->A, nh = hq.n, nl = lq.n;
     const uint32_t rb = hq.rb;
     int e;
-    if ((e = rs_events(s))) return e;
+    if ((e = s->ev.ensure(s))) return e;
     s->tm = pgrc_rsets_timing{};
     s->have_timing = false;
-    HIP_TRY(d, hipEventRecord(s->ev[0], d->stream));
+    HIP_TRY(s, s->ev.record(0, s->stream));
     if ((e = rs_classes(s))) return e;
     uint8_t *cls = (uint8_t *)s->cls.p;
     if ((e = rs_count(s, RsIsClass{cls, 0}, A, 0)) || (e = rs_count(s, RsIsClass{cls, 1}, A, 1))) return e;
     const uint32_t *c_hq = (const uint32_t *)s->cnt[0].p, *c_lq = (const uint32_t *)s->cnt[1].p;
-    if (A) hipLaunchKernelGGL(k_rs_mark_moved, dim3(rs_grid(A)), dim3(RS_TPB), 0, d->stream, cls, A, c_hq, d_is_hq, nh);
-    HIP_TRY(d, hipGetLastError());
+    if (A) hipLaunchKernelGGL(k_rs_mark_moved, dim3(dec_grid(A, RS_TPB)), dim3(RS_TPB), 0, s->stream, cls, A, c_hq, d_is_hq, nh);
+    HIP_TRY(s, hipGetLastError());
     if ((e = rs_count(s, RsIsClass{cls, 3}, A, 2))) return e;
     const uint32_t *c_mv = (const uint32_t *)s->cnt[2].p;
-    HIP_TRY(d, hipEventRecord(s->ev[1], d->stream));
+    HIP_TRY(s, s->ev.record(1, s->stream));
     uint32_t bad[RS_BAD_WORDS] = {}, tot[3] = {};
-    HIP_TRY(d, hipMemcpyAsync(bad, s->words.p, sizeof bad, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipMemcpyAsync(&tot[0], c_hq + A, 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipMemcpyAsync(&tot[1], c_lq + A, 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipMemcpyAsync(&tot[2], c_mv + A, 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(s, hipMemcpyAsync(bad, s->words.p, sizeof bad, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(&tot[0], c_hq + A, 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(&tot[1], c_lq + A, 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(&tot[2], c_mv + A, 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
     if ((e = rs_bad_words(s, bad, "move"))) return e;
     if (tot[0] != nh || tot[1] != nl || tot[2] > nh) return rs_fail(s, PGRC_E_PARAM, "move: the HQ count is not the reads' count minus the LQ and N counts");
     const uint64_t moved = tot[2], new_nl = nl + moved, new_nh = nh - moved;
     DevBuf n_lq_rows, n_lq_map, n_hq_rows;
     auto drop = [&]() { dec_free(n_lq_rows); dec_free(n_lq_map); dec_free(n_hq_rows); };
-    if ((e = pgrc_buf_unpooled(d, n_lq_rows, new_nl * rb)) || (e = pgrc_buf_unpooled(d, n_lq_map, (new_nl + 1) * 4)) || (e = pgrc_buf_unpooled(d, n_hq_rows, new_nh * rb)) ||
-        (e = pgrc_buf_unpooled(d, s->desc[0], new_nl * 4)) || (e = pgrc_buf_unpooled(d, s->desc[1], new_nh * 4))) {
+    if ((e = pgrc_bufs_unpooled(s, {{&n_lq_rows, new_nl * rb}, {&n_lq_map, (new_nl + 1) * 4}, {&n_hq_rows, new_nh * rb}, {&s->desc[0], new_nl * 4}, {&s->desc[1], new_nh * 4}}))) {
         drop();
         return e;
     }
     hipError_t he = hipSuccess;
-    hipLaunchKernelGGL(k_rs_move_desc, dim3(rs_grid(A + 1)), dim3(RS_TPB), 0, d->stream, (const uint8_t *)cls, A, c_hq, c_lq, c_mv, (uint32_t *)s->desc[0].p, (uint32_t *)n_lq_map.p,
+    hipLaunchKernelGGL(k_rs_move_desc, dim3(dec_grid(A + 1, RS_TPB)), dim3(RS_TPB), 0, s->stream, (const uint8_t *)cls, A, c_hq, c_lq, c_mv, (uint32_t *)s->desc[0].p, (uint32_t *)n_lq_map.p,
                        (uint32_t *)s->desc[1].p);
     he = hipGetLastError();
-    if (he == hipSuccess) he = hipEventRecord(s->ev[2], d->stream);
+    if (he == hipSuccess) he = s->ev.record(2, s->stream);
     if (he == hipSuccess) {
         e = rs_move_rows(s, (const uint8_t *)lq.rows.p, nl, (const uint8_t *)hq.rows.p, nh, (const uint32_t *)s->desc[0].p, new_nl, rb, (uint8_t *)n_lq_rows.p);
         if (!e) e = rs_move_rows(s, (const uint8_t *)hq.rows.p, nh, (const uint8_t *)hq.rows.p, nh, (const uint32_t *)s->desc[1].p, new_nh, rb, (uint8_t *)n_hq_rows.p);
-        if (e) { (void)hipStreamSynchronize(d->stream); drop(); return e; }
-        he = hipEventRecord(s->ev[3], d->stream);
+        if (e) { (void)hipStreamSynchronize(s->stream); drop(); return e; }
+        he = s->ev.record(3, s->stream);
     }
-    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(s->stream);
     if (he != hipSuccess) {
         drop();
         return rs_fail(s, pgrc_hip_code(he), std::string("move: ") + hipGetErrorString(he));
@@ -382,57 +354,55 @@ static int rs_move(pgrc_rsets *s, const uint8_t *d_is_hq) {
     s->hq_gen++;
     s->tm.struct_size = sizeof(pgrc_rsets_timing);
     s->tm.edit = 1;
-    s->tm.ms_checks_device = dec_elapsed(s->ev[0], s->ev[1]);
-    s->tm.ms_desc_device = dec_elapsed(s->ev[1], s->ev[2]);
-    s->tm.ms_rows_device = dec_elapsed(s->ev[2], s->ev[3]);
-    s->tm.ms_call = rs_ms(t0);
+    s->tm.ms_checks_device = s->ev.ms(0, 1);
+    s->tm.ms_desc_device = s->ev.ms(1, 2);
+    s->tm.ms_rows_device = s->ev.ms(2, 3);
+    s->tm.ms_call = dec_ms_since(t0);
     s->have_timing = true;
     return PGRC_OK;
 }
 
 static int rs_remove(pgrc_rsets *s, const uint8_t *d_flags) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t A = s->A;
     const bool have_n = s->set[2].symbols != 0;
     const int last = have_n ? 2 : 1;
     int e;
-    if ((e = rs_events(s))) return e;
+    if ((e = s->ev.ensure(s))) return e;
     s->tm = pgrc_rsets_timing{};
     s->have_timing = false;
-    HIP_TRY(d, hipEventRecord(s->ev[0], d->stream));
+    HIP_TRY(s, s->ev.record(0, s->stream));
     const uint8_t *f[3] = {nullptr, d_flags, d_flags + s->set[1].n};        // nBegIdx: the LQ count before its removal
     for (int k = 1; k <= last; k++)
         if ((e = rs_count(s, RsIsZero{f[k]}, s->set[k].n, k - 1))) return e;
-    HIP_TRY(d, hipEventRecord(s->ev[1], d->stream));
+    HIP_TRY(s, s->ev.record(1, s->stream));
     uint32_t kept[3] = {};
-    for (int k = 1; k <= last; k++) HIP_TRY(d, hipMemcpyAsync(&kept[k], (const uint32_t *)s->cnt[k - 1].p + s->set[k].n, 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    for (int k = 1; k <= last; k++) HIP_TRY(s, hipMemcpyAsync(&kept[k], (const uint32_t *)s->cnt[k - 1].p + s->set[k].n, 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
     DevBuf n_rows[3], n_map[3];
     auto drop = [&]() { for (int k = 1; k <= 2; k++) { dec_free(n_rows[k]); dec_free(n_map[k]); } };
     for (int k = 1; k <= last; k++) {
         RsSet &t = s->set[k];
         if (kept[k] > t.n) { drop(); return rs_fail(s, PGRC_E_DEVICE, "remove: more rows kept than the set holds"); }
-        if ((e = pgrc_buf_unpooled(d, n_rows[k], (uint64_t)kept[k] * t.rb)) || (e = pgrc_buf_unpooled(d, n_map[k], ((uint64_t)kept[k] + 1) * 4)) ||
-            (e = pgrc_buf_unpooled(d, s->desc[k - 1], (uint64_t)kept[k] * 4))) {
+        if ((e = pgrc_bufs_unpooled(s, {{&n_rows[k], (uint64_t)kept[k] * t.rb}, {&n_map[k], ((uint64_t)kept[k] + 1) * 4}, {&s->desc[k - 1], (uint64_t)kept[k] * 4}}))) {
             drop();
             return e;
         }
-        hipLaunchKernelGGL(k_rs_keep_desc, dim3(rs_grid(t.n + 1)), dim3(RS_TPB), 0, d->stream, f[k], t.n, (const uint32_t *)s->cnt[k - 1].p, (const uint32_t *)t.map.p, (uint32_t)A,
+        hipLaunchKernelGGL(k_rs_keep_desc, dim3(dec_grid(t.n + 1, RS_TPB)), dim3(RS_TPB), 0, s->stream, f[k], t.n, (const uint32_t *)s->cnt[k - 1].p, (const uint32_t *)t.map.p, (uint32_t)A,
                            (uint32_t *)s->desc[k - 1].p, (uint32_t *)n_map[k].p);
     }
     hipError_t he = hipGetLastError();
-    if (he == hipSuccess) he = hipEventRecord(s->ev[2], d->stream);
+    if (he == hipSuccess) he = s->ev.record(2, s->stream);
     for (int k = 1; k <= last && he == hipSuccess; k++) {
         RsSet &t = s->set[k];
         if ((e = rs_move_rows(s, (const uint8_t *)t.rows.p, t.n, (const uint8_t *)t.rows.p, t.n, (const uint32_t *)s->desc[k - 1].p, kept[k], t.rb, (uint8_t *)n_rows[k].p))) {
-            (void)hipStreamSynchronize(d->stream);
+            (void)hipStreamSynchronize(s->stream);
             drop();
             return e;
         }
     }
-    if (he == hipSuccess) he = hipEventRecord(s->ev[3], d->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
+    if (he == hipSuccess) he = s->ev.record(3, s->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(s->stream);
     if (he != hipSuccess) {
         drop();
         return rs_fail(s, pgrc_hip_code(he), std::string("remove: ") + hipGetErrorString(he));
@@ -445,46 +415,45 @@ static int rs_remove(pgrc_rsets *s, const uint8_t *d_flags) {
     }
     s->tm.struct_size = sizeof(pgrc_rsets_timing);
     s->tm.edit = 2;
-    s->tm.ms_checks_device = dec_elapsed(s->ev[0], s->ev[1]);
-    s->tm.ms_desc_device = dec_elapsed(s->ev[1], s->ev[2]);
-    s->tm.ms_rows_device = dec_elapsed(s->ev[2], s->ev[3]);
-    s->tm.ms_call = rs_ms(t0);
+    s->tm.ms_checks_device = s->ev.ms(0, 1);
+    s->tm.ms_desc_device = s->ev.ms(1, 2);
+    s->tm.ms_rows_device = s->ev.ms(2, 3);
+    s->tm.ms_call = dec_ms_since(t0);
     s->have_timing = true;
     return PGRC_OK;
 }
 
 // generateHqReadsIndexesMapping into desc[0] (nh + 1 entries, queued); out: the host copy, or NULL to leave it on the device
 static int rs_hq_mapping(pgrc_rsets *s, uint32_t *out) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t A = s->A, nh = A - s->set[1].n - s->set[2].n;
     int e;
-    if ((e = rs_events(s))) return e;
+    if ((e = s->ev.ensure(s))) return e;
     s->tm = pgrc_rsets_timing{};
     s->have_timing = false;
-    HIP_TRY(d, hipEventRecord(s->ev[0], d->stream));
+    HIP_TRY(s, s->ev.record(0, s->stream));
     if ((e = rs_classes(s)) || (e = rs_count(s, RsIsClass{(const uint8_t *)s->cls.p, 0}, A, 0))) return e;
-    HIP_TRY(d, hipEventRecord(s->ev[1], d->stream));
-    if ((e = pgrc_buf_unpooled(d, s->desc[0], (nh + 1) * 4))) return e;
+    HIP_TRY(s, s->ev.record(1, s->stream));
+    if ((e = pgrc_buf_unpooled(s, s->desc[0], (nh + 1) * 4))) return e;
     uint32_t bad[RS_BAD_WORDS] = {}, tot = 0;
-    HIP_TRY(d, hipMemcpyAsync(bad, s->words.p, sizeof bad, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipMemcpyAsync(&tot, (const uint32_t *)s->cnt[0].p + A, 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(s, hipMemcpyAsync(bad, s->words.p, sizeof bad, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(&tot, (const uint32_t *)s->cnt[0].p + A, 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
     if ((e = rs_bad_words(s, bad, "HQ mapping"))) return e;
     if (tot != nh) return rs_fail(s, PGRC_E_PARAM, "HQ mapping: the HQ count is not the reads' count minus the LQ and N counts");
-    hipLaunchKernelGGL(k_rs_hq_map, dim3(rs_grid(A + 1)), dim3(RS_TPB), 0, d->stream, (const uint8_t *)s->cls.p, A, (const uint32_t *)s->cnt[0].p, (uint32_t *)s->desc[0].p);
-    HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(s->ev[2], d->stream));
+    hipLaunchKernelGGL(k_rs_hq_map, dim3(dec_grid(A + 1, RS_TPB)), dim3(RS_TPB), 0, s->stream, (const uint8_t *)s->cls.p, A, (const uint32_t *)s->cnt[0].p, (uint32_t *)s->desc[0].p);
+    HIP_TRY(s, hipGetLastError());
+    HIP_TRY(s, s->ev.record(2, s->stream));
     if (out) {
-        if ((e = rs_download(d, out, s->desc[0].p, (nh + 1) * 4))) return e;
+        if ((e = dec_download_host(s, out, s->desc[0].p, (nh + 1) * 4))) return e;
     } else {
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
     }
     s->tm.struct_size = sizeof(pgrc_rsets_timing);
     s->tm.edit = 3;
-    s->tm.ms_checks_device = dec_elapsed(s->ev[0], s->ev[1]);
-    s->tm.ms_desc_device = dec_elapsed(s->ev[1], s->ev[2]);
-    s->tm.ms_call = rs_ms(t0);
+    s->tm.ms_checks_device = s->ev.ms(0, 1);
+    s->tm.ms_desc_device = s->ev.ms(1, 2);
+    s->tm.ms_call = dec_ms_since(t0);
     s->have_timing = true;
     return PGRC_OK;
 }
@@ -492,22 +461,21 @@ static int rs_hq_mapping(pgrc_rsets *s, uint32_t *out) {
 // one batch: rows and batch-local indexes in host memory (on_device = false) or in memory of this device.  The batch's indexes
 // are checked before anything of the object changes: what is written lies behind the sets' counts until the call has succeeded.
 static int rs_append(pgrc_rsets *s, const uint64_t cnt[3], const uint8_t *const rows[3], const uint32_t *const idx[2], uint64_t n_records, bool on_device) {
-    pgrc_decode_ctx *d = s->d;
     int e;
     if (!n_records) return PGRC_OK;
     // the indexes on the device, batch-local, behind one another in stage_idx
     const uint64_t ni = cnt[1] + cnt[2];
-    if ((e = pgrc_buf_unpooled(d, s->stage_idx, (ni + 1) * 4))) return e;
+    if ((e = pgrc_buf_unpooled(s, s->stage_idx, (ni + 1) * 4))) return e;
     uint32_t *loc[2] = {(uint32_t *)s->stage_idx.p, (uint32_t *)s->stage_idx.p + cnt[1]};
     for (int k = 0; k < 2; k++) {
         if (!cnt[k + 1]) continue;
-        if (on_device) HIP_TRY(d, hipMemcpyAsync(loc[k], idx[k], cnt[k + 1] * 4, hipMemcpyDeviceToDevice, d->stream));
-        else if ((e = dec_upload_host(d, loc[k], idx[k], cnt[k + 1] * 4))) return e;
+        if (on_device) HIP_TRY(s, hipMemcpyAsync(loc[k], idx[k], cnt[k + 1] * 4, hipMemcpyDeviceToDevice, s->stream));
+        else if ((e = dec_upload_host(s, loc[k], idx[k], cnt[k + 1] * 4))) return e;
     }
     if ((e = rs_classes_of(s, n_records, loc[0], cnt[1], loc[1], cnt[2]))) return e;
     uint32_t bad[RS_BAD_WORDS] = {};
-    HIP_TRY(d, hipMemcpyAsync(bad, s->words.p, sizeof bad, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(s, hipMemcpyAsync(bad, s->words.p, sizeof bad, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
     if ((e = rs_bad_words(s, bad, "append"))) return e;
     for (int k = 0; k < 3; k++)
         if ((e = rs_reserve(s, s->set[k], s->set[k].n + cnt[k], k ? s->set[k].n + cnt[k] + 1 : 0))) return e;
@@ -515,12 +483,12 @@ static int rs_append(pgrc_rsets *s, const uint64_t cnt[3], const uint8_t *const 
         RsSet &t = s->set[k];
         if (!cnt[k]) continue;
         uint8_t *dst = (uint8_t *)t.rows.p + t.n * t.rb;
-        if (on_device) HIP_TRY(d, hipMemcpyAsync(dst, rows[k], cnt[k] * t.rb, hipMemcpyDeviceToDevice, d->stream));
-        else if ((e = dec_upload_host(d, dst, rows[k], cnt[k] * t.rb))) return e;
-        if (k) hipLaunchKernelGGL(k_rs_offset, dim3(rs_grid(cnt[k])), dim3(RS_TPB), 0, d->stream, (const uint32_t *)loc[k - 1], cnt[k], (uint32_t)s->A, (uint32_t *)t.map.p + t.n);
+        if (on_device) HIP_TRY(s, hipMemcpyAsync(dst, rows[k], cnt[k] * t.rb, hipMemcpyDeviceToDevice, s->stream));
+        else if ((e = dec_upload_host(s, dst, rows[k], cnt[k] * t.rb))) return e;
+        if (k) hipLaunchKernelGGL(k_rs_offset, dim3(dec_grid(cnt[k], RS_TPB)), dim3(RS_TPB), 0, s->stream, (const uint32_t *)loc[k - 1], cnt[k], (uint32_t)s->A, (uint32_t *)t.map.p + t.n);
     }
-    HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(s, hipGetLastError());
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
     for (int k = 0; k < 3; k++) s->set[k].n += cnt[k];
     s->A += n_records;
     return PGRC_OK;
@@ -540,7 +508,7 @@ static int rs_append_checks(pgrc_rsets *s, const uint64_t cnt[3], const uint32_t
 
 extern "C" {
 
-const char *pgrc_rsets_last_error(const pgrc_rsets *s) { return s ? s->d->err.c_str() : g_rs_create_err.c_str(); }
+const char *pgrc_rsets_last_error(const pgrc_rsets *s) { return s ? s->err.c_str() : g_rs_create_err.c_str(); }
 
 int pgrc_rsets_create(const pgrc_rsets_params *p, pgrc_rsets **out) {
     if (!out) return PGRC_E_PARAM;
@@ -548,14 +516,14 @@ int pgrc_rsets_create(const pgrc_rsets_params *p, pgrc_rsets **out) {
     if (!p) { g_rs_create_err = "read sets: params is NULL"; return PGRC_E_PARAM; }
     if (p->struct_size != sizeof(pgrc_rsets_params)) { g_rs_create_err = "read sets: struct_size is not sizeof(pgrc_rsets_params)"; return PGRC_E_PARAM; }
     if (p->read_len < 1 || p->read_len > 255) { g_rs_create_err = "read sets: the read length must be in [1, 255]"; return PGRC_E_PARAM; }
-    pgrc_decode_ctx *d = nullptr;
-    const int e = pgrc_decode_create(p->read_len, p->device, &d);
+    pgrc_rsets *s = new pgrc_rsets();
+    std::string why;
+    const int e = pgrc_stage_open(s, p->device, &why);
     if (e) {
-        g_rs_create_err = std::string("read sets: ") + pgrc_decode_last_error(nullptr);
+        g_rs_create_err = "read sets: " + why;
+        delete s;
         return e;
     }
-    pgrc_rsets *s = new pgrc_rsets();
-    s->d = d;
     s->prm = *p;
     // the alphabets (DividedPCLReadsSets.cpp:10-21)
     const bool n_apart = p->separate_n_reads_set || p->n_reads_lq;
@@ -570,15 +538,11 @@ int pgrc_rsets_create(const pgrc_rsets_params *p, pgrc_rsets **out) {
 
 void pgrc_rsets_destroy(pgrc_rsets *s) {
     if (!s) return;
-    {
-        PgrcDeviceScope scope(s->d->device);
-        (void)hipStreamSynchronize(s->d->stream);
-        for (RsSet &t : s->set) { dec_free(t.rows); dec_free(t.map); }
-        for (DevBuf *b : {&s->cls, &s->cnt[0], &s->cnt[1], &s->cnt[2], &s->flags, &s->desc[0], &s->desc[1], &s->fold, &s->words, &s->stage_idx}) dec_free(*b);
-        for (hipEvent_t ev : s->ev)
-            if (ev) (void)hipEventDestroy(ev);
-    }
-    pgrc_decode_destroy(s->d);
+    PgrcDeviceScope scope(s->device);
+    (void)hipStreamSynchronize(s->stream);
+    dec_free_all(rs_bufs(s));
+    s->ev.release();
+    pgrc_stage_close(s);
     delete s;
 }
 
@@ -593,9 +557,9 @@ int pgrc_rsets_append(pgrc_rsets *s, const pgrc_divided_reads *b, uint64_t n_rec
     if ((e = rs_append_checks(s, cnt, sym, rb, n_records))) return e;
     for (int k = 0; k < 3; k++)
         if (cnt[k] && (!rows[k] || (k && !idx[k - 1]))) return rs_fail(s, PGRC_E_PARAM, "append: a set of the batch has reads and a NULL array");
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     e = rs_append(s, cnt, rows, idx, n_records, false);
-    if (e) (void)hipStreamSynchronize(s->d->stream);
+    if (e) (void)hipStreamSynchronize(s->stream);
     return e;
 }
 
@@ -604,24 +568,23 @@ int pgrc_rsets_append_divider(pgrc_rsets *s, pgrc_divider *dv) {
     if (!dv) return rs_fail(s, PGRC_E_PARAM, "append: divider is NULL");
     PgrcDividerLast l;
     pgrc_divider_last_device(dv, &l);
-    if (l.device != s->d->device) return rs_fail(s, PGRC_E_PARAM, "append: the divider is on another device");
+    if (l.device != s->device) return rs_fail(s, PGRC_E_PARAM, "append: the divider is on another device");
     if (l.prm.read_len != s->prm.read_len || !l.prm.separate_n_reads_set != !s->prm.separate_n_reads_set || !l.prm.n_reads_lq != !s->prm.n_reads_lq)
         return rs_fail(s, PGRC_E_PARAM, "append: the divider's read length or set arguments are not this object's");
     if (s->finished) return rs_fail(s, PGRC_E_STATE, "append after pgrc_rsets_finish");
     if (!l.valid) return rs_fail(s, PGRC_E_STATE, "append: the divider's last run failed, or it has made none");
     int e;
     if ((e = rs_append_checks(s, l.cnt, l.symbols, l.rb, l.n_records))) return e;
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     e = rs_append(s, l.cnt, l.d_rows, l.d_idx, l.n_records, true);
-    if (e) (void)hipStreamSynchronize(s->d->stream);
+    if (e) (void)hipStreamSynchronize(s->stream);
     return e;
 }
 
 int pgrc_rsets_finish(pgrc_rsets *s) {
     if (!s) return PGRC_E_PARAM;
     if (s->finished) return rs_fail(s, PGRC_E_STATE, "finish: already finished");
-    pgrc_decode_ctx *d = s->d;
-    PGRC_ON_DEVICE(d);
+    PGRC_ON_DEVICE(s);
     int e;
     if (s->set[0].n != s->A - s->set[1].n - s->set[2].n) return rs_fail(s, PGRC_E_PARAM, "finish: the HQ count is not the reads' count minus the LQ and N counts");
     for (int k = 1; k < 3; k++) {
@@ -629,13 +592,13 @@ int pgrc_rsets_finish(pgrc_rsets *s) {
         if (!t.symbols) continue;
         if ((e = rs_reserve(s, t, t.n, t.n + 1))) return e;
         const uint32_t guard = (uint32_t)s->A;
-        HIP_TRY(d, hipMemcpyAsync((uint32_t *)t.map.p + t.n, &guard, 4, hipMemcpyHostToDevice, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(s, hipMemcpyAsync((uint32_t *)t.map.p + t.n, &guard, 4, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
     }
     if ((e = rs_classes(s))) return e;
     uint32_t bad[RS_BAD_WORDS] = {};
-    HIP_TRY(d, hipMemcpyAsync(bad, s->words.p, sizeof bad, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(s, hipMemcpyAsync(bad, s->words.p, sizeof bad, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
     if ((e = rs_bad_words(s, bad, "finish"))) return e;
     s->finished = true;
     return PGRC_OK;
@@ -671,8 +634,8 @@ int pgrc_rsets_get_rows(pgrc_rsets *s, int32_t which, uint64_t first, uint64_t n
     if (t.disposed) return rs_fail(s, PGRC_E_STATE, "get_rows: the set has been disposed");
     if (first > t.n || n > t.n - first) return rs_fail(s, PGRC_E_PARAM, "get_rows: rows outside the set");
     if (!out && n) return rs_fail(s, PGRC_E_PARAM, "get_rows: out is NULL");
-    PGRC_ON_DEVICE(s->d);
-    return rs_download(s->d, out, (const uint8_t *)t.rows.p + first * t.rb, n * t.rb);
+    PGRC_ON_DEVICE(s);
+    return dec_download_host(s, out, (const uint8_t *)t.rows.p + first * t.rb, n * t.rb);
 }
 
 int pgrc_rsets_get_mapping(pgrc_rsets *s, int32_t which, uint32_t *out) {
@@ -682,22 +645,22 @@ int pgrc_rsets_get_mapping(pgrc_rsets *s, int32_t which, uint32_t *out) {
     if (!out) return rs_fail(s, PGRC_E_PARAM, "get_mapping: out is NULL");
     if (which == PGRC_RSETS_HQ) {
         if ((e = rs_need(s, "get_mapping", {1, 2}))) return e;
-        PGRC_ON_DEVICE(s->d);
+        PGRC_ON_DEVICE(s);
         e = rs_hq_mapping(s, out);
-        if (e) (void)hipStreamSynchronize(s->d->stream);
+        if (e) (void)hipStreamSynchronize(s->stream);
         return e;
     }
     if ((e = rs_need(s, "get_mapping", {which}))) return e;
-    PGRC_ON_DEVICE(s->d);
-    return rs_download(s->d, out, s->set[which].map.p, (s->set[which].n + 1) * 4);
+    PGRC_ON_DEVICE(s);
+    return dec_download_host(s, out, s->set[which].map.p, (s->set[which].n + 1) * 4);
 }
 
 int pgrc_rsets_dispose(pgrc_rsets *s, int32_t which) {
     if (!s) return PGRC_E_PARAM;
     if (which < 0 || which > 2) return rs_fail(s, PGRC_E_PARAM, "dispose: which is PGRC_RSETS_HQ, PGRC_RSETS_LQ or PGRC_RSETS_N");
     RsSet &t = s->set[which];
-    PGRC_ON_DEVICE(s->d);
-    (void)hipStreamSynchronize(s->d->stream);
+    PGRC_ON_DEVICE(s);
+    (void)hipStreamSynchronize(s->stream);
     dec_free(t.rows);
     dec_free(t.map);
     t.cap_rows = t.cap_map = 0;
@@ -711,9 +674,9 @@ int pgrc_rsets_move_lq(pgrc_rsets *s, const uint8_t *is_hq, int32_t flags_on_dev
     int e;
     if (!is_hq && s->set[0].n) return rs_fail(s, PGRC_E_PARAM, "move: is_hq is NULL");
     if ((e = rs_need(s, "move", {0, 1, 2})) || (e = rs_move_allowed(s))) return e;
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     const uint8_t *d_flags = nullptr;
-    if ((e = rs_flags(s, is_hq, s->set[0].n, flags_on_device, &d_flags)) || (e = rs_move(s, d_flags))) (void)hipStreamSynchronize(s->d->stream);
+    if ((e = rs_flags(s, is_hq, s->set[0].n, flags_on_device, &d_flags)) || (e = rs_move(s, d_flags))) (void)hipStreamSynchronize(s->stream);
     return e;
 }
 
@@ -722,15 +685,15 @@ int pgrc_rsets_move_by_overlap(pgrc_rsets *s, pgrc_ovl_ctx *ovl) {
     if (!ovl) return rs_fail(s, PGRC_E_PARAM, "move: the overlap context is NULL");
     int e;
     if ((e = rs_need(s, "move", {0, 1, 2})) || (e = rs_move_allowed(s))) return e;
-    if (pgovl_device(ovl) != s->d->device) return rs_fail(s, PGRC_E_PARAM, "move: the overlap context is on another device");
+    if (pgovl_device(ovl) != s->device) return rs_fail(s, PGRC_E_PARAM, "move: the overlap context is on another device");
     if (s->ovl_ctx != ovl || !s->ovl_serial || pgovl_run_serial(ovl) != s->ovl_serial || s->ovl_gen != s->hq_gen)
         return rs_fail(s, PGRC_E_STATE, "move: the overlap context's last run was not made by pgrc_rsets_overlap on this object's HQ set as it is now");
     const uint8_t *d_flags = nullptr;
     uint64_t R = 0;
     if ((e = pgovl_both_sides_device(ovl, &d_flags, &R))) return rs_fail(s, e, std::string("move: ") + pgrc_ovl_last_error(ovl));
     if (R != s->set[0].n) return rs_fail(s, PGRC_E_STATE, "move: the overlap context's run has another reads' count than the HQ set");
-    PGRC_ON_DEVICE(s->d);
-    if ((e = rs_move(s, d_flags))) (void)hipStreamSynchronize(s->d->stream);
+    PGRC_ON_DEVICE(s);
+    if ((e = rs_move(s, d_flags))) (void)hipStreamSynchronize(s->stream);
     return e;
 }
 
@@ -740,9 +703,9 @@ int pgrc_rsets_remove(pgrc_rsets *s, const uint8_t *is_mapped, int32_t flags_on_
     const uint64_t n = s->set[1].n + s->set[2].n;
     if (!is_mapped && n) return rs_fail(s, PGRC_E_PARAM, "remove: is_mapped is NULL");
     if ((e = rs_need(s, "remove", {1, 2}))) return e;
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     const uint8_t *d_flags = nullptr;
-    if ((e = rs_flags(s, is_mapped, n, flags_on_device, &d_flags)) || (e = rs_remove(s, d_flags))) (void)hipStreamSynchronize(s->d->stream);
+    if ((e = rs_flags(s, is_mapped, n, flags_on_device, &d_flags)) || (e = rs_remove(s, d_flags))) (void)hipStreamSynchronize(s->stream);
     return e;
 }
 
@@ -753,16 +716,15 @@ int pgrc_rsets_remove_matched(pgrc_rsets *s, pgrc_match_ctx *c) {
     if ((e = rs_need(s, "remove", {1, 2}))) return e;
     const uint64_t n = s->set[1].n + s->set[2].n;
     if (c->multi) return rs_fail(s, PGRC_E_PARAM, "remove: the matcher runs on several devices");
-    if (c->device != s->d->device) return rs_fail(s, PGRC_E_PARAM, "remove: the matcher is on another device");
+    if (c->device != s->device) return rs_fail(s, PGRC_E_PARAM, "remove: the matcher is on another device");
     if (!c->have_reads || c->n != n) return rs_fail(s, PGRC_E_PARAM, "remove: the matcher's read count is not the LQ count plus the N count");
     if (!c->have_results || !c->d_pos.p) return rs_fail(s, PGRC_E_STATE, "remove: the matcher has no results");
-    pgrc_decode_ctx *d = s->d;
-    PGRC_ON_DEVICE(d);
-    HIP_TRY(d, hipStreamSynchronize(c->stream));
-    if ((e = pgrc_buf_unpooled(d, s->flags, n + 16))) return e;
-    if (n) hipLaunchKernelGGL(k_rs_matched, dim3(rs_grid(n)), dim3(RS_TPB), 0, d->stream, (const uint64_t *)c->d_pos.p, n, (uint8_t *)s->flags.p);
-    HIP_TRY(d, hipGetLastError());
-    if ((e = rs_remove(s, (const uint8_t *)s->flags.p))) (void)hipStreamSynchronize(d->stream);
+    PGRC_ON_DEVICE(s);
+    HIP_TRY(s, hipStreamSynchronize(c->stream));
+    if ((e = pgrc_buf_unpooled(s, s->flags, n + 16))) return e;
+    if (n) hipLaunchKernelGGL(k_rs_matched, dim3(dec_grid(n, RS_TPB)), dim3(RS_TPB), 0, s->stream, (const uint64_t *)c->d_pos.p, n, (uint8_t *)s->flags.p);
+    HIP_TRY(s, hipGetLastError());
+    if ((e = rs_remove(s, (const uint8_t *)s->flags.p))) (void)hipStreamSynchronize(s->stream);
     return e;
 }
 
@@ -772,7 +734,7 @@ int pgrc_rsets_overlap(pgrc_rsets *s, int32_t which, pgrc_ovl_ctx *ovl, double s
     if (!ovl || !out) return rs_fail(s, PGRC_E_PARAM, "overlap: the overlap context or out is NULL");
     int e;
     if ((e = rs_which(s, which, "overlap")) || (e = rs_need(s, "overlap", {which}))) return e;
-    if (pgovl_device(ovl) != s->d->device) return rs_fail(s, PGRC_E_PARAM, "overlap: the overlap context is on another device");
+    if (pgovl_device(ovl) != s->device) return rs_fail(s, PGRC_E_PARAM, "overlap: the overlap context is on another device");
     const RsSet &t = s->set[which];
     if (!t.n) return rs_fail(s, PGRC_E_PARAM, "overlap: the set is empty");
     pgrc_ovl_input in{};
@@ -801,7 +763,7 @@ int pgrc_rsets_to_matcher(pgrc_rsets *s, pgrc_match_ctx *c) {
     if ((e = rs_need(s, "to_matcher", {1, 2}))) return e;
     if (c->multi) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher runs on several devices");
     if (c->st_on) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher is in a streamed run");
-    if (c->device != s->d->device) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher is on another device");
+    if (c->device != s->device) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher is on another device");
     if (c->prm.read_len != s->prm.read_len) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher has another read length");
     const RsSet &lq = s->set[1], &nn = s->set[2];
     e = pgrc_match_begin_reads(c, lq.n + nn.n);
@@ -834,9 +796,9 @@ int pgrc_rsets_mapping_device(pgrc_rsets *s, int32_t which, const uint32_t **d_m
     if ((e = rs_which(s, which, "mapping"))) return e;
     if (which == PGRC_RSETS_HQ) {
         if ((e = rs_need(s, "mapping", {1, 2}))) return e;
-        PGRC_ON_DEVICE(s->d);
+        PGRC_ON_DEVICE(s);
         if ((e = rs_hq_mapping(s, nullptr))) {
-            (void)hipStreamSynchronize(s->d->stream);
+            (void)hipStreamSynchronize(s->stream);
             return e;
         }
         *d_map = (const uint32_t *)s->desc[0].p;

@@ -28,10 +28,6 @@ enum { RL_BAD_RANGE, RL_BAD_TWICE, RL_BAD_NEVER, RL_BAD_WORDS };
 static thread_local std::string g_rl_create_err;
 
 static inline uint32_t rl_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + RL_TPB - 1) / RL_TPB, 1), RL_MAX_BLOCKS); }
-static inline uint64_t rl_a16(uint64_t b) { return (b + 15) & ~15ull; }
-static inline float rl_ms(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 static int rl_fail(pgrc_rlist *s, int code, const std::string &msg) { return dec_fail(s->d, code, "reads list: " + msg); }
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -114,16 +110,16 @@ static __global__ void __launch_bounds__(RL_TPB) k_rl_pos_never(const uint8_t *_
 
 // ------------------------------------------------------------------------------------------------ host side: helpers
 static void rl_free(RlBufs &b) {
-    for (DevBuf *x : {&b.off, &b.org, &b.rc, &b.cnt, &b.sym, &b.roff}) dec_free(*x);
+    dec_free_all({&b.off, &b.org, &b.rc, &b.cnt, &b.sym, &b.roff});
     b = RlBufs{};
 }
 
 // fresh buffers of exactly the list's sizes; given back by the caller if its call fails
 static int rl_alloc(pgrc_decode_ctx *d, RlBufs &b, uint64_t n, uint64_t m, bool rc, bool mis, uint32_t off_width) {
     int e;
-    if ((e = pgrc_buf_unpooled(d, b.off, n * 2 + 16)) || (e = pgrc_buf_unpooled(d, b.org, n * 4 + 16))) return e;
+    if ((e = pgrc_bufs_unpooled(d, {{&b.off, n * 2 + 16}, {&b.org, n * 4 + 16}}))) return e;
     if (rc && (e = pgrc_buf_unpooled(d, b.rc, n + 16))) return e;
-    if (mis && ((e = pgrc_buf_unpooled(d, b.cnt, n + 16)) || (e = pgrc_buf_unpooled(d, b.sym, m + 16)) || (e = pgrc_buf_unpooled(d, b.roff, m * off_width + 16)))) return e;
+    if (mis && (e = pgrc_bufs_unpooled(d, {{&b.cnt, n + 16}, {&b.sym, m + 16}, {&b.roff, m * off_width + 16}}))) return e;
     b.n = n;
     b.nmis = m;
     b.has_rc = rc;
@@ -139,8 +135,7 @@ static void rl_swap_in(pgrc_rlist *s, RlBufs &nb) {
 }
 
 static int rl_events(pgrc_rlist *s) {
-    for (hipEvent_t &ev : s->ev)
-        if (!ev) HIP_TRY(s->d, hipEventCreate(&ev));
+    if (int e = s->ev.ensure(s->d)) return e;
     for (hipEvent_t &ev : s->ev_x)
         if (!ev) HIP_TRY(s->d, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     return PGRC_OK;
@@ -151,7 +146,7 @@ static int rl_begin(pgrc_rlist *s) {
     if ((e = rl_events(s))) return e;
     s->have_timing = false;
     s->tm = pgrc_rlist_timing{};
-    HIP_TRY(s->d, hipEventRecord(s->ev[0], s->d->stream));
+    HIP_TRY(s->d, s->ev.record(0, s->d->stream));
     return PGRC_OK;
 }
 
@@ -159,10 +154,10 @@ static int rl_begin(pgrc_rlist *s) {
 static void rl_done(pgrc_rlist *s, uint32_t call, std::chrono::steady_clock::time_point t0) {
     s->tm.struct_size = sizeof(pgrc_rlist_timing);
     s->tm.call = call;
-    s->tm.ms_fetch_device = dec_elapsed(s->ev[0], s->ev[1]);
-    s->tm.ms_build_device = dec_elapsed(s->ev[1], s->ev[2]);
-    s->tm.ms_pack_device = dec_elapsed(s->ev[2], s->ev[3]);
-    s->tm.ms_call = rl_ms(t0);
+    s->tm.ms_fetch_device = s->ev.ms(0, 1);
+    s->tm.ms_build_device = s->ev.ms(1, 2);
+    s->tm.ms_pack_device = s->ev.ms(2, 3);
+    s->tm.ms_call = dec_ms_since(t0);
     s->have_timing = true;
 }
 
@@ -170,24 +165,6 @@ static int rl_copy(pgrc_rlist *s, void *dst, const void *src, uint64_t bytes) {
     if (!bytes) return PGRC_OK;
     HIP_TRY(s->d, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s->d->stream));
     s->tm.bytes_device_copy += bytes;
-    return PGRC_OK;
-}
-
-// device -> host memory that may be pageable
-static int rl_download(pgrc_decode_ctx *d, void *h_dst, const void *d_src, uint64_t bytes) {
-    if (!bytes) return PGRC_OK;
-    if (pgrc_host_pinned(h_dst)) {
-        HIP_TRY(d, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
-        return PGRC_OK;
-    }
-    for (uint64_t at = 0; at < bytes; at += DEC_STAGE_BYTES) {
-        const uint64_t c = std::min<uint64_t>(DEC_STAGE_BYTES, bytes - at);
-        HIP_TRY(d, hipEventSynchronize(d->ev_copied[0]));       // (an upload may still read the staging buffer)
-        HIP_TRY(d, hipMemcpyAsync(d->stage[0], (const uint8_t *)d_src + at, c, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
-        memcpy((uint8_t *)h_dst + at, d->stage[0], c);
-    }
     return PGRC_OK;
 }
 
@@ -200,7 +177,7 @@ static int rl_narrow(pgrc_rlist *s, const uint16_t *in, uint64_t n, uint8_t *out
 
 // the original indexes of a matcher's reads from the read sets: SumOfMappings of the LQ and the N mapping, joined in `map`
 static int rl_reads_org(pgrc_rlist *s, pgrc_rsets *sets, uint64_t matcher_n, const char *what, const uint32_t **d_rorg) {
-    if (sets->d->device != s->d->device) return rl_fail(s, PGRC_E_PARAM, std::string(what) + ": the read sets are on another device");
+    if (sets->device != s->d->device) return rl_fail(s, PGRC_E_PARAM, std::string(what) + ": the read sets are on another device");
     const uint32_t *m[2] = {};
     uint64_t cnt[2] = {};
     int e;
@@ -244,7 +221,7 @@ static int rl_set_host(pgrc_rlist *s, const pgrc_export_streams *in) {
         if ((e = dec_upload_host(d, nb.org.p, in->org_idx, n * 4))) return e;
         if (nb.has_rc && (e = dec_upload_host(d, nb.rc.p, in->rev_comp, n))) return e;
         s->tm.bytes_up = n * w + n * 4 + (nb.has_rc ? n : 0);
-        HIP_TRY(d, hipEventRecord(s->ev[1], d->stream));
+        HIP_TRY(d, s->ev.record(1, d->stream));
         if (mis) {
             if ((e = dec_upload_host(d, nb.cnt.p, in->mis_cnt, n)) || (e = dec_upload_host(d, nb.sym.p, in->mis_sym, m)) || (e = dec_upload_host(d, nb.roff.p, in->mis_rev_off, m * w)))
                 return e;
@@ -256,8 +233,8 @@ static int rl_set_host(pgrc_rlist *s, const pgrc_export_streams *in) {
             HIP_TRY(d, hipStreamSynchronize(d->stream));
             if (m_dev != m) return rl_fail(s, PGRC_E_PARAM, "set_host: n_mismatches is " + std::to_string(m) + ", the counts sum to " + std::to_string(m_dev));
         }
-        HIP_TRY(d, hipEventRecord(s->ev[2], d->stream));
-        HIP_TRY(d, hipEventRecord(s->ev[3], d->stream));
+        HIP_TRY(d, s->ev.record(2, d->stream));
+        HIP_TRY(d, s->ev.record(3, d->stream));
         HIP_TRY(d, hipStreamSynchronize(d->stream));
         return PGRC_OK;
     };
@@ -289,7 +266,7 @@ static int rl_from_assembly(pgrc_rlist *s, const PgasmLastList &l, const uint32_
         } else if ((e = rl_copy(s, nb.org.p, l.d_org, l.n * 4))) {
             return e;
         }
-        for (int k = 1; k < 4; k++) HIP_TRY(d, hipEventRecord(s->ev[k], d->stream));
+        for (int k = 1; k < 4; k++) HIP_TRY(d, s->ev.record(k, d->stream));
         uint32_t h_bad[RL_BAD_WORDS] = {};
         HIP_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(d, hipStreamSynchronize(d->stream));
@@ -326,7 +303,7 @@ static int rl_export(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_a
     a.byte_per_read_length = x->byte_per_read_length;
     a.order_on_device = x->order_on_device;
     // the matcher's stream waits for what this one has queued, and this one for the export: no device-wide wait
-    HIP_TRY(d, hipEventRecord(s->ev[1], d->stream));
+    HIP_TRY(d, s->ev.record(1, d->stream));
     HIP_TRY(d, hipEventRecord(s->ev_x[0], d->stream));
     HIP_TRY(d, hipStreamWaitEvent(c->stream, s->ev_x[0], 0));
     PgrcExportResident r;
@@ -335,14 +312,14 @@ static int rl_export(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_a
     auto run = [&]() -> int {
         HIP_TRY(d, hipEventRecord(s->ev_x[1], c->stream));
         HIP_TRY(d, hipStreamWaitEvent(d->stream, s->ev_x[1], 0));
-        HIP_TRY(d, hipEventRecord(s->ev[2], d->stream));
+        HIP_TRY(d, s->ev.record(2, d->stream));
         if (r.n_entries >= (1ull << 32) || r.n_mismatches >= (1ull << 32)) return rl_fail(s, PGRC_E_PARAM, "export_pg_order: 2^32 entries or mismatches or more");
         const uint64_t n = r.n_entries, m = r.n_mismatches;
         if ((e = rl_alloc(d, nb, n, m, true, true, r.mis_off_width))) return e;
         if ((e = rl_copy(s, nb.off.p, r.d_off, n * 2)) || (e = rl_copy(s, nb.org.p, r.d_org, n * 4)) || (e = rl_copy(s, nb.rc.p, r.d_rc, n)) || (e = rl_copy(s, nb.cnt.p, r.d_cnt, n)) ||
             (e = rl_copy(s, nb.sym.p, r.d_sym, m)) || (e = rl_copy(s, nb.roff.p, r.d_rev_off, m * r.mis_off_width)))
             return e;
-        HIP_TRY(d, hipEventRecord(s->ev[3], d->stream));
+        HIP_TRY(d, s->ev.record(3, d->stream));
         HIP_TRY(d, hipStreamSynchronize(d->stream));
         return PGRC_OK;
     };
@@ -369,7 +346,7 @@ static int rl_download_run(pgrc_rlist *s, pgrc_export_streams *out) {
     const uint64_t n = b.n, m = b.nmis, w = b.off_width;
     int e;
     if ((e = rl_begin(s))) return e;
-    for (int k = 1; k < 3; k++) HIP_TRY(d, hipEventRecord(s->ev[k], d->stream));
+    for (int k = 1; k < 3; k++) HIP_TRY(d, s->ev.record(k, d->stream));
     out->n_entries = n;
     out->n_mismatches = m;
     out->off_width = (uint32_t)w;
@@ -383,13 +360,13 @@ static int rl_download_run(pgrc_rlist *s, pgrc_export_streams *out) {
     if (!out->off || !out->org_idx || !out->rev_comp || !out->mis_cnt || !out->mis_sym || !out->mis_rev_off) return rl_fail(s, PGRC_E_ALLOC, "download: host allocation failed");
     const void *d_off = b.off.p;
     if (w == 1) {
-        if ((e = pgrc_buf_unpooled(d, s->block, rl_a16(n) + 16)) || (e = rl_narrow(s, (const uint16_t *)b.off.p, n, (uint8_t *)s->block.p))) return e;
+        if ((e = pgrc_buf_unpooled(d, s->block, dec_a16(n) + 16)) || (e = rl_narrow(s, (const uint16_t *)b.off.p, n, (uint8_t *)s->block.p))) return e;
         d_off = s->block.p;
     }
-    HIP_TRY(d, hipEventRecord(s->ev[3], d->stream));
-    if ((e = rl_download(d, out->off, d_off, n * w)) || (e = rl_download(d, out->org_idx, b.org.p, n * 4))) return e;
-    if (b.has_rc && (e = rl_download(d, out->rev_comp, b.rc.p, n))) return e;
-    if (b.has_mis && ((e = rl_download(d, out->mis_cnt, b.cnt.p, n)) || (e = rl_download(d, out->mis_sym, b.sym.p, m)) || (e = rl_download(d, out->mis_rev_off, b.roff.p, m * w)))) return e;
+    HIP_TRY(d, s->ev.record(3, d->stream));
+    if ((e = dec_download_host(d, out->off, d_off, n * w)) || (e = dec_download_host(d, out->org_idx, b.org.p, n * 4))) return e;
+    if (b.has_rc && (e = dec_download_host(d, out->rev_comp, b.rc.p, n))) return e;
+    if (b.has_mis && ((e = dec_download_host(d, out->mis_cnt, b.cnt.p, n)) || (e = dec_download_host(d, out->mis_sym, b.sym.p, m)) || (e = dec_download_host(d, out->mis_rev_off, b.roff.p, m * w)))) return e;
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     s->tm.bytes_down = n * w + n * 4 + (b.has_rc ? n : 0) + (b.has_mis ? n + m + m * w : 0);
     rl_done(s, PGRC_RLIST_DOWNLOAD, t0);
@@ -404,14 +381,14 @@ static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, pgrc_rlist_archiv
     int e;
     if ((e = rl_begin(s))) return e;
     // the block: off | revComp | orgIdx | the archive form, each 16-byte aligned
-    const uint64_t at_rc = rl_a16(n * w) + 16, at_org = at_rc + (b.has_rc ? rl_a16(n) + 16 : 0), at_la = at_org + (want_org ? rl_a16(n * 4) + 16 : 0);
+    const uint64_t at_rc = dec_a16(n * w) + 16, at_org = at_rc + (b.has_rc ? dec_a16(n) + 16 : 0), at_la = at_org + (want_org ? dec_a16(n * 4) + 16 : 0);
     const uint64_t dev_bytes = at_la + (b.has_mis ? pgrc_la_device_bytes(n, m) : 0), host_bytes = at_la + (b.has_mis ? pgrc_la_host_bytes(n, m) : 0) + 16;
     if ((e = pgrc_buf_unpooled(d, s->block, dev_bytes + 16))) return e;
     uint8_t *ob = (uint8_t *)s->block.p;
-    HIP_TRY(d, hipEventRecord(s->ev[1], d->stream));
+    HIP_TRY(d, s->ev.record(1, d->stream));
     PgrcLaResident la{};
     if (b.has_mis && (e = pgrc_la_encode_resident(d, (const uint8_t *)b.cnt.p, (const uint8_t *)b.sym.p, (const uint8_t *)b.roff.p, n, m, fast, ob + at_la, &la))) return e;
-    HIP_TRY(d, hipEventRecord(s->ev[2], d->stream));
+    HIP_TRY(d, s->ev.record(2, d->stream));
     if (w == 1) {
         if ((e = rl_narrow(s, (const uint16_t *)b.off.p, n, ob))) return e;
     } else if ((e = rl_copy(s, ob, b.off.p, n * 2))) {
@@ -419,7 +396,7 @@ static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, pgrc_rlist_archiv
     }
     if (b.has_rc && (e = rl_copy(s, ob + at_rc, b.rc.p, n))) return e;
     if (want_org && (e = rl_copy(s, ob + at_org, b.org.p, n * 4))) return e;
-    HIP_TRY(d, hipEventRecord(s->ev[3], d->stream));
+    HIP_TRY(d, s->ev.record(3, d->stream));
     // the streams end where the last of them ends
     const uint64_t down = b.has_mis ? at_la + la.down : want_org ? at_org + n * 4 : b.has_rc ? at_rc + n : n * w;
     uint8_t *blk = nullptr;
@@ -463,9 +440,9 @@ static int rl_pair_order(pgrc_rlist *s, pgrc_rlist *const lists[3], uint64_t T, 
     }
     if (T) hipLaunchKernelGGL(k_rl_join, dim3(rl_grid(T)), dim3(RL_TPB), 0, d->stream, j, (uint32_t *)s->join.p);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(s->ev[1], d->stream));
+    HIP_TRY(d, s->ev.record(1, d->stream));
     if ((e = pgrc_pairorder_encode_joined(d, (const uint32_t *)s->join.p, T, form, out))) return e;
-    for (int k = 2; k < 4; k++) HIP_TRY(d, hipEventRecord(s->ev[k], d->stream));
+    for (int k = 2; k < 4; k++) HIP_TRY(d, s->ev.record(k, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     s->tm.bytes_down = d->potm.bytes_down;
     rl_done(s, PGRC_RLIST_PAIR_ORDER, t0);
@@ -487,9 +464,7 @@ static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pg
             longest = std::max(longest, l->cur.n);
             writers += l->cur.n;
         }
-    if ((e = pgrc_buf_unpooled(d, s->pos, T * 8 + 16)) || (e = pgrc_buf_unpooled(d, s->cls, T + 16)) || (e = pgrc_buf_unpooled(d, s->words, 64)) ||
-        (e = pgrc_buf_unpooled(d, s->scan, longest * 8 + 16)))
-        return e;
+    if ((e = pgrc_bufs_unpooled(d, {{&s->pos, T * 8 + 16}, {&s->cls, T + 16}, {&s->words, 64}, {&s->scan, longest * 8 + 16}}))) return e;
     uint64_t *pos = (uint64_t *)s->pos.p;
     uint8_t *cls = (uint8_t *)s->cls.p;
     uint32_t *bad = (uint32_t *)s->words.p;
@@ -533,14 +508,14 @@ static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pg
     }
     if (T) hipLaunchKernelGGL(k_rl_pos_never, dim3(rl_grid(T)), dim3(RL_TPB), 0, d->stream, (const uint8_t *)cls, T, bad);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipEventRecord(s->ev[1], d->stream));
+    HIP_TRY(d, s->ev.record(1, d->stream));
     uint32_t h_bad[RL_BAD_WORDS] = {};
     HIP_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     if (h_bad[RL_BAD_RANGE]) return rl_fail(s, PGRC_E_PARAM, "pair_positions: an original index of " + std::to_string(T) + " (n_total) or more");
     if (h_bad[RL_BAD_TWICE] || h_bad[RL_BAD_NEVER]) return rl_fail(s, PGRC_E_PARAM, "pair_positions: an index is written twice and another never");
     if ((e = pgrc_pairpos_encode_device(d, pos, T, x->pos_width, out))) return e;
-    for (int k = 2; k < 4; k++) HIP_TRY(d, hipEventRecord(s->ev[k], d->stream));
+    for (int k = 2; k < 4; k++) HIP_TRY(d, s->ev.record(k, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     s->tm.bytes_down = d->ptm.bytes_down;
     rl_done(s, PGRC_RLIST_PAIR_POSITIONS, t0);
@@ -555,7 +530,7 @@ int pgrc_rlist_create(int32_t device, pgrc_rlist **out) {
     if (!out) return PGRC_E_PARAM;
     *out = nullptr;
     pgrc_decode_ctx *d = nullptr;
-    const int e = pgrc_decode_create(1, device, &d);        // (the archive form's decode side alone reads the length; it is not used here)
+    const int e = pgrc_decode_create_on(device, &d);
     if (e) {
         g_rl_create_err = std::string("reads list: ") + pgrc_decode_last_error(nullptr);
         return e;
@@ -572,9 +547,8 @@ void pgrc_rlist_destroy(pgrc_rlist *s) {
         PgrcDeviceScope scope(s->d->device);
         (void)hipStreamSynchronize(s->d->stream);
         rl_free(s->cur);
-        for (DevBuf *b : {&s->map, &s->words, &s->block, &s->join, &s->pos, &s->scan, &s->cls}) dec_free(*b);
-        for (hipEvent_t ev : s->ev)
-            if (ev) (void)hipEventDestroy(ev);
+        dec_free_all({&s->map, &s->words, &s->block, &s->join, &s->pos, &s->scan, &s->cls});
+        s->ev.release();
         for (hipEvent_t ev : s->ev_x)
             if (ev) (void)hipEventDestroy(ev);
     }
@@ -625,7 +599,7 @@ int pgrc_rlist_from_assembly(pgrc_rlist *s, pgrc_asm_ctx *a, pgrc_rsets *sets, i
     PgasmLastList l;
     pgasm_last_list(a, &l);
     if (l.device != s->d->device) return rl_fail(s, PGRC_E_PARAM, "from_assembly: the assembly context is on another device");
-    if (sets && sets->d->device != s->d->device) return rl_fail(s, PGRC_E_PARAM, "from_assembly: the read sets are on another device");
+    if (sets && sets->device != s->d->device) return rl_fail(s, PGRC_E_PARAM, "from_assembly: the read sets are on another device");
     if (sets && (which < PGRC_RSETS_HQ || which > PGRC_RSETS_N)) return rl_fail(s, PGRC_E_PARAM, "from_assembly: which is PGRC_RSETS_HQ, PGRC_RSETS_LQ or PGRC_RSETS_N");
     if (!l.valid) return rl_fail(s, PGRC_E_STATE, "from_assembly: no run has succeeded on the assembly context");
     if (sets && l.mapped) return rl_fail(s, PGRC_E_STATE, "from_assembly: the assembly run has applied a host mapping already");

@@ -1,7 +1,8 @@
 // rlistctx.h -- a pseudogenome's reads list on the device (include/pgrc_readslist.h, rlist.hip) and what rlist.hip uses of the
 // contexts that fill and consume it: the assembly (pgasm.hip), the read sets (readsets.hip), the matcher's export
 // (export.hip), the archive form (listarchive.hip), the pair order (pairorder.hip) and the pair positions (pairpos.hip).
-// Every hook is a C++ function: exports.map keeps it out of the library's dynamic symbols.
+// Every hook is a C++ function: exports.map keeps it out of the library's dynamic symbols.  The list works on a decode context
+// (decctx.h), whose base is the stage handle of stagectx.h.
 #pragma once
 
 #include "pgrc_assemble.h"
@@ -18,12 +19,15 @@ struct RlBufs {
 };
 
 struct pgrc_rlist {
-    pgrc_decode_ctx *d = nullptr;       // the device handle: the stream, the staging buffers, the error string
+    // The stage handle (stagectx.h), and a decode context because the list archive, the pair order and the pair positions run
+    // on one; its read length belongs to the archive form's decode side alone and is not used here
+    pgrc_decode_ctx *d = nullptr;
     RlBufs cur;
     // scratch (grow-only): a mapping / the reads' original indexes, the words of the checks, the device side of the archive
     // block, the joined lists, positions and their scan, the class bytes
     DevBuf map, words, block, join, pos, scan, cls;
-    hipEvent_t ev[4]{}, ev_x[2]{};      // the phases of a call; the hand-overs between this stream and a matcher's
+    PhaseEvents<4> ev;                  // the phases of a call
+    hipEvent_t ev_x[2]{};               // the hand-overs between this stream and a matcher's
     bool have_timing = false;
     pgrc_rlist_timing tm{};
 };

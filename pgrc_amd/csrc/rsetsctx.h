@@ -1,5 +1,6 @@
 // rsetsctx.h -- the divided read sets on the device (include/pgrc_readsets.h, readsets.hip) and what readsets.hip uses of
 // the contexts at both ends of its edits: the divider (divide.hip), the overlap search (pgovl.hip), the matcher (api.hip).
+// The read sets are a stage: stagectx.h's PgrcStage (through decctx.h, which rlistctx.h needs on top of this header).
 #pragma once
 
 #include "decctx.h"
@@ -14,8 +15,7 @@ struct RsSet {
     bool disposed = false;
 };
 
-struct pgrc_rsets {
-    pgrc_decode_ctx *d = nullptr;       // the device handle: the stream, the staging buffers, the error string
+struct pgrc_rsets : PgrcStage {        // (the stream, the staging buffers, the error string)
     pgrc_rsets_params prm{};
     RsSet set[3];
     uint64_t A = 0;                     // records appended; readsTotalCount once finished
@@ -27,7 +27,7 @@ struct pgrc_rsets {
     // scratch of the edits (grow-only): the class bytes, three counts per original index, the flags, per-row counts of a
     // removal, descriptors, scan folds, the words of the checks
     DevBuf cls, cnt[3], flags, desc[2], fold, words, stage_idx;
-    hipEvent_t ev[4]{};
+    PhaseEvents<4> ev;
     bool have_timing = false;
     pgrc_rsets_timing tm{};
 };

@@ -1,8 +1,8 @@
 // selftest.hip -- test entries into the shared primitives: scanops.h's block scan and device scan, radix.hip's stable sort and
 // segment sort; and into the hand-over: pack.hip's text and read kernels, mempack.hip's packing of a text that is in HBM already,
-// and what a context holds of its reads and its text after them.  Thin kernels and host wrappers, nothing else; linked with the product's objects into libpgrc_selftest.so
-// (never into libpgrc_match.so).  tests/test_gpu_primitives.py, tests/test_gpu_handover.py and tests/test_gpu_memdev.py
-// drive it against numpy.
+// what a context holds of its reads and its text after them, and stagectx.h's staged copies up and down.  Thin kernels and host wrappers, nothing else; linked with the product's objects into libpgrc_selftest.so
+// (never into libpgrc_match.so).  tests/test_gpu_primitives.py, tests/test_gpu_handover.py, tests/test_gpu_memdev.py and
+// tests/test_gpu_staging.py drive it against numpy.
 //
 // Every entry takes host arrays (pgrc_selftest_mem_pack_device: its text at a device address), runs on the handle's device and returns host arrays.  Every device buffer that a primitive
 // writes has a guard zone of ST_GUARD elements after its logical end, filled with ST_FILL bytes like the buffer itself; the
@@ -18,6 +18,7 @@
 
 #include "ctx.h"
 #include "scanops.h"
+#include "stagectx.h"
 
 #define ST_GUARD 64
 #define ST_FILL 0xA5
@@ -570,4 +571,55 @@ extern "C" int pgrc_selftest_reads_state(pgrc_selftest *h, const pgrc_match_ctx 
     if (out_nascii && s->n_nreads) HIP_TRY(c, hipMemcpy(out_nascii, s->nread_ascii.p, s->n_nreads * s->prm.read_len, hipMemcpyDeviceToHost));
     if (out_text && s->have_pg) HIP_TRY(c, hipMemcpy(out_text, s->pg2[0].p, s->pg_words * 4, hipMemcpyDeviceToHost));
     return PGRC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- the stage handle
+extern "C" uint64_t pgrc_selftest_stage_bytes(void) { return DEC_STAGE_BYTES; }
+
+// `bytes` bytes of `in` up with dec_upload_host and down again with dec_download_host into `out`, on a stage that the entry
+// opens and closes (stagectx.h).  pinned_up / pinned_down: that side's host memory is page-locked -- allocated here and copied
+// from `in` / into `out` -- so that the copy goes without the staging buffers; otherwise the caller's pageable array is used as
+// it is.  The device buffer has a guard zone; *guards bit 0: it is intact.
+extern "C" int pgrc_selftest_stage_roundtrip(pgrc_selftest *h, const void *in, uint64_t bytes, int pinned_up, int pinned_down, void *out, uint32_t *guards) {
+    PgrcDev *c = &h->dev;
+    *guards = 0;
+    PgrcDeviceScope scope(c->device);
+    if (!scope.ok) {
+        c->err = "selftest: hipSetDevice failed";
+        return PGRC_E_NO_DEVICE;
+    }
+    void *pin[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; k++)
+        if ((k ? pinned_down : pinned_up) && hipHostMalloc(&pin[k], bytes + 16) != hipSuccess) {
+            (void)hipGetLastError();
+            if (pin[0]) (void)hipHostFree(pin[0]);
+            c->err = "selftest: hipHostMalloc failed";
+            return PGRC_E_ALLOC;
+        }
+    if (pin[0]) memcpy(pin[0], in, bytes);
+    StBuf dbuf;
+    PgrcStage s;
+    std::string why;
+    int e = pgrc_stage_open(&s, c->device, &why);
+    if (e) {
+        c->err = "selftest: " + why;
+    } else {
+        bool ok = false;
+        hipError_t he = dbuf.alloc(bytes, ST_GUARD);
+        if (he == hipSuccess) {
+            if (!(e = dec_upload_host(&s, dbuf.p, pin[0] ? pin[0] : in, bytes))) e = dec_download_host(&s, pin[1] ? pin[1] : out, dbuf.p, bytes);
+            if (!e) he = dbuf.intact(&ok);
+        }
+        if (he != hipSuccess) {
+            s.err = hipGetErrorString(he);
+            e = pgrc_hip_code(he);
+        }
+        if (e) c->err = "selftest: " + s.err;
+        *guards = ok ? 1u : 0u;
+        pgrc_stage_close(&s);
+    }
+    if (!e && pin[1]) memcpy(out, pin[1], bytes);
+    for (void *p : pin)
+        if (p) (void)hipHostFree(p);
+    return e;
 }

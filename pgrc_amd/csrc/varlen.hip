@@ -406,13 +406,8 @@ void pgrc_varlen_destroy(pgrc_varlen *v) {
     if (!v) return;
     PgrcDeviceScope scope(v->device);
     if (v->stream) (void)hipStreamSynchronize(v->stream);
-    for (DevBuf *b : {&v->d_tab, &v->d_book, &v->d_src, &v->d_coded, &v->d_text, &v->d_bmap, &v->d_bent, &v->d_bcnt, &v->d_bsum, &v->d_bbase,
-                      &v->d_fold, &v->d_flag}) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-    }
-    for (hipEvent_t ev : v->ev)
-        if (ev) (void)hipEventDestroy(ev);
+    dec_free_all({&v->d_tab, &v->d_book, &v->d_src, &v->d_coded, &v->d_text, &v->d_bmap, &v->d_bent, &v->d_bcnt, &v->d_bsum, &v->d_bbase, &v->d_fold, &v->d_flag});
+    v->ev.release();
     if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
 }
@@ -439,8 +434,7 @@ int pgrc_varlen_create(const void *book, uint64_t book_bytes, int32_t device, pg
     PgrcDeviceScope scope(device);
     if (!scope.ok) e = PGRC_E_NO_DEVICE;
     if (!e && hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess) e = PGRC_E_DEVICE;
-    for (int k = 0; k < 4 && !e; k++)
-        if (hipEventCreate(&v->ev[k]) != hipSuccess) e = PGRC_E_DEVICE;
+    if (!e && v->ev.ensure(v)) e = PGRC_E_DEVICE;
     if (!e) e = pgrc_buf_unpooled(v, v->d_tab, sizeof(VlTables));
     if (!e) e = pgrc_buf_unpooled(v, v->d_book, sizeof(VlBook));
     if (!e) e = pgrc_buf_unpooled(v, v->d_flag, 64);
@@ -515,17 +509,16 @@ int pgrc_varlen_encode(pgrc_varlen *v, const pgrc_varlen_part *parts, uint32_t n
     }
     const uint64_t nb = (n + VL_TILE - 1) / VL_TILE;
     if (nb > 0x7FFFFFFFull) return vl_fail(v, PGRC_E_PARAM, "encode: the text is too long");
-    if ((e = pgrc_buf_unpooled(v, v->d_bmap, nb * 4)) || (e = pgrc_buf_unpooled(v, v->d_bent, nb * 4)) || (e = pgrc_buf_unpooled(v, v->d_bcnt, nb * 8)) ||
-        (e = pgrc_buf_unpooled(v, v->d_bbase, (nb + 1) * 8)) || (e = pgrc_buf_unpooled(v, v->d_fold, sco_scratch_elems(nb) * 8)))
+    if ((e = pgrc_bufs_unpooled(v, {{&v->d_bmap, nb * 4}, {&v->d_bent, nb * 4}, {&v->d_bcnt, nb * 8}, {&v->d_bbase, (nb + 1) * 8}, {&v->d_fold, sco_scratch_elems(nb) * 8}})))
         return e;
     uint32_t *bmap = (uint32_t *)v->d_bmap.p, *bent = (uint32_t *)v->d_bent.p, *d_bad = (uint32_t *)v->d_flag.p;
     uint64_t *bcnt = (uint64_t *)v->d_bcnt.p, *bbase = (uint64_t *)v->d_bbase.p;
     const VlTables *tab = (const VlTables *)v->d_tab.p;
     HIP_TRY(v, hipMemsetAsync(d_bad, 0, 4, st));
-    HIP_TRY(v, hipEventRecord(v->ev[0], st));
+    HIP_TRY(v, v->ev.record(0, st));
     hipLaunchKernelGGL(k_vl_maps, dim3((uint32_t)nb), dim3(VL_TPB), 0, st, s, tab, bmap, bcnt, d_bad);
     HIP_TRY(v, hipGetLastError());
-    HIP_TRY(v, hipEventRecord(v->ev[1], st));
+    HIP_TRY(v, v->ev.record(1, st));
     HIP_TRY(v, (sco_device_scan<false, false>(st, ScoLoad<uint32_t, uint32_t, ScoIdentity>{bmap, ScoIdentity{}}, nb, ScoMap4{}, (uint32_t)SCO_MAP4_IDENTITY,
                                              (uint32_t)SCO_MAP4_IDENTITY, ScoStore<uint32_t>{bent}, (uint32_t *)v->d_fold.p)));
     HIP_TRY(v, (sco_device_scan<false, true>(st, VlBlockCount{bcnt, bent}, nb, ScoPlus{}, (uint64_t)0, (uint64_t)0, ScoStore<uint64_t>{bbase},
@@ -534,7 +527,7 @@ int pgrc_varlen_encode(pgrc_varlen *v, const pgrc_varlen_part *parts, uint32_t n
     uint32_t bad = 0;
     HIP_TRY(v, hipMemcpyAsync(&total, bbase + nb, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(v, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(v, hipEventRecord(v->ev[2], st));
+    HIP_TRY(v, v->ev.record(2, st));
     HIP_TRY(v, hipStreamSynchronize(st));
     if (bad) return vl_fail(v, PGRC_E_SYMBOL, "encode: the text holds a byte that is no symbol of the book");
     if (total > n) return vl_fail(v, PGRC_E_DEVICE, "encode: inconsistent counts");
@@ -548,7 +541,7 @@ int pgrc_varlen_encode(pgrc_varlen *v, const pgrc_varlen_part *parts, uint32_t n
     }
     hipLaunchKernelGGL(k_vl_emit, dim3((uint32_t)nb), dim3(VL_TPB), 0, st, s, tab, (const uint32_t *)bent, (const uint64_t *)bbase, d_out, total);
     HIP_TRY(v, hipGetLastError());
-    HIP_TRY(v, hipEventRecord(v->ev[3], st));
+    HIP_TRY(v, v->ev.record(3, st));
     HIP_TRY(v, hipStreamSynchronize(st));
     if (!out_on_device) {
         const auto t1 = std::chrono::steady_clock::now();
@@ -556,9 +549,9 @@ int pgrc_varlen_encode(pgrc_varlen *v, const pgrc_varlen_part *parts, uint32_t n
         HIP_TRY(v, hipStreamSynchronize(st));
         v->tm.ms_download = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
     }
-    (void)hipEventElapsedTime(&v->tm.ms_maps, v->ev[0], v->ev[1]);
-    (void)hipEventElapsedTime(&v->tm.ms_scan, v->ev[1], v->ev[2]);
-    (void)hipEventElapsedTime(&v->tm.ms_emit, v->ev[2], v->ev[3]);
+    v->tm.ms_maps = v->ev.ms(0, 1);
+    v->tm.ms_scan = v->ev.ms(1, 2);
+    v->tm.ms_emit = v->ev.ms(2, 3);
     v->tm.ms_call = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PGRC_OK;
 }
@@ -592,18 +585,18 @@ int pgrc_varlen_decode(pgrc_varlen *v, const void *coded, uint64_t coded_len, in
     }
     const uint64_t nb = (m + VL_DTILE - 1) / VL_DTILE;
     if (nb > 0x7FFFFFFFull) return vl_fail(v, PGRC_E_PARAM, "decode: the coded stream is too long");
-    if ((e = pgrc_buf_unpooled(v, v->d_bsum, nb * 4)) || (e = pgrc_buf_unpooled(v, v->d_bbase, (nb + 1) * 8)) || (e = pgrc_buf_unpooled(v, v->d_fold, sco_scratch_elems(nb) * 8))) return e;
+    if ((e = pgrc_bufs_unpooled(v, {{&v->d_bsum, nb * 4}, {&v->d_bbase, (nb + 1) * 8}, {&v->d_fold, sco_scratch_elems(nb) * 8}}))) return e;
     uint32_t *bsum = (uint32_t *)v->d_bsum.p;
     uint64_t *bbase = (uint64_t *)v->d_bbase.p;
     const VlBook *book = (const VlBook *)v->d_book.p;
-    HIP_TRY(v, hipEventRecord(v->ev[0], st));
+    HIP_TRY(v, v->ev.record(0, st));
     hipLaunchKernelGGL(k_vl_declen, dim3((uint32_t)nb), dim3(VL_TPB), 0, st, d_coded, m, book, bsum);
     HIP_TRY(v, hipGetLastError());
-    HIP_TRY(v, hipEventRecord(v->ev[1], st));
+    HIP_TRY(v, v->ev.record(1, st));
     HIP_TRY(v, (sco_sum_u64<false>(st, (const uint32_t *)bsum, nb, bbase, (uint64_t *)v->d_fold.p)));
     uint64_t total = 0;
     HIP_TRY(v, hipMemcpyAsync(&total, bbase + nb, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(v, hipEventRecord(v->ev[2], st));
+    HIP_TRY(v, v->ev.record(2, st));
     HIP_TRY(v, hipStreamSynchronize(st));
     v->tm.symbols = total;
     if (total != expected_len)
@@ -616,7 +609,7 @@ int pgrc_varlen_decode(pgrc_varlen *v, const void *coded, uint64_t coded_len, in
         }
         hipLaunchKernelGGL(k_vl_expand, dim3((uint32_t)nb), dim3(VL_TPB), 0, st, d_coded, m, book, (const uint64_t *)bbase, d_out, total);
         HIP_TRY(v, hipGetLastError());
-        HIP_TRY(v, hipEventRecord(v->ev[3], st));
+        HIP_TRY(v, v->ev.record(3, st));
         HIP_TRY(v, hipStreamSynchronize(st));
         if (!out_on_device) {
             const auto t1 = std::chrono::steady_clock::now();
@@ -624,10 +617,10 @@ int pgrc_varlen_decode(pgrc_varlen *v, const void *coded, uint64_t coded_len, in
             HIP_TRY(v, hipStreamSynchronize(st));
             v->tm.ms_download = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
         }
-        (void)hipEventElapsedTime(&v->tm.ms_emit, v->ev[2], v->ev[3]);
+        v->tm.ms_emit = v->ev.ms(2, 3);
     }
-    (void)hipEventElapsedTime(&v->tm.ms_maps, v->ev[0], v->ev[1]);
-    (void)hipEventElapsedTime(&v->tm.ms_scan, v->ev[1], v->ev[2]);
+    v->tm.ms_maps = v->ev.ms(0, 1);
+    v->tm.ms_scan = v->ev.ms(1, 2);
     v->tm.ms_call = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PGRC_OK;
 }

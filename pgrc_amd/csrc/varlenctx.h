@@ -27,7 +27,7 @@ struct VlBook {
 static_assert(sizeof(VlBook) % 16 == 0, "copied to LDS as uint4");
 
 struct pgrc_varlen : PgrcDev {
-    hipEvent_t ev[4]{};
+    PhaseEvents<4> ev;
     uint32_t ncodes = 0;
     VlTables tab{};
     uint8_t t4[4096]{};        // (host only: e is made from it)

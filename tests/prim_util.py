@@ -168,8 +168,16 @@ def lib():
         L.pgrc_selftest_block_scan.argtypes = [vp, i32, u32, i32, i32, vp, vp, vp, vp, C.POINTER(u32)]
         L.pgrc_selftest_sort.argtypes = [vp, vp, vp, u64, u32, u32, vp, vp, C.POINTER(u32)]
         L.pgrc_selftest_sort_segments.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, C.POINTER(u32)]
+        L.pgrc_selftest_stage_bytes.argtypes = []
+        L.pgrc_selftest_stage_bytes.restype = u64
+        L.pgrc_selftest_stage_roundtrip.argtypes = [vp, vp, u64, i32, i32, vp, C.POINTER(u32)]
         _lib = L
     return _lib
+
+
+def stage_bytes():
+    """stagectx.h DEC_STAGE_BYTES: the staging chunk of the copies between pageable host memory and the device"""
+    return lib().pgrc_selftest_stage_bytes()
 
 
 def _ptr(a):
@@ -226,6 +234,14 @@ class SelfTest:
         self._check(lib().pgrc_selftest_sort(self.h, _ptr(keys), _ptr(vals) if vals is not None else None, keys.size, bit_lo, bit_hi, _ptr(ok),
                                              _ptr(ov) if ov is not None else None, C.byref(g)), "sort")
         return ok, ov, g.value
+
+    def stage_roundtrip(self, x, pinned_up, pinned_down):
+        """x up and down again through a stage; each side page-locked or pageable -> (the bytes that came back, guards); guards == 1: intact"""
+        x = np.ascontiguousarray(x, dtype=np.uint8)
+        out = np.zeros(x.size, dtype=np.uint8)
+        g = C.c_uint32(0)
+        self._check(lib().pgrc_selftest_stage_roundtrip(self.h, _ptr(x), x.size, int(pinned_up), int(pinned_down), _ptr(out), C.byref(g)), "stage_roundtrip")
+        return out, g.value
 
     def sort_segments(self, keys, vals, seg, bit_lo, bit_hi, top_bits, cap):
         """-> (keys, values, ovl[0 .. cap], guards); guards == 7: intact"""

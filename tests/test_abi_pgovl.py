@@ -82,3 +82,19 @@ def test_create_fails_without_a_device():
     with pytest.raises(PgrcMatchError) as e:
         OverlapFinder()
     assert e.value.code == 3                                # PGRC_E_NO_DEVICE
+
+
+def test_stage_creates_name_the_missing_device():
+    """the overlap search and the read sets open a stage handle of their own: without a device both creates are
+    PGRC_E_NO_DEVICE, each with its own text"""
+    import torch
+    from pgrc_amd import _lib
+    if torch.cuda.is_available():
+        return
+    lib = _lib.lib
+    h = C.c_void_p()
+    assert lib.pgrc_ovl_create(-1, C.byref(h)) == 3 and not h.value
+    assert lib.pgrc_ovl_last_error(None) == b"no HIP device"
+    prm = _lib.RsetsParams(C.sizeof(_lib.RsetsParams), 100, 0, 0, -1)
+    assert lib.pgrc_rsets_create(C.byref(prm), C.byref(h)) == 3 and not h.value
+    assert lib.pgrc_rsets_last_error(None) == b"read sets: no HIP device"
