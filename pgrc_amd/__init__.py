@@ -24,3 +24,4 @@ from .assemble import PgAssembler  # noqa: F401
 from .overlap import OverlapFinder  # noqa: F401
 from .varlen import VarLenDNACoder  # noqa: F401
 from .rlist import ReadsList  # noqa: F401
+from .verify import Verifier  # noqa: F401

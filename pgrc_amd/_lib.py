@@ -380,6 +380,47 @@ RLIST_PROTOS = [
     ("pgrc_rlist_pair_positions", C.c_int, [C.POINTER(RlistPairPosArgs), _P]),
 ]
 
+
+class VerifyResult(C.Structure):    # pgrc_verify_result
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("ok", C.c_int32), ("salts_used", C.c_uint32),
+                ("n_source", C.c_uint64 * 2), ("n_decoded", C.c_uint64 * 2), ("mismatched_rows", C.c_uint64),
+                ("first_mismatch_file", C.c_uint32), ("first_mismatch_row", C.c_uint64), ("source_unmatched", C.c_uint64),
+                ("decoded_unmatched", C.c_uint64), ("undecided", C.c_uint64), ("first_source_unmatched", C.c_uint64),
+                ("first_decoded_unmatched", C.c_uint64)]
+
+
+class VerifyTiming(C.Structure):    # pgrc_verify_timing
+    _fields_ = [("struct_size", C.c_uint32), ("salts_used", C.c_uint32), ("ms_upload", C.c_float), ("ms_fastq", C.c_float),
+                ("ms_fastq_parse_device", C.c_float), ("ms_fastq_pack_device", C.c_float), ("ms_rows_device", C.c_float),
+                ("ms_compare_device", C.c_float), ("ms_hash_device", C.c_float), ("ms_sort_device", C.c_float),
+                ("ms_scan_device", C.c_float), ("ms_confirm_device", C.c_float), ("ms_finish", C.c_float),
+                ("ms_total", C.c_float), ("bytes_up", C.c_uint64), ("bytes_resident", C.c_uint64)]
+
+
+# include/pgrc_verify.h: exported by libpgrc_verify.so (the product's objects and verify.hip), never by libpgrc_match.so
+_U64P = C.POINTER(C.c_uint64)
+VERIFY_PROTOS = [
+    ("pgrc_verify_begin", C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
+    ("pgrc_verify_add_rows", C.c_int, [_P, C.c_uint32, _P, C.c_uint64]),
+    ("pgrc_verify_add_fastq", C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int32, _U64P, _U64P, _U64P]),
+    ("pgrc_verify_finish", C.c_int, [_P, C.POINTER(VerifyResult)]),
+    ("pgrc_verify_get_timing", C.c_int, [_P, C.POINTER(VerifyTiming)]),
+    ("pgrc_verify_last_error", C.c_char_p, [_P]),
+    ("pgrc_verify_end", None, [_P]),
+]
+VERIFY_EXPORTED_SYMBOLS = [p[0] for p in VERIFY_PROTOS]
+VERIFY_LIB_PATH = os.environ.get("PGRC_VERIFY_LIB") or os.path.join(_HERE, "libpgrc_verify.so")
+
+
+def bind_verify(cdll: C.CDLL) -> C.CDLL:
+    """the prototypes of include/pgrc_verify.h on a library that holds them (libpgrc_verify.so; the tests' libpgrc_selftest.so)"""
+    for name, res, args in VERIFY_PROTOS:
+        fn = getattr(cdll, name)
+        fn.restype = res
+        fn.argtypes = args
+    return cdll
+
+
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 RLIST_EXPORTED_SYMBOLS = [p[0] for p in RLIST_PROTOS]
 RSETS_EXPORTED_SYMBOLS = [p[0] for p in RSETS_PROTOS]
@@ -423,3 +464,6 @@ def _load() -> C.CDLL:
 
 
 lib = _load()
+if not os.path.exists(VERIFY_LIB_PATH):
+    raise ImportError(f"{VERIFY_LIB_PATH} is missing: `make -C pgrc_amd/csrc` builds it beside libpgrc_match.so")
+vlib = bind_verify(C.CDLL(VERIFY_LIB_PATH))

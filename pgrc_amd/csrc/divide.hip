@@ -507,6 +507,10 @@ void pgrc_divider_last_device(const pgrc_divider *d, PgrcDividerLast *out) {
     out->d_idx[0] = (const uint32_t *)d->d_idx[0].p;
     out->d_idx[1] = (const uint32_t *)d->d_idx[1].p;
 }
+void pgrc_divider_last_reads_device(const pgrc_divider *d, const uint8_t **d_reads, uint64_t *n_records) {
+    *d_reads = d->last_valid ? (const uint8_t *)d->d_reads.p : nullptr;
+    *n_records = d->last_valid ? d->last_n : 0;
+}
 extern "C" {
 
 int pgrc_divider_run(pgrc_divider *d, const char *reads, const char *quals, uint64_t n, pgrc_divided_reads *out) {

@@ -43,6 +43,9 @@ struct PgrcDividerLast {
     const uint32_t *d_idx[2];
 };
 void pgrc_divider_last_device(const pgrc_divider *d, PgrcDividerLast *out);
+// divide.hip: the symbol rows of the divider's last run where they lie (n_records rows of read_len bytes in record order, the
+// records of a pair of files interleaved; 16 spare bytes behind them; valid until its next run; NULL after a failed run)
+void pgrc_divider_last_reads_device(const pgrc_divider *d, const uint8_t **d_reads, uint64_t *n_records);
 
 // pgovl.hip
 // pgrc_ovl_run; rows_on_device: in->packed_rows is memory of the context's device, complete when the call is made

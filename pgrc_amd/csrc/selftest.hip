@@ -2,7 +2,8 @@
 // segment sort; and into the hand-over: pack.hip's text and read kernels, mempack.hip's packing of a text that is in HBM already,
 // what a context holds of its reads and its text after them, and stagectx.h's staged copies up and down.  Thin kernels and host wrappers, nothing else; linked with the product's objects into libpgrc_selftest.so
 // (never into libpgrc_match.so).  tests/test_gpu_primitives.py, tests/test_gpu_handover.py, tests/test_gpu_memdev.py and
-// tests/test_gpu_staging.py drive it against numpy.
+// tests/test_gpu_staging.py drive it against numpy; tests/test_gpu_verify.py reaches the verifier's pairing
+// under keys of its own and the cut of its keys (verify.hip).
 //
 // Every entry takes host arrays (pgrc_selftest_mem_pack_device: its text at a device address), runs on the handle's device and returns host arrays.  Every device buffer that a primitive
 // writes has a guard zone of ST_GUARD elements after its logical end, filled with ST_FILL bytes like the buffer itself; the
@@ -19,6 +20,7 @@
 #include "ctx.h"
 #include "scanops.h"
 #include "stagectx.h"
+#include "verifyctx.h"
 
 #define ST_GUARD 64
 #define ST_FILL 0xA5
@@ -623,3 +625,50 @@ extern "C" int pgrc_selftest_stage_roundtrip(pgrc_selftest *h, const void *in, u
         if (p) (void)hipHostFree(p);
     return e;
 }
+
+// ---------------------------------------------------------------------------------------------------- the verifier (verify.hip)
+// Phases 2-4 of the MULTISET kind -- the union sort, the run structure, the byte compare of the pairs -- on keys and items of
+// the caller: n_s source and n_d decoded items of item_bytes bytes each, one key per item.  counts: matched pairs, undecided
+// pairs, unmatched source items, unmatched decoded items, the smallest unmatched source and decoded index (UINT64_MAX: none).
+extern "C" int pgrc_selftest_verify_match(pgrc_selftest *h, const uint64_t *keys_s, const uint8_t *items_s, uint64_t n_s, const uint64_t *keys_d,
+                                          const uint8_t *items_d, uint64_t n_d, uint32_t item_bytes, uint64_t counts[6]) {
+    PgrcDev *c = &h->dev;
+    if (!item_bytes) {
+        c->err = "selftest: item_bytes is 0";
+        return PGRC_E_PARAM;
+    }
+    pgrc_verify *v = nullptr;
+    int e = pgrc_vf_open(c->device, item_bytes, &v);
+    if (e) {
+        c->err = std::string("selftest: ") + pgrc_verify_last_error(nullptr);
+        return e;
+    }
+    PgrcDeviceScope scope(c->device);
+    StBuf its, itd;
+    hipError_t he = its.alloc(n_s * item_bytes, VF_PAD);
+    if (he == hipSuccess) he = itd.alloc(n_d * item_bytes, VF_PAD);
+    if (he == hipSuccess && n_s) he = hipMemcpy(its.p, items_s, n_s * item_bytes, hipMemcpyHostToDevice);
+    if (he == hipSuccess && n_d) he = hipMemcpy(itd.p, items_d, n_d * item_bytes, hipMemcpyHostToDevice);
+    if (he == hipSuccess && !(e = pgrc_vf_key_buffers(v, n_s + n_d))) {
+        if (n_s) he = hipMemcpy(v->key[0].p, keys_s, n_s * 8, hipMemcpyHostToDevice);
+        if (he == hipSuccess && n_d) he = hipMemcpy((uint64_t *)v->key[0].p + n_s, keys_d, n_d * 8, hipMemcpyHostToDevice);
+    }
+    if (he == hipSuccess && !e) {
+        VfSide s{{its.p, nullptr}, {item_bytes, 0}, n_s}, d{{itd.p, nullptr}, {item_bytes, 0}, n_d};
+        VfCounts r;
+        if (!(e = pgrc_vf_match_keys(v, s, d, &r))) {
+            const uint64_t out[6] = {r.matched, r.undecided, r.s_unmatched, r.d_unmatched, r.first_s, r.first_d};
+            memcpy(counts, out, sizeof out);
+        }
+    }
+    if (he != hipSuccess) {
+        v->err = hipGetErrorString(he);
+        e = pgrc_hip_code(he);
+    }
+    if (e) c->err = "selftest: " + v->err;
+    pgrc_verify_end(v);
+    return e;
+}
+
+// the next pgrc_verify_begin of the process (of THIS library: tests call its pgrc_verify_* entries) cuts its keys to `bits` bits
+extern "C" void pgrc_selftest_verify_mask_next_begin(uint32_t bits) { pgrc_vf_mask_next_begin(bits); }

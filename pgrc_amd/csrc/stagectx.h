@@ -1,8 +1,8 @@
 // stagectx.h -- the stage handle: what every encoder and decoder stage beside the matcher needs of the device.  A stage is a
 // PgrcDev (device, stream, error text) with two page-locked staging buffers, the events that guard their reuse, a flag word
 // for device-side findings and a grow-only scratch for the shared scan.  The decode context (decctx.h) is one with the decoder's
-// state on top; the overlap search (pgovl.hip) and the read sets (rsetsctx.h) are one with their own buffers on top; the
-// assembly (pgasm.hip) and the reads list (rlistctx.h) keep a decode context.  DESIGN.md 4.22.
+// state on top; the overlap search (pgovl.hip), the read sets (rsetsctx.h) and the verifier (verifyctx.h) are one with their
+// own buffers on top; the assembly (pgasm.hip) and the reads list (rlistctx.h) keep a decode context.  DESIGN.md 4.22.
 #pragma once
 
 #include <string.h>

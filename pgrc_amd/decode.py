@@ -537,6 +537,12 @@ class PgRCDecoder:
                        rev_compl_pair_file=revComplPairFile)
         return tuple(self.rows(p) for p in range(1 if singleReadsMode else 2))
 
+    def verifier(self, kind: int = 0):
+        """a pgrc_amd.Verifier of this job (text, lists and order set): IN_ORDER for an ORD job and MULTISET for SE and PE
+        by default (include/pgrc_verify.h).  Close it before the job changes or the decoder closes."""
+        from .verify import Verifier
+        return Verifier(self, kind)
+
     def close(self) -> None:
         if self._h:
             lib.pgrc_decode_destroy(self._h)
