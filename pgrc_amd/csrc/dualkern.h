@@ -41,6 +41,17 @@
 // stop still holds after a later rewind of the other strand.  Everything else is replayed in seed order, so ties, limits
 // and U (an upper bound of the falses of the reference's run: skip mode adds nothing to it) come out as before.  F_SEQ never
 // skips.  tests/roundskip_model.py restates the rule; tests/test_round_skip_rule.py holds it to the reference's order.
+//
+// The refill.  A wave reserves a.chunk reads at a time from one work counter, stages SW of them in LDS (lanes 0 .. SW - 1: a
+// full line per row and side item) and hands them to the lanes that have finished their read; a wave that was told once that
+// the counter is past n never asks it again (`dry`: otherwise every iteration of the drain in which a lane finishes is a
+// round trip of the whole wave to the one word all waves share -- a fifth of C2's kernel).  The stage's loads are six to
+// eight dependent round trips in front of the iteration's gathers (the register cap lets the compiler issue them two at a
+// time only).  Bringing them down to one (all 64 lanes, straight into LDS) and hiding that one behind the gathers (the stage
+// decided an iteration ahead) was built and measured: nothing at C3 beyond the run-to-run spread -- a waiting wave is
+// covered by the five others of its SIMD -- and a loss at -M 3; in registers it spills.  Not kept: DESIGN.md appendix A,
+// profiles/stage_ahead_ab.txt, profiles/stage_ahead_kernel_resources.txt.  tests/test_gpu_dual_staging.py holds the refill
+// to the oracle at chunk and stage boundaries.
 #pragma once
 
 #include "ctx.h"
@@ -98,6 +109,7 @@ k_copmem_match_dual(const DualArgs a) {
     __shared__ ulonglong2 hdR_lds[MATCH_TPB];    // the RC head of a lane's current seed, waiting for the forward bucket to finish
     const uint32_t wv = threadIdx.x >> 6;
     uint32_t wbeg = 0, wend = 0, wnext = 0;
+    bool dry = false;                            // the work counter is past n: no chunk is left to reserve
     hash_lut_init(lut);
     const int H = ((int)a.L / 8) * 8;
     const uint32_t nseeds = (a.L - a.K) / a.k2 + 1;
@@ -171,7 +183,10 @@ k_copmem_match_dual(const DualArgs a) {
         // ---- refill (as in k_copmem_match_sm, staged)
         const unsigned long long need = __ballot(mode == M_NEED);
         if (need) {
-            if (cnext == cend) {
+            // (dry: the counter only grows, so a wave that was told "past n" once never asks again.  Without it every
+            // iteration of the drain in which a lane finishes is one more round trip of the whole wave to the one word all
+            // waves share -- up to 64 per wave: 1.3 ms of C2's 6.4 ms, profiles/stage_ahead_ab.txt.)
+            if (cnext == cend && !dry) {
                 unsigned long long base = 0;
                 if (lane == 0) base = atomicAdd(a.work, (unsigned long long)a.chunk);
                 base = __shfl(base, 0, 64);
@@ -181,6 +196,7 @@ k_copmem_match_dual(const DualArgs a) {
                 // last they are what the last waves still work on when the others have run dry (profiles/r04_from_end_ab.txt)
                 cnext = __builtin_amdgcn_readfirstlane((uint32_t)a.n - hi_);
                 cend = __builtin_amdgcn_readfirstlane((uint32_t)a.n - lo_);
+                dry = cnext == cend;
             }
             if (wnext == wend && cnext != cend) {
                 const uint32_t nst = min((uint32_t)SW, cend - cnext);
