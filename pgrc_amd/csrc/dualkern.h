@@ -52,6 +52,18 @@
 // covered by the five others of its SIMD -- and a loss at -M 3; in registers it spills.  Not kept: DESIGN.md appendix A,
 // profiles/stage_ahead_ab.txt, profiles/stage_ahead_kernel_resources.txt.  tests/test_gpu_dual_staging.py holds the refill
 // to the oracle at chunk and stage boundaries.
+//
+// The entry walk.  A load brings a lane up to two entries of a bucket -- a head holds entry 0 and, of a two-entry bucket,
+// entry 1; a fetch from ent[] brings a 16-byte pair -- and the lane goes over both in the iteration that brought them: the
+// position test and the fingerprint reject an entry within a few instructions, without a load, and the first entry they
+// let through goes down the chain (verify cache, then the judge or M_VERIFY).  Only an entry that waits behind one that went
+// to M_VERIFY still costs an iteration of its own (`pend_e`).  Before, every entry took an iteration: 312 M of C3's 1 488 M
+// lane-iterations per launch moved a lane to an entry it already held (profiles/entry_walk_mix.txt).  The entries, their
+// order and the limit each one meets are the same, and so are all counters.  Wider fetches (four or six entries) were
+// measured and are not kept.  The refill makes its LDS addresses from a copy of the thread index that
+// the compiler cannot see through, so that they are not kept in registers through every iteration: the C3 instance is at 70
+// registers (77 before).  tests/test_gpu_dual_entry_walk.py holds the walk to the oracle and to the parent kernel's counters
+// on planted repeat families.
 #pragma once
 
 #include "ctx.h"
@@ -107,7 +119,6 @@ k_copmem_match_dual(const DualArgs a) {
     __shared__ uint8_t stg_c[MATCH_TPB / 64][SW], stg_f[MATCH_TPB / 64][SW];
     __shared__ uint32_t stg_n[MATCH_TPB / 64][SW];
     __shared__ ulonglong2 hdR_lds[MATCH_TPB];    // the RC head of a lane's current seed, waiting for the forward bucket to finish
-    const uint32_t wv = threadIdx.x >> 6;
     uint32_t wbeg = 0, wend = 0, wnext = 0;
     bool dry = false;                            // the work counter is past n: no chunk is left to reserve
     hash_lut_init(lut);
@@ -149,6 +160,11 @@ k_copmem_match_dual(const DualArgs a) {
     pos_t cand_p = 0;
     uint64_t pend_e = 0;
     constexpr int PWN = ((NW + 1 + 3) / 4) * 4;
+    // entries a fetch brings and a lane walks over in one iteration (even).  Two: a 16-byte pair, as a head holds.  Four and six
+    // (two and three pairs per fetch) were measured: entry fetches 167 M -> 133 M / 129 M per launch at C3, the kernel no faster
+    // than with two (four) or as slow as without the walk (six), and six spills in the 64-bit-position instances
+    // (profiles/entry_walk_ab.txt, profiles/entry_walk_kernel_resources.txt).
+    constexpr int WALK = 2;
 #define DK_SI() (sr & 0xFFu)
 #define DK_RQ() ((sr >> 8) & 0xFFu)
 #define DK_RCL(s) ((sr >> (16u + 8u * (s))) & 0xFFu)
@@ -183,6 +199,12 @@ k_copmem_match_dual(const DualArgs a) {
         // ---- refill (as in k_copmem_match_sm, staged)
         const unsigned long long need = __ballot(mode == M_NEED);
         if (need) {
+            // (The refill is the rare path.  Its LDS addresses, lane masks and the cache-clearing constant are made here, from
+            // a copy of the thread index the compiler cannot see through: otherwise it keeps them in registers through every
+            // iteration -- seven registers of the C3 instance, which the entry walk needs.)
+            uint32_t tq = threadIdx.x;
+            __asm__ volatile("" : "+v"(tq));
+            const uint32_t wv = tq >> 6, lane = tq & 63u;
             // (dry: the counter only grows, so a wave that was told "past n" once never asks again.  Without it every
             // iteration of the drain in which a lane finishes is one more round trip of the whole wave to the one word all
             // waves share -- up to 64 per wave: 1.3 ms of C2's 6.4 ms, profiles/stage_ahead_ab.txt.)
@@ -232,7 +254,7 @@ k_copmem_match_dual(const DualArgs a) {
                         uint32_t epoch = (DK_EPOCH() + 1u) & ((1u << EPOCH_BITS) - 1u);
                         if (epoch == 0) {
 #pragma unroll
-                            for (int k = 0; k < VC_SLOTS; k++) vcache[k][threadIdx.x] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+                            for (int k = 0; k < VC_SLOTS; k++) vcache[k][tq] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
                             epoch = 1;
                         }
                         ll = (L0 + 1u) | ((L0 + 1u) << 9) | (epoch << 18);
@@ -253,10 +275,13 @@ k_copmem_match_dual(const DualArgs a) {
 
         const uint32_t m0 = mode;
         // ---- this iteration's loads
-        ulonglong2 hdF = make_ulonglong2(HEAD_EMPTY, HEAD_EMPTY);
-        uint64_t v = 0;
+        // what the lane has at hand in the consume phase: the head of the bucket to open (e[0], e[1]), then the nh entries of
+        // the bucket that it holds, in bucket order: e[0 .. nh) -- a head's one or two, what a fetch brought, or the entry kept
+        // behind a verified one
+        uint64_t e[WALK];
+        uint32_t nh = 0;
         bool counted_ent = false;
-        uint32_t ncand_it = 0, nprobe_it = 0;
+        uint32_t nprobe_it = 0;
         bool n_redo_it = false, rew = false, skip_new = false;
         if (m0 == M_PROBE) {
             // the seed's window, cut out of the read's LDS copy: symbols s .. s + K - 1
@@ -275,22 +300,33 @@ k_copmem_match_dual(const DualArgs a) {
                 h = hash_fp_window_n<KQ>(w[0], w[1], w[2], w[3], a.K, lut, &fp_read, npw, s) & a.mask;
             else
                 h = hash_fp_window<KQ>(w[0], w[1], w[2], w[3], a.K, lut, &fp_read) & a.mask;
-            ulonglong2 hr = make_ulonglong2(HEAD_EMPTY, HEAD_EMPTY);
+            ulonglong2 hdF = make_ulonglong2(HEAD_EMPTY, HEAD_EMPTY), hr = hdF;
             // (the non-temporal hint: in-context A/B 63.4 -> 62.6 ms at C3; on the entry pairs it costs 1 %, on the text windows nothing)
             if (fl & F_ACT0) hdF = dk_ld_nt(&a.head[0][head_slot(h, a.hsh)]);
             if (fl & F_ACT1) hr = dk_ld_nt(&a.head[1][head_slot(h, a.hsh)]);
             hdR_lds[threadIdx.x] = hr;
             nprobe_it = ((fl & F_ACT0) ? 1u : 0u) + ((fl & F_ACT1) ? 1u : 0u);
+            e[0] = (fl & F_ACT0) ? hdF.x : hr.x;                     // the seed's first bucket: the forward one if that strand is active
+            e[1] = (fl & F_ACT0) ? hdF.y : hr.y;
         } else if (m0 == M_ENTRY) {
-            if (DK_PEND()) {
-                v = pend_e;
+            if (DK_PEND()) {                                         // back from a verification: the entry kept behind the verified one
+                e[0] = pend_e;
+                nh = 1;
                 jn &= ~(1u << 9);
             } else {
-                const uint32_t j = DK_J(), nb = DK_NB();
-                const U64x2A8 q = *reinterpret_cast<const U64x2A8 *>((DK_X() ? a.ent[1] : a.ent[0]) + lo + j - 1);
-                v = q.x;
-                pend_e = q.y;
-                jn = (jn & ~(1u << 9)) | ((j + 1 < nb ? 1u : 0u) << 9);
+                // ONE fetch for the bucket's next entries, up to WALK of them from entry j on: 16-byte pairs as far as the
+                // lane's bucket goes (as before, a lane reads at most one entry past its bucket's last)
+                const uint32_t j = DK_J(), rem = DK_NB() - j;
+                const uint64_t *src = (DK_X() ? a.ent[1] : a.ent[0]) + lo + j - 1;
+#pragma unroll
+                for (int k = 0; k < WALK; k += 2) {
+                    if ((uint32_t)k < rem) {
+                        const U64x2A8 q = *reinterpret_cast<const U64x2A8 *>(src + k);
+                        e[k] = q.x;
+                        e[k + 1] = q.y;
+                    }
+                }
+                nh = min(rem, (uint32_t)WALK);
                 counted_ent = true;
             }
         }
@@ -303,10 +339,7 @@ k_copmem_match_dual(const DualArgs a) {
         uint32_t next = m0;
         bool bdone = false;           // the current strand's bucket is finished
         bool op = false, tp = false, jp = false;                     // pending: a bucket to open, an entry to look at, an alignment to judge
-        ulonglong2 oh = make_ulonglong2(HEAD_EMPTY, HEAD_EMPTY);
-        uint64_t te = 0;
         uint32_t jmh = 0, jmt = 0;
-        pos_t jpos = 0;
         if (m0 == M_VERIFY) {
             const uint32_t x = DK_X();
             uint32_t pw[PWN];
@@ -351,16 +384,12 @@ k_copmem_match_dual(const DualArgs a) {
                                                    : (mh | (mt << 8) | (x << 16) | (epoch << 17)));
             jmh = mh;
             jmt = mt;
-            jpos = cand_p;
             jp = true;
         } else if (m0 == M_ENTRY) {
-            jn++;                                                    // j++ (j <= 13: no carry into nb)
-            te = v;
             tp = true;
         } else if (m0 == M_PROBE) {
             const uint32_t x = (fl & F_ACT0) ? 0u : 1u;
             jn = x << 8;
-            oh = x == 0u ? hdF : hdR_lds[threadIdx.x];
             op = true;
         }
 #pragma nounroll
@@ -368,7 +397,7 @@ k_copmem_match_dual(const DualArgs a) {
             if (op) {                                                // open the bucket of strand x for the current seed
                 op = false;
                 const uint32_t x = DK_X();
-                const uint32_t cnt = head_count(oh);
+                const uint32_t cnt = head_count(make_ulonglong2(e[0], e[1]));
                 if (!cnt) {
                     bdone = true;
                 } else if (!(fl & (F_SEQ | F_SKIP)) && DK_U(x) > budget && cnt > PGRC_TRUNC_BUCKET) {
@@ -382,54 +411,79 @@ k_copmem_match_dual(const DualArgs a) {
                     uint32_t nb = cnt;
                     if ((fl & F_SEQ) && DK_U(x) > budget) nb = min(nb, PGRC_TRUNC_BUCKET);   // :510-514
                     if (DK_RQ() < a.k1 && (cnt >= PGRC_BUCKET_CAP || nb < cnt)) fl |= (x == 0u ? (uint32_t)F_DIRTY0 : (uint32_t)F_DIRTY1);
-                    pend_e = oh.y;
-                    lo = (pos_t)(oh.y & W1_BASE_MASK);
-                    jn = 1u | (nb << 4) | (x << 8) | ((cnt == 2 && nb > 1) ? 1u << 9 : 0u);    // j = 1; entry 1 of a two-entry bucket sits in the head
-                    te = oh.x & ENT_MASK;
+                    lo = (pos_t)(e[1] & W1_BASE_MASK);
+                    jn = (nb << 4) | (x << 8);                       // j = 0
+                    e[0] &= ENT_MASK;                                // what a head holds: entry 0, and entry 1 of a two-entry bucket
+                    nh = cnt == 2u ? 2u : 1u;
                     tp = true;
                 }
             }
             bool ap = false;                                         // an entry was examined: what follows it
-            if (tp) {                                                // an entry of the current strand's bucket
-                tp = false;
-                ap = true;
+            // the entries at hand (a head's one or two, what a fetch brought, the one kept behind a verified entry), in order:
+            // a lane walks over those that lie outside the text for this seed or that the fingerprint rejects, up to the
+            // first that passes; that one goes down the rest of the chain.  (A limit only changes through an acceptance, and
+            // the walk ends in front of one: eff() is the same for every entry of a walk.  The loop stays in the wave's common
+            // control flow, so the candidates are counted on the scalar side; it ends when no lane has an entry left.)
+            bool pass = false;                                       // ... and its position is cand_p
+            {
                 const uint32_t x = DK_X(), si = DK_SI();
                 const uint32_t s = si * a.k2;
-                bool inside;                                         // :517-520
-                pos_t p;
-                if (POS64) {
-                    const uint64_t sp = te >> PGRC_FP_BITS;
-                    inside = (uint64_t)s <= sp && sp - s + a.L <= a.G;
-                    p = (pos_t)(sp - s);
-                } else {                                             // (G + 256 < 2^32: positions, and position + L, fit 32 bits)
-                    const uint32_t sp = (uint32_t)(te >> PGRC_FP_BITS);
-                    inside = s <= sp && sp - s + a.L <= (uint32_t)a.G;
-                    p = (pos_t)(sp - s);
-                }
-                if (inside) {
-                    ncand_it++;
-                    const uint32_t xr = ((uint32_t)te ^ fp_read) & ((1u << PGRC_FP_BITS) - 1u);
-                    const int fpc = __popc((xr | (xr >> 1)) & fpm_tab[si]);   // a lower bound of the head count
-                    if (fpc > eff(x)) {
-                        const uint32_t u = ((fl & F_SEQ) || fpc > DK_L0()) ? 1u : 2u;   // (sequential: a certain head reject)
-                        if (!(fl & F_SKIP)) uu += u << (16u * x);
-                    } else {
-                        const uint32_t epoch = DK_EPOCH();
-                        const uint2 cv = vcache[((uint32_t)p * 0x9E3779B1u + x) >> (32 - VC_BITS)][threadIdx.x];
-                        const bool hit = POS64 ? (cv.x == (uint32_t)p && (cv.y >> 20) == epoch && ((cv.y >> 19) & 1u) == x &&
-                                                  ((cv.y >> 11) & 0xFFu) == (uint32_t)((uint64_t)p >> 32))
-                                               : (cv.x == (uint32_t)p && (cv.y >> 17) == epoch && ((cv.y >> 16) & 1u) == x);
-                        if (hit) {
-                            jmh = cv.y & 0xFFu;
-                            jmt = (cv.y >> 8) & (POS64 ? 0x7u : 0xFFu);
-                            jpos = p;
-                            jp = true;
-                        } else {
-                            cand_p = p;
-                            next = M_VERIFY;
-                            ap = false;
+                const int lim = eff(x);
+                const uint32_t fpm = tp ? fpm_tab[si] : 0u;
+                bool walk = tp;
+                ap = tp;
+                tp = false;
+#pragma unroll
+                for (int k = 0; k < WALK; k++) {
+                    const bool live = walk && (uint32_t)k < nh;
+                    if (!__any(live)) break;
+                    bool inside = false;                             // :517-520
+                    if (live) {
+                        jn++;                                        // j++ (j <= 13: no carry into nb)
+                        pos_t pk;
+                        if (POS64) {
+                            const uint64_t sp = e[k] >> PGRC_FP_BITS;
+                            inside = (uint64_t)s <= sp && sp - s + a.L <= a.G;
+                            pk = (pos_t)(sp - s);
+                        } else {                                     // (G + 256 < 2^32: positions, and position + L, fit 32 bits)
+                            const uint32_t sp = (uint32_t)(e[k] >> PGRC_FP_BITS);
+                            inside = s <= sp && sp - s + a.L <= (uint32_t)a.G;
+                            pk = (pos_t)(sp - s);
+                        }
+                        if (inside) {
+                            const uint32_t xr = ((uint32_t)e[k] ^ fp_read) & ((1u << PGRC_FP_BITS) - 1u);
+                            const int fpc = __popc((xr | (xr >> 1)) & fpm);   // a lower bound of the head count
+                            if (fpc > lim) {
+                                const uint32_t u = ((fl & F_SEQ) || fpc > DK_L0()) ? 1u : 2u;   // (sequential: a certain head reject)
+                                if (!(fl & F_SKIP)) uu += u << (16u * x);
+                            } else {
+                                walk = false;
+                                pass = true;
+                                cand_p = pk;
+                                if (k + 1 < WALK && (uint32_t)k + 1u < nh) {    // the entry behind it waits for the return from M_VERIFY
+                                    pend_e = e[k + 1 < WALK ? k + 1 : k];
+                                    jn |= 1u << 9;
+                                }
+                            }
                         }
                     }
+                    n_cand += (uint32_t)__popcll(__ballot(inside));
+                }
+            }
+            if (pass) {                                              // an entry inside the text that the fingerprint lets through
+                const uint32_t x = DK_X();
+                const uint32_t epoch = DK_EPOCH();
+                const uint2 cv = vcache[((uint32_t)cand_p * 0x9E3779B1u + x) >> (32 - VC_BITS)][threadIdx.x];
+                const bool hit = POS64 ? (cv.x == (uint32_t)cand_p && (cv.y >> 20) == epoch && ((cv.y >> 19) & 1u) == x &&
+                                          ((cv.y >> 11) & 0xFFu) == (uint32_t)((uint64_t)cand_p >> 32))
+                                       : (cv.x == (uint32_t)cand_p && (cv.y >> 17) == epoch && ((cv.y >> 16) & 1u) == x);
+                if (hit) {
+                    jmh = cv.y & 0xFFu;
+                    jmt = (cv.y >> 8) & (POS64 ? 0x7u : 0xFFu);
+                    jp = true;
+                } else {
+                    next = M_VERIFY;
+                    ap = false;
                 }
             }
             if (jp) {                                                // a verified alignment of the current strand (head count jmh, tail count jmt)
@@ -455,8 +509,8 @@ k_copmem_match_dual(const DualArgs a) {
                 } else if (m <= eff(x)) {
                     set_cur(x, (uint32_t)m);
                     set_lim(x, m - 1);
-                    if (x == 0u) { best0 = jpos; fl |= F_FOUND0; }
-                    else { best1 = jpos; fl |= F_FOUND1; }
+                    if (x == 0u) { best0 = cand_p; fl |= F_FOUND0; }
+                    else { best1 = cand_p; fl |= F_FOUND1; }
                     if (m == 0) {                                    // m <= min_mismatches: this strand's query returns
                         fl &= ~(x == 0u ? (uint32_t)F_ACT0 : (uint32_t)F_ACT1);
                         if (x == 0u) fl |= F_FWDEXACT;               // ... and the RC pass would skip the read
@@ -475,7 +529,9 @@ k_copmem_match_dual(const DualArgs a) {
             if (chain) {
                 bdone = false;
                 jn = 1u << 8;
-                oh = hdR_lds[threadIdx.x];
+                const ulonglong2 hr = hdR_lds[threadIdx.x];
+                e[0] = hr.x;
+                e[1] = hr.y;
                 op = true;
             }
         }
@@ -543,7 +599,6 @@ k_copmem_match_dual(const DualArgs a) {
         }
         n_ent += (uint32_t)__popcll(__ballot(counted_ent));
         n_ver += (uint32_t)__popcll(__ballot(m0 == M_VERIFY));
-        n_cand += (uint32_t)__popcll(__ballot(ncand_it >= 1)) + (uint32_t)__popcll(__ballot(ncand_it >= 2));
         const bool fin = next == M_NEED && m0 <= M_VERIFY;
         if (fin) {
             // the read is finished: forward wins ties, RC must be strictly better (ReadsMatchers.cpp:437-447, both passes)
