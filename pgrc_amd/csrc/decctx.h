@@ -1,11 +1,11 @@
 // decctx.h -- the decode context of include/pgrc_decode.h and the helpers its sources share: decode.hip (the reads
-// rebuild), restore.hip (the restore of the matched pseudogenomes), pairpos.hip (the pair positions of the paired ORD mode),
-// pairorder.hip (the pair order of the paired non-ORD mode) and listarchive.hip (the archive form of a list's mismatch streams).
-// What it shares with the other stages -- the stream, the staging buffers, the copies through them -- is stagectx.h's PgrcStage.
+// rebuild) and restore.hip (the restore of the matched pseudogenomes).  What it shares with the other stages -- the stream, the
+// staging buffers, the copies through them -- is stagectx.h's PgrcStage.  The exported entry points of the three list codings
+// (pairpos.hip, pairorder.hip, listarchive.hip) take a decode context too: it holds one state of each (codingctx.h), which
+// they hand to coders that know the stage and that state alone.
 #pragma once
 
-#include "pgrc_decode.h"
-#include "stagectx.h"
+#include "codingctx.h"
 
 #define DEC_TPB 256
 #define DEC_TEXT_PAD 64         // zero bytes after the text: aligned 16-byte loads past a window's end stay inside
@@ -45,38 +45,20 @@ struct pgrc_decode_ctx : PgrcStage {
     DevBuf rs_mapped, rs_marks, rs_vals, rs_ptr, rs_bsum;   // the mapped parts and streams; per-mark arrays; values; pointers; block counts
     DevBuf rs_coded, rs_join;   // pgrc_decode_set_mapped_text_coded: the coded bytes and the joined text they decode to
     pgrc_decode_restore_timing rtm{};
-    // the pair-position coding (pairpos.hip): the uploaded input, the sort's records (and values, W = 8) in turn, per-rank
-    // and per-far-pair arrays, the device-side output, scan scratch; pp_sort: the scratch of radix.hip's sort
-    DevBuf pp_in, pp_rec[2], pp_val[2], pp_rank, pp_far, pp_out, pp_bsum;
-    DevBuf pp_sort;
-    PhaseEvents<6> pp_ev;
-    bool have_pp_timing = false;
-    pgrc_pairpos_timing ptm{};
-    // the pair-order coding (pairorder.hip): the joined orgIdx, rev, per-entry and per-pair arrays, the device-side streams,
-    // scan scratch and the two error words
-    DevBuf po_in, po_rev, po_ent, po_pair, po_out, po_bsum;
-    PhaseEvents<11> po_ev;
-    bool have_po_timing = false;
-    pgrc_pairorder_timing potm{};
-    // the archive form of the mismatch streams (listarchive.hip): the uploaded streams, the flag scan, the counts (decode),
-    // the mismatch-list starts (encode), the count matrix and its scan scratch, the per-count words, the device-side block
-    DevBuf la_in, la_inc, la_cnt, la_mcum, la_mat, la_fold, la_small, la_out;
-    PhaseEvents<5> la_ev;
-    bool have_la_timing = false;
-    pgrc_list_archive_timing latm{};
+    // the list codings behind pgrc_pairpos_*, pgrc_pairorder_* and pgrc_list_archive_* (codingctx.h)
+    PgrcPairPos pp;
+    PgrcPairOrder po;
+    PgrcListArchive la;
 };
 
-// decode.hip: pgrc_decode_create without a read length, for the stages that keep a decode context for what it holds and runs
-// and give every call its own length (pgasm.hip: the text; rlist.hip: the list archive, the pair order, the pair positions)
+// decode.hip: pgrc_decode_create without a read length, for the assembly (pgasm.hip), which keeps a decode context for the
+// text it holds and gives every call its own length
 int pgrc_decode_create_on(int32_t device, pgrc_decode_ctx **out);
 // pairpos.hip: the file-major positions of `s` as n_total u64 at d_out (device, on d->stream; synchronised on return);
-// fills d->ptm but for ms_download / ms_call
+// fills d->pp.tm but for ms_download / ms_call
 int pgrc_pairpos_decode_device(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint64_t *d_out);
-int pgrc_pairpos_check_streams(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s);   // the checks that need no device (PGRC_E_PARAM)
-void pgrc_pairpos_release(pgrc_decode_ctx *d);     // the buffers and events above (pgrc_decode_destroy)
-void pgrc_pairorder_release(pgrc_decode_ctx *d);   // pairorder.hip: its buffers and events (pgrc_decode_destroy)
-void pgrc_la_release(pgrc_decode_ctx *d);          // listarchive.hip: its buffers and events (pgrc_decode_destroy)
-// listarchive.hip: the mismatch tables of list `l` (mcum, moff, msym, nmis) from the archive-form streams `s`, on d->stream;
+int pgrc_pairpos_check_streams(PgrcStage *d, const pgrc_pairpos_streams *s);   // the checks that need no device (PGRC_E_PARAM)
+// listarchive.hip: the mismatch tables of list `l` (mcum, moff, msym, nmis) from the archive-form streams `s`, on d->stream with d->la;
 // device-side findings (DEC_F_MISOFF, DEC_F_MISSYM) go to d->flag, which the caller reads (pgrc_decode_add_list_archive)
 int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list_archive_streams *s);
 // decode.hip: pgrc_decode_add_list, with the mismatches from `arch` when it is given

@@ -382,9 +382,9 @@ void pgrc_decode_destroy(pgrc_decode_ctx *d) {
     dec_free_all(dec_bufs(d));
     for (hipEvent_t ev : {d->ev_made[0], d->ev_made[1], d->ev_k0[0], d->ev_k0[1], d->ev_a, d->ev_b})
         if (ev) (void)hipEventDestroy(ev);
-    pgrc_pairpos_release(d);
-    pgrc_pairorder_release(d);
-    pgrc_la_release(d);
+    d->pp.release();
+    d->po.release();
+    d->la.release();
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     pgrc_stage_close(d);
     delete d;
@@ -605,10 +605,10 @@ int pgrc_decode_set_order_pair_streams(pgrc_decode_ctx *d, const pgrc_pairpos_st
     d->ord.paired = 1;
     d->ord.rev_compl_pair_file = rev_compl_pair_file;
     d->have_order = true;
-    d->ptm.ms_download = 0;
-    d->ptm.bytes_down = 0;
-    d->ptm.ms_call = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    d->have_pp_timing = true;
+    d->pp.tm.ms_download = 0;
+    d->pp.tm.bytes_down = 0;
+    d->pp.tm.ms_call = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    d->pp.have_timing = true;
     return PGRC_OK;
 }
 

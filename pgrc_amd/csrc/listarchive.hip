@@ -32,7 +32,7 @@
 static_assert(LA_TILE == PGRC_LIST_ARCHIVE_TILE, "the header states the tile");
 static_assert(LA_WSPAN <= 0xFFFF && LA_TILE <= 0xFFFF, "the LDS counters are 16 bits wide");
 
-// the words of la_small
+// the words of PgrcListArchive::small
 #define LA_S_TOTAL 0            // u64[256]: entries per count
 #define LA_S_START 256          // u64[256]: first byte of destination c among the destinations
 #define LA_S_FIRST 512          // u64[256]: the scanned matrix value of (c, tile 0) = entries with a smaller count
@@ -298,25 +298,20 @@ static __global__ void __launch_bounds__(LA_TPB) k_la_gather(const uint8_t *__re
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int la_fail(pgrc_decode_ctx *d, const char *who, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, std::string("list archive (") + who + "): " + msg); }
+static int la_fail(PgrcStage *d, const char *who, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, std::string("list archive (") + who + "): " + msg); }
 
-void pgrc_la_release(pgrc_decode_ctx *d) {
-    dec_free_all({&d->la_in, &d->la_inc, &d->la_cnt, &d->la_mcum, &d->la_mat, &d->la_fold, &d->la_small, &d->la_out});
-    d->la_ev.release();
-}
-
-// count matrix of the n counts at `cnt`, scanned; the per-count words in la_small and (synchronised) at h_small
-static int la_matrix(pgrc_decode_ctx *d, const uint8_t *cnt, uint64_t n, uint64_t *ntiles_out, uint64_t (&h_small)[LA_S_BINS]) {
+// count matrix of the n counts at `cnt`, scanned; the per-count words in `small` and (synchronised) at h_small
+static int la_matrix(PgrcStage *d, PgrcListArchive &st, const uint8_t *cnt, uint64_t n, uint64_t *ntiles_out, uint64_t (&h_small)[LA_S_BINS]) {
     const uint64_t ntiles = std::max<uint64_t>(1, (n + LA_TILE - 1) / LA_TILE), cells = ntiles * 256;
     int e;
-    if ((e = pgrc_bufs_unpooled(d, {{&d->la_mat, cells * 4 + 16}, {&d->la_fold, pgrc_ps_scan_blocks(cells) * 4 + 16}}))) return e;
-    uint32_t *mat = (uint32_t *)d->la_mat.p;
+    if ((e = pgrc_bufs_unpooled(d, {{&st.mat, cells * 4 + 16}, {&st.fold, pgrc_ps_scan_blocks(cells) * 4 + 16}}))) return e;
+    uint32_t *mat = (uint32_t *)st.mat.p;
     hipLaunchKernelGGL(k_la_count, dim3((uint32_t)ntiles), dim3(LA_TPB), 0, d->stream, cnt, n, ntiles, mat);
     HIP_TRY(d, hipGetLastError());
-    if ((e = pgrc_ps_scan_u32(d, mat, cells, (uint32_t *)d->la_fold.p))) return e;
-    hipLaunchKernelGGL(k_la_starts, dim3(1), dim3(256), 0, d->stream, (const uint32_t *)mat, ntiles, n, (unsigned long long *)d->la_small.p);
+    if ((e = pgrc_ps_scan_u32(d, mat, cells, (uint32_t *)st.fold.p))) return e;
+    hipLaunchKernelGGL(k_la_starts, dim3(1), dim3(256), 0, d->stream, (const uint32_t *)mat, ntiles, n, (unsigned long long *)st.small.p);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, hipMemcpyAsync(h_small, d->la_small.p, sizeof(h_small), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipMemcpyAsync(h_small, st.small.p, sizeof(h_small), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     *ntiles_out = ntiles;
     return PGRC_OK;
@@ -358,15 +353,15 @@ struct LaEncoded {
 };
 
 // the device side of the encoder: cnt (n), sym and off (m each) lie in device memory, complete on d->stream; the block is
-// written at ob (la_layout; room for at_nz + n + 16 bytes).  The caller has recorded la_ev[0].
-static int la_encode_device(pgrc_decode_ctx *d, const uint8_t *cnt, const uint8_t *sym, const uint8_t *off, uint64_t n, uint64_t m, bool fast, uint8_t *ob, LaEncoded *res) {
+// written at ob (la_layout; room for at_nz + n + 16 bytes).  The caller has recorded ev[0].
+static int la_encode_device(PgrcStage *d, PgrcListArchive &st, const uint8_t *cnt, const uint8_t *sym, const uint8_t *off, uint64_t n, uint64_t m, bool fast, uint8_t *ob, LaEncoded *res) {
     static const char *who = "encode";
     int e;
     const LaLayout lay = la_layout(n, m);
-    if ((e = pgrc_bufs_unpooled(d, {{&d->la_inc, n * 4 + 16}, {&d->la_mcum, (n + 1) * 8}, {&d->la_small, LA_S_WORDS * 8}}))) return e;
-    uint32_t *inc = (uint32_t *)d->la_inc.p;
-    uint64_t *mcum = (uint64_t *)d->la_mcum.p;
-    unsigned long long *small = (unsigned long long *)d->la_small.p;
+    if ((e = pgrc_bufs_unpooled(d, {{&st.inc, n * 4 + 16}, {&st.mcum, (n + 1) * 8}, {&st.small, LA_S_WORDS * 8}}))) return e;
+    uint32_t *inc = (uint32_t *)st.inc.p;
+    uint64_t *mcum = (uint64_t *)st.mcum.p;
+    unsigned long long *small = (unsigned long long *)st.small.p;
     HIP_TRY(d, hipMemsetAsync(small, 0, LA_S_WORDS * 8, d->stream));
 
     // flags, non-zero counts, mismatch-list starts
@@ -381,13 +376,13 @@ static int la_encode_device(pgrc_decode_ctx *d, const uint8_t *cnt, const uint8_
     }
     if ((e = dec_scan<false>(d, XfU8{cnt}, n, 0, mcum))) return e;
     HIP_TRY(d, hipMemcpyAsync(&m_dev, mcum + n, 8, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, d->la_ev.record(1, d->stream));
+    HIP_TRY(d, st.ev.record(1, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     // nothing below reads a code or an offset before the counts are known to describe the streams
     if (m_dev != m) return la_fail(d, who, "n_mismatches is " + std::to_string(m) + ", the counts sum to " + std::to_string(m_dev));
 
     // symbols
-    HIP_TRY(d, d->la_ev.record(2, d->stream));
+    HIP_TRY(d, st.ev.record(2, d->stream));
     uint64_t h_bins[8] = {};
     if (m) {
         // 2048 blocks at most, and each bin of a block below 2^32: a block sees m / blocks + 4096 codes at most
@@ -412,7 +407,7 @@ static int la_encode_device(pgrc_decode_ctx *d, const uint8_t *cnt, const uint8_
         hipLaunchKernelGGL(k_la_recode, dim3(pp_grid((m >> 4) + 1)), dim3(PP_TPB), 0, d->stream, (const uint8_t *)sym, m, lo, hi, ob + lay.at_sym);
         HIP_TRY(d, hipGetLastError());
     }
-    HIP_TRY(d, d->la_ev.record(3, d->stream));
+    HIP_TRY(d, st.ev.record(3, d->stream));
 
     // the split
     uint64_t h_small[LA_S_BINS] = {};
@@ -422,15 +417,15 @@ static int la_encode_device(pgrc_decode_ctx *d, const uint8_t *cnt, const uint8_
         if (m) HIP_TRY(d, hipMemcpyAsync(ob + lay.at_dest, off, m, hipMemcpyDeviceToDevice, d->stream));
     } else if (n) {
         uint64_t ntiles = 0;
-        if ((e = la_matrix(d, cnt, n, &ntiles, h_small))) return e;
+        if ((e = la_matrix(d, st, cnt, n, &ntiles, h_small))) return e;
         if (h_small[LA_S_TOTAL + 255]) return la_fail(d, who, std::to_string(h_small[LA_S_TOTAL + 255]) + " entries with 255 mismatches (the reference's map has 255 elements)");
         for (uint32_t c = 1; c < 255; c++)
             if (h_small[LA_S_TOTAL + c]) limit = c;
-        if (m) hipLaunchKernelGGL(k_la_scatter, dim3((uint32_t)ntiles), dim3(LA_TPB), 0, d->stream, (const uint8_t *)cnt, n, ntiles, (const uint32_t *)d->la_mat.p,
+        if (m) hipLaunchKernelGGL(k_la_scatter, dim3((uint32_t)ntiles), dim3(LA_TPB), 0, d->stream, (const uint8_t *)cnt, n, ntiles, (const uint32_t *)st.mat.p,
                                   (const unsigned long long *)small, (const uint64_t *)mcum, (const uint8_t *)off, ob + lay.at_dest);
         HIP_TRY(d, hipGetLastError());
     }
-    HIP_TRY(d, d->la_ev.record(4, d->stream));
+    HIP_TRY(d, st.ev.record(4, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
 
     res->n_nonzero = n_nonzero;
@@ -472,13 +467,13 @@ static void la_describe(pgrc_list_archive_streams *out, uint8_t *blk, uint64_t n
 uint64_t pgrc_la_device_bytes(uint64_t n, uint64_t m) { return la_layout(n, m).at_nz + n + 16; }
 uint64_t pgrc_la_host_bytes(uint64_t n, uint64_t m) { return la_layout(n, m).at_nz + dec_a16(n) + 16 + 256; }
 
-int pgrc_la_encode_resident(pgrc_decode_ctx *d, const uint8_t *d_cnt, const uint8_t *d_sym, const uint8_t *d_off, uint64_t n, uint64_t m, bool fast, uint8_t *d_block,
+int pgrc_la_encode_resident(PgrcStage *d, PgrcListArchive &st, const uint8_t *d_cnt, const uint8_t *d_sym, const uint8_t *d_off, uint64_t n, uint64_t m, bool fast, uint8_t *d_block,
                             PgrcLaResident *res) {
     int e;
-    if ((e = d->la_ev.ensure(d))) return e;
-    HIP_TRY(d, d->la_ev.record(0, d->stream));
+    if ((e = st.ev.ensure(d))) return e;
+    HIP_TRY(d, st.ev.record(0, d->stream));
     LaEncoded r;
-    if ((e = la_encode_device(d, d_cnt, d_sym, d_off, n, m, fast, d_block, &r))) return e;
+    if ((e = la_encode_device(d, st, d_cnt, d_sym, d_off, n, m, fast, d_block, &r))) return e;
     res->down = la_layout(n, m).at_nz + r.n_nonzero;
     res->n_nonzero = r.n_nonzero;
     res->limit = r.limit;
@@ -497,55 +492,48 @@ void pgrc_la_describe_resident(pgrc_list_archive_streams *out, uint8_t *blk, uin
     la_describe(out, blk, n, m, fast, r);
 }
 
-static int la_encode_run(pgrc_decode_ctx *d, const pgrc_export_streams *in, bool fast, pgrc_list_archive_streams *out) {
+static int la_encode_run(PgrcStage *d, PgrcListArchive &st, const pgrc_export_streams *in, bool fast, pgrc_list_archive_streams *out) {
     const uint64_t n = in->n_entries, m = in->n_mismatches;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
-    if ((e = d->la_ev.ensure(d))) return e;
+    if ((e = st.ev.ensure(d))) return e;
     const LaLayout lay = la_layout(n, m);
     const uint64_t sym_at = dec_a16(n) + 16, off_at = sym_at + dec_a16(m) + 16;
-    if ((e = pgrc_bufs_unpooled(d, {{&d->la_in, off_at + m + 16}, {&d->la_out, lay.at_nz + n + 16}}))) return e;
-    uint8_t *ib = (uint8_t *)d->la_in.p, *ob = (uint8_t *)d->la_out.p;
+    if ((e = pgrc_bufs_unpooled(d, {{&st.in, off_at + m + 16}, {&st.out, lay.at_nz + n + 16}}))) return e;
+    uint8_t *ib = (uint8_t *)st.in.p, *ob = (uint8_t *)st.out.p;
     uint8_t *cnt = ib, *sym = ib + sym_at, *off = ib + off_at;
     if ((e = dec_upload_host(d, cnt, in->mis_cnt, n)) || (e = dec_upload_host(d, sym, in->mis_sym, m)) || (e = dec_upload_host(d, off, in->mis_rev_off, m))) return e;
-    HIP_TRY(d, d->la_ev.record(0, d->stream));
+    HIP_TRY(d, st.ev.record(0, d->stream));
     const float ms_upload = dec_ms_since(t0);
     LaEncoded r;
-    if ((e = la_encode_device(d, cnt, sym, off, n, m, fast, ob, &r))) return e;
+    if ((e = la_encode_device(d, st, cnt, sym, off, n, m, fast, ob, &r))) return e;
     const uint32_t n_nonzero = r.n_nonzero, limit = r.limit;
 
     // one page-locked block, one copy: everything the device made; the props are the host's
     const auto t1 = std::chrono::steady_clock::now();
-    const uint64_t at_props = lay.at_nz + dec_a16(n_nonzero) + 16, total = at_props + 256, down = lay.at_nz + n_nonzero;
+    const uint64_t at_props = lay.at_nz + dec_a16(n_nonzero) + 16;
+    const DecBlockLayout<1> h = {{0}, {lay.at_nz + n_nonzero}, at_props + 256};
+    const void *src[1] = {ob};
     uint8_t *blk = nullptr;
-    hipError_t he = hipHostMalloc((void **)&blk, total);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        return dec_fail(d, PGRC_E_ALLOC, "list archive (encode): hipHostMalloc(" + std::to_string(total) + ") failed");
-    }
-    he = hipMemcpyAsync(blk, ob, down, hipMemcpyDeviceToHost, d->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
-    if (he != hipSuccess) {
-        (void)hipHostFree(blk);
-        return dec_fail(d, pgrc_hip_code(he), std::string("list archive (encode): copy down: ") + hipGetErrorString(he));
-    }
+    uint64_t down = 0;
+    if ((e = dec_download_block(d, "list archive (encode)", h, src, &blk, &down))) return e;
     la_describe(out, blk, n, m, fast, r);
     out->block = blk;
-    pgrc_list_archive_timing &t = d->latm;
+    pgrc_list_archive_timing &t = st.tm;
     t = pgrc_list_archive_timing{};
     t.struct_size = sizeof(pgrc_list_archive_timing);
     t.encode = 1;
     t.ms_upload = ms_upload;
-    t.ms_flags_device = d->la_ev.ms(0, 1);
-    t.ms_symbols_device = d->la_ev.ms(2, 3);
-    t.ms_split_device = d->la_ev.ms(3, 4);
+    t.ms_flags_device = st.ev.ms(0, 1);
+    t.ms_symbols_device = st.ev.ms(2, 3);
+    t.ms_split_device = st.ev.ms(3, 4);
     t.ms_download = dec_ms_since(t1);
     t.ms_call = dec_ms_since(t0);
     t.bytes_up = n + 2 * m;
     t.bytes_down = down;
     t.n_nonzero = n_nonzero;
     t.limit = limit;
-    d->have_la_timing = true;
+    st.have_timing = true;
     return PGRC_OK;
 }
 
@@ -554,7 +542,8 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
     static const char *who = "add_list_archive";
     const uint64_t n = s->n_entries, m = s->n_mismatches, nz = s->n_nonzero;
     const auto t0 = std::chrono::steady_clock::now();
-    d->have_la_timing = false;
+    PgrcListArchive &st = d->la;
+    st.have_timing = false;
     // the checks that need no device
     if (n != l.n) return la_fail(d, who, "n_entries differs from the list's");
     if (n >= (1ull << 32) || m >= (1ull << 32)) return la_fail(d, who, "2^32 entries or mismatches or more");
@@ -574,16 +563,16 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
     }
     if (sum != m) return la_fail(d, who, "the destinations hold " + std::to_string(sum) + " bytes, n_mismatches is " + std::to_string(m));
     int e;
-    if ((e = d->la_ev.ensure(d))) return e;
-    // uploads: flags | non-zero counts in la_in, the codes straight into the list, the sources one behind the other in la_out
+    if ((e = st.ev.ensure(d))) return e;
+    // uploads: flags | non-zero counts in `in`, the codes straight into the list, the sources one behind the other in `out`
     const uint64_t nz_at = dec_a16(n) + 16;
-    if ((e = pgrc_bufs_unpooled(d, {{&d->la_in, nz_at + nz + 16}, {&d->la_inc, n * 4 + 16}, {&d->la_cnt, n + 16}, {&d->la_small, LA_S_WORDS * 8}, {&d->la_out, m + 16},
+    if ((e = pgrc_bufs_unpooled(d, {{&st.in, nz_at + nz + 16}, {&st.inc, n * 4 + 16}, {&st.cnt, n + 16}, {&st.small, LA_S_WORDS * 8}, {&st.out, m + 16},
                                     {&l.mcum, (n + 1) * 8}, {&l.moff, m}, {&l.msym, m}})))
         return e;
-    uint8_t *flags = (uint8_t *)d->la_in.p, *nonzero = flags + nz_at, *cnt = (uint8_t *)d->la_cnt.p, *src = (uint8_t *)d->la_out.p;
-    uint32_t *inc = (uint32_t *)d->la_inc.p;
+    uint8_t *flags = (uint8_t *)st.in.p, *nonzero = flags + nz_at, *cnt = (uint8_t *)st.cnt.p, *src = (uint8_t *)st.out.p;
+    uint32_t *inc = (uint32_t *)st.inc.p;
     uint64_t *mcum = (uint64_t *)l.mcum.p;
-    unsigned long long *small = (unsigned long long *)d->la_small.p;
+    unsigned long long *small = (unsigned long long *)st.small.p;
     if ((e = dec_upload_host(d, flags, s->zero_flags, n)) || (e = dec_upload_host(d, nonzero, s->nonzero_cnt, nz)) || (e = dec_upload_host(d, l.msym.p, s->mis_sym, m))) return e;
     uint64_t h_start[256] = {};
     uint64_t at = 0;
@@ -592,7 +581,7 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
         if ((e = dec_upload_host(d, src + at, s->dest[c], s->dest_len[c]))) return e;
         at += s->dest_len[c];
     }
-    HIP_TRY(d, d->la_ev.record(0, d->stream));
+    HIP_TRY(d, st.ev.record(0, d->stream));
     const float ms_upload = dec_ms_since(t0);
 
     // counts from the flags; mismatch-list starts
@@ -610,16 +599,16 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
     HIP_TRY(d, hipGetLastError());
     if ((e = dec_scan<false>(d, XfU8{cnt}, n, 0, mcum))) return e;
     HIP_TRY(d, hipMemcpyAsync(&m_dev, mcum + n, 8, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, d->la_ev.record(1, d->stream));
+    HIP_TRY(d, st.ev.record(1, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     if (m_dev != m) return la_fail(d, who, "n_mismatches is " + std::to_string(m) + ", the counts sum to " + std::to_string(m_dev));
     l.nmis = m;
 
     // the codes
-    HIP_TRY(d, d->la_ev.record(2, d->stream));
+    HIP_TRY(d, st.ev.record(2, d->stream));
     if (m) hipLaunchKernelGGL(k_la_symcheck, dim3((uint32_t)std::min<uint64_t>(pp_grid(m), 4096)), dim3(PP_TPB), 0, d->stream, (const uint8_t *)l.msym.p, m, (uint32_t *)d->flag.p);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, d->la_ev.record(3, d->stream));
+    HIP_TRY(d, st.ev.record(3, d->stream));
 
     // the gather.  limit <= 1: every count reads the one source at its mismatch-list start (its length is m: checked above)
     if (m) {
@@ -630,7 +619,7 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
                                (const unsigned long long *)nullptr, (const uint64_t *)mcum, (const uint8_t *)src, d->L, (uint8_t *)l.moff.p, (uint32_t *)d->flag.p);
         } else {
             uint64_t h_small[LA_S_BINS] = {}, ntiles = 0;
-            if ((e = la_matrix(d, cnt, n, &ntiles, h_small))) return e;
+            if ((e = la_matrix(d, st, cnt, n, &ntiles, h_small))) return e;
             // nothing is gathered before every source is known to hold exactly its entries
             for (uint32_t c = limit + 1; c < 256; c++)
                 if (h_small[LA_S_TOTAL + c]) return la_fail(d, who, "a count of " + std::to_string(c) + ", above the limit " + std::to_string(limit));
@@ -639,21 +628,21 @@ int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list
                     return la_fail(d, who, "source " + std::to_string(c) + " holds " + std::to_string(s->dest_len[c]) + " bytes for " + std::to_string(h_small[LA_S_TOTAL + c]) + " entries");
                 if (h_small[LA_S_START + c] != h_start[c]) return dec_fail(d, PGRC_E_DEVICE, "list archive (add_list_archive): the sources' starts disagree");
             }
-            hipLaunchKernelGGL(k_la_gather<true>, dim3((uint32_t)ntiles), dim3(LA_TPB), 0, d->stream, (const uint8_t *)cnt, n, ntiles, (const uint32_t *)d->la_mat.p,
+            hipLaunchKernelGGL(k_la_gather<true>, dim3((uint32_t)ntiles), dim3(LA_TPB), 0, d->stream, (const uint8_t *)cnt, n, ntiles, (const uint32_t *)st.mat.p,
                                (const unsigned long long *)small, (const uint64_t *)mcum, (const uint8_t *)src, d->L, (uint8_t *)l.moff.p, (uint32_t *)d->flag.p);
         }
         HIP_TRY(d, hipGetLastError());
     }
-    HIP_TRY(d, d->la_ev.record(4, d->stream));
+    HIP_TRY(d, st.ev.record(4, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
-    pgrc_list_archive_timing &t = d->latm;
+    pgrc_list_archive_timing &t = st.tm;
     t = pgrc_list_archive_timing{};
     t.struct_size = sizeof(pgrc_list_archive_timing);
     t.encode = 0;
     t.ms_upload = ms_upload;
-    t.ms_flags_device = d->la_ev.ms(0, 1);
-    t.ms_symbols_device = d->la_ev.ms(2, 3);
-    t.ms_split_device = d->la_ev.ms(3, 4);
+    t.ms_flags_device = st.ev.ms(0, 1);
+    t.ms_symbols_device = st.ev.ms(2, 3);
+    t.ms_split_device = st.ev.ms(3, 4);
     t.bytes_up = n + nz + 2 * m;
     t.n_nonzero = nz;
     t.limit = limit;
@@ -672,8 +661,8 @@ int pgrc_list_archive_encode(pgrc_decode_ctx *d, const pgrc_export_streams *in, 
     if (in->n_entries >= (1ull << 32) || in->n_mismatches >= (1ull << 32)) return la_fail(d, who, "2^32 entries or mismatches or more");
     if ((in->n_entries && !in->mis_cnt) || (in->n_mismatches && (!in->mis_sym || !in->mis_rev_off))) return la_fail(d, who, "a NULL stream with a non-zero count");
     PGRC_ON_DEVICE(d);
-    d->have_la_timing = false;
-    const int e = la_encode_run(d, in, fast_level != 0, out);
+    d->la.have_timing = false;
+    const int e = la_encode_run(d, d->la, in, fast_level != 0, out);
     if (e) *out = pgrc_list_archive_streams{};
     return e;
 }
@@ -688,19 +677,19 @@ int pgrc_decode_add_list_archive(pgrc_decode_ctx *d, const pgrc_decode_list *lis
     if (!d) return PGRC_E_PARAM;
     if (!s || s->struct_size != sizeof(pgrc_list_archive_streams)) return la_fail(d, "add_list_archive", "streams is NULL or struct_size is not sizeof(pgrc_list_archive_streams)");
     const auto t0 = std::chrono::steady_clock::now();
-    d->have_la_timing = false;
+    d->la.have_timing = false;
     const int e = pgrc_dec_add_list(d, list, s);
     if (e) return e;
-    d->latm.ms_call = dec_ms_since(t0);
-    d->have_la_timing = true;
+    d->la.tm.ms_call = dec_ms_since(t0);
+    d->la.have_timing = true;
     return PGRC_OK;
 }
 
 int pgrc_list_archive_get_timing(pgrc_decode_ctx *d, pgrc_list_archive_timing *out) {
     if (!d) return PGRC_E_PARAM;
     if (!out || out->struct_size != sizeof(pgrc_list_archive_timing)) return dec_fail(d, PGRC_E_PARAM, "timing is NULL or struct_size is not sizeof(pgrc_list_archive_timing)");
-    if (!d->have_la_timing) return dec_fail(d, PGRC_E_STATE, "no list-archive call has succeeded on this context");
-    *out = d->latm;
+    if (!d->la.have_timing) return dec_fail(d, PGRC_E_STATE, "no list-archive call has succeeded on this context");
+    *out = d->la.tm;
     return PGRC_OK;
 }
 

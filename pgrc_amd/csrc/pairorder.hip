@@ -88,60 +88,46 @@ static __global__ void __launch_bounds__(PP_TPB) k_po_far(uint64_t nf, const uin
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int po_fail(pgrc_decode_ctx *d, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, "pair order (encode): " + msg); }
-
-void pgrc_pairorder_release(pgrc_decode_ctx *d) {
-    dec_free_all({&d->po_in, &d->po_rev, &d->po_ent, &d->po_pair, &d->po_out, &d->po_bsum});
-    d->po_ev.release();
-}
+static int po_fail(PgrcStage *d, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, "pair order (encode): " + msg); }
 
 // the nine streams in the order of pgrc_pairorder_streams: where they start in a block, and their bytes
 enum { PO_OFF8, PO_OFFV, PO_DELF, PO_DELV, PO_FULL, PO_PBO, PO_OFFF, PO_NONF, PO_REV, PO_NS };
-struct PoLayout {
-    uint64_t at[PO_NS], bytes[PO_NS], total;
-};
+typedef DecBlockLayout<PO_NS> PoLayout;
 static PoLayout po_layout(int32_t form, uint64_t T, uint64_t n_near, uint64_t nf, uint64_t n_del, uint64_t n_full) {
     const uint64_t P = T / 2;
     const bool coded = form != PGRC_PAIRORDER_COMPLETE_SINGLE_FILE, ff = form == PGRC_PAIRORDER_FILE_FLAGS;
     const uint64_t b[PO_NS] = {coded ? P : 0, n_near, nf, n_del, n_full * 4, form == PGRC_PAIRORDER_COMPLETE ? P * 4 : 0, ff ? n_near : 0, ff ? nf : 0, coded ? 0 : T * 4};
-    PoLayout o;
-    o.total = 0;
-    for (int k = 0; k < PO_NS; k++) {
-        o.at[k] = o.total;
-        o.bytes[k] = b[k];
-        o.total += dec_a16(b[k]) + 16;
-    }
-    return o;
+    return dec_block_layout(b);
 }
 
-// d_joined: the joined array in memory of the context's device, complete when the call is made (pgrc_pairorder_encode_joined);
-// NULL: the three host lists go up into po_in
-static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], const uint64_t n[3], const uint32_t *d_joined, uint64_t T, int32_t form, pgrc_pairorder_streams *out) {
+// d_joined: the joined array in memory of the stage's device, complete when the call is made (pgrc_pairorder_encode_joined);
+// NULL: the three host lists go up into the state's `in`
+static int po_encode_run(PgrcStage *d, PgrcPairOrder &st, const uint32_t *const org_h[3], const uint64_t n[3], const uint32_t *d_joined, uint64_t T, int32_t form, pgrc_pairorder_streams *out) {
     const uint64_t P = T / 2;
     const bool coded = form != PGRC_PAIRORDER_COMPLETE_SINGLE_FILE, ff = form == PGRC_PAIRORDER_FILE_FLAGS, complete = form == PGRC_PAIRORDER_COMPLETE;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
-    if ((e = d->po_ev.ensure(d))) return e;
+    if ((e = st.ev.ensure(d))) return e;
     const PoLayout dev = po_layout(form, T, P, P, P, P);         // on the device every stream has room for all pairs
     const uint64_t binc_at = dec_a16(T * 4) + 16, ent_bytes = binc_at + T * 4 + 16;
     const uint64_t file_at = dec_a16(P * 4) + 16, ninc_at = file_at + dec_a16(P) + 16, frel_at = ninc_at + dec_a16(P * 4) + 16, pre_at = frel_at + dec_a16(P * 4) + 16,
                    dinc_at = pre_at + dec_a16(P * 4) + 16, dval_at = dinc_at + dec_a16(P * 4) + 16, map_at = dval_at + dec_a16(P) + 16, pair_bytes = map_at + P + 16;
     const uint64_t sco_bytes = dec_a16(sco_scratch_elems(T) * 4), bsum_bytes = sco_bytes + 32;
-    if ((e = pgrc_bufs_unpooled(d, {{&d->po_in, d_joined ? 16 : T * 4 + 16}, {&d->po_rev, T * 4 + 16}, {&d->po_ent, ent_bytes}, {&d->po_pair, coded ? pair_bytes : 16},
-                                    {&d->po_out, dev.total}, {&d->po_bsum, bsum_bytes}})))
+    if ((e = pgrc_bufs_unpooled(d, {{&st.in, d_joined ? 16 : T * 4 + 16}, {&st.rev, T * 4 + 16}, {&st.ent, ent_bytes}, {&st.pair, coded ? pair_bytes : 16},
+                                    {&st.out, dev.total}, {&st.bsum, bsum_bytes}})))
         return e;
-    const uint32_t *org = d_joined ? d_joined : (const uint32_t *)d->po_in.p;
-    uint32_t *rev = (uint32_t *)d->po_rev.p;
-    uint8_t *en = (uint8_t *)d->po_ent.p, *pr = (uint8_t *)d->po_pair.p, *ob = (uint8_t *)d->po_out.p;
+    const uint32_t *org = d_joined ? d_joined : (const uint32_t *)st.in.p;
+    uint32_t *rev = (uint32_t *)st.rev.p;
+    uint8_t *en = (uint8_t *)st.ent.p, *pr = (uint8_t *)st.pair.p, *ob = (uint8_t *)st.out.p;
     uint32_t *rel = (uint32_t *)en, *base_inc = (uint32_t *)(en + binc_at);
-    uint32_t *sco_tmp = (uint32_t *)d->po_bsum.p, *bad = (uint32_t *)((uint8_t *)d->po_bsum.p + sco_bytes);
+    uint32_t *sco_tmp = (uint32_t *)st.bsum.p, *bad = (uint32_t *)((uint8_t *)st.bsum.p + sco_bytes);
     // the three lists one after the other, as the reads lists number their entries
     uint64_t first = 0;
     for (int l = 0; l < 3 && !d_joined; l++) {
-        if (n[l] && (e = dec_upload(d, (uint32_t *)d->po_in.p + first, org_h[l], n[l] * 4))) return e;
+        if (n[l] && (e = dec_upload(d, (uint32_t *)st.in.p + first, org_h[l], n[l] * 4))) return e;
         first += n[l];
     }
-    HIP_TRY(d, d->po_ev.record(0, d->stream));
+    HIP_TRY(d, st.ev.record(0, d->stream));
     if (T) HIP_TRY(d, hipMemsetAsync(rev, 0xFF, T * 4, d->stream));      // the sentinel: no entry index (T <= 2^32 - 2)
     HIP_TRY(d, hipMemsetAsync(bad, 0, 16, d->stream));
     const float ms_upload = dec_ms_since(t0);
@@ -149,16 +135,16 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     uint32_t h_bad[2] = {0, 0}, n_base = 0, n_near = 0, n_del = 0;
     if (T) {
         hipLaunchKernelGGL(k_po_scatter, dim3(pp_grid(T)), dim3(PP_TPB), 0, d->stream, (const uint32_t *)org, T, rev, bad);
-        HIP_TRY(d, d->po_ev.record(10, d->stream));
+        HIP_TRY(d, st.ev.record(10, d->stream));
         hipLaunchKernelGGL(k_po_class, dim3(pp_grid(T)), dim3(PP_TPB), 0, d->stream, (const uint32_t *)org, T, (const uint32_t *)rev, rel, bad);
         HIP_TRY(d, hipGetLastError());
     }
-    HIP_TRY(d, d->po_ev.record(1, d->stream));
+    HIP_TRY(d, st.ev.record(1, d->stream));
     if (T && coded) {
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint32_t *)rel, base_inc, T, PoNonZero{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_base, base_inc + T - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, d->po_ev.record(2, d->stream));
+    HIP_TRY(d, st.ev.record(2, d->stream));
     HIP_TRY(d, hipMemcpyAsync(h_bad, bad, 8, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     // nothing below is indexed by a pair number before the input is known to be a permutation
@@ -175,23 +161,23 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     uint32_t *full = (uint32_t *)(ob + dev.at[PO_FULL]), *pbo = complete ? (uint32_t *)(ob + dev.at[PO_PBO]) : nullptr;
     uint8_t *off_file = ff ? ob + dev.at[PO_OFFF] : nullptr, *nonoff_file = ff ? ob + dev.at[PO_NONF] : nullptr;
     const bool pairs = coded && P;
-    HIP_TRY(d, d->po_ev.record(8, d->stream));         // (the host's wait above is no device time)
+    HIP_TRY(d, st.ev.record(8, d->stream));         // (the host's wait above is no device time)
     if (pairs) hipLaunchKernelGGL(k_po_pairs, dim3(pp_grid(T)), dim3(PP_TPB), 0, d->stream, (const uint32_t *)org, T, (const uint32_t *)rel, (const uint32_t *)base_inc, prel,
                                   off8_flag, pfile, pbo);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, d->po_ev.record(3, d->stream));
+    HIP_TRY(d, st.ev.record(3, d->stream));
     if (pairs) {
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)off8_flag, near_inc, P, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, d->po_ev.record(4, d->stream));
+    HIP_TRY(d, st.ev.record(4, d->stream));
     if (pairs) hipLaunchKernelGGL(k_po_compact, dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, P, (const uint8_t *)off8_flag, (const uint32_t *)near_inc, (const uint32_t *)prel,
                                   (const uint8_t *)pfile, off_val, off_file, far_rel, nonoff_file);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, d->po_ev.record(5, d->stream));
+    HIP_TRY(d, st.ev.record(5, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     const uint64_t nf = pairs ? P - n_near : 0;
-    HIP_TRY(d, d->po_ev.record(9, d->stream));
+    HIP_TRY(d, st.ev.record(9, d->stream));
     if (nf) {
         hipLaunchKernelGGL((k_pp_enc_maps<int8_t, uint32_t>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rel, map);
         HIP_TRY(d, sco_scan<false>(d->stream, (const uint8_t *)map, pre, nf, ScoIdentity{}, PpCompose{}, PP_MAP_IDENT, sco_tmp));
@@ -199,11 +185,11 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)del_flag, del_inc, nf, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, d->po_ev.record(6, d->stream));
+    HIP_TRY(d, st.ev.record(6, d->stream));
     if (nf) hipLaunchKernelGGL(k_po_far, dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rel, (const uint8_t *)del_flag, (const uint32_t *)del_inc,
                                (const int8_t *)dval, del_val, full);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, d->po_ev.record(7, d->stream));
+    HIP_TRY(d, st.ev.record(7, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
 
     // the streams, now that their sizes are known: one page-locked block
@@ -211,24 +197,8 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     const PoLayout h = po_layout(form, T, n_near, nf, n_del, nf - n_del);
     const void *src[PO_NS] = {off8_flag, off_val, del_flag, del_val, full, ob + dev.at[PO_PBO], ob + dev.at[PO_OFFF], ob + dev.at[PO_NONF], rev};
     uint8_t *blk = nullptr;
-    hipError_t he = hipHostMalloc((void **)&blk, h.total);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        return dec_fail(d, PGRC_E_ALLOC, "pair order (encode): hipHostMalloc(" + std::to_string(h.total) + ") failed");
-    }
     uint64_t down = 0;
-    for (int k = 0; k < PO_NS; k++) {
-        if (h.bytes[k]) {
-            he = hipMemcpyAsync(blk + h.at[k], src[k], h.bytes[k], hipMemcpyDeviceToHost, d->stream);
-            if (he != hipSuccess) break;
-        }
-        down += h.bytes[k];
-    }
-    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
-    if (he != hipSuccess) {
-        (void)hipHostFree(blk);
-        return dec_fail(d, pgrc_hip_code(he), std::string("pair order (encode): copy down: ") + hipGetErrorString(he));
-    }
+    if ((e = dec_download_block(d, "pair order (encode)", h, src, &blk, &down))) return e;
     out->struct_size = sizeof(pgrc_pairorder_streams);
     out->form = form;
     out->n_total = T;
@@ -250,15 +220,15 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     out->n_delta_flag = nf;
     out->n_delta8 = n_del;
     out->n_full = nf - n_del;
-    pgrc_pairorder_timing &t = d->potm;
+    pgrc_pairorder_timing &t = st.tm;
     t = pgrc_pairorder_timing{};
     t.struct_size = sizeof(pgrc_pairorder_timing);
     t.form = form;
     t.ms_upload = ms_upload;
-    t.ms_inverse_device = d->po_ev.ms(0, 1);
-    t.ms_scatter_device = T ? d->po_ev.ms(0, 10) : 0;
-    t.ms_scan_device = d->po_ev.ms(1, 2) + d->po_ev.ms(3, 4) + d->po_ev.ms(9, 6);
-    t.ms_compact_device = d->po_ev.ms(8, 3) + d->po_ev.ms(4, 5) + d->po_ev.ms(6, 7);
+    t.ms_inverse_device = st.ev.ms(0, 1);
+    t.ms_scatter_device = T ? st.ev.ms(0, 10) : 0;
+    t.ms_scan_device = st.ev.ms(1, 2) + st.ev.ms(3, 4) + st.ev.ms(9, 6);
+    t.ms_compact_device = st.ev.ms(8, 3) + st.ev.ms(4, 5) + st.ev.ms(6, 7);
     t.ms_download = dec_ms_since(t1);
     t.ms_call = dec_ms_since(t0);
     t.bytes_up = d_joined ? 0 : T * 4;
@@ -266,17 +236,17 @@ static int po_encode_run(pgrc_decode_ctx *d, const uint32_t *const org_h[3], con
     t.n_near = n_near;
     t.n_delta = n_del;
     t.n_full = nf - n_del;
-    d->have_po_timing = true;
+    st.have_timing = true;
     return PGRC_OK;
 }
 
-int pgrc_pairorder_encode_joined(pgrc_decode_ctx *d, const uint32_t *d_joined, uint64_t T, int32_t form, pgrc_pairorder_streams *out) {
+int pgrc_pairorder_encode_joined(PgrcStage *d, PgrcPairOrder &st, const uint32_t *d_joined, uint64_t T, int32_t form, pgrc_pairorder_streams *out) {
     *out = pgrc_pairorder_streams{};
     if (form < PGRC_PAIRORDER_IGNORE || form > PGRC_PAIRORDER_COMPLETE_SINGLE_FILE) return po_fail(d, "unknown form " + std::to_string(form));
     if (T >= (1ull << 32)) return po_fail(d, "2^32 entries or more");
     if (T & 1) return po_fail(d, "the entries' count is odd");
-    d->have_po_timing = false;
-    const int e = po_encode_run(d, nullptr, nullptr, d_joined, T, form, out);
+    st.have_timing = false;
+    const int e = po_encode_run(d, st, nullptr, nullptr, d_joined, T, form, out);
     if (e) *out = pgrc_pairorder_streams{};
     return e;
 }
@@ -296,8 +266,8 @@ int pgrc_pairorder_encode(pgrc_decode_ctx *d, const uint32_t *const org_idx[3], 
     }
     if (T & 1) return po_fail(d, "the entries' count is odd");
     PGRC_ON_DEVICE(d);
-    d->have_po_timing = false;
-    const int e = po_encode_run(d, org_idx, n, nullptr, T, form, out);
+    d->po.have_timing = false;
+    const int e = po_encode_run(d, d->po, org_idx, n, nullptr, T, form, out);
     if (e) *out = pgrc_pairorder_streams{};
     return e;
 }
@@ -311,8 +281,8 @@ void pgrc_pairorder_free(pgrc_pairorder_streams *s) {
 int pgrc_pairorder_get_timing(pgrc_decode_ctx *d, pgrc_pairorder_timing *out) {
     if (!d) return PGRC_E_PARAM;
     if (!out || out->struct_size != sizeof(pgrc_pairorder_timing)) return dec_fail(d, PGRC_E_PARAM, "timing is NULL or struct_size is not sizeof(pgrc_pairorder_timing)");
-    if (!d->have_po_timing) return dec_fail(d, PGRC_E_STATE, "no pair-order call has succeeded on this context");
-    *out = d->potm;
+    if (!d->po.have_timing) return dec_fail(d, PGRC_E_STATE, "no pair-order call has succeeded on this context");
+    *out = d->po.tm;
     return PGRC_OK;
 }
 

@@ -244,46 +244,40 @@ __global__ void __launch_bounds__(PP_TPB) k_pp_enc_far(uint64_t nf, const uint32
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int pp_fail(pgrc_decode_ctx *d, const char *who, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, std::string(who) + ": " + msg); }
+static int pp_fail(PgrcStage *d, const char *who, const std::string &msg) { return dec_fail(d, PGRC_E_PARAM, std::string(who) + ": " + msg); }
 
-void pgrc_pairpos_release(pgrc_decode_ctx *d) {
-    dec_free_all({&d->pp_in, &d->pp_rec[0], &d->pp_rec[1], &d->pp_val[0], &d->pp_val[1], &d->pp_rank, &d->pp_far, &d->pp_out, &d->pp_bsum});
-    pgrc_buf_free(d->pp_sort);
-    d->pp_ev.release();
-}
-
-// the rank order of the P records in pp_rec[0] (pp_val[0]): stable by the position bits in use
-static int pp_sort(pgrc_decode_ctx *d, bool w8, uint64_t P, uint64_t base_or, const uint64_t **a, const uint64_t **b) {
+// the rank order of the P records in rec[0] (val[0]): stable by the position bits in use
+static int pp_sort(PgrcStage *d, PgrcPairPos &st, bool w8, uint64_t P, uint64_t base_or, const uint64_t **a, const uint64_t **b) {
     uint32_t hb = 0;
     while (hb < 64 && (base_or >> hb)) hb++;
     uint64_t *sorted = nullptr, *vsorted = nullptr;
     int e;
-    if (w8) e = pgrc_radix_sort_pairs_u64(d, (uint64_t *)d->pp_rec[0].p, (uint64_t *)d->pp_rec[1].p, (uint64_t *)d->pp_val[0].p, (uint64_t *)d->pp_val[1].p, P, 0, hb,
-                                          d->pp_sort, &sorted, &vsorted);
-    else e = pgrc_radix_sort_u64(d, (uint64_t *)d->pp_rec[0].p, (uint64_t *)d->pp_rec[1].p, P, 32, 32 + std::min(hb, 32u), d->pp_sort, &sorted);
+    if (w8) e = pgrc_radix_sort_pairs_u64(d, (uint64_t *)st.rec[0].p, (uint64_t *)st.rec[1].p, (uint64_t *)st.val[0].p, (uint64_t *)st.val[1].p, P, 0, hb,
+                                          st.sort, &sorted, &vsorted);
+    else e = pgrc_radix_sort_u64(d, (uint64_t *)st.rec[0].p, (uint64_t *)st.rec[1].p, P, 32, 32 + std::min(hb, 32u), st.sort, &sorted);
     if (e) return dec_fail(d, e, "pair positions: " + d->err);
     *a = sorted;
     *b = vsorted;
     return PGRC_OK;
 }
 
-static int pp_sort_buffers(pgrc_decode_ctx *d, bool w8, uint64_t P) {
+static int pp_sort_buffers(PgrcStage *d, PgrcPairPos &st, bool w8, uint64_t P) {
     int e;
     for (int k = 0; k < 2; k++) {
-        if ((e = pgrc_buf_unpooled(d, d->pp_rec[k], P * 8))) return e;
-        if (w8 && (e = pgrc_buf_unpooled(d, d->pp_val[k], P * 8))) return e;
+        if ((e = pgrc_buf_unpooled(d, st.rec[k], P * 8))) return e;
+        if (w8 && (e = pgrc_buf_unpooled(d, st.val[k], P * 8))) return e;
     }
     return PGRC_OK;
 }
 
 template <bool W8>
-static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint64_t *d_out) {
+static int pp_decode_run(PgrcStage *d, PgrcPairPos &st, const pgrc_pairpos_streams *s, uint64_t *d_out) {
     static const char *who = "pair positions (decode)";
     const uint64_t T = s->n_total, P = T / 2, W = s->pos_width;
     const uint64_t nf = s->n_delta_flag;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
-    if ((e = d->pp_ev.ensure(d)) || (e = pp_sort_buffers(d, W8, P))) return e;
+    if ((e = st.ev.ensure(d)) || (e = pp_sort_buffers(d, st, W8, P))) return e;
     // the streams, each at a 16-byte aligned place
     const void *hsrc[8] = {s->base_pos, s->off16_flag, s->off_base_first, s->off_value, s->delta16_flag, s->delta_base_first, s->delta_value, s->not_base_pos};
     const uint64_t nbytes[8] = {P * W, P, s->n_off16, s->n_off16 * 2, nf, s->n_delta16, s->n_delta16 * 2, s->n_not_base * W};
@@ -295,8 +289,8 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
     }
     const uint64_t near_at = 0, kind_at = near_at + dec_a16(P * 4) + 16, val_at = kind_at + dec_a16(P) + 16, rank_bytes = val_at + P * 8 + 16;
     const uint64_t bsum_bytes = dec_a16(sco_scratch_elems(std::max(P, nf)) * sizeof(PpSeg)) + 2 * PP_OR_BLOCKS * 8 + 64;     // (the flag scans' u32 folds too)
-    if ((e = pgrc_bufs_unpooled(d, {{&d->pp_in, in_bytes}, {&d->pp_rank, rank_bytes}, {&d->pp_far, nf * 4 + 16}, {&d->pp_bsum, bsum_bytes}}))) return e;
-    uint8_t *in = (uint8_t *)d->pp_in.p;
+    if ((e = pgrc_bufs_unpooled(d, {{&st.in, in_bytes}, {&st.rank, rank_bytes}, {&st.far, nf * 4 + 16}, {&st.bsum, bsum_bytes}}))) return e;
+    uint8_t *in = (uint8_t *)st.in.p;
     for (int k = 0; k < 8; k++)
         if (nbytes[k] && (e = dec_upload(d, in + at[k], hsrc[k], nbytes[k]))) return e;
     const float ms_upload = dec_ms_since(t0);
@@ -308,27 +302,27 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
     ds.del_bf = in + at[5];
     ds.del_val = (const int16_t *)(in + at[6]);
     ds.not_base = in + at[7];
-    uint32_t *near_inc = (uint32_t *)((uint8_t *)d->pp_rank.p + near_at), *del_inc = (uint32_t *)d->pp_far.p;
-    uint8_t *kind = (uint8_t *)d->pp_rank.p + kind_at;
-    int64_t *val = (int64_t *)((uint8_t *)d->pp_rank.p + val_at);
+    uint32_t *near_inc = (uint32_t *)((uint8_t *)st.rank.p + near_at), *del_inc = (uint32_t *)st.far.p;
+    uint8_t *kind = (uint8_t *)st.rank.p + kind_at;
+    int64_t *val = (int64_t *)((uint8_t *)st.rank.p + val_at);
     ds.near_inc = near_inc;
     ds.del_inc = del_inc;
-    uint64_t *bor = (uint64_t *)((uint8_t *)d->pp_bsum.p + bsum_bytes - 2 * PP_OR_BLOCKS * 8 - 32);     // block ORs, then the two results
-    uint32_t *sco_tmp = (uint32_t *)d->pp_bsum.p;
+    uint64_t *bor = (uint64_t *)((uint8_t *)st.bsum.p + bsum_bytes - 2 * PP_OR_BLOCKS * 8 - 32);     // block ORs, then the two results
+    uint32_t *sco_tmp = (uint32_t *)st.bsum.p;
 
-    HIP_TRY(d, d->pp_ev.record(0, d->stream));
+    HIP_TRY(d, st.ev.record(0, d->stream));
     const uint32_t nor = (uint32_t)std::min<uint64_t>(pp_grid(P), PP_OR_BLOCKS);
     if (W8) hipLaunchKernelGGL((k_pp_records<true, PpBaseStream<uint64_t>>), dim3(nor), dim3(PP_TPB), 0, d->stream, PpBaseStream<uint64_t>{(const uint64_t *)(in + at[0])}, P,
-                               (uint64_t *)d->pp_rec[0].p, (uint64_t *)d->pp_val[0].p, bor);
+                               (uint64_t *)st.rec[0].p, (uint64_t *)st.val[0].p, bor);
     else hipLaunchKernelGGL((k_pp_records<false, PpBaseStream<uint32_t>>), dim3(nor), dim3(PP_TPB), 0, d->stream, PpBaseStream<uint32_t>{(const uint32_t *)(in + at[0])}, P,
-                            (uint64_t *)d->pp_rec[0].p, (uint64_t *)nullptr, bor);
+                            (uint64_t *)st.rec[0].p, (uint64_t *)nullptr, bor);
     hipLaunchKernelGGL(k_pp_or_final, dim3(1), dim3(64), 0, d->stream, (const uint64_t *)bor, nor, bor + 2 * PP_OR_BLOCKS);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, d->pp_ev.record(1, d->stream));
+    HIP_TRY(d, st.ev.record(1, d->stream));
     // the flags' counts, held against the stream sizes before anything is indexed by them
     HIP_TRY(d, sco_scan<true>(d->stream, ds.off16_flag, near_inc, P, PpIsOne{}, ScoPlus{}, 0u, sco_tmp));
     HIP_TRY(d, sco_scan<true>(d->stream, ds.del_flag, del_inc, nf, PpNonZero{}, ScoPlus{}, 0u, sco_tmp));
-    HIP_TRY(d, d->pp_ev.record(2, d->stream));
+    HIP_TRY(d, st.ev.record(2, d->stream));
     uint64_t ors[2] = {0, 0};
     uint32_t n_near = 0, n_del = 0;
     HIP_TRY(d, hipMemcpyAsync(ors, bor + 2 * PP_OR_BLOCKS, 16, hipMemcpyDeviceToHost, d->stream));
@@ -341,23 +335,23 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
     if (nf - n_del != s->n_not_base) return pp_fail(d, who, "delta16_flag holds " + std::to_string(nf - n_del) + " full pairs, n_not_base is " + std::to_string(s->n_not_base));
 
     const uint64_t *a = nullptr, *b = nullptr;
-    if ((e = pp_sort(d, W8, P, ors[0], &a, &b))) return e;
-    HIP_TRY(d, d->pp_ev.record(3, d->stream));
+    if ((e = pp_sort(d, st, W8, P, ors[0], &a, &b))) return e;
+    HIP_TRY(d, st.ev.record(3, d->stream));
     if (P) hipLaunchKernelGGL((k_pp_dec_ops<W8>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, a, b, P, ds, d_out, kind, val);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, d->pp_ev.record(4, d->stream));
+    HIP_TRY(d, st.ev.record(4, d->stream));
     // refPrev at every ranked pair; the scan's last pass puts the delta pairs' mates in their places
-    HIP_TRY(d, (sco_device_scan<true, false>(d->stream, PpChainIn{kind, val}, P, PpSegOp{}, PpSeg{0, 0u}, PpSeg{0, 0u}, PpDeltaSink<W8>{a, b, kind, P, d_out}, (PpSeg *)d->pp_bsum.p)));
-    HIP_TRY(d, d->pp_ev.record(5, d->stream));
+    HIP_TRY(d, (sco_device_scan<true, false>(d->stream, PpChainIn{kind, val}, P, PpSegOp{}, PpSeg{0, 0u}, PpSeg{0, 0u}, PpDeltaSink<W8>{a, b, kind, P, d_out}, (PpSeg *)st.bsum.p)));
+    HIP_TRY(d, st.ev.record(5, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
-    pgrc_pairpos_timing &t = d->ptm;
+    pgrc_pairpos_timing &t = st.tm;
     t = pgrc_pairpos_timing{};
     t.struct_size = sizeof(pgrc_pairpos_timing);
     t.encode = 0;
     t.ms_upload = ms_upload;
-    t.ms_sort_device = d->pp_ev.ms(0, 1) + d->pp_ev.ms(2, 3);
-    t.ms_scan_device = d->pp_ev.ms(1, 2) + d->pp_ev.ms(3, 4);
-    t.ms_scatter_device = d->pp_ev.ms(4, 5);
+    t.ms_sort_device = st.ev.ms(0, 1) + st.ev.ms(2, 3);
+    t.ms_scan_device = st.ev.ms(1, 2) + st.ev.ms(3, 4);
+    t.ms_scatter_device = st.ev.ms(4, 5);
     t.bytes_up = up;
     t.n_near = n_near;
     t.n_delta = n_del;
@@ -365,7 +359,7 @@ static int pp_decode_run(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint
     return PGRC_OK;
 }
 
-int pgrc_pairpos_check_streams(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s) {
+int pgrc_pairpos_check_streams(PgrcStage *d, const pgrc_pairpos_streams *s) {
     static const char *who = "pair positions (decode)";
     if (!s || s->struct_size != sizeof(pgrc_pairpos_streams)) return pp_fail(d, who, "streams is NULL or struct_size is not sizeof(pgrc_pairpos_streams)");
     if (s->n_total & 1) return pp_fail(d, who, "n_total is odd");
@@ -385,44 +379,35 @@ int pgrc_pairpos_check_streams(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s
 int pgrc_pairpos_decode_device(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint64_t *d_out) {
     int e;
     if ((e = pgrc_pairpos_check_streams(d, s))) return e;
-    d->have_pp_timing = false;
-    return s->pos_width == 8 ? pp_decode_run<true>(d, s, d_out) : pp_decode_run<false>(d, s, d_out);
+    d->pp.have_timing = false;
+    return s->pos_width == 8 ? pp_decode_run<true>(d, d->pp, s, d_out) : pp_decode_run<false>(d, d->pp, s, d_out);
 }
 
-struct PpEncOut {           // where the streams start in the output block, and their bytes
-    uint64_t at[8], bytes[8], total;
-};
+typedef DecBlockLayout<8> PpEncOut;    // where the streams start in the output block, and their bytes
 static PpEncOut pp_enc_layout(uint64_t P, uint64_t W, uint64_t n_near, uint64_t nf, uint64_t n_del, uint64_t n_full) {
-    PpEncOut o;
     const uint64_t b[8] = {P * W, P, n_near, n_near * 2, nf, n_del, n_del * 2, n_full * W};
-    o.total = 0;
-    for (int k = 0; k < 8; k++) {
-        o.at[k] = o.total;
-        o.bytes[k] = b[k];
-        o.total += dec_a16(b[k]) + 16;
-    }
-    return o;
+    return dec_block_layout(b);
 }
 
-// on_device: org_h is memory of the context's device, complete when the call is made, and is read where it lies
+// on_device: org_h is memory of the stage's device, complete when the call is made, and is read where it lies
 template <bool W8>
-static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_device, uint64_t T, pgrc_pairpos_streams *out) {
+static int pp_encode_run(PgrcStage *d, PgrcPairPos &st, const uint64_t *org_h, bool on_device, uint64_t T, pgrc_pairpos_streams *out) {
     static const char *who = "pair positions (encode)";
     const uint64_t P = T / 2, W = W8 ? 8 : 4;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
-    if ((e = d->pp_ev.ensure(d)) || (e = pp_sort_buffers(d, W8, P))) return e;
+    if ((e = st.ev.ensure(d)) || (e = pp_sort_buffers(d, st, W8, P))) return e;
     const PpEncOut dev = pp_enc_layout(P, W, P, P, P, P);        // on the device every stream has room for all pairs
     const uint64_t near_at = dec_a16(P * 8) + 16, bf_at = near_at + dec_a16(P * 4) + 16, rank_bytes = bf_at + P + 16;
     const uint64_t frank_at = dec_a16(P * 8) + 16, pre_at = frank_at + dec_a16(P * 4) + 16, dinc_at = pre_at + dec_a16(P * 4) + 16,
                    dval_at = dinc_at + dec_a16(P * 4) + 16, map_at = dval_at + dec_a16(P * 2) + 16, far_bytes = map_at + P + 16;
     const uint64_t bsum_bytes = dec_a16(sco_scratch_elems(P) * 4) + 2 * PP_OR_BLOCKS * 8 + 64;
-    if ((e = pgrc_bufs_unpooled(d, {{&d->pp_in, on_device ? 16 : T * 8 + 16}, {&d->pp_rank, rank_bytes}, {&d->pp_far, far_bytes}, {&d->pp_out, dev.total}, {&d->pp_bsum, bsum_bytes}})))
+    if ((e = pgrc_bufs_unpooled(d, {{&st.in, on_device ? 16 : T * 8 + 16}, {&st.rank, rank_bytes}, {&st.far, far_bytes}, {&st.out, dev.total}, {&st.bsum, bsum_bytes}})))
         return e;
-    if (T && !on_device && (e = dec_upload(d, d->pp_in.p, org_h, T * 8))) return e;
+    if (T && !on_device && (e = dec_upload(d, st.in.p, org_h, T * 8))) return e;
     const float ms_upload = dec_ms_since(t0);
-    const uint64_t *org = on_device ? org_h : (const uint64_t *)d->pp_in.p;
-    uint8_t *rk = (uint8_t *)d->pp_rank.p, *fr = (uint8_t *)d->pp_far.p, *ob = (uint8_t *)d->pp_out.p;
+    const uint64_t *org = on_device ? org_h : (const uint64_t *)st.in.p;
+    uint8_t *rk = (uint8_t *)st.rank.p, *fr = (uint8_t *)st.far.p, *ob = (uint8_t *)st.out.p;
     uint64_t *rel = (uint64_t *)rk;
     uint32_t *near_inc = (uint32_t *)(rk + near_at);
     uint8_t *bf = rk + bf_at;
@@ -434,13 +419,13 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
     uint16_t *off_val = (uint16_t *)(ob + dev.at[3]);
     int16_t *del_val = (int16_t *)(ob + dev.at[6]);
     void *not_base = ob + dev.at[7];
-    uint64_t *bor = (uint64_t *)((uint8_t *)d->pp_bsum.p + bsum_bytes - 2 * PP_OR_BLOCKS * 8 - 32);
-    uint32_t *sco_tmp = (uint32_t *)d->pp_bsum.p;
+    uint64_t *bor = (uint64_t *)((uint8_t *)st.bsum.p + bsum_bytes - 2 * PP_OR_BLOCKS * 8 - 32);
+    uint32_t *sco_tmp = (uint32_t *)st.bsum.p;
 
-    HIP_TRY(d, d->pp_ev.record(0, d->stream));
+    HIP_TRY(d, st.ev.record(0, d->stream));
     const uint32_t nor = (uint32_t)std::min<uint64_t>(pp_grid(P), PP_OR_BLOCKS);
-    hipLaunchKernelGGL((k_pp_records<W8, PpBaseOrg>), dim3(nor), dim3(PP_TPB), 0, d->stream, PpBaseOrg{org}, P, (uint64_t *)d->pp_rec[0].p,
-                       (uint64_t *)(W8 ? d->pp_val[0].p : nullptr), bor);
+    hipLaunchKernelGGL((k_pp_records<W8, PpBaseOrg>), dim3(nor), dim3(PP_TPB), 0, d->stream, PpBaseOrg{org}, P, (uint64_t *)st.rec[0].p,
+                       (uint64_t *)(W8 ? st.val[0].p : nullptr), bor);
     hipLaunchKernelGGL(k_pp_or_final, dim3(1), dim3(64), 0, d->stream, (const uint64_t *)bor, nor, bor + 2 * PP_OR_BLOCKS);
     HIP_TRY(d, hipGetLastError());
     uint64_t ors[2] = {0, 0};
@@ -448,15 +433,15 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     if (!W8 && (ors[1] >> 32)) return pp_fail(d, who, "a position of 2^32 or more with pos_width 4");
     const uint64_t *a = nullptr, *b = nullptr;
-    if ((e = pp_sort(d, W8, P, ors[0], &a, &b))) return e;
-    HIP_TRY(d, d->pp_ev.record(1, d->stream));
+    if ((e = pp_sort(d, st, W8, P, ors[0], &a, &b))) return e;
+    HIP_TRY(d, st.ev.record(1, d->stream));
     uint32_t n_near = 0, n_del = 0;
     if (P) {
         hipLaunchKernelGGL((k_pp_enc_class<W8>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, a, b, org, P, off16_flag, rel, bf);
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)off16_flag, near_inc, P, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_near, near_inc + P - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, d->pp_ev.record(2, d->stream));
+    HIP_TRY(d, st.ev.record(2, d->stream));
     if (P) {
         if (W8) hipLaunchKernelGGL((k_pp_enc_base<uint64_t>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, org, P, (uint64_t *)(ob + dev.at[0]));
         else hipLaunchKernelGGL((k_pp_enc_base<uint32_t>), dim3(pp_grid(P)), dim3(PP_TPB), 0, d->stream, org, P, (uint32_t *)(ob + dev.at[0]));
@@ -464,7 +449,7 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
                            (const uint8_t *)bf, off_bf, off_val, far_rel, far_rank);
     }
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, d->pp_ev.record(3, d->stream));
+    HIP_TRY(d, st.ev.record(3, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     const uint64_t nf = P - n_near;
     if (nf) {
@@ -474,35 +459,21 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
         HIP_TRY(d, sco_scan<true>(d->stream, (const uint8_t *)del_flag, del_inc, nf, ScoIdentity{}, ScoPlus{}, 0u, sco_tmp));
         HIP_TRY(d, hipMemcpyAsync(&n_del, del_inc + nf - 1, 4, hipMemcpyDeviceToHost, d->stream));
     }
-    HIP_TRY(d, d->pp_ev.record(4, d->stream));
+    HIP_TRY(d, st.ev.record(4, d->stream));
     if (nf) hipLaunchKernelGGL((k_pp_enc_far<W8>), dim3(pp_grid(nf)), dim3(PP_TPB), 0, d->stream, nf, (const uint32_t *)far_rank, (const uint64_t *)far_rel,
                                (const uint8_t *)del_flag, (const uint32_t *)del_inc, (const int16_t *)dval, (const uint8_t *)bf, a, b, del_bf, del_val, not_base);
     HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, d->pp_ev.record(5, d->stream));
+    HIP_TRY(d, st.ev.record(5, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
 
     // the streams, now that their sizes are known: one page-locked block
     const auto t1 = std::chrono::steady_clock::now();
     const PpEncOut h = pp_enc_layout(P, W, n_near, nf, n_del, nf - n_del);
+    const void *src[8];
+    for (int k = 0; k < 8; k++) src[k] = ob + dev.at[k];
     uint8_t *blk = nullptr;
-    hipError_t he = hipHostMalloc((void **)&blk, h.total);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        return dec_fail(d, PGRC_E_ALLOC, "pair positions (encode): hipHostMalloc(" + std::to_string(h.total) + ") failed");
-    }
     uint64_t down = 0;
-    for (int k = 0; k < 8; k++) {
-        if (h.bytes[k]) {
-            he = hipMemcpyAsync(blk + h.at[k], ob + dev.at[k], h.bytes[k], hipMemcpyDeviceToHost, d->stream);
-            if (he != hipSuccess) break;
-        }
-        down += h.bytes[k];
-    }
-    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
-    if (he != hipSuccess) {
-        (void)hipHostFree(blk);
-        return dec_fail(d, pgrc_hip_code(he), std::string("pair positions (encode): copy down: ") + hipGetErrorString(he));
-    }
+    if ((e = dec_download_block(d, who, h, src, &blk, &down))) return e;
     *out = pgrc_pairpos_streams{};
     out->struct_size = sizeof(pgrc_pairpos_streams);
     out->pos_width = (uint32_t)W;
@@ -519,14 +490,14 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
     out->n_delta_flag = nf;
     out->n_delta16 = n_del;
     out->n_not_base = nf - n_del;
-    pgrc_pairpos_timing &t = d->ptm;
+    pgrc_pairpos_timing &t = st.tm;
     t = pgrc_pairpos_timing{};
     t.struct_size = sizeof(pgrc_pairpos_timing);
     t.encode = 1;
     t.ms_upload = ms_upload;
-    t.ms_sort_device = d->pp_ev.ms(0, 1);
-    t.ms_scan_device = d->pp_ev.ms(1, 2) + d->pp_ev.ms(3, 4);
-    t.ms_scatter_device = d->pp_ev.ms(2, 3) + d->pp_ev.ms(4, 5);
+    t.ms_sort_device = st.ev.ms(0, 1);
+    t.ms_scan_device = st.ev.ms(1, 2) + st.ev.ms(3, 4);
+    t.ms_scatter_device = st.ev.ms(2, 3) + st.ev.ms(4, 5);
     t.ms_download = dec_ms_since(t1);
     t.ms_call = dec_ms_since(t0);
     t.bytes_up = on_device ? 0 : T * 8;
@@ -534,17 +505,17 @@ static int pp_encode_run(pgrc_decode_ctx *d, const uint64_t *org_h, bool on_devi
     t.n_near = n_near;
     t.n_delta = n_del;
     t.n_full = nf - n_del;
-    d->have_pp_timing = true;
+    st.have_timing = true;
     return PGRC_OK;
 }
 
-int pgrc_pairpos_encode_device(pgrc_decode_ctx *d, const uint64_t *d_org_idx_to_pos, uint64_t n_total, uint32_t pos_width, pgrc_pairpos_streams *out) {
+int pgrc_pairpos_encode_device(PgrcStage *d, PgrcPairPos &st, const uint64_t *d_org_idx_to_pos, uint64_t n_total, uint32_t pos_width, pgrc_pairpos_streams *out) {
     static const char *who = "pair positions (encode)";
     if (n_total & 1) return pp_fail(d, who, "n_total is odd");
     if (pos_width != 4 && pos_width != 8) return pp_fail(d, who, "pos_width must be 4 or 8");
     if (n_total / 2 >= PP_MAX_PAIRS) return pp_fail(d, who, "too many pairs for the rank sort");
-    d->have_pp_timing = false;
-    return pos_width == 8 ? pp_encode_run<true>(d, d_org_idx_to_pos, true, n_total, out) : pp_encode_run<false>(d, d_org_idx_to_pos, true, n_total, out);
+    st.have_timing = false;
+    return pos_width == 8 ? pp_encode_run<true>(d, st, d_org_idx_to_pos, true, n_total, out) : pp_encode_run<false>(d, st, d_org_idx_to_pos, true, n_total, out);
 }
 
 extern "C" {
@@ -558,8 +529,8 @@ int pgrc_pairpos_encode(pgrc_decode_ctx *d, const uint64_t *org_idx_to_pos, uint
     if (n_total && !org_idx_to_pos) return pp_fail(d, who, "org_idx_to_pos is NULL");
     if (n_total / 2 >= PP_MAX_PAIRS) return pp_fail(d, who, "too many pairs for the rank sort");
     PGRC_ON_DEVICE(d);
-    d->have_pp_timing = false;
-    return pos_width == 8 ? pp_encode_run<true>(d, org_idx_to_pos, false, n_total, out) : pp_encode_run<false>(d, org_idx_to_pos, false, n_total, out);
+    d->pp.have_timing = false;
+    return pos_width == 8 ? pp_encode_run<true>(d, d->pp, org_idx_to_pos, false, n_total, out) : pp_encode_run<false>(d, d->pp, org_idx_to_pos, false, n_total, out);
 }
 
 void pgrc_pairpos_free(pgrc_pairpos_streams *s) {
@@ -575,22 +546,22 @@ int pgrc_pairpos_decode(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint6
     const auto t0 = std::chrono::steady_clock::now();
     int e;
     if ((e = pgrc_pairpos_check_streams(d, s))) return e;
-    if ((e = pgrc_buf_unpooled(d, d->pp_out, s->n_total * 8 + 16))) return e;
-    if ((e = pgrc_pairpos_decode_device(d, s, (uint64_t *)d->pp_out.p))) return e;
+    if ((e = pgrc_buf_unpooled(d, d->pp.out, s->n_total * 8 + 16))) return e;
+    if ((e = pgrc_pairpos_decode_device(d, s, (uint64_t *)d->pp.out.p))) return e;
     const auto t1 = std::chrono::steady_clock::now();
-    if ((e = dec_download_host(d, pg_pos, d->pp_out.p, s->n_total * 8))) return e;
-    d->ptm.ms_download = dec_ms_since(t1);
-    d->ptm.bytes_down = s->n_total * 8;
-    d->ptm.ms_call = dec_ms_since(t0);
-    d->have_pp_timing = true;
+    if ((e = dec_download_host(d, pg_pos, d->pp.out.p, s->n_total * 8))) return e;
+    d->pp.tm.ms_download = dec_ms_since(t1);
+    d->pp.tm.bytes_down = s->n_total * 8;
+    d->pp.tm.ms_call = dec_ms_since(t0);
+    d->pp.have_timing = true;
     return PGRC_OK;
 }
 
 int pgrc_pairpos_get_timing(pgrc_decode_ctx *d, pgrc_pairpos_timing *out) {
     if (!d) return PGRC_E_PARAM;
     if (!out || out->struct_size != sizeof(pgrc_pairpos_timing)) return dec_fail(d, PGRC_E_PARAM, "timing is NULL or struct_size is not sizeof(pgrc_pairpos_timing)");
-    if (!d->have_pp_timing) return dec_fail(d, PGRC_E_STATE, "no pair-position call has succeeded on this context");
-    *out = d->ptm;
+    if (!d->pp.have_timing) return dec_fail(d, PGRC_E_STATE, "no pair-position call has succeeded on this context");
+    *out = d->pp.tm;
     return PGRC_OK;
 }
 

@@ -28,7 +28,7 @@ enum { RL_BAD_RANGE, RL_BAD_TWICE, RL_BAD_NEVER, RL_BAD_WORDS };
 static thread_local std::string g_rl_create_err;
 
 static inline uint32_t rl_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + RL_TPB - 1) / RL_TPB, 1), RL_MAX_BLOCKS); }
-static int rl_fail(pgrc_rlist *s, int code, const std::string &msg) { return dec_fail(s->d, code, "reads list: " + msg); }
+static int rl_fail(pgrc_rlist *s, int code, const std::string &msg) { return dec_fail(s, code, "reads list: " + msg); }
 
 // ------------------------------------------------------------------------------------------------ kernels
 // applyIndexesMapping; an index at or above the mapping's count sets bad[RL_BAD_RANGE] and reads nothing
@@ -109,17 +109,19 @@ static __global__ void __launch_bounds__(RL_TPB) k_rl_pos_never(const uint8_t *_
 }
 
 // ------------------------------------------------------------------------------------------------ host side: helpers
+static DevBufList rl_bufs(pgrc_rlist *s) { return {&s->map, &s->words, &s->block, &s->join, &s->pos, &s->scan, &s->cls}; }
+
 static void rl_free(RlBufs &b) {
     dec_free_all({&b.off, &b.org, &b.rc, &b.cnt, &b.sym, &b.roff});
     b = RlBufs{};
 }
 
 // fresh buffers of exactly the list's sizes; given back by the caller if its call fails
-static int rl_alloc(pgrc_decode_ctx *d, RlBufs &b, uint64_t n, uint64_t m, bool rc, bool mis, uint32_t off_width) {
+static int rl_alloc(PgrcStage *s, RlBufs &b, uint64_t n, uint64_t m, bool rc, bool mis, uint32_t off_width) {
     int e;
-    if ((e = pgrc_bufs_unpooled(d, {{&b.off, n * 2 + 16}, {&b.org, n * 4 + 16}}))) return e;
-    if (rc && (e = pgrc_buf_unpooled(d, b.rc, n + 16))) return e;
-    if (mis && (e = pgrc_bufs_unpooled(d, {{&b.cnt, n + 16}, {&b.sym, m + 16}, {&b.roff, m * off_width + 16}}))) return e;
+    if ((e = pgrc_bufs_unpooled(s, {{&b.off, n * 2 + 16}, {&b.org, n * 4 + 16}}))) return e;
+    if (rc && (e = pgrc_buf_unpooled(s, b.rc, n + 16))) return e;
+    if (mis && (e = pgrc_bufs_unpooled(s, {{&b.cnt, n + 16}, {&b.sym, m + 16}, {&b.roff, m * off_width + 16}}))) return e;
     b.n = n;
     b.nmis = m;
     b.has_rc = rc;
@@ -135,9 +137,9 @@ static void rl_swap_in(pgrc_rlist *s, RlBufs &nb) {
 }
 
 static int rl_events(pgrc_rlist *s) {
-    if (int e = s->ev.ensure(s->d)) return e;
+    if (int e = s->ev.ensure(s)) return e;
     for (hipEvent_t &ev : s->ev_x)
-        if (!ev) HIP_TRY(s->d, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        if (!ev) HIP_TRY(s, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     return PGRC_OK;
 }
 
@@ -146,7 +148,7 @@ static int rl_begin(pgrc_rlist *s) {
     if ((e = rl_events(s))) return e;
     s->have_timing = false;
     s->tm = pgrc_rlist_timing{};
-    HIP_TRY(s->d, s->ev.record(0, s->d->stream));
+    HIP_TRY(s, s->ev.record(0, s->stream));
     return PGRC_OK;
 }
 
@@ -163,21 +165,21 @@ static void rl_done(pgrc_rlist *s, uint32_t call, std::chrono::steady_clock::tim
 
 static int rl_copy(pgrc_rlist *s, void *dst, const void *src, uint64_t bytes) {
     if (!bytes) return PGRC_OK;
-    HIP_TRY(s->d, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s->d->stream));
+    HIP_TRY(s, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s->stream));
     s->tm.bytes_device_copy += bytes;
     return PGRC_OK;
 }
 
 static int rl_narrow(pgrc_rlist *s, const uint16_t *in, uint64_t n, uint8_t *out) {
     if (!n) return PGRC_OK;
-    hipLaunchKernelGGL(k_rl_narrow, dim3(rl_grid(std::max<uint64_t>(n >> 3, 8))), dim3(RL_TPB), 0, s->d->stream, in, n, out);
-    HIP_TRY(s->d, hipGetLastError());
+    hipLaunchKernelGGL(k_rl_narrow, dim3(rl_grid(std::max<uint64_t>(n >> 3, 8))), dim3(RL_TPB), 0, s->stream, in, n, out);
+    HIP_TRY(s, hipGetLastError());
     return PGRC_OK;
 }
 
 // the original indexes of a matcher's reads from the read sets: SumOfMappings of the LQ and the N mapping, joined in `map`
 static int rl_reads_org(pgrc_rlist *s, pgrc_rsets *sets, uint64_t matcher_n, const char *what, const uint32_t **d_rorg) {
-    if (sets->device != s->d->device) return rl_fail(s, PGRC_E_PARAM, std::string(what) + ": the read sets are on another device");
+    if (sets->device != s->device) return rl_fail(s, PGRC_E_PARAM, std::string(what) + ": the read sets are on another device");
     const uint32_t *m[2] = {};
     uint64_t cnt[2] = {};
     int e;
@@ -186,7 +188,7 @@ static int rl_reads_org(pgrc_rlist *s, pgrc_rsets *sets, uint64_t matcher_n, con
         if ((e = pgrc_rsets_mapping_device(sets, k, &m[k - 1], &cnt[k - 1]))) return rl_fail(s, e, std::string(what) + ": " + pgrc_rsets_last_error(sets));
     }
     if (cnt[0] + cnt[1] != matcher_n) return rl_fail(s, PGRC_E_PARAM, std::string(what) + ": the LQ count plus the N count of the read sets is not the matcher's read count");
-    if ((e = pgrc_buf_unpooled(s->d, s->map, matcher_n * 4 + 16))) return e;
+    if ((e = pgrc_buf_unpooled(s, s->map, matcher_n * 4 + 16))) return e;
     uint32_t *dst = (uint32_t *)s->map.p;
     if ((e = rl_copy(s, dst, m[0], cnt[0] * 4)) || (e = rl_copy(s, dst + cnt[0], m[1], cnt[1] * 4))) return e;
     *d_rorg = dst;
@@ -195,13 +197,12 @@ static int rl_reads_org(pgrc_rlist *s, pgrc_rsets *sets, uint64_t matcher_n, con
 
 static int rl_matcher_ok(pgrc_rlist *s, pgrc_match_ctx *c, const char *what) {
     if (c->multi) return rl_fail(s, PGRC_E_PARAM, std::string(what) + ": the matcher runs on several devices");
-    if (c->device != s->d->device) return rl_fail(s, PGRC_E_PARAM, std::string(what) + ": the matcher is on another device");
+    if (c->device != s->device) return rl_fail(s, PGRC_E_PARAM, std::string(what) + ": the matcher is on another device");
     return PGRC_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ host side: the calls
 static int rl_set_host(pgrc_rlist *s, const pgrc_export_streams *in) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t n = in->n_entries, m = in->n_mismatches;
     const bool mis = in->mis_cnt != nullptr;
@@ -210,36 +211,36 @@ static int rl_set_host(pgrc_rlist *s, const pgrc_export_streams *in) {
     if ((e = rl_begin(s))) return e;
     RlBufs nb;
     auto run = [&]() -> int {
-        if ((e = rl_alloc(d, nb, n, m, in->rev_comp != nullptr, mis, w))) return e;
+        if ((e = rl_alloc(s, nb, n, m, in->rev_comp != nullptr, mis, w))) return e;
         if (w == 2) {
-            if ((e = dec_upload_host(d, nb.off.p, in->off, n * 2))) return e;
+            if ((e = dec_upload_host(s, nb.off.p, in->off, n * 2))) return e;
         } else {
-            if ((e = pgrc_buf_unpooled(d, s->block, n + 16)) || (e = dec_upload_host(d, s->block.p, in->off, n))) return e;
-            if (n) hipLaunchKernelGGL(k_rl_widen, dim3(rl_grid(n)), dim3(RL_TPB), 0, d->stream, (const uint8_t *)s->block.p, n, (uint16_t *)nb.off.p);
-            HIP_TRY(d, hipGetLastError());
+            if ((e = pgrc_buf_unpooled(s, s->block, n + 16)) || (e = dec_upload_host(s, s->block.p, in->off, n))) return e;
+            if (n) hipLaunchKernelGGL(k_rl_widen, dim3(rl_grid(n)), dim3(RL_TPB), 0, s->stream, (const uint8_t *)s->block.p, n, (uint16_t *)nb.off.p);
+            HIP_TRY(s, hipGetLastError());
         }
-        if ((e = dec_upload_host(d, nb.org.p, in->org_idx, n * 4))) return e;
-        if (nb.has_rc && (e = dec_upload_host(d, nb.rc.p, in->rev_comp, n))) return e;
+        if ((e = dec_upload_host(s, nb.org.p, in->org_idx, n * 4))) return e;
+        if (nb.has_rc && (e = dec_upload_host(s, nb.rc.p, in->rev_comp, n))) return e;
         s->tm.bytes_up = n * w + n * 4 + (nb.has_rc ? n : 0);
-        HIP_TRY(d, s->ev.record(1, d->stream));
+        HIP_TRY(s, s->ev.record(1, s->stream));
         if (mis) {
-            if ((e = dec_upload_host(d, nb.cnt.p, in->mis_cnt, n)) || (e = dec_upload_host(d, nb.sym.p, in->mis_sym, m)) || (e = dec_upload_host(d, nb.roff.p, in->mis_rev_off, m * w)))
+            if ((e = dec_upload_host(s, nb.cnt.p, in->mis_cnt, n)) || (e = dec_upload_host(s, nb.sym.p, in->mis_sym, m)) || (e = dec_upload_host(s, nb.roff.p, in->mis_rev_off, m * w)))
                 return e;
             s->tm.bytes_up += n + m + m * w;
             // the counts describe the streams
-            if ((e = pgrc_buf_unpooled(d, s->scan, (n + 1) * 8)) || (e = dec_scan<false>(d, XfU8{(const uint8_t *)nb.cnt.p}, n, 0, (uint64_t *)s->scan.p))) return e;
+            if ((e = pgrc_buf_unpooled(s, s->scan, (n + 1) * 8)) || (e = dec_scan<false>(s, XfU8{(const uint8_t *)nb.cnt.p}, n, 0, (uint64_t *)s->scan.p))) return e;
             uint64_t m_dev = 0;
-            HIP_TRY(d, hipMemcpyAsync(&m_dev, (const uint64_t *)s->scan.p + n, 8, hipMemcpyDeviceToHost, d->stream));
-            HIP_TRY(d, hipStreamSynchronize(d->stream));
+            HIP_TRY(s, hipMemcpyAsync(&m_dev, (const uint64_t *)s->scan.p + n, 8, hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(s, hipStreamSynchronize(s->stream));
             if (m_dev != m) return rl_fail(s, PGRC_E_PARAM, "set_host: n_mismatches is " + std::to_string(m) + ", the counts sum to " + std::to_string(m_dev));
         }
-        HIP_TRY(d, s->ev.record(2, d->stream));
-        HIP_TRY(d, s->ev.record(3, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(s, s->ev.record(2, s->stream));
+        HIP_TRY(s, s->ev.record(3, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
         return PGRC_OK;
     };
     if ((e = run())) {
-        (void)hipStreamSynchronize(d->stream);
+        (void)hipStreamSynchronize(s->stream);
         rl_free(nb);
         return e;
     }
@@ -250,31 +251,30 @@ static int rl_set_host(pgrc_rlist *s, const pgrc_export_streams *in) {
 }
 
 static int rl_from_assembly(pgrc_rlist *s, const PgasmLastList &l, const uint32_t *d_map, uint64_t map_count) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
     if ((e = rl_begin(s))) return e;
     RlBufs nb;
     auto run = [&]() -> int {
-        if ((e = rl_alloc(d, nb, l.n, 0, false, false, 1)) || (e = pgrc_buf_unpooled(d, s->words, 64))) return e;
+        if ((e = rl_alloc(s, nb, l.n, 0, false, false, 1)) || (e = pgrc_buf_unpooled(s, s->words, 64))) return e;
         uint32_t *bad = (uint32_t *)s->words.p;
-        HIP_TRY(d, hipMemsetAsync(bad, 0, 64, d->stream));
+        HIP_TRY(s, hipMemsetAsync(bad, 0, 64, s->stream));
         if ((e = rl_copy(s, nb.off.p, l.d_off, l.n * 2))) return e;
         if (d_map) {
-            hipLaunchKernelGGL(k_rl_map, dim3(rl_grid(l.n)), dim3(RL_TPB), 0, d->stream, l.d_org, l.n, d_map, map_count, (uint32_t *)nb.org.p, bad);
-            HIP_TRY(d, hipGetLastError());
+            hipLaunchKernelGGL(k_rl_map, dim3(rl_grid(l.n)), dim3(RL_TPB), 0, s->stream, l.d_org, l.n, d_map, map_count, (uint32_t *)nb.org.p, bad);
+            HIP_TRY(s, hipGetLastError());
         } else if ((e = rl_copy(s, nb.org.p, l.d_org, l.n * 4))) {
             return e;
         }
-        for (int k = 1; k < 4; k++) HIP_TRY(d, s->ev.record(k, d->stream));
+        for (int k = 1; k < 4; k++) HIP_TRY(s, s->ev.record(k, s->stream));
         uint32_t h_bad[RL_BAD_WORDS] = {};
-        HIP_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(s, hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
         if (h_bad[RL_BAD_RANGE]) return rl_fail(s, PGRC_E_PARAM, "from_assembly: an index at or above the mapping's count " + std::to_string(map_count));
         return PGRC_OK;
     };
     if ((e = run())) {
-        (void)hipStreamSynchronize(d->stream);
+        (void)hipStreamSynchronize(s->stream);
         rl_free(nb);
         return e;
     }
@@ -285,7 +285,6 @@ static int rl_from_assembly(pgrc_rlist *s, const PgasmLastList &l, const uint32_
 }
 
 static int rl_export(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_args *x) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
     if ((e = rl_begin(s))) return e;
@@ -303,28 +302,28 @@ static int rl_export(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_a
     a.byte_per_read_length = x->byte_per_read_length;
     a.order_on_device = x->order_on_device;
     // the matcher's stream waits for what this one has queued, and this one for the export: no device-wide wait
-    HIP_TRY(d, s->ev.record(1, d->stream));
-    HIP_TRY(d, hipEventRecord(s->ev_x[0], d->stream));
-    HIP_TRY(d, hipStreamWaitEvent(c->stream, s->ev_x[0], 0));
+    HIP_TRY(s, s->ev.record(1, s->stream));
+    HIP_TRY(s, hipEventRecord(s->ev_x[0], s->stream));
+    HIP_TRY(s, hipStreamWaitEvent(c->stream, s->ev_x[0], 0));
     PgrcExportResident r;
     if ((e = pgrc_export_pg_order_resident(c, &a, &src, &r))) return rl_fail(s, e, std::string("export_pg_order: ") + pgrc_match_last_error(c));
     RlBufs nb;
     auto run = [&]() -> int {
-        HIP_TRY(d, hipEventRecord(s->ev_x[1], c->stream));
-        HIP_TRY(d, hipStreamWaitEvent(d->stream, s->ev_x[1], 0));
-        HIP_TRY(d, s->ev.record(2, d->stream));
+        HIP_TRY(s, hipEventRecord(s->ev_x[1], c->stream));
+        HIP_TRY(s, hipStreamWaitEvent(s->stream, s->ev_x[1], 0));
+        HIP_TRY(s, s->ev.record(2, s->stream));
         if (r.n_entries >= (1ull << 32) || r.n_mismatches >= (1ull << 32)) return rl_fail(s, PGRC_E_PARAM, "export_pg_order: 2^32 entries or mismatches or more");
         const uint64_t n = r.n_entries, m = r.n_mismatches;
-        if ((e = rl_alloc(d, nb, n, m, true, true, r.mis_off_width))) return e;
+        if ((e = rl_alloc(s, nb, n, m, true, true, r.mis_off_width))) return e;
         if ((e = rl_copy(s, nb.off.p, r.d_off, n * 2)) || (e = rl_copy(s, nb.org.p, r.d_org, n * 4)) || (e = rl_copy(s, nb.rc.p, r.d_rc, n)) || (e = rl_copy(s, nb.cnt.p, r.d_cnt, n)) ||
             (e = rl_copy(s, nb.sym.p, r.d_sym, m)) || (e = rl_copy(s, nb.roff.p, r.d_rev_off, m * r.mis_off_width)))
             return e;
-        HIP_TRY(d, s->ev.record(3, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
+        HIP_TRY(s, s->ev.record(3, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
         return PGRC_OK;
     };
     e = run();
-    if (e) (void)hipStreamSynchronize(d->stream);
+    if (e) (void)hipStreamSynchronize(s->stream);
     const uint64_t last = r.last_pos;
     pgrc_export_resident_release(&r);
     if (e) {
@@ -340,13 +339,12 @@ static int rl_export(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_a
 }
 
 static int rl_download_run(pgrc_rlist *s, pgrc_export_streams *out) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     const RlBufs &b = s->cur;
     const uint64_t n = b.n, m = b.nmis, w = b.off_width;
     int e;
     if ((e = rl_begin(s))) return e;
-    for (int k = 1; k < 3; k++) HIP_TRY(d, s->ev.record(k, d->stream));
+    for (int k = 1; k < 3; k++) HIP_TRY(s, s->ev.record(k, s->stream));
     out->n_entries = n;
     out->n_mismatches = m;
     out->off_width = (uint32_t)w;
@@ -360,21 +358,20 @@ static int rl_download_run(pgrc_rlist *s, pgrc_export_streams *out) {
     if (!out->off || !out->org_idx || !out->rev_comp || !out->mis_cnt || !out->mis_sym || !out->mis_rev_off) return rl_fail(s, PGRC_E_ALLOC, "download: host allocation failed");
     const void *d_off = b.off.p;
     if (w == 1) {
-        if ((e = pgrc_buf_unpooled(d, s->block, dec_a16(n) + 16)) || (e = rl_narrow(s, (const uint16_t *)b.off.p, n, (uint8_t *)s->block.p))) return e;
+        if ((e = pgrc_buf_unpooled(s, s->block, dec_a16(n) + 16)) || (e = rl_narrow(s, (const uint16_t *)b.off.p, n, (uint8_t *)s->block.p))) return e;
         d_off = s->block.p;
     }
-    HIP_TRY(d, s->ev.record(3, d->stream));
-    if ((e = dec_download_host(d, out->off, d_off, n * w)) || (e = dec_download_host(d, out->org_idx, b.org.p, n * 4))) return e;
-    if (b.has_rc && (e = dec_download_host(d, out->rev_comp, b.rc.p, n))) return e;
-    if (b.has_mis && ((e = dec_download_host(d, out->mis_cnt, b.cnt.p, n)) || (e = dec_download_host(d, out->mis_sym, b.sym.p, m)) || (e = dec_download_host(d, out->mis_rev_off, b.roff.p, m * w)))) return e;
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(s, s->ev.record(3, s->stream));
+    if ((e = dec_download_host(s, out->off, d_off, n * w)) || (e = dec_download_host(s, out->org_idx, b.org.p, n * 4))) return e;
+    if (b.has_rc && (e = dec_download_host(s, out->rev_comp, b.rc.p, n))) return e;
+    if (b.has_mis && ((e = dec_download_host(s, out->mis_cnt, b.cnt.p, n)) || (e = dec_download_host(s, out->mis_sym, b.sym.p, m)) || (e = dec_download_host(s, out->mis_rev_off, b.roff.p, m * w)))) return e;
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
     s->tm.bytes_down = n * w + n * 4 + (b.has_rc ? n : 0) + (b.has_mis ? n + m + m * w : 0);
     rl_done(s, PGRC_RLIST_DOWNLOAD, t0);
     return PGRC_OK;
 }
 
 static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, pgrc_rlist_archive *out) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     const RlBufs &b = s->cur;
     const uint64_t n = b.n, m = b.nmis, w = b.off_width;
@@ -383,12 +380,12 @@ static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, pgrc_rlist_archiv
     // the block: off | revComp | orgIdx | the archive form, each 16-byte aligned
     const uint64_t at_rc = dec_a16(n * w) + 16, at_org = at_rc + (b.has_rc ? dec_a16(n) + 16 : 0), at_la = at_org + (want_org ? dec_a16(n * 4) + 16 : 0);
     const uint64_t dev_bytes = at_la + (b.has_mis ? pgrc_la_device_bytes(n, m) : 0), host_bytes = at_la + (b.has_mis ? pgrc_la_host_bytes(n, m) : 0) + 16;
-    if ((e = pgrc_buf_unpooled(d, s->block, dev_bytes + 16))) return e;
+    if ((e = pgrc_buf_unpooled(s, s->block, dev_bytes + 16))) return e;
     uint8_t *ob = (uint8_t *)s->block.p;
-    HIP_TRY(d, s->ev.record(1, d->stream));
+    HIP_TRY(s, s->ev.record(1, s->stream));
     PgrcLaResident la{};
-    if (b.has_mis && (e = pgrc_la_encode_resident(d, (const uint8_t *)b.cnt.p, (const uint8_t *)b.sym.p, (const uint8_t *)b.roff.p, n, m, fast, ob + at_la, &la))) return e;
-    HIP_TRY(d, s->ev.record(2, d->stream));
+    if (b.has_mis && (e = pgrc_la_encode_resident(s, s->la, (const uint8_t *)b.cnt.p, (const uint8_t *)b.sym.p, (const uint8_t *)b.roff.p, n, m, fast, ob + at_la, &la))) return e;
+    HIP_TRY(s, s->ev.record(2, s->stream));
     if (w == 1) {
         if ((e = rl_narrow(s, (const uint16_t *)b.off.p, n, ob))) return e;
     } else if ((e = rl_copy(s, ob, b.off.p, n * 2))) {
@@ -396,21 +393,14 @@ static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, pgrc_rlist_archiv
     }
     if (b.has_rc && (e = rl_copy(s, ob + at_rc, b.rc.p, n))) return e;
     if (want_org && (e = rl_copy(s, ob + at_org, b.org.p, n * 4))) return e;
-    HIP_TRY(d, s->ev.record(3, d->stream));
+    HIP_TRY(s, s->ev.record(3, s->stream));
     // the streams end where the last of them ends
-    const uint64_t down = b.has_mis ? at_la + la.down : want_org ? at_org + n * 4 : b.has_rc ? at_rc + n : n * w;
+    const uint64_t end = b.has_mis ? at_la + la.down : want_org ? at_org + n * 4 : b.has_rc ? at_rc + n : n * w;
+    const DecBlockLayout<1> h = {{0}, {end}, host_bytes};     // (one part; the props go behind it)
+    const void *src[1] = {ob};
     uint8_t *blk = nullptr;
-    hipError_t he = hipHostMalloc((void **)&blk, host_bytes);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        return rl_fail(s, PGRC_E_ALLOC, "archive_encode: hipHostMalloc(" + std::to_string(host_bytes) + ") failed");
-    }
-    he = down ? hipMemcpyAsync(blk, ob, down, hipMemcpyDeviceToHost, d->stream) : hipSuccess;
-    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
-    if (he != hipSuccess) {
-        (void)hipHostFree(blk);
-        return rl_fail(s, pgrc_hip_code(he), std::string("archive_encode: copy down: ") + hipGetErrorString(he));
-    }
+    uint64_t down = 0;
+    if ((e = dec_download_block(s, "reads list: archive_encode", h, src, &blk, &down))) return e;
     out->struct_size = sizeof(pgrc_rlist_archive);
     out->off_width = (uint32_t)w;
     out->n_entries = n;
@@ -426,11 +416,10 @@ static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, pgrc_rlist_archiv
 }
 
 static int rl_pair_order(pgrc_rlist *s, pgrc_rlist *const lists[3], uint64_t T, int32_t form, pgrc_pairorder_streams *out) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     int e;
     if ((e = rl_begin(s))) return e;
-    if ((e = pgrc_buf_unpooled(d, s->join, T * 4 + 16))) return e;
+    if ((e = pgrc_buf_unpooled(s, s->join, T * 4 + 16))) return e;
     RlJoin j{};
     uint64_t end = 0;
     for (int l = 0; l < 3; l++) {
@@ -438,19 +427,18 @@ static int rl_pair_order(pgrc_rlist *s, pgrc_rlist *const lists[3], uint64_t T, 
         end += lists[l] ? lists[l]->cur.n : 0;
         j.end[l] = end;
     }
-    if (T) hipLaunchKernelGGL(k_rl_join, dim3(rl_grid(T)), dim3(RL_TPB), 0, d->stream, j, (uint32_t *)s->join.p);
-    HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, s->ev.record(1, d->stream));
-    if ((e = pgrc_pairorder_encode_joined(d, (const uint32_t *)s->join.p, T, form, out))) return e;
-    for (int k = 2; k < 4; k++) HIP_TRY(d, s->ev.record(k, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
-    s->tm.bytes_down = d->potm.bytes_down;
+    if (T) hipLaunchKernelGGL(k_rl_join, dim3(rl_grid(T)), dim3(RL_TPB), 0, s->stream, j, (uint32_t *)s->join.p);
+    HIP_TRY(s, hipGetLastError());
+    HIP_TRY(s, s->ev.record(1, s->stream));
+    if ((e = pgrc_pairorder_encode_joined(s, s->po, (const uint32_t *)s->join.p, T, form, out))) return e;
+    for (int k = 2; k < 4; k++) HIP_TRY(s, s->ev.record(k, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    s->tm.bytes_down = s->po.tm.bytes_down;
     rl_done(s, PGRC_RLIST_PAIR_ORDER, t0);
     return PGRC_OK;
 }
 
 static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pgrc_pairpos_streams *out) {
-    pgrc_decode_ctx *d = s->d;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t T = x->n_total;
     pgrc_match_ctx *c = x->matcher;
@@ -464,7 +452,7 @@ static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pg
             longest = std::max(longest, l->cur.n);
             writers += l->cur.n;
         }
-    if ((e = pgrc_bufs_unpooled(d, {{&s->pos, T * 8 + 16}, {&s->cls, T + 16}, {&s->words, 64}, {&s->scan, longest * 8 + 16}}))) return e;
+    if ((e = pgrc_bufs_unpooled(s, {{&s->pos, T * 8 + 16}, {&s->cls, T + 16}, {&s->words, 64}, {&s->scan, longest * 8 + 16}}))) return e;
     uint64_t *pos = (uint64_t *)s->pos.p;
     uint8_t *cls = (uint8_t *)s->cls.p;
     uint32_t *bad = (uint32_t *)s->words.p;
@@ -476,67 +464,66 @@ static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pg
         if (x->sets) {
             if ((e = rl_reads_org(s, x->sets, c->n, "pair_positions", &d_rorg))) return e;
         } else if (x->read_org_idx) {
-            if ((e = pgrc_buf_unpooled(d, s->map, c->n * 4 + 16)) || (e = dec_upload_host(d, s->map.p, x->read_org_idx, c->n * 4))) return e;
+            if ((e = pgrc_buf_unpooled(s, s->map, c->n * 4 + 16)) || (e = dec_upload_host(s, s->map.p, x->read_org_idx, c->n * 4))) return e;
             s->tm.bytes_up = c->n * 4;
             d_rorg = (const uint32_t *)s->map.p;
         }
-        HIP_TRY(d, hipEventRecord(s->ev_x[0], c->stream));
-        HIP_TRY(d, hipStreamWaitEvent(d->stream, s->ev_x[0], 0));
+        HIP_TRY(s, hipEventRecord(s->ev_x[0], c->stream));
+        HIP_TRY(s, hipStreamWaitEvent(s->stream, s->ev_x[0], 0));
         d_mpos = (const uint64_t *)c->d_pos.p;
-        if ((e = dec_scan<false>(d, XfBelow{d_mpos, PGRC_NOT_MATCHED_POS}, c->n, 0, (uint64_t *)s->scan.p))) return e;
-        HIP_TRY(d, hipMemcpyAsync(&matched, (const uint64_t *)s->scan.p + c->n, 8, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(d, hipStreamSynchronize(d->stream));
+        if ((e = dec_scan<false>(s, XfBelow{d_mpos, PGRC_NOT_MATCHED_POS}, c->n, 0, (uint64_t *)s->scan.p))) return e;
+        HIP_TRY(s, hipMemcpyAsync(&matched, (const uint64_t *)s->scan.p + c->n, 8, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
         writers += matched;
     }
     // nothing is launched for an input that cannot write every index once
     if (writers != T)
         return rl_fail(s, PGRC_E_PARAM, "pair_positions: the lists and the matched reads are " + std::to_string(writers) + ", n_total is " + std::to_string(T) +
                                             (writers > T ? ": an index is written twice" : ": an index is never written"));
-    if (T) HIP_TRY(d, hipMemsetAsync(pos, 0xFF, T * 8, d->stream));      // vector<uint_pg_len_max>(readsTotalCount, -1)
-    if (T) HIP_TRY(d, hipMemsetAsync(cls, 0, T, d->stream));
-    HIP_TRY(d, hipMemsetAsync(bad, 0, 64, d->stream));
-    if ((e = pgrc_buf_unpooled(d, d->scratch, sco_scratch_elems(longest) * sizeof(uint64_t)))) return e;
+    if (T) HIP_TRY(s, hipMemsetAsync(pos, 0xFF, T * 8, s->stream));      // vector<uint_pg_len_max>(readsTotalCount, -1)
+    if (T) HIP_TRY(s, hipMemsetAsync(cls, 0, T, s->stream));
+    HIP_TRY(s, hipMemsetAsync(bad, 0, 64, s->stream));
+    if ((e = pgrc_buf_unpooled(s, s->scratch, sco_scratch_elems(longest) * sizeof(uint64_t)))) return e;
     for (int pass = 0; pass < 2; pass++) {
         for (int l = 0; l < 3; l++) {
             if (!lists[l] || !lists[l]->cur.n) continue;
             const RlBufs &b = lists[l]->cur;
             const RlPosOut o{(const uint32_t *)b.org.p, T, pos, cls, bad, (uint8_t)(l + 1), pass == 1};
-            HIP_TRY(d, (sco_device_scan<true, false>(d->stream, XfU16{(const uint16_t *)b.off.p}, b.n, ScoPlus{}, (uint64_t)0, base[l], o, (uint64_t *)d->scratch.p)));
+            HIP_TRY(s, (sco_device_scan<true, false>(s->stream, XfU16{(const uint16_t *)b.off.p}, b.n, ScoPlus{}, (uint64_t)0, base[l], o, (uint64_t *)s->scratch.p)));
         }
-        if (c && c->n) hipLaunchKernelGGL(k_rl_pos_matched, dim3(rl_grid(c->n)), dim3(RL_TPB), 0, d->stream, d_mpos, c->n, d_rorg, T, pass == 1, pos, cls, bad);
-        HIP_TRY(d, hipGetLastError());
+        if (c && c->n) hipLaunchKernelGGL(k_rl_pos_matched, dim3(rl_grid(c->n)), dim3(RL_TPB), 0, s->stream, d_mpos, c->n, d_rorg, T, pass == 1, pos, cls, bad);
+        HIP_TRY(s, hipGetLastError());
     }
-    if (T) hipLaunchKernelGGL(k_rl_pos_never, dim3(rl_grid(T)), dim3(RL_TPB), 0, d->stream, (const uint8_t *)cls, T, bad);
-    HIP_TRY(d, hipGetLastError());
-    HIP_TRY(d, s->ev.record(1, d->stream));
+    if (T) hipLaunchKernelGGL(k_rl_pos_never, dim3(rl_grid(T)), dim3(RL_TPB), 0, s->stream, (const uint8_t *)cls, T, bad);
+    HIP_TRY(s, hipGetLastError());
+    HIP_TRY(s, s->ev.record(1, s->stream));
     uint32_t h_bad[RL_BAD_WORDS] = {};
-    HIP_TRY(d, hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    HIP_TRY(s, hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
     if (h_bad[RL_BAD_RANGE]) return rl_fail(s, PGRC_E_PARAM, "pair_positions: an original index of " + std::to_string(T) + " (n_total) or more");
     if (h_bad[RL_BAD_TWICE] || h_bad[RL_BAD_NEVER]) return rl_fail(s, PGRC_E_PARAM, "pair_positions: an index is written twice and another never");
-    if ((e = pgrc_pairpos_encode_device(d, pos, T, x->pos_width, out))) return e;
-    for (int k = 2; k < 4; k++) HIP_TRY(d, s->ev.record(k, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
-    s->tm.bytes_down = d->ptm.bytes_down;
+    if ((e = pgrc_pairpos_encode_device(s, s->pp, pos, T, x->pos_width, out))) return e;
+    for (int k = 2; k < 4; k++) HIP_TRY(s, s->ev.record(k, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    s->tm.bytes_down = s->pp.tm.bytes_down;
     rl_done(s, PGRC_RLIST_PAIR_POSITIONS, t0);
     return PGRC_OK;
 }
 
 extern "C" {
 
-const char *pgrc_rlist_last_error(const pgrc_rlist *s) { return s ? s->d->err.c_str() : g_rl_create_err.c_str(); }
+const char *pgrc_rlist_last_error(const pgrc_rlist *s) { return s ? s->err.c_str() : g_rl_create_err.c_str(); }
 
 int pgrc_rlist_create(int32_t device, pgrc_rlist **out) {
     if (!out) return PGRC_E_PARAM;
     *out = nullptr;
-    pgrc_decode_ctx *d = nullptr;
-    const int e = pgrc_decode_create_on(device, &d);
+    pgrc_rlist *s = new pgrc_rlist();
+    const int e = pgrc_stage_open(s, device, &g_rl_create_err);
     if (e) {
-        g_rl_create_err = std::string("reads list: ") + pgrc_decode_last_error(nullptr);
+        g_rl_create_err = "reads list: " + g_rl_create_err;
+        delete s;
         return e;
     }
-    pgrc_rlist *s = new pgrc_rlist();
-    s->d = d;
     *out = s;
     return PGRC_OK;
 }
@@ -544,15 +531,18 @@ int pgrc_rlist_create(int32_t device, pgrc_rlist **out) {
 void pgrc_rlist_destroy(pgrc_rlist *s) {
     if (!s) return;
     {
-        PgrcDeviceScope scope(s->d->device);
-        (void)hipStreamSynchronize(s->d->stream);
+        PgrcDeviceScope scope(s->device);
+        (void)hipStreamSynchronize(s->stream);
         rl_free(s->cur);
-        dec_free_all({&s->map, &s->words, &s->block, &s->join, &s->pos, &s->scan, &s->cls});
+        dec_free_all(rl_bufs(s));
+        s->la.release();
+        s->po.release();
+        s->pp.release();
         s->ev.release();
         for (hipEvent_t ev : s->ev_x)
             if (ev) (void)hipEventDestroy(ev);
     }
-    pgrc_decode_destroy(s->d);
+    pgrc_stage_close(s);
     delete s;
 }
 
@@ -589,7 +579,7 @@ int pgrc_rlist_set_host(pgrc_rlist *s, const pgrc_export_streams *in) {
     if (have != 0 && have != 3) return rl_fail(s, PGRC_E_PARAM, "set_host: the mismatch streams are all present or all absent");
     const bool mis = have == 3;
     if (!mis && in->n_mismatches) return rl_fail(s, PGRC_E_PARAM, "set_host: n_mismatches without the mismatch streams");
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     return rl_set_host(s, in);
 }
 
@@ -598,8 +588,8 @@ int pgrc_rlist_from_assembly(pgrc_rlist *s, pgrc_asm_ctx *a, pgrc_rsets *sets, i
     if (!a) return rl_fail(s, PGRC_E_PARAM, "from_assembly: the assembly context is NULL");
     PgasmLastList l;
     pgasm_last_list(a, &l);
-    if (l.device != s->d->device) return rl_fail(s, PGRC_E_PARAM, "from_assembly: the assembly context is on another device");
-    if (sets && sets->device != s->d->device) return rl_fail(s, PGRC_E_PARAM, "from_assembly: the read sets are on another device");
+    if (l.device != s->device) return rl_fail(s, PGRC_E_PARAM, "from_assembly: the assembly context is on another device");
+    if (sets && sets->device != s->device) return rl_fail(s, PGRC_E_PARAM, "from_assembly: the read sets are on another device");
     if (sets && (which < PGRC_RSETS_HQ || which > PGRC_RSETS_N)) return rl_fail(s, PGRC_E_PARAM, "from_assembly: which is PGRC_RSETS_HQ, PGRC_RSETS_LQ or PGRC_RSETS_N");
     if (!l.valid) return rl_fail(s, PGRC_E_STATE, "from_assembly: no run has succeeded on the assembly context");
     if (sets && l.mapped) return rl_fail(s, PGRC_E_STATE, "from_assembly: the assembly run has applied a host mapping already");
@@ -607,7 +597,7 @@ int pgrc_rlist_from_assembly(pgrc_rlist *s, pgrc_asm_ctx *a, pgrc_rsets *sets, i
     uint64_t count = 0;
     int e;
     if (sets && (e = pgrc_rsets_mapping_device(sets, which, &d_map, &count))) return rl_fail(s, e, std::string("from_assembly: ") + pgrc_rsets_last_error(sets));
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     return rl_from_assembly(s, l, d_map, count);
 }
 
@@ -615,7 +605,7 @@ int pgrc_rlist_from_overlap(pgrc_rlist *s, pgrc_ovl_ctx *ovl, pgrc_asm_ctx *a, p
     if (!s) return PGRC_E_PARAM;
     if (res) *res = pgrc_asm_result{};
     if (!ovl || !a || !res) return rl_fail(s, PGRC_E_PARAM, "from_overlap: the overlap context, the assembly context or the result is NULL");
-    if (pgovl_device(ovl) != s->d->device) return rl_fail(s, PGRC_E_PARAM, "from_overlap: the overlap context is on another device");
+    if (pgovl_device(ovl) != s->device) return rl_fail(s, PGRC_E_PARAM, "from_overlap: the overlap context is on another device");
     int e;
     if ((e = pgovl_assemble(ovl, a, nullptr, res, true))) return rl_fail(s, e, std::string("from_overlap: ") + pgrc_ovl_last_error(ovl));
     if ((e = pgrc_rlist_from_assembly(s, a, sets, which))) *res = pgrc_asm_result{};
@@ -630,8 +620,8 @@ int pgrc_rlist_export_pg_order(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlis
     int e;
     if ((e = rl_matcher_ok(s, c, "export_pg_order"))) return e;
     if (s->cur.has_mis) return rl_fail(s, PGRC_E_STATE, "export_pg_order: the list carries mismatches already");
-    PGRC_ON_DEVICE(s->d);
-    if ((e = rl_export(s, c, x))) (void)hipStreamSynchronize(s->d->stream);
+    PGRC_ON_DEVICE(s);
+    if ((e = rl_export(s, c, x))) (void)hipStreamSynchronize(s->stream);
     return e;
 }
 
@@ -639,10 +629,10 @@ int pgrc_rlist_download(pgrc_rlist *s, pgrc_export_streams *out) {
     if (!s) return PGRC_E_PARAM;
     if (!out) return rl_fail(s, PGRC_E_PARAM, "download: out is NULL");
     memset(out, 0, sizeof *out);
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     const int e = rl_download_run(s, out);
     if (e) {
-        (void)hipStreamSynchronize(s->d->stream);
+        (void)hipStreamSynchronize(s->stream);
         pgrc_match_free_export(out);
     }
     return e;
@@ -654,10 +644,10 @@ int pgrc_rlist_archive_encode(pgrc_rlist *s, int32_t fast_level, int32_t want_or
     *out = pgrc_rlist_archive{};
     if (s->cur.has_mis && s->cur.off_width != 1)
         return rl_fail(s, PGRC_E_PARAM, "archive_encode: offsets of " + std::to_string(s->cur.off_width) + " bytes (the archive's loader reads one byte each)");
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     const int e = rl_archive(s, fast_level != 0, want_org_idx != 0, out);
     if (e) {
-        (void)hipStreamSynchronize(s->d->stream);
+        (void)hipStreamSynchronize(s->stream);
         *out = pgrc_rlist_archive{};
     }
     return e;
@@ -678,12 +668,12 @@ int pgrc_rlist_pair_order(pgrc_rlist *const lists[3], int32_t form, pgrc_pairord
     uint64_t T = 0;
     for (int l = 0; l < 3; l++) {
         if (!lists[l]) continue;
-        if (lists[l]->d->device != s->d->device) return rl_fail(s, PGRC_E_PARAM, "pair_order: the lists are on different devices");
+        if (lists[l]->device != s->device) return rl_fail(s, PGRC_E_PARAM, "pair_order: the lists are on different devices");
         T += lists[l]->cur.n;
     }
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     const int e = rl_pair_order(s, lists, T, form, out);
-    if (e) (void)hipStreamSynchronize(s->d->stream);
+    if (e) (void)hipStreamSynchronize(s->stream);
     return e;
 }
 
@@ -695,15 +685,15 @@ int pgrc_rlist_pair_positions(const pgrc_rlist_pairpos_args *x, pgrc_pairpos_str
     *out = pgrc_pairpos_streams{};
     if (x->sets && x->read_org_idx) return rl_fail(s, PGRC_E_PARAM, "pair_positions: the reads' original indexes are given twice (read_org_idx and sets)");
     for (pgrc_rlist *l : {x->lq, x->n})
-        if (l && l->d->device != s->d->device) return rl_fail(s, PGRC_E_PARAM, "pair_positions: the lists are on different devices");
+        if (l && l->device != s->device) return rl_fail(s, PGRC_E_PARAM, "pair_positions: the lists are on different devices");
     int e;
     if (x->matcher) {
         if ((e = rl_matcher_ok(s, x->matcher, "pair_positions"))) return e;
         if (!x->matcher->have_results || !x->matcher->d_pos.p) return rl_fail(s, PGRC_E_STATE, "pair_positions: the matcher has no results");
     }
-    PGRC_ON_DEVICE(s->d);
+    PGRC_ON_DEVICE(s);
     if ((e = rl_pair_positions(s, x, out))) {
-        (void)hipStreamSynchronize(s->d->stream);
+        (void)hipStreamSynchronize(s->stream);
         *out = pgrc_pairpos_streams{};
     }
     return e;

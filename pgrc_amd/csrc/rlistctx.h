@@ -1,12 +1,14 @@
 // rlistctx.h -- a pseudogenome's reads list on the device (include/pgrc_readslist.h, rlist.hip) and what rlist.hip uses of the
 // contexts that fill and consume it: the assembly (pgasm.hip), the read sets (readsets.hip), the matcher's export
 // (export.hip), the archive form (listarchive.hip), the pair order (pairorder.hip) and the pair positions (pairpos.hip).
-// Every hook is a C++ function: exports.map keeps it out of the library's dynamic symbols.  The list works on a decode context
-// (decctx.h), whose base is the stage handle of stagectx.h.
+// Every hook is a C++ function: exports.map keeps it out of the library's dynamic symbols.  The list is a stage handle
+// (stagectx.h) with the states of the three codings it runs (codingctx.h) and its own buffers on top; the coders' hooks take
+// the stage and the state.
 #pragma once
 
 #include "pgrc_assemble.h"
 #include "pgrc_readslist.h"
+#include "codingctx.h"
 #include "rsetsctx.h"
 
 // off (u16), org_idx (u32) and the optional streams of one list; every buffer is exactly the list's (grow-only scratch lies
@@ -18,10 +20,10 @@ struct RlBufs {
     bool has_rc = false, has_mis = false;
 };
 
-struct pgrc_rlist {
-    // The stage handle (stagectx.h), and a decode context because the list archive, the pair order and the pair positions run
-    // on one; its read length belongs to the archive form's decode side alone and is not used here
-    pgrc_decode_ctx *d = nullptr;
+struct pgrc_rlist : PgrcStage {
+    PgrcListArchive la;                 // the encode halves of the three codings run on this stage with these states
+    PgrcPairOrder po;
+    PgrcPairPos pp;
     RlBufs cur;
     // scratch (grow-only): a mapping / the reads' original indexes, the words of the checks, the device side of the archive
     // block, the joined lists, positions and their scan, the class bytes
@@ -81,11 +83,11 @@ struct PgrcLaResident {
 };
 uint64_t pgrc_la_device_bytes(uint64_t n, uint64_t m);
 uint64_t pgrc_la_host_bytes(uint64_t n, uint64_t m);
-int pgrc_la_encode_resident(pgrc_decode_ctx *d, const uint8_t *d_cnt, const uint8_t *d_sym, const uint8_t *d_off, uint64_t n, uint64_t m, bool fast, uint8_t *d_block,
-                            PgrcLaResident *res);
+int pgrc_la_encode_resident(PgrcStage *s, PgrcListArchive &st, const uint8_t *d_cnt, const uint8_t *d_sym, const uint8_t *d_off, uint64_t n, uint64_t m, bool fast,
+                            uint8_t *d_block, PgrcLaResident *res);
 void pgrc_la_describe_resident(pgrc_list_archive_streams *out, uint8_t *blk, uint64_t n, uint64_t m, bool fast, const PgrcLaResident *res);
 
-// pairorder.hip: pgrc_pairorder_encode on the joined array in memory of the context's device
-int pgrc_pairorder_encode_joined(pgrc_decode_ctx *d, const uint32_t *d_joined, uint64_t T, int32_t form, pgrc_pairorder_streams *out);
-// pairpos.hip: pgrc_pairpos_encode on positions in memory of the context's device, read where they lie
-int pgrc_pairpos_encode_device(pgrc_decode_ctx *d, const uint64_t *d_org_idx_to_pos, uint64_t n_total, uint32_t pos_width, pgrc_pairpos_streams *out);
+// pairorder.hip: pgrc_pairorder_encode on the joined array in memory of the stage's device
+int pgrc_pairorder_encode_joined(PgrcStage *s, PgrcPairOrder &st, const uint32_t *d_joined, uint64_t T, int32_t form, pgrc_pairorder_streams *out);
+// pairpos.hip: pgrc_pairpos_encode on positions in memory of the stage's device, read where they lie
+int pgrc_pairpos_encode_device(PgrcStage *s, PgrcPairPos &st, const uint64_t *d_org_idx_to_pos, uint64_t n_total, uint32_t pos_width, pgrc_pairpos_streams *out);

@@ -1,8 +1,9 @@
 // stagectx.h -- the stage handle: what every encoder and decoder stage beside the matcher needs of the device.  A stage is a
 // PgrcDev (device, stream, error text) with two page-locked staging buffers, the events that guard their reuse, a flag word
 // for device-side findings and a grow-only scratch for the shared scan.  The decode context (decctx.h) is one with the decoder's
-// state on top; the overlap search (pgovl.hip), the read sets (rsetsctx.h) and the verifier (verifyctx.h) are one with their
-// own buffers on top; the assembly (pgasm.hip) and the reads list (rlistctx.h) keep a decode context.  DESIGN.md 4.22.
+// state on top; the overlap search (pgovl.hip), the read sets (rsetsctx.h), the reads list (rlistctx.h) and the verifier
+// (verifyctx.h) are one with their own buffers on top; the assembly (pgasm.hip) keeps a decode context.  The list codings'
+// states (codingctx.h) run on any of them.  DESIGN.md 4.22.
 #pragma once
 
 #include <string.h>
@@ -81,6 +82,49 @@ static int dec_download_host(PgrcStage *d, void *h_dst, const void *d_src, uint6
         HIP_TRY(d, hipStreamSynchronize(d->stream));
         memcpy((uint8_t *)h_dst + o, d->stage[0], c);
     }
+    return PGRC_OK;
+}
+
+// A result block: N parts one behind the other in one page-locked block, each at a 16-byte aligned place with 16 bytes behind it
+template <int N>
+struct DecBlockLayout {
+    uint64_t at[N], bytes[N], total;
+};
+template <int N>
+static DecBlockLayout<N> dec_block_layout(const uint64_t (&bytes)[N]) {
+    DecBlockLayout<N> o;
+    o.total = 0;
+    for (int k = 0; k < N; k++) {
+        o.at[k] = o.total;
+        o.bytes[k] = bytes[k];
+        o.total += dec_a16(bytes[k]) + 16;
+    }
+    return o;
+}
+
+// the block of `h.total` bytes (it may exceed the parts: room for what the host writes behind them) with every non-empty part
+// copied from src[k] after all that is queued on the stream; returns with the stream idle, the block at *blk (the caller's, to
+// give back with hipHostFree) and the copied bytes in *down.  A failure leaves no block.
+template <int N>
+static int dec_download_block(PgrcStage *d, const std::string &who, const DecBlockLayout<N> &h, const void *const (&src)[N], uint8_t **blk, uint64_t *down) {
+    *blk = nullptr;
+    *down = 0;
+    uint8_t *b = nullptr;
+    hipError_t he = hipHostMalloc((void **)&b, h.total);
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        return dec_fail(d, PGRC_E_ALLOC, who + ": hipHostMalloc(" + std::to_string(h.total) + ") failed");
+    }
+    for (int k = 0; k < N && he == hipSuccess; k++) {
+        if (h.bytes[k]) he = hipMemcpyAsync(b + h.at[k], src[k], h.bytes[k], hipMemcpyDeviceToHost, d->stream);
+        *down += h.bytes[k];
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize(d->stream);
+    if (he != hipSuccess) {
+        (void)hipHostFree(b);
+        return dec_fail(d, pgrc_hip_code(he), who + ": copy down: " + hipGetErrorString(he));
+    }
+    *blk = b;
     return PGRC_OK;
 }
 

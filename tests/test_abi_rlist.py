@@ -116,3 +116,16 @@ def test_null_arguments_are_refused_without_a_device():
     a = _lib.RlistPairPosArgs(C.sizeof(_lib.RlistPairPosArgs), 4, 0)
     assert lib.pgrc_rlist_pair_positions(None, C.byref(pp)) == E_PARAM and lib.pgrc_rlist_pair_positions(C.byref(a), C.byref(pp)) == E_PARAM
     assert isinstance(lib.pgrc_rlist_last_error(None), bytes)
+
+
+def test_create_names_the_missing_device():
+    """the reads list opens a stage handle of its own: without a device its create is PGRC_E_NO_DEVICE with the stage's text
+    behind the list's prefix"""
+    import torch
+    from pgrc_amd import _lib
+    if torch.cuda.is_available():
+        return
+    lib = _lib.lib
+    h = C.c_void_p()
+    assert lib.pgrc_rlist_create(-1, C.byref(h)) == 3 and not h.value
+    assert lib.pgrc_rlist_last_error(None) == b"reads list: no HIP device"

@@ -561,3 +561,77 @@ def test_chain_from_the_assembly_to_the_pair_order():
     assert up == [0] * len(up)
     for x in [hq, ctx, dec, ovl, asm, host_asm, sets, div] + rest:
         x.close()
+
+
+# ------------------------------------------------------------------------------------------------ the list's own coding states
+def archive_block(lst, fast=False, want_org=True):
+    """pgrc_rlist_archive_encode itself -> (the block's bytes as they came down, its archive form)"""
+    import ctypes as C
+    from pgrc_amd import _lib
+    from pgrc_amd.decode import _list_archive_dict
+    a = _lib.RlistArchive()
+    code = _lib.lib.pgrc_rlist_archive_encode(lst._h, int(fast), int(want_org), C.byref(a))
+    assert code == 0, _lib.lib.pgrc_rlist_last_error(lst._h)
+    try:
+        assert a.off == a.block and lst.timing()["bytes_down"] == a.block_bytes
+        return C.string_at(a.block, int(a.block_bytes)), _list_archive_dict(a.archive, a.block)
+    finally:
+        _lib.lib.pgrc_rlist_archive_free(C.byref(a))
+
+
+def test_coding_states_of_a_list_neither_share_nor_clobber():
+    """one list handle runs the archive form, the pair order, the pair positions and the archive form again, a decode context
+    of its own codes the same data in between: the two archive blocks are the same bytes, and every coding gives what the
+    decode context gives.  The sizes are the smallest that cross the archive tile (TILE + 1 entries) and the scan block
+    (4097 pairs); the tile being 8192, the list with the mismatches holds all but one of the 8194 entries, the LQ list the
+    last one and the N list none."""
+    n, pairs, L = TILE + 1, 4097, 40
+    T = 2 * pairs
+    sizes = (n, T - n, 0)
+    cnt, sym, rev_off = la.make_list(905, n, L)
+    assert sym.size > n // 4 and T > n
+    rng = np.random.default_rng(905)
+    org = po.make_order(905, pairs, **po.DEFAULT_MIX)
+    assert org.size == T
+    parts = np.split(org, np.cumsum(sizes)[:-1])
+    offs = [rng.integers(0, 250, size=k).astype(np.uint8) for k in sizes]
+    hq = ReadsList(0)
+    hq.set_host(offs[0], parts[0], (rng.random(n) < 0.5).astype(np.uint8), cnt, sym, rev_off)
+    rest = [simple_list(parts[k], offs[k]) for k in (1, 2)]
+    hq_len, lq_len = int(offs[0].sum()) + L, int(offs[1].sum()) + L
+    want_pos = rl.positions_numpy(T, (offs[0], parts[0]), (offs[1], parts[1]), (offs[2], parts[2]), hq_len, lq_len)
+    dec = PgRCDecoder(L, device=0)
+
+    block1, arch1 = archive_block(hq)
+    kept = hq.download()
+    want_arch = dec.list_archive_encode(kept["mis_cnt"], kept["mis_sym"], kept["mis_rev_off"])
+    la.assert_streams(arch1, want_arch)
+    for form in po.FORMS:
+        got = ReadsList.pair_order([hq] + rest, form)
+        assert_pairorder(got, dec.compressReadsOrder(parts, form))
+        assert hq.timing()["bytes_down"] == dec.pairorder_timing()["bytes_down"]
+    for W in (4, 8):
+        got = hq.pair_positions(T, W, rest[0], rest[1], hq_len, lq_len)
+        assert_pairpos(got, dec.compressReadsPgPositions(want_pos, W))
+        assert hq.timing()["bytes_down"] == dec.pairpos_timing()["bytes_down"]
+    la.assert_streams(dec.list_archive_encode(cnt, sym, rev_off), want_arch)
+    block2, arch2 = archive_block(hq)
+    assert block1 == block2 and len(block1) >= 6 * n + 2 * sym.size
+    la.assert_streams(arch2, want_arch)
+    same_streams(hq.download(), kept, "the list after its codings")
+    for x in [hq, dec] + rest:
+        x.close()
+
+
+def test_a_list_closes_unused_and_after_a_refusal():
+    ReadsList(0).close()                                    # no call: no coding state has a buffer or an event
+    lst = ReadsList(0)
+    refused(E_STATE, lst.timing)
+    refused(E_PARAM, lst.set_host, np.zeros(4, np.uint8), np.arange(4, dtype=np.uint32), None, np.ones(4, np.uint8), None, None)
+    refused(E_PARAM, ReadsList.pair_order, [lst], 9)
+    lst.close()
+    lst.close()                                             # (a second close is nothing)
+    again = simple_list(np.arange(6, dtype=np.uint32)[::-1])
+    assert np.array_equal(again.download()["org_idx"], np.arange(6, dtype=np.uint32)[::-1])
+    assert_pairorder(ReadsList.pair_order([again], po.IGNORE), po.compress_parallel(np.arange(6, dtype=np.uint32)[::-1], po.IGNORE))
+    again.close()
