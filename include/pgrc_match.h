@@ -301,6 +301,8 @@ int pgrc_match_get_redo_flags(pgrc_match_ctx *ctx, uint8_t *flags);
  *     PGRC_EARLY_STOP=0      every read probes all its seeds, as the reference does (and the two passes in turn)
  *     PGRC_ROUND_SKIP=0      the dual kernel probes every seed up to the early stop (default 1: between two rounds it
  *                            probes only round seeds until an acceptable candidate makes it go back; dualkern.h)
+ *     PGRC_DUAL_PACK=0       the dual kernel writes a finished read's position, strand and count with three stores (default 1:
+ *                            one packed 8-byte store, taken apart by a streaming pass right behind the kernel; dualkern.h)
  *     PGRC_BUILD_STREAMS=1   the two index builds of such a run on one stream instead of two
  *     PGRC_HEAD_PAIR=0|1..4  no pair table (a head table per strand) / groups of 1, 2, 4, 8 buckets (default 3 = groups of 4)
  *     PGRC_NREAD_INLINE=0    every read with an N takes the byte-path kernel (default: the dual kernel takes those with <= 4 N)

@@ -156,6 +156,7 @@ PgrcOptions pgrc_options_from_env() {
     o.screen = flag("PGRC_SCREEN");
     o.early_stop = flag("PGRC_EARLY_STOP") != 0;
     o.round_skip = flag("PGRC_ROUND_SKIP") != 0;
+    o.dual_pack = flag("PGRC_DUAL_PACK") != 0;
     o.builds_in_turn = flag("PGRC_BUILD_STREAMS") == 1;
     if (const char *hp = getenv("PGRC_HEAD_PAIR")) o.head_pair = hp[0] == '0' ? 0u : (hp[0] >= '1' && hp[0] <= '4') ? 1u << (hp[0] - '1') : 4u;
     if (const char *is = getenv("PGRC_INDEX_SORT")) o.index_front = !strcmp(is, "own") ? 1 : 0;

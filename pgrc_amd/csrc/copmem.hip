@@ -836,6 +836,7 @@ int pgrc_copmem_match_dual(pgrc_match_ctx *c) {
     a.mask = c->cp.hash_size - 1;
     a.kmax = c->prm.max_mismatches;
     a.skip = c->opt.round_skip ? 1u : 0u;                // PGRC_ROUND_SKIP=0: every seed up to the early stop (A/B runs, tests)
+    a.pack = c->opt.dual_pack ? 1u : 0u;                 // PGRC_DUAL_PACK=0: three stores per finished read and no unpack pass (A/B runs, tests)
     switch (c->nw) {
 #define CASE_NW(N) case N: launch_dual<N>(c, a); break;
         CASE_NW(2) CASE_NW(3) CASE_NW(4) CASE_NW(5) CASE_NW(6) CASE_NW(7) CASE_NW(8) CASE_NW(9)
@@ -846,6 +847,9 @@ int pgrc_copmem_match_dual(pgrc_match_ctx *c) {
         return PGRC_E_PARAM;
     }
     HIP_TRY(c, hipGetLastError());
+    // the packed words of this range are taken apart right behind the kernel, on the same stream: whoever waits for the
+    // kernel (a streamed block's download, the N kernel's event, a sharded context's front) waits for the pass too
+    if (a.pack) return pgrc_launch_unpack_results(c, lo, rn);
     return PGRC_OK;
 }
 

@@ -54,6 +54,7 @@ struct PgrcOptions {
     int screen = -1;                // PGRC_SCREEN      -1 not asked for, 0 never, 1 whenever the screened schedule applies
     bool early_stop = true;         // PGRC_EARLY_STOP=0: every read probes all its seeds, as the reference does
     bool round_skip = true;         // PGRC_ROUND_SKIP=0: the dual kernel probes every seed up to the early stop (no round skip)
+    bool dual_pack = true;          // PGRC_DUAL_PACK=0: the dual kernel stores a finished read's pos, rc and mism apart (no packed word, no unpack pass)
     bool builds_in_turn = false;    // PGRC_BUILD_STREAMS=1: the two index builds of a two-strand run on one stream
     uint32_t head_pair = 4;         // PGRC_HEAD_PAIR   0: a head table per strand; 1..4: pair table with groups of 1, 2, 4, 8 buckets
     int index_front = 0;            // PGRC_INDEX_SORT  0 "sweep" (idxsweep.hip), 1 "own" (idxsort.hip's stable scatter passes)
@@ -386,6 +387,14 @@ int pgrc_seedidx_run(pgrc_match_ctx *c, int first_strand, int last_strand);
 // results.hip
 int pgrc_launch_init_results(pgrc_match_ctx *c);
 int pgrc_launch_hist(pgrc_match_ctx *c);
+// The dual kernel's packed result word in pos[] (dualkern.h, "The packed result"): position (< 2^40: api.hip alloc_pg) |
+// count << 40 | strand << 48 | tag.  Bit 62 set and bit 63 clear: neither a plain position (both clear) nor
+// PGRC_NOT_MATCHED_POS (both set).
+#define RES_PACK_MISM_SHIFT 40
+#define RES_PACK_RC_SHIFT 48
+#define RES_PACK_TAG (1ull << 62)
+#define RES_PACK_POS_MASK ((1ull << 40) - 1ull)
+int pgrc_launch_unpack_results(pgrc_match_ctx *c, uint64_t lo, uint64_t n);   // queued on c->stream: reads lo .. lo + n - 1
 int pgrc_extract_mismatches(pgrc_match_ctx *c, const uint8_t *reversed_flags, uint64_t *cum, uint8_t *codes,
                             uint16_t *offsets);
 int pgrc_extract_lists_device(pgrc_match_ctx *c, const uint8_t *d_revflags, bool lists, DevBuf &d_cum, DevBuf &d_codes, DevBuf &d_offs,

@@ -64,6 +64,16 @@
 // the compiler cannot see through, so that they are not kept in registers through every iteration: the C3 instance is at 70
 // registers (77 before).  tests/test_gpu_dual_entry_walk.py holds the walk to the oracle and to the parent kernel's counters
 // on planted repeat families.
+//
+// The packed result (a.pack; PGRC_DUAL_PACK=0 turns it off).  A lane that finishes a matched read stored its position, strand
+// and count to three arrays; lanes finish at different times, so each was a partial-line write of its own: 1.6 * 10^8 write
+// requests and 7.1 GB per launch at C3 for 0.9 GB of results (profiles/packed_result_pmc.txt).  Now it is ONE 8-byte store to
+// pos[]: position | count << 40 | strand << 48 | 1 << 62 (ctx.h RES_PACK_*; positions stay below 2^40: api.hip pgrc_pg_alloc).
+// Bit 62 set and bit 63 clear is neither a plain position nor PGRC_NOT_MATCHED_POS, so k_unpack_results (results.hip), queued
+// right behind the kernel over the same reads, knows the words this launch wrote, stores their three values in full lines and
+// touches no other read: one whose query found nothing keeps what it came with (a second-phase run), a read of the byte path
+// is the N kernel's.  The kernel itself reads mism[] only in the refill, for reads it has not started, and pos[] / rc[] never, so
+// no lane ever sees a packed word.  tests/test_gpu_dual_packed_result.py holds both forms to the oracle and to each other.
 #pragma once
 
 #include "ctx.h"
@@ -89,6 +99,7 @@ struct DualArgs {
     uint32_t L, K, k1, k2, mask, kmax;
     uint32_t chunk;               // reads a wave reserves per visit to the work counter (pgrc_match_chunk)
     uint32_t skip;                // 1: the round skip (see above); 0: every seed up to the early stop (PGRC_ROUND_SKIP=0)
+    uint32_t pack;                // 1: a finished read is ONE store, the packed word in pos[] (see above); 0: three stores (PGRC_DUAL_PACK=0)
 };
 
 // reads a wave stages in LDS per burst of full-line loads: 16 at six waves per SIMD (LDS for six blocks per CU), else 32
@@ -603,14 +614,17 @@ k_copmem_match_dual(const DualArgs a) {
         if (fin) {
             // the read is finished: forward wins ties, RC must be strictly better (ReadsMatchers.cpp:437-447, both passes)
             const uint32_t cur0 = DK_CUR(0u), cur1 = DK_CUR(1u);
-            if ((fl & F_FOUND1) && !((fl & F_FOUND0) && cur0 <= cur1)) {
-                a.pos[idx] = a.G - ((uint64_t)best1 + a.L);
-                a.rc[idx] = 1;
-                a.mism[idx] = (uint8_t)cur1;
-            } else if (fl & F_FOUND0) {
-                a.pos[idx] = (uint64_t)best0;
-                a.rc[idx] = 0;
-                a.mism[idx] = (uint8_t)cur0;
+            const bool rcw = (fl & F_FOUND1) && !((fl & F_FOUND0) && cur0 <= cur1);
+            if (rcw || (fl & F_FOUND0)) {
+                const uint64_t p = rcw ? a.G - ((uint64_t)best1 + a.L) : (uint64_t)best0;
+                const uint32_t m = rcw ? cur1 : cur0;
+                if (a.pack) {                                        // (wave-uniform) one store; k_unpack_results takes it apart
+                    a.pos[idx] = p | ((uint64_t)m << RES_PACK_MISM_SHIFT) | ((uint64_t)rcw << RES_PACK_RC_SHIFT) | RES_PACK_TAG;
+                } else {
+                    a.pos[idx] = p;
+                    a.rc[idx] = (uint8_t)rcw;
+                    a.mism[idx] = (uint8_t)m;
+                }
             }
         }
         n_redo += (uint32_t)__popcll(__ballot(n_redo_it));

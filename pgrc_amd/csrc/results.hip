@@ -27,6 +27,30 @@ int pgrc_launch_init_results(pgrc_match_ctx *c) {
     return PGRC_OK;
 }
 
+// Takes the dual kernel's packed words apart (dualkern.h, "The packed result"): a tagged pos[i] becomes the clean
+// position, rc[i] and mism[i].  NOTHING is stored for a read without the tag, and rc / mism are written byte by byte, never
+// as read-modify-written vectors: beside this pass the N kernel on the side stream writes other reads' bytes of the same
+// lines, and in a second-phase run the untagged reads hold earlier results.
+__global__ void __launch_bounds__(256) k_unpack_results(uint64_t *pos, uint8_t *rc, uint8_t *mism, uint64_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t v = pos[i];
+        if ((v >> 62) == 1ull) {
+            pos[i] = v & RES_PACK_POS_MASK;
+            rc[i] = (uint8_t)((v >> RES_PACK_RC_SHIFT) & 1ull);
+            mism[i] = (uint8_t)(v >> RES_PACK_MISM_SHIFT);
+        }
+    }
+}
+
+int pgrc_launch_unpack_results(pgrc_match_ctx *c, uint64_t lo, uint64_t n) {
+    if (!n) return PGRC_OK;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->num_cus * 16u);
+    hipLaunchKernelGGL(k_unpack_results, dim3(grid), dim3(256), 0, c->stream, (uint64_t *)c->d_pos.p + lo, (uint8_t *)c->d_rc.p + lo,
+                       (uint8_t *)c->d_mism.p + lo, n);
+    HIP_TRY(c, hipGetLastError());
+    return PGRC_OK;
+}
+
 __global__ void __launch_bounds__(256) k_hist(const uint8_t *__restrict__ mism, uint64_t n, unsigned long long *hist) {
     __shared__ uint32_t h[256];
     h[threadIdx.x] = 0;
