@@ -382,11 +382,11 @@ void pgrc_match_destroy(pgrc_match_ctx *c) {
         (void)hipEventDestroy(c->build_ev[0]);
         (void)hipEventDestroy(c->build_ev[1]);
     }
-    DevBuf *bufs[] = {&c->pg2[0], &c->pg2[1], &c->reads_own, &c->nread_idx, &c->nread_ascii, &c->nread_flag, &c->nread_npos, &c->d_pos,
-                      &c->d_rc, &c->d_mism, &c->d_hist, &c->d_counters, &c->d_head, &c->d_headpair, &c->d_skey[0], &c->d_skey[1], &c->d_sval[0], &c->d_sval[1], &c->d_sorttmp,
-                      &c->alt_head, &c->alt_skey[0], &c->alt_skey[1], &c->alt_sval[0], &c->alt_sval[1], &c->alt_sorttmp, &c->d_scr_pos, &c->d_scr_flag,
-                      &c->s_keys, &c->s_filter, &c->s_vals, &c->s_tab, &c->s_hits, &c->s_tmp, &c->s_sort, &c->s_seg, &c->s_hv, &c->s_hvu, &c->s_nmask, &c->s_best, &c->s_rows};
-    pgrc_buf_free_all(bufs, sizeof bufs / sizeof bufs[0]);       // (the device is idle: waited for above)
+    DevBufList bufs = {&c->pg2[0], &c->pg2[1], &c->reads_own, &c->nread_idx, &c->nread_ascii, &c->nread_flag, &c->nread_npos, &c->d_pos,
+                       &c->d_rc, &c->d_mism, &c->d_hist, &c->d_counters, &c->d_headpair, &c->d_scr_pos, &c->d_scr_flag,
+                       &c->s_keys, &c->s_filter, &c->s_vals, &c->s_tab, &c->s_hits, &c->s_tmp, &c->s_sort, &c->s_seg, &c->s_hv, &c->s_hvu, &c->s_nmask, &c->s_best, &c->s_rows};
+    for (PgrcIndexSet &ix : c->idx) bufs.insert(bufs.end(), {&ix.head, &ix.skey[0], &ix.skey[1], &ix.sval[0], &ix.sval[1], &ix.sorttmp});
+    pgrc_buf_free_all(bufs.data(), bufs.size());                 // (the device is idle: waited for above)
     for (DevBuf &b : c->up_nchunks) pgrc_buf_free(b);
     if (c->have_events)
         for (auto &e : c->ev) (void)hipEventDestroy(e);
@@ -448,8 +448,7 @@ int pgrc_pg_alloc(pgrc_match_ctx *c, uint64_t G) {
     }
     c->have_pg = false;
     c->have_rc = false;
-    c->index_strand = -1;
-    c->alt_index_strand = -1;
+    for (PgrcIndexSet &ix : c->idx) ix.strand = -1;
     c->idx_prepared = false;
     if (c->prm.mode == 'c') {
         int r = pgrc_match_copmem_params(c->prm.seed_len, G, &c->cp);
@@ -861,24 +860,6 @@ int pgrc_match_set_results(pgrc_match_ctx *c, const uint64_t *pos, const uint8_t
     return PGRC_OK;
 }
 
-// the two sets of index buffers of the screened schedule swap roles
-static void swap_index_sets(pgrc_match_ctx *c) {
-    std::swap(c->d_head, c->alt_head);
-    std::swap(c->head_ptr, c->alt_head_ptr);
-    std::swap(c->head_sh, c->alt_head_sh);
-    for (int k = 0; k < 2; k++) {
-        std::swap(c->d_skey[k], c->alt_skey[k]);
-        std::swap(c->d_sval[k], c->alt_sval[k]);
-    }
-    std::swap(c->d_sorttmp, c->alt_sorttmp);
-    std::swap(c->ent_ptr, c->alt_ent_ptr);
-    std::swap(c->index_strand, c->alt_index_strand);
-}
-
-} // extern "C"
-void pgrc_swap_index_sets(pgrc_match_ctx *c) { swap_index_sets(c); }
-extern "C" {
-
 // Two-pass runs of mode c with min_mismatches == 0 take the screened schedule (copmem.hip, "Exact-match screen") unless
 // PGRC_SCREEN=0 or the second set of index buffers does not fit.
 static bool screen_wanted(const pgrc_match_ctx *c, int first, int last) {
@@ -906,13 +887,13 @@ static bool dual_wanted(const pgrc_match_ctx *c, int first, int last) {
 }
 
 } // extern "C" (a template, and helpers of stream.hip)
-// The RC text and both strands' indexes: strand 0 ends up in the ALTERNATE set of index buffers, strand 1 in the active
-// one (what the dual kernel and the screened schedule expect).  Both builds at once on two streams (they share nothing
+// The RC text and both strands' indexes: strand 0 goes into the build set, then the build set is turned and strand 1 goes
+// into the other one (the launchers find either by its strand).  Both builds at once on two streams (they share nothing
 // but the bandwidth; PGRC_BUILD_STREAMS=1: in turn); the main stream is made to wait for the second.  `mark` is called
-// after the RC text and after the builds (profiling events).  PGRC_E_ALLOC: no room for the second set -- the caller frees
-// what it got.
+// after the RC text and after the builds (profiling events).  PGRC_E_ALLOC: no room for the second set -- the caller
+// retreats (pgrc_index_retreat).
 template <typename F>
-static int pgrc_build_both_indexes(pgrc_match_ctx *c, bool *two_streams, F mark) {
+static int pgrc_build_both_indexes(pgrc_match_ctx *c, F mark) {
     int e;
     if ((e = pgrc_launch_revcomp(c, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
     c->have_rc = true;
@@ -931,27 +912,23 @@ static int pgrc_build_both_indexes(pgrc_match_ctx *c, bool *two_streams, F mark)
     // Both strands' heads go into ONE table of 32-byte slots {forward head, RC head} per bucket number (round 4): the dual
     // kernel's two gathers of a seed then hit one 64-byte line and one translation.  PGRC_HEAD_PAIR=0: a table per strand
     // (A/B runs); no room for the pair table: the same.
-    {
-        bool pair = c->opt.head_pair != 0;
-        if (pair) {
-            const int pe = pgrc_buf_ensure(c, c->d_headpair, (size_t)c->cp.hash_size * 4 * sizeof(uint64_t));
-            if (pe == PGRC_E_ALLOC) { (void)hipGetLastError(); pair = false; }
-            else if (pe) return pe;
-        }
-        c->pair_build = pair;
-        // buckets per group (headfmt.h; PGRC_HEAD_PAIR=1..4: 1, 2, 4, 8): 4 -- measured at C3 in one context
-        // (profiles/r04_head_interleave_ab.txt): both gathers of a seed cost one request as long as they share a 128-BYTE line
-        // (groups of 1, 2, 4: dual kernel 79.5 -> 64.7 ms; groups of 8 = 256 bytes: 79.6), and the builds' head stores cost
-        // nothing extra only as whole 64-byte runs (groups of 1 and 2: index pair 16.2 -> 24.9 ms; groups of 4: 17.0)
-        c->pair_gm = pair ? c->opt.head_pair - 1u : 3u;
+    bool pair = c->opt.head_pair != 0;
+    if (pair) {
+        const int pe = pgrc_buf_ensure(c, c->d_headpair, (size_t)c->cp.hash_size * 4 * sizeof(uint64_t));
+        if (pe == PGRC_E_ALLOC) { (void)hipGetLastError(); pair = false; }
+        else if (pe) return pe;
     }
-    if ((e = pgrc_copmem_build_index(c, 0))) { c->pair_build = false; return e; }
+    // buckets per group (headfmt.h; PGRC_HEAD_PAIR=1..4: 1, 2, 4, 8): 4 -- measured at C3 in one context
+    // (profiles/r04_head_interleave_ab.txt): both gathers of a seed cost one request as long as they share a 128-BYTE line
+    // (groups of 1, 2, 4: dual kernel 79.5 -> 64.7 ms; groups of 8 = 256 bytes: 79.6), and the builds' head stores cost
+    // nothing extra only as whole 64-byte runs (groups of 1 and 2: index pair 16.2 -> 24.9 ms; groups of 4: 17.0)
+    c->pair_gm = pair ? c->opt.head_pair - 1u : 3u;
+    if ((e = pgrc_copmem_build_index(c, 0, pair))) return e;
     if (!two) mark(); // 2
-    swap_index_sets(c);
+    c->build_set ^= 1;
     if (two) c->stream = c->build_stream;
     // (PGRC_TEST_NO_SECOND_INDEX: tests take the out-of-memory road without exhausting the device)
-    e = c->opt.test_no_second_index ? PGRC_E_ALLOC : pgrc_copmem_build_index(c, 1);
-    c->pair_build = false;
+    e = c->opt.test_no_second_index ? PGRC_E_ALLOC : pgrc_copmem_build_index(c, 1, pair);
     c->stream = main_stream;
     if (two) {
         if (hipEventRecord(c->build_ev[1], c->build_stream) != hipSuccess || hipStreamWaitEvent(main_stream, c->build_ev[1], 0) != hipSuccess) {
@@ -960,7 +937,6 @@ static int pgrc_build_both_indexes(pgrc_match_ctx *c, bool *two_streams, F mark)
         }
         mark(); // 2: both indexes (ms_index[0] is then the pair, ms_index[1] ~ 0)
     }
-    *two_streams = two;
     return e;
 }
 
@@ -976,30 +952,35 @@ bool pgrc_dual_applies(const pgrc_match_ctx *c) {
 
 // pgrc_match_prepare_index / pgrc_match_stream_begin (stream.hip): both strands' indexes now, on their streams
 int pgrc_prepare_both_indexes(pgrc_match_ctx *c) {
-    bool two = false;
-    const int e = pgrc_build_both_indexes(c, &two, []() {});
+    const int e = pgrc_build_both_indexes(c, []() {});
     if (e == PGRC_E_ALLOC) {
-        // no room for the second set: give back what it got; later runs take the two passes with one set
-        (void)hipGetLastError();
-        if (two) (void)hipStreamSynchronize(c->build_stream);
-        DevBuf *part[] = {&c->d_head, &c->d_skey[0], &c->d_skey[1], &c->d_sval[0], &c->d_sval[1], &c->d_sorttmp};
-        for (DevBuf *b : part) pgrc_buf_free(*b);
-        c->ent_ptr = nullptr;
-        c->index_strand = -1;
-        swap_index_sets(c);
-        if (c->head_sh) {                   // (the forward index that was built sits in the pair table: nothing keeps it)
-            (void)hipStreamSynchronize(c->stream);
-            pgrc_buf_free(c->d_headpair);
-            c->head_ptr = c->alt_head_ptr = nullptr;
-            c->head_sh = c->alt_head_sh = 0;
-            c->ent_ptr = nullptr;
-            c->index_strand = -1;
-        }
-        c->screen_broken = true;
+        pgrc_index_retreat(c);
         c->err = "prepare_index: no room for both strands' indexes";
     }
     c->idx_prepared = e == PGRC_OK;
     return e;
+}
+
+// what a run that kept both indexes counted apart (d_counters + 24), into c->ctr: the dual kernel's nine counters, or the
+// screen's work
+int pgrc_fetch_schedule_counters(pgrc_match_ctx *c, bool dual) {
+    uint64_t scr[9];
+    HIP_TRY(c, hipMemcpy(scr, (const uint64_t *)c->d_counters.p + 24, sizeof scr, hipMemcpyDeviceToHost));
+    if (dual) {
+        for (int k = 0; k < 5; k++) c->ctr.dual[k] = scr[k];
+        c->ctr.redo_reads = scr[5];
+        c->ctr.dual_seed_probes = scr[6];
+        c->ctr.dual_skip_reads = scr[7];
+        c->ctr.dual_rewinds = scr[8];
+        c->ctr.screened = 2;
+    } else {                         // the screen ran on the RC text: its work counts with that strand's (not "searched")
+        c->ctr.candidates[1] += scr[1];
+        c->ctr.probes[1] += scr[2];
+        c->ctr.entry_fetches[1] += scr[3];
+        c->ctr.verifies[1] += scr[4];
+        c->ctr.screened = 1;
+    }
+    return PGRC_OK;
 }
 
 extern "C" {
@@ -1026,8 +1007,7 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
         screened = false;
     }
     if (screened) {
-        bool two = false;
-        if (c->idx_prepared && c->index_strand == 1 && c->alt_index_strand == 0 && c->have_rc) {
+        if (c->idx_prepared && pgrc_index_pair_ready(c) && c->have_rc) {
             // both indexes were built ahead of the run (pgrc_match_prepare_index): the builds may still be in flight on
             // their streams; this run's work is ordered behind them
             c->idx_prepared = false;
@@ -1035,34 +1015,20 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
             if (c->build_stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->build_ev[1], 0));
             mark(); // 2
             e = PGRC_OK;
-            two = true;
         } else {
-            e = pgrc_build_both_indexes(c, &two, [&]() { mark(); });
+            e = pgrc_build_both_indexes(c, [&]() { mark(); });
         }
         if (e == PGRC_E_ALLOC) {
-            // no room for both indexes: free what the second set got, and run the passes in the reference's order
-            (void)hipGetLastError();
-            if (two) (void)hipStreamSynchronize(c->build_stream);   // (nothing of a half-started build may still be running)
-            DevBuf *part[] = {&c->d_head, &c->d_skey[0], &c->d_skey[1], &c->d_sval[0], &c->d_sval[1], &c->d_sorttmp};
-            for (DevBuf *b : part) pgrc_buf_free(*b);
-            c->ent_ptr = nullptr;
-            c->index_strand = -1;
-            swap_index_sets(c);
-            c->screen_broken = true;
+            // no room for both indexes: give back what the second set got, and run the passes in the reference's order
+            pgrc_index_retreat(c);
             screened = false;
-            if (c->index_strand != 0 || !c->ent_ptr) {
-                // (it was already the FORWARD index that found no room, e.g. for the pair table's share of it: once more on its
-                //  own, into a table of its own -- if that does not fit either, the run fails with PGRC_E_ALLOC)
-                if (c->head_sh) { (void)hipStreamSynchronize(c->stream); pgrc_buf_free(c->d_headpair); c->head_ptr = c->alt_head_ptr = nullptr; c->head_sh = c->alt_head_sh = 0; }
-                if ((e = pgrc_copmem_build_index(c, 0))) return e;
-            }
+            // (the forward index is gone when it was the one that found no room, or when its heads sat in the pair table: once
+            //  more, into a table of its own -- if that does not fit either, the run fails with PGRC_E_ALLOC)
+            if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, 0))) return e;
             mark(); // 3
             if ((e = pgrc_copmem_match_pass(c, 0))) return e;
             mark(); // 4
-            c->pair_build = c->head_sh != 0;      // (the forward index sits in the pair table: the RC heads take its other half)
-            e = pgrc_copmem_build_index(c, 1);
-            c->pair_build = false;
-            if (e) return e;
+            if ((e = pgrc_copmem_build_index(c, 1))) return e;
             mark(); // 5
             if ((e = pgrc_copmem_match_pass(c, 1))) return e;
             mark(); // 6
@@ -1085,10 +1051,8 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
             } else {
                 if ((e = pgrc_copmem_match_phase(c, 1, 1))) return e;      // screen on the RC text
                 mark(); // 4
-                swap_index_sets(c);
                 if ((e = pgrc_copmem_match_phase(c, 0, 2))) return e;      // forward pass honouring the flags
                 mark(); // 5
-                swap_index_sets(c);
                 if ((e = pgrc_copmem_match_phase(c, 1, 0))) return e;      // RC pass over what is left
                 mark(); // 6
             }
@@ -1113,8 +1077,6 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
     mark();
     uint64_t ctr[16];
     HIP_TRY(c, hipMemcpy(ctr, c->d_counters.p, sizeof ctr, hipMemcpyDeviceToHost));
-    uint64_t scr[9];
-    HIP_TRY(c, hipMemcpy(scr, (const uint64_t *)c->d_counters.p + 24, sizeof scr, hipMemcpyDeviceToHost));
     for (int s = 0; s < 2 && c->prm.mode == 'c'; s++) {      // (modes d/i/e: pgrc_seedidx_run filled searched / candidates)
         c->ctr.searched[s] = ctr[8 * s + 0];
         c->ctr.candidates[s] = ctr[8 * s + 1];
@@ -1122,20 +1084,7 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
         c->ctr.entry_fetches[s] = ctr[8 * s + 3];
         c->ctr.verifies[s] = ctr[8 * s + 4];
     }
-    if (screened && dual) {
-        for (int k = 0; k < 5; k++) c->ctr.dual[k] = scr[k];
-        c->ctr.redo_reads = scr[5];
-        c->ctr.dual_seed_probes = scr[6];
-        c->ctr.dual_skip_reads = scr[7];
-        c->ctr.dual_rewinds = scr[8];
-        c->ctr.screened = 2;
-    } else if (screened) {           // the screen ran on the RC text: its work counts with that strand's (not "searched")
-        c->ctr.candidates[1] += scr[1];
-        c->ctr.probes[1] += scr[2];
-        c->ctr.entry_fetches[1] += scr[3];
-        c->ctr.verifies[1] += scr[4];
-        c->ctr.screened = 1;
-    }
+    if (screened && (e = pgrc_fetch_schedule_counters(c, dual))) return e;
     c->ctr.schedule_downgraded = c->screen_broken ? 1u : 0u;
     if (prof) {
         HIP_TRY(c, hipEventSynchronize(c->ev[evi - 1]));
@@ -1272,8 +1221,8 @@ int pgrc_match_export_index(pgrc_match_ctx *c, int strand, uint32_t *cumm, uint3
         if ((e = pgrc_launch_revcomp(c, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
         c->have_rc = true;
     }
-    if (c->index_strand != strand && (e = pgrc_copmem_build_index(c, strand))) return e;
-    return pgrc_copmem_export_index(c, cumm, positions, count);
+    if (!pgrc_index_of(c, strand) && (e = pgrc_copmem_build_index(c, strand))) return e;
+    return pgrc_copmem_export_index(c, strand, cumm, positions, count);
 }
 
 } // extern "C"

@@ -46,28 +46,72 @@ __global__ void __launch_bounds__(256) k_heads_empty(ulonglong2 *__restrict__ he
         head[head_slot(h, hsh)] = make_ulonglong2(HEAD_EMPTY, HEAD_EMPTY);
 }
 
-int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand) {
+// Builds go to the build set, launches look a strand up.  The set of a strand is the one that describes it and whose
+// build was queued whole (ent set).  Both sets can describe the same strand of the same text -- after an export or a single
+// pass built it again next to a kept pair --: they are then identical, and the build set is taken.
+PgrcIndexSet *pgrc_index_of(pgrc_match_ctx *c, int strand) {
+    for (int k : {c->build_set, c->build_set ^ 1})
+        if (c->idx[k].strand == strand && c->idx[k].ent) return &c->idx[k];
+    return nullptr;
+}
+
+// what the schedules that keep both strands' indexes need (the dual kernel takes ONE head format for both)
+bool pgrc_index_pair_ready(pgrc_match_ctx *c) {
+    const PgrcIndexSet *fw = pgrc_index_of(c, 0), *rv = pgrc_index_of(c, 1);
+    return fw && rv && fw->head_sh == rv->head_sh;
+}
+
+void pgrc_index_drop(pgrc_match_ctx *, PgrcIndexSet &ix) {
+    for (DevBuf *b : {&ix.head, &ix.skey[0], &ix.skey[1], &ix.sval[0], &ix.sval[1], &ix.sorttmp}) pgrc_buf_free(*b);
+    ix.ent = nullptr;
+    ix.head_ptr = nullptr;
+    ix.head_sh = 0;
+    ix.strand = -1;
+}
+
+// No room for the second index set (the build into the build set failed with PGRC_E_ALLOC): give back what that set got and
+// go back to the other one; later runs take the two passes with one set.  A forward index whose heads sit in the pair
+// table goes too, with the table: nothing would keep that table otherwise, and the passes build into a table per set.
+void pgrc_index_retreat(pgrc_match_ctx *c) {
+    (void)hipGetLastError();
+    if (c->build_stream) (void)hipStreamSynchronize(c->build_stream);   // (nothing of a half-started build may still be running)
+    pgrc_index_drop(c, pgrc_build_set(c));
+    c->build_set ^= 1;
+    PgrcIndexSet &left = pgrc_build_set(c);
+    if (left.head_sh) {
+        (void)hipStreamSynchronize(c->stream);                          // (the build that wrote into the table ran here)
+        pgrc_buf_free(c->d_headpair);
+        left.ent = nullptr;                                             // (its other buffers stay: the next build reuses them)
+        left.head_ptr = nullptr;
+        left.head_sh = 0;
+        left.strand = -1;
+    }
+    c->screen_broken = true;
+}
+
+int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand, bool into_pair_table) {
+    PgrcIndexSet &ix = pgrc_build_set(c);
     const uint32_t K = (uint32_t)c->cp.K, k1 = (uint32_t)c->cp.k1;
     const uint64_t hs = c->cp.hash_size;
     c->npos = (c->G >= K) ? (c->G - K) / k1 + 1 : 0;
     const uint64_t npos = c->npos;
     int e;
-    if (c->pair_build) {             // both strands' heads in one table of 32-byte slots (ctx.h)
+    if (into_pair_table) {           // both strands' heads in one table of 32-byte slots (ctx.h)
         if ((e = pgrc_buf_ensure(c, c->d_headpair, hs * 4 * sizeof(uint64_t)))) return e;
-        c->head_ptr = (ulonglong2 *)c->d_headpair.p + (strand ? c->pair_gm + 1u : 0u);
-        c->head_sh = 1u | (c->pair_gm << 8);
+        ix.head_ptr = (ulonglong2 *)c->d_headpair.p + (strand ? c->pair_gm + 1u : 0u);
+        ix.head_sh = 1u | (c->pair_gm << 8);
     } else {
-        if ((e = pgrc_buf_ensure(c, c->d_head, hs * 2 * sizeof(uint64_t)))) return e;
-        c->head_ptr = (ulonglong2 *)c->d_head.p;
-        c->head_sh = 0;
+        if ((e = pgrc_buf_ensure(c, ix.head, hs * 2 * sizeof(uint64_t)))) return e;
+        ix.head_ptr = (ulonglong2 *)ix.head.p;
+        ix.head_sh = 0;
     }
-    c->ent_ptr = nullptr;
-    c->index_strand = strand;
+    ix.ent = nullptr;
+    ix.strand = strand;
     if (!npos) {
-        hipLaunchKernelGGL(k_heads_empty, dim3((uint32_t)std::min<uint64_t>((hs + 255) / 256, 65536ull)), dim3(256), 0, c->stream, c->head_ptr, hs, c->head_sh);
+        hipLaunchKernelGGL(k_heads_empty, dim3((uint32_t)std::min<uint64_t>((hs + 255) / 256, 65536ull)), dim3(256), 0, c->stream, ix.head_ptr, hs, ix.head_sh);
         HIP_TRY(c, hipGetLastError());
-        if ((e = pgrc_buf_ensure(c, c->d_sval[0], 64))) return e;
-        c->ent_ptr = (const uint64_t *)c->d_sval[0].p;
+        if ((e = pgrc_buf_ensure(c, ix.sval[0], 64))) return e;
+        ix.ent = (const uint64_t *)ix.sval[0].p;
         return PGRC_OK;
     }
     int hbits = 0;
@@ -87,7 +131,7 @@ int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand) {
     }
     const uint32_t cb = pgrc_ps_partition_bits((uint32_t)hbits);
     if ((e = pgrc_ps_scatter_front(c, strand, (uint32_t)hbits, cb))) return e;
-    return pgrc_ps_finish(c, (const uint32_t *)c->d_skey[1].p, (const uint64_t *)c->d_sval[1].p, (uint32_t)hbits, cb, (uint64_t *)c->d_sval[0].p);
+    return pgrc_ps_finish(c, (const uint32_t *)ix.skey[1].p, (const uint64_t *)ix.sval[1].p, (uint32_t)hbits, cb, (uint64_t *)ix.sval[0].p);
 }
 
 // ---- canonical export for tests: the reference's (cumm, sampledPositions) from heads + ent ----
@@ -113,8 +157,10 @@ k_export_positions(const ulonglong2 *__restrict__ head, uint32_t hsh, const uint
     }
 }
 
-int pgrc_copmem_export_index(pgrc_match_ctx *c, uint32_t *h_cumm, uint32_t *h_positions, uint64_t *count) {
+int pgrc_copmem_export_index(pgrc_match_ctx *c, int strand, uint32_t *h_cumm, uint32_t *h_positions, uint64_t *count) {
     if (c->G >= (1ull << 32)) { c->err = "export_index: 32-bit positions only (test helper)"; return PGRC_E_PARAM; }
+    const PgrcIndexSet *ix = pgrc_index_of(c, strand);
+    if (!ix) { c->err = "export_index: no index of that strand"; return PGRC_E_STATE; }
     const uint64_t hs = c->cp.hash_size;
     DevBuf cnt, cumm, pos, temp;
     auto cleanup = [&]() { pgrc_buf_free(cnt); pgrc_buf_free(cumm); pgrc_buf_free(pos); pgrc_buf_free(temp); };
@@ -122,7 +168,7 @@ int pgrc_copmem_export_index(pgrc_match_ctx *c, uint32_t *h_cumm, uint32_t *h_po
     if ((e = pgrc_buf_ensure(c, cnt, (hs + 2) * sizeof(uint32_t))) || (e = pgrc_buf_ensure(c, cumm, (hs + 2) * sizeof(uint32_t)))) { cleanup(); return e; }
     HIP_TRY(c, hipMemsetAsync(cnt.p, 0, (hs + 2) * sizeof(uint32_t), c->stream));
     const uint32_t sgrid = (uint32_t)((hs + 255) / 256 < 65536u * 8u ? (hs + 255) / 256 : 65536u * 8u);
-    hipLaunchKernelGGL(k_export_counts, dim3(sgrid), dim3(256), 0, c->stream, (const ulonglong2 *)c->head_ptr, c->head_sh, hs, (uint32_t *)cnt.p);
+    hipLaunchKernelGGL(k_export_counts, dim3(sgrid), dim3(256), 0, c->stream, (const ulonglong2 *)ix->head_ptr, ix->head_sh, hs, (uint32_t *)cnt.p);
     // cumm = exclusive scan of the counts (the build's own scan kernels; in place in `cnt`, then copied)
     if ((e = pgrc_buf_ensure(c, temp, pgrc_ps_scan_blocks(hs + 2) * sizeof(uint32_t)))) { cleanup(); return e; }
     if ((e = pgrc_ps_scan_u32(c, (uint32_t *)cnt.p, hs + 2, (uint32_t *)temp.p))) { cleanup(); return e; }
@@ -135,8 +181,8 @@ int pgrc_copmem_export_index(pgrc_match_ctx *c, uint32_t *h_cumm, uint32_t *h_po
     if (h_cumm && hipMemcpy(h_cumm, cumm.p, (hs + 2) * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) { cleanup(); return PGRC_E_DEVICE; }
     if (h_positions && total) {
         if ((e = pgrc_buf_ensure(c, pos, (size_t)total * sizeof(uint32_t)))) { cleanup(); return e; }
-        hipLaunchKernelGGL(k_export_positions, dim3(sgrid), dim3(256), 0, c->stream, (const ulonglong2 *)c->head_ptr, c->head_sh,
-                           c->ent_ptr, (const uint32_t *)cumm.p, hs, (uint32_t *)pos.p);
+        hipLaunchKernelGGL(k_export_positions, dim3(sgrid), dim3(256), 0, c->stream, (const ulonglong2 *)ix->head_ptr, ix->head_sh,
+                           ix->ent, (const uint32_t *)cumm.p, hs, (uint32_t *)pos.p);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
             hipMemcpy(h_positions, pos.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
             cleanup();
@@ -798,12 +844,13 @@ static void launch_dual(pgrc_match_ctx *c, const DualArgs &a) {
     }
 }
 
-// The dual kernel over all reads without N: the ACTIVE index set must describe the RC strand, the alternate set the
-// forward strand (api.hip builds them in that order).  The reads with N follow in two ordinary passes (phase 4).
-int pgrc_copmem_match_dual(pgrc_match_ctx *c) {
-    const uint64_t lo = std::min<uint64_t>(c->range_lo, c->n), rn = std::min<uint64_t>(c->n - lo, c->range_n);   // (a block of a streamed run, or everything)
+// The dual kernel over the reads without N of a range: it needs a set for either strand, both with their heads in the same
+// kind of table.  The reads with N follow in two ordinary passes (phase 4).
+int pgrc_copmem_match_dual(pgrc_match_ctx *c, PgrcReadRange range) {
+    const uint64_t lo = std::min<uint64_t>(range.lo, c->n), rn = std::min<uint64_t>(c->n - lo, range.n);
     if (rn == 0) return PGRC_OK;
-    if (c->index_strand != 1 || c->alt_index_strand != 0 || !c->ent_ptr || !c->alt_ent_ptr || !c->d_scr_pos.p || c->head_sh != c->alt_head_sh) {
+    const PgrcIndexSet *fw = pgrc_index_of(c, 0), *rv = pgrc_index_of(c, 1);
+    if (!pgrc_index_pair_ready(c) || !c->d_scr_pos.p || !c->d_scr_flag.p) {
         c->err = "dual kernel without both indexes";
         return PGRC_E_STATE;
     }
@@ -817,11 +864,11 @@ int pgrc_copmem_match_dual(pgrc_match_ctx *c) {
     a.nflag = (c->n_nreads || c->up_open) ? (const uint8_t *)c->nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
     // PGRC_NREAD_INLINE=0: every read with an N goes the byte path (A/B runs, tests)
     a.npos = (a.nflag && c->opt.nread_inline && c->nread_npos.p) ? (const uint32_t *)c->nread_npos.p + lo : nullptr;
-    a.head[0] = (const ulonglong2 *)c->alt_head_ptr;
-    a.head[1] = (const ulonglong2 *)c->head_ptr;
-    a.hsh = c->head_sh;
-    a.ent[0] = c->alt_ent_ptr;
-    a.ent[1] = c->ent_ptr;
+    a.head[0] = (const ulonglong2 *)fw->head_ptr;
+    a.head[1] = (const ulonglong2 *)rv->head_ptr;
+    a.hsh = fw->head_sh;
+    a.ent[0] = fw->ent;
+    a.ent[1] = rv->ent;
     a.pos = (uint64_t *)c->d_pos.p + lo;
     a.rc = (uint8_t *)c->d_rc.p + lo;
     a.mism = (uint8_t *)c->d_mism.p + lo;
@@ -879,22 +926,22 @@ static void launch_match(pgrc_match_ctx *c, const MatchArgs &a) {
 }
 
 // The reads with N through the strands first .. last (k_copmem_match_n), on the side stream: it starts when what the main
-// stream holds so far is done (the indexes; a streamed run: when c->n_after says so) and the caller joins it later
-// (pgrc_copmem_join_nreads).  Every strand asked for must be one of the two index sets of the context.  (Launched BEFORE the
+// stream holds so far is done (the indexes; a streamed run: when the event `after` says so) and the caller joins it later
+// (pgrc_copmem_join_nreads).  Every strand asked for must have its index set in the context.  (Launched BEFORE the
 // dual kernel as a small persistent grid it still only starts when that kernel's blocks leave: profiles/r04_nread_beside_ab.txt.)
-int pgrc_copmem_match_nreads(pgrc_match_ctx *c, int first, int last, bool only_many) {
+int pgrc_copmem_match_nreads(pgrc_match_ctx *c, int first, int last, bool only_many, hipEvent_t after) {
     if (!c->n_nreads) return PGRC_OK;
     if (!c->opt.nread_inline) only_many = false;
     if (only_many && !c->n_many) return PGRC_OK;                        // (the dual kernel takes every read with at most 4 N's)
     NReadArgs a;
     a.skip_flag = only_many ? (const uint8_t *)c->nread_flag.p : nullptr;
     for (int s = first; s <= last; s++) {
-        const bool act = c->index_strand == s && c->ent_ptr, alt = !act && c->alt_index_strand == s && c->alt_ent_ptr;
-        if (!act && !alt) { c->err = "reads with N: no index of that strand"; return PGRC_E_STATE; }
+        const PgrcIndexSet *ix = pgrc_index_of(c, s);
+        if (!ix) { c->err = "reads with N: no index of that strand"; return PGRC_E_STATE; }
         a.st[s].pg = (const uint32_t *)c->pg2[s].p;
-        a.st[s].head = act ? c->head_ptr : c->alt_head_ptr;
-        a.st[s].hsh = act ? c->head_sh : c->alt_head_sh;
-        a.st[s].ent = act ? c->ent_ptr : c->alt_ent_ptr;
+        a.st[s].head = ix->head_ptr;
+        a.st[s].hsh = ix->head_sh;
+        a.st[s].ent = ix->ent;
         a.st[s].counters = (unsigned long long *)c->d_counters.p + 8 * s;
     }
     a.G = c->G;
@@ -930,8 +977,8 @@ int pgrc_copmem_match_nreads(pgrc_match_ctx *c, int first, int last, bool only_m
         c->side_ev[0] = e0;
         c->side_ev[1] = e1;
     }
-    if (c->n_after) {                                                   // (a streamed run: not behind the blocks still queued)
-        HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->n_after, 0));
+    if (after) {                                                        // (a streamed run: not behind the blocks still queued)
+        HIP_TRY(c, hipStreamWaitEvent(c->side_stream, after, 0));
     } else {
         HIP_TRY(c, hipEventRecord(c->side_ev[0], c->stream));           // the index (and the previous pass) are complete
         HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->side_ev[0], 0));
@@ -955,9 +1002,11 @@ int pgrc_copmem_match_pass(pgrc_match_ctx *c, int strand) { return pgrc_copmem_m
 
 // phase: 0 = a plain pass; 1 / 2 = the screen and the flag-honouring forward pass of the screened schedule (kernel comment);
 // 4 = after the dual kernel: only the reads with N (the byte-path kernel), in the strand order of the two passes
-int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase) {
-    const uint64_t lo = std::min<uint64_t>(c->range_lo, c->n), rn = std::min<uint64_t>(c->n - lo, c->range_n);   // (a block of a streamed run, or everything)
+int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase, PgrcReadRange range) {
+    const uint64_t lo = std::min<uint64_t>(range.lo, c->n), rn = std::min<uint64_t>(c->n - lo, range.n);
     if (rn == 0) return PGRC_OK;
+    const PgrcIndexSet *ix = pgrc_index_of(c, strand);
+    if (!ix) { c->err = "match pass: no index of that strand"; return PGRC_E_STATE; }
     MatchArgs a;
     a.pg = (const uint32_t *)c->pg2[strand].p;
     a.G = c->G;
@@ -965,9 +1014,9 @@ int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase) {
     a.n = rn;
     a.stride = c->stride;
     a.nflag = (c->n_nreads || c->up_open) ? (const uint8_t *)c->nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
-    a.head = (const ulonglong2 *)c->head_ptr;
-    a.hsh = c->head_sh;
-    a.ent = c->ent_ptr;
+    a.head = (const ulonglong2 *)ix->head_ptr;
+    a.hsh = ix->head_sh;
+    a.ent = ix->ent;
     a.pos = (uint64_t *)c->d_pos.p + lo;
     a.rc = (uint8_t *)c->d_rc.p + lo;
     a.mism = (uint8_t *)c->d_mism.p + lo;
@@ -992,7 +1041,7 @@ int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase) {
     // main kernel, whose persistent blocks simply take the remaining slots; the two kernels write disjoint reads.
     // (the screen only flags reads; reads with N are never flagged.  The N kernel walks the side list, whose indexes
     //  count from read 0: it runs on whole-set launches only, never on a block of a streamed run)
-    const bool with_n = c->n_nreads && phase != 1 && !c->range_skip_n && lo == 0 && rn == c->n;
+    const bool with_n = c->n_nreads && phase != 1 && !range.skip_n && lo == 0 && rn == c->n;
     if (with_n) {
         const int ne = pgrc_copmem_match_nreads(c, strand, strand, false);
         if (ne) return ne;

@@ -9,6 +9,8 @@
 //                                          buckets with >= 3 entries w0 carries a flag, w1 the count and the index
 //                                          of entry 1 in ent[]: one 16-B gather per probe (copmem.hip)
 //   ent           u64[sampled positions]   all entries sorted by (bucket, position): the build's radix-sort output
+//                                          (head and ent of one strand: a PgrcIndexSet; a context has two, and the runs that
+//                                          keep both strands' indexes put both sets' heads into one pair table, headfmt.h)
 //   pos/rc/mism   u64[n] / u8[n] / u8[n]   per-read results (ReadsMatchers.h:32-35,115)
 #pragma once
 
@@ -44,6 +46,24 @@ struct PgrcDev {
 };
 
 struct pgrc_multi;   // multi.hip
+
+// One strand's copMEM index as the build leaves it.  A context has two of them (pgrc_match_ctx::idx): the plain passes
+// rebuild one per pass, the screened schedule and the dual kernel keep the forward index in one and the RC index in the other.
+struct PgrcIndexSet {
+    DevBuf head;                        // ulonglong2[hash_size] bucket heads: this set's own table of 16-byte heads
+    DevBuf skey[2], sval[2], sorttmp;   // (bucket, entry) records: the build's ping-pong buffers and its scratch (grow-only)
+    ulonglong2 *head_ptr = nullptr;     // head h at head_ptr[head_slot(h, head_sh)] (headfmt.h): into `head` (head_sh = 0) or
+    uint32_t head_sh = 0;               // into the context's pair table, which both sets share
+    const uint64_t *ent = nullptr;      // the sorted entries (one of sval[]), ent[] of the match kernels; set when the build is queued whole
+    int strand = -1;                    // which strand's text the set describes; -1: nothing
+};
+
+// The reads a match launch works on: [lo, lo + n) of the set (clipped to it); skip_n: the reads with N are left to a later
+// pass.  The default is everything; a streamed run (stream.hip) launches block by block.
+struct PgrcReadRange {
+    uint64_t lo = 0, n = ~0ull;
+    bool skip_n = false;
+};
 
 // Run-time options of a context.  The environment is read ONCE, when the context is created (pgrc_options_from_env,
 // api.hip) -- never at a launch -- so a production matcher does not change schedule because somebody's environment
@@ -135,27 +155,18 @@ struct pgrc_match_ctx : PgrcDev {
     // copMEM index (rebuilt per pass, buffers reused)
     pgrc_copmem_params cp{};
     uint64_t npos = 0;
-    DevBuf d_head;                      // ulonglong2[hash_size] bucket heads (one strand's table of 16-byte heads)
-    // Where the ACTIVE set's heads really are: head h at head_ptr[head_slot(h, head_sh)] (headfmt.h).  head_sh = 0: d_head,
-    // one table per strand; otherwise (round 4, runs that keep both strands' indexes) the pair table d_headpair, in which
-    // the forward and the RC head of a bucket number share a line -- the dual kernel's two gathers of a seed are then ONE
-    // line request and one translation (copmem.hip, "The dual kernel").
-    ulonglong2 *head_ptr = nullptr;
-    uint32_t head_sh = 0;
-    DevBuf d_headpair;                  // ulonglong2[2 * hash_size], shared by both index sets (never swapped)
+    // The two index sets (PgrcIndexSet above).  A build writes into idx[build_set]; a launch looks its strand up
+    // (pgrc_index_of).  A context that never keeps both strands' indexes only ever owns the buffers of one set; the
+    // schedules that do (copmem.hip, "Exact-match screen" and "The dual kernel") turn build_set between their two builds.
+    PgrcIndexSet idx[2];
+    int build_set = 0;
+    // The pair table (round 4, runs that keep both strands' indexes): the forward and the RC head of a bucket number share
+    // a line -- the dual kernel's two gathers of a seed are then ONE line request and one translation (copmem.hip, "The
+    // dual kernel").  Shared by both sets: a set whose head_sh != 0 has its heads here.
+    DevBuf d_headpair;                  // ulonglong2[2 * hash_size]
     uint32_t pair_gm = 3;               // pair table: buckets per group - 1 (a power of two minus one; headfmt.h)
-    bool pair_build = false;            // pgrc_copmem_build_index writes into d_headpair (set around the builds of both strands)
-    DevBuf d_skey[2], d_sval[2], d_sorttmp; // (bucket, entry) records: radix sort ping-pong + rocPRIM scratch (grow-only)
-    const uint64_t *ent_ptr = nullptr;  // the sorted entries (one of d_sval[]): ent[] of the match kernel
-    int index_strand = -1;  // which strand the buffers currently describe
     bool os_lds_allowed = false;        // idxsweep.hip's kernels were granted their dynamic LDS on this context's device
-    // the screened schedule of a two-pass run (copmem.hip, "Exact-match screen") keeps both strands' indexes: a second
-    // set of index buffers that swaps roles with the first, and per read the flag / position the screen found
-    DevBuf alt_head, alt_skey[2], alt_sval[2], alt_sorttmp;
-    const uint64_t *alt_ent_ptr = nullptr;
-    int alt_index_strand = -1;
-    ulonglong2 *alt_head_ptr = nullptr;
-    uint32_t alt_head_sh = 0;
+    // per read the flag / position the screen found (screened schedule and dual kernel)
     DevBuf d_scr_pos, d_scr_flag;
     bool screen_broken = false;         // no room for the second set: the passes run as the reference orders them
     hipStream_t build_stream = nullptr; // the RC index is built beside the forward one (screened schedule)
@@ -163,8 +174,6 @@ struct pgrc_match_ctx : PgrcDev {
 
     // pipelined hand-over (stream.hip): both indexes built ahead of the run; blocks of reads matched as they arrive
     bool idx_prepared = false;          // pgrc_match_prepare_index built (or is building) both strands' indexes of the current text
-    uint64_t range_lo = 0, range_n = ~0ull;   // the match launchers work on reads [range_lo, range_lo + range_n) ...
-    bool range_skip_n = false;          // ... and leave the reads with N to a later pass
     struct StreamBlock { uint64_t lo, cnt; hipEvent_t done; };
     bool st_on = false, st_dual = false;
     uint64_t *st_pos = nullptr;         // the caller's result arrays: a block's results are copied there as soon as they exist
@@ -173,7 +182,6 @@ struct pgrc_match_ctx : PgrcDev {
                                         // goes to hipFree, which waits for the whole device -- i.e. for the matching of a streamed run)
     std::vector<DevBuf> st_keep;        // streamed run: small device buffers to give back at its end (see end_reads)
     hipEvent_t st_ready = nullptr;      // streamed run: indexes built and per-read state initialised (what the N passes wait for)
-    hipEvent_t n_after = nullptr;       // when set: the N kernel's side stream waits for this event instead of the main stream's tail
     DevBuf up_stage[2];                 // staging areas of append_reads_* (grow-only: no allocation per call), used in turn
     hipStream_t up_stream[2] = {nullptr, nullptr};   // a streamed run uploads and unpacks beside the matching, on two streams in
     hipEvent_t up_ev[2] = {nullptr, nullptr};        // turn: the copy of chunk k+1 must not queue behind the unpacking of chunk k,
@@ -343,7 +351,14 @@ int pgrc_launch_mem_pack_device(PgrcDev *c, const uint8_t *d_ascii, uint64_t n, 
                                 uint32_t *d_flags, uint32_t block_cap);
 
 // copmem.hip
-int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand);
+// Builds go to the build set, launches look a strand up:
+static inline PgrcIndexSet &pgrc_build_set(pgrc_match_ctx *c) { return c->idx[c->build_set]; }   // what the next build writes into
+PgrcIndexSet *pgrc_index_of(pgrc_match_ctx *c, int strand);   // the finished set of that strand (the build set first), or null
+bool pgrc_index_pair_ready(pgrc_match_ctx *c);                 // a set for either strand, their heads in the same kind of table
+void pgrc_index_drop(pgrc_match_ctx *c, PgrcIndexSet &ix);     // frees the set's buffers; it describes nothing afterwards
+void pgrc_index_retreat(pgrc_match_ctx *c);                    // no room for the second set: see its definition
+// into_pair_table: the heads go into the strand's half of the pair table (the builds of a run that keeps both indexes)
+int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand, bool into_pair_table = false);
 // idxsort.hip: the partition build of the same index (hand-written scatter passes, in-LDS finish of a partition)
 uint32_t pgrc_ps_partition_bits(uint32_t hbits);
 bool pgrc_ps_applicable(const pgrc_match_ctx *c, uint32_t hbits);
@@ -362,14 +377,15 @@ int pgrc_copmem_match_pass(pgrc_match_ctx *c, int strand);
 int pgrc_stream_block_arrived(pgrc_match_ctx *c, uint64_t lo, uint64_t cnt, bool may_hold_n, int turn);
 void pgrc_stream_abort(pgrc_match_ctx *c);
 // api.hip
-void pgrc_swap_index_sets(pgrc_match_ctx *c);
 int pgrc_prepare_both_indexes(pgrc_match_ctx *c);
 bool pgrc_dual_applies(const pgrc_match_ctx *c);
-int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase);
-int pgrc_copmem_match_dual(pgrc_match_ctx *c);
-int pgrc_copmem_match_nreads(pgrc_match_ctx *c, int first, int last, bool only_many);
+int pgrc_fetch_schedule_counters(pgrc_match_ctx *c, bool dual);   // the dual kernel's (or the screen's) device counters -> c->ctr
+int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase, PgrcReadRange range = {});
+int pgrc_copmem_match_dual(pgrc_match_ctx *c, PgrcReadRange range = {});
+// after: the N kernel's side stream waits for this event instead of the main stream's tail
+int pgrc_copmem_match_nreads(pgrc_match_ctx *c, int first, int last, bool only_many, hipEvent_t after = nullptr);
 int pgrc_copmem_join_nreads(pgrc_match_ctx *c);
-int pgrc_copmem_export_index(pgrc_match_ctx *c, uint32_t *h_cumm, uint32_t *h_positions, uint64_t *count);
+int pgrc_copmem_export_index(pgrc_match_ctx *c, int strand, uint32_t *h_cumm, uint32_t *h_positions, uint64_t *count);
 
 // radix.hip: stable LSD radix sort of 64-bit records by the bit field [bit_lo, bit_hi) (hand-written; d_b / k_b / v_b: scratch of n
 // records; `scratch` grows as needed; *sorted: wherever the last pass put them); the pairs form carries a 64-bit value per key

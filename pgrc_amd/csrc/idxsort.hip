@@ -609,8 +609,9 @@ bool pgrc_ps_applicable(const pgrc_match_ctx *c, uint32_t hbits) {
 }
 
 // The hand-written front end: records straight from the text, two stable scatter passes over the bucket bits
-// [cb, hbits).  Output in c->d_skey[1] / c->d_sval[1] (sorted by partition, position order inside); c->d_sval[0] is free.
+// [cb, hbits).  Output in the build set's skey[1] / sval[1] (sorted by partition, position order inside); its sval[0] is free.
 int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_t cb) {
+    PgrcIndexSet &ix = pgrc_build_set(c);
     const uint32_t K = (uint32_t)c->cp.K, k1 = (uint32_t)c->cp.k1;
     const uint64_t hs = c->cp.hash_size, n = c->npos;
     PsPlan pl;
@@ -622,13 +623,13 @@ int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_
     const uint32_t D = 1u << pl.b2;                                       // b2 >= b1
     int e;
     for (int k = 0; k < 2; k++)
-        if ((e = pgrc_buf_ensure(c, c->d_skey[k], (n + 16) * sizeof(uint32_t))) || (e = pgrc_buf_ensure(c, c->d_sval[k], (n + 16) * sizeof(uint64_t)))) return e;
+        if ((e = pgrc_buf_ensure(c, ix.skey[k], (n + 16) * sizeof(uint32_t))) || (e = pgrc_buf_ensure(c, ix.sval[k], (n + 16) * sizeof(uint64_t)))) return e;
     const uint64_t ncnt = (uint64_t)D * pl.ntiles;
     const uint64_t nbs = sco_scratch_elems(ncnt);
-    if ((e = pgrc_buf_ensure(c, c->d_sorttmp, (ncnt + nbs) * sizeof(uint32_t) + 256))) return e;
-    uint32_t *cnt = (uint32_t *)c->d_sorttmp.p, *bsum = cnt + ncnt;
-    uint32_t *kA = (uint32_t *)c->d_skey[0].p, *kB = (uint32_t *)c->d_skey[1].p;
-    uint64_t *vA = (uint64_t *)c->d_sval[0].p, *vB = (uint64_t *)c->d_sval[1].p;
+    if ((e = pgrc_buf_ensure(c, ix.sorttmp, (ncnt + nbs) * sizeof(uint32_t) + 256))) return e;
+    uint32_t *cnt = (uint32_t *)ix.sorttmp.p, *bsum = cnt + ncnt;
+    uint32_t *kA = (uint32_t *)ix.skey[0].p, *kB = (uint32_t *)ix.skey[1].p;
+    uint64_t *vA = (uint64_t *)ix.sval[0].p, *vB = (uint64_t *)ix.sval[1].p;
     GenArgs g;
     g.pg = (const uint32_t *)c->pg2[strand].p;
     g.pg_words_alloc = c->pg_words + PGRC_PG_PAD_WORDS;
@@ -656,6 +657,7 @@ int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_
 // unused), packed_sh = bits of (t, fingerprint) in a record.
 static int ps_launch_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uint64_t *d_vals, const uint32_t *pst2, uint32_t *slow, uint32_t np,
                             uint32_t cb, uint64_t *d_ent, uint32_t packed_sh) {
+    PgrcIndexSet &ix = pgrc_build_set(c);
     const uint64_t n = c->npos;
     PsRecFmt fmt;
     fmt.sh = packed_sh;
@@ -664,8 +666,8 @@ static int ps_launch_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uin
     // the partitions the fast kernel cannot take go straight to the general kernel's list (round 5: no flags + compaction kernel in
     // between -- a 256-block launch that, beside the other strand's build, waited 1.4 ms on average for its turn)
     uint32_t *todo = slow + np, *todo_count = todo + np;
-    ulonglong2 *head = c->head_ptr;
-    const uint32_t hsh = c->head_sh;
+    ulonglong2 *head = ix.head_ptr;
+    const uint32_t hsh = ix.head_sh;
     const uint32_t ggrid = std::min<uint32_t>(np, (uint32_t)c->num_cus * 2u);
     // PGRC_INDEX_FINISH=general: the general finish kernel for every partition (tests)
     // (the fast kernel takes a partition's 2^cb buckets in one round of at most 8192: the stable front end's partitions of
@@ -697,7 +699,7 @@ static int ps_launch_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uin
         else hipLaunchKernelGGL(k_ps_finish<false>, dim3(ggrid), dim3(PF_TPB), 0, c->stream, d_keys, d_vals, pst2, cb, d_ent, head, hsh, (const uint32_t *)todo, (const uint32_t *)todo_count, np, fmt);
     }
     HIP_TRY(c, hipGetLastError());
-    c->ent_ptr = d_ent;
+    ix.ent = d_ent;
     return PGRC_OK;
 }
 
@@ -706,8 +708,9 @@ int pgrc_ps_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uint64_t *d_
     const uint64_t n = c->npos;
     const uint32_t np = 1u << (hbits - cb);
     int e;
-    if ((e = pgrc_buf_ensure(c, c->d_sorttmp, (4ull * (np + 2)) * sizeof(uint32_t) + 256))) return e;
-    uint32_t *pst = (uint32_t *)c->d_sorttmp.p, *pst2 = pst + np + 2, *slow = pst2 + np + 2;
+    DevBuf &tmp = pgrc_build_set(c).sorttmp;
+    if ((e = pgrc_buf_ensure(c, tmp, (4ull * (np + 2)) * sizeof(uint32_t) + 256))) return e;
+    uint32_t *pst = (uint32_t *)tmp.p, *pst2 = pst + np + 2, *slow = pst2 + np + 2;
     HIP_TRY(c, hipMemsetAsync(pst, 0xFF, (size_t)(np + 1) * sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(slow, 0, (size_t)(2 * np + 1) * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(k_ps_bounds, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 65536ull * 4)), dim3(256), 0, c->stream, d_keys, n, cb, pst);

@@ -463,27 +463,28 @@ int pgrc_os_build_index(pgrc_match_ctx *c, int strand, uint32_t hbits) {
     pl.ntiles1 = (n + tile - 1) / tile;
     pl.ntiles2_max = pl.ntiles1 + D1;
     int e;
-    // buffers (grow-only, shared with the other front end): d_sval[0] = pass-1 records, later ent[]; d_sval[1] = pass-2
-    // records; d_skey[0] = the pass-2 digit of every pass-1 record; d_sorttmp = count matrices, tables, flags
-    if ((e = pgrc_buf_ensure(c, c->d_sval[0], (n + 16) * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, c->d_sval[1], (n + 16) * sizeof(uint64_t))) ||
-        (e = pgrc_buf_ensure(c, c->d_skey[0], (n + 16) * sizeof(uint32_t))))
+    // buffers of the build set (grow-only, shared with the other front end): sval[0] = pass-1 records, later ent[]; sval[1] =
+    // pass-2 records; skey[0] = the pass-2 digit of every pass-1 record; sorttmp = count matrices, tables, flags
+    PgrcIndexSet &ix = pgrc_build_set(c);
+    if ((e = pgrc_buf_ensure(c, ix.sval[0], (n + 16) * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, ix.sval[1], (n + 16) * sizeof(uint64_t))) ||
+        (e = pgrc_buf_ensure(c, ix.skey[0], (n + 16) * sizeof(uint32_t))))
         return e;
     const uint64_t n1 = (uint64_t)D1 * pl.ntiles1, n2 = (uint64_t)D2 * pl.ntiles2_max;
     const uint64_t nbs = pgrc_ps_scan_blocks(std::max(n1, n2));
     const uint64_t flag_words = 2ull * np + 2;                 // np flags, the list of flagged partitions, its length (idxsort.hip)
     const uint64_t words = flag_words + (OS_MAXD + 2) + (np + 2) + nbs + n1 + n2 + 4 * (pl.ntiles2_max + 1) + 64;
-    if ((e = pgrc_buf_ensure(c, c->d_sorttmp, words * sizeof(uint32_t)))) return e;
+    if ((e = pgrc_buf_ensure(c, ix.sorttmp, words * sizeof(uint32_t)))) return e;
     OsBufs b;
-    b.slow = (uint32_t *)c->d_sorttmp.p;
+    b.slow = (uint32_t *)ix.sorttmp.p;
     b.tile_start = b.slow + flag_words;
     b.pstart = b.tile_start + OS_MAXD + 2;
     b.bsum = b.pstart + np + 2;
     b.cnt1 = b.bsum + nbs;
     b.cnt2 = b.cnt1 + n1;
     b.desc = (OsBinTile *)(((uintptr_t)(b.cnt2 + n2) + 15) & ~(uintptr_t)15);
-    b.recA = (uint64_t *)c->d_sval[0].p;
-    b.recB = (uint64_t *)c->d_sval[1].p;
-    b.aux = c->d_skey[0].p;
+    b.recA = (uint64_t *)ix.sval[0].p;
+    b.recB = (uint64_t *)ix.sval[1].p;
+    b.aux = ix.skey[0].p;
     HIP_TRY(c, hipMemsetAsync(b.slow, 0, flag_words * sizeof(uint32_t), c->stream));
     if (aux16) e = os_passes<1024, 5, 2, uint16_t, uint16_t>(c, strand, pl, b);
     else e = os_passes<1024, 6, 2, uint8_t, uint8_t>(c, strand, pl, b);

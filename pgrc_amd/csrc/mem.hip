@@ -604,8 +604,9 @@ struct StaleWalk {
         pgrc_match_ctx *c = m->base;
         char win[64];                            // (K <= 56)
         const uint32_t h = host_hash(m->K, text_at(dest, d_dw, d_dn, q, (uint32_t)m->K, win)) & (uint32_t)(c->cp.hash_size - 1);
+        const PgrcIndexSet *ix = pgrc_index_of(c, 0);
         unsigned long long hd[2];
-        if (hipMemcpy(hd, (const char *)c->head_ptr + (size_t)head_slot(h, c->head_sh) * 16, 16, hipMemcpyDeviceToHost) != hipSuccess) { lookup_err = 1; return 0; }
+        if (!ix || hipMemcpy(hd, (const char *)ix->head_ptr + (size_t)head_slot(h, ix->head_sh) * 16, 16, hipMemcpyDeviceToHost) != hipSuccess) { lookup_err = 1; return 0; }
         if (hd[0] == HEAD_EMPTY) return 0;
         pos[0] = (hd[0] & ENT_MASK) >> PGRC_FP_BITS;
         if (!(hd[0] & HEAD_OVF)) {
@@ -615,7 +616,7 @@ struct StaleWalk {
         }
         const int cnt = (int)((hd[1] >> 56) & 15u);
         unsigned long long e[PGRC_BUCKET_CAP];
-        if (hipMemcpy(e, c->ent_ptr + (hd[1] & W1_BASE_MASK), (size_t)(cnt - 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) { lookup_err = 1; return 0; }
+        if (hipMemcpy(e, ix->ent + (hd[1] & W1_BASE_MASK), (size_t)(cnt - 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) { lookup_err = 1; return 0; }
         for (int j = 1; j < cnt; j++) pos[j] = e[j - 1] >> PGRC_FP_BITS;
         return cnt;
     }
@@ -866,9 +867,11 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
     a.src = (const uint32_t *)c->pg2[0].p;
     a.N = m->N;
     a.N2 = N2;
-    a.head = (const ulonglong2 *)c->head_ptr;
-    a.hsh = c->head_sh;
-    a.ent = c->ent_ptr;
+    if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, 0))) { m->err = c->err; return e; }   // (only if somebody rebuilt the base index in between)
+    const PgrcIndexSet *ix = pgrc_index_of(c, 0);
+    a.head = (const ulonglong2 *)ix->head_ptr;
+    a.hsh = ix->head_sh;
+    a.ent = ix->ent;
     a.mask = (uint32_t)(c->cp.hash_size - 1);
     a.K = (uint32_t)m->K;
     a.k2 = (uint32_t)m->k2;
@@ -877,12 +880,6 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
     a.nprobes = nprobes;
     a.dest_is_src = dest_is_src ? 1 : 0;
     a.rev_compl = rev_compl ? 1 : 0;
-    if (c->index_strand != 0) {          // (only if somebody rebuilt the base index in between)
-        if ((e = pgrc_copmem_build_index(c, 0))) { m->err = c->err; return e; }
-        a.head = (const ulonglong2 *)c->head_ptr;
-        a.hsh = c->head_sh;
-        a.ent = c->ent_ptr;
-    }
 
     // ---- 1. events
     if ((e = pgrc_buf_ensure(c, m->d_cursor, 8))) { m->err = c->err; return e; }

@@ -95,9 +95,6 @@ void pgrc_stream_abort(pgrc_match_ctx *c) {
     if (!c->st_on && !c->st_worker.joinable()) return;
     stop_worker(c);
     c->st_on = false;
-    c->range_lo = 0;
-    c->range_n = ~0ull;
-    c->range_skip_n = false;
 }
 
 extern "C" int pgrc_match_stream_begin(pgrc_match_ctx *c, uint64_t *pos, uint8_t *rc, uint8_t *mism) {
@@ -108,7 +105,7 @@ extern "C" int pgrc_match_stream_begin(pgrc_match_ctx *c, uint64_t *pos, uint8_t
     PGRC_ON_DEVICE(c);
     pgrc_stream_abort(c);
     int e;
-    if (!(c->idx_prepared && c->index_strand == 1 && c->alt_index_strand == 0) && (e = pgrc_prepare_both_indexes(c))) return e;
+    if (!(c->idx_prepared && pgrc_index_pair_ready(c)) && (e = pgrc_prepare_both_indexes(c))) return e;
     // the per-read state of a first phase (DefaultReadsMatcher::initMatching, ReadsMatchers.cpp:97-105); have_reads is not
     // set yet, so not through pgrc_match_init_results
     if ((e = pgrc_launch_init_results(c))) return e;
@@ -159,9 +156,7 @@ int pgrc_stream_block_arrived(pgrc_match_ctx *c, uint64_t lo, uint64_t cnt, bool
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->up_ev[turn], 0));
     // the kernels' read cursors start at zero for every launch
     HIP_TRY(c, hipMemsetAsync((uint64_t *)c->d_counters.p + 16, 0, 3 * sizeof(uint64_t), c->stream));
-    c->range_lo = lo;
-    c->range_n = cnt;
-    c->range_skip_n = true;
+    const PgrcReadRange block{lo, cnt, true};                        // (the reads with N wait for stream_end)
     int e;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     if (c->opt.stream_timing && c->st_tbase) {
@@ -170,16 +165,11 @@ int pgrc_stream_block_arrived(pgrc_match_ctx *c, uint64_t lo, uint64_t cnt, bool
         HIP_TRY(c, hipEventRecord(t0, c->stream));
     }
     if (c->st_dual) {
-        e = pgrc_copmem_match_dual(c);                               // active set = strand 1, alternate = strand 0
+        e = pgrc_copmem_match_dual(c, block);
     } else {
-        pgrc_swap_index_sets(c);                                     // the two passes in the reference's order
-        e = pgrc_copmem_match_phase(c, 0, 0);
-        pgrc_swap_index_sets(c);
-        if (!e) e = pgrc_copmem_match_phase(c, 1, 0);
+        e = pgrc_copmem_match_phase(c, 0, 0, block);                 // the two passes in the reference's order
+        if (!e) e = pgrc_copmem_match_phase(c, 1, 0, block);
     }
-    c->range_lo = 0;
-    c->range_n = ~0ull;
-    c->range_skip_n = false;
     if (t1) {
         (void)hipEventRecord(t1, c->stream);
         c->st_tev.emplace_back(t0, t1);
@@ -208,10 +198,8 @@ extern "C" int pgrc_match_stream_end(pgrc_match_ctx *c, uint64_t hist[256], uint
     // side stream and BESIDE the blocks that are still being matched (one lane per read, latency-bound: it fits in; the
     // blocks' kernels skip the reads with N, so the two write disjoint reads); the main stream joins it at its tail
     if (c->n_nreads) {
-        c->n_after = c->st_ready;
-        e = pgrc_copmem_match_nreads(c, 0, 1, c->st_dual);   // one launch: a read's forward query, then its RC query (the blocks' dual kernel took the reads with at most 4 N)
+        e = pgrc_copmem_match_nreads(c, 0, 1, c->st_dual, c->st_ready);   // one launch: a read's forward query, then its RC query (the blocks' dual kernel took the reads with at most 4 N)
         if (!e) e = pgrc_copmem_join_nreads(c);
-        c->n_after = nullptr;
     }
     if (c->opt.stream_timing) {
         (void)hipStreamSynchronize(c->stream);
@@ -238,16 +226,7 @@ extern "C" int pgrc_match_stream_end(pgrc_match_ctx *c, uint64_t hist[256], uint
     release_kept(c);
     if (!e && c->st_err) { e = c->st_err; c->err = "stream_end: a result download failed"; }
     if (e) return e;
-    uint64_t scr[9];
-    HIP_TRY(c, hipMemcpy(scr, (const uint64_t *)c->d_counters.p + 24, sizeof scr, hipMemcpyDeviceToHost));
-    if (c->st_dual) {
-        for (int k = 0; k < 5; k++) c->ctr.dual[k] = scr[k];
-        c->ctr.redo_reads = scr[5];
-        c->ctr.dual_seed_probes = scr[6];
-        c->ctr.dual_skip_reads = scr[7];
-        c->ctr.dual_rewinds = scr[8];
-        c->ctr.screened = 2;
-    }
+    if (c->st_dual && (e = pgrc_fetch_schedule_counters(c, true))) return e;
     c->ctr.ms_total = (float)((now_s() - c->st_t0) * 1e3);           // (host clock: stream_begin .. here)
     c->have_results = true;
     if (hist) memcpy(hist, c->hist, sizeof c->hist);
