@@ -18,8 +18,8 @@
  * holds them: the reassembly of the mismatch streams no longer has to stay with the caller; positions and mismatch list starts are prefix scans on the device, every row
  * is an independent job of a row kernel that assembles tiles of rows in LDS, and rows come back to the host in chunks
  * copied down while the next chunk is made.  More of the decoder's stages follow further down: the restore of the matched
- * pseudogenomes, the pair-position coding of the order-preserving paired mode (with its encoder), the encoder's pair-order
- * coding and the archive form of a list's mismatch streams (both directions).
+ * pseudogenomes, the pair-position coding of the order-preserving paired mode (with its encoder), the pair-order coding
+ * of the other paired mode (with its encoder) and the archive form of a list's mismatch streams (both directions).
  *
  * Same conventions as pgrc_match.h: 0 = success, PGRC_E_* otherwise; host buffers stay the caller's (nothing is
  * borrowed beyond a call); no CPU fallback -- without a HIP device every call fails.
@@ -235,9 +235,11 @@ typedef struct {
 int pgrc_pairpos_get_timing(pgrc_decode_ctx *ctx, pgrc_pairpos_timing *out);
 
 /* ---- The pair-order coding of the paired mode that does NOT preserve the order (SeparatedPseudoGenomePersistence::
- * compressReadsOrder, SeparatedPseudoGenomePersistence.cpp:220-339, called from pgrc-encoder.cpp:223): the encoder's side
- * only.  The decoder (decompressReadsOrder, :341-443) is a true recurrence -- the k-th pair lands on the k-th entry that no
- * earlier pair has marked -- and stays with the caller; pgrc_decode_set_order takes its rlIdxOrder.
+ * compressReadsOrder, SeparatedPseudoGenomePersistence.cpp:220-339, called from pgrc-encoder.cpp:223) and its decoder
+ * (decompressReadsOrder, :341-443).  The decoder is a true recurrence -- the k-th pair lands on the k-th entry that no
+ * earlier pair has marked -- so its landing is ONE wave's sweep over the entries, 64 at a time, with everything around it
+ * (the offsets of all pairs, the forms' tails, the checks) parallel: pgrc_pairorder_decode.h, included at the end of this
+ * header.
  *
  * T = readsCount (even, below 2^32) entries of the joined reads lists HQ | LQ | N; org[i] is entry i's original index, a
  * permutation of [0, T); reads 2q and 2q+1 are mates.  With rev[org[i]] = i the mate of entry i is rev[org[i] ^ 1].
@@ -305,6 +307,9 @@ typedef struct {
 } pgrc_pairorder_timing;
 /* of the context's last successful pgrc_pairorder_encode */
 int pgrc_pairorder_get_timing(pgrc_decode_ctx *ctx, pgrc_pairorder_timing *out);
+
+/* The decoder of this coding -- decompressReadsOrder on the device and the PE order straight from the streams -- is declared
+ * in pgrc_pairorder_decode.h, which this header includes at its end. */
 
 /* ---- The archive form of a reads list's mismatch streams (SeparatedPseudoGenomeOutputBuilder::compressedBuild,
  * SeparatedPseudoGenomePersistence.cpp:905-952, and the loader's inverse, ExtendedReadsListWithConstantAccessOption::
@@ -377,6 +382,8 @@ typedef struct {
 } pgrc_list_archive_timing;
 /* of the context's last successful pgrc_list_archive_encode or pgrc_decode_add_list_archive */
 int pgrc_list_archive_get_timing(pgrc_decode_ctx *ctx, pgrc_list_archive_timing *out);
+
+#include "pgrc_pairorder_decode.h"
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,13 @@ from .matchers import (  # noqa: F401
 from .textmatch import CopMEMMatcher  # noqa: F401
 from .readsets import DividedPCLReadsSets, DividedReadsSets  # noqa: F401
 from . import synth  # noqa: F401
-from .decode import PgRCDecoder, compressReadsOrder, compressReadsPgPositions, decompressReadsPgPositions  # noqa: F401
+from .decode import (  # noqa: F401
+    PgRCDecoder,
+    compressReadsOrder,
+    compressReadsPgPositions,
+    decompressReadsOrder,
+    decompressReadsPgPositions,
+)
 from .assemble import PgAssembler  # noqa: F401
 from .overlap import OverlapFinder  # noqa: F401
 from .varlen import VarLenDNACoder  # noqa: F401

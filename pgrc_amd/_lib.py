@@ -73,6 +73,14 @@ class ListArchiveTiming(C.Structure):    # pgrc_list_archive_timing
                 ("bytes_up", C.c_uint64), ("bytes_down", C.c_uint64), ("n_nonzero", C.c_uint64), ("limit", C.c_uint64)]
 
 
+class PairOrderDecodeTiming(C.Structure):    # pgrc_pairorder_decode_timing
+    _fields_ = [("struct_size", C.c_uint32), ("form", C.c_int32), ("ms_upload", C.c_float), ("ms_chain_device", C.c_float),
+                ("ms_landing_device", C.c_float), ("ms_tail_device", C.c_float), ("ms_check_device", C.c_float),
+                ("ms_download", C.c_float), ("ms_call", C.c_float), ("bytes_up", C.c_uint64), ("bytes_down", C.c_uint64),
+                ("n_near", C.c_uint64), ("n_delta", C.c_uint64), ("n_full", C.c_uint64), ("landing_words", C.c_uint64),
+                ("landing_rounds", C.c_uint64)]
+
+
 class ExportPgOrderArgs(C.Structure):   # pgrc_export_pg_order_args
     _fields_ = [("order", C.c_void_p), ("n_matched", C.c_uint64), ("read_org_idx", C.c_void_p), ("list_off", C.c_void_p),
                 ("list_org_idx", C.c_void_p), ("list_rev_comp", C.c_void_p), ("list_count", C.c_uint64),

@@ -2,7 +2,8 @@
 // order (pairorder.hip) and the archive form of a list's mismatch streams (listarchive.hip).  Each holds its grow-only device
 // buffers, the events of its phases and the timing of its last call, and nothing else: a coder runs on any stage handle
 // (stagectx.h) beside the state it is given.  The decode context (decctx.h) holds one of each behind the exported entry
-// points; the reads list (rlistctx.h) holds one of each for the encode halves it runs on lists that lie on the device.
+// points; the reads list (rlistctx.h) holds one of each for the encode halves it runs on lists that lie on the device.  The
+// pair order's decoder has a state of its own, which only the decode context holds.
 #pragma once
 
 #include "pgrc_decode.h"
@@ -28,6 +29,18 @@ struct PgrcPairOrder {
     bool have_timing = false;
     pgrc_pairorder_timing tm{};
     DevBufList bufs() { return {&in, &rev, &ent, &pair, &out, &bsum}; }
+    void release() { dec_free_all(bufs()); ev.release(); }
+};
+
+// the pair-order decoder: the uploaded streams, the flag scans and every pair's offset, the landed pairs (COMPLETE: gathered
+// from there), the landing's bitmap and the check's, scan scratch with the error, count and statistics words, the result of
+// pgrc_pairorder_decode before it goes down
+struct PgrcPairOrderDec {
+    DevBuf in, pair, land, marks, bsum, out;
+    PhaseEvents<7> ev;
+    bool have_timing = false;
+    pgrc_pairorder_decode_timing tm{};
+    DevBufList bufs() { return {&in, &pair, &land, &marks, &bsum, &out}; }
     void release() { dec_free_all(bufs()); ev.release(); }
 };
 

@@ -48,6 +48,7 @@ struct pgrc_decode_ctx : PgrcStage {
     // the list codings behind pgrc_pairpos_*, pgrc_pairorder_* and pgrc_list_archive_* (codingctx.h)
     PgrcPairPos pp;
     PgrcPairOrder po;
+    PgrcPairOrderDec pod;
     PgrcListArchive la;
 };
 
@@ -58,6 +59,10 @@ int pgrc_decode_create_on(int32_t device, pgrc_decode_ctx **out);
 // fills d->pp.tm but for ms_download / ms_call
 int pgrc_pairpos_decode_device(pgrc_decode_ctx *d, const pgrc_pairpos_streams *s, uint64_t *d_out);
 int pgrc_pairpos_check_streams(PgrcStage *d, const pgrc_pairpos_streams *s);   // the checks that need no device (PGRC_E_PARAM)
+// pairorder.hip: rlIdxOrder of `s` as n_total u32 at d_out (device, on d->stream; synchronised on return, every device-side
+// finding already turned into PGRC_E_PARAM); fills d->pod.tm but for ms_download / ms_call
+int pgrc_pairorder_decode_device(pgrc_decode_ctx *d, const pgrc_pairorder_streams *s, uint32_t *d_out);
+int pgrc_pairorder_check_streams(PgrcStage *d, const pgrc_pairorder_streams *s);   // the checks that need no device (PGRC_E_PARAM)
 // listarchive.hip: the mismatch tables of list `l` (mcum, moff, msym, nmis) from the archive-form streams `s`, on d->stream with d->la;
 // device-side findings (DEC_F_MISOFF, DEC_F_MISSYM) go to d->flag, which the caller reads (pgrc_decode_add_list_archive)
 int pgrc_la_tables(pgrc_decode_ctx *d, pgrc_decode_ctx::List &l, const pgrc_list_archive_streams *s);

@@ -384,6 +384,7 @@ void pgrc_decode_destroy(pgrc_decode_ctx *d) {
         if (ev) (void)hipEventDestroy(ev);
     d->pp.release();
     d->po.release();
+    d->pod.release();
     d->la.release();
     if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
     pgrc_stage_close(d);
@@ -609,6 +610,40 @@ int pgrc_decode_set_order_pair_streams(pgrc_decode_ctx *d, const pgrc_pairpos_st
     d->pp.tm.bytes_down = 0;
     d->pp.tm.ms_call = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     d->pp.have_timing = true;
+    return PGRC_OK;
+}
+
+// The PE order from the archive's own streams: rlIdxOrder is decoded on the device (pairorder.hip) into rl_order
+int pgrc_decode_set_order_pair_order_streams(pgrc_decode_ctx *d, const pgrc_pairorder_streams *s, int32_t rev_compl_pair_file) {
+    if (!d) return PGRC_E_PARAM;
+    d->have_order = false;
+    int e;
+    if ((e = pgrc_pairorder_check_streams(d, s))) return e;
+    if (!d->nl) return dec_fail(d, PGRC_E_STATE, "set_order_pair_order_streams before add_list");
+    PGRC_ON_DEVICE(d);
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t T = s->n_total;
+    if (T != dec_entries(d)) return dec_fail(d, PGRC_E_PARAM, "PE order: n_total differs from the lists' entries");
+    if ((e = pgrc_buf_unpooled(d, d->rl_order, T * 4))) return e;
+    if ((e = pgrc_pairorder_decode_device(d, s, (uint32_t *)d->rl_order.p))) return e;
+    if ((e = dec_clear_err(d))) return e;
+    HIP_TRY(d, hipEventRecord(d->ev_a, d->stream));
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((T + 255) / 256, 4096));
+    if (T) hipLaunchKernelGGL(k_dec_check_index, dim3(grid), dim3(256), 0, d->stream, (const uint32_t *)d->rl_order.p, T, dec_entries(d), (uint32_t *)d->flag.p);
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->ev_b, d->stream));
+    if ((e = dec_check_err(d, "set_order_pair_order_streams"))) return e;
+    d->tm.ms_order_device = dec_elapsed(d->ev_a, d->ev_b);
+    d->ord = pgrc_decode_order{};
+    d->ord.struct_size = sizeof(pgrc_decode_order);
+    d->ord.mode = PGRC_DECODE_PE;
+    d->ord.n_total = T;
+    d->ord.rev_compl_pair_file = rev_compl_pair_file;
+    d->have_order = true;
+    d->pod.tm.ms_download = 0;
+    d->pod.tm.bytes_down = 0;
+    d->pod.tm.ms_call = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    d->pod.have_timing = true;
     return PGRC_OK;
 }
 

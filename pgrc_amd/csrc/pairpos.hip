@@ -144,14 +144,7 @@ __global__ void __launch_bounds__(PP_TPB) k_pp_dec_ops(const uint64_t *__restric
     kind[i] = (uint8_t)PP_K_SET;
 }
 
-// The segmented sum: scanops.h's scan over (value, set) with (a, b) -> b.set ? b : (a.v + b.v, a.set)
-struct __attribute__((packed, aligned(4))) PpSeg {      // 12 bytes: three words to shuffle
-    int64_t v;
-    uint32_t set;
-};
-__device__ __forceinline__ PpSeg pp_seg_op(PpSeg a, PpSeg b) { return b.set ? b : PpSeg{a.v + b.v, a.set}; }
-struct PpSegOp { __device__ PpSeg operator()(PpSeg a, PpSeg b) const { return pp_seg_op(a, b); } };
-
+// (the segmented sum itself -- PpSeg, PpSegOp -- is ppchain.h, shared with pairorder.hip's decoder)
 struct PpChainIn {          // the chain's entry of ranked pair i: near and keeping pairs add nothing
     const uint8_t *kind;
     const int64_t *val;

@@ -60,3 +60,12 @@ __global__ void __launch_bounds__(PP_TPB) k_pp_enc_kinds(uint64_t nf, const R *_
     del_flag[k] = pp_fits<D>(dl) ? 1 : 0;
     dval[k] = (D)dl;
 }
+
+// The decoders' refPrev: every far pair is ADD d (delta), SET rel (a full pair that sets it) or ADD 0 (a full pair that keeps it).
+// The segmented sum: scanops.h's scan over (value, set) with (a, b) -> b.set ? b : (a.v + b.v, a.set)
+struct __attribute__((packed, aligned(4))) PpSeg {      // 12 bytes: three words to shuffle
+    int64_t v;
+    uint32_t set;
+};
+__device__ __forceinline__ PpSeg pp_seg_op(PpSeg a, PpSeg b) { return b.set ? b : PpSeg{a.v + b.v, a.set}; }
+struct PpSegOp { __device__ PpSeg operator()(PpSeg a, PpSeg b) const { return pp_seg_op(a, b); } };

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import ExportStreams, ListArchiveStreams, ListArchiveTiming, PgrcMatchError, lib
+from ._lib import ExportStreams, ListArchiveStreams, ListArchiveTiming, PairOrderDecodeTiming, PgrcMatchError, lib
 
 _P = C.c_void_p
 
@@ -102,6 +102,9 @@ DECODE_PROTOS = [
     ("pgrc_pairorder_encode", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.c_int32, C.POINTER(PairOrderStreams)]),
     ("pgrc_pairorder_free", None, [C.POINTER(PairOrderStreams)]),
     ("pgrc_pairorder_get_timing", C.c_int, [_P, C.POINTER(PairOrderTiming)]),
+    ("pgrc_pairorder_decode", C.c_int, [_P, C.POINTER(PairOrderStreams), _P]),
+    ("pgrc_decode_set_order_pair_order_streams", C.c_int, [_P, C.POINTER(PairOrderStreams), C.c_int32]),
+    ("pgrc_pairorder_get_decode_timing", C.c_int, [_P, C.POINTER(PairOrderDecodeTiming)]),
     ("pgrc_list_archive_encode", C.c_int, [_P, C.POINTER(ExportStreams), C.c_int32, C.POINTER(ListArchiveStreams)]),
     ("pgrc_list_archive_free", None, [C.POINTER(ListArchiveStreams)]),
     ("pgrc_decode_add_list_archive", C.c_int, [_P, C.POINTER(DecodeList), C.POINTER(ListArchiveStreams)]),
@@ -163,6 +166,33 @@ def _pairpos_struct(streams: dict):
 PAIRORDER_STREAMS = (("off8_flag", np.uint8), ("off_value", np.uint8), ("delta8_flag", np.uint8), ("delta_value", np.int8),
                      ("full_offset", np.uint32), ("pair_base_org_idx", np.uint32), ("off_base_file_flag", np.uint8),
                      ("nonoff_base_file_flag", np.uint8), ("rev", np.uint32))
+
+
+PGRC_PAIRORDER_DECODE_BATCH = 16384  # entries of one batch of the pair-order landing (include/pgrc_decode.h)
+
+
+def _pairorder_struct(streams: dict):
+    """the dict compressReadsOrder returns (stream name -> array, plus n_total and form) as a pgrc_pairorder_streams: the
+    streams the dict does not hold stay NULL; the counts are the arrays' sizes unless the dict names them (n_off8,
+    n_delta_flag, n_delta8, n_full).  -> (struct, the arrays it points into)"""
+    s = PairOrderStreams()
+    s.struct_size = C.sizeof(PairOrderStreams)
+    s.form = int(streams["form"])
+    s.n_total = int(streams["n_total"])
+    keep = {}
+    for name, dt in PAIRORDER_STREAMS:
+        if streams.get(name) is None:
+            continue
+        a = keep[name] = np.ascontiguousarray(streams[name], dtype=dt)
+        setattr(s, name, _ptr(a) if a.size else None)
+
+    def size(name):
+        return keep[name].size if name in keep else 0
+    s.n_off8 = int(streams.get("n_off8", size("off_value")))
+    s.n_delta_flag = int(streams.get("n_delta_flag", size("delta8_flag")))
+    s.n_delta8 = int(streams.get("n_delta8", size("delta_value")))
+    s.n_full = int(streams.get("n_full", size("full_offset")))
+    return s, keep
 
 
 PGRC_LIST_ARCHIVE_TILE = 8192       # entries of one tile of the split (include/pgrc_decode.h)
@@ -448,6 +478,26 @@ class PgRCDecoder:
         self._ck(lib.pgrc_pairorder_get_timing(self._h, C.byref(t)))
         return {k: getattr(t, k) for k, _ in t._fields_ if k != "struct_size"}
 
+    def decompressReadsOrder(self, streams: dict) -> np.ndarray:
+        """SeparatedPseudoGenomePersistence::decompressReadsOrder (:341-443) on the device: the streams of any form (a dict
+        as compressReadsOrder returns) -> rlIdxOrder as n_total uint32"""
+        s, keep = _pairorder_struct(streams)
+        out = np.empty(int(s.n_total), dtype=np.uint32)
+        self._ck(lib.pgrc_pairorder_decode(self._h, C.byref(s), _ptr(out)))
+        return out
+
+    def set_order_pair_order_streams(self, streams: dict, rev_compl_pair_file: bool = False) -> None:
+        """the PE order from the archive's pair-order streams (a dict as compressReadsOrder returns): rlIdxOrder is decoded
+        on the device into the context's order and never exists on the host"""
+        s, keep = _pairorder_struct(streams)
+        self._ck(lib.pgrc_decode_set_order_pair_order_streams(self._h, C.byref(s), int(bool(rev_compl_pair_file))))
+
+    def pairorder_decode_timing(self) -> dict:
+        t = PairOrderDecodeTiming()
+        t.struct_size = C.sizeof(PairOrderDecodeTiming)
+        self._ck(lib.pgrc_pairorder_get_decode_timing(self._h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_ if k != "struct_size"}
+
     def list_archive_encode(self, mis_cnt, mis_sym, mis_rev_off, fast_level: bool = False) -> dict:
         """SeparatedPseudoGenomeOutputBuilder::compressedBuild's reshaping of a list's mismatch streams (:905-952) on the
         device: counts, context codes and rev-coded offsets as pgrc_export_streams holds them -> zero_flags, nonzero_cnt,
@@ -578,5 +628,16 @@ def compressReadsOrder(org_idx_parts, form: int, device: int = -1) -> dict:
     dec = PgRCDecoder(1, device)
     try:
         return dec.compressReadsOrder(org_idx_parts, form)
+    finally:
+        dec.close()
+
+
+def decompressReadsOrder(streams: dict, ctx: PgRCDecoder | None = None, device: int = -1) -> np.ndarray:
+    """PgRCDecoder.decompressReadsOrder on `ctx`, or on a context of its own"""
+    if ctx is not None:
+        return ctx.decompressReadsOrder(streams)
+    dec = PgRCDecoder(1, device)
+    try:
+        return dec.decompressReadsOrder(streams)
     finally:
         dec.close()
