@@ -357,37 +357,20 @@ void pgrc_match_destroy(pgrc_match_ctx *c) {
     if (!c) return;
     if (c->multi) { pgrc_multi_destroy(c); return; }
     PgrcDeviceScope scope(c->device);
-    pgrc_stream_abort(c);
+    pgrc_stream_release(c);
     // nothing of this context may still be running when its buffers go to the pool, from where the next context takes them
     // (index builds started ahead and never used, an abandoned streamed run)
     (void)hipDeviceSynchronize();
-    for (int k = 0; k < 2; k++) {
-        if (c->up_stream[k]) {
-            (void)hipStreamDestroy(c->up_stream[k]);
-            (void)hipEventDestroy(c->up_ev[k]);
-        }
-        pgrc_buf_free(c->up_stage[k]);
-    }
-    pgrc_buf_free(c->up_flag);
-    pgrc_buf_free(c->up_lidx);
-    if (c->st_ready) (void)hipEventDestroy(c->st_ready);
-    if (c->st_tbase) (void)hipEventDestroy(c->st_tbase);
-    if (c->side_stream) {
-        (void)hipStreamDestroy(c->side_stream);
-        (void)hipEventDestroy(c->side_ev[0]);
-        (void)hipEventDestroy(c->side_ev[1]);
-    }
-    if (c->build_stream) {
-        (void)hipStreamDestroy(c->build_stream);
-        (void)hipEventDestroy(c->build_ev[0]);
-        (void)hipEventDestroy(c->build_ev[1]);
-    }
+    c->up.stream[0].release();
+    c->up.stream[1].release();
+    c->side.release();
+    c->build.release();
     DevBufList bufs = {&c->pg2[0], &c->pg2[1], &c->reads_own, &c->nread_idx, &c->nread_ascii, &c->nread_flag, &c->nread_npos, &c->d_pos,
-                       &c->d_rc, &c->d_mism, &c->d_hist, &c->d_counters, &c->d_headpair, &c->d_scr_pos, &c->d_scr_flag,
-                       &c->s_keys, &c->s_filter, &c->s_vals, &c->s_tab, &c->s_hits, &c->s_tmp, &c->s_sort, &c->s_seg, &c->s_hv, &c->s_hvu, &c->s_nmask, &c->s_best, &c->s_rows};
+                       &c->d_rc, &c->d_mism, &c->d_hist, &c->d_counters, &c->d_headpair, &c->d_scr_pos, &c->d_scr_flag};
+    for (const DevBufList &more : {c->up.bufs(), c->seed.bufs()}) bufs.insert(bufs.end(), more.begin(), more.end());
     for (PgrcIndexSet &ix : c->idx) bufs.insert(bufs.end(), {&ix.head, &ix.skey[0], &ix.skey[1], &ix.sval[0], &ix.sval[1], &ix.sorttmp});
     pgrc_buf_free_all(bufs.data(), bufs.size());                 // (the device is idle: waited for above)
-    for (DevBuf &b : c->up_nchunks) pgrc_buf_free(b);
+    c->up.reset();
     if (c->have_events)
         for (auto &e : c->ev) (void)hipEventDestroy(e);
     delete c;
@@ -434,7 +417,7 @@ int pgrc_pg_alloc(pgrc_match_ctx *c, uint64_t G) {
         return PGRC_E_PARAM;
     }
     if (c->idx_prepared) {                       // index builds started ahead of a run may still be reading the old text
-        if (c->build_stream) (void)hipStreamSynchronize(c->build_stream);
+        if (c->build.stream) (void)hipStreamSynchronize(c->build.stream);
         (void)hipStreamSynchronize(c->stream);
     }
     if (G != c->G) c->screen_broken = false;     // another text: the second index set may fit now
@@ -519,7 +502,7 @@ int pgrc_match_pack_pg_slice(pgrc_match_ctx *c, const char *pg, uint64_t count, 
     for (uint64_t off = 0; off < count && rcode == PGRC_OK; off += CH) {
         const uint64_t len = std::min(CH, count - off);
         if (hipMemcpyAsync(stage.p, pg + off, len, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rcode = PGRC_E_DEVICE; break; }
-        rcode = pgrc_launch_pack_ascii(c, (const uint8_t *)stage.p, len, (uint32_t *)d_words_out + off / 16, (uint32_t *)flag.p);
+        rcode = pgrc_launch_pack_ascii(c, c->stream, (const uint8_t *)stage.p, len, (uint32_t *)d_words_out + off / 16, (uint32_t *)flag.p);
         if (hipStreamSynchronize(c->stream) != hipSuccess) rcode = PGRC_E_DEVICE;
     }
     uint32_t bad = 0;
@@ -571,7 +554,7 @@ int pgrc_match_export_pg(pgrc_match_ctx *c, int strand, uint32_t *words) {
     if (!c->have_pg) { c->err = "export_pg: no pseudogenome set"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     if (strand == 1 && !c->have_rc) {
-        int e = pgrc_launch_revcomp(c, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G);
+        int e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G);
         if (e) return e;
         c->have_rc = true;
     }
@@ -623,127 +606,126 @@ int pgrc_match_begin_reads(pgrc_match_ctx *c, uint64_t n) {
     //  set cannot, and at C3 the array is 400 MB that a memory-tight job would rather give its second index set)
     // (cleared on a stream of its own and waited for: the main stream may hold index builds started ahead of the run --
     //  pgrc_match_prepare_index --, which neither this nor the uploads that follow should queue behind)
-    if (!c->up_stream[0]) {
-        hipError_t he = hipStreamCreateWithFlags(&c->up_stream[0], hipStreamNonBlocking);
-        if (he == hipSuccess) he = hipEventCreateWithFlags(&c->up_ev[0], hipEventDisableTiming);
-        if (he != hipSuccess) { c->up_stream[0] = nullptr; c->err = std::string("begin_reads: ") + hipGetErrorString(he); return pgrc_hip_code(he); }
-    }
-    HIP_TRY(c, hipMemsetAsync(c->nread_flag.p, 0, n ? n : 1, c->up_stream[0]));
-    HIP_TRY(c, hipStreamSynchronize(c->up_stream[0]));
-    c->up_next = 0;
-    c->up_chunk = 0;
-    c->up_nidx.clear();
-    c->up_nmany = 0;
-    for (DevBuf &b : c->up_nchunks) pgrc_buf_free(b);
-    c->up_nchunks.clear();
-    c->up_nchunk_rows.clear();
-    c->up_open = true;
+    if ((e = c->up.stream[0].ensure(c, "begin_reads"))) return e;
+    HIP_TRY(c, hipMemsetAsync(c->nread_flag.p, 0, n ? n : 1, c->up.stream[0].stream));
+    HIP_TRY(c, hipStreamSynchronize(c->up.stream[0].stream));
+    c->up.reset();
+    c->up.open = true;
     return PGRC_OK;
+}
+
+#define UP_MARK(c, what) pgrc_stream_mark(c, "  append: " what)
+
+// A staging chunk, all of it queued on `up`: the rows [first, first + cnt) of the set copied from `src` into `stage`, unpacked
+// into the read array, and -- ASCII and ACGNT rows -- the reads with N flagged and their N's located (flag 1 -> 3 for reads with
+// at most 4 of them: the dual kernel's own)
+static int stage_chunk(pgrc_match_ctx *c, hipStream_t up, void *stage, const uint8_t *src, size_t bytes, bool src_device, uint64_t first, uint64_t cnt,
+                       int32_t symbols) {
+    const uint32_t L = c->prm.read_len;
+    uint32_t *words = (uint32_t *)c->reads_own.p, *bad = (uint32_t *)c->up.flag.p;
+    uint8_t *nflag = (uint8_t *)c->nread_flag.p;
+    if (hipMemcpyAsync(stage, src, bytes, src_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, up) != hipSuccess) return PGRC_E_DEVICE;
+    if (symbols == 4) return pgrc_launch_repack_reads_ref(c, up, (const uint8_t *)stage, first, cnt, L, words, c->stride);   // (an ACGT set cannot hold an N)
+    int e = symbols == 0 ? pgrc_launch_pack_reads_ascii(c, up, (const uint8_t *)stage, first, cnt, L, words, c->stride, nflag, bad)
+                         : pgrc_launch_unpack_reads_acgnt(c, up, (const uint8_t *)stage, first, cnt, L, words, c->stride, nflag, bad);
+    if (e || (e = pgrc_buf_ensure(c, c->nread_npos, std::max<uint64_t>(c->n, 1) * sizeof(uint32_t)))) return e;   // (first such block: allocated)
+    return pgrc_launch_npos_rows(c, up, (const uint8_t *)stage, symbols, first, cnt, L, nflag, (uint32_t *)c->nread_npos.p);
+}
+
+// The N flags of an unpacked chunk come down through `up`: its reads with N join the side list; local: their rows within the chunk
+static int list_n_rows(pgrc_match_ctx *c, hipStream_t up, uint64_t first, uint64_t cnt, std::vector<uint8_t> &nf, std::vector<uint32_t> &local) {
+    nf.resize(cnt);
+    if (hipMemcpyAsync(nf.data(), (const uint8_t *)c->nread_flag.p + first, cnt, hipMemcpyDeviceToHost, up) != hipSuccess || hipStreamSynchronize(up) != hipSuccess)
+        return PGRC_E_DEVICE;
+    local.clear();
+    for (uint64_t k = 0; k < cnt; k++)
+        if (nf[k]) {
+            c->up.nidx.push_back((uint32_t)(first + k));
+            if (nf[k] == 1) c->up.nmany++;
+            local.push_back((uint32_t)k);
+        }
+    UP_MARK(c, "N flags on the host, list made");
+    return PGRC_OK;
+}
+
+// The ASCII rows of a chunk's reads with N stay in HBM, in a buffer of their own (they are a small minority): uploaded from the
+// chunk's host rows (ASCII input) or made from the staged ones on the device (ACGNT input).  Waited for: `stage` is reused.
+static int keep_n_rows(pgrc_match_ctx *c, hipStream_t up, const void *stage, const uint8_t *rows, int32_t symbols, const std::vector<uint32_t> &local,
+                       std::vector<uint8_t> &hrows) {
+    const uint32_t L = c->prm.read_len;
+    const size_t nn = local.size();
+    if (!nn) return PGRC_OK;
+    DevBuf nrows;
+    int e;
+    if ((e = pgrc_buf_ensure(c, nrows, nn * L))) return e;
+    UP_MARK(c, "room for the N rows");
+    c->up.nchunks.push_back(nrows);
+    c->up.nchunk_rows.push_back(nn);
+    if (symbols == 0) {
+        hrows.clear();
+        for (uint32_t k : local) hrows.insert(hrows.end(), rows + (size_t)k * L, rows + (size_t)(k + 1) * L);
+        if (hipMemcpyAsync(nrows.p, hrows.data(), nn * L, hipMemcpyHostToDevice, up) != hipSuccess || hipStreamSynchronize(up) != hipSuccess) return PGRC_E_DEVICE;
+        return PGRC_OK;
+    }
+    if ((e = pgrc_buf_ensure(c, c->up.lidx, nn * sizeof(uint32_t)))) return e;
+    if (hipMemcpyAsync(c->up.lidx.p, local.data(), nn * sizeof(uint32_t), hipMemcpyHostToDevice, up) != hipSuccess) return PGRC_E_DEVICE;
+    e = pgrc_launch_nrows_ascii_acgnt(c, up, (const uint8_t *)stage, (const uint32_t *)c->up.lidx.p, nn, L, (uint8_t *)nrows.p);
+    if (hipStreamSynchronize(up) != hipSuccess) e = PGRC_E_DEVICE;
+    UP_MARK(c, "N rows as ASCII on the device");
+    return e;
 }
 
 // One block of rows in any of the three host formats: `symbols` 0 = ASCII rows (read_len bytes), 4 = the reference's
 // ACGT packing (4 symbols per byte), 5 = its ACGNT packing (3 symbols per byte).  Staged through a bounded device
 // buffer and converted to the word-major 2-bit layout there; reads holding an N are flagged, and their ASCII rows
 // (made on the device for the packed formats) are kept for the side list of end_reads.
-#define UP_MARK(c, what) do { if ((c)->opt.stream_timing && (c)->st_on) fprintf(stderr, "pgrc stream: %8.2f ms    append: %s\n", (std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - (c)->st_t0) * 1e3, what); } while (0)
 // src_device: `rows` is memory of the context's device (packed rows only): the staging copy is device to device
 static int append_rows(pgrc_match_ctx *c, const uint8_t *rows, uint64_t count, int32_t symbols, bool src_device = false) {
-    if (!c->up_open || c->up_next + count > c->n) { c->err = "append_reads: outside begin/end or too many rows"; return PGRC_E_STATE; }
+    if (!c->up.open || c->up.next + count > c->n) { c->err = "append_reads: outside begin/end or too many rows"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     const uint32_t L = c->prm.read_len;
     const uint32_t rb = symbols == 0 ? L : symbols == 4 ? (L + 3) / 4 : (L + 2) / 3;   // host bytes per row
-    DevBuf &flag = c->up_flag, &lidx = c->up_lidx;
-    auto cleanup = [&]() {};
     int e;
+    // a streamed run (stream.hip) uploads and unpacks on streams of its own, beside the matching of the blocks before
+    // (no call on the null stream and no hipFree in here: both wait for the main stream, where a streamed run's matching is queued)
+    const bool streamed = pgrc_stream_active(c);
     // rows per staging chunk: ~256 MiB, a multiple of 1024 rows (a streamed run matches chunk by chunk: whole lines of the
     // word-major read array)
     // (a streamed run matches chunk by chunk, and every launch of the persistent match kernel pays ~4 ms of ramp and drain:
     //  C3 through the boundary 0.29 / 0.23 / 0.22 / 0.20 s with chunks of 128 / 256 / 512 / 1024 MiB, profiles/r03_boundary_c3.json)
-    uint64_t chunk_mib = c->st_on ? 1024 : 256;
+    uint64_t chunk_mib = streamed ? 1024 : 256;
     if (c->opt.upload_chunk_mb) chunk_mib = c->opt.upload_chunk_mb;   // (experiments)
     const uint64_t CHR = std::max<uint64_t>(1024, ((chunk_mib << 20) / rb) & ~1023ull);
     for (int k = 0; k < 2; k++)
-        if ((e = pgrc_buf_ensure(c, c->up_stage[k], (size_t)std::min(CHR, std::max<uint64_t>(count, 1)) * rb))) return e;
-    if ((e = pgrc_buf_ensure(c, flag, sizeof(uint32_t)))) { cleanup(); return e; }
-    // a streamed run (stream.hip) uploads and unpacks on streams of its own, beside the matching of the blocks before
-    // (no call on the null stream and no hipFree in here: both wait for the main stream, where a streamed run's matching is queued)
-    const bool streamed = c->st_on;
-    hipStream_t main_stream = c->stream;
-    hipStream_t ctl = streamed ? c->up_stream[0] : c->stream;
-    if (hipMemsetAsync(flag.p, 0, sizeof(uint32_t), ctl) != hipSuccess || hipStreamSynchronize(ctl) != hipSuccess) { cleanup(); c->err = "append_reads: HIP error"; return PGRC_E_DEVICE; }
+        if ((e = pgrc_buf_ensure(c, c->up.stage[k], (size_t)std::min(CHR, std::max<uint64_t>(count, 1)) * rb))) return e;
+    if ((e = pgrc_buf_ensure(c, c->up.flag, sizeof(uint32_t)))) return e;
+    hipStream_t ctl = streamed ? c->up.stream[0].stream : c->stream;
+    if (hipMemsetAsync(c->up.flag.p, 0, sizeof(uint32_t), ctl) != hipSuccess || hipStreamSynchronize(ctl) != hipSuccess) { c->err = "append_reads: HIP error"; return PGRC_E_DEVICE; }
     int rcode = PGRC_OK;
     std::vector<uint8_t> nf, hrows;
     std::vector<uint32_t> local;
     for (uint64_t off = 0; off < count && rcode == PGRC_OK; off += CHR) {
         const uint64_t cnt = std::min(CHR, count - off);
-        const uint64_t first = c->up_next + off;
-        const int turn = (int)(c->up_chunk++ & 1u);
-        hipStream_t up = streamed ? c->up_stream[turn] : c->stream;
-        void *stage = c->up_stage[turn].p;
-        if (hipMemcpyAsync(stage, rows + off * rb, cnt * rb, src_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, up) != hipSuccess) { rcode = PGRC_E_DEVICE; break; }
-        c->stream = up;                                      // (the launchers below queue on c->stream)
-        if (symbols == 0)
-            rcode = pgrc_launch_pack_reads_ascii(c, (const uint8_t *)stage, first, cnt, L, (uint32_t *)c->reads_own.p, c->stride,
-                                                 (uint8_t *)c->nread_flag.p, (uint32_t *)flag.p);
-        else if (symbols == 4)
-            rcode = pgrc_launch_repack_reads_ref(c, (const uint8_t *)stage, first, cnt, L, (uint32_t *)c->reads_own.p, c->stride);
-        else
-            rcode = pgrc_launch_unpack_reads_acgnt(c, (const uint8_t *)stage, first, cnt, L, (uint32_t *)c->reads_own.p, c->stride,
-                                                   (uint8_t *)c->nread_flag.p, (uint32_t *)flag.p);
-        // where the N's of the flagged reads are (flag 1 -> 3 for reads with at most 4 of them: the dual kernel's own)
-        if (rcode == PGRC_OK && symbols != 4) rcode = pgrc_buf_ensure(c, c->nread_npos, std::max<uint64_t>(c->n, 1) * sizeof(uint32_t));   // (first such block: allocated)
-        if (rcode == PGRC_OK && symbols != 4)
-            rcode = pgrc_launch_npos_rows(c, (const uint8_t *)stage, symbols, first, cnt, L, (uint8_t *)c->nread_flag.p, (uint32_t *)c->nread_npos.p);
-        c->stream = main_stream;
+        const uint64_t first = c->up.next + off;
+        const int turn = (int)(c->up.chunk++ & 1u);
+        hipStream_t up = streamed ? c->up.stream[turn].stream : c->stream;
+        void *stage = c->up.stage[turn].p;
+        rcode = stage_chunk(c, up, stage, rows + off * rb, cnt * rb, src_device, first, cnt, symbols);
         // (the staging area is reused by the next chunk: its copy is queued behind this chunk's kernel on the same stream)
         if (symbols != 4) UP_MARK(c, "rows copied, unpack queued");
         if (!(streamed && symbols == 4) && hipStreamSynchronize(up) != hipSuccess) rcode = PGRC_E_DEVICE;
         if (symbols != 4) UP_MARK(c, "unpacked");
-        if (rcode == PGRC_OK && symbols != 4) {               // (an ACGT set cannot hold an N)
-            // reads with 'N' -> side list: keep their ASCII rows (they are a small minority)
-            nf.resize(cnt);
-            if (hipMemcpyAsync(nf.data(), (const uint8_t *)c->nread_flag.p + first, cnt, hipMemcpyDeviceToHost, up) != hipSuccess ||
-                hipStreamSynchronize(up) != hipSuccess) { rcode = PGRC_E_DEVICE; break; }
-            local.clear();
-            hrows.clear();
-            for (uint64_t k = 0; k < cnt; k++)
-                if (nf[k]) {
-                    c->up_nidx.push_back((uint32_t)(first + k));
-                    if (nf[k] == 1) c->up_nmany++;
-                    if (symbols == 0) hrows.insert(hrows.end(), rows + (off + k) * rb, rows + (off + k + 1) * rb);
-                    else local.push_back((uint32_t)k);
-                }
-            const size_t nn = symbols == 0 ? hrows.size() / L : local.size();
-            UP_MARK(c, "N flags on the host, list made");
-            if (nn) {      // their ASCII rows stay in HBM: uploaded (ASCII input) or made there (packed input)
-                DevBuf nrows;
-                if ((e = pgrc_buf_ensure(c, nrows, nn * L))) { rcode = e; break; }
-                UP_MARK(c, "room for the N rows");
-                c->up_nchunks.push_back(nrows);
-                c->up_nchunk_rows.push_back(nn);
-                if (symbols == 0) {
-                    if (hipMemcpyAsync(nrows.p, hrows.data(), nn * L, hipMemcpyHostToDevice, up) != hipSuccess || hipStreamSynchronize(up) != hipSuccess) rcode = PGRC_E_DEVICE;
-                } else {
-                    if ((e = pgrc_buf_ensure(c, lidx, nn * sizeof(uint32_t)))) { rcode = e; break; }
-                    if (hipMemcpyAsync(lidx.p, local.data(), nn * sizeof(uint32_t), hipMemcpyHostToDevice, up) != hipSuccess) { rcode = PGRC_E_DEVICE; break; }
-                    c->stream = up;
-                    rcode = pgrc_launch_nrows_ascii_acgnt(c, (const uint8_t *)stage, (const uint32_t *)lidx.p, nn, L, (uint8_t *)nrows.p);
-                    c->stream = main_stream;
-                    if (hipStreamSynchronize(up) != hipSuccess) rcode = PGRC_E_DEVICE;    // (stage is reused by the next block)
-                    UP_MARK(c, "N rows as ASCII on the device");
-                }
-            }
-        }
+        if (rcode == PGRC_OK && symbols != 4) rcode = list_n_rows(c, up, first, cnt, nf, local);
+        if (rcode == PGRC_OK && symbols != 4) rcode = keep_n_rows(c, up, stage, rows + off * rb, symbols, local, hrows);
         if (rcode == PGRC_OK && streamed) rcode = pgrc_stream_block_arrived(c, first, cnt, symbols != 4, turn);
     }
     uint32_t bad = 0;
-    if (rcode == PGRC_OK && streamed && (hipStreamSynchronize(c->up_stream[0]) != hipSuccess || hipStreamSynchronize(c->up_stream[1]) != hipSuccess)) rcode = PGRC_E_DEVICE;
+    if (rcode == PGRC_OK && streamed && (hipStreamSynchronize(c->up.stream[0].stream) != hipSuccess || hipStreamSynchronize(c->up.stream[1].stream) != hipSuccess)) rcode = PGRC_E_DEVICE;
     if (rcode == PGRC_OK && !streamed && hipStreamSynchronize(c->stream) != hipSuccess) rcode = PGRC_E_DEVICE;
-    if (rcode == PGRC_OK && (hipMemcpyAsync(&bad, flag.p, sizeof bad, hipMemcpyDeviceToHost, ctl) != hipSuccess || hipStreamSynchronize(ctl) != hipSuccess)) rcode = PGRC_E_DEVICE;
-    cleanup();
+    if (rcode == PGRC_OK && (hipMemcpyAsync(&bad, c->up.flag.p, sizeof bad, hipMemcpyDeviceToHost, ctl) != hipSuccess || hipStreamSynchronize(ctl) != hipSuccess)) rcode = PGRC_E_DEVICE;
     if (rcode != PGRC_OK) { if (c->err.empty()) c->err = "append_reads: HIP error"; pgrc_stream_abort(c); return rcode; }
     if (bad) { c->err = symbols == 5 ? "packed reads hold a byte outside the ACGNT code range" : "reads contain a symbol outside ACGNT"; pgrc_stream_abort(c); return PGRC_E_SYMBOL; }
-    c->up_next += count;
+    c->up.next += count;
     return PGRC_OK;
 }
 
@@ -765,41 +747,49 @@ int pgrc_append_rows_device(pgrc_match_ctx *c, const uint8_t *d_packed, uint64_t
     if (c->multi) { c->err = "append_reads: rows on a device go to a single-device context"; return PGRC_E_PARAM; }
     return append_rows(c, d_packed, count, symbols, true);
 }
+void PgrcUpload::reset() {
+    next = 0;
+    chunk = 0;
+    nidx.clear();
+    nmany = 0;
+    for (DevBuf &b : nchunks) pgrc_buf_free(b);
+    nchunks.clear();
+    nchunk_rows.clear();
+}
+void pgrc_upload_close(pgrc_match_ctx *c) {
+    c->up.open = false;
+    c->have_reads = false;
+}
 extern "C" {
 
 int pgrc_match_end_reads(pgrc_match_ctx *c) {
     if (!c) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_end_reads(c);
-    if (!c->up_open || c->up_next != c->n) { c->err = "end_reads: fewer rows appended than announced"; return PGRC_E_STATE; }
+    if (!c->up.open || c->up.next != c->n) { c->err = "end_reads: fewer rows appended than announced"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     int e;
-    c->n_nreads = c->up_nidx.size();
-    c->n_many = c->up_nmany;
-    c->h_nidx = c->up_nidx;
+    c->n_nreads = c->up.nidx.size();
+    c->n_many = c->up.nmany;
+    c->h_nidx = c->up.nidx;
     if (c->n_nreads) {
         const uint32_t L = c->prm.read_len;
-        if ((e = pgrc_buf_ensure(c, c->nread_idx, c->up_nidx.size() * sizeof(uint32_t)))) return e;
+        if ((e = pgrc_buf_ensure(c, c->nread_idx, c->up.nidx.size() * sizeof(uint32_t)))) return e;
         if ((e = pgrc_buf_ensure(c, c->nread_ascii, c->n_nreads * L))) return e;
         // (a streamed run has its matching queued on the main stream: the side list is put together beside it)
-        hipStream_t s = (c->st_on && c->up_stream[0]) ? c->up_stream[0] : c->stream;
-        HIP_TRY(c, hipMemcpyAsync(c->nread_idx.p, c->up_nidx.data(), c->up_nidx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        hipStream_t s = (pgrc_stream_active(c) && c->up.stream[0].stream) ? c->up.stream[0].stream : c->stream;
+        HIP_TRY(c, hipMemcpyAsync(c->nread_idx.p, c->up.nidx.data(), c->up.nidx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         uint64_t at = 0;
-        for (size_t k = 0; k < c->up_nchunks.size(); k++) {
-            HIP_TRY(c, hipMemcpyAsync((uint8_t *)c->nread_ascii.p + at * L, c->up_nchunks[k].p, c->up_nchunk_rows[k] * L, hipMemcpyDeviceToDevice, s));
-            at += c->up_nchunk_rows[k];
+        for (size_t k = 0; k < c->up.nchunks.size(); k++) {
+            HIP_TRY(c, hipMemcpyAsync((uint8_t *)c->nread_ascii.p + at * L, c->up.nchunks[k].p, c->up.nchunk_rows[k] * L, hipMemcpyDeviceToDevice, s));
+            at += c->up.nchunk_rows[k];
         }
         HIP_TRY(c, hipStreamSynchronize(s));
     }
-    // (chunks below the pool's size go back through hipFree, which waits for the device: a streamed run keeps them until its end)
-    if (c->st_on) {
-        for (DevBuf &b : c->up_nchunks) c->st_keep.push_back(b);
-    } else
-    for (DevBuf &b : c->up_nchunks) pgrc_buf_free(b);
-    c->up_nchunks.clear();
-    c->up_nchunk_rows.clear();
-    c->up_nidx.clear();
-    c->up_nidx.shrink_to_fit();
-    c->up_open = false;
+    pgrc_stream_release_bufs(c, c->up.nchunks);    // (a streamed run keeps them until its end)
+    c->up.nchunk_rows.clear();
+    c->up.nidx.clear();
+    c->up.nidx.shrink_to_fit();
+    c->up.open = false;
     c->have_reads = true;
     return PGRC_OK;
 }
@@ -895,19 +885,14 @@ static bool dual_wanted(const pgrc_match_ctx *c, int first, int last) {
 template <typename F>
 static int pgrc_build_both_indexes(pgrc_match_ctx *c, F mark) {
     int e;
-    if ((e = pgrc_launch_revcomp(c, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
+    if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
     c->have_rc = true;
     mark(); // 1
     bool two = !c->opt.builds_in_turn;
-    if (two && !c->build_stream) {
-        hipError_t he = hipStreamCreateWithFlags(&c->build_stream, hipStreamNonBlocking);
-        for (int k = 0; k < 2 && he == hipSuccess; k++) he = hipEventCreateWithFlags(&c->build_ev[k], hipEventDisableTiming);
-        if (he != hipSuccess) { (void)hipGetLastError(); c->build_stream = nullptr; two = false; }
-    }
-    hipStream_t main_stream = c->stream;
+    if (two && c->build.ensure(c, "index build streams")) { (void)hipGetLastError(); two = false; }   // (no second stream: in turn)
     if (two) {
-        HIP_TRY(c, hipEventRecord(c->build_ev[0], main_stream));             // the RC text is ready
-        HIP_TRY(c, hipStreamWaitEvent(c->build_stream, c->build_ev[0], 0));
+        HIP_TRY(c, hipEventRecord(c->build.ev[0], c->stream));               // the RC text is ready
+        HIP_TRY(c, hipStreamWaitEvent(c->build.stream, c->build.ev[0], 0));
     }
     // Both strands' heads go into ONE table of 32-byte slots {forward head, RC head} per bucket number (round 4): the dual
     // kernel's two gathers of a seed then hit one 64-byte line and one translation.  PGRC_HEAD_PAIR=0: a table per strand
@@ -923,15 +908,13 @@ static int pgrc_build_both_indexes(pgrc_match_ctx *c, F mark) {
     // (groups of 1, 2, 4: dual kernel 79.5 -> 64.7 ms; groups of 8 = 256 bytes: 79.6), and the builds' head stores cost
     // nothing extra only as whole 64-byte runs (groups of 1 and 2: index pair 16.2 -> 24.9 ms; groups of 4: 17.0)
     c->pair_gm = pair ? c->opt.head_pair - 1u : 3u;
-    if ((e = pgrc_copmem_build_index(c, 0, pair))) return e;
+    if ((e = pgrc_copmem_build_index(c, c->stream, 0, pair))) return e;
     if (!two) mark(); // 2
     c->build_set ^= 1;
-    if (two) c->stream = c->build_stream;
     // (PGRC_TEST_NO_SECOND_INDEX: tests take the out-of-memory road without exhausting the device)
-    e = c->opt.test_no_second_index ? PGRC_E_ALLOC : pgrc_copmem_build_index(c, 1, pair);
-    c->stream = main_stream;
+    e = c->opt.test_no_second_index ? PGRC_E_ALLOC : pgrc_copmem_build_index(c, two ? c->build.stream : c->stream, 1, pair);
     if (two) {
-        if (hipEventRecord(c->build_ev[1], c->build_stream) != hipSuccess || hipStreamWaitEvent(main_stream, c->build_ev[1], 0) != hipSuccess) {
+        if (hipEventRecord(c->build.ev[1], c->build.stream) != hipSuccess || hipStreamWaitEvent(c->stream, c->build.ev[1], 0) != hipSuccess) {
             c->err = "index build streams";
             return PGRC_E_DEVICE;
         }
@@ -1012,7 +995,7 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
             // their streams; this run's work is ordered behind them
             c->idx_prepared = false;
             mark(); // 1
-            if (c->build_stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->build_ev[1], 0));
+            if (c->build.stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->build.ev[1], 0));
             mark(); // 2
             e = PGRC_OK;
         } else {
@@ -1024,11 +1007,11 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
             screened = false;
             // (the forward index is gone when it was the one that found no room, or when its heads sat in the pair table: once
             //  more, into a table of its own -- if that does not fit either, the run fails with PGRC_E_ALLOC)
-            if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, 0))) return e;
+            if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, c->stream, 0))) return e;
             mark(); // 3
             if ((e = pgrc_copmem_match_pass(c, 0))) return e;
             mark(); // 4
-            if ((e = pgrc_copmem_build_index(c, 1))) return e;
+            if ((e = pgrc_copmem_build_index(c, c->stream, 1))) return e;
             mark(); // 5
             if ((e = pgrc_copmem_match_pass(c, 1))) return e;
             mark(); // 6
@@ -1061,11 +1044,11 @@ static int run_passes(pgrc_match_ctx *c, int first, int last) {
         for (int pass = first; pass <= last; pass++) {
             if (pass == 1) {
                 // PgHelpers::reverseComplementInPlace(pgPtr), ReadsMatchers.cpp:168 -- rebuilt every run like the reference
-                if ((e = pgrc_launch_revcomp(c, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
+                if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
                 c->have_rc = true;
             }
             mark(); // 1 / 4
-            if ((e = pgrc_copmem_build_index(c, pass))) return e;
+            if ((e = pgrc_copmem_build_index(c, c->stream, pass))) return e;
             mark(); // 2 / 5
             if ((e = pgrc_copmem_match_pass(c, pass))) return e;
             mark(); // 3 / 6
@@ -1218,10 +1201,10 @@ int pgrc_match_export_index(pgrc_match_ctx *c, int strand, uint32_t *cumm, uint3
     PGRC_ON_DEVICE(c);
     int e;
     if (strand == 1 && !c->have_rc) {
-        if ((e = pgrc_launch_revcomp(c, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
+        if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
         c->have_rc = true;
     }
-    if (!pgrc_index_of(c, strand) && (e = pgrc_copmem_build_index(c, strand))) return e;
+    if (!pgrc_index_of(c, strand) && (e = pgrc_copmem_build_index(c, c->stream, strand))) return e;
     return pgrc_copmem_export_index(c, strand, cumm, positions, count);
 }
 

@@ -74,7 +74,7 @@ void pgrc_index_drop(pgrc_match_ctx *, PgrcIndexSet &ix) {
 // table goes too, with the table: nothing would keep that table otherwise, and the passes build into a table per set.
 void pgrc_index_retreat(pgrc_match_ctx *c) {
     (void)hipGetLastError();
-    if (c->build_stream) (void)hipStreamSynchronize(c->build_stream);   // (nothing of a half-started build may still be running)
+    if (c->build.stream) (void)hipStreamSynchronize(c->build.stream);   // (nothing of a half-started build may still be running)
     pgrc_index_drop(c, pgrc_build_set(c));
     c->build_set ^= 1;
     PgrcIndexSet &left = pgrc_build_set(c);
@@ -89,7 +89,7 @@ void pgrc_index_retreat(pgrc_match_ctx *c) {
     c->screen_broken = true;
 }
 
-int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand, bool into_pair_table) {
+int pgrc_copmem_build_index(pgrc_match_ctx *c, hipStream_t stream, int strand, bool into_pair_table) {
     PgrcIndexSet &ix = pgrc_build_set(c);
     const uint32_t K = (uint32_t)c->cp.K, k1 = (uint32_t)c->cp.k1;
     const uint64_t hs = c->cp.hash_size;
@@ -108,7 +108,7 @@ int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand, bool into_pair_table)
     ix.ent = nullptr;
     ix.strand = strand;
     if (!npos) {
-        hipLaunchKernelGGL(k_heads_empty, dim3((uint32_t)std::min<uint64_t>((hs + 255) / 256, 65536ull)), dim3(256), 0, c->stream, ix.head_ptr, hs, ix.head_sh);
+        hipLaunchKernelGGL(k_heads_empty, dim3((uint32_t)std::min<uint64_t>((hs + 255) / 256, 65536ull)), dim3(256), 0, stream, ix.head_ptr, hs, ix.head_sh);
         HIP_TRY(c, hipGetLastError());
         if ((e = pgrc_buf_ensure(c, ix.sval[0], 64))) return e;
         ix.ent = (const uint64_t *)ix.sval[0].p;
@@ -124,14 +124,14 @@ int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand, bool into_pair_table)
     //             texts with more than 2^30 sampled positions take (the 8-byte records of "sweep" have no room for them).
     // The match kernels address ent[] with 32-bit indices unless they run their 64-bit-position variant; both front ends
     // stop at 2^32 samples (a text of k1 * 2^32 > 17 G symbols).
-    if (c->opt.index_front == 0 && pgrc_os_applicable(c, (uint32_t)hbits)) return pgrc_os_build_index(c, strand, (uint32_t)hbits);
+    if (c->opt.index_front == 0 && pgrc_os_applicable(c, (uint32_t)hbits)) return pgrc_os_build_index(c, stream, strand, (uint32_t)hbits);
     if (!pgrc_ps_applicable(c, (uint32_t)hbits)) {
         c->err = "index build: texts with 2^32 or more sampled positions are not supported";
         return PGRC_E_PARAM;
     }
     const uint32_t cb = pgrc_ps_partition_bits((uint32_t)hbits);
-    if ((e = pgrc_ps_scatter_front(c, strand, (uint32_t)hbits, cb))) return e;
-    return pgrc_ps_finish(c, (const uint32_t *)ix.skey[1].p, (const uint64_t *)ix.sval[1].p, (uint32_t)hbits, cb, (uint64_t *)ix.sval[0].p);
+    if ((e = pgrc_ps_scatter_front(c, stream, strand, (uint32_t)hbits, cb))) return e;
+    return pgrc_ps_finish(c, stream, (const uint32_t *)ix.skey[1].p, (const uint64_t *)ix.sval[1].p, (uint32_t)hbits, cb, (uint64_t *)ix.sval[0].p);
 }
 
 // ---- canonical export for tests: the reference's (cumm, sampledPositions) from heads + ent ----
@@ -171,7 +171,7 @@ int pgrc_copmem_export_index(pgrc_match_ctx *c, int strand, uint32_t *h_cumm, ui
     hipLaunchKernelGGL(k_export_counts, dim3(sgrid), dim3(256), 0, c->stream, (const ulonglong2 *)ix->head_ptr, ix->head_sh, hs, (uint32_t *)cnt.p);
     // cumm = exclusive scan of the counts (the build's own scan kernels; in place in `cnt`, then copied)
     if ((e = pgrc_buf_ensure(c, temp, pgrc_ps_scan_blocks(hs + 2) * sizeof(uint32_t)))) { cleanup(); return e; }
-    if ((e = pgrc_ps_scan_u32(c, (uint32_t *)cnt.p, hs + 2, (uint32_t *)temp.p))) { cleanup(); return e; }
+    if ((e = pgrc_ps_scan_u32(c, c->stream, (uint32_t *)cnt.p, hs + 2, (uint32_t *)temp.p))) { cleanup(); return e; }
     hipError_t he = hipMemcpyAsync(cumm.p, cnt.p, (hs + 2) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
     uint32_t total = 0;
     if (he == hipSuccess) he = hipMemcpyAsync(&total, (uint32_t *)cumm.p + hs, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
@@ -845,7 +845,7 @@ static void launch_dual(pgrc_match_ctx *c, const DualArgs &a) {
 }
 
 // The dual kernel over the reads without N of a range: it needs a set for either strand, both with their heads in the same
-// kind of table.  The reads with N follow in two ordinary passes (phase 4).
+// kind of table.  The reads with more N's than it takes follow on the byte path (pgrc_copmem_match_nreads).
 int pgrc_copmem_match_dual(pgrc_match_ctx *c, PgrcReadRange range) {
     const uint64_t lo = std::min<uint64_t>(range.lo, c->n), rn = std::min<uint64_t>(c->n - lo, range.n);
     if (rn == 0) return PGRC_OK;
@@ -861,7 +861,7 @@ int pgrc_copmem_match_dual(pgrc_match_ctx *c, PgrcReadRange range) {
     a.reads = c->reads2 + lo;
     a.n = rn;
     a.stride = c->stride;
-    a.nflag = (c->n_nreads || c->up_open) ? (const uint8_t *)c->nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
+    a.nflag = (c->n_nreads || c->up.open) ? (const uint8_t *)c->nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
     // PGRC_NREAD_INLINE=0: every read with an N goes the byte path (A/B runs, tests)
     a.npos = (a.nflag && c->opt.nread_inline && c->nread_npos.p) ? (const uint32_t *)c->nread_npos.p + lo : nullptr;
     a.head[0] = (const ulonglong2 *)fw->head_ptr;
@@ -905,15 +905,14 @@ static void launch_match(pgrc_match_ctx *c, const MatchArgs &a) {
     // persistent grid: what the chip can hold (8 blocks of 4 waves per CU is the register/LDS limit at most)
     const uint64_t want = (a.n + MATCH_TPB - 1) / MATCH_TPB;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)c->num_cus * 8u);
-    const uint32_t dyn_lds = 0u;
     const bool pos64 = c->G + 256 >= (1ull << 32) || c->opt.force_pos64;   // (PGRC_FORCE_POS64: the 64-bit-position kernel on a small text)
     const bool k28 = a.K == 28;                   // the default seed: compile-time hash loop
     // PGRC_MATCH_STAGE=0: every refilling lane loads its own read (A/B knob; staged is 1.8 % faster on C3, same context)
     const bool staged = c->opt.match_stage;
 #define PGRC_LAUNCH_MATCH(KQ_, P64_)                                                                                              \
     do {                                                                                                                          \
-        if (staged) hipLaunchKernelGGL((k_copmem_match_sm<NW, KQ_, P64_, MATCH_STAGE>), dim3(grid), dim3(MATCH_TPB), dyn_lds, c->stream, a); \
-        else hipLaunchKernelGGL((k_copmem_match_sm<NW, KQ_, P64_, 0>), dim3(grid), dim3(MATCH_TPB), dyn_lds, c->stream, a);       \
+        if (staged) hipLaunchKernelGGL((k_copmem_match_sm<NW, KQ_, P64_, MATCH_STAGE>), dim3(grid), dim3(MATCH_TPB), 0, c->stream, a); \
+        else hipLaunchKernelGGL((k_copmem_match_sm<NW, KQ_, P64_, 0>), dim3(grid), dim3(MATCH_TPB), 0, c->stream, a);       \
     } while (0)
     if (pos64) {
         if (k28) PGRC_LAUNCH_MATCH(7, true);
@@ -961,47 +960,31 @@ int pgrc_copmem_match_nreads(pgrc_match_ctx *c, int first, int last, bool only_m
     a.early = c->opt.early_stop ? 1u : 0u;
     a.first = (uint32_t)first;
     a.last = (uint32_t)last;
-    if (!c->side_stream) {   // stream and both events, or nothing
-        hipStream_t st = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        hipError_t he = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        if (he == hipSuccess) he = hipEventCreateWithFlags(&e0, hipEventDisableTiming);
-        if (he == hipSuccess) he = hipEventCreateWithFlags(&e1, hipEventDisableTiming);
-        if (he != hipSuccess) {
-            if (e0) (void)hipEventDestroy(e0);
-            if (st) (void)hipStreamDestroy(st);
-            c->err = std::string("side stream: ") + hipGetErrorString(he);
-            return pgrc_hip_code(he);
-        }
-        c->side_stream = st;
-        c->side_ev[0] = e0;
-        c->side_ev[1] = e1;
-    }
+    if (int se = c->side.ensure(c, "side stream")) return se;
     if (after) {                                                        // (a streamed run: not behind the blocks still queued)
-        HIP_TRY(c, hipStreamWaitEvent(c->side_stream, after, 0));
+        HIP_TRY(c, hipStreamWaitEvent(c->side.stream, after, 0));
     } else {
-        HIP_TRY(c, hipEventRecord(c->side_ev[0], c->stream));           // the index (and the previous pass) are complete
-        HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->side_ev[0], 0));
+        HIP_TRY(c, hipEventRecord(c->side.ev[0], c->stream));           // the index (and the previous pass) are complete
+        HIP_TRY(c, hipStreamWaitEvent(c->side.stream, c->side.ev[0], 0));
     }
     const uint64_t tiles = (c->n_nreads + NREAD_TPB - 1) / NREAD_TPB;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)c->num_cus * 64u);   // whatever fits
     const uint32_t lds = 2u * ((uint32_t)c->nw + 1u) * NREAD_TPB * (uint32_t)sizeof(uint32_t);
-    hipLaunchKernelGGL(k_copmem_match_n, dim3(grid), dim3(NREAD_TPB), lds, c->side_stream, a);
+    hipLaunchKernelGGL(k_copmem_match_n, dim3(grid), dim3(NREAD_TPB), lds, c->side.stream, a);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->side_ev[1], c->side_stream));
+    HIP_TRY(c, hipEventRecord(c->side.ev[1], c->side.stream));
     return PGRC_OK;
 }
 
 // the main stream goes on when the reads with N are done
 int pgrc_copmem_join_nreads(pgrc_match_ctx *c) {
-    if (c->n_nreads && c->side_stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->side_ev[1], 0));
+    if (c->n_nreads && c->side.stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->side.ev[1], 0));
     return PGRC_OK;
 }
 
 int pgrc_copmem_match_pass(pgrc_match_ctx *c, int strand) { return pgrc_copmem_match_phase(c, strand, 0); }
 
-// phase: 0 = a plain pass; 1 / 2 = the screen and the flag-honouring forward pass of the screened schedule (kernel comment);
-// 4 = after the dual kernel: only the reads with N (the byte-path kernel), in the strand order of the two passes
+// phase: 0 = a plain pass; 1 / 2 = the screen and the flag-honouring forward pass of the screened schedule (kernel comment)
 int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase, PgrcReadRange range) {
     const uint64_t lo = std::min<uint64_t>(range.lo, c->n), rn = std::min<uint64_t>(c->n - lo, range.n);
     if (rn == 0) return PGRC_OK;
@@ -1013,7 +996,7 @@ int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase, PgrcReadRa
     a.reads = c->reads2 + lo;
     a.n = rn;
     a.stride = c->stride;
-    a.nflag = (c->n_nreads || c->up_open) ? (const uint8_t *)c->nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
+    a.nflag = (c->n_nreads || c->up.open) ? (const uint8_t *)c->nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
     a.head = (const ulonglong2 *)ix->head_ptr;
     a.hsh = ix->head_sh;
     a.ent = ix->ent;
@@ -1046,7 +1029,6 @@ int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase, PgrcReadRa
         const int ne = pgrc_copmem_match_nreads(c, strand, strand, false);
         if (ne) return ne;
     }
-    if (phase != 4)                  // (phase 4: the dual kernel has done every read without N)
     switch (c->nw) {
 #define CASE_NW(N) case N: launch_match<N>(c, a); break;
         CASE_NW(2) CASE_NW(3) CASE_NW(4) CASE_NW(5) CASE_NW(6) CASE_NW(7) CASE_NW(8) CASE_NW(9)

@@ -36,6 +36,8 @@ struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
 };
+// A struct names its device buffers once, in a function that returns this list: whoever frees them, or needs all of them, walks it
+typedef std::vector<DevBuf *> DevBufList;
 
 // What every context is on the device side: its device, the stream its work is ordered on and the text of its last
 // error.  The shared services (the allocators below, pack.hip, radix.hip, pgrc_ps_scan_u32) need nothing else.
@@ -43,6 +45,40 @@ struct PgrcDev {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
+};
+
+// HIP failure -> ABI error code: out of memory is PGRC_E_ALLOC, a missing / invalid device PGRC_E_NO_DEVICE, anything
+// else (launch failure, invalid value, ...) PGRC_E_DEVICE
+static inline int pgrc_hip_code(hipError_t e) {
+    if (e == hipErrorOutOfMemory) return PGRC_E_ALLOC;
+    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return PGRC_E_NO_DEVICE;
+    return PGRC_E_DEVICE;
+}
+
+// A stream beside the context's own, with the NEV events (one or two) that order it against the others: made on first use, all
+// of it or nothing, and given back with the context.  Work is queued on it by passing `stream` to whoever launches: nothing
+// ever stands in for a context's own stream.
+template <int NEV = 2>
+struct PgrcAuxStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[NEV]{};
+    int ensure(PgrcDev *c, const char *what) {      // on failure: "<what>: <HIP's text>" in c->err, and nothing made
+        if (stream) return PGRC_OK;
+        hipError_t he = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        for (int k = 0; k < NEV && he == hipSuccess; k++) he = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
+        if (he == hipSuccess) return PGRC_OK;
+        release();
+        c->err = std::string(what) + ": " + hipGetErrorString(he);
+        return pgrc_hip_code(he);
+    }
+    void release() {
+        if (stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+        for (hipEvent_t &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
 };
 
 struct pgrc_multi;   // multi.hip
@@ -102,6 +138,57 @@ struct PgrcOptions {
 PgrcOptions pgrc_options_from_env();
 bool pgrc_pack_ascii_host(const uint8_t *src, uint64_t count, uint32_t *dst, uint32_t threads);   // api.hip: ASCII ACGT -> 2-bit words, false = a symbol outside ACGT
 
+// The chunked upload of a read set (pgrc_match_begin_reads / _append_ / _end_, api.hip): what one begin .. end sequence
+// collects, and the staging it reuses from one sequence to the next.
+struct PgrcUpload {
+    bool open = false;                          // between begin_reads and end_reads
+    uint64_t next = 0;                          // rows appended so far
+    uint64_t chunk = 0;                         // staging chunks so far: chunk k goes through stage[k & 1] and, in a streamed run, stream[k & 1]
+    std::vector<uint32_t> nidx;                 // reads with N seen so far (ascending)
+    uint64_t nmany = 0;                         // ... of them with more than 4 N's
+    std::vector<DevBuf> nchunks;                // their ASCII rows, one device buffer per appended block that had some
+    std::vector<uint64_t> nchunk_rows;
+    DevBuf flag, lidx;                          // bad-symbol flag, positions of a block's N rows (kept: freeing a small buffer goes to
+                                                // hipFree, which waits for the whole device -- i.e. for the matching of a streamed run)
+    DevBuf stage[2];                            // staging areas (grow-only: no allocation per call), used in turn
+    // stream[0]: begin_reads clears the N flags beside index builds queued on the main stream.  A streamed run uploads and unpacks
+    // beside the matching, on both in turn: the copy of chunk k+1 must not queue behind the unpacking of chunk k, which waits for a
+    // free CU while the persistent match kernel of chunk k-1 runs.  ev[0] of each: "this chunk is unpacked" (stream.hip)
+    PgrcAuxStream<1> stream[2];
+    DevBufList bufs() { return {&flag, &lidx, &stage[0], &stage[1]}; }
+    void reset();                               // a new sequence: nothing appended, no reads with N (api.hip)
+};
+
+// A streamed run (stream.hip, the only file that touches the members): blocks of reads matched as they arrive, their results
+// downloaded by a worker thread.  Others ask pgrc_stream_active and call the functions declared under "stream.hip" below.
+struct PgrcStreamRun {
+    struct StreamBlock { uint64_t lo, cnt; hipEvent_t done; };
+    bool on = false, dual = false;
+    uint64_t *pos = nullptr;            // the caller's result arrays: a block's results are copied there as soon as they exist
+    uint8_t *rc = nullptr, *mism = nullptr;
+    std::vector<DevBuf> keep;           // small device buffers to give back at the run's end (pgrc_stream_release_bufs)
+    hipEvent_t ready = nullptr;         // indexes built and per-read state initialised (what the N passes wait for)
+    std::thread worker;                 // downloads finished blocks while the caller uploads the next ones
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<StreamBlock> q;
+    bool quit = false;
+    int err = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> nblocks;   // blocks holding reads with N: downloaded again at the end
+    double t0 = 0;                      // host clock at stream_begin (ms_total, PGRC_STREAM_TIMING)
+    hipEvent_t tbase = nullptr;         // PGRC_STREAM_TIMING: device times of the blocks' match launches
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+};
+
+// The read-side seed index of modes d / i / e (seedidx.hip)
+struct PgrcSeedBufs {
+    DevBuf keys, vals, tab, hits, tmp, sort, seg, hv, hvu;
+    DevBuf filter;          // one bit per slice of the key space
+    DevBuf nmask;           // N masks of the reads with N
+    DevBuf best, rows;      // the atomic-minimum reduction: one key per read, the batch's reads row by row (seedidx.hip 3c)
+    DevBufList bufs() { return {&keys, &filter, &vals, &tab, &hits, &tmp, &sort, &seg, &hv, &hvu, &nmask, &best, &rows}; }
+};
+
 struct pgrc_match_ctx : PgrcDev {
     PgrcOptions opt;                    // read from the environment by pgrc_match_create (see above)
 
@@ -113,8 +200,8 @@ struct pgrc_match_ctx : PgrcDev {
 
     pgrc_match_params prm{};
     int num_cus = 256;
-    hipStream_t side_stream = nullptr;  // the kernel for reads with N runs beside the main match kernel (created on first use)
-    hipEvent_t side_ev[2]{};
+    PgrcAuxStream<2> side;              // the kernel for reads with N runs beside the main match kernel: ev[0] "the main stream is
+                                        // ready for it", ev[1] "it is done"
 
     // pseudogenome
     uint64_t G = 0;
@@ -138,13 +225,7 @@ struct pgrc_match_ctx : PgrcDev {
     uint64_t n_many = 0;    // reads flagged 1: more N's than the dual kernel takes
     std::vector<uint32_t> h_nidx; // host copy of nread_idx (ascending): modes d/i/e cut it per batch of reads
 
-    // chunked upload state (pgrc_match_begin_reads / _append_ / _end_)
-    bool up_open = false;
-    uint64_t up_next = 0;
-    std::vector<uint32_t> up_nidx;                  // reads with N seen so far (ascending)
-    uint64_t up_nmany = 0;                          // ... of them with more than 4 N's
-    std::vector<DevBuf> up_nchunks;                 // their ASCII rows, one device buffer per appended block that had some
-    std::vector<uint64_t> up_nchunk_rows;
+    PgrcUpload up;          // chunked upload (pgrc_match_begin_reads / _append_ / _end_)
 
     // results
     DevBuf d_pos, d_rc, d_mism, d_hist, d_counters;
@@ -169,39 +250,14 @@ struct pgrc_match_ctx : PgrcDev {
     // per read the flag / position the screen found (screened schedule and dual kernel)
     DevBuf d_scr_pos, d_scr_flag;
     bool screen_broken = false;         // no room for the second set: the passes run as the reference orders them
-    hipStream_t build_stream = nullptr; // the RC index is built beside the forward one (screened schedule)
-    hipEvent_t build_ev[2]{};
+    PgrcAuxStream<2> build;             // the RC index is built beside the forward one: ev[0] "the RC text is ready", ev[1] "the
+                                        // RC index is built" (pgrc_build_both_indexes, api.hip)
 
     // pipelined hand-over (stream.hip): both indexes built ahead of the run; blocks of reads matched as they arrive
     bool idx_prepared = false;          // pgrc_match_prepare_index built (or is building) both strands' indexes of the current text
-    struct StreamBlock { uint64_t lo, cnt; hipEvent_t done; };
-    bool st_on = false, st_dual = false;
-    uint64_t *st_pos = nullptr;         // the caller's result arrays: a block's results are copied there as soon as they exist
-    uint8_t *st_rc = nullptr, *st_mism = nullptr;
-    DevBuf up_flag, up_lidx;            // append_reads_*: bad-symbol flag, positions of a block's N rows (kept: freeing a small buffer
-                                        // goes to hipFree, which waits for the whole device -- i.e. for the matching of a streamed run)
-    std::vector<DevBuf> st_keep;        // streamed run: small device buffers to give back at its end (see end_reads)
-    hipEvent_t st_ready = nullptr;      // streamed run: indexes built and per-read state initialised (what the N passes wait for)
-    DevBuf up_stage[2];                 // staging areas of append_reads_* (grow-only: no allocation per call), used in turn
-    hipStream_t up_stream[2] = {nullptr, nullptr};   // a streamed run uploads and unpacks beside the matching, on two streams in
-    hipEvent_t up_ev[2] = {nullptr, nullptr};        // turn: the copy of chunk k+1 must not queue behind the unpacking of chunk k,
-    uint64_t up_chunk = 0;                           // which waits for a free CU while the persistent match kernel of chunk k-1 runs
-    std::thread st_worker;              // downloads finished blocks while the caller uploads the next ones
-    std::mutex st_mu;
-    std::condition_variable st_cv;
-    std::deque<StreamBlock> st_q;
-    bool st_quit = false;
-    int st_err = 0;
-    std::vector<std::pair<uint64_t, uint64_t>> st_nblocks;   // blocks holding reads with N: downloaded again at the end
-    double st_t0 = 0;
-    hipEvent_t st_tbase = nullptr;                           // PGRC_STREAM_TIMING: device times of the blocks' match launches
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> st_tev;
+    PgrcStreamRun st;
 
-    // read-side seed index (modes d / i / e)
-    DevBuf s_keys, s_vals, s_tab, s_hits, s_tmp, s_sort, s_seg, s_hv, s_hvu;
-    DevBuf s_filter;        // modes d/i/e: one bit per slice of the key space (seedidx.hip)
-    DevBuf s_nmask;                             // N masks of the reads with N (modes d/i/e)
-    DevBuf s_best, s_rows;                      // the atomic-minimum reduction: one key per read, the batch's reads row by row (seedidx.hip 3c)
+    PgrcSeedBufs seed;      // modes d / i / e
 
     // profiling
     bool profiling = false;
@@ -209,14 +265,6 @@ struct pgrc_match_ctx : PgrcDev {
     hipEvent_t ev[16]{};
     bool have_events = false;
 };
-
-// HIP failure -> ABI error code: out of memory is PGRC_E_ALLOC, a missing / invalid device PGRC_E_NO_DEVICE, anything
-// else (launch failure, invalid value, ...) PGRC_E_DEVICE
-static inline int pgrc_hip_code(hipError_t e) {
-    if (e == hipErrorOutOfMemory) return PGRC_E_ALLOC;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return PGRC_E_NO_DEVICE;
-    return PGRC_E_DEVICE;
-}
 
 #define HIP_TRY(ctx, expr)                                                                   \
     do {                                                                                     \
@@ -262,9 +310,7 @@ static void dec_free(DevBuf &b) {
     b.bytes = 0;
 }
 
-// A context names its unpooled buffers once, in a function that returns this list: its destroy function frees the list, and
-// whatever else needs all of them walks it
-typedef std::vector<DevBuf *> DevBufList;
+// the unpooled buffers of a context (its list, above), given back by its destroy function
 static void dec_free_all(const DevBufList &bufs) {
     for (DevBuf *b : bufs) dec_free(*b);
 }
@@ -328,20 +374,20 @@ struct PgrcShardView { pgrc_match_ctx *ctx; uint64_t lo, hi; };     // one shard
 std::vector<PgrcShardView> pgrc_multi_shards(pgrc_match_ctx *f);
 void pgrc_export_drop_view(pgrc_match_ctx *front);   // export.hip: forget the gathered view (text, reads or results change)
 
-// pack.hip
-int pgrc_launch_pack_ascii(PgrcDev *c, const uint8_t *d_ascii, uint64_t count, uint32_t *d_words,
+// pack.hip: each queues its kernel on `stream` (c: the error text)
+int pgrc_launch_pack_ascii(PgrcDev *c, hipStream_t stream, const uint8_t *d_ascii, uint64_t count, uint32_t *d_words,
                            uint32_t *d_errflag);
-int pgrc_launch_revcomp(PgrcDev *c, const uint32_t *d_fw, uint32_t *d_rc, uint64_t G);
-int pgrc_launch_pack_reads_ascii(PgrcDev *c, const uint8_t *d_ascii, uint64_t first, uint64_t count,
+int pgrc_launch_revcomp(PgrcDev *c, hipStream_t stream, const uint32_t *d_fw, uint32_t *d_rc, uint64_t G);
+int pgrc_launch_pack_reads_ascii(PgrcDev *c, hipStream_t stream, const uint8_t *d_ascii, uint64_t first, uint64_t count,
                                  uint32_t L, uint32_t *d_words, uint64_t stride, uint8_t *d_nflag,
                                  uint32_t *d_errflag);
-int pgrc_launch_repack_reads_ref(PgrcDev *c, const uint8_t *d_packed, uint64_t first, uint64_t count,
+int pgrc_launch_repack_reads_ref(PgrcDev *c, hipStream_t stream, const uint8_t *d_packed, uint64_t first, uint64_t count,
                                  uint32_t L, uint32_t *d_words, uint64_t stride);
-int pgrc_launch_unpack_reads_acgnt(PgrcDev *c, const uint8_t *d_packed, uint64_t first, uint64_t count,
+int pgrc_launch_unpack_reads_acgnt(PgrcDev *c, hipStream_t stream, const uint8_t *d_packed, uint64_t first, uint64_t count,
                                    uint32_t L, uint32_t *d_words, uint64_t stride, uint8_t *d_nflag, uint32_t *d_errflag);
-int pgrc_launch_npos_rows(PgrcDev *c, const uint8_t *d_rows, int symbols, uint64_t first, uint64_t count, uint32_t L,
+int pgrc_launch_npos_rows(PgrcDev *c, hipStream_t stream, const uint8_t *d_rows, int symbols, uint64_t first, uint64_t count, uint32_t L,
                           uint8_t *d_nflag, uint32_t *d_npos);
-int pgrc_launch_nrows_ascii_acgnt(PgrcDev *c, const uint8_t *d_packed, const uint32_t *d_local_idx, uint64_t count,
+int pgrc_launch_nrows_ascii_acgnt(PgrcDev *c, hipStream_t stream, const uint8_t *d_packed, const uint32_t *d_local_idx, uint64_t count,
                                   uint32_t L, uint8_t *d_ascii);
 
 // mempack.hip: an ASCII text in HBM (any byte alignment) -> words_out 2-bit words (zero behind the text), the N map (or null)
@@ -358,25 +404,35 @@ bool pgrc_index_pair_ready(pgrc_match_ctx *c);                 // a set for eith
 void pgrc_index_drop(pgrc_match_ctx *c, PgrcIndexSet &ix);     // frees the set's buffers; it describes nothing afterwards
 void pgrc_index_retreat(pgrc_match_ctx *c);                    // no room for the second set: see its definition
 // into_pair_table: the heads go into the strand's half of the pair table (the builds of a run that keeps both indexes)
-int pgrc_copmem_build_index(pgrc_match_ctx *c, int strand, bool into_pair_table = false);
+// The build path queues on the stream it is given (the context's own, or its build stream for the second of two builds at once)
+int pgrc_copmem_build_index(pgrc_match_ctx *c, hipStream_t stream, int strand, bool into_pair_table = false);
 // idxsort.hip: the partition build of the same index (hand-written scatter passes, in-LDS finish of a partition)
 uint32_t pgrc_ps_partition_bits(uint32_t hbits);
 bool pgrc_ps_applicable(const pgrc_match_ctx *c, uint32_t hbits);
-int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_t cb);
-int pgrc_ps_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uint64_t *d_vals, uint32_t hbits, uint32_t cb, uint64_t *d_ent);
-int pgrc_ps_finish_packed(pgrc_match_ctx *c, const uint64_t *d_recs, const uint32_t *d_pstart, uint32_t *d_slow, uint32_t np, uint32_t cb,
+int pgrc_ps_scatter_front(pgrc_match_ctx *c, hipStream_t stream, int strand, uint32_t hbits, uint32_t cb);
+int pgrc_ps_finish(pgrc_match_ctx *c, hipStream_t stream, const uint32_t *d_keys, const uint64_t *d_vals, uint32_t hbits, uint32_t cb, uint64_t *d_ent);
+int pgrc_ps_finish_packed(pgrc_match_ctx *c, hipStream_t stream, const uint64_t *d_recs, const uint32_t *d_pstart, uint32_t *d_slow, uint32_t np, uint32_t cb,
                           uint32_t rec_sh, uint64_t *d_ent);
 // the shared scan (scanops.h) in place over u32 counts, exclusive; d_fold: pgrc_ps_scan_blocks(n) words of scratch
 uint64_t pgrc_ps_scan_blocks(uint64_t n);
-int pgrc_ps_scan_u32(PgrcDev *c, uint32_t *d_io, uint64_t n, uint32_t *d_fold);
+int pgrc_ps_scan_u32(PgrcDev *c, hipStream_t stream, uint32_t *d_io, uint64_t n, uint32_t *d_fold);
 // idxsweep.hip: the default front end (one-sweep scatter passes that hash the text themselves, 8-byte records)
 bool pgrc_os_applicable(const pgrc_match_ctx *c, uint32_t hbits);
-int pgrc_os_build_index(pgrc_match_ctx *c, int strand, uint32_t hbits);
+int pgrc_os_build_index(pgrc_match_ctx *c, hipStream_t stream, int strand, uint32_t hbits);
 int pgrc_copmem_match_pass(pgrc_match_ctx *c, int strand);
-// stream.hip: a block of reads just arrived on the device (append_reads_*): match it now if streaming is on
+// stream.hip: what the rest of the matcher sees of a streamed run
+bool pgrc_stream_active(const pgrc_match_ctx *c);
+// a block of reads just arrived on the device (append_reads_*, unpacking queued on up.stream[turn]): match it now if streaming is on
 int pgrc_stream_block_arrived(pgrc_match_ctx *c, uint64_t lo, uint64_t cnt, bool may_hold_n, int turn);
 void pgrc_stream_abort(pgrc_match_ctx *c);
+void pgrc_stream_release(pgrc_match_ctx *c);   // ... and its events given back (pgrc_match_destroy)
+// gives small device buffers back and empties the list: at once, or -- they go to hipFree, which waits for the whole device, i.e. for
+// the matching -- at the end of the streamed run that is on
+void pgrc_stream_release_bufs(pgrc_match_ctx *c, std::vector<DevBuf> &bufs);
+// PGRC_STREAM_TIMING: a milestone of the streamed run that is on, on stderr with the host time since stream_begin
+void pgrc_stream_mark(pgrc_match_ctx *c, const char *what);
 // api.hip
+void pgrc_upload_close(pgrc_match_ctx *c);   // a begin .. end sequence that failed does not stay open: no reads until the next begin_reads
 int pgrc_prepare_both_indexes(pgrc_match_ctx *c);
 bool pgrc_dual_applies(const pgrc_match_ctx *c);
 int pgrc_fetch_schedule_counters(pgrc_match_ctx *c, bool dual);   // the dual kernel's (or the screen's) device counters -> c->ctr

@@ -437,7 +437,7 @@ static int divide_resident(pgrc_divider *d, uint64_t n, pgrc_divided_reads *out)
                        (uint32_t *)d->d_cnt[1].p, (uint32_t *)d->d_cnt[2].p, (uint32_t *)d->d_err.p);
     HIP_TRY(d, hipGetLastError());
     for (int k = 0; k < 3; k++)
-        if ((e = pgrc_ps_scan_u32(c, (uint32_t *)d->d_cnt[k].p, n + 1, (uint32_t *)d->d_bsum.p))) return e;
+        if ((e = pgrc_ps_scan_u32(c, c->stream, (uint32_t *)d->d_cnt[k].p, n + 1, (uint32_t *)d->d_bsum.p))) return e;
     uint32_t cnt[3] = {0, 0, 0}, bad = 0;
     for (int k = 0; k < 3; k++) HIP_TRY(d, hipMemcpyAsync(&cnt[k], (const uint32_t *)d->d_cnt[k].p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(d, hipMemcpyAsync(&bad, d->d_err.p, sizeof bad, hipMemcpyDeviceToHost, s));
@@ -579,7 +579,7 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
         HIP_TRY(d, hipMemsetAsync((uint8_t *)d->d_text[f].p + len[f], 0, 32, s));
         hipLaunchKernelGGL(k_fq_count, dim3((uint32_t)((n16 + 1 + 255) / 256)), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, len[f], n16,
                            (uint32_t *)d->d_nl[f].p);
-        if ((e = pgrc_ps_scan_u32(c, (uint32_t *)d->d_nl[f].p, n16 + 1, (uint32_t *)d->d_bsum.p))) return e;
+        if ((e = pgrc_ps_scan_u32(c, c->stream, (uint32_t *)d->d_nl[f].p, n16 + 1, (uint32_t *)d->d_bsum.p))) return e;
         uint32_t nl = 0;
         uint8_t last = '\n';
         HIP_TRY(d, hipMemcpyAsync(&nl, (const uint32_t *)d->d_nl[f].p + n16, sizeof nl, hipMemcpyDeviceToHost, s));

@@ -45,8 +45,8 @@ struct PsPlan {
 uint64_t pgrc_ps_scan_blocks(uint64_t n) { return sco_scratch_elems(n); }
 
 // in place: counts -> exclusive prefix sums (d_fold: pgrc_ps_scan_blocks(n) words of scratch)
-int pgrc_ps_scan_u32(PgrcDev *c, uint32_t *d_io, uint64_t n, uint32_t *d_fold) {
-    HIP_TRY(c, sco_scan<false>(c->stream, (const uint32_t *)d_io, d_io, n, ScoIdentity{}, ScoPlus{}, 0u, d_fold));
+int pgrc_ps_scan_u32(PgrcDev *c, hipStream_t stream, uint32_t *d_io, uint64_t n, uint32_t *d_fold) {
+    HIP_TRY(c, sco_scan<false>(stream, (const uint32_t *)d_io, d_io, n, ScoIdentity{}, ScoPlus{}, 0u, d_fold));
     return PGRC_OK;
 }
 
@@ -610,7 +610,7 @@ bool pgrc_ps_applicable(const pgrc_match_ctx *c, uint32_t hbits) {
 
 // The hand-written front end: records straight from the text, two stable scatter passes over the bucket bits
 // [cb, hbits).  Output in the build set's skey[1] / sval[1] (sorted by partition, position order inside); its sval[0] is free.
-int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_t cb) {
+int pgrc_ps_scatter_front(pgrc_match_ctx *c, hipStream_t stream, int strand, uint32_t hbits, uint32_t cb) {
     PgrcIndexSet &ix = pgrc_build_set(c);
     const uint32_t K = (uint32_t)c->cp.K, k1 = (uint32_t)c->cp.k1;
     const uint64_t hs = c->cp.hash_size, n = c->npos;
@@ -640,13 +640,13 @@ int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_
     const uint32_t grid = (uint32_t)pl.ntiles;
     const uint32_t sh1 = cb, sh2 = cb + pl.b1;
     // pass 1: text -> A; pass 2: A -> B
-    hipLaunchKernelGGL(k_ps_hist_gen, dim3(grid), dim3(PS_TPB), 0, c->stream, g, sh1, (1u << pl.b1) - 1u, pl.ntiles, cnt);
-    if ((e = pgrc_ps_scan_u32(c, cnt, ((uint64_t)1 << pl.b1) * pl.ntiles, bsum))) return e;
-    hipLaunchKernelGGL(k_ps_scatter_gen, dim3(grid), dim3(PS_TPB), 0, c->stream, g, sh1, pl.b1, pl.ntiles, (const uint32_t *)cnt, kA, vA);
+    hipLaunchKernelGGL(k_ps_hist_gen, dim3(grid), dim3(PS_TPB), 0, stream, g, sh1, (1u << pl.b1) - 1u, pl.ntiles, cnt);
+    if ((e = pgrc_ps_scan_u32(c, stream, cnt, ((uint64_t)1 << pl.b1) * pl.ntiles, bsum))) return e;
+    hipLaunchKernelGGL(k_ps_scatter_gen, dim3(grid), dim3(PS_TPB), 0, stream, g, sh1, pl.b1, pl.ntiles, (const uint32_t *)cnt, kA, vA);
     HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(k_ps_hist_keys, dim3(grid), dim3(PS_TPB), 0, c->stream, (const uint32_t *)kA, n, sh2, (1u << pl.b2) - 1u, pl.ntiles, cnt);
-    if ((e = pgrc_ps_scan_u32(c, cnt, ncnt, bsum))) return e;
-    hipLaunchKernelGGL(k_ps_scatter_keys, dim3(grid), dim3(PS_TPB), 0, c->stream, (const uint32_t *)kA, (const uint64_t *)vA, n, sh2, pl.b2,
+    hipLaunchKernelGGL(k_ps_hist_keys, dim3(grid), dim3(PS_TPB), 0, stream, (const uint32_t *)kA, n, sh2, (1u << pl.b2) - 1u, pl.ntiles, cnt);
+    if ((e = pgrc_ps_scan_u32(c, stream, cnt, ncnt, bsum))) return e;
+    hipLaunchKernelGGL(k_ps_scatter_keys, dim3(grid), dim3(PS_TPB), 0, stream, (const uint32_t *)kA, (const uint64_t *)vA, n, sh2, pl.b2,
                        pl.ntiles, (const uint32_t *)cnt, kB, vB);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
@@ -655,7 +655,7 @@ int pgrc_ps_scatter_front(pgrc_match_ctx *c, int strand, uint32_t hbits, uint32_
 // The finish of every partition.  pst2[0 .. np] = partition starts (device); slow = np flags + np + 1 words for the list
 // of flagged partitions (all zero).  packed_sh != 0: d_vals holds the 64-bit packed records of idxsweep.hip (d_keys
 // unused), packed_sh = bits of (t, fingerprint) in a record.
-static int ps_launch_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uint64_t *d_vals, const uint32_t *pst2, uint32_t *slow, uint32_t np,
+static int ps_launch_finish(pgrc_match_ctx *c, hipStream_t stream, const uint32_t *d_keys, const uint64_t *d_vals, const uint32_t *pst2, uint32_t *slow, uint32_t np,
                             uint32_t cb, uint64_t *d_ent, uint32_t packed_sh) {
     PgrcIndexSet &ix = pgrc_build_set(c);
     const uint64_t n = c->npos;
@@ -673,8 +673,8 @@ static int ps_launch_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uin
     // (the fast kernel takes a partition's 2^cb buckets in one round of at most 8192: the stable front end's partitions of
     //  tables beyond 2^29 buckets are larger and all go to the general kernel)
     if (c->opt.index_finish_general || cb > 13u) {
-        if (packed) hipLaunchKernelGGL(k_ps_finish<true>, dim3(ggrid), dim3(PF_TPB), 0, c->stream, d_keys, d_vals, pst2, cb, d_ent, head, hsh, (const uint32_t *)nullptr, (const uint32_t *)nullptr, np, fmt);
-        else hipLaunchKernelGGL(k_ps_finish<false>, dim3(ggrid), dim3(PF_TPB), 0, c->stream, d_keys, d_vals, pst2, cb, d_ent, head, hsh, (const uint32_t *)nullptr, (const uint32_t *)nullptr, np, fmt);
+        if (packed) hipLaunchKernelGGL(k_ps_finish<true>, dim3(ggrid), dim3(PF_TPB), 0, stream, d_keys, d_vals, pst2, cb, d_ent, head, hsh, (const uint32_t *)nullptr, (const uint32_t *)nullptr, np, fmt);
+        else hipLaunchKernelGGL(k_ps_finish<false>, dim3(ggrid), dim3(PF_TPB), 0, stream, d_keys, d_vals, pst2, cb, d_ent, head, hsh, (const uint32_t *)nullptr, (const uint32_t *)nullptr, np, fmt);
     } else {
         // registers per thread sized for the mean partition (uniform hash values); whatever is larger is flagged
         const uint64_t need = n / np + n / np / 4 + 512;
@@ -683,7 +683,7 @@ static int ps_launch_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uin
         // rounds.  Measured at C3 (index build per strand, tools/ab_finish_cfg.sh in the round-2 history): 512 x 16: 15.1 ms,
         // 256 x 32: 16.0, 256 x 32 with 2048-bucket rounds: 16.8, 512 x 16 with 2048-bucket rounds: 16.4, 1024 x 8: 13.5.
 #define PFF_LAUNCH(E, TPB, SB, CAP, PK)                                                                                   \
-        hipLaunchKernelGGL((k_ps_finish_fast<E, TPB, SB, CAP, PK>), dim3(fgrid), dim3(TPB), 0, c->stream, d_keys, d_vals,  \
+        hipLaunchKernelGGL((k_ps_finish_fast<E, TPB, SB, CAP, PK>), dim3(fgrid), dim3(TPB), 0, stream, d_keys, d_vals,  \
                            pst2, cb, np, d_ent, head, hsh, todo, todo_count, fmt)
         // (one round of 2^cb <= 8192 buckets; staging area for 6144 entries -- the mean partition holds 0.7 * 8192 -- resp.
         //  8191 where partitions are larger: tables beyond 2^29 buckets)
@@ -695,8 +695,8 @@ static int ps_launch_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uin
             else PFF_LAUNCH(16, 1024, 13, 8191, false);
         }
 #undef PFF_LAUNCH
-        if (packed) hipLaunchKernelGGL(k_ps_finish<true>, dim3(ggrid), dim3(PF_TPB), 0, c->stream, d_keys, d_vals, pst2, cb, d_ent, head, hsh, (const uint32_t *)todo, (const uint32_t *)todo_count, np, fmt);
-        else hipLaunchKernelGGL(k_ps_finish<false>, dim3(ggrid), dim3(PF_TPB), 0, c->stream, d_keys, d_vals, pst2, cb, d_ent, head, hsh, (const uint32_t *)todo, (const uint32_t *)todo_count, np, fmt);
+        if (packed) hipLaunchKernelGGL(k_ps_finish<true>, dim3(ggrid), dim3(PF_TPB), 0, stream, d_keys, d_vals, pst2, cb, d_ent, head, hsh, (const uint32_t *)todo, (const uint32_t *)todo_count, np, fmt);
+        else hipLaunchKernelGGL(k_ps_finish<false>, dim3(ggrid), dim3(PF_TPB), 0, stream, d_keys, d_vals, pst2, cb, d_ent, head, hsh, (const uint32_t *)todo, (const uint32_t *)todo_count, np, fmt);
     }
     HIP_TRY(c, hipGetLastError());
     ix.ent = d_ent;
@@ -704,23 +704,23 @@ static int ps_launch_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uin
 }
 
 // records sorted by their bucket bits [cb, hbits) -> ent[] (d_ent) and all bucket heads
-int pgrc_ps_finish(pgrc_match_ctx *c, const uint32_t *d_keys, const uint64_t *d_vals, uint32_t hbits, uint32_t cb, uint64_t *d_ent) {
+int pgrc_ps_finish(pgrc_match_ctx *c, hipStream_t stream, const uint32_t *d_keys, const uint64_t *d_vals, uint32_t hbits, uint32_t cb, uint64_t *d_ent) {
     const uint64_t n = c->npos;
     const uint32_t np = 1u << (hbits - cb);
     int e;
     DevBuf &tmp = pgrc_build_set(c).sorttmp;
     if ((e = pgrc_buf_ensure(c, tmp, (4ull * (np + 2)) * sizeof(uint32_t) + 256))) return e;
     uint32_t *pst = (uint32_t *)tmp.p, *pst2 = pst + np + 2, *slow = pst2 + np + 2;
-    HIP_TRY(c, hipMemsetAsync(pst, 0xFF, (size_t)(np + 1) * sizeof(uint32_t), c->stream));
-    HIP_TRY(c, hipMemsetAsync(slow, 0, (size_t)(2 * np + 1) * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_ps_bounds, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 65536ull * 4)), dim3(256), 0, c->stream, d_keys, n, cb, pst);
-    hipLaunchKernelGGL(k_ps_bounds_fill, dim3((np + 256) / 256), dim3(256), 0, c->stream, (const uint32_t *)pst, np, (uint32_t)n, pst2);
-    return ps_launch_finish(c, d_keys, d_vals, (const uint32_t *)pst2, slow, np, cb, d_ent, 0u);
+    HIP_TRY(c, hipMemsetAsync(pst, 0xFF, (size_t)(np + 1) * sizeof(uint32_t), stream));
+    HIP_TRY(c, hipMemsetAsync(slow, 0, (size_t)(2 * np + 1) * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(k_ps_bounds, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 65536ull * 4)), dim3(256), 0, stream, d_keys, n, cb, pst);
+    hipLaunchKernelGGL(k_ps_bounds_fill, dim3((np + 256) / 256), dim3(256), 0, stream, (const uint32_t *)pst, np, (uint32_t)n, pst2);
+    return ps_launch_finish(c, stream, d_keys, d_vals, (const uint32_t *)pst2, slow, np, cb, d_ent, 0u);
 }
 
 // the same behind the one-sweep front end (idxsweep.hip): packed records, partition starts already known; d_slow = 2 np + 1
 // zeroed words
-int pgrc_ps_finish_packed(pgrc_match_ctx *c, const uint64_t *d_recs, const uint32_t *d_pstart, uint32_t *d_slow, uint32_t np, uint32_t cb,
+int pgrc_ps_finish_packed(pgrc_match_ctx *c, hipStream_t stream, const uint64_t *d_recs, const uint32_t *d_pstart, uint32_t *d_slow, uint32_t np, uint32_t cb,
                           uint32_t rec_sh, uint64_t *d_ent) {
-    return ps_launch_finish(c, nullptr, d_recs, d_pstart, d_slow, np, cb, d_ent, rec_sh);
+    return ps_launch_finish(c, stream, nullptr, d_recs, d_pstart, d_slow, np, cb, d_ent, rec_sh);
 }

@@ -414,7 +414,7 @@ struct OsBufs {
 // everything between the text and the finish, in one block shape: TPB threads x E records, MINB blocks per CU; AUX = type of the
 // pass-2 digit that travels with a pass-1 record, DIG = type of a staged pass-1 digit
 template <int TPB, int E, int MINB, typename AUX, typename DIG>
-static int os_passes(pgrc_match_ctx *c, int strand, const OsPlan &pl, const OsBufs &b) {
+static int os_passes(pgrc_match_ctx *c, hipStream_t stream, int strand, const OsPlan &pl, const OsBufs &b) {
     constexpr uint32_t TILE = TPB * E;
     const uint32_t *pg = (const uint32_t *)c->pg2[strand].p;
     const uint64_t pgw = c->pg_words + PGRC_PG_PAD_WORDS;
@@ -429,23 +429,23 @@ static int os_passes(pgrc_match_ctx *c, int strand, const OsPlan &pl, const OsBu
     const dim3 g1((uint32_t)pl.ntiles1), g2((uint32_t)pl.ntiles2_max), blk(TPB);
     int e;
     // pass 1
-    if (k7) hipLaunchKernelGGL((k_os_count_gen<7, TPB, E>), g1, blk, txt_bytes, c->stream, pg, pgw, pl, b.cnt1);
-    else hipLaunchKernelGGL((k_os_count_gen<0, TPB, E>), g1, blk, txt_bytes, c->stream, pg, pgw, pl, b.cnt1);
-    if ((e = pgrc_ps_scan_u32(c, b.cnt1, (uint64_t)D1 * pl.ntiles1, b.bsum))) return e;
-    hipLaunchKernelGGL(k_os_prepare, dim3(1), dim3(1024), 0, c->stream, pl, (const uint32_t *)b.cnt1, b.tile_start, b.pstart, TILE);
-    if (k7) hipLaunchKernelGGL((k_os_scatter_gen<7, TPB, E, MINB, AUX, DIG>), g1, blk, lds1, c->stream, pg, pgw, pl, (const uint32_t *)b.cnt1, b.recA, (AUX *)b.aux);
-    else hipLaunchKernelGGL((k_os_scatter_gen<0, TPB, E, MINB, AUX, DIG>), g1, blk, lds1, c->stream, pg, pgw, pl, (const uint32_t *)b.cnt1, b.recA, (AUX *)b.aux);
+    if (k7) hipLaunchKernelGGL((k_os_count_gen<7, TPB, E>), g1, blk, txt_bytes, stream, pg, pgw, pl, b.cnt1);
+    else hipLaunchKernelGGL((k_os_count_gen<0, TPB, E>), g1, blk, txt_bytes, stream, pg, pgw, pl, b.cnt1);
+    if ((e = pgrc_ps_scan_u32(c, stream, b.cnt1, (uint64_t)D1 * pl.ntiles1, b.bsum))) return e;
+    hipLaunchKernelGGL(k_os_prepare, dim3(1), dim3(1024), 0, stream, pl, (const uint32_t *)b.cnt1, b.tile_start, b.pstart, TILE);
+    if (k7) hipLaunchKernelGGL((k_os_scatter_gen<7, TPB, E, MINB, AUX, DIG>), g1, blk, lds1, stream, pg, pgw, pl, (const uint32_t *)b.cnt1, b.recA, (AUX *)b.aux);
+    else hipLaunchKernelGGL((k_os_scatter_gen<0, TPB, E, MINB, AUX, DIG>), g1, blk, lds1, stream, pg, pgw, pl, (const uint32_t *)b.cnt1, b.recA, (AUX *)b.aux);
     // pass 2
-    hipLaunchKernelGGL(k_os_tiles, dim3((uint32_t)((pl.ntiles2_max + 255) / 256)), dim3(256), 0, c->stream, pl, (const uint32_t *)b.cnt1, (const uint32_t *)b.tile_start, TILE, b.desc);
-    hipLaunchKernelGGL((k_os_count_bins<512, AUX>), g2, dim3(512), 0, c->stream, (const AUX *)b.aux, (const OsBinTile *)b.desc, pl, b.cnt2);
-    if ((e = pgrc_ps_scan_u32(c, b.cnt2, (uint64_t)D2 * pl.ntiles2_max, b.bsum))) return e;
-    hipLaunchKernelGGL((k_os_scatter_bins<TPB, E, MINB, AUX>), g2, blk, lds2, c->stream, (const uint64_t *)b.recA, (const AUX *)b.aux, pl,
+    hipLaunchKernelGGL(k_os_tiles, dim3((uint32_t)((pl.ntiles2_max + 255) / 256)), dim3(256), 0, stream, pl, (const uint32_t *)b.cnt1, (const uint32_t *)b.tile_start, TILE, b.desc);
+    hipLaunchKernelGGL((k_os_count_bins<512, AUX>), g2, dim3(512), 0, stream, (const AUX *)b.aux, (const OsBinTile *)b.desc, pl, b.cnt2);
+    if ((e = pgrc_ps_scan_u32(c, stream, b.cnt2, (uint64_t)D2 * pl.ntiles2_max, b.bsum))) return e;
+    hipLaunchKernelGGL((k_os_scatter_bins<TPB, E, MINB, AUX>), g2, blk, lds2, stream, (const uint64_t *)b.recA, (const AUX *)b.aux, pl,
                        (const OsBinTile *)b.desc, (const uint32_t *)b.cnt2, b.recB, b.pstart);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
 }
 
-int pgrc_os_build_index(pgrc_match_ctx *c, int strand, uint32_t hbits) {
+int pgrc_os_build_index(pgrc_match_ctx *c, hipStream_t stream, int strand, uint32_t hbits) {
     OsPlan pl;
     if (!os_plan(c, hbits, &pl)) { c->err = "index build (sweep): not applicable"; return PGRC_E_PARAM; }
     // XCD-aware tile order in the passes (os_tile_of_block; round 5): at C3 pass 2 goes 1.83 -> 1.38 ms per strand, pass 1 1.81 ->
@@ -485,9 +485,9 @@ int pgrc_os_build_index(pgrc_match_ctx *c, int strand, uint32_t hbits) {
     b.recA = (uint64_t *)ix.sval[0].p;
     b.recB = (uint64_t *)ix.sval[1].p;
     b.aux = ix.skey[0].p;
-    HIP_TRY(c, hipMemsetAsync(b.slow, 0, flag_words * sizeof(uint32_t), c->stream));
-    if (aux16) e = os_passes<1024, 5, 2, uint16_t, uint16_t>(c, strand, pl, b);
-    else e = os_passes<1024, 6, 2, uint8_t, uint8_t>(c, strand, pl, b);
+    HIP_TRY(c, hipMemsetAsync(b.slow, 0, flag_words * sizeof(uint32_t), stream));
+    if (aux16) e = os_passes<1024, 5, 2, uint16_t, uint16_t>(c, stream, strand, pl, b);
+    else e = os_passes<1024, 6, 2, uint8_t, uint8_t>(c, stream, strand, pl, b);
     if (e) return e;
-    return pgrc_ps_finish_packed(c, b.recB, b.pstart, b.slow, np, pl.cb, pl.rec_sh, b.recA);
+    return pgrc_ps_finish_packed(c, stream, b.recB, b.pstart, b.slow, np, pl.cb, pl.rec_sh, b.recA);
 }

@@ -308,7 +308,7 @@ static int la_matrix(PgrcStage *d, PgrcListArchive &st, const uint8_t *cnt, uint
     uint32_t *mat = (uint32_t *)st.mat.p;
     hipLaunchKernelGGL(k_la_count, dim3((uint32_t)ntiles), dim3(LA_TPB), 0, d->stream, cnt, n, ntiles, mat);
     HIP_TRY(d, hipGetLastError());
-    if ((e = pgrc_ps_scan_u32(d, mat, cells, (uint32_t *)st.fold.p))) return e;
+    if ((e = pgrc_ps_scan_u32(d, d->stream, mat, cells, (uint32_t *)st.fold.p))) return e;
     hipLaunchKernelGGL(k_la_starts, dim3(1), dim3(256), 0, d->stream, (const uint32_t *)mat, ntiles, n, (unsigned long long *)st.small.p);
     HIP_TRY(d, hipGetLastError());
     HIP_TRY(d, hipMemcpyAsync(h_small, st.small.p, sizeof(h_small), hipMemcpyDeviceToHost, d->stream));

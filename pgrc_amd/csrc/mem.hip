@@ -725,7 +725,7 @@ static int mem_set_src(pgrc_mem_ctx *m, const char *host_src, uint64_t n, int (*
     if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     const auto t0 = std::chrono::steady_clock::now();
     int e = pack(m, text, n);
-    if (!e) e = pgrc_copmem_build_index(c, 0);
+    if (!e) e = pgrc_copmem_build_index(c, c->stream, 0);
     if (!e && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "index build failed"; e = PGRC_E_DEVICE; }
     if (e) { m->err = c->err; return e; }
     m->ctr.ms_index = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -811,7 +811,7 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
     const uint64_t dwords = (N2 + 15) / 16;
     if (dest_is_src) {
         if (rev_compl) {
-            if ((e = pgrc_launch_revcomp(c, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) { m->err = c->err; return e; }
+            if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) { m->err = c->err; return e; }
             c->have_rc = true;
         }
         a.dest = (const uint32_t *)c->pg2[rev_compl ? 1 : 0].p;
@@ -867,7 +867,7 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
     a.src = (const uint32_t *)c->pg2[0].p;
     a.N = m->N;
     a.N2 = N2;
-    if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, 0))) { m->err = c->err; return e; }   // (only if somebody rebuilt the base index in between)
+    if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, c->stream, 0))) { m->err = c->err; return e; }   // (only if somebody rebuilt the base index in between)
     const PgrcIndexSet *ix = pgrc_index_of(c, 0);
     a.head = (const ulonglong2 *)ix->head_ptr;
     a.hsh = ix->head_sh;

@@ -47,12 +47,12 @@ __global__ void __launch_bounds__(256) k_pack_ascii(const uint8_t *__restrict__ 
     }
 }
 
-int pgrc_launch_pack_ascii(PgrcDev *c, const uint8_t *d_ascii, uint64_t count, uint32_t *d_words,
+int pgrc_launch_pack_ascii(PgrcDev *c, hipStream_t stream, const uint8_t *d_ascii, uint64_t count, uint32_t *d_words,
                            uint32_t *d_errflag) {
     if (count == 0) return PGRC_OK;
     uint64_t nwords = (count + 15) / 16;
     uint32_t grid = (uint32_t)((nwords + 255) / 256 < 65536 * 4 ? (nwords + 255) / 256 : 65536 * 4);
-    hipLaunchKernelGGL(k_pack_ascii, dim3(grid), dim3(256), 0, c->stream, d_ascii, count, d_words, d_errflag);
+    hipLaunchKernelGGL(k_pack_ascii, dim3(grid), dim3(256), 0, stream, d_ascii, count, d_words, d_errflag);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
 }
@@ -76,11 +76,11 @@ __global__ void __launch_bounds__(256) k_revcomp(const uint32_t *__restrict__ fw
     }
 }
 
-int pgrc_launch_revcomp(PgrcDev *c, const uint32_t *d_fw, uint32_t *d_rc, uint64_t G) {
+int pgrc_launch_revcomp(PgrcDev *c, hipStream_t stream, const uint32_t *d_fw, uint32_t *d_rc, uint64_t G) {
     uint64_t nwords = (G + 15) / 16;
     if (!nwords) return PGRC_OK;
     uint32_t grid = (uint32_t)((nwords + 255) / 256 < 65536 * 4 ? (nwords + 255) / 256 : 65536 * 4);
-    hipLaunchKernelGGL(k_revcomp, dim3(grid), dim3(256), 0, c->stream, d_fw, d_rc, G, nwords);
+    hipLaunchKernelGGL(k_revcomp, dim3(grid), dim3(256), 0, stream, d_fw, d_rc, G, nwords);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
 }
@@ -111,14 +111,14 @@ k_pack_reads_ascii(const uint8_t *__restrict__ ascii, uint64_t first, uint64_t c
     }
 }
 
-int pgrc_launch_pack_reads_ascii(PgrcDev *c, const uint8_t *d_ascii, uint64_t first, uint64_t count,
+int pgrc_launch_pack_reads_ascii(PgrcDev *c, hipStream_t stream, const uint8_t *d_ascii, uint64_t first, uint64_t count,
                                  uint32_t L, uint32_t *d_words, uint64_t stride, uint8_t *d_nflag,
                                  uint32_t *d_errflag) {
     if (!count) return PGRC_OK;
     uint32_t nw = (L + 15) / 16;
     uint64_t total = count * nw;
     uint32_t grid = (uint32_t)((total + 255) / 256 < 65536 * 4 ? (total + 255) / 256 : 65536 * 4);
-    hipLaunchKernelGGL(k_pack_reads_ascii, dim3(grid), dim3(256), 0, c->stream, d_ascii, first, count, L, nw,
+    hipLaunchKernelGGL(k_pack_reads_ascii, dim3(grid), dim3(256), 0, stream, d_ascii, first, count, L, nw,
                        d_words, stride, d_nflag, d_errflag);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
@@ -150,13 +150,13 @@ k_repack_reads_ref(const uint8_t *__restrict__ packed, uint64_t first, uint64_t 
     }
 }
 
-int pgrc_launch_repack_reads_ref(PgrcDev *c, const uint8_t *d_packed, uint64_t first, uint64_t count,
+int pgrc_launch_repack_reads_ref(PgrcDev *c, hipStream_t stream, const uint8_t *d_packed, uint64_t first, uint64_t count,
                                  uint32_t L, uint32_t *d_words, uint64_t stride) {
     if (!count) return PGRC_OK;
     uint32_t nw = (L + 15) / 16, pb = (L + 3) / 4;
     uint64_t total = count * nw;
     uint32_t grid = (uint32_t)((total + 255) / 256 < 65536 * 4 ? (total + 255) / 256 : 65536 * 4);
-    hipLaunchKernelGGL(k_repack_reads_ref, dim3(grid), dim3(256), 0, c->stream, d_packed, first, count, L, nw, pb,
+    hipLaunchKernelGGL(k_repack_reads_ref, dim3(grid), dim3(256), 0, stream, d_packed, first, count, L, nw, pb,
                        d_words, stride);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
@@ -215,13 +215,13 @@ k_unpack_reads_acgnt(const uint8_t *__restrict__ packed, uint64_t first, uint64_
     }
 }
 
-int pgrc_launch_unpack_reads_acgnt(PgrcDev *c, const uint8_t *d_packed, uint64_t first, uint64_t count, uint32_t L,
+int pgrc_launch_unpack_reads_acgnt(PgrcDev *c, hipStream_t stream, const uint8_t *d_packed, uint64_t first, uint64_t count, uint32_t L,
                                    uint32_t *d_words, uint64_t stride, uint8_t *d_nflag, uint32_t *d_errflag) {
     if (!count) return PGRC_OK;
     const uint32_t nw = (L + 15) / 16, pb = (L + 2) / 3;
     const uint64_t total = count * nw;
     const uint32_t grid = (uint32_t)((total + 255) / 256 < 65536 * 4 ? (total + 255) / 256 : 65536 * 4);
-    hipLaunchKernelGGL(k_unpack_reads_acgnt, dim3(grid), dim3(256), 0, c->stream, d_packed, first, count, L, nw, pb, d_words,
+    hipLaunchKernelGGL(k_unpack_reads_acgnt, dim3(grid), dim3(256), 0, stream, d_packed, first, count, L, nw, pb, d_words,
                        stride, d_nflag, d_errflag);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
@@ -241,12 +241,12 @@ k_nrows_ascii_acgnt(const uint8_t *__restrict__ packed, const uint32_t *__restri
     }
 }
 
-int pgrc_launch_nrows_ascii_acgnt(PgrcDev *c, const uint8_t *d_packed, const uint32_t *d_local_idx, uint64_t count,
+int pgrc_launch_nrows_ascii_acgnt(PgrcDev *c, hipStream_t stream, const uint8_t *d_packed, const uint32_t *d_local_idx, uint64_t count,
                                   uint32_t L, uint8_t *d_ascii) {
     if (!count) return PGRC_OK;
     const uint64_t total = count * L;
     const uint32_t grid = (uint32_t)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-    hipLaunchKernelGGL(k_nrows_ascii_acgnt, dim3(grid), dim3(256), 0, c->stream, d_packed, d_local_idx, count, L, (L + 2) / 3,
+    hipLaunchKernelGGL(k_nrows_ascii_acgnt, dim3(grid), dim3(256), 0, stream, d_packed, d_local_idx, count, L, (L + 2) / 3,
                        d_ascii);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
@@ -283,13 +283,13 @@ k_npos_rows(const uint8_t *__restrict__ rows, int symbols, uint64_t first, uint6
     }
 }
 
-int pgrc_launch_npos_rows(PgrcDev *c, const uint8_t *d_rows, int symbols, uint64_t first, uint64_t count, uint32_t L,
+int pgrc_launch_npos_rows(PgrcDev *c, hipStream_t stream, const uint8_t *d_rows, int symbols, uint64_t first, uint64_t count, uint32_t L,
                           uint8_t *d_nflag, uint32_t *d_npos) {
     if (!count) return PGRC_OK;
     if (L > 255 || !d_npos) { c->err = "npos_rows: a read position must fit one byte (read_len <= 255)"; return PGRC_E_PARAM; }
     const uint32_t rb = symbols == 0 ? L : (L + 2) / 3;
     const uint32_t grid = (uint32_t)((count + 255) / 256 < 65536 ? (count + 255) / 256 : 65536);
-    hipLaunchKernelGGL(k_npos_rows, dim3(grid), dim3(256), 0, c->stream, d_rows, symbols, first, count, L, rb, d_nflag, d_npos);
+    hipLaunchKernelGGL(k_npos_rows, dim3(grid), dim3(256), 0, stream, d_rows, symbols, first, count, L, rb, d_nflag, d_npos);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
 }

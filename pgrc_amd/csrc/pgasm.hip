@@ -566,7 +566,7 @@ int pgrc_asm_packed_device(pgrc_asm_ctx *a, const void **d_words) {
         if ((e = pgrc_buf_unpooled(d, a->packed, nwords * 4 + 64))) return e;
         if ((e = dec_clear_err(d))) return e;
         HIP_TRY(d, hipMemsetAsync((uint32_t *)a->packed.p + nwords, 0, 64, d->stream));
-        if ((e = pgrc_launch_pack_ascii(d, (const uint8_t *)d->text.p, d->text_len, (uint32_t *)a->packed.p, (uint32_t *)d->flag.p)))
+        if ((e = pgrc_launch_pack_ascii(d, d->stream, (const uint8_t *)d->text.p, d->text_len, (uint32_t *)a->packed.p, (uint32_t *)d->flag.p)))
             return dec_fail(d, e, "assemble: " + d->err);
         uint32_t symerr = 0;
         HIP_TRY(d, hipMemcpyAsync(&symerr, d->flag.p, 4, hipMemcpyDeviceToHost, d->stream));

@@ -301,7 +301,7 @@ static int rx_sort(PgrcDev *c, uint64_t *d_a, uint64_t *d_b, uint64_t *v_a, uint
         const uint32_t D = 1u << dbits;
         hipLaunchKernelGGL(k_rx_hist, dim3((uint32_t)ntiles), dim3(RX_TPB), 0, c->stream, (const uint64_t *)src, n, shift, D - 1u, ntiles, cnt);
         HIP_TRY(c, hipGetLastError());
-        if ((e = pgrc_ps_scan_u32(c, cnt, (uint64_t)D * ntiles, bsum))) return e;
+        if ((e = pgrc_ps_scan_u32(c, c->stream, cnt, (uint64_t)D * ntiles, bsum))) return e;
         if (pairs)
             hipLaunchKernelGGL(k_rx_scatter<true>, dim3((uint32_t)ntiles), dim3(RX_TPB), RX_TILE * sizeof(uint64_t), c->stream, (const uint64_t *)src, (const uint64_t *)vsrc, n,
                                shift, dbits, ntiles, (const uint32_t *)cnt, dst, vdst);

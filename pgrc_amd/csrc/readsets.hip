@@ -762,7 +762,7 @@ int pgrc_rsets_to_matcher(pgrc_rsets *s, pgrc_match_ctx *c) {
     int e;
     if ((e = rs_need(s, "to_matcher", {1, 2}))) return e;
     if (c->multi) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher runs on several devices");
-    if (c->st_on) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher is in a streamed run");
+    if (pgrc_stream_active(c)) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher is in a streamed run");
     if (c->device != s->device) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher is on another device");
     if (c->prm.read_len != s->prm.read_len) return rs_fail(s, PGRC_E_PARAM, "to_matcher: the matcher has another read length");
     const RsSet &lq = s->set[1], &nn = s->set[2];
@@ -772,8 +772,7 @@ int pgrc_rsets_to_matcher(pgrc_rsets *s, pgrc_match_ctx *c) {
     if (!e) e = pgrc_match_end_reads(c);
     if (e) {
         const std::string why = pgrc_match_last_error(c);
-        c->up_open = false;         // the sequence that begin_reads opened does not stay open: the matcher has no reads until its next begin
-        c->have_reads = false;
+        pgrc_upload_close(c);       // the sequence that begin_reads opened does not stay open: the matcher has no reads until its next begin
         return rs_fail(s, e, "to_matcher: " + why);
     }
     return PGRC_OK;

@@ -1013,11 +1013,11 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
     // range, prefix maximum of home - number; per segment of the sorted pairs: bounds, keys, maximum, first key's number, maximum before it
     const bool by_segments = c->opt.seed_sort >= 0 ? c->opt.seed_sort != 0 : nent >= (1ull << 20);
     const uint32_t nseg = by_segments ? 1u << SX_SEG_BITS : (uint32_t)((nent + SG_EVEN - 1) / SG_EVEN), OVL_CAP = 255u;
-    if ((e = pgrc_buf_ensure(c, c->s_keys, tslots * sizeof(ulonglong2)))) return e;
-    if ((e = pgrc_buf_ensure(c, c->s_vals, 4 * nent * sizeof(uint64_t)))) return e;
-    if ((e = pgrc_buf_ensure(c, c->s_tab, (3 * nent + 8) * sizeof(uint32_t)))) return e;
-    if ((e = pgrc_buf_ensure(c, c->s_seg, (5 * ((size_t)nseg + 1) + OVL_CAP + 1) * sizeof(uint32_t)))) return e;
-    if ((e = pgrc_buf_ensure(c, c->s_tmp, 128))) return e;        // counters, flags
+    if ((e = pgrc_buf_ensure(c, c->seed.keys, tslots * sizeof(ulonglong2)))) return e;
+    if ((e = pgrc_buf_ensure(c, c->seed.vals, 4 * nent * sizeof(uint64_t)))) return e;
+    if ((e = pgrc_buf_ensure(c, c->seed.tab, (3 * nent + 8) * sizeof(uint32_t)))) return e;
+    if ((e = pgrc_buf_ensure(c, c->seed.seg, (5 * ((size_t)nseg + 1) + OVL_CAP + 1) * sizeof(uint32_t)))) return e;
+    if ((e = pgrc_buf_ensure(c, c->seed.tmp, 128))) return e;        // counters, flags
     // the filter: 32 bits per indexed key (3 % of the windows of a random text pass it by chance), at most 2^36 bits.  It
     // pays when most windows of the text equal no key -- the exact matcher at C3: 100 M keys against 1.9 G windows, 0.20 ->
     // 0.16 s -- and costs a dependent round trip where many do (modes d / i with four parts per read: 0.42 -> 0.43 s): used
@@ -1029,28 +1029,28 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
     if (use_filter) {
         int fbits = 10;
         while (fbits < 36 && (1ull << fbits) < 32 * nent) fbits++;
-        if ((e = pgrc_buf_ensure(c, c->s_filter, (size_t)(1ull << fbits) / 8))) return e;
-        HIP_TRY(c, hipMemsetAsync(c->s_filter.p, 0, (size_t)(1ull << fbits) / 8, c->stream));
-        a.filter = (uint32_t *)c->s_filter.p;
+        if ((e = pgrc_buf_ensure(c, c->seed.filter, (size_t)(1ull << fbits) / 8))) return e;
+        HIP_TRY(c, hipMemsetAsync(c->seed.filter.p, 0, (size_t)(1ull << fbits) / 8, c->stream));
+        a.filter = (uint32_t *)c->seed.filter.p;
         a.fshift = 64u - (uint32_t)fbits;
     }
-    a.tab = (ulonglong2 *)c->s_keys.p;
+    a.tab = (ulonglong2 *)c->seed.keys.p;
     a.tmask = tsize - 1;
     a.tbits = tbits;
-    uint64_t *kA = (uint64_t *)c->s_vals.p, *kB = kA + nent, *vA = kB + nent, *vB = vA + nent;
-    uint32_t *dstart = (uint32_t *)c->s_tab.p, *pm = dstart + nent + 1;
+    uint64_t *kA = (uint64_t *)c->seed.vals.p, *kB = kA + nent, *vA = kB + nent, *vB = vA + nent;
+    uint32_t *dstart = (uint32_t *)c->seed.tab.p, *pm = dstart + nent + 1;
     a.ent = pm + nent;
-    uint32_t *seg = (uint32_t *)c->s_seg.p, *seg_nd = seg + nseg + 1, *seg_m = seg_nd + nseg + 1, *seg_base = seg_m + nseg + 1, *seg_pin = seg_base + nseg + 1,
+    uint32_t *seg = (uint32_t *)c->seed.seg.p, *seg_nd = seg + nseg + 1, *seg_m = seg_nd + nseg + 1, *seg_base = seg_m + nseg + 1, *seg_pin = seg_base + nseg + 1,
              *ovl = seg_pin + nseg + 1;
     if (a.nn) {
-        if ((e = pgrc_buf_ensure(c, c->s_nmask, a.nn * a.nwr * sizeof(uint16_t)))) return e;
-        a.nmask = (const uint16_t *)c->s_nmask.p;
+        if ((e = pgrc_buf_ensure(c, c->seed.nmask, a.nn * a.nwr * sizeof(uint16_t)))) return e;
+        a.nmask = (const uint16_t *)c->seed.nmask.p;
         hipLaunchKernelGGL(k_seed_nmask, dim3((uint32_t)((a.nn * a.nwr + 255) / 256)), dim3(256), 0, c->stream, a.nascii, a.nn, L,
-                           a.nwr, (uint16_t *)c->s_nmask.p);
+                           a.nwr, (uint16_t *)c->seed.nmask.p);
     }
-    unsigned long long *counters = (unsigned long long *)c->s_tmp.p;   // [0 / 1] hits of the forward / the RC strand
-    uint32_t *nd_dev = (uint32_t *)((char *)c->s_tmp.p + 64), *ovf_dev = nd_dev + 1;   // distinct keys; "the table ran over"
-    HIP_TRY(c, hipMemsetAsync(c->s_tmp.p, 0, 128, c->stream));
+    unsigned long long *counters = (unsigned long long *)c->seed.tmp.p;   // [0 / 1] hits of the forward / the RC strand
+    uint32_t *nd_dev = (uint32_t *)((char *)c->seed.tmp.p + 64), *ovf_dev = nd_dev + 1;   // distinct keys; "the table ran over"
+    HIP_TRY(c, hipMemsetAsync(c->seed.tmp.p, 0, 128, c->stream));
     // 1. the table (section 1): pairs, sort, distinct keys, prefix maximum, placement
     hipLaunchKernelGGL(k_seed_keys, dim3((uint32_t)((nent + 255) / 256)), dim3(256), 0, c->stream, a, kA, vA);
     if (a.nn)
@@ -1063,7 +1063,7 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
     // takes -- a key with thousands of entries sits in them -- are sorted as ranges of their own with the global passes.
     // PGRC_SEED_SORT=full / segments forces the one or the other (tests).
     if (by_segments) {
-        if ((e = pgrc_radix_sort_pairs_u64(c, kA, kB, vA, vB, nent, 64u - SX_SEG_BITS, 64, c->s_sort, &ks, &vs))) return e;
+        if ((e = pgrc_radix_sort_pairs_u64(c, kA, kB, vA, vB, nent, 64u - SX_SEG_BITS, 64, c->seed.sort, &ks, &vs))) return e;
         uint64_t *ko = ks == kA ? kB : kA, *vo = vs == vA ? vB : vA;     // the other halves of the ping-pong: scratch from here on
         HIP_TRY(c, hipMemsetAsync(ovl, 0, sizeof(uint32_t), c->stream));
         hipLaunchKernelGGL(k_seed_bounds, dim3((nseg + 1 + 255) / 256), dim3(256), 0, c->stream, (const uint64_t *)ks, (uint32_t)nent, seg);
@@ -1074,7 +1074,7 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (h_ovl[0] > OVL_CAP) {
             // (more large segments than the list holds: the whole array once more, by all its bits)
-            if ((e = pgrc_radix_sort_pairs_u64(c, ks, ko, vs, vo, nent, 0, 64, c->s_sort, &ks, &vs))) return e;
+            if ((e = pgrc_radix_sort_pairs_u64(c, ks, ko, vs, vo, nent, 0, 64, c->seed.sort, &ks, &vs))) return e;
         } else if (h_ovl[0]) {
             std::vector<uint32_t> bounds(2 * (size_t)h_ovl[0]);
             for (uint32_t k = 0; k < h_ovl[0]; k++)
@@ -1083,7 +1083,7 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
             for (uint32_t k = 0; k < h_ovl[0]; k++) {
                 const uint64_t s0 = bounds[2 * k], n = bounds[2 * k + 1] - s0;
                 uint64_t *kr = nullptr, *vr = nullptr;
-                if ((e = pgrc_radix_sort_pairs_u64(c, ks + s0, ko + s0, vs + s0, vo + s0, n, 0, 64u - SX_SEG_BITS, c->s_sort, &kr, &vr))) return e;
+                if ((e = pgrc_radix_sort_pairs_u64(c, ks + s0, ko + s0, vs + s0, vo + s0, n, 0, 64u - SX_SEG_BITS, c->seed.sort, &kr, &vr))) return e;
                 if (kr != ks + s0) {
                     HIP_TRY(c, hipMemcpyAsync(ks + s0, kr, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
                     HIP_TRY(c, hipMemcpyAsync(vs + s0, vr, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
@@ -1091,7 +1091,7 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
             }
         }
     } else {
-        if ((e = pgrc_radix_sort_pairs_u64(c, kA, kB, vA, vB, nent, 0, 64, c->s_sort, &ks, &vs))) return e;
+        if ((e = pgrc_radix_sort_pairs_u64(c, kA, kB, vA, vB, nent, 0, 64, c->seed.sort, &ks, &vs))) return e;
         hipLaunchKernelGGL(k_seed_even_bounds, dim3((nseg + 1 + 255) / 256), dim3(256), 0, c->stream, (uint32_t)nent, nseg, seg);   // (pieces of SG_EVEN pairs)
     }
     // dstart, pm, ent (and the number of keys) from the sorted pairs, segment by segment
@@ -1105,11 +1105,11 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
     // a read's hits become its result by the atomic minimum of section 3b: a start key per read, the batch's reads row by row
     const uint32_t rw = (a.nwr + 3u) & ~3u;                 // <= 16: reads have at most 255 symbols (pgrc_match_create)
     if (c->G >= (1ull << 40)) { c->err = "modes d/i/e: texts below 2^40 symbols"; return PGRC_E_PARAM; }
-    if ((e = pgrc_buf_ensure(c, c->s_best, a.n * sizeof(uint64_t)))) return e;
-    if ((e = pgrc_buf_ensure(c, c->s_rows, a.n * rw * sizeof(uint32_t)))) return e;
-    hipLaunchKernelGGL(k_seed_best_init, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), 0, c->stream, a, (uint64_t *)c->s_best.p);
+    if ((e = pgrc_buf_ensure(c, c->seed.best, a.n * sizeof(uint64_t)))) return e;
+    if ((e = pgrc_buf_ensure(c, c->seed.rows, a.n * rw * sizeof(uint32_t)))) return e;
+    hipLaunchKernelGGL(k_seed_best_init, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), 0, c->stream, a, (uint64_t *)c->seed.best.p);
     hipLaunchKernelGGL(k_seed_rows, dim3((uint32_t)((a.n + ROWS_TPB - 1) / ROWS_TPB)), dim3(ROWS_TPB), rw * (ROWS_TPB + 1) * sizeof(uint32_t),
-                       c->stream, a, rw, (uint32_t *)c->s_rows.p);
+                       c->stream, a, rw, (uint32_t *)c->seed.rows.p);
     HIP_TRY(c, hipGetLastError());
 
     // ONE scan of the forward text finds the hits of both strands (SeedArgs), in launches of at most seg_windows window starts
@@ -1121,12 +1121,12 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
     a.rc_top = nwin_all ? nwin_all - 1u + (a.cstride - 1u) : 0;
     const uint64_t nscan = !nwin_all ? 0 : (a.want & 2u) ? a.rc_top + 1u : nwin_all;
     const uint32_t per_block = (SCAN_TPB / a.cstride) * a.cstride * SCAN_R;
-    const uint32_t *rows = (const uint32_t *)c->s_rows.p;
-    uint64_t *best = (uint64_t *)c->s_best.p;
+    const uint32_t *rows = (const uint32_t *)c->seed.rows.p;
+    uint64_t *best = (uint64_t *)c->seed.best.p;
     const uint64_t pgw = c->pg_words + PGRC_PG_PAD_WORDS;
     const uint64_t wseg = std::min<uint64_t>(seg_windows, nscan);
-    if ((e = pgrc_buf_ensure(c, c->s_hits, std::max<uint64_t>(wseg, 1) * (sizeof(uint64_t) + sizeof(uint32_t))))) return e;     // one word per window start of a launch + the list of the heavy ones
-    uint64_t *wrec = (uint64_t *)c->s_hits.p;
+    if ((e = pgrc_buf_ensure(c, c->seed.hits, std::max<uint64_t>(wseg, 1) * (sizeof(uint64_t) + sizeof(uint32_t))))) return e;     // one word per window start of a launch + the list of the heavy ones
+    uint64_t *wrec = (uint64_t *)c->seed.hits.p;
     uint32_t *hlist = (uint32_t *)(wrec + std::max<uint64_t>(wseg, 1));
     for (uint64_t w0 = 0; w0 < nscan; w0 += wseg) {
         const uint64_t nwin = std::min(nscan, w0 + wseg);
@@ -1155,17 +1155,17 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             if (nheavy) {
                 const uint32_t nhv = (uint32_t)nheavy;
-                if ((e = pgrc_buf_ensure(c, c->s_hv, 2 * (size_t)nhv * sizeof(uint64_t)))) return e;
-                uint64_t *recA = (uint64_t *)c->s_hv.p, *recB = recA + nhv, *recs = nullptr;
+                if ((e = pgrc_buf_ensure(c, c->seed.hv, 2 * (size_t)nhv * sizeof(uint64_t)))) return e;
+                uint64_t *recA = (uint64_t *)c->seed.hv.p, *recB = recA + nhv, *recs = nullptr;
                 hipLaunchKernelGGL(k_seed_hv_records, dim3((nhv + 255) / 256), dim3(256), 0, c->stream, (const uint64_t *)wrec, (const uint32_t *)hlist, nhv, recA);
-                if ((e = pgrc_radix_sort_u64(c, recA, recB, nhv, 32, 32 + WREC_CNT_SH, c->s_sort, &recs))) return e;
+                if ((e = pgrc_radix_sort_u64(c, recA, recB, nhv, 32, 32 + WREC_CNT_SH, c->seed.sort, &recs))) return e;
                 // the units: counted, then listed (a key's windows x its entries, in pieces of HVG_WC x HVG_EC)
                 hipLaunchKernelGGL(k_seed_hv_units, dim3((nhv + 255) / 256), dim3(256), 0, c->stream, (const uint64_t *)recs, (const uint64_t *)wrec, nhv, (uint64_t *)nullptr, 0ull, counters + 4);
                 unsigned long long nunits = 0;
                 HIP_TRY(c, hipMemcpyAsync(&nunits, counters + 4, sizeof nunits, hipMemcpyDeviceToHost, c->stream));
                 HIP_TRY(c, hipStreamSynchronize(c->stream));
-                if ((e = pgrc_buf_ensure(c, c->s_hvu, (size_t)nunits * sizeof(uint64_t)))) return e;
-                uint64_t *units = (uint64_t *)c->s_hvu.p;
+                if ((e = pgrc_buf_ensure(c, c->seed.hvu, (size_t)nunits * sizeof(uint64_t)))) return e;
+                uint64_t *units = (uint64_t *)c->seed.hvu.p;
                 HIP_TRY(c, hipMemsetAsync(counters + 4, 0, sizeof(unsigned long long), c->stream));
                 hipLaunchKernelGGL(k_seed_hv_units, dim3((nhv + 255) / 256), dim3(256), 0, c->stream, (const uint64_t *)recs, (const uint64_t *)wrec, nhv, units, nunits, counters + 4);
 #define HVG_LAUNCH(R) hipLaunchKernelGGL((k_seed_heavy_grouped<R>), hgrid, dim3(HVG_TPB), 0, c->stream, a, w0, (const uint64_t *)wrec, (const uint64_t *)recs, (const uint64_t *)units, rows, best, counters, pgw)
@@ -1181,7 +1181,7 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
         }
     }
     // the keys that a hit has lowered become the reads' results
-    hipLaunchKernelGGL(k_seed_best_store, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), 0, c->stream, a, (const uint64_t *)c->s_best.p);
+    hipLaunchKernelGGL(k_seed_best_store, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), 0, c->stream, a, (const uint64_t *)c->seed.best.p);
     HIP_TRY(c, hipGetLastError());
     unsigned long long nh[2] = {0, 0};
     uint32_t tinfo[2] = {0, 0};
@@ -1214,7 +1214,7 @@ int pgrc_seedidx_run(pgrc_match_ctx *c, int first_strand, int last_strand) {
     if (c->n == 0) return PGRC_OK;
     int e;
     if (last_strand >= 1) {
-        if ((e = pgrc_launch_revcomp(c, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
+        if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
         c->have_rc = true;
     }
     // a batch holds at most 2^30 entries (SX_FLAG); a launch of the scan 2^29 window starts (6 GB of scratch).  The knobs force

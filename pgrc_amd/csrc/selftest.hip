@@ -350,7 +350,7 @@ extern "C" int pgrc_selftest_pack_text(pgrc_selftest *h, const uint8_t *ascii, u
     HIP_TRY(c, dflag.alloc(4, ST_GUARD * 4));
     HIP_TRY(c, hipMemcpy(din.p, ascii, count, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(dflag.p, 0, 4));
-    const int e = pgrc_launch_pack_ascii(c, din.p, count, (uint32_t *)dw.p, (uint32_t *)dflag.p);
+    const int e = pgrc_launch_pack_ascii(c, c->stream, din.p, count, (uint32_t *)dw.p, (uint32_t *)dflag.p);
     if (e) return e;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(out_words, dw.p, nwords * 4, hipMemcpyDeviceToHost));
@@ -447,7 +447,7 @@ extern "C" int pgrc_selftest_revcomp(pgrc_selftest *h, const uint32_t *words, ui
     HIP_TRY(c, drc.alloc(nwords * 4, ST_GUARD * 4));
     HIP_TRY(c, hipMemset(dfw.p, 0, (nwords + PGRC_PG_PAD_WORDS) * 4));
     HIP_TRY(c, hipMemcpy(dfw.p, words, nwords * 4, hipMemcpyHostToDevice));
-    const int e = pgrc_launch_revcomp(c, (const uint32_t *)dfw.p, (uint32_t *)drc.p, G);
+    const int e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)dfw.p, (uint32_t *)drc.p, G);
     if (e) return e;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(out_words, drc.p, nwords * 4, hipMemcpyDeviceToHost));
@@ -481,10 +481,10 @@ extern "C" int pgrc_selftest_pack_reads(pgrc_selftest *h, int kind, const uint8_
     HIP_TRY(c, hipMemset(dnf.p, 0, n_total));
     HIP_TRY(c, hipMemset(dflag.p, 0, 4));
     int e;
-    if (kind == 0) e = pgrc_launch_pack_reads_ascii(c, drows.p, first, count, L, (uint32_t *)dw.p, stride, dnf.p, (uint32_t *)dflag.p);
-    else if (kind == 4) e = pgrc_launch_repack_reads_ref(c, drows.p, first, count, L, (uint32_t *)dw.p, stride);
-    else e = pgrc_launch_unpack_reads_acgnt(c, drows.p, first, count, L, (uint32_t *)dw.p, stride, dnf.p, (uint32_t *)dflag.p);
-    if (!e && kind != 4) e = pgrc_launch_npos_rows(c, drows.p, kind, first, count, L, dnf.p, (uint32_t *)dnp.p);
+    if (kind == 0) e = pgrc_launch_pack_reads_ascii(c, c->stream, drows.p, first, count, L, (uint32_t *)dw.p, stride, dnf.p, (uint32_t *)dflag.p);
+    else if (kind == 4) e = pgrc_launch_repack_reads_ref(c, c->stream, drows.p, first, count, L, (uint32_t *)dw.p, stride);
+    else e = pgrc_launch_unpack_reads_acgnt(c, c->stream, drows.p, first, count, L, (uint32_t *)dw.p, stride, dnf.p, (uint32_t *)dflag.p);
+    if (!e && kind != 4) e = pgrc_launch_npos_rows(c, c->stream, drows.p, kind, first, count, L, dnf.p, (uint32_t *)dnp.p);
     if (e) return e;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(out_words, dw.p, (size_t)nw * stride * 4, hipMemcpyDeviceToHost));
@@ -520,7 +520,7 @@ extern "C" int pgrc_selftest_nrows_ascii(pgrc_selftest *h, const uint8_t *packed
     HIP_TRY(c, dout.alloc(count * L, ST_GUARD));
     HIP_TRY(c, hipMemcpy(drows.p, packed, n_rows * pb, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(didx.p, local_idx, count * 4, hipMemcpyHostToDevice));
-    const int e = pgrc_launch_nrows_ascii_acgnt(c, drows.p, (const uint32_t *)didx.p, count, L, dout.p);
+    const int e = pgrc_launch_nrows_ascii_acgnt(c, c->stream, drows.p, (const uint32_t *)didx.p, count, L, dout.p);
     if (e) return e;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(out_ascii, dout.p, count * L, hipMemcpyDeviceToHost));

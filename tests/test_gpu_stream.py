@@ -97,3 +97,38 @@ def test_streaming_refuses_what_it_does_not_cover():
     two.set_pg_ascii(pg)
     with pytest.raises(PgrcMatchError):
         two.prepare_index(True)
+
+
+@pytest.mark.parametrize("rows", ["ascii", "acgnt"])
+def test_failed_streamed_run_leaves_the_context_usable(rows):
+    """a bad symbol in the last block ends a streamed run with PGRC_E_SYMBOL; the same context then serves a streamed run of
+    the clean rows and a plain run, both equal to the oracle (nothing of the failed run's streams or state is left behind)"""
+    from pgrc_amd import MatchContext, PgrcMatchError
+    n_nset = 60
+    pg, reads = make_inputs(100_000, 3000, 100, seed=11, n_with_n=n_nset)
+    o = orc.oracle_match("c", pg, reads, 38, 2, 0)
+    ctx = MatchContext(100, 38, 2, 0, "c")
+    ctx.set_pg_ascii(pg)
+    ctx.prepare_index(True)
+    n_lq = reads.shape[0] - n_nset
+    if rows == "ascii":
+        clean = [(reads, reads.shape[0], 0)]
+        bad = reads.copy()
+        bad[reads.shape[0] - 5, 40] = ord("X")
+        broken = [(bad, reads.shape[0], 0)]
+    else:
+        nset = pack_rows(reads[n_lq:], b"ACGNT")
+        clean = [(pack_rows(reads[:n_lq]), n_lq, 4), (nset, n_nset, 5)]
+        bad = nset.copy()
+        bad[n_nset - 5, 7] = 125
+        broken = [clean[0], (bad, n_nset, 5)]
+    with pytest.raises(PgrcMatchError) as e:
+        ctx.match_streamed(broken, blocks=3)
+    assert e.value.code == 5, str(e.value)
+    pos, rc, mism, hist, matched = ctx.match_streamed(clean, blocks=3)
+    assert_same_results({"pos": pos, "rc": rc, "mism": mism, "hist": hist, "matched": matched}, o, f"streamed run after a failed one, {rows} rows")
+    ctx.init_results()
+    ctx.run(True)
+    pos, rc, mism, hist, matched = ctx.get_results()
+    assert_same_results({"pos": pos, "rc": rc, "mism": mism, "hist": hist, "matched": matched}, o, f"plain run after both, {rows} rows")
+    assert ctx.counters()["screened"] == 2
