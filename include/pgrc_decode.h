@@ -218,6 +218,12 @@ int pgrc_pairpos_decode(pgrc_decode_ctx *ctx, const pgrc_pairpos_streams *stream
  * straight into the context's order: the array never exists on the host.  Every check of pgrc_decode_set_order runs on
  * the decoded positions; after any failure the context has no order. */
 int pgrc_decode_set_order_pair_streams(pgrc_decode_ctx *ctx, const pgrc_pairpos_streams *streams, int32_t rev_compl_pair_file);
+/* What pgrc_decode_set_order does for mode = PGRC_DECODE_ORD, paired = 0, from the array as the single-file archive holds it
+ * (decompressReadsPgPositions with singleFileMode): n_total positions of pos_width (4 or 8) bytes each, uploaded as they are
+ * and widened on the device into the context's order.  Every check of pgrc_decode_set_order runs on the widened positions;
+ * after any failure the context has no order.  PGRC_E_PARAM: a width other than 4 or 8, NULL with n_total > 0. */
+int pgrc_decode_set_order_positions(pgrc_decode_ctx *ctx, const void *positions, uint32_t pos_width, uint64_t n_total,
+                                    int32_t rev_compl_pair_file);
 
 typedef struct {
     uint32_t struct_size;           /* sizeof(pgrc_pairpos_timing) */

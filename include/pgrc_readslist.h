@@ -11,7 +11,8 @@
  *                 order of the paired mode that does not keep the order) and compressReadsPgPositions over orgIdx2PgPos (the
  *                 pair positions of the mode that does)
  * No list array crosses the link unless the archive needs it: what comes down is the archive block of
- * pgrc_rlist_archive_encode and the pair streams.  DESIGN.md 4.20.
+ * pgrc_rlist_archive_encode and the pair streams.  The order-preserving mode's own calls are in pgrc_readslist_ord.h.
+ * DESIGN.md 4.20.
  *
  * The list holds n_entries offsets (16 bits each on the device, written in off_width bytes), n_entries original indexes,
  * optionally n_entries RC flags, optionally the mismatch streams (a count per entry, n_mismatches codes, n_mismatches offsets
@@ -57,7 +58,9 @@ enum {
     PGRC_RLIST_DOWNLOAD = 4,
     PGRC_RLIST_ARCHIVE = 5,
     PGRC_RLIST_PAIR_ORDER = 6,
-    PGRC_RLIST_PAIR_POSITIONS = 7
+    PGRC_RLIST_PAIR_POSITIONS = 7,
+    PGRC_RLIST_EXPORT_ORIGINAL = 8,
+    PGRC_RLIST_POSITIONS = 9         /* (8 and 9: pgrc_readslist_ord.h; pgrc_rlist_archive_encode_ord reports PGRC_RLIST_ARCHIVE) */
 };
 
 typedef struct {
@@ -167,6 +170,7 @@ typedef struct {
  * index written twice, an index never written), and for a position of 2^32 or more with pos_width 4.  Works on the HQ list's
  * handle.  *out is freed by pgrc_pairpos_free. */
 int pgrc_rlist_pair_positions(const pgrc_rlist_pairpos_args *args, pgrc_pairpos_streams *out);
+
 
 #ifdef __cplusplus
 }

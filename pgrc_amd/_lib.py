@@ -222,8 +222,18 @@ class RlistPairPosArgs(C.Structure):     # pgrc_rlist_pairpos_args
                 ("sets", C.c_void_p)]
 
 
+class RlistExportOrgArgs(C.Structure):  # pgrc_rlist_export_org_args (include/pgrc_readslist_ord.h)
+    _fields_ = [("struct_size", C.c_uint32), ("pair_file_mode", C.c_int32), ("read_org_idx", C.c_void_p), ("sets", C.c_void_p),
+                ("reads_total_count", C.c_uint64), ("rev_compl_pair_file", C.c_int32), ("byte_per_read_length", C.c_int32)]
+
+
+class RlistPositionsOut(C.Structure):   # pgrc_rlist_positions_out
+    _fields_ = [("struct_size", C.c_uint32), ("pos_width", C.c_uint32), ("n_total", C.c_uint64), ("positions", C.c_void_p),
+                ("block_bytes", C.c_uint64), ("block", C.c_void_p)]
+
+
 RLIST_CALLS = {1: "set_host", 2: "from_assembly", 3: "export_pg_order", 4: "download", 5: "archive_encode", 6: "pair_order",
-               7: "pair_positions"}     # PGRC_RLIST_*
+               7: "pair_positions", 8: "export_original_order", 9: "positions"}     # PGRC_RLIST_*
 
 # every symbol include/pgrc_match.h and include/pgrc_mem.h declare: (name, restype, argtypes)
 _P = C.c_void_p
@@ -388,6 +398,16 @@ RLIST_PROTOS = [
     ("pgrc_rlist_pair_positions", C.c_int, [C.POINTER(RlistPairPosArgs), _P]),
 ]
 
+# include/pgrc_readslist_ord.h: exported by libpgrc_rlist_ord.so (the product's objects and rlistord.hip), never by libpgrc_match.so
+RLIST_ORD_PROTOS = [
+    ("pgrc_rlist_export_original_order", C.c_int, [_P, _P, C.POINTER(RlistExportOrgArgs)]),
+    ("pgrc_rlist_archive_encode_ord", C.c_int, [_P, C.c_int32, C.POINTER(RlistArchive)]),
+    ("pgrc_rlist_positions", C.c_int, [C.POINTER(RlistPairPosArgs), C.POINTER(RlistPositionsOut)]),
+    ("pgrc_rlist_positions_free", None, [C.POINTER(RlistPositionsOut)]),
+]
+RLIST_ORD_EXPORTED_SYMBOLS = [p[0] for p in RLIST_ORD_PROTOS]
+RLIST_ORD_LIB_PATH = os.environ.get("PGRC_RLIST_ORD_LIB") or os.path.join(_HERE, "libpgrc_rlist_ord.so")
+
 
 class VerifyResult(C.Structure):    # pgrc_verify_result
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("ok", C.c_int32), ("salts_used", C.c_uint32),
@@ -475,3 +495,10 @@ lib = _load()
 if not os.path.exists(VERIFY_LIB_PATH):
     raise ImportError(f"{VERIFY_LIB_PATH} is missing: `make -C pgrc_amd/csrc` builds it beside libpgrc_match.so")
 vlib = bind_verify(C.CDLL(VERIFY_LIB_PATH))
+if not os.path.exists(RLIST_ORD_LIB_PATH):
+    raise ImportError(f"{RLIST_ORD_LIB_PATH} is missing: `make -C pgrc_amd/csrc` builds it beside libpgrc_match.so")
+olib = C.CDLL(RLIST_ORD_LIB_PATH)
+for _name, _res, _args in RLIST_ORD_PROTOS:
+    _fn = getattr(olib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args

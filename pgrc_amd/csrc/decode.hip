@@ -63,6 +63,11 @@ __global__ void k_dec_widen_pos(const uint64_t *__restrict__ in, uint64_t n, uin
         out[i] = in[i] + base;
 }
 
+// positions of four bytes, as the single-file ORD archive holds them for a joined text below 2^32, in the order's eight
+__global__ void __launch_bounds__(256) k_dec_widen_u32(const uint32_t *__restrict__ in, uint64_t n, uint64_t *__restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) out[i] = in[i];
+}
+
 // every window inside the text: pos + L <= len
 __global__ void k_dec_check_windows(const uint64_t *__restrict__ pos, uint64_t n, uint64_t lim, uint32_t *err) {
     uint32_t bad = 0;
@@ -610,6 +615,42 @@ int pgrc_decode_set_order_pair_streams(pgrc_decode_ctx *d, const pgrc_pairpos_st
     d->pp.tm.bytes_down = 0;
     d->pp.tm.ms_call = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     d->pp.have_timing = true;
+    return PGRC_OK;
+}
+
+// The single-file ORD order from the archive's own array: positions of W bytes go up as they are; four-byte ones are staged
+// in `rank` (the scan of dec_ord_checks fills it afterwards) and widened into org2pos
+int pgrc_decode_set_order_positions(pgrc_decode_ctx *d, const void *positions, uint32_t pos_width, uint64_t n_total, int32_t rev_compl_pair_file) {
+    if (!d) return PGRC_E_PARAM;
+    d->have_order = false;
+    if (pos_width != 4 && pos_width != 8) return dec_fail(d, PGRC_E_PARAM, "set_order_positions: pos_width must be 4 or 8");
+    if (!positions && n_total) return dec_fail(d, PGRC_E_PARAM, "set_order_positions: positions is NULL with n_total > 0");
+    if (!d->nl) return dec_fail(d, PGRC_E_STATE, "set_order_positions before add_list");
+    PGRC_ON_DEVICE(d);
+    const uint64_t T = n_total;
+    int e;
+    if ((e = pgrc_buf_unpooled(d, d->org2pos, T * 8)) || (e = pgrc_buf_unpooled(d, d->rank, (T + 1) * 8))) return e;
+    if ((e = dec_clear_err(d))) return e;
+    HIP_TRY(d, hipEventRecord(d->ev_a, d->stream));
+    if (pos_width == 8) {
+        if ((e = dec_upload(d, d->org2pos.p, positions, T * 8))) return e;
+    } else {
+        if ((e = dec_upload(d, d->rank.p, positions, T * 4))) return e;
+        const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((T + 255) / 256, 4096));
+        if (T) hipLaunchKernelGGL(k_dec_widen_u32, dim3(grid), dim3(256), 0, d->stream, (const uint32_t *)d->rank.p, T, (uint64_t *)d->org2pos.p);
+        HIP_TRY(d, hipGetLastError());
+    }
+    if ((e = dec_ord_checks(d, T))) return e;
+    HIP_TRY(d, hipGetLastError());
+    HIP_TRY(d, hipEventRecord(d->ev_b, d->stream));
+    if ((e = dec_check_err(d, "set_order_positions"))) return e;
+    d->tm.ms_order_device = dec_elapsed(d->ev_a, d->ev_b);
+    d->ord = pgrc_decode_order{};
+    d->ord.struct_size = sizeof(pgrc_decode_order);
+    d->ord.mode = PGRC_DECODE_ORD;
+    d->ord.n_total = T;
+    d->ord.rev_compl_pair_file = rev_compl_pair_file;
+    d->have_order = true;
     return PGRC_OK;
 }
 

@@ -725,23 +725,8 @@ extern "C" int pgrc_match_export_pg_order(pgrc_match_ctx *c, const pgrc_export_p
     return e;
 }
 
-// pgrc_match_export_pg_order with the old list read on the device and the merged list left there (rlistctx.h).  The caller
-// has checked what pgrc_match_export_pg_order checks of the pointers; the rest is checked here.
-int pgrc_export_pg_order_resident(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x, const PgrcExportListSrc *src, PgrcExportResident *res) {
-    *res = PgrcExportResident{};
-    if (c->multi) { c->err = "export: the resident export needs a matcher on one device"; return PGRC_E_PARAM; }
-    if (!c->have_results || !c->have_pg || !c->have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
-    if (!x->order_on_device) {
-        if (x->n_matched > c->n) { c->err = "export: more matched reads than reads"; return PGRC_E_PARAM; }
-        if (!x->order && x->n_matched) { c->err = "export_pg_order: order == NULL with n_matched > 0 (set order_on_device to let the library make the order)"; return PGRC_E_PARAM; }
-    }
-    for (uint64_t j = 0; !x->order_on_device && x->order && j < x->n_matched; j++)
-        if (x->order[j] >= c->n) { c->err = "export_pg_order: read index out of range"; return PGRC_E_PARAM; }
-    PgrcDeviceScope scope(c->device);
-    Bufs *b = new Bufs();
-    pgrc_export_streams st;
-    memset(&st, 0, sizeof st);
-    const int e = export_pg_order(c, x, *b, &st, src);
+// the hand-over of a resident export: the streams stay in *b until pgrc_export_resident_release
+static int resident_result(int e, Bufs *b, const pgrc_export_streams &st, PgrcExportResident *res) {
     if (e) {
         b->release();
         delete b;
@@ -761,6 +746,26 @@ int pgrc_export_pg_order_resident(pgrc_match_ctx *c, const pgrc_export_pg_order_
     return PGRC_OK;
 }
 
+// pgrc_match_export_pg_order with the old list read on the device and the merged list left there (rlistctx.h).  The caller
+// has checked what pgrc_match_export_pg_order checks of the pointers; the rest is checked here.
+int pgrc_export_pg_order_resident(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x, const PgrcExportListSrc *src, PgrcExportResident *res) {
+    *res = PgrcExportResident{};
+    if (c->multi) { c->err = "export: the resident export needs a matcher on one device"; return PGRC_E_PARAM; }
+    if (!c->have_results || !c->have_pg || !c->have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
+    if (!x->order_on_device) {
+        if (x->n_matched > c->n) { c->err = "export: more matched reads than reads"; return PGRC_E_PARAM; }
+        if (!x->order && x->n_matched) { c->err = "export_pg_order: order == NULL with n_matched > 0 (set order_on_device to let the library make the order)"; return PGRC_E_PARAM; }
+    }
+    for (uint64_t j = 0; !x->order_on_device && x->order && j < x->n_matched; j++)
+        if (x->order[j] >= c->n) { c->err = "export_pg_order: read index out of range"; return PGRC_E_PARAM; }
+    PgrcDeviceScope scope(c->device);
+    Bufs *b = new Bufs();
+    pgrc_export_streams st;
+    memset(&st, 0, sizeof st);
+    const int e = export_pg_order(c, x, *b, &st, src);
+    return resident_result(e, b, st, res);
+}
+
 void pgrc_export_resident_release(PgrcExportResident *res) {
     if (res->keep) {
         Bufs *b = (Bufs *)res->keep;
@@ -770,21 +775,23 @@ void pgrc_export_resident_release(PgrcExportResident *res) {
     *res = PgrcExportResident{};
 }
 
-// b.eread / b.eorg hold the entry list on the device: field arrays, offsets, mismatch streams
-static int export_entries_device(pgrc_match_ctx *c, uint64_t ne, int pair_file, uint32_t width, Bufs &b, pgrc_export_streams *out) {
+// b.eread / b.eorg hold the entry list on the device: field arrays, offsets, mismatch streams.  download = false
+// (pgrc_export_original_order_resident): the offsets are made in 16 bits whatever the mode and everything stays in `b`
+static int export_entries_device(pgrc_match_ctx *c, uint64_t ne, int pair_file, uint32_t width, Bufs &b, pgrc_export_streams *out, bool download = true) {
+    const uint32_t off_width = download ? width : 2u;
     int e;
     if ((e = pgrc_buf_ensure(c, b.epos, ne * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, b.erc, ne)) || (e = pgrc_buf_ensure(c, b.emc, ne)) ||
-        (e = pgrc_buf_ensure(c, b.off, ne * width)))
+        (e = pgrc_buf_ensure(c, b.off, ne * off_width)))
         return e;
     if (ne) {
         hipLaunchKernelGGL(k_export_fill_entries, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint32_t *)b.eread.p, ne,
                            (const uint64_t *)c->d_pos.p, (const uint8_t *)c->d_rc.p, (const uint8_t *)c->d_mism.p, (uint64_t *)b.epos.p,
                            (uint8_t *)b.erc.p, (uint8_t *)b.emc.p);
-        if (width == 1) hipLaunchKernelGGL(k_export_offsets_abs<uint8_t>, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint64_t *)b.epos.p, ne, (uint8_t *)b.off.p);
+        if (off_width == 1) hipLaunchKernelGGL(k_export_offsets_abs<uint8_t>, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint64_t *)b.epos.p, ne, (uint8_t *)b.off.p);
         else hipLaunchKernelGGL(k_export_offsets_abs<uint16_t>, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint64_t *)b.epos.p, ne, (uint16_t *)b.off.p);
         HIP_TRY(c, hipGetLastError());
     }
-    return finish_export(c, b, ne, pair_file, width, out);
+    return finish_export(c, b, ne, pair_file, width, out, download);
 }
 
 static int export_entries(pgrc_match_ctx *c, const uint32_t *entry_read, const uint32_t *entry_org_idx, uint64_t ne, int pair_file,
@@ -794,14 +801,20 @@ static int export_entries(pgrc_match_ctx *c, const uint32_t *entry_read, const u
     return export_entries_device(c, ne, pair_file, width, b, out);
 }
 
-// exportMatchesInOriginalOrder with the entry list made here (see k_oo_claim)
-static int export_original_order(pgrc_match_ctx *c, const pgrc_export_original_order_args *x, Bufs &b, pgrc_export_streams *out) {
+// exportMatchesInOriginalOrder with the entry list made here (see k_oo_claim).  d_read_org != NULL: the reads' original indexes
+// where they lie on the device; download = false: see export_entries_device
+static int export_original_order(pgrc_match_ctx *c, const pgrc_export_original_order_args *x, Bufs &b, pgrc_export_streams *out,
+                                 const uint32_t *d_read_org = nullptr, bool download = true) {
     const uint64_t total = x->reads_total_count;
     const uint32_t parts = x->pair_file_mode ? 2u : 1u, width = x->byte_per_read_length ? 1u : 2u;
     DevBuf owner, keep, rank, flag;
     auto done = [&](int code) { DevBuf *all[] = {&owner, &keep, &rank, &flag}; pgrc_buf_free_all(all, 4); return code; };
     int e;
-    if ((e = upload(c, b.rorg, x->read_org_idx, c->n * sizeof(uint32_t))) || (e = pgrc_buf_ensure(c, owner, std::max<uint64_t>(total, 1) * sizeof(uint32_t))) ||
+    if (!d_read_org) {
+        if ((e = upload(c, b.rorg, x->read_org_idx, c->n * sizeof(uint32_t)))) return done(e);
+        d_read_org = (const uint32_t *)b.rorg.p;
+    }
+    if ((e = pgrc_buf_ensure(c, owner, std::max<uint64_t>(total, 1) * sizeof(uint32_t))) ||
         (e = pgrc_buf_ensure(c, keep, std::max<uint64_t>(total, 1))) || (e = pgrc_buf_ensure(c, rank, (total + 1) * sizeof(uint64_t))) ||
         (e = pgrc_buf_ensure(c, flag, sizeof(uint32_t))))
         return done(e);
@@ -809,7 +822,7 @@ static int export_original_order(pgrc_match_ctx *c, const pgrc_export_original_o
     if (he == hipSuccess) he = hipMemsetAsync(flag.p, 0, sizeof(uint32_t), c->stream);
     if (he != hipSuccess) { c->err = std::string("export: ") + hipGetErrorString(he); return done(pgrc_hip_code(he)); }
     if (c->n)
-        hipLaunchKernelGGL(k_oo_claim, dim3(grid_for(c->n)), dim3(256), 0, c->stream, (const uint32_t *)b.rorg.p, c->n, (const uint8_t *)c->d_mism.p,
+        hipLaunchKernelGGL(k_oo_claim, dim3(grid_for(c->n)), dim3(256), 0, c->stream, d_read_org, c->n, (const uint8_t *)c->d_mism.p,
                            total, (uint32_t *)owner.p, (uint32_t *)flag.p);
     if (total) hipLaunchKernelGGL(k_oo_keep, dim3(grid_for(total)), dim3(256), 0, c->stream, (const uint32_t *)owner.p, total, parts, (uint8_t *)keep.p);
     if ((e = device_scan<uint8_t, false>(c, (const uint8_t *)keep.p, total, (uint64_t *)rank.p, b.bs))) return done(e);
@@ -831,7 +844,22 @@ static int export_original_order(pgrc_match_ctx *c, const pgrc_export_original_o
         he = hipGetLastError();
         if (he != hipSuccess) { c->err = std::string("export: ") + hipGetErrorString(he); return done(pgrc_hip_code(he)); }
     }
-    return done(export_entries_device(c, ne, x->rev_compl_pair_file, width, b, out));
+    return done(export_entries_device(c, ne, x->rev_compl_pair_file, width, b, out, download));
+}
+
+// pgrc_match_export_original_order with the reads' original indexes read on the device (d_read_org; NULL: x->read_org_idx goes
+// up) and the list left there.  The caller has checked the pointers; the rest is checked here.
+int pgrc_export_original_order_resident(pgrc_match_ctx *c, const pgrc_export_original_order_args *x, const uint32_t *d_read_org, PgrcExportResident *res) {
+    *res = PgrcExportResident{};
+    if (c->multi) { c->err = "export: the resident export needs a matcher on one device"; return PGRC_E_PARAM; }
+    if (!c->have_results || !c->have_pg || !c->have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
+    if (x->reads_total_count >= EX_SKIP) { c->err = "export_original_order: too many original indexes"; return PGRC_E_PARAM; }
+    PgrcDeviceScope scope(c->device);
+    Bufs *b = new Bufs();
+    pgrc_export_streams st;
+    memset(&st, 0, sizeof st);
+    const int e = export_original_order(c, x, *b, &st, d_read_org, false);
+    return resident_result(e, b, st, res);
 }
 
 extern "C" int pgrc_match_export_entries(pgrc_match_ctx *c, const uint32_t *entry_read, const uint32_t *entry_org_idx, uint64_t n_entries,

@@ -11,19 +11,23 @@
 //                           index's class byte; a second pass reads every write back; one pass over the T class bytes finds an
 //                           index nobody wrote.  With the writers' count equal to T that proves "every index exactly once"
 //                           without a sort and without an atomic
+//   the narrowing of it     64 -> 32 bits for the single-file order-preserving mode, which writes the array itself
+// The order-preserving mode's export (export.hip's entry list behind a second resident door) goes into a list of its own, and
+// its archive block starts at revComp: that mode writes neither off nor orgIdx.
 // Producers build the new content beside the old one and swap it in on success.  No library kernel.
 #include <stdlib.h>
 
 #include <chrono>
 
 #include "devutil.h"
+#include "pgrc_readslist_ord.h"
 #include "rlistctx.h"
 
 #define RL_TPB 256
 #define RL_MAX_BLOCKS (1u << 18)
 
 // the words of `words`
-enum { RL_BAD_RANGE, RL_BAD_TWICE, RL_BAD_NEVER, RL_BAD_WORDS };
+enum { RL_BAD_RANGE, RL_BAD_TWICE, RL_BAD_NEVER, RL_BAD_WIDE, RL_BAD_WORDS };
 
 static thread_local std::string g_rl_create_err;
 
@@ -106,6 +110,16 @@ static __global__ void __launch_bounds__(RL_TPB) k_rl_pos_matched(const uint64_t
 static __global__ void __launch_bounds__(RL_TPB) k_rl_pos_never(const uint8_t *__restrict__ cls, uint64_t T, uint32_t *__restrict__ bad) {
     for (uint64_t t = (uint64_t)blockIdx.x * RL_TPB + threadIdx.x; t < T; t += (uint64_t)gridDim.x * RL_TPB)
         if (!cls[t]) bad[RL_BAD_NEVER] = 1;
+}
+
+// orgIdx2PgPos in four bytes each (compressReadsPgPositions' singleFileMode, SeparatedPseudoGenomePersistence.cpp:454-459); a
+// position that does not fit sets bad[RL_BAD_WIDE]
+static __global__ void __launch_bounds__(RL_TPB) k_rl_pos_narrow(const uint64_t *__restrict__ pos, uint64_t T, uint32_t *__restrict__ out, uint32_t *__restrict__ bad) {
+    for (uint64_t t = (uint64_t)blockIdx.x * RL_TPB + threadIdx.x; t < T; t += (uint64_t)gridDim.x * RL_TPB) {
+        const uint64_t p = pos[t];
+        if (p >> 32) bad[RL_BAD_WIDE] = 1;
+        out[t] = (uint32_t)p;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ host side: helpers
@@ -284,6 +298,41 @@ static int rl_from_assembly(pgrc_rlist *s, const PgasmLastList &l, const uint32_
     return PGRC_OK;
 }
 
+// the list an export of the matcher left in r, copied into fresh buffers and swapped in; r is released either way
+static int rl_take_export(pgrc_rlist *s, pgrc_match_ctx *c, PgrcExportResident &r, const char *what, uint32_t call, uint64_t bytes_up,
+                          std::chrono::steady_clock::time_point t0) {
+    int e;
+    RlBufs nb;
+    auto run = [&]() -> int {
+        HIP_TRY(s, hipEventRecord(s->ev_x[1], c->stream));
+        HIP_TRY(s, hipStreamWaitEvent(s->stream, s->ev_x[1], 0));
+        HIP_TRY(s, s->ev.record(2, s->stream));
+        if (r.n_entries >= (1ull << 32) || r.n_mismatches >= (1ull << 32)) return rl_fail(s, PGRC_E_PARAM, std::string(what) + ": 2^32 entries or mismatches or more");
+        const uint64_t n = r.n_entries, m = r.n_mismatches;
+        if ((e = rl_alloc(s, nb, n, m, true, true, r.mis_off_width))) return e;
+        if ((e = rl_copy(s, nb.off.p, r.d_off, n * 2)) || (e = rl_copy(s, nb.org.p, r.d_org, n * 4)) || (e = rl_copy(s, nb.rc.p, r.d_rc, n)) || (e = rl_copy(s, nb.cnt.p, r.d_cnt, n)) ||
+            (e = rl_copy(s, nb.sym.p, r.d_sym, m)) || (e = rl_copy(s, nb.roff.p, r.d_rev_off, m * r.mis_off_width)))
+            return e;
+        HIP_TRY(s, s->ev.record(3, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
+        return PGRC_OK;
+    };
+    e = run();
+    if (e) (void)hipStreamSynchronize(s->stream);
+    const uint64_t last = r.last_pos;
+    pgrc_export_resident_release(&r);
+    if (e) {
+        rl_free(nb);
+        return e;
+    }
+    nb.last_pos = last;
+    rl_swap_in(s, nb);
+    s->tm.bytes_up = bytes_up;
+    rl_done(s, call, t0);
+    // (the export ran on the matcher's stream between ev[1] and ev[2] of this one, which waited for it)
+    return PGRC_OK;
+}
+
 static int rl_export(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_args *x) {
     const auto t0 = std::chrono::steady_clock::now();
     int e;
@@ -307,35 +356,28 @@ static int rl_export(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_a
     HIP_TRY(s, hipStreamWaitEvent(c->stream, s->ev_x[0], 0));
     PgrcExportResident r;
     if ((e = pgrc_export_pg_order_resident(c, &a, &src, &r))) return rl_fail(s, e, std::string("export_pg_order: ") + pgrc_match_last_error(c));
-    RlBufs nb;
-    auto run = [&]() -> int {
-        HIP_TRY(s, hipEventRecord(s->ev_x[1], c->stream));
-        HIP_TRY(s, hipStreamWaitEvent(s->stream, s->ev_x[1], 0));
-        HIP_TRY(s, s->ev.record(2, s->stream));
-        if (r.n_entries >= (1ull << 32) || r.n_mismatches >= (1ull << 32)) return rl_fail(s, PGRC_E_PARAM, "export_pg_order: 2^32 entries or mismatches or more");
-        const uint64_t n = r.n_entries, m = r.n_mismatches;
-        if ((e = rl_alloc(s, nb, n, m, true, true, r.mis_off_width))) return e;
-        if ((e = rl_copy(s, nb.off.p, r.d_off, n * 2)) || (e = rl_copy(s, nb.org.p, r.d_org, n * 4)) || (e = rl_copy(s, nb.rc.p, r.d_rc, n)) || (e = rl_copy(s, nb.cnt.p, r.d_cnt, n)) ||
-            (e = rl_copy(s, nb.sym.p, r.d_sym, m)) || (e = rl_copy(s, nb.roff.p, r.d_rev_off, m * r.mis_off_width)))
-            return e;
-        HIP_TRY(s, s->ev.record(3, s->stream));
-        HIP_TRY(s, hipStreamSynchronize(s->stream));
-        return PGRC_OK;
-    };
-    e = run();
-    if (e) (void)hipStreamSynchronize(s->stream);
-    const uint64_t last = r.last_pos;
-    pgrc_export_resident_release(&r);
-    if (e) {
-        rl_free(nb);
-        return e;
-    }
-    nb.last_pos = last;
-    rl_swap_in(s, nb);
-    s->tm.bytes_up = (x->order_on_device ? 0 : x->n_matched * 4) + (x->read_org_idx ? c->n * 4 : 0);
-    rl_done(s, PGRC_RLIST_EXPORT, t0);
-    // (the merge ran on the matcher's stream between ev[1] and ev[2] of this one, which waited for it)
-    return PGRC_OK;
+    return rl_take_export(s, c, r, "export_pg_order", PGRC_RLIST_EXPORT, (x->order_on_device ? 0 : x->n_matched * 4) + (x->read_org_idx ? c->n * 4 : 0), t0);
+}
+
+// exportMatchesInOriginalOrder: nothing of the old list is read; the same two hand-overs between the streams
+static int rl_export_org(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_org_args *x) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int e;
+    if ((e = rl_begin(s))) return e;
+    const uint32_t *d_rorg = nullptr;
+    if (x->sets && (e = rl_reads_org(s, x->sets, c->n, "export_original_order", &d_rorg))) return e;
+    pgrc_export_original_order_args a{};
+    a.read_org_idx = x->read_org_idx;
+    a.reads_total_count = x->reads_total_count;
+    a.pair_file_mode = x->pair_file_mode;
+    a.rev_compl_pair_file = x->rev_compl_pair_file;
+    a.byte_per_read_length = x->byte_per_read_length;
+    HIP_TRY(s, s->ev.record(1, s->stream));
+    HIP_TRY(s, hipEventRecord(s->ev_x[0], s->stream));
+    HIP_TRY(s, hipStreamWaitEvent(c->stream, s->ev_x[0], 0));
+    PgrcExportResident r;
+    if ((e = pgrc_export_original_order_resident(c, &a, d_rorg, &r))) return rl_fail(s, e, std::string("export_original_order: ") + pgrc_match_last_error(c));
+    return rl_take_export(s, c, r, "export_original_order", PGRC_RLIST_EXPORT_ORIGINAL, x->read_org_idx ? c->n * 4 : 0, t0);
 }
 
 static int rl_download_run(pgrc_rlist *s, pgrc_export_streams *out) {
@@ -371,14 +413,16 @@ static int rl_download_run(pgrc_rlist *s, pgrc_export_streams *out) {
     return PGRC_OK;
 }
 
-static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, pgrc_rlist_archive *out) {
+// ord (pgrc_rlist_archive_encode_ord; the list has RC flags and mismatch streams): the block starts with revComp, no off
+static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, bool ord, pgrc_rlist_archive *out) {
+    const char *who = ord ? "reads list: archive_encode_ord" : "reads list: archive_encode";
     const auto t0 = std::chrono::steady_clock::now();
     const RlBufs &b = s->cur;
     const uint64_t n = b.n, m = b.nmis, w = b.off_width;
     int e;
     if ((e = rl_begin(s))) return e;
     // the block: off | revComp | orgIdx | the archive form, each 16-byte aligned
-    const uint64_t at_rc = dec_a16(n * w) + 16, at_org = at_rc + (b.has_rc ? dec_a16(n) + 16 : 0), at_la = at_org + (want_org ? dec_a16(n * 4) + 16 : 0);
+    const uint64_t at_rc = ord ? 0 : dec_a16(n * w) + 16, at_org = at_rc + (b.has_rc ? dec_a16(n) + 16 : 0), at_la = at_org + (want_org ? dec_a16(n * 4) + 16 : 0);
     const uint64_t dev_bytes = at_la + (b.has_mis ? pgrc_la_device_bytes(n, m) : 0), host_bytes = at_la + (b.has_mis ? pgrc_la_host_bytes(n, m) : 0) + 16;
     if ((e = pgrc_buf_unpooled(s, s->block, dev_bytes + 16))) return e;
     uint8_t *ob = (uint8_t *)s->block.p;
@@ -386,11 +430,7 @@ static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, pgrc_rlist_archiv
     PgrcLaResident la{};
     if (b.has_mis && (e = pgrc_la_encode_resident(s, s->la, (const uint8_t *)b.cnt.p, (const uint8_t *)b.sym.p, (const uint8_t *)b.roff.p, n, m, fast, ob + at_la, &la))) return e;
     HIP_TRY(s, s->ev.record(2, s->stream));
-    if (w == 1) {
-        if ((e = rl_narrow(s, (const uint16_t *)b.off.p, n, ob))) return e;
-    } else if ((e = rl_copy(s, ob, b.off.p, n * 2))) {
-        return e;
-    }
+    if (!ord && (e = w == 1 ? rl_narrow(s, (const uint16_t *)b.off.p, n, ob) : rl_copy(s, ob, b.off.p, n * 2))) return e;
     if (b.has_rc && (e = rl_copy(s, ob + at_rc, b.rc.p, n))) return e;
     if (want_org && (e = rl_copy(s, ob + at_org, b.org.p, n * 4))) return e;
     HIP_TRY(s, s->ev.record(3, s->stream));
@@ -400,11 +440,11 @@ static int rl_archive(pgrc_rlist *s, bool fast, bool want_org, pgrc_rlist_archiv
     const void *src[1] = {ob};
     uint8_t *blk = nullptr;
     uint64_t down = 0;
-    if ((e = dec_download_block(s, "reads list: archive_encode", h, src, &blk, &down))) return e;
+    if ((e = dec_download_block(s, who, h, src, &blk, &down))) return e;
     out->struct_size = sizeof(pgrc_rlist_archive);
     out->off_width = (uint32_t)w;
     out->n_entries = n;
-    out->off = blk;
+    out->off = ord ? nullptr : blk;
     out->rev_comp = b.has_rc ? blk + at_rc : nullptr;
     out->org_idx = want_org ? (const uint32_t *)(blk + at_org) : nullptr;
     out->block_bytes = down;
@@ -438,12 +478,12 @@ static int rl_pair_order(pgrc_rlist *s, pgrc_rlist *const lists[3], uint64_t T, 
     return PGRC_OK;
 }
 
-static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pgrc_pairpos_streams *out) {
-    const auto t0 = std::chrono::steady_clock::now();
+// orgIdx2PgPos in s->pos (T positions of eight bytes) with the proof that every index is written exactly once; on return the
+// stream is idle and ev[1] recorded.  Shared by pgrc_rlist_pair_positions and pgrc_rlist_positions (`who`)
+static int rl_positions_build(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, const std::string &who) {
     const uint64_t T = x->n_total;
     pgrc_match_ctx *c = x->matcher;
     int e;
-    if ((e = rl_begin(s))) return e;
     pgrc_rlist *const lists[3] = {x->hq, x->lq, x->n};
     const uint64_t base[3] = {0, x->hq_len, x->hq_len + x->lq_len};
     uint64_t longest = c ? c->n + 1 : 1, writers = 0;
@@ -462,7 +502,7 @@ static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pg
     uint64_t matched = 0;
     if (c) {
         if (x->sets) {
-            if ((e = rl_reads_org(s, x->sets, c->n, "pair_positions", &d_rorg))) return e;
+            if ((e = rl_reads_org(s, x->sets, c->n, who.c_str(), &d_rorg))) return e;
         } else if (x->read_org_idx) {
             if ((e = pgrc_buf_unpooled(s, s->map, c->n * 4 + 16)) || (e = dec_upload_host(s, s->map.p, x->read_org_idx, c->n * 4))) return e;
             s->tm.bytes_up = c->n * 4;
@@ -478,7 +518,7 @@ static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pg
     }
     // nothing is launched for an input that cannot write every index once
     if (writers != T)
-        return rl_fail(s, PGRC_E_PARAM, "pair_positions: the lists and the matched reads are " + std::to_string(writers) + ", n_total is " + std::to_string(T) +
+        return rl_fail(s, PGRC_E_PARAM, who + ": the lists and the matched reads are " + std::to_string(writers) + ", n_total is " + std::to_string(T) +
                                             (writers > T ? ": an index is written twice" : ": an index is never written"));
     if (T) HIP_TRY(s, hipMemsetAsync(pos, 0xFF, T * 8, s->stream));      // vector<uint_pg_len_max>(readsTotalCount, -1)
     if (T) HIP_TRY(s, hipMemsetAsync(cls, 0, T, s->stream));
@@ -500,13 +540,57 @@ static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pg
     uint32_t h_bad[RL_BAD_WORDS] = {};
     HIP_TRY(s, hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
-    if (h_bad[RL_BAD_RANGE]) return rl_fail(s, PGRC_E_PARAM, "pair_positions: an original index of " + std::to_string(T) + " (n_total) or more");
-    if (h_bad[RL_BAD_TWICE] || h_bad[RL_BAD_NEVER]) return rl_fail(s, PGRC_E_PARAM, "pair_positions: an index is written twice and another never");
-    if ((e = pgrc_pairpos_encode_device(s, s->pp, pos, T, x->pos_width, out))) return e;
+    if (h_bad[RL_BAD_RANGE]) return rl_fail(s, PGRC_E_PARAM, who + ": an original index of " + std::to_string(T) + " (n_total) or more");
+    if (h_bad[RL_BAD_TWICE] || h_bad[RL_BAD_NEVER]) return rl_fail(s, PGRC_E_PARAM, who + ": an index is written twice and another never");
+    return PGRC_OK;
+}
+
+static int rl_pair_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pgrc_pairpos_streams *out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t T = x->n_total;
+    int e;
+    if ((e = rl_begin(s)) || (e = rl_positions_build(s, x, "pair_positions"))) return e;
+    if ((e = pgrc_pairpos_encode_device(s, s->pp, (const uint64_t *)s->pos.p, T, x->pos_width, out))) return e;
     for (int k = 2; k < 4; k++) HIP_TRY(s, s->ev.record(k, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     s->tm.bytes_down = s->pp.tm.bytes_down;
     rl_done(s, PGRC_RLIST_PAIR_POSITIONS, t0);
+    return PGRC_OK;
+}
+
+// the array narrowed to pos_width bytes on the device and brought down in one block
+static int rl_positions(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, pgrc_rlist_positions_out *out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t T = x->n_total, W = x->pos_width;
+    int e;
+    if ((e = rl_begin(s)) || (e = rl_positions_build(s, x, "positions"))) return e;
+    HIP_TRY(s, s->ev.record(2, s->stream));
+    const void *d_out = s->pos.p;
+    if (W == 4) {
+        uint32_t *bad = (uint32_t *)s->words.p;       // (all zero: the build has returned)
+        if ((e = pgrc_buf_unpooled(s, s->block, T * 4 + 16))) return e;
+        if (T) hipLaunchKernelGGL(k_rl_pos_narrow, dim3(rl_grid(T)), dim3(RL_TPB), 0, s->stream, (const uint64_t *)s->pos.p, T, (uint32_t *)s->block.p, bad);
+        HIP_TRY(s, hipGetLastError());
+        uint32_t h_bad[RL_BAD_WORDS] = {};
+        HIP_TRY(s, hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
+        if (h_bad[RL_BAD_WIDE]) return rl_fail(s, PGRC_E_PARAM, "positions: a position of 2^32 or more with pos_width 4");
+        d_out = s->block.p;
+    }
+    HIP_TRY(s, s->ev.record(3, s->stream));
+    const uint64_t bytes[1] = {T * W};
+    const void *src[1] = {d_out};
+    uint8_t *blk = nullptr;
+    uint64_t down = 0;
+    if ((e = dec_download_block(s, "reads list: positions", dec_block_layout(bytes), src, &blk, &down))) return e;
+    out->struct_size = sizeof(pgrc_rlist_positions_out);
+    out->pos_width = (uint32_t)W;
+    out->n_total = T;
+    out->positions = blk;
+    out->block_bytes = down;
+    out->block = blk;
+    s->tm.bytes_down = down;
+    rl_done(s, PGRC_RLIST_POSITIONS, t0);
     return PGRC_OK;
 }
 
@@ -645,7 +729,7 @@ int pgrc_rlist_archive_encode(pgrc_rlist *s, int32_t fast_level, int32_t want_or
     if (s->cur.has_mis && s->cur.off_width != 1)
         return rl_fail(s, PGRC_E_PARAM, "archive_encode: offsets of " + std::to_string(s->cur.off_width) + " bytes (the archive's loader reads one byte each)");
     PGRC_ON_DEVICE(s);
-    const int e = rl_archive(s, fast_level != 0, want_org_idx != 0, out);
+    const int e = rl_archive(s, fast_level != 0, want_org_idx != 0, false, out);
     if (e) {
         (void)hipStreamSynchronize(s->stream);
         *out = pgrc_rlist_archive{};
@@ -677,20 +761,29 @@ int pgrc_rlist_pair_order(pgrc_rlist *const lists[3], int32_t form, pgrc_pairord
     return e;
 }
 
+// what both position calls check of their arguments (x->hq is there)
+static int rl_positions_args_ok(const pgrc_rlist_pairpos_args *x, const std::string &who) {
+    pgrc_rlist *s = x->hq;
+    if (x->struct_size != sizeof(pgrc_rlist_pairpos_args)) return rl_fail(s, PGRC_E_PARAM, who + ": struct_size is not sizeof(pgrc_rlist_pairpos_args)");
+    if (x->sets && x->read_org_idx) return rl_fail(s, PGRC_E_PARAM, who + ": the reads' original indexes are given twice (read_org_idx and sets)");
+    for (pgrc_rlist *l : {x->lq, x->n})
+        if (l && l->device != s->device) return rl_fail(s, PGRC_E_PARAM, who + ": the lists are on different devices");
+    int e;
+    if (x->matcher) {
+        if ((e = rl_matcher_ok(s, x->matcher, who.c_str()))) return e;
+        if (!x->matcher->have_results || !x->matcher->d_pos.p) return rl_fail(s, PGRC_E_STATE, who + ": the matcher has no results");
+    }
+    return PGRC_OK;
+}
+
 int pgrc_rlist_pair_positions(const pgrc_rlist_pairpos_args *x, pgrc_pairpos_streams *out) {
     if (!x || !x->hq) return PGRC_E_PARAM;
     pgrc_rlist *s = x->hq;
     if (x->struct_size != sizeof(pgrc_rlist_pairpos_args)) return rl_fail(s, PGRC_E_PARAM, "pair_positions: struct_size is not sizeof(pgrc_rlist_pairpos_args)");
     if (!out) return rl_fail(s, PGRC_E_PARAM, "pair_positions: out is NULL");
     *out = pgrc_pairpos_streams{};
-    if (x->sets && x->read_org_idx) return rl_fail(s, PGRC_E_PARAM, "pair_positions: the reads' original indexes are given twice (read_org_idx and sets)");
-    for (pgrc_rlist *l : {x->lq, x->n})
-        if (l && l->device != s->device) return rl_fail(s, PGRC_E_PARAM, "pair_positions: the lists are on different devices");
     int e;
-    if (x->matcher) {
-        if ((e = rl_matcher_ok(s, x->matcher, "pair_positions"))) return e;
-        if (!x->matcher->have_results || !x->matcher->d_pos.p) return rl_fail(s, PGRC_E_STATE, "pair_positions: the matcher has no results");
-    }
+    if ((e = rl_positions_args_ok(x, "pair_positions"))) return e;
     PGRC_ON_DEVICE(s);
     if ((e = rl_pair_positions(s, x, out))) {
         (void)hipStreamSynchronize(s->stream);
@@ -700,3 +793,57 @@ int pgrc_rlist_pair_positions(const pgrc_rlist_pairpos_args *x, pgrc_pairpos_str
 }
 
 }   // extern "C"
+
+// ------------------------------------------------------------------------------------------------ the order-preserving mode
+// The entry points of include/pgrc_readslist_ord.h (rlistord.hip exports them from a library of its own)
+int pgrc_rl_export_original_order(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_org_args *x) {
+    if (!s) return PGRC_E_PARAM;
+    if (!c) return rl_fail(s, PGRC_E_PARAM, "export_original_order: the matcher is NULL");
+    if (!x || x->struct_size != sizeof(pgrc_rlist_export_org_args))
+        return rl_fail(s, PGRC_E_PARAM, "export_original_order: args is NULL or struct_size is not sizeof(pgrc_rlist_export_org_args)");
+    if (x->sets && x->read_org_idx) return rl_fail(s, PGRC_E_PARAM, "export_original_order: the reads' original indexes are given twice (read_org_idx and sets)");
+    int e;
+    if ((e = rl_matcher_ok(s, c, "export_original_order"))) return e;
+    if (c->n && !x->sets && !x->read_org_idx) return rl_fail(s, PGRC_E_PARAM, "export_original_order: neither read_org_idx nor sets");
+    PGRC_ON_DEVICE(s);
+    if ((e = rl_export_org(s, c, x))) (void)hipStreamSynchronize(s->stream);
+    return e;
+}
+
+int pgrc_rl_archive_encode_ord(pgrc_rlist *s, int32_t fast_level, pgrc_rlist_archive *out) {
+    if (!s) return PGRC_E_PARAM;
+    if (!out) return rl_fail(s, PGRC_E_PARAM, "archive_encode_ord: out is NULL");
+    *out = pgrc_rlist_archive{};
+    if (!s->cur.has_rc || !s->cur.has_mis) return rl_fail(s, PGRC_E_STATE, "archive_encode_ord: the list has no RC flags or no mismatch streams (export_original_order makes them)");
+    if (s->cur.off_width != 1)
+        return rl_fail(s, PGRC_E_PARAM, "archive_encode_ord: offsets of " + std::to_string(s->cur.off_width) + " bytes (the archive's loader reads one byte each)");
+    PGRC_ON_DEVICE(s);
+    const int e = rl_archive(s, fast_level != 0, false, true, out);
+    if (e) {
+        (void)hipStreamSynchronize(s->stream);
+        *out = pgrc_rlist_archive{};
+    }
+    return e;
+}
+
+int pgrc_rl_positions(const pgrc_rlist_pairpos_args *x, pgrc_rlist_positions_out *out) {
+    if (!x || !x->hq) return PGRC_E_PARAM;
+    pgrc_rlist *s = x->hq;
+    if (!out || out->struct_size != sizeof(pgrc_rlist_positions_out)) return rl_fail(s, PGRC_E_PARAM, "positions: out is NULL or struct_size is not sizeof(pgrc_rlist_positions_out)");
+    *out = pgrc_rlist_positions_out{};
+    int e;
+    if ((e = rl_positions_args_ok(x, "positions"))) return e;
+    if (x->pos_width != 4 && x->pos_width != 8) return rl_fail(s, PGRC_E_PARAM, "positions: pos_width must be 4 or 8");
+    PGRC_ON_DEVICE(s);
+    if ((e = rl_positions(s, x, out))) {
+        (void)hipStreamSynchronize(s->stream);
+        *out = pgrc_rlist_positions_out{};
+    }
+    return e;
+}
+
+void pgrc_rl_positions_free(pgrc_rlist_positions_out *o) {
+    if (!o) return;
+    if (o->block) (void)hipHostFree(o->block);
+    *o = pgrc_rlist_positions_out{};
+}

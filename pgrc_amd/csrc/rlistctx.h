@@ -8,6 +8,7 @@
 
 #include "pgrc_assemble.h"
 #include "pgrc_readslist.h"
+#include "pgrc_readslist_ord.h"
 #include "codingctx.h"
 #include "rsetsctx.h"
 
@@ -70,6 +71,9 @@ struct PgrcExportResident {
     void *keep;
 };
 int pgrc_export_pg_order_resident(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x, const PgrcExportListSrc *src, PgrcExportResident *res);
+// exportMatchesInOriginalOrder likewise: the reads' original indexes in memory of the matcher's device (NULL: x->read_org_idx
+// goes up), the entry list left in pooled buffers of the matcher until the release; last_pos is 0 as the host call's
+int pgrc_export_original_order_resident(pgrc_match_ctx *c, const pgrc_export_original_order_args *x, const uint32_t *d_read_org, PgrcExportResident *res);
 void pgrc_export_resident_release(PgrcExportResident *res);
 
 // listarchive.hip: pgrc_list_archive_encode's device side on streams that lie on the device; the block is written at d_block
@@ -91,3 +95,9 @@ void pgrc_la_describe_resident(pgrc_list_archive_streams *out, uint8_t *blk, uin
 int pgrc_pairorder_encode_joined(PgrcStage *s, PgrcPairOrder &st, const uint32_t *d_joined, uint64_t T, int32_t form, pgrc_pairorder_streams *out);
 // pairpos.hip: pgrc_pairpos_encode on positions in memory of the stage's device, read where they lie
 int pgrc_pairpos_encode_device(PgrcStage *s, PgrcPairPos &st, const uint64_t *d_org_idx_to_pos, uint64_t n_total, uint32_t pos_width, pgrc_pairpos_streams *out);
+
+// rlist.hip: the order-preserving mode's calls, exported under the names of pgrc_readslist_ord.h by rlistord.hip
+int pgrc_rl_export_original_order(pgrc_rlist *list, pgrc_match_ctx *matcher, const pgrc_rlist_export_org_args *args);
+int pgrc_rl_archive_encode_ord(pgrc_rlist *list, int32_t fast_level, pgrc_rlist_archive *out);
+int pgrc_rl_positions(const pgrc_rlist_pairpos_args *args, pgrc_rlist_positions_out *out);
+void pgrc_rl_positions_free(pgrc_rlist_positions_out *out);

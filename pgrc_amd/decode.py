@@ -98,6 +98,7 @@ DECODE_PROTOS = [
     ("pgrc_pairpos_free", None, [C.POINTER(PairPosStreams)]),
     ("pgrc_pairpos_decode", C.c_int, [_P, C.POINTER(PairPosStreams), _P]),
     ("pgrc_decode_set_order_pair_streams", C.c_int, [_P, C.POINTER(PairPosStreams), C.c_int32]),
+    ("pgrc_decode_set_order_positions", C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_int32]),
     ("pgrc_pairpos_get_timing", C.c_int, [_P, C.POINTER(PairPosTiming)]),
     ("pgrc_pairorder_encode", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.c_int32, C.POINTER(PairOrderStreams)]),
     ("pgrc_pairorder_free", None, [C.POINTER(PairOrderStreams)]),
@@ -424,6 +425,13 @@ class PgRCDecoder:
         the positions are decoded on the device into the context's order and never exist on the host"""
         s, keep = _pairpos_struct(streams)
         self._ck(lib.pgrc_decode_set_order_pair_streams(self._h, C.byref(s), int(bool(rev_compl_pair_file))))
+
+    def set_order_positions(self, positions, rev_compl_pair_file: bool = False) -> None:
+        """the single-file ORD order from orgIdx2PgPos as the archive holds it: an unsigned integer array whose dtype is the
+        position width (uint32 or uint64; any other width is the library's to refuse), widened on the device"""
+        a = np.ascontiguousarray(positions)
+        assert a.dtype.kind == "u" and a.ndim == 1
+        self._ck(lib.pgrc_decode_set_order_positions(self._h, _ptr(a), a.dtype.itemsize, a.size, int(bool(rev_compl_pair_file))))
 
     def decompressReadsPgPositions(self, streams: dict) -> np.ndarray:
         """SeparatedPseudoGenomePersistence::decompressReadsPgPositions (:582-673) on the device: the positions as

@@ -1,4 +1,5 @@
-"""A pseudogenome's reads list on the device from the assembly to the archive (include/pgrc_readslist.h): ReadsList mirrors
+"""A pseudogenome's reads list on the device from the assembly to the archive (include/pgrc_readslist.h, and
+include/pgrc_readslist_ord.h for the order-preserving mode, whose four calls libpgrc_rlist_ord.so exports): ReadsList mirrors
 the calls.  No compute of its own."""
 from __future__ import annotations
 
@@ -8,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import PgrcMatchError, lib
+from ._lib import PgrcMatchError, lib, olib
 from .decode import PairOrderStreams, PairPosStreams, _list_archive_dict, _pairorder_dict, _pairpos_dict
 from .matchers import MatchContext
 
@@ -19,7 +20,8 @@ def _p(a):
 
 class ReadsList:
     """off, orgIdx, revComp and the mismatch streams of one pseudogenome's reads list in device memory.  Producers: set_host,
-    from_assembly, export_pg_order; consumers: download, archive_encode, pair_order, pair_positions."""
+    from_assembly, export_pg_order, export_original_order; consumers: download, archive_encode, archive_encode_ord, pair_order,
+    pair_positions, positions."""
 
     def __init__(self, device: int = -1):
         self._h = C.c_void_p()
@@ -101,6 +103,20 @@ class ReadsList:
         a.rev_compl_pair_file, a.byte_per_read_length = int(rev_compl_pair_file), int(byte_per_read_length)
         self._ck(lib.pgrc_rlist_export_pg_order(self._h, matcher._h, C.byref(a)))
 
+    def export_original_order(self, matcher, total: int, read_org_idx=None, sets=None, pair_file_mode: bool = False,
+                              rev_compl_pair_file: bool = False, byte_per_read_length: bool = True) -> None:
+        """exportMatchesInOriginalOrder: one entry per original index below `total`; the result replaces this list"""
+        a = _lib.RlistExportOrgArgs(C.sizeof(_lib.RlistExportOrgArgs))
+        keep = None
+        if read_org_idx is not None:
+            keep = np.ascontiguousarray(read_org_idx, dtype=np.uint32)
+            a.read_org_idx = keep.ctypes.data
+        if sets is not None:
+            a.sets = sets._h
+        a.reads_total_count, a.pair_file_mode = int(total), int(pair_file_mode)
+        a.rev_compl_pair_file, a.byte_per_read_length = int(rev_compl_pair_file), int(byte_per_read_length)
+        self._ck(olib.pgrc_rlist_export_original_order(self._h, matcher._h, C.byref(a)))
+
     def download(self) -> dict:
         """the streams as MatchContext.export_pg_order returns them"""
         st = _lib.ExportStreams()
@@ -112,13 +128,27 @@ class ReadsList:
         archive (as PgRCDecoder.list_archive_encode returns it; None for a list without mismatch streams), block_bytes"""
         a = _lib.RlistArchive()
         self._ck(lib.pgrc_rlist_archive_encode(self._h, int(bool(fast_level)), int(bool(want_org_idx)), C.byref(a)))
+        return self._archive_dict(a)
+
+    def archive_encode_ord(self, fast_level: bool = False) -> dict:
+        """what compressedBuild(.., ignoreOffDest = true) hands to the coders in the order-preserving mode: as archive_encode
+        returns it, with off and org_idx None (the block holds neither) and block_start = "rev_comp", the stream at the start
+        of the block"""
+        a = _lib.RlistArchive()
+        self._ck(olib.pgrc_rlist_archive_encode_ord(self._h, int(bool(fast_level)), C.byref(a)))
+        start = "rev_comp" if a.rev_comp and a.rev_comp == a.block else None
+        return dict(self._archive_dict(a), block_start=start)
+
+    @staticmethod
+    def _archive_dict(a) -> dict:
         try:
             n, w = int(a.n_entries), int(a.off_width)
 
             def take(p, count, dt):
                 dt = np.dtype(dt)
                 return np.frombuffer((C.c_uint8 * (count * dt.itemsize)).from_address(p), dtype=dt).copy() if count else np.zeros(0, dt)
-            out = {"n_entries": n, "off_width": w, "block_bytes": int(a.block_bytes), "off": take(a.off, n, np.uint8 if w == 1 else np.uint16),
+            out = {"n_entries": n, "off_width": w, "block_bytes": int(a.block_bytes),
+                   "off": take(a.off, n, np.uint8 if w == 1 else np.uint16) if a.off else None,
                    "rev_comp": take(a.rev_comp, n, np.uint8) if a.rev_comp else None,
                    "org_idx": take(a.org_idx, n, np.uint32) if a.org_idx else None,
                    "archive": _list_archive_dict(a.archive, a.block) if a.archive.struct_size else None}
@@ -143,10 +173,7 @@ class ReadsList:
         finally:
             lib.pgrc_pairorder_free(C.byref(s))
 
-    def pair_positions(self, n_total: int, pos_width: int, lq=None, n=None, hq_len: int = 0, lq_len: int = 0, matcher=None,
-                       read_org_idx=None, sets=None) -> dict:
-        """orgIdx2PgPos of the order-preserving paired mode from this (HQ) list, the LQ and N lists and the matcher's matched
-        reads, built and coded on the device -> as PgRCDecoder.compressReadsPgPositions"""
+    def _pairpos_args(self, n_total, pos_width, lq, n, hq_len, lq_len, matcher, read_org_idx, sets):
         a = _lib.RlistPairPosArgs(C.sizeof(_lib.RlistPairPosArgs), int(pos_width), int(n_total))
         a.hq, a.lq, a.n = self._h, (lq._h if lq is not None else None), (n._h if n is not None else None)
         a.hq_len, a.lq_len = int(hq_len), int(lq_len)
@@ -158,12 +185,34 @@ class ReadsList:
             a.read_org_idx = keep.ctypes.data
         if sets is not None:
             a.sets = sets._h
+        return a, keep
+
+    def pair_positions(self, n_total: int, pos_width: int, lq=None, n=None, hq_len: int = 0, lq_len: int = 0, matcher=None,
+                       read_org_idx=None, sets=None) -> dict:
+        """orgIdx2PgPos of the order-preserving paired mode from this (HQ) list, the LQ and N lists and the matcher's matched
+        reads, built and coded on the device -> as PgRCDecoder.compressReadsPgPositions"""
+        a, keep = self._pairpos_args(n_total, pos_width, lq, n, hq_len, lq_len, matcher, read_org_idx, sets)
         s = PairPosStreams()
         self._ck(lib.pgrc_rlist_pair_positions(C.byref(a), C.byref(s)))
         try:
             return _pairpos_dict(s)
         finally:
             lib.pgrc_pairpos_free(C.byref(s))
+
+    def positions(self, n_total: int, pos_width: int, lq=None, n=None, hq_len: int = 0, lq_len: int = 0, matcher=None,
+                  read_org_idx=None, sets=None) -> np.ndarray:
+        """orgIdx2PgPos of the order-preserving single-file mode, built as pair_positions builds it (n_total may be odd) and
+        narrowed to pos_width bytes on the device -> n_total positions, uint32 or uint64"""
+        a, keep = self._pairpos_args(n_total, pos_width, lq, n, hq_len, lq_len, matcher, read_org_idx, sets)
+        o = _lib.RlistPositionsOut(C.sizeof(_lib.RlistPositionsOut))
+        self._ck(olib.pgrc_rlist_positions(C.byref(a), C.byref(o)))
+        try:
+            dt = np.dtype(np.uint32 if int(o.pos_width) == 4 else np.uint64)
+            T = int(o.n_total)
+            assert o.positions == o.block and int(o.block_bytes) == T * dt.itemsize
+            return np.frombuffer((C.c_uint8 * (T * dt.itemsize)).from_address(o.positions), dtype=dt).copy() if T else np.zeros(0, dt)
+        finally:
+            olib.pgrc_rlist_positions_free(C.byref(o))
 
     def close(self) -> None:
         if self._h:

@@ -15,7 +15,14 @@ medians of --repeats after a warm-up, and the bytes that cross the link on each:
   pair_order pgrc_pairorder_encode on the three host arrays against pgrc_rlist_pair_order
 Prints one JSON object and writes it to --out.  Needs the device: there is no other way to take these numbers.
 
-    python tools/rlist_rate.py [--reads R] [--repeats N] [--out profiles/rlist_rate.json]
+--ord times the order-preserving mode's way instead, on the same split and the same lists and matcher:
+  export     pgrc_match_export_original_order (seven streams of one entry per original read down into pageable memory) against
+             pgrc_rlist_export_original_order into a second list (the reads' original indexes from host memory on both)
+  archive    pgrc_list_archive_encode on the streams the export returned against pgrc_rlist_archive_encode_ord
+  positions  the three lists' off and org_idx brought down (pgrc_rlist_download) and orgIdx2PgPos scattered with numpy and
+             narrowed to four bytes, against pgrc_rlist_positions
+
+    python tools/rlist_rate.py [--ord] [--reads R] [--repeats N] [--out profiles/rlist_rate.json | profiles/rlist_rate_ord.json]
 """
 import argparse
 import json
@@ -42,12 +49,73 @@ def timed(fn, *a, **kw):
     return r, (time.perf_counter() - t0) * 1e3
 
 
+def positions_host(T, lists, bases, read_org, pos, matched):
+    """the caller's way to orgIdx2PgPos without pgrc_rlist_positions: every list's off and org_idx down, three scatters"""
+    arr = np.full(T, np.uint64(2**64 - 1), dtype=np.uint64)
+    down = 0
+    for l, base in zip(lists, bases):
+        st = l.download()
+        down += int(l.timing()["bytes_down"])
+        arr[st["org_idx"]] = np.uint64(base) + np.cumsum(st["off"], dtype=np.uint64)
+    arr[read_org[matched]] = pos[matched]
+    return arr.astype(np.uint32), down
+
+
+def main_ord(args, ctx, dec, hq, rest, read_org, pos, matched, R, n_hq, n_rest, G):
+    """the ORD way on both routes; the lists and the matcher are main()'s"""
+    from pgrc_amd import ReadsList
+    lq_len = L
+    bases = (0, G, G + lq_len)
+    out_list = ReadsList(0)
+    seams = {k: {"host_ms": [], "resident_ms": []} for k in ("export", "archive", "positions")}
+    dev = {k: [] for k in seams}
+    for rep in range(args.repeats + 1):
+        exp, ms_eh = timed(ctx.export_original_order, read_org, R, False, False, True)
+        _, ms_er = timed(out_list.export_original_order, ctx, R, read_org, None, False, False, True)
+        t_exp = out_list.timing()
+        _, ms_ah = timed(dec.list_archive_encode, exp["mis_cnt"], exp["mis_sym"], exp["mis_rev_off"])
+        arch, ms_ar = timed(out_list.archive_encode_ord, False)
+        t_arch = out_list.timing()
+        (want, pos_down), ms_ph = timed(positions_host, R, [hq] + rest, bases, read_org, pos, matched)
+        got, ms_pr = timed(hq.positions, R, 4, rest[0], rest[1], G, lq_len, ctx, read_org)
+        t_pos = hq.timing()
+        assert np.array_equal(got, want)
+        if rep:                             # (the first round is the warm-up)
+            for k, h, r, t in (("export", ms_eh, ms_er, t_exp), ("archive", ms_ah, ms_ar, t_arch), ("positions", ms_ph, ms_pr, t_pos)):
+                seams[k]["host_ms"].append(h)
+                seams[k]["resident_ms"].append(r)
+                dev[k].append(t)
+    ne, nm = int(exp["org_idx"].size), int(exp["mis_sym"].size)
+    out = {"mode": "ord", "reads": R, "read_len": L, "repeats": args.repeats, "hq_entries": n_hq, "matcher_reads": n_rest, "matched": int(matched.sum()),
+           "entries": ne, "mismatches": nm, "text_symbols": G, "pos_width": 4, "seams": {}}
+    bytes_host = {"export": {"up": 4 * n_rest, "down": 7 * ne + 2 * nm},
+                  "archive": {"up": ne + 2 * nm, "down": int(dec.list_archive_timing()["bytes_down"])},
+                  "positions": {"up": 0, "down": pos_down}}
+    for k, v in seams.items():
+        t = dev[k][-1]
+        o = {"host_route": {"ms": stat(v["host_ms"]), "bytes": bytes_host[k]},
+             "resident_route": {"ms": stat(v["resident_ms"]), "bytes": {"up": int(t["bytes_up"]), "down": int(t["bytes_down"]), "device_copy": int(t["bytes_device_copy"])},
+                                "device_ms": {p: stat([x[p] for x in dev[k]]) for p in ("ms_fetch_device", "ms_build_device", "ms_pack_device")},
+                                "call_ms": stat([x["ms_call"] for x in dev[k]])}}
+        o["host_over_resident"] = round(o["host_route"]["ms"]["median"] / max(o["resident_route"]["ms"]["median"], 1e-6), 2)
+        out["seams"][k] = o
+    out["link_bytes"] = {"host_route": sum(sum(b.values()) for b in bytes_host.values()),
+                         "resident_route": sum(o["resident_route"]["bytes"]["up"] + o["resident_route"]["bytes"]["down"] for o in out["seams"].values())}
+    out["archive_block_bytes"] = int(arch["block_bytes"])
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=100_000_000)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rlist_rate.json"))
+    ap.add_argument("--ord", action="store_true", help="the order-preserving mode's way (export, archive block, positions)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "rlist_rate_ord.json" if args.ord else "rlist_rate.json")
     import torch
     from pgrc_amd import MatchContext, PgRCDecoder, ReadsList
     rng = np.random.default_rng(1)
@@ -80,6 +148,9 @@ def main():
         l.set_host(np.zeros(org.size, np.uint8), org)
         rest.append(l)
     hq = ReadsList(0)
+    if args.ord:
+        hq.set_host(hq_off, hq_org)
+        return main_ord(args, ctx, dec, hq, rest, read_org, pos, matched, R, n_hq, n_rest, G)
     seams = {k: {"host_ms": [], "resident_ms": []} for k in ("assembly", "export", "archive", "pair_order")}
     dev = {k: [] for k in ("export", "archive", "pair_order")}
     # the assembly seam and the yardstick: 6 bytes per entry down to page-locked memory, or device to device
