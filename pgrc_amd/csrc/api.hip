@@ -13,6 +13,7 @@
 
 #include "ctx.h"
 #include "devutil.h"
+#include "matchdev.h"
 
 // Large device buffers that a context gives back are kept for the next context of the process instead of going back to
 // the driver: re-allocating tens of GB right after freeing them can stall for seconds (the driver scrubs freed memory
@@ -337,15 +338,15 @@ int pgrc_match_create(const pgrc_match_params *p, pgrc_match_ctx **out) {
     c->prm = *p;
     c->opt = pgrc_options_from_env();
     c->device = dev;
-    c->nw = (p->read_len + 15) / 16;
+    c->rd.nw = (p->read_len + 15) / 16;
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
     }
     int be;
-    if ((be = pgrc_buf_ensure(c, c->d_hist, 256 * sizeof(uint64_t))) || (be = pgrc_buf_ensure(c, c->d_counters, 40 * sizeof(uint64_t)))) {
+    if ((be = pgrc_buf_ensure(c, c->res.d_hist, 256 * sizeof(uint64_t))) || (be = pgrc_buf_ensure(c, c->res.d_counters, sizeof(PgrcDevCounters)))) {
         g_create_err = c->err;
-        pgrc_buf_free(c->d_hist);
+        pgrc_buf_free(c->res.d_hist);
         delete c;
         return be;
     }
@@ -365,14 +366,12 @@ void pgrc_match_destroy(pgrc_match_ctx *c) {
     c->up.stream[1].release();
     c->side.release();
     c->build.release();
-    DevBufList bufs = {&c->pg2[0], &c->pg2[1], &c->reads_own, &c->nread_idx, &c->nread_ascii, &c->nread_flag, &c->nread_npos, &c->d_pos,
-                       &c->d_rc, &c->d_mism, &c->d_hist, &c->d_counters, &c->d_headpair, &c->d_scr_pos, &c->d_scr_flag};
-    for (const DevBufList &more : {c->up.bufs(), c->seed.bufs()}) bufs.insert(bufs.end(), more.begin(), more.end());
+    DevBufList bufs = {&c->d_headpair};
+    for (const DevBufList &more : {c->txt.bufs(), c->rd.bufs(), c->res.bufs(), c->up.bufs(), c->seed.bufs()}) bufs.insert(bufs.end(), more.begin(), more.end());
     for (PgrcIndexSet &ix : c->idx) bufs.insert(bufs.end(), {&ix.head, &ix.skey[0], &ix.skey[1], &ix.sval[0], &ix.sval[1], &ix.sorttmp});
     pgrc_buf_free_all(bufs.data(), bufs.size());                 // (the device is idle: waited for above)
     c->up.reset();
-    if (c->have_events)
-        for (auto &e : c->ev) (void)hipEventDestroy(e);
+    c->tm.ev.release();
     delete c;
 }
 
@@ -389,10 +388,8 @@ int pgrc_match_set_profiling(pgrc_match_ctx *c, int enabled) {
     if (!c) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_set_profiling(c, enabled);
     PGRC_ON_DEVICE(c);
-    if (enabled && !c->have_events) {
-        for (auto &e : c->ev) HIP_TRY(c, hipEventCreate(&e));
-        c->have_events = true;
-    }
+    if (enabled)
+        if (int e = c->tm.ensure(c)) return e;
     c->profiling = enabled != 0;
     return PGRC_OK;
 }
@@ -420,17 +417,17 @@ int pgrc_pg_alloc(pgrc_match_ctx *c, uint64_t G) {
         if (c->build.stream) (void)hipStreamSynchronize(c->build.stream);
         (void)hipStreamSynchronize(c->stream);
     }
-    if (G != c->G) c->screen_broken = false;     // another text: the second index set may fit now
-    c->G = G;
-    c->pg_words = (G + 15) / 16;
-    const size_t bytes = (c->pg_words + PGRC_PG_PAD_WORDS) * sizeof(uint32_t);
+    if (G != c->txt.G) c->screen_broken = false;     // another text: the second index set may fit now
+    c->txt.G = G;
+    c->txt.pg_words = (G + 15) / 16;
+    const size_t bytes = (c->txt.pg_words + PGRC_PG_PAD_WORDS) * sizeof(uint32_t);
     int e;
     for (int s = 0; s < 2; s++) {
-        if ((e = pgrc_buf_ensure(c, c->pg2[s], bytes))) return e;
-        HIP_TRY(c, hipMemsetAsync(c->pg2[s].p, 0, bytes, c->stream));
+        if ((e = pgrc_buf_ensure(c, c->txt.pg2[s], bytes))) return e;
+        HIP_TRY(c, hipMemsetAsync(c->txt.pg2[s].p, 0, bytes, c->stream));
     }
-    c->have_pg = false;
-    c->have_rc = false;
+    c->txt.have_pg = false;
+    c->txt.have_rc = false;
     for (PgrcIndexSet &ix : c->idx) ix.strand = -1;
     c->idx_prepared = false;
     if (c->prm.mode == 'c') {
@@ -523,8 +520,8 @@ int pgrc_match_set_pg_ascii(pgrc_match_ctx *c, const char *pg, uint64_t G) {
     PGRC_ON_DEVICE(c);
     int e = pgrc_pg_alloc(c, G);
     if (e) return e;
-    if ((e = pgrc_match_pack_pg_slice(c, pg, G, c->pg2[0].p))) return e;
-    c->have_pg = true;
+    if ((e = pgrc_match_pack_pg_slice(c, pg, G, c->txt.pg2[0].p))) return e;
+    c->txt.have_pg = true;
     return PGRC_OK;
 }
 
@@ -534,32 +531,40 @@ int pgrc_match_set_pg_packed_device(pgrc_match_ctx *c, const void *d_words, uint
     PGRC_ON_DEVICE(c);
     int e = pgrc_pg_alloc(c, G);
     if (e) return e;
-    HIP_TRY(c, hipMemcpyAsync(c->pg2[0].p, d_words, c->pg_words * sizeof(uint32_t), hipMemcpyDefault, c->stream));   // (the source may live on another device)
+    HIP_TRY(c, hipMemcpyAsync(c->txt.pg2[0].p, d_words, c->txt.pg_words * sizeof(uint32_t), hipMemcpyDefault, c->stream));   // (the source may live on another device)
     // clear the bits after symbol G-1 in the last word: padding must read as zero
     if (G % 16) {
         uint32_t last;
-        HIP_TRY(c, hipMemcpyAsync(&last, (const uint32_t *)d_words + c->pg_words - 1, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&last, (const uint32_t *)d_words + c->txt.pg_words - 1, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         last &= (1u << (2 * (G % 16))) - 1u;
-        HIP_TRY(c, hipMemcpyAsync((uint32_t *)c->pg2[0].p + c->pg_words - 1, &last, 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync((uint32_t *)c->txt.pg2[0].p + c->txt.pg_words - 1, &last, 4, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    c->have_pg = true;
+    c->txt.have_pg = true;
     return PGRC_OK;
 }
+
+}   // extern "C"
+// The RC text from the forward one, queued on `stream`.  Runs make it every time, like the reference
+// (PgHelpers::reverseComplementInPlace(pgPtr), ReadsMatchers.cpp:168); an export only when it is missing.
+int pgrc_make_rc_text(pgrc_match_ctx *c, hipStream_t stream) {
+    if (int e = pgrc_launch_revcomp(c, stream, (const uint32_t *)c->txt.pg2[0].p, (uint32_t *)c->txt.pg2[1].p, c->txt.G)) return e;
+    c->txt.have_rc = true;
+    return PGRC_OK;
+}
+int pgrc_need_rc_text(pgrc_match_ctx *c) { return c->txt.have_rc ? PGRC_OK : pgrc_make_rc_text(c, c->stream); }
+extern "C" {
 
 int pgrc_match_export_pg(pgrc_match_ctx *c, int strand, uint32_t *words) {
     if (!c || !words || strand < 0 || strand > 1) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_export_pg(c, strand, words);
-    if (!c->have_pg) { c->err = "export_pg: no pseudogenome set"; return PGRC_E_STATE; }
+    if (!c->txt.have_pg) { c->err = "export_pg: no pseudogenome set"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
-    if (strand == 1 && !c->have_rc) {
-        int e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G);
-        if (e) return e;
-        c->have_rc = true;
-    }
+    if (strand == 1)
+        if (int e = pgrc_need_rc_text(c)) return e;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(words, c->pg2[strand].p, c->pg_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(words, c->txt.pg2[strand].p, c->txt.pg_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return PGRC_OK;
 }
 
@@ -567,27 +572,27 @@ int pgrc_match_export_pg(pgrc_match_ctx *c, int strand, uint32_t *words) {
 
 static int alloc_results(pgrc_match_ctx *c, uint64_t n) {
     int e;
-    if ((e = pgrc_buf_ensure(c, c->d_pos, n * sizeof(uint64_t)))) return e;
-    if ((e = pgrc_buf_ensure(c, c->d_rc, n))) return e;
-    if ((e = pgrc_buf_ensure(c, c->d_mism, n))) return e;
-    c->have_results = false;
+    if ((e = pgrc_buf_ensure(c, c->res.d_pos, n * sizeof(uint64_t)))) return e;
+    if ((e = pgrc_buf_ensure(c, c->res.d_rc, n))) return e;
+    if ((e = pgrc_buf_ensure(c, c->res.d_mism, n))) return e;
+    c->res.have_results = false;
     return PGRC_OK;
 }
 
 static int begin_reads(pgrc_match_ctx *c, uint64_t n, bool own) {
     pgrc_stream_abort(c);                        // (a streamed run that was never finished)
     if (n >= (1ull << 32) - 1) { c->err = "reads count must stay below 2^32-1 (uint_reads_cnt_max, pg-config.h:21-22)"; return PGRC_E_PARAM; }
-    if (n != c->n) c->screen_broken = false;     // another read set: the screen's per-read arrays may fit now
-    c->n = n;
-    c->n_nreads = 0;
-    c->n_many = 0;
-    c->h_nidx.clear();
-    c->have_reads = false;
+    if (n != c->rd.n) c->screen_broken = false;     // another read set: the screen's per-read arrays may fit now
+    c->rd.n = n;
+    c->rd.n_nreads = 0;
+    c->rd.n_many = 0;
+    c->rd.h_nidx.clear();
+    c->rd.have_reads = false;
     int e;
     if (own) {
-        c->stride = (n + 63) & ~63ull;
-        if ((e = pgrc_buf_ensure(c, c->reads_own, (size_t)c->nw * std::max<uint64_t>(c->stride, 64) * sizeof(uint32_t)))) return e;
-        c->reads2 = (const uint32_t *)c->reads_own.p;
+        c->rd.stride = (n + 63) & ~63ull;
+        if ((e = pgrc_buf_ensure(c, c->rd.reads_own, (size_t)c->rd.nw * std::max<uint64_t>(c->rd.stride, 64) * sizeof(uint32_t)))) return e;
+        c->rd.reads2 = (const uint32_t *)c->rd.reads_own.p;
     }
     return alloc_results(c, n);
 }
@@ -601,13 +606,13 @@ int pgrc_match_begin_reads(pgrc_match_ctx *c, uint64_t n) {
     PGRC_ON_DEVICE(c);
     int e = begin_reads(c, n, true);
     if (e) return e;
-    if ((e = pgrc_buf_ensure(c, c->nread_flag, n))) return e;
+    if ((e = pgrc_buf_ensure(c, c->rd.nread_flag, n))) return e;
     // (nread_npos, 4 bytes per read, only exists once a block that CAN hold an N arrives: ASCII rows or an ACGNT set -- an ACGT
     //  set cannot, and at C3 the array is 400 MB that a memory-tight job would rather give its second index set)
     // (cleared on a stream of its own and waited for: the main stream may hold index builds started ahead of the run --
     //  pgrc_match_prepare_index --, which neither this nor the uploads that follow should queue behind)
     if ((e = c->up.stream[0].ensure(c, "begin_reads"))) return e;
-    HIP_TRY(c, hipMemsetAsync(c->nread_flag.p, 0, n ? n : 1, c->up.stream[0].stream));
+    HIP_TRY(c, hipMemsetAsync(c->rd.nread_flag.p, 0, n ? n : 1, c->up.stream[0].stream));
     HIP_TRY(c, hipStreamSynchronize(c->up.stream[0].stream));
     c->up.reset();
     c->up.open = true;
@@ -622,20 +627,20 @@ int pgrc_match_begin_reads(pgrc_match_ctx *c, uint64_t n) {
 static int stage_chunk(pgrc_match_ctx *c, hipStream_t up, void *stage, const uint8_t *src, size_t bytes, bool src_device, uint64_t first, uint64_t cnt,
                        int32_t symbols) {
     const uint32_t L = c->prm.read_len;
-    uint32_t *words = (uint32_t *)c->reads_own.p, *bad = (uint32_t *)c->up.flag.p;
-    uint8_t *nflag = (uint8_t *)c->nread_flag.p;
+    uint32_t *words = (uint32_t *)c->rd.reads_own.p, *bad = (uint32_t *)c->up.flag.p;
+    uint8_t *nflag = (uint8_t *)c->rd.nread_flag.p;
     if (hipMemcpyAsync(stage, src, bytes, src_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, up) != hipSuccess) return PGRC_E_DEVICE;
-    if (symbols == 4) return pgrc_launch_repack_reads_ref(c, up, (const uint8_t *)stage, first, cnt, L, words, c->stride);   // (an ACGT set cannot hold an N)
-    int e = symbols == 0 ? pgrc_launch_pack_reads_ascii(c, up, (const uint8_t *)stage, first, cnt, L, words, c->stride, nflag, bad)
-                         : pgrc_launch_unpack_reads_acgnt(c, up, (const uint8_t *)stage, first, cnt, L, words, c->stride, nflag, bad);
-    if (e || (e = pgrc_buf_ensure(c, c->nread_npos, std::max<uint64_t>(c->n, 1) * sizeof(uint32_t)))) return e;   // (first such block: allocated)
-    return pgrc_launch_npos_rows(c, up, (const uint8_t *)stage, symbols, first, cnt, L, nflag, (uint32_t *)c->nread_npos.p);
+    if (symbols == 4) return pgrc_launch_repack_reads_ref(c, up, (const uint8_t *)stage, first, cnt, L, words, c->rd.stride);   // (an ACGT set cannot hold an N)
+    int e = symbols == 0 ? pgrc_launch_pack_reads_ascii(c, up, (const uint8_t *)stage, first, cnt, L, words, c->rd.stride, nflag, bad)
+                         : pgrc_launch_unpack_reads_acgnt(c, up, (const uint8_t *)stage, first, cnt, L, words, c->rd.stride, nflag, bad);
+    if (e || (e = pgrc_buf_ensure(c, c->rd.nread_npos, std::max<uint64_t>(c->rd.n, 1) * sizeof(uint32_t)))) return e;   // (first such block: allocated)
+    return pgrc_launch_npos_rows(c, up, (const uint8_t *)stage, symbols, first, cnt, L, nflag, (uint32_t *)c->rd.nread_npos.p);
 }
 
 // The N flags of an unpacked chunk come down through `up`: its reads with N join the side list; local: their rows within the chunk
 static int list_n_rows(pgrc_match_ctx *c, hipStream_t up, uint64_t first, uint64_t cnt, std::vector<uint8_t> &nf, std::vector<uint32_t> &local) {
     nf.resize(cnt);
-    if (hipMemcpyAsync(nf.data(), (const uint8_t *)c->nread_flag.p + first, cnt, hipMemcpyDeviceToHost, up) != hipSuccess || hipStreamSynchronize(up) != hipSuccess)
+    if (hipMemcpyAsync(nf.data(), (const uint8_t *)c->rd.nread_flag.p + first, cnt, hipMemcpyDeviceToHost, up) != hipSuccess || hipStreamSynchronize(up) != hipSuccess)
         return PGRC_E_DEVICE;
     local.clear();
     for (uint64_t k = 0; k < cnt; k++)
@@ -681,7 +686,7 @@ static int keep_n_rows(pgrc_match_ctx *c, hipStream_t up, const void *stage, con
 // (made on the device for the packed formats) are kept for the side list of end_reads.
 // src_device: `rows` is memory of the context's device (packed rows only): the staging copy is device to device
 static int append_rows(pgrc_match_ctx *c, const uint8_t *rows, uint64_t count, int32_t symbols, bool src_device = false) {
-    if (!c->up.open || c->up.next + count > c->n) { c->err = "append_reads: outside begin/end or too many rows"; return PGRC_E_STATE; }
+    if (!c->up.open || c->up.next + count > c->rd.n) { c->err = "append_reads: outside begin/end or too many rows"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     const uint32_t L = c->prm.read_len;
     const uint32_t rb = symbols == 0 ? L : symbols == 4 ? (L + 3) / 4 : (L + 2) / 3;   // host bytes per row
@@ -758,29 +763,29 @@ void PgrcUpload::reset() {
 }
 void pgrc_upload_close(pgrc_match_ctx *c) {
     c->up.open = false;
-    c->have_reads = false;
+    c->rd.have_reads = false;
 }
 extern "C" {
 
 int pgrc_match_end_reads(pgrc_match_ctx *c) {
     if (!c) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_end_reads(c);
-    if (!c->up.open || c->up.next != c->n) { c->err = "end_reads: fewer rows appended than announced"; return PGRC_E_STATE; }
+    if (!c->up.open || c->up.next != c->rd.n) { c->err = "end_reads: fewer rows appended than announced"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     int e;
-    c->n_nreads = c->up.nidx.size();
-    c->n_many = c->up.nmany;
-    c->h_nidx = c->up.nidx;
-    if (c->n_nreads) {
+    c->rd.n_nreads = c->up.nidx.size();
+    c->rd.n_many = c->up.nmany;
+    c->rd.h_nidx = c->up.nidx;
+    if (c->rd.n_nreads) {
         const uint32_t L = c->prm.read_len;
-        if ((e = pgrc_buf_ensure(c, c->nread_idx, c->up.nidx.size() * sizeof(uint32_t)))) return e;
-        if ((e = pgrc_buf_ensure(c, c->nread_ascii, c->n_nreads * L))) return e;
+        if ((e = pgrc_buf_ensure(c, c->rd.nread_idx, c->up.nidx.size() * sizeof(uint32_t)))) return e;
+        if ((e = pgrc_buf_ensure(c, c->rd.nread_ascii, c->rd.n_nreads * L))) return e;
         // (a streamed run has its matching queued on the main stream: the side list is put together beside it)
         hipStream_t s = (pgrc_stream_active(c) && c->up.stream[0].stream) ? c->up.stream[0].stream : c->stream;
-        HIP_TRY(c, hipMemcpyAsync(c->nread_idx.p, c->up.nidx.data(), c->up.nidx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->rd.nread_idx.p, c->up.nidx.data(), c->up.nidx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         uint64_t at = 0;
         for (size_t k = 0; k < c->up.nchunks.size(); k++) {
-            HIP_TRY(c, hipMemcpyAsync((uint8_t *)c->nread_ascii.p + at * L, c->up.nchunks[k].p, c->up.nchunk_rows[k] * L, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync((uint8_t *)c->rd.nread_ascii.p + at * L, c->up.nchunks[k].p, c->up.nchunk_rows[k] * L, hipMemcpyDeviceToDevice, s));
             at += c->up.nchunk_rows[k];
         }
         HIP_TRY(c, hipStreamSynchronize(s));
@@ -790,7 +795,7 @@ int pgrc_match_end_reads(pgrc_match_ctx *c) {
     c->up.nidx.clear();
     c->up.nidx.shrink_to_fit();
     c->up.open = false;
-    c->have_reads = true;
+    c->rd.have_reads = true;
     return PGRC_OK;
 }
 
@@ -816,9 +821,9 @@ int pgrc_match_set_reads_device(pgrc_match_ctx *c, const void *d_words, uint64_t
     PGRC_ON_DEVICE(c);
     int e = begin_reads(c, n, false);
     if (e) return e;
-    c->reads2 = (const uint32_t *)d_words;
-    c->stride = stride;
-    c->have_reads = true;
+    c->rd.reads2 = (const uint32_t *)d_words;
+    c->rd.stride = stride;
+    c->rd.have_reads = true;
     return PGRC_OK;
 }
 
@@ -827,33 +832,33 @@ int pgrc_match_set_reads_device(pgrc_match_ctx *c, const void *d_words, uint64_t
 int pgrc_match_init_results(pgrc_match_ctx *c) {
     if (!c) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_init_results(c);
-    if (!c->have_reads) { c->err = "init_results: no reads set"; return PGRC_E_STATE; }
+    if (!c->rd.have_reads) { c->err = "init_results: no reads set"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     int e = pgrc_launch_init_results(c);
     if (e) return e;
-    c->have_results = true;
+    c->res.have_results = true;
     return PGRC_OK;
 }
 
 int pgrc_match_set_results(pgrc_match_ctx *c, const uint64_t *pos, const uint8_t *rc, const uint8_t *mism) {
     if (!c || !pos || !rc || !mism) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_set_results(c, pos, rc, mism);
-    if (!c->have_reads) { c->err = "set_results: no reads set"; return PGRC_E_STATE; }
+    if (!c->rd.have_reads) { c->err = "set_results: no reads set"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
-    if (c->n) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_pos.p, pos, c->n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->d_rc.p, rc, c->n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->d_mism.p, mism, c->n, hipMemcpyHostToDevice, c->stream));
+    if (c->rd.n) {
+        HIP_TRY(c, hipMemcpyAsync(c->res.d_pos.p, pos, c->rd.n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->res.d_rc.p, rc, c->rd.n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->res.d_mism.p, mism, c->rd.n, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    c->have_results = true;
+    c->res.have_results = true;
     return PGRC_OK;
 }
 
 // Two-pass runs of mode c with min_mismatches == 0 take the screened schedule (copmem.hip, "Exact-match screen") unless
 // PGRC_SCREEN=0 or the second set of index buffers does not fit.
 static bool screen_wanted(const pgrc_match_ctx *c, int first, int last) {
-    if (c->prm.mode != 'c' || first != 0 || last != 1 || c->prm.min_mismatches != 0 || !c->n || c->screen_broken) return false;
+    if (c->prm.mode != 'c' || first != 0 || last != 1 || c->prm.min_mismatches != 0 || !c->rd.n || c->screen_broken) return false;
     if (c->opt.screen >= 0) return c->opt.screen == 1;     // PGRC_SCREEN: 0 never, 1 whenever it applies; unset: where it pays
     if (!c->opt.early_stop) return false;       // (the screen's proofs of absence ARE the early-stop rule)
     // The screen is one more sweep over all reads (~5 probes each) and saves a read that matches the other strand exactly
@@ -865,7 +870,7 @@ static bool screen_wanted(const pgrc_match_ctx *c, int first, int last) {
 
 // ... and, when they apply, rather ONE query per read over both strands (copmem.hip, "The dual kernel"); PGRC_DUAL=0: never
 static bool dual_wanted(const pgrc_match_ctx *c, int first, int last) {
-    if (c->prm.mode != 'c' || first != 0 || last != 1 || c->prm.min_mismatches != 0 || !c->n || c->screen_broken) return false;
+    if (c->prm.mode != 'c' || first != 0 || last != 1 || c->prm.min_mismatches != 0 || !c->rd.n || c->screen_broken) return false;
     if (c->opt.dual == 0) return false;
     if (!c->opt.early_stop || c->opt.screen >= 0) return false;   // the older schedules were asked for
     if (c->opt.dual == 1) return true;
@@ -876,18 +881,16 @@ static bool dual_wanted(const pgrc_match_ctx *c, int first, int last) {
     return k2 && c->prm.read_len >= K;
 }
 
-} // extern "C" (a template, and helpers of stream.hip)
+} // extern "C" (helpers of stream.hip)
 // The RC text and both strands' indexes: strand 0 goes into the build set, then the build set is turned and strand 1 goes
 // into the other one (the launchers find either by its strand).  Both builds at once on two streams (they share nothing
-// but the bandwidth; PGRC_BUILD_STREAMS=1: in turn); the main stream is made to wait for the second.  `mark` is called
-// after the RC text and after the builds (profiling events).  PGRC_E_ALLOC: no room for the second set -- the caller
-// retreats (pgrc_index_retreat).
-template <typename F>
-static int pgrc_build_both_indexes(pgrc_match_ctx *c, F mark) {
+// but the bandwidth; PGRC_BUILD_STREAMS=1: in turn); the main stream is made to wait for the second.  A run's timer gets
+// the RC text, the forward index (builds in turn only) and both indexes (on two streams even when the second found no
+// room).  PGRC_E_ALLOC: no room for the second set -- the caller retreats (pgrc_index_retreat).
+static int pgrc_build_both_indexes(pgrc_match_ctx *c) {
     int e;
-    if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
-    c->have_rc = true;
-    mark(); // 1
+    if ((e = pgrc_make_rc_text(c, c->stream))) return e;
+    c->tm.mark(TM_RC_TEXT, c->stream);
     bool two = !c->opt.builds_in_turn;
     if (two && c->build.ensure(c, "index build streams")) { (void)hipGetLastError(); two = false; }   // (no second stream: in turn)
     if (two) {
@@ -909,17 +912,15 @@ static int pgrc_build_both_indexes(pgrc_match_ctx *c, F mark) {
     // nothing extra only as whole 64-byte runs (groups of 1 and 2: index pair 16.2 -> 24.9 ms; groups of 4: 17.0)
     c->pair_gm = pair ? c->opt.head_pair - 1u : 3u;
     if ((e = pgrc_copmem_build_index(c, c->stream, 0, pair))) return e;
-    if (!two) mark(); // 2
+    if (!two) c->tm.mark(TM_FW_INDEX, c->stream);
     c->build_set ^= 1;
     // (PGRC_TEST_NO_SECOND_INDEX: tests take the out-of-memory road without exhausting the device)
     e = c->opt.test_no_second_index ? PGRC_E_ALLOC : pgrc_copmem_build_index(c, two ? c->build.stream : c->stream, 1, pair);
-    if (two) {
-        if (hipEventRecord(c->build.ev[1], c->build.stream) != hipSuccess || hipStreamWaitEvent(c->stream, c->build.ev[1], 0) != hipSuccess) {
-            c->err = "index build streams";
-            return PGRC_E_DEVICE;
-        }
-        mark(); // 2: both indexes (ms_index[0] is then the pair, ms_index[1] ~ 0)
+    if (two && (hipEventRecord(c->build.ev[1], c->build.stream) != hipSuccess || hipStreamWaitEvent(c->stream, c->build.ev[1], 0) != hipSuccess)) {
+        c->err = "index build streams";
+        return PGRC_E_DEVICE;
     }
+    if (two || !e) c->tm.mark(TM_BOTH_INDEXES, c->stream);
     return e;
 }
 
@@ -928,14 +929,15 @@ bool pgrc_dual_applies(const pgrc_match_ctx *c) {
     probe.prm = c->prm;
     probe.opt = c->opt;
     probe.cp = c->cp;
-    probe.n = 1;
+    probe.rd.n = 1;
     probe.screen_broken = c->screen_broken;
     return dual_wanted(&probe, 0, 1);
 }
 
 // pgrc_match_prepare_index / pgrc_match_stream_begin (stream.hip): both strands' indexes now, on their streams
 int pgrc_prepare_both_indexes(pgrc_match_ctx *c) {
-    const int e = pgrc_build_both_indexes(c, []() {});
+    c->tm.begin(false);                       // (not a run: nothing is timed)
+    const int e = pgrc_build_both_indexes(c);
     if (e == PGRC_E_ALLOC) {
         pgrc_index_retreat(c);
         c->err = "prepare_index: no room for both strands' indexes";
@@ -944,161 +946,168 @@ int pgrc_prepare_both_indexes(pgrc_match_ctx *c) {
     return e;
 }
 
-// what a run that kept both indexes counted apart (d_counters + 24), into c->ctr: the dual kernel's nine counters, or the
-// screen's work
+// A run begins: the device counter block and c->ctr are zero (queued on the main stream)
+int pgrc_counters_clear(pgrc_match_ctx *c) {
+    HIP_TRY(c, hipMemsetAsync(c->res.d_counters.p, 0, sizeof(PgrcDevCounters), c->stream));
+    memset(&c->ctr, 0, sizeof c->ctr);
+    return PGRC_OK;
+}
+
+// what a run that kept both indexes counted apart, into c->ctr: the dual kernel's nine counters, or the screen's work
 int pgrc_fetch_schedule_counters(pgrc_match_ctx *c, bool dual) {
-    uint64_t scr[9];
-    HIP_TRY(c, hipMemcpy(scr, (const uint64_t *)c->d_counters.p + 24, sizeof scr, hipMemcpyDeviceToHost));
+    PgrcDualCounters h;
+    HIP_TRY(c, hipMemcpy(&h, &((const PgrcDevCounters *)c->res.d_counters.p)->sched, sizeof h, hipMemcpyDeviceToHost));
     if (dual) {
-        for (int k = 0; k < 5; k++) c->ctr.dual[k] = scr[k];
-        c->ctr.redo_reads = scr[5];
-        c->ctr.dual_seed_probes = scr[6];
-        c->ctr.dual_skip_reads = scr[7];
-        c->ctr.dual_rewinds = scr[8];
+        c->ctr.dual[0] = h.w.searched;
+        c->ctr.dual[1] = h.w.candidates;
+        c->ctr.dual[2] = h.w.probes;
+        c->ctr.dual[3] = h.w.entry_fetches;
+        c->ctr.dual[4] = h.w.verifies;
+        c->ctr.redo_reads = h.redo;
+        c->ctr.dual_seed_probes = h.seed_probes;
+        c->ctr.dual_skip_reads = h.skip_reads;
+        c->ctr.dual_rewinds = h.rewinds;
         c->ctr.screened = 2;
     } else {                         // the screen ran on the RC text: its work counts with that strand's (not "searched")
-        c->ctr.candidates[1] += scr[1];
-        c->ctr.probes[1] += scr[2];
-        c->ctr.entry_fetches[1] += scr[3];
-        c->ctr.verifies[1] += scr[4];
+        c->ctr.candidates[1] += h.w.candidates;
+        c->ctr.probes[1] += h.w.probes;
+        c->ctr.entry_fetches[1] += h.w.entry_fetches;
+        c->ctr.verifies[1] += h.w.verifies;
         c->ctr.screened = 1;
     }
     return PGRC_OK;
+}
+
+// The ms_* fields of a run that is through, from the boundaries it marked (PgrcBoundary, ctx.h; a span with an end that
+// was not marked is 0).  Three layouts in mode c; modes d / i / e have the total only.
+//   both indexes kept (screened; fallback: the second found no room, then the two passes in turn): the forward index is
+//     RC text .. forward index (builds in turn) or .. both indexes (on two streams: the pair; prepared ahead: the wait)
+//   plain passes: per strand, begin .. index .. matched
+static void run_phase_times(pgrc_match_ctx *c, bool screened, bool fallback) {
+    const PgrcRunTimer &t = c->tm;
+    pgrc_match_counters &r = c->ctr;
+    const auto pass = [](int strand, int b) { return b + 3 * strand; };
+    if (screened || fallback) r.ms_index[0] = t.ms(TM_RC_TEXT, t.has(TM_FW_INDEX) ? TM_FW_INDEX : TM_BOTH_INDEXES);
+    if (screened) {
+        r.ms_index[1] = t.ms(TM_FW_INDEX, TM_BOTH_INDEXES);
+        r.ms_screen = t.ms(TM_BOTH_INDEXES, TM_SCHEDULE);
+        // screen: the forward pass honouring the flags, the RC pass over what is left; dual kernel: what the reads with N
+        // took beyond it, and nothing
+        r.ms_match[0] = t.ms(TM_SCHEDULE, pass(0, TM_PASS_MATCHED));
+        r.ms_match[1] = t.ms(pass(0, TM_PASS_MATCHED), pass(1, TM_PASS_MATCHED));
+    } else if (fallback) {
+        r.ms_match[0] = t.ms(pass(0, TM_PASS_BEGIN), pass(0, TM_PASS_MATCHED));
+        r.ms_index[1] = t.ms(pass(0, TM_PASS_MATCHED), pass(1, TM_PASS_INDEX));
+        r.ms_match[1] = t.ms(pass(1, TM_PASS_INDEX), pass(1, TM_PASS_MATCHED));
+    } else {
+        for (int s = 0; s < 2; s++) {
+            r.ms_index[s] = t.ms(pass(s, TM_PASS_BEGIN), pass(s, TM_PASS_INDEX));
+            r.ms_match[s] = t.ms(pass(s, TM_PASS_INDEX), pass(s, TM_PASS_MATCHED));
+        }
+    }
+    r.ms_total = t.ms(TM_RUN_START, TM_RUN_END);
+    r.ms_other = r.ms_total - r.ms_index[0] - r.ms_index[1] - r.ms_match[0] - r.ms_match[1] - r.ms_screen;
 }
 
 extern "C" {
 static int run_passes(pgrc_match_ctx *c, int first, int last) {
     if (!c) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_run(c, first, last);
-    if (!c->have_pg || !c->have_reads) { c->err = "run: set the pseudogenome and the reads first"; return PGRC_E_STATE; }
+    if (!c->txt.have_pg || !c->rd.have_reads) { c->err = "run: set the pseudogenome and the reads first"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     int e;
-    if (!c->have_results && (e = pgrc_match_init_results(c))) return e;
-    HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, 40 * sizeof(uint64_t), c->stream));
-    memset(&c->ctr, 0, sizeof c->ctr);
-    const bool prof = c->profiling && c->have_events;
-    int evi = 0;
-    auto mark = [&]() { if (prof) (void)hipEventRecord(c->ev[evi], c->stream); evi++; };
-    mark(); // 0
-    bool fallback_layout = false;
+    if (!c->res.have_results && (e = pgrc_match_init_results(c))) return e;
+    if ((e = pgrc_counters_clear(c))) return e;
+    PgrcRunTimer &tm = c->tm;
+    const auto pass = [](int strand, int b) { return b + 3 * strand; };
+    tm.begin(c->profiling);
+    tm.mark(TM_RUN_START, c->stream);
+    bool fallback = false;
     const bool dual = dual_wanted(c, first, last);
     bool screened = dual || screen_wanted(c, first, last);
-    if (screened && ((e = pgrc_buf_ensure(c, c->d_scr_pos, c->n * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, c->d_scr_flag, c->n)))) {
+    if (screened && ((e = pgrc_buf_ensure(c, c->res.d_scr_pos, c->rd.n * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, c->res.d_scr_flag, c->rd.n)))) {
         if (e != PGRC_E_ALLOC) return e;
         (void)hipGetLastError();
         c->screen_broken = true;
         screened = false;
     }
     if (screened) {
-        if (c->idx_prepared && pgrc_index_pair_ready(c) && c->have_rc) {
+        if (c->idx_prepared && pgrc_index_pair_ready(c) && c->txt.have_rc) {
             // both indexes were built ahead of the run (pgrc_match_prepare_index): the builds may still be in flight on
             // their streams; this run's work is ordered behind them
             c->idx_prepared = false;
-            mark(); // 1
+            tm.mark(TM_RC_TEXT, c->stream);
             if (c->build.stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->build.ev[1], 0));
-            mark(); // 2
+            tm.mark(TM_BOTH_INDEXES, c->stream);
             e = PGRC_OK;
         } else {
-            e = pgrc_build_both_indexes(c, [&]() { mark(); });
+            e = pgrc_build_both_indexes(c);
         }
         if (e == PGRC_E_ALLOC) {
             // no room for both indexes: give back what the second set got, and run the passes in the reference's order
             pgrc_index_retreat(c);
             screened = false;
+            fallback = true;
             // (the forward index is gone when it was the one that found no room, or when its heads sat in the pair table: once
             //  more, into a table of its own -- if that does not fit either, the run fails with PGRC_E_ALLOC)
             if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, c->stream, 0))) return e;
-            mark(); // 3
+            tm.mark(pass(0, TM_PASS_BEGIN), c->stream);
             if ((e = pgrc_copmem_match_pass(c, 0))) return e;
-            mark(); // 4
+            tm.mark(pass(0, TM_PASS_MATCHED), c->stream);
             if ((e = pgrc_copmem_build_index(c, c->stream, 1))) return e;
-            mark(); // 5
+            tm.mark(pass(1, TM_PASS_INDEX), c->stream);
             if ((e = pgrc_copmem_match_pass(c, 1))) return e;
-            mark(); // 6
-            fallback_layout = true;  // (events: see the timing below)
+            tm.mark(pass(1, TM_PASS_MATCHED), c->stream);
         } else {
             if (e) return e;
-            mark(); // 3
-            HIP_TRY(c, hipMemsetAsync(c->d_scr_flag.p, 0, c->n, c->stream));
+            HIP_TRY(c, hipMemsetAsync(c->res.d_scr_flag.p, 0, c->rd.n, c->stream));
             if (dual) {
                 // the reads with N: those with at most 4 N's are the dual kernel's own (its N-aware hash and verification);
                 // the others go the byte path on the side stream, a read's forward query and then its RC query in one lane,
                 // behind the dual kernel.  (Launched first, as a small persistent grid, that kernel still only starts when the
                 //  dual kernel's persistent blocks leave -- profiles/r04_nread_beside_ab.txt)
                 if ((e = pgrc_copmem_match_dual(c))) return e;             // one query per read over both strands
-                mark(); // 4
+                tm.mark(TM_SCHEDULE, c->stream);
                 if ((e = pgrc_copmem_match_nreads(c, 0, 1, true))) return e;
                 if ((e = pgrc_copmem_join_nreads(c))) return e;
-                mark(); // 5: what the reads with N took beyond the dual kernel
-                mark(); // 6
+                tm.mark(pass(0, TM_PASS_MATCHED), c->stream);              // what the reads with N took beyond the dual kernel
             } else {
                 if ((e = pgrc_copmem_match_phase(c, 1, 1))) return e;      // screen on the RC text
-                mark(); // 4
+                tm.mark(TM_SCHEDULE, c->stream);
                 if ((e = pgrc_copmem_match_phase(c, 0, 2))) return e;      // forward pass honouring the flags
-                mark(); // 5
+                tm.mark(pass(0, TM_PASS_MATCHED), c->stream);
                 if ((e = pgrc_copmem_match_phase(c, 1, 0))) return e;      // RC pass over what is left
-                mark(); // 6
+                tm.mark(pass(1, TM_PASS_MATCHED), c->stream);
             }
         }
     } else if (c->prm.mode == 'c') {
-        for (int pass = first; pass <= last; pass++) {
-            if (pass == 1) {
-                // PgHelpers::reverseComplementInPlace(pgPtr), ReadsMatchers.cpp:168 -- rebuilt every run like the reference
-                if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
-                c->have_rc = true;
-            }
-            mark(); // 1 / 4
-            if ((e = pgrc_copmem_build_index(c, c->stream, pass))) return e;
-            mark(); // 2 / 5
-            if ((e = pgrc_copmem_match_pass(c, pass))) return e;
-            mark(); // 3 / 6
+        for (int s = first; s <= last; s++) {
+            if (s == 1 && (e = pgrc_make_rc_text(c, c->stream))) return e;
+            tm.mark(pass(s, TM_PASS_BEGIN), c->stream);
+            if ((e = pgrc_copmem_build_index(c, c->stream, s))) return e;
+            tm.mark(pass(s, TM_PASS_INDEX), c->stream);
+            if ((e = pgrc_copmem_match_pass(c, s))) return e;
+            tm.mark(pass(s, TM_PASS_MATCHED), c->stream);
         }
     } else {
         if ((e = pgrc_seedidx_run(c, first, last))) return e;
     }
     if ((e = pgrc_launch_hist(c))) return e; // synchronises the stream
-    mark();
-    uint64_t ctr[16];
-    HIP_TRY(c, hipMemcpy(ctr, c->d_counters.p, sizeof ctr, hipMemcpyDeviceToHost));
+    tm.mark(TM_RUN_END, c->stream);
+    PgrcDevCounters h;
+    HIP_TRY(c, hipMemcpy(h.pass, c->res.d_counters.p, sizeof h.pass, hipMemcpyDeviceToHost));
     for (int s = 0; s < 2 && c->prm.mode == 'c'; s++) {      // (modes d/i/e: pgrc_seedidx_run filled searched / candidates)
-        c->ctr.searched[s] = ctr[8 * s + 0];
-        c->ctr.candidates[s] = ctr[8 * s + 1];
-        c->ctr.probes[s] = ctr[8 * s + 2];
-        c->ctr.entry_fetches[s] = ctr[8 * s + 3];
-        c->ctr.verifies[s] = ctr[8 * s + 4];
+        c->ctr.searched[s] = h.pass[s].w.searched;
+        c->ctr.candidates[s] = h.pass[s].w.candidates;
+        c->ctr.probes[s] = h.pass[s].w.probes;
+        c->ctr.entry_fetches[s] = h.pass[s].w.entry_fetches;
+        c->ctr.verifies[s] = h.pass[s].w.verifies;
     }
     if (screened && (e = pgrc_fetch_schedule_counters(c, dual))) return e;
     c->ctr.schedule_downgraded = c->screen_broken ? 1u : 0u;
-    if (prof) {
-        HIP_TRY(c, hipEventSynchronize(c->ev[evi - 1]));
-        float ms = 0;
-        if (c->prm.mode == 'c' && (screened || fallback_layout)) {
-            // events: 1 start of the forward index, 2 its end; then (screened) RC index, screen, forward match, RC match
-            //         or (fallback) forward match, RC index, RC match
-            auto span = [&](int x, int y) { float t = 0; (void)hipEventElapsedTime(&t, c->ev[x], c->ev[y]); return t; };
-            c->ctr.ms_index[0] = span(1, 2);
-            if (screened) {
-                c->ctr.ms_index[1] = span(2, 3);
-                c->ctr.ms_screen = span(3, 4);
-                c->ctr.ms_match[0] = span(4, 5);
-                c->ctr.ms_match[1] = span(5, 6);
-            } else {
-                c->ctr.ms_match[0] = span(3, 4);
-                c->ctr.ms_index[1] = span(4, 5);
-                c->ctr.ms_match[1] = span(5, 6);
-            }
-        } else if (c->prm.mode == 'c') {
-            int b = 1;
-            for (int pass = first; pass <= last; pass++, b += 3) {
-                (void)hipEventElapsedTime(&ms, c->ev[b], c->ev[b + 1]);
-                c->ctr.ms_index[pass] = ms;
-                (void)hipEventElapsedTime(&ms, c->ev[b + 1], c->ev[b + 2]);
-                c->ctr.ms_match[pass] = ms;
-            }
-        }
-        (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[evi - 1]);
-        c->ctr.ms_total = ms;
-        c->ctr.ms_other = ms - c->ctr.ms_index[0] - c->ctr.ms_index[1] - c->ctr.ms_match[0] - c->ctr.ms_match[1] - c->ctr.ms_screen;
+    if (tm.on) {
+        HIP_TRY(c, hipEventSynchronize(tm.ev.ev[TM_RUN_END]));
+        run_phase_times(c, screened, fallback);
     }
     return PGRC_OK;
 }
@@ -1114,26 +1123,26 @@ int pgrc_match_run_pass(pgrc_match_ctx *c, int strand) {
 int pgrc_match_get_results(pgrc_match_ctx *c, uint64_t *pos, uint8_t *rc, uint8_t *mism, uint64_t hist[256], uint64_t *matched) {
     if (!c) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_get_results(c, pos, rc, mism, hist, matched);
-    if (!c->have_results) { c->err = "get_results: nothing computed"; return PGRC_E_STATE; }
+    if (!c->res.have_results) { c->err = "get_results: nothing computed"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->n) {
-        if (pos) HIP_TRY(c, hipMemcpy(pos, c->d_pos.p, c->n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        if (rc) HIP_TRY(c, hipMemcpy(rc, c->d_rc.p, c->n, hipMemcpyDeviceToHost));
-        if (mism) HIP_TRY(c, hipMemcpy(mism, c->d_mism.p, c->n, hipMemcpyDeviceToHost));
+    if (c->rd.n) {
+        if (pos) HIP_TRY(c, hipMemcpy(pos, c->res.d_pos.p, c->rd.n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (rc) HIP_TRY(c, hipMemcpy(rc, c->res.d_rc.p, c->rd.n, hipMemcpyDeviceToHost));
+        if (mism) HIP_TRY(c, hipMemcpy(mism, c->res.d_mism.p, c->rd.n, hipMemcpyDeviceToHost));
     }
-    if (hist) memcpy(hist, c->hist, sizeof c->hist);
-    if (matched) *matched = c->matched;
+    if (hist) memcpy(hist, c->res.hist, sizeof c->res.hist);
+    if (matched) *matched = c->res.matched;
     return PGRC_OK;
 }
 
 int pgrc_match_get_results_device(pgrc_match_ctx *c, void **d_pos, void **d_rc, void **d_mism) {
     if (!c) return PGRC_E_PARAM;
     if (c->multi) { c->err = "get_results_device: the results of a multi-device context live on several devices"; return PGRC_E_PARAM; }
-    if (!c->have_reads) { c->err = "get_results_device: no reads set"; return PGRC_E_STATE; }
-    if (d_pos) *d_pos = c->d_pos.p;
-    if (d_rc) *d_rc = c->d_rc.p;
-    if (d_mism) *d_mism = c->d_mism.p;
+    if (!c->rd.have_reads) { c->err = "get_results_device: no reads set"; return PGRC_E_STATE; }
+    if (d_pos) *d_pos = c->res.d_pos.p;
+    if (d_rc) *d_rc = c->res.d_rc.p;
+    if (d_mism) *d_mism = c->res.d_mism.p;
     return PGRC_OK;
 }
 
@@ -1177,11 +1186,11 @@ int pgrc_match_get_redo_flags(pgrc_match_ctx *c, uint8_t *flags) {
         }
         return PGRC_OK;
     }
-    if (!c->have_results) { c->err = "get_redo_flags: run first"; return PGRC_E_STATE; }
-    if (c->ctr.screened != 2) { memset(flags, 0, c->n); return PGRC_OK; }     // no dual kernel in the last run: nothing was redone
+    if (!c->res.have_results) { c->err = "get_redo_flags: run first"; return PGRC_E_STATE; }
+    if (c->ctr.screened != 2) { memset(flags, 0, c->rd.n); return PGRC_OK; }     // no dual kernel in the last run: nothing was redone
     PGRC_ON_DEVICE(c);
-    HIP_TRY(c, hipMemcpy(flags, c->d_scr_flag.p, c->n, hipMemcpyDeviceToHost));
-    for (uint64_t i = 0; i < c->n; i++) flags[i] = flags[i] >> 1;
+    HIP_TRY(c, hipMemcpy(flags, c->res.d_scr_flag.p, c->rd.n, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < c->rd.n; i++) flags[i] = flags[i] >> 1;
     return PGRC_OK;
 }
 
@@ -1189,7 +1198,7 @@ int pgrc_match_extract_mismatches(pgrc_match_ctx *c, const uint8_t *reversed_fla
                                   uint16_t *offsets) {
     if (!c || !cum) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_extract_mismatches(c, reversed_flags, cum, codes, offsets);
-    if (!c->have_results || !c->have_pg) { c->err = "extract_mismatches: run first"; return PGRC_E_STATE; }
+    if (!c->res.have_results || !c->txt.have_pg) { c->err = "extract_mismatches: run first"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     return pgrc_extract_mismatches(c, reversed_flags, cum, codes, offsets);
 }
@@ -1197,13 +1206,10 @@ int pgrc_match_extract_mismatches(pgrc_match_ctx *c, const uint8_t *reversed_fla
 int pgrc_match_export_index(pgrc_match_ctx *c, int strand, uint32_t *cumm, uint32_t *positions, uint64_t *count) {
     if (!c || strand < 0 || strand > 1) return PGRC_E_PARAM;
     if (c->multi) return pgrc_multi_export_index(c, strand, cumm, positions, count);
-    if (!c->have_pg || c->prm.mode != 'c') { c->err = "export_index: mode c with a pseudogenome only"; return PGRC_E_STATE; }
+    if (!c->txt.have_pg || c->prm.mode != 'c') { c->err = "export_index: mode c with a pseudogenome only"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     int e;
-    if (strand == 1 && !c->have_rc) {
-        if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
-        c->have_rc = true;
-    }
+    if (strand == 1 && (e = pgrc_need_rc_text(c))) return e;
     if (!pgrc_index_of(c, strand) && (e = pgrc_copmem_build_index(c, c->stream, strand))) return e;
     return pgrc_copmem_export_index(c, strand, cumm, positions, count);
 }

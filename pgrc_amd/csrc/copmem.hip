@@ -93,7 +93,7 @@ int pgrc_copmem_build_index(pgrc_match_ctx *c, hipStream_t stream, int strand, b
     PgrcIndexSet &ix = pgrc_build_set(c);
     const uint32_t K = (uint32_t)c->cp.K, k1 = (uint32_t)c->cp.k1;
     const uint64_t hs = c->cp.hash_size;
-    c->npos = (c->G >= K) ? (c->G - K) / k1 + 1 : 0;
+    c->npos = (c->txt.G >= K) ? (c->txt.G - K) / k1 + 1 : 0;
     const uint64_t npos = c->npos;
     int e;
     if (into_pair_table) {           // both strands' heads in one table of 32-byte slots (ctx.h)
@@ -158,7 +158,7 @@ k_export_positions(const ulonglong2 *__restrict__ head, uint32_t hsh, const uint
 }
 
 int pgrc_copmem_export_index(pgrc_match_ctx *c, int strand, uint32_t *h_cumm, uint32_t *h_positions, uint64_t *count) {
-    if (c->G >= (1ull << 32)) { c->err = "export_index: 32-bit positions only (test helper)"; return PGRC_E_PARAM; }
+    if (c->txt.G >= (1ull << 32)) { c->err = "export_index: 32-bit positions only (test helper)"; return PGRC_E_PARAM; }
     const PgrcIndexSet *ix = pgrc_index_of(c, strand);
     if (!ix) { c->err = "export_index: no index of that strand"; return PGRC_E_STATE; }
     const uint64_t hs = c->cp.hash_size;
@@ -207,7 +207,7 @@ struct MatchArgs {
     const uint64_t *ent;
     uint64_t *pos;
     uint8_t *rc, *mism;
-    unsigned long long *counters; // [0] searched [1] candidates [2] probes
+    PgrcWorkCounters *counters;   // (matchdev.h)
     unsigned long long *work;     // global read cursor of the persistent match kernel
     uint32_t L, K, k2, mask, kmax, kmin, strand;
     uint32_t k1, early;           // sampling step of the index; early = 1: stop a read once nothing can be accepted any more
@@ -625,11 +625,11 @@ __global__ void __launch_bounds__(MATCH_TPB) k_copmem_match_sm(const MatchArgs a
     }
     if (a.counters) {
         if (lane == 0) {
-            atomicAdd(&a.counters[0], (unsigned long long)n_search);
-            atomicAdd(&a.counters[1], (unsigned long long)n_cand);
-            atomicAdd(&a.counters[2], (unsigned long long)n_probe);
-            atomicAdd(&a.counters[3], (unsigned long long)n_ent);
-            atomicAdd(&a.counters[4], (unsigned long long)n_ver);
+            atomicAdd(&a.counters->searched, (unsigned long long)n_search);
+            atomicAdd(&a.counters->candidates, (unsigned long long)n_cand);
+            atomicAdd(&a.counters->probes, (unsigned long long)n_probe);
+            atomicAdd(&a.counters->entry_fetches, (unsigned long long)n_ent);
+            atomicAdd(&a.counters->verifies, (unsigned long long)n_ver);
         }
     }
 }
@@ -650,7 +650,7 @@ struct NStrandArgs {
     const ulonglong2 *head;       // headfmt.h
     uint32_t hsh;
     const uint64_t *ent;
-    unsigned long long *counters; // [0] searched [1] candidates [2] probes (added to the strand's pass counters)
+    PgrcWorkCounters *counters;   // searched, candidates and probes are added to the strand's pass counters
 };
 struct NReadArgs {
     NStrandArgs st[2];
@@ -816,9 +816,9 @@ __global__ void __launch_bounds__(NREAD_TPB) k_copmem_match_n(const NReadArgs a)
         if (!a.st[strand].counters) continue;
         const uint64_t s0 = wave_sum_u64(n_srch[strand]), s1 = wave_sum_u64(n_cand[strand]), s2 = wave_sum_u64(n_probe[strand]);
         if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&a.st[strand].counters[0], (unsigned long long)s0);
-            atomicAdd(&a.st[strand].counters[1], (unsigned long long)s1);
-            atomicAdd(&a.st[strand].counters[2], (unsigned long long)s2);
+            atomicAdd(&a.st[strand].counters->searched, (unsigned long long)s0);
+            atomicAdd(&a.st[strand].counters->candidates, (unsigned long long)s1);
+            atomicAdd(&a.st[strand].counters->probes, (unsigned long long)s2);
         }
     }
 }
@@ -833,7 +833,7 @@ static void launch_dual(pgrc_match_ctx *c, const DualArgs &a) {
     // A persistent grid: more blocks than fit (six per CU at 150 bp) simply queue.
     const uint32_t per_cu = 8u;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)c->num_cus * per_cu);
-    const bool pos64 = c->G + 256 >= (1ull << 32) || c->opt.force_pos64;
+    const bool pos64 = c->txt.G + 256 >= (1ull << 32) || c->opt.force_pos64;
     const bool k28 = a.K == 28;
     if (pos64) {
         if (k28) hipLaunchKernelGGL((k_copmem_match_dual<NW, 7, true, WAVES>), dim3(grid), dim3(MATCH_TPB), 0, c->stream, a);
@@ -847,34 +847,35 @@ static void launch_dual(pgrc_match_ctx *c, const DualArgs &a) {
 // The dual kernel over the reads without N of a range: it needs a set for either strand, both with their heads in the same
 // kind of table.  The reads with more N's than it takes follow on the byte path (pgrc_copmem_match_nreads).
 int pgrc_copmem_match_dual(pgrc_match_ctx *c, PgrcReadRange range) {
-    const uint64_t lo = std::min<uint64_t>(range.lo, c->n), rn = std::min<uint64_t>(c->n - lo, range.n);
+    const uint64_t lo = std::min<uint64_t>(range.lo, c->rd.n), rn = std::min<uint64_t>(c->rd.n - lo, range.n);
     if (rn == 0) return PGRC_OK;
     const PgrcIndexSet *fw = pgrc_index_of(c, 0), *rv = pgrc_index_of(c, 1);
-    if (!pgrc_index_pair_ready(c) || !c->d_scr_pos.p || !c->d_scr_flag.p) {
+    if (!pgrc_index_pair_ready(c) || !c->res.d_scr_pos.p || !c->res.d_scr_flag.p) {
         c->err = "dual kernel without both indexes";
         return PGRC_E_STATE;
     }
     DualArgs a;
-    a.pg[0] = (const uint32_t *)c->pg2[0].p;
-    a.pg[1] = (const uint32_t *)c->pg2[1].p;
-    a.G = c->G;
-    a.reads = c->reads2 + lo;
+    a.pg[0] = (const uint32_t *)c->txt.pg2[0].p;
+    a.pg[1] = (const uint32_t *)c->txt.pg2[1].p;
+    a.G = c->txt.G;
+    a.reads = c->rd.reads2 + lo;
     a.n = rn;
-    a.stride = c->stride;
-    a.nflag = (c->n_nreads || c->up.open) ? (const uint8_t *)c->nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
+    a.stride = c->rd.stride;
+    a.nflag = (c->rd.n_nreads || c->up.open) ? (const uint8_t *)c->rd.nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
     // PGRC_NREAD_INLINE=0: every read with an N goes the byte path (A/B runs, tests)
-    a.npos = (a.nflag && c->opt.nread_inline && c->nread_npos.p) ? (const uint32_t *)c->nread_npos.p + lo : nullptr;
+    a.npos = (a.nflag && c->opt.nread_inline && c->rd.nread_npos.p) ? (const uint32_t *)c->rd.nread_npos.p + lo : nullptr;
     a.head[0] = (const ulonglong2 *)fw->head_ptr;
     a.head[1] = (const ulonglong2 *)rv->head_ptr;
     a.hsh = fw->head_sh;
     a.ent[0] = fw->ent;
     a.ent[1] = rv->ent;
-    a.pos = (uint64_t *)c->d_pos.p + lo;
-    a.rc = (uint8_t *)c->d_rc.p + lo;
-    a.mism = (uint8_t *)c->d_mism.p + lo;
-    a.counters = (unsigned long long *)c->d_counters.p + 24;
-    a.work = (unsigned long long *)c->d_counters.p + 18;
-    a.redo_flag = (uint8_t *)c->d_scr_flag.p + lo;     // (zeroed by the caller; the screen's own use of it is another schedule)
+    a.pos = (uint64_t *)c->res.d_pos.p + lo;
+    a.rc = (uint8_t *)c->res.d_rc.p + lo;
+    a.mism = (uint8_t *)c->res.d_mism.p + lo;
+    PgrcDevCounters *dc = (PgrcDevCounters *)c->res.d_counters.p;
+    a.counters = &dc->sched;
+    a.work = &dc->cursor[2];
+    a.redo_flag = (uint8_t *)c->res.d_scr_flag.p + lo;     // (zeroed by the caller; the screen's own use of it is another schedule)
     a.chunk = pgrc_match_chunk(c, rn);
     a.L = c->prm.read_len;
     a.K = (uint32_t)c->cp.K;
@@ -884,7 +885,7 @@ int pgrc_copmem_match_dual(pgrc_match_ctx *c, PgrcReadRange range) {
     a.kmax = c->prm.max_mismatches;
     a.skip = c->opt.round_skip ? 1u : 0u;                // PGRC_ROUND_SKIP=0: every seed up to the early stop (A/B runs, tests)
     a.pack = c->opt.dual_pack ? 1u : 0u;                 // PGRC_DUAL_PACK=0: three stores per finished read and no unpack pass (A/B runs, tests)
-    switch (c->nw) {
+    switch (c->rd.nw) {
 #define CASE_NW(N) case N: launch_dual<N>(c, a); break;
         CASE_NW(2) CASE_NW(3) CASE_NW(4) CASE_NW(5) CASE_NW(6) CASE_NW(7) CASE_NW(8) CASE_NW(9)
         CASE_NW(10) CASE_NW(11) CASE_NW(12) CASE_NW(13) CASE_NW(14) CASE_NW(15) CASE_NW(16)
@@ -905,7 +906,7 @@ static void launch_match(pgrc_match_ctx *c, const MatchArgs &a) {
     // persistent grid: what the chip can hold (8 blocks of 4 waves per CU is the register/LDS limit at most)
     const uint64_t want = (a.n + MATCH_TPB - 1) / MATCH_TPB;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)c->num_cus * 8u);
-    const bool pos64 = c->G + 256 >= (1ull << 32) || c->opt.force_pos64;   // (PGRC_FORCE_POS64: the 64-bit-position kernel on a small text)
+    const bool pos64 = c->txt.G + 256 >= (1ull << 32) || c->opt.force_pos64;   // (PGRC_FORCE_POS64: the 64-bit-position kernel on a small text)
     const bool k28 = a.K == 28;                   // the default seed: compile-time hash loop
     // PGRC_MATCH_STAGE=0: every refilling lane loads its own read (A/B knob; staged is 1.8 % faster on C3, same context)
     const bool staged = c->opt.match_stage;
@@ -929,27 +930,27 @@ static void launch_match(pgrc_match_ctx *c, const MatchArgs &a) {
 // (pgrc_copmem_join_nreads).  Every strand asked for must have its index set in the context.  (Launched BEFORE the
 // dual kernel as a small persistent grid it still only starts when that kernel's blocks leave: profiles/r04_nread_beside_ab.txt.)
 int pgrc_copmem_match_nreads(pgrc_match_ctx *c, int first, int last, bool only_many, hipEvent_t after) {
-    if (!c->n_nreads) return PGRC_OK;
+    if (!c->rd.n_nreads) return PGRC_OK;
     if (!c->opt.nread_inline) only_many = false;
-    if (only_many && !c->n_many) return PGRC_OK;                        // (the dual kernel takes every read with at most 4 N's)
+    if (only_many && !c->rd.n_many) return PGRC_OK;                        // (the dual kernel takes every read with at most 4 N's)
     NReadArgs a;
-    a.skip_flag = only_many ? (const uint8_t *)c->nread_flag.p : nullptr;
+    a.skip_flag = only_many ? (const uint8_t *)c->rd.nread_flag.p : nullptr;
     for (int s = first; s <= last; s++) {
         const PgrcIndexSet *ix = pgrc_index_of(c, s);
         if (!ix) { c->err = "reads with N: no index of that strand"; return PGRC_E_STATE; }
-        a.st[s].pg = (const uint32_t *)c->pg2[s].p;
+        a.st[s].pg = (const uint32_t *)c->txt.pg2[s].p;
         a.st[s].head = ix->head_ptr;
         a.st[s].hsh = ix->head_sh;
         a.st[s].ent = ix->ent;
-        a.st[s].counters = (unsigned long long *)c->d_counters.p + 8 * s;
+        a.st[s].counters = &((PgrcDevCounters *)c->res.d_counters.p)->pass[s].w;
     }
-    a.G = c->G;
-    a.pos = (uint64_t *)c->d_pos.p;
-    a.rc = (uint8_t *)c->d_rc.p;
-    a.mism = (uint8_t *)c->d_mism.p;
-    a.nidx = (const uint32_t *)c->nread_idx.p;
-    a.nascii = (const uint8_t *)c->nread_ascii.p;
-    a.nn = c->n_nreads;
+    a.G = c->txt.G;
+    a.pos = (uint64_t *)c->res.d_pos.p;
+    a.rc = (uint8_t *)c->res.d_rc.p;
+    a.mism = (uint8_t *)c->res.d_mism.p;
+    a.nidx = (const uint32_t *)c->rd.nread_idx.p;
+    a.nascii = (const uint8_t *)c->rd.nread_ascii.p;
+    a.nn = c->rd.n_nreads;
     a.L = c->prm.read_len;
     a.K = (uint32_t)c->cp.K;
     a.k1 = (uint32_t)c->cp.k1;
@@ -967,9 +968,9 @@ int pgrc_copmem_match_nreads(pgrc_match_ctx *c, int first, int last, bool only_m
         HIP_TRY(c, hipEventRecord(c->side.ev[0], c->stream));           // the index (and the previous pass) are complete
         HIP_TRY(c, hipStreamWaitEvent(c->side.stream, c->side.ev[0], 0));
     }
-    const uint64_t tiles = (c->n_nreads + NREAD_TPB - 1) / NREAD_TPB;
+    const uint64_t tiles = (c->rd.n_nreads + NREAD_TPB - 1) / NREAD_TPB;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)c->num_cus * 64u);   // whatever fits
-    const uint32_t lds = 2u * ((uint32_t)c->nw + 1u) * NREAD_TPB * (uint32_t)sizeof(uint32_t);
+    const uint32_t lds = 2u * ((uint32_t)c->rd.nw + 1u) * NREAD_TPB * (uint32_t)sizeof(uint32_t);
     hipLaunchKernelGGL(k_copmem_match_n, dim3(grid), dim3(NREAD_TPB), lds, c->side.stream, a);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->side.ev[1], c->side.stream));
@@ -978,7 +979,7 @@ int pgrc_copmem_match_nreads(pgrc_match_ctx *c, int first, int last, bool only_m
 
 // the main stream goes on when the reads with N are done
 int pgrc_copmem_join_nreads(pgrc_match_ctx *c) {
-    if (c->n_nreads && c->side.stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->side.ev[1], 0));
+    if (c->rd.n_nreads && c->side.stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->side.ev[1], 0));
     return PGRC_OK;
 }
 
@@ -986,28 +987,29 @@ int pgrc_copmem_match_pass(pgrc_match_ctx *c, int strand) { return pgrc_copmem_m
 
 // phase: 0 = a plain pass; 1 / 2 = the screen and the flag-honouring forward pass of the screened schedule (kernel comment)
 int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase, PgrcReadRange range) {
-    const uint64_t lo = std::min<uint64_t>(range.lo, c->n), rn = std::min<uint64_t>(c->n - lo, range.n);
+    const uint64_t lo = std::min<uint64_t>(range.lo, c->rd.n), rn = std::min<uint64_t>(c->rd.n - lo, range.n);
     if (rn == 0) return PGRC_OK;
     const PgrcIndexSet *ix = pgrc_index_of(c, strand);
     if (!ix) { c->err = "match pass: no index of that strand"; return PGRC_E_STATE; }
     MatchArgs a;
-    a.pg = (const uint32_t *)c->pg2[strand].p;
-    a.G = c->G;
-    a.reads = c->reads2 + lo;
+    a.pg = (const uint32_t *)c->txt.pg2[strand].p;
+    a.G = c->txt.G;
+    a.reads = c->rd.reads2 + lo;
     a.n = rn;
-    a.stride = c->stride;
-    a.nflag = (c->n_nreads || c->up.open) ? (const uint8_t *)c->nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
+    a.stride = c->rd.stride;
+    a.nflag = (c->rd.n_nreads || c->up.open) ? (const uint8_t *)c->rd.nread_flag.p + lo : nullptr;   // (during an upload the side list is not final yet: the flags are)
     a.head = (const ulonglong2 *)ix->head_ptr;
     a.hsh = ix->head_sh;
     a.ent = ix->ent;
-    a.pos = (uint64_t *)c->d_pos.p + lo;
-    a.rc = (uint8_t *)c->d_rc.p + lo;
-    a.mism = (uint8_t *)c->d_mism.p + lo;
-    a.counters = (unsigned long long *)c->d_counters.p + (phase == 1 ? 24 : 8 * strand);   // the screen counts apart
-    a.work = (unsigned long long *)c->d_counters.p + (phase == 1 ? 18 : 16 + strand);
+    a.pos = (uint64_t *)c->res.d_pos.p + lo;
+    a.rc = (uint8_t *)c->res.d_rc.p + lo;
+    a.mism = (uint8_t *)c->res.d_mism.p + lo;
+    PgrcDevCounters *dc = (PgrcDevCounters *)c->res.d_counters.p;
+    a.counters = phase == 1 ? &dc->sched.w : &dc->pass[strand].w;   // the screen counts apart
+    a.work = &dc->cursor[phase == 1 ? 2 : strand];
     a.phase = (uint32_t)phase;
-    a.scr_pos = c->d_scr_pos.p ? (uint64_t *)c->d_scr_pos.p + lo : nullptr;
-    a.scr_flag = c->d_scr_flag.p ? (uint8_t *)c->d_scr_flag.p + lo : nullptr;
+    a.scr_pos = c->res.d_scr_pos.p ? (uint64_t *)c->res.d_scr_pos.p + lo : nullptr;
+    a.scr_flag = c->res.d_scr_flag.p ? (uint8_t *)c->res.d_scr_flag.p + lo : nullptr;
     if (phase && (!a.scr_flag || !a.scr_pos)) { c->err = "screened schedule without its buffers"; return PGRC_E_STATE; }
 
     a.L = c->prm.read_len;
@@ -1024,12 +1026,12 @@ int pgrc_copmem_match_phase(pgrc_match_ctx *c, int strand, int phase, PgrcReadRa
     // main kernel, whose persistent blocks simply take the remaining slots; the two kernels write disjoint reads.
     // (the screen only flags reads; reads with N are never flagged.  The N kernel walks the side list, whose indexes
     //  count from read 0: it runs on whole-set launches only, never on a block of a streamed run)
-    const bool with_n = c->n_nreads && phase != 1 && !range.skip_n && lo == 0 && rn == c->n;
+    const bool with_n = c->rd.n_nreads && phase != 1 && !range.skip_n && lo == 0 && rn == c->rd.n;
     if (with_n) {
         const int ne = pgrc_copmem_match_nreads(c, strand, strand, false);
         if (ne) return ne;
     }
-    switch (c->nw) {
+    switch (c->rd.nw) {
 #define CASE_NW(N) case N: launch_match<N>(c, a); break;
         CASE_NW(2) CASE_NW(3) CASE_NW(4) CASE_NW(5) CASE_NW(6) CASE_NW(7) CASE_NW(8) CASE_NW(9)
         CASE_NW(10) CASE_NW(11) CASE_NW(12) CASE_NW(13) CASE_NW(14) CASE_NW(15) CASE_NW(16)

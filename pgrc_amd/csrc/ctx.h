@@ -189,27 +189,52 @@ struct PgrcSeedBufs {
     DevBufList bufs() { return {&keys, &filter, &vals, &tab, &hits, &tmp, &sort, &seg, &hv, &hvu, &nmask, &best, &rows}; }
 };
 
-struct pgrc_match_ctx : PgrcDev {
-    PgrcOptions opt;                    // read from the environment by pgrc_match_create (see above)
+#define HIP_TRY(ctx, expr)                                                                   \
+    do {                                                                                     \
+        hipError_t e__ = (expr);                                                             \
+        if (e__ != hipSuccess) {                                                             \
+            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                 \
+            return pgrc_hip_code(e__);                                                       \
+        }                                                                                    \
+    } while (0)
 
-    // several devices behind this object (pgrc_match_create_multi): it is then only the front, the work happens in
-    // one child context per device
-    pgrc_multi *multi = nullptr;
-    void *export_view = nullptr;        // multi-device front: the shards' results gathered on the first device (export.hip)
-    pgrc_match_ctx *export_front = nullptr;   // set in that gathered view: the front whose shards hold the reads (mismatch lists per shard)
+static float dec_elapsed(hipEvent_t a, hipEvent_t b) {       // 0 if either event was never recorded
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return ms;
+}
 
-    pgrc_match_params prm{};
-    int num_cus = 256;
-    PgrcAuxStream<2> side;              // the kernel for reads with N runs beside the main match kernel: ev[0] "the main stream is
-                                        // ready for it", ev[1] "it is done"
+// The timing events of a call's phases: made on first use, recorded on a stream, read in pairs, given back with the context
+template <int N>
+struct PhaseEvents {
+    hipEvent_t ev[N]{};
+    template <typename Ctx>     // (a PgrcDev, or the Pg-vs-Pg matcher's context with an error text of its own)
+    int ensure(Ctx *c) {
+        for (hipEvent_t &ev : this->ev)
+            if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+        return PGRC_OK;
+    }
+    hipError_t record(int k, hipStream_t stream) { return hipEventRecord(ev[k], stream); }
+    float ms(int a, int b) const { return dec_elapsed(ev[a], ev[b]); }
+    void release() {
+        for (hipEvent_t &ev : this->ev) {
+            if (ev) (void)hipEventDestroy(ev);
+            ev = nullptr;
+        }
+    }
+};
 
-    // pseudogenome
+// The text of a context: both strands as 2-bit words (the layout above)
+struct PgrcText {
     uint64_t G = 0;
-    uint64_t pg_words = 0;
+    uint64_t pg_words = 0;  // ceil(G / 16)
     DevBuf pg2[2];          // [0] forward, [1] reverse complement
     bool have_pg = false, have_rc = false;
+    DevBufList bufs() { return {&pg2[0], &pg2[1]}; }
+};
 
-    // reads
+// The read set of a context
+struct PgrcReadSet {
     uint64_t n = 0, stride = 0;
     uint32_t nw = 0;
     DevBuf reads_own;       // owned copy (set_reads_ascii / _packed)
@@ -224,14 +249,69 @@ struct pgrc_match_ctx : PgrcDev {
     DevBuf nread_npos;      // u32[n] four position bytes (0xFF = none) of the reads flagged 3 (pack.hip, k_npos_rows)
     uint64_t n_many = 0;    // reads flagged 1: more N's than the dual kernel takes
     std::vector<uint32_t> h_nidx; // host copy of nread_idx (ascending): modes d/i/e cut it per batch of reads
+    DevBufList bufs() { return {&reads_own, &nread_idx, &nread_ascii, &nread_flag, &nread_npos}; }
+};
 
-    PgrcUpload up;          // chunked upload (pgrc_match_begin_reads / _append_ / _end_)
-
-    // results
+// What a run leaves: the per-read results, their histogram, the device counter block (PgrcDevCounters, matchdev.h)
+struct PgrcResults {
     DevBuf d_pos, d_rc, d_mism, d_hist, d_counters;
+    DevBuf d_scr_pos, d_scr_flag;       // per read the flag / position the screen found (screened schedule and dual kernel)
     bool have_results = false;
     uint64_t hist[256]{};
     uint64_t matched = 0;
+    DevBufList bufs() { return {&d_pos, &d_rc, &d_mism, &d_hist, &d_counters, &d_scr_pos, &d_scr_flag}; }
+};
+
+// The boundaries between the timed phases of a run (pgrc_match_run / _run_pass, api.hip), each an event on the main stream.
+// Which of them a run marks depends on its schedule; the ms_* fields of pgrc_match_counters are spans between them
+// (run_phase_times, api.hip).
+enum PgrcBoundary {
+    TM_RUN_START,
+    TM_RC_TEXT,             // both indexes in one go: the RC text is made, the builds begin (prepared indexes: the wait for them)
+    TM_FW_INDEX,            // ... builds in turn only: the forward index is built
+    TM_BOTH_INDEXES,        // ... both are (builds on two streams: the main stream has waited for the second)
+    TM_SCHEDULE,            // the screen, or the dual kernel, is through the reads
+    TM_PASS_BEGIN,          // + 3 * strand: a pass of its own begins (the RC pass: its RC text is made),
+    TM_PASS_INDEX,          //               has its index,
+    TM_PASS_MATCHED,        //               is through the reads
+    TM_RUN_END = TM_PASS_BEGIN + 6,
+    TM_COUNT
+};
+// The timer of a run: made by pgrc_match_set_profiling, and off (nothing recorded) outside a run with profiling on
+struct PgrcRunTimer {
+    PhaseEvents<TM_COUNT> ev;
+    uint32_t marked = 0;    // the boundaries this run marked: an event of an earlier run with another schedule is not read
+    bool on = false;
+    int ensure(PgrcDev *c) { return ev.ensure(c); }
+    void begin(bool profiling) { on = profiling && ev.ev[0]; marked = 0; }
+    void mark(int b, hipStream_t stream) {
+        if (!on) return;
+        (void)ev.record(b, stream);
+        marked |= 1u << b;
+    }
+    bool has(int b) const { return marked >> b & 1u; }
+    float ms(int a, int b) const { return has(a) && has(b) ? ev.ms(a, b) : 0.f; }   // 0: not recorded
+};
+
+struct pgrc_match_ctx : PgrcDev {
+    PgrcOptions opt;                    // read from the environment by pgrc_match_create (see above)
+
+    // several devices behind this object (pgrc_match_create_multi): it is then only the front, the work happens in
+    // one child context per device
+    pgrc_multi *multi = nullptr;
+    void *export_view = nullptr;        // multi-device front: the shards' results gathered on the first device (export.hip)
+    pgrc_match_ctx *export_front = nullptr;   // set in that gathered view: the front whose shards hold the reads (mismatch lists per shard)
+
+    pgrc_match_params prm{};
+    int num_cus = 256;
+    PgrcAuxStream<2> side;              // the kernel for reads with N runs beside the main match kernel: ev[0] "the main stream is
+                                        // ready for it", ev[1] "it is done"
+
+    PgrcText txt;           // pseudogenome
+    PgrcReadSet rd;         // reads
+    PgrcUpload up;          // chunked upload (pgrc_match_begin_reads / _append_ / _end_)
+
+    PgrcResults res;        // per-read results, their histogram, the device counters
 
     // copMEM index (rebuilt per pass, buffers reused)
     pgrc_copmem_params cp{};
@@ -247,8 +327,6 @@ struct pgrc_match_ctx : PgrcDev {
     DevBuf d_headpair;                  // ulonglong2[2 * hash_size]
     uint32_t pair_gm = 3;               // pair table: buckets per group - 1 (a power of two minus one; headfmt.h)
     bool os_lds_allowed = false;        // idxsweep.hip's kernels were granted their dynamic LDS on this context's device
-    // per read the flag / position the screen found (screened schedule and dual kernel)
-    DevBuf d_scr_pos, d_scr_flag;
     bool screen_broken = false;         // no room for the second set: the passes run as the reference orders them
     PgrcAuxStream<2> build;             // the RC index is built beside the forward one: ev[0] "the RC text is ready", ev[1] "the
                                         // RC index is built" (pgrc_build_both_indexes, api.hip)
@@ -262,18 +340,8 @@ struct pgrc_match_ctx : PgrcDev {
     // profiling
     bool profiling = false;
     pgrc_match_counters ctr{};
-    hipEvent_t ev[16]{};
-    bool have_events = false;
+    PgrcRunTimer tm;
 };
-
-#define HIP_TRY(ctx, expr)                                                                   \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                 \
-            return pgrc_hip_code(e__);                                                       \
-        }                                                                                    \
-    } while (0)
 
 // Every ABI entry point runs on its context's device and leaves the caller's current device (e.g. torch's) as it
 // found it.
@@ -321,32 +389,6 @@ static int pgrc_bufs_unpooled(PgrcDev *c, std::initializer_list<std::pair<DevBuf
         if (int e = pgrc_buf_unpooled(c, *w.first, w.second)) return e;
     return PGRC_OK;
 }
-
-static float dec_elapsed(hipEvent_t a, hipEvent_t b) {       // 0 if either event was never recorded
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return ms;
-}
-
-// The timing events of a call's phases: made on first use, recorded on a stream, read in pairs, given back with the context
-template <int N>
-struct PhaseEvents {
-    hipEvent_t ev[N]{};
-    template <typename Ctx>     // (a PgrcDev, or the Pg-vs-Pg matcher's context with an error text of its own)
-    int ensure(Ctx *c) {
-        for (hipEvent_t &ev : this->ev)
-            if (!ev) HIP_TRY(c, hipEventCreate(&ev));
-        return PGRC_OK;
-    }
-    hipError_t record(int k, hipStream_t stream) { return hipEventRecord(ev[k], stream); }
-    float ms(int a, int b) const { return dec_elapsed(ev[a], ev[b]); }
-    void release() {
-        for (hipEvent_t &ev : this->ev) {
-            if (ev) (void)hipEventDestroy(ev);
-            ev = nullptr;
-        }
-    }
-};
 
 // api.hip: (re)allocates and clears both strands' text buffers for a text of G symbols
 extern "C" int pgrc_pg_alloc(pgrc_match_ctx *c, uint64_t G);
@@ -432,6 +474,9 @@ void pgrc_stream_release_bufs(pgrc_match_ctx *c, std::vector<DevBuf> &bufs);
 // PGRC_STREAM_TIMING: a milestone of the streamed run that is on, on stderr with the host time since stream_begin
 void pgrc_stream_mark(pgrc_match_ctx *c, const char *what);
 // api.hip
+int pgrc_make_rc_text(pgrc_match_ctx *c, hipStream_t stream);   // the RC text from the forward one, queued on `stream` (what every run does)
+int pgrc_need_rc_text(pgrc_match_ctx *c);                       // ... on the context's stream, and only if it is missing (the exports)
+int pgrc_counters_clear(pgrc_match_ctx *c);                     // a run begins: the device counter block and c->ctr are zero
 void pgrc_upload_close(pgrc_match_ctx *c);   // a begin .. end sequence that failed does not stay open: no reads until the next begin_reads
 int pgrc_prepare_both_indexes(pgrc_match_ctx *c);
 bool pgrc_dual_applies(const pgrc_match_ctx *c);

@@ -92,8 +92,7 @@ struct DualArgs {
     uint64_t *pos;
     uint8_t *rc;
     uint8_t *mism;
-    unsigned long long *counters; // [0] searched [1] candidates [2] heads probed [3] entry fetches [4] verifies [5] redo [6] seeds probed
-                                  // [7] reads that entered skip mode [8] rewinds
+    PgrcDualCounters *counters;   // (matchdev.h)
     unsigned long long *work;
     uint8_t *redo_flag;           // per read: 2 = done again in the reference's order (F_SEQ); introspection only
     uint32_t L, K, k1, k2, mask, kmax;
@@ -633,15 +632,15 @@ k_copmem_match_dual(const DualArgs a) {
         mode = next;
     }
     if (a.counters && lane == 0) {
-        atomicAdd(&a.counters[0], (unsigned long long)n_search);
-        atomicAdd(&a.counters[1], (unsigned long long)n_cand);
-        atomicAdd(&a.counters[2], (unsigned long long)n_probe);
-        atomicAdd(&a.counters[3], (unsigned long long)n_ent);
-        atomicAdd(&a.counters[4], (unsigned long long)n_ver);
-        atomicAdd(&a.counters[5], (unsigned long long)n_redo);
-        atomicAdd(&a.counters[6], (unsigned long long)n_seed);
-        atomicAdd(&a.counters[7], (unsigned long long)n_skip);
-        atomicAdd(&a.counters[8], (unsigned long long)n_rew);
+        atomicAdd(&a.counters->w.searched, (unsigned long long)n_search);
+        atomicAdd(&a.counters->w.candidates, (unsigned long long)n_cand);
+        atomicAdd(&a.counters->w.probes, (unsigned long long)n_probe);
+        atomicAdd(&a.counters->w.entry_fetches, (unsigned long long)n_ent);
+        atomicAdd(&a.counters->w.verifies, (unsigned long long)n_ver);
+        atomicAdd(&a.counters->redo, (unsigned long long)n_redo);
+        atomicAdd(&a.counters->seed_probes, (unsigned long long)n_seed);
+        atomicAdd(&a.counters->skip_reads, (unsigned long long)n_skip);
+        atomicAdd(&a.counters->rewinds, (unsigned long long)n_rew);
     }
 #undef DK_SI
 #undef DK_RQ

@@ -333,7 +333,7 @@ struct Bufs {
 static int mismatch_streams_from_shards(pgrc_match_ctx *view, Bufs &b, uint64_t ne, int pair_file, uint32_t width, uint64_t total) {
     pgrc_match_ctx *f = view->export_front;
     const std::vector<PgrcShardView> sh = pgrc_multi_shards(f);
-    const uint64_t n = view->n;
+    const uint64_t n = view->rd.n;
     DevBuf par, rev, cumAll, codesAll, offsAll;
     auto done = [&](int e) { DevBuf *all[] = {&par, &rev, &cumAll, &codesAll, &offsAll}; pgrc_buf_free_all(all, 5); return e; };
     int e;
@@ -344,7 +344,7 @@ static int mismatch_streams_from_shards(pgrc_match_ctx *view, Bufs &b, uint64_t 
     hipError_t he = hipMemsetAsync(par.p, 0, n ? n : 1, view->stream);
     if (he == hipSuccess && ne) {
         hipLaunchKernelGGL(k_ex_parity, dim3(grid_for(ne)), dim3(256), 0, view->stream, (const uint32_t *)b.eread.p, (const uint32_t *)b.eorg.p, ne, (uint8_t *)par.p);
-        if (n) hipLaunchKernelGGL(k_ex_revflags, dim3(grid_for(n)), dim3(256), 0, view->stream, (const uint8_t *)view->d_rc.p, (const uint8_t *)par.p, n,
+        if (n) hipLaunchKernelGGL(k_ex_revflags, dim3(grid_for(n)), dim3(256), 0, view->stream, (const uint8_t *)view->res.d_rc.p, (const uint8_t *)par.p, n,
                                   pair_file ? 1u : 0u, (uint8_t *)rev.p);
         he = hipGetLastError();
     }
@@ -434,15 +434,15 @@ static int finish_export(pgrc_match_ctx *c, Bufs &b, uint64_t ne, int pair_file,
     } else if (total) {
         if ((e = pgrc_buf_ensure(c, b.sym, total)) || (e = pgrc_buf_ensure(c, b.roff, total * width))) return e;
         MisArgs a;
-        a.pg = (const uint32_t *)c->pg2[0].p;
-        a.reads = c->reads2;
-        a.stride = c->stride;
-        a.nflag = c->n_nreads ? (const uint8_t *)c->nread_flag.p : nullptr;
-        a.nidx = (const uint32_t *)c->nread_idx.p;
-        a.nascii = (const uint8_t *)c->nread_ascii.p;
-        a.nn = c->n_nreads;
-        a.pos = (const uint64_t *)c->d_pos.p;
-        a.rc = (const uint8_t *)c->d_rc.p;
+        a.pg = (const uint32_t *)c->txt.pg2[0].p;
+        a.reads = c->rd.reads2;
+        a.stride = c->rd.stride;
+        a.nflag = c->rd.n_nreads ? (const uint8_t *)c->rd.nread_flag.p : nullptr;
+        a.nidx = (const uint32_t *)c->rd.nread_idx.p;
+        a.nascii = (const uint8_t *)c->rd.nread_ascii.p;
+        a.nn = c->rd.n_nreads;
+        a.pos = (const uint64_t *)c->res.d_pos.p;
+        a.rc = (const uint8_t *)c->res.d_rc.p;
         a.eread = (const uint32_t *)b.eread.p;
         a.eorg = (const uint32_t *)b.eorg.p;
         a.emc = (const uint8_t *)b.emc.p;
@@ -518,13 +518,13 @@ __global__ void __launch_bounds__(256) k_ord_reads(const uint64_t *__restrict__ 
 
 // -> b.order (device), *m_out = matched reads
 static int device_position_order(pgrc_match_ctx *c, Bufs &b, uint64_t *m_out) {
-    const uint64_t n = c->n;
-    if (c->G >= (1ull << 32)) { c->err = "export_pg_order: the device-made order needs a text below 2^32 symbols (pass order[])"; return PGRC_E_PARAM; }
+    const uint64_t n = c->rd.n;
+    if (c->txt.G >= (1ull << 32)) { c->err = "export_pg_order: the device-made order needs a text below 2^32 symbols (pass order[])"; return PGRC_E_PARAM; }
     DevBuf flag, slot, ra, rb, scratch;
     auto done = [&](int e) { DevBuf *all[] = {&flag, &slot, &ra, &rb, &scratch}; pgrc_buf_free_all(all, 5); return e; };
     int e;
     if ((e = pgrc_buf_ensure(c, flag, n)) || (e = pgrc_buf_ensure(c, slot, (n + 1) * sizeof(uint64_t)))) return done(e);
-    if (n) hipLaunchKernelGGL(k_ord_flags, dim3(grid_for(n)), dim3(256), 0, c->stream, (const uint64_t *)c->d_pos.p, n, (uint8_t *)flag.p);
+    if (n) hipLaunchKernelGGL(k_ord_flags, dim3(grid_for(n)), dim3(256), 0, c->stream, (const uint64_t *)c->res.d_pos.p, n, (uint8_t *)flag.p);
     if ((e = device_scan<uint8_t, false>(c, (const uint8_t *)flag.p, n, (uint64_t *)slot.p, b.bs))) return done(e);
     uint64_t m = 0;
     if (hipMemcpyAsync(&m, (const uint64_t *)slot.p + n, sizeof m, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -533,9 +533,9 @@ static int device_position_order(pgrc_match_ctx *c, Bufs &b, uint64_t *m_out) {
     if ((e = pgrc_buf_ensure(c, b.order, m * sizeof(uint32_t)))) return done(e);
     if (!m) return done(PGRC_OK);
     if ((e = pgrc_buf_ensure(c, ra, m * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, rb, m * sizeof(uint64_t)))) return done(e);
-    hipLaunchKernelGGL(k_ord_records, dim3(grid_for(n)), dim3(256), 0, c->stream, (const uint64_t *)c->d_pos.p, (const uint64_t *)slot.p, n, (uint64_t *)ra.p);
+    hipLaunchKernelGGL(k_ord_records, dim3(grid_for(n)), dim3(256), 0, c->stream, (const uint64_t *)c->res.d_pos.p, (const uint64_t *)slot.p, n, (uint64_t *)ra.p);
     uint32_t pbits = 1;
-    while (pbits < 32 && (c->G >> pbits)) pbits++;
+    while (pbits < 32 && (c->txt.G >> pbits)) pbits++;
     uint64_t *sorted = nullptr;
     if ((e = pgrc_radix_sort_u64(c, (uint64_t *)ra.p, (uint64_t *)rb.p, m, 32u, 32u + pbits, scratch, &sorted))) return done(e);
     hipLaunchKernelGGL(k_ord_reads, dim3(grid_for(m)), dim3(256), 0, c->stream, (const uint64_t *)sorted, m, (uint32_t *)b.order.p);
@@ -558,7 +558,7 @@ static int export_pg_order(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x
     const uint8_t *d_lrc = dev ? dev->d_rc : nullptr;
     const bool have_lrc = dev ? dev->d_rc != nullptr : x->list_rev_comp != nullptr;
     if (!d_rorg && x->read_org_idx) {
-        if ((e = upload(c, b.rorg, x->read_org_idx, c->n * sizeof(uint32_t)))) return e;
+        if ((e = upload(c, b.rorg, x->read_org_idx, c->rd.n * sizeof(uint32_t)))) return e;
         d_rorg = (const uint32_t *)b.rorg.p;
     }
     if ((e = pgrc_buf_ensure(c, b.lpos, (h + 1) * sizeof(uint64_t)))) return e;
@@ -576,9 +576,9 @@ static int export_pg_order(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x
         (e = pgrc_buf_ensure(c, b.emc, ne)) || (e = pgrc_buf_ensure(c, b.off, ne * off_width)))
         return e;
     ExportArgs a;
-    a.pos = (const uint64_t *)c->d_pos.p;
-    a.rc = (const uint8_t *)c->d_rc.p;
-    a.mism = (const uint8_t *)c->d_mism.p;
+    a.pos = (const uint64_t *)c->res.d_pos.p;
+    a.rc = (const uint8_t *)c->res.d_rc.p;
+    a.mism = (const uint8_t *)c->res.d_mism.p;
     a.order = (const uint32_t *)b.order.p;
     a.m = m;
     a.read_org = d_rorg;
@@ -634,7 +634,7 @@ struct GatheredView {
         pgrc_match_ctx *c0 = sh[0].ctx;
         PgrcDeviceScope scope(c0->device);
         if (!scope.ok) { f->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
-        const uint64_t n = f->n;
+        const uint64_t n = f->rd.n;
         int e;
         auto fail = [&](int code) { f->err = c0->err; return code; };
         if ((e = pgrc_buf_ensure(c0, pos, std::max<uint64_t>(n, 1) * 8)) || (e = pgrc_buf_ensure(c0, rc, std::max<uint64_t>(n, 1))) ||
@@ -649,9 +649,9 @@ struct GatheredView {
                 PgrcDeviceScope cs(c->device);
                 he = hipStreamSynchronize(c->stream);
             }
-            if (he == hipSuccess) he = hipMemcpyAsync((uint64_t *)pos.p + s.lo, c->d_pos.p, cnt * 8, hipMemcpyDefault, c0->stream);
-            if (he == hipSuccess) he = hipMemcpyAsync((uint8_t *)rc.p + s.lo, c->d_rc.p, cnt, hipMemcpyDefault, c0->stream);
-            if (he == hipSuccess) he = hipMemcpyAsync((uint8_t *)mism.p + s.lo, c->d_mism.p, cnt, hipMemcpyDefault, c0->stream);
+            if (he == hipSuccess) he = hipMemcpyAsync((uint64_t *)pos.p + s.lo, c->res.d_pos.p, cnt * 8, hipMemcpyDefault, c0->stream);
+            if (he == hipSuccess) he = hipMemcpyAsync((uint8_t *)rc.p + s.lo, c->res.d_rc.p, cnt, hipMemcpyDefault, c0->stream);
+            if (he == hipSuccess) he = hipMemcpyAsync((uint8_t *)mism.p + s.lo, c->res.d_mism.p, cnt, hipMemcpyDefault, c0->stream);
         }
         if (he == hipSuccess) he = hipStreamSynchronize(c0->stream);
         if (he != hipSuccess) { f->err = std::string("export: gathering the shards: ") + hipGetErrorString(he); return pgrc_hip_code(he); }
@@ -659,19 +659,19 @@ struct GatheredView {
         view.device = c0->device;
         view.stream = c0->stream;
         view.num_cus = c0->num_cus;
-        view.nw = c0->nw;
-        view.n = n;
-        view.stride = 0;
-        view.reads2 = nullptr;            // (the reads stay on their shards)
-        view.n_nreads = 0;
+        view.rd.nw = c0->rd.nw;
+        view.rd.n = n;
+        view.rd.stride = 0;
+        view.rd.reads2 = nullptr;            // (the reads stay on their shards)
+        view.rd.n_nreads = 0;
         view.export_front = f;
-        view.d_pos = pos;                 // (DevBuf copies: the view never frees anything, this object does)
-        view.d_rc = rc;
-        view.d_mism = mism;
-        view.pg2[0] = c0->pg2[0];
-        view.G = c0->G;
-        view.pg_words = c0->pg_words;
-        view.have_pg = view.have_reads = view.have_results = true;
+        view.res.d_pos = pos;                 // (DevBuf copies: the view never frees anything, this object does)
+        view.res.d_rc = rc;
+        view.res.d_mism = mism;
+        view.txt.pg2[0] = c0->txt.pg2[0];
+        view.txt.G = c0->txt.G;
+        view.txt.pg_words = c0->txt.pg_words;
+        view.txt.have_pg = view.rd.have_reads = view.res.have_results = true;
         return PGRC_OK;
     }
 };
@@ -706,13 +706,13 @@ void pgrc_export_drop_view(pgrc_match_ctx *c) {
 extern "C" int pgrc_match_export_pg_order(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x, pgrc_export_streams *out) {
     if (!c || !x || !out || (x->list_count && (!x->list_off || !x->list_org_idx))) return PGRC_E_PARAM;
     memset(out, 0, sizeof *out);
-    if (!c->have_results || !c->have_pg || !c->have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
+    if (!c->res.have_results || !c->txt.have_pg || !c->rd.have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
     if (!x->order_on_device) {
-        if (x->n_matched > c->n) { c->err = "export: more matched reads than reads"; return PGRC_E_PARAM; }
+        if (x->n_matched > c->rd.n) { c->err = "export: more matched reads than reads"; return PGRC_E_PARAM; }
         if (!x->order && x->n_matched) { c->err = "export_pg_order: order == NULL with n_matched > 0 (set order_on_device to let the library make the order)"; return PGRC_E_PARAM; }
     }
     for (uint64_t j = 0; !x->order_on_device && x->order && j < x->n_matched; j++)
-        if (x->order[j] >= c->n) { c->err = "export_pg_order: read index out of range"; return PGRC_E_PARAM; }
+        if (x->order[j] >= c->rd.n) { c->err = "export_pg_order: read index out of range"; return PGRC_E_PARAM; }
     pgrc_match_ctx *w = c;
     int ge = view_for(c, &w);
     if (ge) return ge;
@@ -751,13 +751,13 @@ static int resident_result(int e, Bufs *b, const pgrc_export_streams &st, PgrcEx
 int pgrc_export_pg_order_resident(pgrc_match_ctx *c, const pgrc_export_pg_order_args *x, const PgrcExportListSrc *src, PgrcExportResident *res) {
     *res = PgrcExportResident{};
     if (c->multi) { c->err = "export: the resident export needs a matcher on one device"; return PGRC_E_PARAM; }
-    if (!c->have_results || !c->have_pg || !c->have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
+    if (!c->res.have_results || !c->txt.have_pg || !c->rd.have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
     if (!x->order_on_device) {
-        if (x->n_matched > c->n) { c->err = "export: more matched reads than reads"; return PGRC_E_PARAM; }
+        if (x->n_matched > c->rd.n) { c->err = "export: more matched reads than reads"; return PGRC_E_PARAM; }
         if (!x->order && x->n_matched) { c->err = "export_pg_order: order == NULL with n_matched > 0 (set order_on_device to let the library make the order)"; return PGRC_E_PARAM; }
     }
     for (uint64_t j = 0; !x->order_on_device && x->order && j < x->n_matched; j++)
-        if (x->order[j] >= c->n) { c->err = "export_pg_order: read index out of range"; return PGRC_E_PARAM; }
+        if (x->order[j] >= c->rd.n) { c->err = "export_pg_order: read index out of range"; return PGRC_E_PARAM; }
     PgrcDeviceScope scope(c->device);
     Bufs *b = new Bufs();
     pgrc_export_streams st;
@@ -785,7 +785,7 @@ static int export_entries_device(pgrc_match_ctx *c, uint64_t ne, int pair_file, 
         return e;
     if (ne) {
         hipLaunchKernelGGL(k_export_fill_entries, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint32_t *)b.eread.p, ne,
-                           (const uint64_t *)c->d_pos.p, (const uint8_t *)c->d_rc.p, (const uint8_t *)c->d_mism.p, (uint64_t *)b.epos.p,
+                           (const uint64_t *)c->res.d_pos.p, (const uint8_t *)c->res.d_rc.p, (const uint8_t *)c->res.d_mism.p, (uint64_t *)b.epos.p,
                            (uint8_t *)b.erc.p, (uint8_t *)b.emc.p);
         if (off_width == 1) hipLaunchKernelGGL(k_export_offsets_abs<uint8_t>, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint64_t *)b.epos.p, ne, (uint8_t *)b.off.p);
         else hipLaunchKernelGGL(k_export_offsets_abs<uint16_t>, dim3(grid_for(ne)), dim3(256), 0, c->stream, (const uint64_t *)b.epos.p, ne, (uint16_t *)b.off.p);
@@ -811,7 +811,7 @@ static int export_original_order(pgrc_match_ctx *c, const pgrc_export_original_o
     auto done = [&](int code) { DevBuf *all[] = {&owner, &keep, &rank, &flag}; pgrc_buf_free_all(all, 4); return code; };
     int e;
     if (!d_read_org) {
-        if ((e = upload(c, b.rorg, x->read_org_idx, c->n * sizeof(uint32_t)))) return done(e);
+        if ((e = upload(c, b.rorg, x->read_org_idx, c->rd.n * sizeof(uint32_t)))) return done(e);
         d_read_org = (const uint32_t *)b.rorg.p;
     }
     if ((e = pgrc_buf_ensure(c, owner, std::max<uint64_t>(total, 1) * sizeof(uint32_t))) ||
@@ -821,8 +821,8 @@ static int export_original_order(pgrc_match_ctx *c, const pgrc_export_original_o
     hipError_t he = hipMemsetAsync(owner.p, 0xFF, std::max<uint64_t>(total, 1) * sizeof(uint32_t), c->stream);   // EX_NONE everywhere: fillers
     if (he == hipSuccess) he = hipMemsetAsync(flag.p, 0, sizeof(uint32_t), c->stream);
     if (he != hipSuccess) { c->err = std::string("export: ") + hipGetErrorString(he); return done(pgrc_hip_code(he)); }
-    if (c->n)
-        hipLaunchKernelGGL(k_oo_claim, dim3(grid_for(c->n)), dim3(256), 0, c->stream, d_read_org, c->n, (const uint8_t *)c->d_mism.p,
+    if (c->rd.n)
+        hipLaunchKernelGGL(k_oo_claim, dim3(grid_for(c->rd.n)), dim3(256), 0, c->stream, d_read_org, c->rd.n, (const uint8_t *)c->res.d_mism.p,
                            total, (uint32_t *)owner.p, (uint32_t *)flag.p);
     if (total) hipLaunchKernelGGL(k_oo_keep, dim3(grid_for(total)), dim3(256), 0, c->stream, (const uint32_t *)owner.p, total, parts, (uint8_t *)keep.p);
     if ((e = device_scan<uint8_t, false>(c, (const uint8_t *)keep.p, total, (uint64_t *)rank.p, b.bs))) return done(e);
@@ -852,7 +852,7 @@ static int export_original_order(pgrc_match_ctx *c, const pgrc_export_original_o
 int pgrc_export_original_order_resident(pgrc_match_ctx *c, const pgrc_export_original_order_args *x, const uint32_t *d_read_org, PgrcExportResident *res) {
     *res = PgrcExportResident{};
     if (c->multi) { c->err = "export: the resident export needs a matcher on one device"; return PGRC_E_PARAM; }
-    if (!c->have_results || !c->have_pg || !c->have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
+    if (!c->res.have_results || !c->txt.have_pg || !c->rd.have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
     if (x->reads_total_count >= EX_SKIP) { c->err = "export_original_order: too many original indexes"; return PGRC_E_PARAM; }
     PgrcDeviceScope scope(c->device);
     Bufs *b = new Bufs();
@@ -866,9 +866,9 @@ extern "C" int pgrc_match_export_entries(pgrc_match_ctx *c, const uint32_t *entr
                                          int32_t rev_compl_pair_file, int32_t byte_per_read_length, pgrc_export_streams *out) {
     if (!c || !out || (n_entries && (!entry_read || !entry_org_idx))) return PGRC_E_PARAM;
     memset(out, 0, sizeof *out);
-    if (!c->have_results || !c->have_pg || !c->have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
+    if (!c->res.have_results || !c->txt.have_pg || !c->rd.have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
     for (uint64_t k = 0; k < n_entries; k++)
-        if (entry_read[k] != EX_NONE && entry_read[k] >= c->n) { c->err = "export_entries: read index out of range"; return PGRC_E_PARAM; }
+        if (entry_read[k] != EX_NONE && entry_read[k] >= c->rd.n) { c->err = "export_entries: read index out of range"; return PGRC_E_PARAM; }
     pgrc_match_ctx *w = c;
     int ge = view_for(c, &w);
     if (ge) return ge;
@@ -882,9 +882,9 @@ extern "C" int pgrc_match_export_entries(pgrc_match_ctx *c, const uint32_t *entr
 }
 
 extern "C" int pgrc_match_export_original_order(pgrc_match_ctx *c, const pgrc_export_original_order_args *x, pgrc_export_streams *out) {
-    if (!c || !x || !out || (c->n && !x->read_org_idx)) return PGRC_E_PARAM;
+    if (!c || !x || !out || (c->rd.n && !x->read_org_idx)) return PGRC_E_PARAM;
     memset(out, 0, sizeof *out);
-    if (!c->have_results || !c->have_pg || !c->have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
+    if (!c->res.have_results || !c->txt.have_pg || !c->rd.have_reads) { c->err = "export: run first"; return PGRC_E_STATE; }
     if (x->reads_total_count >= EX_SKIP) { c->err = "export_original_order: too many original indexes"; return PGRC_E_PARAM; }
     pgrc_match_ctx *w = c;
     int ge = view_for(c, &w);

@@ -631,8 +631,8 @@ int pgrc_ps_scatter_front(pgrc_match_ctx *c, hipStream_t stream, int strand, uin
     uint32_t *kA = (uint32_t *)ix.skey[0].p, *kB = (uint32_t *)ix.skey[1].p;
     uint64_t *vA = (uint64_t *)ix.sval[0].p, *vB = (uint64_t *)ix.sval[1].p;
     GenArgs g;
-    g.pg = (const uint32_t *)c->pg2[strand].p;
-    g.pg_words_alloc = c->pg_words + PGRC_PG_PAD_WORDS;
+    g.pg = (const uint32_t *)c->txt.pg2[strand].p;
+    g.pg_words_alloc = c->txt.pg_words + PGRC_PG_PAD_WORDS;
     g.npos = n;
     g.k1 = k1;
     g.K = K;

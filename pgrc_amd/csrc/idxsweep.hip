@@ -416,8 +416,8 @@ struct OsBufs {
 template <int TPB, int E, int MINB, typename AUX, typename DIG>
 static int os_passes(pgrc_match_ctx *c, hipStream_t stream, int strand, const OsPlan &pl, const OsBufs &b) {
     constexpr uint32_t TILE = TPB * E;
-    const uint32_t *pg = (const uint32_t *)c->pg2[strand].p;
-    const uint64_t pgw = c->pg_words + PGRC_PG_PAD_WORDS;
+    const uint32_t *pg = (const uint32_t *)c->txt.pg2[strand].p;
+    const uint64_t pgw = c->txt.pg_words + PGRC_PG_PAD_WORDS;
     const uint32_t D1 = 1u << pl.b1, D2 = 1u << pl.b2;
     const size_t txt_bytes = (size_t)os_txt_words(TILE, pl.k1, pl.K) * sizeof(uint32_t);
     const size_t lds1 = std::max<size_t>((size_t)TILE * (8 + sizeof(AUX) + sizeof(DIG)), txt_bytes), lds2 = (size_t)TILE * (8 + sizeof(AUX));

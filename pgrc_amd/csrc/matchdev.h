@@ -1,12 +1,37 @@
 // matchdev.h -- device-side pieces shared by the match kernels of mode c (copmem.hip, dualkern.h).
 #pragma once
 
+#include <stddef.h>
 #include <type_traits>
 
 #include "devutil.h"
 #include "headfmt.h"
 
 #define MATCH_TPB 256
+
+// The counter block of a context in HBM (res.d_counters), as the kernels add to it and the host clears and reads it: the
+// layout is written down here and nowhere else.  Launchers hand out addresses of members, the host copies the block (or
+// a part) into one of these and reads members.
+struct PgrcWorkCounters {               // what a match kernel counts of its work
+    unsigned long long searched, candidates, probes, entry_fetches, verifies;
+};
+struct PgrcDualCounters {               // the dual kernel's: its work (probes: heads probed), then
+    PgrcWorkCounters w;
+    unsigned long long redo;            // reads done again in the reference's order
+    unsigned long long seed_probes;     // seeds probed (a seed's two heads are one line request)
+    unsigned long long skip_reads;      // reads that entered skip mode
+    unsigned long long rewinds;
+};
+struct PgrcDevCounters {
+    struct { PgrcWorkCounters w; unsigned long long pad[3]; } pass[2];   // the passes over strand 0 and 1 (the N kernel adds to them)
+    unsigned long long cursor[3];       // the kernels' read cursors: forward pass, RC pass, screen or dual kernel
+    unsigned long long pad0[5];
+    PgrcDualCounters sched;             // what a run that keeps both indexes counts apart: the dual kernel, or (sched.w) the screen
+    unsigned long long pad1[7];
+};
+static_assert(sizeof(PgrcDevCounters) == 320, "the counter block is 40 words");
+static_assert(offsetof(PgrcDevCounters, pass[1]) == 64 && offsetof(PgrcDevCounters, cursor) == 128 && offsetof(PgrcDevCounters, sched) == 192,
+              "every word of the counter block stays where it was");
 
 // Per-read state of the reference's sequential query (CopMEMMatcher.cpp:483-566).
 template <typename pos_t>

@@ -560,7 +560,7 @@ struct StaleWalk {
     }
     uint32_t src32(uint64_t pos) {
         char buf[4];
-        return le32(text_at(m->src, (const uint32_t *)m->base->pg2[0].p, nullptr, pos, 4, buf));
+        return le32(text_at(m->src, (const uint32_t *)m->base->txt.pg2[0].p, nullptr, pos, 4, buf));
     }
     uint32_t dest32(uint64_t pos) {
         char buf[4];
@@ -770,12 +770,12 @@ int pgrc_mem_set_src_device(pgrc_mem_ctx *m, const void *d_ascii, uint64_t n) {
         if (!e) e = pgrc_buf_ensure(c, mm->d_flag, 4);
         if (e) return e;
         HIP_TRY(c, hipMemsetAsync(mm->d_flag.p, 0, 4, c->stream));
-        if ((e = pgrc_launch_mem_pack_device(c, (const uint8_t *)text, len, false, (uint32_t *)c->pg2[0].p, nullptr, c->pg_words, (uint32_t *)mm->d_flag.p, 0))) return e;
+        if ((e = pgrc_launch_mem_pack_device(c, (const uint8_t *)text, len, false, (uint32_t *)c->txt.pg2[0].p, nullptr, c->txt.pg_words, (uint32_t *)mm->d_flag.p, 0))) return e;
         uint32_t fl = 0;
         HIP_TRY(c, hipMemcpyAsync(&fl, mm->d_flag.p, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (fl) { c->err = "pseudogenome contains a symbol outside ACGT"; return PGRC_E_SYMBOL; }
-        c->have_pg = true;
+        c->txt.have_pg = true;
         return PGRC_OK;
     }, d_ascii);
 }
@@ -811,12 +811,11 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
     const uint64_t dwords = (N2 + 15) / 16;
     if (dest_is_src) {
         if (rev_compl) {
-            if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) { m->err = c->err; return e; }
-            c->have_rc = true;
+            if ((e = pgrc_make_rc_text(c, c->stream))) { m->err = c->err; return e; }
         }
-        a.dest = (const uint32_t *)c->pg2[rev_compl ? 1 : 0].p;
+        a.dest = (const uint32_t *)c->txt.pg2[rev_compl ? 1 : 0].p;
         a.nmap = nullptr;
-        a.dest_words_alloc = c->pg_words + PGRC_PG_PAD_WORDS;
+        a.dest_words_alloc = c->txt.pg_words + PGRC_PG_PAD_WORDS;
     } else {
         const uint64_t CH = 64ull << 20;
         if ((e = pgrc_buf_ensure(c, m->d_dest, (dwords + PGRC_PG_PAD_WORDS) * 4)) || (e = pgrc_buf_ensure(c, m->d_nmap, (dwords + PGRC_PG_PAD_WORDS) * 2)) ||
@@ -864,7 +863,7 @@ static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, 
         return PGRC_OK;
     };
     if (nprobes == 0) return done();      // (a text shorter than K: no window, no match)
-    a.src = (const uint32_t *)c->pg2[0].p;
+    a.src = (const uint32_t *)c->txt.pg2[0].p;
     a.N = m->N;
     a.N2 = N2;
     if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, c->stream, 0))) { m->err = c->err; return e; }   // (only if somebody rebuilt the base index in between)

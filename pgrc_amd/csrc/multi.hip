@@ -123,7 +123,7 @@ int pgrc_match_shard_info(const pgrc_match_ctx *c, int32_t shard, int32_t *devic
     if (!c->multi) {
         if (device) *device = c->device;
         if (first_read) *first_read = 0;
-        if (n_reads) *n_reads = c->n;
+        if (n_reads) *n_reads = c->rd.n;
         return PGRC_OK;
     }
     const pgrc_multi *m = c->multi;
@@ -142,7 +142,7 @@ int pgrc_match_create_multi(const pgrc_match_params *p, int32_t n_devices, const
     f->prm = *p;
     f->opt = pgrc_options_from_env();
     f->device = devices[0];
-    f->nw = (p->read_len + 15) / 16;
+    f->rd.nw = (p->read_len + 15) / 16;
     int e = PGRC_OK;
     for (int32_t r = 0; r < n_devices && !e; r++) {
         for (int32_t q = 0; q < r; q++)
@@ -216,7 +216,7 @@ static int allgather_text(pgrc_match_ctx *f, uint64_t sw) {
         for (size_t r = 0; r < k && nr == ncclSuccess; r++) {
             pgrc_match_ctx *c = m->child[r];
             PgrcDeviceScope scope(c->device);
-            uint32_t *buf = (uint32_t *)c->pg2[0].p;
+            uint32_t *buf = (uint32_t *)c->txt.pg2[0].p;
             nr = m->rccl.AllGather(buf + r * sw, buf, (size_t)sw, ncclUint32, m->comm[r], c->stream);
         }
         const ncclResult_t ge = m->rccl.GroupEnd();
@@ -230,8 +230,8 @@ static int allgather_text(pgrc_match_ctx *f, uint64_t sw) {
             PgrcDeviceScope scope(c->device);
             for (size_t s = 0; s < k; s++) {
                 if (s == r) continue;
-                const uint32_t *src = (const uint32_t *)m->child[s]->pg2[0].p + s * sw;
-                uint32_t *dst = (uint32_t *)c->pg2[0].p + s * sw;
+                const uint32_t *src = (const uint32_t *)m->child[s]->txt.pg2[0].p + s * sw;
+                uint32_t *dst = (uint32_t *)c->txt.pg2[0].p + s * sw;
                 hipError_t he = m->dev[s] == m->dev[r]
                                     ? hipMemcpyAsync(dst, src, sw * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream)
                                     : hipMemcpyPeerAsync(dst, m->dev[r], src, m->dev[s], sw * sizeof(uint32_t), c->stream);
@@ -261,17 +261,17 @@ int pgrc_multi_set_pg_ascii(pgrc_match_ctx *f, const char *pg, uint64_t G) {
         int ce = pgrc_pg_alloc(c, G);
         if (ce) return ce;
         const uint64_t lo = std::min<uint64_t>(G, (uint64_t)r * sw * 16), hi = std::min<uint64_t>(G, (uint64_t)(r + 1) * sw * 16);
-        if (hi > lo && (ce = pgrc_match_pack_pg_slice(c, pg + lo, hi - lo, (uint32_t *)c->pg2[0].p + r * sw))) return ce;
+        if (hi > lo && (ce = pgrc_match_pack_pg_slice(c, pg + lo, hi - lo, (uint32_t *)c->txt.pg2[0].p + r * sw))) return ce;
         hipError_t he = hipStreamSynchronize(c->stream);
         if (he != hipSuccess) { c->err = std::string("pack: ") + hipGetErrorString(he); return pgrc_hip_code(he); }
         return PGRC_OK;
     });
     if (e) return e;
     if ((e = allgather_text(f, sw))) return e;
-    for (pgrc_match_ctx *c : m->child) c->have_pg = true;
-    f->G = G;
+    for (pgrc_match_ctx *c : m->child) c->txt.have_pg = true;
+    f->txt.G = G;
     f->cp = m->child[0]->cp;
-    f->have_pg = true;
+    f->txt.have_pg = true;
     return PGRC_OK;
 }
 
@@ -280,9 +280,9 @@ int pgrc_multi_set_pg_packed_device(pgrc_match_ctx *f, const void *d_words, uint
     pgrc_multi *m = f->multi;
     int e = on_children(f, [&](size_t r) { return pgrc_match_set_pg_packed_device(m->child[r], d_words, G); });
     if (e) return e;
-    f->G = G;
+    f->txt.G = G;
     f->cp = m->child[0]->cp;
-    f->have_pg = true;
+    f->txt.have_pg = true;
     return PGRC_OK;
 }
 
@@ -325,9 +325,9 @@ int pgrc_multi_begin_reads(pgrc_match_ctx *f, uint64_t n) {
     m->lo.assign(k, 0);
     m->hi.assign(k, 0);
     for (size_t r = 0; r < k; r++) shard_range(n, r, k, &m->lo[r], &m->hi[r]);
-    f->n = n;
-    f->have_reads = false;
-    f->have_results = false;
+    f->rd.n = n;
+    f->rd.have_reads = false;
+    f->res.have_results = false;
     m->up_next = 0;
     m->up_open = false;
     int e = on_children(f, [&](size_t r) { return pgrc_match_begin_reads(m->child[r], m->hi[r] - m->lo[r]); });
@@ -339,7 +339,7 @@ int pgrc_multi_begin_reads(pgrc_match_ctx *f, uint64_t n) {
 // rows [up_next, up_next + count) of the announced set: every shard takes its part
 int pgrc_multi_append_reads(pgrc_match_ctx *f, const void *rows, uint64_t count, int32_t symbols) {
     pgrc_multi *m = f->multi;
-    if (!m->up_open || m->up_next + count > f->n) { f->err = "append_reads: outside begin/end or too many rows"; return PGRC_E_STATE; }
+    if (!m->up_open || m->up_next + count > f->rd.n) { f->err = "append_reads: outside begin/end or too many rows"; return PGRC_E_STATE; }
     const uint32_t L = f->prm.read_len;
     const uint64_t rb = symbols == 0 ? L : symbols == 4 ? (L + 3) / 4 : (L + 2) / 3;
     const uint64_t a = m->up_next, b = m->up_next + count;
@@ -357,11 +357,11 @@ int pgrc_multi_append_reads(pgrc_match_ctx *f, const void *rows, uint64_t count,
 
 int pgrc_multi_end_reads(pgrc_match_ctx *f) {
     pgrc_multi *m = f->multi;
-    if (!m->up_open || m->up_next != f->n) { f->err = "end_reads: fewer rows appended than announced"; return PGRC_E_STATE; }
+    if (!m->up_open || m->up_next != f->rd.n) { f->err = "end_reads: fewer rows appended than announced"; return PGRC_E_STATE; }
     int e = on_children(f, [&](size_t r) { return pgrc_match_end_reads(m->child[r]); });
     if (e) return e;
     m->up_open = false;
-    f->have_reads = true;
+    f->rd.have_reads = true;
     return PGRC_OK;
 }
 
@@ -373,9 +373,9 @@ int pgrc_multi_set_reads_device(pgrc_match_ctx *f, const void *d_words, uint64_t
     if (e) { f->err = m->child[0]->err; return e; }
     m->lo.assign(1, 0);
     m->hi.assign(1, n);
-    f->n = n;
-    f->have_reads = true;
-    f->have_results = false;
+    f->rd.n = n;
+    f->rd.have_reads = true;
+    f->res.have_results = false;
     return PGRC_OK;
 }
 
@@ -384,43 +384,43 @@ int pgrc_multi_set_reads_device(pgrc_match_ctx *f, const void *d_words, uint64_t
 int pgrc_multi_init_results(pgrc_match_ctx *f) {
     pgrc_export_drop_view(f);
     pgrc_multi *m = f->multi;
-    if (!f->have_reads) { f->err = "init_results: no reads set"; return PGRC_E_STATE; }
+    if (!f->rd.have_reads) { f->err = "init_results: no reads set"; return PGRC_E_STATE; }
     int e = on_children(f, [&](size_t r) { return pgrc_match_init_results(m->child[r]); });
-    if (!e) f->have_results = true;
+    if (!e) f->res.have_results = true;
     return e;
 }
 
 int pgrc_multi_set_results(pgrc_match_ctx *f, const uint64_t *pos, const uint8_t *rc, const uint8_t *mism) {
     pgrc_export_drop_view(f);
     pgrc_multi *m = f->multi;
-    if (!f->have_reads) { f->err = "set_results: no reads set"; return PGRC_E_STATE; }
+    if (!f->rd.have_reads) { f->err = "set_results: no reads set"; return PGRC_E_STATE; }
     int e = on_children(f, [&](size_t r) { return pgrc_match_set_results(m->child[r], pos + m->lo[r], rc + m->lo[r], mism + m->lo[r]); });
-    if (!e) f->have_results = true;
+    if (!e) f->res.have_results = true;
     return e;
 }
 
 int pgrc_multi_run(pgrc_match_ctx *f, int first, int last) {
     pgrc_export_drop_view(f);
     pgrc_multi *m = f->multi;
-    if (!f->have_pg || !f->have_reads) { f->err = "run: set the pseudogenome and the reads first"; return PGRC_E_STATE; }
+    if (!f->txt.have_pg || !f->rd.have_reads) { f->err = "run: set the pseudogenome and the reads first"; return PGRC_E_STATE; }
     int e = on_children(f, [&](size_t r) -> int {
         pgrc_match_ctx *c = m->child[r];
         return first == last ? pgrc_match_run_pass(c, first) : pgrc_match_run(c, 1);
     });
     if (e) return e;
-    f->have_results = true;
-    memset(f->hist, 0, sizeof f->hist);
-    f->matched = 0;
+    f->res.have_results = true;
+    memset(f->res.hist, 0, sizeof f->res.hist);
+    f->res.matched = 0;
     for (pgrc_match_ctx *c : m->child) {
-        for (int x = 0; x < 256; x++) f->hist[x] += c->hist[x];
-        f->matched += c->matched;
+        for (int x = 0; x < 256; x++) f->res.hist[x] += c->res.hist[x];
+        f->res.matched += c->res.matched;
     }
     return PGRC_OK;
 }
 
 int pgrc_multi_get_results(pgrc_match_ctx *f, uint64_t *pos, uint8_t *rc, uint8_t *mism, uint64_t hist[256], uint64_t *matched) {
     pgrc_multi *m = f->multi;
-    if (!f->have_results) { f->err = "get_results: nothing computed"; return PGRC_E_STATE; }
+    if (!f->res.have_results) { f->err = "get_results: nothing computed"; return PGRC_E_STATE; }
     const size_t k = m->child.size();
     std::vector<uint64_t> h(k * 256, 0), mt(k, 0);
     int e = on_children(f, [&](size_t r) {
@@ -444,7 +444,7 @@ int pgrc_multi_get_results(pgrc_match_ctx *f, uint64_t *pos, uint8_t *rc, uint8_
 // cum[] is global (reads in set order); codes / offsets of shard r start at cum[lo_r]
 int pgrc_multi_extract_mismatches(pgrc_match_ctx *f, const uint8_t *reversed_flags, uint64_t *cum, uint8_t *codes, uint16_t *offsets) {
     pgrc_multi *m = f->multi;
-    if (!f->have_results || !f->have_pg) { f->err = "extract_mismatches: run first"; return PGRC_E_STATE; }
+    if (!f->res.have_results || !f->txt.have_pg) { f->err = "extract_mismatches: run first"; return PGRC_E_STATE; }
     const size_t k = m->child.size();
     std::vector<std::vector<uint64_t>> lc(k);
     int e = on_children(f, [&](size_t r) {
@@ -456,7 +456,7 @@ int pgrc_multi_extract_mismatches(pgrc_match_ctx *f, const uint8_t *reversed_fla
     for (size_t r = 0; r < k; r++) base[r + 1] = base[r] + lc[r].back();
     for (size_t r = 0; r < k; r++)
         for (uint64_t i = 0; i + m->lo[r] < m->hi[r]; i++) cum[m->lo[r] + i] = base[r] + lc[r][i];
-    cum[f->n] = base[k];
+    cum[f->rd.n] = base[k];
     if (!codes || !offsets || !base[k]) return PGRC_OK;
     return on_children(f, [&](size_t r) -> int {
         if (base[r + 1] == base[r]) return PGRC_OK;

@@ -517,7 +517,7 @@ static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, u
     if (e) return e;
     if (nwords) {
         PmText t;
-        t.text = dis ? (const uint32_t *)c->pg2[0].p : (const uint32_t *)m->d_dest.p;
+        t.text = dis ? (const uint32_t *)c->txt.pg2[0].p : (const uint32_t *)m->d_dest.p;
         t.nmap = (!dis && m->map_has_n) ? (const uint16_t *)m->d_nmap.p : nullptr;
         t.N2 = N2;
         t.mirror = (!dis && rc) ? 1u : 0u;

@@ -717,12 +717,12 @@ int pgrc_rsets_remove_matched(pgrc_rsets *s, pgrc_match_ctx *c) {
     const uint64_t n = s->set[1].n + s->set[2].n;
     if (c->multi) return rs_fail(s, PGRC_E_PARAM, "remove: the matcher runs on several devices");
     if (c->device != s->device) return rs_fail(s, PGRC_E_PARAM, "remove: the matcher is on another device");
-    if (!c->have_reads || c->n != n) return rs_fail(s, PGRC_E_PARAM, "remove: the matcher's read count is not the LQ count plus the N count");
-    if (!c->have_results || !c->d_pos.p) return rs_fail(s, PGRC_E_STATE, "remove: the matcher has no results");
+    if (!c->rd.have_reads || c->rd.n != n) return rs_fail(s, PGRC_E_PARAM, "remove: the matcher's read count is not the LQ count plus the N count");
+    if (!c->res.have_results || !c->res.d_pos.p) return rs_fail(s, PGRC_E_STATE, "remove: the matcher has no results");
     PGRC_ON_DEVICE(s);
     HIP_TRY(s, hipStreamSynchronize(c->stream));
     if ((e = pgrc_buf_unpooled(s, s->flags, n + 16))) return e;
-    if (n) hipLaunchKernelGGL(k_rs_matched, dim3(dec_grid(n, RS_TPB)), dim3(RS_TPB), 0, s->stream, (const uint64_t *)c->d_pos.p, n, (uint8_t *)s->flags.p);
+    if (n) hipLaunchKernelGGL(k_rs_matched, dim3(dec_grid(n, RS_TPB)), dim3(RS_TPB), 0, s->stream, (const uint64_t *)c->res.d_pos.p, n, (uint8_t *)s->flags.p);
     HIP_TRY(s, hipGetLastError());
     if ((e = rs_remove(s, (const uint8_t *)s->flags.p))) (void)hipStreamSynchronize(s->stream);
     return e;

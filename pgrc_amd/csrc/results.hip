@@ -19,10 +19,10 @@ __global__ void __launch_bounds__(256) k_init_results(uint64_t *pos, uint8_t *rc
 }
 
 int pgrc_launch_init_results(pgrc_match_ctx *c) {
-    if (!c->n) return PGRC_OK;
-    uint32_t grid = (uint32_t)((c->n + 255) / 256 < 65536 ? (c->n + 255) / 256 : 65536);
-    hipLaunchKernelGGL(k_init_results, dim3(grid), dim3(256), 0, c->stream, (uint64_t *)c->d_pos.p, (uint8_t *)c->d_rc.p,
-                       (uint8_t *)c->d_mism.p, c->n);
+    if (!c->rd.n) return PGRC_OK;
+    uint32_t grid = (uint32_t)((c->rd.n + 255) / 256 < 65536 ? (c->rd.n + 255) / 256 : 65536);
+    hipLaunchKernelGGL(k_init_results, dim3(grid), dim3(256), 0, c->stream, (uint64_t *)c->res.d_pos.p, (uint8_t *)c->res.d_rc.p,
+                       (uint8_t *)c->res.d_mism.p, c->rd.n);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
 }
@@ -45,8 +45,8 @@ __global__ void __launch_bounds__(256) k_unpack_results(uint64_t *pos, uint8_t *
 int pgrc_launch_unpack_results(pgrc_match_ctx *c, uint64_t lo, uint64_t n) {
     if (!n) return PGRC_OK;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->num_cus * 16u);
-    hipLaunchKernelGGL(k_unpack_results, dim3(grid), dim3(256), 0, c->stream, (uint64_t *)c->d_pos.p + lo, (uint8_t *)c->d_rc.p + lo,
-                       (uint8_t *)c->d_mism.p + lo, n);
+    hipLaunchKernelGGL(k_unpack_results, dim3(grid), dim3(256), 0, c->stream, (uint64_t *)c->res.d_pos.p + lo, (uint8_t *)c->res.d_rc.p + lo,
+                       (uint8_t *)c->res.d_mism.p + lo, n);
     HIP_TRY(c, hipGetLastError());
     return PGRC_OK;
 }
@@ -63,16 +63,16 @@ __global__ void __launch_bounds__(256) k_hist(const uint8_t *__restrict__ mism, 
 }
 
 int pgrc_launch_hist(pgrc_match_ctx *c) {
-    HIP_TRY(c, hipMemsetAsync(c->d_hist.p, 0, 256 * sizeof(uint64_t), c->stream));
-    if (c->n) {
-        uint32_t grid = (uint32_t)((c->n + 255) / 256 < 2048 ? (c->n + 255) / 256 : 2048);
-        hipLaunchKernelGGL(k_hist, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)c->d_mism.p, c->n,
-                           (unsigned long long *)c->d_hist.p);
+    HIP_TRY(c, hipMemsetAsync(c->res.d_hist.p, 0, 256 * sizeof(uint64_t), c->stream));
+    if (c->rd.n) {
+        uint32_t grid = (uint32_t)((c->rd.n + 255) / 256 < 2048 ? (c->rd.n + 255) / 256 : 2048);
+        hipLaunchKernelGGL(k_hist, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)c->res.d_mism.p, c->rd.n,
+                           (unsigned long long *)c->res.d_hist.p);
         HIP_TRY(c, hipGetLastError());
     }
-    HIP_TRY(c, hipMemcpyAsync(c->hist, c->d_hist.p, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->res.hist, c->res.d_hist.p, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->matched = c->n - c->hist[PGRC_NOT_MATCHED_CNT];
+    c->res.matched = c->rd.n - c->res.hist[PGRC_NOT_MATCHED_CNT];
     return PGRC_OK;
 }
 
@@ -147,13 +147,13 @@ __global__ void __launch_bounds__(256) k_extract(const ExtractArgs a) {
 // mismatch), *total.  d_revflags: per-read orientation flags ON THE DEVICE (nullptr: reversed iff the read matched the RC strand).
 // Everything is queued on c->stream; the call returns after the scan's total is known (one synchronisation).
 int pgrc_extract_lists_device(pgrc_match_ctx *c, const uint8_t *d_revflags, bool lists, DevBuf &d_cum, DevBuf &d_codes, DevBuf &d_offs, uint64_t *total_out) {
-    const uint64_t n = c->n;
+    const uint64_t n = c->rd.n;
     DevBuf d_bsum;
     int e;
     if ((e = pgrc_buf_ensure(c, d_cum, (n + 1) * sizeof(uint64_t)))) return e;
     if ((e = pgrc_buf_ensure(c, d_bsum, sco_scratch_elems(n) * sizeof(uint64_t)))) return e;
     // d_cum = exclusive scan of the counts in u64, d_cum[n] = their total
-    const hipError_t he = sco_device_scan<false, true>(c->stream, ScoLoad<uint64_t, uint8_t, XsCount>{(const uint8_t *)c->d_mism.p, XsCount{}}, n, ScoPlus{}, (uint64_t)0, (uint64_t)0,
+    const hipError_t he = sco_device_scan<false, true>(c->stream, ScoLoad<uint64_t, uint8_t, XsCount>{(const uint8_t *)c->res.d_mism.p, XsCount{}}, n, ScoPlus{}, (uint64_t)0, (uint64_t)0,
                                                  ScoStore<uint64_t>{(uint64_t *)d_cum.p}, (uint64_t *)d_bsum.p);
     uint64_t total = 0;
     if (he != hipSuccess || hipMemcpyAsync(&total, (const uint64_t *)d_cum.p + n, sizeof total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -167,32 +167,32 @@ int pgrc_extract_lists_device(pgrc_match_ctx *c, const uint8_t *d_revflags, bool
     if (!total || !lists) return PGRC_OK;                   // (lists = false: only the counts' scan was asked for)
     if ((e = pgrc_buf_ensure(c, d_codes, total)) || (e = pgrc_buf_ensure(c, d_offs, total * sizeof(uint16_t)))) return e;
     ExtractArgs a;
-    a.pg = (const uint32_t *)c->pg2[0].p;
-    a.reads = c->reads2;
+    a.pg = (const uint32_t *)c->txt.pg2[0].p;
+    a.reads = c->rd.reads2;
     a.n = n;
-    a.stride = c->stride;
-    a.nflag = c->n_nreads ? (const uint8_t *)c->nread_flag.p : nullptr;
-    a.nidx = (const uint32_t *)c->nread_idx.p;
-    a.nascii = (const uint8_t *)c->nread_ascii.p;
-    a.nn = c->n_nreads;
-    a.pos = (const uint64_t *)c->d_pos.p;
-    a.rc = (const uint8_t *)c->d_rc.p;
-    a.mism = (const uint8_t *)c->d_mism.p;
+    a.stride = c->rd.stride;
+    a.nflag = c->rd.n_nreads ? (const uint8_t *)c->rd.nread_flag.p : nullptr;
+    a.nidx = (const uint32_t *)c->rd.nread_idx.p;
+    a.nascii = (const uint8_t *)c->rd.nread_ascii.p;
+    a.nn = c->rd.n_nreads;
+    a.pos = (const uint64_t *)c->res.d_pos.p;
+    a.rc = (const uint8_t *)c->res.d_rc.p;
+    a.mism = (const uint8_t *)c->res.d_mism.p;
     a.revflags = d_revflags;
     a.cum = (const uint64_t *)d_cum.p;
     a.codes = (uint8_t *)d_codes.p;
     a.offsets = (uint16_t *)d_offs.p;
     a.L = c->prm.read_len;
     hipLaunchKernelGGL(k_extract<false>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, a);
-    if (c->n_nreads)
-        hipLaunchKernelGGL(k_extract<true>, dim3((uint32_t)((c->n_nreads + 255) / 256)), dim3(256), 0, c->stream, a);
+    if (c->rd.n_nreads)
+        hipLaunchKernelGGL(k_extract<true>, dim3((uint32_t)((c->rd.n_nreads + 255) / 256)), dim3(256), 0, c->stream, a);
     if (hipGetLastError() != hipSuccess) { c->err = "extract: kernel failed"; return PGRC_E_DEVICE; }
     return PGRC_OK;
 }
 
 int pgrc_extract_mismatches(pgrc_match_ctx *c, const uint8_t *reversed_flags, uint64_t *cum, uint8_t *codes,
                             uint16_t *offsets) {
-    const uint64_t n = c->n;
+    const uint64_t n = c->rd.n;
     DevBuf d_cum, d_codes, d_offs, d_flags;
     int e;
     auto cleanup = [&]() { pgrc_buf_free(d_cum); pgrc_buf_free(d_codes); pgrc_buf_free(d_offs); pgrc_buf_free(d_flags); };

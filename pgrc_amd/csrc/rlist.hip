@@ -342,7 +342,7 @@ static int rl_export(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_a
     src.d_off = (const uint16_t *)s->cur.off.p;
     src.d_org = (const uint32_t *)s->cur.org.p;
     src.d_rc = s->cur.has_rc ? (const uint8_t *)s->cur.rc.p : nullptr;
-    if (x->sets && (e = rl_reads_org(s, x->sets, c->n, "export_pg_order", &src.d_read_org))) return e;
+    if (x->sets && (e = rl_reads_org(s, x->sets, c->rd.n, "export_pg_order", &src.d_read_org))) return e;
     pgrc_export_pg_order_args a{};
     a.order = x->order;
     a.n_matched = x->n_matched;
@@ -356,7 +356,7 @@ static int rl_export(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_export_a
     HIP_TRY(s, hipStreamWaitEvent(c->stream, s->ev_x[0], 0));
     PgrcExportResident r;
     if ((e = pgrc_export_pg_order_resident(c, &a, &src, &r))) return rl_fail(s, e, std::string("export_pg_order: ") + pgrc_match_last_error(c));
-    return rl_take_export(s, c, r, "export_pg_order", PGRC_RLIST_EXPORT, (x->order_on_device ? 0 : x->n_matched * 4) + (x->read_org_idx ? c->n * 4 : 0), t0);
+    return rl_take_export(s, c, r, "export_pg_order", PGRC_RLIST_EXPORT, (x->order_on_device ? 0 : x->n_matched * 4) + (x->read_org_idx ? c->rd.n * 4 : 0), t0);
 }
 
 // exportMatchesInOriginalOrder: nothing of the old list is read; the same two hand-overs between the streams
@@ -365,7 +365,7 @@ static int rl_export_org(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_expo
     int e;
     if ((e = rl_begin(s))) return e;
     const uint32_t *d_rorg = nullptr;
-    if (x->sets && (e = rl_reads_org(s, x->sets, c->n, "export_original_order", &d_rorg))) return e;
+    if (x->sets && (e = rl_reads_org(s, x->sets, c->rd.n, "export_original_order", &d_rorg))) return e;
     pgrc_export_original_order_args a{};
     a.read_org_idx = x->read_org_idx;
     a.reads_total_count = x->reads_total_count;
@@ -377,7 +377,7 @@ static int rl_export_org(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_rlist_expo
     HIP_TRY(s, hipStreamWaitEvent(c->stream, s->ev_x[0], 0));
     PgrcExportResident r;
     if ((e = pgrc_export_original_order_resident(c, &a, d_rorg, &r))) return rl_fail(s, e, std::string("export_original_order: ") + pgrc_match_last_error(c));
-    return rl_take_export(s, c, r, "export_original_order", PGRC_RLIST_EXPORT_ORIGINAL, x->read_org_idx ? c->n * 4 : 0, t0);
+    return rl_take_export(s, c, r, "export_original_order", PGRC_RLIST_EXPORT_ORIGINAL, x->read_org_idx ? c->rd.n * 4 : 0, t0);
 }
 
 static int rl_download_run(pgrc_rlist *s, pgrc_export_streams *out) {
@@ -486,7 +486,7 @@ static int rl_positions_build(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, c
     int e;
     pgrc_rlist *const lists[3] = {x->hq, x->lq, x->n};
     const uint64_t base[3] = {0, x->hq_len, x->hq_len + x->lq_len};
-    uint64_t longest = c ? c->n + 1 : 1, writers = 0;
+    uint64_t longest = c ? c->rd.n + 1 : 1, writers = 0;
     for (pgrc_rlist *l : lists)
         if (l) {
             longest = std::max(longest, l->cur.n);
@@ -502,17 +502,17 @@ static int rl_positions_build(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, c
     uint64_t matched = 0;
     if (c) {
         if (x->sets) {
-            if ((e = rl_reads_org(s, x->sets, c->n, who.c_str(), &d_rorg))) return e;
+            if ((e = rl_reads_org(s, x->sets, c->rd.n, who.c_str(), &d_rorg))) return e;
         } else if (x->read_org_idx) {
-            if ((e = pgrc_buf_unpooled(s, s->map, c->n * 4 + 16)) || (e = dec_upload_host(s, s->map.p, x->read_org_idx, c->n * 4))) return e;
-            s->tm.bytes_up = c->n * 4;
+            if ((e = pgrc_buf_unpooled(s, s->map, c->rd.n * 4 + 16)) || (e = dec_upload_host(s, s->map.p, x->read_org_idx, c->rd.n * 4))) return e;
+            s->tm.bytes_up = c->rd.n * 4;
             d_rorg = (const uint32_t *)s->map.p;
         }
         HIP_TRY(s, hipEventRecord(s->ev_x[0], c->stream));
         HIP_TRY(s, hipStreamWaitEvent(s->stream, s->ev_x[0], 0));
-        d_mpos = (const uint64_t *)c->d_pos.p;
-        if ((e = dec_scan<false>(s, XfBelow{d_mpos, PGRC_NOT_MATCHED_POS}, c->n, 0, (uint64_t *)s->scan.p))) return e;
-        HIP_TRY(s, hipMemcpyAsync(&matched, (const uint64_t *)s->scan.p + c->n, 8, hipMemcpyDeviceToHost, s->stream));
+        d_mpos = (const uint64_t *)c->res.d_pos.p;
+        if ((e = dec_scan<false>(s, XfBelow{d_mpos, PGRC_NOT_MATCHED_POS}, c->rd.n, 0, (uint64_t *)s->scan.p))) return e;
+        HIP_TRY(s, hipMemcpyAsync(&matched, (const uint64_t *)s->scan.p + c->rd.n, 8, hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(s, hipStreamSynchronize(s->stream));
         writers += matched;
     }
@@ -531,7 +531,7 @@ static int rl_positions_build(pgrc_rlist *s, const pgrc_rlist_pairpos_args *x, c
             const RlPosOut o{(const uint32_t *)b.org.p, T, pos, cls, bad, (uint8_t)(l + 1), pass == 1};
             HIP_TRY(s, (sco_device_scan<true, false>(s->stream, XfU16{(const uint16_t *)b.off.p}, b.n, ScoPlus{}, (uint64_t)0, base[l], o, (uint64_t *)s->scratch.p)));
         }
-        if (c && c->n) hipLaunchKernelGGL(k_rl_pos_matched, dim3(rl_grid(c->n)), dim3(RL_TPB), 0, s->stream, d_mpos, c->n, d_rorg, T, pass == 1, pos, cls, bad);
+        if (c && c->rd.n) hipLaunchKernelGGL(k_rl_pos_matched, dim3(rl_grid(c->rd.n)), dim3(RL_TPB), 0, s->stream, d_mpos, c->rd.n, d_rorg, T, pass == 1, pos, cls, bad);
         HIP_TRY(s, hipGetLastError());
     }
     if (T) hipLaunchKernelGGL(k_rl_pos_never, dim3(rl_grid(T)), dim3(RL_TPB), 0, s->stream, (const uint8_t *)cls, T, bad);
@@ -771,7 +771,7 @@ static int rl_positions_args_ok(const pgrc_rlist_pairpos_args *x, const std::str
     int e;
     if (x->matcher) {
         if ((e = rl_matcher_ok(s, x->matcher, who.c_str()))) return e;
-        if (!x->matcher->have_results || !x->matcher->d_pos.p) return rl_fail(s, PGRC_E_STATE, who + ": the matcher has no results");
+        if (!x->matcher->res.have_results || !x->matcher->res.d_pos.p) return rl_fail(s, PGRC_E_STATE, who + ": the matcher has no results");
     }
     return PGRC_OK;
 }
@@ -804,7 +804,7 @@ int pgrc_rl_export_original_order(pgrc_rlist *s, pgrc_match_ctx *c, const pgrc_r
     if (x->sets && x->read_org_idx) return rl_fail(s, PGRC_E_PARAM, "export_original_order: the reads' original indexes are given twice (read_org_idx and sets)");
     int e;
     if ((e = rl_matcher_ok(s, c, "export_original_order"))) return e;
-    if (c->n && !x->sets && !x->read_org_idx) return rl_fail(s, PGRC_E_PARAM, "export_original_order: neither read_org_idx nor sets");
+    if (c->rd.n && !x->sets && !x->read_org_idx) return rl_fail(s, PGRC_E_PARAM, "export_original_order: neither read_org_idx nor sets");
     PGRC_ON_DEVICE(s);
     if ((e = rl_export_org(s, c, x))) (void)hipStreamSynchronize(s->stream);
     return e;

@@ -1022,7 +1022,7 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
     // pays when most windows of the text equal no key -- the exact matcher at C3: 100 M keys against 1.9 G windows, 0.20 ->
     // 0.16 s -- and costs a dependent round trip where many do (modes d / i with four parts per read: 0.42 -> 0.43 s): used
     // when there is at most one key per eight text positions (PGRC_SEED_FILTER=0 / 1: never / always, tests and A/B runs)
-    bool use_filter = nent * 8 <= c->G;
+    bool use_filter = nent * 8 <= c->txt.G;
     if (c->opt.seed_filter >= 0) use_filter = c->opt.seed_filter != 0;
     a.filter = nullptr;
     a.fshift = 0;
@@ -1104,7 +1104,7 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
     HIP_TRY(c, hipGetLastError());
     // a read's hits become its result by the atomic minimum of section 3b: a start key per read, the batch's reads row by row
     const uint32_t rw = (a.nwr + 3u) & ~3u;                 // <= 16: reads have at most 255 symbols (pgrc_match_create)
-    if (c->G >= (1ull << 40)) { c->err = "modes d/i/e: texts below 2^40 symbols"; return PGRC_E_PARAM; }
+    if (c->txt.G >= (1ull << 40)) { c->err = "modes d/i/e: texts below 2^40 symbols"; return PGRC_E_PARAM; }
     if ((e = pgrc_buf_ensure(c, c->seed.best, a.n * sizeof(uint64_t)))) return e;
     if ((e = pgrc_buf_ensure(c, c->seed.rows, a.n * rw * sizeof(uint32_t)))) return e;
     hipLaunchKernelGGL(k_seed_best_init, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), 0, c->stream, a, (uint64_t *)c->seed.best.p);
@@ -1113,17 +1113,17 @@ static int seedidx_batch(pgrc_match_ctx *c, SeedArgs a, uint64_t seg_windows, in
     HIP_TRY(c, hipGetLastError());
 
     // ONE scan of the forward text finds the hits of both strands (SeedArgs), in launches of at most seg_windows window starts
-    a.pg = (const uint32_t *)c->pg2[0].p;
-    a.pg_rc = (const uint32_t *)c->pg2[1].p;
+    a.pg = (const uint32_t *)c->txt.pg2[0].p;
+    a.pg_rc = (const uint32_t *)c->txt.pg2[1].p;
     a.want = (first_strand == 0 ? 1u : 0u) | (last_strand == 1 ? 2u : 0u);
-    const uint64_t nwin_all = c->G >= span ? c->G - span + 1 : 0;       // window starts of either strand (none: the reference's scan loops are empty / undefined there)
+    const uint64_t nwin_all = c->txt.G >= span ? c->txt.G - span + 1 : 0;       // window starts of either strand (none: the reference's scan loops are empty / undefined there)
     a.nwin_all = nwin_all;
     a.rc_top = nwin_all ? nwin_all - 1u + (a.cstride - 1u) : 0;
     const uint64_t nscan = !nwin_all ? 0 : (a.want & 2u) ? a.rc_top + 1u : nwin_all;
     const uint32_t per_block = (SCAN_TPB / a.cstride) * a.cstride * SCAN_R;
     const uint32_t *rows = (const uint32_t *)c->seed.rows.p;
     uint64_t *best = (uint64_t *)c->seed.best.p;
-    const uint64_t pgw = c->pg_words + PGRC_PG_PAD_WORDS;
+    const uint64_t pgw = c->txt.pg_words + PGRC_PG_PAD_WORDS;
     const uint64_t wseg = std::min<uint64_t>(seg_windows, nscan);
     if ((e = pgrc_buf_ensure(c, c->seed.hits, std::max<uint64_t>(wseg, 1) * (sizeof(uint64_t) + sizeof(uint32_t))))) return e;     // one word per window start of a launch + the list of the heavy ones
     uint64_t *wrec = (uint64_t *)c->seed.hits.p;
@@ -1206,38 +1206,37 @@ int pgrc_seedidx_run(pgrc_match_ctx *c, int first_strand, int last_strand) {
     a.m = (mode == 'e') ? L : c->prm.seed_len;
     a.cstride = (mode == 'i') ? a.P : 1u;
     if (a.P == 0 || a.P > 15) { c->err = "modes d/i: 1..15 seed parts supported"; return PGRC_E_PARAM; }
-    a.G = c->G;
-    a.stride = c->stride;
+    a.G = c->txt.G;
+    a.stride = c->rd.stride;
     a.nwr = (L + 15) / 16;
     a.kmax = c->prm.max_mismatches;
     a.kmin = c->prm.min_mismatches;
-    if (c->n == 0) return PGRC_OK;
+    if (c->rd.n == 0) return PGRC_OK;
     int e;
     if (last_strand >= 1) {
-        if ((e = pgrc_launch_revcomp(c, c->stream, (const uint32_t *)c->pg2[0].p, (uint32_t *)c->pg2[1].p, c->G))) return e;
-        c->have_rc = true;
+        if ((e = pgrc_make_rc_text(c, c->stream))) return e;
     }
     // a batch holds at most 2^30 entries (SX_FLAG); a launch of the scan 2^29 window starts (6 GB of scratch).  The knobs force
     // small batches / launches so that tests cover the loops on small inputs
     uint64_t batch = (1ull << 30) / a.P, seg = 1ull << 29;
     if (c->opt.seed_read_batch) batch = std::max<uint64_t>(1, std::min<uint64_t>(batch, c->opt.seed_read_batch));
     if (c->opt.seed_segment) seg = std::max<uint64_t>(4096, std::min<uint64_t>(seg, c->opt.seed_segment));
-    const uint32_t *d_nidx = (const uint32_t *)c->nread_idx.p;
-    for (uint64_t r0 = 0; r0 < c->n; r0 += batch) {
-        const uint64_t r1 = std::min(c->n, r0 + batch);
+    const uint32_t *d_nidx = (const uint32_t *)c->rd.nread_idx.p;
+    for (uint64_t r0 = 0; r0 < c->rd.n; r0 += batch) {
+        const uint64_t r1 = std::min(c->rd.n, r0 + batch);
         a.ibase = r0;
         a.n = r1 - r0;
-        a.reads = c->reads2 + r0;                      // word-major: word w of read i at reads[w * stride + i]
-        a.pos = (uint64_t *)c->d_pos.p + r0;
-        a.rc = (uint8_t *)c->d_rc.p + r0;
-        a.mism = (uint8_t *)c->d_mism.p + r0;
+        a.reads = c->rd.reads2 + r0;                      // word-major: word w of read i at reads[w * stride + i]
+        a.pos = (uint64_t *)c->res.d_pos.p + r0;
+        a.rc = (uint8_t *)c->res.d_rc.p + r0;
+        a.mism = (uint8_t *)c->res.d_mism.p + r0;
         // the batch's part of the side list of reads with N (indexes ascending)
-        const auto nlo = std::lower_bound(c->h_nidx.begin(), c->h_nidx.end(), (uint32_t)r0) - c->h_nidx.begin();
-        const auto nhi = std::lower_bound(c->h_nidx.begin(), c->h_nidx.end(), (uint32_t)std::min<uint64_t>(r1, 0xFFFFFFFFull)) - c->h_nidx.begin();
+        const auto nlo = std::lower_bound(c->rd.h_nidx.begin(), c->rd.h_nidx.end(), (uint32_t)r0) - c->rd.h_nidx.begin();
+        const auto nhi = std::lower_bound(c->rd.h_nidx.begin(), c->rd.h_nidx.end(), (uint32_t)std::min<uint64_t>(r1, 0xFFFFFFFFull)) - c->rd.h_nidx.begin();
         a.nn = (uint64_t)(nhi - nlo);
-        a.nflag = a.nn ? (const uint8_t *)c->nread_flag.p + r0 : nullptr;
+        a.nflag = a.nn ? (const uint8_t *)c->rd.nread_flag.p + r0 : nullptr;
         a.nidx = d_nidx + nlo;
-        a.nascii = (const uint8_t *)c->nread_ascii.p + (uint64_t)nlo * L;
+        a.nascii = (const uint8_t *)c->rd.nread_ascii.p + (uint64_t)nlo * L;
         if ((e = seedidx_batch(c, a, seg, first_strand, last_strand))) return e;
     }
     return PGRC_OK;

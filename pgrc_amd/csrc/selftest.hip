@@ -545,7 +545,7 @@ extern "C" int pgrc_selftest_reads_state(pgrc_selftest *h, const pgrc_match_ctx 
         return PGRC_E_PARAM;
     }
     const pgrc_match_ctx *s = ctx;
-    uint64_t lo = 0, hi = ctx->n, shards = 1;
+    uint64_t lo = 0, hi = ctx->rd.n, shards = 1;
     if (ctx->multi) {
         const std::vector<PgrcShardView> v = pgrc_multi_shards(const_cast<pgrc_match_ctx *>(ctx));
         if ((size_t)shard >= v.size()) {
@@ -557,8 +557,8 @@ extern "C" int pgrc_selftest_reads_state(pgrc_selftest *h, const pgrc_match_ctx 
         hi = v[shard].hi;
         shards = v.size();
     }
-    const bool has_npos = s->nread_npos.p && s->nread_npos.bytes >= s->n * 4;
-    const uint64_t vals[10] = {s->n, s->stride, s->nw, s->n_nreads, s->n_many, has_npos ? 1u : 0u, s->have_pg ? s->pg_words : 0, lo, hi, shards};
+    const bool has_npos = s->rd.nread_npos.p && s->rd.nread_npos.bytes >= s->rd.n * 4;
+    const uint64_t vals[10] = {s->rd.n, s->rd.stride, s->rd.nw, s->rd.n_nreads, s->rd.n_many, has_npos ? 1u : 0u, s->txt.have_pg ? s->txt.pg_words : 0, lo, hi, shards};
     for (int k = 0; k < 10; k++) info[k] = vals[k];
     PgrcDeviceScope scope(s->device);
     if (!scope.ok) {
@@ -566,12 +566,12 @@ extern "C" int pgrc_selftest_reads_state(pgrc_selftest *h, const pgrc_match_ctx 
         return PGRC_E_NO_DEVICE;
     }
     HIP_TRY(c, hipDeviceSynchronize());
-    if (out_reads2 && s->have_reads && s->n) HIP_TRY(c, hipMemcpy(out_reads2, s->reads2, (size_t)s->nw * s->stride * 4, hipMemcpyDeviceToHost));
-    if (out_nflag && s->n && s->nread_flag.p) HIP_TRY(c, hipMemcpy(out_nflag, s->nread_flag.p, s->n, hipMemcpyDeviceToHost));
-    if (out_npos && s->n && has_npos) HIP_TRY(c, hipMemcpy(out_npos, s->nread_npos.p, s->n * 4, hipMemcpyDeviceToHost));
-    if (out_nidx && s->n_nreads) HIP_TRY(c, hipMemcpy(out_nidx, s->nread_idx.p, s->n_nreads * 4, hipMemcpyDeviceToHost));
-    if (out_nascii && s->n_nreads) HIP_TRY(c, hipMemcpy(out_nascii, s->nread_ascii.p, s->n_nreads * s->prm.read_len, hipMemcpyDeviceToHost));
-    if (out_text && s->have_pg) HIP_TRY(c, hipMemcpy(out_text, s->pg2[0].p, s->pg_words * 4, hipMemcpyDeviceToHost));
+    if (out_reads2 && s->rd.have_reads && s->rd.n) HIP_TRY(c, hipMemcpy(out_reads2, s->rd.reads2, (size_t)s->rd.nw * s->rd.stride * 4, hipMemcpyDeviceToHost));
+    if (out_nflag && s->rd.n && s->rd.nread_flag.p) HIP_TRY(c, hipMemcpy(out_nflag, s->rd.nread_flag.p, s->rd.n, hipMemcpyDeviceToHost));
+    if (out_npos && s->rd.n && has_npos) HIP_TRY(c, hipMemcpy(out_npos, s->rd.nread_npos.p, s->rd.n * 4, hipMemcpyDeviceToHost));
+    if (out_nidx && s->rd.n_nreads) HIP_TRY(c, hipMemcpy(out_nidx, s->rd.nread_idx.p, s->rd.n_nreads * 4, hipMemcpyDeviceToHost));
+    if (out_nascii && s->rd.n_nreads) HIP_TRY(c, hipMemcpy(out_nascii, s->rd.nread_ascii.p, s->rd.n_nreads * s->prm.read_len, hipMemcpyDeviceToHost));
+    if (out_text && s->txt.have_pg) HIP_TRY(c, hipMemcpy(out_text, s->txt.pg2[0].p, s->txt.pg_words * 4, hipMemcpyDeviceToHost));
     return PGRC_OK;
 }
 

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "matchdev.h"
 
 // PGRC_STREAM_TIMING=1: host-clock milestones of a streamed run on stderr
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -37,7 +38,7 @@ extern "C" int pgrc_match_prepare_index(pgrc_match_ctx *c, int32_t both_strands)
     if (!c) return PGRC_E_PARAM;
     if (c->multi) { c->err = "prepare_index: single-device contexts only"; return PGRC_E_STATE; }
     if (c->prm.mode != 'c' || !both_strands) { c->err = "prepare_index: two-strand runs of mode c only"; return PGRC_E_STATE; }
-    if (!c->have_pg) { c->err = "prepare_index: set the pseudogenome first"; return PGRC_E_STATE; }
+    if (!c->txt.have_pg) { c->err = "prepare_index: set the pseudogenome first"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     return pgrc_prepare_both_indexes(c);
 }
@@ -61,9 +62,9 @@ static void stream_worker(pgrc_match_ctx *c) {
         }
         hipError_t he = b.done ? hipEventSynchronize(b.done) : hipSuccess;
         if (he == hipSuccess && b.cnt) {
-            he = hipMemcpyAsync(c->st.pos + b.lo, (const uint64_t *)c->d_pos.p + b.lo, b.cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, down);
-            if (he == hipSuccess) he = hipMemcpyAsync(c->st.rc + b.lo, (const uint8_t *)c->d_rc.p + b.lo, b.cnt, hipMemcpyDeviceToHost, down);
-            if (he == hipSuccess) he = hipMemcpyAsync(c->st.mism + b.lo, (const uint8_t *)c->d_mism.p + b.lo, b.cnt, hipMemcpyDeviceToHost, down);
+            he = hipMemcpyAsync(c->st.pos + b.lo, (const uint64_t *)c->res.d_pos.p + b.lo, b.cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, down);
+            if (he == hipSuccess) he = hipMemcpyAsync(c->st.rc + b.lo, (const uint8_t *)c->res.d_rc.p + b.lo, b.cnt, hipMemcpyDeviceToHost, down);
+            if (he == hipSuccess) he = hipMemcpyAsync(c->st.mism + b.lo, (const uint8_t *)c->res.d_mism.p + b.lo, b.cnt, hipMemcpyDeviceToHost, down);
             if (he == hipSuccess) he = hipStreamSynchronize(down);
         }
         if (c->opt.stream_timing) fprintf(stderr, "pgrc stream: %8.2f ms  results of block [%llu, +%llu) on the host\n", (now_s() - c->st.t0) * 1e3, (unsigned long long)b.lo, (unsigned long long)b.cnt);
@@ -119,7 +120,7 @@ extern "C" int pgrc_match_stream_begin(pgrc_match_ctx *c, uint64_t *pos, uint8_t
     if (!c || !pos || !rc || !mism) return PGRC_E_PARAM;
     if (c->multi) { c->err = "stream_begin: single-device contexts only"; return PGRC_E_STATE; }
     if (c->prm.mode != 'c' || c->prm.min_mismatches != 0) { c->err = "stream_begin: mode c with min_mismatches == 0 only"; return PGRC_E_STATE; }
-    if (!c->have_pg || !c->up.open || c->up.next != 0) { c->err = "stream_begin: call it after set_pg and begin_reads, before the first rows"; return PGRC_E_STATE; }
+    if (!c->txt.have_pg || !c->up.open || c->up.next != 0) { c->err = "stream_begin: call it after set_pg and begin_reads, before the first rows"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     pgrc_stream_abort(c);
     int e;
@@ -127,10 +128,9 @@ extern "C" int pgrc_match_stream_begin(pgrc_match_ctx *c, uint64_t *pos, uint8_t
     // the per-read state of a first phase (DefaultReadsMatcher::initMatching, ReadsMatchers.cpp:97-105); have_reads is not
     // set yet, so not through pgrc_match_init_results
     if ((e = pgrc_launch_init_results(c))) return e;
-    if ((e = pgrc_buf_ensure(c, c->d_scr_pos, c->n * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, c->d_scr_flag, c->n ? c->n : 1))) return e;
-    HIP_TRY(c, hipMemsetAsync(c->d_scr_flag.p, 0, c->n ? c->n : 1, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, 40 * sizeof(uint64_t), c->stream));
-    memset(&c->ctr, 0, sizeof c->ctr);
+    if ((e = pgrc_buf_ensure(c, c->res.d_scr_pos, c->rd.n * sizeof(uint64_t))) || (e = pgrc_buf_ensure(c, c->res.d_scr_flag, c->rd.n ? c->rd.n : 1))) return e;
+    HIP_TRY(c, hipMemsetAsync(c->res.d_scr_flag.p, 0, c->rd.n ? c->rd.n : 1, c->stream));
+    if ((e = pgrc_counters_clear(c))) return e;
     if (!c->st.ready) HIP_TRY(c, hipEventCreateWithFlags(&c->st.ready, hipEventDisableTiming));
     HIP_TRY(c, hipEventRecord(c->st.ready, c->stream));              // both indexes built, per-read state initialised
     // (Round 5, tried and dropped, profiles/r05_boundary_stream_variants.txt: the blocks' launches on two streams in turn, so that
@@ -152,7 +152,7 @@ extern "C" int pgrc_match_stream_begin(pgrc_match_ctx *c, uint64_t *pos, uint8_t
     c->st.nblocks.clear();
     c->st.worker = std::thread(stream_worker, c);
     c->st.on = true;
-    c->have_results = false;
+    c->res.have_results = false;
     c->st.t0 = now_s();
     if (c->opt.stream_timing) {
         if (!c->st.tbase) HIP_TRY(c, hipEventCreate(&c->st.tbase));
@@ -169,7 +169,8 @@ int pgrc_stream_block_arrived(pgrc_match_ctx *c, uint64_t lo, uint64_t cnt, bool
     HIP_TRY(c, hipEventRecord(c->up.stream[turn].ev[0], c->up.stream[turn].stream));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->up.stream[turn].ev[0], 0));
     // the kernels' read cursors start at zero for every launch
-    HIP_TRY(c, hipMemsetAsync((uint64_t *)c->d_counters.p + 16, 0, 3 * sizeof(uint64_t), c->stream));
+    PgrcDevCounters *dc = (PgrcDevCounters *)c->res.d_counters.p;
+    HIP_TRY(c, hipMemsetAsync(dc->cursor, 0, sizeof dc->cursor, c->stream));
     const PgrcReadRange block{lo, cnt, true};                        // (the reads with N wait for stream_end)
     int e;
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -204,14 +205,14 @@ int pgrc_stream_block_arrived(pgrc_match_ctx *c, uint64_t lo, uint64_t cnt, bool
 extern "C" int pgrc_match_stream_end(pgrc_match_ctx *c, uint64_t hist[256], uint64_t *matched) {
     if (!c) return PGRC_E_PARAM;
     if (!c->st.on) { c->err = "stream_end: no streamed run in progress"; return PGRC_E_STATE; }
-    if (c->up.open || !c->have_reads) { pgrc_stream_abort(c); c->err = "stream_end: call pgrc_match_end_reads first"; return PGRC_E_STATE; }
+    if (c->up.open || !c->rd.have_reads) { pgrc_stream_abort(c); c->err = "stream_end: call pgrc_match_end_reads first"; return PGRC_E_STATE; }
     PGRC_ON_DEVICE(c);
     int e = PGRC_OK;
     pgrc_stream_mark(c, "stream_end called");
     // the reads with N: their kernel over the side list, forward strand then RC strand (ReadsMatchers.cpp:162-172), on the
     // side stream and BESIDE the blocks that are still being matched (one lane per read, latency-bound: it fits in; the
     // blocks' kernels skip the reads with N, so the two write disjoint reads); the main stream joins it at its tail
-    if (c->n_nreads) {
+    if (c->rd.n_nreads) {
         e = pgrc_copmem_match_nreads(c, 0, 1, c->st.dual, c->st.ready);   // one launch: a read's forward query, then its RC query (the blocks' dual kernel took the reads with at most 4 N)
         if (!e) e = pgrc_copmem_join_nreads(c);
     }
@@ -230,7 +231,7 @@ extern "C" int pgrc_match_stream_end(pgrc_match_ctx *c, uint64_t hist[256], uint
     }
     if (!e) e = pgrc_launch_hist(c);                                 // synchronises the main stream: every block is done
     pgrc_stream_mark(c, "histogram done");
-    if (!e && c->n_nreads) {
+    if (!e && c->rd.n_nreads) {
         std::lock_guard<std::mutex> g(c->st.mu);
         for (const auto &b : c->st.nblocks) c->st.q.push_back({b.first, b.second, nullptr});
     }
@@ -242,8 +243,8 @@ extern "C" int pgrc_match_stream_end(pgrc_match_ctx *c, uint64_t hist[256], uint
     if (e) return e;
     if (c->st.dual && (e = pgrc_fetch_schedule_counters(c, true))) return e;
     c->ctr.ms_total = (float)((now_s() - c->st.t0) * 1e3);           // (host clock: stream_begin .. here)
-    c->have_results = true;
-    if (hist) memcpy(hist, c->hist, sizeof c->hist);
-    if (matched) *matched = c->matched;
+    c->res.have_results = true;
+    if (hist) memcpy(hist, c->res.hist, sizeof c->res.hist);
+    if (matched) *matched = c->res.matched;
     return PGRC_OK;
 }
