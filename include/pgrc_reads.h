@@ -84,7 +84,44 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
                            int32_t rev_compl_pair, int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed,
                            uint64_t *n_records, pgrc_divided_reads *out);
 
-/* 1 if the last pgrc_divider_run_fastq took the last records the reference's iteration would take (its source is through
+/* The reads sources of the reference (ManagedReadsSetIterator, readsset/persistance/ReadsSetPersistence.cpp:36-47, picks by the
+ * first byte of the FILE: '@' -> FASTQ, '>' or ';' -> FASTA, anything else -> one read per line; pgrc_reads_text_format in
+ * pgrc_reads_text.h restates that choice). */
+#define PGRC_READS_FASTQ 0
+#define PGRC_READS_FASTA 1
+#define PGRC_READS_LINES 2     /* one read per line, ConcatenatedReadsSourceIterator */
+
+/* pgrc_divider_run_fastq for any of the three text formats, under the same contract for pieces (file order, below 2 GiB),
+ * final_piece, *consumed / *pair_consumed, pgrc_divider_last_was_terminal and the arrays in *out.  PGRC_READS_FASTQ forwards
+ * to pgrc_divider_run_fastq.  The other two (FASTAReadsSourceIterator, readsset/iterator/ReadsSetIterator.cpp:118-134;
+ * ConcatenatedReadsSourceIterator, :66-76):
+ *   lines    std::getline lines: in a piece that is not the last of its text only lines that have their newline; where the
+ *            text ends, a last line without a newline counts.
+ *   FASTA    a line whose first byte is '>' or ';' is passed over -- any number of them in a row, anywhere, at the very end of
+ *            the file too; every other line is one read, an empty line included.  A sequence wrapped over several lines is
+ *            several reads, as in the reference.
+ *   LINES    every line is one read.
+ *   the read is the leading run of letters of its line ('\r', blanks and what follows them are cut) and must be read_len long:
+ *            PGRC_E_PARAM otherwise (the reference exits with "Unsupported variable length reads"); a symbol outside ACGNT is
+ *            PGRC_E_SYMBOL -- lower case too, except in a reverse-complemented second file, whose complement table
+ *            upper-cases it.
+ *   pairs    (FASTA) reads are taken from the two texts in turn, the first file first; in each file the k-th read is its k-th
+ *            line that is not passed over; the reference stops at the first exhausted file, and the `terminal` rule is the one
+ *            of pgrc_divider_run_fastq with complete read lines where that has complete records.  rev_compl_pair as there.
+ * *consumed is the first byte after the last read line taken: header lines behind it are handed over again with the next
+ * piece; there is no "ends inside a record".  A piece that holds header lines only, or nothing, gives *n_records = 0 and
+ * *consumed = 0.
+ * Refused with PGRC_E_PARAM before the device is touched, the divider's last run staying what it was:
+ *   PGRC_READS_LINES with pair_text != NULL or rev_compl_pair != 0 (the reference silently ignores the second file there: its
+ *            ConcatenatedReadsSourceIterator never sees it -- a caller that relied on that gets an error instead of half its reads);
+ *   error_limit < 1 with FASTA or LINES (there are no qualities; the reference reads an empty string at an index);
+ *   an unknown format.
+ * After a refused or failed call the divider stays usable. */
+int pgrc_divider_run_text(pgrc_divider *d, int32_t format, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes,
+                          int32_t rev_compl_pair, int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed,
+                          uint64_t *n_records, pgrc_divided_reads *out);
+
+/* 1 if the last pgrc_divider_run_fastq / pgrc_divider_run_text took the last records the reference's iteration would take (its source is through
  * when its turn comes: one text ended and its records are used up) -- the caller stops; 0: hand over the next pieces */
 int pgrc_divider_last_was_terminal(const pgrc_divider *d);
 

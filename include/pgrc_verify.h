@@ -60,7 +60,9 @@ int pgrc_verify_add_rows(pgrc_verify *v, uint32_t file, const char *rows, uint64
  * and pair files of unequal length, with rev_compl_pair = 0: the decoder's output is the source as it was.  pair_text is
  * the second file's piece: NULL for a job of one file, needed (pair_bytes may be 0) for a job of two.  *n_records = records
  * taken, the files in turn.  Refuses what the divider refuses (a read that is not L letters long, text that ends inside a
- * record: PGRC_E_PARAM; a symbol outside ACGNT: PGRC_E_SYMBOL). */
+ * record: PGRC_E_PARAM; a symbol outside ACGNT: PGRC_E_SYMBOL).
+ * A FASTA or one-read-per-line source goes through pgrc_verify_add_text (pgrc_reads_text.h, libpgrc_reads_text.so: this
+ * library's seven names stay seven), which takes a handle of this library as it is. */
 int pgrc_verify_add_fastq(pgrc_verify *v, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes,
                           int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed, uint64_t *n_records);
 

@@ -17,7 +17,7 @@ from .matchers import (  # noqa: F401
     mapReadsIntoPg,
 )
 from .textmatch import CopMEMMatcher  # noqa: F401
-from .readsets import DividedPCLReadsSets, DividedReadsSets  # noqa: F401
+from .readsets import DividedPCLReadsSets, DividedReadsSets, reads_text_format  # noqa: F401
 from . import synth  # noqa: F401
 from .decode import (  # noqa: F401
     PgRCDecoder,

@@ -311,6 +311,8 @@ _PROTOS = [
     ("pgrc_divider_run", C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(DividedReads)]),
     ("pgrc_divider_run_fastq", C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(DividedReads)]),
+    ("pgrc_divider_run_text", C.c_int, [_P, C.c_int32, _P, C.c_uint64, _P, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(DividedReads)]),
     ("pgrc_divider_last_ms", C.c_int, [_P, C.POINTER(C.c_float * 3)]),
     ("pgrc_divider_last_was_terminal", C.c_int, [_P]),
 ]
@@ -449,6 +451,22 @@ def bind_verify(cdll: C.CDLL) -> C.CDLL:
     return cdll
 
 
+# include/pgrc_reads_text.h: exported by libpgrc_reads_text.so (libpgrc_verify.so's objects and readstext.hip) alone
+READS_FASTQ, READS_FASTA, READS_LINES = 0, 1, 2
+READS_FORMATS = {"fastq": READS_FASTQ, "fasta": READS_FASTA, "lines": READS_LINES}
+READS_TEXT_PROTOS = [
+    ("pgrc_reads_text_format", C.c_int, [C.c_int]),
+    ("pgrc_verify_add_text", C.c_int, [_P, C.c_int32, _P, C.c_uint64, _P, C.c_uint64, C.c_int32, _U64P, _U64P, _U64P]),
+]
+READS_TEXT_EXPORTED_SYMBOLS = [p[0] for p in READS_TEXT_PROTOS]
+READS_TEXT_LIB_PATH = os.environ.get("PGRC_READS_TEXT_LIB") or os.path.join(_HERE, "libpgrc_reads_text.so")
+
+
+def reads_format(fmt) -> int:
+    """"fastq" / "fasta" / "lines" or a PGRC_READS_* number -> the number"""
+    return READS_FORMATS[fmt.lower()] if isinstance(fmt, str) else int(fmt)
+
+
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
 RLIST_EXPORTED_SYMBOLS = [p[0] for p in RLIST_PROTOS]
 RSETS_EXPORTED_SYMBOLS = [p[0] for p in RSETS_PROTOS]
@@ -495,6 +513,13 @@ lib = _load()
 if not os.path.exists(VERIFY_LIB_PATH):
     raise ImportError(f"{VERIFY_LIB_PATH} is missing: `make -C pgrc_amd/csrc` builds it beside libpgrc_match.so")
 vlib = bind_verify(C.CDLL(VERIFY_LIB_PATH))
+if not os.path.exists(READS_TEXT_LIB_PATH):
+    raise ImportError(f"{READS_TEXT_LIB_PATH} is missing: `make -C pgrc_amd/csrc` builds it beside libpgrc_match.so")
+tlib = C.CDLL(READS_TEXT_LIB_PATH)
+for _name, _res, _args in READS_TEXT_PROTOS:
+    _fn = getattr(tlib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
 if not os.path.exists(RLIST_ORD_LIB_PATH):
     raise ImportError(f"{RLIST_ORD_LIB_PATH} is missing: `make -C pgrc_amd/csrc` builds it beside libpgrc_match.so")
 olib = C.CDLL(RLIST_ORD_LIB_PATH)

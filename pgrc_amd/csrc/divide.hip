@@ -15,6 +15,8 @@
 //                     comparison with the error limit sees the same double;
 //   3. k_dv_class + three exclusive scans: the read's set and its row in it;
 //   4. k_dv_pack    : one thread per OUTPUT byte (3 or 4 symbols as base-5 / base-4 digits), rows written in place.
+// In front of it, for callers that have text: k_fq_* (FASTQ) and k_tx_* (FASTA, one read per line) find the lines and copy the
+// records' rows out (pgrc_divider_run_fastq, pgrc_divider_run_text).
 // All byte work, bound by the host link (2 x read_len bytes per read up, read_len / 4 down): no MFMA.
 #include <math.h>
 #include <stdlib.h>
@@ -41,12 +43,13 @@ struct pgrc_divider : PgrcDev {
     int suffix_pos = 0;
     DevBuf d_reads, d_quals, d_flags, d_high, d_cls, d_cnt[3], d_bsum, d_rows[3], d_idx[2], d_lut, d_err;
     DevBuf d_text[2], d_nl[2], d_ls[2];   // FASTQ text of one or two files, newlines per 16 bytes, line starts
+    DevBuf d_rlf[2], d_rl[2], d_ends;     // FASTA / one read per line: read-line flags (scanned in place), read lines, where the records taken end
     // the results of a run on the host: pinned, grow-only, the divider's (fresh pageable pages would be touched for the first
     // time by the copy, at one thread's page-fault rate: 11 GB/s against the link's 56)
     struct HostBuf { void *p = nullptr; size_t bytes = 0; } h_rows[3], h_idx[2];
     PhaseEvents<4> ev;
     float ms[3] = {0, 0, 0};
-    bool last_terminal = false;   // the last pgrc_divider_run_fastq took what the reference's iteration would take before it ends
+    bool last_terminal = false;   // the last pgrc_divider_run_fastq / _run_text took what the reference's iteration would take before it ends
     // what the last run left in d_rows / d_idx (pgrc_divider_last_device: readsets.hip takes the sets where they lie)
     bool last_valid = false;
     uint64_t last_n = 0, last_cnt[3] = {0, 0, 0};
@@ -318,6 +321,70 @@ k_fq_rows(const FqRowsArgs a) {
     }
 }
 
+// ---- FASTA and one read per line: the read lines among the lines
+// flag[j] = line j is a read (FASTAReadsSourceIterator::moveNext, ReadsSetIterator.cpp:123-126: a line whose first byte is '>' or
+// ';' is passed over; ConcatenatedReadsSourceIterator, :66-68: every line is a read); entry `lines`: 0, the end of the scan.
+// A line that starts at the end of the text has no first byte: an empty line, a read like any other.
+__global__ void __launch_bounds__(256)
+k_tx_flags(const uint8_t *__restrict__ text, uint32_t bytes, const uint32_t *__restrict__ ls, uint32_t lines, uint32_t fasta,
+           uint32_t *__restrict__ flag) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > lines) return;
+    uint32_t f = 0;
+    if (j < lines) {
+        f = 1;
+        const uint32_t s = ls[j];
+        if (fasta && s < bytes) {
+            const uint32_t ch = text[s];
+            f = (ch != '>' && ch != ';') ? 1u : 0u;
+        }
+    }
+    flag[j] = f;
+}
+// rl[k] = the line of read k; before = the exclusive scan of the flags (entry `lines`: the number of reads)
+__global__ void __launch_bounds__(256)
+k_tx_compact(const uint32_t *__restrict__ before, uint32_t lines, uint32_t *__restrict__ rl) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= lines) return;
+    const uint32_t k = before[j];
+    if (before[j + 1] != k) rl[k] = (uint32_t)j;
+}
+
+struct TxRowsArgs {
+    const uint8_t *text[2];
+    const uint32_t *ls[2], *rl[2];
+    uint32_t nl[2], take[2];    // newlines of each text; reads taken from it
+    uint32_t paired, rc_second, L;
+    uint64_t n;
+    uint8_t *reads;
+    uint32_t *err, *ends;       // ends[f]: the first byte after the last read line taken from text f
+};
+// k_fq_rows without the quality column: record k of the batch = read k (or k / 2 of file k % 2), its line taken from rl
+__global__ void __launch_bounds__(256)
+k_tx_rows(const TxRowsArgs a) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t k = g / (a.L + 1);
+    const uint32_t x = (uint32_t)(g % (a.L + 1));
+    if (k >= a.n) return;
+    const uint32_t f = a.paired ? (uint32_t)(k & 1) : 0u;
+    const uint32_t r = (uint32_t)(a.paired ? k >> 1 : k);
+    const uint8_t *t = a.text[f];
+    const uint32_t *ls = a.ls[f];
+    const uint32_t j = a.rl[f][r];
+    const uint32_t s = ls[j];
+    const uint32_t next = ls[j + 1];                                   // (j <= nl, and ls has nl + 7 entries)
+    const uint32_t e = next - (j < a.nl[f] ? 1u : 0u);                 // up to the newline; a last line without one: up to the end
+    const uint32_t ch = (s + x < e) ? t[s + x] : 0u;
+    if (x == a.L) {
+        if (fq_alpha(ch)) atomicOr(a.err, 1u);                         // the read is longer than read_len
+        if (r + 1 == a.take[f]) a.ends[f] = next;
+        return;
+    }
+    if (!fq_alpha(ch)) atomicOr(a.err, 1u);                            // ... or shorter
+    const bool rc = a.rc_second && f == 1;
+    a.reads[k * a.L + (rc ? a.L - 1 - x : x)] = (uint8_t)(rc ? fq_complement(ch) : ch);
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 extern "C" {
@@ -378,7 +445,8 @@ void pgrc_divider_destroy(pgrc_divider *d) {
     (void)hipDeviceSynchronize();
     DevBuf *bufs[] = {&d->d_reads, &d->d_quals, &d->d_flags, &d->d_high, &d->d_cls, &d->d_cnt[0], &d->d_cnt[1], &d->d_cnt[2], &d->d_bsum,
                       &d->d_rows[0], &d->d_rows[1], &d->d_rows[2], &d->d_idx[0], &d->d_idx[1], &d->d_lut, &d->d_err,
-                      &d->d_text[0], &d->d_text[1], &d->d_nl[0], &d->d_nl[1], &d->d_ls[0], &d->d_ls[1]};
+                      &d->d_text[0], &d->d_text[1], &d->d_nl[0], &d->d_nl[1], &d->d_ls[0], &d->d_ls[1],
+                      &d->d_rlf[0], &d->d_rlf[1], &d->d_rl[0], &d->d_rl[1], &d->d_ends};
     for (DevBuf *b : bufs) pgrc_buf_free(*b);
     for (auto *h : {&d->h_rows[0], &d->h_rows[1], &d->h_rows[2], &d->h_idx[0], &d->h_idx[1]})
         if (h->p) (void)hipHostFree(h->p);
@@ -645,6 +713,125 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
             if (take[f]) HIP_TRY(d, hipMemcpyAsync(&ends[f], (const uint32_t *)d->d_ls[f].p + 4 * take[f], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(d, hipStreamSynchronize(s));
         if (bad) { c->err = "Unsupported variable length reads (a FASTQ record whose read is not read_len letters long)"; return PGRC_E_PARAM; }
+    }
+    *consumed = ends[0];
+    if (paired) *pair_consumed = ends[1];
+    (void)d->ev.record(1, s);
+    *n_records = n;
+    return divide_resident(d, n, out);
+}
+
+// ---- FASTA and one-read-per-line text in, sets out (FASTAReadsSourceIterator and ConcatenatedReadsSourceIterator,
+// readsset/iterator/ReadsSetIterator.cpp:118-134 and :66-76).  The lines are found as for FASTQ text; which of them are reads
+// is a flag per line, their places an exclusive scan of the flags, the list of read lines a compaction.  The rows kernel takes
+// read k's line from that list; the division runs on the rows where they lie.  One host wait more than the FASTQ path: the
+// numbers of reads of both texts, fetched together.
+int pgrc_divider_run_text(pgrc_divider *d, int32_t format, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes,
+                          int32_t rev_compl_pair, int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed,
+                          uint64_t *n_records, pgrc_divided_reads *out) {
+    if (format == PGRC_READS_FASTQ)
+        return pgrc_divider_run_fastq(d, text, bytes, pair_text, pair_bytes, rev_compl_pair, final_piece, consumed, pair_consumed, n_records, out);
+    if (!d || !out || !consumed || !n_records || (bytes && !text) || (pair_bytes && !pair_text) || (pair_text && !pair_consumed)) return PGRC_E_PARAM;
+    PgrcDev *c = d;
+    // refused before anything of the divider changes: the sets of its last run stay its last
+    if (format != PGRC_READS_FASTA && format != PGRC_READS_LINES) { c->err = "divider: unknown text format " + std::to_string(format); return PGRC_E_PARAM; }
+    if (format == PGRC_READS_LINES && (pair_text || rev_compl_pair)) {
+        c->err = "divider: one-read-per-line text has no pair file (the reference ignores it silently)";
+        return PGRC_E_PARAM;
+    }
+    if (d->prm.error_limit < 1) { c->err = "divider: FASTA and one-read-per-line text carry no qualities: error_limit must be >= 1"; return PGRC_E_PARAM; }
+    if (bytes >= (1ull << 31) || pair_bytes >= (1ull << 31)) { c->err = "divider: pieces of text below 2 GiB"; return PGRC_E_PARAM; }
+    d->last_valid = false;
+    memset(out, 0, sizeof *out);
+    *consumed = 0;
+    *n_records = 0;
+    if (pair_consumed) *pair_consumed = 0;
+    PgrcDeviceScope scope(c->device);
+    if (!scope.ok) { c->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
+    int e;
+    if ((e = d->ev.ensure(d))) return e;
+    const uint32_t L = d->prm.read_len;
+    const bool paired = pair_text != nullptr;
+    const int nf = paired ? 2 : 1;
+    hipStream_t s = c->stream;
+    const char *src[2] = {text, pair_text};
+    const uint64_t len[2] = {bytes, pair_bytes};
+    const bool fin[2] = {(final_piece & 3) != 0, (final_piece & 5) != 0};      // (as pgrc_divider_run_fastq)
+    uint32_t lines[2] = {0, 0}, nls[2] = {0, 0}, rec[2] = {0, 0};
+    (void)d->ev.record(0, s);
+    for (int f = 0; f < nf; f++) {
+        const uint64_t n16 = (len[f] + 15) / 16;
+        if ((e = pgrc_buf_ensure(c, d->d_text[f], len[f] + 32)) || (e = pgrc_buf_ensure(c, d->d_nl[f], (n16 + 1) * sizeof(uint32_t))) ||
+            (e = pgrc_buf_ensure(c, d->d_bsum, pgrc_ps_scan_blocks(n16 + 1) * sizeof(uint32_t))))
+            return e;
+        if (len[f]) HIP_TRY(d, hipMemcpyAsync(d->d_text[f].p, src[f], len[f], hipMemcpyHostToDevice, s));
+        HIP_TRY(d, hipMemsetAsync((uint8_t *)d->d_text[f].p + len[f], 0, 32, s));         // the 16-byte loads run past the end
+        hipLaunchKernelGGL(k_fq_count, dim3((uint32_t)((n16 + 1 + 255) / 256)), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, len[f], n16,
+                           (uint32_t *)d->d_nl[f].p);
+        if ((e = pgrc_ps_scan_u32(c, s, (uint32_t *)d->d_nl[f].p, n16 + 1, (uint32_t *)d->d_bsum.p))) return e;
+        uint32_t nl = 0;
+        HIP_TRY(d, hipMemcpyAsync(&nl, (const uint32_t *)d->d_nl[f].p + n16, sizeof nl, hipMemcpyDeviceToHost, s));
+        HIP_TRY(d, hipStreamSynchronize(s));
+        // std::getline: a last piece without its newline is a line too, once nothing more will come
+        lines[f] = nl + ((fin[f] && len[f] && src[f][len[f] - 1] != '\n') ? 1u : 0u);
+        nls[f] = nl;
+        if ((e = pgrc_buf_ensure(c, d->d_ls[f], ((size_t)nl + 8) * sizeof(uint32_t))) ||
+            (e = pgrc_buf_ensure(c, d->d_rlf[f], ((size_t)lines[f] + 1) * sizeof(uint32_t))) ||
+            (e = pgrc_buf_ensure(c, d->d_rl[f], ((size_t)lines[f] + 1) * sizeof(uint32_t))) ||
+            (e = pgrc_buf_ensure(c, d->d_bsum, pgrc_ps_scan_blocks((uint64_t)lines[f] + 1) * sizeof(uint32_t))))
+            return e;
+        hipLaunchKernelGGL(k_fq_starts, dim3((uint32_t)((n16 + 255) / 256 + 1)), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, len[f], n16,
+                           (const uint32_t *)d->d_nl[f].p, nl, (uint32_t *)d->d_ls[f].p);
+        hipLaunchKernelGGL(k_tx_flags, dim3((lines[f] + 1 + 255) / 256), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, (uint32_t)len[f],
+                           (const uint32_t *)d->d_ls[f].p, lines[f], format == PGRC_READS_FASTA ? 1u : 0u, (uint32_t *)d->d_rlf[f].p);
+        HIP_TRY(d, hipGetLastError());
+        if ((e = pgrc_ps_scan_u32(c, s, (uint32_t *)d->d_rlf[f].p, (uint64_t)lines[f] + 1, (uint32_t *)d->d_bsum.p))) return e;
+        if (lines[f]) {
+            hipLaunchKernelGGL(k_tx_compact, dim3((lines[f] + 255) / 256), dim3(256), 0, s, (const uint32_t *)d->d_rlf[f].p, lines[f],
+                               (uint32_t *)d->d_rl[f].p);
+            HIP_TRY(d, hipGetLastError());
+        }
+        HIP_TRY(d, hipMemcpyAsync(&rec[f], (const uint32_t *)d->d_rlf[f].p + lines[f], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(d, hipStreamSynchronize(s));                   // rec[]: the read lines each piece holds
+    // records taken and `terminal`: the rule of pgrc_divider_run_fastq, with read lines where it has lines / 4
+    uint64_t n;
+    uint32_t take[2];
+    bool terminal;
+    if (!paired) { n = rec[0]; take[0] = rec[0]; take[1] = 0; terminal = fin[0]; }
+    else if ((fin[0] && fin[1]) || (fin[0] && rec[1] >= rec[0]) || (fin[1] && rec[0] >= rec[1] + 1)) {
+        n = rec[0] <= rec[1] ? 2 * (uint64_t)rec[0] : 2 * (uint64_t)rec[1] + 1; take[0] = (uint32_t)((n + 1) / 2); take[1] = (uint32_t)(n / 2); terminal = true;
+    } else { const uint32_t m = std::min(rec[0], rec[1]); n = 2 * (uint64_t)m; take[0] = take[1] = m; terminal = false; }
+    d->last_terminal = terminal;
+    if (n >= (1ull << 32) - 1) { c->err = "divider: batches of less than 2^32 - 1 reads"; return PGRC_E_PARAM; }
+    uint32_t ends[2] = {0, 0};        // first byte after the last read line taken from each piece; header lines behind it come again
+    if (n) {
+        if ((e = pgrc_buf_ensure(c, d->d_reads, (size_t)n * L + 16)) || (e = pgrc_buf_ensure(c, d->d_ends, 2 * sizeof(uint32_t)))) return e;
+        HIP_TRY(d, hipMemsetAsync(d->d_err.p, 0, sizeof(uint32_t), s));
+        HIP_TRY(d, hipMemsetAsync(d->d_ends.p, 0, 2 * sizeof(uint32_t), s));
+        TxRowsArgs a;
+        for (int f = 0; f < 2; f++) {
+            a.text[f] = (const uint8_t *)d->d_text[f].p;
+            a.ls[f] = (const uint32_t *)d->d_ls[f].p;
+            a.rl[f] = (const uint32_t *)d->d_rl[f].p;
+            a.nl[f] = nls[f];
+            a.take[f] = take[f];
+        }
+        a.paired = paired ? 1u : 0u;
+        a.rc_second = (paired && rev_compl_pair) ? 1u : 0u;
+        a.L = L;
+        a.n = n;
+        a.reads = (uint8_t *)d->d_reads.p;
+        a.err = (uint32_t *)d->d_err.p;
+        a.ends = (uint32_t *)d->d_ends.p;
+        const uint64_t work = n * (L + 1);
+        hipLaunchKernelGGL(k_tx_rows, dim3((uint32_t)((work + 255) / 256)), dim3(256), 0, s, a);
+        HIP_TRY(d, hipGetLastError());
+        uint32_t bad = 0;
+        HIP_TRY(d, hipMemcpyAsync(&bad, d->d_err.p, sizeof bad, hipMemcpyDeviceToHost, s));
+        HIP_TRY(d, hipMemcpyAsync(ends, d->d_ends.p, sizeof ends, hipMemcpyDeviceToHost, s));
+        HIP_TRY(d, hipStreamSynchronize(s));
+        if (bad) { c->err = "Unsupported variable length reads (a read line whose read is not read_len letters long)"; return PGRC_E_PARAM; }
     }
     *consumed = ends[0];
     if (paired) *pair_consumed = ends[1];

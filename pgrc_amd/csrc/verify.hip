@@ -471,15 +471,19 @@ int pgrc_verify_add_rows(pgrc_verify *v, uint32_t file, const char *rows, uint64
     return PGRC_OK;
 }
 
-int pgrc_verify_add_fastq(pgrc_verify *v, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes, int32_t final_piece, uint64_t *consumed,
-                          uint64_t *pair_consumed, uint64_t *n_records) {
+}   // extern "C"
+// source text of any format: the divider parses it (pgrc_divider_run_text; PGRC_READS_FASTQ is pgrc_divider_run_fastq), the rows
+// are taken where it leaves them
+int pgrc_vf_add_text(pgrc_verify *v, const char *who, int32_t format, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes,
+                     int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed, uint64_t *n_records) {
     if (!v) return PGRC_E_PARAM;
     int e;
-    if ((e = vf_add_checks(v, "add_fastq"))) return e;
+    const std::string pre = std::string(who) + ": ";
+    if ((e = vf_add_checks(v, who))) return e;
     if (!consumed || !n_records || (bytes && !text) || (pair_bytes && !pair_text) || (pair_text && !pair_consumed))
-        return vf_fail(v, PGRC_E_PARAM, "add_fastq: a NULL argument");
-    if (pair_text && v->F == 1) return vf_fail(v, PGRC_E_PARAM, "add_fastq: pair_text on a job of one file");
-    if (!pair_text && v->F == 2) return vf_fail(v, PGRC_E_PARAM, "add_fastq: a job of two files needs pair_text");
+        return vf_fail(v, PGRC_E_PARAM, pre + "a NULL argument");
+    if (pair_text && v->F == 1) return vf_fail(v, PGRC_E_PARAM, pre + "pair_text on a job of one file");
+    if (!pair_text && v->F == 2) return vf_fail(v, PGRC_E_PARAM, pre + "a job of two files needs pair_text");
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t L = v->L, F = v->F;
     if (!v->divider) {
@@ -487,15 +491,15 @@ int pgrc_verify_add_fastq(pgrc_verify *v, const char *text, uint64_t bytes, cons
         p.read_len = L;
         p.error_limit = 1;          // no quality division: the quality lines are not looked at
         p.device = v->device;
-        if ((e = pgrc_divider_create(&p, &v->divider))) return vf_fail(v, e, std::string("add_fastq: ") + pgrc_divider_last_error(nullptr));
+        if ((e = pgrc_divider_create(&p, &v->divider))) return vf_fail(v, e, pre + pgrc_divider_last_error(nullptr));
     }
     pgrc_divided_reads dr;
     uint64_t n = 0;
-    if ((e = pgrc_divider_run_fastq(v->divider, text, bytes, pair_text, pair_bytes, 0, final_piece, consumed, pair_consumed, &n, &dr))) {
+    if ((e = pgrc_divider_run_text(v->divider, format, text, bytes, pair_text, pair_bytes, 0, final_piece, consumed, pair_consumed, &n, &dr))) {
         *consumed = 0;
         *n_records = 0;
         if (pair_consumed) *pair_consumed = 0;
-        return vf_fail(v, e, std::string("add_fastq: ") + pgrc_divider_last_error(v->divider));
+        return vf_fail(v, e, pre + pgrc_divider_last_error(v->divider));
     }
     const uint8_t *d_reads = nullptr;
     uint64_t n_last = 0;
@@ -510,7 +514,7 @@ int pgrc_verify_add_fastq(pgrc_verify *v, const char *text, uint64_t bytes, cons
     *n_records = n;
     if (n) {
         PGRC_ON_DEVICE(v);
-        if (n_last != n || !d_reads) return vf_fail(v, PGRC_E_DEVICE, "add_fastq: internal: the divider's rows are not those of this run");
+        if (n_last != n || !d_reads) return vf_fail(v, PGRC_E_DEVICE, pre + "internal: the divider's rows are not those of this run");
         float ms[3] = {0, 0, 0};
         (void)pgrc_divider_last_ms(v->divider, ms);
         v->tm.ms_fastq_parse_device += ms[0];
@@ -539,6 +543,12 @@ int pgrc_verify_add_fastq(pgrc_verify *v, const char *text, uint64_t bytes, cons
     }
     v->tm.ms_fastq += dec_ms_since(t0);
     return PGRC_OK;
+}
+extern "C" {
+
+int pgrc_verify_add_fastq(pgrc_verify *v, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes, int32_t final_piece, uint64_t *consumed,
+                          uint64_t *pair_consumed, uint64_t *n_records) {
+    return pgrc_vf_add_text(v, "add_fastq", PGRC_READS_FASTQ, text, bytes, pair_text, pair_bytes, final_piece, consumed, pair_consumed, n_records);
 }
 
 int pgrc_verify_finish(pgrc_verify *v, pgrc_verify_result *out) {

@@ -49,3 +49,7 @@ int pgrc_vf_match_keys(pgrc_verify *v, const VfSide &s, const VfSide &d, VfCount
 void pgrc_vf_mask_next_begin(uint32_t bits);
 // grow-only buffers of the handle for a caller that fills them itself (PGRC_E_ALLOC names the bytes)
 int pgrc_vf_key_buffers(pgrc_verify *v, uint64_t n);
+// verify.hip, for readstext.hip: source text of any format (PGRC_READS_*, pgrc_reads.h) through the divider; `who` names the
+// entry point in the error texts ("add_fastq", "add_text")
+int pgrc_vf_add_text(pgrc_verify *v, const char *who, int32_t format, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes,
+                     int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed, uint64_t *n_records);

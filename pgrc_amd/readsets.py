@@ -12,6 +12,14 @@ from . import _lib
 from ._lib import PgrcMatchError, lib
 
 
+def reads_text_format(first_byte) -> int:
+    """the reference's choice of the reads source by the first byte of the file (pgrc_reads_text_format): a byte value, a
+    bytes object (its first byte; empty: -1, the end of the file) or -1 -> 0 FASTQ, 1 FASTA, 2 one read per line"""
+    if isinstance(first_byte, (bytes, bytearray)):
+        first_byte = first_byte[0] if len(first_byte) else -1
+    return int(_lib.tlib.pgrc_reads_text_format(int(first_byte)))
+
+
 class DividedPCLReadsSets:
     """DividedPCLReadsSets::getQualityDivisionBasedReadsSets (DividedPCLReadsSets.cpp:59-100) over batches of FASTQ
     records given as row arrays.  `divide(reads, quals)` returns the packed rows of the HQ / LQ / N sets of the batch
@@ -89,8 +97,24 @@ class DividedPCLReadsSets:
                                             C.byref(used), C.byref(pused), C.byref(nrec), C.byref(out)))
         return self._result(out), int(nrec.value), int(used.value), int(pused.value)
 
+    def divide_text(self, fmt, text: bytes, pair_text: Optional[bytes] = None, rev_compl_pair: bool = False, final=True):
+        """divide_fastq for any of the reference's three text formats (pgrc_divider_run_text): fmt is "fastq", "fasta" or
+        "lines" (one read per line), or what reads_text_format gives for the file's first byte.  Returns what divide_fastq
+        returns."""
+        out = _lib.DividedReads()
+        used, pused, nrec = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        t = np.frombuffer(text, dtype=np.uint8) if len(text) else np.zeros(1, np.uint8)
+        pt = None
+        if pair_text is not None:
+            pt = np.frombuffer(pair_text, dtype=np.uint8) if len(pair_text) else np.zeros(1, np.uint8)
+        self._ck(lib.pgrc_divider_run_text(self._h, _lib.reads_format(fmt), t.ctypes.data_as(C.c_void_p), len(text),
+                                           pt.ctypes.data_as(C.c_void_p) if pt is not None else None,
+                                           len(pair_text) if pair_text is not None else 0, int(bool(rev_compl_pair)), int(final),
+                                           C.byref(used), C.byref(pused), C.byref(nrec), C.byref(out)))
+        return self._result(out), int(nrec.value), int(used.value), int(pused.value)
+
     def last_was_terminal(self) -> bool:
-        """did the last divide_fastq take the last records the reference's iteration would take (pgrc_divider_last_was_terminal)"""
+        """did the last divide_fastq / divide_text take the last records the reference's iteration would take (pgrc_divider_last_was_terminal)"""
         return bool(lib.pgrc_divider_last_was_terminal(self._h))
 
     def last_ms(self):

@@ -72,6 +72,21 @@ class Verifier:
                                                  fin, C.byref(used), C.byref(pused) if p is not None else None, C.byref(nrec)))
         return used.value, pused.value, nrec.value
 
+    def add_text(self, fmt, text, pair_text=None, final: bool | int = False):
+        """add_fastq for any of the reference's three text formats (pgrc_verify_add_text, include/pgrc_reads_text.h): fmt is
+        "fastq", "fasta" or "lines", or a PGRC_READS_* number"""
+        t = _u8(text)
+        p = None if pair_text is None else _u8(pair_text)
+        used, pused, nrec = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        fin = int(final) if not isinstance(final, bool) else (1 if final else 0)
+        keep = np.zeros(1, np.uint8)
+        # (libpgrc_reads_text.so holds the verifier's code too: a handle of either library is a handle of the other)
+        rc = _lib.tlib.pgrc_verify_add_text(self._h, _lib.reads_format(fmt), t.ctypes.data_as(_P) if t.size else None, t.size,
+                                            None if p is None else (p if p.size else keep).ctypes.data_as(_P), 0 if p is None else p.size,
+                                            fin, C.byref(used), C.byref(pused) if p is not None else None, C.byref(nrec))
+        self._ck(rc)
+        return used.value, pused.value, nrec.value
+
     def finish(self) -> dict:
         """the result, once: pgrc_verify_result's fields by name (n_source and n_decoded as lists, ok as a bool)"""
         r = VerifyResult()
