@@ -15,8 +15,10 @@
 //                     comparison with the error limit sees the same double;
 //   3. k_dv_class + three exclusive scans: the read's set and its row in it;
 //   4. k_dv_pack    : one thread per OUTPUT byte (3 or 4 symbols as base-5 / base-4 digits), rows written in place.
-// In front of it, for callers that have text: k_fq_* (FASTQ) and k_tx_* (FASTA, one read per line) find the lines and copy the
-// records' rows out (pgrc_divider_run_fastq, pgrc_divider_run_text).
+// In front of it, for callers that have text (pgrc_divider_run_fastq, pgrc_divider_run_text: one body, dv_run_text), per file
+// of a pair (DvTextFile): k_fq_count / k_fq_starts find the lines (dv_find_lines), for FASTA and one read per line k_tx_flags /
+// k_tx_compact the read lines among them (dv_read_lines); dv_take says how many records the call takes from each file, and
+// k_dv_rows<FASTQ> copies their rows out.
 // All byte work, bound by the host link (2 x read_len bytes per read up, read_len / 4 down): no MFMA.
 #include <math.h>
 #include <stdlib.h>
@@ -38,12 +40,29 @@
 #define DVF_BAD 2u          // a byte outside ACGNT in the symbol row
 #define DVF_BAD_Q 4u        // a quality character beyond the reference's table (133 entries)
 
+// One file's piece of text in a run (dv_run_text) and what was found in it
+struct DvTextFile {
+    DevBuf text, nl, ls;          // the piece, newlines per 16 bytes (scanned in place), line starts
+    DevBuf rlf, rl;               // FASTA / one read per line: read-line flags (scanned in place), the lines that are reads
+    uint64_t len = 0;             // bytes of the piece
+    uint32_t nls = 0, lines = 0;  // newlines; std::getline lines (a last one without a newline counts once nothing follows)
+    uint32_t rec = 0;             // whole records: lines / 4 (FASTQ), read lines (FASTA, one read per line)
+    DevBufList bufs() { return {&text, &nl, &ls, &rlf, &rl}; }
+};
+
 struct pgrc_divider : PgrcDev {
     pgrc_divide_params prm{};
     int suffix_pos = 0;
     DevBuf d_reads, d_quals, d_flags, d_high, d_cls, d_cnt[3], d_bsum, d_rows[3], d_idx[2], d_lut, d_err;
-    DevBuf d_text[2], d_nl[2], d_ls[2];   // FASTQ text of one or two files, newlines per 16 bytes, line starts
-    DevBuf d_rlf[2], d_rl[2], d_ends;     // FASTA / one read per line: read-line flags (scanned in place), read lines, where the records taken end
+    DvTextFile file[2];           // text in: the file and its pair file
+    DevBuf d_ends;                // FASTA / one read per line: where the records taken end in each text
+    DevBufList bufs() {
+        DevBufList all = {&d_reads, &d_quals, &d_flags, &d_high, &d_cls, &d_cnt[0], &d_cnt[1], &d_cnt[2], &d_bsum, &d_rows[0], &d_rows[1], &d_rows[2],
+                          &d_idx[0], &d_idx[1], &d_lut, &d_err, &d_ends};
+        for (DvTextFile &t : file)
+            for (DevBuf *b : t.bufs()) all.push_back(b);
+        return all;
+    }
     // the results of a run on the host: pinned, grow-only, the divider's (fresh pageable pages would be touched for the first
     // time by the copy, at one thread's page-fault rate: 11 GB/s against the link's 56)
     struct HostBuf { void *p = nullptr; size_t bytes = 0; } h_rows[3], h_idx[2];
@@ -223,7 +242,7 @@ k_dv_pack(const DvPackArgs a) {
     if (b == 0 && c != DV_HQ) a.idx[c - 1][slot] = (uint32_t)r;
 }
 
-// ---- FASTQ text: lines and rows
+// ---- text of any format: lines
 // newlines per 16 bytes (entry n16: 0, the end of the scan)
 __global__ void __launch_bounds__(256)
 k_fq_count(const uint8_t *__restrict__ text, uint64_t bytes, uint64_t n16, uint32_t *__restrict__ cnt) {
@@ -255,15 +274,6 @@ k_fq_starts(const uint8_t *__restrict__ text, uint64_t bytes, uint64_t n16, cons
         if (((w[k >> 2] >> (8 * (k & 3))) & 255u) == '\n') ls[++j] = (uint32_t)(16 * i + k + 1);
 }
 
-struct FqRowsArgs {
-    const uint8_t *text[2];
-    const uint32_t *ls[2];
-    uint32_t len[2], nl[2];     // bytes and newlines of each text
-    uint32_t paired, rc_second, L;
-    uint64_t n;
-    uint8_t *reads, *quals;     // quals: null when the division does not ask them
-    uint32_t *err;
-};
 __device__ __forceinline__ bool fq_alpha(uint32_t ch) { return (ch - 'A') < 26u || (ch - 'a') < 26u; }
 // What PgHelpers' complement table does to a symbol of the second file's reads (utils/helper.cpp:261-282): both cases of
 // A C G T N U and of the IUPAC pairs Y/R K/M B/V D/H map to the UPPER-case complement (so a lower-case `a` comes out as a
@@ -286,38 +296,6 @@ __device__ __forceinline__ uint32_t fq_complement(uint32_t ch) {
     case 'h': return 'D';
     case 'v': return 'B';
     default: return 0u;
-    }
-}
-
-// record k of the batch = record k (or k / 2 of file k % 2) of the text: column x < L copies symbol and quality character,
-// column L checks that the run of letters ends there (FASTQReadsSourceIterator::moveNext, :218-220)
-__global__ void __launch_bounds__(256)
-k_fq_rows(const FqRowsArgs a) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t k = g / (a.L + 1);
-    const uint32_t x = (uint32_t)(g % (a.L + 1));
-    if (k >= a.n) return;
-    const uint32_t f = a.paired ? (uint32_t)(k & 1) : 0u;
-    const uint64_t r = a.paired ? k >> 1 : k;
-    const uint8_t *t = a.text[f];
-    const uint32_t *ls = a.ls[f];
-    // line j spans [ls[j], ls[j + 1] - 1) -- up to its newline --, a last line without one [ls[j], ls[j + 1]) = up to the end
-    const uint32_t nl = a.nl[f];
-    const uint32_t j1 = (uint32_t)(4 * r + 1), j3 = j1 + 2;
-    const uint32_t s = ls[j1];
-    const uint32_t e = ls[j1 + 1] - (j1 < nl ? 1u : 0u);
-    const uint32_t ch = (s + x < e) ? t[s + x] : 0u;
-    if (x == a.L) {
-        if (fq_alpha(ch)) atomicOr(a.err, 1u);                         // the read is longer than read_len
-        return;
-    }
-    if (!fq_alpha(ch)) atomicOr(a.err, 1u);                            // ... or shorter
-    const bool rc = a.rc_second && f == 1;
-    a.reads[k * a.L + (rc ? a.L - 1 - x : x)] = (uint8_t)(rc ? fq_complement(ch) : ch);
-    if (a.quals) {
-        const uint32_t qs = ls[j3];
-        const uint32_t qe = ls[j3 + 1] - (j3 < nl ? 1u : 0u);
-        a.quals[k * a.L + x] = (qs + x < qe) ? t[qs + x] : (uint8_t)0;  // quality.resize(length): cut or zero-padded, never reversed
     }
 }
 
@@ -350,18 +328,23 @@ k_tx_compact(const uint32_t *__restrict__ before, uint32_t lines, uint32_t *__re
     if (before[j + 1] != k) rl[k] = (uint32_t)j;
 }
 
-struct TxRowsArgs {
+// ---- the records' rows, from text of any of the three formats
+struct DvRowsArgs {
     const uint8_t *text[2];
-    const uint32_t *ls[2], *rl[2];
-    uint32_t nl[2], take[2];    // newlines of each text; reads taken from it
+    const uint32_t *ls[2], *rl[2];  // line starts; FASTA / one read per line: the line of every read
+    uint32_t nl[2], take[2];        // newlines of each text; FASTA / one read per line: reads taken from it
     uint32_t paired, rc_second, L;
     uint64_t n;
-    uint8_t *reads;
-    uint32_t *err, *ends;       // ends[f]: the first byte after the last read line taken from text f
+    uint8_t *reads, *quals;         // quals (FASTQ): null when the division does not ask them
+    uint32_t *err, *ends;           // ends[f] (FASTA / one read per line): the first byte after the last read line taken from text f
 };
-// k_fq_rows without the quality column: record k of the batch = read k (or k / 2 of file k % 2), its line taken from rl
+// record k of the batch = record k (or k / 2 of file k % 2) of the text, its symbols on line 4 * r + 1 (FASTQ) or rl[r]:
+// column x < L copies the symbol (FASTQ: and the quality character, two lines on), column L checks that the run of letters
+// ends there (FASTQReadsSourceIterator::moveNext, :218-220).  FASTQ's records end where line 4 * take starts, which the host
+// reads from ls; the other formats' thread of the last read taken writes where its line ends.
+template <bool FASTQ>
 __global__ void __launch_bounds__(256)
-k_tx_rows(const TxRowsArgs a) {
+k_dv_rows(const DvRowsArgs a) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t k = g / (a.L + 1);
     const uint32_t x = (uint32_t)(g % (a.L + 1));
@@ -370,19 +353,26 @@ k_tx_rows(const TxRowsArgs a) {
     const uint32_t r = (uint32_t)(a.paired ? k >> 1 : k);
     const uint8_t *t = a.text[f];
     const uint32_t *ls = a.ls[f];
-    const uint32_t j = a.rl[f][r];
+    // line j spans [ls[j], ls[j + 1] - 1) -- up to its newline --, a last line without one [ls[j], ls[j + 1]) = up to the end
+    const uint32_t j = FASTQ ? 4 * r + 1 : a.rl[f][r];
     const uint32_t s = ls[j];
     const uint32_t next = ls[j + 1];                                   // (j <= nl, and ls has nl + 7 entries)
-    const uint32_t e = next - (j < a.nl[f] ? 1u : 0u);                 // up to the newline; a last line without one: up to the end
+    const uint32_t e = next - (j < a.nl[f] ? 1u : 0u);
     const uint32_t ch = (s + x < e) ? t[s + x] : 0u;
     if (x == a.L) {
         if (fq_alpha(ch)) atomicOr(a.err, 1u);                         // the read is longer than read_len
-        if (r + 1 == a.take[f]) a.ends[f] = next;
+        if (!FASTQ && r + 1 == a.take[f]) a.ends[f] = next;
         return;
     }
     if (!fq_alpha(ch)) atomicOr(a.err, 1u);                            // ... or shorter
     const bool rc = a.rc_second && f == 1;
     a.reads[k * a.L + (rc ? a.L - 1 - x : x)] = (uint8_t)(rc ? fq_complement(ch) : ch);
+    if (FASTQ && a.quals) {
+        const uint32_t j3 = j + 2;
+        const uint32_t qs = ls[j3];
+        const uint32_t qe = ls[j3 + 1] - (j3 < a.nl[f] ? 1u : 0u);
+        a.quals[k * a.L + x] = (qs + x < qe) ? t[qs + x] : (uint8_t)0;  // quality.resize(length): cut or zero-padded, never reversed
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -443,11 +433,7 @@ void pgrc_divider_destroy(pgrc_divider *d) {
     if (!d) return;
     PgrcDeviceScope scope(d->device);
     (void)hipDeviceSynchronize();
-    DevBuf *bufs[] = {&d->d_reads, &d->d_quals, &d->d_flags, &d->d_high, &d->d_cls, &d->d_cnt[0], &d->d_cnt[1], &d->d_cnt[2], &d->d_bsum,
-                      &d->d_rows[0], &d->d_rows[1], &d->d_rows[2], &d->d_idx[0], &d->d_idx[1], &d->d_lut, &d->d_err,
-                      &d->d_text[0], &d->d_text[1], &d->d_nl[0], &d->d_nl[1], &d->d_ls[0], &d->d_ls[1],
-                      &d->d_rlf[0], &d->d_rlf[1], &d->d_rl[0], &d->d_rl[1], &d->d_ends};
-    for (DevBuf *b : bufs) pgrc_buf_free(*b);
+    for (DevBuf *b : d->bufs()) pgrc_buf_free(*b);
     for (auto *h : {&d->h_rows[0], &d->h_rows[1], &d->h_rows[2], &d->h_idx[0], &d->h_idx[1]})
         if (h->p) (void)hipHostFree(h->p);
     d->ev.release();
@@ -604,98 +590,155 @@ int pgrc_divider_run(pgrc_divider *d, const char *reads, const char *quals, uint
     return divide_resident(d, n, out);
 }
 
-// ---- FASTQ text in, sets out (FASTQReadsSourceIterator, readsset/iterator/ReadsSetIterator.cpp:189-224; the pairing and the
+}   // extern "C"
+
+// ---- text in, sets out.  FASTQ (FASTQReadsSourceIterator, readsset/iterator/ReadsSetIterator.cpp:189-224; the pairing and the
 // reverse complement of the second file's reads, RevComplPairReadsSetIterator, :256-284; ManagedReadsSetIterator,
-// readsset/persistance/ReadsSetPersistence.cpp:20-56).  The reference reads four lines per record with std::getline --
+// readsset/persistance/ReadsSetPersistence.cpp:20-56): the reference reads four lines per record with std::getline --
 // identifier, symbols, '+' line, qualities --, alternately from the two files of a pair; the read is the leading run of
-// letters of the symbol line, the quality string is cut or zero-padded to that length.  Here the caller hands over a piece
-// of each file's text; the lines are found by all threads (newlines counted per 16 bytes, an exclusive scan, line starts
-// written in place), the records' rows are copied out byte-parallel -- every second record of a pair reverse-complemented
-// when asked -- and the division above runs on them where they are: the text goes up once, nothing else.
-int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes,
-                           int32_t rev_compl_pair, int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed,
-                           uint64_t *n_records, pgrc_divided_reads *out) {
+// letters of the symbol line, the quality string is cut or zero-padded to that length.  FASTA and one read per line
+// (FASTAReadsSourceIterator and ConcatenatedReadsSourceIterator, :118-134 and :66-76): every line, or every line whose first
+// byte is neither '>' nor ';', is a read.  Here the caller hands over a piece of each file's text; the lines are found by all
+// threads (dv_find_lines), for the two other formats the read lines among them (dv_read_lines), the records' rows are copied
+// out byte-parallel (k_dv_rows) -- every second record of a pair reverse-complemented when asked -- and the division above
+// runs on them where they are: the text goes up once, nothing else.
+
+// The lines of file f's piece: newlines counted per 16 bytes, an exclusive scan, line starts written in place.  One host wait:
+// the number of newlines sizes the array of line starts.
+static int dv_find_lines(pgrc_divider *d, int f, const char *src, uint64_t len, bool fin) {
+    DvTextFile &t = d->file[f];
+    hipStream_t s = d->stream;
+    const uint64_t n16 = (len + 15) / 16;
+    int e;
+    if ((e = pgrc_buf_ensure(d, t.text, len + 32)) || (e = pgrc_buf_ensure(d, t.nl, (n16 + 1) * sizeof(uint32_t))) ||
+        (e = pgrc_buf_ensure(d, d->d_bsum, pgrc_ps_scan_blocks(n16 + 1) * sizeof(uint32_t))))
+        return e;
+    if (len) HIP_TRY(d, hipMemcpyAsync(t.text.p, src, len, hipMemcpyHostToDevice, s));
+    HIP_TRY(d, hipMemsetAsync((uint8_t *)t.text.p + len, 0, 32, s));                   // the 16-byte loads run past the end
+    hipLaunchKernelGGL(k_fq_count, dim3((uint32_t)((n16 + 1 + 255) / 256)), dim3(256), 0, s, (const uint8_t *)t.text.p, len, n16, (uint32_t *)t.nl.p);
+    if ((e = pgrc_ps_scan_u32(d, s, (uint32_t *)t.nl.p, n16 + 1, (uint32_t *)d->d_bsum.p))) return e;
+    uint32_t nl = 0;
+    HIP_TRY(d, hipMemcpyAsync(&nl, (const uint32_t *)t.nl.p + n16, sizeof nl, hipMemcpyDeviceToHost, s));
+    HIP_TRY(d, hipStreamSynchronize(s));
+    t.len = len;
+    t.nls = nl;
+    // std::getline: a last piece without its newline is a line too, once nothing more will come
+    t.lines = nl + ((fin && len && src[len - 1] != '\n') ? 1u : 0u);
+    if ((e = pgrc_buf_ensure(d, t.ls, ((size_t)nl + 8) * sizeof(uint32_t)))) return e;
+    hipLaunchKernelGGL(k_fq_starts, dim3((uint32_t)((n16 + 255) / 256 + 1)), dim3(256), 0, s, (const uint8_t *)t.text.p, len, n16,
+                       (const uint32_t *)t.nl.p, nl, (uint32_t *)t.ls.p);
+    HIP_TRY(d, hipGetLastError());
+    return PGRC_OK;
+}
+
+// FASTA and one read per line: which of file f's lines are reads is a flag per line, their places an exclusive scan of the
+// flags, the list of read lines a compaction.  The number of reads is on its way to t.rec when this returns: the caller
+// waits once for both files.
+static int dv_read_lines(pgrc_divider *d, int f, bool fasta) {
+    DvTextFile &t = d->file[f];
+    hipStream_t s = d->stream;
+    int e;
+    if ((e = pgrc_buf_ensure(d, t.rlf, ((size_t)t.lines + 1) * sizeof(uint32_t))) || (e = pgrc_buf_ensure(d, t.rl, ((size_t)t.lines + 1) * sizeof(uint32_t))) ||
+        (e = pgrc_buf_ensure(d, d->d_bsum, pgrc_ps_scan_blocks((uint64_t)t.lines + 1) * sizeof(uint32_t))))
+        return e;
+    hipLaunchKernelGGL(k_tx_flags, dim3((t.lines + 1 + 255) / 256), dim3(256), 0, s, (const uint8_t *)t.text.p, (uint32_t)t.len, (const uint32_t *)t.ls.p,
+                       t.lines, fasta ? 1u : 0u, (uint32_t *)t.rlf.p);
+    HIP_TRY(d, hipGetLastError());
+    if ((e = pgrc_ps_scan_u32(d, s, (uint32_t *)t.rlf.p, (uint64_t)t.lines + 1, (uint32_t *)d->d_bsum.p))) return e;
+    if (t.lines) {
+        hipLaunchKernelGGL(k_tx_compact, dim3((t.lines + 255) / 256), dim3(256), 0, s, (const uint32_t *)t.rlf.p, t.lines, (uint32_t *)t.rl.p);
+        HIP_TRY(d, hipGetLastError());
+    }
+    HIP_TRY(d, hipMemcpyAsync(&t.rec, (const uint32_t *)t.rlf.p + t.lines, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    return PGRC_OK;
+}
+
+// What a call takes of the rec[f] whole records its pieces hold: n records, the two files of a pair in turn, first file
+// first, until one of them has no more; take[f] of them from file f.
+// `terminal`: the reference's iteration ends with this call -- a source is through when its turn comes (it stops at the
+// first exhausted file).  One text may end here while the other goes on (fin[f] alone): the pairs its records form are
+// taken as soon as the other piece holds their mates, whatever lies beyond them there.
+static void dv_take(bool paired, const bool fin[2], const uint64_t rec[2], uint64_t *n, uint64_t take[2], bool *terminal) {
+    if (!paired) { *n = rec[0]; take[0] = rec[0]; take[1] = 0; *terminal = fin[0]; }
+    else if ((fin[0] && fin[1]) || (fin[0] && rec[1] >= rec[0]) || (fin[1] && rec[0] >= rec[1] + 1)) {
+        *n = rec[0] <= rec[1] ? 2 * rec[0] : 2 * rec[1] + 1; take[0] = (*n + 1) / 2; take[1] = *n / 2; *terminal = true;
+    } else { const uint64_t m = std::min(rec[0], rec[1]); *n = 2 * m; take[0] = take[1] = m; *terminal = false; }
+}
+
+// The body of pgrc_divider_run_fastq and pgrc_divider_run_text.  Host waits: one per file (dv_find_lines), FASTA / one read
+// per line one more for the numbers of reads of both texts, and one behind the rows kernel when records are taken.
+static int dv_run_text(pgrc_divider *d, int32_t format, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes,
+                       int32_t rev_compl_pair, int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed, uint64_t *n_records,
+                       pgrc_divided_reads *out) {
     if (!d || !out || !consumed || !n_records || (bytes && !text) || (pair_bytes && !pair_text) || (pair_text && !pair_consumed)) return PGRC_E_PARAM;
+    const bool fastq = format == PGRC_READS_FASTQ;
+    if (!fastq) {
+        // refused before anything of the divider changes: the sets of its last run stay its last
+        if (format != PGRC_READS_FASTA && format != PGRC_READS_LINES) { d->err = "divider: unknown text format " + std::to_string(format); return PGRC_E_PARAM; }
+        if (format == PGRC_READS_LINES && (pair_text || rev_compl_pair)) {
+            d->err = "divider: one-read-per-line text has no pair file (the reference ignores it silently)";
+            return PGRC_E_PARAM;
+        }
+        if (d->prm.error_limit < 1) { d->err = "divider: FASTA and one-read-per-line text carry no qualities: error_limit must be >= 1"; return PGRC_E_PARAM; }
+        if (bytes >= (1ull << 31) || pair_bytes >= (1ull << 31)) { d->err = "divider: pieces of text below 2 GiB"; return PGRC_E_PARAM; }
+    }
     d->last_valid = false;
     memset(out, 0, sizeof *out);
     *consumed = 0;
     *n_records = 0;
     if (pair_consumed) *pair_consumed = 0;
-    PgrcDev *c = d;
-    if (bytes >= (1ull << 31) || pair_bytes >= (1ull << 31)) { c->err = "divider: pieces of FASTQ text below 2 GiB"; return PGRC_E_PARAM; }
-    PgrcDeviceScope scope(c->device);
-    if (!scope.ok) { c->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
+    if (fastq && (bytes >= (1ull << 31) || pair_bytes >= (1ull << 31))) { d->err = "divider: pieces of FASTQ text below 2 GiB"; return PGRC_E_PARAM; }
+    PgrcDeviceScope scope(d->device);
+    if (!scope.ok) { d->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
     int e;
     if ((e = d->ev.ensure(d))) return e;
     const uint32_t L = d->prm.read_len;
     const bool paired = pair_text != nullptr;
-    const bool by_quality = d->prm.error_limit < 1;
-    hipStream_t s = c->stream;
+    const int nf = paired ? 2 : 1;
+    const bool by_quality = d->prm.error_limit < 1;       // (FASTQ only: the other formats were refused above)
+    hipStream_t s = d->stream;
     const char *src[2] = {text, pair_text};
     const uint64_t len[2] = {bytes, pair_bytes};
     // final_piece: bit 0 = nothing follows in either text; bit 1 / bit 2 = the first / the second text ends here (the other may go on)
     const bool fin[2] = {(final_piece & 3) != 0, (final_piece & 5) != 0};
-    uint64_t lines[2] = {0, 0};
-    uint32_t nls[2] = {0, 0};
+    for (DvTextFile &t : d->file) { t.len = 0; t.nls = t.lines = t.rec = 0; }   // (nothing of the last run's; a single file leaves the second one's slots empty)
     (void)d->ev.record(0, s);
-    for (int f = 0; f < (paired ? 2 : 1); f++) {
-        const uint64_t n16 = (len[f] + 15) / 16;
-        if ((e = pgrc_buf_ensure(c, d->d_text[f], len[f] + 32)) || (e = pgrc_buf_ensure(c, d->d_nl[f], (n16 + 1) * sizeof(uint32_t))) ||
-            (e = pgrc_buf_ensure(c, d->d_bsum, pgrc_ps_scan_blocks(n16 + 1) * sizeof(uint32_t))))
-            return e;
-        if (len[f]) HIP_TRY(d, hipMemcpyAsync(d->d_text[f].p, src[f], len[f], hipMemcpyHostToDevice, s));
-        HIP_TRY(d, hipMemsetAsync((uint8_t *)d->d_text[f].p + len[f], 0, 32, s));
-        hipLaunchKernelGGL(k_fq_count, dim3((uint32_t)((n16 + 1 + 255) / 256)), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, len[f], n16,
-                           (uint32_t *)d->d_nl[f].p);
-        if ((e = pgrc_ps_scan_u32(c, c->stream, (uint32_t *)d->d_nl[f].p, n16 + 1, (uint32_t *)d->d_bsum.p))) return e;
-        uint32_t nl = 0;
-        uint8_t last = '\n';
-        HIP_TRY(d, hipMemcpyAsync(&nl, (const uint32_t *)d->d_nl[f].p + n16, sizeof nl, hipMemcpyDeviceToHost, s));
-        HIP_TRY(d, hipStreamSynchronize(s));
-        if (len[f]) last = (uint8_t)src[f][len[f] - 1];
-        // std::getline: a last piece without its newline is a line too, once nothing more will come
-        lines[f] = nl + ((fin[f] && len[f] && last != '\n') ? 1u : 0u);
-        nls[f] = nl;
-        if ((e = pgrc_buf_ensure(c, d->d_ls[f], ((size_t)nl + 8) * sizeof(uint32_t)))) return e;
-        hipLaunchKernelGGL(k_fq_starts, dim3((uint32_t)((n16 + 255) / 256 + 1)), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, len[f], n16,
-                           (const uint32_t *)d->d_nl[f].p, nl, (uint32_t *)d->d_ls[f].p);
-        HIP_TRY(d, hipGetLastError());
-    }
-    // whole records in what we have: four lines each
-    const uint64_t rec[2] = {lines[0] / 4, lines[1] / 4};
-    uint64_t n;                       // records taken: the two files in turn, first file first, until one of them has no more
-    uint64_t take[2];
-    // `terminal`: the reference's iteration ends with this call -- a source is through when its turn comes (it stops at the
-    // first exhausted file).  One text may end here while the other goes on (final_piece bits 2 / 4): the pairs its records
-    // form are taken as soon as the other piece holds their mates, whatever lies beyond them there.
+    for (int f = 0; f < nf; f++)
+        if ((e = dv_find_lines(d, f, src[f], len[f], fin[f])) || (!fastq && (e = dv_read_lines(d, f, format == PGRC_READS_FASTA)))) return e;
+    if (!fastq) HIP_TRY(d, hipStreamSynchronize(s));                                   // rec: the read lines each piece holds
+    else for (int f = 0; f < nf; f++) d->file[f].rec = d->file[f].lines / 4;           // whole records in what we have: four lines each
+    const uint64_t rec[2] = {d->file[0].rec, d->file[1].rec};
+    uint64_t n, take[2];
     bool terminal;
-    if (!paired) { n = rec[0]; take[0] = rec[0]; take[1] = 0; terminal = fin[0]; }
-    else if ((fin[0] && fin[1]) || (fin[0] && rec[1] >= rec[0]) || (fin[1] && rec[0] >= rec[1] + 1)) {
-        n = rec[0] <= rec[1] ? 2 * rec[0] : 2 * rec[1] + 1; take[0] = (n + 1) / 2; take[1] = n / 2; terminal = true;
-    } else { const uint64_t m = std::min(rec[0], rec[1]); n = 2 * m; take[0] = take[1] = m; terminal = false; }
+    dv_take(paired, fin, rec, &n, take, &terminal);
     d->last_terminal = terminal;
-    if (terminal && fin[paired ? (int)(n & 1) : 0]) {
+    if (fastq && terminal && fin[paired ? (int)(n & 1) : 0]) {
         // The record the reference would read next: none (its source is through: it stops) -- or the beginning of one.  What it
         // makes of a cut-off last record depends on state left over in its iterator (a std::getline on a stream already at
-        // its end leaves the string of the record BEFORE in place): not reproduced, reported instead.
+        // its end leaves the string of the record BEFORE in place): not reproduced, reported instead.  (FASTA and one read
+        // per line have no such case: header lines behind the last read taken come again with the next piece.)
         const int f = paired ? (int)(n & 1) : 0;
-        if (lines[f] % 4 && rec[f] == (paired ? n >> 1 : n)) {
-            c->err = "FASTQ text ends inside a record";
+        if (d->file[f].lines % 4 && rec[f] == (paired ? n >> 1 : n)) {
+            d->err = "FASTQ text ends inside a record";
             return PGRC_E_PARAM;
         }
     }
-    if (n >= (1ull << 32) - 1) { c->err = "divider: batches of less than 2^32 - 1 reads"; return PGRC_E_PARAM; }
+    if (n >= (1ull << 32) - 1) { d->err = "divider: batches of less than 2^32 - 1 reads"; return PGRC_E_PARAM; }
     const size_t rows = (size_t)n * L;
-    if ((e = pgrc_buf_ensure(c, d->d_reads, rows + 16)) || (by_quality && (e = pgrc_buf_ensure(c, d->d_quals, rows + 16)))) return e;
-    HIP_TRY(d, hipMemsetAsync(d->d_err.p, 0, sizeof(uint32_t), s));
+    if ((e = pgrc_buf_ensure(d, d->d_reads, rows + 16)) || (by_quality && (e = pgrc_buf_ensure(d, d->d_quals, rows + 16))) ||
+        (!fastq && (e = pgrc_buf_ensure(d, d->d_ends, 2 * sizeof(uint32_t)))))
+        return e;
     uint32_t ends[2] = {0, 0};        // first byte after the last record taken from each piece
     if (n) {
-        FqRowsArgs a;
+        HIP_TRY(d, hipMemsetAsync(d->d_err.p, 0, sizeof(uint32_t), s));
+        if (!fastq) HIP_TRY(d, hipMemsetAsync(d->d_ends.p, 0, sizeof ends, s));
+        DvRowsArgs a;
         for (int f = 0; f < 2; f++) {
-            a.text[f] = (const uint8_t *)d->d_text[f].p;
-            a.ls[f] = (const uint32_t *)d->d_ls[f].p;
-            a.len[f] = (uint32_t)len[f];
-            a.nl[f] = nls[f];
+            a.text[f] = (const uint8_t *)d->file[f].text.p;
+            a.ls[f] = (const uint32_t *)d->file[f].ls.p;
+            a.rl[f] = (const uint32_t *)d->file[f].rl.p;
+            a.nl[f] = d->file[f].nls;
+            a.take[f] = (uint32_t)take[f];
         }
         a.paired = paired ? 1u : 0u;
         a.rc_second = (paired && rev_compl_pair) ? 1u : 0u;
@@ -704,15 +747,21 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
         a.reads = (uint8_t *)d->d_reads.p;
         a.quals = by_quality ? (uint8_t *)d->d_quals.p : nullptr;
         a.err = (uint32_t *)d->d_err.p;
+        a.ends = (uint32_t *)d->d_ends.p;
         const uint64_t work = n * (L + 1);
-        hipLaunchKernelGGL(k_fq_rows, dim3((uint32_t)((work + 255) / 256)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((fastq ? k_dv_rows<true> : k_dv_rows<false>), dim3((uint32_t)((work + 255) / 256)), dim3(256), 0, s, a);
         HIP_TRY(d, hipGetLastError());
         uint32_t bad = 0;
         HIP_TRY(d, hipMemcpyAsync(&bad, d->d_err.p, sizeof bad, hipMemcpyDeviceToHost, s));
-        for (int f = 0; f < (paired ? 2 : 1); f++)         // line 4 * take starts where the records taken end (ls[nl + 1] = the end of the text)
-            if (take[f]) HIP_TRY(d, hipMemcpyAsync(&ends[f], (const uint32_t *)d->d_ls[f].p + 4 * take[f], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (!fastq) HIP_TRY(d, hipMemcpyAsync(ends, d->d_ends.p, sizeof ends, hipMemcpyDeviceToHost, s));
+        else for (int f = 0; f < nf; f++)                 // line 4 * take starts where the records taken end (ls[nl + 1] = the end of the text)
+            if (take[f]) HIP_TRY(d, hipMemcpyAsync(&ends[f], (const uint32_t *)d->file[f].ls.p + 4 * take[f], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(d, hipStreamSynchronize(s));
-        if (bad) { c->err = "Unsupported variable length reads (a FASTQ record whose read is not read_len letters long)"; return PGRC_E_PARAM; }
+        if (bad) {
+            d->err = fastq ? "Unsupported variable length reads (a FASTQ record whose read is not read_len letters long)"
+                           : "Unsupported variable length reads (a read line whose read is not read_len letters long)";
+            return PGRC_E_PARAM;
+        }
     }
     *consumed = ends[0];
     if (paired) *pair_consumed = ends[1];
@@ -721,123 +770,19 @@ int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, co
     return divide_resident(d, n, out);
 }
 
-// ---- FASTA and one-read-per-line text in, sets out (FASTAReadsSourceIterator and ConcatenatedReadsSourceIterator,
-// readsset/iterator/ReadsSetIterator.cpp:118-134 and :66-76).  The lines are found as for FASTQ text; which of them are reads
-// is a flag per line, their places an exclusive scan of the flags, the list of read lines a compaction.  The rows kernel takes
-// read k's line from that list; the division runs on the rows where they lie.  One host wait more than the FASTQ path: the
-// numbers of reads of both texts, fetched together.
+extern "C" {
+
+int pgrc_divider_run_fastq(pgrc_divider *d, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes,
+                           int32_t rev_compl_pair, int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed,
+                           uint64_t *n_records, pgrc_divided_reads *out) {
+    return dv_run_text(d, PGRC_READS_FASTQ, text, bytes, pair_text, pair_bytes, rev_compl_pair, final_piece, consumed, pair_consumed, n_records, out);
+}
+
 int pgrc_divider_run_text(pgrc_divider *d, int32_t format, const char *text, uint64_t bytes, const char *pair_text, uint64_t pair_bytes,
                           int32_t rev_compl_pair, int32_t final_piece, uint64_t *consumed, uint64_t *pair_consumed,
                           uint64_t *n_records, pgrc_divided_reads *out) {
-    if (format == PGRC_READS_FASTQ)
-        return pgrc_divider_run_fastq(d, text, bytes, pair_text, pair_bytes, rev_compl_pair, final_piece, consumed, pair_consumed, n_records, out);
-    if (!d || !out || !consumed || !n_records || (bytes && !text) || (pair_bytes && !pair_text) || (pair_text && !pair_consumed)) return PGRC_E_PARAM;
-    PgrcDev *c = d;
-    // refused before anything of the divider changes: the sets of its last run stay its last
-    if (format != PGRC_READS_FASTA && format != PGRC_READS_LINES) { c->err = "divider: unknown text format " + std::to_string(format); return PGRC_E_PARAM; }
-    if (format == PGRC_READS_LINES && (pair_text || rev_compl_pair)) {
-        c->err = "divider: one-read-per-line text has no pair file (the reference ignores it silently)";
-        return PGRC_E_PARAM;
-    }
-    if (d->prm.error_limit < 1) { c->err = "divider: FASTA and one-read-per-line text carry no qualities: error_limit must be >= 1"; return PGRC_E_PARAM; }
-    if (bytes >= (1ull << 31) || pair_bytes >= (1ull << 31)) { c->err = "divider: pieces of text below 2 GiB"; return PGRC_E_PARAM; }
-    d->last_valid = false;
-    memset(out, 0, sizeof *out);
-    *consumed = 0;
-    *n_records = 0;
-    if (pair_consumed) *pair_consumed = 0;
-    PgrcDeviceScope scope(c->device);
-    if (!scope.ok) { c->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
-    int e;
-    if ((e = d->ev.ensure(d))) return e;
-    const uint32_t L = d->prm.read_len;
-    const bool paired = pair_text != nullptr;
-    const int nf = paired ? 2 : 1;
-    hipStream_t s = c->stream;
-    const char *src[2] = {text, pair_text};
-    const uint64_t len[2] = {bytes, pair_bytes};
-    const bool fin[2] = {(final_piece & 3) != 0, (final_piece & 5) != 0};      // (as pgrc_divider_run_fastq)
-    uint32_t lines[2] = {0, 0}, nls[2] = {0, 0}, rec[2] = {0, 0};
-    (void)d->ev.record(0, s);
-    for (int f = 0; f < nf; f++) {
-        const uint64_t n16 = (len[f] + 15) / 16;
-        if ((e = pgrc_buf_ensure(c, d->d_text[f], len[f] + 32)) || (e = pgrc_buf_ensure(c, d->d_nl[f], (n16 + 1) * sizeof(uint32_t))) ||
-            (e = pgrc_buf_ensure(c, d->d_bsum, pgrc_ps_scan_blocks(n16 + 1) * sizeof(uint32_t))))
-            return e;
-        if (len[f]) HIP_TRY(d, hipMemcpyAsync(d->d_text[f].p, src[f], len[f], hipMemcpyHostToDevice, s));
-        HIP_TRY(d, hipMemsetAsync((uint8_t *)d->d_text[f].p + len[f], 0, 32, s));         // the 16-byte loads run past the end
-        hipLaunchKernelGGL(k_fq_count, dim3((uint32_t)((n16 + 1 + 255) / 256)), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, len[f], n16,
-                           (uint32_t *)d->d_nl[f].p);
-        if ((e = pgrc_ps_scan_u32(c, s, (uint32_t *)d->d_nl[f].p, n16 + 1, (uint32_t *)d->d_bsum.p))) return e;
-        uint32_t nl = 0;
-        HIP_TRY(d, hipMemcpyAsync(&nl, (const uint32_t *)d->d_nl[f].p + n16, sizeof nl, hipMemcpyDeviceToHost, s));
-        HIP_TRY(d, hipStreamSynchronize(s));
-        // std::getline: a last piece without its newline is a line too, once nothing more will come
-        lines[f] = nl + ((fin[f] && len[f] && src[f][len[f] - 1] != '\n') ? 1u : 0u);
-        nls[f] = nl;
-        if ((e = pgrc_buf_ensure(c, d->d_ls[f], ((size_t)nl + 8) * sizeof(uint32_t))) ||
-            (e = pgrc_buf_ensure(c, d->d_rlf[f], ((size_t)lines[f] + 1) * sizeof(uint32_t))) ||
-            (e = pgrc_buf_ensure(c, d->d_rl[f], ((size_t)lines[f] + 1) * sizeof(uint32_t))) ||
-            (e = pgrc_buf_ensure(c, d->d_bsum, pgrc_ps_scan_blocks((uint64_t)lines[f] + 1) * sizeof(uint32_t))))
-            return e;
-        hipLaunchKernelGGL(k_fq_starts, dim3((uint32_t)((n16 + 255) / 256 + 1)), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, len[f], n16,
-                           (const uint32_t *)d->d_nl[f].p, nl, (uint32_t *)d->d_ls[f].p);
-        hipLaunchKernelGGL(k_tx_flags, dim3((lines[f] + 1 + 255) / 256), dim3(256), 0, s, (const uint8_t *)d->d_text[f].p, (uint32_t)len[f],
-                           (const uint32_t *)d->d_ls[f].p, lines[f], format == PGRC_READS_FASTA ? 1u : 0u, (uint32_t *)d->d_rlf[f].p);
-        HIP_TRY(d, hipGetLastError());
-        if ((e = pgrc_ps_scan_u32(c, s, (uint32_t *)d->d_rlf[f].p, (uint64_t)lines[f] + 1, (uint32_t *)d->d_bsum.p))) return e;
-        if (lines[f]) {
-            hipLaunchKernelGGL(k_tx_compact, dim3((lines[f] + 255) / 256), dim3(256), 0, s, (const uint32_t *)d->d_rlf[f].p, lines[f],
-                               (uint32_t *)d->d_rl[f].p);
-            HIP_TRY(d, hipGetLastError());
-        }
-        HIP_TRY(d, hipMemcpyAsync(&rec[f], (const uint32_t *)d->d_rlf[f].p + lines[f], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(d, hipStreamSynchronize(s));                   // rec[]: the read lines each piece holds
-    // records taken and `terminal`: the rule of pgrc_divider_run_fastq, with read lines where it has lines / 4
-    uint64_t n;
-    uint32_t take[2];
-    bool terminal;
-    if (!paired) { n = rec[0]; take[0] = rec[0]; take[1] = 0; terminal = fin[0]; }
-    else if ((fin[0] && fin[1]) || (fin[0] && rec[1] >= rec[0]) || (fin[1] && rec[0] >= rec[1] + 1)) {
-        n = rec[0] <= rec[1] ? 2 * (uint64_t)rec[0] : 2 * (uint64_t)rec[1] + 1; take[0] = (uint32_t)((n + 1) / 2); take[1] = (uint32_t)(n / 2); terminal = true;
-    } else { const uint32_t m = std::min(rec[0], rec[1]); n = 2 * (uint64_t)m; take[0] = take[1] = m; terminal = false; }
-    d->last_terminal = terminal;
-    if (n >= (1ull << 32) - 1) { c->err = "divider: batches of less than 2^32 - 1 reads"; return PGRC_E_PARAM; }
-    uint32_t ends[2] = {0, 0};        // first byte after the last read line taken from each piece; header lines behind it come again
-    if (n) {
-        if ((e = pgrc_buf_ensure(c, d->d_reads, (size_t)n * L + 16)) || (e = pgrc_buf_ensure(c, d->d_ends, 2 * sizeof(uint32_t)))) return e;
-        HIP_TRY(d, hipMemsetAsync(d->d_err.p, 0, sizeof(uint32_t), s));
-        HIP_TRY(d, hipMemsetAsync(d->d_ends.p, 0, 2 * sizeof(uint32_t), s));
-        TxRowsArgs a;
-        for (int f = 0; f < 2; f++) {
-            a.text[f] = (const uint8_t *)d->d_text[f].p;
-            a.ls[f] = (const uint32_t *)d->d_ls[f].p;
-            a.rl[f] = (const uint32_t *)d->d_rl[f].p;
-            a.nl[f] = nls[f];
-            a.take[f] = take[f];
-        }
-        a.paired = paired ? 1u : 0u;
-        a.rc_second = (paired && rev_compl_pair) ? 1u : 0u;
-        a.L = L;
-        a.n = n;
-        a.reads = (uint8_t *)d->d_reads.p;
-        a.err = (uint32_t *)d->d_err.p;
-        a.ends = (uint32_t *)d->d_ends.p;
-        const uint64_t work = n * (L + 1);
-        hipLaunchKernelGGL(k_tx_rows, dim3((uint32_t)((work + 255) / 256)), dim3(256), 0, s, a);
-        HIP_TRY(d, hipGetLastError());
-        uint32_t bad = 0;
-        HIP_TRY(d, hipMemcpyAsync(&bad, d->d_err.p, sizeof bad, hipMemcpyDeviceToHost, s));
-        HIP_TRY(d, hipMemcpyAsync(ends, d->d_ends.p, sizeof ends, hipMemcpyDeviceToHost, s));
-        HIP_TRY(d, hipStreamSynchronize(s));
-        if (bad) { c->err = "Unsupported variable length reads (a read line whose read is not read_len letters long)"; return PGRC_E_PARAM; }
-    }
-    *consumed = ends[0];
-    if (paired) *pair_consumed = ends[1];
-    (void)d->ev.record(1, s);
-    *n_records = n;
-    return divide_resident(d, n, out);
+    return dv_run_text(d, format, text, bytes, pair_text, pair_bytes, rev_compl_pair, final_piece, consumed, pair_consumed, n_records, out);
 }
 
 } // extern "C"
+

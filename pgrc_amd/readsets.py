@@ -51,27 +51,13 @@ class DividedPCLReadsSets:
             qp = quals.ctypes.data_as(C.c_void_p)
         out = _lib.DividedReads()
         self._ck(lib.pgrc_divider_run(self._h, reads.ctypes.data_as(C.c_void_p), qp, n, C.byref(out)))
-
-        def arr(ptr, count, dtype):
-            if not count:
-                return np.zeros(0, dtype=dtype)
-            a = np.empty(count, dtype=dtype)                 # (the library's arrays live until the next run: copy out)
-            C.memmove(a.ctypes.data, ptr, a.nbytes)
-            return a
-        res = {"n_hq": int(out.n_hq), "n_lq": int(out.n_lq), "n_n": int(out.n_n),
-               "symbols": (int(out.hq_symbols), int(out.lq_symbols), int(out.n_symbols)),
-               "row_bytes": (int(out.hq_row_bytes), int(out.lq_row_bytes), int(out.n_row_bytes)),
-               "hq_rows": arr(out.hq_rows, out.n_hq * out.hq_row_bytes, np.uint8),
-               "lq_rows": arr(out.lq_rows, out.n_lq * out.lq_row_bytes, np.uint8),
-               "n_rows": arr(out.n_rows, out.n_n * out.n_row_bytes, np.uint8),
-               "lq_index": arr(out.lq_index, out.n_lq, np.uint32), "n_index": arr(out.n_index, out.n_n, np.uint32)}
-        return res
+        return self._result(out)
 
     def _result(self, out) -> dict:
         def arr(ptr, count, dtype):
             if not count:
                 return np.zeros(0, dtype=dtype)
-            a = np.empty(count, dtype=dtype)
+            a = np.empty(count, dtype=dtype)                 # (the library's arrays live until the next run: copy out)
             C.memmove(a.ctypes.data, ptr, a.nbytes)
             return a
         return {"n_hq": int(out.n_hq), "n_lq": int(out.n_lq), "n_n": int(out.n_n),
@@ -82,36 +68,31 @@ class DividedPCLReadsSets:
                 "n_rows": arr(out.n_rows, out.n_n * out.n_row_bytes, np.uint8),
                 "lq_index": arr(out.lq_index, out.n_lq, np.uint32), "n_index": arr(out.n_index, out.n_n, np.uint32)}
 
-    def divide_fastq(self, text: bytes, pair_text: Optional[bytes] = None, rev_compl_pair: bool = False, final=True):
-        """One piece of FASTQ text (and of the pair file's): (result dict, records taken, bytes consumed, pair bytes consumed).
-        final: True / 1 = nothing follows in either text; 2 / 4 = only the first / the second text ends here."""
+    def _run_text(self, run, text: bytes, pair_text: Optional[bytes], rev_compl_pair: bool, final):
+        """run(text, bytes, pair_text, pair_bytes, rev_compl_pair, final_piece, consumed, pair_consumed, n_records, out) -> what
+        divide_fastq returns"""
         out = _lib.DividedReads()
         used, pused, nrec = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         t = np.frombuffer(text, dtype=np.uint8) if len(text) else np.zeros(1, np.uint8)
         pt = None
         if pair_text is not None:
             pt = np.frombuffer(pair_text, dtype=np.uint8) if len(pair_text) else np.zeros(1, np.uint8)
-        self._ck(lib.pgrc_divider_run_fastq(self._h, t.ctypes.data_as(C.c_void_p), len(text),
-                                            pt.ctypes.data_as(C.c_void_p) if pt is not None else None,
-                                            len(pair_text) if pair_text is not None else 0, int(bool(rev_compl_pair)), int(final),
-                                            C.byref(used), C.byref(pused), C.byref(nrec), C.byref(out)))
+        self._ck(run(t.ctypes.data_as(C.c_void_p), len(text), pt.ctypes.data_as(C.c_void_p) if pt is not None else None,
+                     len(pair_text) if pair_text is not None else 0, int(bool(rev_compl_pair)), int(final),
+                     C.byref(used), C.byref(pused), C.byref(nrec), C.byref(out)))
         return self._result(out), int(nrec.value), int(used.value), int(pused.value)
+
+    def divide_fastq(self, text: bytes, pair_text: Optional[bytes] = None, rev_compl_pair: bool = False, final=True):
+        """One piece of FASTQ text (and of the pair file's): (result dict, records taken, bytes consumed, pair bytes consumed).
+        final: True / 1 = nothing follows in either text; 2 / 4 = only the first / the second text ends here."""
+        return self._run_text(lambda *a: lib.pgrc_divider_run_fastq(self._h, *a), text, pair_text, rev_compl_pair, final)
 
     def divide_text(self, fmt, text: bytes, pair_text: Optional[bytes] = None, rev_compl_pair: bool = False, final=True):
         """divide_fastq for any of the reference's three text formats (pgrc_divider_run_text): fmt is "fastq", "fasta" or
         "lines" (one read per line), or what reads_text_format gives for the file's first byte.  Returns what divide_fastq
         returns."""
-        out = _lib.DividedReads()
-        used, pused, nrec = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        t = np.frombuffer(text, dtype=np.uint8) if len(text) else np.zeros(1, np.uint8)
-        pt = None
-        if pair_text is not None:
-            pt = np.frombuffer(pair_text, dtype=np.uint8) if len(pair_text) else np.zeros(1, np.uint8)
-        self._ck(lib.pgrc_divider_run_text(self._h, _lib.reads_format(fmt), t.ctypes.data_as(C.c_void_p), len(text),
-                                           pt.ctypes.data_as(C.c_void_p) if pt is not None else None,
-                                           len(pair_text) if pair_text is not None else 0, int(bool(rev_compl_pair)), int(final),
-                                           C.byref(used), C.byref(pused), C.byref(nrec), C.byref(out)))
-        return self._result(out), int(nrec.value), int(used.value), int(pused.value)
+        fmt = _lib.reads_format(fmt)
+        return self._run_text(lambda *a: lib.pgrc_divider_run_text(self._h, fmt, *a), text, pair_text, rev_compl_pair, final)
 
     def last_was_terminal(self) -> bool:
         """did the last divide_fastq / divide_text take the last records the reference's iteration would take (pgrc_divider_last_was_terminal)"""

@@ -8,7 +8,7 @@ import pytest
 import oracle as orc
 import rsets_util as ru
 import textformat_util as tu
-from divide_util import COMBOS, make_fastq, make_records, oracle_divide, ref_divide_files, same
+from divide_util import COMBOS, make_fastq, make_records, oracle_divide, oracle_divide_fastq, ref_divide_files, same
 from pgrc_amd import DividedPCLReadsSets, DividedReadsSets, PgrcMatchError, Verifier
 
 pytestmark = pytest.mark.gpu
@@ -262,3 +262,180 @@ def test_verifier_takes_a_fasta_source(kind, two_files):
                 v.add_text("lines", b"ACGT\n", b"ACGT\n", final=True)
         v.add_text("fasta", *[tu.write_fasta(f) for f in files], final=True)
         assert v.finish()["ok"]
+
+
+# ---- one text path for the three formats: state kept per file must not outlive its run, a refusal must leave what it leaves
+# today, and the rule of what a call takes from a pair must be one rule
+
+def fastq_pieces(d, a, b, rev, piece):
+    """tests/test_gpu_divide.py's piece loop on a divider that is already in use -> (result, records, terminal, bytes consumed)"""
+    parts, buf, at, used_all = [], [b"", b""], [0, 0], [0, 0]
+    src = [a, b if b is not None else b""]
+    while True:
+        for f in range(2 if b is not None else 1):
+            buf[f] += src[f][at[f]: at[f] + piece]
+            at[f] += piece
+        final = at[0] >= len(src[0]) and at[1] >= len(src[1])
+        res, nrec, used, pused = d.divide_fastq(buf[0], buf[1] if b is not None else None, rev, final=final)
+        parts.append((res, nrec))
+        buf[0], buf[1] = buf[0][used:], buf[1][pused:]
+        used_all = [used_all[0] + used, used_all[1] + pused]
+        if final:
+            break
+    res, n = tu.concat(parts)
+    return res, n, d.last_was_terminal(), used_all
+
+
+def test_one_divider_takes_the_formats_in_turn():
+    """paired FASTQ, FASTA, lines, FASTQ, a FASTA pair of unequal length, FASTA -- on ONE divider, whole and in pieces of 257
+    bytes, every file with another number of lines: nothing a run keeps per file (line and read counts, the list of read
+    lines, the ends of what was taken, the second file's slots) may reach the next one"""
+    L, n = 21, 300
+    reads = np.array(records(L, n))
+    quals = make_records(seed=5, n=n, L=L)[1]
+    combo = SEP_N
+    steps = [(tu.FASTQ, make_fastq(reads[0::2], quals[0::2], seed=1), make_fastq(reads[1::2], quals[1::2], seed=2, crlf=True), True, n),
+             (tu.FASTA, tu.write_fasta(reads[:280], seed=1, comments=True), None, False, 280),
+             (tu.LINES, tu.write_lines(reads[:190], crlf=True, trailing_newline=False), None, False, 190),
+             (tu.FASTQ, make_fastq(reads[:250], quals[:250], seed=3, trailing_newline=False), None, False, 250),
+             (tu.FASTA, tu.write_fasta(reads[0::2], seed=3, multi_headers=True), tu.write_fasta(reads[1::2][:149], seed=4, crlf=True), True, 299),
+             (tu.FASTA, tu.write_fasta(reads, seed=7, multi_headers=True, header_last=True), None, False, n)]
+    assert len({len(tu.getlines(s[1])) for s in steps}) == len(steps)
+    d = DividedPCLReadsSets(L, *combo)
+    for k, (fmt, a, b, rev, want_n) in enumerate(steps):
+        if fmt == tu.FASTQ:
+            want = oracle_divide_fastq(a, b, rev, L, combo)
+        else:
+            rows = tu.restate(fmt, a, b, rev, L)
+            assert rows.shape[0] == want_n
+            want = oracle_divide(rows, None, *combo)
+        res, nrec, used, pused = d.divide_text(fmt, a, b, rev, final=True)
+        assert nrec == want_n and d.last_was_terminal() and same(res, want) is None, (k, nrec, same(res, want))
+        if fmt == tu.FASTQ:
+            assert (used, pused) == (len(a), len(b) if b is not None else 0), k
+        else:
+            assert len(tu.read_lines(fmt, a[:used])) == ((want_n + 1) // 2 if b is not None else want_n), k
+            assert used == len(a) or a[used - 1: used] == b"\n", k
+            assert tu.read_lines(fmt, a[used:]) == [], k
+            if b is not None:
+                assert len(tu.read_lines(fmt, b[:pused])) == want_n // 2 and tu.read_lines(fmt, b[pused:]) == [], k
+            else:
+                assert pused == 0, k
+        if fmt == tu.FASTQ:
+            got, m, term, used_all = fastq_pieces(d, a, b, rev, 257)
+            assert used_all == [len(a), len(b) if b is not None else 0], k
+        else:
+            cuts = tu.piece_cuts(max(len(a), len(b or b"")), 257)
+            got, m, term, _ = tu.feed(d, fmt, a, b, rev, cuts)
+        assert m == want_n and term and same(got, want) is None, (k, m, same(got, want))
+    d.close()
+
+
+def appended(div, L, separate_n, n_reads_lq):
+    s = DividedReadsSets(L, separate_n, n_reads_lq)
+    s.append_divider(div)
+    s.finish()
+    st = ru.device_state(s)
+    s.close()
+    return st
+
+
+def test_a_refusal_leaves_the_last_run_standing_or_not():
+    """the refusals of FASTA / one-read-per-line text come before anything of the divider changes: pgrc_rsets_append_divider still
+    takes the sets of the good run before them.  A FASTQ call that fails has dropped them: PGRC_E_STATE."""
+    L, n = 21, 300
+    reads = np.array(records(L, n))
+    good = tu.write_fasta(reads, seed=5)
+    lines = tu.write_lines(reads)
+    div = DividedPCLReadsSets(L, *SEP_N)
+    batch, nrec, _, _ = div.divide_text(tu.FASTA, good, None, False, final=True)
+    host = DividedReadsSets(L, True, False)
+    host.append(batch, nrec)
+    host.finish()
+    want = ru.device_state(host)
+    host.close()
+    assert want["A"] == n and ru.same_state(appended(div, L, True, False), want)
+    for name, fmt, a, b, rev in (("format 7", 7, good, None, False), ("lines with a pair", tu.LINES, lines, lines, False),
+                                 ("lines with rev_compl_pair", tu.LINES, lines, None, True)):
+        with pytest.raises(PgrcMatchError) as e:
+            div.divide_text(fmt, a, b, rev, final=True)
+        assert e.value.code == tu.E_PARAM, name
+        assert ru.same_state(appended(div, L, True, False), want), name
+    # a quality division: its good run is FASTQ, and a FASTA or lines file of two records is refused
+    qcombo = (0.2, False, True, False)
+    quals = make_records(seed=1, n=n, L=L)[1]
+    fq = make_fastq(reads, quals, seed=1)
+    q = DividedPCLReadsSets(L, *qcombo)
+    batch, nrec, _, _ = q.divide_fastq(fq, None, False, final=True)
+    host = DividedReadsSets(L, True, False)
+    host.append(batch, nrec)
+    host.finish()
+    qwant = ru.device_state(host)
+    host.close()
+    for fmt, text in ((tu.FASTA, tu.write_fasta(reads[:2])), (tu.LINES, tu.write_lines(reads[:2]))):
+        with pytest.raises(PgrcMatchError) as e:
+            q.divide_text(fmt, text, None, False, final=True)
+        assert e.value.code == tu.E_PARAM
+        assert ru.same_state(appended(q, L, True, False), qwant), fmt
+    # FASTQ text that ends inside a record: the call has dropped the last run's sets before it fails, through either entry
+    cut = fq[: fq.rstrip(b"\n").rfind(b"\n+")]
+    for entry in (lambda: q.divide_fastq(cut, None, False, final=True), lambda: q.divide_text(tu.FASTQ, cut, None, False, final=True)):
+        q.divide_fastq(fq, None, False, final=True)
+        with pytest.raises(PgrcMatchError) as e:
+            entry()
+        assert e.value.code == tu.E_PARAM and "ends inside a record" in str(e.value)
+        with pytest.raises(PgrcMatchError) as e:
+            appended(q, L, True, False)
+        assert e.value.code == 6                             # PGRC_E_STATE
+    for s in (div, q):
+        s.close()
+
+
+# (records of the first file, of the second, calls as (records handed over so far of the first, of the second, final bits),
+#  records each call takes, the call that is terminal): worked out from the reference's iteration -- the two files in turn,
+#  first file first, until the one whose turn it is has no more; a call takes the whole pairs it holds, and the odd last read
+#  once the second file is known to have no mate for it
+TAKE_CASES = {
+    "3 against 5, the first ends": (3, 5, [(3, 5, 2)], [6], 0),
+    "3 against 5, the second ends, the first goes on": (6, 5, [(3, 5, 4), (6, 5, 1)], [6, 5], 1),
+    "5 against 3, the first ends, the second goes on": (5, 6, [(5, 3, 2), (5, 6, 1)], [6, 4], 1),
+    "5 against 3, the second ends": (5, 3, [(5, 3, 4)], [7], 0),
+    "the first is through, its mates arrive later": (3, 5, [(3, 1, 2), (3, 5, 2)], [2, 4], 1),
+    "the second is through, the first's reads arrive later": (5, 3, [(1, 3, 4), (5, 3, 4)], [2, 5], 1),
+    "neither is through, then the first ends": (3, 5, [(2, 4, 0), (3, 5, 2)], [4, 2], 1),
+}
+
+
+@pytest.mark.parametrize("case", list(TAKE_CASES))
+def test_fastq_and_fasta_pairs_take_the_same_records(case):
+    """what a call takes from a pair and whether it is the terminal one depends on the numbers of records alone: the same
+    calls in FASTQ and in FASTA give the same counts, the same terminal call and the same rows"""
+    L = 21
+    na, nb, calls, want_nrec, want_terminal = TAKE_CASES[case]
+    reads = np.array(records(L, 300))
+    quals = make_records(seed=5, n=300, L=L)[1]
+    ra, rb = reads[0:2 * na:2], reads[1:2 * nb:2]
+    qa, qb = quals[0:2 * na:2], quals[1:2 * nb:2]
+    texts = {tu.FASTQ: ([make_fastq(ra[i:i + 1], qa[i:i + 1], seed=i) for i in range(na)],
+                        [make_fastq(rb[i:i + 1], qb[i:i + 1], seed=50 + i, crlf=True) for i in range(nb)]),
+             tu.FASTA: ([tu.write_fasta(ra[i:i + 1], seed=i, comments=True) for i in range(na)],
+                        [tu.write_fasta(rb[i:i + 1], seed=50 + i, crlf=True) for i in range(nb)])}
+    rows = tu.restate(tu.FASTA, b"".join(texts[tu.FASTA][0]), b"".join(texts[tu.FASTA][1]), True, L)
+    assert rows.shape[0] == sum(want_nrec)
+    want = oracle_divide(rows, None, *SEP_N)
+    seen = {}
+    for fmt, (ta, tb) in texts.items():
+        d = DividedPCLReadsSets(L, *SEP_N)
+        at, parts, terminal = [0, 0], [], []
+        for ha, hb, bits in calls:
+            a, b = b"".join(ta[:ha]), b"".join(tb[:hb])
+            res, nrec, used, pused = d.divide_text(fmt, a[at[0]:], b[at[1]:], True, final=bits)
+            parts.append((res, nrec))
+            terminal.append(d.last_was_terminal())
+            at = [at[0] + used, at[1] + pused]
+        d.close()
+        got, total = tu.concat(parts)
+        assert same(got, want) is None, (fmt, same(got, want))
+        seen[fmt] = ([p[1] for p in parts], terminal.index(True) if True in terminal else None)
+        assert terminal.count(True) == 1 and terminal[-1]
+    assert seen[tu.FASTQ] == seen[tu.FASTA] == (want_nrec, want_terminal)
