@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <initializer_list>
@@ -203,13 +204,15 @@ static float dec_elapsed(hipEvent_t a, hipEvent_t b) {       // 0 if either even
     if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return ms;
 }
+static inline float dec_ms_since(std::chrono::steady_clock::time_point t0) {   // host time since t0
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // The timing events of a call's phases: made on first use, recorded on a stream, read in pairs, given back with the context
 template <int N>
 struct PhaseEvents {
     hipEvent_t ev[N]{};
-    template <typename Ctx>     // (a PgrcDev, or the Pg-vs-Pg matcher's context with an error text of its own)
-    int ensure(Ctx *c) {
+    int ensure(PgrcDev *c) {
         for (hipEvent_t &ev : this->ev)
             if (!ev) HIP_TRY(c, hipEventCreate(&ev));
         return PGRC_OK;

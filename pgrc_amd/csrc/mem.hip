@@ -560,7 +560,7 @@ struct StaleWalk {
     }
     uint32_t src32(uint64_t pos) {
         char buf[4];
-        return le32(text_at(m->src, (const uint32_t *)m->base->txt.pg2[0].p, nullptr, pos, 4, buf));
+        return le32(text_at(m->src.text, (const uint32_t *)m->base->txt.pg2[0].p, nullptr, pos, 4, buf));
     }
     uint32_t dest32(uint64_t pos) {
         char buf[4];
@@ -603,7 +603,7 @@ struct StaleWalk {
     int bucket(uint64_t q, uint64_t *pos) {
         pgrc_match_ctx *c = m->base;
         char win[64];                            // (K <= 56)
-        const uint32_t h = host_hash(m->K, text_at(dest, d_dw, d_dn, q, (uint32_t)m->K, win)) & (uint32_t)(c->cp.hash_size - 1);
+        const uint32_t h = host_hash(m->src.K, text_at(dest, d_dw, d_dn, q, (uint32_t)m->src.K, win)) & (uint32_t)(c->cp.hash_size - 1);
         const PgrcIndexSet *ix = pgrc_index_of(c, 0);
         unsigned long long hd[2];
         if (!ix || hipMemcpy(hd, (const char *)ix->head_ptr + (size_t)head_slot(h, ix->head_sh) * 16, 16, hipMemcpyDeviceToHost) != hipSuccess) { lookup_err = 1; return 0; }
@@ -629,13 +629,13 @@ struct StaleWalk {
         uint64_t tt = t;
         uint32_t upto = order;                       // entries [0, upto) of probe tt were examined before
         for (;;) {
-            const uint64_t q = tt * (uint64_t)m->k2;
+            const uint64_t q = tt * (uint64_t)m->src.k2;
             const int cnt = bucket(q, pos);
             for (int j = std::min<int>(cnt, (int)upto) - 1; j >= 0; j--) {
                 const uint64_t p = pos[j];
                 if (self_filtered(q, p)) continue;   // (a): never reached the register update
-                if (left ? p >= (uint64_t)m->LK2 : p + (uint64_t)m->KLK24 + 4 <= m->N)
-                    return src32(left ? p - m->LK2 : p + m->KLK24);
+                if (left ? p >= (uint64_t)m->src.LK2 : p + (uint64_t)m->src.KLK24 + 4 <= m->src.N)
+                    return src32(left ? p - m->src.LK2 : p + m->src.KLK24);
             }
             // previous examined probe
             for (;;) {
@@ -657,10 +657,10 @@ struct StaleWalk {
         while (tt > 0 && !lookup_err) {
             tt--;
             if (!examined(tt)) continue;
-            const uint64_t q = tt * (uint64_t)m->k2;
-            if (q + (uint64_t)m->KLK24 + 4 > N2) continue;
+            const uint64_t q = tt * (uint64_t)m->src.k2;
+            if (q + (uint64_t)m->src.KLK24 + 4 > N2) continue;
             if (bucket(q, pos) == 0) continue;       // empty bucket: the registers are not touched (:376-379)
-            return dest32(q + m->KLK24);
+            return dest32(q + m->src.KLK24);
         }
         return 0u;
     }
@@ -668,7 +668,7 @@ struct StaleWalk {
 
 extern "C" {
 
-const char *pgrc_mem_last_error(const pgrc_mem_ctx *m) { return m ? m->err.c_str() : g_mem_create_err.c_str(); }
+const char *pgrc_mem_last_error(const pgrc_mem_ctx *m) { return m ? m->base->err.c_str() : g_mem_create_err.c_str(); }
 
 int pgrc_mem_create(uint32_t target_len, uint32_t ctor_min_len, int32_t device, pgrc_mem_ctx **out) {
     if (!out) return PGRC_E_PARAM;
@@ -687,7 +687,7 @@ int pgrc_mem_create(uint32_t target_len, uint32_t ctor_min_len, int32_t device, 
     if (e) { g_mem_create_err = pgrc_match_last_error(nullptr); return e; }
     pgrc_mem_ctx *m = new pgrc_mem_ctx();
     m->base = base;
-    m->L = target_len;
+    m->src.L = target_len;
     *out = m;
     return PGRC_OK;
 }
@@ -697,14 +697,11 @@ void pgrc_mem_destroy(pgrc_mem_ctx *m) {
     {
         PgrcDeviceScope scope(m->base->device);
         (void)hipDeviceSynchronize();          // (its buffers go to the pool of device buffers: nothing may still be running)
+        DevBufList bufs = m->bufs();
+        pgrc_buf_free_all(bufs.data(), bufs.size());
+        m->ev.release();
+        m->pm.ev.release();
     }
-    DevBuf *bufs[] = {&m->d_dest, &m->d_nmap, &m->d_stage, &m->d_flag, &m->d_cursor, &m->d_evk[0], &m->d_evk[1], &m->d_evv[0],
-                      &m->d_evv[1], &m->d_tmp, &m->d_scan, &m->d_orun, &m->d_oflag, &m->d_skey[0], &m->d_skey[1], &m->d_sidx[0],
-                      &m->d_sidx[1], &m->d_first, &m->d_runid, &m->d_rstart, &m->d_rend, &m->d_rdend, &m->d_outc, &m->d_ebstart,
-                      &m->d_ebin, &m->d_ebout, &m->d_ebinc, &m->d_small, &m->d_match};
-    for (DevBuf *b : bufs) pgrc_buf_free(*b);
-    pgrc_pgmap_release(m);
-    m->ev.release();
     pgrc_match_destroy(m->base);
     delete m;
 }
@@ -718,23 +715,22 @@ int pgrc_mem_get_counters(pgrc_mem_ctx *m, pgrc_mem_counters *out) {
 // what both forms of "set the source" share: the old source's state forgotten, `pack` puts the text into the base context, the index
 static int mem_set_src(pgrc_mem_ctx *m, const char *host_src, uint64_t n, int (*pack)(pgrc_mem_ctx *, const void *, uint64_t), const void *text) {
     pgrc_match_ctx *c = m->base;
-    m->have_src = false;
-    m->map_ready = false;
-    for (bool &set : m->res_set) set = false;   // (the mapped texts kept in HBM belong to the old source)
+    m->forget_source();                         // (the mapped texts kept in HBM belong to the old source)
     PgrcDeviceScope dev_scope__(c->device);
-    if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
+    if (!dev_scope__.ok) return mem_fail(m, PGRC_E_NO_DEVICE, "hipSetDevice failed");
     const auto t0 = std::chrono::steady_clock::now();
     int e = pack(m, text, n);
     if (!e) e = pgrc_copmem_build_index(c, c->stream, 0);
-    if (!e && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "index build failed"; e = PGRC_E_DEVICE; }
-    if (e) { m->err = c->err; return e; }
-    m->ctr.ms_index = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    m->K = c->cp.K; m->k1 = c->cp.k1; m->k2 = c->cp.k2;
-    m->LK2 = ((int)m->L - m->K) / 2;                       // CopMEMMatcher.cpp:87-89
-    m->KLK24 = m->K + m->LK2 - 4;
-    m->src = host_src;
-    m->N = n;
-    m->have_src = true;
+    if (!e && hipStreamSynchronize(c->stream) != hipSuccess) e = mem_fail(m, PGRC_E_DEVICE, "index build failed");
+    if (e) return e;
+    m->ctr.ms_index = dec_ms_since(t0);
+    MemSource &s = m->src;
+    s.K = c->cp.K; s.k1 = c->cp.k1; s.k2 = c->cp.k2;
+    s.LK2 = ((int)s.L - s.K) / 2;                          // CopMEMMatcher.cpp:87-89
+    s.KLK24 = s.K + s.LK2 - 4;
+    s.text = host_src;
+    s.N = n;
+    s.have = true;
     return PGRC_OK;
 }
 
@@ -756,25 +752,23 @@ int pgrc_mem_set_src_ascii(pgrc_mem_ctx *m, const char *src, uint64_t n) {
 int pgrc_mem_set_src_device(pgrc_mem_ctx *m, const void *d_ascii, uint64_t n) {
     if (!m || !d_ascii) return PGRC_E_PARAM;
     if (!mem_on_device(m, d_ascii)) {
-        m->have_src = false;
-        m->map_ready = false;
-        for (bool &set : m->res_set) set = false;
-        m->err = "set_src_device: the text is not memory of the context's device";
-        return PGRC_E_PARAM;
+        m->forget_source();
+        return mem_fail(m, PGRC_E_PARAM, "set_src_device: the text is not memory of the context's device");
     }
     // the text is packed into the context's own words by k_mem_pack_dev (no N map: an N is as wrong here as any other symbol),
     // and the flag is read back before the call returns: nothing of the caller's buffer is read afterwards
     return mem_set_src(m, nullptr, n, [](pgrc_mem_ctx *mm, const void *text, uint64_t len) -> int {
         pgrc_match_ctx *c = mm->base;
         int e = pgrc_pg_alloc(c, len);
-        if (!e) e = pgrc_buf_ensure(c, mm->d_flag, 4);
+        if (!e) e = pgrc_buf_ensure(c, mm->dst.flag, 4);
         if (e) return e;
-        HIP_TRY(c, hipMemsetAsync(mm->d_flag.p, 0, 4, c->stream));
-        if ((e = pgrc_launch_mem_pack_device(c, (const uint8_t *)text, len, false, (uint32_t *)c->txt.pg2[0].p, nullptr, c->txt.pg_words, (uint32_t *)mm->d_flag.p, 0))) return e;
+        uint32_t *d_flag = (uint32_t *)mm->dst.flag.p;
+        HIP_TRY(c, hipMemsetAsync(d_flag, 0, 4, c->stream));
+        if ((e = pgrc_launch_mem_pack_device(c, (const uint8_t *)text, len, false, (uint32_t *)c->txt.pg2[0].p, nullptr, c->txt.pg_words, d_flag, 0))) return e;
         uint32_t fl = 0;
-        HIP_TRY(c, hipMemcpyAsync(&fl, mm->d_flag.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&fl, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (fl) { c->err = "pseudogenome contains a symbol outside ACGT"; return PGRC_E_SYMBOL; }
+        if (fl) return mem_fail(mm, PGRC_E_SYMBOL, "pseudogenome contains a symbol outside ACGT");
         c->txt.have_pg = true;
         return PGRC_OK;
     }, d_ascii);
@@ -782,292 +776,348 @@ int pgrc_mem_set_src_device(pgrc_mem_ctx *m, const void *d_ascii, uint64_t n) {
 
 void pgrc_mem_free_matches(pgrc_text_match *p) { free(p); }
 
-// matchTexts over a destination on the host (dest: the text as matched, reverse-complemented already when rev_compl) or in HBM
-// (dest == null, d_ascii: the FORWARD text, which the packing kernel reverse-complements; it may be null with dest_is_src)
-static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, uint64_t N2, int dest_is_src, int rev_compl, uint32_t min_len,
-                     pgrc_text_match **matches, uint64_t *count) {
-    *matches = nullptr;
-    *count = 0;
-    m->map_ready = false;                 // (a failed call leaves no destination for pgrc_mem_mark_and_remove)
-    if (!m->have_src) { m->err = "match_texts: set the source text first"; return PGRC_E_STATE; }
-    pgrc_match_ctx *c = m->base;
-    if ((int)min_len < m->K) { m->err = "Minimal matching length cannot be smaller than K"; return PGRC_E_PARAM; }   // :606-609
-    if (dest_is_src && N2 != m->N) { m->err = "match_texts: dest_is_src with a text of another length"; return PGRC_E_PARAM; }
-    if (N2 / (uint64_t)m->k2 + 1 >= (1ull << 40)) { m->err = "destination text too long"; return PGRC_E_PARAM; }
-    if (d_ascii && !mem_on_device(m, d_ascii)) { m->err = "match_texts_device: the destination is not memory of the context's device"; return PGRC_E_PARAM; }
-    PgrcDeviceScope dev_scope__(c->device);
-    if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
-    m->ctr.probes = m->ctr.events = m->ctr.stale_lookups = 0;
-    const uint64_t K = (uint64_t)m->K, k2 = (uint64_t)m->k2;
-    const uint64_t nprobes = N2 >= K ? (N2 - K) / k2 + 1 : 0;          // windows q = t * k2 with q + K <= N2
-    m->ctr.probes = nprobes;
-    int e;
-    if ((e = m->ev.ensure(m))) return e;
-    auto &ev = m->ev;
+// What the phases of one mem_match call hand to each other; it lives on mem_match's stack
+struct MemCall {
+    const char *dest;                // the destination on the host (as matched: reverse-complemented already when rev_compl), or null:
+    const uint8_t *d_ascii;          // ... the FORWARD text in HBM, which the packing kernel reverse-complements (null with dest_is_src)
+    uint64_t N2;
+    bool dest_is_src, rev_compl;
+    uint32_t min_len;
+    uint64_t nprobes;                // windows q = t * k2 with q + K <= N2
+    bool unread_symbol = false;      // a text shorter than K with a symbol outside ACGNT: no window reads it, no error, nothing to map
+    MemArgs a;                       // what every kernel up to the replay gets (mem_dest_to_hbm: the destination; mem_probe: the rest)
+    uint64_t nev = 0;                // events
+    const uint64_t *ek = nullptr, *ep = nullptr;   // ... in the reference's order: (window << 4) | bucket order, source position
+    uint32_t grid = 0;               // blocks of 256 events
+    uint64_t nmain = 0;              // windows of the reference's main loop (whole blocks of 256)
+    MemReplayArgs ra;                // the replay's launch: filled once, `first` turned off after round 0
+    uint32_t replay_grid = 0;
+};
 
-    // ---- the destination in HBM
-    MemArgs a;
-    memset(&a, 0, sizeof a);
-    const uint64_t dwords = (N2 + 15) / 16;
-    if (dest_is_src) {
-        if (rev_compl) {
-            if ((e = pgrc_make_rc_text(c, c->stream))) { m->err = c->err; return e; }
-        }
-        a.dest = (const uint32_t *)c->txt.pg2[rev_compl ? 1 : 0].p;
+// ---- the destination in HBM
+static int mem_dest_to_hbm(pgrc_mem_ctx *m, MemCall &k) {
+    pgrc_match_ctx *c = m->base;
+    MemDest &d = m->dst;
+    MemArgs &a = k.a;
+    const uint64_t N2 = k.N2, dwords = (N2 + 15) / 16;
+    int e;
+    if (k.dest_is_src) {
+        if (k.rev_compl && (e = pgrc_make_rc_text(c, c->stream))) return e;
+        a.dest = (const uint32_t *)c->txt.pg2[k.rev_compl ? 1 : 0].p;
         a.nmap = nullptr;
         a.dest_words_alloc = c->txt.pg_words + PGRC_PG_PAD_WORDS;
-    } else {
-        const uint64_t CH = 64ull << 20;
-        if ((e = pgrc_buf_ensure(c, m->d_dest, (dwords + PGRC_PG_PAD_WORDS) * 4)) || (e = pgrc_buf_ensure(c, m->d_nmap, (dwords + PGRC_PG_PAD_WORDS) * 2)) ||
-            (dest && (e = pgrc_buf_ensure(c, m->d_stage, (size_t)std::max<uint64_t>(16, std::min(CH, N2))))) || (e = pgrc_buf_ensure(c, m->d_flag, 4))) { m->err = c->err; return e; }
-        (void)hipMemsetAsync(m->d_flag.p, 0, 4, c->stream);
-        if (!dest) {
-            // the text is in HBM: ONE launch packs it whole, reverse-complemented on the way if need be, and writes the zero pad
-            // behind it too (k_mem_pack_dev, mempack.hip); the flag's download below ends the reading of the caller's buffer
-            if ((e = pgrc_launch_mem_pack_device(c, d_ascii, N2, rev_compl != 0, (uint32_t *)m->d_dest.p, (uint16_t *)m->d_nmap.p, dwords + PGRC_PG_PAD_WORDS,
-                                                 (uint32_t *)m->d_flag.p, 0))) { m->err = c->err; return e; }
-            const hipError_t he = hipStreamSynchronize(c->stream);
-            if (he != hipSuccess) { m->err = std::string("destination packing: ") + hipGetErrorString(he); return PGRC_E_DEVICE; }
-        } else {
-            (void)hipMemsetAsync(m->d_dest.p, 0, (dwords + PGRC_PG_PAD_WORDS) * 4, c->stream);
-            (void)hipMemsetAsync(m->d_nmap.p, 0, (dwords + PGRC_PG_PAD_WORDS) * 2, c->stream);
-        }
-        for (uint64_t off = 0; dest && off < N2; off += CH) {
-            const uint64_t len = std::min(CH, N2 - off);
-            hipError_t he = hipMemcpyAsync(m->d_stage.p, dest + off, len, hipMemcpyHostToDevice, c->stream);
-            if (he == hipSuccess) {
-                const uint64_t nw = (len + 15) / 16;
-                hipLaunchKernelGGL(k_mem_pack, dim3((uint32_t)std::min<uint64_t>((nw + 255) / 256, 65536)), dim3(256), 0, c->stream,
-                                   (const uint8_t *)m->d_stage.p, len, (uint32_t *)m->d_dest.p + off / 16, (uint16_t *)m->d_nmap.p + off / 16,
-                                   (uint32_t *)m->d_flag.p);
-                he = hipStreamSynchronize(c->stream);
-            }
-            if (he != hipSuccess) { m->err = std::string("destination upload: ") + hipGetErrorString(he); return PGRC_E_DEVICE; }
-        }
-        uint32_t fl = 0;
-        HIP_TRY(m, hipMemcpy(&fl, m->d_flag.p, 4, hipMemcpyDeviceToHost));
-        // no window reads it: no error, as before texts shorter than K were uploaded; but it cannot be mapped (pgrc_mem.h)
-        if ((fl & 1u) && nprobes == 0) return PGRC_OK;
-        if (fl & 1u) { m->err = "destination text contains a symbol outside ACGNT"; return PGRC_E_SYMBOL; }
-        a.dest = (const uint32_t *)m->d_dest.p;
-        a.nmap = (fl & 2u) ? (const uint16_t *)m->d_nmap.p : nullptr;
-        a.dest_words_alloc = dwords + PGRC_PG_PAD_WORDS;
-    }
-    // the destination is resident from here on: what pgrc_mem_mark_and_remove maps once this call has succeeded
-    auto done = [&]() {
-        m->map_ready = true;
-        m->map_n2 = N2;
-        m->map_dest_is_src = dest_is_src != 0;
-        m->map_rev_compl = rev_compl != 0;
-        m->map_has_n = a.nmap != nullptr;
         return PGRC_OK;
-    };
-    if (nprobes == 0) return done();      // (a text shorter than K: no window, no match)
+    }
+    const uint64_t CH = 64ull << 20;
+    if ((e = pgrc_buf_ensure(c, d.words, (dwords + PGRC_PG_PAD_WORDS) * 4)) || (e = pgrc_buf_ensure(c, d.nmap, (dwords + PGRC_PG_PAD_WORDS) * 2)) ||
+        (k.dest && (e = pgrc_buf_ensure(c, d.stage, (size_t)std::max<uint64_t>(16, std::min(CH, N2))))) || (e = pgrc_buf_ensure(c, d.flag, 4))) return e;
+    uint32_t *d_words = (uint32_t *)d.words.p, *d_flag = (uint32_t *)d.flag.p;
+    uint16_t *d_nmap = (uint16_t *)d.nmap.p;
+    HIP_TRY(c, hipMemsetAsync(d_flag, 0, 4, c->stream));
+    if (!k.dest) {
+        // the text is in HBM: ONE launch packs it whole, reverse-complemented on the way if need be, and writes the zero pad
+        // behind it too (k_mem_pack_dev, mempack.hip); the flag's download below ends the reading of the caller's buffer
+        if ((e = pgrc_launch_mem_pack_device(c, k.d_ascii, N2, k.rev_compl, d_words, d_nmap, dwords + PGRC_PG_PAD_WORDS, d_flag, 0))) return e;
+        const hipError_t he = hipStreamSynchronize(c->stream);
+        if (he != hipSuccess) return mem_fail(m, PGRC_E_DEVICE, std::string("destination packing: ") + hipGetErrorString(he));
+    } else {
+        HIP_TRY(c, hipMemsetAsync(d_words, 0, (dwords + PGRC_PG_PAD_WORDS) * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(d_nmap, 0, (dwords + PGRC_PG_PAD_WORDS) * 2, c->stream));
+    }
+    for (uint64_t off = 0; k.dest && off < N2; off += CH) {
+        const uint64_t len = std::min(CH, N2 - off);
+        hipError_t he = hipMemcpyAsync(d.stage.p, k.dest + off, len, hipMemcpyHostToDevice, c->stream);
+        if (he == hipSuccess) {
+            const uint64_t nw = (len + 15) / 16;
+            hipLaunchKernelGGL(k_mem_pack, dim3((uint32_t)std::min<uint64_t>((nw + 255) / 256, 65536)), dim3(256), 0, c->stream,
+                               (const uint8_t *)d.stage.p, len, d_words + off / 16, d_nmap + off / 16, d_flag);
+            he = hipStreamSynchronize(c->stream);
+        }
+        if (he != hipSuccess) return mem_fail(m, PGRC_E_DEVICE, std::string("destination upload: ") + hipGetErrorString(he));
+    }
+    uint32_t fl = 0;
+    HIP_TRY(c, hipMemcpyAsync(&fl, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // no window reads it: no error, as before texts shorter than K were uploaded; but it cannot be mapped (pgrc_mem.h)
+    if ((fl & 1u) && k.nprobes == 0) { k.unread_symbol = true; return PGRC_OK; }
+    if (fl & 1u) return mem_fail(m, PGRC_E_SYMBOL, "destination text contains a symbol outside ACGNT");
+    a.dest = d_words;
+    a.nmap = (fl & 2u) ? d_nmap : nullptr;
+    a.dest_words_alloc = dwords + PGRC_PG_PAD_WORDS;
+    return PGRC_OK;
+}
+
+// ---- 1. events
+static int mem_probe(pgrc_mem_ctx *m, MemCall &k) {
+    pgrc_match_ctx *c = m->base;
+    MemEvents &v = m->evs;
+    MemArgs &a = k.a;
+    int e;
     a.src = (const uint32_t *)c->txt.pg2[0].p;
-    a.N = m->N;
-    a.N2 = N2;
-    if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, c->stream, 0))) { m->err = c->err; return e; }   // (only if somebody rebuilt the base index in between)
+    a.N = m->src.N;
+    a.N2 = k.N2;
+    if (!pgrc_index_of(c, 0) && (e = pgrc_copmem_build_index(c, c->stream, 0))) return e;   // (only if somebody rebuilt the base index in between)
     const PgrcIndexSet *ix = pgrc_index_of(c, 0);
     a.head = (const ulonglong2 *)ix->head_ptr;
     a.hsh = ix->head_sh;
     a.ent = ix->ent;
     a.mask = (uint32_t)(c->cp.hash_size - 1);
-    a.K = (uint32_t)m->K;
-    a.k2 = (uint32_t)m->k2;
-    a.LK2 = (uint32_t)m->LK2;
-    a.KLK24 = (uint32_t)m->KLK24;
-    a.nprobes = nprobes;
-    a.dest_is_src = dest_is_src ? 1 : 0;
-    a.rev_compl = rev_compl ? 1 : 0;
+    a.K = (uint32_t)m->src.K;
+    a.k2 = (uint32_t)m->src.k2;
+    a.LK2 = (uint32_t)m->src.LK2;
+    a.KLK24 = (uint32_t)m->src.KLK24;
+    a.nprobes = k.nprobes;
+    a.dest_is_src = k.dest_is_src ? 1 : 0;
+    a.rev_compl = k.rev_compl ? 1 : 0;
 
-    // ---- 1. events
-    if ((e = pgrc_buf_ensure(c, m->d_cursor, 8))) { m->err = c->err; return e; }
+    if ((e = pgrc_buf_ensure(c, v.cursor, 8))) return e;
     // room for the events (32 bytes each, in four arrays): one per probe for a short text -- a low-quality text against the high-quality
     // one makes 0.6 events per probe --, one per four probes for a long one (a text against itself, forward: 0.18; against its reverse
     // complement, the encoder's call: 0.004); a probe that finds more is run again with what it counted (rounds 1-5a started at one
     // event per 64 probes: the event-rich calls probed twice the first time)
-    uint64_t cap = std::max<uint64_t>((nprobes <= (64ull << 20) ? nprobes : nprobes / 4) + 65536, m->d_evk[0].bytes / 8);
+    const uint64_t nprobes = k.nprobes;
+    uint64_t cap = std::max<uint64_t>((nprobes <= (64ull << 20) ? nprobes : nprobes / 4) + 65536, v.evk[0].bytes / 8);
     if (c->opt.mem_event_cap) cap = c->opt.mem_event_cap;   // (PGRC_MEM_EVENT_CAP, test knob: start tiny to exercise the regrow-and-rerun path)
     unsigned long long nev = 0;
-    (void)ev.record(0, c->stream);
+    HIP_TRY(c, m->ev.record(0, c->stream));
     for (int attempt = 0; attempt < 2; attempt++) {
-        for (int k = 0; k < 2; k++)
-            if ((e = pgrc_buf_ensure(c, m->d_evk[k], cap * 8)) || (e = pgrc_buf_ensure(c, m->d_evv[k], cap * 8))) { m->err = c->err; return e; }
-        (void)hipMemsetAsync(m->d_cursor.p, 0, 8, c->stream);
+        for (int b = 0; b < 2; b++)
+            if ((e = pgrc_buf_ensure(c, v.evk[b], cap * 8)) || (e = pgrc_buf_ensure(c, v.evv[b], cap * 8))) return e;
+        HIP_TRY(c, hipMemsetAsync(v.cursor.p, 0, 8, c->stream));
         hipLaunchKernelGGL(k_mem_probe, dim3((uint32_t)((nprobes + MEM_TPB - 1) / MEM_TPB)), dim3(MEM_TPB), 0, c->stream, a,
-                           (unsigned long long *)m->d_cursor.p, (uint64_t *)m->d_evk[0].p, (uint64_t *)m->d_evv[0].p, cap);
+                           (unsigned long long *)v.cursor.p, (uint64_t *)v.evk[0].p, (uint64_t *)v.evv[0].p, cap);
         hipError_t he = hipGetLastError();
-        if (he == hipSuccess) he = hipMemcpyAsync(&nev, m->d_cursor.p, 8, hipMemcpyDeviceToHost, c->stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(&nev, v.cursor.p, 8, hipMemcpyDeviceToHost, c->stream);
         if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-        if (he != hipSuccess) { m->err = std::string("probe kernel: ") + hipGetErrorString(he); return PGRC_E_DEVICE; }
+        if (he != hipSuccess) return mem_fail(m, PGRC_E_DEVICE, std::string("probe kernel: ") + hipGetErrorString(he));
         if (nev <= cap) break;
         cap = nev + nev / 4;                                // the guess was too small: once more, with headroom for the next call
     }
-    (void)ev.record(1, c->stream);
+    HIP_TRY(c, m->ev.record(1, c->stream));
+    k.nev = nev;
+    k.grid = (uint32_t)((nev + 255) / 256);
     m->ctr.events = nev;
     m->ctr.replay_rounds = m->ctr.event_blocks = 0;
     m->ctr.ms_sort = m->ctr.ms_extend = m->ctr.ms_replay = m->ctr.ms_host = 0.f;
-    (void)hipEventSynchronize(ev.ev[1]);
-    m->ctr.ms_probe = ev.ms(0, 1);
-    if (!nev) return done();
-    if (nev >= 0xFFFFFFF0ull) { m->err = "more than 2^32 events"; return PGRC_E_PARAM; }
+    HIP_TRY(c, hipEventSynchronize(m->ev.ev[1]));
+    m->ctr.ms_probe = m->ev.ms(0, 1);
+    return PGRC_OK;
+}
 
-    // ---- 2. the order in which the reference meets them: by window, then by bucket order
+// ---- 2. the order in which the reference meets them: by window, then by bucket order
+static int mem_order(pgrc_mem_ctx *m, MemCall &k) {
+    pgrc_match_ctx *c = m->base;
+    MemEvents &v = m->evs;
     int tb = 1;
-    while ((1ull << tb) < nprobes) tb++;
+    while ((1ull << tb) < k.nprobes) tb++;
     // (a stable LSD sort of (key, value) pairs: radix.hip, hand-written; the library's pair sort until round 5)
     uint64_t *ksorted = nullptr, *vsorted = nullptr;
-    if ((e = pgrc_radix_sort_pairs_u64(c, (uint64_t *)m->d_evk[0].p, (uint64_t *)m->d_evk[1].p, (uint64_t *)m->d_evv[0].p, (uint64_t *)m->d_evv[1].p, nev, 0,
-                                       4 + tb, m->d_tmp, &ksorted, &vsorted))) { m->err = c->err; return e; }
-    (void)ev.record(2, c->stream);
-    const uint64_t *ek = ksorted, *ep = vsorted;
+    if (int e = pgrc_radix_sort_pairs_u64(c, (uint64_t *)v.evk[0].p, (uint64_t *)v.evk[1].p, (uint64_t *)v.evv[0].p, (uint64_t *)v.evv[1].p, k.nev, 0, 4 + tb,
+                                          v.tmp, &ksorted, &vsorted)) return e;
+    HIP_TRY(c, m->ev.record(2, c->stream));
+    k.ek = ksorted;
+    k.ep = vsorted;
+    return PGRC_OK;
+}
 
-    // ---- 3. side contexts; extents per run of connected events on a diagonal
+// ---- 3. side contexts; extents per run of connected events on a diagonal
+static int mem_runs(pgrc_mem_ctx *m, MemCall &k) {
+    pgrc_match_ctx *c = m->base;
+    MemRuns &r = m->runs;
+    const MemArgs &a = k.a;
+    const uint64_t nev = k.nev, *ek = k.ek, *ep = k.ep;
+    const uint32_t g = k.grid;
+    int e;
     const uint64_t ecap = nev + nev / 8 + 4096;               // per-event arrays: by the events there are (with room for a similar call), not by the first guess
-    if ((e = pgrc_buf_ensure(c, m->d_orun, ecap * 4)) || (e = pgrc_buf_ensure(c, m->d_oflag, ecap)) || (e = pgrc_buf_ensure(c, m->d_first, ecap * 4)) ||
-        (e = pgrc_buf_ensure(c, m->d_runid, ecap * 4)) || (e = pgrc_buf_ensure(c, m->d_rstart, ecap * 8)) || (e = pgrc_buf_ensure(c, m->d_rend, ecap * 8)) ||
-        (e = pgrc_buf_ensure(c, m->d_rdend, ecap * 8)) || (e = pgrc_buf_ensure(c, m->d_outc, ecap)) || (e = pgrc_buf_ensure(c, m->d_small, 64))) { m->err = c->err; return e; }
-    for (int k = 0; k < 2; k++)
-        if ((e = pgrc_buf_ensure(c, m->d_skey[k], ecap * 8)) || (e = pgrc_buf_ensure(c, m->d_sidx[k], ecap * 8))) { m->err = c->err; return e; }
-    // d_small: [0] "a block was replayed" flag, [1] first stale event, [2] events with a context outside a text, [4..7] two u64 of a range
-    uint32_t *d_changed = (uint32_t *)m->d_small.p, *d_first_stale = d_changed + 1, *d_nstale = d_changed + 2;
-    uint64_t *d_range = (uint64_t *)m->d_small.p + 2;
-    HIP_TRY(m, hipMemsetAsync(m->d_small.p, 0, 64, c->stream));
-    const uint32_t g = (uint32_t)((nev + 255) / 256);
+    if ((e = pgrc_buf_ensure(c, r.orun, ecap * 4)) || (e = pgrc_buf_ensure(c, r.oflag, ecap)) || (e = pgrc_buf_ensure(c, r.mark, ecap * 4)) ||
+        (e = pgrc_buf_ensure(c, r.rank, ecap * 4)) || (e = pgrc_buf_ensure(c, r.rstart, ecap * 8)) || (e = pgrc_buf_ensure(c, r.rend, ecap * 8)) ||
+        (e = pgrc_buf_ensure(c, r.rdend, ecap * 8)) || (e = pgrc_buf_ensure(c, m->rp.outc, ecap)) || (e = pgrc_buf_ensure(c, m->rp.small, sizeof(MemSmall)))) return e;
+    for (int b = 0; b < 2; b++)
+        if ((e = pgrc_buf_ensure(c, r.skey[b], ecap * 8)) || (e = pgrc_buf_ensure(c, r.sidx[b], ecap * 8))) return e;
+    HIP_TRY(c, hipMemsetAsync(m->rp.small.p, 0, sizeof(MemSmall), c->stream));
     // scratch of the scans below (scanops.h): block folds of nev values
-    if ((e = pgrc_buf_ensure(c, m->d_scan, sco_scratch_elems(nev) * sizeof(uint32_t)))) { m->err = c->err; return e; }
-    uint32_t *d_bsum = (uint32_t *)m->d_scan.p;
-    {
-        uint64_t *sk0 = (uint64_t *)m->d_skey[0].p, *si0 = (uint64_t *)m->d_sidx[0].p;
-        hipLaunchKernelGGL(k_mem_flags, dim3(g), dim3(256), 0, c->stream, a, ek, ep, (uint64_t)nev, (uint8_t *)m->d_oflag.p, sk0, si0, d_nstale);
-        int db = 1;
-        while ((1ull << db) < N2 + m->N) db++;
-        // (diagonal, window) order: the events ARE in window order (step 2), so one stable sort by diagonal does it (until round 4 a
-        // sort by window came first: a third of the sorting time of an event-rich call, for nothing)
-        hipLaunchKernelGGL(k_mem_diag, dim3(g), dim3(256), 0, c->stream, a, ek, ep, (const uint64_t *)si0, (uint64_t)nev, sk0);
-        uint64_t *sks = nullptr, *sis = nullptr;
-        if ((e = pgrc_radix_sort_pairs_u64(c, sk0, (uint64_t *)m->d_skey[1].p, si0, (uint64_t *)m->d_sidx[1].p, nev, 0, (uint32_t)db, m->d_tmp, &sks, &sis))) { m->err = c->err; return e; }
-        const uint64_t *sidx = sis, *skey = sks;
-        hipLaunchKernelGGL(k_mem_connect, dim3(g), dim3(256), 0, c->stream, a, ek, ep, sidx, skey, (uint64_t)nev, (uint32_t *)m->d_first.p);
-        HIP_TRY(m, (sco_scan<true>(c->stream, (const uint32_t *)m->d_first.p, (uint32_t *)m->d_runid.p, (uint64_t)nev, ScoIdentity(), ScoPlus(), 0u, d_bsum)));
-        hipLaunchKernelGGL(k_mem_run_ends, dim3(g), dim3(256), 0, c->stream, a, ek, ep, sidx, (const uint32_t *)m->d_first.p,
-                           (const uint32_t *)m->d_runid.p, (uint64_t)nev, (uint64_t *)m->d_rstart.p, (uint64_t *)m->d_rend.p, (uint64_t *)m->d_rdend.p);
-        hipLaunchKernelGGL(k_mem_apply, dim3(g), dim3(256), 0, c->stream, sidx, (const uint32_t *)m->d_runid.p, (uint64_t)nev,
-                           (const uint64_t *)m->d_rstart.p, (const uint64_t *)m->d_rend.p, min_len, (uint32_t *)m->d_orun.p, (uint8_t *)m->d_oflag.p);
-        HIP_TRY(m, hipGetLastError());
-    }
-    (void)ev.record(3, c->stream);
+    if ((e = pgrc_buf_ensure(c, r.scan, sco_scratch_elems(nev) * sizeof(uint32_t)))) return e;
+    uint64_t *sk0 = (uint64_t *)r.skey[0].p, *si0 = (uint64_t *)r.sidx[0].p;
+    const uint64_t *rstart = (const uint64_t *)r.rstart.p, *rend = (const uint64_t *)r.rend.p;
+    uint8_t *oflag = (uint8_t *)r.oflag.p;
+    hipLaunchKernelGGL(k_mem_flags, dim3(g), dim3(256), 0, c->stream, a, ek, ep, nev, oflag, sk0, si0, m->rp.nstale());
+    int db = 1;
+    while ((1ull << db) < k.N2 + m->src.N) db++;
+    // (diagonal, window) order: the events ARE in window order (step 2), so one stable sort by diagonal does it (until round 4 a
+    // sort by window came first: a third of the sorting time of an event-rich call, for nothing)
+    hipLaunchKernelGGL(k_mem_diag, dim3(g), dim3(256), 0, c->stream, a, ek, ep, (const uint64_t *)si0, nev, sk0);
+    uint64_t *sks = nullptr, *sis = nullptr;
+    if ((e = pgrc_radix_sort_pairs_u64(c, sk0, (uint64_t *)r.skey[1].p, si0, (uint64_t *)r.sidx[1].p, nev, 0, (uint32_t)db, m->evs.tmp, &sks, &sis))) return e;
+    const uint64_t *sidx = sis, *skey = sks;
+    hipLaunchKernelGGL(k_mem_connect, dim3(g), dim3(256), 0, c->stream, a, ek, ep, sidx, skey, nev, r.run_first());
+    HIP_TRY(c, (sco_scan<true>(c->stream, (const uint32_t *)r.run_first(), r.run_id(), nev, ScoIdentity(), ScoPlus(), 0u, r.folds())));
+    hipLaunchKernelGGL(k_mem_run_ends, dim3(g), dim3(256), 0, c->stream, a, ek, ep, sidx, (const uint32_t *)r.run_first(), (const uint32_t *)r.run_id(), nev,
+                       (uint64_t *)r.rstart.p, (uint64_t *)r.rend.p, (uint64_t *)r.rdend.p);
+    hipLaunchKernelGGL(k_mem_apply, dim3(g), dim3(256), 0, c->stream, sidx, (const uint32_t *)r.run_id(), nev, rstart, rend, k.min_len, (uint32_t *)r.orun.p, oflag);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, m->ev.record(3, c->stream));
+    return PGRC_OK;
+}
 
-    // ---- 4. the sequential rules on the device (k_mem_replay)
-    uint64_t nmain;
+// rounds of the replay until no block's incoming match differs from what it assumed
+static int mem_settle(pgrc_mem_ctx *m, const MemCall &k) {
+    pgrc_match_ctx *c = m->base;
+    for (;;) {
+        uint32_t changed = 0;
+        HIP_TRY(c, (sco_scan<false>(c->stream, (const uint32_t *)m->rp.ebout.p, (uint32_t *)m->rp.ebinc.p, (uint64_t)k.ra.neb, ScoIdentity(), MemLastValid(), MR_NONE,
+                                    m->runs.folds())));
+        HIP_TRY(c, hipMemsetAsync(m->rp.changed(), 0, 4, c->stream));
+        hipLaunchKernelGGL(k_mem_replay, dim3(k.replay_grid), dim3(64 * MEM_RP_WAVES), 0, c->stream, k.ra);
+        HIP_TRY(c, hipMemcpyAsync(&changed, m->rp.changed(), 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (!changed) return PGRC_OK;
+        m->ctr.replay_rounds++;
+    }
+}
+
+// ---- 4. the sequential rules on the device (k_mem_replay)
+static int mem_replay(pgrc_mem_ctx *m, MemCall &k) {
+    pgrc_match_ctx *c = m->base;
+    MemRuns &r = m->runs;
+    MemReplay &p = m->rp;
+    const uint64_t nev = k.nev, K = (uint64_t)m->src.K, k2 = (uint64_t)m->src.k2;
+    const uint32_t g = k.grid;
+    int e;
     {   // main loop: blocks of 256 windows while i1 + K + 256 * k2 < N2 + 1 (:365)
         const uint64_t block = 256 * k2;
-        const uint64_t lim = N2 + 1;                                               // i1 + K + block < lim
+        const uint64_t lim = k.N2 + 1;                                             // i1 + K + block < lim
         uint64_t nb = 0;
         if (lim > K + block) nb = (lim - K - block + block - 1) / block;
-        nmain = nb * 256;
+        k.nmain = nb * 256;
     }
-    uint32_t *d_lead = (uint32_t *)m->d_first.p, *d_lid = (uint32_t *)m->d_runid.p;      // (free again: the runs are numbered)
-    hipLaunchKernelGGL(k_mem_lead, dim3(g), dim3(256), 0, c->stream, ek, (uint64_t)nev, nmain, d_lead);
-    HIP_TRY(m, (sco_scan<true>(c->stream, (const uint32_t *)d_lead, d_lid, (uint64_t)nev, ScoIdentity(), ScoPlus(), 0u, d_bsum)));
+    // (r.mark and r.rank are free again: the runs are numbered)
+    hipLaunchKernelGGL(k_mem_lead, dim3(g), dim3(256), 0, c->stream, k.ek, nev, k.nmain, r.block_lead());
+    HIP_TRY(c, (sco_scan<true>(c->stream, (const uint32_t *)r.block_lead(), r.block_id(), nev, ScoIdentity(), ScoPlus(), 0u, r.folds())));
     uint32_t neb = 0, nstale = 0;
-    HIP_TRY(m, hipMemcpyAsync(&neb, d_lid + (nev - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(m, hipMemcpyAsync(&nstale, d_nstale, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(m, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&neb, r.block_id() + (nev - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&nstale, p.nstale(), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     m->ctr.event_blocks = neb;
-    if ((e = pgrc_buf_ensure(c, m->d_ebstart, ((size_t)neb + 1) * 4)) || (e = pgrc_buf_ensure(c, m->d_ebin, (size_t)neb * 4)) ||
-        (e = pgrc_buf_ensure(c, m->d_ebout, (size_t)neb * 4)) || (e = pgrc_buf_ensure(c, m->d_ebinc, (size_t)neb * 4))) { m->err = c->err; return e; }
-    hipLaunchKernelGGL(k_mem_eb_start, dim3(g), dim3(256), 0, c->stream, (const uint32_t *)d_lead, (const uint32_t *)d_lid, (uint64_t)nev, (uint32_t *)m->d_ebstart.p);
-    MemReplayArgs ra;
-    ra.ek = ek;
-    ra.orun = (const uint32_t *)m->d_orun.p;
-    ra.oflag = (const uint8_t *)m->d_oflag.p;
-    ra.outc = (uint8_t *)m->d_outc.p;
-    ra.run_dend = (const uint64_t *)m->d_rdend.p;
-    ra.eb_start = (const uint32_t *)m->d_ebstart.p;
-    ra.eb_in = (uint32_t *)m->d_ebin.p;
-    ra.eb_out = (uint32_t *)m->d_ebout.p;
-    ra.eb_inc = (const uint32_t *)m->d_ebinc.p;
+    if ((e = pgrc_buf_ensure(c, p.ebstart, ((size_t)neb + 1) * 4)) || (e = pgrc_buf_ensure(c, p.ebin, (size_t)neb * 4)) ||
+        (e = pgrc_buf_ensure(c, p.ebout, (size_t)neb * 4)) || (e = pgrc_buf_ensure(c, p.ebinc, (size_t)neb * 4))) return e;
+    hipLaunchKernelGGL(k_mem_eb_start, dim3(g), dim3(256), 0, c->stream, (const uint32_t *)r.block_lead(), (const uint32_t *)r.block_id(), nev, (uint32_t *)p.ebstart.p);
+    MemReplayArgs &ra = k.ra;
+    ra.ek = k.ek;
+    ra.orun = (const uint32_t *)r.orun.p;
+    ra.oflag = (const uint8_t *)r.oflag.p;
+    ra.outc = (uint8_t *)p.outc.p;
+    ra.run_dend = (const uint64_t *)r.rdend.p;
+    ra.eb_start = (const uint32_t *)p.ebstart.p;
+    ra.eb_in = (uint32_t *)p.ebin.p;
+    ra.eb_out = (uint32_t *)p.ebout.p;
+    ra.eb_inc = (const uint32_t *)p.ebinc.p;
     ra.neb = neb;
     ra.K = (uint32_t)K;
     ra.k2 = (uint32_t)k2;
-    ra.skip = (uint32_t)(m->K / m->k1 - 1);                                            // :352
-    ra.changed = d_changed;
+    ra.skip = (uint32_t)(m->src.K / m->src.k1 - 1);                                    // :352
+    ra.changed = p.changed();
     ra.first = 1;
-    const uint32_t gb = (neb + MEM_RP_WAVES - 1) / MEM_RP_WAVES;
-    hipLaunchKernelGGL(k_mem_replay, dim3(gb), dim3(64 * MEM_RP_WAVES), 0, c->stream, ra);
+    k.replay_grid = (neb + MEM_RP_WAVES - 1) / MEM_RP_WAVES;
+    hipLaunchKernelGGL(k_mem_replay, dim3(k.replay_grid), dim3(64 * MEM_RP_WAVES), 0, c->stream, ra);
     m->ctr.replay_rounds = 1;
     ra.first = 0;
-    // rounds until no block's incoming match differs from what it assumed
-    auto settle = [&]() -> int {
-        for (;;) {
-            uint32_t changed = 0;
-            HIP_TRY(m, (sco_scan<false>(c->stream, (const uint32_t *)m->d_ebout.p, (uint32_t *)m->d_ebinc.p, (uint64_t)neb, ScoIdentity(), MemLastValid(), MR_NONE, d_bsum)));
-            HIP_TRY(m, hipMemsetAsync(d_changed, 0, 4, c->stream));
-            hipLaunchKernelGGL(k_mem_replay, dim3(gb), dim3(64 * MEM_RP_WAVES), 0, c->stream, ra);
-            HIP_TRY(m, hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(m, hipStreamSynchronize(c->stream));
-            if (!changed) return PGRC_OK;
-            m->ctr.replay_rounds++;
-        }
-    };
-    if ((e = settle())) return e;
+    if ((e = mem_settle(m, k))) return e;
     // events whose registers are stale, in order: the first one reached is decided on the host, then the replay goes on
     while (nstale) {
         uint32_t x = MR_NONE;
-        HIP_TRY(m, hipMemsetAsync(d_first_stale, 0xFF, 4, c->stream));
-        hipLaunchKernelGGL(k_mem_first_stale, dim3((uint32_t)std::min<uint64_t>((nev + 255) / 256, 4096)), dim3(256), 0, c->stream,
-                           (const uint8_t *)m->d_outc.p, (uint64_t)nev, d_first_stale);
-        HIP_TRY(m, hipMemcpyAsync(&x, d_first_stale, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(m, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemsetAsync(p.first_stale(), 0xFF, 4, c->stream));
+        hipLaunchKernelGGL(k_mem_first_stale, dim3((uint32_t)std::min<uint64_t>((nev + 255) / 256, 4096)), dim3(256), 0, c->stream, (const uint8_t *)p.outc.p, nev,
+                           p.first_stale());
+        HIP_TRY(c, hipMemcpyAsync(&x, p.first_stale(), 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (x == MR_NONE) break;
-        uint64_t key = 0, p = 0;
+        uint64_t key = 0, ps = 0;
         uint8_t fl8 = 0;
-        HIP_TRY(m, hipMemcpy(&key, ek + x, 8, hipMemcpyDeviceToHost));
-        HIP_TRY(m, hipMemcpy(&p, ep + x, 8, hipMemcpyDeviceToHost));
-        HIP_TRY(m, hipMemcpy(&fl8, (const uint8_t *)m->d_oflag.p + x, 1, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpyAsync(&key, k.ek + x, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&ps, k.ep + x, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&fl8, (const uint8_t *)r.oflag.p + x, 1, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
         StaleWalk sw;
-        sw.m = m; sw.dest = dest; sw.d_dw = a.dest; sw.d_dn = a.nmap; sw.N2 = N2; sw.dest_is_src = dest_is_src != 0; sw.rev_compl = rev_compl != 0;
-        sw.skip = ra.skip; sw.nmain = nmain; sw.d_ek = ek; sw.d_outc = (const uint8_t *)m->d_outc.p; sw.nev = nev; sw.d_range = d_range;
+        sw.m = m; sw.dest = k.dest; sw.d_dw = k.a.dest; sw.d_dn = k.a.nmap; sw.N2 = k.N2; sw.dest_is_src = k.dest_is_src; sw.rev_compl = k.rev_compl;
+        sw.skip = ra.skip; sw.nmain = k.nmain; sw.d_ek = k.ek; sw.d_outc = (const uint8_t *)p.outc.p; sw.nev = nev; sw.d_range = p.range();
         const uint64_t t = key >> 4, q = t * k2;
         const uint32_t order = (uint32_t)(key & 15u), fl = fl8;
         m->ctr.stale_lookups++;
         // (c) with the registers as the reference holds them (:401-404)
-        const uint32_t l1 = (fl & MF_L1_OK) ? sw.src32(p - m->LK2) : sw.stale_src_reg(true, t, order);
-        const uint32_t r1 = (fl & MF_R1_OK) ? sw.src32(p + m->KLK24) : sw.stale_src_reg(false, t, order);
-        const uint32_t l2 = (fl & MF_L2_OK) ? sw.dest32(q - m->LK2) : 0u;     // windows below LK2 come first: still the initial 0
-        const uint32_t r2 = (fl & MF_R2_OK) ? sw.dest32(q + m->KLK24) : sw.stale_r2(t);
-        if (sw.lookup_err) { m->err = "bucket lookup failed"; return PGRC_E_DEVICE; }
-        hipLaunchKernelGGL(k_mem_resolve, dim3(1), dim3(1), 0, c->stream, x, (r1 == r2 || l1 == l2) ? 1 : 0, (uint8_t *)m->d_oflag.p,
-                           (const uint32_t *)d_lid, (uint32_t *)m->d_ebin.p);
-        if ((e = settle())) return e;
+        const uint32_t l1 = (fl & MF_L1_OK) ? sw.src32(ps - m->src.LK2) : sw.stale_src_reg(true, t, order);
+        const uint32_t r1 = (fl & MF_R1_OK) ? sw.src32(ps + m->src.KLK24) : sw.stale_src_reg(false, t, order);
+        const uint32_t l2 = (fl & MF_L2_OK) ? sw.dest32(q - m->src.LK2) : 0u;     // windows below LK2 come first: still the initial 0
+        const uint32_t r2 = (fl & MF_R2_OK) ? sw.dest32(q + m->src.KLK24) : sw.stale_r2(t);
+        if (sw.lookup_err) return mem_fail(m, PGRC_E_DEVICE, "bucket lookup failed");
+        hipLaunchKernelGGL(k_mem_resolve, dim3(1), dim3(1), 0, c->stream, x, (r1 == r2 || l1 == l2) ? 1 : 0, (uint8_t *)r.oflag.p, (const uint32_t *)r.block_id(),
+                           (uint32_t *)p.ebin.p);
+        if ((e = mem_settle(m, k))) return e;
     }
-    (void)ev.record(4, c->stream);
+    HIP_TRY(c, m->ev.record(4, c->stream));
+    return PGRC_OK;
+}
 
-    // ---- 5. the matches, in discovery order
+// ---- 5. the matches, in discovery order
+static int mem_emit(pgrc_mem_ctx *m, const MemCall &k, pgrc_text_match **matches, uint64_t *count) {
+    pgrc_match_ctx *c = m->base;
+    MemRuns &r = m->runs;
+    const uint64_t nev = k.nev;
     const auto th0 = std::chrono::steady_clock::now();
-    uint32_t *d_slot = (uint32_t *)m->d_first.p;                                       // (the block leaders are not needed any more)
-    HIP_TRY(m, (sco_scan<true>(c->stream, (const uint8_t *)m->d_outc.p, d_slot, (uint64_t)nev, MemIsAccept(), ScoPlus(), 0u, d_bsum)));
+    uint32_t *d_slot = r.emit_slot();                                                  // (the block leaders are not needed any more)
+    HIP_TRY(c, (sco_scan<true>(c->stream, (const uint8_t *)m->rp.outc.p, d_slot, nev, MemIsAccept(), ScoPlus(), 0u, r.folds())));
     uint32_t nmatch = 0;
-    HIP_TRY(m, hipMemcpyAsync(&nmatch, d_slot + (nev - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(m, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&nmatch, d_slot + (nev - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (nmatch) {
-        if ((e = pgrc_buf_ensure(c, m->d_match, (size_t)nmatch * sizeof(pgrc_text_match)))) { m->err = c->err; return e; }
-        hipLaunchKernelGGL(k_mem_emit, dim3(g), dim3(256), 0, c->stream, ek, ep, (const uint32_t *)m->d_orun.p, (const uint8_t *)m->d_outc.p,
-                           (const uint32_t *)d_slot, (uint64_t)nev, (uint32_t)k2, (const uint64_t *)m->d_rstart.p, (const uint64_t *)m->d_rend.p,
-                           (pgrc_text_match *)m->d_match.p);
-        pgrc_text_match *outp = (pgrc_text_match *)malloc((size_t)nmatch * sizeof(pgrc_text_match));
-        if (!outp) { m->err = "out of host memory"; return PGRC_E_ALLOC; }
-        hipError_t he = hipMemcpyAsync(outp, m->d_match.p, (size_t)nmatch * sizeof(pgrc_text_match), hipMemcpyDeviceToHost, c->stream);
+        const size_t bytes = (size_t)nmatch * sizeof(pgrc_text_match);
+        if (int e = pgrc_buf_ensure(c, m->rp.match, bytes)) return e;
+        hipLaunchKernelGGL(k_mem_emit, dim3(k.grid), dim3(256), 0, c->stream, k.ek, k.ep, (const uint32_t *)r.orun.p, (const uint8_t *)m->rp.outc.p,
+                           (const uint32_t *)d_slot, nev, (uint32_t)m->src.k2, (const uint64_t *)r.rstart.p, (const uint64_t *)r.rend.p,
+                           (pgrc_text_match *)m->rp.match.p);
+        pgrc_text_match *outp = (pgrc_text_match *)malloc(bytes);
+        if (!outp) return mem_fail(m, PGRC_E_ALLOC, "out of host memory");
+        hipError_t he = hipMemcpyAsync(outp, m->rp.match.p, bytes, hipMemcpyDeviceToHost, c->stream);
         if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-        if (he != hipSuccess) { free(outp); m->err = std::string("match download: ") + hipGetErrorString(he); return PGRC_E_DEVICE; }
+        if (he != hipSuccess) { free(outp); return mem_fail(m, PGRC_E_DEVICE, std::string("match download: ") + hipGetErrorString(he)); }
         *matches = outp;
     }
     *count = nmatch;
-    m->ctr.ms_sort = ev.ms(1, 2);
-    m->ctr.ms_extend = ev.ms(2, 3);
-    m->ctr.ms_replay = ev.ms(3, 4);                       // (with the host's part between the rounds)
-    m->ctr.ms_host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - th0).count();
+    m->ctr.ms_sort = m->ev.ms(1, 2);
+    m->ctr.ms_extend = m->ev.ms(2, 3);
+    m->ctr.ms_replay = m->ev.ms(3, 4);                    // (with the host's part between the rounds)
+    m->ctr.ms_host = dec_ms_since(th0);
+    return PGRC_OK;
+}
+
+// matchTexts over a destination on the host or in HBM (MemCall::dest, ::d_ascii)
+static int mem_match(pgrc_mem_ctx *m, const char *dest, const uint8_t *d_ascii, uint64_t N2, int dest_is_src, int rev_compl, uint32_t min_len,
+                     pgrc_text_match **matches, uint64_t *count) {
+    *matches = nullptr;
+    *count = 0;
+    m->dst.ready = false;                 // (a failed call leaves no destination for pgrc_mem_mark_and_remove)
+    if (!m->src.have) return mem_fail(m, PGRC_E_STATE, "match_texts: set the source text first");
+    pgrc_match_ctx *c = m->base;
+    if ((int)min_len < m->src.K) return mem_fail(m, PGRC_E_PARAM, "Minimal matching length cannot be smaller than K");   // :606-609
+    if (dest_is_src && N2 != m->src.N) return mem_fail(m, PGRC_E_PARAM, "match_texts: dest_is_src with a text of another length");
+    if (N2 / (uint64_t)m->src.k2 + 1 >= (1ull << 40)) return mem_fail(m, PGRC_E_PARAM, "destination text too long");
+    if (d_ascii && !mem_on_device(m, d_ascii)) return mem_fail(m, PGRC_E_PARAM, "match_texts_device: the destination is not memory of the context's device");
+    PgrcDeviceScope dev_scope__(c->device);
+    if (!dev_scope__.ok) return mem_fail(m, PGRC_E_NO_DEVICE, "hipSetDevice failed");
+    m->ctr.probes = m->ctr.events = m->ctr.stale_lookups = 0;
+    const uint64_t K = (uint64_t)m->src.K, k2 = (uint64_t)m->src.k2;
+    MemCall k{dest, d_ascii, N2, dest_is_src != 0, rev_compl != 0, min_len, N2 >= K ? (N2 - K) / k2 + 1 : 0};   // (the rest: zero)
+    m->ctr.probes = k.nprobes;
+    int e;
+    if ((e = m->ev.ensure(c))) return e;
+    if ((e = mem_dest_to_hbm(m, k))) return e;
+    if (k.unread_symbol) return PGRC_OK;
+    // the destination is resident from here on: what pgrc_mem_mark_and_remove maps once this call has succeeded
+    auto done = [&]() { return m->dst.done(N2, k.dest_is_src, k.rev_compl, k.a.nmap != nullptr); };
+    if (k.nprobes == 0) return done();    // (a text shorter than K: no window, no match)
+    if ((e = mem_probe(m, k))) return e;
+    if (!k.nev) return done();
+    if (k.nev >= 0xFFFFFFF0ull) return mem_fail(m, PGRC_E_PARAM, "more than 2^32 events");
+    if ((e = mem_order(m, k)) || (e = mem_runs(m, k)) || (e = mem_replay(m, k)) || (e = mem_emit(m, k, matches, count))) return e;
     return done();
 }
 

@@ -281,6 +281,9 @@ __global__ void __launch_bounds__(PM_TPB) k_pm_text(const PmText a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+//
+// Of the match that went before, the mapping reads m->dst (the destination's words, N map and what kind of call it was),
+// m->evs.tmp (the radix sort's scratch) and m->base->txt (the packed source): memctx.h.  Everything else it touches is m->pm / m->res.
 
 static uint32_t pm_bits(uint64_t v) {
     uint32_t b = 0;
@@ -289,20 +292,241 @@ static uint32_t pm_bits(uint64_t v) {
 }
 static uint32_t pm_grid(uint64_t items) { return (uint32_t)std::max<uint64_t>(1, (items + PM_TPB - 1) / PM_TPB); }
 
-void pgrc_pgmap_release(pgrc_mem_ctx *m) {
-    DevBuf *bufs[] = {&m->pm_in, &m->pm_f[0], &m->pm_f[1], &m->pm_f[2], &m->pm_key[0], &m->pm_key[1], &m->pm_idx[0], &m->pm_idx[1], &m->pm_flag,
-                      &m->pm_slot, &m->pm_u[0], &m->pm_u[1], &m->pm_u[2], &m->pm_u[3], &m->pm_pmax, &m->pm_jump[0], &m->pm_jump[1], &m->pm_kept,
-                      &m->pm_m[0], &m->pm_m[1], &m->pm_m[2], &m->pm_dp, &m->pm_len, &m->pm_nb, &m->pm_cum, &m->pm_nbpos, &m->pm_mp, &m->pm_off,
-                      &m->pm_lens, &m->pm_out, &m->pm_fold, &m->pm_small, &m->pm_res[0], &m->pm_res[1], &m->pm_res[2]};
-    for (bool &set : m->res_set) set = false;
-    for (DevBuf *b : bufs) pgrc_buf_free(*b);
-    m->pm_ev.release();
+// every {buffer, bytes} in turn, 64 bytes at least; the first error ends it
+static int pm_ensure(pgrc_mem_ctx *m, std::initializer_list<std::pair<DevBuf *, uint64_t>> want) {
+    for (const auto &w : want)
+        if (int e = pgrc_buf_ensure(m->base, *w.first, (size_t)std::max<uint64_t>(w.second, 64))) return e;
+    return PGRC_OK;
+}
+
+// What the phases of one pm_mark_and_remove call hand to each other; it lives on that function's stack
+struct PmCall {
+    const pgrc_text_match *matches;  // as handed over, on the host
+    uint64_t n;
+    uint64_t N, N2, min_len;
+    uint32_t width;                  // bytes of an entry of the offsets stream
+    bool rc, dis;                    // the match call's rev_compl and dest_is_src
+    int part;                        // 0 .. 2: the mapped text stays in HBM, in that slot; < 0: it goes down to mapped_out
+    char *mapped_out;
+    uint64_t nu = 0, nuniq = 0;      // matches that enter the greedy pass; distinct matches
+    uint64_t marks = 0;
+    uint64_t tot[2] = {0, 0};        // matched symbols; bytes of the length values
+    uint64_t mapped_len = 0;
+    bool resident() const { return part >= 0; }
+};
+
+// ---- 1. normalise, sort by (dst, src, len), unique
+static int pm_sort_unique(pgrc_mem_ctx *m, PmCall &k) {
+    pgrc_match_ctx *c = m->base;
+    PmBufs &b = m->pm;
+    hipStream_t st = c->stream;
+    const uint64_t n = k.n;
+    int e;
+    if ((e = pm_ensure(m, {{&b.in, n * sizeof(pgrc_text_match)}, {&b.f[0], n * 8}, {&b.f[1], n * 8}, {&b.f[2], n * 8}, {&b.key[0], n * 8}, {&b.idx[0], n * 8},
+                           {&b.key[1], n * 8}, {&b.idx[1], n * 8}, {&b.flag, n}, {&b.slot, 2 * n * 4}}))) return e;
+    uint64_t *f_dst = (uint64_t *)b.f[0].p, *f_src = (uint64_t *)b.f[1].p, *f_len = (uint64_t *)b.f[2].p;
+    uint32_t *d_bad = (uint32_t *)b.small.p, *fold32 = (uint32_t *)b.fold.p;
+    HIP_TRY(c, hipMemsetAsync(d_bad, 0, 4, st));
+    HIP_TRY(c, hipMemcpyAsync(b.in.p, k.matches, n * sizeof(pgrc_text_match), hipMemcpyHostToDevice, st));
+    uint64_t *kcur = (uint64_t *)b.key[0].p, *kalt = (uint64_t *)b.key[1].p, *icur = (uint64_t *)b.idx[0].p, *ialt = (uint64_t *)b.idx[1].p;
+    PmNorm a;
+    a.in = (const pgrc_text_match *)b.in.p;
+    a.n = n; a.N = k.N; a.N2 = k.N2;
+    a.dest_is_src = k.dis ? 1u : 0u;
+    a.rev_compl = k.rc ? 1u : 0u;
+    a.dst = f_dst; a.src = f_src; a.len = f_len; a.key = kcur; a.idx = icur;
+    a.bad = d_bad;
+    hipLaunchKernelGGL(k_pm_norm, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, a);
+    uint32_t bad = 0;
+    HIP_TRY(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (bad)
+        return mem_fail(m, PGRC_E_PARAM, std::string("mark_and_remove: a match ") + ((bad & PM_BAD_LEN) ? "of length 0" : (bad & PM_BAD_SRC) ? "reaches past the source's end" : "reaches past the destination's end"));
+    // stable passes over the bits in use, least significant field first
+    const uint64_t *fields[3] = {f_len, f_src, f_dst};
+    const uint32_t fbits[3] = {pm_bits(std::min(k.N, k.N2)), pm_bits(k.N), pm_bits(k.N2)};
+    for (int f = 0; f < 3; f++) {
+        if (f) hipLaunchKernelGGL(k_pm_gather, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, fields[f], (const uint64_t *)icur, n, kcur);
+        uint64_t *ks = nullptr, *vs = nullptr;
+        if ((e = pgrc_radix_sort_pairs_u64(c, kcur, kalt, icur, ialt, n, 0, fbits[f], m->evs.tmp, &ks, &vs))) return e;
+        if (vs != icur) { std::swap(icur, ialt); std::swap(kcur, kalt); }
+    }
+    uint32_t *d_slot = (uint32_t *)b.slot.p, *d_uslot = d_slot + n;
+    hipLaunchKernelGGL(k_pm_uniq, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, (const uint64_t *)icur, (const uint64_t *)f_dst, (const uint64_t *)f_src,
+                       (const uint64_t *)f_len, n, k.min_len, (uint8_t *)b.flag.p);
+    HIP_TRY(c, (sco_scan<true>(st, (const uint8_t *)b.flag.p, d_slot, n, PmBit0(), ScoPlus(), 0u, fold32)));
+    HIP_TRY(c, (sco_scan<true>(st, (const uint8_t *)b.flag.p, d_uslot, n, PmBit1(), ScoPlus(), 0u, fold32)));
+    uint32_t cnt[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(&cnt[0], d_slot + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&cnt[1], d_uslot + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    k.nu = cnt[0];
+    k.nuniq = cnt[1];
+    if (k.nu) {
+        if ((e = pm_ensure(m, {{&b.u[0], k.nu * 8}, {&b.u[1], k.nu * 8}, {&b.u[2], k.nu * 8}, {&b.u[3], k.nu * 8}}))) return e;
+        hipLaunchKernelGGL(k_pm_compact, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, (const uint64_t *)icur, (const uint8_t *)b.flag.p, (const uint32_t *)d_slot,
+                           (const uint64_t *)f_dst, (const uint64_t *)f_src, (const uint64_t *)f_len, n, k.min_len, (uint64_t *)b.u[0].p, (uint64_t *)b.u[1].p,
+                           (uint64_t *)b.u[2].p, (uint64_t *)b.u[3].p);
+    }
+    return PGRC_OK;
+}
+
+// ---- 2. the greedy pass as a path
+static int pm_greedy_path(pgrc_mem_ctx *m, PmCall &k) {
+    pgrc_match_ctx *c = m->base;
+    PmBufs &b = m->pm;
+    hipStream_t st = c->stream;
+    const uint64_t nu = k.nu;
+    const uint64_t *ud = (const uint64_t *)b.u[0].p, *us = (const uint64_t *)b.u[1].p, *ue = (const uint64_t *)b.u[2].p, *ut = (const uint64_t *)b.u[3].p;
+    if (int e = pm_ensure(m, {{&b.pmax, nu * 8}, {&b.jump[0], (nu + 1) * 4}, {&b.jump[1], (nu + 1) * 4}, {&b.kept, (nu + 1) * 4}, {&b.slot, nu * 4},
+                              {&b.m[0], nu * 8}, {&b.m[1], nu * 8}, {&b.m[2], nu * 8}})) return e;
+    uint64_t *pmax = (uint64_t *)b.pmax.p;
+    uint32_t *kept = (uint32_t *)b.kept.p, *kslot = (uint32_t *)b.slot.p;
+    HIP_TRY(c, (sco_device_scan<true, false>(st, ScoLoad<uint64_t, uint64_t, ScoIdentity>{ut, ScoIdentity{}}, nu, PmMax(), (uint64_t)0, (uint64_t)0,
+                                             ScoStore<uint64_t>{pmax}, (uint64_t *)b.fold.p)));
+    uint32_t *jin = (uint32_t *)b.jump[0].p, *jout = (uint32_t *)b.jump[1].p;
+    hipLaunchKernelGGL(k_pm_next, dim3(pm_grid(nu + 1)), dim3(PM_TPB), 0, st, ue, (const uint64_t *)pmax, nu, jin, kept);
+    for (uint64_t reach = 1; reach < nu; reach <<= 1) {
+        hipLaunchKernelGGL(k_pm_jump, dim3(pm_grid(nu + 1)), dim3(PM_TPB), 0, st, (const uint32_t *)jin, jout, kept, nu);
+        std::swap(jin, jout);
+    }
+    HIP_TRY(c, (sco_scan<true>(st, (const uint32_t *)kept, kslot, nu, ScoIdentity(), ScoPlus(), 0u, (uint32_t *)b.fold.p)));
+    uint32_t nk = 0;
+    HIP_TRY(c, hipMemcpyAsync(&nk, kslot + (nu - 1), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    k.marks = nk;
+    hipLaunchKernelGGL(k_pm_marks, dim3(pm_grid(nu)), dim3(PM_TPB), 0, st, (const uint32_t *)kept, (const uint32_t *)kslot, ud, us, ue, nu, (uint64_t *)b.m[0].p,
+                       (uint64_t *)b.m[1].p, (uint64_t *)b.m[2].p);
+    return PGRC_OK;
+}
+
+// ---- 3. the marks and the two streams
+static int pm_streams(pgrc_mem_ctx *m, PmCall &k) {
+    pgrc_match_ctx *c = m->base;
+    PmBufs &b = m->pm;
+    hipStream_t st = c->stream;
+    const uint64_t marks = k.marks;
+    int e;
+    if ((e = pm_ensure(m, {{&b.dp, marks * 8}, {&b.len, marks * 8}, {&b.nb, marks}, {&b.cum, (marks + 1) * 8}, {&b.nbpos, (marks + 1) * 8}, {&b.mp, marks * 8},
+                           {&b.off, marks * k.width}}))) return e;
+    uint64_t *cum = (uint64_t *)b.cum.p, *nbpos = (uint64_t *)b.nbpos.p, *fold64 = (uint64_t *)b.fold.p;
+    if (marks)
+        hipLaunchKernelGGL(k_pm_shape, dim3(pm_grid(marks)), dim3(PM_TPB), 0, st, (const uint64_t *)b.m[0].p, (const uint64_t *)b.m[1].p, (const uint64_t *)b.m[2].p,
+                           marks, k.rc ? 1u : 0u, k.min_len, k.width, (uint64_t *)b.dp.p, (uint64_t *)b.len.p, (uint8_t *)b.nb.p, b.off.p);
+    HIP_TRY(c, (sco_sum_u64<false>(st, (const uint64_t *)b.len.p, marks, cum, fold64)));
+    HIP_TRY(c, (sco_sum_u64<false>(st, (const uint8_t *)b.nb.p, marks, nbpos, fold64)));
+    HIP_TRY(c, hipMemcpyAsync(&k.tot[0], cum + marks, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&k.tot[1], nbpos + marks, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (k.tot[0] > k.N2 || k.tot[1] > 10 * marks) return mem_fail(m, PGRC_E_DEVICE, "mark_and_remove: inconsistent marks");
+    if ((e = pm_ensure(m, {{&b.lens, k.tot[1]}}))) return e;
+    if (marks)
+        hipLaunchKernelGGL(k_pm_streams, dim3(pm_grid(marks)), dim3(PM_TPB), 0, st, (const uint64_t *)b.dp.p, (const uint64_t *)b.len.p, (const uint64_t *)cum,
+                           (const uint64_t *)nbpos, marks, k.min_len, (uint64_t *)b.mp.p, (uint8_t *)b.lens.p);
+    return PGRC_OK;
+}
+
+// ---- 4. the mapped text
+static int pm_text(pgrc_mem_ctx *m, PmCall &k) {
+    pgrc_match_ctx *c = m->base;
+    k.mapped_len = k.N2 - k.tot[0] + k.marks;                  // (every mark replaces at least one symbol: <= N2)
+    const uint64_t nwords = (k.mapped_len + 7) / 8;
+    DevBuf &text_buf = k.resident() ? m->res.text[k.part] : m->pm.out;
+    if (int e = pm_ensure(m, {{&text_buf, nwords * 8}})) return e;
+    if (!nwords) return PGRC_OK;
+    PmText t;
+    t.text = k.dis ? (const uint32_t *)c->txt.pg2[0].p : (const uint32_t *)m->dst.words.p;
+    t.nmap = (!k.dis && m->dst.has_n) ? (const uint16_t *)m->dst.nmap.p : nullptr;
+    t.N2 = k.N2;
+    t.mirror = (!k.dis && k.rc) ? 1u : 0u;
+    t.mp = (const uint64_t *)m->pm.mp.p;
+    t.cum = (const uint64_t *)m->pm.cum.p;
+    t.marks = k.marks;
+    t.mapped_len = k.mapped_len;
+    t.nwords = nwords;
+    t.out = (uint64_t *)text_buf.p;
+    hipLaunchKernelGGL(k_pm_text, dim3(pm_grid((nwords + PM_LPT - 1) / PM_LPT)), dim3(PM_TPB), 0, c->stream, t);
+    HIP_TRY(c, hipGetLastError());
+    return PGRC_OK;
+}
+
+// ---- 5. the downloads
+static int pm_download(pgrc_mem_ctx *m, const PmCall &k, pgrc_mem_mapping *out) {
+    hipStream_t st = m->base->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint8_t hdr[10];
+    uint32_t nh = 0;
+    for (uint64_t v = k.min_len;; v /= 128) {
+        if (v >= 128) hdr[nh++] = (uint8_t)(128 + v % 128);
+        else { hdr[nh++] = (uint8_t)v; break; }
+    }
+    const uint64_t off_bytes = k.marks * k.width, len_bytes = nh + k.tot[1];
+    uint8_t *block = (uint8_t *)malloc((size_t)(off_bytes + len_bytes + 1));
+    if (!block) return mem_fail(m, PGRC_E_ALLOC, "out of host memory");
+    memcpy(block + off_bytes, hdr, nh);
+    hipError_t he = hipSuccess;
+    if (off_bytes) he = hipMemcpyAsync(block, m->pm.off.p, off_bytes, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && k.tot[1]) he = hipMemcpyAsync(block + off_bytes + nh, m->pm.lens.p, k.tot[1], hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && k.mapped_len && !k.resident()) he = hipMemcpyAsync(k.mapped_out, m->pm.out.p, k.mapped_len, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) { free(block); return mem_fail(m, pgrc_hip_code(he), std::string("mapping download: ") + hipGetErrorString(he)); }
+    m->pm.ms[4] = dec_ms_since(t0);
+    out->mapped_len = k.mapped_len;
+    out->marks = k.marks;
+    out->unique_matches = k.nuniq;
+    out->matched_symbols = k.tot[0];
+    out->map_off = block;
+    out->map_off_bytes = off_bytes;
+    out->map_len = block + off_bytes;
+    out->map_len_bytes = len_bytes;
+    return PGRC_OK;
 }
 
 // pgrc_mem_mark_and_remove (part < 0: the mapped text goes down to mapped_out) and pgrc_mem_mark_and_remove_resident (part
 // 0 .. 2: it stays in HBM, in the context's slot `part`)
 static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, uint64_t count, uint32_t min_match_len, char *mapped_out,
-                              uint64_t mapped_cap, int part, pgrc_mem_mapping *out);
+                              uint64_t mapped_cap, int part, pgrc_mem_mapping *out) {
+    if (!m || !out) return PGRC_E_PARAM;
+    memset(out, 0, sizeof *out);
+    const bool resident = part >= 0;
+    if (resident) m->res.set[part] = false;                    // (a failed call leaves no text in the slot)
+    if (!m->dst.ready || !m->src.have) return mem_fail(m, PGRC_E_STATE, "mark_and_remove: no destination (call pgrc_mem_match_texts first)");
+    const uint64_t N = m->src.N, N2 = m->dst.n2;
+    const uint64_t min_len = min_match_len == UINT32_MAX ? m->src.L : min_match_len;
+    if (min_len == 0) return mem_fail(m, PGRC_E_PARAM, "mark_and_remove: min_match_len is 0");
+    if (!resident && (mapped_cap < N2 || (N2 && !mapped_out))) return mem_fail(m, PGRC_E_PARAM, "mark_and_remove: mapped_out is smaller than the destination");
+    if (count && !matches) return PGRC_E_PARAM;
+    if (count >= 0xFFFFF000ull) return mem_fail(m, PGRC_E_PARAM, "mark_and_remove: too many matches");
+    pgrc_match_ctx *c = m->base;
+    PgrcDeviceScope dev_scope__(c->device);
+    if (!dev_scope__.ok) return mem_fail(m, PGRC_E_NO_DEVICE, "hipSetDevice failed");
+    int e = m->pm.ev.ensure(c);
+    if (e) return e;
+    auto &ev = m->pm.ev;
+    hipStream_t st = c->stream;
+    PmCall k{matches, count, N, N2, min_len, N <= UINT32_MAX ? 4u : 8u, m->dst.rev_compl, m->dst.dest_is_src, part, mapped_out};
+    if ((e = pm_ensure(m, {{&m->pm.fold, sco_scratch_elems(std::max<uint64_t>(count, 1)) * 8}, {&m->pm.small, 64}}))) return e;
+    HIP_TRY(c, ev.record(0, st));
+    if (k.n && (e = pm_sort_unique(m, k))) return e;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, ev.record(1, st));
+    if (k.nu && (e = pm_greedy_path(m, k))) return e;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, ev.record(2, st));
+    if ((e = pm_streams(m, k))) return e;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, ev.record(3, st));
+    if ((e = pm_text(m, k))) return e;
+    HIP_TRY(c, ev.record(4, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if ((e = pm_download(m, k, out))) return e;
+    for (int p = 0; p < 4; p++) m->pm.ms[p] = ev.ms(p, p + 1);
+    if (resident) {
+        m->res.len[part] = k.mapped_len;
+        m->res.set[part] = true;
+    }
+    return PGRC_OK;
+}
 
 extern "C" {
 
@@ -314,7 +538,7 @@ void pgrc_mem_free_mapping(pgrc_mem_mapping *mp) {
 
 int pgrc_mem_mapping_timing(pgrc_mem_ctx *m, float ms[5]) {
     if (!m || !ms) return PGRC_E_PARAM;
-    memcpy(ms, m->pm_ms, sizeof m->pm_ms);
+    memcpy(ms, m->pm.ms, sizeof m->pm.ms);
     return PGRC_OK;
 }
 
@@ -327,243 +551,29 @@ int pgrc_mem_mark_and_remove_resident(pgrc_mem_ctx *m, const pgrc_text_match *ma
                                       pgrc_mem_mapping *out) {
     if (m && out && (part < 0 || part > 2)) {
         memset(out, 0, sizeof *out);
-        m->err = "mark_and_remove_resident: part must be 0 (HQ), 1 (LQ) or 2 (N)";
-        return PGRC_E_PARAM;
+        return mem_fail(m, PGRC_E_PARAM, "mark_and_remove_resident: part must be 0 (HQ), 1 (LQ) or 2 (N)");
     }
     return pm_mark_and_remove(m, matches, count, min_match_len, nullptr, 0, part, out);
 }
 
 int pgrc_mem_encode_mapped(pgrc_mem_ctx *m, pgrc_varlen *v, void *coded_out, uint64_t cap, uint64_t *coded_len, uint64_t lens[3]) {
     if (!m) return PGRC_E_PARAM;
-    if (!v || !coded_len || !lens) { m->err = "encode_mapped: the coder, coded_len or lens is NULL"; return PGRC_E_PARAM; }
+    if (!v || !coded_len || !lens) return mem_fail(m, PGRC_E_PARAM, "encode_mapped: the coder, coded_len or lens is NULL");
     *coded_len = 0;
     lens[0] = lens[1] = lens[2] = 0;
-    if (!m->res_set[0] || !m->res_set[1]) {
-        m->err = "encode_mapped: no resident HQ or LQ text (call pgrc_mem_mark_and_remove_resident for parts 1, 2 and 0 first)";
-        return PGRC_E_STATE;
-    }
-    if (v->device != m->base->device) { m->err = "encode_mapped: the coder is on another device"; return PGRC_E_PARAM; }
+    if (!m->res.set[0] || !m->res.set[1])
+        return mem_fail(m, PGRC_E_STATE, "encode_mapped: no resident HQ or LQ text (call pgrc_mem_mark_and_remove_resident for parts 1, 2 and 0 first)");
+    if (v->device != m->base->device) return mem_fail(m, PGRC_E_PARAM, "encode_mapped: the coder is on another device");
     pgrc_varlen_part parts[3];
     for (int p = 0; p < 3; p++) {
-        parts[p].len = m->res_set[p] ? m->res_len[p] : 0;       // (an unset N slot: an empty part)
-        parts[p].ptr = m->pm_res[p].p;
+        parts[p].len = m->res.set[p] ? m->res.len[p] : 0;       // (an unset N slot: an empty part)
+        parts[p].ptr = m->res.text[p].p;
         parts[p].on_device = 1;
     }
     const int e = pgrc_varlen_encode(v, parts, 3, coded_out, cap, 0, coded_len);
-    if (e) { m->err = std::string("encode_mapped: ") + pgrc_varlen_last_error(v); return e; }
+    if (e) return mem_fail(m, e, std::string("encode_mapped: ") + pgrc_varlen_last_error(v));
     for (int p = 0; p < 3; p++) lens[p] = parts[p].len;
     return PGRC_OK;
 }
 
 } // extern "C"
-
-static int pm_mark_and_remove(pgrc_mem_ctx *m, const pgrc_text_match *matches, uint64_t count, uint32_t min_match_len, char *mapped_out,
-                              uint64_t mapped_cap, int part, pgrc_mem_mapping *out) {
-    if (!m || !out) return PGRC_E_PARAM;
-    memset(out, 0, sizeof *out);
-    const bool resident = part >= 0;
-    if (resident) m->res_set[part] = false;                    // (a failed call leaves no text in the slot)
-    if (!m->map_ready || !m->have_src) { m->err = "mark_and_remove: no destination (call pgrc_mem_match_texts first)"; return PGRC_E_STATE; }
-    const uint64_t N = m->N, N2 = m->map_n2, n = count;
-    const uint64_t min_len = min_match_len == UINT32_MAX ? m->L : min_match_len;
-    if (min_len == 0) { m->err = "mark_and_remove: min_match_len is 0"; return PGRC_E_PARAM; }
-    if (!resident && (mapped_cap < N2 || (N2 && !mapped_out))) { m->err = "mark_and_remove: mapped_out is smaller than the destination"; return PGRC_E_PARAM; }
-    if (n && !matches) return PGRC_E_PARAM;
-    if (n >= 0xFFFFF000ull) { m->err = "mark_and_remove: too many matches"; return PGRC_E_PARAM; }
-    pgrc_match_ctx *c = m->base;
-    PgrcDeviceScope dev_scope__(c->device);
-    if (!dev_scope__.ok) { m->err = "hipSetDevice failed"; return PGRC_E_NO_DEVICE; }
-    int e = m->pm_ev.ensure(m);
-    if (e) return e;
-    auto &ev = m->pm_ev;
-    hipStream_t st = c->stream;
-    auto ens = [&](DevBuf &b, uint64_t bytes) {
-        if (!e && (e = pgrc_buf_ensure(c, b, (size_t)std::max<uint64_t>(bytes, 64)))) m->err = c->err;
-    };
-    const bool rc = m->map_rev_compl, dis = m->map_dest_is_src;
-    const uint32_t width = N <= UINT32_MAX ? 4u : 8u;
-    ens(m->pm_fold, sco_scratch_elems(std::max<uint64_t>(n, 1)) * 8);
-    ens(m->pm_small, 64);
-    if (e) return e;
-    uint64_t *fold64 = (uint64_t *)m->pm_fold.p;
-    uint32_t *fold32 = (uint32_t *)m->pm_fold.p;
-    HIP_TRY(m, ev.record(0, st));
-
-    // ---- 1. normalise, sort by (dst, src, len), unique
-    uint64_t nu = 0, nuniq = 0;
-    if (n) {
-        ens(m->pm_in, n * sizeof(pgrc_text_match));
-        for (int k = 0; k < 3; k++) ens(m->pm_f[k], n * 8);
-        for (int k = 0; k < 2; k++) { ens(m->pm_key[k], n * 8); ens(m->pm_idx[k], n * 8); }
-        ens(m->pm_flag, n);
-        ens(m->pm_slot, 2 * n * 4);
-        if (e) return e;
-        uint64_t *f_dst = (uint64_t *)m->pm_f[0].p, *f_src = (uint64_t *)m->pm_f[1].p, *f_len = (uint64_t *)m->pm_f[2].p;
-        uint32_t *d_bad = (uint32_t *)m->pm_small.p;
-        HIP_TRY(m, hipMemsetAsync(d_bad, 0, 4, st));
-        HIP_TRY(m, hipMemcpyAsync(m->pm_in.p, matches, n * sizeof(pgrc_text_match), hipMemcpyHostToDevice, st));
-        uint64_t *kcur = (uint64_t *)m->pm_key[0].p, *kalt = (uint64_t *)m->pm_key[1].p, *icur = (uint64_t *)m->pm_idx[0].p, *ialt = (uint64_t *)m->pm_idx[1].p;
-        PmNorm a;
-        a.in = (const pgrc_text_match *)m->pm_in.p;
-        a.n = n; a.N = N; a.N2 = N2;
-        a.dest_is_src = dis ? 1u : 0u;
-        a.rev_compl = rc ? 1u : 0u;
-        a.dst = f_dst; a.src = f_src; a.len = f_len; a.key = kcur; a.idx = icur;
-        a.bad = d_bad;
-        hipLaunchKernelGGL(k_pm_norm, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, a);
-        uint32_t bad = 0;
-        HIP_TRY(m, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(m, hipStreamSynchronize(st));
-        if (bad) {
-            m->err = std::string("mark_and_remove: a match ") + ((bad & PM_BAD_LEN) ? "of length 0" : (bad & PM_BAD_SRC) ? "reaches past the source's end" : "reaches past the destination's end");
-            return PGRC_E_PARAM;
-        }
-        // stable passes over the bits in use, least significant field first
-        const uint64_t *fields[3] = {f_len, f_src, f_dst};
-        const uint32_t fbits[3] = {pm_bits(std::min(N, N2)), pm_bits(N), pm_bits(N2)};
-        for (int f = 0; f < 3; f++) {
-            if (f) hipLaunchKernelGGL(k_pm_gather, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, fields[f], (const uint64_t *)icur, n, kcur);
-            uint64_t *ks = nullptr, *vs = nullptr;
-            if ((e = pgrc_radix_sort_pairs_u64(c, kcur, kalt, icur, ialt, n, 0, fbits[f], m->d_tmp, &ks, &vs))) { m->err = c->err; return e; }
-            if (vs != icur) { std::swap(icur, ialt); std::swap(kcur, kalt); }
-        }
-        uint32_t *d_slot = (uint32_t *)m->pm_slot.p, *d_uslot = d_slot + n;
-        hipLaunchKernelGGL(k_pm_uniq, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, (const uint64_t *)icur, (const uint64_t *)f_dst, (const uint64_t *)f_src,
-                           (const uint64_t *)f_len, n, min_len, (uint8_t *)m->pm_flag.p);
-        HIP_TRY(m, (sco_scan<true>(st, (const uint8_t *)m->pm_flag.p, d_slot, n, PmBit0(), ScoPlus(), 0u, fold32)));
-        HIP_TRY(m, (sco_scan<true>(st, (const uint8_t *)m->pm_flag.p, d_uslot, n, PmBit1(), ScoPlus(), 0u, fold32)));
-        uint32_t cnt[2] = {0, 0};
-        HIP_TRY(m, hipMemcpyAsync(&cnt[0], d_slot + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(m, hipMemcpyAsync(&cnt[1], d_uslot + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(m, hipStreamSynchronize(st));
-        nu = cnt[0];
-        nuniq = cnt[1];
-        if (nu) {
-            for (int k = 0; k < 4; k++) ens(m->pm_u[k], nu * 8);
-            if (e) return e;
-            hipLaunchKernelGGL(k_pm_compact, dim3(pm_grid(n)), dim3(PM_TPB), 0, st, (const uint64_t *)icur, (const uint8_t *)m->pm_flag.p, (const uint32_t *)d_slot,
-                               (const uint64_t *)f_dst, (const uint64_t *)f_src, (const uint64_t *)f_len, n, min_len, (uint64_t *)m->pm_u[0].p,
-                               (uint64_t *)m->pm_u[1].p, (uint64_t *)m->pm_u[2].p, (uint64_t *)m->pm_u[3].p);
-        }
-    }
-    HIP_TRY(m, hipGetLastError());
-    HIP_TRY(m, ev.record(1, st));
-
-    // ---- 2. the greedy pass as a path
-    uint64_t marks = 0;
-    if (nu) {
-        const uint64_t *ud = (const uint64_t *)m->pm_u[0].p, *us = (const uint64_t *)m->pm_u[1].p, *ue = (const uint64_t *)m->pm_u[2].p, *ut = (const uint64_t *)m->pm_u[3].p;
-        ens(m->pm_pmax, nu * 8);
-        for (int k = 0; k < 2; k++) ens(m->pm_jump[k], (nu + 1) * 4);
-        ens(m->pm_kept, (nu + 1) * 4);
-        ens(m->pm_slot, nu * 4);
-        for (int k = 0; k < 3; k++) ens(m->pm_m[k], nu * 8);
-        if (e) return e;
-        uint64_t *pmax = (uint64_t *)m->pm_pmax.p;
-        uint32_t *kept = (uint32_t *)m->pm_kept.p, *kslot = (uint32_t *)m->pm_slot.p;
-        HIP_TRY(m, (sco_device_scan<true, false>(st, ScoLoad<uint64_t, uint64_t, ScoIdentity>{ut, ScoIdentity{}}, nu, PmMax(), (uint64_t)0, (uint64_t)0,
-                                                 ScoStore<uint64_t>{pmax}, fold64)));
-        uint32_t *jin = (uint32_t *)m->pm_jump[0].p, *jout = (uint32_t *)m->pm_jump[1].p;
-        hipLaunchKernelGGL(k_pm_next, dim3(pm_grid(nu + 1)), dim3(PM_TPB), 0, st, ue, (const uint64_t *)pmax, nu, jin, kept);
-        for (uint64_t reach = 1; reach < nu; reach <<= 1) {
-            hipLaunchKernelGGL(k_pm_jump, dim3(pm_grid(nu + 1)), dim3(PM_TPB), 0, st, (const uint32_t *)jin, jout, kept, nu);
-            std::swap(jin, jout);
-        }
-        HIP_TRY(m, (sco_scan<true>(st, (const uint32_t *)kept, kslot, nu, ScoIdentity(), ScoPlus(), 0u, fold32)));
-        uint32_t nk = 0;
-        HIP_TRY(m, hipMemcpyAsync(&nk, kslot + (nu - 1), 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(m, hipStreamSynchronize(st));
-        marks = nk;
-        hipLaunchKernelGGL(k_pm_marks, dim3(pm_grid(nu)), dim3(PM_TPB), 0, st, (const uint32_t *)kept, (const uint32_t *)kslot, ud, us, ue, nu,
-                           (uint64_t *)m->pm_m[0].p, (uint64_t *)m->pm_m[1].p, (uint64_t *)m->pm_m[2].p);
-    }
-    HIP_TRY(m, hipGetLastError());
-    HIP_TRY(m, ev.record(2, st));
-
-    // ---- 3. the marks and the two streams
-    ens(m->pm_dp, marks * 8);
-    ens(m->pm_len, marks * 8);
-    ens(m->pm_nb, marks);
-    ens(m->pm_cum, (marks + 1) * 8);
-    ens(m->pm_nbpos, (marks + 1) * 8);
-    ens(m->pm_mp, marks * 8);
-    ens(m->pm_off, marks * width);
-    if (e) return e;
-    uint64_t *cum = (uint64_t *)m->pm_cum.p, *nbpos = (uint64_t *)m->pm_nbpos.p;
-    if (marks)
-        hipLaunchKernelGGL(k_pm_shape, dim3(pm_grid(marks)), dim3(PM_TPB), 0, st, (const uint64_t *)m->pm_m[0].p, (const uint64_t *)m->pm_m[1].p,
-                           (const uint64_t *)m->pm_m[2].p, marks, rc ? 1u : 0u, min_len, width, (uint64_t *)m->pm_dp.p, (uint64_t *)m->pm_len.p,
-                           (uint8_t *)m->pm_nb.p, m->pm_off.p);
-    HIP_TRY(m, (sco_sum_u64<false>(st, (const uint64_t *)m->pm_len.p, marks, cum, fold64)));
-    HIP_TRY(m, (sco_sum_u64<false>(st, (const uint8_t *)m->pm_nb.p, marks, nbpos, fold64)));
-    uint64_t tot[2] = {0, 0};                                  // matched symbols; bytes of the length values
-    HIP_TRY(m, hipMemcpyAsync(&tot[0], cum + marks, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(m, hipMemcpyAsync(&tot[1], nbpos + marks, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(m, hipStreamSynchronize(st));
-    if (tot[0] > N2 || tot[1] > 10 * marks) { m->err = "mark_and_remove: inconsistent marks"; return PGRC_E_DEVICE; }
-    ens(m->pm_lens, tot[1]);
-    if (e) return e;
-    if (marks)
-        hipLaunchKernelGGL(k_pm_streams, dim3(pm_grid(marks)), dim3(PM_TPB), 0, st, (const uint64_t *)m->pm_dp.p, (const uint64_t *)m->pm_len.p,
-                           (const uint64_t *)cum, (const uint64_t *)nbpos, marks, min_len, (uint64_t *)m->pm_mp.p, (uint8_t *)m->pm_lens.p);
-    HIP_TRY(m, hipGetLastError());
-    HIP_TRY(m, ev.record(3, st));
-
-    // ---- 4. the mapped text
-    const uint64_t mapped_len = N2 - tot[0] + marks;           // (every mark replaces at least one symbol: <= N2)
-    const uint64_t nwords = (mapped_len + 7) / 8;
-    DevBuf &text_buf = resident ? m->pm_res[part] : m->pm_out;
-    ens(text_buf, nwords * 8);
-    if (e) return e;
-    if (nwords) {
-        PmText t;
-        t.text = dis ? (const uint32_t *)c->txt.pg2[0].p : (const uint32_t *)m->d_dest.p;
-        t.nmap = (!dis && m->map_has_n) ? (const uint16_t *)m->d_nmap.p : nullptr;
-        t.N2 = N2;
-        t.mirror = (!dis && rc) ? 1u : 0u;
-        t.mp = (const uint64_t *)m->pm_mp.p;
-        t.cum = cum;
-        t.marks = marks;
-        t.mapped_len = mapped_len;
-        t.nwords = nwords;
-        t.out = (uint64_t *)text_buf.p;
-        hipLaunchKernelGGL(k_pm_text, dim3(pm_grid((nwords + PM_LPT - 1) / PM_LPT)), dim3(PM_TPB), 0, st, t);
-        HIP_TRY(m, hipGetLastError());
-    }
-    HIP_TRY(m, ev.record(4, st));
-    HIP_TRY(m, hipStreamSynchronize(st));
-
-    // ---- 5. the downloads
-    const auto t0 = std::chrono::steady_clock::now();
-    uint8_t hdr[10];
-    uint32_t nh = 0;
-    for (uint64_t v = min_len;; v /= 128) {
-        if (v >= 128) hdr[nh++] = (uint8_t)(128 + v % 128);
-        else { hdr[nh++] = (uint8_t)v; break; }
-    }
-    const uint64_t off_bytes = marks * width, len_bytes = nh + tot[1];
-    uint8_t *block = (uint8_t *)malloc((size_t)(off_bytes + len_bytes + 1));
-    if (!block) { m->err = "out of host memory"; return PGRC_E_ALLOC; }
-    memcpy(block + off_bytes, hdr, nh);
-    hipError_t he = hipSuccess;
-    if (off_bytes) he = hipMemcpyAsync(block, m->pm_off.p, off_bytes, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && tot[1]) he = hipMemcpyAsync(block + off_bytes + nh, m->pm_lens.p, tot[1], hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && mapped_len && !resident) he = hipMemcpyAsync(mapped_out, m->pm_out.p, mapped_len, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) { free(block); m->err = std::string("mapping download: ") + hipGetErrorString(he); return pgrc_hip_code(he); }
-    m->pm_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (int k = 0; k < 4; k++) m->pm_ms[k] = ev.ms(k, k + 1);
-    out->mapped_len = mapped_len;
-    out->marks = marks;
-    out->unique_matches = nuniq;
-    out->matched_symbols = tot[0];
-    out->map_off = block;
-    out->map_off_bytes = off_bytes;
-    out->map_len = block + off_bytes;
-    out->map_len_bytes = len_bytes;
-    if (resident) {
-        m->res_len[part] = mapped_len;
-        m->res_set[part] = true;
-    }
-    return PGRC_OK;
-}

@@ -30,9 +30,6 @@ void pgrc_stage_close(PgrcStage *s);    // waits for the stream; safe on a stage
 
 static inline uint64_t dec_a16(uint64_t b) { return (b + 15) & ~15ull; }
 static inline uint32_t dec_grid(uint64_t n, uint32_t tpb) { return (uint32_t)((n + tpb - 1) / tpb); }
-static inline float dec_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 static int dec_fail(PgrcStage *d, int code, const std::string &msg) {
     d->err = msg;
