@@ -31,3 +31,5 @@ from .overlap import OverlapFinder  # noqa: F401
 from .varlen import VarLenDNACoder  # noqa: F401
 from .rlist import ReadsList  # noqa: F401
 from .verify import Verifier  # noqa: F401
+from . import archive  # noqa: F401
+from .pipeline import compress, decompress  # noqa: F401

@@ -27,7 +27,10 @@ def _wait_for_torch(*args) -> None:
 
 
 def _view(a):
-    """-> (keep-alive object, pointer or None, length, on_device)"""
+    """-> (keep-alive object, pointer or None, length, on_device); a tuple (address, length) is raw memory of the coder's device"""
+    if isinstance(a, tuple):
+        ptr, n = int(a[0] or 0), int(a[1])
+        return a, (ptr if n else None), n, 1
     if _is_tensor(a):
         import torch
         if a.dtype != torch.uint8 or not a.is_contiguous():
@@ -61,7 +64,8 @@ class VarLenDNACoder:
         return int(lib.pgrc_varlen_bound(int(n)))
 
     def encode(self, parts, out=None):
-        """parts: one text or a list of up to three (HQ | LQ | N), coded as ONE text.  out: a uint8 host array or device
+        """parts: one text or a list of up to three (HQ | LQ | N), coded as ONE text; a part may be a tuple (device address,
+        length), such as PgAssembler.text_device() gives, complete before the call (include/pgrc_varlen.h).  out: a uint8 host array or device
         tensor to write into; without it, a device tensor when every part is one, else a host array.  -> the coded
         bytes (a view of out)."""
         if _is_tensor(parts) or not isinstance(parts, (list, tuple)):
@@ -72,7 +76,7 @@ class VarLenDNACoder:
             arr[k].ptr, arr[k].len, arr[k].on_device = ptr, n, dev
         total = sum(v[2] for v in views)
         if out is None:
-            if views and all(v[3] for v in views):
+            if views and all(v[3] and _is_tensor(v[0]) for v in views):
                 import torch
                 out = torch.empty(max(self.bound(total), 1), dtype=torch.uint8, device=views[0][0].device)
             else:
