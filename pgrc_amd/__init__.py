@@ -29,6 +29,7 @@ from .decode import (  # noqa: F401
 from .assemble import PgAssembler  # noqa: F401
 from .overlap import OverlapFinder  # noqa: F401
 from .varlen import VarLenDNACoder  # noqa: F401
+from .huf import HufCoder  # noqa: F401
 from .rlist import ReadsList  # noqa: F401
 from .verify import Verifier  # noqa: F401
 from . import archive  # noqa: F401

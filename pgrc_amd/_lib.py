@@ -462,6 +462,28 @@ READS_TEXT_EXPORTED_SYMBOLS = [p[0] for p in READS_TEXT_PROTOS]
 READS_TEXT_LIB_PATH = os.environ.get("PGRC_READS_TEXT_LIB") or os.path.join(_HERE, "libpgrc_reads_text.so")
 
 
+class HufTimes(C.Structure):     # pgrc_huf_times (include/pgrc_huf.h)
+    _fields_ = [("ms_upload", C.c_float), ("ms_tables", C.c_float), ("ms_emit", C.c_float), ("ms_compact", C.c_float),
+                ("ms_download", C.c_float), ("ms_call", C.c_float), ("bytes", C.c_uint64), ("coded_bytes", C.c_uint64),
+                ("chunks", C.c_uint32), ("huf_chunks", C.c_uint32), ("rle_chunks", C.c_uint32), ("raw_chunks", C.c_uint32),
+                ("was_decode", C.c_int32)]
+
+
+# include/pgrc_huf.h: exported by libpgrc_huf.so (the product's objects and huf.hip) alone
+HUF_ORDER_MAX, HUF_TABLE_LOG_MIN, HUF_TABLE_LOG_MAX = 17, 8, 11
+HUF_PROTOS = [
+    ("pgrc_huf_create", C.c_int, [C.c_int32, C.POINTER(_P)]),
+    ("pgrc_huf_destroy", None, [_P]),
+    ("pgrc_huf_last_error", C.c_char_p, [_P]),
+    ("pgrc_huf_bound", C.c_uint64, [C.c_uint64, C.c_uint32]),
+    ("pgrc_huf_encode", C.c_int, [_P, _P, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]),
+    ("pgrc_huf_decode", C.c_int, [_P, _P, C.c_uint64, C.c_int32, C.c_uint64, _P, C.c_int32]),
+    ("pgrc_huf_timing", C.c_int, [_P, C.POINTER(HufTimes)]),
+]
+HUF_EXPORTED_SYMBOLS = [p[0] for p in HUF_PROTOS]
+HUF_LIB_PATH = os.environ.get("PGRC_HUF_LIB") or os.path.join(_HERE, "libpgrc_huf.so")
+
+
 def reads_format(fmt) -> int:
     """"fastq" / "fasta" / "lines" or a PGRC_READS_* number -> the number"""
     return READS_FORMATS[fmt.lower()] if isinstance(fmt, str) else int(fmt)
@@ -525,5 +547,12 @@ if not os.path.exists(RLIST_ORD_LIB_PATH):
 olib = C.CDLL(RLIST_ORD_LIB_PATH)
 for _name, _res, _args in RLIST_ORD_PROTOS:
     _fn = getattr(olib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+if not os.path.exists(HUF_LIB_PATH):
+    raise ImportError(f"{HUF_LIB_PATH} is missing: `make -C pgrc_amd/csrc` builds it beside libpgrc_match.so")
+hlib = C.CDLL(HUF_LIB_PATH)
+for _name, _res, _args in HUF_PROTOS:
+    _fn = getattr(hlib, _name)
     _fn.restype = _res
     _fn.argtypes = _args
